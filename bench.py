@@ -1,7 +1,7 @@
 """
 bench.py -- DegNorm NMF-OA hot path on MI355X.
 
-    python bench.py [--config c2|c4] [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--config c2|c4] [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 With --gpus N > 1 and no WORLD_SIZE in the environment this process is only a LAUNCHER: before touching torch or the GPU it
 starts `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py ...`
@@ -32,6 +32,12 @@ Rank 0 prints ONE JSON line with the driver contract fields plus
   end_to_end    GeneNMFOA.fit(cov_dict, reads) on the full float64 coverage dict: pack + H2D, run, estimates, D2H,
   cpu_baseline  the oracle on this box's host cores (all cores, and one thread) on a bounded sample,
   also          (default run only) config 4 measured in the same process after config 2.
+
+--dump-outputs DIR writes what the last timed step of the headline configuration handed its caller (fetch_state) as float64 /
+float32 .npy files, rows in global gene order: rho.npy, x_adj.npy, x_weighted.npy (genes x samples), ran_baseline_selection.npy
+(genes x iterations, 0 / 1) and scale_factors.npy (samples).  At most DUMP_BYTES in all: a larger output is cut to a fixed, seeded
+sample of genes, whose ids are then written to gene_ids.npy.  The inputs are a pure function of the arguments, so two builds run
+with the same arguments can be compared file by file.
 """
 import argparse
 import hashlib
@@ -56,6 +62,8 @@ FP64_VECTOR_PEAK_TFLOPS = 78.6   # 256 CUs x 4 SIMDs x 16 fp64 FMA lanes/clk x 2
 FP64_ISSUE_CYCLES_1WAVE = 4.08
 ROUND = 'round4'
 REFERENCE_PY_GENES_PER_S_PER_THREAD = 0.18    # the reference itself (n_jobs = 1) on config-2-like genes, 5 iterations
+DUMP_BYTES = 64 * 10 ** 6                     # --dump-outputs: cap on the bytes written
+DUMP_SEED = 20261015                          # --dump-outputs: the gene sample when the cap bites
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -507,10 +515,63 @@ def end_to_end_sharded(ctx, cfg, p, n_genes, args, rate):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# --dump-outputs
+# ---------------------------------------------------------------------------------------------------------------------
+def step_outputs(eng, comm, world):
+    """
+    What a step handed its caller, copied right after the clock stops: per gene the DI scores, the adjusted and the weighted
+    read counts, the baseline-selection flags of every outer iteration, and the per-sample scale factors.  Collective when
+    world > 1: rank 0 receives every rank's rows and puts them in global gene order; the other ranks get None.
+    """
+    def rows(a, cols, dtype):
+        return np.zeros((0, cols), dtype=dtype) if a is None else np.array(a, dtype=dtype).reshape(-1, cols)
+    p, iters = eng.p, eng.degnorm_iter
+    mine = (np.asarray(eng.global_ids if eng.global_ids is not None else np.arange(eng.n_local), dtype=np.int64),
+            rows(eng.rho, p, np.float64), rows(eng.x_adj, p, np.float64), rows(eng.x_weighted, p, np.float64),
+            rows(eng.ran_baseline_selection, iters, np.float32))
+    parts = comm.gather_objects(mine) if world > 1 else [mine]
+    if comm.rank != 0:
+        return None
+    ids = np.concatenate([q[0] for q in parts])
+    order = np.argsort(ids, kind='stable')
+    names = ('rho', 'x_adj', 'x_weighted', 'ran_baseline_selection')
+    out = {n: np.concatenate([q[k + 1] for q in parts])[order] for k, n in enumerate(names)}
+    out['scale_factors'] = np.array(eng.scale_factors, dtype=np.float64)
+    out['gene_ids'] = ids[order]
+    return out
+
+
+def dump_outputs(outputs, path):
+    """Write `outputs` (step_outputs) as <path>/<name>.npy; above DUMP_BYTES only a seeded sample of the genes, listed in
+    gene_ids.npy.  Returns what was written."""
+    n = len(outputs['gene_ids'])
+    per_gene = sum(outputs[k].itemsize * outputs[k].shape[1] for k in ('rho', 'x_adj', 'x_weighted', 'ran_baseline_selection'))
+    budget = DUMP_BYTES - outputs['scale_factors'].nbytes - 6 * 128                   # 128: an .npy header
+    room = budget // per_gene
+    sampled = n > room
+    if sampled:
+        room = budget // (per_gene + 8)                                                 # gene_ids.npy (float64) comes along
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=int(room), replace=False))
+    os.makedirs(path, exist_ok=True)
+    written = {}
+    for name, arr in outputs.items():
+        if name == 'gene_ids':
+            if not sampled:
+                continue
+            arr = arr.astype(np.float64)
+        if sampled and name != 'scale_factors':
+            arr = arr[pick]
+        np.save(os.path.join(path, name + '.npy'), arr)
+        written[name] = list(arr.shape)
+    return {'dir': path, 'arrays': written, 'genes': n, 'sampled_genes': int(room) if sampled else None}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # one configuration on this rank
 # ---------------------------------------------------------------------------------------------------------------------
-def measure(config, args, ctx, steps, warmup, n_parity, n_cpu, n_single, want_e2e):
-    """Generate, upload, time `steps` steps; rank 0 returns the result object (other ranks None)."""
+def measure(config, args, ctx, steps, warmup, n_parity, n_cpu, n_single, want_e2e, dump_dir=''):
+    """Generate, upload, time `steps` steps; rank 0 returns the result object (other ranks None).  `dump_dir`: write the outputs
+    of the last timed step there (dump_outputs)."""
     import torch
     from degnorm_amd import synth
     from degnorm_amd.nmf_mpi import ShardedNMFOA
@@ -624,6 +685,7 @@ def measure(config, args, ctx, steps, warmup, n_parity, n_cpu, n_single, want_e2
         dist.all_gather_object(counts, (len(my_genes), int(wide.sum()), int((~wide & ~pair).sum()), int(pair.sum()), float(np.sum(lengths))))
     else:
         counts = [(len(my_genes), int(wide.sum()), int((~wide & ~pair).sum()), int(pair.sum()), float(np.sum(lengths)))]
+    outputs = step_outputs(eng, comm, world) if dump_dir else None     # before any post-clock check touches the engine
     if rank != 0:
         try:
             eng.dev.close()                                             # the handle (and its RCCL communicator) goes now, not at interpreter exit
@@ -757,6 +819,9 @@ def measure(config, args, ctx, steps, warmup, n_parity, n_cpu, n_single, want_e2
                         'counts 8 p L_g per gene and outer iteration = {0:.3e} B per launch'.format(alg_init),
             'note': 'rank-0 shard; HIP events on the library stream'}
     out['setup'] = {'synth_s': t_gen, 'upload_s': t_up}
+    if outputs is not None:
+        out['dumped_outputs'] = dump_outputs(outputs, dump_dir)
+        del outputs
     if args.dump_traces:                                                # per-gene counters of the last step (tools/partition_study.py)
         np.savez_compressed(args.dump_traces + '.' + config, lengths=lengths, gene_ids=np.asarray(my_genes),
                             traces=np.stack([tr[:, :8] for tr in eng.traces]), class_ms=np.asarray(eng.class_ms))
@@ -861,7 +926,8 @@ def run_rank(args):
 
     n_cpu = args.cpu_sample if args.cpu_sample >= 0 else (768 if args.config == 'c2' else 2048)
     n_single = args.cpu_single if args.cpu_single >= 0 else (64 if args.config == 'c2' else 512)
-    out = measure(args.config, args, ctx, args.steps, args.warmup, args.parity_genes, n_cpu, n_single, not args.no_end_to_end)
+    out = measure(args.config, args, ctx, args.steps, args.warmup, args.parity_genes, n_cpu, n_single, not args.no_end_to_end,
+                  dump_dir=args.dump_outputs)
     if rank == 0 and world == 1 and args.config == 'c2' and not args.no_also and args.genes <= 0:
         # BASELINE configs[3] in the same process, after the config-2 clock has stopped (its own generation, upload, warm-up, clock)
         sub = measure('c4', args, ctx, 3, 2, args.parity_genes, 2048 if n_cpu > 0 else 0, 512 if n_single > 0 else 0, False)
@@ -881,7 +947,7 @@ def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--config', default='c2', choices=['c2', 'c4'])
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=3)
+    ap.add_argument('--steps', type=int, default=3, help='timed steps of the headline configuration (>= 1)')
     ap.add_argument('--warmup', type=int, default=2)    # the first step after the first-ever one still carries ~18 ms of one-time host cost
     ap.add_argument('--genes', type=int, default=0, help='total genes (default: the configuration\'s: 20000 / 50000)')
     ap.add_argument('--iters', type=int, default=5, help='outer DegNorm iterations per step')
@@ -901,10 +967,17 @@ def parse(argv=None):
                     help='run the per-iteration all-reduce through torch.distributed on the library\'s device buffer (round 3) instead of '
                          'inside the library (dn_comm_*, the default with the nccl backend)')
     ap.add_argument('--dump-traces', default='', help='write the per-gene device counters of the last step to FILE.<config>.npz')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='write what the last timed step of the headline configuration computed to DIR/<name>.npy (at most 64 MB)')
     ap.add_argument('--backend', default='nccl', choices=['nccl', 'gloo'],
                     help='collective backend of the ranks: nccl = RCCL (the measured path); gloo only to rehearse N > 1 on ONE GPU '
                          '(every rank on device 0; the line is then marked "rehearsal")')
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
+    return args
 
 
 def main(argv=None):
