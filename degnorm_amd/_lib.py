@@ -14,6 +14,12 @@ TRACE_LEN = 48
 DN_OK = 0
 DN_E_INVALID, DN_E_HIP, DN_E_STATE, DN_E_UNSUPPORTED, DN_E_NO_DEVICE = -1, -2, -3, -4, -5
 
+# dn_nmf_f64 modes (include/degnorm_amd.h)
+NMF_RANK_ONE, NMF, NMF_RATIO = 0, 1, 2
+# per-matrix / per-gene status of the float64 path (trace[6] of the baseline kernels)
+STATUS_NAMES = {0: 'ok', -1: 'ArpackError (all-zero matrix)', -2: 'empty minimum (no |K| >= 1e-5)',
+                -3: 'ValueError (fewer than 2 rows or columns)', -4: 'ArpackNoConvergence (solver step cap)'}
+
 EXIT_NAMES = ('low_cov', 'zero_sample', 'median', 'no_loop', 'refined', 'refine_fallback', 'not_found_fallback')
 
 _lib = None
@@ -107,6 +113,10 @@ def load(build_if_missing=False):
     lib.dn_comm_allreduce.argtypes = [vp, P(dbl), i32]
     lib.dn_init_allreduce.argtypes = [vp, P(dbl)]
     lib.dn_outer_allreduce.argtypes = [vp, P(dbl)]
+    lib.dn_nmf_f64.argtypes = [vp, i64, i32, P(vp), P(i64), i32, i32, P(dbl), P(dbl), P(dbl), P(i32)]
+    lib.dn_baseline_selection_f64.argtypes = [vp, i64, i32, P(vp), P(i64), P(Params), P(i64), P(dbl), P(i32), P(i32), P(dbl)]
+    lib.dn_last_f64_ms.argtypes = [vp]
+    lib.dn_last_f64_ms.restype = dbl
     _lib = lib
     return lib
 
@@ -391,6 +401,75 @@ class Device:
             out.append(flat[o:o + cnt].reshape(self.p, int(L)))
             o += cnt
         return out
+
+    # -- the float64-input path (dn_nmf_f64 / dn_baseline_selection_f64): buffers of its own, no resident state ------------
+    @staticmethod
+    def _f64_batch(mats):
+        keep = [np.ascontiguousarray(m, dtype=np.float64) for m in mats]
+        if not keep:
+            raise ValueError('no matrices')
+        p = int(keep[0].shape[0]) if keep[0].ndim == 2 else 0
+        for m in keep:
+            if m.ndim != 2:
+                raise ValueError('Not all coverage matrices are 2-d arrays!')
+            if m.shape[0] != p:
+                raise ValueError('matrices disagree on the number of rows')
+        ptrs = (ctypes.c_void_p * len(keep))(*[m.ctypes.data for m in keep])
+        lengths = np.array([m.shape[1] for m in keep], dtype=np.int64)
+        return keep, ptrs, lengths, p
+
+    def nmf_f64(self, mats, mode, nmf_iter=100, want_est=False):
+        """
+        Batched rank-one / nmf() / ratio_svd on float64 matrices (p x n_k each, one launch).  mode: NMF_RANK_ONE, NMF or
+        NMF_RATIO.  Returns (K list of (p,), E list of (n_k,), est list of (p x n_k) or None, status int32 array).
+        """
+        keep, ptrs, lengths, p = self._f64_batch(mats)
+        n = len(keep)
+        K = np.zeros(n * p)
+        E = np.zeros(int(lengths.sum()))
+        est = np.zeros(p * int(lengths.sum())) if want_est else None
+        status = np.zeros(n, dtype=np.int32)
+        _check(self.lib.dn_nmf_f64(self.h, n, p, ptrs, _p(lengths, ctypes.c_int64), int(mode), int(nmf_iter),
+                                   _p(K, ctypes.c_double), _p(E, ctypes.c_double),
+                                   _p(est, ctypes.c_double) if want_est else None, _p(status, ctypes.c_int32)))
+        offs = np.concatenate([[0], np.cumsum(lengths)])
+        Ks = [K[k * p:(k + 1) * p] for k in range(n)]
+        Es = [E[offs[k]:offs[k + 1]] for k in range(n)]
+        ests = [est[p * offs[k]:p * offs[k + 1]].reshape(p, int(lengths[k])) for k in range(n)] if want_est else None
+        return Ks, Es, ests, status
+
+    def baseline_selection_f64(self, mats, nmf_iter=100, bins=20, min_high_coverage=50, downsample_rate=1,
+                               skip_baseline_selection=False, ds_start=None, want_est=False):
+        """
+        baseline_selection (nmf.py:189-372) on float64 coverage as given (no scale factors).  Returns (rho n x p unclipped,
+        flags bool n, trace n x TRACE_LEN int32, estimates list of (p x L_g) or None); trace[:, 6] is the per-gene status.
+        """
+        keep, ptrs, lengths, p = self._f64_batch(mats)
+        n = len(keep)
+        prm = Params(int(nmf_iter), int(bins), int(min_high_coverage), int(downsample_rate),
+                     int(bool(skip_baseline_selection)), int(bool(want_est)))
+        dsp = None
+        if ds_start is not None:
+            ds_arr = np.ascontiguousarray(ds_start, dtype=np.int64)
+            if ds_arr.shape != (n,):
+                raise ValueError('ds_start must have one entry per gene')
+            dsp = _p(ds_arr, ctypes.c_int64)
+        rho = np.zeros((n, p))
+        flags = np.zeros(n, dtype=np.int32)
+        trace = np.zeros((n, TRACE_LEN), dtype=np.int32)
+        est = np.zeros(p * int(lengths.sum())) if want_est else None
+        _check(self.lib.dn_baseline_selection_f64(self.h, n, p, ptrs, _p(lengths, ctypes.c_int64), ctypes.byref(prm), dsp,
+                                                  _p(rho, ctypes.c_double), _p(flags, ctypes.c_int32), _p(trace, ctypes.c_int32),
+                                                  _p(est, ctypes.c_double) if want_est else None))
+        ests = None
+        if want_est:
+            offs = np.concatenate([[0], np.cumsum(lengths)])
+            ests = [est[p * offs[k]:p * offs[k + 1]].reshape(p, int(lengths[k])) for k in range(n)]
+        return rho, flags.astype(bool), trace, ests
+
+    def last_f64_ms(self):
+        """Device time of the most recent float64-path kernel (dn_nmf_f64 / dn_baseline_selection_f64)."""
+        return float(self.lib.dn_last_f64_ms(self.h))
 
     # -- measurement -------------------------------------------------------------------------------
     def last_kernel_ms(self):

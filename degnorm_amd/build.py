@@ -3,7 +3,8 @@ In-tree build of libdegnorm_amd.so (HIP kernels + C ABI) for gfx950 with hipcc.
 
     python -m degnorm_amd.build [--force]
 
-One translation unit per sample count p (dn_inst.hip -DDN_P=p) plus the C-ABI unit; objects are compiled
+One translation unit per sample count p (dn_inst.hip -DDN_P=p), the run-time-p family (dn_generic.hip, compiled three
+times: 256- and 64-thread builds on float32 counts, a 256-thread build on float64 input) plus the C-ABI unit; objects are compiled
 in parallel and linked into degnorm_amd/libdegnorm_amd.so.  hipcc cross-compiles without a GPU.
 """
 import os
@@ -107,6 +108,10 @@ def build_library(force=False, verbose=False):
         objs.append(o_gen)
         if force or _newer(o_gen, [gen] + hdr):
             jobs.append([hipcc] + FLAGS + EXTRA + ['-DDN_GEN_NT={0}'.format(gnt), '-c', gen, '-o', o_gen])
+    o_f64 = os.path.join(OBJ, 'dn_generic_f64.o')        # the same source on float64 input (dn_nmf_f64, dn_baseline_selection_f64)
+    objs.append(o_f64)
+    if force or _newer(o_f64, [gen] + hdr):
+        jobs.append([hipcc] + FLAGS + EXTRA + ['-DDN_GEN_NT=256', '-DDN_GEN_F64=1', '-c', gen, '-o', o_f64])
     asm = os.path.join(CSRC, 'dn_assemble.hip')
     o_asm = os.path.join(OBJ, 'dn_assemble.o')
     objs.append(o_asm)

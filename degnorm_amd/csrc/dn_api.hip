@@ -413,6 +413,7 @@ struct dn_handle_s {
     float last_span_ms = 0.f;     // first launch to last end of the class kernels of the most recent dn_baseline_iteration
     float last_init_ms = 0.f;     // device time of the most recent dn_ratio_svd_sums kernel
     float last_rowmax_ms = 0.f;   // device time of k_row_max at the most recent upload
+    float last_f64_ms = 0.f;      // device time of the most recent dn_nmf_f64 / dn_baseline_selection_f64 kernels
     char init_name[64] = {0};
     hipEvent_t ev_i0 = nullptr, ev_i1 = nullptr;
     // the collective inside the library (dn_comm_*): one RCCL communicator per handle, all-reduces on the handle's stream
@@ -502,6 +503,57 @@ static void free_device(dn_handle h)
     h->n_iter = 0;
     h->have_estimate_state = false;
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// The float64-input path (dn_generic.hip, DN_GEN_F64 build): per-call device buffers, freed on every return path; the
+// handle contributes its device, stream, CU count and solver step cap only.
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+struct F64Buffers {
+    std::vector<void *> ptrs;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ~F64Buffers()
+    {
+        for (void *q : ptrs) (void) hipFree(q);
+        if (e0) (void) hipEventDestroy(e0);
+        if (e1) (void) hipEventDestroy(e1);
+    }
+    template <class T> hipError_t alloc(T **out, size_t count)
+    {
+        *out = nullptr;
+        const hipError_t e = hipMalloc((void **) out, sizeof(T) * std::max<size_t>(count, 1));
+        if (e == hipSuccess) ptrs.push_back((void *) *out);
+        return e;
+    }
+};
+
+// Persistent workgroups for a float64-path kernel: as many as fit on the device (occupancy x CUs), at most one per item,
+// fewer when their scratch slots would take more than a third of free HBM.  0 and g_err set when one slot alone is too big.
+int f64_grid(dn_handle h, int which, int64_t items, int64_t slot_bytes)
+{
+    int per_cu = dn::blocks_per_cu_f64(which);
+    if (per_cu < 1) per_cu = 1;
+    int64_t grid = std::min<int64_t>(items, (int64_t) per_cu * h->n_cus);
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return fail(0, "hipMemGetInfo failed");
+    const int64_t budget = (int64_t) (free_b / 3);
+    if (slot_bytes > budget) return fail(0, "a matrix is too wide for the device scratch");
+    grid = std::max<int64_t>(1, std::min<int64_t>(grid, budget / std::max<int64_t>(slot_bytes, 1)));
+    return (int) grid;
+}
+
+int check_f64_batch(dn_handle h, int64_t n, int32_t p, const double *const *x, const int64_t *lengths, const char *what)
+{
+    if (!h) return fail(DN_E_STATE, std::string(what) + ": null handle");
+    if (p < 2 || p > dn::P_MAX) return fail(DN_E_UNSUPPORTED, std::string(what) + ": p = " + std::to_string(p) + " outside [2, 64]");
+    if (n < 1 || n > INT32_MAX || !x || !lengths) return fail(DN_E_INVALID, std::string(what) + ": bad batch");
+    for (int64_t m = 0; m < n; m++) {
+        if (!x[m]) return fail(DN_E_INVALID, std::string(what) + ": null matrix");
+        if (lengths[m] < 1 || lengths[m] > (1 << 26)) return fail(DN_E_INVALID, std::string(what) + ": matrix length out of [1, 2^26]");
+    }
+    return DN_OK;
+}
+}  // namespace
 
 extern "C" {
 
@@ -1500,6 +1552,199 @@ int dn_fetch_estimates_subset(dn_handle h, int64_t n_sel, const int64_t *gene_id
     if (le != hipSuccess) return fail(DN_E_HIP, std::string("dn_fetch_estimates_subset: ") + hipGetErrorString(le));
     return DN_OK;
 }
+
+
+int dn_nmf_f64(dn_handle h, int64_t n, int32_t p, const double *const *x, const int64_t *lengths, int32_t mode,
+               int32_t nmf_iter, double *K, double *E, double *est, int32_t *status)
+{
+    const int rc = check_f64_batch(h, n, p, x, lengths, "dn_nmf_f64");
+    if (rc != DN_OK) return rc;
+    if (!K || !E || !status) return fail(DN_E_INVALID, "dn_nmf_f64: null output");
+    if (mode != DN_NMF_RANK_ONE && mode != DN_NMF && mode != DN_NMF_RATIO) return fail(DN_E_INVALID, "dn_nmf_f64: unknown mode");
+    if (mode == DN_NMF && nmf_iter < 0) return fail(DN_E_INVALID, "dn_nmf_f64: nmf_iter must be >= 0");
+    HIP_TRY(hipSetDevice(h->device));
+    std::vector<int64_t> xoff(n), eoff(n + 1, 0);
+    std::vector<int32_t> ncol(n);
+    int64_t maxn = 0;
+    for (int64_t m = 0; m < n; m++) {
+        ncol[m] = (int32_t) lengths[m];
+        eoff[m + 1] = eoff[m] + lengths[m];
+        xoff[m] = (int64_t) p * eoff[m];
+        maxn = std::max<int64_t>(maxn, lengths[m]);
+    }
+    const int64_t total = (int64_t) p * eoff[n];
+    std::vector<double> packed((size_t) total);
+    for (int64_t m = 0; m < n; m++) std::memcpy(packed.data() + xoff[m], x[m], sizeof(double) * (size_t) p * (size_t) lengths[m]);
+    std::vector<int32_t> order(n);                                    // widest first
+    std::iota(order.begin(), order.end(), 0);
+    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return ncol[a] > ncol[b]; });
+    // slot: x + lambda [p][n], residual profile, s_start, A^T u [n] -- fp64, 256-byte aligned
+    const int64_t slot_bytes = ((int64_t) sizeof(double) * (p + 3) * maxn + 255) & ~(int64_t) 255;
+    const int grid = f64_grid(h, 1, n, slot_bytes);
+    if (grid < 1) return fail(DN_E_INVALID, "dn_nmf_f64: " + g_err);
+
+    F64Buffers B;
+    dn::NmfArgsF64 a;
+    std::memset(&a, 0, sizeof(a));
+    double *d_x = nullptr, *d_K = nullptr, *d_E = nullptr, *d_est = nullptr;
+    int64_t *d_xoff = nullptr, *d_eoff = nullptr;
+    int32_t *d_ncol = nullptr, *d_order = nullptr, *d_counter = nullptr, *d_status = nullptr;
+    char *d_ws = nullptr;
+    HIP_TRY(B.alloc(&d_x, (size_t) total));
+    HIP_TRY(B.alloc(&d_xoff, (size_t) n));
+    HIP_TRY(B.alloc(&d_eoff, (size_t) n));
+    HIP_TRY(B.alloc(&d_ncol, (size_t) n));
+    HIP_TRY(B.alloc(&d_order, (size_t) n));
+    HIP_TRY(B.alloc(&d_counter, 4));
+    HIP_TRY(B.alloc(&d_status, (size_t) n));
+    HIP_TRY(B.alloc(&d_K, (size_t) n * p));
+    HIP_TRY(B.alloc(&d_E, (size_t) eoff[n]));
+    if (est) HIP_TRY(B.alloc(&d_est, (size_t) total));
+    HIP_TRY(B.alloc(&d_ws, (size_t) slot_bytes * (size_t) grid));
+    HIP_TRY(hipEventCreate(&B.e0));
+    HIP_TRY(hipEventCreate(&B.e1));
+    HIP_TRY(hipMemcpyAsync(d_x, packed.data(), sizeof(double) * (size_t) total, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(d_xoff, xoff.data(), sizeof(int64_t) * (size_t) n, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(d_eoff, eoff.data(), sizeof(int64_t) * (size_t) n, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(d_ncol, ncol.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(d_order, order.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemsetAsync(d_counter, 0, sizeof(int32_t) * 4, h->stream));
+    a.x = d_x; a.xoff = d_xoff; a.ncol = d_ncol; a.eoff = d_eoff; a.order = d_order; a.counter = d_counter;
+    a.K = d_K; a.E = d_E; a.est = d_est; a.status = d_status; a.ws = d_ws; a.slot_bytes = slot_bytes;
+    a.n = (int32_t) n; a.p = p; a.T = mode == DN_NMF ? nmf_iter : 0; a.ratio = mode == DN_NMF_RATIO ? 1 : 0;
+    a.max_steps = h->max_steps;
+    HIP_TRY(hipEventRecord(B.e0, h->stream));
+    const int lrc = dn::launch_nmf_f64(a, grid, h->stream);
+    if (lrc != 0) return fail(DN_E_HIP, std::string("k_nmf_f64 launch: ") + hipGetErrorString((hipError_t) lrc));
+    HIP_TRY(hipEventRecord(B.e1, h->stream));
+    HIP_TRY(hipMemcpyAsync(K, d_K, sizeof(double) * (size_t) n * p, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(E, d_E, sizeof(double) * (size_t) eoff[n], hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(status, d_status, sizeof(int32_t) * (size_t) n, hipMemcpyDeviceToHost, h->stream));
+    if (est) HIP_TRY(hipMemcpyAsync(est, d_est, sizeof(double) * (size_t) total, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipEventElapsedTime(&h->last_f64_ms, B.e0, B.e1));
+    return DN_OK;
+}
+
+int dn_baseline_selection_f64(dn_handle h, int64_t n, int32_t p, const double *const *F, const int64_t *lengths,
+                              const dn_params *prm, const int64_t *ds_start, double *rho, int32_t *flags,
+                              int32_t *trace, double *est)
+{
+    const int rc = check_f64_batch(h, n, p, F, lengths, "dn_baseline_selection_f64");
+    if (rc != DN_OK) return rc;
+    if (!prm || !rho || !flags) return fail(DN_E_INVALID, "dn_baseline_selection_f64: null argument");
+    if (prm->nmf_iter < 1) return fail(DN_E_INVALID, "nmf_iter must be >= 1");
+    if (prm->bins < 1 || prm->bins > dn::MAX_BINS) return fail(DN_E_INVALID, "bins must be in [1, 64]");
+    if (prm->min_high_coverage < 2) return fail(DN_E_INVALID, "min_high_coverage must be >= 2 (nmf.py:34)");
+    if (prm->downsample_rate < 1) return fail(DN_E_INVALID, "downsample_rate must be >= 1");
+    if (prm->downsample_rate > 1) {
+        if (!ds_start) return fail(DN_E_INVALID, "downsample_rate > 1 needs per-gene start offsets");
+        for (int64_t g = 0; g < n; g++) {
+            if (lengths[g] <= prm->downsample_rate) return fail(DN_E_INVALID, "downsample_rate is too large; take-every size > at least one gene.");
+            if (ds_start[g] < 0 || ds_start[g] >= prm->downsample_rate) return fail(DN_E_INVALID, "ds_start out of [0, rate)");
+        }
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    std::vector<int64_t> goff(n + 1, 0), svoff(n + 1, 0);
+    std::vector<int32_t> glen(n);
+    int64_t maxl = 0;
+    for (int64_t g = 0; g < n; g++) {
+        glen[g] = (int32_t) lengths[g];
+        goff[g + 1] = goff[g] + (int64_t) p * lengths[g];
+        svoff[g + 1] = svoff[g] + lengths[g];
+        maxl = std::max<int64_t>(maxl, lengths[g]);
+    }
+    const int64_t total = goff[n];
+    std::vector<double> packed((size_t) total);
+    for (int64_t g = 0; g < n; g++) std::memcpy(packed.data() + goff[g], F[g], sizeof(double) * (size_t) p * (size_t) lengths[g]);
+    std::vector<int32_t> order(n);                                    // longest first
+    std::iota(order.begin(), order.end(), 0);
+    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return glen[a] > glen[b]; });
+    std::vector<int32_t> tg, tc;                                      // estimate tiles: (gene, first column) per 256 columns
+    if (est)
+        for (int64_t g = 0; g < n; g++)
+            for (int32_t c = 0; c < glen[g]; c += 256) { tg.push_back((int32_t) g); tc.push_back(c); }
+    // slot: Fs, Fb (fp64, p x S) + x + lambda (fp64 [p][S]) + s_start, residual profile, A^T u (fp64 [S])
+    const int32_t S = (int32_t) ((maxl + 63) & ~(int64_t) 63);
+    const int64_t slot_bytes = (int64_t) S * ((int64_t) p * 3 * sizeof(double) + 3 * sizeof(double));
+    const int grid = f64_grid(h, 0, n, slot_bytes);
+    if (grid < 1) return fail(DN_E_INVALID, "dn_baseline_selection_f64: " + g_err);
+
+    F64Buffers B;
+    double *d_cov = nullptr, *d_rowmax = nullptr, *d_rho = nullptr, *d_kfin = nullptr, *d_svec = nullptr, *d_est = nullptr;
+    int64_t *d_goff = nullptr, *d_ds = nullptr, *d_svoff = nullptr;
+    int32_t *d_glen = nullptr, *d_order = nullptr, *d_counter = nullptr, *d_flags = nullptr, *d_trace = nullptr, *d_emode = nullptr;
+    int32_t *d_tg = nullptr, *d_tc = nullptr;
+    char *d_ws = nullptr;
+    HIP_TRY(B.alloc(&d_cov, (size_t) total));
+    HIP_TRY(B.alloc(&d_goff, (size_t) n + 1));
+    HIP_TRY(B.alloc(&d_glen, (size_t) n));
+    HIP_TRY(B.alloc(&d_order, (size_t) n));
+    HIP_TRY(B.alloc(&d_counter, 4));
+    HIP_TRY(B.alloc(&d_rowmax, (size_t) n * p));
+    HIP_TRY(B.alloc(&d_rho, (size_t) n * p));
+    HIP_TRY(B.alloc(&d_flags, (size_t) n));
+    HIP_TRY(B.alloc(&d_trace, (size_t) n * dn::TRACE_LEN));
+    HIP_TRY(B.alloc(&d_kfin, (size_t) n * p));
+    HIP_TRY(B.alloc(&d_emode, (size_t) n));
+    HIP_TRY(B.alloc(&d_ws, (size_t) slot_bytes * (size_t) grid));
+    if (prm->downsample_rate > 1) HIP_TRY(B.alloc(&d_ds, (size_t) n));
+    if (est) {
+        HIP_TRY(B.alloc(&d_svoff, (size_t) n + 1));
+        HIP_TRY(B.alloc(&d_svec, (size_t) svoff[n]));
+        HIP_TRY(B.alloc(&d_est, (size_t) total));
+        HIP_TRY(B.alloc(&d_tg, tg.size()));
+        HIP_TRY(B.alloc(&d_tc, tc.size()));
+    }
+    HIP_TRY(hipEventCreate(&B.e0));
+    HIP_TRY(hipEventCreate(&B.e1));
+    HIP_TRY(hipMemcpyAsync(d_cov, packed.data(), sizeof(double) * (size_t) total, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(d_goff, goff.data(), sizeof(int64_t) * (size_t) (n + 1), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(d_glen, glen.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(d_order, order.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemsetAsync(d_counter, 0, sizeof(int32_t) * 4, h->stream));
+    HIP_TRY(hipMemsetAsync(d_trace, 0, sizeof(int32_t) * (size_t) n * dn::TRACE_LEN, h->stream));
+    if (d_ds) HIP_TRY(hipMemcpyAsync(d_ds, ds_start, sizeof(int64_t) * (size_t) n, hipMemcpyHostToDevice, h->stream));
+    if (est) {
+        HIP_TRY(hipMemcpyAsync(d_svoff, svoff.data(), sizeof(int64_t) * (size_t) (n + 1), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(d_tg, tg.data(), sizeof(int32_t) * tg.size(), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(d_tc, tc.data(), sizeof(int32_t) * tc.size(), hipMemcpyHostToDevice, h->stream));
+    }
+    HIP_TRY(hipEventRecord(B.e0, h->stream));
+    int lrc = dn::launch_row_max_f64(d_cov, d_goff, d_glen, d_rowmax, (int) n, p,
+                                     (int) std::min<int64_t>(n, (int64_t) h->n_cus * 8), h->stream);
+    if (lrc != 0) return fail(DN_E_HIP, std::string("k_row_max_f64 launch: ") + hipGetErrorString((hipError_t) lrc));
+
+    dn::IterArgsF64 a;
+    std::memset(&a, 0, sizeof(a));
+    a.cov = d_cov; a.goff = d_goff; a.glen = d_glen; a.order = d_order; a.counter = d_counter; a.ds_start = d_ds;
+    a.rowmax = d_rowmax; a.x16 = nullptr; a.ws = d_ws; a.rho = d_rho; a.flags = d_flags; a.trace = d_trace; a.kfin = d_kfin;
+    a.emode = d_emode; a.svec = d_svec; a.svoff = d_svoff; a.slot_bytes = slot_bytes; a.n_genes = (int32_t) n; a.S = S;
+    a.lds_cols = 0; a.T = prm->nmf_iter; a.bins = prm->bins; a.min_hc = prm->min_high_coverage; a.rate = prm->downsample_rate;
+    a.skip = prm->skip_baseline_selection ? 1 : 0; a.want_est = est ? 1 : 0; a.p = p; a.max_steps = h->max_steps;
+    for (int i = 0; i < dn::P_MAX; i++) { a.scale[i] = 1.0; a.inv_scale[i] = 1.0; }      // F as given
+    lrc = dn::launch_baseline_f64(a, grid, h->stream);
+    if (lrc != 0) return fail(DN_E_HIP, std::string("k_baseline_gen (float64) launch: ") + hipGetErrorString((hipError_t) lrc));
+    if (est) {
+        dn::EstArgsF64 e;
+        std::memset(&e, 0, sizeof(e));
+        e.cov = d_cov; e.goff = d_goff; e.glen = d_glen; e.kfin = d_kfin; e.emode = d_emode; e.svec = d_svec; e.svoff = d_svoff;
+        e.out = d_est; e.ooff = nullptr; e.n_genes = (int32_t) n; e.p = p;
+        for (int i = 0; i < dn::P_MAX; i++) e.scale[i] = 1.0;
+        lrc = dn::launch_est_f64(e, d_tg, d_tc, (int) tg.size(), h->stream);
+        if (lrc != 0) return fail(DN_E_HIP, std::string("k_estimates_gen (float64) launch: ") + hipGetErrorString((hipError_t) lrc));
+    }
+    HIP_TRY(hipEventRecord(B.e1, h->stream));
+    HIP_TRY(hipMemcpyAsync(rho, d_rho, sizeof(double) * (size_t) n * p, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(flags, d_flags, sizeof(int32_t) * (size_t) n, hipMemcpyDeviceToHost, h->stream));
+    if (trace) HIP_TRY(hipMemcpyAsync(trace, d_trace, sizeof(int32_t) * (size_t) n * dn::TRACE_LEN, hipMemcpyDeviceToHost, h->stream));
+    if (est) HIP_TRY(hipMemcpyAsync(est, d_est, sizeof(double) * (size_t) total, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipEventElapsedTime(&h->last_f64_ms, B.e0, B.e1));
+    return DN_OK;
+}
+
+double dn_last_f64_ms(dn_handle h) { return h ? (double) h->last_f64_ms : 0.0; }
 
 double dn_last_kernel_ms(dn_handle h) { return h ? (double) h->last_ms : 0.0; }
 double dn_last_init_ms(dn_handle h) { return h ? (double) h->last_init_ms : 0.0; }

@@ -15,15 +15,30 @@
 // one-wavefront-per-gene family (kernel_set_rows) that serves data sets in which no gene can keep more than NSM_MAX
 // active columns: there only nmf_rows runs, a single wave does all the work of a gene, and 64-thread workgroups let a
 // CU keep 16 genes in flight instead of 2.
+//
+// -DDN_GEN_F64=1 (with DN_GEN_NT=256) is a third compilation, namespace gen_f64: the float64-input path behind dn_nmf_f64 and
+// dn_baseline_selection_f64.  The coverage element type cov_t becomes double (float in the two builds above), the row maxima
+// come from k_row_max_f64 in float64, and the batched bare-factorisation kernel k_nmf_f64 exists only here.  The initial
+// ratio-SVD pass (InitArgs, raw counts) is not part of it.
 #include <cstdio>
 #ifndef DN_GEN_NT
 #define DN_GEN_NT 256
+#endif
+#ifndef DN_GEN_F64
+#define DN_GEN_F64 0
 #endif
 #define DN_P 8          // sizes the shared reduction scratch only (Smem<8, NT>)
 #define DN_NT DN_GEN_NT
 #include "dn_kernels.hpp"
 
-#if DN_GEN_NT == 256
+#if DN_GEN_F64
+#if DN_GEN_NT != 256
+#error "the float64-input build (DN_GEN_F64) is a 256-thread build"
+#endif
+#define DN_GEN_NS gen_f64
+#undef DN_GEN_MINW
+#define DN_GEN_MINW 2
+#elif DN_GEN_NT == 256
 #define DN_GEN_NS gen
 #undef DN_GEN_MINW
 #define DN_GEN_MINW 2           // two workgroups per CU
@@ -39,6 +54,16 @@
 
 namespace dn {
 namespace DN_GEN_NS {
+
+#if DN_GEN_F64
+using cov_t = double;           // coverage as given (float64), the row maxima in float64
+using GenIterArgs = IterArgsF64;
+using GenEstArgs = EstArgsF64;
+#else
+using cov_t = float;            // float32 storage of integer counts (dn_upload_ragged)
+using GenIterArgs = IterArgs;
+using GenEstArgs = EstArgs;
+#endif
 
 constexpr int GP = P_MAX;       // 64
 constexpr int NT = DN_GEN_NT;
@@ -110,7 +135,7 @@ __device__ __forceinline__ int top_singular(const double *A, double *sj, int n, 
 }
 
 // One nmf() call (nmf.py:78-107) on Fb (raw counts of the active columns); results in g_st.
-__device__ __attribute__((noinline)) void nmf_gen(const float *Fb, double *A, double *rs, double *sv, double *sj,
+__device__ __attribute__((noinline)) void nmf_gen(const cov_t *Fb, double *A, double *rs, double *sv, double *sj,
                                                    int n, int S, int T, int first_i, int p)
 {
     const int tid = threadIdx.x;
@@ -210,7 +235,7 @@ constexpr int ROWS_ZSLOT = 255;               // last double of g_rows_tot, kept
 // SAFE: the repeat of a call whose result shows samples decoupled from the top block (dn_kernels.hpp, warm_start_unsafe): every solve
 // block by block.  A separate instantiation -- inside the hot one the rare path cost 32 % (17.6 against 13.3 ms per launch on config 4)
 template <int NSM, bool SAFE = false>
-__device__ __attribute__((noinline)) void nmf_rows(const float *Fb, double *rs, double *sv, double *sj,
+__device__ __attribute__((noinline)) void nmf_rows(const cov_t *Fb, double *rs, double *sv, double *sj,
                                                    int n, int S, int T, int first_i, int p)
 {
     constexpr int NGS = NSM * (NSM + 1) / 2;  // packed Gram entries: 10, 36, 78
@@ -228,7 +253,7 @@ __device__ __attribute__((noinline)) void nmf_rows(const float *Fb, double *rs, 
         double f[NSM], a[NSM], v[NSM];
 #pragma unroll
         for (int j = 0; j < NSM; j++) {
-            const float xv = (live && j < n) ? Fb[(size_t) lane * S + j] : 0.0f;
+            const cov_t xv = (live && j < n) ? Fb[(size_t) lane * S + j] : (cov_t) 0;
             f[j] = (double) xv * inv_s;
             a[j] = f[j];                                                // lmbda = 0 (nmf.py:90)
             v[j] = 0.0;
@@ -340,14 +365,14 @@ __device__ __forceinline__ int fix_k_lds(int p)
     return ST_OK;
 }
 
-__global__ __launch_bounds__(NT, DN_GEN_MINW) void k_baseline_gen(IterArgs A)
+__global__ __launch_bounds__(NT, DN_GEN_MINW) void k_baseline_gen(GenIterArgs A)
 {
     constexpr int W = NT / 64;
     const int tid = threadIdx.x, lane = lane_id(), w = wave_id();
     const int p = A.p, S = A.S;
     char *slot = A.ws + (size_t) blockIdx.x * A.slot_bytes;
-    float *Fs = reinterpret_cast<float *>(slot);
-    float *Fb = Fs + (size_t) p * S;
+    cov_t *Fs = reinterpret_cast<cov_t *>(slot);
+    cov_t *Fb = Fs + (size_t) p * S;
     double *Ast = reinterpret_cast<double *>(Fb + (size_t) p * S);
     double *sv = Ast + (size_t) p * S;
     double *rs = sv + S;
@@ -364,7 +389,7 @@ __global__ __launch_bounds__(NT, DN_GEN_MINW) void k_baseline_gen(IterArgs A)
         if (q >= A.n_genes) break;
         const int g = A.order[q];
         const int L = A.glen[g];
-        const float *x = A.cov + A.goff[g];
+        const cov_t *x = A.cov + A.goff[g];
         int n0 = 0, n_calls = 0, n_drops = 0, exit_code = EXIT_LOW_COV, loop_reason = LOOP_NOT_ENTERED;
         int status = ST_OK, flag = 0, emode = EM_INPUT;
         long long sum_cols = 0;
@@ -377,7 +402,7 @@ __global__ __launch_bounds__(NT, DN_GEN_MINW) void k_baseline_gen(IterArgs A)
         // (division by a positive scalar is monotone): the threshold needs only the row maxima of the raw counts (k_row_max).
         double gm = 0.0;
         {
-            const float *rmx = A.rowmax + (size_t) g * p;
+            const cov_t *rmx = A.rowmax + (size_t) g * p;
             for (int i = 0; i < p; i++) { const double f = (double) rmx[i] / g_st.scale[i]; gm = f > gm ? f : gm; }
         }
         const double thr = 0.1 * gm;
@@ -402,7 +427,7 @@ __global__ __launch_bounds__(NT, DN_GEN_MINW) void k_baseline_gen(IterArgs A)
                 const unsigned long long mask = __ballot(hi);
                 if (pass == 1 && hi) {
                     const int pos = base + run + __popcll(mask & ((1ull << lane) - 1ull));
-                    for (int i = 0; i < p; i++) { const float v = x[(size_t) i * L + j]; Fs[(size_t) i * S + pos] = v; Fb[(size_t) i * S + pos] = v; }
+                    for (int i = 0; i < p; i++) { const cov_t v = x[(size_t) i * L + j]; Fs[(size_t) i * S + pos] = v; Fb[(size_t) i * S + pos] = v; }
                 }
                 run += __popcll(mask);
             }
@@ -628,7 +653,7 @@ __global__ __launch_bounds__(NT, DN_GEN_MINW) void k_baseline_gen(IterArgs A)
     }
 }
 
-#if DN_GEN_NT == 256
+#if DN_GEN_NT == 256 && !DN_GEN_F64
 // ratio_svd + row sums (nmf.py:109-121, :524-525) for run-time p; uses the same scratch slots.
 // y = A (A^T u) on the RAW fp32 coverage (row stride L) in ONE pass: every thread forms s = u . a_j for its columns and
 // adds s a_j to per-thread partials of all p rows (registers), which are then block-reduced in tiles of 8.  The
@@ -1385,16 +1410,16 @@ __global__ __launch_bounds__(NT) void k_ratio_svd_gen(InitArgs A)
     }
 }
 
-#endif  // DN_GEN_NT == 256
+#endif  // DN_GEN_NT == 256 && !DN_GEN_F64
 
-__global__ __launch_bounds__(256) void k_estimates_gen(EstArgs A, const int32_t *__restrict__ tile_gene,
+__global__ __launch_bounds__(256) void k_estimates_gen(GenEstArgs A, const int32_t *__restrict__ tile_gene,
                                                        const int32_t *__restrict__ tile_col0)
 {
     const int g = tile_gene[blockIdx.x];
     const int j = tile_col0[blockIdx.x] + threadIdx.x;
     const int L = A.glen[g], p = A.p;
     if (j >= L) return;
-    const float *x = A.cov + A.goff[g];
+    const cov_t *x = A.cov + A.goff[g];
     double *o = A.out + (A.ooff ? A.ooff[g] : A.goff[g]);
     const int em = A.emode[g];
     const double *K = A.kfin + (size_t) g * p;
@@ -1419,6 +1444,130 @@ __global__ __launch_bounds__(256) void k_estimates_gen(EstArgs A, const int32_t 
         }
     }
 }
+
+#if DN_GEN_F64
+// ---------------------------------------------------------------------------------------------------
+// The float64-input path.
+// ---------------------------------------------------------------------------------------------------
+// Row maxima of float64 coverage (get_high_coverage_idx, nmf.py:66-76): k_baseline_gen's threshold is 0.1 max_i rowmax[i] / s_i,
+// here with s = 1.  One workgroup per gene (grid-stride), one row at a time.
+__global__ __launch_bounds__(256) void k_row_max_f64(const double *__restrict__ cov, const int64_t *__restrict__ goff,
+                                                     const int32_t *__restrict__ glen, double *__restrict__ rowmax, int n, int p)
+{
+    __shared__ double wmax[4];
+    for (int g = blockIdx.x; g < n; g += gridDim.x) {
+        const int L = glen[g];
+        const double *x = cov + goff[g];
+        for (int i = 0; i < p; i++) {
+            double m = -INFINITY;
+            for (int k = threadIdx.x; k < L; k += 256) m = fmax(m, x[(size_t) i * L + k]);
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) m = fmax(m, __shfl_xor(m, o));
+            if (lane_id() == 0) wmax[wave_id()] = m;
+            __syncthreads();
+            if (threadIdx.x == 0) rowmax[(size_t) g * p + i] = fmax(fmax(wmax[0], wmax[1]), fmax(wmax[2], wmax[3]));
+            __syncthreads();
+        }
+    }
+}
+
+// Bare factorisations of a batch of independent p x n matrices, one launch, persistent workgroups on a widest-first queue.
+// Every matrix is one nmf_gen call (the block-wide power iteration on A A^T to fp64 round-off, like svds with tol = 0; for
+// n < p the same top singular triplet as scipy's n x n Gram): T = 0 is rank_one_approx (nmf.py:55-64) and ratio_svd
+// (:109-121), T > 0 is nmf() (:78-107).  Outputs K = u sigma, E = v = (A^T u) / sigma with sigma = ||A^T u||, and optionally
+// the estimate u_i (A^T u)_k = (K E)_ik, clamped below by x for ratio_svd.  The input is read in place (row stride n); the
+// x + lambda state and the column vectors live in the workgroup's scratch slot.
+__global__ __launch_bounds__(NT, DN_GEN_MINW) void k_nmf_f64(NmfArgsF64 A)
+{
+    const int tid = threadIdx.x;
+    const int p = A.p;
+    char *slot = A.ws + (size_t) blockIdx.x * A.slot_bytes;
+    if (tid < p) { g_st.scale[tid] = 1.0; g_st.inv[tid] = 1.0; }
+    if (tid == 0) g_st.max_steps = A.max_steps > 0 ? A.max_steps : EIG_MAX_STEPS_DEFAULT;
+    __syncthreads();
+    for (;;) {
+        if (tid == 0) g_sm.gene = atomicAdd(A.counter, 1);
+        __syncthreads();
+        const int q = g_sm.gene;
+        __syncthreads();
+        if (q >= A.n) break;
+        const int m = A.order[q];
+        const int n = A.ncol[m];
+        const double *x = A.x + A.xoff[m];
+        double *Ast = reinterpret_cast<double *>(slot);
+        double *rs = Ast + (size_t) p * n;
+        double *sv = rs + n;
+        double *sj = sv + n;
+        int status = ST_OK;
+        if (n < 2) status = ST_VALUE_ERROR;                                  // svds(k=1) needs min(p, n) >= 2
+        else {
+            if (tid == 0) g_st.steps = 0;
+            __syncthreads();
+            nmf_gen(x, Ast, rs, sv, sj, n, n, A.T, 1, p);
+            status = g_st.status;
+        }
+        if (status == ST_OK) {
+            double part[TI];
+#pragma unroll
+            for (int r = 0; r < TI; r++) part[r] = 0.0;
+            for (int k = tid; k < n; k += NT) part[0] = fma(sj[k], sj[k], part[0]);
+            tile_sum(part);
+            const double sig = sqrt(g_sm.tot[0]);
+            __syncthreads();
+            if (!(sig > 0.0)) status = ST_ARPACK;
+            else {
+                if (tid < p) A.K[(size_t) m * p + tid] = g_st.u[tid] * sig;
+                double *E = A.E + A.eoff[m];
+                for (int k = tid; k < n; k += NT) E[k] = sj[k] / sig;
+                if (A.est) {
+                    double *o = A.est + A.xoff[m];
+                    for (int k = tid; k < n; k += NT) {
+                        const double s = sj[k];
+                        for (int i = 0; i < p; i++) {
+                            double v = g_st.u[i] * s;
+                            if (A.ratio) { const double xv = x[(size_t) i * n + k]; v = v < xv ? xv : v; }     // nmf.py:119
+                            o[(size_t) i * n + k] = v;
+                        }
+                    }
+                }
+            }
+        }
+        if (tid == 0) A.status[m] = status;
+        __syncthreads();
+    }
+}
+
+}  // namespace gen_f64
+
+int launch_row_max_f64(const double *cov, const int64_t *goff, const int32_t *glen, double *rowmax, int n, int p, int grid, hipStream_t s)
+{
+    hipLaunchKernelGGL(gen_f64::k_row_max_f64, dim3(grid), dim3(256), 0, s, cov, goff, glen, rowmax, n, p);
+    return (int) hipGetLastError();
+}
+int launch_baseline_f64(const IterArgsF64 &a, int grid, hipStream_t s)
+{
+    hipLaunchKernelGGL(gen_f64::k_baseline_gen, dim3(grid), dim3(gen_f64::NT), 0, s, a);
+    return (int) hipGetLastError();
+}
+int launch_est_f64(const EstArgsF64 &a, const int32_t *tile_gene, const int32_t *tile_col0, int n_tiles, hipStream_t s)
+{
+    hipLaunchKernelGGL(gen_f64::k_estimates_gen, dim3(n_tiles), dim3(256), 0, s, a, tile_gene, tile_col0);
+    return (int) hipGetLastError();
+}
+int launch_nmf_f64(const NmfArgsF64 &a, int grid, hipStream_t s)
+{
+    hipLaunchKernelGGL(gen_f64::k_nmf_f64, dim3(grid), dim3(gen_f64::NT), 0, s, a);
+    return (int) hipGetLastError();
+}
+int blocks_per_cu_f64(int which)
+{
+    int nb = 0;
+    const hipError_t e = which == 0 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, gen_f64::k_baseline_gen, gen_f64::NT, 0)
+                                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, gen_f64::k_nmf_f64, gen_f64::NT, 0);
+    return e == hipSuccess ? nb : 0;
+}
+
+#else   // the float32 count builds: kernel sets
 
 static int launch_baseline(const IterArgs &a, int grid, size_t, hipStream_t s)
 {
@@ -1484,5 +1633,6 @@ const KernelSet *kernel_set_rows()
     return &ks;
 }
 #endif
+#endif  // DN_GEN_F64
 
 }  // namespace dn

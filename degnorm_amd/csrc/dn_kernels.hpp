@@ -120,6 +120,69 @@ struct EstArgs {
     double         scale[P_MAX];
 };
 
+// The float64-input path (dn_generic.hip compiled with DN_GEN_F64=1, namespace gen_f64; dn_nmf_f64 / dn_baseline_selection_f64):
+// the same fields as IterArgs / EstArgs with float64 coverage and float64 row maxima (k_row_max_f64).  Its own buffers, scale 1.
+struct IterArgsF64 {
+    const double  *cov;
+    const int64_t *goff;
+    const int32_t *glen;
+    const int32_t *order;
+    int32_t       *counter;
+    const int64_t *ds_start;
+    const double  *rowmax;     // n x p: max_j F[i][j]
+    const int32_t *x16;        // unused (nullptr): no 16-bit packing of float64 input
+    char          *ws;
+    double        *rho;
+    int32_t       *flags;
+    int32_t       *trace;
+    double        *kfin;
+    int32_t       *emode;
+    double        *svec;
+    const int64_t *svoff;
+    int64_t        slot_bytes;
+    int32_t        n_genes;
+    int32_t        S;
+    int32_t        lds_cols;
+    int32_t        T, bins, min_hc, rate, skip, want_est;
+    int32_t        p;
+    int32_t        max_steps;
+    double         scale[P_MAX];
+    double         inv_scale[P_MAX];
+};
+
+struct EstArgsF64 {
+    const double  *cov;
+    const int64_t *goff;
+    const int32_t *glen;
+    const double  *kfin;
+    const int32_t *emode;
+    const double  *svec;
+    const int64_t *svoff;
+    double        *out;
+    const int64_t *ooff;
+    int32_t        n_genes;
+    int32_t        p;
+    double         scale[P_MAX];
+};
+
+// Bare factorisations of a batch of independent float64 matrices (k_nmf_f64): rank_one_approx (nmf.py:55-64, T = 0),
+// nmf() (:78-107, T iterations), ratio_svd (:109-121, T = 0, ratio = 1).
+struct NmfArgsF64 {
+    const double  *x;          // matrix m at xoff[m]: p x ncol[m], row-major
+    const int64_t *xoff;
+    const int32_t *ncol;
+    const int64_t *eoff;       // column offset of matrix m (E at eoff[m], est at p * eoff[m] = xoff[m])
+    const int32_t *order;      // work queue: matrix ids, widest first
+    int32_t       *counter;
+    double        *K;          // n x p
+    double        *E;          // sum of ncol
+    double        *est;        // nullable: p x ncol[m] at xoff[m]
+    int32_t       *status;     // n
+    char          *ws;         // scratch: slots x slot_bytes (x + lambda [p][S], residual profile, s_start, A^T u [S])
+    int64_t        slot_bytes;
+    int32_t        n, p, T, ratio, max_steps;
+};
+
 // ---------------------------------------------------------------------------------------------------
 // LDS layout of one workgroup (static part; the lambda tile is dynamic shared memory behind it).
 // ---------------------------------------------------------------------------------------------------
@@ -2721,5 +2784,12 @@ struct KernelSet {
 
 const KernelSet *kernel_set_for(int p);   // dn_api.hip
 const KernelSet *kernel_set_generic();    // dn_generic.hip (run-time p, any p <= P_MAX)
+
+// dn_generic.hip compiled with DN_GEN_F64=1 (namespace gen_f64): the float64-input path.  Launchers return hipGetLastError().
+int launch_row_max_f64(const double *cov, const int64_t *goff, const int32_t *glen, double *rowmax, int n, int p, int grid, hipStream_t s);
+int launch_baseline_f64(const IterArgsF64 &a, int grid, hipStream_t s);
+int launch_est_f64(const EstArgsF64 &a, const int32_t *tile_gene, const int32_t *tile_col0, int n_tiles, hipStream_t s);
+int launch_nmf_f64(const NmfArgsF64 &a, int grid, hipStream_t s);
+int blocks_per_cu_f64(int which);         // which: 0 k_baseline_gen, 1 k_nmf_f64
 
 }  // namespace dn

@@ -13,7 +13,12 @@ correct_di_scores (:148-158) and the read-count / scale-factor update (:575-590)
 (threads, float64 -> float32 staging, dn_upload_ragged), sees 3p + 4 numbers per outer iteration, and copies rho / x_adj /
 x_weighted / ran_baseline_selection back once at the end (fetch_state) plus the estimates of the last iteration.
 
-There is no CPU fallback: if the HIP library or a GPU is missing, run() raises.
+The reference's per-gene methods (rank_one_approx, nmf, ratio_svd, baseline_selection, ... nmf.py:55-453) are here as well,
+with its signatures and return order: the factorisations run on the float64-input device path (degnorm_amd/per_gene.py,
+dn_nmf_f64 / dn_baseline_selection_f64), one launch per call, on the matrices as given -- e.g. coverage already scaled by
+1/s_i, which the float32 count path of run() cannot hold exactly.  They reuse the Device run() opened, or open one lazily.
+
+There is no CPU fallback: if the HIP library or a GPU is missing, run() and the per-gene methods raise.
 """
 import logging
 import os
@@ -182,6 +187,89 @@ class GeneNMFOA(object):
             raise ValueError('Model not yet fit. NMF-OA has not been run.')
         pos = {g: k for k, g in enumerate(self.genes)}
         return self._dev.fetch_estimates_subset([pos[g] for g in genes])
+
+    # ------------------------------------------------------------------------------------------- #
+    # The reference's per-gene methods (nmf.py:55-453) on the float64-input device path (per_gene.py).
+    def _device(self):
+        """The Device run() opened, else one opened now for self.device (raises without the HIP library or a GPU)."""
+        if self._dev is None:
+            from . import _lib
+            self._dev = _lib.Device(self.device)
+        return self._dev
+
+    @staticmethod
+    def rank_one_approx(x):
+        """(K p x 1, E 1 x n): the top singular triplet of x as u * sigma and v (nmf.py:55-64)."""
+        from . import per_gene
+        return per_gene.rank_one_approx(per_gene.static_device, x)
+
+    @staticmethod
+    def get_high_coverage_idx(x):
+        """Positions whose sample-wise maximum exceeds 10 % of the matrix maximum (nmf.py:66-76)."""
+        from . import per_gene
+        return per_gene.get_high_coverage_idx(x)
+
+    def nmf(self, x, factors=False):
+        """NMF-OA of x with self.nmf_iter iterations (nmf.py:78-107): (K, E) if factors, else K.dot(E)."""
+        from . import per_gene
+        return per_gene.nmf(self._device, x, self.nmf_iter, factors)
+
+    def ratio_svd(self, x):
+        """max(K E, x) elementwise for the rank-one K E of x (nmf.py:109-121)."""
+        from . import per_gene
+        return per_gene.ratio_svd_list(self._device, [x])[0]
+
+    def run_ratio_svd_serial(self, x):
+        """ratio_svd of every matrix of the list, one device launch (nmf.py:123-124)."""
+        from . import per_gene
+        return per_gene.ratio_svd_list(self._device, x)
+
+    def adjust_coverage_curves(self, dat):
+        """F / s_i row by row with self.scale_factors (nmf.py:142-146)."""
+        from . import per_gene
+        return per_gene.adjust_coverage_curves(dat, self.scale_factors)
+
+    @staticmethod
+    def shift_bins(bins, dropped_bin):
+        """Keep the bins consecutive after bin `dropped_bin` was deleted, in place (nmf.py:160-187)."""
+        from . import per_gene
+        return per_gene.shift_bins(bins, dropped_bin)
+
+    def baseline_selection(self, F):
+        """(rho unclipped, estimate, ran_baseline_selection) of one coverage matrix as given (nmf.py:189-372)."""
+        return self.run_baseline_selection_serial([F])[0]
+
+    def run_baseline_selection_serial(self, x):
+        """baseline_selection of every matrix of the list, one device launch (nmf.py:374-375)."""
+        from . import per_gene
+        return per_gene.baseline_selection_list(self._device, x, nmf_iter=self.nmf_iter, bins=self.bins,
+                                                min_high_coverage=self.min_high_coverage, downsample_rate=self.downsample_rate,
+                                                skip_baseline_selection=self.skip_baseline_selection, p=self.p)
+
+    def par_apply_baseline_selection(self, dat, degnorm_iter):
+        """
+        baseline_selection over all genes (nmf.py:377-406): rho clipped to [0, 0.9] into self.rho, column degnorm_iter of
+        self.ran_baseline_selection set; returns the estimates.  One device launch; n_jobs keeps its meaning for run().
+        """
+        out = self.run_baseline_selection_serial(dat)
+        self.rho = np.vstack([r[0] for r in out])
+        self.rho[self.rho > 0.9] = 0.9
+        self.rho[self.rho < 0.] = 0.
+        if self.ran_baseline_selection is None:
+            self.ran_baseline_selection = np.zeros(shape=[len(out), max(self.degnorm_iter, degnorm_iter + 1)]).astype(bool)
+        self.ran_baseline_selection[:, degnorm_iter] = np.array([r[2] for r in out])
+        return [r[1] for r in out]
+
+    @staticmethod
+    def _systematic_sample(n, take_every):
+        """Every take_every-th index from a random start drawn from np.random (nmf.py:408-425)."""
+        from . import per_gene
+        return per_gene.systematic_sample(n, take_every)
+
+    def downsample_2d(self, x, by_row=True):
+        """Systematic sample of the rows (or columns) of x at self.downsample_rate: (sampled x, indices) (nmf.py:427-453)."""
+        from . import per_gene
+        return per_gene.downsample_2d(x, self.downsample_rate, by_row)
 
     # ------------------------------------------------------------------------------------------- #
     def save_results(self, estimates, gene_manifest_df, output_dir='.', sample_ids=None):

@@ -176,6 +176,35 @@ int  dn_fetch_estimates(dn_handle h, double *out);
  * __main__.py:291-316): gene_ids[n_sel] in upload order; out holds the selected genes back to back, in that order. */
 int  dn_fetch_estimates_subset(dn_handle h, int64_t n_sel, const int64_t *gene_ids, double *out);
 
+/* The float64-input path: per-gene calls on matrices as given ------------------------------------------------
+ * Replaces: GeneNMFOA.rank_one_approx / nmf / ratio_svd / run_ratio_svd_serial / baseline_selection /
+ * run_baseline_selection_serial (nmf.py:55-121, :189-375) and their module twins (nmf_mpi.py:10-78, :174-378) called on
+ * arbitrary float64 matrices -- e.g. coverage already scaled by 1/s_i (nmf.py:196, :563), which the float32 count storage
+ * of dn_upload_* cannot hold exactly.  Each call is one kernel launch over the whole batch (longest-first work queue) in
+ * device buffers of its own: the handle's resident coverage, scratch slots and outer-iteration state are not touched, so
+ * dn_fetch_estimates* and the dn_outer_* calls see what they saw before.  x[m] / F[m]: C-contiguous p x lengths[m] float64.
+ * Outputs are packed back to back in caller order (K: n x p; E and est at the running column offset, est p x L each).
+ * 2 <= p <= 64, else DN_E_UNSUPPORTED (dn_p_supported is about the count path and unchanged).
+ *
+ * dn_nmf_f64  mode DN_NMF_RANK_ONE: svds(x, k=1) -> K = u sigma, E = v (nmf.py:55-64)
+ *             mode DN_NMF:          nmf(x) with nmf_iter (>= 0) Lagrangian iterations, factors K, E (nmf.py:78-107)
+ *             mode DN_NMF_RATIO:    rank one, est = max(K E, x) (nmf.py:109-121)
+ *             est (nullable) receives K E (or the clamped estimate); status[n]: 0, or -3 for min(p, n_k) < 2 (svds'
+ *             ValueError), -1 for an all-zero matrix (ArpackError), -4 for an eigen-solve left through its step cap.
+ * dn_baseline_selection_f64  baseline_selection (nmf.py:189-372) on F as given (scale 1): rho[n*p] unclipped, flags[n]
+ *             (ran_baseline_selection), trace[n*DN_TRACE_LEN] (nullable; [6] is the status), est (nullable; the
+ *             estimate of every gene).  prm->want_estimates is ignored (est decides).  ds_start: as dn_baseline_iteration. */
+#define DN_NMF_RANK_ONE       0
+#define DN_NMF                1
+#define DN_NMF_RATIO          2
+int  dn_nmf_f64(dn_handle h, int64_t n, int32_t p, const double *const *x, const int64_t *lengths, int32_t mode,
+                int32_t nmf_iter, double *K, double *E, double *est, int32_t *status);
+int  dn_baseline_selection_f64(dn_handle h, int64_t n, int32_t p, const double *const *F, const int64_t *lengths,
+                               const dn_params *prm, const int64_t *ds_start, double *rho, int32_t *flags,
+                               int32_t *trace, double *est);
+/* Device time in ms of the kernel(s) of the most recent dn_nmf_f64 / dn_baseline_selection_f64 call.                  */
+double dn_last_f64_ms(dn_handle h);
+
 /* Coverage-matrix assembly -------------------------------------------------------------
  * Replaces: the densify-and-slice loop of merge_chrom_coverage (reads_coverage_merge.py:283-353).
  * Per sample i the chromosome coverage is the CSR row written by reads.py:785-786: nnz[i] positions indices[i][]
