@@ -73,7 +73,7 @@ struct GState {
     double scale[GP], inv[GP], sumF[GP], rho[GP], K[GP], us[GP], rho_fb[GP], u[GP], y[GP], csum[GP], rsum[GP];
     double S, theta, sig0;
     int32_t status, steps;
-    int32_t max_steps;          // cap of one eigen-solve in MFMA-solver units (IterArgs::max_steps); the plain power
+    int32_t max_steps;          // cap of one eigen-solve in power-step equivalents (IterArgs::max_steps); the plain power
 };                              // iterations below (one step per pass) get 5x that many
 __shared__ GState g_st;
 __shared__ double g_rows_tot[256];     // nmf_rows: the wave's Gram totals (<= 78) and the solver's zero slot
@@ -222,16 +222,13 @@ __device__ __attribute__((noinline)) void nmf_gen(const cov_t *Fb, double *A, do
 // inner iteration (nmf_gen: ~37 us each, almost all of it barriers) is the wrong shape.  Here sample s is lane s of
 // wave 0 and keeps its row of x + lambda in registers; the right singular vector v comes from the n x n Gram matrix
 // A^T A = sum over the lanes of a_s a_s^T (what scipy's svds does when n < p) through the same register reduce-scatter
-// and MFMA squaring solver as the templated kernels, with no barrier inside the loop: ~2 us per inner iteration.
+// and eigen-solver (Solver<NSM>: top_eig_dpp) as the templated kernels, with no barrier inside the loop: ~2 us per inner iteration.
 // K E = (A v) v^T, so u_s sigma = a_s . v.  Same outputs as nmf_gen.  The other waves of the workgroup wait.
 // ---------------------------------------------------------------------------------------------------
 constexpr int NSM_MAX = 12;                   // widest active matrix the row-wise routine takes
-#ifndef DN_ROWS_EXACT
-#define DN_ROWS_EXACT 1         // one instantiation of nmf_rows per column count 2..12 (0: capacities 4 / 6 / 8 / 10 / 12)
-#endif
 constexpr int ROWS_ZSLOT = 255;               // last double of g_rows_tot, kept at 0.0 (padding lanes of the solver read it)
 
-// NSM: compiled column capacity (4, 6, 8, 10 or 12: the Gram matrix and the solver's tile shrink with it)
+// NSM: compiled column count (2 .. 12: the Gram matrix and the solver's work shrink with it)
 // SAFE: the repeat of a call whose result shows samples decoupled from the top block (dn_kernels.hpp, warm_start_unsafe): every solve
 // block by block.  A separate instantiation -- inside the hot one the rare path cost 32 % (17.6 against 13.3 ms per launch on config 4)
 template <int NSM, bool SAFE = false>
@@ -464,11 +461,9 @@ __global__ __launch_bounds__(NT, DN_GEN_MINW) void k_baseline_gen(GenIterArgs A)
                 int csize = 1, n_bins = 0;
                 bool first = true, in_loop = false;
                 for (;;) {
-                    // one instantiation per column count (DN_ROWS_EXACT) or per even capacity: the n x n Gram matrix has
-                    // NSM (NSM + 1) / 2 entries to multiply and reduce-scatter over the lanes every inner iteration (the
-                    // bulk of the loop's ~1 000 instructions; at most 64 entries go in ONE round) and the solver
-                    // ceil(NSM / 4) MFMAs per product -- config 4's first calls have 9-10 columns
-#if DN_ROWS_EXACT
+                    // one instantiation per column count: the n x n Gram matrix has NSM (NSM + 1) / 2 entries to multiply
+                    // and reduce-scatter over the lanes every inner iteration (the bulk of the loop's ~1 000 instructions; at
+                    // most 64 entries go in ONE round) -- config 4's first calls have 9-10 columns
 #define DN_ROWS_CASE(N) case N: nmf_rows<N>(Fb, rs, sv, sj, n, S, A.T, first ? 1 : 0, p); break;
                     if (n <= NSM_MAX) {
                         switch (n) {
@@ -478,13 +473,6 @@ __global__ __launch_bounds__(NT, DN_GEN_MINW) void k_baseline_gen(GenIterArgs A)
                         }
                     }
 #undef DN_ROWS_CASE
-#else
-                    if (n <= 4) nmf_rows<4>(Fb, rs, sv, sj, n, S, A.T, first ? 1 : 0, p);
-                    else if (n <= 6) nmf_rows<6>(Fb, rs, sv, sj, n, S, A.T, first ? 1 : 0, p);
-                    else if (n <= 8) nmf_rows<8>(Fb, rs, sv, sj, n, S, A.T, first ? 1 : 0, p);
-                    else if (n <= 10) nmf_rows<10>(Fb, rs, sv, sj, n, S, A.T, first ? 1 : 0, p);
-                    else if (n <= NSM_MAX) nmf_rows<12>(Fb, rs, sv, sj, n, S, A.T, first ? 1 : 0, p);
-#endif
                     else nmf_gen(Fb, Ast, rs, sv, sj, n, S, A.T, first ? 1 : 0, p);
                     if (n <= NSM_MAX) {
                         // the safe repeat (dn_kernels.hpp, warm_start_unsafe): a covered sample whose component of u is (nearly) zero is
@@ -497,7 +485,6 @@ __global__ __launch_bounds__(NT, DN_GEN_MINW) void k_baseline_gen(GenIterArgs A)
                         }
                         if (unsafe) {
                             __syncthreads();
-#if DN_ROWS_EXACT
 #define DN_ROWS_CASE(N) case N: nmf_rows<N, true>(Fb, rs, sv, sj, n, S, A.T, first ? 1 : 0, p); break;
                             switch (n) {
                                 DN_ROWS_CASE(3) DN_ROWS_CASE(4) DN_ROWS_CASE(5) DN_ROWS_CASE(6) DN_ROWS_CASE(7) DN_ROWS_CASE(8)
@@ -505,9 +492,6 @@ __global__ __launch_bounds__(NT, DN_GEN_MINW) void k_baseline_gen(GenIterArgs A)
                                 default: nmf_rows<2, true>(Fb, rs, sv, sj, n, S, A.T, first ? 1 : 0, p); break;
                             }
 #undef DN_ROWS_CASE
-#else
-                            nmf_rows<12, true>(Fb, rs, sv, sj, n, S, A.T, first ? 1 : 0, p);
-#endif
                         }
                     }
                     if (g_st.status != ST_OK) { status = g_st.status; break; }
@@ -733,15 +717,7 @@ __device__ __forceinline__ int top_singular_raw(const float *x, int L, int p)
 // ---------------------------------------------------------------------------------------------------
 // The two streaming passes are inlined into the kernel (round 4): as functions of their own they saved and restored ~110 callee-saved
 // vector registers per call -- 55 KB of scratch traffic per wave and call, 440 KB per gene next to the gene's own 2 x 550 KB
-// (3.94 against 4.29 ms on the 16 000-gene slice; DN_MG_INLINE=0 builds the functions).
-#ifndef DN_MG_INLINE
-#define DN_MG_INLINE 1
-#endif
-#if DN_MG_INLINE
-#define DN_MG_FN __device__ __forceinline__
-#else
-#define DN_MG_FN __device__ __attribute__((noinline))
-#endif
+// (3.94 against 4.29 ms on the 16 000-gene slice).
 constexpr int MG_ROWS = 80;                  // 5 tiles of 16: p <= 64 samples + the row of ones
 constexpr int MG_LD = MG_ROWS + 1;           // LDS row stride in doubles (odd: the column walk of the solver is conflict-light)
 __shared__ double g_mg[MG_ROWS * MG_LD];
@@ -917,26 +893,11 @@ __device__ __attribute__((noinline)) void mg_finalize_i8(int L, int p)
     __syncthreads();
 }
 
-#ifndef DN_I8_ROWSEG
-#define DN_I8_ROWSEG 1          // 1: a load instruction reads 64 contiguous bytes per row (0: round 3's 64 contiguous bytes per LANE)
-#endif
-constexpr int I8_LK = DN_I8_ROWSEG ? 4 : 16, I8_Q = DN_I8_ROWSEG ? 16 : 4;     // column offset per lane group / per load
-#if defined(DN_PASS1_NT) && DN_PASS1_NT
-#define DN_P1_LOAD(ptr) __builtin_nontemporal_load(ptr)
-#else
-#define DN_P1_LOAD(ptr) (*(ptr))
-#endif
-#ifndef DN_PASS2_NT
-#define DN_PASS2_NT 1           // pass 2 is the last use of the gene's bytes: non-temporal loads (-5 % on the kernel)
-#endif
-#if DN_PASS2_NT
-#define DN_P2_LOAD(ptr) __builtin_nontemporal_load(ptr)
-#else
-#define DN_P2_LOAD(ptr) (*(ptr))
-#endif
+// a load instruction reads 64 contiguous bytes per row (round 3 read 64 contiguous bytes per LANE)
+constexpr int I8_LK = 4, I8_Q = 16;          // column offset per lane group / per load
 
 template <int TR>
-DN_MG_FN void mg_gram_pass_i8(const float *x, int L, int p)
+__device__ __forceinline__ void mg_gram_pass_i8(const float *x, int L, int p)
 {
     constexpr int NTILE = TR * (TR + 1) / 2;
     constexpr int W = NT / 64;
@@ -988,7 +949,7 @@ DN_MG_FN void mg_gram_pass_i8(const float *x, int L, int p)
 #pragma unroll
         for (int t = 0; t < TR; t++)
 #pragma unroll
-            for (int q = 0; q < 4; q++) raw[t][q] = DN_P1_LOAD((gF4_cptr) (rowp[t] + 64 * w + I8_Q * q));
+            for (int q = 0; q < 4; q++) raw[t][q] = *(gF4_cptr) (rowp[t] + 64 * w + I8_Q * q);
         auto trip = [&](auto more_c, int gn) {
             constexpr bool MORE = decltype(more_c)::value;
             dn_int4 H[TR], Lo[TR];
@@ -1004,7 +965,7 @@ DN_MG_FN void mg_gram_pass_i8(const float *x, int L, int p)
                 }
                 if constexpr (MORE) {
 #pragma unroll
-                    for (int q = 0; q < 4; q++) raw[t][q] = DN_P1_LOAD((gF4_cptr) (rowp[t] + 64 * gn + I8_Q * q));
+                    for (int q = 0; q < 4; q++) raw[t][q] = *(gF4_cptr) (rowp[t] + 64 * gn + I8_Q * q);
                 }
             }
             if constexpr (MORE) __builtin_amdgcn_sched_barrier(0);         // the loads stay in front of the products (the scheduler sinks them to save registers)
@@ -1033,7 +994,7 @@ DN_MG_FN void mg_gram_pass_i8(const float *x, int L, int p)
             for (int t = 0; t < TR; t++) {
                 dn_f4 v[4];
 #pragma unroll
-                for (int q = 0; q < 4; q++) v[q] = DN_P1_LOAD((gF4_cptr) (rowp[t] + (L - 64) + I8_Q * q));
+                for (int q = 0; q < 4; q++) v[q] = *(gF4_cptr) (rowp[t] + (L - 64) + I8_Q * q);
 #pragma unroll
                 for (int q = 0; q < 4; q++) {
                     unsigned lo, hi;
@@ -1182,11 +1143,11 @@ __device__ __attribute__((noinline)) int mg_solve(int p, int maxs, double *u_out
 // i of the wave's NEXT block into the register it just freed -- a full block of loads in flight through the second half of every
 // trip at no register cost; (ii) the blocks are walked from the gene's END: what pass 1 read last is read first, while it still
 // sits in the Infinity Cache / L2 (the 512 resident workgroups read ~280 MB between a byte's two uses otherwise), with
-// non-temporal loads (the last use of these bytes); (iii) a row's address is one 32-bit vector add away from the previous row's
-// (scalar block base + lane offset; the running 64-bit scalar base cost four scalar instructions per load); (iv) the block that
-// the gene's end leaves partial is done first, on its own, under the one exec mask it needs.
+// non-temporal loads (the last use of these bytes: -5 % on the kernel); (iii) a row's address is one 32-bit vector add away
+// from the previous row's (scalar block base + lane offset; the running 64-bit scalar base cost four scalar instructions per
+// load); (iv) the block that the gene's end leaves partial is done first, on its own, under the one exec mask it needs.
 template <int RC>                                                    // row capacity of this instantiation (p <= RC, p > RC - 8), a multiple of 8
-DN_MG_FN void mg_pass2(const float *x_, int L, int p)
+__device__ __forceinline__ void mg_pass2(const float *x_, int L, int p)
 {
     constexpr int W = NT / 64;
     const int tid = threadIdx.x, lane = lane_id(), w = __builtin_amdgcn_readfirstlane(wave_id());
@@ -1209,7 +1170,7 @@ DN_MG_FN void mg_pass2(const float *x_, int L, int p)
         gbyte_cptr blk = (gbyte_cptr) (x + k0);
         asm volatile("" : "+v"(off));                                   // (the row offsets are formed as the rows are walked: hoisted, they are 2 RC registers)
 #pragma unroll
-        for (int i = 0; i < RC; i++) { xv[i] = DN_P2_LOAD((gF_cptr) (blk + off)); off += step(i); }
+        for (int i = 0; i < RC; i++) { xv[i] = __builtin_nontemporal_load((gF_cptr) (blk + off)); off += step(i); }
     };
     auto dot = [&]() {
         double s0 = 0.0, s1 = 0.0;
@@ -1249,7 +1210,7 @@ DN_MG_FN void mg_pass2(const float *x_, int L, int p)
             for (int i = 0; i < RC; i++) {
                 asm volatile("" : "+v"(xv[i]));
                 const double xd = (double) xv[i];
-                if constexpr (MORE) { xv[i] = DN_P2_LOAD((gF_cptr) (blk + off)); off += step(i); }
+                if constexpr (MORE) { xv[i] = __builtin_nontemporal_load((gF_cptr) (blk + off)); off += step(i); }
                 acc[i] += fmax(g_st.u[i] * sj, xd);                     // est[est < x] = x   nmf.py:119
             }
         };

@@ -17,9 +17,10 @@
 // iteration updates the state a = x + lambda AND accumulates the p x p Gram matrix of the *next* a in registers (fp64).
 // The per-lane Gram partials are reduce-scattered inside each wave in registers (dn_reduce.hpp: v_permlane swaps + DPP,
 // fixed order => deterministic, no atomics), added across waves through LDS, and the top eigenvector of the p x p
-// matrix comes from repeated squaring on the fp64 matrix cores (top_eig_mfma, p <= 16; v_mfma_f64_16x16x4_f64) or a
-// row-distributed shifted power iteration (p > 16), to fp64 round-off like the reference's ARPACK call with tol = 0.
-// For p >= DN_MG_MIN_P the Gram matrix itself is accumulated on the matrix cores (mg_core).
+// matrix comes from a warm-started shifted power iteration, to fp64 round-off like the reference's ARPACK call with tol = 0:
+// for p <= 16 on the vector pipe with the iterate broadcast by DPP inside the multiply (top_eig_dpp), above that with the
+// matrix distributed by rows (top_eig_rows).  The register-tier cohorts keep the state of the inner loop in raw count units
+// (raw_units).  For p >= DN_MG_MIN_P the Gram matrix itself is accumulated on the matrix cores (mg_core).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -28,8 +29,8 @@
 #include "dn_dpp_ops.hpp"
 
 // Measured dead ends are recorded in DESIGN.md (section 4, "tried and not kept"), not kept here as compile-time branches:
-// non-temporal spill accesses, fp32 Gram accumulators, raw-count-units state, a lane-major tier save area, the register
-// tier as a masked loop for genes that fill it.
+// non-temporal spill accesses, fp32 Gram accumulators, a lane-major tier save area, the register tier as a masked loop for
+// genes that fill it, the squaring eigen-solver on the fp64 matrix cores of rounds 1-3.
 // Diagnostic ISA builds (-DDN_MARKS, tools/isa_regions.py): named comment lines in the generated assembly, so that the
 // instructions of each phase of an inner iteration can be counted statically.  Never defined for the product.
 #ifdef DN_MARKS
@@ -470,26 +471,15 @@ __device__ __forceinline__ int top_eig(const double (&G)[P * (P + 1) / 2], doubl
     return steps;
 }
 
-// The hot loop finds the same eigenpair through the fp64 matrix cores: repeated squaring instead of single power steps.
-// v_mfma_f64_16x16x4_f64 (gfx950, 64 cycles) takes A as lane (i = l & 15, k = l >> 4) -> A[i][k], B as lane
-// (j, k) -> B[k][j] and returns D[q + 4 r][j] in register r of lane (j, q = l >> 4).  For a symmetric matrix
-// held as h[kb] = H[l & 15][(l >> 4) + 4 kb] the product H H = sum_kb mfma(h[kb], h[kb]) therefore comes back in
-// the layout it went in, so M squarings cost M * ceil(p / 4) MFMAs and no data movement, and one step with
-// H = ((G - mu I) / tr)^(2^M) equals 2^M shifted power steps.  The iterate lives in the B layout (register kb of
-// lane group q holds v[q + 4 kb], every column alike), which is also what the step returns; norms are all-reduced
-// over the four 16-lane rows with the permlane swaps, so every lane sees identical bits.  The shift uses the
-// eigenvalue of the previous solve (theta on entry, 0 on a cold start).  theta = u^T G u of the unshifted matrix.
+// the accumulator of v_mfma_f64_16x16x4_f64 (mg_core)
 typedef double dn_double4 __attribute__((ext_vector_type(4)));
 
+// sum over the four 16-lane rows of the wave (permlane swaps): every lane gets identical bits
 __device__ __forceinline__ double allsum_rows(double v)
 {
     v = swap32_add(v, v);
     return swap16_add(v, v);
 }
-
-#ifndef DN_EIG_SQUARINGS
-#define DN_EIG_SQUARINGS 2
-#endif
 
 __device__ __forceinline__ double rsqrt_newton(double n2)
 {
@@ -510,152 +500,10 @@ __device__ __forceinline__ double rcp_newton(double x)
     return y;
 }
 
-template <int KB>
-__device__ __forceinline__ dn_double4 mfma_sym(const double (&h)[KB], const double (&v)[KB])
-{
-    dn_double4 y = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int kb = 0; kb < KB; kb++) y = __builtin_amdgcn_mfma_f64_16x16x4f64(h[kb], v[kb], y, 0, 0, 0);
-    return y;
-}
-
-// State carried from one solve to the next inside an nmf() call: the iterate in the MFMA B layout (no rebuild
-// from the broadcast u), and the scale / shift the next solve starts from (they only steer convergence).
-template <int P>
-struct EigState {
-    static constexpr int KB = (P + 3) / 4;
-    double v[KB];        // v[kb] of lane group q = u[q + 4 kb]
-    double sc;           // ~ 1 / trace(G)
-    double mu;           // shift in the units of G (0: none); the caller subtracts it from the diagonal in LDS
-};
-
-template <int P>
-__device__ __forceinline__ void eig_state_cold(EigState<P> &st, double tr)
-{
-    const int q = lane_id() >> 4;
-    const double u0 = 1.0 / sqrt((double) P);
-#pragma unroll
-    for (int kb = 0; kb < EigState<P>::KB; kb++) st.v[kb] = (q + 4 * kb < P) ? u0 : 0.0;
-    st.sc = __builtin_amdgcn_rcp(tr);
-    st.mu = 0.0;
-}
-
-// tot holds G - st.mu I (packed, plus a zero at zslot).  On return u is the unit top eigenvector (broadcast),
-// theta the eigenvalue of G: exact (Rayleigh quotient) when asked for, else an estimate that only feeds the next shift.
-template <int P>
-__device__ __forceinline__ int top_eig_mfma(const double *tot, int zslot, double (&u)[P], double &theta, EigState<P> &st,
-                                            bool exact_theta, int maxs = EIG_MAX_STEPS_DEFAULT)
-{
-    static_assert(P <= 16, "one 16 x 16 MFMA tile");
-    constexpr int KB = EigState<P>::KB;
-    constexpr int M = DN_EIG_SQUARINGS;
-    const int c = lane_id() & 15, q = lane_id() >> 4;
-    const double sc = st.sc, mu = st.mu;
-    double g[KB], h[KB], v[KB];
-#pragma unroll
-    for (int kb = 0; kb < KB; kb++) {
-        const int k = q + 4 * kb;
-        const int a = c > k ? c : k, b = c > k ? k : c;
-        g[kb] = tot[a < P ? a * (a + 1) / 2 + b : zslot] * sc;          // rows / columns >= P are zero and stay zero
-        h[kb] = g[kb];
-        v[kb] = st.v[kb];
-    }
-    DN_MARK("solver_loaded");
-#pragma unroll
-    for (int m = 0; m < M; m++) {
-        const dn_double4 d = mfma_sym<KB>(h, h);
-#pragma unroll
-        for (int kb = 0; kb < KB; kb++) h[kb] = d[kb];
-    }
-    // two steps back to back; the norm of the first iterate is formed in the shadow of the second product
-    const dn_double4 y1 = mfma_sym<KB>(h, v);
-    double y1r[KB];
-#pragma unroll
-    for (int kb = 0; kb < KB; kb++) y1r[kb] = y1[kb];
-    const dn_double4 y2 = mfma_sym<KB>(h, y1r);
-    // trace of G for the next solve's scale and shift: independent of the products above
-    double dg[P];
-#pragma unroll
-    for (int i = 0; i < P; i++) dg[i] = tot[i * (i + 1) / 2 + i];
-#pragma unroll
-    for (int w = 1; w < P; w *= 2) {
-#pragma unroll
-        for (int i = 0; i + w < P; i += 2 * w) dg[i] += dg[i + w];
-    }
-    const double tr = fma((double) P, mu, dg[0]);
-    double p1 = 0.0, p2 = 0.0;
-#pragma unroll
-    for (int kb = 0; kb < KB; kb++) { p1 = fma(y1[kb], y1[kb], p1); p2 = fma(y2[kb], y2[kb], p2); }
-    const double n1 = allsum_rows(p1), n2 = allsum_rows(p2);
-    if (!(n1 > 0.0) || !(n2 > 0.0)) { theta = 0.0; return 1; }
-    const double i1 = rsqrt_newton(n1), i2 = rsqrt_newton(n2);
-    double e1p = 0.0, e2p = 0.0;
-#pragma unroll
-    for (int kb = 0; kb < KB; kb++) {
-        const double u1 = y1[kb] * i1, u2 = y2[kb] * i2;
-        const double da = u1 - v[kb], db = u2 - u1;
-        e1p = fma(da, da, e1p); e2p = fma(db, db, e2p);
-        v[kb] = u2;
-    }
-    double d2_prev = allsum_rows(e1p), d2 = allsum_rows(e2p);
-    DN_MARK("solver_checked");
-    double n_last = n2 * i2, i_prev = i1;                               // |y2| and 1 / |y1|: y2 = H y1
-    int steps = 1 + (2 << M);
-    // as in top_eig_rows: stop when the error predicted from the contraction between two checks is ~1e-13
-    // (ratio = d2 / d2_prev < 0.25 and 4 d2 ratio <= 1e-26, written without the division)
-    bool conv;
-    while (!(conv = (d2 <= 1e-26 || (4.0 * d2 < d2_prev && 4.0 * d2 * d2 <= 1e-26 * d2_prev))) && steps < maxs) {
-        const dn_double4 y = mfma_sym<KB>(h, v);
-        double part = 0.0;
-#pragma unroll
-        for (int kb = 0; kb < KB; kb++) part = fma(y[kb], y[kb], part);
-        const double nn = allsum_rows(part);
-        if (!(nn > 0.0)) { theta = 0.0; return steps; }
-        const double inv = rsqrt_newton(nn);
-        n_last = nn * inv; i_prev = 1.0;                               // v was a unit vector here
-        double dpart = 0.0;
-#pragma unroll
-        for (int kb = 0; kb < KB; kb++) {
-            const double un = y[kb] * inv;
-            const double d = un - v[kb];
-            dpart = fma(d, d, dpart);
-            v[kb] = un;
-        }
-        d2_prev = d2;
-        d2 = allsum_rows(dpart);
-        steps += 1 << M;
-    }
-#pragma unroll
-    for (int i = 0; i < P; i++) {
-        const double t = v[i >> 2];
-        u[i] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(t), 16 * (i & 3)),
-                                __builtin_amdgcn_readlane(__double2loint(t), 16 * (i & 3)));
-    }
-    if (exact_theta) {
-        const dn_double4 w = mfma_sym<KB>(g, v);                       // Rayleigh quotient: v^T (G - mu I) v / |v|^2 + mu
-        double tp = 0.0;
-#pragma unroll
-        for (int kb = 0; kb < KB; kb++) tp = fma(v[kb], w[kb], tp);
-        theta = allsum_rows(tp) / sc + mu;
-    } else {
-        // dominant eigenvalue of H ~ |H y| / |y|, and H = ((G - mu I) sc)^(2^M)
-        double lam = n_last * i_prev;
-#pragma unroll
-        for (int m = 0; m < M; m++) lam = __builtin_amdgcn_sqrt(lam);
-        theta = fma(lam, __builtin_amdgcn_rcp(sc), mu);
-    }
-#pragma unroll
-    for (int kb = 0; kb < KB; kb++) st.v[kb] = v[kb];
-    st.sc = __builtin_amdgcn_rcp(tr);
-    double mn = (tr - theta) * (1.0 / (double) (P > 1 ? P - 1 : 1));
-    st.mu = (theta > 0.0 && mn > 0.0 && mn < 0.5 * theta) ? mn : 0.0;
-    return conv ? (steps < maxs ? steps + 1 : maxs) : maxs + 1;         // > maxs: left through the step cap
-}
-
 // ---------------------------------------------------------------------------------------------------
-// Round 4: the same eigenpair by a warm-started, shifted power iteration on the vector pipe, lane = row, with the iterate
-// broadcast INSIDE the multiply: gfx90a+ has DPP forms of two fp64 instructions, v_fmac_f64 and v_mov_b64, restricted to
-// row_newbcast:j ("every lane of a 16-lane row reads lane j of the row").  With row r of H = (G - mu I) sc in the registers of
+// The hot loop's solver for p <= 16 (top_eig_dpp, round 4): a warm-started, shifted power iteration on the vector pipe,
+// lane = row, with the iterate broadcast INSIDE the multiply: gfx90a+ has DPP forms of two fp64 instructions, v_fmac_f64 and
+// v_mov_b64, restricted to row_newbcast:j ("every lane of a 16-lane row reads lane j of the row").  With row r of H = (G - mu I) sc in the registers of
 // lane r (every 16-lane row of the wave keeps its own copy of the matrix, p <= 16), one power step is p instructions
 //     y_r += bcast_j(v) * H[r][j]          v_fmac_f64_dpp acc, v, h_j row_newbcast:j          (dn_dpp_ops.hpp, generated)
 // and leaves y distributed as v was -- no v_readlane, no LDS, no matrix instruction; a dot product over the rows costs the same p
@@ -708,7 +556,7 @@ __device__ __forceinline__ double bcast_lane(double t, int i)
 
 constexpr int EIG_RHO_MAX_AGE = 8;
 
-// Same contract as top_eig_mfma: tot holds G - st.mu I (packed, plus a zero at zslot); u the unit top eigenvector (broadcast),
+// tot holds G - st.mu I (packed lower triangle, plus a zero at zslot); on return u is the unit top eigenvector (broadcast),
 // theta the eigenvalue of G -- the exact Rayleigh quotient when asked for (the last solve of a call), an estimate after a cold
 // solve (it sets shift and scale), untouched otherwise.  COLD: the first solve of an nmf() call.
 // ss (diagnostics, tools/ubench/solver_ab.hip): cycles per phase { load, blind steps, first normalisation, looks, epilogue }
@@ -824,7 +672,7 @@ __device__ __forceinline__ int top_eig_dpp(const double *tot, int zslot, double 
     return conv ? (steps < maxs ? steps + 1 : maxs) : maxs + 1;           // > maxs: left through the step cap
 }
 
-// Sample counts above 16 (more than one MFMA tile): shifted power iteration with the matrix distributed by rows --
+// Sample counts above 16 (more than one 16-lane row): shifted power iteration with the matrix distributed by rows --
 // lane l keeps row l of G, computes one component of G v per step, v_readlane broadcasts the p components.  Two
 // unnormalised steps between convergence checks; the check predicts the current error from the contraction between
 // consecutive checks and stops at ~1e-13.  Warm-started from u.  All waves run it redundantly on identical data.
@@ -992,36 +840,23 @@ __device__ __forceinline__ int top_eig_rows_lds(const double *tot, double *uv, d
 // below 1e-7 -> the call is done by the safe path, which solves block by block (solve_by_blocks below).  A stuck iterate keeps
 // its tiny components, so the test catches it wherever in the call it got stuck; it costs such genes only.
 constexpr double WARM_START_MIN_COMPONENT = 1e-7;
-// One interface over the two solvers: the MFMA squaring solver with its carried state for p <= 16, the row-distributed
-// power iteration above it.
-template <int P, bool MFMA = (P <= 16)> struct Solver;
-#ifndef DN_SOLVER_DPP
-#define DN_SOLVER_DPP 1          // 1: top_eig_dpp (round 4), 0: top_eig_mfma (rounds 1-3)
-#endif
+// One interface over the two solvers: top_eig_dpp with its carried state for p <= 16, the row-distributed power iteration
+// above it.
+template <int P, bool DPP = (P <= 16)> struct Solver;
 template <int P> struct Solver<P, true> {
-#if DN_SOLVER_DPP
     EigStateD<P> st;
     // component i of the iterate sits in lane i (of every 16-lane row)
     __device__ __forceinline__ double iterate_of_row() const { return st.vl; }
     static __device__ __forceinline__ int row_of_lane() { return lane_id() & 15; }
     static __device__ __forceinline__ double bcast_component(double t, int i) { return bcast_lane<P>(t, i); }
-#else
-    EigState<P> st;
-#endif
     __device__ __forceinline__ void cold(double tr, double (&u)[P]) { (void) u; eig_state_cold<P>(st, tr); }
     // the next solve starts from the normalised indicator vector of the rows in `rows` (scale and shift stay): solve_by_blocks
     __device__ __forceinline__ void start_from(unsigned long long rows, double (&u)[P])
     {
         (void) u;
         const double u0 = 1.0 / sqrt((double) __builtin_popcountll(rows));
-#if DN_SOLVER_DPP
         st.vl = ((rows >> (lane_id() & 15)) & 1ull) ? u0 : 0.0;
         st.k0 = 0; st.rho2 = 1.0; st.q = 1.0; st.age = 0;    // nothing is known about this start: look after every step
-#else
-        const int q = lane_id() >> 4;
-#pragma unroll
-        for (int kb = 0; kb < EigState<P>::KB; kb++) st.v[kb] = ((rows >> (q + 4 * kb)) & 1ull) ? u0 : 0.0;
-#endif
     }
     // the shift of the carried state is taken from the top block's eigenvalue: mu < theta / 2 keeps the TOP of the matrix on top,
     // but inside another block it can put the bottom of that block's spectrum on top -- block-by-block solves run unshifted
@@ -1032,19 +867,14 @@ template <int P> struct Solver<P, true> {
     __device__ __forceinline__ double shift() const { return st.mu; }
     __device__ __forceinline__ double scale() const { return st.sc; }
     static constexpr bool SHIFTED = true;
-    static constexpr bool SQUARE = DN_SOLVER_DPP != 0;                  // takes the scaled square copy of the matrix
+    static constexpr bool SQUARE = true;                                // takes the scaled square copy of the matrix
     // cold: the first solve of an nmf() call (it may set what the call's warm solves keep: shift, scale)
     // sq: the matrix once more as the scaled square copy a block_sum_lds<..., SQ> left (Smem::sq), or null
     template <bool SQ = false>
     __device__ __forceinline__ int run(const double *tot, int zslot, double (&u)[P], double &theta, bool exact, int maxs, bool cold = false,
                                        const double *sq = nullptr)
     {
-#if DN_SOLVER_DPP
         return top_eig_dpp<P, false, SQ>(tot, zslot, u, theta, st, exact, cold, maxs, nullptr, sq);
-#else
-        (void) cold; (void) sq;
-        return top_eig_mfma<P>(tot, zslot, u, theta, st, exact, maxs);
-#endif
     }
 };
 template <int P> struct Solver<P, false> {
@@ -1233,7 +1063,7 @@ struct GeneState {
     double rho_fb[P];    // DI of max(K_start E_start, F_start)                   nmf.py:345-346, :352-353
     double sig0;         // sigma of the first call
     double inv[P];       // 1 / scale factors
-    double scl[P];       // the scale factors again (1 / inv): u_i s_i of the raw-unit pass (DN_RAW_UNITS)
+    double scl[P];       // the scale factors again (1 / inv): u_i s_i of the raw-unit pass (raw_units)
     double u[P];         // outputs of the last nmf() call: top left singular vector,
     double theta;        //   sigma^2,
     double sums[2 * P + 1];   // { sum_j s_j, clamped row sums (P), row sums of Fb (P) }
@@ -1274,7 +1104,7 @@ typedef double __attribute__((address_space(1))) *gdouble_ptr;
 template <int P>
 __device__ __forceinline__ void col_update(const double (&f)[P], double (&a)[P], const double (&u)[P], const double (&ur)[P], double c)
 {
-    // u: the coefficients of the dot product, ur: those of the residual -- the same vector, except in raw count units (DN_RAW_UNITS:
+    // u: the coefficients of the dot product, ur: those of the residual -- the same vector, except in raw count units (raw_units:
     // u_i / s_i and u_i s_i)
     double s0 = 0.0, s1 = 0.0;
 #pragma unroll
@@ -1379,7 +1209,7 @@ __device__ __forceinline__ void load_f(gF_cptr Fb, int k, const double (&inv)[P]
     for (int i = 0; i < P; i++) f[i] = (double) x[i] * inv[i];
 }
 
-// the counts of a column as the pass wants them: scaled (x / s_i), or left raw when the state is kept in raw units (DN_RAW_UNITS)
+// the counts of a column as the pass wants them: scaled (x / s_i), or left raw when the state is kept in raw units (raw_units)
 template <int P, bool RAW>
 __device__ __forceinline__ void pass_counts(const float (&x)[P], const double (&inv)[P], double (&f)[P])
 {
@@ -1617,14 +1447,7 @@ __device__ __forceinline__ int mg_core(gF_cptr Fb, gdouble_ptr Lg, double *lam, 
 #define DN_RT_MIN_P 2            // round 3: the tier (and with it the pair class) serves every p <= 12.  Round 2 stopped at 8 ("below it a
 #endif                           // workgroup needs so few registers that several share a SIMD") -- measured on config-2-shaped genes: p = 3
                                  // +31 %, 4 +7 %, 5 +31 %, 6 +26 %, 7 +47 % genes/s (tools/p_sweep.py, profiles/round3/p_sweep.txt)
-// DN_RAW_UNITS: inside the T loop of the register-tier cohorts the state is kept in RAW count units (a~ = x + lambda / s_i instead
-// of x / s_i + lambda): the counts need no scaling multiply per element and pass (-10 of the 171 vector instructions of a
-// register-tier column at p = 10); u is handed to the pass as u_i / s_i (dot product) and u_i s_i (residual), the Gram matrix is
-// accumulated in raw units and scaled entry by entry as the block total is written (block_sum_lds), so the solver sees what it saw
-#ifndef DN_RAW_UNITS
-#define DN_RAW_UNITS 1
-#endif
-#if defined(DN_P) && DN_P >= DN_RT_MIN_P && DN_P <= DN_RT_MAX_P && !defined(DN_NO_REG_TIER)
+#if defined(DN_P) && DN_P >= DN_RT_MIN_P && DN_P <= DN_RT_MAX_P
 #define DN_REG_TIER 1
 #define DN_KERNEL_WAVES 2        // the register ALLOCATOR's budget: 512 / 2 registers (the kernel really runs one wave per SIMD)
 // The caller's view: nmf_call() visibly uses no AGPR (it must not name one in a constraint or clobber: a function that
@@ -1639,18 +1462,13 @@ __device__ __forceinline__ int mg_core(gF_cptr Fb, gdouble_ptr Lg, double *lam, 
 #define DN_KERNEL_WAVES 1
 #define DN_RT_CLAIM()
 #endif
-#ifndef DN_RAW_MAX_P
-#if DN_SOLVER_DPP
-#define DN_RAW_MAX_P 12          // every register-tier cohort (round 4)
-#else
-#define DN_RAW_MAX_P 11          // with the squaring solver of rounds 1-3 (DN_SOLVER_DPP=0) p = 12 stays in scaled units: its raw-unit pair build
-                                 // failed the edge-shape parity test on genes that fill the register tier -- the two coefficient sets of the pass
-                                 // came out wrong when they were scaled in that solver's iterate layout (lane group q holds v[q + 4 kb], 3 registers
-                                 // at p = 12 with NO padding lane) and broadcast from there; with top_eig_dpp the iterate is one register, component i
-                                 // in lane i, the same two multiplies and readlanes pass (tests: pair class and edge shapes, p = 2 .. 12, tier-filling genes)
-#endif
-#endif
-template <int P> constexpr bool raw_units() { return DN_RAW_UNITS != 0 && DN_REG_TIER != 0 && P <= DN_RAW_MAX_P && P < DN_MG_MIN_P; }
+// The raw-unit pass: inside the T loop of the register-tier cohorts the state is kept in RAW count units (a~ = x + lambda / s_i
+// instead of x / s_i + lambda): the counts need no scaling multiply per element and pass (-10 of the 171 vector instructions of a
+// register-tier column at p = 10); u is handed to the pass as u_i / s_i (dot product) and u_i s_i (residual), the Gram matrix is
+// accumulated in raw units and scaled entry by entry as the block total is written (block_sum_lds), so the solver sees the matrix
+// of scaled units.
+#define DN_RAW_MAX_P 12          // every register-tier cohort (p = 12 in raw count units)
+template <int P> constexpr bool raw_units() { return DN_REG_TIER != 0 && P <= DN_RAW_MAX_P && P < DN_MG_MIN_P; }
 
 // agpr_get1<N>() / agpr_put1<N>(v): the 32-bit value held in aN.  Register names must be literal text, hence the list.
 template <int IDX> __device__ __forceinline__ int agpr_get1();
@@ -1817,7 +1635,7 @@ __device__ __forceinline__ void nmf_body(const float *Fb_, double *Lg_, double *
     constexpr int RT = DN_REG_TIER ? rt_cols<P, X16>() : 0;   // columns per lane held in AGPRs (register tier)
     constexpr int CS = rt_col_regs<P, X16>();              // registers per column: the state, and with X16 the packed raw counts
     constexpr int NR = RT * NT;                            // the gene's first NR columns
-    constexpr bool RAW = raw_units<P>();                   // the state of the T loop in raw count units (DN_RAW_UNITS)
+    constexpr bool RAW = raw_units<P>();                   // the state of the T loop in raw count units
     double ud[P], ur[P];                                   // u as the pass takes it: dot-product and residual coefficients (col_update)
     const int nLe = (n < NR + nL) ? n : NR + nL;           // end of the LDS tier (absolute column); LDS slot of column k: k - NR
     const int kS0 = NR + nL;                               // first column of the spill tier
@@ -1880,33 +1698,13 @@ __device__ __forceinline__ void nmf_body(const float *Fb_, double *Lg_, double *
     }
     const double c = 1.0 / sqrt((double) T);                         // nmf.py:91
     // u for the pass, in scalar registers (two-VGPR-source FMAs).  Raw units: u_i / s_i and u_i s_i, scaled per lane in the solver's
-    // iterate layout (lane group q holds v[q + 4 kb]) and broadcast from there
+    // iterate layout (component i in lane i) and broadcast from there
     auto pass_u = [&]() {
         if constexpr (RAW) {
-#if DN_SOLVER_DPP
             const int k = Solver<P>::row_of_lane() < P ? Solver<P>::row_of_lane() : P - 1;
             const double vt = solver.iterate_of_row() * g_gs.inv[k], vh = solver.iterate_of_row() * g_gs.scl[k];
 #pragma unroll
             for (int i = 0; i < P; i++) { ud[i] = Solver<P>::bcast_component(vt, i); ur[i] = Solver<P>::bcast_component(vh, i); }
-#else
-            constexpr int KB = EigState<P>::KB;
-            const int q = lane_id() >> 4;
-            double vt[KB], vh[KB];
-#pragma unroll
-            for (int kb = 0; kb < KB; kb++) {
-                const int k = q + 4 * kb < P ? q + 4 * kb : P - 1;
-                vt[kb] = solver.st.v[kb] * g_gs.inv[k];
-                vh[kb] = solver.st.v[kb] * g_gs.scl[k];
-            }
-#pragma unroll
-            for (int i = 0; i < P; i++) {
-                const double a_ = vt[i >> 2], b_ = vh[i >> 2];
-                ud[i] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(a_), 16 * (i & 3)),
-                                         __builtin_amdgcn_readlane(__double2loint(a_), 16 * (i & 3)));
-                ur[i] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(b_), 16 * (i & 3)),
-                                         __builtin_amdgcn_readlane(__double2loint(b_), 16 * (i & 3)));
-            }
-#endif
         } else {
 #pragma unroll
             for (int i = 0; i < P; i++) { u[i] = uniform(u[i]); ud[i] = u[i]; ur[i] = u[i]; }
@@ -2130,15 +1928,7 @@ __device__ __forceinline__ void nmf_body(const float *Fb_, double *Lg_, double *
     if constexpr (SQ && NT > 64) dn_sync();                 // the loop's last reduction had one barrier: no wave is still reading xw / xw2
     if constexpr (RAW) {
 #pragma unroll
-        for (int i = 0; i < P; i++) {
-#if DN_SOLVER_DPP
-            u[i] = Solver<P>::bcast_component(solver.iterate_of_row(), i);
-#else
-            const double t_ = solver.st.v[i >> 2];
-            u[i] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(t_), 16 * (i & 3)),
-                                    __builtin_amdgcn_readlane(__double2loint(t_), 16 * (i & 3)));
-#endif
-        }
+        for (int i = 0; i < P; i++) u[i] = Solver<P>::bcast_component(solver.iterate_of_row(), i);
     }
     }   // narrow cohorts
 
@@ -2421,9 +2211,6 @@ __global__ __launch_bounds__(NT * DN_UNITS, DN_KERNEL_WAVES) void k_baseline(Ite
                         // with block-by-block solves
                         const int st_call = __builtin_amdgcn_readfirstlane(gs.status);
                         bool unsafe = st_call == ST_NO_CONVERGENCE;
-#ifdef DN_FORCE_SAFE                                                        // diagnostic: every call is repeated by the safe path
-                        unsafe = unsafe || st_call == ST_OK;
-#endif
                         if (st_call == ST_OK) {
 #pragma unroll
                             for (int i = 0; i < P; i++)                      // a sample WITHOUT coverage in the active columns has u_i = 0 by right

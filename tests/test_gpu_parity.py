@@ -618,9 +618,9 @@ def test_one_very_long_gene_vs_oracle(device, oracle):
 
 def test_eigen_solver_hard_spectra_vs_oracle(device, oracle):
     """
-    Gram matrices the on-chip eigen-solver (MFMA squaring, csrc/dn_kernels.hpp top_eig_mfma) finds hard or unusual:
-    two sample groups with nearly equal energy on disjoint halves of the transcript (sigma_2 / sigma_1 close to 1, many
-    squaring steps), two identical samples (a zero eigenvalue), one dominant sample (huge dynamic range inside the
+    Gram matrices the on-chip eigen-solver (warm-started shifted power iteration, csrc/dn_kernels.hpp top_eig_dpp) finds hard
+    or unusual: two sample groups with nearly equal energy on disjoint halves of the transcript (sigma_2 / sigma_1 close to 1,
+    many power steps), two identical samples (a zero eigenvalue), one dominant sample (huge dynamic range inside the
     Gram matrix), very deep coverage (entries ~1e13) and very shallow coverage.  The oracle solves the same matrices
     with Jacobi rotations.
     """

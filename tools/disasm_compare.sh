@@ -1,16 +1,17 @@
 #!/bin/bash
 # usage: tools/disasm_compare.sh OLD_OBJ_DIR NEW_OBJ_DIR
-# Diffs the gfx950 disassembly (llvm-objdump -d of the code object in each unit's .hip_fatbin) of the float32 kernel units --
-# dn_inst_p*_nt*.o, dn_inst_p*_pair.o, dn_generic_nt256.o, dn_generic_nt64.o -- of two builds (e.g. a copy of
-# degnorm_amd/csrc/obj from the parent commit and the current one).  Prints "DIFF: <unit>" per unit that changed and the number
-# compared; exit status 1 if any changed.  No GPU needed.
+# Diffs the gfx950 disassembly (llvm-objdump -d of the code object in each unit's .hip_fatbin) of every object of two builds
+# that carries device code (e.g. a copy of degnorm_amd/csrc/obj from the parent commit and the current one); objects without a
+# .hip_fatbin section are skipped.  Prints "DIFF: <unit>" per unit that changed and the number compared; exit status 1 if any
+# changed.  No GPU needed.
 set -u
 B=${ROCM_PATH:-/opt/rocm}/llvm/bin
 W=$(mktemp -d)
 trap 'rm -rf "$W"' EXIT
 rc=0; n=0
-for o in "$1"/dn_inst_p*_nt*.o "$1"/dn_inst_p*_pair.o "$1"/dn_generic_nt256.o "$1"/dn_generic_nt64.o; do
+for o in "$1"/*.o; do
   f=$(basename "$o")
+  "$B/llvm-objdump" --section-headers "$o" | grep -q '\.hip_fatbin' || continue
   for side in old new; do
     src=$([ $side = old ] && echo "$1/$f" || echo "$2/$f")
     "$B/llvm-objcopy" --dump-section=.hip_fatbin="$W/$side.fatbin" "$src" &&

@@ -1,6 +1,6 @@
 """
-A/B of the hot loop's eigen-solvers on the Gram-matrix sequences of real nmf() calls (config-2 genes): cycles per warm solve at one
-wave per SIMD, steps, and the distance of every returned eigenvector from numpy's eigh.  GPU box:
+The hot loop's eigen-solver (top_eig_dpp) on the Gram-matrix sequences of real nmf() calls (config-2 genes): cycles per warm solve
+at one wave per SIMD, steps, cycles per phase, and the distance of every returned eigenvector from numpy's eigh.  GPU box:
     python tools/ubench/solver_ab.py [n_genes]          (builds tools/ubench/libsolver_ab.so if missing)
 """
 import ctypes, os, subprocess, sys
@@ -45,8 +45,8 @@ def main():
     n_genes = int(sys.argv[1]) if len(sys.argv) > 1 else 12
     lib = ctypes.CDLL(build())
     cfg = synth.CONFIGS['c2']
-    tot = np.zeros(9); k = 0
-    worst = np.zeros(2)
+    tot = np.zeros(7); k = 0
+    worst = 0.0
     for g in range(n_genes):
         cov, cls = synth.synth_gene(cfg['seed'], g, P, 200, 5000)
         x = cov[:, cov.max(0) > 0.1 * cov.max()].astype(np.float64)
@@ -54,18 +54,17 @@ def main():
             continue
         Gs, us = gram_sequence(x)
         Gs = np.ascontiguousarray(Gs)
-        uo = np.zeros((2, T + 1, P + 1)); res = np.zeros(9)
+        uo = np.zeros((T + 1, P + 1)); res = np.zeros(7)
         rc = lib.solver_ab(Gs.ctypes.data_as(ctypes.c_void_p), T + 1, uo.ctypes.data_as(ctypes.c_void_p), res.ctypes.data_as(ctypes.c_void_p))
         assert rc == 0
-        err = [np.abs(np.abs(uo[v, :, :P]) - np.abs(us[:, :P])).max() for v in range(2)]
-        th = [abs(uo[v, -1, P] / us[-1, P] - 1.0) for v in range(2)]
-        print('gene %3d class %d n %4d | mfma %6.0f cycles %5.2f steps err %.1e theta %.1e | dpp %6.0f cycles %5.2f steps err %.1e theta %.1e'
-              % (g, cls, x.shape[1], res[0], res[1], err[0], th[0], res[2], res[3], err[1], th[1]), flush=True)
+        err = np.abs(np.abs(uo[:, :P]) - np.abs(us[:, :P])).max()
+        th = abs(uo[-1, P] / us[-1, P] - 1.0)
+        print('gene %3d class %d n %4d | %6.0f cycles %5.2f steps err %.1e theta %.1e'
+              % (g, cls, x.shape[1], res[0], res[1], err, th), flush=True)
         tot += res; k += 1
-        worst = np.maximum(worst, err)
-    print('mean over %d genes: mfma %.0f cycles per warm solve, dpp %.0f cycles (%.2f steps); worst |u - eigh| mfma %.1e dpp %.1e'
-          % (k, tot[0] / k, tot[2] / k, tot[3] / k, worst[0], worst[1]))
-    print('dpp phases (cycles per solve): load %.0f, blind steps %.0f, first normalisation %.0f, looks %.0f, epilogue %.0f' % tuple(tot[4:] / k))
+        worst = max(worst, err)
+    print('mean over %d genes: %.0f cycles per warm solve (%.2f steps); worst |u - eigh| %.1e' % (k, tot[0] / k, tot[1] / k, worst))
+    print('phases (cycles per solve): load %.0f, blind steps %.0f, first normalisation %.0f, looks %.0f, epilogue %.0f' % tuple(tot[2:] / k))
 
 
 if __name__ == '__main__':
