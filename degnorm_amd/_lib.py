@@ -103,6 +103,12 @@ def load(build_if_missing=False):
     lib.dn_assemble_coverage.argtypes = [c.c_int, i64, i32, P(i64), P(vp), P(vp), i64, P(i64), i64, P(i32), P(i64), P(i64), P(i32),
                                          P(c.c_float), P(dbl)]
     lib.dn_assemble_last_error.restype = c.c_char_p
+    u8 = c.c_uint8
+    lib.dn_read_coverage.argtypes = [c.c_int, i32, i64, P(i64), P(i64), P(u8), P(i32), i64, i64, i64, i64, i64, P(i64),
+                                     i64, P(i64), P(i32), P(i32), P(i64), P(i64), P(i32), P(i64), i64, P(i64), P(i32),
+                                     i64, P(i64), i64, P(i64), P(i64), i64, P(i64), P(i32), P(i64), P(i64), P(dbl)]
+    lib.dn_reads_cigar_bounds.argtypes = [c.c_int, i64, P(i64), P(i64), P(u8), i32, P(i32), P(i64), P(i64)]
+    lib.dn_reads_last_error.restype = c.c_char_p
     lib.dn_outer_partials_device.argtypes = [vp, P(vp)]
     lib.dn_comm_unique_id.argtypes = [P(c.c_uint8)]
     lib.dn_comm_create.argtypes = [vp, P(c.c_uint8), i32, i32]

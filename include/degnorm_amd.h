@@ -220,6 +220,49 @@ int  dn_assemble_coverage(int device, int64_t chrom_len, int32_t p, const int64_
                           float *out_packed, double *device_ms);
 const char *dn_assemble_last_error(void);
 
+/* Reads -> coverage and read counts (one sample, one chromosome) -------------------------------------
+ * Replaces: the per-read loop of BamReadsProcessor.chromosome_coverage_read_counts (reads.py:397-774): CIGAR parsing
+ * (cigar_segment_bounds, :9-66; end_pos :404-405), the position pre-filter (:410-413), the pair filter (:417-420), the
+ * mate clipping (:459-470), the exon-union filter (:423-516), the overlap-group stage (:545-644) and the isolated-gene
+ * stage (:669-786).  Positions are the reference's 0-based read positions; every interval below is closed [lo, hi],
+ * given as flat (lo, hi) pairs sorted by lo.
+ *   reads     n_rows rows in the caller's order: pos, CIGAR bytes cigar[cigar_off[r] .. cigar_off[r+1]) (ASCII), and when
+ *             paired the pair id of every row (0 .. n_pair_ids-1, the qname without its mate suffix); pairs are the
+ *             consecutive rows left after the pre-filter keep_lo <= pos, end_pos <= keep_hi and the two-rows-per-id rule.
+ *   exon_iv   the merged union of all exons (0-based [start-1, end-1]; touching exons merged).
+ *   groups    n_groups overlap groups, disjoint spans group_iv ([min gene_start-1, max gene_end-1]); the genes of group g are
+ *             entries group_gene_off[g] .. group_gene_off[g+1] of the ol_* arrays: ol_gene (index into counts),
+ *             ol_gene_start0 (gene_start-1), their exon bounds ol_exon_bounds[ol_exon_off[q] ..] as (start-1, end) pairs of
+ *             separately sorted starts and ends (:575), and their span vectors at ol_cov_off[q] .. ol_cov_off[q+1]-1 of
+ *             ol_cov (gene_end - gene_start + 1 values, then one pad slot).
+ *   isolated  n_iso disjoint gene spans iso_iv ([gene_start-1, gene_end-1]) with their count indices iso_gene, and the
+ *             merged union of those spans iso_union.
+ * Outputs: counts[n_genes] (read counts), ol_cov (the span vectors, before the projection onto exon positions of :644),
+ * the chromosome coverage as CSR nonzeros (*nnz positions csr_idx ascending, values csr_val; at most csr_cap: the length
+ * of the exon union bounds it), *n_isolated_reads (0: the reference writes no chrom_coverage file, :711) and device_ms
+ * (nullable).  A kept row whose CIGAR has no M op returns DN_E_INVALID (the reference's ValueError, :63-64); one with more
+ * than DN_READS_MAX_SEG M ops returns DN_E_UNSUPPORTED.  A pair whose clipped mate-2 bounds reach below position 0 is dropped
+ * (the reference indexes from the vector's end there).  Results are bit-identical from run to run.  Text of the last error:
+ * dn_reads_last_error(). */
+#define DN_READS_MAX_SEG      32  /* match segments (M ops) per row                                                   */
+int  dn_read_coverage(int device, int32_t paired, int64_t n_rows, const int64_t *pos, const int64_t *cigar_off,
+                      const uint8_t *cigar, const int32_t *pair_id, int64_t n_pair_ids,
+                      int64_t chrom_len, int64_t keep_lo, int64_t keep_hi,
+                      int64_t n_exon, const int64_t *exon_iv,
+                      int64_t n_groups, const int64_t *group_iv, const int32_t *group_gene_off,
+                      const int32_t *ol_gene, const int64_t *ol_gene_start0, const int64_t *ol_cov_off,
+                      const int32_t *ol_exon_off, const int64_t *ol_exon_bounds,
+                      int64_t n_iso, const int64_t *iso_iv, const int32_t *iso_gene,
+                      int64_t n_iso_union, const int64_t *iso_union,
+                      int64_t n_genes, int64_t *counts, int64_t *ol_cov,
+                      int64_t csr_cap, int64_t *nnz, int32_t *csr_idx, int64_t *csr_val,
+                      int64_t *n_isolated_reads, double *device_ms);
+/* Debug view of the device CIGAR parser (cigar_segment_bounds, :9-66): per row nseg[r] match segments (0: no M op, -1: more
+ * than max_seg) as bounds[r * 2 * max_seg ..] (start, end inclusive), and end_pos[r] = pos + sum of all op lengths (:404). */
+int  dn_reads_cigar_bounds(int device, int64_t n, const int64_t *pos, const int64_t *cigar_off, const uint8_t *cigar,
+                           int32_t max_seg, int32_t *nseg, int64_t *bounds, int64_t *end_pos);
+const char *dn_reads_last_error(void);
+
 /* Measurement hooks (bench.py) -------------------------------------------------------------------- */
 /* Device time in ms of the most recent dn_baseline_iteration's main kernel, measured with HIP events
  * on the library's own stream; kernel name via dn_main_kernel_name().                               */

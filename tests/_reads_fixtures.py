@@ -1,0 +1,272 @@
+"""
+Synthetic chromosomes and reads for the reads -> coverage / read counts path (test tooling, not product code).
+
+`golden_layout` is the hand-built annotation of the golden cases (tests/golden/make_golden_reads.py runs the reference on
+it): two overlap groups (one holding a gene with a nested exon), a chain of three overlapping genes, isolated genes that
+touch, and a gene no read lands on.  `synth_reads` / `synth_pairs` draw reads over it with every CIGAR op.  `scale_case`
+and `restate_single_end` are the 20 Mb / 2 M-read case of the GPU scale test and its numpy restatement of the reference's
+rules (reads.py:404-786) for reads of the forms `aM` and `aMnNbM`.
+"""
+import numpy as np
+import pandas as pd
+
+from degnorm_amd.gene_processing import get_gene_overlap_structure
+
+OPS = 'MIDNSHP=X'
+
+
+def tables(chrom, genes):
+    """genes: [(name, [(exon start, exon end), ...]), ...] 1-based inclusive -> (gene_df, exon_df) in the reference's layout."""
+    ex = pd.DataFrame([(chrom, g, a, b) for g, exons in genes for a, b in exons], columns=['chr', 'gene', 'start', 'end'])
+    gdf = ex.groupby(['chr', 'gene'], sort=False).agg(gene_start=('start', 'min'), gene_end=('end', 'max')).reset_index()
+    return gdf, ex.merge(gdf, on=['chr', 'gene'])
+
+
+def golden_layout():
+    genes = [('A', [(101, 300), (501, 900)]),
+             ('B', [(251, 350), (601, 700)]),
+             ('C', [(851, 1000), (1101, 1200)]),                       # A - B, A - C: a chain through A
+             ('D', [(2001, 2600), (2101, 2300), (2701, 2800)]),        # nested exon: sorted starts / ends pair up differently
+             ('E', [(2501, 2650), (2901, 3000)]),
+             ('F', [(3201, 3350), (3451, 3600)]),
+             ('G', [(3601, 3900)]),                                    # touches F: isolated, not overlapping
+             ('H', [(4001, 4100), (4301, 4400)]),
+             ('I', [(5001, 5200)])]                                    # no reads
+    return 'chr1', 6000, genes
+
+
+def quiet_layout():
+    """A chromosome whose isolated stage gets no read: reads only inside the overlap group."""
+    genes = [('P', [(101, 400)]), ('Q', [(301, 600)]), ('R', [(1001, 1300)])]
+    return 'chr2', 2000, genes
+
+
+def random_cigar(rng, n_ops=None, need_m=True):
+    n_ops = n_ops or int(rng.integers(1, 8))
+    ops = [OPS[int(rng.integers(0, len(OPS)))] for _ in range(n_ops)]
+    if need_m and 'M' not in ops:
+        ops[int(rng.integers(0, n_ops))] = 'M'
+    return ''.join('{0}{1}'.format(int(rng.integers(1, 60)), o) for o in ops)
+
+
+def _exon_read(rng, genes):
+    """A read whose CIGAR advances like the reference's parser expects: clips / indels / splices over the gene's exons."""
+    name, exons = genes[int(rng.integers(0, len(genes)))]
+    k = int(rng.integers(0, len(exons)))
+    a, b = exons[k]
+    kind = int(rng.integers(0, 6))
+    if kind == 0 and k + 1 < len(exons):                 # spliced across to the next exon
+        s = int(rng.integers(max(a - 1, b - 40), b))
+        m1 = b - s
+        n = exons[k + 1][0] - 1 - s - m1
+        if n >= 1:
+            return s, '{0}M{1}N{2}M'.format(m1, n, int(rng.integers(5, 40)))
+    if kind == 1:                                        # starting on the gene's first base
+        s = exons[0][0] - 1
+        return s, '{0}M'.format(int(rng.integers(5, 50)))
+    s = int(rng.integers(a - 1, max(a, b - 20)))
+    if kind == 2:
+        return s, '{0}S{1}M{2}I{3}M'.format(int(rng.integers(1, 5)), int(rng.integers(5, 20)), int(rng.integers(1, 3)),
+                                           int(rng.integers(5, 20)))
+    if kind == 3:
+        return s, '{0}M{1}D{2}M{3}H'.format(int(rng.integers(5, 20)), int(rng.integers(1, 4)), int(rng.integers(5, 20)),
+                                           int(rng.integers(1, 5)))
+    if kind == 4:
+        return s, '{0}={1}X{2}M{3}P{4}M'.format(int(rng.integers(1, 5)), int(rng.integers(1, 3)), int(rng.integers(5, 20)),
+                                               int(rng.integers(1, 3)), int(rng.integers(3, 10)))
+    return s, '{0}M'.format(int(rng.integers(10, 80)))
+
+
+def synth_reads(seed, layout, n, skip=('I',), noise=0.15):
+    """Single-end reads: DataFrame(qname, pos, cigar), mostly on exons, some anywhere (random CIGARs)."""
+    chrom, chrom_len, genes = layout
+    rng = np.random.default_rng(seed)
+    src = [g for g in genes if g[0] not in skip]
+    rows = []
+    for i in range(n):
+        if rng.random() < noise:
+            rows.append(('q{0}'.format(i), int(rng.integers(0, chrom_len - 400)), random_cigar(rng)))
+        else:
+            s, c = _exon_read(rng, src)
+            rows.append(('q{0}'.format(i), s, c))
+    return pd.DataFrame(rows, columns=['qname', 'pos', 'cigar'])
+
+
+def synth_pairs(seed, layout, n_pairs, skip=('I',)):
+    """
+    Paired reads: consecutive rows per pair (mate order sometimes swapped), mates that overlap, contain each other or are
+    spliced, and a few orphans (one mate only) -- DataFrame(qname, pos, cigar, qname_unpaired).
+    """
+    chrom, chrom_len, genes = layout
+    rng = np.random.default_rng(seed)
+    src = [g for g in genes if g[0] not in skip]
+    rows = []
+    for i in range(n_pairs):
+        q = 'p{0}'.format(i)
+        s1, c1 = _exon_read(rng, src)
+        kind = int(rng.integers(0, 4))
+        if kind == 0:                                    # mate 2 inside mate 1 (or the other way round)
+            s2, c2 = s1 + int(rng.integers(0, 5)), '{0}M'.format(int(rng.integers(3, 10)))
+        elif kind == 1:                                  # mate 2 to the left
+            s2, c2 = max(0, s1 - int(rng.integers(5, 60))), '{0}M'.format(int(rng.integers(10, 60)))
+        elif kind == 2:                                  # anywhere on the exons
+            s2, c2 = _exon_read(rng, src)
+        else:
+            s2, c2 = s1 + int(rng.integers(0, 80)), random_cigar(rng) if rng.random() < 0.3 else '{0}M'.format(int(rng.integers(10, 60)))
+        mates = [(q + '.1', s1, c1, q), (q + '.2', s2, c2, q)]
+        if rng.random() < 0.2:
+            mates.reverse()
+        if rng.random() < 0.04:                          # orphan
+            mates = mates[:1]
+        rows += mates
+    return pd.DataFrame(rows, columns=['qname', 'pos', 'cigar', 'qname_unpaired'])
+
+
+def fuzz_cigars(seed, n):
+    """Random CIGAR strings over every op (a few without an M) with random starts."""
+    rng = np.random.default_rng(seed)
+    cig = [random_cigar(rng, need_m=rng.random() > 0.03) for _ in range(n)]
+    return cig, rng.integers(0, 100000, size=n)
+
+
+# --- the scale case --------------------------------------------------------------------------------------------------------
+
+def scale_case(seed=11, chrom_len=20_000_000, n_genes=2000, n_reads=2_000_000):
+    """
+    A 20 Mb chromosome with n_genes genes of 2-6 exons (about one in six overlapping a neighbour) and n_reads single-end reads
+    of the forms aM and aMnNbM over them.  Returns (reads_df, chrom_len, gene_overlap_dat, gene_df, exon_df).
+    """
+    rng = np.random.default_rng(seed)
+    genes = []
+    step = chrom_len // (n_genes + 1)
+    for g in range(n_genes):
+        base = 1000 + g * step + int(rng.integers(0, step // 4))
+        if g % 6 == 5:                                   # pull this gene onto its predecessor's span
+            base = genes[-1][1][-1][1] - int(rng.integers(200, 1500))
+        ne = int(rng.integers(2, 7))
+        exons, a = [], base
+        for _ in range(ne):
+            ln = int(rng.integers(150, 1200))
+            exons.append((a, a + ln - 1))
+            a += ln + int(rng.integers(100, 3000))
+        genes.append(('g{0:05d}'.format(g), exons))
+    gene_df, exon_df = tables('chrS', genes)
+    ov = get_gene_overlap_structure(gene_df)
+    # reads: pick an exon, then a plain or a spliced read inside it / into the next exon
+    ex_lo = exon_df['start'].values - 1
+    ex_hi = exon_df['end'].values - 1
+    k = rng.integers(0, len(ex_lo), size=n_reads)
+    a = rng.integers(80, 150, size=n_reads)
+    s = ex_lo[k] + (rng.random(n_reads) * np.maximum(ex_hi[k] - ex_lo[k] - 20, 1)).astype(np.int64) - 5
+    s = np.maximum(s, 0)
+    spliced = rng.random(n_reads) < 0.3
+    m1 = rng.integers(10, 70, size=n_reads)
+    nn = rng.integers(50, 3000, size=n_reads)
+    cig = np.where(spliced, np.char.add(np.char.add(np.char.add(np.char.add(m1.astype(str), 'M'), nn.astype(str)), 'N'),
+                                        np.char.add((a - m1).astype(str), 'M')),
+                   np.char.add(a.astype(str), 'M'))
+    reads = pd.DataFrame({'qname': np.arange(n_reads), 'pos': s.astype(np.int64), 'cigar': cig.tolist()})
+    return reads, chrom_len, ov, gene_df, exon_df
+
+
+def _segments_simple(reads_df):
+    """Match segments of aM / aMnNbM reads: (pos, end_pos, seg starts (n, 2), seg ends (n, 2), has second segment)."""
+    cig = reads_df['cigar'].values.astype(str)
+    pos = reads_df['pos'].values.astype(np.int64)
+    two = np.char.find(cig, 'N') >= 0
+    parts = np.char.partition(cig, 'M')
+    m1 = parts[:, 0].astype(np.int64)
+    rest = parts[:, 2]
+    n = np.zeros(len(cig), dtype=np.int64)
+    m2 = np.zeros(len(cig), dtype=np.int64)
+    if two.any():
+        r2 = np.char.partition(rest[two], 'N')
+        n[two] = r2[:, 0].astype(np.int64)
+        m2[two] = np.char.rstrip(r2[:, 2], 'M').astype(np.int64)
+    a = np.stack([pos, pos + m1 + n], axis=1)                 # after M: pos + m1 - 1; the N advances n + 1
+    b = np.stack([pos + m1 - 1, pos + m1 + n + m2 - 1], axis=1)
+    return pos, pos + m1 + n + m2, a, b, two
+
+
+def _inside(lo, hi, x, y):
+    k = np.searchsorted(lo, x, side='right') - 1
+    return (k >= 0) & (y <= hi[np.maximum(k, 0)])
+
+
+def restate_single_end(reads_df, chrom_len, gene_overlap_dat, gene_df, exon_df):
+    """
+    numpy restatement of the reference's single-end computation (reads.py:404-786) for aM / aMnNbM reads:
+    (CSR indices, CSR values, {overlap gene: coverage}, {gene: count}).
+    """
+    pos, end, sa, sb, two = _segments_simple(reads_df)
+    genes = gene_df['gene'].tolist()
+    gi = {g: i for i, g in enumerate(genes)}
+    counts = np.zeros(len(genes), dtype=np.int64)
+    keep = (pos >= gene_df.gene_start.min() - 1) & (end <= gene_df.gene_end.max() - 1)
+    # exon union, touching exons merged
+    lo = np.sort(exon_df['start'].values - 1)
+    hi = exon_df['end'].values[np.argsort(exon_df['start'].values - 1, kind='stable')]
+    hi = np.maximum.accumulate(hi)
+    new = np.r_[True, lo[1:] > hi[:-1]]
+    st = np.flatnonzero(new)
+    u_lo, u_hi = lo[st], hi[np.r_[st[1:], lo.size] - 1] - 1
+    keep &= _inside(u_lo, u_hi, sa[:, 0], sb[:, 0])
+    keep &= ~two | _inside(u_lo, u_hi, sa[:, 1], sb[:, 1])
+    ol_cov = {}
+    g_start = dict(zip(gene_df.gene, gene_df.gene_start))
+    g_end = dict(zip(gene_df.gene, gene_df.gene_end))
+    ex_by_gene = {g: d for g, d in exon_df.groupby('gene')}
+    for grp in gene_overlap_dat['overlap_genes']:
+        glo, ghi = min(g_start[g] for g in grp) - 1, max(g_end[g] for g in grp) - 1
+        idx = np.flatnonzero(keep & (pos >= glo) & (end <= ghi))
+        caught = np.zeros(idx.size, dtype=np.int64)
+        who = np.full(idx.size, -1)
+        for q, g in enumerate(grp):
+            d = ex_by_gene[g]
+            e0, e1 = np.sort(d.start.values) - 1, np.sort(d.end.values)
+            ok = np.ones(idx.size, dtype=bool)
+            for j in range(2):
+                segin = np.zeros(idx.size, dtype=bool)
+                for x, y in zip(e0, e1):
+                    segin |= (sa[idx, j] >= x) & (sb[idx, j] <= y)
+                ok &= segin | (~two[idx] if j == 1 else False)
+            caught += ok
+            who[ok] = q
+        for q, g in enumerate(grp):
+            d = ex_by_gene[g]
+            gs0, ge0 = int(d.gene_start.iloc[0]) - 1, int(d.gene_end.iloc[0]) - 1
+            L = ge0 - gs0 + 1
+            sel = idx[(caught == 1) & (who == q)]
+            counts[gi[g]] += sel.size
+            cov = np.zeros(L, dtype=np.int64)
+            for j in range(2):
+                m = sel if j == 0 else sel[two[sel]]
+                lo_i, hi_i = sa[m, j] - gs0 - 1, sb[m, j] - gs0 - 1
+                wrap = lo_i < 0
+                np.add.at(cov, np.full(int(wrap.sum()), L - 1), 1)
+                lo_i = np.maximum(lo_i, 0)
+                diff = np.zeros(L + 1, dtype=np.int64)
+                np.add.at(diff, lo_i, 1)
+                np.add.at(diff, hi_i + 1, -1)
+                cov += np.cumsum(diff)[:L]
+            e0, e1 = np.sort(d.start.values) - 1, np.sort(d.end.values)
+            t = np.unique(np.concatenate([np.arange(x, y) for x, y in zip(e0, e1)]))
+            ol_cov[g] = cov[t - gs0]
+        keep[idx[caught != 0]] = False
+    iso = gene_df[gene_df.gene.isin(gene_overlap_dat['isolated_genes'])].sort_values('gene_start')
+    i_lo, i_hi = iso.gene_start.values - 1, iso.gene_end.values - 1
+    acc = np.maximum.accumulate(i_hi)                        # union of the spans, touching ones merged (:685-698)
+    st = np.flatnonzero(np.r_[True, i_lo[1:] > acc[:-1] + 1])
+    keep &= _inside(i_lo[st], acc[np.r_[st[1:], i_lo.size] - 1], pos, end)
+    k = np.searchsorted(i_lo, pos, side='right') - 1
+    keep &= (k >= 0) & (pos <= i_hi[np.maximum(k, 0)])
+    sel = np.flatnonzero(keep)
+    np.add.at(counts, np.array([gi[g] for g in iso.gene.values], dtype=np.int64)[k[sel]], 1)
+    diff = np.zeros(chrom_len + 1, dtype=np.int64)
+    for j in range(2):
+        m = sel if j == 0 else sel[two[sel]]
+        np.add.at(diff, sa[m, j], 1)
+        np.add.at(diff, sb[m, j] + 1, -1)
+    cov = np.cumsum(diff)[:chrom_len]
+    nz = np.flatnonzero(cov)
+    return nz.astype(np.int32), cov[nz], ol_cov, {g: int(c) for g, c in zip(genes, counts)}
