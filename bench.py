@@ -1,7 +1,7 @@
 """
 bench.py -- DegNorm NMF-OA hot path on MI355X.
 
-    python bench.py [--config c2|c4] [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--config c2|c4] [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 With --gpus N > 1 and no WORLD_SIZE in the environment this process is only a LAUNCHER: before touching torch or the GPU it
 starts `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py ...`
@@ -24,14 +24,19 @@ Rank 0 prints ONE JSON line with the driver contract fields plus
   roofline      the dominant kernel against the resource that binds it (c2: fp64 vector issue, with the measured
                 one-wave issue ceiling as a second peak and SURVEY 8(d)'s algorithmic bytes/s as a named secondary
                 figure; c4: HBM bytes of the initial pass + the latency bound of the iteration kernel), `traffic` from the
-                committed rocprofv3 PMC passes of THIS source tree (refused when the sources differ from the profiled ones),
+                committed rocprofv3 PMC passes of THIS source tree (refused when the sources differ from the profiled ones);
+                all of it from the timed steps' own events and counters, except the stream-read ceiling (--full).
+
+A plain run stops there: set-up, warm-up, the timed steps, --dump-outputs, the line.  With --full the line also carries what
+takes runs of its own after the clock stops (and the stream-read ceiling, measured before it):
   parity        after the clock stops: (i) the oracle re-runs a sample of genes with the scale factors each timed outer
                 iteration actually used (kernels alone), (ii) `chain`: the whole run -- initial pass, 5 iterations, device-side
                 outer update -- on the CPU-baseline sample against the oracle's own run, flipped genes counted and measured,
                 (iii) `tie_sensitive`: genes with a column exactly on the 0.1 x max threshold of get_high_coverage_idx,
   end_to_end    GeneNMFOA.fit(cov_dict, reads) on the full float64 coverage dict: pack + H2D, run, estimates, D2H,
   cpu_baseline  the oracle on this box's host cores (all cores, and one thread) on a bounded sample,
-  also          (default run only) config 4 measured in the same process after config 2.
+  also          (default configuration only) config 4 measured in the same process after config 2.
+The timed steps are the same with and without --full: the parity sample's raw device rows are fetched inside them either way.
 
 --dump-outputs DIR writes what the last timed step of the headline configuration handed its caller (fetch_state) as float64 /
 float32 .npy files, rows in global gene order: rho.npy, x_adj.npy, x_weighted.npy (genes x samples), ran_baseline_selection.npy
@@ -569,9 +574,10 @@ def dump_outputs(outputs, path):
 # ---------------------------------------------------------------------------------------------------------------------
 # one configuration on this rank
 # ---------------------------------------------------------------------------------------------------------------------
-def measure(config, args, ctx, steps, warmup, n_parity, n_cpu, n_single, want_e2e, dump_dir=''):
+def measure(config, args, ctx, steps, warmup, n_parity, n_cpu, n_single, want_e2e, dump_dir='', full=True):
     """Generate, upload, time `steps` steps; rank 0 returns the result object (other ranks None).  `dump_dir`: write the outputs
-    of the last timed step there (dump_outputs)."""
+    of the last timed step there (dump_outputs).  `full`: also measure the stream-read ceiling and run the post-clock checks
+    (parity, then cpu_baseline / end_to_end as `n_cpu` / `want_e2e` ask)."""
     import torch
     from degnorm_amd import synth
     from degnorm_amd.nmf_mpi import ShardedNMFOA
@@ -619,7 +625,7 @@ def measure(config, args, ctx, steps, warmup, n_parity, n_cpu, n_single, want_e2
             if ok[0] < world and lib_comm is not None:
                 eng.dev.comm_destroy()
                 eng._lib_comm, lib_comm = False, None
-    keep_packed = rank == 0 and world == 1 and config == 'c2'              # the float64 dict of end_to_end / the tie count are made from it
+    keep_packed = full and rank == 0 and world == 1 and config == 'c2'     # the float64 dict of end_to_end / the tie count are made from it
     if not keep_packed:
         packed = None
 
@@ -657,7 +663,7 @@ def measure(config, args, ctx, steps, warmup, n_parity, n_cpu, n_single, want_e2
     tiny = eng.dev.tiny_length() if split > 0 else 0
     # the measured stream-read ceiling of this device, beside the data sheet's 8 TB/s (a read-only kernel with four
     # 16-byte loads per lane in flight over 1 GiB, best of 5; outside the clock)
-    stream_gbps = eng.dev.measure_read_gbps(1 << 30, 5) if (rank == 0 and eng.n_local > 0) else None
+    stream_gbps = eng.dev.measure_read_gbps(1 << 30, 5) if (full and rank == 0 and eng.n_local > 0) else None
     wide = lengths > split if split > 0 else np.ones(len(lengths), dtype=bool)
     pair = (lengths <= tiny) & ~wide                                    # class 2: one wavefront per gene, two genes per workgroup
     kernel_ms, narrow_ms, pair_ms, all_traces, eng_span = [], [], [], [], []
@@ -702,7 +708,7 @@ def measure(config, args, ctx, steps, warmup, n_parity, n_cpu, n_single, want_e2
                   else 'genes/sec (50k genes x 50 samples, downsample-grid 500, 5 iters)',
         'value': value, 'unit': 'genes/sec', 'n_gpus': world, 'steps': steps, 'warmup': warmup,
         'ms_per_step': dt / steps * 1e3, 'higher_is_better': True, 'scaling': 'strong',
-        'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',
+        'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic', 'full': full,
         'config': {'workload': 'config {0}: {1} synthetic genes x {2} samples, L~U[{3},{4}], {5} DegNorm iters, nmf_iter {6}{7}, '
                                'fp32 coverage in HBM, fp64 arithmetic'
                                .format(2 if config == 'c2' else 4, n_genes, p, cfg['l_min'], cfg['l_max'], args.iters,
@@ -825,7 +831,7 @@ def measure(config, args, ctx, steps, warmup, n_parity, n_cpu, n_single, want_e2
     if args.dump_traces:                                                # per-gene counters of the last step (tools/partition_study.py)
         np.savez_compressed(args.dump_traces + '.' + config, lengths=lengths, gene_ids=np.asarray(my_genes),
                             traces=np.stack([tr[:, :8] for tr in eng.traces]), class_ms=np.asarray(eng.class_ms))
-    out['parity'] = parity_check(eng, pick, cfg, p, my_genes, lengths, split, args.nmf_iter, rate) if pick is not None else None
+    out['parity'] = parity_check(eng, pick, cfg, p, my_genes, lengths, split, args.nmf_iter, rate) if (full and pick is not None) else None
     final_scale = np.copy(eng.scale_factors)
     try:
         eng.dev.close()                                                 # free the shard before the follow-up runs open their own handles
@@ -834,7 +840,7 @@ def measure(config, args, ctx, steps, warmup, n_parity, n_cpu, n_single, want_e2
     if world > 1 and args.sharded_api:
         out['end_to_end_sharded'] = dict(end_to_end_sharded(ctx, cfg, p, n_genes, args, rate),
                                          pieces_of_the_timed_path={'upload_s': t_up, 'step_s': dt / steps})
-    if world == 1 and n_cpu > 0:
+    if full and world == 1 and n_cpu > 0:
         out['cpu_baseline'], ref, covs, rd = cpu_baseline(cfg, config, p, args.nmf_iter, args.iters, rate, n_cpu, n_single)
         if out['parity'] is not None:
             out['parity']['chain'] = chain_parity(ref, covs, rd, args.nmf_iter, args.iters, rate, local_rank)
@@ -927,8 +933,8 @@ def run_rank(args):
     n_cpu = args.cpu_sample if args.cpu_sample >= 0 else (768 if args.config == 'c2' else 2048)
     n_single = args.cpu_single if args.cpu_single >= 0 else (64 if args.config == 'c2' else 512)
     out = measure(args.config, args, ctx, args.steps, args.warmup, args.parity_genes, n_cpu, n_single, not args.no_end_to_end,
-                  dump_dir=args.dump_outputs)
-    if rank == 0 and world == 1 and args.config == 'c2' and not args.no_also and args.genes <= 0:
+                  dump_dir=args.dump_outputs, full=args.full)
+    if args.full and rank == 0 and world == 1 and args.config == 'c2' and not args.no_also and args.genes <= 0:
         # BASELINE configs[3] in the same process, after the config-2 clock has stopped (its own generation, upload, warm-up, clock)
         sub = measure('c4', args, ctx, 3, 2, args.parity_genes, 2048 if n_cpu > 0 else 0, 512 if n_single > 0 else 0, False)
         out['also'] = {'config 4': {k: sub[k] for k in ('metric', 'value', 'unit', 'steps', 'warmup', 'ms_per_step', 'config', 'roofline',
@@ -952,11 +958,15 @@ def parse(argv=None):
     ap.add_argument('--genes', type=int, default=0, help='total genes (default: the configuration\'s: 20000 / 50000)')
     ap.add_argument('--iters', type=int, default=5, help='outer DegNorm iterations per step')
     ap.add_argument('--nmf-iter', type=int, default=100)
-    ap.add_argument('--cpu-sample', type=int, default=-1, help='genes in the CPU-baseline sample (0 = skip; default 768 / 2048)')
-    ap.add_argument('--cpu-single', type=int, default=-1, help='genes of that sample also run on ONE thread (0 = skip; default 64 / 512)')
-    ap.add_argument('--parity-genes', type=int, default=160, help='genes in the post-clock parity sample (0 = skip)')
-    ap.add_argument('--no-end-to-end', action='store_true', help='skip the GeneNMFOA.fit() end-to-end timing (config 2, N = 1)')
-    ap.add_argument('--no-also', action='store_true', help='skip the config-4 measurement appended to the default config-2 line')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check what takes runs of its own: the stream-read ceiling, the post-clock parity checks, '
+                         'the CPU baseline, the GeneNMFOA.fit() end-to-end timing and (default configuration) config 4')
+    ap.add_argument('--cpu-sample', type=int, default=-1, help='--full: genes in the CPU-baseline sample (0 = skip; default 768 / 2048)')
+    ap.add_argument('--cpu-single', type=int, default=-1, help='--full: genes of that sample also run on ONE thread (0 = skip; default 64 / 512)')
+    ap.add_argument('--parity-genes', type=int, default=160,
+                    help='genes in the parity sample: their raw rows are kept in every timed step, checked after the clock with --full (0 = none)')
+    ap.add_argument('--no-end-to-end', action='store_true', help='--full: skip the GeneNMFOA.fit() end-to-end timing (config 2, N = 1)')
+    ap.add_argument('--no-also', action='store_true', help='--full: skip the config-4 measurement appended to the default config-2 line')
     ap.add_argument('--no-rccl', action='store_true', help='N = 1 without torchrun: do not open a one-rank RCCL process group')
     ap.add_argument('--redeal', action='store_true',
                     help='N > 1: before the warm-up, one untimed run re-deals the genes from the measured cost of its first outer iteration')

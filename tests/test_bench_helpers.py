@@ -109,3 +109,9 @@ def test_steps_must_be_positive():
     assert bench.parse(['--steps', '7']).steps == 7
     with pytest.raises(SystemExit):
         bench.parse(['--steps', '0'])
+
+
+def test_full_is_off_by_default():
+    import bench
+    assert bench.parse(['--gpus', '1', '--steps', '3', '--warmup', '2']).full is False
+    assert bench.parse(['--full']).full is True

@@ -1,6 +1,6 @@
 #!/bin/bash
-# Collects the round's judged profiles on the GPU box: kernel stats, the two PMC passes (separately, as the
-# MI355X guide prescribes), the hashes of the kernel sources / library they were taken on, and the plain bench line.
+# Collects the round's judged profiles on an MI355X: kernel stats, the two PMC passes (one counter per run, without other
+# tracing), the hashes of the kernel sources / library they were taken on, and the bench line with --full.
 # Usage: bash tools/profile_round.sh <out-dir-under-gpurun_out> [bench.py arguments, e.g. --config c4]
 set -e
 export TMPDIR=/tmp
@@ -15,5 +15,5 @@ rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/fetch -o run --output-format csv
 echo "fetch done"
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/write -o run --output-format csv -- python3 bench.py $LEAN "$@" > $O/write.log 2>&1
 echo "write done"
-python3 bench.py --no-also "$@" > $O/bench.json 2> $O/bench.err
+python3 bench.py --full --no-also "$@" > $O/bench.json 2> $O/bench.err
 find $O -name "*.csv" | head -20
