@@ -89,6 +89,7 @@ def build_library(force=False, verbose=False):
     hipcc = _hipcc()
     hdr = [os.path.join(CSRC, 'dn_kernels.hpp'), os.path.join(CSRC, 'dn_reduce.hpp'), os.path.join(HERE, '..', 'include', 'degnorm_amd.h'),
            os.path.abspath(__file__)]
+    host_hdr = hdr + [os.path.join(CSRC, 'dn_host.hpp')]     # the host-side units: api, reads, assemble
     jobs = []
     objs = []
     inst = os.path.join(CSRC, 'dn_inst.hip')
@@ -116,12 +117,12 @@ def build_library(force=False, verbose=False):
     asm = os.path.join(CSRC, 'dn_assemble.hip')
     o_asm = os.path.join(OBJ, 'dn_assemble.o')
     objs.append(o_asm)
-    if force or _newer(o_asm, [asm] + hdr):
+    if force or _newer(o_asm, [asm] + host_hdr):
         jobs.append([hipcc] + FLAGS + ['-c', asm, '-o', o_asm])
     rd = os.path.join(CSRC, 'dn_reads.hip')             # reads -> coverage / read counts (BamReadsProcessor, reads.py)
     o_rd = os.path.join(OBJ, 'dn_reads.o')
     objs.append(o_rd)
-    if force or _newer(o_rd, [rd] + hdr):
+    if force or _newer(o_rd, [rd] + host_hdr):
         jobs.append([hipcc] + FLAGS + ['-c', rd, '-o', o_rd])
     api = os.path.join(CSRC, 'dn_api.hip')
     o_api = os.path.join(OBJ, 'dn_api.o')
@@ -131,7 +132,7 @@ def build_library(force=False, verbose=False):
     if not os.path.exists(stamp_file) or open(stamp_file).read() != stamp:      # another compiler or other flags: the C-ABI unit names them
         with open(stamp_file, 'w') as f:
             f.write(stamp)
-    if force or _newer(o_api, [api, stamp_file] + hdr):
+    if force or _newer(o_api, [api, stamp_file] + host_hdr):
         jobs.append([hipcc] + FLAGS + ['-DDN_BUILD_STAMP="{0}"'.format(stamp.replace('"', "'")),
                                        '-DDN_WIDE_NT={0}'.format(WIDE_NT), '-DDN_P_MAX_TEMPLATED={0}'.format(P_LIST[-1]),
                                        '-DDN_P_PAIR(X)=' + ' '.join('X({0})'.format(q) for q in PAIR_P_LIST), '-c', api, '-o', o_api])

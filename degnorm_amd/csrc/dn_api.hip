@@ -1,6 +1,7 @@
 // dn_api.hip -- C ABI (include/degnorm_amd.h) over the kernels of dn_kernels.hpp: device handle, host packer,
 // resident buffers, launches.  Host side only; the kernels are instantiated per sample count in dn_inst.hip.
 #include "dn_kernels.hpp"
+#include "dn_host.hpp"
 #include "../../include/degnorm_amd.h"
 
 #include <dlfcn.h>
@@ -327,18 +328,24 @@ static thread_local std::string g_err;
 
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
 
-#define HIP_TRY(expr)                                                                              \
+// HIP_TRY_AS: the message is `what`, then the HIP error; HIP_TRY names the failed expression
+#define HIP_TRY_AS(what, expr)                                                                     \
     do {                                                                                           \
         hipError_t e_ = (expr);                                                                    \
         if (e_ != hipSuccess)                                                                      \
-            return fail(DN_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));              \
+            return fail(DN_E_HIP, std::string(what) + ": " + hipGetErrorString(e_));              \
     } while (0)
+#define HIP_TRY(expr) HIP_TRY_AS(#expr, expr)
 
 struct dn_handle_s {
     int device = -1;
     int n_cus = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    static constexpr int NCLS = 3;   // gene classes, see GeneClass
+    // one stream and one pair of timing events per gene class; stream[0] is also the handle's stream for everything else
+    // (declared before `data`, so that the buffers are released first)
+    dn::Stream stream[NCLS];
+    dn::Event ev_start[NCLS], ev_end[NCLS];
+    dn::Event ev_ready, ev_i0, ev_i1;
     const dn::KernelSet *ks = nullptr;
 
     int64_t n = 0;
@@ -349,45 +356,20 @@ struct dn_handle_s {
     std::vector<int32_t> glen;
     std::vector<int64_t> svoff;   // n + 1, in columns
 
-    float   *d_cov = nullptr;
-    int64_t *d_goff = nullptr;
-    int32_t *d_glen = nullptr;
-    int32_t *d_order = nullptr;
-    int32_t *d_counter = nullptr;
-    int64_t *d_ds = nullptr;
-    char    *d_ws = nullptr;          // alias of cls[0].d_ws
-    double  *d_rho = nullptr;
-    int32_t *d_flags = nullptr;
-    int32_t *d_trace = nullptr;
-    double  *d_kfin = nullptr;
-    int32_t *d_emode = nullptr;
-    double  *d_svec = nullptr;
-    int64_t *d_svoff = nullptr;
-    float   *d_rowmax = nullptr;      // n x p row maxima of the raw coverage (k_row_max at upload)
-    int32_t *d_x16 = nullptr;         // n: 1 when every count of the gene is a whole number <= 65535 (packable into 16 bits)
-    // outer-update state (dn_outer_begin): clipped / corrected DI, x_weighted, x_adj, ran_baseline_selection, partial sums
-    double  *d_rhoc = nullptr, *d_xw = nullptr, *d_xadj = nullptr, *d_part = nullptr, *d_pvec = nullptr;
-    double  *d_x = nullptr;           // the read counts (n x p), resident for the device-side initial normalisation (dn_init_begin)
-    uint8_t *d_ran = nullptr;
-    int32_t  n_iter = 0;
-    double  *d_est_sums = nullptr, *d_cov_sums = nullptr;
-    int32_t *d_status = nullptr;
-    double  *d_est = nullptr;
-    int32_t *d_tile_gene = nullptr, *d_tile_col = nullptr;
-    int64_t n_tiles = 0;
-
     // Gene classes: [0] wide genes on the main kernel set (256-thread workgroups, one per CU, the whole LDS for one
     // gene), [1] narrow genes (length <= split_len) on 128-thread workgroups, two per CU, so that the serial
     // reduction / eigen-solver phases of one gene overlap the pass of another.  Each class has its own longest-first
     // queue, scratch slots and stream; class 0 is launched first and class 1 fills the CUs as they drain.
+    // [2]: the shortest genes (length <= tiny_len), one wavefront per gene, two genes per 128-thread workgroup (the pair
+    // build): no cross-wave step, the serial phases are paid by ONE SIMD
     struct GeneClass {
         const dn::KernelSet *ks = nullptr;
         int32_t n = 0;
         int32_t longest = 0;              // longest gene of the class
-        int32_t *d_order = nullptr;
+        dn::DeviceBuffer<int32_t> d_order;
         std::vector<int32_t> order;       // host copy of the work queue (gene ids)
-        int32_t *d_counter = nullptr;
-        char *d_ws = nullptr;
+        dn::DeviceBuffer<int32_t> d_counter;
+        dn::DeviceBuffer<char> d_ws;
         int slots = 0;
         int32_t S = 0;
         int64_t slot_bytes = 0;
@@ -395,40 +377,56 @@ struct dn_handle_s {
         size_t dyn_lds = 0;
         float last_ms = 0.f;
     };
-    static constexpr int NCLS = 3;   // [2]: the shortest genes (length <= tiny_len), one wavefront per gene, two genes per 128-thread
-                                     // workgroup (the pair build): no cross-wave step, the serial phases are paid by ONE SIMD
-    GeneClass cls[NCLS];
+    // the buffers and state of one uploaded data set: free_device releases them all at once
+    struct DataSet {
+        dn::DeviceBuffer<float> d_cov;
+        dn::DeviceBuffer<int64_t> d_goff;
+        dn::DeviceBuffer<int32_t> d_glen;
+        dn::DeviceBuffer<int32_t> d_order;
+        dn::DeviceBuffer<int32_t> d_counter;
+        dn::DeviceBuffer<int64_t> d_ds;
+        dn::DeviceBuffer<double> d_rho;
+        dn::DeviceBuffer<int32_t> d_flags;
+        dn::DeviceBuffer<int32_t> d_trace;
+        dn::DeviceBuffer<double> d_kfin;
+        dn::DeviceBuffer<int32_t> d_emode;
+        dn::DeviceBuffer<double> d_svec;
+        dn::DeviceBuffer<int64_t> d_svoff;
+        dn::DeviceBuffer<float> d_rowmax;     // n x p row maxima of the raw coverage (k_row_max at upload)
+        dn::DeviceBuffer<int32_t> d_x16;      // n: 1 when every count of the gene is a whole number <= 65535 (packable into 16 bits)
+        // outer-update state (dn_outer_begin): clipped / corrected DI, x_weighted, x_adj, ran_baseline_selection, partial sums
+        dn::DeviceBuffer<double> d_rhoc, d_xw, d_xadj, d_part, d_pvec;
+        dn::DeviceBuffer<double> d_x;         // the read counts (n x p), resident for the device-side initial normalisation (dn_init_begin)
+        dn::DeviceBuffer<uint8_t> d_ran;
+        int32_t n_iter = 0;
+        dn::DeviceBuffer<double> d_est_sums, d_cov_sums;
+        dn::DeviceBuffer<int32_t> d_status;
+        dn::DeviceBuffer<double> d_est;
+        dn::DeviceBuffer<int32_t> d_tile_gene, d_tile_col;
+        GeneClass cls[NCLS];
+        bool have_estimate_state = false;
+        // per-gene counters of the previous dn_baseline_iteration: the narrow class orders its queue by the work they predict
+        dn::PinnedBuffer<int32_t> host_trace;     // the per-gene counters come back every iteration (n x trace_cols)
+        size_t host_trace_len = 0;
+        dn::DeviceBuffer<int32_t> d_trace_head;   // n x trace_cols, packed (only when trace_cols < TRACE_LEN)
+    } data;
+    int64_t n_tiles = 0;
     int32_t split_len = 0, tiny_len = 0;
-    hipStream_t stream2 = nullptr, stream3 = nullptr;
-    hipEvent_t ev2a = nullptr, ev2b = nullptr, ev3a = nullptr, ev3b = nullptr, ev_ready = nullptr;
-    hipStream_t class_stream(int c) const { return c == 0 ? stream : (c == 1 ? stream2 : stream3); }
-    hipEvent_t class_ev_a(int c) const { return c == 0 ? ev0 : (c == 1 ? ev2a : ev3a); }
-    hipEvent_t class_ev_b(int c) const { return c == 0 ? ev1 : (c == 1 ? ev2b : ev3b); }
-    int slots = 0;              // class 0 (kept for the run-time-p init kernel)
-    int32_t S = 0;
-    int64_t slot_bytes = 0;
     double last_scale[dn::P_MAX] = {0};
-    bool have_estimate_state = false;
     float last_ms = 0.f;
     float last_span_ms = 0.f;     // first launch to last end of the class kernels of the most recent dn_baseline_iteration
     float last_init_ms = 0.f;     // device time of the most recent dn_ratio_svd_sums kernel
     float last_rowmax_ms = 0.f;   // device time of k_row_max at the most recent upload
     float last_f64_ms = 0.f;      // device time of the most recent dn_nmf_f64 / dn_baseline_selection_f64 kernels
     char init_name[64] = {0};
-    hipEvent_t ev_i0 = nullptr, ev_i1 = nullptr;
     // the collective inside the library (dn_comm_*): one RCCL communicator per handle, all-reduces on the handle's stream
     void *comm = nullptr;         // ncclComm_t
     int32_t comm_rank = 0, comm_size = 0;
-    double *d_comm = nullptr;     // 256 doubles of scratch (ranks without genes, small host vectors)
+    dn::DeviceBuffer<double> d_comm;     // 256 doubles of scratch (ranks without genes, small host vectors)
     int32_t ds_hint = 1;          // take-every rate the caller intends to use (dn_set_downsample_hint); 1 = none
     int32_t max_steps = dn::EIG_MAX_STEPS_DEFAULT;   // step cap of one eigen-solve (dn_set_solver_step_cap)
-    // per-gene counters of the previous dn_baseline_iteration: the narrow class orders its queue by the work they predict
-    int32_t *host_trace = nullptr;        // pinned (hipHostMalloc): the per-gene counters come back every iteration (n x trace_cols)
-    size_t host_trace_len = 0;
     int32_t trace_cols = dn::TRACE_LEN;   // leading trace columns copied back per iteration (dn_set_trace_columns)
-    int32_t *d_trace_head = nullptr;      // n x trace_cols, packed (only when trace_cols < TRACE_LEN)
     bool have_trace = false;
-
 };
 
 // ---------------------------------------------------------------------------------------------------
@@ -460,8 +458,10 @@ static RcclApi *rccl_api(std::string &err)
         if (!api.lib) { const char *e = getenv("DN_RCCL_PATH"); if (e && *e) { api.lib = dlopen(e, RTLD_NOW | RTLD_LOCAL); if (api.lib) api.path = e; } }
         const char *sys[] = {"librccl.so.1", "/opt/rocm/lib/librccl.so.1", "librccl.so"};
         for (const char *n : sys) if (!api.lib) { api.lib = dlopen(n, RTLD_NOW | RTLD_LOCAL); if (api.lib) api.path = n; }
-        if (!api.lib) load_err = std::string("librccl not found (") + (dlerror() ? dlerror() : "?") + "); set DN_RCCL_PATH";
-        else {
+        if (!api.lib) {
+            const char *why = dlerror();                        // once: the call clears the message
+            load_err = std::string("librccl not found (") + (why ? why : "?") + "); set DN_RCCL_PATH";
+        } else {
             api.GetUniqueId = (decltype(api.GetUniqueId)) dlsym(api.lib, "ncclGetUniqueId");
             api.CommInitRank = (decltype(api.CommInitRank)) dlsym(api.lib, "ncclCommInitRank");
             api.CommDestroy = (decltype(api.CommDestroy)) dlsym(api.lib, "ncclCommDestroy");
@@ -478,54 +478,15 @@ static RcclApi *rccl_api(std::string &err)
     return &api;
 }
 
-static void free_device(dn_handle h)
-{
-    void *ptrs[] = {h->d_cov, h->d_goff, h->d_glen, h->d_order, h->d_counter, h->d_ds, h->d_ws, h->d_rho, h->d_flags,
-                    h->d_trace, h->d_kfin, h->d_emode, h->d_svec, h->d_svoff, h->d_est_sums, h->d_cov_sums,
-                    h->d_status, h->d_est, h->d_tile_gene, h->d_tile_col, h->d_rowmax, h->d_x16, h->d_rhoc, h->d_xw, h->d_xadj,
-                    h->d_part, h->d_pvec, h->d_ran, h->d_x};
-    for (void *q : ptrs) if (q && q != (void *) h->cls[0].d_ws) (void) hipFree(q);
-    if (h->host_trace) { (void) hipHostFree(h->host_trace); h->host_trace = nullptr; h->host_trace_len = 0; }
-    if (h->d_trace_head) { (void) hipFree(h->d_trace_head); h->d_trace_head = nullptr; }
-    for (auto &c : h->cls) {
-        if (c.d_order) (void) hipFree(c.d_order);
-        if (c.d_counter) (void) hipFree(c.d_counter);
-        if (c.d_ws) (void) hipFree(c.d_ws);
-        c = dn_handle_s::GeneClass();
-    }
-    h->d_cov = nullptr; h->d_goff = nullptr; h->d_glen = nullptr; h->d_order = nullptr; h->d_counter = nullptr;
-    h->d_ds = nullptr; h->d_ws = nullptr; h->d_rho = nullptr; h->d_flags = nullptr; h->d_trace = nullptr;
-    h->d_kfin = nullptr; h->d_emode = nullptr; h->d_svec = nullptr; h->d_svoff = nullptr; h->d_est_sums = nullptr;
-    h->d_cov_sums = nullptr; h->d_status = nullptr; h->d_est = nullptr; h->d_tile_gene = nullptr; h->d_tile_col = nullptr;
-    h->d_rowmax = nullptr; h->d_x16 = nullptr;
-    h->d_rhoc = nullptr; h->d_xw = nullptr; h->d_xadj = nullptr; h->d_part = nullptr; h->d_pvec = nullptr; h->d_ran = nullptr;
-    h->d_x = nullptr;
-    h->n_iter = 0;
-    h->have_estimate_state = false;
-}
+static void free_device(dn_handle h) { h->data = dn_handle_s::DataSet(); }
 
 // ---------------------------------------------------------------------------------------------------------------
 // The float64-input path (dn_generic.hip, DN_GEN_F64 build): per-call device buffers, freed on every return path; the
 // handle contributes its device, stream, CU count and solver step cap only.
 // ---------------------------------------------------------------------------------------------------------------
 namespace {
-struct F64Buffers {
-    std::vector<void *> ptrs;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~F64Buffers()
-    {
-        for (void *q : ptrs) (void) hipFree(q);
-        if (e0) (void) hipEventDestroy(e0);
-        if (e1) (void) hipEventDestroy(e1);
-    }
-    template <class T> hipError_t alloc(T **out, size_t count)
-    {
-        *out = nullptr;
-        const hipError_t e = hipMalloc((void **) out, sizeof(T) * std::max<size_t>(count, 1));
-        if (e == hipSuccess) ptrs.push_back((void *) *out);
-        return e;
-    }
-};
+// a per-call buffer of `count` elements (at least one)
+template <class T> hipError_t alloc_f64(dn::DeviceBuffer<T> &b, size_t count) { return b.alloc(sizeof(T) * std::max<size_t>(count, 1)); }
 
 // Persistent workgroups for a float64-path kernel: as many as fit on the device (occupancy x CUs), at most one per item,
 // fewer when their scratch slots would take more than a third of free HBM.  0 and g_err set when one slot alone is too big.
@@ -582,19 +543,15 @@ static int create_streams(dn_handle h)
     // place pending wide workgroups first, then narrow ones, then pairs.
     int prio_least = 0, prio_greatest = 0;
     HIP_TRY(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-    const int prio_mid = (prio_least + prio_greatest) / 2;
-    HIP_TRY(hipStreamCreateWithPriority(&h->stream, hipStreamNonBlocking, prio_greatest));
-    HIP_TRY(hipEventCreate(&h->ev0));
-    HIP_TRY(hipEventCreate(&h->ev1));
-    HIP_TRY(hipStreamCreateWithPriority(&h->stream2, hipStreamNonBlocking, prio_mid));
-    HIP_TRY(hipEventCreate(&h->ev2a));
-    HIP_TRY(hipEventCreate(&h->ev2b));
-    HIP_TRY(hipStreamCreateWithPriority(&h->stream3, hipStreamNonBlocking, prio_least));
-    HIP_TRY(hipEventCreate(&h->ev3a));
-    HIP_TRY(hipEventCreate(&h->ev3b));
-    HIP_TRY(hipEventCreateWithFlags(&h->ev_ready, hipEventDisableTiming));
-    HIP_TRY(hipEventCreate(&h->ev_i0));
-    HIP_TRY(hipEventCreate(&h->ev_i1));
+    const int prio[dn_handle_s::NCLS] = {prio_greatest, (prio_least + prio_greatest) / 2, prio_least};
+    for (int c = 0; c < dn_handle_s::NCLS; c++) {
+        HIP_TRY(h->stream[c].create(hipStreamCreateWithPriority, hipStreamNonBlocking, prio[c]));
+        HIP_TRY(h->ev_start[c].create(hipEventCreate));
+        HIP_TRY(h->ev_end[c].create(hipEventCreate));
+    }
+    HIP_TRY(h->ev_ready.create(hipEventCreateWithFlags, hipEventDisableTiming));
+    HIP_TRY(h->ev_i0.create(hipEventCreate));
+    HIP_TRY(h->ev_i1.create(hipEventCreate));
     return DN_OK;
 }
 
@@ -625,28 +582,14 @@ int dn_destroy(dn_handle h)
 {
     if (!h) return DN_OK;
     (void) hipSetDevice(h->device);
-    if (h->stream) (void) hipStreamSynchronize(h->stream);
+    if (h->stream[0]) (void) hipStreamSynchronize(h->stream[0]);
     (void) dn_comm_destroy(h);
-    free_device(h);
-    if (h->ev0) (void) hipEventDestroy(h->ev0);
-    if (h->ev1) (void) hipEventDestroy(h->ev1);
-    if (h->ev2a) (void) hipEventDestroy(h->ev2a);
-    if (h->ev2b) (void) hipEventDestroy(h->ev2b);
-    if (h->ev3a) (void) hipEventDestroy(h->ev3a);
-    if (h->ev3b) (void) hipEventDestroy(h->ev3b);
-    if (h->stream3) (void) hipStreamDestroy(h->stream3);
-    if (h->ev_ready) (void) hipEventDestroy(h->ev_ready);
-    if (h->ev_i0) (void) hipEventDestroy(h->ev_i0);
-    if (h->ev_i1) (void) hipEventDestroy(h->ev_i1);
-    if (h->stream2) (void) hipStreamDestroy(h->stream2);
-    if (h->stream) (void) hipStreamDestroy(h->stream);
-    delete h;
+    delete h;                                // the owners release the buffers, then the events and streams
     return DN_OK;
 }
 
 // Scratch slots and LDS tier of one gene class for genes of up to `cols` active columns.  The new scratch is allocated
-// FIRST and swapped in only on success: a failed (re)size leaves the class -- and the handle's alias of class 0's slots --
-// exactly as it was, still valid.
+// FIRST and swapped in only on success: a failed (re)size leaves the class exactly as it was, still valid.
 static int size_class(dn_handle h, dn_handle_s::GeneClass &C, int32_t cols)
 {
     const int32_t p = h->p;
@@ -666,12 +609,10 @@ static int size_class(dn_handle h, dn_handle_s::GeneClass &C, int32_t cols)
         if (slot_bytes > budget) return fail(DN_E_INVALID, "a gene is too long for the device scratch (" + std::to_string(S) + " columns)");
         slots = (int) std::max<int64_t>(units, std::min<int64_t>(slots, budget / slot_bytes / units * units));
     }
-    char *ws = nullptr;
-    HIP_TRY(hipMalloc(&ws, (size_t) slot_bytes * (size_t) std::max(slots, 1)));
-    const bool aliased = (h->d_ws == C.d_ws);
-    if (C.d_ws) (void) hipFree(C.d_ws);
-    C.d_ws = ws; C.slots = slots; C.S = S; C.slot_bytes = slot_bytes;
-    if (aliased && &C == &h->cls[0]) h->d_ws = ws;
+    dn::DeviceBuffer<char> ws;
+    HIP_TRY(ws.alloc((size_t) slot_bytes * (size_t) std::max(slots, 1)));
+    C.d_ws = std::move(ws);                                // releases the old scratch
+    C.slots = slots; C.S = S; C.slot_bytes = slot_bytes;
     // lambda LDS tier: whatever of the CU's 160 KiB is left per resident workgroup after the static part
     const int64_t lds_per_block = (160 * 1024) / per_cu - (int64_t) C.ks->static_lds_bytes - 256;
     const int64_t ps = p + (p & 1);                        // LDS column stride in doubles (16-B aligned)
@@ -731,15 +672,12 @@ static int upload_ragged_chunks(dn_handle h, const CoverageSource &src)
     if (const char *env = getenv("DN_UPLOAD_CHUNK_FLOATS")) chunk = std::max<int64_t>(1, atoll(env));    // tests: many small chunks
     for (int64_t g = 0; g < n; g++) chunk = std::max(chunk, (int64_t) h->p * h->glen[g]);
     chunk = std::min(chunk, std::max<int64_t>(h->total, 1));
-    float *stage[2] = {nullptr, nullptr};
-    hipEvent_t done[2] = {nullptr, nullptr};
+    dn::PinnedBuffer<float> stage[2];
+    dn::Event done[2];
     int rc = DN_OK;
-    auto cleanup = [&]() {
-        for (int b = 0; b < 2; b++) { if (stage[b]) (void) hipHostFree(stage[b]); if (done[b]) (void) hipEventDestroy(done[b]); }
-    };
     for (int b = 0; b < 2 && rc == DN_OK; b++) {
-        if (hipHostMalloc(&stage[b], sizeof(float) * (size_t) chunk, hipHostMallocDefault) != hipSuccess ||
-            hipEventCreateWithFlags(&done[b], hipEventDisableTiming) != hipSuccess) rc = fail(DN_E_HIP, "upload: pinned staging buffer");
+        if (stage[b].alloc(sizeof(float) * (size_t) chunk) != hipSuccess ||
+            done[b].create(hipEventCreateWithFlags, hipEventDisableTiming) != hipSuccess) rc = fail(DN_E_HIP, "upload: pinned staging buffer");
     }
     int64_t g0 = 0;
     for (int k = 0; rc == DN_OK && g0 < n; k++) {
@@ -748,15 +686,13 @@ static int upload_ragged_chunks(dn_handle h, const CoverageSource &src)
         const int b = k & 1;
         if (k >= 2 && hipEventSynchronize(done[b]) != hipSuccess) { rc = fail(DN_E_HIP, "upload: event"); break; }
         pack_genes(h, src, g0, g1, stage[b]);
-        if (hipMemcpyAsync(h->d_cov + h->goff[g0], stage[b], sizeof(float) * (size_t) fl, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
-            hipEventRecord(done[b], h->stream) != hipSuccess) { rc = fail(DN_E_HIP, "upload: copy"); break; }
+        if (hipMemcpyAsync(h->data.d_cov + h->goff[g0], stage[b], sizeof(float) * (size_t) fl, hipMemcpyHostToDevice, h->stream[0]) != hipSuccess ||
+            hipEventRecord(done[b], h->stream[0]) != hipSuccess) { rc = fail(DN_E_HIP, "upload: copy"); break; }
         g0 = g1;
     }
-    if (rc == DN_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(DN_E_HIP, "upload: synchronize");
-    if (rc != DN_OK) (void) hipStreamSynchronize(h->stream);                // nothing may still read the staging buffers
-    const std::string msg = g_err;
-    cleanup();
-    return rc == DN_OK ? DN_OK : fail(rc, msg);
+    if (rc == DN_OK && hipStreamSynchronize(h->stream[0]) != hipSuccess) rc = fail(DN_E_HIP, "upload: synchronize");
+    if (rc != DN_OK) (void) hipStreamSynchronize(h->stream[0]);                // nothing may still read the staging buffers
+    return rc;
 }
 
 // Class boundaries of a cohort of p samples served by kernel set `ks` (see dn_handle_s::GeneClass): genes longer than
@@ -832,40 +768,40 @@ static int finish_upload_impl(dn_handle h, const CoverageSource &src)
         for (int32_t c = 0; c < h->glen[g]; c += 256) { tg.push_back((int32_t) g); tc.push_back(c); }
     h->n_tiles = (int64_t) tg.size();
 
-    HIP_TRY(hipMalloc(&h->d_cov, sizeof(float) * (size_t) std::max<int64_t>(h->total, 1)));
-    HIP_TRY(hipMalloc(&h->d_goff, sizeof(int64_t) * (size_t) (n + 1)));
-    HIP_TRY(hipMalloc(&h->d_glen, sizeof(int32_t) * (size_t) n));
-    HIP_TRY(hipMalloc(&h->d_order, sizeof(int32_t) * (size_t) n));
-    HIP_TRY(hipMalloc(&h->d_counter, sizeof(int32_t) * 4));
-    HIP_TRY(hipMalloc(&h->d_ds, sizeof(int64_t) * (size_t) n));
-    HIP_TRY(hipMalloc(&h->d_rho, sizeof(double) * (size_t) n * p));
-    HIP_TRY(hipMalloc(&h->d_flags, sizeof(int32_t) * (size_t) n));
-    HIP_TRY(hipMalloc(&h->d_trace, sizeof(int32_t) * (size_t) n * dn::TRACE_LEN));
-    HIP_TRY(hipMalloc(&h->d_kfin, sizeof(double) * (size_t) n * p));
-    HIP_TRY(hipMalloc(&h->d_emode, sizeof(int32_t) * (size_t) n));
-    HIP_TRY(hipMalloc(&h->d_svoff, sizeof(int64_t) * (size_t) (n + 1)));
-    HIP_TRY(hipMalloc(&h->d_est_sums, sizeof(double) * (size_t) n * p));
-    HIP_TRY(hipMalloc(&h->d_cov_sums, sizeof(double) * (size_t) n * p));
-    HIP_TRY(hipMalloc(&h->d_status, sizeof(int32_t) * (size_t) n));
-    HIP_TRY(hipMalloc(&h->d_rowmax, sizeof(float) * (size_t) n * p));
-    HIP_TRY(hipMalloc(&h->d_x16, sizeof(int32_t) * (size_t) n));
-    HIP_TRY(hipMalloc(&h->d_tile_gene, sizeof(int32_t) * (size_t) std::max<int64_t>(h->n_tiles, 1)));
-    HIP_TRY(hipMalloc(&h->d_tile_col, sizeof(int32_t) * (size_t) std::max<int64_t>(h->n_tiles, 1)));
+    HIP_TRY(h->data.d_cov.alloc(sizeof(float) * (size_t) std::max<int64_t>(h->total, 1)));
+    HIP_TRY(h->data.d_goff.alloc(sizeof(int64_t) * (size_t) (n + 1)));
+    HIP_TRY(h->data.d_glen.alloc(sizeof(int32_t) * (size_t) n));
+    HIP_TRY(h->data.d_order.alloc(sizeof(int32_t) * (size_t) n));
+    HIP_TRY(h->data.d_counter.alloc(sizeof(int32_t) * 4));
+    HIP_TRY(h->data.d_ds.alloc(sizeof(int64_t) * (size_t) n));
+    HIP_TRY(h->data.d_rho.alloc(sizeof(double) * (size_t) n * p));
+    HIP_TRY(h->data.d_flags.alloc(sizeof(int32_t) * (size_t) n));
+    HIP_TRY(h->data.d_trace.alloc(sizeof(int32_t) * (size_t) n * dn::TRACE_LEN));
+    HIP_TRY(h->data.d_kfin.alloc(sizeof(double) * (size_t) n * p));
+    HIP_TRY(h->data.d_emode.alloc(sizeof(int32_t) * (size_t) n));
+    HIP_TRY(h->data.d_svoff.alloc(sizeof(int64_t) * (size_t) (n + 1)));
+    HIP_TRY(h->data.d_est_sums.alloc(sizeof(double) * (size_t) n * p));
+    HIP_TRY(h->data.d_cov_sums.alloc(sizeof(double) * (size_t) n * p));
+    HIP_TRY(h->data.d_status.alloc(sizeof(int32_t) * (size_t) n));
+    HIP_TRY(h->data.d_rowmax.alloc(sizeof(float) * (size_t) n * p));
+    HIP_TRY(h->data.d_x16.alloc(sizeof(int32_t) * (size_t) n));
+    HIP_TRY(h->data.d_tile_gene.alloc(sizeof(int32_t) * (size_t) std::max<int64_t>(h->n_tiles, 1)));
+    HIP_TRY(h->data.d_tile_col.alloc(sizeof(int32_t) * (size_t) std::max<int64_t>(h->n_tiles, 1)));
 
-    if (src.packed) HIP_TRY(hipMemcpyAsync(h->d_cov, src.packed, sizeof(float) * (size_t) h->total, hipMemcpyHostToDevice, h->stream));
+    if (src.packed) HIP_TRY(hipMemcpyAsync(h->data.d_cov, src.packed, sizeof(float) * (size_t) h->total, hipMemcpyHostToDevice, h->stream[0]));
     else { const int rcu = upload_ragged_chunks(h, src); if (rcu != DN_OK) return rcu; }
-    HIP_TRY(hipMemcpyAsync(h->d_goff, h->goff.data(), sizeof(int64_t) * (size_t) (n + 1), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->d_glen, h->glen.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->d_order, order.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->d_svoff, h->svoff.data(), sizeof(int64_t) * (size_t) (n + 1), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->d_tile_gene, tg.data(), sizeof(int32_t) * tg.size(), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->d_tile_col, tc.data(), sizeof(int32_t) * tc.size(), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipEventRecord(h->ev_i0, h->stream));
-    hipLaunchKernelGGL(k_row_max, dim3((unsigned) std::min<int64_t>(n, (int64_t) h->n_cus * 8)), dim3(256), 0, h->stream,
-                       h->d_cov, h->d_goff, h->d_glen, h->d_rowmax, h->d_x16, (int) n, (int) p);
+    HIP_TRY(hipMemcpyAsync(h->data.d_goff, h->goff.data(), sizeof(int64_t) * (size_t) (n + 1), hipMemcpyHostToDevice, h->stream[0]));
+    HIP_TRY(hipMemcpyAsync(h->data.d_glen, h->glen.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
+    HIP_TRY(hipMemcpyAsync(h->data.d_order, order.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
+    HIP_TRY(hipMemcpyAsync(h->data.d_svoff, h->svoff.data(), sizeof(int64_t) * (size_t) (n + 1), hipMemcpyHostToDevice, h->stream[0]));
+    HIP_TRY(hipMemcpyAsync(h->data.d_tile_gene, tg.data(), sizeof(int32_t) * tg.size(), hipMemcpyHostToDevice, h->stream[0]));
+    HIP_TRY(hipMemcpyAsync(h->data.d_tile_col, tc.data(), sizeof(int32_t) * tc.size(), hipMemcpyHostToDevice, h->stream[0]));
+    HIP_TRY(hipEventRecord(h->ev_i0, h->stream[0]));
+    hipLaunchKernelGGL(k_row_max, dim3((unsigned) std::min<int64_t>(n, (int64_t) h->n_cus * 8)), dim3(256), 0, h->stream[0],
+                       h->data.d_cov, h->data.d_goff, h->data.d_glen, h->data.d_rowmax, h->data.d_x16, (int) n, (int) p);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(h->ev_i1, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipEventRecord(h->ev_i1, h->stream[0]));
+    HIP_TRY(hipStreamSynchronize(h->stream[0]));
     (void) hipEventElapsedTime(&h->last_rowmax_ms, h->ev_i0, h->ev_i1);
 
     // gene classes
@@ -877,35 +813,29 @@ static int finish_upload_impl(dn_handle h, const CoverageSource &src)
             const int32_t L = h->glen[g];
             ord[(h->split_len > 0 && L <= h->split_len) ? ((pair && L <= h->tiny_len) ? 2 : 1) : 0].push_back(g);
         }
-        h->cls[0].ks = h->ks;
-        h->cls[1].ks = (h->ks->p != 0 && h->split_len > 0) ? dn::kernel_set_narrow(p) : nullptr;
-        h->cls[2].ks = pair;
-        {
-            // Queue order of a class: longest first, then zigzagged (longest, shortest, 2nd longest, 2nd shortest, ...).
+        h->data.cls[0].ks = h->ks;
+        h->data.cls[1].ks = (h->ks->p != 0 && h->split_len > 0) ? dn::kernel_set_narrow(p) : nullptr;
+        h->data.cls[2].ks = pair;
+        if (ord[0].size() >= 8) {
+            // Queue order of the wide class: longest first, then zigzagged (longest, shortest, 2nd longest, 2nd shortest, ...).
             // Long genes keep most of their state in the spill tier and pull ~60 GB/s per CU through the fabric, short
             // ones a quarter of that; running only long genes everywhere at the start of a launch saturates the fabric
             // (their pass is 1.4x slower than alone on the chip, tools/contention.sh).  The zigzag keeps the demand level
             // over the launch: +2.9 % on config 2 and more on short queues (+6 % at 5 000 genes per GPU against ordering
             // by the cost predicted from the previous iteration's counters, which clusters the heavy genes even more).
-            // DN_ORDER_MIX=0 restores plain longest-first, bit c selects class c.
-            const char *mix = getenv("DN_ORDER_MIX");
-            const int mask = mix ? atoi(mix) : 1;
-            for (int c = 0; c < dn_handle_s::NCLS; c++) {
-                if (!((mask >> c) & 1) || ord[c].size() < 8) continue;
-                const size_t n0 = ord[c].size();
-                std::vector<int32_t> mixed;
-                mixed.reserve(n0);
-                for (size_t i = 0, j = n0 - 1; i < j; i++, j--) { mixed.push_back(ord[c][i]); mixed.push_back(ord[c][j]); }
-                if (n0 & 1) mixed.push_back(ord[c][n0 / 2]);
-                ord[c] = mixed;
-            }
+            const size_t n0 = ord[0].size();
+            std::vector<int32_t> mixed;
+            mixed.reserve(n0);
+            for (size_t i = 0, j = n0 - 1; i < j; i++, j--) { mixed.push_back(ord[0][i]); mixed.push_back(ord[0][j]); }
+            if (n0 & 1) mixed.push_back(ord[0][n0 / 2]);
+            ord[0] = mixed;
         }
         for (int c = 0; c < dn_handle_s::NCLS; c++) {
-            auto &C = h->cls[c];
+            auto &C = h->data.cls[c];
             C.n = (int32_t) ord[c].size();
             if (C.n == 0 || !C.ks) { C.n = 0; continue; }
-            HIP_TRY(hipMalloc(&C.d_order, sizeof(int32_t) * (size_t) C.n));
-            HIP_TRY(hipMalloc(&C.d_counter, sizeof(int32_t) * 4));
+            HIP_TRY(C.d_order.alloc(sizeof(int32_t) * (size_t) C.n));
+            HIP_TRY(C.d_counter.alloc(sizeof(int32_t) * 4));
             HIP_TRY(hipMemcpy(C.d_order, ord[c].data(), sizeof(int32_t) * (size_t) C.n, hipMemcpyHostToDevice));
             C.order = ord[c];
             // columns a scratch slot must hold: the longest gene of the class, or -- for the one-wave-per-gene family,
@@ -915,8 +845,7 @@ static int finish_upload_impl(dn_handle h, const CoverageSource &src)
             const int rc = size_class(h, C, cols);
             if (rc != DN_OK) return rc;
         }
-        if (h->cls[0].n == 0 && (h->cls[1].n > 0 || h->cls[2].n > 0) && h->ks->p == 0) return fail(DN_E_STATE, "internal: empty wide class for the generic kernels");
-        h->slots = h->cls[0].slots; h->S = h->cls[0].S; h->slot_bytes = h->cls[0].slot_bytes; h->d_ws = h->cls[0].d_ws;
+        if (h->data.cls[0].n == 0 && (h->data.cls[1].n > 0 || h->data.cls[2].n > 0) && h->ks->p == 0) return fail(DN_E_STATE, "internal: empty wide class for the generic kernels");
     }
     return DN_OK;
 }
@@ -1022,44 +951,43 @@ int dn_upload_ragged(dn_handle h, int64_t n_genes, int32_t p, const void *const 
 
 int dn_ratio_svd_sums(dn_handle h, double *est_sums, double *cov_sums, int32_t *status)
 {
-    if (!h || !h->d_cov) return fail(DN_E_STATE, "dn_ratio_svd_sums: nothing uploaded");
+    if (!h || !h->data.d_cov) return fail(DN_E_STATE, "dn_ratio_svd_sums: nothing uploaded");
     if ((est_sums == nullptr) != (cov_sums == nullptr)) return fail(DN_E_INVALID, "dn_ratio_svd_sums: the two sums are fetched together or not at all");
     HIP_TRY(hipSetDevice(h->device));
     dn::InitArgs a;
-    a.cov = h->d_cov; a.goff = h->d_goff; a.glen = h->d_glen; a.order = h->d_order; a.counter = h->d_counter;
-    a.est_sums = h->d_est_sums; a.cov_sums = h->d_cov_sums; a.status = h->d_status; a.n_genes = (int32_t) h->n;
-    a.p = h->p; a.ws = h->d_ws; a.slot_bytes = h->slot_bytes; a.S = h->S; a.max_steps = h->max_steps;
-    a.x16 = h->d_x16;
+    a.cov = h->data.d_cov; a.goff = h->data.d_goff; a.glen = h->data.d_glen; a.order = h->data.d_order; a.counter = h->data.d_counter;
+    a.est_sums = h->data.d_est_sums; a.cov_sums = h->data.d_cov_sums; a.status = h->data.d_status; a.n_genes = (int32_t) h->n;
+    a.p = h->p; a.ws = h->data.cls[0].d_ws; a.slot_bytes = h->data.cls[0].slot_bytes; a.S = h->data.cls[0].S; a.max_steps = h->max_steps;
+    a.x16 = h->data.d_x16;
     { const char *f64 = getenv("DN_INIT_FP64"); a.force_fp64 = (f64 && f64[0] == '1') ? 1 : 0; }
-    HIP_TRY(hipMemsetAsync(h->d_counter, 0, sizeof(int32_t) * 4, h->stream));
+    HIP_TRY(hipMemsetAsync(h->data.d_counter, 0, sizeof(int32_t) * 4, h->stream[0]));
     // occupancy of the kernel that ks->init() will start: from 17 samples on it is the matrix-core variant (round 2 asked for
     // the power-iteration kernel's figure here and ran k_ratio_svd_mg at ONE workgroup per CU instead of two)
-    const char *pw = getenv("DN_INIT_POWER");
-    const int which_init = (h->p >= 17 && !(pw && pw[0] == '1')) ? 2 : 1;
+    const int which_init = h->p >= 17 ? 2 : 1;
     int per_cu = std::max(1, h->ks->blocks_per_cu(which_init));
     int grid = (int) std::min<int64_t>(h->n, (int64_t) per_cu * h->n_cus);
-    if (h->ks->p == 0) grid = std::min(grid, h->slots);          // generic kernels work in the scratch slots
-    HIP_TRY(hipEventRecord(h->ev_i0, h->stream));
-    h->ks->init(a, grid, h->stream);
+    if (h->ks->p == 0) grid = std::min(grid, h->data.cls[0].slots);          // generic kernels work in the scratch slots
+    HIP_TRY(hipEventRecord(h->ev_i0, h->stream[0]));
+    h->ks->init(a, grid, h->stream[0]);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(h->ev_i1, h->stream));
+    HIP_TRY(hipEventRecord(h->ev_i1, h->stream[0]));
     const size_t np = (size_t) h->n * h->p;
     if (est_sums) {                     // null: the sums stay on the device (dn_init_partials reduces them there)
-        HIP_TRY(hipMemcpyAsync(est_sums, h->d_est_sums, sizeof(double) * np, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipMemcpyAsync(cov_sums, h->d_cov_sums, sizeof(double) * np, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(est_sums, h->data.d_est_sums, sizeof(double) * np, hipMemcpyDeviceToHost, h->stream[0]));
+        HIP_TRY(hipMemcpyAsync(cov_sums, h->data.d_cov_sums, sizeof(double) * np, hipMemcpyDeviceToHost, h->stream[0]));
     }
-    if (status) HIP_TRY(hipMemcpyAsync(status, h->d_status, sizeof(int32_t) * (size_t) h->n, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (status) HIP_TRY(hipMemcpyAsync(status, h->data.d_status, sizeof(int32_t) * (size_t) h->n, hipMemcpyDeviceToHost, h->stream[0]));
+    HIP_TRY(hipStreamSynchronize(h->stream[0]));
     HIP_TRY(hipEventElapsedTime(&h->last_init_ms, h->ev_i0, h->ev_i1));
     if (h->ks->p >= 2 && h->ks->p <= 16) snprintf(h->init_name, sizeof(h->init_name), "k_ratio_svd<%d,%d>", h->ks->p, h->ks->nt);
-    else snprintf(h->init_name, sizeof(h->init_name), (h->p >= 17 && !(getenv("DN_INIT_POWER") && getenv("DN_INIT_POWER")[0] == '1')) ? "gen::k_ratio_svd_mg" : "gen::k_ratio_svd_gen");
+    else snprintf(h->init_name, sizeof(h->init_name), h->p >= 17 ? "gen::k_ratio_svd_mg" : "gen::k_ratio_svd_gen");
     return DN_OK;
 }
 
 int dn_baseline_iteration(dn_handle h, const double *scale, const dn_params *prm, const int64_t *ds_start,
                           double *rho, int32_t *flags, int32_t *trace)
 {
-    if (!h || !h->d_cov) return fail(DN_E_STATE, "dn_baseline_iteration: nothing uploaded");
+    if (!h || !h->data.d_cov) return fail(DN_E_STATE, "dn_baseline_iteration: nothing uploaded");
     if (!scale || !prm) return fail(DN_E_INVALID, "dn_baseline_iteration: null argument");
     if ((rho == nullptr) != (flags == nullptr)) return fail(DN_E_INVALID, "dn_baseline_iteration: rho and flags are fetched together or not at all");
     if (prm->nmf_iter < 1) return fail(DN_E_INVALID, "nmf_iter must be >= 1");
@@ -1081,235 +1009,229 @@ int dn_baseline_iteration(dn_handle h, const double *scale, const dn_params *prm
         // the scratch slots were sized at upload (for the announced take-every rate in the one-wave-per-gene family):
         // grow them if this iteration's rate leaves more active columns than they hold
         const int32_t rate = prm->downsample_rate;
-        for (auto &C : h->cls) {
+        for (auto &C : h->data.cls) {
             if (C.n == 0 || !C.ks) continue;
             const int32_t longest = C.longest;
             const int32_t need = rate > 1 ? (longest + rate - 1) / rate : longest;
             if (need > C.S) {
-                HIP_TRY(hipStreamSynchronize(h->stream));
+                HIP_TRY(hipStreamSynchronize(h->stream[0]));
                 const int rc = size_class(h, C, need);
                 if (rc != DN_OK) return rc;
-                if (&C == &h->cls[0]) { h->slots = C.slots; h->S = C.S; h->slot_bytes = C.slot_bytes; h->d_ws = C.d_ws; }
             }
         }
     }
-    if (prm->want_estimates && !h->d_svec)
-        HIP_TRY(hipMalloc(&h->d_svec, sizeof(double) * (size_t) std::max<int64_t>(h->svoff[h->n], 1)));
+    if (prm->want_estimates && !h->data.d_svec)
+        HIP_TRY(h->data.d_svec.alloc(sizeof(double) * (size_t) std::max<int64_t>(h->svoff[h->n], 1)));
 
     dn::IterArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.cov = h->d_cov; a.goff = h->d_goff; a.glen = h->d_glen; a.order = h->d_order; a.counter = h->d_counter;
+    a.cov = h->data.d_cov; a.goff = h->data.d_goff; a.glen = h->data.d_glen; a.order = h->data.d_order; a.counter = h->data.d_counter;
     a.ds_start = nullptr;
-    a.ws = h->d_ws; a.rho = h->d_rho; a.flags = h->d_flags; a.trace = h->d_trace; a.kfin = h->d_kfin; a.emode = h->d_emode;
-    a.svec = h->d_svec; a.svoff = h->d_svoff; a.slot_bytes = h->slot_bytes; a.n_genes = (int32_t) h->n; a.S = h->S;
-    a.p = h->p; a.rowmax = h->d_rowmax; a.x16 = h->d_x16; a.max_steps = h->max_steps;
+    a.ws = h->data.cls[0].d_ws; a.rho = h->data.d_rho; a.flags = h->data.d_flags; a.trace = h->data.d_trace; a.kfin = h->data.d_kfin; a.emode = h->data.d_emode;
+    a.svec = h->data.d_svec; a.svoff = h->data.d_svoff; a.slot_bytes = h->data.cls[0].slot_bytes; a.n_genes = (int32_t) h->n; a.S = h->data.cls[0].S;
+    a.p = h->p; a.rowmax = h->data.d_rowmax; a.x16 = h->data.d_x16; a.max_steps = h->max_steps;
     a.T = prm->nmf_iter; a.bins = prm->bins; a.min_hc = prm->min_high_coverage; a.rate = prm->downsample_rate;
     a.skip = prm->skip_baseline_selection ? 1 : 0; a.want_est = prm->want_estimates ? 1 : 0;
     for (int i = 0; i < h->p; i++) { a.scale[i] = scale[i]; a.inv_scale[i] = 1.0 / scale[i]; h->last_scale[i] = scale[i]; }
     for (int i = h->p; i < dn::P_MAX; i++) { a.scale[i] = 1.0; a.inv_scale[i] = 1.0; }
     if (prm->downsample_rate > 1) {
-        HIP_TRY(hipMemcpyAsync(h->d_ds, ds_start, sizeof(int64_t) * (size_t) h->n, hipMemcpyHostToDevice, h->stream));
-        a.ds_start = h->d_ds;
+        HIP_TRY(hipMemcpyAsync(h->data.d_ds, ds_start, sizeof(int64_t) * (size_t) h->n, hipMemcpyHostToDevice, h->stream[0]));
+        a.ds_start = h->data.d_ds;
     }
     // The narrow class (state in LDS, little fabric traffic) orders its queue most expensive first from the second
     // iteration on, the cost of a gene predicted from the previous iteration's counters (sum of active columns over its
     // nmf() calls plus a fixed part per call worth ~4 columns per lane): its genes are what fills the end of a launch.
-    // The wide class keeps the zigzag (it is bound by the fabric, see upload).  DN_NARROW_WORK_ORDER=0 disables.
-    {
-        const char *wo = getenv("DN_NARROW_WORK_ORDER");
-        for (int wc = 1; wc < dn_handle_s::NCLS; wc++) {
-        auto &C = h->cls[wc];
-        if (h->have_trace && C.n > 0 && C.ks && !(wo && wo[0] == '0')) {
-            const double per_call = 4.0 * (double) (C.ks->nt > 0 ? C.ks->nt : 128);
-            std::vector<std::pair<double, int32_t>> key((size_t) C.n);
-            for (int32_t k = 0; k < C.n; k++) {
-                const int32_t g = C.order[k];
-                const int32_t *tr = &h->host_trace[(size_t) g * h->trace_cols];
-                key[k] = {(double) tr[2] + per_call * (double) tr[1] + 1e-3 * (double) h->glen[g], g};
-            }
-            std::stable_sort(key.begin(), key.end(), [](const std::pair<double, int32_t> &a, const std::pair<double, int32_t> &b) { return a.first > b.first; });
-            for (int32_t k = 0; k < C.n; k++) C.order[k] = key[k].second;
-            HIP_TRY(hipMemcpyAsync(C.d_order, C.order.data(), sizeof(int32_t) * (size_t) C.n, hipMemcpyHostToDevice, h->stream));
+    // The wide class keeps the zigzag (it is bound by the fabric, see upload).
+    for (int wc = 1; wc < dn_handle_s::NCLS; wc++) {
+        auto &C = h->data.cls[wc];
+        if (!h->have_trace || C.n == 0 || !C.ks) continue;
+        const double per_call = 4.0 * (double) (C.ks->nt > 0 ? C.ks->nt : 128);
+        std::vector<std::pair<double, int32_t>> key((size_t) C.n);
+        for (int32_t k = 0; k < C.n; k++) {
+            const int32_t g = C.order[k];
+            const int32_t *tr = &h->data.host_trace[(size_t) g * h->trace_cols];
+            key[k] = {(double) tr[2] + per_call * (double) tr[1] + 1e-3 * (double) h->glen[g], g};
         }
-        }
+        std::stable_sort(key.begin(), key.end(), [](const std::pair<double, int32_t> &a, const std::pair<double, int32_t> &b) { return a.first > b.first; });
+        for (int32_t k = 0; k < C.n; k++) C.order[k] = key[k].second;
+        HIP_TRY(hipMemcpyAsync(C.d_order, C.order.data(), sizeof(int32_t) * (size_t) C.n, hipMemcpyHostToDevice, h->stream[0]));
     }
-    HIP_TRY(hipMemsetAsync(h->d_trace, 0, sizeof(int32_t) * (size_t) h->n * dn::TRACE_LEN, h->stream));
-    for (auto &C : h->cls) if (C.n > 0) HIP_TRY(hipMemsetAsync(C.d_counter, 0, sizeof(int32_t) * 4, h->stream));
-    HIP_TRY(hipEventRecord(h->ev_ready, h->stream));
+    HIP_TRY(hipMemsetAsync(h->data.d_trace, 0, sizeof(int32_t) * (size_t) h->n * dn::TRACE_LEN, h->stream[0]));
+    for (auto &C : h->data.cls) if (C.n > 0) HIP_TRY(hipMemsetAsync(C.d_counter, 0, sizeof(int32_t) * 4, h->stream[0]));
+    HIP_TRY(hipEventRecord(h->ev_ready, h->stream[0]));
     int first_cls = -1;
     for (int c = 0; c < dn_handle_s::NCLS; c++) {
-        auto &C = h->cls[c];
+        auto &C = h->data.cls[c];
         C.last_ms = 0.f;
         if (C.n == 0) continue;
         if (first_cls < 0) first_cls = c;
-        hipStream_t st = h->class_stream(c);
+        hipStream_t st = h->stream[c];
         if (c > 0) HIP_TRY(hipStreamWaitEvent(st, h->ev_ready, 0));
         a.order = C.d_order; a.counter = C.d_counter; a.ws = C.d_ws; a.slot_bytes = C.slot_bytes; a.S = C.S;
         a.lds_cols = C.lds_cols; a.n_genes = C.n;
-        HIP_TRY(hipEventRecord(h->class_ev_a(c), st));
+        HIP_TRY(hipEventRecord(h->ev_start[c], st));
         const int lrc = C.ks->baseline(a, C.slots, C.dyn_lds, st);
         if (lrc != 0) return fail(DN_E_HIP, std::string("k_baseline launch: ") + hipGetErrorString((hipError_t) lrc));
-        HIP_TRY(hipEventRecord(h->class_ev_b(c), st));
+        HIP_TRY(hipEventRecord(h->ev_end[c], st));
     }
     for (int c = 1; c < dn_handle_s::NCLS; c++)                                   // results are copied on the main stream
-        if (h->cls[c].n > 0) HIP_TRY(hipStreamWaitEvent(h->stream, h->class_ev_b(c), 0));
+        if (h->data.cls[c].n > 0) HIP_TRY(hipStreamWaitEvent(h->stream[0], h->ev_end[c], 0));
     if (rho) {                          // null: the DI rows stay on the device (dn_outer_partials / dn_outer_apply / dn_fetch_outer)
-        HIP_TRY(hipMemcpyAsync(rho, h->d_rho, sizeof(double) * (size_t) h->n * h->p, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipMemcpyAsync(flags, h->d_flags, sizeof(int32_t) * (size_t) h->n, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(rho, h->data.d_rho, sizeof(double) * (size_t) h->n * h->p, hipMemcpyDeviceToHost, h->stream[0]));
+        HIP_TRY(hipMemcpyAsync(flags, h->data.d_flags, sizeof(int32_t) * (size_t) h->n, hipMemcpyDeviceToHost, h->stream[0]));
     }
     const int32_t tcols = h->trace_cols;
     const size_t trace_ints = (size_t) h->n * (size_t) tcols;
-    if (h->host_trace_len < trace_ints) {
-        if (h->host_trace) { (void) hipHostFree(h->host_trace); h->host_trace = nullptr; h->host_trace_len = 0; }
-        HIP_TRY(hipHostMalloc((void **) &h->host_trace, sizeof(int32_t) * trace_ints, hipHostMallocDefault));
-        h->host_trace_len = trace_ints;
+    if (h->data.host_trace_len < trace_ints) {
+        h->data.host_trace_len = 0;
+        HIP_TRY(h->data.host_trace.alloc(sizeof(int32_t) * trace_ints));
+        h->data.host_trace_len = trace_ints;
     }
     if (tcols == dn::TRACE_LEN)
-        HIP_TRY(hipMemcpyAsync(h->host_trace, h->d_trace, sizeof(int32_t) * trace_ints, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(h->data.host_trace, h->data.d_trace, sizeof(int32_t) * trace_ints, hipMemcpyDeviceToHost, h->stream[0]));
     else {
-        if (!h->d_trace_head) HIP_TRY(hipMalloc(&h->d_trace_head, sizeof(int32_t) * (size_t) h->n * dn::TRACE_LEN));
-        hipLaunchKernelGGL(k_trace_head, dim3((unsigned) std::min<size_t>(1024, (trace_ints + 255) / 256)), dim3(256), 0, h->stream,
-                           h->d_trace, h->d_trace_head, (long long) trace_ints, (int) tcols);
+        if (!h->data.d_trace_head) HIP_TRY(h->data.d_trace_head.alloc(sizeof(int32_t) * (size_t) h->n * dn::TRACE_LEN));
+        hipLaunchKernelGGL(k_trace_head, dim3((unsigned) std::min<size_t>(1024, (trace_ints + 255) / 256)), dim3(256), 0, h->stream[0],
+                           h->data.d_trace, h->data.d_trace_head, (long long) trace_ints, (int) tcols);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(h->host_trace, h->d_trace_head, sizeof(int32_t) * trace_ints, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(h->data.host_trace, h->data.d_trace_head, sizeof(int32_t) * trace_ints, hipMemcpyDeviceToHost, h->stream[0]));
     }
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream[0]));
     h->have_trace = (prm->downsample_rate <= 1);          // with down-sampling the active columns are redrawn every iteration
-    if (trace) std::memcpy(trace, h->host_trace, sizeof(int32_t) * trace_ints);
+    if (trace) std::memcpy(trace, h->data.host_trace, sizeof(int32_t) * trace_ints);
     h->last_span_ms = 0.f;
     for (int c = 0; c < dn_handle_s::NCLS; c++) {
-        if (h->cls[c].n == 0) continue;
-        HIP_TRY(hipEventElapsedTime(&h->cls[c].last_ms, h->class_ev_a(c), h->class_ev_b(c)));
+        if (h->data.cls[c].n == 0) continue;
+        HIP_TRY(hipEventElapsedTime(&h->data.cls[c].last_ms, h->ev_start[c], h->ev_end[c]));
         float span = 0.f;                                                // the classes are launched in order: the first start opens the span
-        HIP_TRY(hipEventElapsedTime(&span, h->class_ev_a(first_cls), h->class_ev_b(c)));
+        HIP_TRY(hipEventElapsedTime(&span, h->ev_start[first_cls], h->ev_end[c]));
         h->last_span_ms = std::max(h->last_span_ms, span);
     }
-    h->last_ms = first_cls >= 0 ? h->cls[first_cls].last_ms : 0.f;
-    h->have_estimate_state = prm->want_estimates != 0;
+    h->last_ms = first_cls >= 0 ? h->data.cls[first_cls].last_ms : 0.f;
+    h->data.have_estimate_state = prm->want_estimates != 0;
     return DN_OK;
 }
 
 static int outer_alloc(dn_handle h, int32_t degnorm_iter)
 {
     const size_t np = (size_t) h->n * h->p;
-    if (!h->d_rhoc) {
-        HIP_TRY(hipMalloc(&h->d_rhoc, sizeof(double) * np));
-        HIP_TRY(hipMalloc(&h->d_xw, sizeof(double) * np));
-        HIP_TRY(hipMalloc(&h->d_xadj, sizeof(double) * np));
+    if (!h->data.d_rhoc) {
+        HIP_TRY(h->data.d_rhoc.alloc(sizeof(double) * np));
+        HIP_TRY(h->data.d_xw.alloc(sizeof(double) * np));
+        HIP_TRY(h->data.d_xadj.alloc(sizeof(double) * np));
     }
-    if (!h->d_part) {
-        HIP_TRY(hipMalloc(&h->d_part, sizeof(double) * (size_t) OUT_BLOCKS * OUT_STRIDE));
-        HIP_TRY(hipMalloc(&h->d_pvec, sizeof(double) * (3 * dn::P_MAX + 4 + 2 * dn::P_MAX)));
+    if (!h->data.d_part) {
+        HIP_TRY(h->data.d_part.alloc(sizeof(double) * (size_t) OUT_BLOCKS * OUT_STRIDE));
+        HIP_TRY(h->data.d_pvec.alloc(sizeof(double) * (3 * dn::P_MAX + 4 + 2 * dn::P_MAX)));
     }
-    if (degnorm_iter > 0 && h->n_iter != degnorm_iter) {
-        if (h->d_ran) { (void) hipFree(h->d_ran); h->d_ran = nullptr; }
-        HIP_TRY(hipMalloc(&h->d_ran, (size_t) h->n * degnorm_iter));
-        h->n_iter = degnorm_iter;
+    if (degnorm_iter > 0 && h->data.n_iter != degnorm_iter) {
+        HIP_TRY(h->data.d_ran.alloc((size_t) h->n * degnorm_iter));
+        h->data.n_iter = degnorm_iter;
     }
     return DN_OK;
 }
 
 int dn_init_begin(dn_handle h, const double *reads)
 {
-    if (!h || !h->d_cov) return fail(DN_E_STATE, "dn_init_begin: nothing uploaded");
+    if (!h || !h->data.d_cov) return fail(DN_E_STATE, "dn_init_begin: nothing uploaded");
     if (!reads) return fail(DN_E_INVALID, "dn_init_begin: null argument");
     HIP_TRY(hipSetDevice(h->device));
     const size_t np = (size_t) h->n * h->p;
-    if (!h->d_x) HIP_TRY(hipMalloc(&h->d_x, sizeof(double) * np));
-    HIP_TRY(hipMemcpyAsync(h->d_x, reads, sizeof(double) * np, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (!h->data.d_x) HIP_TRY(h->data.d_x.alloc(sizeof(double) * np));
+    HIP_TRY(hipMemcpyAsync(h->data.d_x, reads, sizeof(double) * np, hipMemcpyHostToDevice, h->stream[0]));
+    HIP_TRY(hipStreamSynchronize(h->stream[0]));
     return DN_OK;
 }
 
 int dn_init_partials(dn_handle h, double *partials)
 {
-    if (!h || !h->d_x) return fail(DN_E_STATE, "dn_init_partials: dn_init_begin has not been called");
+    if (!h || !h->data.d_x) return fail(DN_E_STATE, "dn_init_partials: dn_init_begin has not been called");
     if (!partials) return fail(DN_E_INVALID, "dn_init_partials: null output");
     HIP_TRY(hipSetDevice(h->device));
     { const int rc = outer_alloc(h, 0); if (rc != DN_OK) return rc; }
     const int blocks = (int) std::min<int64_t>(OUT_BLOCKS, (h->n + 3) / 4);
-    hipLaunchKernelGGL(k_init_partials, dim3(blocks), dim3(256), 0, h->stream, h->d_est_sums, h->d_cov_sums, h->d_status, h->d_x, h->d_part,
+    hipLaunchKernelGGL(k_init_partials, dim3(blocks), dim3(256), 0, h->stream[0], h->data.d_est_sums, h->data.d_cov_sums, h->data.d_status, h->data.d_x, h->data.d_part,
                        (int) h->n, (int) h->p);
-    hipLaunchKernelGGL(k_outer_reduce, dim3(1), dim3(256), 0, h->stream, h->d_part, h->d_pvec, blocks, (int) h->p);
+    hipLaunchKernelGGL(k_outer_reduce, dim3(1), dim3(256), 0, h->stream[0], h->data.d_part, h->data.d_pvec, blocks, (int) h->p);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(partials, h->d_pvec, sizeof(double) * (size_t) (3 * h->p + 4), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpyAsync(partials, h->data.d_pvec, sizeof(double) * (size_t) (3 * h->p + 4), hipMemcpyDeviceToHost, h->stream[0]));
+    HIP_TRY(hipStreamSynchronize(h->stream[0]));
     return DN_OK;
 }
 
 int dn_outer_begin_scaled(dn_handle h, const double *norm, int32_t degnorm_iter)
 {
-    if (!h || !h->d_x) return fail(DN_E_STATE, "dn_outer_begin_scaled: dn_init_begin has not been called");
+    if (!h || !h->data.d_x) return fail(DN_E_STATE, "dn_outer_begin_scaled: dn_init_begin has not been called");
     if (!norm || degnorm_iter < 1) return fail(DN_E_INVALID, "dn_outer_begin_scaled: bad argument");
     HIP_TRY(hipSetDevice(h->device));
     { const int rc = outer_alloc(h, degnorm_iter); if (rc != DN_OK) return rc; }
     const size_t np = (size_t) h->n * h->p;
-    double *d_norm = h->d_pvec + (3 * dn::P_MAX + 4) + dn::P_MAX;
-    HIP_TRY(hipMemsetAsync(h->d_ran, 0, (size_t) h->n * degnorm_iter, h->stream));
-    HIP_TRY(hipMemcpyAsync(d_norm, norm, sizeof(double) * (size_t) h->p, hipMemcpyHostToDevice, h->stream));
+    double *d_norm = h->data.d_pvec + (3 * dn::P_MAX + 4) + dn::P_MAX;
+    HIP_TRY(hipMemsetAsync(h->data.d_ran, 0, (size_t) h->n * degnorm_iter, h->stream[0]));
+    HIP_TRY(hipMemcpyAsync(d_norm, norm, sizeof(double) * (size_t) h->p, hipMemcpyHostToDevice, h->stream[0]));
     const int blocks = (int) std::min<size_t>(2048, (np + 255) / 256);
-    hipLaunchKernelGGL(k_scale_reads, dim3(blocks), dim3(256), 0, h->stream, h->d_x, d_norm, h->d_xw, (long long) np, (int) h->p);
+    hipLaunchKernelGGL(k_scale_reads, dim3(blocks), dim3(256), 0, h->stream[0], h->data.d_x, d_norm, h->data.d_xw, (long long) np, (int) h->p);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream[0]));
     return DN_OK;
 }
 
 int dn_outer_begin(dn_handle h, const double *x_weighted, int32_t degnorm_iter)
 {
-    if (!h || !h->d_cov) return fail(DN_E_STATE, "dn_outer_begin: nothing uploaded");
+    if (!h || !h->data.d_cov) return fail(DN_E_STATE, "dn_outer_begin: nothing uploaded");
     if (!x_weighted || degnorm_iter < 1) return fail(DN_E_INVALID, "dn_outer_begin: bad argument");
     HIP_TRY(hipSetDevice(h->device));
     const size_t np = (size_t) h->n * h->p;
     { const int rc = outer_alloc(h, degnorm_iter); if (rc != DN_OK) return rc; }
-    HIP_TRY(hipMemsetAsync(h->d_ran, 0, (size_t) h->n * degnorm_iter, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->d_xw, x_weighted, sizeof(double) * np, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemsetAsync(h->data.d_ran, 0, (size_t) h->n * degnorm_iter, h->stream[0]));
+    HIP_TRY(hipMemcpyAsync(h->data.d_xw, x_weighted, sizeof(double) * np, hipMemcpyHostToDevice, h->stream[0]));
+    HIP_TRY(hipStreamSynchronize(h->stream[0]));
     return DN_OK;
 }
 
 int dn_outer_partials(dn_handle h, double *partials)
 {
-    if (!h || !h->d_xw) return fail(DN_E_STATE, "dn_outer_partials: dn_outer_begin has not been called");
+    if (!h || !h->data.d_xw) return fail(DN_E_STATE, "dn_outer_partials: dn_outer_begin has not been called");
     if (!partials) return fail(DN_E_INVALID, "dn_outer_partials: null output");
     HIP_TRY(hipSetDevice(h->device));
     const int blocks = (int) std::min<int64_t>(OUT_BLOCKS, (h->n + 3) / 4);
-    hipLaunchKernelGGL(k_outer_partials, dim3(blocks), dim3(256), 0, h->stream, h->d_rho, h->d_rhoc, h->d_xw, h->d_trace, h->d_flags, h->d_part,
+    hipLaunchKernelGGL(k_outer_partials, dim3(blocks), dim3(256), 0, h->stream[0], h->data.d_rho, h->data.d_rhoc, h->data.d_xw, h->data.d_trace, h->data.d_flags, h->data.d_part,
                        (int) h->n, (int) h->p);
-    hipLaunchKernelGGL(k_outer_reduce, dim3(1), dim3(256), 0, h->stream, h->d_part, h->d_pvec, blocks, (int) h->p);
+    hipLaunchKernelGGL(k_outer_reduce, dim3(1), dim3(256), 0, h->stream[0], h->data.d_part, h->data.d_pvec, blocks, (int) h->p);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(partials, h->d_pvec, sizeof(double) * (size_t) (3 * h->p + 4), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpyAsync(partials, h->data.d_pvec, sizeof(double) * (size_t) (3 * h->p + 4), hipMemcpyDeviceToHost, h->stream[0]));
+    HIP_TRY(hipStreamSynchronize(h->stream[0]));
     return DN_OK;
 }
 
 int dn_outer_partials_device(dn_handle h, double **d_partials)
 {
-    if (!h || !h->d_xw) return fail(DN_E_STATE, "dn_outer_partials_device: dn_outer_begin has not been called");
+    if (!h || !h->data.d_xw) return fail(DN_E_STATE, "dn_outer_partials_device: dn_outer_begin has not been called");
     if (!d_partials) return fail(DN_E_INVALID, "dn_outer_partials_device: null output");
     HIP_TRY(hipSetDevice(h->device));
     const int blocks = (int) std::min<int64_t>(OUT_BLOCKS, (h->n + 3) / 4);
-    hipLaunchKernelGGL(k_outer_partials, dim3(blocks), dim3(256), 0, h->stream, h->d_rho, h->d_rhoc, h->d_xw, h->d_trace, h->d_flags, h->d_part,
+    hipLaunchKernelGGL(k_outer_partials, dim3(blocks), dim3(256), 0, h->stream[0], h->data.d_rho, h->data.d_rhoc, h->data.d_xw, h->data.d_trace, h->data.d_flags, h->data.d_part,
                        (int) h->n, (int) h->p);
-    hipLaunchKernelGGL(k_outer_reduce, dim3(1), dim3(256), 0, h->stream, h->d_part, h->d_pvec, blocks, (int) h->p);
+    hipLaunchKernelGGL(k_outer_reduce, dim3(1), dim3(256), 0, h->stream[0], h->data.d_part, h->data.d_pvec, blocks, (int) h->p);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(h->stream));           // the collective runs on the caller's stream: the sums must be there
-    *d_partials = h->d_pvec;
+    HIP_TRY(hipStreamSynchronize(h->stream[0]));           // the collective runs on the caller's stream: the sums must be there
+    *d_partials = h->data.d_pvec;
     return DN_OK;
 }
 
 int dn_outer_apply(dn_handle h, const double *avg_di, const double *norm, int32_t iter)
 {
-    if (!h || !h->d_xw) return fail(DN_E_STATE, "dn_outer_apply: dn_outer_begin has not been called");
+    if (!h || !h->data.d_xw) return fail(DN_E_STATE, "dn_outer_apply: dn_outer_begin has not been called");
     if (!norm || iter < 0) return fail(DN_E_INVALID, "dn_outer_apply: bad argument");
     HIP_TRY(hipSetDevice(h->device));
-    double *d_avg = h->d_pvec + (3 * dn::P_MAX + 4), *d_norm = d_avg + dn::P_MAX;
-    if (avg_di) HIP_TRY(hipMemcpyAsync(d_avg, avg_di, sizeof(double) * (size_t) h->p, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(d_norm, norm, sizeof(double) * (size_t) h->p, hipMemcpyHostToDevice, h->stream));
+    double *d_avg = h->data.d_pvec + (3 * dn::P_MAX + 4), *d_norm = d_avg + dn::P_MAX;
+    if (avg_di) HIP_TRY(hipMemcpyAsync(d_avg, avg_di, sizeof(double) * (size_t) h->p, hipMemcpyHostToDevice, h->stream[0]));
+    HIP_TRY(hipMemcpyAsync(d_norm, norm, sizeof(double) * (size_t) h->p, hipMemcpyHostToDevice, h->stream[0]));
     const int blocks = (int) std::min<int64_t>(OUT_BLOCKS, (h->n + 3) / 4);
-    hipLaunchKernelGGL(k_outer_apply, dim3(blocks), dim3(256), 0, h->stream, h->d_rhoc, h->d_xw, h->d_xadj, h->d_flags, h->d_ran, d_avg, d_norm,
-                       avg_di ? 1 : 0, (int) h->n, (int) h->p, (int) iter, (int) h->n_iter);
+    hipLaunchKernelGGL(k_outer_apply, dim3(blocks), dim3(256), 0, h->stream[0], h->data.d_rhoc, h->data.d_xw, h->data.d_xadj, h->data.d_flags, h->data.d_ran, d_avg, d_norm,
+                       avg_di ? 1 : 0, (int) h->n, (int) h->p, (int) iter, (int) h->data.n_iter);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(h->stream));           // the host buffers behind avg_di / norm may go away
+    HIP_TRY(hipStreamSynchronize(h->stream[0]));           // the host buffers behind avg_di / norm may go away
     return DN_OK;
 }
 
@@ -1351,7 +1273,7 @@ int dn_comm_create(dn_handle h, const uint8_t *id, int32_t rank, int32_t size)
     ncclComm_t c = nullptr;
     RCCL_TRY(api, api->CommInitRank(&c, size, u, rank));
     h->comm = c; h->comm_rank = rank; h->comm_size = size;
-    if (!h->d_comm) HIP_TRY(hipMalloc(&h->d_comm, sizeof(double) * 256));
+    if (!h->d_comm) HIP_TRY(h->d_comm.alloc(sizeof(double) * 256));
     return DN_OK;
 }
 
@@ -1361,10 +1283,10 @@ int dn_comm_destroy(dn_handle h)
     std::string err;
     RcclApi *api = rccl_api(err);
     (void) hipSetDevice(h->device);
-    if (h->stream) (void) hipStreamSynchronize(h->stream);
+    if (h->stream[0]) (void) hipStreamSynchronize(h->stream[0]);
     if (api) (void) api->CommDestroy((ncclComm_t) h->comm);
     h->comm = nullptr; h->comm_size = 0; h->comm_rank = 0;
-    if (h->d_comm) { (void) hipFree(h->d_comm); h->d_comm = nullptr; }
+    h->d_comm.reset();
     return DN_OK;
 }
 
@@ -1388,9 +1310,9 @@ static int allreduce_to_host(dn_handle h, double *d_buf, int32_t count, double *
     std::string err;
     RcclApi *api = rccl_api(err);
     if (!api) return fail(DN_E_STATE, err);
-    RCCL_TRY(api, api->AllReduce(d_buf, d_buf, (size_t) count, ncclDouble, ncclSum, (ncclComm_t) h->comm, h->stream));
-    HIP_TRY(hipMemcpyAsync(totals, d_buf, sizeof(double) * (size_t) count, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    RCCL_TRY(api, api->AllReduce(d_buf, d_buf, (size_t) count, ncclDouble, ncclSum, (ncclComm_t) h->comm, h->stream[0]));
+    HIP_TRY(hipMemcpyAsync(totals, d_buf, sizeof(double) * (size_t) count, hipMemcpyDeviceToHost, h->stream[0]));
+    HIP_TRY(hipStreamSynchronize(h->stream[0]));
     return DN_OK;
 }
 
@@ -1399,73 +1321,72 @@ int dn_comm_allreduce(dn_handle h, double *buf, int32_t count)
     if (!h || !h->comm) return fail(DN_E_STATE, "dn_comm_allreduce: dn_comm_create has not been called");
     if (!buf || count < 1 || count > 256) return fail(DN_E_INVALID, "dn_comm_allreduce: 1 .. 256 doubles");
     HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipMemcpyAsync(h->d_comm, buf, sizeof(double) * (size_t) count, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->d_comm, buf, sizeof(double) * (size_t) count, hipMemcpyHostToDevice, h->stream[0]));
     return allreduce_to_host(h, h->d_comm, count, buf);
 }
 
 int dn_init_allreduce(dn_handle h, double *totals)
 {
     if (!h || !h->comm) return fail(DN_E_STATE, "dn_init_allreduce: dn_comm_create has not been called");
-    if (!h->d_x) return fail(DN_E_STATE, "dn_init_allreduce: dn_init_begin has not been called");
+    if (!h->data.d_x) return fail(DN_E_STATE, "dn_init_allreduce: dn_init_begin has not been called");
     if (!totals) return fail(DN_E_INVALID, "dn_init_allreduce: null output");
     HIP_TRY(hipSetDevice(h->device));
     { const int rc = outer_alloc(h, 0); if (rc != DN_OK) return rc; }
     const int blocks = (int) std::min<int64_t>(OUT_BLOCKS, (h->n + 3) / 4);
-    hipLaunchKernelGGL(k_init_partials, dim3(blocks), dim3(256), 0, h->stream, h->d_est_sums, h->d_cov_sums, h->d_status, h->d_x, h->d_part,
+    hipLaunchKernelGGL(k_init_partials, dim3(blocks), dim3(256), 0, h->stream[0], h->data.d_est_sums, h->data.d_cov_sums, h->data.d_status, h->data.d_x, h->data.d_part,
                        (int) h->n, (int) h->p);
-    hipLaunchKernelGGL(k_outer_reduce, dim3(1), dim3(256), 0, h->stream, h->d_part, h->d_pvec, blocks, (int) h->p);
+    hipLaunchKernelGGL(k_outer_reduce, dim3(1), dim3(256), 0, h->stream[0], h->data.d_part, h->data.d_pvec, blocks, (int) h->p);
     HIP_TRY(hipGetLastError());
-    return allreduce_to_host(h, h->d_pvec, 3 * h->p + 4, totals);
+    return allreduce_to_host(h, h->data.d_pvec, 3 * h->p + 4, totals);
 }
 
 int dn_outer_allreduce(dn_handle h, double *totals)
 {
     if (!h || !h->comm) return fail(DN_E_STATE, "dn_outer_allreduce: dn_comm_create has not been called");
-    if (!h->d_xw) return fail(DN_E_STATE, "dn_outer_allreduce: dn_outer_begin has not been called");
+    if (!h->data.d_xw) return fail(DN_E_STATE, "dn_outer_allreduce: dn_outer_begin has not been called");
     if (!totals) return fail(DN_E_INVALID, "dn_outer_allreduce: null output");
     HIP_TRY(hipSetDevice(h->device));
     const int blocks = (int) std::min<int64_t>(OUT_BLOCKS, (h->n + 3) / 4);
-    hipLaunchKernelGGL(k_outer_partials, dim3(blocks), dim3(256), 0, h->stream, h->d_rho, h->d_rhoc, h->d_xw, h->d_trace, h->d_flags, h->d_part,
+    hipLaunchKernelGGL(k_outer_partials, dim3(blocks), dim3(256), 0, h->stream[0], h->data.d_rho, h->data.d_rhoc, h->data.d_xw, h->data.d_trace, h->data.d_flags, h->data.d_part,
                        (int) h->n, (int) h->p);
-    hipLaunchKernelGGL(k_outer_reduce, dim3(1), dim3(256), 0, h->stream, h->d_part, h->d_pvec, blocks, (int) h->p);
+    hipLaunchKernelGGL(k_outer_reduce, dim3(1), dim3(256), 0, h->stream[0], h->data.d_part, h->data.d_pvec, blocks, (int) h->p);
     HIP_TRY(hipGetLastError());
-    return allreduce_to_host(h, h->d_pvec, 3 * h->p + 4, totals);
+    return allreduce_to_host(h, h->data.d_pvec, 3 * h->p + 4, totals);
 }
 
 int dn_fetch_outer(dn_handle h, double *rho, double *x_adj, double *x_weighted, uint8_t *ran)
 {
-    if (!h || !h->d_xw) return fail(DN_E_STATE, "dn_fetch_outer: dn_outer_begin has not been called");
+    if (!h || !h->data.d_xw) return fail(DN_E_STATE, "dn_fetch_outer: dn_outer_begin has not been called");
     HIP_TRY(hipSetDevice(h->device));
     const size_t np = (size_t) h->n * h->p;
-    if (rho) HIP_TRY(hipMemcpyAsync(rho, h->d_rhoc, sizeof(double) * np, hipMemcpyDeviceToHost, h->stream));
-    if (x_adj) HIP_TRY(hipMemcpyAsync(x_adj, h->d_xadj, sizeof(double) * np, hipMemcpyDeviceToHost, h->stream));
-    if (x_weighted) HIP_TRY(hipMemcpyAsync(x_weighted, h->d_xw, sizeof(double) * np, hipMemcpyDeviceToHost, h->stream));
-    if (ran) HIP_TRY(hipMemcpyAsync(ran, h->d_ran, (size_t) h->n * h->n_iter, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (rho) HIP_TRY(hipMemcpyAsync(rho, h->data.d_rhoc, sizeof(double) * np, hipMemcpyDeviceToHost, h->stream[0]));
+    if (x_adj) HIP_TRY(hipMemcpyAsync(x_adj, h->data.d_xadj, sizeof(double) * np, hipMemcpyDeviceToHost, h->stream[0]));
+    if (x_weighted) HIP_TRY(hipMemcpyAsync(x_weighted, h->data.d_xw, sizeof(double) * np, hipMemcpyDeviceToHost, h->stream[0]));
+    if (ran) HIP_TRY(hipMemcpyAsync(ran, h->data.d_ran, (size_t) h->n * h->data.n_iter, hipMemcpyDeviceToHost, h->stream[0]));
+    HIP_TRY(hipStreamSynchronize(h->stream[0]));
     return DN_OK;
 }
 
 int dn_fetch_rows(dn_handle h, int64_t n_rows, const int64_t *rows, double *rho_raw, int32_t *flags)
 {
-    if (!h || !h->d_cov) return fail(DN_E_STATE, "dn_fetch_rows: nothing uploaded");
+    if (!h || !h->data.d_cov) return fail(DN_E_STATE, "dn_fetch_rows: nothing uploaded");
     if (n_rows <= 0 || !rows || !rho_raw || !flags) return fail(DN_E_INVALID, "dn_fetch_rows: bad argument");
     for (int64_t k = 0; k < n_rows; k++) if (rows[k] < 0 || rows[k] >= h->n) return fail(DN_E_INVALID, "dn_fetch_rows: row out of range");
     HIP_TRY(hipSetDevice(h->device));
-    int64_t *d_rows = nullptr; double *d_out = nullptr; int32_t *d_fl = nullptr;
-    HIP_TRY(hipMalloc(&d_rows, sizeof(int64_t) * (size_t) n_rows));
-    hipError_t e = hipMalloc(&d_out, sizeof(double) * (size_t) n_rows * h->p);
-    if (e == hipSuccess) e = hipMalloc(&d_fl, sizeof(int32_t) * (size_t) n_rows);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_rows, rows, sizeof(int64_t) * (size_t) n_rows, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) {
-        const int tot = (int) (n_rows * h->p);
-        hipLaunchKernelGGL(k_gather_rows, dim3((tot + 255) / 256), dim3(256), 0, h->stream, h->d_rho, h->d_flags, d_rows, d_out, d_fl, (int) n_rows, (int) h->p);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(rho_raw, d_out, sizeof(double) * (size_t) n_rows * h->p, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(flags, d_fl, sizeof(int32_t) * (size_t) n_rows, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    (void) hipFree(d_rows); if (d_out) (void) hipFree(d_out); if (d_fl) (void) hipFree(d_fl);
-    if (e != hipSuccess) return fail(DN_E_HIP, std::string("dn_fetch_rows: ") + hipGetErrorString(e));
+    const char *what = "dn_fetch_rows";
+    dn::DeviceBuffer<int64_t> d_rows;
+    dn::DeviceBuffer<double> d_out;
+    dn::DeviceBuffer<int32_t> d_fl;
+    HIP_TRY(d_rows.alloc(sizeof(int64_t) * (size_t) n_rows));
+    HIP_TRY_AS(what, d_out.alloc(sizeof(double) * (size_t) n_rows * h->p));
+    HIP_TRY_AS(what, d_fl.alloc(sizeof(int32_t) * (size_t) n_rows));
+    HIP_TRY_AS(what, hipMemcpyAsync(d_rows, rows, sizeof(int64_t) * (size_t) n_rows, hipMemcpyHostToDevice, h->stream[0]));
+    const int tot = (int) (n_rows * h->p);
+    hipLaunchKernelGGL(k_gather_rows, dim3((tot + 255) / 256), dim3(256), 0, h->stream[0], h->data.d_rho, h->data.d_flags, d_rows, d_out, d_fl, (int) n_rows, (int) h->p);
+    HIP_TRY_AS(what, hipGetLastError());
+    HIP_TRY_AS(what, hipMemcpyAsync(rho_raw, d_out, sizeof(double) * (size_t) n_rows * h->p, hipMemcpyDeviceToHost, h->stream[0]));
+    HIP_TRY_AS(what, hipMemcpyAsync(flags, d_fl, sizeof(int32_t) * (size_t) n_rows, hipMemcpyDeviceToHost, h->stream[0]));
+    HIP_TRY_AS(what, hipStreamSynchronize(h->stream[0]));
     return DN_OK;
 }
 
@@ -1489,28 +1410,28 @@ static void prefault_pages(void *ptr, size_t bytes, int n_threads)
 
 int dn_fetch_estimates(dn_handle h, double *out)
 {
-    if (!h || !h->d_cov) return fail(DN_E_STATE, "dn_fetch_estimates: nothing uploaded");
-    if (!h->have_estimate_state) return fail(DN_E_STATE, "dn_fetch_estimates: last iteration did not run with want_estimates = 1");
+    if (!h || !h->data.d_cov) return fail(DN_E_STATE, "dn_fetch_estimates: nothing uploaded");
+    if (!h->data.have_estimate_state) return fail(DN_E_STATE, "dn_fetch_estimates: last iteration did not run with want_estimates = 1");
     if (!out) return fail(DN_E_INVALID, "dn_fetch_estimates: null output");
     HIP_TRY(hipSetDevice(h->device));
-    if (!h->d_est) HIP_TRY(hipMalloc(&h->d_est, sizeof(double) * (size_t) h->total));
+    if (!h->data.d_est) HIP_TRY(h->data.d_est.alloc(sizeof(double) * (size_t) h->total));
     dn::EstArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.cov = h->d_cov; a.goff = h->d_goff; a.glen = h->d_glen; a.kfin = h->d_kfin; a.emode = h->d_emode;
-    a.svec = h->d_svec; a.svoff = h->d_svoff; a.out = h->d_est; a.n_genes = (int32_t) h->n; a.p = h->p;
+    a.cov = h->data.d_cov; a.goff = h->data.d_goff; a.glen = h->data.d_glen; a.kfin = h->data.d_kfin; a.emode = h->data.d_emode;
+    a.svec = h->data.d_svec; a.svoff = h->data.d_svoff; a.out = h->data.d_est; a.n_genes = (int32_t) h->n; a.p = h->p;
     for (int i = 0; i < dn::P_MAX; i++) a.scale[i] = i < h->p ? h->last_scale[i] : 1.0;
-    h->ks->est(a, h->d_tile_gene, h->d_tile_col, (int) h->n_tiles, h->stream);
+    h->ks->est(a, h->data.d_tile_gene, h->data.d_tile_col, (int) h->n_tiles, h->stream[0]);
     HIP_TRY(hipGetLastError());
     prefault_pages(out, sizeof(double) * (size_t) h->total, (int) std::thread::hardware_concurrency());     // while the kernel runs
-    HIP_TRY(hipMemcpyAsync(out, h->d_est, sizeof(double) * (size_t) h->total, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpyAsync(out, h->data.d_est, sizeof(double) * (size_t) h->total, hipMemcpyDeviceToHost, h->stream[0]));
+    HIP_TRY(hipStreamSynchronize(h->stream[0]));
     return DN_OK;
 }
 
 int dn_fetch_estimates_subset(dn_handle h, int64_t n_sel, const int64_t *gene_ids, double *out)
 {
-    if (!h || !h->d_cov) return fail(DN_E_STATE, "dn_fetch_estimates_subset: nothing uploaded");
-    if (!h->have_estimate_state) return fail(DN_E_STATE, "dn_fetch_estimates_subset: last iteration did not run with want_estimates = 1");
+    if (!h || !h->data.d_cov) return fail(DN_E_STATE, "dn_fetch_estimates_subset: nothing uploaded");
+    if (!h->data.have_estimate_state) return fail(DN_E_STATE, "dn_fetch_estimates_subset: last iteration did not run with want_estimates = 1");
     if (n_sel <= 0 || !gene_ids || !out) return fail(DN_E_INVALID, "dn_fetch_estimates_subset: bad argument");
     HIP_TRY(hipSetDevice(h->device));
     std::vector<int64_t> ooff(h->n, -1);
@@ -1524,32 +1445,26 @@ int dn_fetch_estimates_subset(dn_handle h, int64_t n_sel, const int64_t *gene_id
         total += (int64_t) h->p * h->glen[g];
         for (int32_t c = 0; c < h->glen[g]; c += 256) { tg.push_back((int32_t) g); tc.push_back(c); }
     }
-    double *d_out = nullptr; int64_t *d_ooff = nullptr; int32_t *d_tg = nullptr, *d_tc = nullptr;
-    hipError_t le = hipMalloc(&d_out, sizeof(double) * (size_t) total);            // nothing leaks on a failure half-way
-    if (le == hipSuccess) le = hipMalloc(&d_ooff, sizeof(int64_t) * (size_t) h->n);
-    if (le == hipSuccess) le = hipMalloc(&d_tg, sizeof(int32_t) * tg.size());
-    if (le == hipSuccess) le = hipMalloc(&d_tc, sizeof(int32_t) * tc.size());
-    if (le == hipSuccess) le = hipMemcpyAsync(d_ooff, ooff.data(), sizeof(int64_t) * (size_t) h->n, hipMemcpyHostToDevice, h->stream);
-    if (le == hipSuccess) le = hipMemcpyAsync(d_tg, tg.data(), sizeof(int32_t) * tg.size(), hipMemcpyHostToDevice, h->stream);
-    if (le == hipSuccess) le = hipMemcpyAsync(d_tc, tc.data(), sizeof(int32_t) * tc.size(), hipMemcpyHostToDevice, h->stream);
-    if (le != hipSuccess) {
-        if (d_out) (void) hipFree(d_out);
-        if (d_ooff) (void) hipFree(d_ooff);
-        if (d_tg) (void) hipFree(d_tg);
-        if (d_tc) (void) hipFree(d_tc);
-        return fail(DN_E_HIP, std::string("dn_fetch_estimates_subset: ") + hipGetErrorString(le));
-    }
+    const char *what = "dn_fetch_estimates_subset";
+    dn::DeviceBuffer<double> d_out;
+    dn::DeviceBuffer<int64_t> d_ooff;
+    dn::DeviceBuffer<int32_t> d_tg, d_tc;
+    HIP_TRY_AS(what, d_out.alloc(sizeof(double) * (size_t) total));
+    HIP_TRY_AS(what, d_ooff.alloc(sizeof(int64_t) * (size_t) h->n));
+    HIP_TRY_AS(what, d_tg.alloc(sizeof(int32_t) * tg.size()));
+    HIP_TRY_AS(what, d_tc.alloc(sizeof(int32_t) * tc.size()));
+    HIP_TRY_AS(what, hipMemcpyAsync(d_ooff, ooff.data(), sizeof(int64_t) * (size_t) h->n, hipMemcpyHostToDevice, h->stream[0]));
+    HIP_TRY_AS(what, hipMemcpyAsync(d_tg, tg.data(), sizeof(int32_t) * tg.size(), hipMemcpyHostToDevice, h->stream[0]));
+    HIP_TRY_AS(what, hipMemcpyAsync(d_tc, tc.data(), sizeof(int32_t) * tc.size(), hipMemcpyHostToDevice, h->stream[0]));
     dn::EstArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.cov = h->d_cov; a.goff = h->d_goff; a.glen = h->d_glen; a.kfin = h->d_kfin; a.emode = h->d_emode;
-    a.svec = h->d_svec; a.svoff = h->d_svoff; a.out = d_out; a.ooff = d_ooff; a.n_genes = (int32_t) h->n; a.p = h->p;
+    a.cov = h->data.d_cov; a.goff = h->data.d_goff; a.glen = h->data.d_glen; a.kfin = h->data.d_kfin; a.emode = h->data.d_emode;
+    a.svec = h->data.d_svec; a.svoff = h->data.d_svoff; a.out = d_out; a.ooff = d_ooff; a.n_genes = (int32_t) h->n; a.p = h->p;
     for (int i = 0; i < dn::P_MAX; i++) a.scale[i] = i < h->p ? h->last_scale[i] : 1.0;
-    h->ks->est(a, d_tg, d_tc, (int) tg.size(), h->stream);
-    le = hipGetLastError();
-    if (le == hipSuccess) le = hipMemcpyAsync(out, d_out, sizeof(double) * (size_t) total, hipMemcpyDeviceToHost, h->stream);
-    if (le == hipSuccess) le = hipStreamSynchronize(h->stream);
-    (void) hipFree(d_out); (void) hipFree(d_ooff); (void) hipFree(d_tg); (void) hipFree(d_tc);
-    if (le != hipSuccess) return fail(DN_E_HIP, std::string("dn_fetch_estimates_subset: ") + hipGetErrorString(le));
+    h->ks->est(a, d_tg, d_tc, (int) tg.size(), h->stream[0]);
+    HIP_TRY_AS(what, hipGetLastError());
+    HIP_TRY_AS(what, hipMemcpyAsync(out, d_out, sizeof(double) * (size_t) total, hipMemcpyDeviceToHost, h->stream[0]));
+    HIP_TRY_AS(what, hipStreamSynchronize(h->stream[0]));
     return DN_OK;
 }
 
@@ -1583,46 +1498,46 @@ int dn_nmf_f64(dn_handle h, int64_t n, int32_t p, const double *const *x, const 
     const int grid = f64_grid(h, 1, n, slot_bytes);
     if (grid < 1) return fail(DN_E_INVALID, "dn_nmf_f64: " + g_err);
 
-    F64Buffers B;
     dn::NmfArgsF64 a;
     std::memset(&a, 0, sizeof(a));
-    double *d_x = nullptr, *d_K = nullptr, *d_E = nullptr, *d_est = nullptr;
-    int64_t *d_xoff = nullptr, *d_eoff = nullptr;
-    int32_t *d_ncol = nullptr, *d_order = nullptr, *d_counter = nullptr, *d_status = nullptr;
-    char *d_ws = nullptr;
-    HIP_TRY(B.alloc(&d_x, (size_t) total));
-    HIP_TRY(B.alloc(&d_xoff, (size_t) n));
-    HIP_TRY(B.alloc(&d_eoff, (size_t) n));
-    HIP_TRY(B.alloc(&d_ncol, (size_t) n));
-    HIP_TRY(B.alloc(&d_order, (size_t) n));
-    HIP_TRY(B.alloc(&d_counter, 4));
-    HIP_TRY(B.alloc(&d_status, (size_t) n));
-    HIP_TRY(B.alloc(&d_K, (size_t) n * p));
-    HIP_TRY(B.alloc(&d_E, (size_t) eoff[n]));
-    if (est) HIP_TRY(B.alloc(&d_est, (size_t) total));
-    HIP_TRY(B.alloc(&d_ws, (size_t) slot_bytes * (size_t) grid));
-    HIP_TRY(hipEventCreate(&B.e0));
-    HIP_TRY(hipEventCreate(&B.e1));
-    HIP_TRY(hipMemcpyAsync(d_x, packed.data(), sizeof(double) * (size_t) total, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(d_xoff, xoff.data(), sizeof(int64_t) * (size_t) n, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(d_eoff, eoff.data(), sizeof(int64_t) * (size_t) n, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(d_ncol, ncol.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(d_order, order.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemsetAsync(d_counter, 0, sizeof(int32_t) * 4, h->stream));
+    dn::DeviceBuffer<double> d_x, d_K, d_E, d_est;
+    dn::DeviceBuffer<int64_t> d_xoff, d_eoff;
+    dn::DeviceBuffer<int32_t> d_ncol, d_order, d_counter, d_status;
+    dn::DeviceBuffer<char> d_ws;
+    dn::Event e0, e1;
+    HIP_TRY(alloc_f64(d_x, (size_t) total));
+    HIP_TRY(alloc_f64(d_xoff, (size_t) n));
+    HIP_TRY(alloc_f64(d_eoff, (size_t) n));
+    HIP_TRY(alloc_f64(d_ncol, (size_t) n));
+    HIP_TRY(alloc_f64(d_order, (size_t) n));
+    HIP_TRY(alloc_f64(d_counter, 4));
+    HIP_TRY(alloc_f64(d_status, (size_t) n));
+    HIP_TRY(alloc_f64(d_K, (size_t) n * p));
+    HIP_TRY(alloc_f64(d_E, (size_t) eoff[n]));
+    if (est) HIP_TRY(alloc_f64(d_est, (size_t) total));
+    HIP_TRY(alloc_f64(d_ws, (size_t) slot_bytes * (size_t) grid));
+    HIP_TRY(e0.create(hipEventCreate));
+    HIP_TRY(e1.create(hipEventCreate));
+    HIP_TRY(hipMemcpyAsync(d_x, packed.data(), sizeof(double) * (size_t) total, hipMemcpyHostToDevice, h->stream[0]));
+    HIP_TRY(hipMemcpyAsync(d_xoff, xoff.data(), sizeof(int64_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
+    HIP_TRY(hipMemcpyAsync(d_eoff, eoff.data(), sizeof(int64_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
+    HIP_TRY(hipMemcpyAsync(d_ncol, ncol.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
+    HIP_TRY(hipMemcpyAsync(d_order, order.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
+    HIP_TRY(hipMemsetAsync(d_counter, 0, sizeof(int32_t) * 4, h->stream[0]));
     a.x = d_x; a.xoff = d_xoff; a.ncol = d_ncol; a.eoff = d_eoff; a.order = d_order; a.counter = d_counter;
     a.K = d_K; a.E = d_E; a.est = d_est; a.status = d_status; a.ws = d_ws; a.slot_bytes = slot_bytes;
     a.n = (int32_t) n; a.p = p; a.T = mode == DN_NMF ? nmf_iter : 0; a.ratio = mode == DN_NMF_RATIO ? 1 : 0;
     a.max_steps = h->max_steps;
-    HIP_TRY(hipEventRecord(B.e0, h->stream));
-    const int lrc = dn::launch_nmf_f64(a, grid, h->stream);
+    HIP_TRY(hipEventRecord(e0, h->stream[0]));
+    const int lrc = dn::launch_nmf_f64(a, grid, h->stream[0]);
     if (lrc != 0) return fail(DN_E_HIP, std::string("k_nmf_f64 launch: ") + hipGetErrorString((hipError_t) lrc));
-    HIP_TRY(hipEventRecord(B.e1, h->stream));
-    HIP_TRY(hipMemcpyAsync(K, d_K, sizeof(double) * (size_t) n * p, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(E, d_E, sizeof(double) * (size_t) eoff[n], hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(status, d_status, sizeof(int32_t) * (size_t) n, hipMemcpyDeviceToHost, h->stream));
-    if (est) HIP_TRY(hipMemcpyAsync(est, d_est, sizeof(double) * (size_t) total, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipEventElapsedTime(&h->last_f64_ms, B.e0, B.e1));
+    HIP_TRY(hipEventRecord(e1, h->stream[0]));
+    HIP_TRY(hipMemcpyAsync(K, d_K, sizeof(double) * (size_t) n * p, hipMemcpyDeviceToHost, h->stream[0]));
+    HIP_TRY(hipMemcpyAsync(E, d_E, sizeof(double) * (size_t) eoff[n], hipMemcpyDeviceToHost, h->stream[0]));
+    HIP_TRY(hipMemcpyAsync(status, d_status, sizeof(int32_t) * (size_t) n, hipMemcpyDeviceToHost, h->stream[0]));
+    if (est) HIP_TRY(hipMemcpyAsync(est, d_est, sizeof(double) * (size_t) total, hipMemcpyDeviceToHost, h->stream[0]));
+    HIP_TRY(hipStreamSynchronize(h->stream[0]));
+    HIP_TRY(hipEventElapsedTime(&h->last_f64_ms, e0, e1));
     return DN_OK;
 }
 
@@ -1670,49 +1585,49 @@ int dn_baseline_selection_f64(dn_handle h, int64_t n, int32_t p, const double *c
     const int grid = f64_grid(h, 0, n, slot_bytes);
     if (grid < 1) return fail(DN_E_INVALID, "dn_baseline_selection_f64: " + g_err);
 
-    F64Buffers B;
-    double *d_cov = nullptr, *d_rowmax = nullptr, *d_rho = nullptr, *d_kfin = nullptr, *d_svec = nullptr, *d_est = nullptr;
-    int64_t *d_goff = nullptr, *d_ds = nullptr, *d_svoff = nullptr;
-    int32_t *d_glen = nullptr, *d_order = nullptr, *d_counter = nullptr, *d_flags = nullptr, *d_trace = nullptr, *d_emode = nullptr;
-    int32_t *d_tg = nullptr, *d_tc = nullptr;
-    char *d_ws = nullptr;
-    HIP_TRY(B.alloc(&d_cov, (size_t) total));
-    HIP_TRY(B.alloc(&d_goff, (size_t) n + 1));
-    HIP_TRY(B.alloc(&d_glen, (size_t) n));
-    HIP_TRY(B.alloc(&d_order, (size_t) n));
-    HIP_TRY(B.alloc(&d_counter, 4));
-    HIP_TRY(B.alloc(&d_rowmax, (size_t) n * p));
-    HIP_TRY(B.alloc(&d_rho, (size_t) n * p));
-    HIP_TRY(B.alloc(&d_flags, (size_t) n));
-    HIP_TRY(B.alloc(&d_trace, (size_t) n * dn::TRACE_LEN));
-    HIP_TRY(B.alloc(&d_kfin, (size_t) n * p));
-    HIP_TRY(B.alloc(&d_emode, (size_t) n));
-    HIP_TRY(B.alloc(&d_ws, (size_t) slot_bytes * (size_t) grid));
-    if (prm->downsample_rate > 1) HIP_TRY(B.alloc(&d_ds, (size_t) n));
+    dn::DeviceBuffer<double> d_cov, d_rowmax, d_rho, d_kfin, d_svec, d_est;
+    dn::DeviceBuffer<int64_t> d_goff, d_ds, d_svoff;
+    dn::DeviceBuffer<int32_t> d_glen, d_order, d_counter, d_flags, d_trace, d_emode;
+    dn::DeviceBuffer<int32_t> d_tg, d_tc;
+    dn::DeviceBuffer<char> d_ws;
+    dn::Event e0, e1;
+    HIP_TRY(alloc_f64(d_cov, (size_t) total));
+    HIP_TRY(alloc_f64(d_goff, (size_t) n + 1));
+    HIP_TRY(alloc_f64(d_glen, (size_t) n));
+    HIP_TRY(alloc_f64(d_order, (size_t) n));
+    HIP_TRY(alloc_f64(d_counter, 4));
+    HIP_TRY(alloc_f64(d_rowmax, (size_t) n * p));
+    HIP_TRY(alloc_f64(d_rho, (size_t) n * p));
+    HIP_TRY(alloc_f64(d_flags, (size_t) n));
+    HIP_TRY(alloc_f64(d_trace, (size_t) n * dn::TRACE_LEN));
+    HIP_TRY(alloc_f64(d_kfin, (size_t) n * p));
+    HIP_TRY(alloc_f64(d_emode, (size_t) n));
+    HIP_TRY(alloc_f64(d_ws, (size_t) slot_bytes * (size_t) grid));
+    if (prm->downsample_rate > 1) HIP_TRY(alloc_f64(d_ds, (size_t) n));
     if (est) {
-        HIP_TRY(B.alloc(&d_svoff, (size_t) n + 1));
-        HIP_TRY(B.alloc(&d_svec, (size_t) svoff[n]));
-        HIP_TRY(B.alloc(&d_est, (size_t) total));
-        HIP_TRY(B.alloc(&d_tg, tg.size()));
-        HIP_TRY(B.alloc(&d_tc, tc.size()));
+        HIP_TRY(alloc_f64(d_svoff, (size_t) n + 1));
+        HIP_TRY(alloc_f64(d_svec, (size_t) svoff[n]));
+        HIP_TRY(alloc_f64(d_est, (size_t) total));
+        HIP_TRY(alloc_f64(d_tg, tg.size()));
+        HIP_TRY(alloc_f64(d_tc, tc.size()));
     }
-    HIP_TRY(hipEventCreate(&B.e0));
-    HIP_TRY(hipEventCreate(&B.e1));
-    HIP_TRY(hipMemcpyAsync(d_cov, packed.data(), sizeof(double) * (size_t) total, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(d_goff, goff.data(), sizeof(int64_t) * (size_t) (n + 1), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(d_glen, glen.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(d_order, order.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemsetAsync(d_counter, 0, sizeof(int32_t) * 4, h->stream));
-    HIP_TRY(hipMemsetAsync(d_trace, 0, sizeof(int32_t) * (size_t) n * dn::TRACE_LEN, h->stream));
-    if (d_ds) HIP_TRY(hipMemcpyAsync(d_ds, ds_start, sizeof(int64_t) * (size_t) n, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(e0.create(hipEventCreate));
+    HIP_TRY(e1.create(hipEventCreate));
+    HIP_TRY(hipMemcpyAsync(d_cov, packed.data(), sizeof(double) * (size_t) total, hipMemcpyHostToDevice, h->stream[0]));
+    HIP_TRY(hipMemcpyAsync(d_goff, goff.data(), sizeof(int64_t) * (size_t) (n + 1), hipMemcpyHostToDevice, h->stream[0]));
+    HIP_TRY(hipMemcpyAsync(d_glen, glen.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
+    HIP_TRY(hipMemcpyAsync(d_order, order.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
+    HIP_TRY(hipMemsetAsync(d_counter, 0, sizeof(int32_t) * 4, h->stream[0]));
+    HIP_TRY(hipMemsetAsync(d_trace, 0, sizeof(int32_t) * (size_t) n * dn::TRACE_LEN, h->stream[0]));
+    if (d_ds) HIP_TRY(hipMemcpyAsync(d_ds, ds_start, sizeof(int64_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
     if (est) {
-        HIP_TRY(hipMemcpyAsync(d_svoff, svoff.data(), sizeof(int64_t) * (size_t) (n + 1), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipMemcpyAsync(d_tg, tg.data(), sizeof(int32_t) * tg.size(), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipMemcpyAsync(d_tc, tc.data(), sizeof(int32_t) * tc.size(), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(d_svoff, svoff.data(), sizeof(int64_t) * (size_t) (n + 1), hipMemcpyHostToDevice, h->stream[0]));
+        HIP_TRY(hipMemcpyAsync(d_tg, tg.data(), sizeof(int32_t) * tg.size(), hipMemcpyHostToDevice, h->stream[0]));
+        HIP_TRY(hipMemcpyAsync(d_tc, tc.data(), sizeof(int32_t) * tc.size(), hipMemcpyHostToDevice, h->stream[0]));
     }
-    HIP_TRY(hipEventRecord(B.e0, h->stream));
+    HIP_TRY(hipEventRecord(e0, h->stream[0]));
     int lrc = dn::launch_row_max_f64(d_cov, d_goff, d_glen, d_rowmax, (int) n, p,
-                                     (int) std::min<int64_t>(n, (int64_t) h->n_cus * 8), h->stream);
+                                     (int) std::min<int64_t>(n, (int64_t) h->n_cus * 8), h->stream[0]);
     if (lrc != 0) return fail(DN_E_HIP, std::string("k_row_max_f64 launch: ") + hipGetErrorString((hipError_t) lrc));
 
     dn::IterArgsF64 a;
@@ -1723,7 +1638,7 @@ int dn_baseline_selection_f64(dn_handle h, int64_t n, int32_t p, const double *c
     a.lds_cols = 0; a.T = prm->nmf_iter; a.bins = prm->bins; a.min_hc = prm->min_high_coverage; a.rate = prm->downsample_rate;
     a.skip = prm->skip_baseline_selection ? 1 : 0; a.want_est = est ? 1 : 0; a.p = p; a.max_steps = h->max_steps;
     for (int i = 0; i < dn::P_MAX; i++) { a.scale[i] = 1.0; a.inv_scale[i] = 1.0; }      // F as given
-    lrc = dn::launch_baseline_f64(a, grid, h->stream);
+    lrc = dn::launch_baseline_f64(a, grid, h->stream[0]);
     if (lrc != 0) return fail(DN_E_HIP, std::string("k_baseline_gen (float64) launch: ") + hipGetErrorString((hipError_t) lrc));
     if (est) {
         dn::EstArgsF64 e;
@@ -1731,16 +1646,16 @@ int dn_baseline_selection_f64(dn_handle h, int64_t n, int32_t p, const double *c
         e.cov = d_cov; e.goff = d_goff; e.glen = d_glen; e.kfin = d_kfin; e.emode = d_emode; e.svec = d_svec; e.svoff = d_svoff;
         e.out = d_est; e.ooff = nullptr; e.n_genes = (int32_t) n; e.p = p;
         for (int i = 0; i < dn::P_MAX; i++) e.scale[i] = 1.0;
-        lrc = dn::launch_est_f64(e, d_tg, d_tc, (int) tg.size(), h->stream);
+        lrc = dn::launch_est_f64(e, d_tg, d_tc, (int) tg.size(), h->stream[0]);
         if (lrc != 0) return fail(DN_E_HIP, std::string("k_estimates_gen (float64) launch: ") + hipGetErrorString((hipError_t) lrc));
     }
-    HIP_TRY(hipEventRecord(B.e1, h->stream));
-    HIP_TRY(hipMemcpyAsync(rho, d_rho, sizeof(double) * (size_t) n * p, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(flags, d_flags, sizeof(int32_t) * (size_t) n, hipMemcpyDeviceToHost, h->stream));
-    if (trace) HIP_TRY(hipMemcpyAsync(trace, d_trace, sizeof(int32_t) * (size_t) n * dn::TRACE_LEN, hipMemcpyDeviceToHost, h->stream));
-    if (est) HIP_TRY(hipMemcpyAsync(est, d_est, sizeof(double) * (size_t) total, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipEventElapsedTime(&h->last_f64_ms, B.e0, B.e1));
+    HIP_TRY(hipEventRecord(e1, h->stream[0]));
+    HIP_TRY(hipMemcpyAsync(rho, d_rho, sizeof(double) * (size_t) n * p, hipMemcpyDeviceToHost, h->stream[0]));
+    HIP_TRY(hipMemcpyAsync(flags, d_flags, sizeof(int32_t) * (size_t) n, hipMemcpyDeviceToHost, h->stream[0]));
+    if (trace) HIP_TRY(hipMemcpyAsync(trace, d_trace, sizeof(int32_t) * (size_t) n * dn::TRACE_LEN, hipMemcpyDeviceToHost, h->stream[0]));
+    if (est) HIP_TRY(hipMemcpyAsync(est, d_est, sizeof(double) * (size_t) total, hipMemcpyDeviceToHost, h->stream[0]));
+    HIP_TRY(hipStreamSynchronize(h->stream[0]));
+    HIP_TRY(hipEventElapsedTime(&h->last_f64_ms, e0, e1));
     return DN_OK;
 }
 
@@ -1752,8 +1667,8 @@ double dn_last_span_ms(dn_handle h) { return h ? (double) h->last_span_ms : 0.0;
 double dn_last_rowmax_ms(dn_handle h) { return h ? (double) h->last_rowmax_ms : 0.0; }
 const char *dn_init_kernel_name(dn_handle h) { return h ? h->init_name : ""; }
 const char *dn_main_kernel_name(dn_handle h) { return (h && h->ks) ? h->ks->baseline_name : ""; }
-double dn_class_kernel_ms(dn_handle h, int cls) { return (h && cls >= 0 && cls < dn_handle_s::NCLS) ? (double) h->cls[cls].last_ms : 0.0; }
-const char *dn_class_kernel_name(dn_handle h, int cls) { return (h && cls >= 0 && cls < dn_handle_s::NCLS && h->cls[cls].ks && h->cls[cls].n > 0) ? h->cls[cls].ks->baseline_name : ""; }
+double dn_class_kernel_ms(dn_handle h, int cls) { return (h && cls >= 0 && cls < dn_handle_s::NCLS) ? (double) h->data.cls[cls].last_ms : 0.0; }
+const char *dn_class_kernel_name(dn_handle h, int cls) { return (h && cls >= 0 && cls < dn_handle_s::NCLS && h->data.cls[cls].ks && h->data.cls[cls].n > 0) ? h->data.cls[cls].ks->baseline_name : ""; }
 int32_t dn_tiny_length(dn_handle h) { return h ? h->tiny_len : 0; }
 int dn_class_lengths(dn_handle h, int32_t p, int32_t downsample_rate, int32_t *split_len, int32_t *tiny_len)
 {
@@ -1772,7 +1687,7 @@ int dn_synchronize(dn_handle h)
 {
     if (!h) return fail(DN_E_INVALID, "null handle");
     HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream[0]));
     return DN_OK;
 }
 
@@ -1821,33 +1736,32 @@ extern "C" double dn_measure_read_gbps(dn_handle h, int64_t bytes, int reps)
 {
     if (!h || bytes < (1 << 20)) return 0.0;
     if (hipSetDevice(h->device) != hipSuccess) return 0.0;
-    float4 *a = nullptr; float *sink = nullptr;
+    dn::DeviceBuffer<float4> a;
+    dn::DeviceBuffer<float> sink;
     const size_t n4 = (size_t) bytes / sizeof(float4);
-    if (hipMalloc(&a, n4 * sizeof(float4)) != hipSuccess) return 0.0;
-    if (hipMalloc(&sink, 256) != hipSuccess) { (void) hipFree(a); return 0.0; }
-    (void) hipMemsetAsync(a, 1, n4 * sizeof(float4), h->stream);
+    if (a.alloc(n4 * sizeof(float4)) != hipSuccess || sink.alloc(256) != hipSuccess) return 0.0;
+    (void) hipMemsetAsync(a, 1, n4 * sizeof(float4), h->stream[0]);
     double best = 0.0;
     for (int mult : {4, 8, 16, 32}) {                      // workgroups per CU: the best grid is the ceiling
         for (int r = 0; r < reps + 1; r++) {
-            (void) hipEventRecord(h->ev0, h->stream);
-            hipLaunchKernelGGL(k_read4, dim3(h->n_cus * mult), dim3(256), 0, h->stream, a, sink, n4);
-            (void) hipEventRecord(h->ev1, h->stream);
-            (void) hipStreamSynchronize(h->stream);
+            (void) hipEventRecord(h->ev_start[0], h->stream[0]);
+            hipLaunchKernelGGL(k_read4, dim3(h->n_cus * mult), dim3(256), 0, h->stream[0], a, sink, n4);
+            (void) hipEventRecord(h->ev_end[0], h->stream[0]);
+            (void) hipStreamSynchronize(h->stream[0]);
             float ms = 0.f;
-            (void) hipEventElapsedTime(&ms, h->ev0, h->ev1);
+            (void) hipEventElapsedTime(&ms, h->ev_start[0], h->ev_end[0]);
             if (r > 0 && ms > 0.f) best = std::max(best, (double) n4 * sizeof(float4) / (ms * 1e-3) / 1e9);
         }
         for (int r = 0; r < reps + 1; r++) {
-            (void) hipEventRecord(h->ev0, h->stream);
-            hipLaunchKernelGGL(k_read8nt, dim3(h->n_cus * mult), dim3(256), 0, h->stream, a, sink, n4);
-            (void) hipEventRecord(h->ev1, h->stream);
-            (void) hipStreamSynchronize(h->stream);
+            (void) hipEventRecord(h->ev_start[0], h->stream[0]);
+            hipLaunchKernelGGL(k_read8nt, dim3(h->n_cus * mult), dim3(256), 0, h->stream[0], a, sink, n4);
+            (void) hipEventRecord(h->ev_end[0], h->stream[0]);
+            (void) hipStreamSynchronize(h->stream[0]);
             float ms = 0.f;
-            (void) hipEventElapsedTime(&ms, h->ev0, h->ev1);
+            (void) hipEventElapsedTime(&ms, h->ev_start[0], h->ev_end[0]);
             if (r > 0 && ms > 0.f) best = std::max(best, (double) n4 * sizeof(float4) / (ms * 1e-3) / 1e9);
         }
     }
-    (void) hipFree(a); (void) hipFree(sink);
     return best;
 }
 
@@ -1855,21 +1769,19 @@ extern "C" double dn_measure_copy_gbps(dn_handle h, int64_t bytes, int reps)
 {
     if (!h || bytes < (1 << 20)) return 0.0;
     if (hipSetDevice(h->device) != hipSuccess) return 0.0;
-    float4 *a = nullptr, *b = nullptr;
+    dn::DeviceBuffer<float4> a, b;
     const size_t n4 = (size_t) bytes / sizeof(float4);
-    if (hipMalloc(&a, n4 * sizeof(float4)) != hipSuccess) return 0.0;
-    if (hipMalloc(&b, n4 * sizeof(float4)) != hipSuccess) { (void) hipFree(a); return 0.0; }
-    (void) hipMemsetAsync(a, 1, n4 * sizeof(float4), h->stream);
+    if (a.alloc(n4 * sizeof(float4)) != hipSuccess || b.alloc(n4 * sizeof(float4)) != hipSuccess) return 0.0;
+    (void) hipMemsetAsync(a, 1, n4 * sizeof(float4), h->stream[0]);
     double best = 0.0;
     for (int r = 0; r < reps + 1; r++) {
-        (void) hipEventRecord(h->ev0, h->stream);
-        hipLaunchKernelGGL(k_copy4, dim3(h->n_cus * 8), dim3(256), 0, h->stream, a, b, n4);
-        (void) hipEventRecord(h->ev1, h->stream);
-        (void) hipStreamSynchronize(h->stream);
+        (void) hipEventRecord(h->ev_start[0], h->stream[0]);
+        hipLaunchKernelGGL(k_copy4, dim3(h->n_cus * 8), dim3(256), 0, h->stream[0], a, b, n4);
+        (void) hipEventRecord(h->ev_end[0], h->stream[0]);
+        (void) hipStreamSynchronize(h->stream[0]);
         float ms = 0.f;
-        (void) hipEventElapsedTime(&ms, h->ev0, h->ev1);
+        (void) hipEventElapsedTime(&ms, h->ev_start[0], h->ev_end[0]);
         if (r > 0 && ms > 0.f) best = std::max(best, 2.0 * (double) n4 * sizeof(float4) / (ms * 1e-3) / 1e9);
     }
-    (void) hipFree(a); (void) hipFree(b);
     return best;
 }

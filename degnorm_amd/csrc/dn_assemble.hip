@@ -9,6 +9,7 @@
 #include <stdint.h>
 #include <string>
 #include "../../include/degnorm_amd.h"
+#include "dn_host.hpp"
 
 namespace {
 
@@ -54,11 +55,11 @@ extern "C" int dn_assemble_coverage(int device, int64_t chrom_len, int32_t p, co
                                     float *out_packed, double *device_ms)
 {
     int rc = DN_OK;
-    float *d_dense = nullptr, *d_out = nullptr, *d_val = nullptr;
-    int32_t *d_idx = nullptr, *d_clen = nullptr;
-    int64_t *d_csrc = nullptr, *d_cdst = nullptr;
-    hipStream_t st = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    dn::Stream st;
+    dn::Event e0, e1;
+    dn::DeviceBuffer<float> d_dense, d_out, d_val;
+    dn::DeviceBuffer<int32_t> d_idx, d_clen;
+    dn::DeviceBuffer<int64_t> d_csrc, d_cdst;
     int64_t total = 0, max_nnz = 1;
     if (chrom_len <= 0 || p < 1 || n_genes < 1 || !lengths || !out_packed || n_chunks < 0) { g_asm_err = "dn_assemble_coverage: bad argument"; return DN_E_INVALID; }
     {
@@ -73,16 +74,16 @@ extern "C" int dn_assemble_coverage(int device, int64_t chrom_len, int32_t p, co
         for (int i = 0; i < p; i++) if (nnz[i] > max_nnz) max_nnz = nnz[i];
 
         ASM_TRY(hipSetDevice(device));
-        ASM_TRY(hipStreamCreate(&st));
-        ASM_TRY(hipEventCreate(&e0));
-        ASM_TRY(hipEventCreate(&e1));
-        ASM_TRY(hipMalloc(&d_dense, sizeof(float) * (size_t) chrom_len));
-        ASM_TRY(hipMalloc(&d_out, sizeof(float) * (size_t) (total > 0 ? total : 1)));
-        ASM_TRY(hipMalloc(&d_idx, sizeof(int32_t) * (size_t) max_nnz));
-        ASM_TRY(hipMalloc(&d_val, sizeof(float) * (size_t) max_nnz));
-        ASM_TRY(hipMalloc(&d_csrc, sizeof(int64_t) * (size_t) (n_chunks > 0 ? n_chunks : 1)));
-        ASM_TRY(hipMalloc(&d_cdst, sizeof(int64_t) * (size_t) (n_chunks > 0 ? n_chunks : 1)));
-        ASM_TRY(hipMalloc(&d_clen, sizeof(int32_t) * (size_t) (n_chunks > 0 ? n_chunks : 1)));
+        ASM_TRY(st.create(hipStreamCreate));
+        ASM_TRY(e0.create(hipEventCreate));
+        ASM_TRY(e1.create(hipEventCreate));
+        ASM_TRY(d_dense.alloc(sizeof(float) * (size_t) chrom_len));
+        ASM_TRY(d_out.alloc(sizeof(float) * (size_t) (total > 0 ? total : 1)));
+        ASM_TRY(d_idx.alloc(sizeof(int32_t) * (size_t) max_nnz));
+        ASM_TRY(d_val.alloc(sizeof(float) * (size_t) max_nnz));
+        ASM_TRY(d_csrc.alloc(sizeof(int64_t) * (size_t) (n_chunks > 0 ? n_chunks : 1)));
+        ASM_TRY(d_cdst.alloc(sizeof(int64_t) * (size_t) (n_chunks > 0 ? n_chunks : 1)));
+        ASM_TRY(d_clen.alloc(sizeof(int32_t) * (size_t) (n_chunks > 0 ? n_chunks : 1)));
         if (n_chunks > 0) {
             ASM_TRY(hipMemcpyAsync(d_csrc, chunk_src, sizeof(int64_t) * (size_t) n_chunks, hipMemcpyHostToDevice, st));
             ASM_TRY(hipMemcpyAsync(d_clen, chunk_len, sizeof(int32_t) * (size_t) n_chunks, hipMemcpyHostToDevice, st));
@@ -115,15 +116,5 @@ extern "C" int dn_assemble_coverage(int device, int64_t chrom_len, int32_t p, co
         delete[] goff;
         delete[] cdst;
     }
-    if (d_dense) (void) hipFree(d_dense);
-    if (d_out) (void) hipFree(d_out);
-    if (d_idx) (void) hipFree(d_idx);
-    if (d_val) (void) hipFree(d_val);
-    if (d_csrc) (void) hipFree(d_csrc);
-    if (d_cdst) (void) hipFree(d_cdst);
-    if (d_clen) (void) hipFree(d_clen);
-    if (e0) (void) hipEventDestroy(e0);
-    if (e1) (void) hipEventDestroy(e1);
-    if (st) (void) hipStreamDestroy(st);
     return rc;
 }

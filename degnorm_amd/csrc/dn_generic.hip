@@ -1542,10 +1542,9 @@ static void launch_est(const EstArgs &a, const int32_t *tg, const int32_t *tc, i
 #if DN_GEN_NT == 256
 static void launch_init(const InitArgs &a, int grid, hipStream_t s)
 {
-    // 17 <= p <= 64: two passes over the coverage with the Gram matrix on the matrix cores; DN_INIT_POWER=1 keeps the
-    // one-pass-per-power-step kernel (cross-check in the tests); below 17 samples only the tests come here (DN_FORCE_GENERIC)
-    const char *pw = getenv("DN_INIT_POWER");
-    if (a.p >= 17 && !(pw && pw[0] == '1')) hipLaunchKernelGGL(k_ratio_svd_mg, dim3(grid), dim3(NT), 0, s, a);
+    // 17 <= p <= 64: two passes over the coverage with the Gram matrix on the matrix cores; below 17 samples (only the tests
+    // come here, DN_FORCE_GENERIC) the one-pass-per-power-step kernel
+    if (a.p >= 17) hipLaunchKernelGGL(k_ratio_svd_mg, dim3(grid), dim3(NT), 0, s, a);
     else hipLaunchKernelGGL(k_ratio_svd_gen, dim3(grid), dim3(NT), 0, s, a);
 }
 static int blocks_per_cu(int which)

@@ -22,6 +22,7 @@
 #include <string>
 #include <vector>
 #include "../../include/degnorm_amd.h"
+#include "dn_host.hpp"
 
 namespace {
 
@@ -289,16 +290,8 @@ thread_local std::string g_reads_err;
 
 inline unsigned grid_for(int64_t n) { const int64_t g = (n + kNT - 1) / kNT; return (unsigned) (g < 1 ? 1 : g > 65536 ? 65536 : g); }
 
-// device buffers freed on every exit path
-struct Bufs {
-    std::vector<void *> p;
-    template <class T> hipError_t alloc(T **x, size_t n) {
-        hipError_t e = hipMalloc((void **) x, n * sizeof(T) + 16);
-        if (e == hipSuccess) p.push_back(*x); else *x = nullptr;
-        return e;
-    }
-    ~Bufs() { for (void *x : p) (void) hipFree(x); }
-};
+// n elements and 16 bytes of slack
+template <class T> hipError_t alloc_padded(dn::DeviceBuffer<T> &b, size_t n) { return b.alloc(n * sizeof(T) + 16); }
 
 }  // namespace
 
@@ -349,16 +342,16 @@ extern "C" int dn_read_coverage(int device, int32_t paired, int64_t n_rows, cons
         if (exon_iv[2 * k] < 0 || exon_iv[2 * k + 1] >= chrom_len) { g_reads_err = "dn_read_coverage: exon union outside the chromosome"; return DN_E_INVALID; }
     const int64_t n_ol_exon = n_ol > 0 ? ol_exon_off[n_ol] : 0;
     const int64_t n_bytes = n_rows > 0 ? cigar_off[n_rows] : 0;
-    Bufs B;
-    hipStream_t st = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int64_t *d_pos, *d_off, *d_end, *d_exon, *d_giv, *d_gs0, *d_coff, *d_oex, *d_iiv, *d_iu;
-    int64_t *d_val64, *d_csr_val;
-    uint8_t *d_cig;
-    int32_t *d_pid = nullptr, *d_pcnt = nullptr, *d_rank = nullptr, *d_rows = nullptr, *d_keep, *d_ggo, *d_olg, *d_oxo, *d_ig, *d_csr_idx;
-    int *d_counts, *d_oldiff, *d_olcov, *d_cdiff, *d_ccov, *d_nsel;
-    unsigned long long *d_niso, *d_err;
-    void *d_tmp = nullptr;
+    dn::DeviceBuffer<int64_t> d_pos, d_off, d_end, d_exon, d_giv, d_gs0, d_coff, d_oex, d_iiv, d_iu;
+    dn::DeviceBuffer<int64_t> d_val64, d_csr_val;
+    dn::DeviceBuffer<uint8_t> d_cig;
+    dn::DeviceBuffer<int32_t> d_pid, d_pcnt, d_rank, d_rows, d_keep, d_ggo, d_olg, d_oxo, d_ig, d_csr_idx;
+    dn::DeviceBuffer<int> d_counts, d_oldiff, d_olcov, d_cdiff, d_ccov, d_nsel;
+    dn::DeviceBuffer<unsigned long long> d_niso, d_err;
+    std::vector<dn::DeviceBuffer<uint8_t>> tmp;     // scan / select scratch: a larger one is added when a call needs more
+    void *d_tmp = nullptr;                           // the latest of them
+    dn::Stream st;
+    dn::Event e0, e1;
     size_t tmp_bytes = 0, need = 0;
     int64_t n_units = 0;
     unsigned long long h_err[3], h_niso = 0;
@@ -367,23 +360,23 @@ extern "C" int dn_read_coverage(int device, int32_t paired, int64_t n_rows, cons
     std::vector<int> h_counts(n_genes > 0 ? n_genes : 1);
 
     RD_TRY(hipSetDevice(device));
-    RD_TRY(hipStreamCreate(&st));
-    RD_TRY(hipEventCreate(&e0));
-    RD_TRY(hipEventCreate(&e1));
-    RD_TRY(B.alloc(&d_pos, n_rows)); RD_TRY(B.alloc(&d_off, n_rows + 1)); RD_TRY(B.alloc(&d_end, n_rows));
-    RD_TRY(B.alloc(&d_cig, n_bytes)); RD_TRY(B.alloc(&d_keep, n_rows + 1));
-    RD_TRY(B.alloc(&d_exon, 2 * n_exon)); RD_TRY(B.alloc(&d_giv, 2 * n_groups)); RD_TRY(B.alloc(&d_ggo, n_groups + 1));
-    RD_TRY(B.alloc(&d_olg, n_ol)); RD_TRY(B.alloc(&d_gs0, n_ol)); RD_TRY(B.alloc(&d_coff, n_ol + 1));
-    RD_TRY(B.alloc(&d_oxo, n_ol + 1)); RD_TRY(B.alloc(&d_oex, 2 * n_ol_exon));
-    RD_TRY(B.alloc(&d_iiv, 2 * n_iso)); RD_TRY(B.alloc(&d_ig, n_iso)); RD_TRY(B.alloc(&d_iu, 2 * n_iso_union));
-    RD_TRY(B.alloc(&d_counts, n_genes)); RD_TRY(B.alloc(&d_oldiff, ol_total)); RD_TRY(B.alloc(&d_olcov, ol_total));
-    RD_TRY(B.alloc(&d_val64, ol_total));
-    RD_TRY(B.alloc(&d_cdiff, chrom_len + 1)); RD_TRY(B.alloc(&d_ccov, chrom_len + 1));
-    RD_TRY(B.alloc(&d_csr_idx, chrom_len)); RD_TRY(B.alloc(&d_csr_val, chrom_len)); RD_TRY(B.alloc(&d_nsel, 1));
-    RD_TRY(B.alloc(&d_niso, 1)); RD_TRY(B.alloc(&d_err, 3));
+    RD_TRY(st.create(hipStreamCreate));
+    RD_TRY(e0.create(hipEventCreate));
+    RD_TRY(e1.create(hipEventCreate));
+    RD_TRY(alloc_padded(d_pos, n_rows)); RD_TRY(alloc_padded(d_off, n_rows + 1)); RD_TRY(alloc_padded(d_end, n_rows));
+    RD_TRY(alloc_padded(d_cig, n_bytes)); RD_TRY(alloc_padded(d_keep, n_rows + 1));
+    RD_TRY(alloc_padded(d_exon, 2 * n_exon)); RD_TRY(alloc_padded(d_giv, 2 * n_groups)); RD_TRY(alloc_padded(d_ggo, n_groups + 1));
+    RD_TRY(alloc_padded(d_olg, n_ol)); RD_TRY(alloc_padded(d_gs0, n_ol)); RD_TRY(alloc_padded(d_coff, n_ol + 1));
+    RD_TRY(alloc_padded(d_oxo, n_ol + 1)); RD_TRY(alloc_padded(d_oex, 2 * n_ol_exon));
+    RD_TRY(alloc_padded(d_iiv, 2 * n_iso)); RD_TRY(alloc_padded(d_ig, n_iso)); RD_TRY(alloc_padded(d_iu, 2 * n_iso_union));
+    RD_TRY(alloc_padded(d_counts, n_genes)); RD_TRY(alloc_padded(d_oldiff, ol_total)); RD_TRY(alloc_padded(d_olcov, ol_total));
+    RD_TRY(alloc_padded(d_val64, ol_total));
+    RD_TRY(alloc_padded(d_cdiff, chrom_len + 1)); RD_TRY(alloc_padded(d_ccov, chrom_len + 1));
+    RD_TRY(alloc_padded(d_csr_idx, chrom_len)); RD_TRY(alloc_padded(d_csr_val, chrom_len)); RD_TRY(alloc_padded(d_nsel, 1));
+    RD_TRY(alloc_padded(d_niso, 1)); RD_TRY(alloc_padded(d_err, 3));
     if (paired) {
-        RD_TRY(B.alloc(&d_pid, n_rows)); RD_TRY(B.alloc(&d_pcnt, n_pair_ids)); RD_TRY(B.alloc(&d_rank, n_rows + 1));
-        RD_TRY(B.alloc(&d_rows, n_rows));
+        RD_TRY(alloc_padded(d_pid, n_rows)); RD_TRY(alloc_padded(d_pcnt, n_pair_ids)); RD_TRY(alloc_padded(d_rank, n_rows + 1));
+        RD_TRY(alloc_padded(d_rows, n_rows));
     }
 #define H2D(d, h, n) do { if ((n) > 0) RD_TRY(hipMemcpyAsync(d, h, sizeof(*(d)) * (size_t) (n), hipMemcpyHostToDevice, st)); } while (0)
     H2D(d_pos, pos, n_rows); H2D(d_off, cigar_off, n_rows > 0 ? n_rows + 1 : 0); H2D(d_cig, cigar, n_bytes);
@@ -402,7 +395,7 @@ extern "C" int dn_read_coverage(int device, int32_t paired, int64_t n_rows, cons
     if (paired) RD_TRY(hipMemsetAsync(d_pcnt, 0, sizeof(int32_t) * (size_t) n_pair_ids, st));
     if (n_rows > 0) {
         hipLaunchKernelGGL(k_prefilter, dim3(grid_for(n_rows)), dim3(kNT), 0, st, n_rows, d_pos, d_off, d_cig, keep_lo, keep_hi,
-                           paired ? d_pid : (const int32_t *) nullptr, d_pcnt, d_end, d_keep);
+                           paired ? d_pid.get() : (const int32_t *) nullptr, d_pcnt, d_end, d_keep);
         RD_TRY(hipGetLastError());
         n_units = n_rows;
         if (paired) {
@@ -410,9 +403,9 @@ extern "C" int dn_read_coverage(int device, int32_t paired, int64_t n_rows, cons
             RD_TRY(hipGetLastError());
             // exclusive rank of every surviving row; rank[n_rows] is the number of survivors
             RD_TRY(hipMemsetAsync(d_keep + n_rows, 0, sizeof(int32_t), st));       // keep[n_rows] = 0: rank[n_rows] = #survivors
-            RD_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, d_keep, d_rank, (int) n_rows + 1, st));
-            if (need > tmp_bytes) { RD_TRY(B.alloc((uint8_t **) &d_tmp, need)); tmp_bytes = need; }
-            RD_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, need, d_keep, d_rank, (int) n_rows + 1, st));
+            RD_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, d_keep.get(), d_rank.get(), (int) n_rows + 1, st));
+            if (need > tmp_bytes) { tmp.emplace_back(); RD_TRY(alloc_padded(tmp.back(), need)); d_tmp = tmp.back(); tmp_bytes = need; }
+            RD_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, need, d_keep.get(), d_rank.get(), (int) n_rows + 1, st));
             hipLaunchKernelGGL(k_pair_compact, dim3(grid_for(n_rows)), dim3(kNT), 0, st, n_rows, d_keep, d_rank, d_rows);
             RD_TRY(hipGetLastError());
             RD_TRY(hipMemcpyAsync(&survivors, d_rank + n_rows, sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -433,25 +426,25 @@ extern "C" int dn_read_coverage(int device, int32_t paired, int64_t n_rows, cons
     }
     // difference arrays -> coverage
     need = 0;
-    RD_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, need, d_cdiff, d_ccov, (int) chrom_len, st));
-    if (need > tmp_bytes) { RD_TRY(B.alloc((uint8_t **) &d_tmp, need)); tmp_bytes = need; }
-    RD_TRY(hipcub::DeviceScan::InclusiveSum(d_tmp, need, d_cdiff, d_ccov, (int) chrom_len, st));
+    RD_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, need, d_cdiff.get(), d_ccov.get(), (int) chrom_len, st));
+    if (need > tmp_bytes) { tmp.emplace_back(); RD_TRY(alloc_padded(tmp.back(), need)); d_tmp = tmp.back(); tmp_bytes = need; }
+    RD_TRY(hipcub::DeviceScan::InclusiveSum(d_tmp, need, d_cdiff.get(), d_ccov.get(), (int) chrom_len, st));
     if (ol_total > 0) {
         need = 0;
-        RD_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, need, d_oldiff, d_olcov, (int) ol_total, st));
-        if (need > tmp_bytes) { RD_TRY(B.alloc((uint8_t **) &d_tmp, need)); tmp_bytes = need; }
-        RD_TRY(hipcub::DeviceScan::InclusiveSum(d_tmp, need, d_oldiff, d_olcov, (int) ol_total, st));
+        RD_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, need, d_oldiff.get(), d_olcov.get(), (int) ol_total, st));
+        if (need > tmp_bytes) { tmp.emplace_back(); RD_TRY(alloc_padded(tmp.back(), need)); d_tmp = tmp.back(); tmp_bytes = need; }
+        RD_TRY(hipcub::DeviceScan::InclusiveSum(d_tmp, need, d_oldiff.get(), d_olcov.get(), (int) ol_total, st));
         hipLaunchKernelGGL(k_widen, dim3(grid_for(ol_total)), dim3(kNT), 0, st, ol_total, d_olcov, d_val64);
         RD_TRY(hipGetLastError());
     }
     // chromosome vector -> CSR (positions ascending)
     {
         hipcub::CountingInputIterator<int32_t> ids(0);
-        NonZero nz{d_ccov};
+        NonZero nz{d_ccov.get()};
         need = 0;
-        RD_TRY(hipcub::DeviceSelect::If(nullptr, need, ids, d_csr_idx, d_nsel, (int) chrom_len, nz, st));
-        if (need > tmp_bytes) { RD_TRY(B.alloc((uint8_t **) &d_tmp, need)); tmp_bytes = need; }
-        RD_TRY(hipcub::DeviceSelect::If(d_tmp, need, ids, d_csr_idx, d_nsel, (int) chrom_len, nz, st));
+        RD_TRY(hipcub::DeviceSelect::If(nullptr, need, ids, d_csr_idx.get(), d_nsel.get(), (int) chrom_len, nz, st));
+        if (need > tmp_bytes) { tmp.emplace_back(); RD_TRY(alloc_padded(tmp.back(), need)); d_tmp = tmp.back(); tmp_bytes = need; }
+        RD_TRY(hipcub::DeviceSelect::If(d_tmp, need, ids, d_csr_idx.get(), d_nsel.get(), (int) chrom_len, nz, st));
     }
     RD_TRY(hipMemcpyAsync(&h_nsel, d_nsel, sizeof(int), hipMemcpyDeviceToHost, st));
     RD_TRY(hipMemcpyAsync(h_err, d_err, sizeof(h_err), hipMemcpyDeviceToHost, st));
@@ -499,9 +492,6 @@ extern "C" int dn_read_coverage(int device, int32_t paired, int64_t n_rows, cons
     if (device_ms) { float ms = 0.f; RD_TRY(hipEventElapsedTime(&ms, e0, e1)); *device_ms = ms; }
 done:
     if (st) (void) hipStreamSynchronize(st);
-    if (e0) (void) hipEventDestroy(e0);
-    if (e1) (void) hipEventDestroy(e1);
-    if (st) (void) hipStreamDestroy(st);
     return rc;
 }
 
@@ -515,16 +505,15 @@ extern "C" int dn_reads_cigar_bounds(int device, int64_t n, const int64_t *pos, 
         return DN_E_INVALID;
     }
     if (n == 0) return DN_OK;
-    Bufs B;
-    hipStream_t st = nullptr;
-    int64_t *d_pos, *d_off, *d_b, *d_end;
-    uint8_t *d_cig;
-    int32_t *d_n;
+    dn::DeviceBuffer<int64_t> d_pos, d_off, d_b, d_end;
+    dn::DeviceBuffer<uint8_t> d_cig;
+    dn::DeviceBuffer<int32_t> d_n;
+    dn::Stream st;
     const int64_t n_bytes = cigar_off[n];
     RD_TRY(hipSetDevice(device));
-    RD_TRY(hipStreamCreate(&st));
-    RD_TRY(B.alloc(&d_pos, n)); RD_TRY(B.alloc(&d_off, n + 1)); RD_TRY(B.alloc(&d_cig, n_bytes)); RD_TRY(B.alloc(&d_n, n));
-    RD_TRY(B.alloc(&d_b, n * 2 * max_seg)); RD_TRY(B.alloc(&d_end, n));
+    RD_TRY(st.create(hipStreamCreate));
+    RD_TRY(alloc_padded(d_pos, n)); RD_TRY(alloc_padded(d_off, n + 1)); RD_TRY(alloc_padded(d_cig, n_bytes)); RD_TRY(alloc_padded(d_n, n));
+    RD_TRY(alloc_padded(d_b, n * 2 * max_seg)); RD_TRY(alloc_padded(d_end, n));
     RD_TRY(hipMemcpyAsync(d_pos, pos, sizeof(int64_t) * (size_t) n, hipMemcpyHostToDevice, st));
     RD_TRY(hipMemcpyAsync(d_off, cigar_off, sizeof(int64_t) * (size_t) (n + 1), hipMemcpyHostToDevice, st));
     if (n_bytes > 0) RD_TRY(hipMemcpyAsync(d_cig, cigar, (size_t) n_bytes, hipMemcpyHostToDevice, st));
@@ -536,6 +525,6 @@ extern "C" int dn_reads_cigar_bounds(int device, int64_t n, const int64_t *pos, 
     RD_TRY(hipMemcpyAsync(end_pos, d_end, sizeof(int64_t) * (size_t) n, hipMemcpyDeviceToHost, st));
     RD_TRY(hipStreamSynchronize(st));
 done:
-    if (st) { (void) hipStreamSynchronize(st); (void) hipStreamDestroy(st); }
+    if (st) (void) hipStreamSynchronize(st);
     return rc;
 }
