@@ -109,6 +109,17 @@ def load(build_if_missing=False):
                                      i64, P(i64), i64, P(i64), P(i64), i64, P(i64), P(i32), P(i64), P(i64), P(dbl)]
     lib.dn_reads_cigar_bounds.argtypes = [c.c_int, i64, P(i64), P(i64), P(u8), i32, P(i32), P(i64), P(i64)]
     lib.dn_reads_last_error.restype = c.c_char_p
+    u32 = c.c_uint32
+    lib.dn_bam_frame.argtypes = [P(u8), i64, i32, P(i32), P(i64), i64, P(i64), P(i64)]
+    lib.dn_bam_rows_create.argtypes = [c.c_int, i32, i32, i32, P(vp)]
+    lib.dn_bam_rows_destroy.argtypes = [vp]
+    lib.dn_bam_rows_destroy.restype = None
+    lib.dn_bam_rows_append.argtypes = [vp, P(u8), i64, P(i64), i64]
+    lib.dn_bam_rows_info.argtypes = [vp, P(i64), P(i64), P(i64), P(i32)]
+    lib.dn_bam_rows_keys.argtypes = [vp, i32, P(u8)]
+    lib.dn_bam_rows_fetch.argtypes = [vp, P(i64), P(i64), P(i32), P(u32), P(i64), P(i32), P(u8)]
+    lib.dn_bam_rows_coverage.argtypes = [vp, P(i32), P(i32), i64] + lib.dn_read_coverage.argtypes[8:]
+    lib.dn_bam_cigar_bounds.argtypes = [c.c_int, i64, P(i64), P(i64), P(u32), i32, P(i32), P(i64), P(i64)]
     lib.dn_outer_partials_device.argtypes = [vp, P(vp)]
     lib.dn_comm_unique_id.argtypes = [P(c.c_uint8)]
     lib.dn_comm_create.argtypes = [vp, P(c.c_uint8), i32, i32]

@@ -1,0 +1,449 @@
+"""
+Native BAM input for the reads stage: NativeBamReadsProcessor opens sorted, indexed .bam files without pysam.
+
+    host      BGZF block walk; raw-deflate inflate (zlib, in a thread pool of n_jobs) of only the blocks that hold the
+              requested chromosome, window by window (about window_bytes each; a record cut by a window end is carried to
+              the next); the header's reference list; the .bai pseudo-bin of the chromosome; record framing in the
+              library's host C++ (dn_bam_frame), which also checks that the range is sorted and belongs to the chromosome
+    device    (csrc/dn_reads.hip) the records of each window are decoded, filtered by the reference's rules (reads.py
+              load_chromosome_reads) and appended to a device-resident row store; the coverage stages read their binary
+              CIGARs in place
+
+Single-end reads never come back to the host.  Paired reads bring back only their qname_unpaired keys: the host sorts them
+as pandas' sort_values does (numpy's quicksort on fixed-width bytes) and hands the order and the pair ids back.
+"""
+import ctypes
+import os
+import struct
+import time
+import zlib
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+
+from . import _lib
+from .reads import BamReadsProcessor, Annotation, coverage_outputs, reads_frame, _ptr
+
+BGZF_EOF = bytes.fromhex('1f8b08040000000000ff0600424302001b0003000000000000000000')
+PSEUDO_BIN = 37450
+CIGAR_OPS = 'MIDNSHP=X'
+_INT32_MIN = -2 ** 31
+_CHUNK = 4 << 20                 # compressed bytes read from the file at a time
+
+
+# --- BGZF --------------------------------------------------------------------------------------------------------------
+
+def _block_size(buf, p, where):
+    """Total size of the BGZF block whose header starts at buf[p] (its BC extra subfield + 1)."""
+    if buf[p:p + 4] != b'\x1f\x8b\x08\x04':
+        raise ValueError('{0}: no BGZF block header at byte {1}'.format(where, p))
+    xlen = struct.unpack_from('<H', buf, p + 10)[0]
+    q, end = p + 12, p + 12 + xlen
+    if end > len(buf):
+        return None
+    while q + 4 <= end:
+        si1, si2, slen = buf[q], buf[q + 1], struct.unpack_from('<H', buf, q + 2)[0]
+        if si1 == 66 and si2 == 67 and slen == 2:
+            return struct.unpack_from('<H', buf, q + 4)[0] + 1
+        q += 4 + slen
+    raise ValueError('{0}: BGZF block at byte {1} has no BC subfield'.format(where, p))
+
+
+def iter_blocks(path, start=0):
+    """(file offset, block bytes) of every BGZF block from file offset `start` on.  ValueError on a cut or foreign block."""
+    with open(path, 'rb') as f:
+        f.seek(start)
+        buf, base, p = b'', start, 0
+        while True:
+            if len(buf) - p < 18 or len(buf) - p < (_block_size(buf, p, path) or 1 << 30):
+                more = f.read(_CHUNK)
+                buf, base, p = buf[p:] + more, base + p, 0
+                if not buf:
+                    return
+                if len(buf) < 18:
+                    raise ValueError('{0}: truncated BGZF block at byte {1}'.format(path, base))
+            total = _block_size(buf, p, path)
+            if total is None or total > len(buf) - p:
+                raise ValueError('{0}: truncated BGZF block at byte {1}'.format(path, base + p))
+            yield base + p, memoryview(buf)[p:p + total]
+            p += total
+
+
+def bgzf_blocks(path):
+    """Offsets, compressed sizes and inflated sizes of every block of a BGZF file (int64 arrays)."""
+    offs, sizes, isizes = [], [], []
+    for off, blk in iter_blocks(path):
+        offs.append(off)
+        sizes.append(len(blk))
+        isizes.append(struct.unpack_from('<I', blk, len(blk) - 4)[0])
+    return np.array(offs, np.int64), np.array(sizes, np.int64), np.array(isizes, np.int64)
+
+
+def has_eof_block(path):
+    """True when the file ends with BGZF's 28-byte empty block."""
+    size = os.path.getsize(path)
+    if size < len(BGZF_EOF):
+        return False
+    with open(path, 'rb') as f:
+        f.seek(size - len(BGZF_EOF))
+        return f.read() == BGZF_EOF
+
+
+def inflate_block(blk):
+    """The data of one BGZF block (raw deflate between the header and the CRC32 / ISIZE trailer)."""
+    xlen = struct.unpack_from('<H', blk, 10)[0]
+    isize = struct.unpack_from('<I', blk, len(blk) - 4)[0]
+    data = zlib.decompress(blk[12 + xlen:len(blk) - 8], -15)
+    if len(data) != isize:
+        raise ValueError('BGZF block inflates to {0} bytes, ISIZE says {1}'.format(len(data), isize))
+    return data
+
+
+# --- header and index ----------------------------------------------------------------------------------------------------
+
+def parse_header(data):
+    """(header end, [(name, length)]) of inflated BAM bytes, or None while `data` holds less than the whole header."""
+    if len(data) < 12:
+        return None
+    if bytes(data[:4]) != b'BAM\x01':
+        raise ValueError('not a BAM file (magic {0!r})'.format(bytes(data[:4])))
+    l_text = struct.unpack_from('<i', data, 4)[0]
+    p = 8 + l_text
+    if len(data) < p + 4:
+        return None
+    n_ref = struct.unpack_from('<i', data, p)[0]
+    p += 4
+    refs = []
+    for _ in range(n_ref):
+        if len(data) < p + 4:
+            return None
+        l_name = struct.unpack_from('<i', data, p)[0]
+        if len(data) < p + 8 + l_name:
+            return None
+        name = bytes(data[p + 4:p + 4 + l_name]).rstrip(b'\x00').decode('ascii')
+        refs.append((name, struct.unpack_from('<i', data, p + 4 + l_name)[0]))
+        p += 8 + l_name
+    return p, refs
+
+
+def read_header(path):
+    """[(SQ name, length)] of a BAM file, in refID order."""
+    data = bytearray()
+    for _, blk in iter_blocks(path):
+        data += inflate_block(blk)
+        got = parse_header(data)
+        if got is not None:
+            return got[1]
+    raise ValueError('{0}: BAM header cut short'.format(path))
+
+
+def read_bai(path):
+    """
+    A .bai index: (per reference a dict with `n_bin`, `pseudo` = (ref_beg, ref_end, n_mapped, n_unmapped) or None,
+    `chunk_min` / `chunk_max` over all chunks of the real bins (None without any), n_no_coor or None).
+    """
+    with open(path, 'rb') as f:
+        b = f.read()
+    if b[:4] != b'BAI\x01':
+        raise ValueError('{0} is not a .bai index'.format(path))
+    n_ref = struct.unpack_from('<i', b, 4)[0]
+    p, refs = 8, []
+    try:
+        for _ in range(n_ref):
+            n_bin = struct.unpack_from('<i', b, p)[0]
+            p += 4
+            pseudo, lo, hi = None, None, None
+            for _ in range(n_bin):
+                bin_id, n_chunk = struct.unpack_from('<Ii', b, p)
+                p += 8
+                ch = np.frombuffer(b, dtype='<u8', count=2 * n_chunk, offset=p).reshape(n_chunk, 2)
+                p += 16 * n_chunk
+                if bin_id == PSEUDO_BIN:
+                    pseudo = tuple(int(x) for x in ch.reshape(-1)[:4])
+                elif n_chunk:
+                    lo = int(ch[:, 0].min()) if lo is None else min(lo, int(ch[:, 0].min()))
+                    hi = int(ch[:, 1].max()) if hi is None else max(hi, int(ch[:, 1].max()))
+            n_intv = struct.unpack_from('<i', b, p)[0]
+            p += 4 + 8 * n_intv
+            refs.append({'n_bin': n_bin, 'pseudo': pseudo, 'chunk_min': lo, 'chunk_max': hi})
+    except (struct.error, ValueError) as e:
+        raise ValueError('{0}: truncated .bai index ({1})'.format(path, e))
+    n_no_coor = struct.unpack_from('<Q', b, p)[0] if len(b) >= p + 8 else None
+    return refs, n_no_coor
+
+
+def reference_range(ref):
+    """[begin, end) virtual offsets of one reference's records from its .bai entry, or None when it has no reads."""
+    if ref['pseudo'] is not None:
+        return ref['pseudo'][0], ref['pseudo'][1]
+    if ref['chunk_min'] is None:
+        return None
+    return ref['chunk_min'], ref['chunk_max']
+
+
+# --- framing and the device row store ------------------------------------------------------------------------------------
+
+def _check(rc, what):
+    if rc != _lib.DN_OK:
+        msg = _lib.load().dn_reads_last_error().decode('utf-8', 'replace')
+        if rc == _lib.DN_E_INVALID:
+            raise ValueError(msg)
+        raise _lib.DegnormAmdError('{0} failed ({1}): {2}'.format(what, rc, msg))
+
+
+def frame_records(buf, tid=-1, last_pos=_INT32_MIN):
+    """
+    Start offsets (int64) of the complete records of inflated BAM bytes, the bytes they span (the rest is a record cut by
+    the end of buf) and the last record's pos.  With tid >= 0 every record must belong to tid and be sorted (ValueError).
+    Runs in the library's host code: no device needed.
+    """
+    a = np.frombuffer(buf, dtype=np.uint8) if len(buf) else np.zeros(1, np.uint8)
+    cap = len(buf) // 36 + 1
+    off = np.empty(cap, dtype=np.int64)
+    n, used, lp = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int32(last_pos)
+    _check(_lib.load().dn_bam_frame(_ptr(a, ctypes.c_uint8), len(buf), int(tid), ctypes.byref(lp), _ptr(off, ctypes.c_int64),
+                                    cap, ctypes.byref(n), ctypes.byref(used)), 'dn_bam_frame')
+    return off[:n.value], int(used.value), int(lp.value)
+
+
+class DeviceRows(object):
+    """The device-resident rows of one chromosome (dn_bam_rows): kept records in file order."""
+
+    def __init__(self, tid, unique_alignment, paired, device=None):
+        self.lib = _lib.load()
+        self.paired = bool(paired)
+        self.h = ctypes.c_void_p()
+        dev = int(os.environ.get('LOCAL_RANK', 0)) if device is None else int(device)
+        _check(self.lib.dn_bam_rows_create(dev, int(tid), 1 if unique_alignment else 0, 1 if paired else 0,
+                                           ctypes.byref(self.h)), 'dn_bam_rows_create')
+
+    def close(self):
+        if self.h:
+            self.lib.dn_bam_rows_destroy(self.h)
+            self.h = ctypes.c_void_p()
+
+    def __del__(self):
+        self.close()
+
+    def append(self, buf, rec_off):
+        if len(rec_off) == 0:
+            return
+        a = np.frombuffer(buf, dtype=np.uint8)
+        _check(self.lib.dn_bam_rows_append(self.h, _ptr(a, ctypes.c_uint8), len(buf), _ptr(rec_off, ctypes.c_int64),
+                                           len(rec_off)), 'dn_bam_rows_append')
+
+    def info(self):
+        n, n_ops, n_names, mk = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32()
+        _check(self.lib.dn_bam_rows_info(self.h, ctypes.byref(n), ctypes.byref(n_ops), ctypes.byref(n_names), ctypes.byref(mk)),
+               'dn_bam_rows_info')
+        return n.value, n_ops.value, n_names.value, mk.value
+
+    def keys(self):
+        """qname_unpaired of every row as a fixed-width bytes array (numpy S)."""
+        n, _, _, mk = self.info()
+        width = max(mk, 1)
+        out = np.zeros((max(n, 1), width), dtype=np.uint8)
+        _check(self.lib.dn_bam_rows_keys(self.h, width, _ptr(out, ctypes.c_uint8)), 'dn_bam_rows_keys')
+        return out[:n].view('S{0}'.format(width)).reshape(n)
+
+    def fetch(self):
+        """(pos int64, op_beg int64, n_op int32, ops uint32, name_beg int64, name_len int32, names uint8) of the rows."""
+        n, n_ops, n_names, _ = self.info()
+        pos, op_beg, name_beg = (np.zeros(max(n, 1), np.int64) for _ in range(3))
+        n_op, name_len = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        ops, names = np.zeros(max(n_ops, 1), np.uint32), np.zeros(max(n_names, 1), np.uint8)
+        i64, i32 = ctypes.c_int64, ctypes.c_int32
+        _check(self.lib.dn_bam_rows_fetch(self.h, _ptr(pos, i64), _ptr(op_beg, i64), _ptr(n_op, i32), _ptr(ops, ctypes.c_uint32),
+                                          _ptr(name_beg, i64), _ptr(name_len, i32), _ptr(names, ctypes.c_uint8)), 'dn_bam_rows_fetch')
+        return pos[:n], op_beg[:n], n_op[:n], ops[:n_ops], name_beg[:n], name_len[:n], names[:n_names]
+
+    def coverage(self, ann):
+        """dn_bam_rows_coverage: the outputs of reads.device_read_coverage for the stored rows."""
+        order, pair_id, n_ids = None, None, 0
+        if self.paired:
+            order, pair_id, n_ids = pair_order(self.keys())
+        i32, i64, dbl = ctypes.c_int32, ctypes.c_int64, ctypes.c_double
+        n_genes = len(ann.genes)
+        counts = np.zeros(max(n_genes, 1), dtype=np.int64)
+        ol_cov = np.zeros(max(int(ann.ol_cov_off[-1]), 1), dtype=np.int64)
+        cap = max(ann.exon_union_len, 1)
+        csr_idx = np.zeros(cap, dtype=np.int32)
+        csr_val = np.zeros(cap, dtype=np.int64)
+        nnz, n_iso_reads, ms = ctypes.c_int64(0), ctypes.c_int64(0), dbl(0.0)
+        rc = self.lib.dn_bam_rows_coverage(self.h, _ptr(order, i32), _ptr(pair_id, i32), int(n_ids),
+                                           ann.chrom_len, ann.keep_lo, ann.keep_hi,
+                                           len(ann.exon_iv), _ptr(ann.exon_iv, i64),
+                                           len(ann.group_iv), _ptr(ann.group_iv, i64), _ptr(ann.group_gene_off, i32),
+                                           _ptr(ann.ol_gene, i32), _ptr(ann.ol_gs0, i64), _ptr(ann.ol_cov_off, i64),
+                                           _ptr(ann.ol_exon_off, i32), _ptr(ann.ol_exon, i64),
+                                           len(ann.iso_iv), _ptr(ann.iso_iv, i64), _ptr(ann.iso_gene, i32),
+                                           len(ann.iso_union), _ptr(ann.iso_union, i64),
+                                           n_genes, _ptr(counts, i64), _ptr(ol_cov, i64), cap, ctypes.byref(nnz),
+                                           _ptr(csr_idx, i32), _ptr(csr_val, i64), ctypes.byref(n_iso_reads), ctypes.byref(ms))
+        _check(rc, 'dn_bam_rows_coverage')
+        k = int(nnz.value)
+        return counts[:n_genes], ol_cov, csr_idx[:k].copy(), csr_val[:k].copy(), int(n_iso_reads.value), float(ms.value)
+
+
+def pair_order(keys):
+    """
+    The row order of DataFrame.sort_values('qname_unpaired') (pandas' default quicksort) on rows in file order with these
+    keys, and the pair id of each row taken in that order: (order int32, pair_id int32, number of ids).
+    """
+    keys = np.asarray(keys)
+    order = np.argsort(keys, kind='quicksort').astype(np.int32)
+    sk = keys[order]
+    pair_id = np.zeros(len(sk), dtype=np.int32)
+    if len(sk) > 1:
+        np.cumsum(sk[1:] != sk[:-1], out=pair_id[1:])
+    return order, pair_id, int(pair_id[-1]) + 1 if len(sk) else 0
+
+
+def cigar_strings(op_beg, n_op, ops):
+    """pysam's cigarstring of every row (None for a row without ops)."""
+    lens, codes = (ops >> 4).tolist(), (ops & 15).tolist()
+    tok = [str(l) + CIGAR_OPS[c] if c < 9 else str(l) + '?' for l, c in zip(lens, codes)]
+    return [''.join(tok[b:b + k]) if k else None for b, k in zip(op_beg.tolist(), n_op.tolist())]
+
+
+# --- the processor -------------------------------------------------------------------------------------------------------
+
+class NativeBamReadsProcessor(BamReadsProcessor):
+
+    def __init__(self, bam_file, index_file, chroms=None, n_jobs=1, output_dir=None, unique_alignment=True, verbose=True,
+                 window_bytes=256 << 20):
+        """
+        BamReadsProcessor on the library's own BAM reader: no pysam.  n_jobs sizes the thread pool that inflates BGZF
+        blocks; window_bytes bounds the inflated bytes held (on the host and on the device) besides the chromosome's rows.
+        """
+        self.window_bytes = max(int(window_bytes), 1)
+        self.timing = {}
+        super(NativeBamReadsProcessor, self).__init__(bam_file, index_file, chroms=chroms, n_jobs=n_jobs, output_dir=output_dir,
+                                                      unique_alignment=unique_alignment, verbose=verbose)
+
+    def _open_backend(self):
+        self._refs = None
+        self._index = None
+
+    def _load(self):
+        if self._refs is None:
+            if not has_eof_block(self.filename):
+                raise ValueError('{0}: no BGZF end-of-file block; the file is truncated'.format(self.filename))
+            self._refs = read_header(self.filename)
+            self._index, _ = read_bai(self.index_filename)
+            if len(self._index) != len(self._refs):
+                raise ValueError('{0} indexes {1} references, {2} has {3}'.format(
+                    self.index_filename, len(self._index), self.filename, len(self._refs)))
+            self._tid = {name: k for k, (name, _) in enumerate(self._refs)}
+
+    def _reference_lengths(self):
+        self._load()
+        return {name: length for name, length in self._refs}
+
+    def windows(self, chrom, window_bytes=None):
+        """
+        Inflated bytes of the blocks that hold chrom's records, about window_bytes at a time; a record may be cut at the
+        end of one window and continue in the next.  Adds host inflate seconds to self.timing['inflate_s'].
+        """
+        self._load()
+        rng = reference_range(self._index[self._tid[chrom]])
+        if rng is None:
+            return
+        window_bytes = window_bytes or self.window_bytes
+        vbeg, vend = rng
+        cbeg, ubeg, cend, uend = vbeg >> 16, vbeg & 0xffff, vend >> 16, vend & 0xffff
+        pool = ThreadPoolExecutor(max_workers=int(self.n_jobs)) if int(self.n_jobs) > 1 else None
+        try:
+            batch, size = [], 0
+            for off, blk in iter_blocks(self.filename, cbeg):
+                if off > cend or (off == cend and uend == 0):
+                    break
+                batch.append((off, blk))
+                size += struct.unpack_from('<I', blk, len(blk) - 4)[0]
+                if size >= window_bytes:
+                    yield self._inflate(batch, pool, cbeg, ubeg, cend, uend)
+                    batch, size = [], 0
+            if batch:
+                yield self._inflate(batch, pool, cbeg, ubeg, cend, uend)
+        finally:
+            if pool is not None:
+                pool.shutdown()
+
+    def _inflate(self, batch, pool, cbeg, ubeg, cend, uend):
+        t0 = time.perf_counter()
+        blocks = [b for _, b in batch]
+        data = list(pool.map(inflate_block, blocks)) if pool is not None else [inflate_block(b) for b in blocks]
+        for k, (off, _) in enumerate(batch):
+            if off == cend:
+                data[k] = data[k][:uend]
+            if off == cbeg:
+                data[k] = data[k][ubeg:]
+        out = b''.join(data)
+        self.timing['inflate_s'] = self.timing.get('inflate_s', 0.0) + time.perf_counter() - t0
+        return out
+
+    def _leading_query_names(self, chrom):
+        self._load()
+        names, carry, last = [], b'', _INT32_MIN
+        for win in self.windows(chrom, window_bytes=1 << 20):
+            data = carry + win
+            off, used, last = frame_records(data, self._tid[chrom], last)
+            for o in off.tolist():
+                l_name = data[o + 12]
+                names.append(data[o + 36:o + 35 + l_name].decode('ascii', 'replace'))
+                if len(names) > 300:
+                    return names
+            carry = data[used:]
+        return names
+
+    def device_rows(self, chrom, device=None):
+        """The chromosome's kept records as a DeviceRows store (file order)."""
+        self._load()
+        rows = DeviceRows(self._tid[chrom], self.unique_alignment, self.paired, device)
+        carry, last = b'', _INT32_MIN
+        t = self.timing
+        try:
+            for win in self.windows(chrom):
+                data = carry + win if carry else win
+                t0 = time.perf_counter()
+                off, used, last = frame_records(data, self._tid[chrom], last)
+                t1 = time.perf_counter()
+                rows.append(data, off)
+                t2 = time.perf_counter()
+                t['frame_s'] = t.get('frame_s', 0.0) + t1 - t0
+                t['decode_s'] = t.get('decode_s', 0.0) + t2 - t1
+                carry = data[used:]
+            if carry:
+                raise ValueError('{0}: a record of {1} is cut short at the end of its index range'.format(self.filename, chrom))
+        except Exception:
+            rows.close()
+            raise
+        return rows
+
+    def load_chromosome_reads(self, chrom):
+        """
+        The reference's DataFrame of one chromosome's reads (`qname`, `pos`, `cigar`, plus `qname_unpaired` and sorted by
+        it when paired), built from the device-decoded rows.
+        """
+        rows = self.device_rows(chrom)
+        try:
+            pos, op_beg, n_op, ops, name_beg, name_len, names = rows.fetch()
+        finally:
+            rows.close()
+        nb = names.tobytes()
+        qname = [nb[b:b + k].decode('ascii', 'replace') for b, k in zip(name_beg.tolist(), name_len.tolist())]
+        return reads_frame(list(zip(qname, pos.tolist(), cigar_strings(op_beg, n_op, ops))), self.paired)
+
+    def _chromosome_coverage(self, chrom, chrom_len, gene_overlap_dat, chrom_gene_df, chrom_exon_df):
+        ann = Annotation(chrom_len, gene_overlap_dat, chrom_gene_df, chrom_exon_df)
+        rows = self.device_rows(chrom)
+        try:
+            n_reads = rows.info()[0]
+            t0 = time.perf_counter()
+            counts, ol_cov, idx, val, n_iso_reads, ms = rows.coverage(ann)
+            self.timing['coverage_s'] = self.timing.get('coverage_s', 0.0) + time.perf_counter() - t0
+            self.timing['coverage_device_ms'] = self.timing.get('coverage_device_ms', 0.0) + ms
+        finally:
+            rows.close()
+        csr, ol_cov_dict, read_counts = coverage_outputs(ann, counts, ol_cov, idx, val, n_iso_reads)
+        return csr, ol_cov_dict, read_counts, n_reads

@@ -19,6 +19,8 @@
 #include <hipcub/hipcub.hpp>
 #include <stdint.h>
 #include <stdio.h>
+#include <string.h>
+#include <functional>
 #include <string>
 #include <vector>
 #include "../../include/degnorm_amd.h"
@@ -32,35 +34,73 @@ constexpr int kMaxPiece = 2 * kMaxSeg + 1;          // a pair's segments plus th
 
 __device__ __forceinline__ bool is_digit(uint8_t c) { return c >= '0' && c <= '9'; }
 
-// Sum of all op lengths of a CIGAR string: the token grammar of the reference's regex (\d+)([A-Z]?) (:404-405).
-__device__ int64_t cigar_length(const uint8_t *s, int64_t n)
-{
-    int64_t tot = 0, i = 0;
-    while (i < n) {
-        if (!is_digit(s[i])) { i++; continue; }
-        int64_t len = 0;
+// CIGAR sources.  A row's CIGAR is read as a sequence of tokens (length, is-M); the stages below are written once against
+// a source type and instantiated for two of them:
+//   StrCigars   ASCII strings cigar[off[r] .. off[r+1]) in the token grammar of the reference's regex (\d+)([A-Z]?):
+//               text that is not a digit run is skipped, a digit run is one token, M only when the capital letter 'M'
+//               directly follows it (:9-66, :404-405)
+//   BamCigars   BAM's binary ops (len << 4 | op) ops[beg[r] .. beg[r] + cnt[r]): only op 0 (M) is a match; every other op,
+//               = (7) and X (8) included, is "other" -- what pysam's cigarstring gives the regex
+struct StrTokens {
+    const uint8_t *s;
+    int64_t n, i;
+    __device__ bool next(int64_t &len, bool &m)
+    {
+        while (i < n && !is_digit(s[i])) i++;
+        if (i >= n) return false;
+        len = 0;
         while (i < n && is_digit(s[i])) { len = len * 10 + (s[i] - '0'); i++; }
-        tot += len;
-        if (i < n && s[i] >= 'A' && s[i] <= 'Z') i++;
+        m = false;
+        if (i < n && s[i] >= 'A' && s[i] <= 'Z') { m = s[i] == 'M'; i++; }
+        return true;
     }
+};
+
+struct BamTokens {
+    const uint32_t *p;
+    int64_t n, i;
+    __device__ bool next(int64_t &len, bool &m)
+    {
+        if (i >= n) return false;
+        const uint32_t v = p[i++];
+        len = v >> 4;
+        m = (v & 15u) == 0;
+        return true;
+    }
+};
+
+struct StrCigars {
+    const int64_t *off;
+    const uint8_t *cig;
+    __device__ StrTokens row(int64_t r) const { return StrTokens{cig + off[r], off[r + 1] - off[r], 0}; }
+};
+
+struct BamCigars {
+    const int64_t *beg;
+    const int32_t *cnt;
+    const uint32_t *ops;
+    __device__ BamTokens row(int64_t r) const { return BamTokens{ops + beg[r], cnt[r], 0}; }
+};
+
+// Sum of all op lengths of a CIGAR (:404-405).
+template <class T> __device__ int64_t cigar_length(T t)
+{
+    int64_t tot = 0, len;
+    bool m;
+    while (t.next(len, m)) tot += len;
     return tot;
 }
 
-// Match segments of one CIGAR string starting at `start` (cigar_segment_bounds, :9-66): an M op of length L gives
-// [start, start + L - 1] and advances by L - 1; any other op (a digit run followed by no capital letter, e.g. '=',
-// included) advances by its length, by one more when it directly follows an M.  Returns the number of M ops (0: the
-// reference raises ValueError); segments beyond `cap` are counted but not stored.
-__device__ int cigar_segments(const uint8_t *s, int64_t n, int64_t start, int32_t *a, int32_t *b, int cap)
+// Match segments of one CIGAR starting at `start` (cigar_segment_bounds, :9-66): an M op of length L gives
+// [start, start + L - 1] and advances by L - 1; any other op advances by its length, by one more when it directly follows
+// an M.  Returns the number of M ops (0: the reference raises ValueError); segments beyond `cap` are counted but not stored.
+template <class T> __device__ int cigar_segments(T t, int64_t start, int32_t *a, int32_t *b, int cap)
 {
     int nseg = 0;
     bool augment = false;
-    int64_t i = 0;
-    while (i < n) {
-        if (!is_digit(s[i])) { i++; continue; }
-        int64_t len = 0;
-        while (i < n && is_digit(s[i])) { len = len * 10 + (s[i] - '0'); i++; }
-        bool m = false;
-        if (i < n && s[i] >= 'A' && s[i] <= 'Z') { m = s[i] == 'M'; i++; }
+    int64_t len;
+    bool m;
+    while (t.next(len, m)) {
         if (m) {
             if (nseg < cap) { a[nseg] = (int32_t) start; b[nseg] = (int32_t) (start + len - 1); }
             nseg++;
@@ -115,11 +155,11 @@ __device__ void emit_runs(int32_t *a, int32_t *b, int n, int *diff, int64_t base
     }
 }
 
-struct ReadsArgs {
+template <class C> struct ReadsArgs {
     int32_t paired;
     int64_t n_units;                      // reads (single-end) or pairs
-    const int64_t *pos, *end_pos, *cig_off;
-    const uint8_t *cig;
+    const int64_t *pos, *end_pos;
+    C cig;
     const int32_t *keep;                  // single-end: pre-filter flags per row
     const int32_t *rows;                  // paired: the surviving rows in order (2 per pair)
     int64_t n_exon; const int64_t *exon_iv;
@@ -133,13 +173,13 @@ struct ReadsArgs {
                                           // overlap-gene index leaves [-1, L) (exons outside the gene span)
 };
 
-__global__ __launch_bounds__(kNT) void k_prefilter(int64_t n, const int64_t *__restrict__ pos, const int64_t *__restrict__ off,
-                                                   const uint8_t *__restrict__ cig, int64_t keep_lo, int64_t keep_hi,
+template <class C>
+__global__ __launch_bounds__(kNT) void k_prefilter(int64_t n, const int64_t *__restrict__ pos, C cig, int64_t keep_lo, int64_t keep_hi,
                                                    const int32_t *__restrict__ pair_id, int32_t *__restrict__ pair_cnt,
                                                    int64_t *__restrict__ end_pos, int32_t *__restrict__ keep)
 {
     for (int64_t r = (int64_t) blockIdx.x * kNT + threadIdx.x; r < n; r += (int64_t) gridDim.x * kNT) {
-        const int64_t e = pos[r] + cigar_length(cig + off[r], off[r + 1] - off[r]);
+        const int64_t e = pos[r] + cigar_length(cig.row(r));
         end_pos[r] = e;
         const int32_t k = pos[r] >= keep_lo && e <= keep_hi;
         keep[r] = k;
@@ -161,7 +201,7 @@ __global__ __launch_bounds__(kNT) void k_pair_compact(int64_t n, const int32_t *
         if (keep[r]) rows[rank[r]] = (int32_t) r;
 }
 
-__global__ __launch_bounds__(kNT) void k_reads(ReadsArgs A)
+template <class C> __global__ __launch_bounds__(kNT) void k_reads(ReadsArgs<C> A)
 {
     int32_t sa[kMaxPiece], sb[kMaxPiece];
     for (int64_t u = (int64_t) blockIdx.x * kNT + threadIdx.x; u < A.n_units; u += (int64_t) gridDim.x * kNT) {
@@ -170,14 +210,14 @@ __global__ __launch_bounds__(kNT) void k_reads(ReadsArgs A)
         if (!A.paired) {
             r2 = u;
             if (!A.keep[u]) continue;
-            nseg = cigar_segments(A.cig + A.cig_off[u], A.cig_off[u + 1] - A.cig_off[u], A.pos[u], sa, sb, kMaxSeg);
+            nseg = cigar_segments(A.cig.row(u), A.pos[u], sa, sb, kMaxSeg);
             if (nseg == 0) { atomicMin(A.err + 0, (unsigned long long) u); continue; }
             if (nseg > kMaxSeg) { atomicMin(A.err + 1, (unsigned long long) u); continue; }
         } else {
             const int64_t r1 = A.rows[2 * u];
             r2 = A.rows[2 * u + 1];
-            const int n1 = cigar_segments(A.cig + A.cig_off[r1], A.cig_off[r1 + 1] - A.cig_off[r1], A.pos[r1], sa, sb, kMaxSeg);
-            const int n2 = cigar_segments(A.cig + A.cig_off[r2], A.cig_off[r2 + 1] - A.cig_off[r2], A.pos[r2],
+            const int n1 = cigar_segments(A.cig.row(r1), A.pos[r1], sa, sb, kMaxSeg);
+            const int n2 = cigar_segments(A.cig.row(r2), A.pos[r2],
                                           sa + (n1 < kMaxSeg ? n1 : kMaxSeg), sb + (n1 < kMaxSeg ? n1 : kMaxSeg), kMaxSeg);
             if (n1 == 0 || n2 == 0) { atomicMin(A.err + 0, (unsigned long long) (n1 == 0 ? r1 : r2)); continue; }
             if (n1 > kMaxSeg || n2 > kMaxSeg) { atomicMin(A.err + 1, (unsigned long long) (n1 > kMaxSeg ? r1 : r2)); continue; }
@@ -267,14 +307,14 @@ __global__ __launch_bounds__(kNT) void k_widen(int64_t n, const int *__restrict_
     for (int64_t i = (int64_t) blockIdx.x * kNT + threadIdx.x; i < n; i += (int64_t) gridDim.x * kNT) y[i] = x[i];
 }
 
-__global__ __launch_bounds__(kNT) void k_cigar_debug(int64_t n, const int64_t *__restrict__ pos, const int64_t *__restrict__ off,
-                                                     const uint8_t *__restrict__ cig, int32_t max_seg, int32_t *__restrict__ nseg,
+template <class C>
+__global__ __launch_bounds__(kNT) void k_cigar_debug(int64_t n, const int64_t *__restrict__ pos, C cig, int32_t max_seg, int32_t *__restrict__ nseg,
                                                      int64_t *__restrict__ bounds, int64_t *__restrict__ end_pos)
 {
     int32_t a[kMaxSeg], b[kMaxSeg];
     for (int64_t r = (int64_t) blockIdx.x * kNT + threadIdx.x; r < n; r += (int64_t) gridDim.x * kNT) {
-        const int k = cigar_segments(cig + off[r], off[r + 1] - off[r], pos[r], a, b, kMaxSeg);
-        end_pos[r] = pos[r] + cigar_length(cig + off[r], off[r + 1] - off[r]);
+        const int k = cigar_segments(cig.row(r), pos[r], a, b, kMaxSeg);
+        end_pos[r] = pos[r] + cigar_length(cig.row(r));
         nseg[r] = k == 0 ? 0 : (k > max_seg || k > kMaxSeg) ? -1 : k;
         if (nseg[r] > 0)
             for (int j = 0; j < k; j++) { bounds[(int64_t) r * 2 * max_seg + 2 * j] = a[j]; bounds[(int64_t) r * 2 * max_seg + 2 * j + 1] = b[j]; }
@@ -303,31 +343,64 @@ template <class T> hipError_t alloc_padded(dn::DeviceBuffer<T> &b, size_t n) { r
 
 extern "C" const char *dn_reads_last_error(void) { return g_reads_err.c_str(); }
 
-extern "C" int dn_read_coverage(int device, int32_t paired, int64_t n_rows, const int64_t *pos, const int64_t *cigar_off,
-                                const uint8_t *cigar, const int32_t *pair_id, int64_t n_pair_ids,
-                                int64_t chrom_len, int64_t keep_lo, int64_t keep_hi,
-                                int64_t n_exon, const int64_t *exon_iv,
-                                int64_t n_groups, const int64_t *group_iv, const int32_t *group_gene_off,
-                                const int32_t *ol_gene, const int64_t *ol_gene_start0, const int64_t *ol_cov_off,
-                                const int32_t *ol_exon_off, const int64_t *ol_exon_bounds,
-                                int64_t n_iso, const int64_t *iso_iv, const int32_t *iso_gene,
-                                int64_t n_iso_union, const int64_t *iso_union,
-                                int64_t n_genes, int64_t *counts, int64_t *ol_cov,
-                                int64_t csr_cap, int64_t *nnz, int32_t *csr_idx, int64_t *csr_val,
-                                int64_t *n_isolated_reads, double *device_ms)
+namespace {
+
+// k_cigar_debug on n rows whose CIGARs are already on the device (`cig`); pos and the outputs are host arrays.
+template <class C>
+int cigar_debug(hipStream_t st, int64_t n, const int64_t *pos, C cig, int32_t max_seg, int32_t *nseg, int64_t *bounds, int64_t *end_pos)
 {
     int rc = DN_OK;
-    g_reads_err.clear();
+    dn::DeviceBuffer<int64_t> d_pos, d_b, d_end;
+    dn::DeviceBuffer<int32_t> d_n;
+    RD_TRY(alloc_padded(d_pos, n)); RD_TRY(alloc_padded(d_n, n)); RD_TRY(alloc_padded(d_b, n * 2 * max_seg)); RD_TRY(alloc_padded(d_end, n));
+    RD_TRY(hipMemcpyAsync(d_pos, pos, sizeof(int64_t) * (size_t) n, hipMemcpyHostToDevice, st));
+    RD_TRY(hipMemsetAsync(d_b, 0, sizeof(int64_t) * (size_t) (n * 2 * max_seg), st));
+    hipLaunchKernelGGL(k_cigar_debug<C>, dim3(grid_for(n)), dim3(kNT), 0, st, n, d_pos, cig, max_seg, d_n, d_b, d_end);
+    RD_TRY(hipGetLastError());
+    RD_TRY(hipMemcpyAsync(nseg, d_n, sizeof(int32_t) * (size_t) n, hipMemcpyDeviceToHost, st));
+    RD_TRY(hipMemcpyAsync(bounds, d_b, sizeof(int64_t) * (size_t) (n * 2 * max_seg), hipMemcpyDeviceToHost, st));
+    RD_TRY(hipMemcpyAsync(end_pos, d_end, sizeof(int64_t) * (size_t) n, hipMemcpyDeviceToHost, st));
+    RD_TRY(hipStreamSynchronize(st));
+done:
+    (void) hipStreamSynchronize(st);
+    return rc;
+}
+
+// The annotation and the outputs of one coverage call (the arguments of dn_read_coverage after the reads).
+struct CoverageIO {
+    int64_t chrom_len, keep_lo, keep_hi;
+    int64_t n_exon; const int64_t *exon_iv;
+    int64_t n_groups; const int64_t *group_iv; const int32_t *group_gene_off;
+    const int32_t *ol_gene; const int64_t *ol_gene_start0, *ol_cov_off; const int32_t *ol_exon_off; const int64_t *ol_exon_bounds;
+    int64_t n_iso; const int64_t *iso_iv; const int32_t *iso_gene;
+    int64_t n_iso_union; const int64_t *iso_union;
+    int64_t n_genes; int64_t *counts, *ol_cov;
+    int64_t csr_cap; int64_t *nnz; int32_t *csr_idx; int64_t *csr_val;
+    int64_t *n_isolated_reads; double *device_ms;
+};
+
+// The coverage stages on n_rows device-resident rows (positions d_pos, CIGARs `cig`), queued on `st` after whatever the
+// caller queued there (its uploads).  pair_id (host, paired only) is uploaded here.  cigar_text(r) gives row r's CIGAR
+// as text for the error messages.
+template <class C>
+int coverage_stages(hipStream_t st, int32_t paired, int64_t n_rows, const int64_t *d_pos, C cig, const int32_t *pair_id,
+                    int64_t n_pair_ids, const CoverageIO &io, const std::function<std::string(int64_t)> &cigar_text)
+{
+    int rc = DN_OK;
+    const int64_t chrom_len = io.chrom_len, n_exon = io.n_exon, n_groups = io.n_groups, n_iso = io.n_iso, n_iso_union = io.n_iso_union,
+                  n_genes = io.n_genes, csr_cap = io.csr_cap;
     if (n_rows < 0 || n_rows > INT32_MAX - 1 || chrom_len <= 0 || chrom_len > INT32_MAX - 4 || n_exon < 0 || n_groups < 0 || n_iso < 0 || n_iso_union < 0 ||
-        n_genes < 0 || !counts || !nnz || !n_isolated_reads || (paired && n_rows > 0 && (!pair_id || n_pair_ids < 1)) ||
-        (n_rows > 0 && (!pos || !cigar_off || !cigar)) || (n_groups > 0 && (!group_iv || !group_gene_off || !ol_cov || !ol_cov_off)) ||
-        (n_iso > 0 && (!iso_iv || !iso_gene || !iso_union)) || csr_cap < 0 || (csr_cap > 0 && (!csr_idx || !csr_val))) {
+        n_genes < 0 || !io.counts || !io.nnz || !io.n_isolated_reads || (paired && n_rows > 0 && (!pair_id || n_pair_ids < 1)) ||
+        (n_groups > 0 && (!io.group_iv || !io.group_gene_off || !io.ol_cov || !io.ol_cov_off)) ||
+        (n_iso > 0 && (!io.iso_iv || !io.iso_gene || !io.iso_union)) || csr_cap < 0 || (csr_cap > 0 && (!io.csr_idx || !io.csr_val))) {
         g_reads_err = "dn_read_coverage: bad argument";
         return DN_E_INVALID;
     }
     if (paired)
         for (int64_t r = 0; r < n_rows; r++)
             if (pair_id[r] < 0 || pair_id[r] >= n_pair_ids) { g_reads_err = "dn_read_coverage: pair id out of range"; return DN_E_INVALID; }
+    const int32_t *group_gene_off = io.group_gene_off, *ol_gene = io.ol_gene, *ol_exon_off = io.ol_exon_off, *iso_gene = io.iso_gene;
+    const int64_t *ol_cov_off = io.ol_cov_off, *exon_iv = io.exon_iv;
     const int64_t n_ol = n_groups > 0 ? group_gene_off[n_groups] : 0;
     const int64_t ol_total = n_ol > 0 ? ol_cov_off[n_ol] : 0;
     // every index the kernels follow stays inside its array
@@ -341,16 +414,13 @@ extern "C" int dn_read_coverage(int device, int32_t paired, int64_t n_rows, cons
     for (int64_t k = 0; k < n_exon; k++)
         if (exon_iv[2 * k] < 0 || exon_iv[2 * k + 1] >= chrom_len) { g_reads_err = "dn_read_coverage: exon union outside the chromosome"; return DN_E_INVALID; }
     const int64_t n_ol_exon = n_ol > 0 ? ol_exon_off[n_ol] : 0;
-    const int64_t n_bytes = n_rows > 0 ? cigar_off[n_rows] : 0;
-    dn::DeviceBuffer<int64_t> d_pos, d_off, d_end, d_exon, d_giv, d_gs0, d_coff, d_oex, d_iiv, d_iu;
+    dn::DeviceBuffer<int64_t> d_end, d_exon, d_giv, d_gs0, d_coff, d_oex, d_iiv, d_iu;
     dn::DeviceBuffer<int64_t> d_val64, d_csr_val;
-    dn::DeviceBuffer<uint8_t> d_cig;
     dn::DeviceBuffer<int32_t> d_pid, d_pcnt, d_rank, d_rows, d_keep, d_ggo, d_olg, d_oxo, d_ig, d_csr_idx;
     dn::DeviceBuffer<int> d_counts, d_oldiff, d_olcov, d_cdiff, d_ccov, d_nsel;
     dn::DeviceBuffer<unsigned long long> d_niso, d_err;
     std::vector<dn::DeviceBuffer<uint8_t>> tmp;     // scan / select scratch: a larger one is added when a call needs more
     void *d_tmp = nullptr;                           // the latest of them
-    dn::Stream st;
     dn::Event e0, e1;
     size_t tmp_bytes = 0, need = 0;
     int64_t n_units = 0;
@@ -359,12 +429,9 @@ extern "C" int dn_read_coverage(int device, int32_t paired, int64_t n_rows, cons
     int32_t survivors = 0;
     std::vector<int> h_counts(n_genes > 0 ? n_genes : 1);
 
-    RD_TRY(hipSetDevice(device));
-    RD_TRY(st.create(hipStreamCreate));
     RD_TRY(e0.create(hipEventCreate));
     RD_TRY(e1.create(hipEventCreate));
-    RD_TRY(alloc_padded(d_pos, n_rows)); RD_TRY(alloc_padded(d_off, n_rows + 1)); RD_TRY(alloc_padded(d_end, n_rows));
-    RD_TRY(alloc_padded(d_cig, n_bytes)); RD_TRY(alloc_padded(d_keep, n_rows + 1));
+    RD_TRY(alloc_padded(d_end, n_rows)); RD_TRY(alloc_padded(d_keep, n_rows + 1));
     RD_TRY(alloc_padded(d_exon, 2 * n_exon)); RD_TRY(alloc_padded(d_giv, 2 * n_groups)); RD_TRY(alloc_padded(d_ggo, n_groups + 1));
     RD_TRY(alloc_padded(d_olg, n_ol)); RD_TRY(alloc_padded(d_gs0, n_ol)); RD_TRY(alloc_padded(d_coff, n_ol + 1));
     RD_TRY(alloc_padded(d_oxo, n_ol + 1)); RD_TRY(alloc_padded(d_oex, 2 * n_ol_exon));
@@ -379,11 +446,10 @@ extern "C" int dn_read_coverage(int device, int32_t paired, int64_t n_rows, cons
         RD_TRY(alloc_padded(d_rows, n_rows));
     }
 #define H2D(d, h, n) do { if ((n) > 0) RD_TRY(hipMemcpyAsync(d, h, sizeof(*(d)) * (size_t) (n), hipMemcpyHostToDevice, st)); } while (0)
-    H2D(d_pos, pos, n_rows); H2D(d_off, cigar_off, n_rows > 0 ? n_rows + 1 : 0); H2D(d_cig, cigar, n_bytes);
-    H2D(d_exon, exon_iv, 2 * n_exon); H2D(d_giv, group_iv, 2 * n_groups); H2D(d_ggo, group_gene_off, n_groups > 0 ? n_groups + 1 : 0);
-    H2D(d_olg, ol_gene, n_ol); H2D(d_gs0, ol_gene_start0, n_ol); H2D(d_coff, ol_cov_off, n_ol > 0 ? n_ol + 1 : 0);
-    H2D(d_oxo, ol_exon_off, n_ol > 0 ? n_ol + 1 : 0); H2D(d_oex, ol_exon_bounds, 2 * n_ol_exon);
-    H2D(d_iiv, iso_iv, 2 * n_iso); H2D(d_ig, iso_gene, n_iso); H2D(d_iu, iso_union, 2 * n_iso_union);
+    H2D(d_exon, exon_iv, 2 * n_exon); H2D(d_giv, io.group_iv, 2 * n_groups); H2D(d_ggo, group_gene_off, n_groups > 0 ? n_groups + 1 : 0);
+    H2D(d_olg, ol_gene, n_ol); H2D(d_gs0, io.ol_gene_start0, n_ol); H2D(d_coff, ol_cov_off, n_ol > 0 ? n_ol + 1 : 0);
+    H2D(d_oxo, ol_exon_off, n_ol > 0 ? n_ol + 1 : 0); H2D(d_oex, io.ol_exon_bounds, 2 * n_ol_exon);
+    H2D(d_iiv, io.iso_iv, 2 * n_iso); H2D(d_ig, iso_gene, n_iso); H2D(d_iu, io.iso_union, 2 * n_iso_union);
     if (paired) H2D(d_pid, pair_id, n_rows);
 #undef H2D
     RD_TRY(hipEventRecord(e0, st));
@@ -394,7 +460,7 @@ extern "C" int dn_read_coverage(int device, int32_t paired, int64_t n_rows, cons
     RD_TRY(hipMemsetAsync(d_err, 0xff, 3 * sizeof(unsigned long long), st));
     if (paired) RD_TRY(hipMemsetAsync(d_pcnt, 0, sizeof(int32_t) * (size_t) n_pair_ids, st));
     if (n_rows > 0) {
-        hipLaunchKernelGGL(k_prefilter, dim3(grid_for(n_rows)), dim3(kNT), 0, st, n_rows, d_pos, d_off, d_cig, keep_lo, keep_hi,
+        hipLaunchKernelGGL(k_prefilter<C>, dim3(grid_for(n_rows)), dim3(kNT), 0, st, n_rows, d_pos, cig, io.keep_lo, io.keep_hi,
                            paired ? d_pid.get() : (const int32_t *) nullptr, d_pcnt, d_end, d_keep);
         RD_TRY(hipGetLastError());
         n_units = n_rows;
@@ -413,14 +479,14 @@ extern "C" int dn_read_coverage(int device, int32_t paired, int64_t n_rows, cons
             n_units = survivors / 2;
         }
         if (n_units > 0) {
-            ReadsArgs A;
-            A.paired = paired; A.n_units = n_units; A.pos = d_pos; A.end_pos = d_end; A.cig_off = d_off; A.cig = d_cig;
+            ReadsArgs<C> A;
+            A.paired = paired; A.n_units = n_units; A.pos = d_pos; A.end_pos = d_end; A.cig = cig;
             A.keep = d_keep; A.rows = d_rows;
             A.n_exon = n_exon; A.exon_iv = d_exon; A.n_groups = n_groups; A.group_iv = d_giv; A.group_gene_off = d_ggo;
             A.ol_gene = d_olg; A.ol_gstart0 = d_gs0; A.ol_cov_off = d_coff; A.ol_exon_off = d_oxo; A.ol_exon = d_oex;
             A.n_iso = n_iso; A.iso_iv = d_iiv; A.iso_gene = d_ig; A.n_iso_union = n_iso_union; A.iso_union = d_iu;
             A.counts = d_counts; A.ol_diff = d_oldiff; A.chrom_diff = d_cdiff; A.n_iso_reads = d_niso; A.err = d_err;
-            hipLaunchKernelGGL(k_reads, dim3(grid_for(n_units)), dim3(kNT), 0, st, A);
+            hipLaunchKernelGGL(k_reads<C>, dim3(grid_for(n_units)), dim3(kNT), 0, st, A);
             RD_TRY(hipGetLastError());
         }
     }
@@ -456,16 +522,13 @@ extern "C" int dn_read_coverage(int device, int32_t paired, int64_t n_rows, cons
     }
     RD_TRY(hipEventRecord(e1, st));
     if (h_err[0] != ~0ull) {
-        const int64_t r = (int64_t) h_err[0];
-        g_reads_err = "CIGAR string " + std::string((const char *) cigar + cigar_off[r], (size_t) (cigar_off[r + 1] - cigar_off[r])) +
-                      " has no matching region.";
+        g_reads_err = "CIGAR string " + cigar_text((int64_t) h_err[0]) + " has no matching region.";
         rc = DN_E_INVALID;
         goto done;
     }
     if (h_err[1] != ~0ull) {
-        const int64_t r = (int64_t) h_err[1];
-        g_reads_err = "CIGAR string " + std::string((const char *) cigar + cigar_off[r], (size_t) (cigar_off[r + 1] - cigar_off[r])) +
-                      " has more than " + std::to_string(kMaxSeg) + " match segments (DN_READS_MAX_SEG)";
+        g_reads_err = "CIGAR string " + cigar_text((int64_t) h_err[1]) + " has more than " + std::to_string(kMaxSeg) +
+                      " match segments (DN_READS_MAX_SEG)";
         rc = DN_E_UNSUPPORTED;
         goto done;
     }
@@ -479,17 +542,64 @@ extern "C" int dn_read_coverage(int device, int32_t paired, int64_t n_rows, cons
         rc = DN_E_INVALID;
         goto done;
     }
-    *nnz = h_nsel;
-    *n_isolated_reads = (int64_t) h_niso;
+    *io.nnz = h_nsel;
+    *io.n_isolated_reads = (int64_t) h_niso;
     if (h_nsel > 0) {
-        RD_TRY(hipMemcpyAsync(csr_idx, d_csr_idx, sizeof(int32_t) * (size_t) h_nsel, hipMemcpyDeviceToHost, st));
-        RD_TRY(hipMemcpyAsync(csr_val, d_csr_val, sizeof(int64_t) * (size_t) h_nsel, hipMemcpyDeviceToHost, st));
+        RD_TRY(hipMemcpyAsync(io.csr_idx, d_csr_idx, sizeof(int32_t) * (size_t) h_nsel, hipMemcpyDeviceToHost, st));
+        RD_TRY(hipMemcpyAsync(io.csr_val, d_csr_val, sizeof(int64_t) * (size_t) h_nsel, hipMemcpyDeviceToHost, st));
     }
-    if (ol_total > 0) RD_TRY(hipMemcpyAsync(ol_cov, d_val64, sizeof(int64_t) * (size_t) ol_total, hipMemcpyDeviceToHost, st));
+    if (ol_total > 0) RD_TRY(hipMemcpyAsync(io.ol_cov, d_val64, sizeof(int64_t) * (size_t) ol_total, hipMemcpyDeviceToHost, st));
     if (n_genes > 0) RD_TRY(hipMemcpyAsync(h_counts.data(), d_counts, sizeof(int) * (size_t) n_genes, hipMemcpyDeviceToHost, st));
     RD_TRY(hipStreamSynchronize(st));
-    for (int64_t k = 0; k < n_genes; k++) counts[k] = h_counts[k];
-    if (device_ms) { float ms = 0.f; RD_TRY(hipEventElapsedTime(&ms, e0, e1)); *device_ms = ms; }
+    for (int64_t k = 0; k < n_genes; k++) io.counts[k] = h_counts[k];
+    if (io.device_ms) { float ms = 0.f; RD_TRY(hipEventElapsedTime(&ms, e0, e1)); *io.device_ms = ms; }
+done:
+    (void) hipStreamSynchronize(st);
+    return rc;
+}
+
+}  // namespace
+
+#define COVERAGE_IO                                                                                                    \
+    CoverageIO io{chrom_len, keep_lo, keep_hi, n_exon, exon_iv, n_groups, group_iv, group_gene_off, ol_gene, ol_gene_start0, \
+                  ol_cov_off, ol_exon_off, ol_exon_bounds, n_iso, iso_iv, iso_gene, n_iso_union, iso_union, n_genes, counts,  \
+                  ol_cov, csr_cap, nnz, csr_idx, csr_val, n_isolated_reads, device_ms}
+
+extern "C" int dn_read_coverage(int device, int32_t paired, int64_t n_rows, const int64_t *pos, const int64_t *cigar_off,
+                                const uint8_t *cigar, const int32_t *pair_id, int64_t n_pair_ids,
+                                int64_t chrom_len, int64_t keep_lo, int64_t keep_hi,
+                                int64_t n_exon, const int64_t *exon_iv,
+                                int64_t n_groups, const int64_t *group_iv, const int32_t *group_gene_off,
+                                const int32_t *ol_gene, const int64_t *ol_gene_start0, const int64_t *ol_cov_off,
+                                const int32_t *ol_exon_off, const int64_t *ol_exon_bounds,
+                                int64_t n_iso, const int64_t *iso_iv, const int32_t *iso_gene,
+                                int64_t n_iso_union, const int64_t *iso_union,
+                                int64_t n_genes, int64_t *counts, int64_t *ol_cov,
+                                int64_t csr_cap, int64_t *nnz, int32_t *csr_idx, int64_t *csr_val,
+                                int64_t *n_isolated_reads, double *device_ms)
+{
+    int rc = DN_OK;
+    g_reads_err.clear();
+    if (n_rows < 0 || n_rows > INT32_MAX - 1 || (n_rows > 0 && (!pos || !cigar_off || !cigar))) {
+        g_reads_err = "dn_read_coverage: bad argument";
+        return DN_E_INVALID;
+    }
+    COVERAGE_IO;
+    const int64_t n_bytes = n_rows > 0 ? cigar_off[n_rows] : 0;
+    dn::DeviceBuffer<int64_t> d_pos, d_off;
+    dn::DeviceBuffer<uint8_t> d_cig;
+    dn::Stream st;
+    RD_TRY(hipSetDevice(device));
+    RD_TRY(st.create(hipStreamCreate));
+    RD_TRY(alloc_padded(d_pos, n_rows)); RD_TRY(alloc_padded(d_off, n_rows + 1)); RD_TRY(alloc_padded(d_cig, n_bytes));
+    if (n_rows > 0) {
+        RD_TRY(hipMemcpyAsync(d_pos, pos, sizeof(int64_t) * (size_t) n_rows, hipMemcpyHostToDevice, st));
+        RD_TRY(hipMemcpyAsync(d_off, cigar_off, sizeof(int64_t) * (size_t) (n_rows + 1), hipMemcpyHostToDevice, st));
+    }
+    if (n_bytes > 0) RD_TRY(hipMemcpyAsync(d_cig, cigar, (size_t) n_bytes, hipMemcpyHostToDevice, st));
+    rc = coverage_stages(st, paired, n_rows, d_pos, StrCigars{d_off, d_cig}, pair_id, n_pair_ids, io, [&](int64_t r) {
+        return std::string((const char *) cigar + cigar_off[r], (size_t) (cigar_off[r + 1] - cigar_off[r]));
+    });
 done:
     if (st) (void) hipStreamSynchronize(st);
     return rc;
@@ -505,25 +615,593 @@ extern "C" int dn_reads_cigar_bounds(int device, int64_t n, const int64_t *pos, 
         return DN_E_INVALID;
     }
     if (n == 0) return DN_OK;
-    dn::DeviceBuffer<int64_t> d_pos, d_off, d_b, d_end;
+    dn::DeviceBuffer<int64_t> d_off;
     dn::DeviceBuffer<uint8_t> d_cig;
-    dn::DeviceBuffer<int32_t> d_n;
     dn::Stream st;
     const int64_t n_bytes = cigar_off[n];
     RD_TRY(hipSetDevice(device));
     RD_TRY(st.create(hipStreamCreate));
-    RD_TRY(alloc_padded(d_pos, n)); RD_TRY(alloc_padded(d_off, n + 1)); RD_TRY(alloc_padded(d_cig, n_bytes)); RD_TRY(alloc_padded(d_n, n));
-    RD_TRY(alloc_padded(d_b, n * 2 * max_seg)); RD_TRY(alloc_padded(d_end, n));
-    RD_TRY(hipMemcpyAsync(d_pos, pos, sizeof(int64_t) * (size_t) n, hipMemcpyHostToDevice, st));
+    RD_TRY(alloc_padded(d_off, n + 1)); RD_TRY(alloc_padded(d_cig, n_bytes));
     RD_TRY(hipMemcpyAsync(d_off, cigar_off, sizeof(int64_t) * (size_t) (n + 1), hipMemcpyHostToDevice, st));
     if (n_bytes > 0) RD_TRY(hipMemcpyAsync(d_cig, cigar, (size_t) n_bytes, hipMemcpyHostToDevice, st));
-    RD_TRY(hipMemsetAsync(d_b, 0, sizeof(int64_t) * (size_t) (n * 2 * max_seg), st));
-    hipLaunchKernelGGL(k_cigar_debug, dim3(grid_for(n)), dim3(kNT), 0, st, n, d_pos, d_off, d_cig, max_seg, d_n, d_b, d_end);
-    RD_TRY(hipGetLastError());
-    RD_TRY(hipMemcpyAsync(nseg, d_n, sizeof(int32_t) * (size_t) n, hipMemcpyDeviceToHost, st));
-    RD_TRY(hipMemcpyAsync(bounds, d_b, sizeof(int64_t) * (size_t) (n * 2 * max_seg), hipMemcpyDeviceToHost, st));
-    RD_TRY(hipMemcpyAsync(end_pos, d_end, sizeof(int64_t) * (size_t) n, hipMemcpyDeviceToHost, st));
-    RD_TRY(hipStreamSynchronize(st));
+    rc = cigar_debug(st, n, pos, StrCigars{d_off, d_cig}, max_seg, nseg, bounds, end_pos);
+done:
+    if (st) (void) hipStreamSynchronize(st);
+    return rc;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// BAM records -> device-resident rows (NativeBamReadsProcessor, degnorm_amd/bam.py).
+//
+// The host inflates one window of a chromosome's BGZF blocks and frames it (dn_bam_frame: the start of every complete
+// record); k_bam_scan decodes every record of the window and applies the reference's read filters (reads.py
+// load_chromosome_reads), three scans give each kept row its place, and k_bam_write appends the kept rows, in file order,
+// to the row store: position, binary CIGAR ops, read name and the length of its qname_unpaired prefix.  The coverage
+// stages then read the binary CIGARs in place (BamCigars).  Record fields sit at arbitrary byte offsets: every load below
+// is a byte load.
+
+namespace {
+
+enum { kBamErrMalformed, kBamErrUnsupported, kBamErrNh, kBamErrNoCigar, kBamNErr };
+
+__device__ __forceinline__ uint32_t ld_u16(const uint8_t *p) { return (uint32_t) p[0] | ((uint32_t) p[1] << 8); }
+__device__ __forceinline__ uint32_t ld_u32(const uint8_t *p)
+{
+    return (uint32_t) p[0] | ((uint32_t) p[1] << 8) | ((uint32_t) p[2] << 16) | ((uint32_t) p[3] << 24);
+}
+
+struct BamRec {
+    int32_t ref, pos, next_ref, l_seq;
+    uint32_t l_name, n_cig;
+    int64_t name, cig, aux, end;        // byte offsets into the window
+};
+
+// the fixed part of the record at window offset o; false when the record does not fit its block_size / the window
+__device__ bool bam_parse(const uint8_t *w, int64_t n_bytes, int64_t o, BamRec &R)
+{
+    if (o < 0 || o + 36 > n_bytes) return false;
+    const int32_t bs = (int32_t) ld_u32(w + o);
+    if (bs < 32 || o + 4 + (int64_t) bs > n_bytes) return false;
+    const uint8_t *p = w + o + 4;
+    R.ref = (int32_t) ld_u32(p);
+    R.pos = (int32_t) ld_u32(p + 4);
+    R.l_name = p[8];
+    R.n_cig = ld_u16(p + 12);
+    R.l_seq = (int32_t) ld_u32(p + 16);
+    R.next_ref = (int32_t) ld_u32(p + 20);
+    R.name = o + 36;
+    R.cig = R.name + R.l_name;
+    R.end = o + 4 + bs;
+    if (R.l_name < 1 || R.l_seq < 0) return false;
+    R.aux = R.cig + 4 * (int64_t) R.n_cig + ((int64_t) R.l_seq + 1) / 2 + R.l_seq;
+    return R.aux <= R.end;
+}
+
+__device__ __forceinline__ int aux_size(uint8_t t)
+{
+    switch (t) {
+    case 'A': case 'c': case 'C': return 1;
+    case 's': case 'S': return 2;
+    case 'i': case 'I': case 'f': return 4;
+    default: return 0;
+    }
+}
+
+// Walk the aux fields [q, end): the first NH tag (nh_state 0 absent, 1 integer with value nh, 2 another type) and whether
+// a CG tag is present.  False when a field runs past the record or has an unknown type.
+__device__ bool bam_aux(const uint8_t *w, int64_t q, int64_t end, int &nh_state, int64_t &nh, bool &cg)
+{
+    nh_state = 0;
+    nh = 0;
+    cg = false;
+    while (q < end) {
+        if (q + 3 > end) return false;
+        const uint8_t t0 = w[q], t1 = w[q + 1], ty = w[q + 2];
+        q += 3;
+        const bool is_nh = t0 == 'N' && t1 == 'H' && nh_state == 0;
+        if (t0 == 'C' && t1 == 'G') cg = true;
+        const int sz = aux_size(ty);
+        if (sz > 0) {
+            if (q + sz > end) return false;
+            if (is_nh) {
+                nh_state = 1;
+                switch (ty) {
+                case 'c': nh = (int8_t) w[q]; break;
+                case 'C': nh = w[q]; break;
+                case 's': nh = (int16_t) ld_u16(w + q); break;
+                case 'S': nh = ld_u16(w + q); break;
+                case 'i': nh = (int32_t) ld_u32(w + q); break;
+                case 'I': nh = ld_u32(w + q); break;
+                default: nh_state = 2;                      // A, f
+                }
+            }
+            q += sz;
+        } else if (ty == 'Z' || ty == 'H') {
+            while (q < end && w[q] != 0) q++;
+            if (q >= end) return false;
+            q++;
+            if (is_nh) nh_state = 2;
+        } else if (ty == 'B') {
+            if (q + 5 > end) return false;
+            const int esz = aux_size(w[q]);
+            const int64_t cnt = ld_u32(w + q + 1);
+            if (esz == 0 || w[q] == 'A') return false;
+            q += 5;
+            if (cnt * esz > end - q) return false;
+            q += cnt * esz;
+            if (is_nh) nh_state = 2;
+        } else {
+            return false;
+        }
+    }
+    return true;
+}
+
+struct BamFilter {
+    int32_t tid, unique, paired;
+};
+
+// per record: kept (refID == tid, NH rule, mate rule), its op count and name length when kept; errors (first record index)
+__global__ __launch_bounds__(kNT) void k_bam_scan(const uint8_t *__restrict__ w, int64_t n_bytes, const int64_t *__restrict__ rec_off,
+                                                  int64_t n_rec, BamFilter F, int32_t *__restrict__ keep, int32_t *__restrict__ n_ops,
+                                                  int32_t *__restrict__ n_name, unsigned long long *__restrict__ err)
+{
+    for (int64_t i = (int64_t) blockIdx.x * kNT + threadIdx.x; i < n_rec; i += (int64_t) gridDim.x * kNT) {
+        BamRec R;
+        int32_t k = 0;
+        if (!bam_parse(w, n_bytes, rec_off[i], R)) {
+            atomicMin(err + kBamErrMalformed, (unsigned long long) i);
+        } else if (R.ref == F.tid) {
+            int nh_state;
+            int64_t nh;
+            bool cg;
+            k = 1;
+            if (!bam_aux(w, R.aux, R.end, nh_state, nh, cg)) { atomicMin(err + kBamErrMalformed, (unsigned long long) i); k = 0; }
+            else if (F.unique && nh_state == 2) { atomicMin(err + kBamErrNh, (unsigned long long) i); k = 0; }
+            else if (F.unique && nh_state == 1 && nh > 1) k = 0;
+            else if (F.paired && R.next_ref == -1) k = 0;
+            if (k) {
+                if (R.n_cig == 0) atomicMin(err + kBamErrNoCigar, (unsigned long long) i);
+                bool bad = false;
+                for (uint32_t c = 0; c < R.n_cig; c++) bad |= (ld_u32(w + R.cig + 4 * (int64_t) c) & 15u) > 8u;
+                // a CIGAR moved to the CG tag leaves <l_seq>S<ref_len>N in the record
+                if (cg && R.n_cig == 2 && ld_u32(w + R.cig) == (((uint32_t) R.l_seq << 4) | 4u) && (ld_u32(w + R.cig + 4) & 15u) == 3u)
+                    bad = true;
+                if (bad) atomicMin(err + kBamErrUnsupported, (unsigned long long) i);
+            }
+        }
+        keep[i] = k;
+        n_ops[i] = k ? (int32_t) R.n_cig : 0;
+        n_name[i] = k ? (int32_t) R.l_name - 1 : 0;
+    }
+}
+
+struct BamRowsOut {
+    int64_t *pos, *op_beg, *name_beg;
+    int32_t *n_op, *name_len, *key_len;
+    uint32_t *ops;
+    uint8_t *names;
+    int32_t *max_key;
+};
+
+__global__ __launch_bounds__(kNT) void k_bam_write(const uint8_t *__restrict__ w, int64_t n_bytes, const int64_t *__restrict__ rec_off,
+                                                   int64_t n_rec, const int32_t *__restrict__ keep, const int32_t *__restrict__ rank,
+                                                   const int32_t *__restrict__ op_rank, const int32_t *__restrict__ name_rank,
+                                                   int64_t row0, int64_t op0, int64_t name0, BamRowsOut O)
+{
+    for (int64_t i = (int64_t) blockIdx.x * kNT + threadIdx.x; i < n_rec; i += (int64_t) gridDim.x * kNT) {
+        BamRec R;
+        if (!keep[i] || !bam_parse(w, n_bytes, rec_off[i], R)) continue;
+        const int64_t r = row0 + rank[i], ob = op0 + op_rank[i], nb = name0 + name_rank[i];
+        const int32_t nl = (int32_t) R.l_name - 1;
+        O.pos[r] = R.pos;
+        O.op_beg[r] = ob;
+        O.n_op[r] = (int32_t) R.n_cig;
+        for (uint32_t c = 0; c < R.n_cig; c++) O.ops[ob + c] = ld_u32(w + R.cig + 4 * (int64_t) c);
+        int32_t key = 0;                        // qname_unpaired = the name up to its last '.', '' without one
+        for (int32_t c = 0; c < nl; c++) {
+            const uint8_t ch = w[R.name + c];
+            O.names[nb + c] = ch;
+            if (ch == '.') key = c;
+        }
+        O.name_beg[r] = nb;
+        O.name_len[r] = nl;
+        O.key_len[r] = key;
+        atomicMax(O.max_key, key);
+    }
+}
+
+__global__ __launch_bounds__(kNT) void k_bam_keys(int64_t n, const int64_t *__restrict__ name_beg, const int32_t *__restrict__ key_len,
+                                                  const uint8_t *__restrict__ names, int32_t width, uint8_t *__restrict__ out)
+{
+    for (int64_t r = (int64_t) blockIdx.x * kNT + threadIdx.x; r < n; r += (int64_t) gridDim.x * kNT)
+        for (int32_t c = 0; c < width; c++) out[r * width + c] = c < key_len[r] ? names[name_beg[r] + c] : 0;
+}
+
+__global__ __launch_bounds__(kNT) void k_bam_gather(int64_t n, const int32_t *__restrict__ order, const int64_t *__restrict__ pos,
+                                                    const int64_t *__restrict__ op_beg, const int32_t *__restrict__ n_op,
+                                                    int64_t *__restrict__ pos_o, int64_t *__restrict__ op_beg_o, int32_t *__restrict__ n_op_o)
+{
+    for (int64_t r = (int64_t) blockIdx.x * kNT + threadIdx.x; r < n; r += (int64_t) gridDim.x * kNT) {
+        const int32_t s = order[r];
+        pos_o[r] = pos[s]; op_beg_o[r] = op_beg[s]; n_op_o[r] = n_op[s];
+    }
+}
+
+int64_t next_cap(int64_t cap, int64_t need)
+{
+    int64_t nc = cap * 2 > need ? cap * 2 : need;
+    return nc < 1024 ? 1024 : nc;
+}
+
+// a buffer of new_cap elements holding the first `used` elements of b (the stream has finished with b when this returns)
+template <class T> hipError_t resize(dn::DeviceBuffer<T> &b, int64_t used, int64_t new_cap, hipStream_t st)
+{
+    dn::DeviceBuffer<T> nb;
+    hipError_t e = alloc_padded(nb, (size_t) new_cap);
+    if (e == hipSuccess && used > 0) e = hipMemcpyAsync(nb, b, sizeof(T) * (size_t) used, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return e;
+    b = std::move(nb);
+    return hipSuccess;
+}
+
+std::string bam_name(const uint8_t *w, int64_t n_bytes, int64_t o)
+{
+    if (o + 36 > n_bytes) return "?";
+    const int64_t l = w[o + 12];
+    if (l < 1 || o + 36 + l > n_bytes) return "?";
+    return std::string((const char *) w + o + 36, (size_t) (l - 1));
+}
+
+std::string cigar_string(const uint32_t *ops, int64_t n)
+{
+    std::string s;
+    for (int64_t k = 0; k < n; k++) s += std::to_string(ops[k] >> 4) + "MIDNSHP=X"[(ops[k] & 15u) < 9u ? (ops[k] & 15u) : 0];
+    return s;
+}
+
+}  // namespace
+
+struct dn_bam_rows_s {
+    int device;
+    BamFilter F;
+    dn::Stream st;
+    int64_t n_rows = 0, n_ops = 0, n_names = 0;
+    int64_t cap_rows = 0, cap_ops = 0, cap_names = 0, cap_win = 0, cap_rec = 0;
+    dn::DeviceBuffer<int64_t> pos, op_beg, name_beg, rec_off;
+    dn::DeviceBuffer<int32_t> n_op, name_len, key_len, max_key, keep, w_ops, w_name, rank, op_rank, name_rank;
+    dn::DeviceBuffer<uint32_t> ops;
+    dn::DeviceBuffer<uint8_t> names, win;
+    dn::DeviceBuffer<unsigned long long> err;
+    std::vector<dn::DeviceBuffer<uint8_t>> tmp;
+    size_t tmp_bytes = 0;
+    std::string no_cigar;                  // the name of the first kept row without CIGAR ops ("" while there is none)
+    bool has_no_cigar = false;
+};
+
+#define BAM_TRY(expr)                                                                                                   \
+    do {                                                                                                                \
+        hipError_t e_ = (expr);                                                                                         \
+        if (e_ != hipSuccess) { g_reads_err = std::string(#expr) + ": " + hipGetErrorString(e_); return DN_E_HIP; }     \
+    } while (0)
+
+extern "C" int dn_bam_frame(const uint8_t *buf, int64_t n_bytes, int32_t tid, int32_t *last_pos, int64_t *rec_off, int64_t cap,
+                            int64_t *n_rec, int64_t *consumed)
+{
+    g_reads_err.clear();
+    if (n_bytes < 0 || (n_bytes > 0 && !buf) || cap < 0 || (cap > 0 && !rec_off) || !n_rec || !consumed || (tid >= 0 && !last_pos)) {
+        g_reads_err = "dn_bam_frame: bad argument";
+        return DN_E_INVALID;
+    }
+    int64_t o = 0, n = 0;
+    while (o + 4 <= n_bytes) {
+        int32_t bs, ref, pos;
+        memcpy(&bs, buf + o, 4);
+        if (bs < 32) {
+            g_reads_err = "malformed BAM record at byte " + std::to_string(o) + " of the window (block_size " + std::to_string(bs) + ")";
+            return DN_E_INVALID;
+        }
+        if (o + 4 + (int64_t) bs > n_bytes) break;          // the tail: carried over to the next window
+        if (n >= cap) { g_reads_err = "dn_bam_frame: more records than cap"; return DN_E_INVALID; }
+        if (tid >= 0) {
+            memcpy(&ref, buf + o + 4, 4);
+            memcpy(&pos, buf + o + 8, 4);
+            if (ref != tid || pos < *last_pos) {
+                g_reads_err = "BAM file is not sorted by coordinate, or its index is stale: a record of refID " + std::to_string(ref) +
+                              " at position " + std::to_string(pos) + " follows position " + std::to_string(*last_pos) +
+                              " inside the index range of refID " + std::to_string(tid);
+                return DN_E_INVALID;
+            }
+            *last_pos = pos;
+        }
+        rec_off[n++] = o;
+        o += 4 + (int64_t) bs;
+    }
+    *n_rec = n;
+    *consumed = o;
+    return DN_OK;
+}
+
+extern "C" int dn_bam_rows_create(int device, int32_t tid, int32_t unique_alignment, int32_t paired, dn_bam_rows *out)
+{
+    g_reads_err.clear();
+    if (!out) { g_reads_err = "dn_bam_rows_create: bad argument"; return DN_E_INVALID; }
+    *out = nullptr;
+    dn_bam_rows_s *h = new dn_bam_rows_s();
+    h->device = device;
+    h->F = BamFilter{tid, unique_alignment ? 1 : 0, paired ? 1 : 0};
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) e = h->st.create(hipStreamCreate);
+    if (e == hipSuccess) e = alloc_padded(h->max_key, 1);
+    if (e == hipSuccess) e = alloc_padded(h->err, kBamNErr);
+    if (e == hipSuccess) e = hipMemsetAsync(h->max_key, 0, sizeof(int32_t), h->st);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->st);
+    if (e != hipSuccess) {
+        g_reads_err = std::string("dn_bam_rows_create: ") + hipGetErrorString(e);
+        delete h;
+        return DN_E_HIP;
+    }
+    *out = h;
+    return DN_OK;
+}
+
+extern "C" void dn_bam_rows_destroy(dn_bam_rows h)
+{
+    if (!h) return;
+    (void) hipSetDevice(h->device);
+    if (h->st) (void) hipStreamSynchronize(h->st);
+    delete h;
+}
+
+extern "C" int dn_bam_rows_append(dn_bam_rows h, const uint8_t *window, int64_t n_bytes, const int64_t *rec_off, int64_t n_rec)
+{
+    g_reads_err.clear();
+    if (!h || n_bytes < 0 || n_bytes > INT32_MAX || n_rec < 0 || (n_rec > 0 && (!window || !rec_off))) {
+        g_reads_err = "dn_bam_rows_append: bad argument";
+        return DN_E_INVALID;
+    }
+    if (n_rec == 0) return DN_OK;
+    for (int64_t i = 0; i < n_rec; i++)              // the kernels read 36 bytes at every offset: keep them inside the window
+        if (rec_off[i] < 0 || rec_off[i] + 36 > n_bytes) { g_reads_err = "dn_bam_rows_append: record offset outside the window"; return DN_E_INVALID; }
+    hipStream_t st = h->st;
+    BAM_TRY(hipSetDevice(h->device));
+    if (n_bytes > h->cap_win) {                       // window scratch: nothing to keep (the previous append has finished)
+        const int64_t c = next_cap(h->cap_win, n_bytes);
+        BAM_TRY(resize(h->win, 0, c, st));
+        h->cap_win = c;
+    }
+    if (n_rec + 1 > h->cap_rec) {
+        const int64_t c = next_cap(h->cap_rec, n_rec + 1);
+        BAM_TRY(resize(h->rec_off, 0, c, st)); BAM_TRY(resize(h->keep, 0, c, st)); BAM_TRY(resize(h->w_ops, 0, c, st));
+        BAM_TRY(resize(h->w_name, 0, c, st)); BAM_TRY(resize(h->rank, 0, c, st)); BAM_TRY(resize(h->op_rank, 0, c, st));
+        BAM_TRY(resize(h->name_rank, 0, c, st));
+        h->cap_rec = c;
+    }
+    BAM_TRY(hipMemcpyAsync(h->win, window, (size_t) n_bytes, hipMemcpyHostToDevice, st));
+    BAM_TRY(hipMemcpyAsync(h->rec_off, rec_off, sizeof(int64_t) * (size_t) n_rec, hipMemcpyHostToDevice, st));
+    BAM_TRY(hipMemsetAsync(h->err, 0xff, sizeof(unsigned long long) * kBamNErr, st));
+    BAM_TRY(hipMemsetAsync(h->keep + n_rec, 0, sizeof(int32_t), st));
+    BAM_TRY(hipMemsetAsync(h->w_ops + n_rec, 0, sizeof(int32_t), st));
+    BAM_TRY(hipMemsetAsync(h->w_name + n_rec, 0, sizeof(int32_t), st));
+    hipLaunchKernelGGL(k_bam_scan, dim3(grid_for(n_rec)), dim3(kNT), 0, st, h->win.get(), n_bytes, h->rec_off.get(), n_rec, h->F,
+                       h->keep.get(), h->w_ops.get(), h->w_name.get(), h->err.get());
+    BAM_TRY(hipGetLastError());
+    {
+        const int n = (int) n_rec + 1;
+        size_t need = 0;
+        BAM_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, h->keep.get(), h->rank.get(), n, st));
+        if (need > h->tmp_bytes) { h->tmp.emplace_back(); BAM_TRY(alloc_padded(h->tmp.back(), need)); h->tmp_bytes = need; }
+        void *t = h->tmp.back();
+        BAM_TRY(hipcub::DeviceScan::ExclusiveSum(t, need, h->keep.get(), h->rank.get(), n, st));
+        BAM_TRY(hipcub::DeviceScan::ExclusiveSum(t, need, h->w_ops.get(), h->op_rank.get(), n, st));
+        BAM_TRY(hipcub::DeviceScan::ExclusiveSum(t, need, h->w_name.get(), h->name_rank.get(), n, st));
+    }
+    int32_t tot[3];
+    unsigned long long herr[kBamNErr];
+    BAM_TRY(hipMemcpyAsync(tot + 0, h->rank + n_rec, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    BAM_TRY(hipMemcpyAsync(tot + 1, h->op_rank + n_rec, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    BAM_TRY(hipMemcpyAsync(tot + 2, h->name_rank + n_rec, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    BAM_TRY(hipMemcpyAsync(herr, h->err, sizeof(herr), hipMemcpyDeviceToHost, st));
+    BAM_TRY(hipStreamSynchronize(st));
+    if (herr[kBamErrMalformed] != ~0ull) {
+        g_reads_err = "malformed BAM record (read " + bam_name(window, n_bytes, rec_off[herr[kBamErrMalformed]]) + ")";
+        return DN_E_INVALID;
+    }
+    if (herr[kBamErrNh] != ~0ull) {
+        g_reads_err = "read " + bam_name(window, n_bytes, rec_off[herr[kBamErrNh]]) + " has an NH tag of a non-integer type";
+        return DN_E_INVALID;
+    }
+    if (herr[kBamErrUnsupported] != ~0ull) {
+        g_reads_err = "read " + bam_name(window, n_bytes, rec_off[herr[kBamErrUnsupported]]) +
+                      " has a CIGAR op code above 8 or a CIGAR moved to the CG tag (not supported)";
+        return DN_E_UNSUPPORTED;
+    }
+    if (herr[kBamErrNoCigar] != ~0ull && !h->has_no_cigar) {
+        h->has_no_cigar = true;
+        h->no_cigar = bam_name(window, n_bytes, rec_off[herr[kBamErrNoCigar]]);
+    }
+    if (h->n_rows + tot[0] > INT32_MAX - 1) { g_reads_err = "dn_bam_rows_append: more than 2^31 - 2 rows"; return DN_E_UNSUPPORTED; }
+    if (tot[0] > 0) {
+        if (h->n_rows + tot[0] > h->cap_rows) {
+            const int64_t c = next_cap(h->cap_rows, h->n_rows + tot[0]), n = h->n_rows;
+            BAM_TRY(resize(h->pos, n, c, st)); BAM_TRY(resize(h->op_beg, n, c, st)); BAM_TRY(resize(h->name_beg, n, c, st));
+            BAM_TRY(resize(h->n_op, n, c, st)); BAM_TRY(resize(h->name_len, n, c, st)); BAM_TRY(resize(h->key_len, n, c, st));
+            h->cap_rows = c;
+        }
+        if (h->n_ops + tot[1] > h->cap_ops) {
+            const int64_t c = next_cap(h->cap_ops, h->n_ops + tot[1]);
+            BAM_TRY(resize(h->ops, h->n_ops, c, st));
+            h->cap_ops = c;
+        }
+        if (h->n_names + tot[2] > h->cap_names) {
+            const int64_t c = next_cap(h->cap_names, h->n_names + tot[2]);
+            BAM_TRY(resize(h->names, h->n_names, c, st));
+            h->cap_names = c;
+        }
+        BamRowsOut O{h->pos, h->op_beg, h->name_beg, h->n_op, h->name_len, h->key_len, h->ops, h->names, h->max_key};
+        hipLaunchKernelGGL(k_bam_write, dim3(grid_for(n_rec)), dim3(kNT), 0, st, h->win.get(), n_bytes, h->rec_off.get(), n_rec,
+                           h->keep.get(), h->rank.get(), h->op_rank.get(), h->name_rank.get(), h->n_rows, h->n_ops, h->n_names, O);
+        BAM_TRY(hipGetLastError());
+        BAM_TRY(hipStreamSynchronize(st));
+        h->n_rows += tot[0];
+        h->n_ops += tot[1];
+        h->n_names += tot[2];
+    }
+    return DN_OK;
+}
+
+extern "C" int dn_bam_rows_info(dn_bam_rows h, int64_t *n_rows, int64_t *n_ops, int64_t *n_name_bytes, int32_t *max_key_len)
+{
+    g_reads_err.clear();
+    if (!h) { g_reads_err = "dn_bam_rows_info: bad argument"; return DN_E_INVALID; }
+    if (n_rows) *n_rows = h->n_rows;
+    if (n_ops) *n_ops = h->n_ops;
+    if (n_name_bytes) *n_name_bytes = h->n_names;
+    if (max_key_len) {
+        BAM_TRY(hipSetDevice(h->device));
+        BAM_TRY(hipMemcpyAsync(max_key_len, h->max_key, sizeof(int32_t), hipMemcpyDeviceToHost, h->st));
+        BAM_TRY(hipStreamSynchronize(h->st));
+    }
+    return DN_OK;
+}
+
+extern "C" int dn_bam_rows_keys(dn_bam_rows h, int32_t width, uint8_t *keys)
+{
+    g_reads_err.clear();
+    if (!h || width < 1 || (h->n_rows > 0 && !keys)) { g_reads_err = "dn_bam_rows_keys: bad argument"; return DN_E_INVALID; }
+    if (h->n_rows == 0) return DN_OK;
+    int32_t mk = 0;
+    BAM_TRY(hipSetDevice(h->device));
+    BAM_TRY(hipMemcpyAsync(&mk, h->max_key, sizeof(int32_t), hipMemcpyDeviceToHost, h->st));
+    BAM_TRY(hipStreamSynchronize(h->st));
+    if (width < mk) { g_reads_err = "dn_bam_rows_keys: width below the longest key (" + std::to_string(mk) + ")"; return DN_E_INVALID; }
+    dn::DeviceBuffer<uint8_t> d_keys;
+    BAM_TRY(alloc_padded(d_keys, (size_t) (h->n_rows * width)));
+    hipLaunchKernelGGL(k_bam_keys, dim3(grid_for(h->n_rows)), dim3(kNT), 0, h->st, h->n_rows, h->name_beg.get(), h->key_len.get(),
+                       h->names.get(), width, d_keys.get());
+    BAM_TRY(hipGetLastError());
+    BAM_TRY(hipMemcpyAsync(keys, d_keys, (size_t) (h->n_rows * width), hipMemcpyDeviceToHost, h->st));
+    BAM_TRY(hipStreamSynchronize(h->st));
+    return DN_OK;
+}
+
+extern "C" int dn_bam_rows_fetch(dn_bam_rows h, int64_t *pos, int64_t *op_beg, int32_t *n_op, uint32_t *ops, int64_t *name_beg,
+                                 int32_t *name_len, uint8_t *names)
+{
+    g_reads_err.clear();
+    if (!h) { g_reads_err = "dn_bam_rows_fetch: bad argument"; return DN_E_INVALID; }
+    hipStream_t st = h->st;
+    const size_t n = (size_t) h->n_rows;
+    BAM_TRY(hipSetDevice(h->device));
+    if (n > 0) {
+        if (pos) BAM_TRY(hipMemcpyAsync(pos, h->pos, sizeof(int64_t) * n, hipMemcpyDeviceToHost, st));
+        if (op_beg) BAM_TRY(hipMemcpyAsync(op_beg, h->op_beg, sizeof(int64_t) * n, hipMemcpyDeviceToHost, st));
+        if (n_op) BAM_TRY(hipMemcpyAsync(n_op, h->n_op, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+        if (name_beg) BAM_TRY(hipMemcpyAsync(name_beg, h->name_beg, sizeof(int64_t) * n, hipMemcpyDeviceToHost, st));
+        if (name_len) BAM_TRY(hipMemcpyAsync(name_len, h->name_len, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+    }
+    if (ops && h->n_ops > 0) BAM_TRY(hipMemcpyAsync(ops, h->ops, sizeof(uint32_t) * (size_t) h->n_ops, hipMemcpyDeviceToHost, st));
+    if (names && h->n_names > 0) BAM_TRY(hipMemcpyAsync(names, h->names, (size_t) h->n_names, hipMemcpyDeviceToHost, st));
+    BAM_TRY(hipStreamSynchronize(st));
+    return DN_OK;
+}
+
+extern "C" int dn_bam_rows_coverage(dn_bam_rows h, const int32_t *order, const int32_t *pair_id, int64_t n_pair_ids,
+                                    int64_t chrom_len, int64_t keep_lo, int64_t keep_hi,
+                                    int64_t n_exon, const int64_t *exon_iv,
+                                    int64_t n_groups, const int64_t *group_iv, const int32_t *group_gene_off,
+                                    const int32_t *ol_gene, const int64_t *ol_gene_start0, const int64_t *ol_cov_off,
+                                    const int32_t *ol_exon_off, const int64_t *ol_exon_bounds,
+                                    int64_t n_iso, const int64_t *iso_iv, const int32_t *iso_gene,
+                                    int64_t n_iso_union, const int64_t *iso_union,
+                                    int64_t n_genes, int64_t *counts, int64_t *ol_cov,
+                                    int64_t csr_cap, int64_t *nnz, int32_t *csr_idx, int64_t *csr_val,
+                                    int64_t *n_isolated_reads, double *device_ms)
+{
+    int rc = DN_OK;
+    g_reads_err.clear();
+    if (!h || (h->F.paired && h->n_rows > 0 && !order)) { g_reads_err = "dn_bam_rows_coverage: bad argument"; return DN_E_INVALID; }
+    if (h->has_no_cigar) {                                  // the reference's CIGAR regex on cigarstring None
+        g_reads_err = "read " + h->no_cigar + " has no CIGAR string";
+        return DN_E_INVALID;
+    }
+    COVERAGE_IO;
+    const int64_t n = h->n_rows;
+    hipStream_t st = h->st;
+    std::vector<int32_t> h_order;
+    dn::DeviceBuffer<int64_t> g_pos, g_beg;
+    dn::DeviceBuffer<int32_t> g_cnt, d_order;
+    const int64_t *p_pos = h->pos, *p_beg = h->op_beg;
+    const int32_t *p_cnt = h->n_op;
+    RD_TRY(hipSetDevice(h->device));
+    if (order && n > 0) {                                   // rows in the caller's order (paired: the sort by qname_unpaired)
+        h_order.assign(order, order + n);
+        for (int64_t r = 0; r < n; r++)
+            if (order[r] < 0 || order[r] >= n) { g_reads_err = "dn_bam_rows_coverage: order out of range"; return DN_E_INVALID; }
+        RD_TRY(alloc_padded(d_order, n)); RD_TRY(alloc_padded(g_pos, n)); RD_TRY(alloc_padded(g_beg, n)); RD_TRY(alloc_padded(g_cnt, n));
+        RD_TRY(hipMemcpyAsync(d_order, order, sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_bam_gather, dim3(grid_for(n)), dim3(kNT), 0, st, n, d_order.get(), h->pos.get(), h->op_beg.get(),
+                           h->n_op.get(), g_pos.get(), g_beg.get(), g_cnt.get());
+        RD_TRY(hipGetLastError());
+        p_pos = g_pos; p_beg = g_beg; p_cnt = g_cnt;
+    }
+    rc = coverage_stages(st, h->F.paired, n, p_pos, BamCigars{p_beg, p_cnt, h->ops}, pair_id, n_pair_ids, io, [&](int64_t r) {
+        const int64_t s = h_order.empty() ? r : h_order[r];
+        int64_t beg = 0;
+        int32_t cnt = 0;
+        std::vector<uint32_t> ops;
+        std::string name;
+        if (hipMemcpy(&beg, h->op_beg + s, sizeof(beg), hipMemcpyDeviceToHost) == hipSuccess &&
+            hipMemcpy(&cnt, h->n_op + s, sizeof(cnt), hipMemcpyDeviceToHost) == hipSuccess && cnt >= 0) {
+            ops.resize((size_t) cnt);
+            if (cnt > 0 && hipMemcpy(ops.data(), h->ops + beg, sizeof(uint32_t) * (size_t) cnt, hipMemcpyDeviceToHost) != hipSuccess) ops.clear();
+        }
+        int64_t nb = 0;
+        int32_t nl = 0;
+        if (hipMemcpy(&nb, h->name_beg + s, sizeof(nb), hipMemcpyDeviceToHost) == hipSuccess &&
+            hipMemcpy(&nl, h->name_len + s, sizeof(nl), hipMemcpyDeviceToHost) == hipSuccess && nl > 0) {
+            name.resize((size_t) nl);
+            if (hipMemcpy(&name[0], h->names + nb, (size_t) nl, hipMemcpyDeviceToHost) != hipSuccess) name = "?";
+        }
+        return cigar_string(ops.data(), (int64_t) ops.size()) + " (read " + name + ")";
+    });
+done:
+    (void) hipStreamSynchronize(st);
+    return rc;
+}
+
+extern "C" int dn_bam_cigar_bounds(int device, int64_t n, const int64_t *pos, const int64_t *op_off, const uint32_t *ops,
+                                   int32_t max_seg, int32_t *nseg, int64_t *bounds, int64_t *end_pos)
+{
+    int rc = DN_OK;
+    g_reads_err.clear();
+    if (n < 0 || max_seg < 1 || max_seg > kMaxSeg || (n > 0 && (!pos || !op_off || !nseg || !bounds || !end_pos))) {
+        g_reads_err = "dn_bam_cigar_bounds: bad argument";
+        return DN_E_INVALID;
+    }
+    if (n == 0) return DN_OK;
+    const int64_t n_ops = op_off[n];
+    std::vector<int32_t> cnt((size_t) n);
+    for (int64_t r = 0; r < n; r++) {
+        if (op_off[r + 1] < op_off[r] || op_off[r] < 0 || op_off[r + 1] - op_off[r] > INT32_MAX) {
+            g_reads_err = "dn_bam_cigar_bounds: bad op_off";
+            return DN_E_INVALID;
+        }
+        cnt[(size_t) r] = (int32_t) (op_off[r + 1] - op_off[r]);
+    }
+    if (n_ops > 0 && !ops) { g_reads_err = "dn_bam_cigar_bounds: bad argument"; return DN_E_INVALID; }
+    dn::DeviceBuffer<int64_t> d_beg;
+    dn::DeviceBuffer<int32_t> d_cnt;
+    dn::DeviceBuffer<uint32_t> d_ops;
+    dn::Stream st;
+    RD_TRY(hipSetDevice(device));
+    RD_TRY(st.create(hipStreamCreate));
+    RD_TRY(alloc_padded(d_beg, n)); RD_TRY(alloc_padded(d_cnt, n)); RD_TRY(alloc_padded(d_ops, n_ops));
+    RD_TRY(hipMemcpyAsync(d_beg, op_off, sizeof(int64_t) * (size_t) n, hipMemcpyHostToDevice, st));
+    RD_TRY(hipMemcpyAsync(d_cnt, cnt.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, st));
+    if (n_ops > 0) RD_TRY(hipMemcpyAsync(d_ops, ops, sizeof(uint32_t) * (size_t) n_ops, hipMemcpyHostToDevice, st));
+    rc = cigar_debug(st, n, pos, BamCigars{d_beg, d_cnt, d_ops}, max_seg, nseg, bounds, end_pos);
 done:
     if (st) (void) hipStreamSynchronize(st);
     return rc;

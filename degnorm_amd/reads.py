@@ -248,10 +248,15 @@ def chromosome_coverage_read_counts_df(reads_df, chrom_len, gene_overlap_dat, ch
     read reached the isolated stage; {overlap gene: int64 coverage over its exon positions} in gene_overlap_dat order;
     {gene: read count} in chrom_gene_df order)
     """
-    from scipy import sparse
     ann = Annotation(chrom_len, gene_overlap_dat, chrom_gene_df, chrom_exon_df)
     pos, off, cig, pair_id, n_ids = pack_reads(reads_df, paired)
     counts, ol_cov, idx, val, n_iso_reads, _ = device_read_coverage(pos, off, cig, pair_id, n_ids, ann, paired, device)
+    return coverage_outputs(ann, counts, ol_cov, idx, val, n_iso_reads)
+
+
+def coverage_outputs(ann, counts, ol_cov, idx, val, n_iso_reads):
+    """The results of one device coverage call in the reference's form: (CSR row or None, {overlap gene: coverage}, counts)."""
+    from scipy import sparse
     ol_span = {}
     for q, g in enumerate(ann.ol_names):
         ol_span[g] = ol_cov[ann.ol_cov_off[q]:ann.ol_cov_off[q + 1] - 1][ann.ol_tidx[q]]
@@ -270,6 +275,18 @@ def _require_pysam():
         raise ImportError('reading .bam files needs pysam, which is not installed ({0}); load the reads yourself and '
                           'call degnorm_amd.reads.chromosome_coverage_read_counts_df'.format(e))
     return pysam
+
+
+def reads_frame(rows, paired):
+    """The reference's reads DataFrame from (qname, pos, cigar) rows in file order: `qname_unpaired` added and the rows
+    sorted by it (pandas' default quicksort) when paired."""
+    from pandas import DataFrame
+    df = DataFrame(rows, columns=['qname', 'pos', 'cigar'])
+    df['pos'] = df['pos'].astype('int')
+    if paired:
+        df['qname_unpaired'] = df.qname.apply(lambda x: '.'.join(x.split('.')[:-1]))
+        df.sort_values('qname_unpaired', inplace=True)
+    return df
 
 
 class BamReadsProcessor(object):
@@ -292,7 +309,7 @@ class BamReadsProcessor(object):
         self.paired = None
         self.chroms = chroms
         self.unique_alignment = unique_alignment
-        self._pysam = _require_pysam()
+        self._open_backend()
         if not os.path.isfile(bam_file) or not bam_file.endswith('.bam'):
             raise ValueError('{0} is not a .bam file'.format(bam_file))
         if not os.path.isfile(index_file):
@@ -304,6 +321,10 @@ class BamReadsProcessor(object):
         if self.verbose:
             logging.info('SAMPLE {0} -- sample contains {1} reads'.format(self.sample_id, 'paired' if self.paired else 'single-end'))
 
+    def _open_backend(self):
+        """What reading the file needs, checked before the file itself: pysam."""
+        self._pysam = _require_pysam()
+
     def _open(self):
         pysam = getattr(self, '_pysam', None) or _require_pysam()
         return pysam.AlignmentFile(self.filename, 'rb', index_filename=self.index_filename)
@@ -311,26 +332,35 @@ class BamReadsProcessor(object):
     def get_header(self):
         """self.header: DataFrame of `chr`, `length` from the .bam header; self.chroms: requested chromosomes in it."""
         from pandas import DataFrame
-        bam = self._open()
-        sq = bam.header.to_dict().get('SQ', [])
-        bam.close()
-        lengths = {h.get('SN'): h.get('LN') for h in sq}
+        lengths = self._reference_lengths()
         self.header = DataFrame(list(lengths.items()), columns=['chr', 'length'])
         if self.chroms is not None:
             self.chroms = np.intersect1d(self.chroms, self.header.chr.unique()).tolist()
         else:
             self.chroms = self.header.chr.unique().tolist()
 
-    def determine_if_paired(self):
-        """Paired when the query names of the first ~300 reads end in exactly the suffixes .1 and .2."""
-        self.paired = False
+    def _reference_lengths(self):
+        """{SQ name: length} of the .bam header."""
+        bam = self._open()
+        sq = bam.header.to_dict().get('SQ', [])
+        bam.close()
+        return {h.get('SN'): h.get('LN') for h in sq}
+
+    def _leading_query_names(self, chrom):
+        """Query names of the first 301 reads of chrom, in file order, unfiltered."""
         bam = self._open()
         names = []
-        for read in bam.fetch(self.chroms[0]):
+        for read in bam.fetch(chrom):
             names.append(read.query_name)
             if len(names) > 300:
                 break
         bam.close()
+        return names
+
+    def determine_if_paired(self):
+        """Paired when the query names of the first ~300 reads end in exactly the suffixes .1 and .2."""
+        self.paired = False
+        names = self._leading_query_names(self.chroms[0])
         self.paired = set(x.split('.')[-1] for x in names) == {'1', '2'}
 
     def load_chromosome_reads(self, chrom):
@@ -338,7 +368,6 @@ class BamReadsProcessor(object):
         DataFrame of `qname`, `pos`, `cigar` (and `qname_unpaired`, sorted by it, when paired) of one chromosome's reads;
         reads with NH > 1 are skipped when unique_alignment, unpaired reads (RNEXT '*') when paired.
         """
-        from pandas import DataFrame
         rows = []
         bam = self._open()
         for read in bam.fetch(chrom):
@@ -348,12 +377,7 @@ class BamReadsProcessor(object):
                 continue
             rows.append((read.query_name, read.reference_start, read.cigarstring))
         bam.close()
-        df = DataFrame(rows, columns=['qname', 'pos', 'cigar'])
-        df['pos'] = df['pos'].astype('int')
-        if self.paired:
-            df['qname_unpaired'] = df.qname.apply(lambda x: '.'.join(x.split('.')[:-1]))
-            df.sort_values('qname_unpaired', inplace=True)
-        return df
+        return reads_frame(rows, self.paired)
 
     @staticmethod
     def determine_full_inclusion(read_bounds, gene_exon_bounds):
@@ -396,10 +420,9 @@ class BamReadsProcessor(object):
                 logging.info('SAMPLE {0}, CHR {1} -- all coverage and read count files already present; skipping.'
                              .format(self.sample_id, chrom))
             return None
-        reads_df = self.load_chromosome_reads(chrom)
         chrom_len = int(self.header[self.header.chr == chrom].length.iloc[0])
-        csr, ol_cov_dict, read_counts = chromosome_coverage_read_counts_df(
-            reads_df, chrom_len, gene_overlap_dat, chrom_gene_df, chrom_exon_df, self.paired)
+        csr, ol_cov_dict, read_counts, n_reads = self._chromosome_coverage(chrom, chrom_len, gene_overlap_dat, chrom_gene_df,
+                                                                           chrom_exon_df)
         if n_ol > 0:
             with open(ol_cov_file, 'wb') as f:
                 pkl.dump(ol_cov_dict, f)
@@ -408,8 +431,15 @@ class BamReadsProcessor(object):
         DataFrame({'gene': list(read_counts.keys()), self.sample_id: list(read_counts.values())}).to_csv(count_file, index=False)
         if verbose:
             logging.info('SAMPLE {0}, CHR {1} -- {2} reads, {3} counted'.format(
-                self.sample_id, chrom, reads_df.shape[0], sum(read_counts.values())))
+                self.sample_id, chrom, n_reads, sum(read_counts.values())))
         return None
+
+    def _chromosome_coverage(self, chrom, chrom_len, gene_overlap_dat, chrom_gene_df, chrom_exon_df):
+        """(CSR row or None, overlap coverage, read counts, number of reads loaded) of one chromosome."""
+        reads_df = self.load_chromosome_reads(chrom)
+        csr, ol_cov_dict, read_counts = chromosome_coverage_read_counts_df(
+            reads_df, chrom_len, gene_overlap_dat, chrom_gene_df, chrom_exon_df, self.paired)
+        return csr, ol_cov_dict, read_counts, reads_df.shape[0]
 
     def coverage_read_counts(self, gene_overlap_dict, gene_df, exon_df):
         """chromosome_coverage_read_counts for every chromosome of self.chroms (reference reads.py:820-847)."""

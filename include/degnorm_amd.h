@@ -263,6 +263,52 @@ int  dn_reads_cigar_bounds(int device, int64_t n, const int64_t *pos, const int6
                            int32_t max_seg, int32_t *nseg, int64_t *bounds, int64_t *end_pos);
 const char *dn_reads_last_error(void);
 
+/* BAM records -> coverage and read counts (NativeBamReadsProcessor, degnorm_amd/bam.py) ------------------------------
+ * The host inflates a chromosome's BGZF blocks window by window; the device decodes the records and keeps the rows the
+ * reference's load_chromosome_reads keeps (reads.py): refID == tid, no NH > 1 when unique_alignment (NH of any integer type;
+ * another type is DN_E_INVALID), and when paired next_refID != -1.  Kept rows go, in file order, into a device-resident
+ * row store; the coverage stages of dn_read_coverage then read their binary CIGARs in place.
+ *   dn_bam_frame          host only: the start offsets of the complete records of buf (a walk over block_size), at most
+ *                         cap of them; *consumed = the bytes they span (the rest is a record cut by the window end).  With
+ *                         tid >= 0 every record must have refID tid and a pos no smaller than the one before it (*last_pos,
+ *                         carried between windows; start at INT32_MIN), else DN_E_INVALID (unsorted file or stale index).
+ *   dn_bam_rows_create    an empty row store on `device` for reference tid.
+ *   dn_bam_rows_append    decode the n_rec records of one window (offsets from dn_bam_frame) and append its kept rows.  An op
+ *                         code above 8 or a CIGAR moved to the CG tag in a kept row: DN_E_UNSUPPORTED.
+ *   dn_bam_rows_info      rows, CIGAR ops and name bytes stored, and the longest qname_unpaired key (nullable outputs).
+ *   dn_bam_rows_keys      every row's qname_unpaired (the name up to its last '.'; empty without one) as width bytes,
+ *                         NUL padded: n_rows x width.
+ *   dn_bam_rows_fetch     the rows (nullable outputs): pos, their ops at op_beg[r] .. op_beg[r] + n_op[r] of ops (len << 4 |
+ *                         op), their names at name_beg[r] .. name_beg[r] + name_len[r] of names (without NUL).
+ *   dn_bam_rows_coverage  dn_read_coverage on the stored rows, taken in `order` (row indices; required when paired, NULL for
+ *                         file order) with pair_id[k] the pair id of the k-th row taken.  A kept row without CIGAR ops gives
+ *                         DN_E_INVALID naming the read (the reference's regex fails on cigarstring None).
+ *   dn_bam_cigar_bounds   dn_reads_cigar_bounds on binary CIGARs: row r's ops are ops[op_off[r] .. op_off[r+1]).
+ * Errors: dn_reads_last_error(). */
+typedef struct dn_bam_rows_s *dn_bam_rows;
+int  dn_bam_frame(const uint8_t *buf, int64_t n_bytes, int32_t tid, int32_t *last_pos, int64_t *rec_off, int64_t cap,
+                  int64_t *n_rec, int64_t *consumed);
+int  dn_bam_rows_create(int device, int32_t tid, int32_t unique_alignment, int32_t paired, dn_bam_rows *out);
+void dn_bam_rows_destroy(dn_bam_rows h);
+int  dn_bam_rows_append(dn_bam_rows h, const uint8_t *window, int64_t n_bytes, const int64_t *rec_off, int64_t n_rec);
+int  dn_bam_rows_info(dn_bam_rows h, int64_t *n_rows, int64_t *n_ops, int64_t *n_name_bytes, int32_t *max_key_len);
+int  dn_bam_rows_keys(dn_bam_rows h, int32_t width, uint8_t *keys);
+int  dn_bam_rows_fetch(dn_bam_rows h, int64_t *pos, int64_t *op_beg, int32_t *n_op, uint32_t *ops, int64_t *name_beg,
+                       int32_t *name_len, uint8_t *names);
+int  dn_bam_rows_coverage(dn_bam_rows h, const int32_t *order, const int32_t *pair_id, int64_t n_pair_ids,
+                          int64_t chrom_len, int64_t keep_lo, int64_t keep_hi,
+                          int64_t n_exon, const int64_t *exon_iv,
+                          int64_t n_groups, const int64_t *group_iv, const int32_t *group_gene_off,
+                          const int32_t *ol_gene, const int64_t *ol_gene_start0, const int64_t *ol_cov_off,
+                          const int32_t *ol_exon_off, const int64_t *ol_exon_bounds,
+                          int64_t n_iso, const int64_t *iso_iv, const int32_t *iso_gene,
+                          int64_t n_iso_union, const int64_t *iso_union,
+                          int64_t n_genes, int64_t *counts, int64_t *ol_cov,
+                          int64_t csr_cap, int64_t *nnz, int32_t *csr_idx, int64_t *csr_val,
+                          int64_t *n_isolated_reads, double *device_ms);
+int  dn_bam_cigar_bounds(int device, int64_t n, const int64_t *pos, const int64_t *op_off, const uint32_t *ops,
+                         int32_t max_seg, int32_t *nseg, int64_t *bounds, int64_t *end_pos);
+
 /* Measurement hooks (bench.py) -------------------------------------------------------------------- */
 /* Device time in ms of the most recent dn_baseline_iteration's main kernel, measured with HIP events
  * on the library's own stream; kernel name via dn_main_kernel_name().                               */
