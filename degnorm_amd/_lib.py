@@ -87,6 +87,7 @@ def load(build_if_missing=False):
     lib.dn_split_length.argtypes = [vp]
     lib.dn_split_length.restype = i32
     lib.dn_class_lengths.argtypes = [vp, i32, i32, P(i32), P(i32)]
+    lib.dn_class_tier_cols.argtypes = [vp, c.c_int, P(i32), P(i32)]
     lib.dn_tiny_length.argtypes = [vp]
     lib.dn_tiny_length.restype = i32
     lib.dn_class_kernel_ms.argtypes = [vp, c.c_int]
@@ -511,6 +512,12 @@ class Device:
         """(split_len, tiny_len) of a cohort of p samples on this device, before any upload (0: the class does not exist)."""
         a, b = ctypes.c_int32(0), ctypes.c_int32(0)
         _check(self.lib.dn_class_lengths(self.h, int(p), int(downsample_rate), ctypes.byref(a), ctypes.byref(b)))
+        return int(a.value), int(b.value)
+
+    def class_tier_cols(self, cls):
+        """(register-tier columns, LDS-tier columns) of one gene of class `cls` after an upload; beyond their sum: the spill tier."""
+        a, b = ctypes.c_int32(0), ctypes.c_int32(0)
+        _check(self.lib.dn_class_tier_cols(self.h, int(cls), ctypes.byref(a), ctypes.byref(b)))
         return int(a.value), int(b.value)
 
     def tiny_length(self):

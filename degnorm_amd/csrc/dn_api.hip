@@ -598,8 +598,10 @@ static int size_class(dn_handle h, dn_handle_s::GeneClass &C, int32_t cols)
     const int units = std::max(1, C.ks->units);          // genes a workgroup carries at once: a slot and an LDS tile per unit
     int slots = (int) std::min<int64_t>(((int64_t) C.n + units - 1) / units * units, (int64_t) per_cu * h->n_cus * units);
     const int32_t S = (cols + 63) & ~63;
-    // slot: Fs, Fb (fp32, p x S) + x + lambda spill (fp64 [p][S]) + s_start, residual profile, A^T u (fp64 [S])
-    const int64_t slot_bytes = (int64_t) S * ((int64_t) p * (2 * sizeof(float) + sizeof(double)) + 3 * sizeof(double)) + (int64_t) C.ks->slot_extra_bytes;
+    // slot: Fs, Fb (fp32, p x S) + x + lambda spill (fp64, ps = p rounded up to even doubles per column: planes of double2) +
+    // s_start, residual profile, A^T u (fp64 [S])
+    const int64_t slot_bytes = (int64_t) S * ((int64_t) p * 2 * sizeof(float) + (int64_t) (p + (p & 1)) * sizeof(double) + 3 * sizeof(double)) +
+                               (int64_t) C.ks->slot_extra_bytes;
     {
         // one very long gene sizes every slot of its class: keep the scratch within a share of free HBM by
         // running fewer persistent workgroups rather than failing (the old scratch, still allocated, counts as free)
@@ -1670,6 +1672,15 @@ const char *dn_main_kernel_name(dn_handle h) { return (h && h->ks) ? h->ks->base
 double dn_class_kernel_ms(dn_handle h, int cls) { return (h && cls >= 0 && cls < dn_handle_s::NCLS) ? (double) h->data.cls[cls].last_ms : 0.0; }
 const char *dn_class_kernel_name(dn_handle h, int cls) { return (h && cls >= 0 && cls < dn_handle_s::NCLS && h->data.cls[cls].ks && h->data.cls[cls].n > 0) ? h->data.cls[cls].ks->baseline_name : ""; }
 int32_t dn_tiny_length(dn_handle h) { return h ? h->tiny_len : 0; }
+int dn_class_tier_cols(dn_handle h, int cls, int32_t *reg_cols, int32_t *lds_cols)
+{
+    if (!h || cls < 0 || cls >= dn_handle_s::NCLS || !reg_cols || !lds_cols) return fail(DN_E_INVALID, "dn_class_tier_cols: bad argument");
+    const auto &C = h->data.cls[cls];
+    const bool live = C.ks && C.n > 0;
+    *reg_cols = live ? C.ks->reg_tier_cols : 0;
+    *lds_cols = live ? C.lds_cols : 0;
+    return DN_OK;
+}
 int dn_class_lengths(dn_handle h, int32_t p, int32_t downsample_rate, int32_t *split_len, int32_t *tiny_len)
 {
     if (!h || !split_len || !tiny_len) return fail(DN_E_INVALID, "dn_class_lengths: null argument");

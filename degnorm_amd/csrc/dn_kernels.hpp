@@ -1090,10 +1090,12 @@ typedef double __attribute__((address_space(1))) *gdouble_ptr;
 // Where the data lives.  Fb: the raw fp32 counts of the n active columns (column-contiguous, p floats per column) in
 // the workgroup's scratch slot -- read-only inside the call, ~40 B per column per pass, served by the XCD's L2 /
 // Infinity Cache because the slot is touched by this CU only.  F = x * (1/s_i) is formed in registers.  The state
-// (fp64, read AND written every pass) never leaves the chip when the gene fits: column k of lane tid = k % NT sits
-//     k <  lds_cols         in the dynamic LDS tile lam[k * PS + i]                           "LDS tier"
-//     else                  in the slot's global spill array, spill_ptr(Lg, k)[i * 64]        "spill tier"
-// (a register-resident tier in front of these was measured slower and is gone: DESIGN.md, dead ends)
+// (fp64, read AND written every pass) never leaves the chip when the gene fits.  Three tiers along a gene, with
+// NR = reg_tier_cols * NT (0 outside the register-tier cohorts): column k of lane tid = k % NT sits
+//     k <  NR               in the lane's accumulation registers (rt_read / rt_write)         "register tier"
+//     k <  NR + lds_cols    in the dynamic LDS tile lam[(k - NR) * PS + i]                    "LDS tier"
+//     else                  in the slot's global spill array (spill_col_read / _write)        "spill tier"
+// All three are initialised by the cold start (state a = x) and walked by the T loop as load / update / store.
 // On return u, theta describe the last SVD; sums[] = { sum_j s_j, clamped row sums (P), row sums of Fb (P) };
 // rs[k] = squared relative residual of column k (nmf.py:280-282), sv[k] = s_k when `first`.
 // ---------------------------------------------------------------------------------------------------
@@ -1217,14 +1219,40 @@ __device__ __forceinline__ void pass_counts(const float (&x)[P], const double (&
     for (int i = 0; i < P; i++) f[i] = RAW ? (double) x[i] : (double) x[i] * inv[i];
 }
 
-// Spill-tier layout: blocks of 64 columns, inside a block the p rows of 64 doubles back to back.  A wave (64 consecutive
-// columns) reads or writes 512 contiguous bytes per row exactly as with whole rows [p][S], but the ten accesses of a
-// column differ only by the immediate offset i * 512 from ONE address -- with whole rows every row needs its own 64-bit
-// address register (20 VGPRs at p = 10), which pushed the prefetched column into AGPRs (40 extra moves per column).
+// Spill-tier layout: blocks of 64 columns; inside a block PS / 2 planes of 64 double2 (PS = p rounded up to even, as in the LDS
+// tier): plane q holds (a[2q], a[2q + 1]) of the block's column l at byte q * 1024 + l * 16.  A wave (64 consecutive columns)
+// reads or writes 1 024 contiguous bytes per plane with ONE 128-bit access, and the PS / 2 accesses of a column differ only by
+// an immediate offset from ONE address: five loads and five stores at p = 10 where rows of doubles 512 bytes apart took ten of
+// each (every instruction is an issue slot: DESIGN.md section 4).  The immediate offset of a global access is 13-bit signed
+// (-4 096 .. 4 095 bytes), so the column's address points at the MIDDLE plane: offsets -2 048 .. 2 048 at p = 10, one
+// address register up to p = 16.  With whole rows [p][S] every row would need its own 64-bit address register (20 VGPRs at
+// p = 10), which pushed the prefetched column into AGPRs (40 extra moves per column).
+typedef double dn_d2 __attribute__((ext_vector_type(2)));
+typedef dn_d2 __attribute__((address_space(1))) *gd2_ptr;
+template <int P> constexpr int spill_mid() { return (P + (P & 1)) / 4; }          // the plane a column's address points at
 template <int P>
-__device__ __forceinline__ gdouble_ptr spill_ptr(gdouble_ptr Lg, int k)
+__device__ __forceinline__ gd2_ptr spill_col(gdouble_ptr Lg, int k)
 {
-    return Lg + ((size_t) (k >> 6) * (64 * P) + (size_t) (k & 63));
+    constexpr int PS = P + (P & 1);
+    gd2_ptr col = (gd2_ptr) (Lg + ((size_t) (k >> 6) * (64 * PS) + (size_t) (k & 63) * 2)) + spill_mid<P>() * 64;
+    asm volatile("" : "+v"(col));      // opaque: the compiler would fold the bias back into the offsets (0 .. 4 096) and give the last plane its own address
+    return col;
+}
+template <int P>
+__device__ __forceinline__ void spill_col_read(gd2_ptr col, double (&a)[P])
+{
+#pragma unroll
+    for (int q = 0; q < (P + 1) / 2; q++) {
+        const dn_d2 v = col[(q - spill_mid<P>()) * 64];
+        a[2 * q] = v.x;
+        if (2 * q + 1 < P) a[2 * q + 1] = v.y;
+    }
+}
+template <int P>
+__device__ __forceinline__ void spill_col_write(gd2_ptr col, const double (&a)[P])
+{
+#pragma unroll
+    for (int q = 0; q < (P + 1) / 2; q++) col[(q - spill_mid<P>()) * 64] = dn_d2{a[2 * q], 2 * q + 1 < P ? a[2 * q + 1 < P ? 2 * q + 1 : 2 * q] : 0.0};   // odd p: the pad is zero
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1331,18 +1359,15 @@ __device__ __forceinline__ int mg_core(gF_cptr Fb, gdouble_ptr Lg, double *lam, 
                 float xr[P];
                 double aa[P];
                 load_x<P>(Fb, k, xr);
-                if (cold || t == 0) {
+                const gd2_ptr col = spill_col<P>(Lg, k);
+                if (cold) {
 #pragma unroll
                     for (int i = 0; i < P; i++) aa[i] = (double) xr[i] * invp[i];
                 } else {
-#pragma unroll
-                    for (int i = 0; i < P; i++) aa[i] = *(spill_ptr<P>(Lg, k) + i * 64);
-                }
-                if (!cold) {
+                    spill_col_read<P>(col, aa);
                     col_update_lds<P>(xr, invp, aa, uv, c);
-#pragma unroll
-                    for (int i = 0; i < P; i++) *(spill_ptr<P>(Lg, k) + i * 64) = aa[i];
                 }
+                spill_col_write<P>(col, aa);                            // as in the LDS tier: the cold pass leaves the state a = x
 #pragma unroll
                 for (int i = 0; i < P; i++) a[i] = aa[i];
             }
@@ -1731,6 +1756,15 @@ __device__ __forceinline__ void nmf_body(const float *Fb_, double *Lg_, double *
         for (int i = 0; i < PS; i++) a[i] = i < P ? f[i] : 0.0;
         lds_col_write<PS>(lam + (size_t) (k - NR) * PS, a);
     }
+    if constexpr (!ONCHIP) {
+        // the spill tier starts from the same state: 8 PS bytes stored per column and call, and the T loop reads every tier
+        // unconditionally (a select per element between the state and x in every pass cost 2 p instructions per column)
+        for (int k = kS0 + tid; k < n; k += NT) {
+            double f[P];
+            { float xf[P]; load_x<P>(Fb, k, xf); pass_counts<P, RAW>(xf, inv, f); }
+            spill_col_write<P>(spill_col<P>(Lg, k), f);
+        }
+    }
 #ifdef DN_STAMP
     stamp[3] += __builtin_amdgcn_s_memtime() - t_cold0;
 #endif
@@ -1832,45 +1866,44 @@ __device__ __forceinline__ void nmf_body(const float *Fb_, double *Lg_, double *
         };
         // spill tier: x + lambda of the columns that do not fit in LDS lives in the slot (L2 / Infinity Cache).
         // Here the loads are far away, and prefetching the next column's counts and state does pay (1.15x).
+        // The column is priced by its instruction count, so the loop carries nothing but the work: the
+        // state is read unconditionally (the cold start wrote it), five 128-bit accesses each way (spill_col), and the
+        // prefetch is unconditional with the index clamped to the lane's last column -- a per-lane branch around it merged
+        // through ~30 register copies per column.  The lane's last column, not a trip count, ends the loop: the clamp is then
+        // one v_min / v_max and the loop keeps two lane values (k, kend).
         auto spill_tier = [&]() {
             if constexpr (ONCHIP) return;
-            const int first = kS0 + tid;
-            const int cnt = first < n ? (n - first + NT - 1) / NT : 0;
+            // (the lane index is opaque here: as values fixed for the whole call the compiler hoists the lane's first and last
+            // column and the addresses derived from them out of the T loop, has no room for them next to the Gram accumulators
+            // and fetches them back from scratch in every pass)
+            int tq = tid;
+            asm volatile("" : "+v"(tq));
+            const int first = kS0 + tq;
+            if (first >= n) return;
             const int step = dir * NT;
-            int k = dir > 0 ? first : first + (cnt - 1) * NT;
+            const int last = first + (n - 1 - first) / NT * NT;        // the lane's last column
+            int k = dir > 0 ? first : last;
+            const int kend = dir > 0 ? last : first;                    // ... in walking order
             float xn[P];
             double an[P];
-            if (cnt > 0) {
-                // (the first column's index is opaque here: as a value fixed for the whole call the compiler keeps the addresses of its rows
-                // beyond the 4 095-byte reach of an immediate offset -- rows 8 and 9 at p = 10 -- in registers of their own, has no room
-                // for them next to the Gram accumulators and fetches each back from scratch in front of its load: reload, s_waitcnt
-                // vmcnt(0), load -- two memory round trips in a row at the head of every pass over a spill tier)
-                int kq = k;
-                asm volatile("" : "+v"(kq));
-                load_x<P>(Fb, kq, xn);
-                if (t > 0) {
-#pragma unroll
-                    for (int i = 0; i < P; i++) an[i] = *(spill_ptr<P>(Lg, kq) + i * 64);
-                }
-            }
+            load_x<P>(Fb, k, xn);
+            spill_col_read<P>(spill_col<P>(Lg, k), an);
+            bool more;
 #pragma clang loop unroll(disable)
-            for (int j = 0; j < cnt; j++, k += step) {
+            do {
                 double f[P], a[P];
                 pass_counts<P, RAW>(xn, inv, f);
 #pragma unroll
-                for (int i = 0; i < P; i++) a[i] = t > 0 ? an[i] : f[i];
-                if (j + 1 < cnt) {
-                    load_x<P>(Fb, k + step, xn);
-                    if (t > 0) {
-#pragma unroll
-                        for (int i = 0; i < P; i++) an[i] = *(spill_ptr<P>(Lg, k + step) + i * 64);
-                    }
-                }
+                for (int i = 0; i < P; i++) a[i] = an[i];
+                const int kn = dir > 0 ? min(k + step, kend) : max(k + step, kend);     // the last trip re-reads its own column (unused)
+                load_x<P>(Fb, kn, xn);
+                spill_col_read<P>(spill_col<P>(Lg, kn), an);
                 col_update<P>(f, a, ud, ur, c);
                 gram_add_range<P, 0, CH>(G, a);
-#pragma unroll
-                for (int i = 0; i < P; i++) *(spill_ptr<P>(Lg, k) + i * 64) = a[i];
-            }
+                spill_col_write<P>(spill_col<P>(Lg, k), a);
+                more = k != kend;
+                k += step;
+            } while (more);
         };
 #if defined(DN_STAMP) && defined(DN_EXP_TIER)           // diagnostic: only tier DN_EXP_TIER (1 register, 2 LDS, 3 spill) is timed into the pass slot
 #define DN_TIER(id, call) do { if (DN_EXP_TIER == id) { const long long tt_ = __builtin_amdgcn_s_memtime(); call; stamp[0] += __builtin_amdgcn_s_memtime() - tt_; } else { call; } } while (0)
@@ -1906,8 +1939,7 @@ __device__ __forceinline__ void nmf_body(const float *Fb_, double *Lg_, double *
 #pragma clang loop unroll(disable)
             for (int k = kS0 + tid; k < n; k += NT) {
                 double aa[P];
-#pragma unroll
-                for (int i = 0; i < P; i++) aa[i] = *(spill_ptr<P>(Lg, k) + i * 64);
+                spill_col_read<P>(spill_col<P>(Lg, k), aa);
                 gram_add_range<P, Q * CH, NQ>(Gq, aa);
             }
             block_sum_lds<NQ, P, NT, gram_t, Solver<P>::SHIFTED, Q * CH>(Gq, g_sm, solver.shift());
@@ -1979,10 +2011,7 @@ __device__ __forceinline__ void nmf_body(const float *Fb_, double *Lg_, double *
             lds_col_read<PS>(lam + (size_t) (k - NR) * PS, al);
 #pragma unroll
             for (int i = 0; i < P; i++) l[i] = al[i];
-        } else {
-#pragma unroll
-            for (int i = 0; i < P; i++) l[i] = *(spill_ptr<P>(Lg, k) + i * 64);
-        }
+        } else spill_col_read<P>(spill_col<P>(Lg, k), l);
         fin(k, f, l);
     }
     block_sum_lds<2 * P + 1, P, NT, double>(acc, sm);
@@ -2066,8 +2095,8 @@ __global__ __launch_bounds__(NT * DN_UNITS, DN_KERNEL_WAVES) void k_baseline(Ite
     char *slot = A.ws + ((size_t) blockIdx.x * DN_UNITS + DN_UNIT) * A.slot_bytes;
     float *Fs = reinterpret_cast<float *>(slot);                      // pristine compacted raw counts  [P][S]
     float *Fb = Fs + (size_t) P * S;                                  // working copy after bin drops   [S][P]
-    double *Lg = reinterpret_cast<double *>(Fb + (size_t) P * S);     // x + lambda, spill tier         [S / 64][P][64]
-    double *sv = Lg + (size_t) P * S;                                 // s_start                        [S]
+    double *Lg = reinterpret_cast<double *>(Fb + (size_t) P * S);     // x + lambda, spill tier         [S / 64][PS / 2][64] double2
+    double *sv = Lg + (size_t) (P + (P & 1)) * S;                     // s_start                        [S]
     double *rs = sv + S;                                              // residual profile               [S]
     double *rtsave = rs + 2 * (size_t) S;                             // caller's AGPRs during an nmf() call  [RT * P][NT]
     DN_RT_CLAIM();

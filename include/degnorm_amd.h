@@ -333,6 +333,10 @@ double dn_class_kernel_ms(dn_handle h, int cls);
 /* First launch to last end of the class kernels of the most recent dn_baseline_iteration (they overlap).          */
 double dn_last_span_ms(dn_handle h);
 const char *dn_class_kernel_name(dn_handle h, int cls);
+/* On-chip capacity of a class after an upload, in columns of ONE gene: those held in registers (with the counts packed next to
+ * the state; a gene with a count beyond 16 bits keeps more) and those of its LDS tile.  Active columns beyond their sum live in
+ * the scratch slot (spill tier).  0 / 0 for an empty class. */
+int  dn_class_tier_cols(dn_handle h, int cls, int32_t *reg_cols, int32_t *lds_cols);
 int  dn_synchronize(dn_handle h);
 /* Stream-copy ceiling of this device (GB/s, float4 copy of `bytes` bytes, best of `reps`).          */
 double dn_measure_copy_gbps(dn_handle h, int64_t bytes, int reps);
