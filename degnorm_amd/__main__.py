@@ -1,0 +1,175 @@
+"""
+`python -m degnorm_amd`: the `degnorm` command on the MI355X (reference: `degnorm/__main__.py`, `degnorm/utils.py:195-484`).
+
+    python -m degnorm_amd --bam-files s1.bam s2.bam -g genes.gtf -o out [--iter 5 --nmf-iter 100 -d 1 ...]
+    python -m degnorm_amd --bam-dir DIR -g genes.gtf -o out
+    python -m degnorm_amd -w PREVIOUS_OUTPUT_DIR -o out
+
+The flags and their validation follow the reference.  Not offered: --plot-genes, the HTML report, creating missing .bai
+files (a missing index is an error here; the reference shells out to samtools) and the MPI command (see
+degnorm_amd.warm_start --mpi for the sharded NMF-OA run).
+"""
+import argparse
+import logging
+import os
+import re
+import sys
+from datetime import datetime
+
+
+def argparser():
+    ap = argparse.ArgumentParser(
+        prog='python -m degnorm_amd',
+        description='DegNorm (RNA-seq degradation normalization) from .bam and .gtf files on an AMD Instinct GPU.',
+        epilog='Not available in this command: --plot-genes, the HTML summary report, creation of missing .bai index files '
+               '(index your .bam files first, e.g. with samtools index) and the MPI command.')
+    ap.add_argument('--bam-files', nargs='+', default=None,
+                    help='sorted .bam alignment files, one per sample (single-end or paired), at least two')
+    ap.add_argument('--bai-files', nargs='+', default=None,
+                    help='.bai index files in the order of --bam-files; without this flag every X.bam needs X.bai next to it')
+    ap.add_argument('--bam-dir', default=None,
+                    help='directory whose .bam files (with .bai files of the same base name) are the input; '
+                         'not together with --bam-files / --bai-files')
+    ap.add_argument('-w', '--warm-start-dir', default=None,
+                    help='output directory of an earlier run: reuse its coverage matrices, read counts and gene table and '
+                         'skip the alignment and annotation stages (.bam / .gtf arguments are then ignored)')
+    ap.add_argument('-g', '--genome-annotation', type=str, default=None,
+                    help='.gtf annotation file; required unless -w is given')
+    ap.add_argument('-o', '--output-dir', type=str, default=None,
+                    help='output directory: created when it does not exist; inside an existing directory, or without this '
+                         'flag in the working directory, a degnorm_<mmddYYYY>_<HHMMSS> directory is created')
+    ap.add_argument('-d', '--downsample-rate', type=int, default=1,
+                    help='fit every gene on each d-th base of its transcript (default 1: all bases)')
+    ap.add_argument('--nmf-iter', type=int, default=100, help='iterations of one NMF-OA factorisation (default 100)')
+    ap.add_argument('--iter', type=int, default=5, help='DegNorm iterations (default 5)')
+    ap.add_argument('--minimax-coverage', type=int, default=0,
+                    help='leave out genes whose highest coverage over all samples is below this (default 0)')
+    ap.add_argument('-s', '--skip-baseline-selection', action='store_true', help='do not run baseline selection')
+    ap.add_argument('--non-unique-alignments', action='store_true',
+                    help='keep reads flagged NH > 1 (by default only uniquely aligned reads count)')
+    ap.add_argument('-p', '--proc-per-node', type=int, default=1,
+                    help='host threads for reading .bam files and packing genes (default 1)')
+    return ap
+
+
+def bai_from_bam_file(bam_file):
+    if not bam_file.endswith('.bam'):
+        raise ValueError('{0} must have a .bam extension.'.format(bam_file))
+    return bam_file[:-3] + 'bai'
+
+
+def _default_bai_files(bam_files):
+    bai_files = []
+    for bam_file in bam_files:
+        bai_file = re.sub('.bam$', '.bai', bam_file)
+        if not os.path.isfile(bai_file):
+            raise FileNotFoundError('No .bai index file {0} for {1}: index the .bam file first (e.g. samtools index), or name '
+                                    'the index files with --bai-files.'.format(bai_from_bam_file(bam_file), bam_file))
+        bai_files.append(bai_file)
+    return bai_files
+
+
+def validate_args(args):
+    """The reference's checks on parsed arguments (utils.py:338-482); fills args.bam_files / args.bai_files."""
+    if (not args.bam_files and not args.bam_dir) and (not args.warm_start_dir):
+        raise ValueError('Must specify either --bam-files, --bam-dir, or --warm-start-dir as a data input option.')
+    n_cpu = os.cpu_count() or 1
+    if args.proc_per_node > n_cpu:
+        logging.warning('{0} is greater than the number of available cores ({1}). Reducing to {2}.'
+                        .format(args.proc_per_node, n_cpu, max(n_cpu - 1, 1)))
+        args.proc_per_node = max(n_cpu - 1, 1)
+    if (args.nmf_iter < 1) or (args.iter < 1) or (args.downsample_rate < 1):
+        raise ValueError('--nmf-iter, --iter, and --downsample-rate must all be >= 1.')
+    if args.warm_start_dir:
+        if not os.path.isdir(args.warm_start_dir):
+            raise NotADirectoryError('Cannot find --warm-start-dir {0}'.format(args.warm_start_dir))
+        if args.bam_files or args.bam_dir or args.genome_annotation:
+            logging.warning('Using warm-start directory. Supplied .bam files, .bam directory, '
+                            'and genome annotation file will be ignored.')
+        args.bam_files = args.bai_files = args.bam_dir = args.genome_annotation = None
+        return args
+    if not args.genome_annotation:
+        raise ValueError('If warm-start directory not specified, gene annotation file must be specified!')
+    if not os.path.isfile(args.genome_annotation):
+        raise FileNotFoundError('Gene annotation file {0} not found.'.format(args.genome_annotation))
+    bam_files, bai_files = [], []
+    if args.bam_dir:
+        if args.bam_files is not None or args.bai_files is not None:
+            raise ValueError('Do not specify both a --bam-dir and either --bam-files and/or --bai-files.'
+                             'Use one input selection method or the other.')
+        if not os.path.isdir(args.bam_dir):
+            raise NotADirectoryError('Cannot find --bam-dir {0}'.format(args.bam_dir))
+        bam_files = [os.path.join(args.bam_dir, f) for f in sorted(os.listdir(args.bam_dir)) if f.endswith('.bam')]
+        if len(bam_files) < 2:
+            raise ValueError('Only found {0} .bam files within directory {1}'.format(len(bam_files), args.bam_dir))
+        bai_files = _default_bai_files(bam_files)
+    else:
+        for bam_file in args.bam_files:
+            if not bam_file.endswith('.bam'):
+                raise ValueError('{0} is not a .bam file.'.format(bam_file))
+            if not os.path.isfile(bam_file):
+                raise FileNotFoundError('Count not find .bam file {0}'.format(bam_file))
+            bam_files.append(bam_file)
+        if args.bai_files is not None:
+            if len(args.bai_files) != len(bam_files):
+                raise ValueError('Number of supplied .bai files does not match number of supplied .bam files.')
+            for bai_file in args.bai_files:
+                if not bai_file.endswith('.bai'):
+                    raise ValueError('{0} is not a .bai file.'.format(bai_file))
+                if not os.path.isfile(bai_file):
+                    raise FileNotFoundError('Count not find .bai file {0}'.format(bai_file))
+                bai_files.append(bai_file)
+        else:
+            bai_files = _default_bai_files(bam_files)
+    if len(bam_files) < 2:
+        raise ValueError('Fewer than 2 .bam files were found. Not sufficiently many to run DegNorm.')
+    if len(bam_files) != len(set(bam_files)):
+        raise ValueError('Supplied .bam files are not uniquely named!')
+    args.bam_files, args.bai_files = bam_files, bai_files
+    return args
+
+
+def create_output_dir(user_input=None):
+    """
+    The output directory (created when missing), by the reference's three rules (utils.py:49-79): none given ->
+    ./degnorm_<mmddYYYY>_<HHMMSS>; an existing path -> <path>/degnorm_<mmddYYYY>_<HHMMSS>; otherwise the path itself, in the
+    working directory when it is a bare name.
+    """
+    stamp = 'degnorm_' + datetime.now().strftime('%m%d%Y_%H%M%S')
+    if not user_input:
+        output_dir = os.path.join(os.getcwd(), stamp)
+    elif os.path.exists(user_input):
+        output_dir = os.path.join(user_input, stamp)
+    else:
+        output_dir = user_input
+        if os.path.dirname(user_input) == '':
+            output_dir = os.path.join(os.getcwd(), user_input)
+    if not os.path.exists(output_dir):
+        os.makedirs(output_dir)
+    return output_dir
+
+
+def main(argv=None):
+    args = validate_args(argparser().parse_args(argv))
+    output_dir = create_output_dir(args.output_dir)
+    logging.basicConfig(level=logging.INFO, format='DegNorm (%(asctime)s) ---- %(message)s', datefmt='%m/%d/%Y %I:%M:%S',
+                        handlers=[logging.StreamHandler(), logging.FileHandler(os.path.join(output_dir, 'degnorm.log'))])
+    logging.info('DegNorm output directory -- {0}'.format(output_dir))
+    if args.warm_start_dir:
+        from .warm_start import run_from_warm_start
+        logging.info('WARM-START: loading data from previous DegNorm run contained in {0}'.format(args.warm_start_dir))
+        run_from_warm_start(args.warm_start_dir, output_dir, degnorm_iter=args.iter, nmf_iter=args.nmf_iter,
+                            downsample_rate=args.downsample_rate, skip_baseline_selection=args.skip_baseline_selection,
+                            minimax_coverage=args.minimax_coverage)
+    else:
+        from .pipeline import run_pipeline
+        run_pipeline(args.bam_files, args.bai_files, args.genome_annotation, output_dir, degnorm_iter=args.iter,
+                     nmf_iter=args.nmf_iter, downsample_rate=args.downsample_rate, minimax_coverage=args.minimax_coverage,
+                     skip_baseline_selection=args.skip_baseline_selection, unique_alignment=not args.non_unique_alignments,
+                     n_jobs=args.proc_per_node)
+    logging.info('DegNorm pipeline complete! Exiting...')
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

@@ -121,6 +121,10 @@ def load(build_if_missing=False):
     lib.dn_bam_rows_fetch.argtypes = [vp, P(i64), P(i64), P(i32), P(u32), P(i64), P(i32), P(u8)]
     lib.dn_bam_rows_coverage.argtypes = [vp, P(i32), P(i32), i64] + lib.dn_read_coverage.argtypes[8:]
     lib.dn_bam_cigar_bounds.argtypes = [c.c_int, i64, P(i64), P(i64), P(u32), i32, P(i32), P(i64), P(i64)]
+    u64 = c.c_uint64
+    lib.dn_gtf_scan.argtypes = [c.c_int, P(c.c_uint8), i64, i64, P(i64), P(i64), P(i64), P(i64), P(i32), P(u64), P(i64), P(i64),
+                                P(i64), P(i32), P(u64), P(i64), P(i32), P(dbl), P(dbl)]
+    lib.dn_gtf_last_error.restype = c.c_char_p
     lib.dn_outer_partials_device.argtypes = [vp, P(vp)]
     lib.dn_comm_unique_id.argtypes = [P(c.c_uint8)]
     lib.dn_comm_create.argtypes = [vp, P(c.c_uint8), i32, i32]

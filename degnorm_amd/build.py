@@ -4,8 +4,8 @@ In-tree build of libdegnorm_amd.so (HIP kernels + C ABI) for gfx950 with hipcc.
     python -m degnorm_amd.build [--force]
 
 One translation unit per sample count p (dn_inst.hip -DDN_P=p), the run-time-p family (dn_generic.hip, compiled three
-times: 256- and 64-thread builds on float32 counts, a 256-thread build on float64 input), the coverage-assembly and
-reads-processing units plus the C-ABI unit; objects are compiled
+times: 256- and 64-thread builds on float32 counts, a 256-thread build on float64 input), the coverage-assembly,
+reads-processing and GTF-scan units plus the C-ABI unit; objects are compiled
 in parallel and linked into degnorm_amd/libdegnorm_amd.so.  hipcc cross-compiles without a GPU.
 """
 import os
@@ -124,8 +124,13 @@ def build_library(force=False, verbose=False):
     objs.append(o_rd)
     if force or _newer(o_rd, [rd] + host_hdr):
         jobs.append([hipcc] + FLAGS + ['-c', rd, '-o', o_rd])
+    gtf = os.path.join(CSRC, 'dn_gtf.hip')              # GTF bytes -> exon table (GeneAnnotationLoader, loaders.py)
+    o_gtf = os.path.join(OBJ, 'dn_gtf.o')
+    objs.append(o_gtf)
+    if force or _newer(o_gtf, [gtf] + host_hdr):
+        jobs.append([hipcc] + FLAGS + ['-c', gtf, '-o', o_gtf])
     api = os.path.join(CSRC, 'dn_api.hip')
-    o_api = os.path.join(OBJ, 'dn_api.o')
+    o_api =os.path.join(OBJ, 'dn_api.o')
     objs.append(o_api)
     stamp = build_stamp(hipcc)
     stamp_file = os.path.join(OBJ, 'build_stamp.txt')

@@ -9,10 +9,16 @@ packed fp32 layout the NMF-OA kernels read (`dn_assemble_coverage`, csrc/dn_asse
 
     merge_chrom_coverage(data_dir, sample_ids, chrom_exon_df)   same signature and return value as the reference
     assemble_chrom_packed(...)                                  (genes, packed fp32, lengths) for Device.upload_packed
+
+Its callers in the reference's pipeline (`reads_coverage_merge.py:13-164, 375-457`) are host table work and are here too:
+merge_read_counts, merge_overlap_gene_coverage and merge_coverage, which takes the chromosomes one after another through
+the device merge_chrom_coverage.
 """
 import ctypes
 import logging
 import os
+import pickle as pkl
+from collections import OrderedDict
 
 import numpy as np
 
@@ -148,3 +154,71 @@ def merge_chrom_coverage(data_dir, sample_ids, chrom_exon_df, verbose=True, devi
     if verbose:
         logging.info('CHR {0} -- obtained {1} coverage matrices.'.format(chrom_exon_df.chr.unique()[0], len(out)))
     return out
+
+
+def merge_read_counts(data_dir, sample_ids, chroms):
+    """
+    The samples' `<data_dir>/<sample>/read_counts_<sample>_<chr>.csv` files as one DataFrame with columns `chr`, `gene`,
+    <sample ids>, chromosomes stacked in the order given, each keeping its own row index (reference
+    reads_coverage_merge.py:13-90).  FileNotFoundError for a missing file.
+    """
+    from pandas import read_csv, concat
+    chrom_dfs = []
+    for chrom in chroms:
+        chrom_counts_df = None
+        for sample_id in sample_ids:
+            counts_file = os.path.join(data_dir, sample_id, 'read_counts_{0}_{1}.csv'.format(sample_id, chrom))
+            if not os.path.isfile(counts_file):
+                raise FileNotFoundError('read counts file {0} not available!'.format(counts_file))
+            df = read_csv(counts_file)
+            chrom_counts_df = df if chrom_counts_df is None else chrom_counts_df.merge(df, on='gene')
+        chrom_counts_df['chr'] = chrom
+        chrom_dfs.append(chrom_counts_df[['chr', 'gene'] + list(sample_ids)])
+    return concat(chrom_dfs)
+
+
+def merge_overlap_gene_coverage(data_dir, sample_ids, chrom):
+    """
+    {gene: (p x L) float64} of the genes in overlap groups of one chromosome, from the samples'
+    `overlap_coverage_<sample>_<chr>.pkl` files; an empty dict as soon as one sample has no such file (reference
+    reads_coverage_merge.py:93-164).
+    """
+    gene_cov_dict = dict()
+    n_samples = len(sample_ids)
+    for i, sample_id in enumerate(sample_ids):
+        cov_file = os.path.join(data_dir, sample_id, 'overlap_coverage_{0}_{1}.pkl'.format(sample_id, chrom))
+        if not os.path.isfile(cov_file):
+            return dict()
+        with open(cov_file, 'rb') as f:
+            sample_cov_dict = pkl.load(f)
+        for gene, cov_vec in sample_cov_dict.items():
+            if i == 0:
+                gene_cov_dict[gene] = np.zeros(shape=[n_samples, len(cov_vec)], dtype=np.float64)
+            gene_cov_dict[gene][i, :] = cov_vec
+    return gene_cov_dict
+
+
+def merge_coverage(data_dir, sample_ids, exon_df, n_jobs=1, output_dir=None, verbose=True, device=None):
+    """
+    OrderedDict {gene: (p x L) float64} of every gene of exon_df, chromosome by chromosome in exon_df's order (reference
+    reads_coverage_merge.py:375-457): the genes merge_chrom_coverage slices from the chromosome coverage, then the genes of
+    overlap groups, whose matrices from the overlap files replace the sliced ones.  With output_dir each chromosome's dict
+    is pickled to `<output_dir>/<chr>/coverage_matrices_<chr>.pkl`.  n_jobs is kept for the signature: the chromosomes go
+    through the device one after another.
+    """
+    gene_cov_dict = OrderedDict()
+    for chrom in exon_df.chr.unique():
+        chrom_cov_dict = merge_chrom_coverage(data_dir, sample_ids, exon_df[exon_df.chr.isin([chrom])], verbose=verbose, device=device)
+        chrom_cov_dict = {**chrom_cov_dict, **merge_overlap_gene_coverage(data_dir, sample_ids, chrom)}
+        for gene in chrom_cov_dict:
+            gene_cov_dict[gene] = chrom_cov_dict[gene]
+        if output_dir:
+            save_dir = os.path.join(output_dir, str(chrom))
+            if not os.path.isdir(save_dir):
+                os.makedirs(save_dir)
+            chrom_cov_file = os.path.join(save_dir, 'coverage_matrices_{0}.pkl'.format(chrom))
+            if verbose:
+                logging.info('CHR {0} -- saving coverage matrices to {1}'.format(chrom, chrom_cov_file))
+            with open(chrom_cov_file, 'wb') as f:
+                pkl.dump(chrom_cov_dict, f)
+    return gene_cov_dict

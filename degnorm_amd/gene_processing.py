@@ -1,14 +1,97 @@
 """
-Gene overlap structure of one chromosome (reference: `degnorm/gene_processing.py:126-231`).
+Annotation processing (reference: `degnorm/gene_processing.py`): GeneAnnotationProcessor (:8-123) turns a .gtf file into
+the exon table the reads stage, the coverage merge and the result writer take, and get_gene_overlap_structure (:126-231)
+splits one chromosome's genes into overlap groups and isolated genes.
 
-The reference builds an HTSeq GenomicArrayOfSets of the gene spans, a dense n x n adjacency matrix and walks it with
+GeneAnnotationProcessor loads the file through the device scanner (loaders.py); the table work after it is grouped
+pandas / numpy on integer codes: no Python call per gene (the reference's gene_outline runs a lambda per gene).
+
+For the overlap structure the reference builds an HTSeq GenomicArrayOfSets of the gene spans, a dense n x n adjacency matrix and walks it with
 networkx; neither HTSeq nor `nx.from_numpy_matrix` (removed in networkx 3.4) is available on this stack.  Two genes
 overlap when their 0-based half-open spans [gene_start - 1, gene_end) intersect -- the test the reference's
 GenomicArrayOfSets query makes -- so genes whose spans merely touch (one ends at base b, the next starts at b + 1) do not
 overlap.  The groups are the connected components of that relation, which one sort-and-sweep over the spans finds in
 O(n log n).
 """
+import logging
+
 import numpy as np
+
+from .loaders import GeneAnnotationLoader
+from .utils import subset_to_chrom
+
+
+class GeneAnnotationProcessor(object):
+
+    def __init__(self, annotation_file, chroms=None, verbose=True):
+        """
+        :param annotation_file: str .gtf file
+        :param chroms: str or list of str chromosome names: subset the annotation to them
+        :param verbose: bool write progress to the logger?
+        """
+        self.filename = annotation_file
+        self.verbose = verbose
+        self.chroms = chroms
+        self.loader = None
+        if self.chroms:
+            if not isinstance(self.chroms, list):
+                self.chroms = [self.chroms]
+
+    def load(self):
+        """The exon rows of the file (GeneAnnotationLoader.get_data), subset to self.chroms when given."""
+        self.loader = GeneAnnotationLoader(self.filename)
+        return self._subset(self.loader.get_data())
+
+    def _subset(self, exon_df):
+        if self.chroms:
+            if self.verbose:
+                logging.info('Subsetting exon data to {0} chromosomes:\n'
+                             '\t{1}'.format(len(self.chroms), ', '.join(self.chroms)))
+            exon_df = subset_to_chrom(exon_df, chrom=self.chroms)
+        if self.verbose:
+            logging.info('Successfully loaded exon data -- shape: {0}'.format(exon_df.shape))
+        if exon_df.empty:
+            raise ValueError('Exon DataFrame is empty!')
+        return exon_df
+
+    @staticmethod
+    def remove_multichrom_genes(df):
+        """df without the genes that show up on more than one chromosome."""
+        per_gene = df.groupby('gene').chr.nunique()
+        return df[~df.gene.isin(per_gene[per_gene > 1].index.tolist())]
+
+    @staticmethod
+    def gene_outline(df):
+        """
+        min(start) and max(end) of every (chr, gene) of an exon table: DataFrame of `chr`, `gene`, `gene_start`, `gene_end`,
+        sorted by chr, then gene (as the reference's groupby).
+        """
+        grp = df.groupby(['chr', 'gene'])
+        return grp.agg(gene_start=('start', 'min'), gene_end=('end', 'max')).reset_index()
+
+    def process(self, exon_df):
+        """The steps of run() after load(): multi-chromosome genes out, gene outlines joined on, duplicates dropped."""
+        exon_df = self.remove_multichrom_genes(exon_df).drop_duplicates()
+        gene_df = self.gene_outline(exon_df)
+        exon_df = exon_df.merge(gene_df, on=['chr', 'gene']).drop_duplicates()
+        return exon_df
+
+    def run(self):
+        """
+        Load the annotation file, remove the genes that occur on several chromosomes, outline every gene and drop
+        duplicates (reference gene_processing.py:89-123).
+
+        :return: DataFrame with `chr`, `start`, `end`, `gene`, `gene_start`, `gene_end`: the exons, in file order.
+        """
+        if self.verbose:
+            logging.info('Loading genome annotation file {0}...'.format(self.filename))
+        exon_df = self.load()
+        if self.verbose:
+            logging.info('Begin genome annotation file processing.')
+        exon_df = self.process(exon_df)
+        if self.verbose:
+            logging.info('Processing successful. Final shape -- {0}'.format(exon_df.shape))
+        return exon_df
 
 
 def get_gene_overlap_structure(gene_df):

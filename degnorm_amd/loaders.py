@@ -1,0 +1,201 @@
+"""
+GTF annotation loader on the device (reference: `degnorm/loaders.py:73-168`, GeneAnnotationLoader).
+
+The reference reads the nine columns with pandas, lower-cases the feature column and runs a regex per exon row.  Here the
+file's bytes go to the GPU window by window (about window_bytes each, cut at line ends) and `dn_gtf_scan`
+(csrc/dn_gtf.hip) returns the exon lines in file order: start, end and the byte spans of the chromosome and gene names
+with a hash of each.  The host turns every distinct name into one Python string (names are grouped by hash and length and
+then compared byte for byte, so two names that share a hash stay apart) and drops duplicate rows on integer codes.
+
+The gene name of a line follows the reference's `_attribute_to_gene` (loaders.py:102-112): the attribute field is split
+at `;`, every piece stripped; the first piece that begins with `gene_name` gives the name, and when there is none or its
+value is empty the first piece that begins with `gene_id` does; the value is the rest of the piece without blanks and `"`
+at either end.  Narrowings: a blank is the ASCII space; the tag is cut off once, at the front of the piece (the reference
+removes every occurrence of the tag's text from the piece); start and end are 1 to 18 decimal digits and nothing else.
+
+Two deliberate differences from the reference: lines that start with `#` and empty lines are skipped (the reference
+raises on them, so it refuses every Ensembl or GENCODE download), and `chr` is always the file's text (pandas' type
+inference turns a column of `01` into 1).  There is no CPU fallback: without a device `get_data` raises DegnormAmdError.
+"""
+import ctypes
+import os
+import time
+
+import numpy as np
+
+from . import _lib
+
+WINDOW_BYTES = 256 << 20            # as NativeBamReadsProcessor (bam.py)
+_COMPARE_BYTES = 32 << 20           # bytes held at a time when the names of a hash group are compared
+_KINDS = {1: 'must have the 9 mandatory .gtf columns.\nRead more at https://useast.ensembl.org/info/website/upload/gff.html',
+          2: 'is an exon record without a usable gene_name or gene_id identifier tag.',
+          3: 'is an exon record whose start or end is not an integer.'}
+
+
+class Loader(object):
+
+    def __init__(self, filetypes):
+        """File loader for files that end with one of `filetypes` (a str or a list of str)."""
+        self.filetypes = filetypes if isinstance(filetypes, list) else [filetypes]
+        self.filename = None
+
+    def get_file(self, to_load):
+        if not isinstance(to_load, str):
+            raise ValueError('{0} data type not understood'.format(to_load))
+        if not os.path.exists(to_load):
+            raise FileNotFoundError('file {0} not found'.format(to_load))
+        if not any(to_load.endswith(ft) for ft in self.filetypes):
+            raise ValueError('file {0} does not end with {1}'.format(to_load, ', '.join(self.filetypes)))
+        self.filename = to_load
+
+    def get_data(self):
+        raise NotImplementedError('get_data not yet implemented for {0}'.format(self.__class__.__name__))
+
+
+def scan_window(buf, device=None):
+    """
+    dn_gtf_scan on the bytes of one window: (number of lines, dict of the kept lines' columns -- `line` 1-based within the
+    window, `chr_beg`, `chr_len`, `chr_hash`, `start`, `end`, `gene_beg`, `gene_len`, `gene_hash` -- (error line, error kind)
+    or None, copy-in ms, device ms).
+    """
+    lib = _lib.load()
+    a = np.frombuffer(buf, dtype=np.uint8)
+    cap = a.size // 20 + 1
+    i64, i32, u64 = ctypes.c_int64, ctypes.c_int32, ctypes.c_uint64
+    cols = {k: np.empty(cap, dtype=t) for k, t in (('line', np.int64), ('chr_beg', np.int64), ('chr_len', np.int32),
+                                                  ('chr_hash', np.uint64), ('start', np.int64), ('end', np.int64),
+                                                  ('gene_beg', np.int64), ('gene_len', np.int32), ('gene_hash', np.uint64))}
+    n_lines, n_rows, err_line, err_kind = i64(0), i64(0), i64(0), i32(0)
+    copy_ms, dev_ms = ctypes.c_double(0.0), ctypes.c_double(0.0)
+    dev = int(os.environ.get('LOCAL_RANK', 0)) if device is None else int(device)
+    rc = lib.dn_gtf_scan(dev, _lib._p(a, ctypes.c_uint8), a.size, cap, ctypes.byref(n_lines), ctypes.byref(n_rows),
+                         _lib._p(cols['line'], i64), _lib._p(cols['chr_beg'], i64), _lib._p(cols['chr_len'], i32),
+                         _lib._p(cols['chr_hash'], u64), _lib._p(cols['start'], i64), _lib._p(cols['end'], i64),
+                         _lib._p(cols['gene_beg'], i64), _lib._p(cols['gene_len'], i32), _lib._p(cols['gene_hash'], u64),
+                         ctypes.byref(err_line), ctypes.byref(err_kind), ctypes.byref(copy_ms), ctypes.byref(dev_ms))
+    if rc != _lib.DN_OK:
+        msg = lib.dn_gtf_last_error().decode('utf-8', 'replace')
+        if rc == _lib.DN_E_INVALID:
+            raise ValueError(msg)
+        raise _lib.DegnormAmdError('dn_gtf_scan failed ({0}): {1}'.format(rc, msg))
+    n = int(n_rows.value)
+    err = (int(err_line.value), int(err_kind.value)) if err_kind.value else None
+    return int(n_lines.value), {k: v[:n] for k, v in cols.items()}, err, float(copy_ms.value), float(dev_ms.value)
+
+
+def _same_bytes(a, beg, other, length):
+    """True when bytes a[beg[r] : beg[r] + length[r]] equal a[other[r] : other[r] + length[r]] for every row r."""
+    width = int(length.max()) if length.size else 0
+    if width == 0:
+        return True
+    step = max(_COMPARE_BYTES // width, 1)
+    col = np.arange(width, dtype=np.int64)
+    for lo in range(0, length.size, step):
+        n = length[lo:lo + step, None]
+        inside = col[None, :] < n
+        x = a[np.where(inside, beg[lo:lo + step, None] + col, 0)]
+        y = a[np.where(inside, other[lo:lo + step, None] + col, 0)]
+        if not np.array_equal(x[inside], y[inside]):
+            return False
+    return True
+
+
+def intern_spans(a, beg, length, hashes, table):
+    """
+    Codes of the byte spans a[beg : beg + length] in `table` ({bytes: code}, extended here): one bytes object per distinct
+    span of the window.  Spans are grouped by hash; a group whose members differ (two names, one hash) sends the whole
+    window through the dict one span at a time.
+    """
+    if beg.size == 0:
+        return np.zeros(0, dtype=np.int64)
+    _, first, inv = np.unique(hashes, return_index=True, return_inverse=True)
+    inv = inv.reshape(-1)
+    rep = first[inv]
+    if np.array_equal(length, length[rep]) and _same_bytes(a, beg, beg[rep], length):
+        codes = np.empty(first.size, dtype=np.int64)
+        for k in np.argsort(first).tolist():             # new names get their codes in order of first appearance
+            r = int(first[k])
+            codes[k] =table.setdefault(a[beg[r]:beg[r] + length[r]].tobytes(), len(table))
+        return codes[inv]
+    return np.array([table.setdefault(a[b:b + n].tobytes(), len(table)) for b, n in zip(beg.tolist(), length.tolist())],
+                    dtype=np.int64)
+
+
+def iter_windows(filename, window_bytes):
+    """The file's bytes in pieces of about window_bytes that end at a line end (the last one at the end of the file)."""
+    carry = b''
+    with open(filename, 'rb') as f:
+        while True:
+            more = f.read(window_bytes)
+            if not more:
+                break
+            cut = more.rfind(b'\n') + 1
+            if cut == 0:                                  # a line longer than the window: keep reading
+                carry += more
+                continue
+            head = more if cut == len(more) else more[:cut]
+            yield carry + head if carry else head
+            carry = more[cut:]
+    if carry:
+        yield carry
+
+
+class GeneAnnotationLoader(Loader):
+
+    def __init__(self, to_load, window_bytes=None, device=None):
+        """
+        .gtf file loader on the device.
+
+        :param to_load: str the realpath to a .gtf file.
+        :param window_bytes: the file is scanned in windows of about this many bytes, cut at line ends (default WINDOW_BYTES).
+        :param device: HIP device index (default: LOCAL_RANK or 0).
+        """
+        Loader.__init__(self, '.gtf')
+        self.get_file(to_load)
+        self.window_bytes = max(int(WINDOW_BYTES if window_bytes is None else window_bytes), 1)
+        self.device = device
+        self.timing = {}
+
+    def exon_codes(self):
+        """
+        The exon lines of the file in file order, names as codes: (chr code, start, end, gene code -- int64 arrays --,
+        chromosome names, gene names: lists of str indexed by code, in order of first appearance).
+        """
+        chr_table, gene_table = {}, {}
+        parts = []
+        line_base = 0
+        t = self.timing = {'read_s': 0.0, 'copy_ms': 0.0, 'device_ms': 0.0, 'bytes': 0}
+        t0 = time.perf_counter()
+        for win in iter_windows(self.filename, self.window_bytes):
+            t['read_s'] += time.perf_counter() - t0
+            n_lines, cols, err, copy_ms, dev_ms = scan_window(win, self.device)
+            t['copy_ms'] += copy_ms
+            t['device_ms'] += dev_ms
+            t['bytes'] += len(win)
+            if err is not None:
+                raise ValueError('File {0}, line {1} {2}'.format(self.filename, line_base + err[0], _KINDS[err[1]]))
+            a = np.frombuffer(win, dtype=np.uint8)
+            parts.append((intern_spans(a, cols['chr_beg'], cols['chr_len'].astype(np.int64), cols['chr_hash'], chr_table),
+                          cols['start'], cols['end'],
+                          intern_spans(a, cols['gene_beg'], cols['gene_len'].astype(np.int64), cols['gene_hash'], gene_table)))
+            line_base += n_lines
+            t0 = time.perf_counter()
+        t['read_s'] += time.perf_counter() - t0
+        t['lines'] = line_base
+        cat = [np.concatenate([p[k] for p in parts]) if parts else np.zeros(0, dtype=np.int64) for k in range(4)]
+        names = [[b.decode('utf-8', 'replace') for b in tab] for tab in (chr_table, gene_table)]     # dicts keep insertion order
+        return cat[0], cat[1], cat[2], cat[3], names[0], names[1]
+
+    def get_data(self):
+        """
+        The reference's exon table (loaders.py:114-168): columns `chr` (str), `start` (int64), `end` (int64), `gene` (str),
+        one row per exon line of the file, duplicates of the four columns dropped (the first one stays), RangeIndex.
+        Malformed input raises ValueError naming the file, the line and what is wrong with it.
+        """
+        from pandas import DataFrame
+        chr_code, start, end, gene_code, chr_names, gene_names = self.exon_codes()
+        codes = DataFrame({'chr': chr_code, 'start': start, 'end': end, 'gene': gene_code})
+        keep = ~codes.duplicated().values
+        return DataFrame({'chr': np.array(chr_names, dtype=object)[chr_code[keep]] if chr_names else np.zeros(0, dtype=object),
+                          'start': start[keep].astype(np.int64), 'end': end[keep].astype(np.int64),
+                          'gene': np.array(gene_names, dtype=object)[gene_code[keep]] if gene_names else np.zeros(0, dtype=object)})

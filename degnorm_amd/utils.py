@@ -2,6 +2,21 @@
 import numpy as np
 
 
+def subset_to_chrom(df, chrom, reindex=False):
+    """
+    Rows of a DataFrame with a `chr` column that belong to chromosome(s) `chrom` (a str or a list), as the reference's
+    subset_to_chrom (degnorm/utils.py:82-103); the index is reset when `reindex`.  ValueError when nothing is left.
+    """
+    if not isinstance(chrom, list):
+        chrom = [chrom]
+    sub_df = df[df['chr'].isin(chrom)]
+    if reindex:
+        sub_df = sub_df.reset_index(drop=True)
+    if sub_df.empty:
+        raise ValueError('Chromosome subsetting resulted in an empty DataFrame!')
+    return sub_df
+
+
 def split_into_chunks(x, n):
     """
     Contiguous near-equal chunks with the reference's exact semantics (degnorm/utils.py:176-192):

@@ -309,6 +309,32 @@ int  dn_bam_rows_coverage(dn_bam_rows h, const int32_t *order, const int32_t *pa
 int  dn_bam_cigar_bounds(int device, int64_t n, const int64_t *pos, const int64_t *op_off, const uint32_t *ops,
                          int32_t max_seg, int32_t *nseg, int64_t *bounds, int64_t *end_pos);
 
+/* GTF annotation scan (GeneAnnotationLoader, degnorm_amd/loaders.py) --------------------------------------------------
+ * Replaces the reference's read_csv of the nine columns, its lower-case `apply` on the feature column and its regex
+ * `apply` per exon row (loaders.py:128-152, _attribute_to_gene :102-112).  buf holds the n_bytes raw bytes of a GTF file,
+ * or of a window of it that ends at a line end.  A line ends at '\n' (a '\r' before it belongs to the line end) or at the
+ * end of the bytes.  Empty lines and lines whose first byte is '#' are skipped.  Every other line must hold eight tabs
+ * (DN_GTF_E_FIELDS); it is kept when its third field is `exon` in any letter case.  A kept line's fourth and fifth fields
+ * must be 1 .. 18 decimal digits (DN_GTF_E_INTEGER), and its ninth field (up to a further tab or the line end) must name a
+ * gene (DN_GTF_E_GENE): of the pieces between ';', blanks stripped, the first that begins with `gene_name` gives the name
+ * -- the rest of the piece without blanks and '"' at either end -- and when there is none, or its value is empty, the
+ * first piece that begins with `gene_id` does.
+ * Outputs, host arrays of row_cap entries (n_bytes / 20 + 1 always suffices: a kept line is longer than 20 bytes):
+ * the kept lines in file order as line (1-based, within buf), the byte span of the chromosome name (chr_beg, chr_len)
+ * and of the gene name (gene_beg, gene_len) with the 64-bit FNV-1a hash of each span, start and end; *n_rows of them;
+ * *n_lines, the number of lines of buf.  On malformed input the call still returns DN_OK: *err_kind is the DN_GTF_E_*
+ * of the first offending line, *err_line its number, and no rows come back.  copy_ms / device_ms (nullable): the copy of
+ * buf to the device and the kernels, by HIP events.  Results are bit-identical from run to run.  Text of the last
+ * error: dn_gtf_last_error(). */
+#define DN_GTF_E_FIELDS   1   /* fewer than nine tab-separated fields                                                   */
+#define DN_GTF_E_GENE     2   /* an exon line without a usable gene_name / gene_id                                      */
+#define DN_GTF_E_INTEGER  3   /* an exon line whose start or end is not a decimal integer                               */
+int  dn_gtf_scan(int device, const uint8_t *buf, int64_t n_bytes, int64_t row_cap, int64_t *n_lines, int64_t *n_rows,
+                 int64_t *line, int64_t *chr_beg, int32_t *chr_len, uint64_t *chr_hash, int64_t *start, int64_t *end,
+                 int64_t *gene_beg, int32_t *gene_len, uint64_t *gene_hash, int64_t *err_line, int32_t *err_kind,
+                 double *copy_ms, double *device_ms);
+const char *dn_gtf_last_error(void);
+
 /* Measurement hooks (bench.py) -------------------------------------------------------------------- */
 /* Device time in ms of the most recent dn_baseline_iteration's main kernel, measured with HIP events
  * on the library's own stream; kernel name via dn_main_kernel_name().                               */
