@@ -49,6 +49,8 @@ def argparser():
                     help='keep reads flagged NH > 1 (by default only uniquely aligned reads count)')
     ap.add_argument('-p', '--proc-per-node', type=int, default=1,
                     help='host threads for reading .bam files and packing genes (default 1)')
+    ap.add_argument('--device-inflate', action='store_true',
+                    help='inflate the BGZF blocks of the .bam files on the GPU instead of with zlib on the host')
     return ap
 
 
@@ -166,7 +168,7 @@ def main(argv=None):
         run_pipeline(args.bam_files, args.bai_files, args.genome_annotation, output_dir, degnorm_iter=args.iter,
                      nmf_iter=args.nmf_iter, downsample_rate=args.downsample_rate, minimax_coverage=args.minimax_coverage,
                      skip_baseline_selection=args.skip_baseline_selection, unique_alignment=not args.non_unique_alignments,
-                     n_jobs=args.proc_per_node)
+                     n_jobs=args.proc_per_node, inflate='device' if args.device_inflate else 'host')
     logging.info('DegNorm pipeline complete! Exiting...')
     return 0
 

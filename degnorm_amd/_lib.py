@@ -116,6 +116,11 @@ def load(build_if_missing=False):
     lib.dn_bam_rows_destroy.argtypes = [vp]
     lib.dn_bam_rows_destroy.restype = None
     lib.dn_bam_rows_append.argtypes = [vp, P(u8), i64, P(i64), i64]
+    lib.dn_bam_rows_append_resident.argtypes = [vp, P(i64), i64]
+    lib.dn_bam_rows_inflate.argtypes = [vp, P(u8), i64, P(u8), i64, i64, P(i64), P(i32), P(i32), i32, i32, P(P(u8)), P(i64),
+                                        P(i32), P(dbl)]
+    lib.dn_bgzf_inflate_host.argtypes = [P(u8), i64, i64, P(i64), P(i32), P(i64), P(u8), P(i32)]
+    lib.dn_bgzf_inflate.argtypes = [c.c_int, P(u8), i64, i64, P(i64), P(i32), P(i64), P(u8), P(i32), P(dbl), P(dbl)]
     lib.dn_bam_rows_info.argtypes = [vp, P(i64), P(i64), P(i64), P(i32)]
     lib.dn_bam_rows_keys.argtypes = [vp, i32, P(u8)]
     lib.dn_bam_rows_fetch.argtypes = [vp, P(i64), P(i64), P(i32), P(u32), P(i64), P(i32), P(u8)]

@@ -5,6 +5,9 @@ Native BAM input for the reads stage: NativeBamReadsProcessor opens sorted, inde
               requested chromosome, window by window (about window_bytes each; a record cut by a window end is carried to
               the next); the header's reference list; the .bai pseudo-bin of the chromosome; record framing in the
               library's host C++ (dn_bam_frame), which also checks that the range is sorted and belongs to the chromosome
+              With inflate='device' the blocks of a window go to the device as they are in the file and the library's own
+              DEFLATE decoder (csrc/dn_inflate.hip, one block per wavefront) builds the window where the decode kernels
+              read it; the host frames a copy of it and uploads only the record offsets
     device    (csrc/dn_reads.hip) the records of each window are decoded, filtered by the reference's rules (reads.py
               load_chromosome_reads) and appended to a device-resident row store; the coverage stages read their binary
               CIGARs in place
@@ -97,6 +100,60 @@ def inflate_block(blk):
     if len(data) != isize:
         raise ValueError('BGZF block inflates to {0} bytes, ISIZE says {1}'.format(len(data), isize))
     return data
+
+
+INFLATE_ERRORS = {1: 'bad block type or header', 2: 'bad code lengths', 3: 'invalid code', 4: 'distance too far back',
+                  5: 'input ended early', 6: 'inflated size differs from ISIZE', 7: 'bytes after the final deflate block'}
+
+
+def _block_layout(blocks):
+    """Blocks joined into one uint8 array, and per block the offset and length of its deflate payload and its ISIZE."""
+    n = len(blocks)
+    pay_off, pay_len, isize = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int64)
+    p = 0
+    for k, blk in enumerate(blocks):
+        if len(blk) < 20:
+            raise ValueError('BGZF block {0} is cut short ({1} bytes)'.format(k, len(blk)))
+        head = 12 + struct.unpack_from('<H', blk, 10)[0]
+        if head + 8 > len(blk):
+            raise ValueError('BGZF block {0} is cut short ({1} bytes)'.format(k, len(blk)))
+        pay_off[k], pay_len[k], isize[k] = p + head, len(blk) - 8 - head, struct.unpack_from('<I', blk, len(blk) - 4)[0]
+        p += len(blk)
+    comp = np.frombuffer(b''.join(blocks), dtype=np.uint8) if p else np.zeros(1, np.uint8)
+    return comp, p, pay_off, pay_len, isize
+
+
+def inflate_blocks(blocks, device=None):
+    """
+    The data of whole BGZF blocks (as iter_blocks yields them), inflated by the library's own DEFLATE decoder: on the host
+    (device=None; no GPU needed) or on GPU `device`, one block per wavefront.  ValueError names the first block that does
+    not decode.
+    """
+    blocks = list(blocks)
+    n = len(blocks)
+    comp, n_comp, pay_off, pay_len, isize = _block_layout(blocks)
+    if n and int(isize[:n].max()) > 65536:
+        raise ValueError('BGZF block {0} claims an inflated size of {1} bytes'.format(int(isize[:n].argmax()), int(isize[:n].max())))
+    out_off = np.zeros(n + 1, np.int64)
+    np.cumsum(isize[:n], out=out_off[1:])
+    out = np.zeros(int(out_off[-1]) + 1, np.uint8)
+    status = np.zeros(max(n, 1), np.int32)
+    i64, i32, u8 = ctypes.c_int64, ctypes.c_int32, ctypes.c_uint8
+    args = (_ptr(comp, u8), n_comp, n, _ptr(pay_off, i64), _ptr(pay_len, i32), _ptr(out_off, i64), _ptr(out, u8), _ptr(status, i32))
+    if device is None:
+        _check(_lib.load().dn_bgzf_inflate_host(*args), 'dn_bgzf_inflate_host')
+    else:
+        _check(_lib.load().dn_bgzf_inflate(int(device), *(args + (None, None))), 'dn_bgzf_inflate')
+    _raise_status(status[:n], lambda k: 'BGZF block {0}'.format(k))
+    data = out.tobytes()
+    return [data[out_off[k]:out_off[k + 1]] for k in range(n)]
+
+
+def _raise_status(status, where):
+    bad = np.flatnonzero(status)
+    if len(bad):
+        k = int(bad[0])
+        raise ValueError('{0} does not inflate: {1}'.format(where(k), INFLATE_ERRORS.get(int(status[k]), 'error {0}'.format(int(status[k])))))
 
 
 # --- header and index ----------------------------------------------------------------------------------------------------
@@ -232,6 +289,29 @@ class DeviceRows(object):
         _check(self.lib.dn_bam_rows_append(self.h, _ptr(a, ctypes.c_uint8), len(buf), _ptr(rec_off, ctypes.c_int64),
                                            len(rec_off)), 'dn_bam_rows_append')
 
+    def inflate(self, carry, blocks, head_skip, tail_keep):
+        """
+        dn_bam_rows_inflate: the next window (carry + the inflated blocks, trimmed) built on the device.  Returns a view of
+        the library's host copy of it (valid until the next call), the status of every block and the kernel's ms.
+        """
+        comp, n_comp, pay_off, pay_len, isize = _block_layout(blocks)
+        isize32 = np.where(isize > 2 ** 31 - 1, -1, isize).astype(np.int32)      # the library refuses a negative size
+        status = np.zeros(max(len(blocks), 1), np.int32)
+        c = np.frombuffer(carry, dtype=np.uint8) if len(carry) else np.zeros(1, np.uint8)
+        view, n_bytes, ms = ctypes.POINTER(ctypes.c_uint8)(), ctypes.c_int64(0), ctypes.c_double(0.0)
+        i64, i32, u8 = ctypes.c_int64, ctypes.c_int32, ctypes.c_uint8
+        _check(self.lib.dn_bam_rows_inflate(self.h, _ptr(c, u8), len(carry), _ptr(comp, u8), n_comp, len(blocks), _ptr(pay_off, i64),
+                                            _ptr(pay_len, i32), _ptr(isize32, i32), int(head_skip), int(tail_keep),
+                                            ctypes.byref(view), ctypes.byref(n_bytes), _ptr(status, i32), ctypes.byref(ms)),
+               'dn_bam_rows_inflate')
+        data = np.ctypeslib.as_array(view, shape=(n_bytes.value,)) if n_bytes.value else np.zeros(0, np.uint8)
+        return data, status[:len(blocks)], float(ms.value)
+
+    def append_resident(self, rec_off):
+        if len(rec_off) == 0:
+            return
+        _check(self.lib.dn_bam_rows_append_resident(self.h, _ptr(rec_off, ctypes.c_int64), len(rec_off)), 'dn_bam_rows_append_resident')
+
     def info(self):
         n, n_ops, n_names, mk = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32()
         _check(self.lib.dn_bam_rows_info(self.h, ctypes.byref(n), ctypes.byref(n_ops), ctypes.byref(n_names), ctypes.byref(mk)),
@@ -311,11 +391,16 @@ def cigar_strings(op_beg, n_op, ops):
 class NativeBamReadsProcessor(BamReadsProcessor):
 
     def __init__(self, bam_file, index_file, chroms=None, n_jobs=1, output_dir=None, unique_alignment=True, verbose=True,
-                 window_bytes=256 << 20):
+                 window_bytes=256 << 20, inflate='host'):
         """
         BamReadsProcessor on the library's own BAM reader: no pysam.  n_jobs sizes the thread pool that inflates BGZF
         blocks; window_bytes bounds the inflated bytes held (on the host and on the device) besides the chromosome's rows.
+        inflate='host' inflates with zlib in that pool; inflate='device' hands the compressed blocks to the library's DEFLATE
+        kernel (device_rows, and with it coverage and load_chromosome_reads; the header and the strand check stay on zlib).
         """
+        if inflate not in ('host', 'device'):
+            raise ValueError("inflate must be 'host' or 'device', not {0!r}".format(inflate))
+        self.inflate = inflate
         self.window_bytes = max(int(window_bytes), 1)
         self.timing = {}
         super(NativeBamReadsProcessor, self).__init__(bam_file, index_file, chroms=chroms, n_jobs=n_jobs, output_dir=output_dir,
@@ -340,11 +425,8 @@ class NativeBamReadsProcessor(BamReadsProcessor):
         self._load()
         return {name: length for name, length in self._refs}
 
-    def windows(self, chrom, window_bytes=None):
-        """
-        Inflated bytes of the blocks that hold chrom's records, about window_bytes at a time; a record may be cut at the
-        end of one window and continue in the next.  Adds host inflate seconds to self.timing['inflate_s'].
-        """
+    def _batches(self, chrom, window_bytes=None):
+        """((file offset, block) of about window_bytes of inflated data, cbeg, ubeg, cend, uend) over chrom's index range."""
         self._load()
         rng = reference_range(self._index[self._tid[chrom]])
         if rng is None:
@@ -352,18 +434,26 @@ class NativeBamReadsProcessor(BamReadsProcessor):
         window_bytes = window_bytes or self.window_bytes
         vbeg, vend = rng
         cbeg, ubeg, cend, uend = vbeg >> 16, vbeg & 0xffff, vend >> 16, vend & 0xffff
+        batch, size = [], 0
+        for off, blk in iter_blocks(self.filename, cbeg):
+            if off > cend or (off == cend and uend == 0):
+                break
+            batch.append((off, blk))
+            size += struct.unpack_from('<I', blk, len(blk) - 4)[0]
+            if size >= window_bytes:
+                yield batch, cbeg, ubeg, cend, uend
+                batch, size = [], 0
+        if batch:
+            yield batch, cbeg, ubeg, cend, uend
+
+    def windows(self, chrom, window_bytes=None):
+        """
+        Inflated bytes of the blocks that hold chrom's records, about window_bytes at a time; a record may be cut at the
+        end of one window and continue in the next.  Adds host inflate seconds to self.timing['inflate_s'].
+        """
         pool = ThreadPoolExecutor(max_workers=int(self.n_jobs)) if int(self.n_jobs) > 1 else None
         try:
-            batch, size = [], 0
-            for off, blk in iter_blocks(self.filename, cbeg):
-                if off > cend or (off == cend and uend == 0):
-                    break
-                batch.append((off, blk))
-                size += struct.unpack_from('<I', blk, len(blk) - 4)[0]
-                if size >= window_bytes:
-                    yield self._inflate(batch, pool, cbeg, ubeg, cend, uend)
-                    batch, size = [], 0
-            if batch:
+            for batch, cbeg, ubeg, cend, uend in self._batches(chrom, window_bytes):
                 yield self._inflate(batch, pool, cbeg, ubeg, cend, uend)
         finally:
             if pool is not None:
@@ -403,6 +493,8 @@ class NativeBamReadsProcessor(BamReadsProcessor):
         carry, last = b'', _INT32_MIN
         t = self.timing
         try:
+            if self.inflate == 'device':
+                return self._device_windows(chrom, rows)
             for win in self.windows(chrom):
                 data = carry + win if carry else win
                 t0 = time.perf_counter()
@@ -418,6 +510,29 @@ class NativeBamReadsProcessor(BamReadsProcessor):
         except Exception:
             rows.close()
             raise
+        return rows
+
+    def _device_windows(self, chrom, rows):
+        """device_rows with inflate='device': every window is inflated into the row store and decoded where it lies."""
+        carry, last = b'', _INT32_MIN
+        t = self.timing
+        for batch, cbeg, ubeg, cend, uend in self._batches(chrom):
+            t0 = time.perf_counter()
+            data, status, ms = rows.inflate(carry, [b for _, b in batch], ubeg if batch[0][0] == cbeg else 0,
+                                            uend if batch[-1][0] == cend else -1)
+            t1 = time.perf_counter()
+            _raise_status(status, lambda k: '{0}: the BGZF block at byte {1}'.format(self.filename, batch[k][0]))
+            off, used, last = frame_records(data, self._tid[chrom], last)
+            t2 = time.perf_counter()
+            rows.append_resident(off)
+            t3 = time.perf_counter()
+            t['inflate_s'] = t.get('inflate_s', 0.0) + t1 - t0
+            t['inflate_device_ms'] = t.get('inflate_device_ms', 0.0) + ms
+            t['frame_s'] = t.get('frame_s', 0.0) + t2 - t1
+            t['decode_s'] = t.get('decode_s', 0.0) + t3 - t2
+            carry = data[used:].tobytes()
+        if carry:
+            raise ValueError('{0}: a record of {1} is cut short at the end of its index range'.format(self.filename, chrom))
         return rows
 
     def load_chromosome_reads(self, chrom):

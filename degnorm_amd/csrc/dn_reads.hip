@@ -25,6 +25,7 @@
 #include <vector>
 #include "../../include/degnorm_amd.h"
 #include "dn_host.hpp"
+#include "dn_inflate.hpp"
 
 namespace {
 
@@ -342,6 +343,7 @@ template <class T> hipError_t alloc_padded(dn::DeviceBuffer<T> &b, size_t n) { r
     } while (0)
 
 extern "C" const char *dn_reads_last_error(void) { return g_reads_err.c_str(); }
+void dn::set_reads_error(const std::string &msg) { g_reads_err = msg; }
 
 namespace {
 
@@ -876,6 +878,14 @@ struct dn_bam_rows_s {
     dn::DeviceBuffer<unsigned long long> err;
     std::vector<dn::DeviceBuffer<uint8_t>> tmp;
     size_t tmp_bytes = 0;
+    // device inflate (dn_bam_rows_inflate): the compressed blocks, their descriptors and states, the pinned host copy of the
+    // window, and the bytes of h->win that hold the resident window (-1: none)
+    dn::DeviceBuffer<uint8_t> comp;
+    dn::DeviceBuffer<dn::InflateBlock> blk;
+    dn::DeviceBuffer<int32_t> blk_status;
+    dn::PinnedBuffer<uint8_t> host_win;
+    dn::Event ev0, ev1;
+    int64_t cap_comp = 0, cap_blk = 0, cap_host = 0, resident = -1;
     std::string no_cigar;                  // the name of the first kept row without CIGAR ops ("" while there is none)
     bool has_no_cigar = false;
 };
@@ -954,23 +964,13 @@ extern "C" void dn_bam_rows_destroy(dn_bam_rows h)
     delete h;
 }
 
-extern "C" int dn_bam_rows_append(dn_bam_rows h, const uint8_t *window, int64_t n_bytes, const int64_t *rec_off, int64_t n_rec)
+namespace {
+
+// Decode, filter and compact the n_rec records of the window in h->win (n_bytes of it; `window` is a host copy of the same
+// bytes, read only to name a read in an error text) and append the kept rows.
+int append_window(dn_bam_rows h, const uint8_t *window, int64_t n_bytes, const int64_t *rec_off, int64_t n_rec)
 {
-    g_reads_err.clear();
-    if (!h || n_bytes < 0 || n_bytes > INT32_MAX || n_rec < 0 || (n_rec > 0 && (!window || !rec_off))) {
-        g_reads_err = "dn_bam_rows_append: bad argument";
-        return DN_E_INVALID;
-    }
-    if (n_rec == 0) return DN_OK;
-    for (int64_t i = 0; i < n_rec; i++)              // the kernels read 36 bytes at every offset: keep them inside the window
-        if (rec_off[i] < 0 || rec_off[i] + 36 > n_bytes) { g_reads_err = "dn_bam_rows_append: record offset outside the window"; return DN_E_INVALID; }
     hipStream_t st = h->st;
-    BAM_TRY(hipSetDevice(h->device));
-    if (n_bytes > h->cap_win) {                       // window scratch: nothing to keep (the previous append has finished)
-        const int64_t c = next_cap(h->cap_win, n_bytes);
-        BAM_TRY(resize(h->win, 0, c, st));
-        h->cap_win = c;
-    }
     if (n_rec + 1 > h->cap_rec) {
         const int64_t c = next_cap(h->cap_rec, n_rec + 1);
         BAM_TRY(resize(h->rec_off, 0, c, st)); BAM_TRY(resize(h->keep, 0, c, st)); BAM_TRY(resize(h->w_ops, 0, c, st));
@@ -978,7 +978,6 @@ extern "C" int dn_bam_rows_append(dn_bam_rows h, const uint8_t *window, int64_t 
         BAM_TRY(resize(h->name_rank, 0, c, st));
         h->cap_rec = c;
     }
-    BAM_TRY(hipMemcpyAsync(h->win, window, (size_t) n_bytes, hipMemcpyHostToDevice, st));
     BAM_TRY(hipMemcpyAsync(h->rec_off, rec_off, sizeof(int64_t) * (size_t) n_rec, hipMemcpyHostToDevice, st));
     BAM_TRY(hipMemsetAsync(h->err, 0xff, sizeof(unsigned long long) * kBamNErr, st));
     BAM_TRY(hipMemsetAsync(h->keep + n_rec, 0, sizeof(int32_t), st));
@@ -1049,6 +1048,130 @@ extern "C" int dn_bam_rows_append(dn_bam_rows h, const uint8_t *window, int64_t 
         h->n_names += tot[2];
     }
     return DN_OK;
+}
+
+int grow_window(dn_bam_rows h, int64_t n_bytes)       // window scratch: nothing to keep (the previous append has finished)
+{
+    if (n_bytes > h->cap_win) {
+        const int64_t c = next_cap(h->cap_win, n_bytes);
+        BAM_TRY(resize(h->win, 0, c, h->st));
+        h->cap_win = c;
+    }
+    return DN_OK;
+}
+
+int check_offsets(const char *who, int64_t n_bytes, const int64_t *rec_off, int64_t n_rec)
+{
+    for (int64_t i = 0; i < n_rec; i++)              // the kernels read 36 bytes at every offset: keep them inside the window
+        if (rec_off[i] < 0 || rec_off[i] + 36 > n_bytes) { g_reads_err = std::string(who) + ": record offset outside the window"; return DN_E_INVALID; }
+    return DN_OK;
+}
+
+}  // namespace
+
+extern "C" int dn_bam_rows_append(dn_bam_rows h, const uint8_t *window, int64_t n_bytes, const int64_t *rec_off, int64_t n_rec)
+{
+    g_reads_err.clear();
+    if (!h || n_bytes < 0 || n_bytes > INT32_MAX || n_rec < 0 || (n_rec > 0 && (!window || !rec_off))) {
+        g_reads_err = "dn_bam_rows_append: bad argument";
+        return DN_E_INVALID;
+    }
+    if (n_rec == 0) return DN_OK;
+    int rc = check_offsets("dn_bam_rows_append", n_bytes, rec_off, n_rec);
+    if (rc != DN_OK) return rc;
+    BAM_TRY(hipSetDevice(h->device));
+    h->resident = -1;
+    rc = grow_window(h, n_bytes);
+    if (rc != DN_OK) return rc;
+    BAM_TRY(hipMemcpyAsync(h->win, window, (size_t) n_bytes, hipMemcpyHostToDevice, h->st));
+    return append_window(h, window, n_bytes, rec_off, n_rec);
+}
+
+extern "C" int dn_bam_rows_inflate(dn_bam_rows h, const uint8_t *carry, int64_t n_carry, const uint8_t *comp, int64_t n_comp,
+                                   int64_t n_blocks, const int64_t *pay_off, const int32_t *pay_len, const int32_t *isize,
+                                   int32_t head_skip, int32_t tail_keep, const uint8_t **host_window, int64_t *n_bytes,
+                                   int32_t *status, double *device_ms)
+{
+    g_reads_err.clear();
+    if (!h || n_carry < 0 || (n_carry > 0 && !carry) || n_comp < 0 || (n_comp > 0 && !comp) || n_blocks < 0 || n_blocks > INT32_MAX ||
+        (n_blocks > 0 && (!pay_off || !pay_len || !isize || !status)) || head_skip < 0 || !host_window || !n_bytes) {
+        g_reads_err = "dn_bam_rows_inflate: bad argument";
+        return DN_E_INVALID;
+    }
+    std::vector<dn::InflateBlock> blk((size_t) n_blocks);
+    int64_t total = n_carry;
+    for (int64_t b = 0; b < n_blocks; b++) {
+        if (pay_off[b] < 0 || pay_len[b] < 0 || pay_off[b] > n_comp || pay_len[b] > n_comp - pay_off[b]) {
+            g_reads_err = "dn_bam_rows_inflate: payload of block " + std::to_string(b) + " outside comp";
+            return DN_E_INVALID;
+        }
+        if (isize[b] < 0) {     // no upper bound: the ring decoder does not need one, and the host path reads over-long blocks too
+            g_reads_err = "dn_bam_rows_inflate: block " + std::to_string(b) + " has a negative inflated size";
+            return DN_E_INVALID;
+        }
+        int32_t hi = isize[b], lo = 0;                  // the last block is cut first, then the first one, as the host path does
+        if (b == n_blocks - 1 && tail_keep >= 0 && tail_keep < hi) hi = tail_keep;
+        if (b == 0) lo = head_skip < hi ? head_skip : hi;
+        blk[(size_t) b] = dn::InflateBlock{pay_off[b], total, pay_len[b], isize[b], lo, hi - lo};
+        total += hi - lo;
+    }
+    if (total > INT32_MAX) { g_reads_err = "dn_bam_rows_inflate: window beyond 2^31 - 1 bytes"; return DN_E_INVALID; }
+    hipStream_t st = h->st;
+    BAM_TRY(hipSetDevice(h->device));
+    h->resident = -1;
+    int rc = grow_window(h, total);
+    if (rc != DN_OK) return rc;
+    const int64_t comp_cap = dn::inflate_comp_cap(n_comp);
+    if (comp_cap > h->cap_comp) {
+        const int64_t c = next_cap(h->cap_comp, comp_cap);
+        BAM_TRY(resize(h->comp, 0, c, st));
+        h->cap_comp = c;
+    }
+    if (n_blocks > h->cap_blk) {
+        const int64_t c = next_cap(h->cap_blk, n_blocks);
+        BAM_TRY(resize(h->blk, 0, c, st)); BAM_TRY(resize(h->blk_status, 0, c, st));
+        h->cap_blk = c;
+    }
+    if (total + 16 > h->cap_host) {
+        const int64_t c = next_cap(h->cap_host, total + 16);
+        dn::PinnedBuffer<uint8_t> nb;                   // the old copy stays until the new one exists, as in resize()
+        BAM_TRY(nb.alloc((size_t) c));
+        h->host_win = std::move(nb);
+        h->cap_host = c;
+    }
+    if (!h->ev0) { BAM_TRY(h->ev0.create(hipEventCreate)); BAM_TRY(h->ev1.create(hipEventCreate)); }
+    if (n_carry > 0) BAM_TRY(hipMemcpyAsync(h->win, carry, (size_t) n_carry, hipMemcpyHostToDevice, st));
+    if (n_comp > 0) BAM_TRY(hipMemcpyAsync(h->comp, comp, (size_t) n_comp, hipMemcpyHostToDevice, st));
+    if (n_blocks > 0) BAM_TRY(hipMemcpyAsync(h->blk, blk.data(), sizeof(dn::InflateBlock) * (size_t) n_blocks, hipMemcpyHostToDevice, st));
+    BAM_TRY(hipEventRecord(h->ev0, st));
+    BAM_TRY(dn::inflate_launch(st, h->comp, comp_cap, h->blk, n_blocks, h->win, h->blk_status));
+    BAM_TRY(hipEventRecord(h->ev1, st));
+    if (total > 0) BAM_TRY(hipMemcpyAsync(h->host_win, h->win, (size_t) total, hipMemcpyDeviceToHost, st));
+    if (n_blocks > 0) BAM_TRY(hipMemcpyAsync(status, h->blk_status, sizeof(int32_t) * (size_t) n_blocks, hipMemcpyDeviceToHost, st));
+    BAM_TRY(hipStreamSynchronize(st));
+    if (device_ms) {
+        float ms = 0.f;
+        BAM_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+        *device_ms = ms;
+    }
+    *host_window = h->host_win;
+    *n_bytes = total;
+    h->resident = total;
+    for (int64_t b = 0; b < n_blocks; b++)
+        if (status[b] != 0) { h->resident = -1; break; }     // a block that failed left its bytes unspecified
+    return DN_OK;
+}
+
+extern "C" int dn_bam_rows_append_resident(dn_bam_rows h, const int64_t *rec_off, int64_t n_rec)
+{
+    g_reads_err.clear();
+    if (!h || n_rec < 0 || (n_rec > 0 && !rec_off)) { g_reads_err = "dn_bam_rows_append_resident: bad argument"; return DN_E_INVALID; }
+    if (h->resident < 0) { g_reads_err = "dn_bam_rows_append_resident: no resident window (dn_bam_rows_inflate first)"; return DN_E_STATE; }
+    if (n_rec == 0) return DN_OK;
+    const int rc = check_offsets("dn_bam_rows_append_resident", h->resident, rec_off, n_rec);
+    if (rc != DN_OK) return rc;
+    BAM_TRY(hipSetDevice(h->device));
+    return append_window(h, h->host_win, h->resident, rec_off, n_rec);
 }
 
 extern "C" int dn_bam_rows_info(dn_bam_rows h, int64_t *n_rows, int64_t *n_ops, int64_t *n_name_bytes, int32_t *max_key_len)

@@ -309,6 +309,44 @@ int  dn_bam_rows_coverage(dn_bam_rows h, const int32_t *order, const int32_t *pa
 int  dn_bam_cigar_bounds(int device, int64_t n, const int64_t *pos, const int64_t *op_off, const uint32_t *ops,
                          int32_t max_seg, int32_t *nseg, int64_t *bounds, int64_t *end_pos);
 
+/* BGZF inflate on the device (csrc/dn_inflate.hip) ----------------------------------------------------------------------
+ * A raw-DEFLATE (RFC 1951) decoder of the library's own: one BGZF block per wavefront, no zlib.  Block b's payload (the
+ * bytes between its gzip header and its CRC32 / ISIZE trailer) is comp[pay_off[b] .. pay_off[b] + pay_len[b]) and must
+ * inflate to exactly out_off[b+1] - out_off[b] bytes (its ISIZE, 0 .. 65536), which go to out + out_off[b]; out_off has
+ * n_blocks + 1 entries and starts at 0.  The input is untrusted: a block that does not decode sets status[b] to one of the
+ * DN_INFLATE_E_* below, leaves its output bytes unspecified and does not fail the call (DN_OK); status[b] = 0 otherwise.
+ * Arrays that contradict each other (a payload outside comp, a size outside 0 .. 65536, out_off not monotone): DN_E_INVALID.
+ *   dn_bgzf_inflate_host  the same decoder source compiled for the host, one block after the other; no device is touched.
+ *   dn_bgzf_inflate       copy comp to `device`, inflate, copy back to out (host memory).  copy_ms / device_ms (nullable):
+ *                         the copy in and the kernel, by HIP events.
+ *   dn_bam_rows_inflate   build the next window of a row store on its device: n_carry bytes of `carry` (the record cut by the
+ *                         end of the window before), then the inflated blocks; the first block loses its first head_skip
+ *                         bytes, the last one is cut to tail_keep bytes first (tail_keep < 0: kept whole).  *host_window
+ *                         points at a pinned host copy of the *n_bytes of the window (owned by the store, valid until its
+ *                         next dn_bam_rows_inflate or its destruction) for dn_bam_frame; the window stays resident unless a
+ *                         block failed.  isize[b] may exceed 65536 here (the decoder keeps 32 KiB of history, not the
+ *                         block, and zlib-based readers accept such files).  device_ms (nullable): the inflate kernel.
+ *   dn_bam_rows_append_resident   dn_bam_rows_append on the resident window, without uploading it again; DN_E_STATE when
+ *                         there is none.
+ * Errors: dn_reads_last_error(). */
+#define DN_INFLATE_E_HEADER    1   /* block type 3, a stored block whose LEN / NLEN disagree, too many code lengths         */
+#define DN_INFLATE_E_LENGTHS   2   /* over-subscribed or incomplete code lengths, a bad repeat, no end-of-block code        */
+#define DN_INFLATE_E_CODE      3   /* a code that is not in the table, or a length / distance symbol that does not exist    */
+#define DN_INFLATE_E_DISTANCE  4   /* a distance beyond the output so far                                                   */
+#define DN_INFLATE_E_INPUT     5   /* the payload ends before the final block does                                          */
+#define DN_INFLATE_E_SIZE      6   /* the output is not ISIZE bytes long                                                    */
+#define DN_INFLATE_E_TRAILING  7   /* bytes left in the payload after the final block                                       */
+int  dn_bgzf_inflate_host(const uint8_t *comp, int64_t n_comp, int64_t n_blocks, const int64_t *pay_off, const int32_t *pay_len,
+                          const int64_t *out_off, uint8_t *out, int32_t *status);
+int  dn_bgzf_inflate(int device, const uint8_t *comp, int64_t n_comp, int64_t n_blocks, const int64_t *pay_off,
+                     const int32_t *pay_len, const int64_t *out_off, uint8_t *out, int32_t *status, double *copy_ms,
+                     double *device_ms);
+int  dn_bam_rows_inflate(dn_bam_rows h, const uint8_t *carry, int64_t n_carry, const uint8_t *comp, int64_t n_comp,
+                         int64_t n_blocks, const int64_t *pay_off, const int32_t *pay_len, const int32_t *isize,
+                         int32_t head_skip, int32_t tail_keep, const uint8_t **host_window, int64_t *n_bytes,
+                         int32_t *status, double *device_ms);
+int  dn_bam_rows_append_resident(dn_bam_rows h, const int64_t *rec_off, int64_t n_rec);
+
 /* GTF annotation scan (GeneAnnotationLoader, degnorm_amd/loaders.py) --------------------------------------------------
  * Replaces the reference's read_csv of the nine columns, its lower-case `apply` on the feature column and its regex
  * `apply` per exon row (loaders.py:128-152, _attribute_to_gene :102-112).  buf holds the n_bytes raw bytes of a GTF file,

@@ -3,7 +3,9 @@ Speed of the native BAM path (degnorm_amd.bam.NativeBamReadsProcessor) on the sy
 (tests/_reads_fixtures.scale_case: 20 Mb, 2 000 genes, 2 M single-end reads of the forms aM / aMnNbM), written as a sorted,
 indexed BAM, and on a paired variant (the same reads named <i // 2>.1 / .2, mates next to each other):
 
-  inflate_ms        host BGZF inflate of the chromosome's blocks (n_jobs threads)
+  inflate_ms        BGZF inflate of the chromosome's blocks: zlib on the host in n_jobs threads (--inflate host), or the
+                    library's DEFLATE kernel with the copy of the compressed blocks in and of the window back (--inflate device)
+  inflate_device_ms the DEFLATE kernel alone, by events (0 with --inflate host); inflate_gbps: inflated bytes over it
   frame_ms          host record framing (dn_bam_frame)
   decode_ms         the append calls: window upload, decode / filter kernels, compaction into the row store
   coverage_ms       the coverage call on the stored rows (paired: with the key download and the host sort)
@@ -11,9 +13,12 @@ indexed BAM, and on a paired variant (the same reads named <i // 2>.1 / .2, mate
   reads_per_s       end to end: reads / chromosome_coverage_read_counts (files written, index and header already read)
   in_memory_reads_per_s  chromosome_coverage_read_counts_df on the same reads held as a DataFrame
 
-    python tools/bam_speed.py [--reads 2000000] [--jobs 4] [--reps 3] [--dir DIR]
+    python tools/bam_speed.py [--reads 2000000] [--jobs 4] [--reps 3] [--dir DIR] [--inflate host|device] [--level 1]
 
-Prints one JSON line.  Needs a GPU.
+--level is the deflate level of the written files (the fixture writer's level 1 on random sequence bytes is nearly
+literal-only; real files are level 6 and full of matches).  Files found in --dir from an earlier run with the same
+--reads and --level are used again.  Every case reports its best repetition (by e2e_ms) and, as *_min / *_max, the
+spread of inflate_ms and e2e_ms over the repetitions.  Prints one JSON line.  Needs a GPU.
 """
 import argparse
 import json
@@ -36,21 +41,29 @@ from degnorm_amd import bam                          # noqa: E402
 from degnorm_amd import reads as dr                  # noqa: E402
 
 
-def _best(path, chrom, ov, gene_df, exon_df, out, jobs, reps):
-    best = None
+def _best(path, chrom, ov, gene_df, exon_df, out, jobs, reps, inflate):
+    best, rows = None, []
     for k in range(reps + 1):                        # the first run loads the library and warms the device up
-        proc = bam.NativeBamReadsProcessor(path, path + '.bai', output_dir=os.path.join(out, str(k)), n_jobs=jobs, verbose=False)
+        proc = bam.NativeBamReadsProcessor(path, path + '.bai', output_dir=os.path.join(out, str(k)), n_jobs=jobs, verbose=False,
+                                           inflate=inflate)
         os.makedirs(proc.save_dir, exist_ok=True)
         proc.timing = {}
         t0 = time.perf_counter()
         proc.chromosome_coverage_read_counts(ov, gene_df, exon_df, chrom)
         e2e = time.perf_counter() - t0
         t = proc.timing
-        row = {'inflate_ms': 1e3 * t.get('inflate_s', 0), 'frame_ms': 1e3 * t.get('frame_s', 0), 'decode_ms': 1e3 * t.get('decode_s', 0),
+        row = {'inflate_ms': 1e3 * t.get('inflate_s', 0), 'inflate_device_ms': t.get('inflate_device_ms', 0),
+               'frame_ms': 1e3 * t.get('frame_s', 0), 'decode_ms': 1e3 * t.get('decode_s', 0),
                'coverage_ms': 1e3 * t.get('coverage_s', 0), 'coverage_device_ms': t.get('coverage_device_ms', 0), 'e2e_ms': 1e3 * e2e}
-        if k > 0 and (best is None or row['e2e_ms'] < best['e2e_ms']):
-            best = row
-    return {key: round(v, 1 if key != 'coverage_device_ms' else 3) for key, v in best.items()}
+        if k > 0:
+            rows.append(row)
+            if best is None or row['e2e_ms'] < best['e2e_ms']:
+                best = row
+    best = {key: round(v, 3 if key.endswith('device_ms') else 1) for key, v in best.items()}
+    for key in ('inflate_ms', 'e2e_ms'):
+        best[key + '_min'] = round(min(r[key] for r in rows), 1)
+        best[key + '_max'] = round(max(r[key] for r in rows), 1)
+    return best
 
 
 def main():
@@ -59,6 +72,8 @@ def main():
     ap.add_argument('--jobs', type=int, default=4)
     ap.add_argument('--reps', type=int, default=3)
     ap.add_argument('--dir', default=None)
+    ap.add_argument('--inflate', choices=['host', 'device'], default='host')
+    ap.add_argument('--level', type=int, default=1)
     a = ap.parse_args()
     reads, chrom_len, ov, gene_df, exon_df = rf.scale_case(n_reads=a.reads)
     work = a.dir or tempfile.mkdtemp(prefix='bam_speed_')
@@ -66,20 +81,26 @@ def main():
         se = pd.DataFrame({'ref': 0, 'pos': reads.pos.values, 'qname': reads.qname.astype(str).values, 'cigar': reads.cigar.values})
         pe = se.assign(qname=['{0}.{1}'.format(i // 2, 1 + i % 2) for i in range(len(se))], next_ref=0)
         t0 = time.perf_counter()
-        bf.write_bam(os.path.join(work, 'se.bam'), [('chrS', chrom_len)], se)
-        bf.write_bam(os.path.join(work, 'pe.bam'), [('chrS', chrom_len)], pe)
+        files = {name: os.path.join(work, '{0}_{1}_l{2}.bam'.format(name, a.reads, a.level)) for name in ('se', 'pe')}
+        for name, df in (('se', se), ('pe', pe)):
+            if not (os.path.isfile(files[name]) and os.path.isfile(files[name] + '.bai')):
+                bf.write_bam(files[name], [('chrS', chrom_len)], df, level=a.level)
         write_s = time.perf_counter() - t0
+        inflated = {name: int(bam.bgzf_blocks(files[name])[2].sum()) for name in files}
         in_mem = None
         for _ in range(a.reps + 1):
             t0 = time.perf_counter()
             dr.chromosome_coverage_read_counts_df(reads, chrom_len, ov, gene_df, exon_df, False)
             dt = time.perf_counter() - t0
             in_mem = dt if in_mem is None else min(in_mem, dt)
-        out = {'tool': 'bam_speed', 'reads': a.reads, 'jobs': a.jobs, 'bam_mb': round(os.path.getsize(os.path.join(work, 'se.bam')) / 2 ** 20, 1),
+        out = {'tool': 'bam_speed', 'reads': a.reads, 'jobs': a.jobs, 'inflate': a.inflate, 'level': a.level,
+               'bam_mb': round(os.path.getsize(files['se']) / 2 ** 20, 1), 'inflated_mb': round(inflated['se'] / 2 ** 20, 1),
                'write_s': round(write_s, 1)}
         for name in ('se', 'pe'):
-            row = _best(os.path.join(work, name + '.bam'), 'chrS', ov, gene_df, exon_df, os.path.join(work, 'out_' + name),
-                        a.jobs, a.reps)
+            row = _best(files[name], 'chrS', ov, gene_df, exon_df, os.path.join(work, 'out_{0}_{1}'.format(name, a.inflate)),
+                        a.jobs, a.reps, a.inflate)
+            if row['inflate_device_ms'] > 0:
+                row['inflate_gbps'] = round(inflated[name] / (row['inflate_device_ms'] * 1e-3) / 1e9, 2)
             row['reads_per_s'] = round(a.reads / (row['e2e_ms'] * 1e-3))
             out[name] = row
         out['in_memory_ms'] = round(1e3 * in_mem, 1)
