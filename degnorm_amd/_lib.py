@@ -148,17 +148,21 @@ def load(build_if_missing=False):
     return lib
 
 
-def _check(rc):
+def _check(rc, what=None, invalid_is_value_error=True):
+    """Raise for the return code of a failed C call, with the library's error text (one text for every family of calls):
+    ValueError for DN_E_INVALID unless invalid_is_value_error is off, DegnormAmdError naming `what` otherwise."""
     if rc == DN_OK:
         return
     msg = load().dn_last_error().decode('utf-8', 'replace')
-    if rc == DN_E_INVALID:
+    if rc == DN_E_INVALID and invalid_is_value_error:
         raise ValueError(msg)
-    raise DegnormAmdError('degnorm_amd error {0}: {1}'.format(rc, msg))
+    if what is None:
+        raise DegnormAmdError('degnorm_amd error {0}: {1}'.format(rc, msg))
+    raise DegnormAmdError('{0} failed ({1}): {2}'.format(what, rc, msg))
 
 
 def _p(arr, ctype):
-    return arr.ctypes.data_as(ctypes.POINTER(ctype))
+    return arr.ctypes.data_as(ctypes.POINTER(ctype)) if arr is not None else None
 
 
 def device_count():

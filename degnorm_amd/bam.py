@@ -25,7 +25,8 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 
 from . import _lib
-from .reads import BamReadsProcessor, Annotation, coverage_outputs, reads_frame, _ptr
+from ._lib import _check, _p as _ptr
+from .reads import BamReadsProcessor, Annotation, coverage_outputs, reads_frame
 
 BGZF_EOF = bytes.fromhex('1f8b08040000000000ff0600424302001b0003000000000000000000')
 PSEUDO_BIN = 37450
@@ -239,14 +240,6 @@ def reference_range(ref):
 
 
 # --- framing and the device row store ------------------------------------------------------------------------------------
-
-def _check(rc, what):
-    if rc != _lib.DN_OK:
-        msg = _lib.load().dn_reads_last_error().decode('utf-8', 'replace')
-        if rc == _lib.DN_E_INVALID:
-            raise ValueError(msg)
-        raise _lib.DegnormAmdError('{0} failed ({1}): {2}'.format(what, rc, msg))
-
 
 def frame_records(buf, tid=-1, last_pos=_INT32_MIN):
     """

@@ -131,9 +131,7 @@ def assemble_chrom_packed(data_dir, sample_ids, chrom_exon_df, device=None, verb
                                   _lib._p(lengths, ctypes.c_int64), int(c_gene.size), _lib._p(c_gene, ctypes.c_int32),
                                   _lib._p(c_src, ctypes.c_int64), _lib._p(c_dst, ctypes.c_int64),
                                   _lib._p(c_len, ctypes.c_int32), _lib._p(packed, ctypes.c_float), ctypes.byref(ms))
-    if rc != 0:
-        raise _lib.DegnormAmdError('dn_assemble_coverage failed ({0}): {1}'.format(
-            rc, lib.dn_assemble_last_error().decode('utf-8', 'replace')))
+    _lib._check(rc, 'dn_assemble_coverage', invalid_is_value_error=False)
     return genes, packed, lengths, float(ms.value)
 
 

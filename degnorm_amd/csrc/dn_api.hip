@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <numeric>
 #include <string>
 #include <thread>
@@ -324,18 +325,14 @@ __global__ __launch_bounds__(256) void k_trace_head(const int32_t *__restrict__ 
     }
 }
 
+// the library's one error text (dn_host.hpp); every dn_*_last_error returns it
 static thread_local std::string g_err;
 
-static int fail(int code, const std::string &msg) { g_err = msg; return code; }
-
-// HIP_TRY_AS: the message is `what`, then the HIP error; HIP_TRY names the failed expression
-#define HIP_TRY_AS(what, expr)                                                                     \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess)                                                                      \
-            return fail(DN_E_HIP, std::string(what) + ": " + hipGetErrorString(e_));              \
-    } while (0)
-#define HIP_TRY(expr) HIP_TRY_AS(#expr, expr)
+int dn::fail(int code, const std::string &msg) { g_err = msg; return code; }
+int dn::fail_hip(const char *what, hipError_t e) { return fail(DN_E_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
+void dn::clear_error() { g_err.clear(); }
+const char *dn::last_error() { return g_err.c_str(); }
+using dn::fail;
 
 struct dn_handle_s {
     int device = -1;
@@ -524,7 +521,10 @@ extern "C" {
 // the library, its target, and the build it is: compiler version and code-generation flags (degnorm_amd/build.py build_stamp).
 // Results are bit-reproducible per binary; what may differ between two builds is named here.
 const char *dn_version(void) { return "degnorm_amd 0.2.0 (gfx950) [" DN_BUILD_STAMP "]"; }
-const char *dn_last_error(void) { return g_err.c_str(); }
+const char *dn_last_error(void) { return dn::last_error(); }
+const char *dn_reads_last_error(void) { return dn::last_error(); }
+const char *dn_assemble_last_error(void) { return dn::last_error(); }
+const char *dn_gtf_last_error(void) { return dn::last_error(); }
 
 int dn_device_count(void)
 {
@@ -542,16 +542,16 @@ static int create_streams(dn_handle h)
     // emptied its queue (seen: the wide kernel then ends LAST, sweep 291 -> 307 ms).  Stream priorities make the dispatcher
     // place pending wide workgroups first, then narrow ones, then pairs.
     int prio_least = 0, prio_greatest = 0;
-    HIP_TRY(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
+    DN_TRY(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
     const int prio[dn_handle_s::NCLS] = {prio_greatest, (prio_least + prio_greatest) / 2, prio_least};
     for (int c = 0; c < dn_handle_s::NCLS; c++) {
-        HIP_TRY(h->stream[c].create(hipStreamCreateWithPriority, hipStreamNonBlocking, prio[c]));
-        HIP_TRY(h->ev_start[c].create(hipEventCreate));
-        HIP_TRY(h->ev_end[c].create(hipEventCreate));
+        DN_TRY(h->stream[c].create(hipStreamCreateWithPriority, hipStreamNonBlocking, prio[c]));
+        DN_TRY(h->ev_start[c].create(hipEventCreate));
+        DN_TRY(h->ev_end[c].create(hipEventCreate));
     }
-    HIP_TRY(h->ev_ready.create(hipEventCreateWithFlags, hipEventDisableTiming));
-    HIP_TRY(h->ev_i0.create(hipEventCreate));
-    HIP_TRY(h->ev_i1.create(hipEventCreate));
+    DN_TRY(h->ev_ready.create(hipEventCreateWithFlags, hipEventDisableTiming));
+    DN_TRY(h->ev_i0.create(hipEventCreate));
+    DN_TRY(h->ev_i1.create(hipEventCreate));
     return DN_OK;
 }
 
@@ -562,10 +562,10 @@ int dn_create(int device, dn_handle *out)
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(DN_E_NO_DEVICE, "no HIP device visible");
     if (device < 0 || device >= ndev) return fail(DN_E_INVALID, "dn_create: device index out of range");
-    HIP_TRY(hipSetDevice(device));
+    DN_TRY(hipSetDevice(device));
     hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, device));
-    dn_handle h = new dn_handle_s();
+    DN_TRY(hipGetDeviceProperties(&prop, device));
+    dn_handle h = std::make_unique<dn_handle_s>().release();      // dn_destroy deletes it
     h->device = device;
     h->n_cus = prop.multiProcessorCount;
     const int rc = create_streams(h);
@@ -606,13 +606,13 @@ static int size_class(dn_handle h, dn_handle_s::GeneClass &C, int32_t cols)
         // one very long gene sizes every slot of its class: keep the scratch within a share of free HBM by
         // running fewer persistent workgroups rather than failing (the old scratch, still allocated, counts as free)
         size_t free_b = 0, total_b = 0;
-        HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+        DN_TRY(hipMemGetInfo(&free_b, &total_b));
         const int64_t budget = (int64_t) ((free_b + (C.d_ws ? (size_t) C.slot_bytes * (size_t) std::max(C.slots, 1) : 0)) / 3);
         if (slot_bytes > budget) return fail(DN_E_INVALID, "a gene is too long for the device scratch (" + std::to_string(S) + " columns)");
         slots = (int) std::max<int64_t>(units, std::min<int64_t>(slots, budget / slot_bytes / units * units));
     }
     dn::DeviceBuffer<char> ws;
-    HIP_TRY(ws.alloc((size_t) slot_bytes * (size_t) std::max(slots, 1)));
+    DN_TRY(ws.alloc((size_t) slot_bytes * (size_t) std::max(slots, 1)));
     C.d_ws = std::move(ws);                                // releases the old scratch
     C.slots = slots; C.S = S; C.slot_bytes = slot_bytes;
     // lambda LDS tier: whatever of the CU's 160 KiB is left per resident workgroup after the static part
@@ -753,7 +753,7 @@ static int finish_upload_impl(dn_handle h, const CoverageSource &src)
     const int64_t n = h->n;
     const int32_t p = h->p;
     free_device(h);
-    HIP_TRY(hipSetDevice(h->device));
+    DN_TRY(hipSetDevice(h->device));
 
     // work queue: longest gene first (a 17-call gene costs ~17x a 1-call gene)
     h->have_trace = false;
@@ -770,40 +770,40 @@ static int finish_upload_impl(dn_handle h, const CoverageSource &src)
         for (int32_t c = 0; c < h->glen[g]; c += 256) { tg.push_back((int32_t) g); tc.push_back(c); }
     h->n_tiles = (int64_t) tg.size();
 
-    HIP_TRY(h->data.d_cov.alloc(sizeof(float) * (size_t) std::max<int64_t>(h->total, 1)));
-    HIP_TRY(h->data.d_goff.alloc(sizeof(int64_t) * (size_t) (n + 1)));
-    HIP_TRY(h->data.d_glen.alloc(sizeof(int32_t) * (size_t) n));
-    HIP_TRY(h->data.d_order.alloc(sizeof(int32_t) * (size_t) n));
-    HIP_TRY(h->data.d_counter.alloc(sizeof(int32_t) * 4));
-    HIP_TRY(h->data.d_ds.alloc(sizeof(int64_t) * (size_t) n));
-    HIP_TRY(h->data.d_rho.alloc(sizeof(double) * (size_t) n * p));
-    HIP_TRY(h->data.d_flags.alloc(sizeof(int32_t) * (size_t) n));
-    HIP_TRY(h->data.d_trace.alloc(sizeof(int32_t) * (size_t) n * dn::TRACE_LEN));
-    HIP_TRY(h->data.d_kfin.alloc(sizeof(double) * (size_t) n * p));
-    HIP_TRY(h->data.d_emode.alloc(sizeof(int32_t) * (size_t) n));
-    HIP_TRY(h->data.d_svoff.alloc(sizeof(int64_t) * (size_t) (n + 1)));
-    HIP_TRY(h->data.d_est_sums.alloc(sizeof(double) * (size_t) n * p));
-    HIP_TRY(h->data.d_cov_sums.alloc(sizeof(double) * (size_t) n * p));
-    HIP_TRY(h->data.d_status.alloc(sizeof(int32_t) * (size_t) n));
-    HIP_TRY(h->data.d_rowmax.alloc(sizeof(float) * (size_t) n * p));
-    HIP_TRY(h->data.d_x16.alloc(sizeof(int32_t) * (size_t) n));
-    HIP_TRY(h->data.d_tile_gene.alloc(sizeof(int32_t) * (size_t) std::max<int64_t>(h->n_tiles, 1)));
-    HIP_TRY(h->data.d_tile_col.alloc(sizeof(int32_t) * (size_t) std::max<int64_t>(h->n_tiles, 1)));
+    DN_TRY(h->data.d_cov.alloc(sizeof(float) * (size_t) std::max<int64_t>(h->total, 1)));
+    DN_TRY(h->data.d_goff.alloc(sizeof(int64_t) * (size_t) (n + 1)));
+    DN_TRY(h->data.d_glen.alloc(sizeof(int32_t) * (size_t) n));
+    DN_TRY(h->data.d_order.alloc(sizeof(int32_t) * (size_t) n));
+    DN_TRY(h->data.d_counter.alloc(sizeof(int32_t) * 4));
+    DN_TRY(h->data.d_ds.alloc(sizeof(int64_t) * (size_t) n));
+    DN_TRY(h->data.d_rho.alloc(sizeof(double) * (size_t) n * p));
+    DN_TRY(h->data.d_flags.alloc(sizeof(int32_t) * (size_t) n));
+    DN_TRY(h->data.d_trace.alloc(sizeof(int32_t) * (size_t) n * dn::TRACE_LEN));
+    DN_TRY(h->data.d_kfin.alloc(sizeof(double) * (size_t) n * p));
+    DN_TRY(h->data.d_emode.alloc(sizeof(int32_t) * (size_t) n));
+    DN_TRY(h->data.d_svoff.alloc(sizeof(int64_t) * (size_t) (n + 1)));
+    DN_TRY(h->data.d_est_sums.alloc(sizeof(double) * (size_t) n * p));
+    DN_TRY(h->data.d_cov_sums.alloc(sizeof(double) * (size_t) n * p));
+    DN_TRY(h->data.d_status.alloc(sizeof(int32_t) * (size_t) n));
+    DN_TRY(h->data.d_rowmax.alloc(sizeof(float) * (size_t) n * p));
+    DN_TRY(h->data.d_x16.alloc(sizeof(int32_t) * (size_t) n));
+    DN_TRY(h->data.d_tile_gene.alloc(sizeof(int32_t) * (size_t) std::max<int64_t>(h->n_tiles, 1)));
+    DN_TRY(h->data.d_tile_col.alloc(sizeof(int32_t) * (size_t) std::max<int64_t>(h->n_tiles, 1)));
 
-    if (src.packed) HIP_TRY(hipMemcpyAsync(h->data.d_cov, src.packed, sizeof(float) * (size_t) h->total, hipMemcpyHostToDevice, h->stream[0]));
+    if (src.packed) DN_TRY(hipMemcpyAsync(h->data.d_cov, src.packed, sizeof(float) * (size_t) h->total, hipMemcpyHostToDevice, h->stream[0]));
     else { const int rcu = upload_ragged_chunks(h, src); if (rcu != DN_OK) return rcu; }
-    HIP_TRY(hipMemcpyAsync(h->data.d_goff, h->goff.data(), sizeof(int64_t) * (size_t) (n + 1), hipMemcpyHostToDevice, h->stream[0]));
-    HIP_TRY(hipMemcpyAsync(h->data.d_glen, h->glen.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
-    HIP_TRY(hipMemcpyAsync(h->data.d_order, order.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
-    HIP_TRY(hipMemcpyAsync(h->data.d_svoff, h->svoff.data(), sizeof(int64_t) * (size_t) (n + 1), hipMemcpyHostToDevice, h->stream[0]));
-    HIP_TRY(hipMemcpyAsync(h->data.d_tile_gene, tg.data(), sizeof(int32_t) * tg.size(), hipMemcpyHostToDevice, h->stream[0]));
-    HIP_TRY(hipMemcpyAsync(h->data.d_tile_col, tc.data(), sizeof(int32_t) * tc.size(), hipMemcpyHostToDevice, h->stream[0]));
-    HIP_TRY(hipEventRecord(h->ev_i0, h->stream[0]));
+    DN_TRY(hipMemcpyAsync(h->data.d_goff, h->goff.data(), sizeof(int64_t) * (size_t) (n + 1), hipMemcpyHostToDevice, h->stream[0]));
+    DN_TRY(hipMemcpyAsync(h->data.d_glen, h->glen.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
+    DN_TRY(hipMemcpyAsync(h->data.d_order, order.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
+    DN_TRY(hipMemcpyAsync(h->data.d_svoff, h->svoff.data(), sizeof(int64_t) * (size_t) (n + 1), hipMemcpyHostToDevice, h->stream[0]));
+    DN_TRY(hipMemcpyAsync(h->data.d_tile_gene, tg.data(), sizeof(int32_t) * tg.size(), hipMemcpyHostToDevice, h->stream[0]));
+    DN_TRY(hipMemcpyAsync(h->data.d_tile_col, tc.data(), sizeof(int32_t) * tc.size(), hipMemcpyHostToDevice, h->stream[0]));
+    DN_TRY(hipEventRecord(h->ev_i0, h->stream[0]));
     hipLaunchKernelGGL(k_row_max, dim3((unsigned) std::min<int64_t>(n, (int64_t) h->n_cus * 8)), dim3(256), 0, h->stream[0],
                        h->data.d_cov, h->data.d_goff, h->data.d_glen, h->data.d_rowmax, h->data.d_x16, (int) n, (int) p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(h->ev_i1, h->stream[0]));
-    HIP_TRY(hipStreamSynchronize(h->stream[0]));
+    DN_TRY(hipGetLastError());
+    DN_TRY(hipEventRecord(h->ev_i1, h->stream[0]));
+    DN_TRY(hipStreamSynchronize(h->stream[0]));
     (void) hipEventElapsedTime(&h->last_rowmax_ms, h->ev_i0, h->ev_i1);
 
     // gene classes
@@ -836,9 +836,9 @@ static int finish_upload_impl(dn_handle h, const CoverageSource &src)
             auto &C = h->data.cls[c];
             C.n = (int32_t) ord[c].size();
             if (C.n == 0 || !C.ks) { C.n = 0; continue; }
-            HIP_TRY(C.d_order.alloc(sizeof(int32_t) * (size_t) C.n));
-            HIP_TRY(C.d_counter.alloc(sizeof(int32_t) * 4));
-            HIP_TRY(hipMemcpy(C.d_order, ord[c].data(), sizeof(int32_t) * (size_t) C.n, hipMemcpyHostToDevice));
+            DN_TRY(C.d_order.alloc(sizeof(int32_t) * (size_t) C.n));
+            DN_TRY(C.d_counter.alloc(sizeof(int32_t) * 4));
+            DN_TRY(hipMemcpy(C.d_order, ord[c].data(), sizeof(int32_t) * (size_t) C.n, hipMemcpyHostToDevice));
             C.order = ord[c];
             // columns a scratch slot must hold: the longest gene of the class, or -- for the one-wave-per-gene family,
             // chosen because the announced take-every rate leaves every gene at most 12 active columns -- that bound
@@ -941,7 +941,7 @@ int dn_upload_ragged(dn_handle h, int64_t n_genes, int32_t p, const void *const 
     if (!genes || !lengths) return fail(DN_E_INVALID, "dn_upload_ragged: null argument");
     int rc = check_shape(h, n_genes, p, lengths);
     if (rc != DN_OK) return rc;
-    HIP_TRY(hipSetDevice(h->device));
+    DN_TRY(hipSetDevice(h->device));
     if (n_threads < 1) n_threads = (int32_t) std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
     std::atomic<int64_t> bad(0);
     CoverageSource src;
@@ -955,32 +955,32 @@ int dn_ratio_svd_sums(dn_handle h, double *est_sums, double *cov_sums, int32_t *
 {
     if (!h || !h->data.d_cov) return fail(DN_E_STATE, "dn_ratio_svd_sums: nothing uploaded");
     if ((est_sums == nullptr) != (cov_sums == nullptr)) return fail(DN_E_INVALID, "dn_ratio_svd_sums: the two sums are fetched together or not at all");
-    HIP_TRY(hipSetDevice(h->device));
+    DN_TRY(hipSetDevice(h->device));
     dn::InitArgs a;
     a.cov = h->data.d_cov; a.goff = h->data.d_goff; a.glen = h->data.d_glen; a.order = h->data.d_order; a.counter = h->data.d_counter;
     a.est_sums = h->data.d_est_sums; a.cov_sums = h->data.d_cov_sums; a.status = h->data.d_status; a.n_genes = (int32_t) h->n;
     a.p = h->p; a.ws = h->data.cls[0].d_ws; a.slot_bytes = h->data.cls[0].slot_bytes; a.S = h->data.cls[0].S; a.max_steps = h->max_steps;
     a.x16 = h->data.d_x16;
     { const char *f64 = getenv("DN_INIT_FP64"); a.force_fp64 = (f64 && f64[0] == '1') ? 1 : 0; }
-    HIP_TRY(hipMemsetAsync(h->data.d_counter, 0, sizeof(int32_t) * 4, h->stream[0]));
+    DN_TRY(hipMemsetAsync(h->data.d_counter, 0, sizeof(int32_t) * 4, h->stream[0]));
     // occupancy of the kernel that ks->init() will start: from 17 samples on it is the matrix-core variant (round 2 asked for
     // the power-iteration kernel's figure here and ran k_ratio_svd_mg at ONE workgroup per CU instead of two)
     const int which_init = h->p >= 17 ? 2 : 1;
     int per_cu = std::max(1, h->ks->blocks_per_cu(which_init));
     int grid = (int) std::min<int64_t>(h->n, (int64_t) per_cu * h->n_cus);
     if (h->ks->p == 0) grid = std::min(grid, h->data.cls[0].slots);          // generic kernels work in the scratch slots
-    HIP_TRY(hipEventRecord(h->ev_i0, h->stream[0]));
+    DN_TRY(hipEventRecord(h->ev_i0, h->stream[0]));
     h->ks->init(a, grid, h->stream[0]);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(h->ev_i1, h->stream[0]));
+    DN_TRY(hipGetLastError());
+    DN_TRY(hipEventRecord(h->ev_i1, h->stream[0]));
     const size_t np = (size_t) h->n * h->p;
     if (est_sums) {                     // null: the sums stay on the device (dn_init_partials reduces them there)
-        HIP_TRY(hipMemcpyAsync(est_sums, h->data.d_est_sums, sizeof(double) * np, hipMemcpyDeviceToHost, h->stream[0]));
-        HIP_TRY(hipMemcpyAsync(cov_sums, h->data.d_cov_sums, sizeof(double) * np, hipMemcpyDeviceToHost, h->stream[0]));
+        DN_TRY(hipMemcpyAsync(est_sums, h->data.d_est_sums, sizeof(double) * np, hipMemcpyDeviceToHost, h->stream[0]));
+        DN_TRY(hipMemcpyAsync(cov_sums, h->data.d_cov_sums, sizeof(double) * np, hipMemcpyDeviceToHost, h->stream[0]));
     }
-    if (status) HIP_TRY(hipMemcpyAsync(status, h->data.d_status, sizeof(int32_t) * (size_t) h->n, hipMemcpyDeviceToHost, h->stream[0]));
-    HIP_TRY(hipStreamSynchronize(h->stream[0]));
-    HIP_TRY(hipEventElapsedTime(&h->last_init_ms, h->ev_i0, h->ev_i1));
+    if (status) DN_TRY(hipMemcpyAsync(status, h->data.d_status, sizeof(int32_t) * (size_t) h->n, hipMemcpyDeviceToHost, h->stream[0]));
+    DN_TRY(hipStreamSynchronize(h->stream[0]));
+    DN_TRY(hipEventElapsedTime(&h->last_init_ms, h->ev_i0, h->ev_i1));
     if (h->ks->p >= 2 && h->ks->p <= 16) snprintf(h->init_name, sizeof(h->init_name), "k_ratio_svd<%d,%d>", h->ks->p, h->ks->nt);
     else snprintf(h->init_name, sizeof(h->init_name), h->p >= 17 ? "gen::k_ratio_svd_mg" : "gen::k_ratio_svd_gen");
     return DN_OK;
@@ -1005,7 +1005,7 @@ int dn_baseline_iteration(dn_handle h, const double *scale, const dn_params *prm
         }
     }
     for (int i = 0; i < h->p; i++) if (!(scale[i] > 0.0) || !std::isfinite(scale[i])) return fail(DN_E_INVALID, "scale factors must be positive and finite");
-    HIP_TRY(hipSetDevice(h->device));
+    DN_TRY(hipSetDevice(h->device));
 
     {
         // the scratch slots were sized at upload (for the announced take-every rate in the one-wave-per-gene family):
@@ -1016,14 +1016,14 @@ int dn_baseline_iteration(dn_handle h, const double *scale, const dn_params *prm
             const int32_t longest = C.longest;
             const int32_t need = rate > 1 ? (longest + rate - 1) / rate : longest;
             if (need > C.S) {
-                HIP_TRY(hipStreamSynchronize(h->stream[0]));
+                DN_TRY(hipStreamSynchronize(h->stream[0]));
                 const int rc = size_class(h, C, need);
                 if (rc != DN_OK) return rc;
             }
         }
     }
     if (prm->want_estimates && !h->data.d_svec)
-        HIP_TRY(h->data.d_svec.alloc(sizeof(double) * (size_t) std::max<int64_t>(h->svoff[h->n], 1)));
+        DN_TRY(h->data.d_svec.alloc(sizeof(double) * (size_t) std::max<int64_t>(h->svoff[h->n], 1)));
 
     dn::IterArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -1037,7 +1037,7 @@ int dn_baseline_iteration(dn_handle h, const double *scale, const dn_params *prm
     for (int i = 0; i < h->p; i++) { a.scale[i] = scale[i]; a.inv_scale[i] = 1.0 / scale[i]; h->last_scale[i] = scale[i]; }
     for (int i = h->p; i < dn::P_MAX; i++) { a.scale[i] = 1.0; a.inv_scale[i] = 1.0; }
     if (prm->downsample_rate > 1) {
-        HIP_TRY(hipMemcpyAsync(h->data.d_ds, ds_start, sizeof(int64_t) * (size_t) h->n, hipMemcpyHostToDevice, h->stream[0]));
+        DN_TRY(hipMemcpyAsync(h->data.d_ds, ds_start, sizeof(int64_t) * (size_t) h->n, hipMemcpyHostToDevice, h->stream[0]));
         a.ds_start = h->data.d_ds;
     }
     // The narrow class (state in LDS, little fabric traffic) orders its queue most expensive first from the second
@@ -1056,11 +1056,11 @@ int dn_baseline_iteration(dn_handle h, const double *scale, const dn_params *prm
         }
         std::stable_sort(key.begin(), key.end(), [](const std::pair<double, int32_t> &a, const std::pair<double, int32_t> &b) { return a.first > b.first; });
         for (int32_t k = 0; k < C.n; k++) C.order[k] = key[k].second;
-        HIP_TRY(hipMemcpyAsync(C.d_order, C.order.data(), sizeof(int32_t) * (size_t) C.n, hipMemcpyHostToDevice, h->stream[0]));
+        DN_TRY(hipMemcpyAsync(C.d_order, C.order.data(), sizeof(int32_t) * (size_t) C.n, hipMemcpyHostToDevice, h->stream[0]));
     }
-    HIP_TRY(hipMemsetAsync(h->data.d_trace, 0, sizeof(int32_t) * (size_t) h->n * dn::TRACE_LEN, h->stream[0]));
-    for (auto &C : h->data.cls) if (C.n > 0) HIP_TRY(hipMemsetAsync(C.d_counter, 0, sizeof(int32_t) * 4, h->stream[0]));
-    HIP_TRY(hipEventRecord(h->ev_ready, h->stream[0]));
+    DN_TRY(hipMemsetAsync(h->data.d_trace, 0, sizeof(int32_t) * (size_t) h->n * dn::TRACE_LEN, h->stream[0]));
+    for (auto &C : h->data.cls) if (C.n > 0) DN_TRY(hipMemsetAsync(C.d_counter, 0, sizeof(int32_t) * 4, h->stream[0]));
+    DN_TRY(hipEventRecord(h->ev_ready, h->stream[0]));
     int first_cls = -1;
     for (int c = 0; c < dn_handle_s::NCLS; c++) {
         auto &C = h->data.cls[c];
@@ -1068,45 +1068,45 @@ int dn_baseline_iteration(dn_handle h, const double *scale, const dn_params *prm
         if (C.n == 0) continue;
         if (first_cls < 0) first_cls = c;
         hipStream_t st = h->stream[c];
-        if (c > 0) HIP_TRY(hipStreamWaitEvent(st, h->ev_ready, 0));
+        if (c > 0) DN_TRY(hipStreamWaitEvent(st, h->ev_ready, 0));
         a.order = C.d_order; a.counter = C.d_counter; a.ws = C.d_ws; a.slot_bytes = C.slot_bytes; a.S = C.S;
         a.lds_cols = C.lds_cols; a.n_genes = C.n;
-        HIP_TRY(hipEventRecord(h->ev_start[c], st));
+        DN_TRY(hipEventRecord(h->ev_start[c], st));
         const int lrc = C.ks->baseline(a, C.slots, C.dyn_lds, st);
         if (lrc != 0) return fail(DN_E_HIP, std::string("k_baseline launch: ") + hipGetErrorString((hipError_t) lrc));
-        HIP_TRY(hipEventRecord(h->ev_end[c], st));
+        DN_TRY(hipEventRecord(h->ev_end[c], st));
     }
     for (int c = 1; c < dn_handle_s::NCLS; c++)                                   // results are copied on the main stream
-        if (h->data.cls[c].n > 0) HIP_TRY(hipStreamWaitEvent(h->stream[0], h->ev_end[c], 0));
+        if (h->data.cls[c].n > 0) DN_TRY(hipStreamWaitEvent(h->stream[0], h->ev_end[c], 0));
     if (rho) {                          // null: the DI rows stay on the device (dn_outer_partials / dn_outer_apply / dn_fetch_outer)
-        HIP_TRY(hipMemcpyAsync(rho, h->data.d_rho, sizeof(double) * (size_t) h->n * h->p, hipMemcpyDeviceToHost, h->stream[0]));
-        HIP_TRY(hipMemcpyAsync(flags, h->data.d_flags, sizeof(int32_t) * (size_t) h->n, hipMemcpyDeviceToHost, h->stream[0]));
+        DN_TRY(hipMemcpyAsync(rho, h->data.d_rho, sizeof(double) * (size_t) h->n * h->p, hipMemcpyDeviceToHost, h->stream[0]));
+        DN_TRY(hipMemcpyAsync(flags, h->data.d_flags, sizeof(int32_t) * (size_t) h->n, hipMemcpyDeviceToHost, h->stream[0]));
     }
     const int32_t tcols = h->trace_cols;
     const size_t trace_ints = (size_t) h->n * (size_t) tcols;
     if (h->data.host_trace_len < trace_ints) {
         h->data.host_trace_len = 0;
-        HIP_TRY(h->data.host_trace.alloc(sizeof(int32_t) * trace_ints));
+        DN_TRY(h->data.host_trace.alloc(sizeof(int32_t) * trace_ints));
         h->data.host_trace_len = trace_ints;
     }
     if (tcols == dn::TRACE_LEN)
-        HIP_TRY(hipMemcpyAsync(h->data.host_trace, h->data.d_trace, sizeof(int32_t) * trace_ints, hipMemcpyDeviceToHost, h->stream[0]));
+        DN_TRY(hipMemcpyAsync(h->data.host_trace, h->data.d_trace, sizeof(int32_t) * trace_ints, hipMemcpyDeviceToHost, h->stream[0]));
     else {
-        if (!h->data.d_trace_head) HIP_TRY(h->data.d_trace_head.alloc(sizeof(int32_t) * (size_t) h->n * dn::TRACE_LEN));
+        if (!h->data.d_trace_head) DN_TRY(h->data.d_trace_head.alloc(sizeof(int32_t) * (size_t) h->n * dn::TRACE_LEN));
         hipLaunchKernelGGL(k_trace_head, dim3((unsigned) std::min<size_t>(1024, (trace_ints + 255) / 256)), dim3(256), 0, h->stream[0],
                            h->data.d_trace, h->data.d_trace_head, (long long) trace_ints, (int) tcols);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(h->data.host_trace, h->data.d_trace_head, sizeof(int32_t) * trace_ints, hipMemcpyDeviceToHost, h->stream[0]));
+        DN_TRY(hipGetLastError());
+        DN_TRY(hipMemcpyAsync(h->data.host_trace, h->data.d_trace_head, sizeof(int32_t) * trace_ints, hipMemcpyDeviceToHost, h->stream[0]));
     }
-    HIP_TRY(hipStreamSynchronize(h->stream[0]));
+    DN_TRY(hipStreamSynchronize(h->stream[0]));
     h->have_trace = (prm->downsample_rate <= 1);          // with down-sampling the active columns are redrawn every iteration
     if (trace) std::memcpy(trace, h->data.host_trace, sizeof(int32_t) * trace_ints);
     h->last_span_ms = 0.f;
     for (int c = 0; c < dn_handle_s::NCLS; c++) {
         if (h->data.cls[c].n == 0) continue;
-        HIP_TRY(hipEventElapsedTime(&h->data.cls[c].last_ms, h->ev_start[c], h->ev_end[c]));
+        DN_TRY(hipEventElapsedTime(&h->data.cls[c].last_ms, h->ev_start[c], h->ev_end[c]));
         float span = 0.f;                                                // the classes are launched in order: the first start opens the span
-        HIP_TRY(hipEventElapsedTime(&span, h->ev_start[first_cls], h->ev_end[c]));
+        DN_TRY(hipEventElapsedTime(&span, h->ev_start[first_cls], h->ev_end[c]));
         h->last_span_ms = std::max(h->last_span_ms, span);
     }
     h->last_ms = first_cls >= 0 ? h->data.cls[first_cls].last_ms : 0.f;
@@ -1118,16 +1118,16 @@ static int outer_alloc(dn_handle h, int32_t degnorm_iter)
 {
     const size_t np = (size_t) h->n * h->p;
     if (!h->data.d_rhoc) {
-        HIP_TRY(h->data.d_rhoc.alloc(sizeof(double) * np));
-        HIP_TRY(h->data.d_xw.alloc(sizeof(double) * np));
-        HIP_TRY(h->data.d_xadj.alloc(sizeof(double) * np));
+        DN_TRY(h->data.d_rhoc.alloc(sizeof(double) * np));
+        DN_TRY(h->data.d_xw.alloc(sizeof(double) * np));
+        DN_TRY(h->data.d_xadj.alloc(sizeof(double) * np));
     }
     if (!h->data.d_part) {
-        HIP_TRY(h->data.d_part.alloc(sizeof(double) * (size_t) OUT_BLOCKS * OUT_STRIDE));
-        HIP_TRY(h->data.d_pvec.alloc(sizeof(double) * (3 * dn::P_MAX + 4 + 2 * dn::P_MAX)));
+        DN_TRY(h->data.d_part.alloc(sizeof(double) * (size_t) OUT_BLOCKS * OUT_STRIDE));
+        DN_TRY(h->data.d_pvec.alloc(sizeof(double) * (3 * dn::P_MAX + 4 + 2 * dn::P_MAX)));
     }
     if (degnorm_iter > 0 && h->data.n_iter != degnorm_iter) {
-        HIP_TRY(h->data.d_ran.alloc((size_t) h->n * degnorm_iter));
+        DN_TRY(h->data.d_ran.alloc((size_t) h->n * degnorm_iter));
         h->data.n_iter = degnorm_iter;
     }
     return DN_OK;
@@ -1137,11 +1137,11 @@ int dn_init_begin(dn_handle h, const double *reads)
 {
     if (!h || !h->data.d_cov) return fail(DN_E_STATE, "dn_init_begin: nothing uploaded");
     if (!reads) return fail(DN_E_INVALID, "dn_init_begin: null argument");
-    HIP_TRY(hipSetDevice(h->device));
+    DN_TRY(hipSetDevice(h->device));
     const size_t np = (size_t) h->n * h->p;
-    if (!h->data.d_x) HIP_TRY(h->data.d_x.alloc(sizeof(double) * np));
-    HIP_TRY(hipMemcpyAsync(h->data.d_x, reads, sizeof(double) * np, hipMemcpyHostToDevice, h->stream[0]));
-    HIP_TRY(hipStreamSynchronize(h->stream[0]));
+    if (!h->data.d_x) DN_TRY(h->data.d_x.alloc(sizeof(double) * np));
+    DN_TRY(hipMemcpyAsync(h->data.d_x, reads, sizeof(double) * np, hipMemcpyHostToDevice, h->stream[0]));
+    DN_TRY(hipStreamSynchronize(h->stream[0]));
     return DN_OK;
 }
 
@@ -1149,15 +1149,15 @@ int dn_init_partials(dn_handle h, double *partials)
 {
     if (!h || !h->data.d_x) return fail(DN_E_STATE, "dn_init_partials: dn_init_begin has not been called");
     if (!partials) return fail(DN_E_INVALID, "dn_init_partials: null output");
-    HIP_TRY(hipSetDevice(h->device));
+    DN_TRY(hipSetDevice(h->device));
     { const int rc = outer_alloc(h, 0); if (rc != DN_OK) return rc; }
     const int blocks = (int) std::min<int64_t>(OUT_BLOCKS, (h->n + 3) / 4);
     hipLaunchKernelGGL(k_init_partials, dim3(blocks), dim3(256), 0, h->stream[0], h->data.d_est_sums, h->data.d_cov_sums, h->data.d_status, h->data.d_x, h->data.d_part,
                        (int) h->n, (int) h->p);
     hipLaunchKernelGGL(k_outer_reduce, dim3(1), dim3(256), 0, h->stream[0], h->data.d_part, h->data.d_pvec, blocks, (int) h->p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(partials, h->data.d_pvec, sizeof(double) * (size_t) (3 * h->p + 4), hipMemcpyDeviceToHost, h->stream[0]));
-    HIP_TRY(hipStreamSynchronize(h->stream[0]));
+    DN_TRY(hipGetLastError());
+    DN_TRY(hipMemcpyAsync(partials, h->data.d_pvec, sizeof(double) * (size_t) (3 * h->p + 4), hipMemcpyDeviceToHost, h->stream[0]));
+    DN_TRY(hipStreamSynchronize(h->stream[0]));
     return DN_OK;
 }
 
@@ -1165,16 +1165,16 @@ int dn_outer_begin_scaled(dn_handle h, const double *norm, int32_t degnorm_iter)
 {
     if (!h || !h->data.d_x) return fail(DN_E_STATE, "dn_outer_begin_scaled: dn_init_begin has not been called");
     if (!norm || degnorm_iter < 1) return fail(DN_E_INVALID, "dn_outer_begin_scaled: bad argument");
-    HIP_TRY(hipSetDevice(h->device));
+    DN_TRY(hipSetDevice(h->device));
     { const int rc = outer_alloc(h, degnorm_iter); if (rc != DN_OK) return rc; }
     const size_t np = (size_t) h->n * h->p;
     double *d_norm = h->data.d_pvec + (3 * dn::P_MAX + 4) + dn::P_MAX;
-    HIP_TRY(hipMemsetAsync(h->data.d_ran, 0, (size_t) h->n * degnorm_iter, h->stream[0]));
-    HIP_TRY(hipMemcpyAsync(d_norm, norm, sizeof(double) * (size_t) h->p, hipMemcpyHostToDevice, h->stream[0]));
+    DN_TRY(hipMemsetAsync(h->data.d_ran, 0, (size_t) h->n * degnorm_iter, h->stream[0]));
+    DN_TRY(hipMemcpyAsync(d_norm, norm, sizeof(double) * (size_t) h->p, hipMemcpyHostToDevice, h->stream[0]));
     const int blocks = (int) std::min<size_t>(2048, (np + 255) / 256);
     hipLaunchKernelGGL(k_scale_reads, dim3(blocks), dim3(256), 0, h->stream[0], h->data.d_x, d_norm, h->data.d_xw, (long long) np, (int) h->p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(h->stream[0]));
+    DN_TRY(hipGetLastError());
+    DN_TRY(hipStreamSynchronize(h->stream[0]));
     return DN_OK;
 }
 
@@ -1182,12 +1182,12 @@ int dn_outer_begin(dn_handle h, const double *x_weighted, int32_t degnorm_iter)
 {
     if (!h || !h->data.d_cov) return fail(DN_E_STATE, "dn_outer_begin: nothing uploaded");
     if (!x_weighted || degnorm_iter < 1) return fail(DN_E_INVALID, "dn_outer_begin: bad argument");
-    HIP_TRY(hipSetDevice(h->device));
+    DN_TRY(hipSetDevice(h->device));
     const size_t np = (size_t) h->n * h->p;
     { const int rc = outer_alloc(h, degnorm_iter); if (rc != DN_OK) return rc; }
-    HIP_TRY(hipMemsetAsync(h->data.d_ran, 0, (size_t) h->n * degnorm_iter, h->stream[0]));
-    HIP_TRY(hipMemcpyAsync(h->data.d_xw, x_weighted, sizeof(double) * np, hipMemcpyHostToDevice, h->stream[0]));
-    HIP_TRY(hipStreamSynchronize(h->stream[0]));
+    DN_TRY(hipMemsetAsync(h->data.d_ran, 0, (size_t) h->n * degnorm_iter, h->stream[0]));
+    DN_TRY(hipMemcpyAsync(h->data.d_xw, x_weighted, sizeof(double) * np, hipMemcpyHostToDevice, h->stream[0]));
+    DN_TRY(hipStreamSynchronize(h->stream[0]));
     return DN_OK;
 }
 
@@ -1195,14 +1195,14 @@ int dn_outer_partials(dn_handle h, double *partials)
 {
     if (!h || !h->data.d_xw) return fail(DN_E_STATE, "dn_outer_partials: dn_outer_begin has not been called");
     if (!partials) return fail(DN_E_INVALID, "dn_outer_partials: null output");
-    HIP_TRY(hipSetDevice(h->device));
+    DN_TRY(hipSetDevice(h->device));
     const int blocks = (int) std::min<int64_t>(OUT_BLOCKS, (h->n + 3) / 4);
     hipLaunchKernelGGL(k_outer_partials, dim3(blocks), dim3(256), 0, h->stream[0], h->data.d_rho, h->data.d_rhoc, h->data.d_xw, h->data.d_trace, h->data.d_flags, h->data.d_part,
                        (int) h->n, (int) h->p);
     hipLaunchKernelGGL(k_outer_reduce, dim3(1), dim3(256), 0, h->stream[0], h->data.d_part, h->data.d_pvec, blocks, (int) h->p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(partials, h->data.d_pvec, sizeof(double) * (size_t) (3 * h->p + 4), hipMemcpyDeviceToHost, h->stream[0]));
-    HIP_TRY(hipStreamSynchronize(h->stream[0]));
+    DN_TRY(hipGetLastError());
+    DN_TRY(hipMemcpyAsync(partials, h->data.d_pvec, sizeof(double) * (size_t) (3 * h->p + 4), hipMemcpyDeviceToHost, h->stream[0]));
+    DN_TRY(hipStreamSynchronize(h->stream[0]));
     return DN_OK;
 }
 
@@ -1210,13 +1210,13 @@ int dn_outer_partials_device(dn_handle h, double **d_partials)
 {
     if (!h || !h->data.d_xw) return fail(DN_E_STATE, "dn_outer_partials_device: dn_outer_begin has not been called");
     if (!d_partials) return fail(DN_E_INVALID, "dn_outer_partials_device: null output");
-    HIP_TRY(hipSetDevice(h->device));
+    DN_TRY(hipSetDevice(h->device));
     const int blocks = (int) std::min<int64_t>(OUT_BLOCKS, (h->n + 3) / 4);
     hipLaunchKernelGGL(k_outer_partials, dim3(blocks), dim3(256), 0, h->stream[0], h->data.d_rho, h->data.d_rhoc, h->data.d_xw, h->data.d_trace, h->data.d_flags, h->data.d_part,
                        (int) h->n, (int) h->p);
     hipLaunchKernelGGL(k_outer_reduce, dim3(1), dim3(256), 0, h->stream[0], h->data.d_part, h->data.d_pvec, blocks, (int) h->p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(h->stream[0]));           // the collective runs on the caller's stream: the sums must be there
+    DN_TRY(hipGetLastError());
+    DN_TRY(hipStreamSynchronize(h->stream[0]));           // the collective runs on the caller's stream: the sums must be there
     *d_partials = h->data.d_pvec;
     return DN_OK;
 }
@@ -1225,15 +1225,15 @@ int dn_outer_apply(dn_handle h, const double *avg_di, const double *norm, int32_
 {
     if (!h || !h->data.d_xw) return fail(DN_E_STATE, "dn_outer_apply: dn_outer_begin has not been called");
     if (!norm || iter < 0) return fail(DN_E_INVALID, "dn_outer_apply: bad argument");
-    HIP_TRY(hipSetDevice(h->device));
+    DN_TRY(hipSetDevice(h->device));
     double *d_avg = h->data.d_pvec + (3 * dn::P_MAX + 4), *d_norm = d_avg + dn::P_MAX;
-    if (avg_di) HIP_TRY(hipMemcpyAsync(d_avg, avg_di, sizeof(double) * (size_t) h->p, hipMemcpyHostToDevice, h->stream[0]));
-    HIP_TRY(hipMemcpyAsync(d_norm, norm, sizeof(double) * (size_t) h->p, hipMemcpyHostToDevice, h->stream[0]));
+    if (avg_di) DN_TRY(hipMemcpyAsync(d_avg, avg_di, sizeof(double) * (size_t) h->p, hipMemcpyHostToDevice, h->stream[0]));
+    DN_TRY(hipMemcpyAsync(d_norm, norm, sizeof(double) * (size_t) h->p, hipMemcpyHostToDevice, h->stream[0]));
     const int blocks = (int) std::min<int64_t>(OUT_BLOCKS, (h->n + 3) / 4);
     hipLaunchKernelGGL(k_outer_apply, dim3(blocks), dim3(256), 0, h->stream[0], h->data.d_rhoc, h->data.d_xw, h->data.d_xadj, h->data.d_flags, h->data.d_ran, d_avg, d_norm,
                        avg_di ? 1 : 0, (int) h->n, (int) h->p, (int) iter, (int) h->data.n_iter);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(h->stream[0]));           // the host buffers behind avg_di / norm may go away
+    DN_TRY(hipGetLastError());
+    DN_TRY(hipStreamSynchronize(h->stream[0]));           // the host buffers behind avg_di / norm may go away
     return DN_OK;
 }
 
@@ -1269,13 +1269,13 @@ int dn_comm_create(dn_handle h, const uint8_t *id, int32_t rank, int32_t size)
     std::string err;
     RcclApi *api = rccl_api(err);
     if (!api) return fail(DN_E_STATE, "dn_comm_create: " + err);
-    HIP_TRY(hipSetDevice(h->device));
+    DN_TRY(hipSetDevice(h->device));
     ncclUniqueId u;
     memcpy(&u, id, sizeof(u));
     ncclComm_t c = nullptr;
     RCCL_TRY(api, api->CommInitRank(&c, size, u, rank));
     h->comm = c; h->comm_rank = rank; h->comm_size = size;
-    if (!h->d_comm) HIP_TRY(h->d_comm.alloc(sizeof(double) * 256));
+    if (!h->d_comm) DN_TRY(h->d_comm.alloc(sizeof(double) * 256));
     return DN_OK;
 }
 
@@ -1313,8 +1313,8 @@ static int allreduce_to_host(dn_handle h, double *d_buf, int32_t count, double *
     RcclApi *api = rccl_api(err);
     if (!api) return fail(DN_E_STATE, err);
     RCCL_TRY(api, api->AllReduce(d_buf, d_buf, (size_t) count, ncclDouble, ncclSum, (ncclComm_t) h->comm, h->stream[0]));
-    HIP_TRY(hipMemcpyAsync(totals, d_buf, sizeof(double) * (size_t) count, hipMemcpyDeviceToHost, h->stream[0]));
-    HIP_TRY(hipStreamSynchronize(h->stream[0]));
+    DN_TRY(hipMemcpyAsync(totals, d_buf, sizeof(double) * (size_t) count, hipMemcpyDeviceToHost, h->stream[0]));
+    DN_TRY(hipStreamSynchronize(h->stream[0]));
     return DN_OK;
 }
 
@@ -1322,8 +1322,8 @@ int dn_comm_allreduce(dn_handle h, double *buf, int32_t count)
 {
     if (!h || !h->comm) return fail(DN_E_STATE, "dn_comm_allreduce: dn_comm_create has not been called");
     if (!buf || count < 1 || count > 256) return fail(DN_E_INVALID, "dn_comm_allreduce: 1 .. 256 doubles");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipMemcpyAsync(h->d_comm, buf, sizeof(double) * (size_t) count, hipMemcpyHostToDevice, h->stream[0]));
+    DN_TRY(hipSetDevice(h->device));
+    DN_TRY(hipMemcpyAsync(h->d_comm, buf, sizeof(double) * (size_t) count, hipMemcpyHostToDevice, h->stream[0]));
     return allreduce_to_host(h, h->d_comm, count, buf);
 }
 
@@ -1332,13 +1332,13 @@ int dn_init_allreduce(dn_handle h, double *totals)
     if (!h || !h->comm) return fail(DN_E_STATE, "dn_init_allreduce: dn_comm_create has not been called");
     if (!h->data.d_x) return fail(DN_E_STATE, "dn_init_allreduce: dn_init_begin has not been called");
     if (!totals) return fail(DN_E_INVALID, "dn_init_allreduce: null output");
-    HIP_TRY(hipSetDevice(h->device));
+    DN_TRY(hipSetDevice(h->device));
     { const int rc = outer_alloc(h, 0); if (rc != DN_OK) return rc; }
     const int blocks = (int) std::min<int64_t>(OUT_BLOCKS, (h->n + 3) / 4);
     hipLaunchKernelGGL(k_init_partials, dim3(blocks), dim3(256), 0, h->stream[0], h->data.d_est_sums, h->data.d_cov_sums, h->data.d_status, h->data.d_x, h->data.d_part,
                        (int) h->n, (int) h->p);
     hipLaunchKernelGGL(k_outer_reduce, dim3(1), dim3(256), 0, h->stream[0], h->data.d_part, h->data.d_pvec, blocks, (int) h->p);
-    HIP_TRY(hipGetLastError());
+    DN_TRY(hipGetLastError());
     return allreduce_to_host(h, h->data.d_pvec, 3 * h->p + 4, totals);
 }
 
@@ -1347,25 +1347,25 @@ int dn_outer_allreduce(dn_handle h, double *totals)
     if (!h || !h->comm) return fail(DN_E_STATE, "dn_outer_allreduce: dn_comm_create has not been called");
     if (!h->data.d_xw) return fail(DN_E_STATE, "dn_outer_allreduce: dn_outer_begin has not been called");
     if (!totals) return fail(DN_E_INVALID, "dn_outer_allreduce: null output");
-    HIP_TRY(hipSetDevice(h->device));
+    DN_TRY(hipSetDevice(h->device));
     const int blocks = (int) std::min<int64_t>(OUT_BLOCKS, (h->n + 3) / 4);
     hipLaunchKernelGGL(k_outer_partials, dim3(blocks), dim3(256), 0, h->stream[0], h->data.d_rho, h->data.d_rhoc, h->data.d_xw, h->data.d_trace, h->data.d_flags, h->data.d_part,
                        (int) h->n, (int) h->p);
     hipLaunchKernelGGL(k_outer_reduce, dim3(1), dim3(256), 0, h->stream[0], h->data.d_part, h->data.d_pvec, blocks, (int) h->p);
-    HIP_TRY(hipGetLastError());
+    DN_TRY(hipGetLastError());
     return allreduce_to_host(h, h->data.d_pvec, 3 * h->p + 4, totals);
 }
 
 int dn_fetch_outer(dn_handle h, double *rho, double *x_adj, double *x_weighted, uint8_t *ran)
 {
     if (!h || !h->data.d_xw) return fail(DN_E_STATE, "dn_fetch_outer: dn_outer_begin has not been called");
-    HIP_TRY(hipSetDevice(h->device));
+    DN_TRY(hipSetDevice(h->device));
     const size_t np = (size_t) h->n * h->p;
-    if (rho) HIP_TRY(hipMemcpyAsync(rho, h->data.d_rhoc, sizeof(double) * np, hipMemcpyDeviceToHost, h->stream[0]));
-    if (x_adj) HIP_TRY(hipMemcpyAsync(x_adj, h->data.d_xadj, sizeof(double) * np, hipMemcpyDeviceToHost, h->stream[0]));
-    if (x_weighted) HIP_TRY(hipMemcpyAsync(x_weighted, h->data.d_xw, sizeof(double) * np, hipMemcpyDeviceToHost, h->stream[0]));
-    if (ran) HIP_TRY(hipMemcpyAsync(ran, h->data.d_ran, (size_t) h->n * h->data.n_iter, hipMemcpyDeviceToHost, h->stream[0]));
-    HIP_TRY(hipStreamSynchronize(h->stream[0]));
+    if (rho) DN_TRY(hipMemcpyAsync(rho, h->data.d_rhoc, sizeof(double) * np, hipMemcpyDeviceToHost, h->stream[0]));
+    if (x_adj) DN_TRY(hipMemcpyAsync(x_adj, h->data.d_xadj, sizeof(double) * np, hipMemcpyDeviceToHost, h->stream[0]));
+    if (x_weighted) DN_TRY(hipMemcpyAsync(x_weighted, h->data.d_xw, sizeof(double) * np, hipMemcpyDeviceToHost, h->stream[0]));
+    if (ran) DN_TRY(hipMemcpyAsync(ran, h->data.d_ran, (size_t) h->n * h->data.n_iter, hipMemcpyDeviceToHost, h->stream[0]));
+    DN_TRY(hipStreamSynchronize(h->stream[0]));
     return DN_OK;
 }
 
@@ -1374,21 +1374,21 @@ int dn_fetch_rows(dn_handle h, int64_t n_rows, const int64_t *rows, double *rho_
     if (!h || !h->data.d_cov) return fail(DN_E_STATE, "dn_fetch_rows: nothing uploaded");
     if (n_rows <= 0 || !rows || !rho_raw || !flags) return fail(DN_E_INVALID, "dn_fetch_rows: bad argument");
     for (int64_t k = 0; k < n_rows; k++) if (rows[k] < 0 || rows[k] >= h->n) return fail(DN_E_INVALID, "dn_fetch_rows: row out of range");
-    HIP_TRY(hipSetDevice(h->device));
+    DN_TRY(hipSetDevice(h->device));
     const char *what = "dn_fetch_rows";
     dn::DeviceBuffer<int64_t> d_rows;
     dn::DeviceBuffer<double> d_out;
     dn::DeviceBuffer<int32_t> d_fl;
-    HIP_TRY(d_rows.alloc(sizeof(int64_t) * (size_t) n_rows));
-    HIP_TRY_AS(what, d_out.alloc(sizeof(double) * (size_t) n_rows * h->p));
-    HIP_TRY_AS(what, d_fl.alloc(sizeof(int32_t) * (size_t) n_rows));
-    HIP_TRY_AS(what, hipMemcpyAsync(d_rows, rows, sizeof(int64_t) * (size_t) n_rows, hipMemcpyHostToDevice, h->stream[0]));
+    DN_TRY(d_rows.alloc(sizeof(int64_t) * (size_t) n_rows));
+    DN_TRY_AS(what, d_out.alloc(sizeof(double) * (size_t) n_rows * h->p));
+    DN_TRY_AS(what, d_fl.alloc(sizeof(int32_t) * (size_t) n_rows));
+    DN_TRY_AS(what, hipMemcpyAsync(d_rows, rows, sizeof(int64_t) * (size_t) n_rows, hipMemcpyHostToDevice, h->stream[0]));
     const int tot = (int) (n_rows * h->p);
     hipLaunchKernelGGL(k_gather_rows, dim3((tot + 255) / 256), dim3(256), 0, h->stream[0], h->data.d_rho, h->data.d_flags, d_rows, d_out, d_fl, (int) n_rows, (int) h->p);
-    HIP_TRY_AS(what, hipGetLastError());
-    HIP_TRY_AS(what, hipMemcpyAsync(rho_raw, d_out, sizeof(double) * (size_t) n_rows * h->p, hipMemcpyDeviceToHost, h->stream[0]));
-    HIP_TRY_AS(what, hipMemcpyAsync(flags, d_fl, sizeof(int32_t) * (size_t) n_rows, hipMemcpyDeviceToHost, h->stream[0]));
-    HIP_TRY_AS(what, hipStreamSynchronize(h->stream[0]));
+    DN_TRY_AS(what, hipGetLastError());
+    DN_TRY_AS(what, hipMemcpyAsync(rho_raw, d_out, sizeof(double) * (size_t) n_rows * h->p, hipMemcpyDeviceToHost, h->stream[0]));
+    DN_TRY_AS(what, hipMemcpyAsync(flags, d_fl, sizeof(int32_t) * (size_t) n_rows, hipMemcpyDeviceToHost, h->stream[0]));
+    DN_TRY_AS(what, hipStreamSynchronize(h->stream[0]));
     return DN_OK;
 }
 
@@ -1415,18 +1415,18 @@ int dn_fetch_estimates(dn_handle h, double *out)
     if (!h || !h->data.d_cov) return fail(DN_E_STATE, "dn_fetch_estimates: nothing uploaded");
     if (!h->data.have_estimate_state) return fail(DN_E_STATE, "dn_fetch_estimates: last iteration did not run with want_estimates = 1");
     if (!out) return fail(DN_E_INVALID, "dn_fetch_estimates: null output");
-    HIP_TRY(hipSetDevice(h->device));
-    if (!h->data.d_est) HIP_TRY(h->data.d_est.alloc(sizeof(double) * (size_t) h->total));
+    DN_TRY(hipSetDevice(h->device));
+    if (!h->data.d_est) DN_TRY(h->data.d_est.alloc(sizeof(double) * (size_t) h->total));
     dn::EstArgs a;
     std::memset(&a, 0, sizeof(a));
     a.cov = h->data.d_cov; a.goff = h->data.d_goff; a.glen = h->data.d_glen; a.kfin = h->data.d_kfin; a.emode = h->data.d_emode;
     a.svec = h->data.d_svec; a.svoff = h->data.d_svoff; a.out = h->data.d_est; a.n_genes = (int32_t) h->n; a.p = h->p;
     for (int i = 0; i < dn::P_MAX; i++) a.scale[i] = i < h->p ? h->last_scale[i] : 1.0;
     h->ks->est(a, h->data.d_tile_gene, h->data.d_tile_col, (int) h->n_tiles, h->stream[0]);
-    HIP_TRY(hipGetLastError());
+    DN_TRY(hipGetLastError());
     prefault_pages(out, sizeof(double) * (size_t) h->total, (int) std::thread::hardware_concurrency());     // while the kernel runs
-    HIP_TRY(hipMemcpyAsync(out, h->data.d_est, sizeof(double) * (size_t) h->total, hipMemcpyDeviceToHost, h->stream[0]));
-    HIP_TRY(hipStreamSynchronize(h->stream[0]));
+    DN_TRY(hipMemcpyAsync(out, h->data.d_est, sizeof(double) * (size_t) h->total, hipMemcpyDeviceToHost, h->stream[0]));
+    DN_TRY(hipStreamSynchronize(h->stream[0]));
     return DN_OK;
 }
 
@@ -1435,7 +1435,7 @@ int dn_fetch_estimates_subset(dn_handle h, int64_t n_sel, const int64_t *gene_id
     if (!h || !h->data.d_cov) return fail(DN_E_STATE, "dn_fetch_estimates_subset: nothing uploaded");
     if (!h->data.have_estimate_state) return fail(DN_E_STATE, "dn_fetch_estimates_subset: last iteration did not run with want_estimates = 1");
     if (n_sel <= 0 || !gene_ids || !out) return fail(DN_E_INVALID, "dn_fetch_estimates_subset: bad argument");
-    HIP_TRY(hipSetDevice(h->device));
+    DN_TRY(hipSetDevice(h->device));
     std::vector<int64_t> ooff(h->n, -1);
     std::vector<int32_t> tg, tc;
     int64_t total = 0;
@@ -1451,22 +1451,22 @@ int dn_fetch_estimates_subset(dn_handle h, int64_t n_sel, const int64_t *gene_id
     dn::DeviceBuffer<double> d_out;
     dn::DeviceBuffer<int64_t> d_ooff;
     dn::DeviceBuffer<int32_t> d_tg, d_tc;
-    HIP_TRY_AS(what, d_out.alloc(sizeof(double) * (size_t) total));
-    HIP_TRY_AS(what, d_ooff.alloc(sizeof(int64_t) * (size_t) h->n));
-    HIP_TRY_AS(what, d_tg.alloc(sizeof(int32_t) * tg.size()));
-    HIP_TRY_AS(what, d_tc.alloc(sizeof(int32_t) * tc.size()));
-    HIP_TRY_AS(what, hipMemcpyAsync(d_ooff, ooff.data(), sizeof(int64_t) * (size_t) h->n, hipMemcpyHostToDevice, h->stream[0]));
-    HIP_TRY_AS(what, hipMemcpyAsync(d_tg, tg.data(), sizeof(int32_t) * tg.size(), hipMemcpyHostToDevice, h->stream[0]));
-    HIP_TRY_AS(what, hipMemcpyAsync(d_tc, tc.data(), sizeof(int32_t) * tc.size(), hipMemcpyHostToDevice, h->stream[0]));
+    DN_TRY_AS(what, d_out.alloc(sizeof(double) * (size_t) total));
+    DN_TRY_AS(what, d_ooff.alloc(sizeof(int64_t) * (size_t) h->n));
+    DN_TRY_AS(what, d_tg.alloc(sizeof(int32_t) * tg.size()));
+    DN_TRY_AS(what, d_tc.alloc(sizeof(int32_t) * tc.size()));
+    DN_TRY_AS(what, hipMemcpyAsync(d_ooff, ooff.data(), sizeof(int64_t) * (size_t) h->n, hipMemcpyHostToDevice, h->stream[0]));
+    DN_TRY_AS(what, hipMemcpyAsync(d_tg, tg.data(), sizeof(int32_t) * tg.size(), hipMemcpyHostToDevice, h->stream[0]));
+    DN_TRY_AS(what, hipMemcpyAsync(d_tc, tc.data(), sizeof(int32_t) * tc.size(), hipMemcpyHostToDevice, h->stream[0]));
     dn::EstArgs a;
     std::memset(&a, 0, sizeof(a));
     a.cov = h->data.d_cov; a.goff = h->data.d_goff; a.glen = h->data.d_glen; a.kfin = h->data.d_kfin; a.emode = h->data.d_emode;
     a.svec = h->data.d_svec; a.svoff = h->data.d_svoff; a.out = d_out; a.ooff = d_ooff; a.n_genes = (int32_t) h->n; a.p = h->p;
     for (int i = 0; i < dn::P_MAX; i++) a.scale[i] = i < h->p ? h->last_scale[i] : 1.0;
     h->ks->est(a, d_tg, d_tc, (int) tg.size(), h->stream[0]);
-    HIP_TRY_AS(what, hipGetLastError());
-    HIP_TRY_AS(what, hipMemcpyAsync(out, d_out, sizeof(double) * (size_t) total, hipMemcpyDeviceToHost, h->stream[0]));
-    HIP_TRY_AS(what, hipStreamSynchronize(h->stream[0]));
+    DN_TRY_AS(what, hipGetLastError());
+    DN_TRY_AS(what, hipMemcpyAsync(out, d_out, sizeof(double) * (size_t) total, hipMemcpyDeviceToHost, h->stream[0]));
+    DN_TRY_AS(what, hipStreamSynchronize(h->stream[0]));
     return DN_OK;
 }
 
@@ -1479,7 +1479,7 @@ int dn_nmf_f64(dn_handle h, int64_t n, int32_t p, const double *const *x, const 
     if (!K || !E || !status) return fail(DN_E_INVALID, "dn_nmf_f64: null output");
     if (mode != DN_NMF_RANK_ONE && mode != DN_NMF && mode != DN_NMF_RATIO) return fail(DN_E_INVALID, "dn_nmf_f64: unknown mode");
     if (mode == DN_NMF && nmf_iter < 0) return fail(DN_E_INVALID, "dn_nmf_f64: nmf_iter must be >= 0");
-    HIP_TRY(hipSetDevice(h->device));
+    DN_TRY(hipSetDevice(h->device));
     std::vector<int64_t> xoff(n), eoff(n + 1, 0);
     std::vector<int32_t> ncol(n);
     int64_t maxn = 0;
@@ -1507,39 +1507,39 @@ int dn_nmf_f64(dn_handle h, int64_t n, int32_t p, const double *const *x, const 
     dn::DeviceBuffer<int32_t> d_ncol, d_order, d_counter, d_status;
     dn::DeviceBuffer<char> d_ws;
     dn::Event e0, e1;
-    HIP_TRY(alloc_f64(d_x, (size_t) total));
-    HIP_TRY(alloc_f64(d_xoff, (size_t) n));
-    HIP_TRY(alloc_f64(d_eoff, (size_t) n));
-    HIP_TRY(alloc_f64(d_ncol, (size_t) n));
-    HIP_TRY(alloc_f64(d_order, (size_t) n));
-    HIP_TRY(alloc_f64(d_counter, 4));
-    HIP_TRY(alloc_f64(d_status, (size_t) n));
-    HIP_TRY(alloc_f64(d_K, (size_t) n * p));
-    HIP_TRY(alloc_f64(d_E, (size_t) eoff[n]));
-    if (est) HIP_TRY(alloc_f64(d_est, (size_t) total));
-    HIP_TRY(alloc_f64(d_ws, (size_t) slot_bytes * (size_t) grid));
-    HIP_TRY(e0.create(hipEventCreate));
-    HIP_TRY(e1.create(hipEventCreate));
-    HIP_TRY(hipMemcpyAsync(d_x, packed.data(), sizeof(double) * (size_t) total, hipMemcpyHostToDevice, h->stream[0]));
-    HIP_TRY(hipMemcpyAsync(d_xoff, xoff.data(), sizeof(int64_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
-    HIP_TRY(hipMemcpyAsync(d_eoff, eoff.data(), sizeof(int64_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
-    HIP_TRY(hipMemcpyAsync(d_ncol, ncol.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
-    HIP_TRY(hipMemcpyAsync(d_order, order.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
-    HIP_TRY(hipMemsetAsync(d_counter, 0, sizeof(int32_t) * 4, h->stream[0]));
+    DN_TRY(alloc_f64(d_x, (size_t) total));
+    DN_TRY(alloc_f64(d_xoff, (size_t) n));
+    DN_TRY(alloc_f64(d_eoff, (size_t) n));
+    DN_TRY(alloc_f64(d_ncol, (size_t) n));
+    DN_TRY(alloc_f64(d_order, (size_t) n));
+    DN_TRY(alloc_f64(d_counter, 4));
+    DN_TRY(alloc_f64(d_status, (size_t) n));
+    DN_TRY(alloc_f64(d_K, (size_t) n * p));
+    DN_TRY(alloc_f64(d_E, (size_t) eoff[n]));
+    if (est) DN_TRY(alloc_f64(d_est, (size_t) total));
+    DN_TRY(alloc_f64(d_ws, (size_t) slot_bytes * (size_t) grid));
+    DN_TRY(e0.create(hipEventCreate));
+    DN_TRY(e1.create(hipEventCreate));
+    DN_TRY(hipMemcpyAsync(d_x, packed.data(), sizeof(double) * (size_t) total, hipMemcpyHostToDevice, h->stream[0]));
+    DN_TRY(hipMemcpyAsync(d_xoff, xoff.data(), sizeof(int64_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
+    DN_TRY(hipMemcpyAsync(d_eoff, eoff.data(), sizeof(int64_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
+    DN_TRY(hipMemcpyAsync(d_ncol, ncol.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
+    DN_TRY(hipMemcpyAsync(d_order, order.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
+    DN_TRY(hipMemsetAsync(d_counter, 0, sizeof(int32_t) * 4, h->stream[0]));
     a.x = d_x; a.xoff = d_xoff; a.ncol = d_ncol; a.eoff = d_eoff; a.order = d_order; a.counter = d_counter;
     a.K = d_K; a.E = d_E; a.est = d_est; a.status = d_status; a.ws = d_ws; a.slot_bytes = slot_bytes;
     a.n = (int32_t) n; a.p = p; a.T = mode == DN_NMF ? nmf_iter : 0; a.ratio = mode == DN_NMF_RATIO ? 1 : 0;
     a.max_steps = h->max_steps;
-    HIP_TRY(hipEventRecord(e0, h->stream[0]));
+    DN_TRY(hipEventRecord(e0, h->stream[0]));
     const int lrc = dn::launch_nmf_f64(a, grid, h->stream[0]);
     if (lrc != 0) return fail(DN_E_HIP, std::string("k_nmf_f64 launch: ") + hipGetErrorString((hipError_t) lrc));
-    HIP_TRY(hipEventRecord(e1, h->stream[0]));
-    HIP_TRY(hipMemcpyAsync(K, d_K, sizeof(double) * (size_t) n * p, hipMemcpyDeviceToHost, h->stream[0]));
-    HIP_TRY(hipMemcpyAsync(E, d_E, sizeof(double) * (size_t) eoff[n], hipMemcpyDeviceToHost, h->stream[0]));
-    HIP_TRY(hipMemcpyAsync(status, d_status, sizeof(int32_t) * (size_t) n, hipMemcpyDeviceToHost, h->stream[0]));
-    if (est) HIP_TRY(hipMemcpyAsync(est, d_est, sizeof(double) * (size_t) total, hipMemcpyDeviceToHost, h->stream[0]));
-    HIP_TRY(hipStreamSynchronize(h->stream[0]));
-    HIP_TRY(hipEventElapsedTime(&h->last_f64_ms, e0, e1));
+    DN_TRY(hipEventRecord(e1, h->stream[0]));
+    DN_TRY(hipMemcpyAsync(K, d_K, sizeof(double) * (size_t) n * p, hipMemcpyDeviceToHost, h->stream[0]));
+    DN_TRY(hipMemcpyAsync(E, d_E, sizeof(double) * (size_t) eoff[n], hipMemcpyDeviceToHost, h->stream[0]));
+    DN_TRY(hipMemcpyAsync(status, d_status, sizeof(int32_t) * (size_t) n, hipMemcpyDeviceToHost, h->stream[0]));
+    if (est) DN_TRY(hipMemcpyAsync(est, d_est, sizeof(double) * (size_t) total, hipMemcpyDeviceToHost, h->stream[0]));
+    DN_TRY(hipStreamSynchronize(h->stream[0]));
+    DN_TRY(hipEventElapsedTime(&h->last_f64_ms, e0, e1));
     return DN_OK;
 }
 
@@ -1561,7 +1561,7 @@ int dn_baseline_selection_f64(dn_handle h, int64_t n, int32_t p, const double *c
             if (ds_start[g] < 0 || ds_start[g] >= prm->downsample_rate) return fail(DN_E_INVALID, "ds_start out of [0, rate)");
         }
     }
-    HIP_TRY(hipSetDevice(h->device));
+    DN_TRY(hipSetDevice(h->device));
     std::vector<int64_t> goff(n + 1, 0), svoff(n + 1, 0);
     std::vector<int32_t> glen(n);
     int64_t maxl = 0;
@@ -1593,41 +1593,41 @@ int dn_baseline_selection_f64(dn_handle h, int64_t n, int32_t p, const double *c
     dn::DeviceBuffer<int32_t> d_tg, d_tc;
     dn::DeviceBuffer<char> d_ws;
     dn::Event e0, e1;
-    HIP_TRY(alloc_f64(d_cov, (size_t) total));
-    HIP_TRY(alloc_f64(d_goff, (size_t) n + 1));
-    HIP_TRY(alloc_f64(d_glen, (size_t) n));
-    HIP_TRY(alloc_f64(d_order, (size_t) n));
-    HIP_TRY(alloc_f64(d_counter, 4));
-    HIP_TRY(alloc_f64(d_rowmax, (size_t) n * p));
-    HIP_TRY(alloc_f64(d_rho, (size_t) n * p));
-    HIP_TRY(alloc_f64(d_flags, (size_t) n));
-    HIP_TRY(alloc_f64(d_trace, (size_t) n * dn::TRACE_LEN));
-    HIP_TRY(alloc_f64(d_kfin, (size_t) n * p));
-    HIP_TRY(alloc_f64(d_emode, (size_t) n));
-    HIP_TRY(alloc_f64(d_ws, (size_t) slot_bytes * (size_t) grid));
-    if (prm->downsample_rate > 1) HIP_TRY(alloc_f64(d_ds, (size_t) n));
+    DN_TRY(alloc_f64(d_cov, (size_t) total));
+    DN_TRY(alloc_f64(d_goff, (size_t) n + 1));
+    DN_TRY(alloc_f64(d_glen, (size_t) n));
+    DN_TRY(alloc_f64(d_order, (size_t) n));
+    DN_TRY(alloc_f64(d_counter, 4));
+    DN_TRY(alloc_f64(d_rowmax, (size_t) n * p));
+    DN_TRY(alloc_f64(d_rho, (size_t) n * p));
+    DN_TRY(alloc_f64(d_flags, (size_t) n));
+    DN_TRY(alloc_f64(d_trace, (size_t) n * dn::TRACE_LEN));
+    DN_TRY(alloc_f64(d_kfin, (size_t) n * p));
+    DN_TRY(alloc_f64(d_emode, (size_t) n));
+    DN_TRY(alloc_f64(d_ws, (size_t) slot_bytes * (size_t) grid));
+    if (prm->downsample_rate > 1) DN_TRY(alloc_f64(d_ds, (size_t) n));
     if (est) {
-        HIP_TRY(alloc_f64(d_svoff, (size_t) n + 1));
-        HIP_TRY(alloc_f64(d_svec, (size_t) svoff[n]));
-        HIP_TRY(alloc_f64(d_est, (size_t) total));
-        HIP_TRY(alloc_f64(d_tg, tg.size()));
-        HIP_TRY(alloc_f64(d_tc, tc.size()));
+        DN_TRY(alloc_f64(d_svoff, (size_t) n + 1));
+        DN_TRY(alloc_f64(d_svec, (size_t) svoff[n]));
+        DN_TRY(alloc_f64(d_est, (size_t) total));
+        DN_TRY(alloc_f64(d_tg, tg.size()));
+        DN_TRY(alloc_f64(d_tc, tc.size()));
     }
-    HIP_TRY(e0.create(hipEventCreate));
-    HIP_TRY(e1.create(hipEventCreate));
-    HIP_TRY(hipMemcpyAsync(d_cov, packed.data(), sizeof(double) * (size_t) total, hipMemcpyHostToDevice, h->stream[0]));
-    HIP_TRY(hipMemcpyAsync(d_goff, goff.data(), sizeof(int64_t) * (size_t) (n + 1), hipMemcpyHostToDevice, h->stream[0]));
-    HIP_TRY(hipMemcpyAsync(d_glen, glen.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
-    HIP_TRY(hipMemcpyAsync(d_order, order.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
-    HIP_TRY(hipMemsetAsync(d_counter, 0, sizeof(int32_t) * 4, h->stream[0]));
-    HIP_TRY(hipMemsetAsync(d_trace, 0, sizeof(int32_t) * (size_t) n * dn::TRACE_LEN, h->stream[0]));
-    if (d_ds) HIP_TRY(hipMemcpyAsync(d_ds, ds_start, sizeof(int64_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
+    DN_TRY(e0.create(hipEventCreate));
+    DN_TRY(e1.create(hipEventCreate));
+    DN_TRY(hipMemcpyAsync(d_cov, packed.data(), sizeof(double) * (size_t) total, hipMemcpyHostToDevice, h->stream[0]));
+    DN_TRY(hipMemcpyAsync(d_goff, goff.data(), sizeof(int64_t) * (size_t) (n + 1), hipMemcpyHostToDevice, h->stream[0]));
+    DN_TRY(hipMemcpyAsync(d_glen, glen.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
+    DN_TRY(hipMemcpyAsync(d_order, order.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
+    DN_TRY(hipMemsetAsync(d_counter, 0, sizeof(int32_t) * 4, h->stream[0]));
+    DN_TRY(hipMemsetAsync(d_trace, 0, sizeof(int32_t) * (size_t) n * dn::TRACE_LEN, h->stream[0]));
+    if (d_ds) DN_TRY(hipMemcpyAsync(d_ds, ds_start, sizeof(int64_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
     if (est) {
-        HIP_TRY(hipMemcpyAsync(d_svoff, svoff.data(), sizeof(int64_t) * (size_t) (n + 1), hipMemcpyHostToDevice, h->stream[0]));
-        HIP_TRY(hipMemcpyAsync(d_tg, tg.data(), sizeof(int32_t) * tg.size(), hipMemcpyHostToDevice, h->stream[0]));
-        HIP_TRY(hipMemcpyAsync(d_tc, tc.data(), sizeof(int32_t) * tc.size(), hipMemcpyHostToDevice, h->stream[0]));
+        DN_TRY(hipMemcpyAsync(d_svoff, svoff.data(), sizeof(int64_t) * (size_t) (n + 1), hipMemcpyHostToDevice, h->stream[0]));
+        DN_TRY(hipMemcpyAsync(d_tg, tg.data(), sizeof(int32_t) * tg.size(), hipMemcpyHostToDevice, h->stream[0]));
+        DN_TRY(hipMemcpyAsync(d_tc, tc.data(), sizeof(int32_t) * tc.size(), hipMemcpyHostToDevice, h->stream[0]));
     }
-    HIP_TRY(hipEventRecord(e0, h->stream[0]));
+    DN_TRY(hipEventRecord(e0, h->stream[0]));
     int lrc = dn::launch_row_max_f64(d_cov, d_goff, d_glen, d_rowmax, (int) n, p,
                                      (int) std::min<int64_t>(n, (int64_t) h->n_cus * 8), h->stream[0]);
     if (lrc != 0) return fail(DN_E_HIP, std::string("k_row_max_f64 launch: ") + hipGetErrorString((hipError_t) lrc));
@@ -1651,13 +1651,13 @@ int dn_baseline_selection_f64(dn_handle h, int64_t n, int32_t p, const double *c
         lrc = dn::launch_est_f64(e, d_tg, d_tc, (int) tg.size(), h->stream[0]);
         if (lrc != 0) return fail(DN_E_HIP, std::string("k_estimates_gen (float64) launch: ") + hipGetErrorString((hipError_t) lrc));
     }
-    HIP_TRY(hipEventRecord(e1, h->stream[0]));
-    HIP_TRY(hipMemcpyAsync(rho, d_rho, sizeof(double) * (size_t) n * p, hipMemcpyDeviceToHost, h->stream[0]));
-    HIP_TRY(hipMemcpyAsync(flags, d_flags, sizeof(int32_t) * (size_t) n, hipMemcpyDeviceToHost, h->stream[0]));
-    if (trace) HIP_TRY(hipMemcpyAsync(trace, d_trace, sizeof(int32_t) * (size_t) n * dn::TRACE_LEN, hipMemcpyDeviceToHost, h->stream[0]));
-    if (est) HIP_TRY(hipMemcpyAsync(est, d_est, sizeof(double) * (size_t) total, hipMemcpyDeviceToHost, h->stream[0]));
-    HIP_TRY(hipStreamSynchronize(h->stream[0]));
-    HIP_TRY(hipEventElapsedTime(&h->last_f64_ms, e0, e1));
+    DN_TRY(hipEventRecord(e1, h->stream[0]));
+    DN_TRY(hipMemcpyAsync(rho, d_rho, sizeof(double) * (size_t) n * p, hipMemcpyDeviceToHost, h->stream[0]));
+    DN_TRY(hipMemcpyAsync(flags, d_flags, sizeof(int32_t) * (size_t) n, hipMemcpyDeviceToHost, h->stream[0]));
+    if (trace) DN_TRY(hipMemcpyAsync(trace, d_trace, sizeof(int32_t) * (size_t) n * dn::TRACE_LEN, hipMemcpyDeviceToHost, h->stream[0]));
+    if (est) DN_TRY(hipMemcpyAsync(est, d_est, sizeof(double) * (size_t) total, hipMemcpyDeviceToHost, h->stream[0]));
+    DN_TRY(hipStreamSynchronize(h->stream[0]));
+    DN_TRY(hipEventElapsedTime(&h->last_f64_ms, e0, e1));
     return DN_OK;
 }
 
@@ -1686,7 +1686,7 @@ int dn_class_lengths(dn_handle h, int32_t p, int32_t downsample_rate, int32_t *s
     if (!h || !split_len || !tiny_len) return fail(DN_E_INVALID, "dn_class_lengths: null argument");
     const dn::KernelSet *ks = dn::kernel_set_for(p);
     if (!ks) return fail(DN_E_UNSUPPORTED, "no kernels compiled for p = " + std::to_string(p));
-    HIP_TRY(hipSetDevice(h->device));
+    DN_TRY(hipSetDevice(h->device));
     *split_len = 0; *tiny_len = 0;
     if (downsample_rate > 1 && p >= 8) return DN_OK;        // the one-wavefront-per-gene family of the down-sampled regime has one class
     const dn::KernelSet *pair = nullptr;
@@ -1697,8 +1697,8 @@ int32_t dn_split_length(dn_handle h) { return h ? h->split_len : 0; }
 int dn_synchronize(dn_handle h)
 {
     if (!h) return fail(DN_E_INVALID, "null handle");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream[0]));
+    DN_TRY(hipSetDevice(h->device));
+    DN_TRY(hipStreamSynchronize(h->stream[0]));
     return DN_OK;
 }
 

@@ -7,7 +7,7 @@
 // (gene g at p * sum(lengths[:g]), p rows of lengths[g]).  No float64 host dictionary is needed on the way to HBM.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <string>
+#include <vector>
 #include "../../include/degnorm_amd.h"
 #include "dn_host.hpp"
 
@@ -35,17 +35,7 @@ __global__ __launch_bounds__(256) void k_gather_intervals(const float *__restric
     }
 }
 
-thread_local std::string g_asm_err;
-
 }  // namespace
-
-#define ASM_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) { g_asm_err = std::string(#expr) + ": " + hipGetErrorString(e_); rc = DN_E_HIP; goto done; } \
-    } while (0)
-
-extern "C" const char *dn_assemble_last_error(void) { return g_asm_err.c_str(); }
 
 extern "C" int dn_assemble_coverage(int device, int64_t chrom_len, int32_t p, const int64_t *nnz,
                                     const int32_t *const *indices, const float *const *values,
@@ -54,67 +44,59 @@ extern "C" int dn_assemble_coverage(int device, int64_t chrom_len, int32_t p, co
                                     const int64_t *chunk_dst_in_gene, const int32_t *chunk_len,
                                     float *out_packed, double *device_ms)
 {
-    int rc = DN_OK;
+    if (chrom_len <= 0 || p < 1 || n_genes < 1 || !lengths || !out_packed || n_chunks < 0) return dn::fail(DN_E_INVALID, "dn_assemble_coverage: bad argument");
+    // absolute destination of every chunk for sample 0; sample i adds i * L_gene
+    std::vector<int64_t> goff((size_t) n_genes + 1, 0);
+    for (int64_t g = 0; g < n_genes; g++) goff[g + 1] = goff[g] + (int64_t) p * lengths[g];
+    const int64_t total = goff[n_genes], chunk_cap = n_chunks > 0 ? n_chunks : 1;
+    std::vector<int64_t> cdst((size_t) chunk_cap), cd((size_t) chunk_cap);
+    for (int64_t c = 0; c < n_chunks; c++) cdst[c] = goff[chunk_gene[c]] + chunk_dst_in_gene[c];
+    int64_t max_nnz = 1;
+    for (int i = 0; i < p; i++) if (nnz[i] > max_nnz) max_nnz = nnz[i];
+
     dn::Stream st;
     dn::Event e0, e1;
     dn::DeviceBuffer<float> d_dense, d_out, d_val;
     dn::DeviceBuffer<int32_t> d_idx, d_clen;
     dn::DeviceBuffer<int64_t> d_csrc, d_cdst;
-    int64_t total = 0, max_nnz = 1;
-    if (chrom_len <= 0 || p < 1 || n_genes < 1 || !lengths || !out_packed || n_chunks < 0) { g_asm_err = "dn_assemble_coverage: bad argument"; return DN_E_INVALID; }
-    {
-        std::string offs_err;
-        // absolute destination of every chunk for sample 0; sample i adds i * L_gene
-        int64_t *goff = new int64_t[n_genes + 1];
-        goff[0] = 0;
-        for (int64_t g = 0; g < n_genes; g++) goff[g + 1] = goff[g] + (int64_t) p * lengths[g];
-        total = goff[n_genes];
-        int64_t *cdst = new int64_t[n_chunks > 0 ? n_chunks : 1];
-        for (int64_t c = 0; c < n_chunks; c++) cdst[c] = goff[chunk_gene[c]] + chunk_dst_in_gene[c];
-        for (int i = 0; i < p; i++) if (nnz[i] > max_nnz) max_nnz = nnz[i];
-
-        ASM_TRY(hipSetDevice(device));
-        ASM_TRY(st.create(hipStreamCreate));
-        ASM_TRY(e0.create(hipEventCreate));
-        ASM_TRY(e1.create(hipEventCreate));
-        ASM_TRY(d_dense.alloc(sizeof(float) * (size_t) chrom_len));
-        ASM_TRY(d_out.alloc(sizeof(float) * (size_t) (total > 0 ? total : 1)));
-        ASM_TRY(d_idx.alloc(sizeof(int32_t) * (size_t) max_nnz));
-        ASM_TRY(d_val.alloc(sizeof(float) * (size_t) max_nnz));
-        ASM_TRY(d_csrc.alloc(sizeof(int64_t) * (size_t) (n_chunks > 0 ? n_chunks : 1)));
-        ASM_TRY(d_cdst.alloc(sizeof(int64_t) * (size_t) (n_chunks > 0 ? n_chunks : 1)));
-        ASM_TRY(d_clen.alloc(sizeof(int32_t) * (size_t) (n_chunks > 0 ? n_chunks : 1)));
+    DN_TRY(hipSetDevice(device));
+    DN_TRY(st.create(hipStreamCreate));
+    return dn::synced(st, [&]() -> int {
+        DN_TRY(e0.create(hipEventCreate));
+        DN_TRY(e1.create(hipEventCreate));
+        DN_TRY(d_dense.alloc(sizeof(float) * (size_t) chrom_len));
+        DN_TRY(d_out.alloc(sizeof(float) * (size_t) (total > 0 ? total : 1)));
+        DN_TRY(d_idx.alloc(sizeof(int32_t) * (size_t) max_nnz));
+        DN_TRY(d_val.alloc(sizeof(float) * (size_t) max_nnz));
+        DN_TRY(d_csrc.alloc(sizeof(int64_t) * (size_t) (n_chunks > 0 ? n_chunks : 1)));
+        DN_TRY(d_cdst.alloc(sizeof(int64_t) * (size_t) (n_chunks > 0 ? n_chunks : 1)));
+        DN_TRY(d_clen.alloc(sizeof(int32_t) * (size_t) (n_chunks > 0 ? n_chunks : 1)));
         if (n_chunks > 0) {
-            ASM_TRY(hipMemcpyAsync(d_csrc, chunk_src, sizeof(int64_t) * (size_t) n_chunks, hipMemcpyHostToDevice, st));
-            ASM_TRY(hipMemcpyAsync(d_clen, chunk_len, sizeof(int32_t) * (size_t) n_chunks, hipMemcpyHostToDevice, st));
+            DN_TRY(hipMemcpyAsync(d_csrc, chunk_src, sizeof(int64_t) * (size_t) n_chunks, hipMemcpyHostToDevice, st));
+            DN_TRY(hipMemcpyAsync(d_clen, chunk_len, sizeof(int32_t) * (size_t) n_chunks, hipMemcpyHostToDevice, st));
         }
-        ASM_TRY(hipEventRecord(e0, st));
+        DN_TRY(hipEventRecord(e0, st));
         for (int i = 0; i < p; i++) {
-            // per-sample destinations: row i of every gene
-            int64_t *cd = new int64_t[n_chunks > 0 ? n_chunks : 1];
+            // per-sample destinations: row i of every gene (cd is rewritten only after the stream has read it)
             for (int64_t c = 0; c < n_chunks; c++) cd[c] = cdst[c] + (int64_t) i * lengths[chunk_gene[c]];
-            hipError_t ee = n_chunks > 0 ? hipMemcpyAsync(d_cdst, cd, sizeof(int64_t) * (size_t) n_chunks, hipMemcpyHostToDevice, st) : hipSuccess;
+            hipError_t ee = n_chunks > 0 ? hipMemcpyAsync(d_cdst, cd.data(), sizeof(int64_t) * (size_t) n_chunks, hipMemcpyHostToDevice, st) : hipSuccess;
             if (ee == hipSuccess) ee = hipStreamSynchronize(st);
-            delete[] cd;
-            ASM_TRY(ee);
-            ASM_TRY(hipMemsetAsync(d_dense, 0, sizeof(float) * (size_t) chrom_len, st));        // missing file: all zeros (reference :309-316)
+            DN_TRY(ee);
+            DN_TRY(hipMemsetAsync(d_dense, 0, sizeof(float) * (size_t) chrom_len, st));        // missing file: all zeros (reference :309-316)
             if (nnz[i] > 0) {
-                ASM_TRY(hipMemcpyAsync(d_idx, indices[i], sizeof(int32_t) * (size_t) nnz[i], hipMemcpyHostToDevice, st));
-                ASM_TRY(hipMemcpyAsync(d_val, values[i], sizeof(float) * (size_t) nnz[i], hipMemcpyHostToDevice, st));
+                DN_TRY(hipMemcpyAsync(d_idx, indices[i], sizeof(int32_t) * (size_t) nnz[i], hipMemcpyHostToDevice, st));
+                DN_TRY(hipMemcpyAsync(d_val, values[i], sizeof(float) * (size_t) nnz[i], hipMemcpyHostToDevice, st));
                 const int grid = (int) ((nnz[i] + 255) / 256 < 65536 ? (nnz[i] + 255) / 256 : 65536);
                 hipLaunchKernelGGL(k_scatter_csr, dim3(grid), dim3(256), 0, st, d_idx, d_val, nnz[i], d_dense, chrom_len);
             }
             if (n_chunks > 0)
                 hipLaunchKernelGGL(k_gather_intervals, dim3((unsigned) n_chunks), dim3(256), 0, st, d_dense, chrom_len, d_csrc, d_cdst, d_clen, d_out);
-            ASM_TRY(hipGetLastError());
+            DN_TRY(hipGetLastError());
         }
-        ASM_TRY(hipEventRecord(e1, st));
-        ASM_TRY(hipMemcpyAsync(out_packed, d_out, sizeof(float) * (size_t) total, hipMemcpyDeviceToHost, st));
-        ASM_TRY(hipStreamSynchronize(st));
-        if (device_ms) { float ms = 0.f; ASM_TRY(hipEventElapsedTime(&ms, e0, e1)); *device_ms = ms; }
-    done:
-        delete[] goff;
-        delete[] cdst;
-    }
-    return rc;
+        DN_TRY(hipEventRecord(e1, st));
+        DN_TRY(hipMemcpyAsync(out_packed, d_out, sizeof(float) * (size_t) total, hipMemcpyDeviceToHost, st));
+        DN_TRY(hipStreamSynchronize(st));
+        if (device_ms) { float ms = 0.f; DN_TRY(hipEventElapsedTime(&ms, e0, e1)); *device_ms = ms; }
+        return DN_OK;
+    });
 }

@@ -305,26 +305,21 @@ struct TableBuffers {
     Table view() const { return Table{line, chr_beg, start, end, gene_beg, chr_len, gene_len, chr_hash, gene_hash}; }
 };
 
-thread_local std::string g_gtf_err;
-
 inline unsigned grid_capped(int64_t n) { return (unsigned) (n < 1 ? 1 : n > 2048 ? 2048 : n); }
 
 }  // namespace
-
-#define GTF_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) { g_gtf_err = std::string(#expr) + ": " + hipGetErrorString(e_); rc = DN_E_HIP; goto done; } \
-    } while (0)
-
-extern "C" const char *dn_gtf_last_error(void) { return g_gtf_err.c_str(); }
 
 extern "C" int dn_gtf_scan(int device, const uint8_t *buf, int64_t n_bytes, int64_t row_cap, int64_t *n_lines, int64_t *n_rows,
                            int64_t *line, int64_t *chr_beg, int32_t *chr_len, uint64_t *chr_hash, int64_t *start, int64_t *end,
                            int64_t *gene_beg, int32_t *gene_len, uint64_t *gene_hash, int64_t *err_line, int32_t *err_kind,
                            double *copy_ms, double *device_ms)
 {
-    int rc = DN_OK;
+    if (!buf || n_bytes < 1 || row_cap < 0 || !n_lines || !n_rows || !line || !chr_beg || !chr_len || !chr_hash || !start || !end
+        || !gene_beg || !gene_len || !gene_hash || !err_line || !err_kind)
+        return dn::fail(DN_E_INVALID, "dn_gtf_scan: bad argument");
+    const int64_t n_tiles = (n_bytes + kTile - 1) / kTile, padded = n_tiles * kTile;
+    *n_lines = 0; *n_rows = 0; *err_line = 0; *err_kind = 0;
+    // what the stream reads or writes: owned here, so that it outlives the wait of dn::synced
     dn::Stream st;
     dn::Event e0, e1, e2;
     dn::DeviceBuffer<uint8_t> d_buf, d_keep;
@@ -334,82 +329,73 @@ extern "C" int dn_gtf_scan(int device, const uint8_t *buf, int64_t n_bytes, int6
     TableBuffers rec, row;
     const unsigned long long no_error = ~0ull;
     unsigned long long first_error = no_error;
-    int64_t n_newlines = 0, n_starts = 0, n_blocks = 0, kept = 0;
-    if (!buf || n_bytes < 1 || row_cap < 0 || !n_lines || !n_rows || !line || !chr_beg || !chr_len || !chr_hash || !start || !end
-        || !gene_beg || !gene_len || !gene_hash || !err_line || !err_kind) {
-        g_gtf_err = "dn_gtf_scan: bad argument";
-        return DN_E_INVALID;
-    }
-    {
-        const int64_t n_tiles = (n_bytes + kTile - 1) / kTile, padded = n_tiles * kTile;
-        *n_lines = 0; *n_rows = 0; *err_line = 0; *err_kind = 0;
-        GTF_TRY(hipSetDevice(device));
-        GTF_TRY(st.create(hipStreamCreate));
-        GTF_TRY(e0.create(hipEventCreate));
-        GTF_TRY(e1.create(hipEventCreate));
-        GTF_TRY(e2.create(hipEventCreate));
-        GTF_TRY(d_buf.alloc((size_t) padded));
-        GTF_TRY(d_tile_count.alloc(sizeof(int32_t) * (size_t) n_tiles));
-        GTF_TRY(d_tile_off.alloc(sizeof(int64_t) * (size_t) n_tiles));
-        GTF_TRY(d_total.alloc(sizeof(int64_t)));
-        GTF_TRY(d_err.alloc(sizeof(unsigned long long)));
-        GTF_TRY(hipEventRecord(e0, st));
-        GTF_TRY(hipMemcpyAsync(d_buf, buf, (size_t) n_bytes, hipMemcpyHostToDevice, st));
-        if (padded > n_bytes) GTF_TRY(hipMemsetAsync(d_buf.get() + n_bytes, 0, (size_t) (padded - n_bytes), st));
-        GTF_TRY(hipMemcpyAsync(d_err, &no_error, sizeof(no_error), hipMemcpyHostToDevice, st));
-        GTF_TRY(hipEventRecord(e1, st));
+    int64_t n_newlines = 0, kept = 0;
+    DN_TRY(hipSetDevice(device));
+    DN_TRY(st.create(hipStreamCreate));
+    return dn::synced(st, [&]() -> int {
+        DN_TRY(e0.create(hipEventCreate));
+        DN_TRY(e1.create(hipEventCreate));
+        DN_TRY(e2.create(hipEventCreate));
+        DN_TRY(d_buf.alloc((size_t) padded));
+        DN_TRY(d_tile_count.alloc(sizeof(int32_t) * (size_t) n_tiles));
+        DN_TRY(d_tile_off.alloc(sizeof(int64_t) * (size_t) n_tiles));
+        DN_TRY(d_total.alloc(sizeof(int64_t)));
+        DN_TRY(d_err.alloc(sizeof(unsigned long long)));
+        DN_TRY(hipEventRecord(e0, st));
+        DN_TRY(hipMemcpyAsync(d_buf, buf, (size_t) n_bytes, hipMemcpyHostToDevice, st));
+        if (padded > n_bytes) DN_TRY(hipMemsetAsync(d_buf.get() + n_bytes, 0, (size_t) (padded - n_bytes), st));
+        DN_TRY(hipMemcpyAsync(d_err, &no_error, sizeof(no_error), hipMemcpyHostToDevice, st));
+        DN_TRY(hipEventRecord(e1, st));
 
         hipLaunchKernelGGL(k_count_newlines, dim3(grid_capped(n_tiles)), dim3(kNT), 0, st, (const uint4 *) d_buf.get(), n_tiles, d_tile_count.get());
         hipLaunchKernelGGL(k_scan, dim3(1), dim3(kScanNT), 0, st, d_tile_count.get(), n_tiles, d_tile_off.get(), d_total.get());
-        GTF_TRY(hipGetLastError());
-        GTF_TRY(hipMemcpyAsync(&n_newlines, d_total, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        GTF_TRY(hipStreamSynchronize(st));
-        if (n_newlines < 0 || n_newlines > n_bytes) { g_gtf_err = "dn_gtf_scan: newline count out of range"; rc = DN_E_STATE; goto done; }
+        DN_TRY(hipGetLastError());
+        DN_TRY(hipMemcpyAsync(&n_newlines, d_total, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        DN_TRY(hipStreamSynchronize(st));
+        if (n_newlines < 0 || n_newlines > n_bytes) return dn::fail(DN_E_STATE, "dn_gtf_scan: newline count out of range");
 
-        n_starts = n_newlines + 1;                                     // the last one starts an empty line when the bytes end in '\n'
-        n_blocks = (n_starts + kNT - 1) / kNT;
-        GTF_TRY(d_line_start.alloc(sizeof(int64_t) * (size_t) n_starts));
-        GTF_TRY(d_keep.alloc((size_t) n_starts));
-        GTF_TRY(d_block_kept.alloc(sizeof(int32_t) * (size_t) n_blocks));
-        GTF_TRY(d_block_off.alloc(sizeof(int64_t) * (size_t) n_blocks));
-        GTF_TRY(rec.alloc(n_starts));
-        GTF_TRY(hipMemsetAsync(d_line_start, 0, sizeof(int64_t), st));
+        const int64_t n_starts = n_newlines + 1;                       // the last one starts an empty line when the bytes end in '\n'
+        const int64_t n_blocks = (n_starts + kNT - 1) / kNT;
+        DN_TRY(d_line_start.alloc(sizeof(int64_t) * (size_t) n_starts));
+        DN_TRY(d_keep.alloc((size_t) n_starts));
+        DN_TRY(d_block_kept.alloc(sizeof(int32_t) * (size_t) n_blocks));
+        DN_TRY(d_block_off.alloc(sizeof(int64_t) * (size_t) n_blocks));
+        DN_TRY(rec.alloc(n_starts));
+        DN_TRY(hipMemsetAsync(d_line_start, 0, sizeof(int64_t), st));
         hipLaunchKernelGGL(k_line_starts, dim3(grid_capped(n_tiles)), dim3(kNT), 0, st, (const uint8_t *) d_buf.get(), n_tiles,
                            (const int64_t *) d_tile_off.get(), d_line_start.get(), n_starts);
         hipLaunchKernelGGL(k_parse_lines, dim3((unsigned) n_blocks), dim3(kNT), 0, st, (const uint8_t *) d_buf.get(), n_bytes,
                            (const int64_t *) d_line_start.get(), n_starts, rec.view(), d_keep.get(), d_block_kept.get(), d_err.get());
         hipLaunchKernelGGL(k_scan, dim3(1), dim3(kScanNT), 0, st, d_block_kept.get(), n_blocks, d_block_off.get(), d_total.get());
-        GTF_TRY(hipGetLastError());
-        GTF_TRY(hipMemcpyAsync(&kept, d_total, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        GTF_TRY(hipMemcpyAsync(&first_error, d_err, sizeof(first_error), hipMemcpyDeviceToHost, st));
-        GTF_TRY(hipStreamSynchronize(st));
+        DN_TRY(hipGetLastError());
+        DN_TRY(hipMemcpyAsync(&kept, d_total, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        DN_TRY(hipMemcpyAsync(&first_error, d_err, sizeof(first_error), hipMemcpyDeviceToHost, st));
+        DN_TRY(hipStreamSynchronize(st));
 
         *n_lines = n_newlines + (buf[n_bytes - 1] != '\n' ? 1 : 0);
         if (first_error != no_error) {
             *err_line = (int64_t) (first_error >> 8);
             *err_kind = (int32_t) (first_error & 0xffu);
-            GTF_TRY(hipEventRecord(e2, st));
+            DN_TRY(hipEventRecord(e2, st));
         } else {
-            if (kept < 0 || kept > row_cap) { g_gtf_err = "dn_gtf_scan: more exon lines than the caller's tables hold"; rc = DN_E_INVALID; goto done; }
-            GTF_TRY(row.alloc(kept));
+            if (kept < 0 || kept > row_cap) return dn::fail(DN_E_INVALID, "dn_gtf_scan: more exon lines than the caller's tables hold");
+            DN_TRY(row.alloc(kept));
             if (kept > 0) {
                 hipLaunchKernelGGL(k_compact, dim3((unsigned) n_blocks), dim3(kNT), 0, st, n_starts, (const uint8_t *) d_keep.get(),
                                    (const int64_t *) d_block_off.get(), rec.view(), row.view(), kept);
-                GTF_TRY(hipGetLastError());
+                DN_TRY(hipGetLastError());
             }
-            GTF_TRY(hipEventRecord(e2, st));
-#define GTF_OUT(h, d, T) do { if (kept > 0) GTF_TRY(hipMemcpyAsync(h, d, sizeof(T) * (size_t) kept, hipMemcpyDeviceToHost, st)); } while (0)
+            DN_TRY(hipEventRecord(e2, st));
+#define GTF_OUT(h, d, T) do { if (kept > 0) DN_TRY(hipMemcpyAsync(h, d, sizeof(T) * (size_t) kept, hipMemcpyDeviceToHost, st)); } while (0)
             GTF_OUT(line, row.line, int64_t); GTF_OUT(chr_beg, row.chr_beg, int64_t); GTF_OUT(chr_len, row.chr_len, int32_t);
             GTF_OUT(chr_hash, row.chr_hash, uint64_t); GTF_OUT(start, row.start, int64_t); GTF_OUT(end, row.end, int64_t);
             GTF_OUT(gene_beg, row.gene_beg, int64_t); GTF_OUT(gene_len, row.gene_len, int32_t); GTF_OUT(gene_hash, row.gene_hash, uint64_t);
 #undef GTF_OUT
             *n_rows = kept;
         }
-        GTF_TRY(hipStreamSynchronize(st));
-        if (copy_ms) { float ms = 0.f; GTF_TRY(hipEventElapsedTime(&ms, e0, e1)); *copy_ms = ms; }
-        if (device_ms) { float ms = 0.f; GTF_TRY(hipEventElapsedTime(&ms, e1, e2)); *device_ms = ms; }
-    }
-done:
-    if (st) (void) hipStreamSynchronize(st);
-    return rc;
+        DN_TRY(hipStreamSynchronize(st));
+        if (copy_ms) { float ms = 0.f; DN_TRY(hipEventElapsedTime(&ms, e0, e1)); *copy_ms = ms; }
+        if (device_ms) { float ms = 0.f; DN_TRY(hipEventElapsedTime(&ms, e1, e2)); *device_ms = ms; }
+        return DN_OK;
+    });
 }

@@ -413,7 +413,7 @@ __global__ __launch_bounds__(64) void k_bgzf_inflate(const uint8_t *__restrict__
     if (threadIdx.x == 0) status[b] = rc;
 }
 
-int bad(const std::string &msg) { dn::set_reads_error(msg); return DN_E_INVALID; }
+int bad(const std::string &msg) { return dn::fail(DN_E_INVALID, msg); }
 
 // the checks of both entry points; fills blk (skip 0, keep everything, output at out_off[b])
 int validate(const char *who, const uint8_t *comp, int64_t n_comp, int64_t n_blocks, const int64_t *pay_off, const int32_t *pay_len,
@@ -448,7 +448,7 @@ hipError_t dn::inflate_launch(hipStream_t st, const uint8_t *d_comp, int64_t com
 extern "C" int dn_bgzf_inflate_host(const uint8_t *comp, int64_t n_comp, int64_t n_blocks, const int64_t *pay_off, const int32_t *pay_len,
                                     const int64_t *out_off, uint8_t *out, int32_t *status)
 {
-    dn::set_reads_error("");
+    dn::clear_error();
     std::vector<dn::InflateBlock> blk;
     const int rc = validate("dn_bgzf_inflate_host", comp, n_comp, n_blocks, pay_off, pay_len, out_off, out, status, blk);
     if (rc != DN_OK) return rc;
@@ -462,17 +462,11 @@ extern "C" int dn_bgzf_inflate_host(const uint8_t *comp, int64_t n_comp, int64_t
     return DN_OK;
 }
 
-#define INF_TRY(expr)                                                                                                           \
-    do {                                                                                                                        \
-        hipError_t e_ = (expr);                                                                                                 \
-        if (e_ != hipSuccess) { dn::set_reads_error(std::string(#expr) + ": " + hipGetErrorString(e_)); return DN_E_HIP; }      \
-    } while (0)
-
 extern "C" int dn_bgzf_inflate(int device, const uint8_t *comp, int64_t n_comp, int64_t n_blocks, const int64_t *pay_off,
                                const int32_t *pay_len, const int64_t *out_off, uint8_t *out, int32_t *status, double *copy_ms,
                                double *device_ms)
 {
-    dn::set_reads_error("");
+    dn::clear_error();
     std::vector<dn::InflateBlock> blk;
     const int rc = validate("dn_bgzf_inflate", comp, n_comp, n_blocks, pay_off, pay_len, out_off, out, status, blk);
     if (rc != DN_OK) return rc;
@@ -486,24 +480,26 @@ extern "C" int dn_bgzf_inflate(int device, const uint8_t *comp, int64_t n_comp, 
     dn::DeviceBuffer<uint8_t> d_comp, d_out;
     dn::DeviceBuffer<dn::InflateBlock> d_blk;
     dn::DeviceBuffer<int32_t> d_status;
-    INF_TRY(hipSetDevice(device));
-    INF_TRY(st.create(hipStreamCreate));
-    INF_TRY(e0.create(hipEventCreate)); INF_TRY(e1.create(hipEventCreate)); INF_TRY(e2.create(hipEventCreate));
-    INF_TRY(d_comp.alloc((size_t) cap));
-    INF_TRY(d_out.alloc((size_t) n_out + 16));
-    INF_TRY(d_blk.alloc(sizeof(dn::InflateBlock) * (size_t) n_blocks));
-    INF_TRY(d_status.alloc(sizeof(int32_t) * (size_t) n_blocks));
-    INF_TRY(hipEventRecord(e0, st));
-    if (n_comp > 0) INF_TRY(hipMemcpyAsync(d_comp, comp, (size_t) n_comp, hipMemcpyHostToDevice, st));
-    INF_TRY(hipMemcpyAsync(d_blk, blk.data(), sizeof(dn::InflateBlock) * (size_t) n_blocks, hipMemcpyHostToDevice, st));
-    INF_TRY(hipEventRecord(e1, st));
-    INF_TRY(dn::inflate_launch(st, d_comp, cap, d_blk, n_blocks, d_out, d_status));
-    INF_TRY(hipEventRecord(e2, st));
-    if (n_out > 0) INF_TRY(hipMemcpyAsync(out, d_out, (size_t) n_out, hipMemcpyDeviceToHost, st));
-    INF_TRY(hipMemcpyAsync(status, d_status, sizeof(int32_t) * (size_t) n_blocks, hipMemcpyDeviceToHost, st));
-    INF_TRY(hipStreamSynchronize(st));
-    float ms = 0.f;
-    if (copy_ms) { INF_TRY(hipEventElapsedTime(&ms, e0, e1)); *copy_ms = ms; }
-    if (device_ms) { INF_TRY(hipEventElapsedTime(&ms, e1, e2)); *device_ms = ms; }
-    return DN_OK;
+    DN_TRY(hipSetDevice(device));
+    DN_TRY(st.create(hipStreamCreate));
+    return dn::synced(st, [&]() -> int {
+        DN_TRY(e0.create(hipEventCreate)); DN_TRY(e1.create(hipEventCreate)); DN_TRY(e2.create(hipEventCreate));
+        DN_TRY(d_comp.alloc((size_t) cap));
+        DN_TRY(d_out.alloc((size_t) n_out + 16));
+        DN_TRY(d_blk.alloc(sizeof(dn::InflateBlock) * (size_t) n_blocks));
+        DN_TRY(d_status.alloc(sizeof(int32_t) * (size_t) n_blocks));
+        DN_TRY(hipEventRecord(e0, st));
+        if (n_comp > 0) DN_TRY(hipMemcpyAsync(d_comp, comp, (size_t) n_comp, hipMemcpyHostToDevice, st));
+        DN_TRY(hipMemcpyAsync(d_blk, blk.data(), sizeof(dn::InflateBlock) * (size_t) n_blocks, hipMemcpyHostToDevice, st));
+        DN_TRY(hipEventRecord(e1, st));
+        DN_TRY(dn::inflate_launch(st, d_comp, cap, d_blk, n_blocks, d_out, d_status));
+        DN_TRY(hipEventRecord(e2, st));
+        if (n_out > 0) DN_TRY(hipMemcpyAsync(out, d_out, (size_t) n_out, hipMemcpyDeviceToHost, st));
+        DN_TRY(hipMemcpyAsync(status, d_status, sizeof(int32_t) * (size_t) n_blocks, hipMemcpyDeviceToHost, st));
+        DN_TRY(hipStreamSynchronize(st));
+        float ms = 0.f;
+        if (copy_ms) { DN_TRY(hipEventElapsedTime(&ms, e0, e1)); *copy_ms = ms; }
+        if (device_ms) { DN_TRY(hipEventElapsedTime(&ms, e1, e2)); *device_ms = ms; }
+        return DN_OK;
+    });
 }

@@ -3,8 +3,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <string>
-
 namespace dn {
 
 // One BGZF block of a launch.  Its raw-deflate payload is comp[pay_off .. pay_off + pay_len) and must inflate to exactly
@@ -20,8 +18,5 @@ inline int64_t inflate_comp_cap(int64_t n_comp) { return ((n_comp + 15) & ~(int6
 // one wave per block on stream st; d_status[b] = 0 or DN_INFLATE_E_*.  The arrays were validated by the caller.
 hipError_t inflate_launch(hipStream_t st, const uint8_t *d_comp, int64_t comp_cap, const InflateBlock *d_blk, int64_t n_blocks,
                           uint8_t *d_out, int32_t *d_status);
-
-// the text of dn_reads_last_error() (owned by dn_reads.hip)
-void set_reads_error(const std::string &msg);
 
 }  // namespace dn

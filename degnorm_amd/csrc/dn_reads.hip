@@ -21,6 +21,7 @@
 #include <stdio.h>
 #include <string.h>
 #include <functional>
+#include <memory>
 #include <string>
 #include <vector>
 #include "../../include/degnorm_amd.h"
@@ -327,45 +328,26 @@ struct NonZero {
     __host__ __device__ bool operator()(const int32_t &i) const { return cov[i] != 0; }
 };
 
-thread_local std::string g_reads_err;
-
 inline unsigned grid_for(int64_t n) { const int64_t g = (n + kNT - 1) / kNT; return (unsigned) (g < 1 ? 1 : g > 65536 ? 65536 : g); }
-
-// n elements and 16 bytes of slack
-template <class T> hipError_t alloc_padded(dn::DeviceBuffer<T> &b, size_t n) { return b.alloc(n * sizeof(T) + 16); }
-
-}  // namespace
-
-#define RD_TRY(expr)                                                                          \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) { g_reads_err = std::string(#expr) + ": " + hipGetErrorString(e_); rc = DN_E_HIP; goto done; } \
-    } while (0)
-
-extern "C" const char *dn_reads_last_error(void) { return g_reads_err.c_str(); }
-void dn::set_reads_error(const std::string &msg) { g_reads_err = msg; }
-
-namespace {
 
 // k_cigar_debug on n rows whose CIGARs are already on the device (`cig`); pos and the outputs are host arrays.
 template <class C>
 int cigar_debug(hipStream_t st, int64_t n, const int64_t *pos, C cig, int32_t max_seg, int32_t *nseg, int64_t *bounds, int64_t *end_pos)
 {
-    int rc = DN_OK;
     dn::DeviceBuffer<int64_t> d_pos, d_b, d_end;
     dn::DeviceBuffer<int32_t> d_n;
-    RD_TRY(alloc_padded(d_pos, n)); RD_TRY(alloc_padded(d_n, n)); RD_TRY(alloc_padded(d_b, n * 2 * max_seg)); RD_TRY(alloc_padded(d_end, n));
-    RD_TRY(hipMemcpyAsync(d_pos, pos, sizeof(int64_t) * (size_t) n, hipMemcpyHostToDevice, st));
-    RD_TRY(hipMemsetAsync(d_b, 0, sizeof(int64_t) * (size_t) (n * 2 * max_seg), st));
-    hipLaunchKernelGGL(k_cigar_debug<C>, dim3(grid_for(n)), dim3(kNT), 0, st, n, d_pos, cig, max_seg, d_n, d_b, d_end);
-    RD_TRY(hipGetLastError());
-    RD_TRY(hipMemcpyAsync(nseg, d_n, sizeof(int32_t) * (size_t) n, hipMemcpyDeviceToHost, st));
-    RD_TRY(hipMemcpyAsync(bounds, d_b, sizeof(int64_t) * (size_t) (n * 2 * max_seg), hipMemcpyDeviceToHost, st));
-    RD_TRY(hipMemcpyAsync(end_pos, d_end, sizeof(int64_t) * (size_t) n, hipMemcpyDeviceToHost, st));
-    RD_TRY(hipStreamSynchronize(st));
-done:
-    (void) hipStreamSynchronize(st);
-    return rc;
+    return dn::synced(st, [&]() -> int {
+        DN_TRY(alloc_padded(d_pos, n)); DN_TRY(alloc_padded(d_n, n)); DN_TRY(alloc_padded(d_b, n * 2 * max_seg)); DN_TRY(alloc_padded(d_end, n));
+        DN_TRY(hipMemcpyAsync(d_pos, pos, sizeof(int64_t) * (size_t) n, hipMemcpyHostToDevice, st));
+        DN_TRY(hipMemsetAsync(d_b, 0, sizeof(int64_t) * (size_t) (n * 2 * max_seg), st));
+        hipLaunchKernelGGL(k_cigar_debug<C>, dim3(grid_for(n)), dim3(kNT), 0, st, n, d_pos, cig, max_seg, d_n, d_b, d_end);
+        DN_TRY(hipGetLastError());
+        DN_TRY(hipMemcpyAsync(nseg, d_n, sizeof(int32_t) * (size_t) n, hipMemcpyDeviceToHost, st));
+        DN_TRY(hipMemcpyAsync(bounds, d_b, sizeof(int64_t) * (size_t) (n * 2 * max_seg), hipMemcpyDeviceToHost, st));
+        DN_TRY(hipMemcpyAsync(end_pos, d_end, sizeof(int64_t) * (size_t) n, hipMemcpyDeviceToHost, st));
+        DN_TRY(hipStreamSynchronize(st));
+        return DN_OK;
+    });
 }
 
 // The annotation and the outputs of one coverage call (the arguments of dn_read_coverage after the reads).
@@ -388,176 +370,151 @@ template <class C>
 int coverage_stages(hipStream_t st, int32_t paired, int64_t n_rows, const int64_t *d_pos, C cig, const int32_t *pair_id,
                     int64_t n_pair_ids, const CoverageIO &io, const std::function<std::string(int64_t)> &cigar_text)
 {
-    int rc = DN_OK;
     const int64_t chrom_len = io.chrom_len, n_exon = io.n_exon, n_groups = io.n_groups, n_iso = io.n_iso, n_iso_union = io.n_iso_union,
                   n_genes = io.n_genes, csr_cap = io.csr_cap;
     if (n_rows < 0 || n_rows > INT32_MAX - 1 || chrom_len <= 0 || chrom_len > INT32_MAX - 4 || n_exon < 0 || n_groups < 0 || n_iso < 0 || n_iso_union < 0 ||
         n_genes < 0 || !io.counts || !io.nnz || !io.n_isolated_reads || (paired && n_rows > 0 && (!pair_id || n_pair_ids < 1)) ||
         (n_groups > 0 && (!io.group_iv || !io.group_gene_off || !io.ol_cov || !io.ol_cov_off)) ||
-        (n_iso > 0 && (!io.iso_iv || !io.iso_gene || !io.iso_union)) || csr_cap < 0 || (csr_cap > 0 && (!io.csr_idx || !io.csr_val))) {
-        g_reads_err = "dn_read_coverage: bad argument";
-        return DN_E_INVALID;
-    }
+        (n_iso > 0 && (!io.iso_iv || !io.iso_gene || !io.iso_union)) || csr_cap < 0 || (csr_cap > 0 && (!io.csr_idx || !io.csr_val)))
+        return dn::fail(DN_E_INVALID, "dn_read_coverage: bad argument");
     if (paired)
         for (int64_t r = 0; r < n_rows; r++)
-            if (pair_id[r] < 0 || pair_id[r] >= n_pair_ids) { g_reads_err = "dn_read_coverage: pair id out of range"; return DN_E_INVALID; }
+            if (pair_id[r] < 0 || pair_id[r] >= n_pair_ids) return dn::fail(DN_E_INVALID, "dn_read_coverage: pair id out of range");
     const int32_t *group_gene_off = io.group_gene_off, *ol_gene = io.ol_gene, *ol_exon_off = io.ol_exon_off, *iso_gene = io.iso_gene;
     const int64_t *ol_cov_off = io.ol_cov_off, *exon_iv = io.exon_iv;
     const int64_t n_ol = n_groups > 0 ? group_gene_off[n_groups] : 0;
     const int64_t ol_total = n_ol > 0 ? ol_cov_off[n_ol] : 0;
     // every index the kernels follow stays inside its array
     for (int64_t g = 0; g < n_groups; g++)
-        if (group_gene_off[g] < 0 || group_gene_off[g + 1] < group_gene_off[g]) { g_reads_err = "dn_read_coverage: bad group_gene_off"; return DN_E_INVALID; }
+        if (group_gene_off[g] < 0 || group_gene_off[g + 1] < group_gene_off[g]) return dn::fail(DN_E_INVALID, "dn_read_coverage: bad group_gene_off");
     for (int64_t q = 0; q < n_ol; q++)
         if (ol_gene[q] < 0 || ol_gene[q] >= n_genes || ol_cov_off[q + 1] - ol_cov_off[q] < 2 || ol_exon_off[q + 1] < ol_exon_off[q] ||
-            (q == 0 && (ol_cov_off[0] != 0 || ol_exon_off[0] != 0))) { g_reads_err = "dn_read_coverage: bad overlap-gene tables"; return DN_E_INVALID; }
+            (q == 0 && (ol_cov_off[0] != 0 || ol_exon_off[0] != 0))) return dn::fail(DN_E_INVALID, "dn_read_coverage: bad overlap-gene tables");
     for (int64_t k = 0; k < n_iso; k++)
-        if (iso_gene[k] < 0 || iso_gene[k] >= n_genes) { g_reads_err = "dn_read_coverage: bad iso_gene"; return DN_E_INVALID; }
+        if (iso_gene[k] < 0 || iso_gene[k] >= n_genes) return dn::fail(DN_E_INVALID, "dn_read_coverage: bad iso_gene");
     for (int64_t k = 0; k < n_exon; k++)
-        if (exon_iv[2 * k] < 0 || exon_iv[2 * k + 1] >= chrom_len) { g_reads_err = "dn_read_coverage: exon union outside the chromosome"; return DN_E_INVALID; }
+        if (exon_iv[2 * k] < 0 || exon_iv[2 * k + 1] >= chrom_len) return dn::fail(DN_E_INVALID, "dn_read_coverage: exon union outside the chromosome");
     const int64_t n_ol_exon = n_ol > 0 ? ol_exon_off[n_ol] : 0;
     dn::DeviceBuffer<int64_t> d_end, d_exon, d_giv, d_gs0, d_coff, d_oex, d_iiv, d_iu;
     dn::DeviceBuffer<int64_t> d_val64, d_csr_val;
     dn::DeviceBuffer<int32_t> d_pid, d_pcnt, d_rank, d_rows, d_keep, d_ggo, d_olg, d_oxo, d_ig, d_csr_idx;
     dn::DeviceBuffer<int> d_counts, d_oldiff, d_olcov, d_cdiff, d_ccov, d_nsel;
     dn::DeviceBuffer<unsigned long long> d_niso, d_err;
-    std::vector<dn::DeviceBuffer<uint8_t>> tmp;     // scan / select scratch: a larger one is added when a call needs more
-    void *d_tmp = nullptr;                           // the latest of them
+    dn::Scratch scratch;                             // of the scans and the select
     dn::Event e0, e1;
-    size_t tmp_bytes = 0, need = 0;
-    int64_t n_units = 0;
-    unsigned long long h_err[3], h_niso = 0;
+    unsigned long long h_err[3], h_niso = 0;         // what the stream copies to the host
     int h_nsel = 0;
     int32_t survivors = 0;
     std::vector<int> h_counts(n_genes > 0 ? n_genes : 1);
-
-    RD_TRY(e0.create(hipEventCreate));
-    RD_TRY(e1.create(hipEventCreate));
-    RD_TRY(alloc_padded(d_end, n_rows)); RD_TRY(alloc_padded(d_keep, n_rows + 1));
-    RD_TRY(alloc_padded(d_exon, 2 * n_exon)); RD_TRY(alloc_padded(d_giv, 2 * n_groups)); RD_TRY(alloc_padded(d_ggo, n_groups + 1));
-    RD_TRY(alloc_padded(d_olg, n_ol)); RD_TRY(alloc_padded(d_gs0, n_ol)); RD_TRY(alloc_padded(d_coff, n_ol + 1));
-    RD_TRY(alloc_padded(d_oxo, n_ol + 1)); RD_TRY(alloc_padded(d_oex, 2 * n_ol_exon));
-    RD_TRY(alloc_padded(d_iiv, 2 * n_iso)); RD_TRY(alloc_padded(d_ig, n_iso)); RD_TRY(alloc_padded(d_iu, 2 * n_iso_union));
-    RD_TRY(alloc_padded(d_counts, n_genes)); RD_TRY(alloc_padded(d_oldiff, ol_total)); RD_TRY(alloc_padded(d_olcov, ol_total));
-    RD_TRY(alloc_padded(d_val64, ol_total));
-    RD_TRY(alloc_padded(d_cdiff, chrom_len + 1)); RD_TRY(alloc_padded(d_ccov, chrom_len + 1));
-    RD_TRY(alloc_padded(d_csr_idx, chrom_len)); RD_TRY(alloc_padded(d_csr_val, chrom_len)); RD_TRY(alloc_padded(d_nsel, 1));
-    RD_TRY(alloc_padded(d_niso, 1)); RD_TRY(alloc_padded(d_err, 3));
-    if (paired) {
-        RD_TRY(alloc_padded(d_pid, n_rows)); RD_TRY(alloc_padded(d_pcnt, n_pair_ids)); RD_TRY(alloc_padded(d_rank, n_rows + 1));
-        RD_TRY(alloc_padded(d_rows, n_rows));
-    }
-#define H2D(d, h, n) do { if ((n) > 0) RD_TRY(hipMemcpyAsync(d, h, sizeof(*(d)) * (size_t) (n), hipMemcpyHostToDevice, st)); } while (0)
-    H2D(d_exon, exon_iv, 2 * n_exon); H2D(d_giv, io.group_iv, 2 * n_groups); H2D(d_ggo, group_gene_off, n_groups > 0 ? n_groups + 1 : 0);
-    H2D(d_olg, ol_gene, n_ol); H2D(d_gs0, io.ol_gene_start0, n_ol); H2D(d_coff, ol_cov_off, n_ol > 0 ? n_ol + 1 : 0);
-    H2D(d_oxo, ol_exon_off, n_ol > 0 ? n_ol + 1 : 0); H2D(d_oex, io.ol_exon_bounds, 2 * n_ol_exon);
-    H2D(d_iiv, io.iso_iv, 2 * n_iso); H2D(d_ig, iso_gene, n_iso); H2D(d_iu, io.iso_union, 2 * n_iso_union);
-    if (paired) H2D(d_pid, pair_id, n_rows);
-#undef H2D
-    RD_TRY(hipEventRecord(e0, st));
-    RD_TRY(hipMemsetAsync(d_counts, 0, sizeof(int) * (size_t) (n_genes > 0 ? n_genes : 1), st));
-    RD_TRY(hipMemsetAsync(d_oldiff, 0, sizeof(int) * (size_t) (ol_total > 0 ? ol_total : 1), st));
-    RD_TRY(hipMemsetAsync(d_cdiff, 0, sizeof(int) * (size_t) (chrom_len + 1), st));
-    RD_TRY(hipMemsetAsync(d_niso, 0, sizeof(unsigned long long), st));
-    RD_TRY(hipMemsetAsync(d_err, 0xff, 3 * sizeof(unsigned long long), st));
-    if (paired) RD_TRY(hipMemsetAsync(d_pcnt, 0, sizeof(int32_t) * (size_t) n_pair_ids, st));
-    if (n_rows > 0) {
-        hipLaunchKernelGGL(k_prefilter<C>, dim3(grid_for(n_rows)), dim3(kNT), 0, st, n_rows, d_pos, cig, io.keep_lo, io.keep_hi,
-                           paired ? d_pid.get() : (const int32_t *) nullptr, d_pcnt, d_end, d_keep);
-        RD_TRY(hipGetLastError());
-        n_units = n_rows;
+    return dn::synced(st, [&]() -> int {
+        DN_TRY(e0.create(hipEventCreate));
+        DN_TRY(e1.create(hipEventCreate));
+        DN_TRY(alloc_padded(d_end, n_rows)); DN_TRY(alloc_padded(d_keep, n_rows + 1));
+        DN_TRY(alloc_padded(d_exon, 2 * n_exon)); DN_TRY(alloc_padded(d_giv, 2 * n_groups)); DN_TRY(alloc_padded(d_ggo, n_groups + 1));
+        DN_TRY(alloc_padded(d_olg, n_ol)); DN_TRY(alloc_padded(d_gs0, n_ol)); DN_TRY(alloc_padded(d_coff, n_ol + 1));
+        DN_TRY(alloc_padded(d_oxo, n_ol + 1)); DN_TRY(alloc_padded(d_oex, 2 * n_ol_exon));
+        DN_TRY(alloc_padded(d_iiv, 2 * n_iso)); DN_TRY(alloc_padded(d_ig, n_iso)); DN_TRY(alloc_padded(d_iu, 2 * n_iso_union));
+        DN_TRY(alloc_padded(d_counts, n_genes)); DN_TRY(alloc_padded(d_oldiff, ol_total)); DN_TRY(alloc_padded(d_olcov, ol_total));
+        DN_TRY(alloc_padded(d_val64, ol_total));
+        DN_TRY(alloc_padded(d_cdiff, chrom_len + 1)); DN_TRY(alloc_padded(d_ccov, chrom_len + 1));
+        DN_TRY(alloc_padded(d_csr_idx, chrom_len)); DN_TRY(alloc_padded(d_csr_val, chrom_len)); DN_TRY(alloc_padded(d_nsel, 1));
+        DN_TRY(alloc_padded(d_niso, 1)); DN_TRY(alloc_padded(d_err, 3));
         if (paired) {
-            hipLaunchKernelGGL(k_pair_flag, dim3(grid_for(n_rows)), dim3(kNT), 0, st, n_rows, d_pid, d_pcnt, d_keep);
-            RD_TRY(hipGetLastError());
-            // exclusive rank of every surviving row; rank[n_rows] is the number of survivors
-            RD_TRY(hipMemsetAsync(d_keep + n_rows, 0, sizeof(int32_t), st));       // keep[n_rows] = 0: rank[n_rows] = #survivors
-            RD_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, d_keep.get(), d_rank.get(), (int) n_rows + 1, st));
-            if (need > tmp_bytes) { tmp.emplace_back(); RD_TRY(alloc_padded(tmp.back(), need)); d_tmp = tmp.back(); tmp_bytes = need; }
-            RD_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, need, d_keep.get(), d_rank.get(), (int) n_rows + 1, st));
-            hipLaunchKernelGGL(k_pair_compact, dim3(grid_for(n_rows)), dim3(kNT), 0, st, n_rows, d_keep, d_rank, d_rows);
-            RD_TRY(hipGetLastError());
-            RD_TRY(hipMemcpyAsync(&survivors, d_rank + n_rows, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-            RD_TRY(hipStreamSynchronize(st));
-            n_units = survivors / 2;
+            DN_TRY(alloc_padded(d_pid, n_rows)); DN_TRY(alloc_padded(d_pcnt, n_pair_ids)); DN_TRY(alloc_padded(d_rank, n_rows + 1));
+            DN_TRY(alloc_padded(d_rows, n_rows));
         }
-        if (n_units > 0) {
-            ReadsArgs<C> A;
-            A.paired = paired; A.n_units = n_units; A.pos = d_pos; A.end_pos = d_end; A.cig = cig;
-            A.keep = d_keep; A.rows = d_rows;
-            A.n_exon = n_exon; A.exon_iv = d_exon; A.n_groups = n_groups; A.group_iv = d_giv; A.group_gene_off = d_ggo;
-            A.ol_gene = d_olg; A.ol_gstart0 = d_gs0; A.ol_cov_off = d_coff; A.ol_exon_off = d_oxo; A.ol_exon = d_oex;
-            A.n_iso = n_iso; A.iso_iv = d_iiv; A.iso_gene = d_ig; A.n_iso_union = n_iso_union; A.iso_union = d_iu;
-            A.counts = d_counts; A.ol_diff = d_oldiff; A.chrom_diff = d_cdiff; A.n_iso_reads = d_niso; A.err = d_err;
-            hipLaunchKernelGGL(k_reads<C>, dim3(grid_for(n_units)), dim3(kNT), 0, st, A);
-            RD_TRY(hipGetLastError());
+#define H2D(d, h, n) do { if ((n) > 0) DN_TRY(hipMemcpyAsync(d, h, sizeof(*(d)) * (size_t) (n), hipMemcpyHostToDevice, st)); } while (0)
+        H2D(d_exon, exon_iv, 2 * n_exon); H2D(d_giv, io.group_iv, 2 * n_groups); H2D(d_ggo, group_gene_off, n_groups > 0 ? n_groups + 1 : 0);
+        H2D(d_olg, ol_gene, n_ol); H2D(d_gs0, io.ol_gene_start0, n_ol); H2D(d_coff, ol_cov_off, n_ol > 0 ? n_ol + 1 : 0);
+        H2D(d_oxo, ol_exon_off, n_ol > 0 ? n_ol + 1 : 0); H2D(d_oex, io.ol_exon_bounds, 2 * n_ol_exon);
+        H2D(d_iiv, io.iso_iv, 2 * n_iso); H2D(d_ig, iso_gene, n_iso); H2D(d_iu, io.iso_union, 2 * n_iso_union);
+        if (paired) H2D(d_pid, pair_id, n_rows);
+#undef H2D
+        DN_TRY(hipEventRecord(e0, st));
+        DN_TRY(hipMemsetAsync(d_counts, 0, sizeof(int) * (size_t) (n_genes > 0 ? n_genes : 1), st));
+        DN_TRY(hipMemsetAsync(d_oldiff, 0, sizeof(int) * (size_t) (ol_total > 0 ? ol_total : 1), st));
+        DN_TRY(hipMemsetAsync(d_cdiff, 0, sizeof(int) * (size_t) (chrom_len + 1), st));
+        DN_TRY(hipMemsetAsync(d_niso, 0, sizeof(unsigned long long), st));
+        DN_TRY(hipMemsetAsync(d_err, 0xff, 3 * sizeof(unsigned long long), st));
+        if (paired) DN_TRY(hipMemsetAsync(d_pcnt, 0, sizeof(int32_t) * (size_t) n_pair_ids, st));
+        if (n_rows > 0) {
+            hipLaunchKernelGGL(k_prefilter<C>, dim3(grid_for(n_rows)), dim3(kNT), 0, st, n_rows, d_pos, cig, io.keep_lo, io.keep_hi,
+                               paired ? d_pid.get() : (const int32_t *) nullptr, d_pcnt, d_end, d_keep);
+            DN_TRY(hipGetLastError());
+            int64_t n_units = n_rows;
+            if (paired) {
+                hipLaunchKernelGGL(k_pair_flag, dim3(grid_for(n_rows)), dim3(kNT), 0, st, n_rows, d_pid, d_pcnt, d_keep);
+                DN_TRY(hipGetLastError());
+                // exclusive rank of every surviving row; rank[n_rows] is the number of survivors
+                DN_TRY(hipMemsetAsync(d_keep + n_rows, 0, sizeof(int32_t), st));       // keep[n_rows] = 0: rank[n_rows] = #survivors
+                DN_TRY(scratch.run([&](void *tmp, size_t &bytes) {
+                    return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, d_keep.get(), d_rank.get(), (int) n_rows + 1, st);
+                }));
+                hipLaunchKernelGGL(k_pair_compact, dim3(grid_for(n_rows)), dim3(kNT), 0, st, n_rows, d_keep, d_rank, d_rows);
+                DN_TRY(hipGetLastError());
+                DN_TRY(hipMemcpyAsync(&survivors, d_rank + n_rows, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+                DN_TRY(hipStreamSynchronize(st));
+                n_units = survivors / 2;
+            }
+            if (n_units > 0) {
+                ReadsArgs<C> A;
+                A.paired = paired; A.n_units = n_units; A.pos = d_pos; A.end_pos = d_end; A.cig = cig;
+                A.keep = d_keep; A.rows = d_rows;
+                A.n_exon = n_exon; A.exon_iv = d_exon; A.n_groups = n_groups; A.group_iv = d_giv; A.group_gene_off = d_ggo;
+                A.ol_gene = d_olg; A.ol_gstart0 = d_gs0; A.ol_cov_off = d_coff; A.ol_exon_off = d_oxo; A.ol_exon = d_oex;
+                A.n_iso = n_iso; A.iso_iv = d_iiv; A.iso_gene = d_ig; A.n_iso_union = n_iso_union; A.iso_union = d_iu;
+                A.counts = d_counts; A.ol_diff = d_oldiff; A.chrom_diff = d_cdiff; A.n_iso_reads = d_niso; A.err = d_err;
+                hipLaunchKernelGGL(k_reads<C>, dim3(grid_for(n_units)), dim3(kNT), 0, st, A);
+                DN_TRY(hipGetLastError());
+            }
         }
-    }
-    // difference arrays -> coverage
-    need = 0;
-    RD_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, need, d_cdiff.get(), d_ccov.get(), (int) chrom_len, st));
-    if (need > tmp_bytes) { tmp.emplace_back(); RD_TRY(alloc_padded(tmp.back(), need)); d_tmp = tmp.back(); tmp_bytes = need; }
-    RD_TRY(hipcub::DeviceScan::InclusiveSum(d_tmp, need, d_cdiff.get(), d_ccov.get(), (int) chrom_len, st));
-    if (ol_total > 0) {
-        need = 0;
-        RD_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, need, d_oldiff.get(), d_olcov.get(), (int) ol_total, st));
-        if (need > tmp_bytes) { tmp.emplace_back(); RD_TRY(alloc_padded(tmp.back(), need)); d_tmp = tmp.back(); tmp_bytes = need; }
-        RD_TRY(hipcub::DeviceScan::InclusiveSum(d_tmp, need, d_oldiff.get(), d_olcov.get(), (int) ol_total, st));
-        hipLaunchKernelGGL(k_widen, dim3(grid_for(ol_total)), dim3(kNT), 0, st, ol_total, d_olcov, d_val64);
-        RD_TRY(hipGetLastError());
-    }
-    // chromosome vector -> CSR (positions ascending)
-    {
-        hipcub::CountingInputIterator<int32_t> ids(0);
-        NonZero nz{d_ccov.get()};
-        need = 0;
-        RD_TRY(hipcub::DeviceSelect::If(nullptr, need, ids, d_csr_idx.get(), d_nsel.get(), (int) chrom_len, nz, st));
-        if (need > tmp_bytes) { tmp.emplace_back(); RD_TRY(alloc_padded(tmp.back(), need)); d_tmp = tmp.back(); tmp_bytes = need; }
-        RD_TRY(hipcub::DeviceSelect::If(d_tmp, need, ids, d_csr_idx.get(), d_nsel.get(), (int) chrom_len, nz, st));
-    }
-    RD_TRY(hipMemcpyAsync(&h_nsel, d_nsel, sizeof(int), hipMemcpyDeviceToHost, st));
-    RD_TRY(hipMemcpyAsync(h_err, d_err, sizeof(h_err), hipMemcpyDeviceToHost, st));
-    RD_TRY(hipMemcpyAsync(&h_niso, d_niso, sizeof(h_niso), hipMemcpyDeviceToHost, st));
-    RD_TRY(hipStreamSynchronize(st));
-    if (h_nsel > 0) {
-        hipLaunchKernelGGL(k_gather_csr, dim3(grid_for(h_nsel)), dim3(kNT), 0, st, (int64_t) h_nsel, d_csr_idx, d_ccov, d_csr_val);
-        RD_TRY(hipGetLastError());
-    }
-    RD_TRY(hipEventRecord(e1, st));
-    if (h_err[0] != ~0ull) {
-        g_reads_err = "CIGAR string " + cigar_text((int64_t) h_err[0]) + " has no matching region.";
-        rc = DN_E_INVALID;
-        goto done;
-    }
-    if (h_err[1] != ~0ull) {
-        g_reads_err = "CIGAR string " + cigar_text((int64_t) h_err[1]) + " has more than " + std::to_string(kMaxSeg) +
-                      " match segments (DN_READS_MAX_SEG)";
-        rc = DN_E_UNSUPPORTED;
-        goto done;
-    }
-    if (h_err[2] != ~0ull) {
-        g_reads_err = "an overlap gene's exons reach past its gene span (row " + std::to_string(h_err[2]) + ")";
-        rc = DN_E_INVALID;
-        goto done;
-    }
-    if (h_nsel > csr_cap) {
-        g_reads_err = "dn_read_coverage: " + std::to_string(h_nsel) + " nonzeros exceed csr_cap " + std::to_string(csr_cap);
-        rc = DN_E_INVALID;
-        goto done;
-    }
-    *io.nnz = h_nsel;
-    *io.n_isolated_reads = (int64_t) h_niso;
-    if (h_nsel > 0) {
-        RD_TRY(hipMemcpyAsync(io.csr_idx, d_csr_idx, sizeof(int32_t) * (size_t) h_nsel, hipMemcpyDeviceToHost, st));
-        RD_TRY(hipMemcpyAsync(io.csr_val, d_csr_val, sizeof(int64_t) * (size_t) h_nsel, hipMemcpyDeviceToHost, st));
-    }
-    if (ol_total > 0) RD_TRY(hipMemcpyAsync(io.ol_cov, d_val64, sizeof(int64_t) * (size_t) ol_total, hipMemcpyDeviceToHost, st));
-    if (n_genes > 0) RD_TRY(hipMemcpyAsync(h_counts.data(), d_counts, sizeof(int) * (size_t) n_genes, hipMemcpyDeviceToHost, st));
-    RD_TRY(hipStreamSynchronize(st));
-    for (int64_t k = 0; k < n_genes; k++) io.counts[k] = h_counts[k];
-    if (io.device_ms) { float ms = 0.f; RD_TRY(hipEventElapsedTime(&ms, e0, e1)); *io.device_ms = ms; }
-done:
-    (void) hipStreamSynchronize(st);
-    return rc;
+        // difference arrays -> coverage
+        DN_TRY(scratch.run([&](void *tmp, size_t &bytes) {
+            return hipcub::DeviceScan::InclusiveSum(tmp, bytes, d_cdiff.get(), d_ccov.get(), (int) chrom_len, st);
+        }));
+        if (ol_total > 0) {
+            DN_TRY(scratch.run([&](void *tmp, size_t &bytes) {
+                return hipcub::DeviceScan::InclusiveSum(tmp, bytes, d_oldiff.get(), d_olcov.get(), (int) ol_total, st);
+            }));
+            hipLaunchKernelGGL(k_widen, dim3(grid_for(ol_total)), dim3(kNT), 0, st, ol_total, d_olcov, d_val64);
+            DN_TRY(hipGetLastError());
+        }
+        // chromosome vector -> CSR (positions ascending)
+        DN_TRY(scratch.run([&](void *tmp, size_t &bytes) {
+            return hipcub::DeviceSelect::If(tmp, bytes, hipcub::CountingInputIterator<int32_t>(0), d_csr_idx.get(), d_nsel.get(), (int) chrom_len,
+                                            NonZero{d_ccov.get()}, st);
+        }));
+        DN_TRY(hipMemcpyAsync(&h_nsel, d_nsel, sizeof(int), hipMemcpyDeviceToHost, st));
+        DN_TRY(hipMemcpyAsync(h_err, d_err, sizeof(h_err), hipMemcpyDeviceToHost, st));
+        DN_TRY(hipMemcpyAsync(&h_niso, d_niso, sizeof(h_niso), hipMemcpyDeviceToHost, st));
+        DN_TRY(hipStreamSynchronize(st));
+        if (h_nsel > 0) {
+            hipLaunchKernelGGL(k_gather_csr, dim3(grid_for(h_nsel)), dim3(kNT), 0, st, (int64_t) h_nsel, d_csr_idx, d_ccov, d_csr_val);
+            DN_TRY(hipGetLastError());
+        }
+        DN_TRY(hipEventRecord(e1, st));
+        if (h_err[0] != ~0ull)
+            return dn::fail(DN_E_INVALID, "CIGAR string " + cigar_text((int64_t) h_err[0]) + " has no matching region.");
+        if (h_err[1] != ~0ull)
+            return dn::fail(DN_E_UNSUPPORTED, "CIGAR string " + cigar_text((int64_t) h_err[1]) + " has more than " + std::to_string(kMaxSeg) +
+                                              " match segments (DN_READS_MAX_SEG)");
+        if (h_err[2] != ~0ull)
+            return dn::fail(DN_E_INVALID, "an overlap gene's exons reach past its gene span (row " + std::to_string(h_err[2]) + ")");
+        if (h_nsel > csr_cap)
+            return dn::fail(DN_E_INVALID, "dn_read_coverage: " + std::to_string(h_nsel) + " nonzeros exceed csr_cap " + std::to_string(csr_cap));
+        *io.nnz = h_nsel;
+        *io.n_isolated_reads = (int64_t) h_niso;
+        if (h_nsel > 0) {
+            DN_TRY(hipMemcpyAsync(io.csr_idx, d_csr_idx, sizeof(int32_t) * (size_t) h_nsel, hipMemcpyDeviceToHost, st));
+            DN_TRY(hipMemcpyAsync(io.csr_val, d_csr_val, sizeof(int64_t) * (size_t) h_nsel, hipMemcpyDeviceToHost, st));
+        }
+        if (ol_total > 0) DN_TRY(hipMemcpyAsync(io.ol_cov, d_val64, sizeof(int64_t) * (size_t) ol_total, hipMemcpyDeviceToHost, st));
+        if (n_genes > 0) DN_TRY(hipMemcpyAsync(h_counts.data(), d_counts, sizeof(int) * (size_t) n_genes, hipMemcpyDeviceToHost, st));
+        DN_TRY(hipStreamSynchronize(st));
+        for (int64_t k = 0; k < n_genes; k++) io.counts[k] = h_counts[k];
+        if (io.device_ms) { float ms = 0.f; DN_TRY(hipEventElapsedTime(&ms, e0, e1)); *io.device_ms = ms; }
+        return DN_OK;
+    });
 }
 
 }  // namespace
@@ -580,56 +537,48 @@ extern "C" int dn_read_coverage(int device, int32_t paired, int64_t n_rows, cons
                                 int64_t csr_cap, int64_t *nnz, int32_t *csr_idx, int64_t *csr_val,
                                 int64_t *n_isolated_reads, double *device_ms)
 {
-    int rc = DN_OK;
-    g_reads_err.clear();
-    if (n_rows < 0 || n_rows > INT32_MAX - 1 || (n_rows > 0 && (!pos || !cigar_off || !cigar))) {
-        g_reads_err = "dn_read_coverage: bad argument";
-        return DN_E_INVALID;
-    }
+    dn::clear_error();
+    if (n_rows < 0 || n_rows > INT32_MAX - 1 || (n_rows > 0 && (!pos || !cigar_off || !cigar)))
+        return dn::fail(DN_E_INVALID, "dn_read_coverage: bad argument");
     COVERAGE_IO;
     const int64_t n_bytes = n_rows > 0 ? cigar_off[n_rows] : 0;
     dn::DeviceBuffer<int64_t> d_pos, d_off;
     dn::DeviceBuffer<uint8_t> d_cig;
     dn::Stream st;
-    RD_TRY(hipSetDevice(device));
-    RD_TRY(st.create(hipStreamCreate));
-    RD_TRY(alloc_padded(d_pos, n_rows)); RD_TRY(alloc_padded(d_off, n_rows + 1)); RD_TRY(alloc_padded(d_cig, n_bytes));
-    if (n_rows > 0) {
-        RD_TRY(hipMemcpyAsync(d_pos, pos, sizeof(int64_t) * (size_t) n_rows, hipMemcpyHostToDevice, st));
-        RD_TRY(hipMemcpyAsync(d_off, cigar_off, sizeof(int64_t) * (size_t) (n_rows + 1), hipMemcpyHostToDevice, st));
-    }
-    if (n_bytes > 0) RD_TRY(hipMemcpyAsync(d_cig, cigar, (size_t) n_bytes, hipMemcpyHostToDevice, st));
-    rc = coverage_stages(st, paired, n_rows, d_pos, StrCigars{d_off, d_cig}, pair_id, n_pair_ids, io, [&](int64_t r) {
-        return std::string((const char *) cigar + cigar_off[r], (size_t) (cigar_off[r + 1] - cigar_off[r]));
+    DN_TRY(hipSetDevice(device));
+    DN_TRY(st.create(hipStreamCreate));
+    return dn::synced(st, [&]() -> int {
+        DN_TRY(alloc_padded(d_pos, n_rows)); DN_TRY(alloc_padded(d_off, n_rows + 1)); DN_TRY(alloc_padded(d_cig, n_bytes));
+        if (n_rows > 0) {
+            DN_TRY(hipMemcpyAsync(d_pos, pos, sizeof(int64_t) * (size_t) n_rows, hipMemcpyHostToDevice, st));
+            DN_TRY(hipMemcpyAsync(d_off, cigar_off, sizeof(int64_t) * (size_t) (n_rows + 1), hipMemcpyHostToDevice, st));
+        }
+        if (n_bytes > 0) DN_TRY(hipMemcpyAsync(d_cig, cigar, (size_t) n_bytes, hipMemcpyHostToDevice, st));
+        return coverage_stages(st, paired, n_rows, d_pos, StrCigars{d_off, d_cig}, pair_id, n_pair_ids, io, [&](int64_t r) {
+            return std::string((const char *) cigar + cigar_off[r], (size_t) (cigar_off[r + 1] - cigar_off[r]));
+        });
     });
-done:
-    if (st) (void) hipStreamSynchronize(st);
-    return rc;
 }
 
 extern "C" int dn_reads_cigar_bounds(int device, int64_t n, const int64_t *pos, const int64_t *cigar_off, const uint8_t *cigar,
                                      int32_t max_seg, int32_t *nseg, int64_t *bounds, int64_t *end_pos)
 {
-    int rc = DN_OK;
-    g_reads_err.clear();
-    if (n < 0 || max_seg < 1 || max_seg > kMaxSeg || (n > 0 && (!pos || !cigar_off || !cigar || !nseg || !bounds || !end_pos))) {
-        g_reads_err = "dn_reads_cigar_bounds: bad argument";
-        return DN_E_INVALID;
-    }
+    dn::clear_error();
+    if (n < 0 || max_seg < 1 || max_seg > kMaxSeg || (n > 0 && (!pos || !cigar_off || !cigar || !nseg || !bounds || !end_pos)))
+        return dn::fail(DN_E_INVALID, "dn_reads_cigar_bounds: bad argument");
     if (n == 0) return DN_OK;
     dn::DeviceBuffer<int64_t> d_off;
     dn::DeviceBuffer<uint8_t> d_cig;
     dn::Stream st;
     const int64_t n_bytes = cigar_off[n];
-    RD_TRY(hipSetDevice(device));
-    RD_TRY(st.create(hipStreamCreate));
-    RD_TRY(alloc_padded(d_off, n + 1)); RD_TRY(alloc_padded(d_cig, n_bytes));
-    RD_TRY(hipMemcpyAsync(d_off, cigar_off, sizeof(int64_t) * (size_t) (n + 1), hipMemcpyHostToDevice, st));
-    if (n_bytes > 0) RD_TRY(hipMemcpyAsync(d_cig, cigar, (size_t) n_bytes, hipMemcpyHostToDevice, st));
-    rc = cigar_debug(st, n, pos, StrCigars{d_off, d_cig}, max_seg, nseg, bounds, end_pos);
-done:
-    if (st) (void) hipStreamSynchronize(st);
-    return rc;
+    DN_TRY(hipSetDevice(device));
+    DN_TRY(st.create(hipStreamCreate));
+    return dn::synced(st, [&]() -> int {
+        DN_TRY(alloc_padded(d_off, n + 1)); DN_TRY(alloc_padded(d_cig, n_bytes));
+        DN_TRY(hipMemcpyAsync(d_off, cigar_off, sizeof(int64_t) * (size_t) (n + 1), hipMemcpyHostToDevice, st));
+        if (n_bytes > 0) DN_TRY(hipMemcpyAsync(d_cig, cigar, (size_t) n_bytes, hipMemcpyHostToDevice, st));
+        return cigar_debug(st, n, pos, StrCigars{d_off, d_cig}, max_seg, nseg, bounds, end_pos);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -830,24 +779,6 @@ __global__ __launch_bounds__(kNT) void k_bam_gather(int64_t n, const int32_t *__
     }
 }
 
-int64_t next_cap(int64_t cap, int64_t need)
-{
-    int64_t nc = cap * 2 > need ? cap * 2 : need;
-    return nc < 1024 ? 1024 : nc;
-}
-
-// a buffer of new_cap elements holding the first `used` elements of b (the stream has finished with b when this returns)
-template <class T> hipError_t resize(dn::DeviceBuffer<T> &b, int64_t used, int64_t new_cap, hipStream_t st)
-{
-    dn::DeviceBuffer<T> nb;
-    hipError_t e = alloc_padded(nb, (size_t) new_cap);
-    if (e == hipSuccess && used > 0) e = hipMemcpyAsync(nb, b, sizeof(T) * (size_t) used, hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return e;
-    b = std::move(nb);
-    return hipSuccess;
-}
-
 std::string bam_name(const uint8_t *w, int64_t n_bytes, int64_t o)
 {
     if (o + 36 > n_bytes) return "?";
@@ -870,59 +801,47 @@ struct dn_bam_rows_s {
     BamFilter F;
     dn::Stream st;
     int64_t n_rows = 0, n_ops = 0, n_names = 0;
-    int64_t cap_rows = 0, cap_ops = 0, cap_names = 0, cap_win = 0, cap_rec = 0;
-    dn::DeviceBuffer<int64_t> pos, op_beg, name_beg, rec_off;
-    dn::DeviceBuffer<int32_t> n_op, name_len, key_len, max_key, keep, w_ops, w_name, rank, op_rank, name_rank;
-    dn::DeviceBuffer<uint32_t> ops;
-    dn::DeviceBuffer<uint8_t> names, win;
+    dn::GrowBuffer<int64_t> pos, op_beg, name_beg, rec_off;
+    dn::GrowBuffer<int32_t> n_op, name_len, key_len;
+    dn::DeviceBuffer<int32_t> max_key;
+    dn::GrowBuffer<int32_t> keep, w_ops, w_name, rank, op_rank, name_rank;
+    dn::GrowBuffer<uint32_t> ops;
+    dn::GrowBuffer<uint8_t> names, win;
     dn::DeviceBuffer<unsigned long long> err;
-    std::vector<dn::DeviceBuffer<uint8_t>> tmp;
-    size_t tmp_bytes = 0;
+    dn::Scratch scratch;                   // of the three scans of a window
     // device inflate (dn_bam_rows_inflate): the compressed blocks, their descriptors and states, the pinned host copy of the
     // window, and the bytes of h->win that hold the resident window (-1: none)
-    dn::DeviceBuffer<uint8_t> comp;
-    dn::DeviceBuffer<dn::InflateBlock> blk;
-    dn::DeviceBuffer<int32_t> blk_status;
+    dn::GrowBuffer<uint8_t> comp;
+    dn::GrowBuffer<dn::InflateBlock> blk;
+    dn::GrowBuffer<int32_t> blk_status;
     dn::PinnedBuffer<uint8_t> host_win;
     dn::Event ev0, ev1;
-    int64_t cap_comp = 0, cap_blk = 0, cap_host = 0, resident = -1;
+    int64_t cap_host = 0, resident = -1;
     std::string no_cigar;                  // the name of the first kept row without CIGAR ops ("" while there is none)
     bool has_no_cigar = false;
 };
 
-#define BAM_TRY(expr)                                                                                                   \
-    do {                                                                                                                \
-        hipError_t e_ = (expr);                                                                                         \
-        if (e_ != hipSuccess) { g_reads_err = std::string(#expr) + ": " + hipGetErrorString(e_); return DN_E_HIP; }     \
-    } while (0)
-
 extern "C" int dn_bam_frame(const uint8_t *buf, int64_t n_bytes, int32_t tid, int32_t *last_pos, int64_t *rec_off, int64_t cap,
                             int64_t *n_rec, int64_t *consumed)
 {
-    g_reads_err.clear();
-    if (n_bytes < 0 || (n_bytes > 0 && !buf) || cap < 0 || (cap > 0 && !rec_off) || !n_rec || !consumed || (tid >= 0 && !last_pos)) {
-        g_reads_err = "dn_bam_frame: bad argument";
-        return DN_E_INVALID;
-    }
+    dn::clear_error();
+    if (n_bytes < 0 || (n_bytes > 0 && !buf) || cap < 0 || (cap > 0 && !rec_off) || !n_rec || !consumed || (tid >= 0 && !last_pos))
+        return dn::fail(DN_E_INVALID, "dn_bam_frame: bad argument");
     int64_t o = 0, n = 0;
     while (o + 4 <= n_bytes) {
         int32_t bs, ref, pos;
         memcpy(&bs, buf + o, 4);
-        if (bs < 32) {
-            g_reads_err = "malformed BAM record at byte " + std::to_string(o) + " of the window (block_size " + std::to_string(bs) + ")";
-            return DN_E_INVALID;
-        }
+        if (bs < 32)
+            return dn::fail(DN_E_INVALID, "malformed BAM record at byte " + std::to_string(o) + " of the window (block_size " + std::to_string(bs) + ")");
         if (o + 4 + (int64_t) bs > n_bytes) break;          // the tail: carried over to the next window
-        if (n >= cap) { g_reads_err = "dn_bam_frame: more records than cap"; return DN_E_INVALID; }
+        if (n >= cap) return dn::fail(DN_E_INVALID, "dn_bam_frame: more records than cap");
         if (tid >= 0) {
             memcpy(&ref, buf + o + 4, 4);
             memcpy(&pos, buf + o + 8, 4);
-            if (ref != tid || pos < *last_pos) {
-                g_reads_err = "BAM file is not sorted by coordinate, or its index is stale: a record of refID " + std::to_string(ref) +
-                              " at position " + std::to_string(pos) + " follows position " + std::to_string(*last_pos) +
-                              " inside the index range of refID " + std::to_string(tid);
-                return DN_E_INVALID;
-            }
+            if (ref != tid || pos < *last_pos)
+                return dn::fail(DN_E_INVALID, "BAM file is not sorted by coordinate, or its index is stale: a record of refID " + std::to_string(ref) +
+                                              " at position " + std::to_string(pos) + " follows position " + std::to_string(*last_pos) +
+                                              " inside the index range of refID " + std::to_string(tid));
             *last_pos = pos;
         }
         rec_off[n++] = o;
@@ -935,25 +854,24 @@ extern "C" int dn_bam_frame(const uint8_t *buf, int64_t n_bytes, int32_t tid, in
 
 extern "C" int dn_bam_rows_create(int device, int32_t tid, int32_t unique_alignment, int32_t paired, dn_bam_rows *out)
 {
-    g_reads_err.clear();
-    if (!out) { g_reads_err = "dn_bam_rows_create: bad argument"; return DN_E_INVALID; }
+    dn::clear_error();
+    if (!out) return dn::fail(DN_E_INVALID, "dn_bam_rows_create: bad argument");
     *out = nullptr;
-    dn_bam_rows_s *h = new dn_bam_rows_s();
+    const char *who = "dn_bam_rows_create";
+    auto h = std::make_unique<dn_bam_rows_s>();
     h->device = device;
     h->F = BamFilter{tid, unique_alignment ? 1 : 0, paired ? 1 : 0};
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) e = h->st.create(hipStreamCreate);
-    if (e == hipSuccess) e = alloc_padded(h->max_key, 1);
-    if (e == hipSuccess) e = alloc_padded(h->err, kBamNErr);
-    if (e == hipSuccess) e = hipMemsetAsync(h->max_key, 0, sizeof(int32_t), h->st);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->st);
-    if (e != hipSuccess) {
-        g_reads_err = std::string("dn_bam_rows_create: ") + hipGetErrorString(e);
-        delete h;
-        return DN_E_HIP;
-    }
-    *out = h;
-    return DN_OK;
+    DN_TRY_AS(who, hipSetDevice(device));
+    DN_TRY_AS(who, h->st.create(hipStreamCreate));
+    const int rc = dn::synced(h->st, [&]() -> int {
+        DN_TRY_AS(who, alloc_padded(h->max_key, 1));
+        DN_TRY_AS(who, alloc_padded(h->err, kBamNErr));
+        DN_TRY_AS(who, hipMemsetAsync(h->max_key, 0, sizeof(int32_t), h->st));
+        DN_TRY_AS(who, hipStreamSynchronize(h->st));
+        return DN_OK;
+    });
+    if (rc == DN_OK) *out = h.release();
+    return rc;
 }
 
 extern "C" void dn_bam_rows_destroy(dn_bam_rows h)
@@ -971,99 +889,65 @@ namespace {
 int append_window(dn_bam_rows h, const uint8_t *window, int64_t n_bytes, const int64_t *rec_off, int64_t n_rec)
 {
     hipStream_t st = h->st;
-    if (n_rec + 1 > h->cap_rec) {
-        const int64_t c = next_cap(h->cap_rec, n_rec + 1);
-        BAM_TRY(resize(h->rec_off, 0, c, st)); BAM_TRY(resize(h->keep, 0, c, st)); BAM_TRY(resize(h->w_ops, 0, c, st));
-        BAM_TRY(resize(h->w_name, 0, c, st)); BAM_TRY(resize(h->rank, 0, c, st)); BAM_TRY(resize(h->op_rank, 0, c, st));
-        BAM_TRY(resize(h->name_rank, 0, c, st));
-        h->cap_rec = c;
-    }
-    BAM_TRY(hipMemcpyAsync(h->rec_off, rec_off, sizeof(int64_t) * (size_t) n_rec, hipMemcpyHostToDevice, st));
-    BAM_TRY(hipMemsetAsync(h->err, 0xff, sizeof(unsigned long long) * kBamNErr, st));
-    BAM_TRY(hipMemsetAsync(h->keep + n_rec, 0, sizeof(int32_t), st));
-    BAM_TRY(hipMemsetAsync(h->w_ops + n_rec, 0, sizeof(int32_t), st));
-    BAM_TRY(hipMemsetAsync(h->w_name + n_rec, 0, sizeof(int32_t), st));
-    hipLaunchKernelGGL(k_bam_scan, dim3(grid_for(n_rec)), dim3(kNT), 0, st, h->win.get(), n_bytes, h->rec_off.get(), n_rec, h->F,
-                       h->keep.get(), h->w_ops.get(), h->w_name.get(), h->err.get());
-    BAM_TRY(hipGetLastError());
-    {
-        const int n = (int) n_rec + 1;
-        size_t need = 0;
-        BAM_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, h->keep.get(), h->rank.get(), n, st));
-        if (need > h->tmp_bytes) { h->tmp.emplace_back(); BAM_TRY(alloc_padded(h->tmp.back(), need)); h->tmp_bytes = need; }
-        void *t = h->tmp.back();
-        BAM_TRY(hipcub::DeviceScan::ExclusiveSum(t, need, h->keep.get(), h->rank.get(), n, st));
-        BAM_TRY(hipcub::DeviceScan::ExclusiveSum(t, need, h->w_ops.get(), h->op_rank.get(), n, st));
-        BAM_TRY(hipcub::DeviceScan::ExclusiveSum(t, need, h->w_name.get(), h->name_rank.get(), n, st));
-    }
-    int32_t tot[3];
+    int32_t tot[3];                                  // what the stream copies to the host
     unsigned long long herr[kBamNErr];
-    BAM_TRY(hipMemcpyAsync(tot + 0, h->rank + n_rec, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    BAM_TRY(hipMemcpyAsync(tot + 1, h->op_rank + n_rec, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    BAM_TRY(hipMemcpyAsync(tot + 2, h->name_rank + n_rec, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    BAM_TRY(hipMemcpyAsync(herr, h->err, sizeof(herr), hipMemcpyDeviceToHost, st));
-    BAM_TRY(hipStreamSynchronize(st));
-    if (herr[kBamErrMalformed] != ~0ull) {
-        g_reads_err = "malformed BAM record (read " + bam_name(window, n_bytes, rec_off[herr[kBamErrMalformed]]) + ")";
-        return DN_E_INVALID;
-    }
-    if (herr[kBamErrNh] != ~0ull) {
-        g_reads_err = "read " + bam_name(window, n_bytes, rec_off[herr[kBamErrNh]]) + " has an NH tag of a non-integer type";
-        return DN_E_INVALID;
-    }
-    if (herr[kBamErrUnsupported] != ~0ull) {
-        g_reads_err = "read " + bam_name(window, n_bytes, rec_off[herr[kBamErrUnsupported]]) +
-                      " has a CIGAR op code above 8 or a CIGAR moved to the CG tag (not supported)";
-        return DN_E_UNSUPPORTED;
-    }
-    if (herr[kBamErrNoCigar] != ~0ull && !h->has_no_cigar) {
-        h->has_no_cigar = true;
-        h->no_cigar = bam_name(window, n_bytes, rec_off[herr[kBamErrNoCigar]]);
-    }
-    if (h->n_rows + tot[0] > INT32_MAX - 1) { g_reads_err = "dn_bam_rows_append: more than 2^31 - 2 rows"; return DN_E_UNSUPPORTED; }
-    if (tot[0] > 0) {
-        if (h->n_rows + tot[0] > h->cap_rows) {
-            const int64_t c = next_cap(h->cap_rows, h->n_rows + tot[0]), n = h->n_rows;
-            BAM_TRY(resize(h->pos, n, c, st)); BAM_TRY(resize(h->op_beg, n, c, st)); BAM_TRY(resize(h->name_beg, n, c, st));
-            BAM_TRY(resize(h->n_op, n, c, st)); BAM_TRY(resize(h->name_len, n, c, st)); BAM_TRY(resize(h->key_len, n, c, st));
-            h->cap_rows = c;
+    return dn::synced(st, [&]() -> int {
+        // per record, and one more for the totals of the scans
+        DN_TRY(h->rec_off.reserve(n_rec + 1, 0, st)); DN_TRY(h->keep.reserve(n_rec + 1, 0, st)); DN_TRY(h->w_ops.reserve(n_rec + 1, 0, st));
+        DN_TRY(h->w_name.reserve(n_rec + 1, 0, st)); DN_TRY(h->rank.reserve(n_rec + 1, 0, st)); DN_TRY(h->op_rank.reserve(n_rec + 1, 0, st));
+        DN_TRY(h->name_rank.reserve(n_rec + 1, 0, st));
+        DN_TRY(hipMemcpyAsync(h->rec_off, rec_off, sizeof(int64_t) * (size_t) n_rec, hipMemcpyHostToDevice, st));
+        DN_TRY(hipMemsetAsync(h->err, 0xff, sizeof(unsigned long long) * kBamNErr, st));
+        DN_TRY(hipMemsetAsync(h->keep + n_rec, 0, sizeof(int32_t), st));
+        DN_TRY(hipMemsetAsync(h->w_ops + n_rec, 0, sizeof(int32_t), st));
+        DN_TRY(hipMemsetAsync(h->w_name + n_rec, 0, sizeof(int32_t), st));
+        hipLaunchKernelGGL(k_bam_scan, dim3(grid_for(n_rec)), dim3(kNT), 0, st, h->win.get(), n_bytes, h->rec_off.get(), n_rec, h->F,
+                           h->keep.get(), h->w_ops.get(), h->w_name.get(), h->err.get());
+        DN_TRY(hipGetLastError());
+        const auto rank_of = [&](int32_t *flag, int32_t *rank) {      // exclusive; rank[n_rec] is the total
+            return h->scratch.run([&](void *tmp, size_t &bytes) { return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, flag, rank, (int) n_rec + 1, st); });
+        };
+        DN_TRY(rank_of(h->keep, h->rank)); DN_TRY(rank_of(h->w_ops, h->op_rank)); DN_TRY(rank_of(h->w_name, h->name_rank));
+        DN_TRY(hipMemcpyAsync(tot + 0, h->rank + n_rec, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        DN_TRY(hipMemcpyAsync(tot + 1, h->op_rank + n_rec, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        DN_TRY(hipMemcpyAsync(tot + 2, h->name_rank + n_rec, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        DN_TRY(hipMemcpyAsync(herr, h->err, sizeof(herr), hipMemcpyDeviceToHost, st));
+        DN_TRY(hipStreamSynchronize(st));
+        if (herr[kBamErrMalformed] != ~0ull)
+            return dn::fail(DN_E_INVALID, "malformed BAM record (read " + bam_name(window, n_bytes, rec_off[herr[kBamErrMalformed]]) + ")");
+        if (herr[kBamErrNh] != ~0ull)
+            return dn::fail(DN_E_INVALID, "read " + bam_name(window, n_bytes, rec_off[herr[kBamErrNh]]) + " has an NH tag of a non-integer type");
+        if (herr[kBamErrUnsupported] != ~0ull)
+            return dn::fail(DN_E_UNSUPPORTED, "read " + bam_name(window, n_bytes, rec_off[herr[kBamErrUnsupported]]) +
+                                              " has a CIGAR op code above 8 or a CIGAR moved to the CG tag (not supported)");
+        if (herr[kBamErrNoCigar] != ~0ull && !h->has_no_cigar) {
+            h->has_no_cigar = true;
+            h->no_cigar = bam_name(window, n_bytes, rec_off[herr[kBamErrNoCigar]]);
         }
-        if (h->n_ops + tot[1] > h->cap_ops) {
-            const int64_t c = next_cap(h->cap_ops, h->n_ops + tot[1]);
-            BAM_TRY(resize(h->ops, h->n_ops, c, st));
-            h->cap_ops = c;
+        if (h->n_rows + tot[0] > INT32_MAX - 1) return dn::fail(DN_E_UNSUPPORTED, "dn_bam_rows_append: more than 2^31 - 2 rows");
+        if (tot[0] > 0) {
+            const int64_t n = h->n_rows, rows = n + tot[0];
+            DN_TRY(h->pos.reserve(rows, n, st)); DN_TRY(h->op_beg.reserve(rows, n, st)); DN_TRY(h->name_beg.reserve(rows, n, st));
+            DN_TRY(h->n_op.reserve(rows, n, st)); DN_TRY(h->name_len.reserve(rows, n, st)); DN_TRY(h->key_len.reserve(rows, n, st));
+            DN_TRY(h->ops.reserve(h->n_ops + tot[1], h->n_ops, st));
+            DN_TRY(h->names.reserve(h->n_names + tot[2], h->n_names, st));
+            BamRowsOut O{h->pos, h->op_beg, h->name_beg, h->n_op, h->name_len, h->key_len, h->ops, h->names, h->max_key};
+            hipLaunchKernelGGL(k_bam_write, dim3(grid_for(n_rec)), dim3(kNT), 0, st, h->win.get(), n_bytes, h->rec_off.get(), n_rec,
+                               h->keep.get(), h->rank.get(), h->op_rank.get(), h->name_rank.get(), h->n_rows, h->n_ops, h->n_names, O);
+            DN_TRY(hipGetLastError());
+            DN_TRY(hipStreamSynchronize(st));
+            h->n_rows += tot[0];
+            h->n_ops += tot[1];
+            h->n_names += tot[2];
         }
-        if (h->n_names + tot[2] > h->cap_names) {
-            const int64_t c = next_cap(h->cap_names, h->n_names + tot[2]);
-            BAM_TRY(resize(h->names, h->n_names, c, st));
-            h->cap_names = c;
-        }
-        BamRowsOut O{h->pos, h->op_beg, h->name_beg, h->n_op, h->name_len, h->key_len, h->ops, h->names, h->max_key};
-        hipLaunchKernelGGL(k_bam_write, dim3(grid_for(n_rec)), dim3(kNT), 0, st, h->win.get(), n_bytes, h->rec_off.get(), n_rec,
-                           h->keep.get(), h->rank.get(), h->op_rank.get(), h->name_rank.get(), h->n_rows, h->n_ops, h->n_names, O);
-        BAM_TRY(hipGetLastError());
-        BAM_TRY(hipStreamSynchronize(st));
-        h->n_rows += tot[0];
-        h->n_ops += tot[1];
-        h->n_names += tot[2];
-    }
-    return DN_OK;
-}
-
-int grow_window(dn_bam_rows h, int64_t n_bytes)       // window scratch: nothing to keep (the previous append has finished)
-{
-    if (n_bytes > h->cap_win) {
-        const int64_t c = next_cap(h->cap_win, n_bytes);
-        BAM_TRY(resize(h->win, 0, c, h->st));
-        h->cap_win = c;
-    }
-    return DN_OK;
+        return DN_OK;
+    });
 }
 
 int check_offsets(const char *who, int64_t n_bytes, const int64_t *rec_off, int64_t n_rec)
 {
     for (int64_t i = 0; i < n_rec; i++)              // the kernels read 36 bytes at every offset: keep them inside the window
-        if (rec_off[i] < 0 || rec_off[i] + 36 > n_bytes) { g_reads_err = std::string(who) + ": record offset outside the window"; return DN_E_INVALID; }
+        if (rec_off[i] < 0 || rec_off[i] + 36 > n_bytes) return dn::fail(DN_E_INVALID, std::string(who) + ": record offset outside the window");
     return DN_OK;
 }
 
@@ -1071,20 +955,19 @@ int check_offsets(const char *who, int64_t n_bytes, const int64_t *rec_off, int6
 
 extern "C" int dn_bam_rows_append(dn_bam_rows h, const uint8_t *window, int64_t n_bytes, const int64_t *rec_off, int64_t n_rec)
 {
-    g_reads_err.clear();
-    if (!h || n_bytes < 0 || n_bytes > INT32_MAX || n_rec < 0 || (n_rec > 0 && (!window || !rec_off))) {
-        g_reads_err = "dn_bam_rows_append: bad argument";
-        return DN_E_INVALID;
-    }
+    dn::clear_error();
+    if (!h || n_bytes < 0 || n_bytes > INT32_MAX || n_rec < 0 || (n_rec > 0 && (!window || !rec_off)))
+        return dn::fail(DN_E_INVALID, "dn_bam_rows_append: bad argument");
     if (n_rec == 0) return DN_OK;
-    int rc = check_offsets("dn_bam_rows_append", n_bytes, rec_off, n_rec);
+    const int rc = check_offsets("dn_bam_rows_append", n_bytes, rec_off, n_rec);
     if (rc != DN_OK) return rc;
-    BAM_TRY(hipSetDevice(h->device));
+    DN_TRY(hipSetDevice(h->device));
     h->resident = -1;
-    rc = grow_window(h, n_bytes);
-    if (rc != DN_OK) return rc;
-    BAM_TRY(hipMemcpyAsync(h->win, window, (size_t) n_bytes, hipMemcpyHostToDevice, h->st));
-    return append_window(h, window, n_bytes, rec_off, n_rec);
+    return dn::synced(h->st, [&]() -> int {
+        DN_TRY(h->win.reserve(n_bytes, 0, h->st));         // window scratch: nothing to keep (the previous append has finished)
+        DN_TRY(hipMemcpyAsync(h->win, window, (size_t) n_bytes, hipMemcpyHostToDevice, h->st));
+        return append_window(h, window, n_bytes, rec_off, n_rec);
+    });
 }
 
 extern "C" int dn_bam_rows_inflate(dn_bam_rows h, const uint8_t *carry, int64_t n_carry, const uint8_t *comp, int64_t n_comp,
@@ -1092,142 +975,134 @@ extern "C" int dn_bam_rows_inflate(dn_bam_rows h, const uint8_t *carry, int64_t 
                                    int32_t head_skip, int32_t tail_keep, const uint8_t **host_window, int64_t *n_bytes,
                                    int32_t *status, double *device_ms)
 {
-    g_reads_err.clear();
+    dn::clear_error();
     if (!h || n_carry < 0 || (n_carry > 0 && !carry) || n_comp < 0 || (n_comp > 0 && !comp) || n_blocks < 0 || n_blocks > INT32_MAX ||
-        (n_blocks > 0 && (!pay_off || !pay_len || !isize || !status)) || head_skip < 0 || !host_window || !n_bytes) {
-        g_reads_err = "dn_bam_rows_inflate: bad argument";
-        return DN_E_INVALID;
-    }
+        (n_blocks > 0 && (!pay_off || !pay_len || !isize || !status)) || head_skip < 0 || !host_window || !n_bytes)
+        return dn::fail(DN_E_INVALID, "dn_bam_rows_inflate: bad argument");
     std::vector<dn::InflateBlock> blk((size_t) n_blocks);
     int64_t total = n_carry;
     for (int64_t b = 0; b < n_blocks; b++) {
-        if (pay_off[b] < 0 || pay_len[b] < 0 || pay_off[b] > n_comp || pay_len[b] > n_comp - pay_off[b]) {
-            g_reads_err = "dn_bam_rows_inflate: payload of block " + std::to_string(b) + " outside comp";
-            return DN_E_INVALID;
-        }
-        if (isize[b] < 0) {     // no upper bound: the ring decoder does not need one, and the host path reads over-long blocks too
-            g_reads_err = "dn_bam_rows_inflate: block " + std::to_string(b) + " has a negative inflated size";
-            return DN_E_INVALID;
-        }
+        if (pay_off[b] < 0 || pay_len[b] < 0 || pay_off[b] > n_comp || pay_len[b] > n_comp - pay_off[b])
+            return dn::fail(DN_E_INVALID, "dn_bam_rows_inflate: payload of block " + std::to_string(b) + " outside comp");
+        if (isize[b] < 0)       // no upper bound: the ring decoder does not need one, and the host path reads over-long blocks too
+            return dn::fail(DN_E_INVALID, "dn_bam_rows_inflate: block " + std::to_string(b) + " has a negative inflated size");
         int32_t hi = isize[b], lo = 0;                  // the last block is cut first, then the first one, as the host path does
         if (b == n_blocks - 1 && tail_keep >= 0 && tail_keep < hi) hi = tail_keep;
         if (b == 0) lo = head_skip < hi ? head_skip : hi;
         blk[(size_t) b] = dn::InflateBlock{pay_off[b], total, pay_len[b], isize[b], lo, hi - lo};
         total += hi - lo;
     }
-    if (total > INT32_MAX) { g_reads_err = "dn_bam_rows_inflate: window beyond 2^31 - 1 bytes"; return DN_E_INVALID; }
+    if (total > INT32_MAX) return dn::fail(DN_E_INVALID, "dn_bam_rows_inflate: window beyond 2^31 - 1 bytes");
     hipStream_t st = h->st;
-    BAM_TRY(hipSetDevice(h->device));
+    DN_TRY(hipSetDevice(h->device));
     h->resident = -1;
-    int rc = grow_window(h, total);
-    if (rc != DN_OK) return rc;
-    const int64_t comp_cap = dn::inflate_comp_cap(n_comp);
-    if (comp_cap > h->cap_comp) {
-        const int64_t c = next_cap(h->cap_comp, comp_cap);
-        BAM_TRY(resize(h->comp, 0, c, st));
-        h->cap_comp = c;
-    }
-    if (n_blocks > h->cap_blk) {
-        const int64_t c = next_cap(h->cap_blk, n_blocks);
-        BAM_TRY(resize(h->blk, 0, c, st)); BAM_TRY(resize(h->blk_status, 0, c, st));
-        h->cap_blk = c;
-    }
-    if (total + 16 > h->cap_host) {
-        const int64_t c = next_cap(h->cap_host, total + 16);
-        dn::PinnedBuffer<uint8_t> nb;                   // the old copy stays until the new one exists, as in resize()
-        BAM_TRY(nb.alloc((size_t) c));
-        h->host_win = std::move(nb);
-        h->cap_host = c;
-    }
-    if (!h->ev0) { BAM_TRY(h->ev0.create(hipEventCreate)); BAM_TRY(h->ev1.create(hipEventCreate)); }
-    if (n_carry > 0) BAM_TRY(hipMemcpyAsync(h->win, carry, (size_t) n_carry, hipMemcpyHostToDevice, st));
-    if (n_comp > 0) BAM_TRY(hipMemcpyAsync(h->comp, comp, (size_t) n_comp, hipMemcpyHostToDevice, st));
-    if (n_blocks > 0) BAM_TRY(hipMemcpyAsync(h->blk, blk.data(), sizeof(dn::InflateBlock) * (size_t) n_blocks, hipMemcpyHostToDevice, st));
-    BAM_TRY(hipEventRecord(h->ev0, st));
-    BAM_TRY(dn::inflate_launch(st, h->comp, comp_cap, h->blk, n_blocks, h->win, h->blk_status));
-    BAM_TRY(hipEventRecord(h->ev1, st));
-    if (total > 0) BAM_TRY(hipMemcpyAsync(h->host_win, h->win, (size_t) total, hipMemcpyDeviceToHost, st));
-    if (n_blocks > 0) BAM_TRY(hipMemcpyAsync(status, h->blk_status, sizeof(int32_t) * (size_t) n_blocks, hipMemcpyDeviceToHost, st));
-    BAM_TRY(hipStreamSynchronize(st));
-    if (device_ms) {
-        float ms = 0.f;
-        BAM_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-        *device_ms = ms;
-    }
-    *host_window = h->host_win;
-    *n_bytes = total;
-    h->resident = total;
-    for (int64_t b = 0; b < n_blocks; b++)
-        if (status[b] != 0) { h->resident = -1; break; }     // a block that failed left its bytes unspecified
-    return DN_OK;
+    return dn::synced(st, [&]() -> int {
+        DN_TRY(h->win.reserve(total, 0, st));
+        const int64_t comp_cap = dn::inflate_comp_cap(n_comp);
+        DN_TRY(h->comp.reserve(comp_cap, 0, st));
+        DN_TRY(h->blk.reserve(n_blocks, 0, st)); DN_TRY(h->blk_status.reserve(n_blocks, 0, st));
+        if (total + 16 > h->cap_host) {
+            const int64_t c = dn::grown_capacity(h->cap_host, total + 16);
+            dn::PinnedBuffer<uint8_t> nb;                   // the old copy stays until the new one exists, as in GrowBuffer
+            DN_TRY(nb.alloc((size_t) c));
+            h->host_win = std::move(nb);
+            h->cap_host = c;
+        }
+        if (!h->ev0) { DN_TRY(h->ev0.create(hipEventCreate)); DN_TRY(h->ev1.create(hipEventCreate)); }
+        if (n_carry > 0) DN_TRY(hipMemcpyAsync(h->win, carry, (size_t) n_carry, hipMemcpyHostToDevice, st));
+        if (n_comp > 0) DN_TRY(hipMemcpyAsync(h->comp, comp, (size_t) n_comp, hipMemcpyHostToDevice, st));
+        if (n_blocks > 0) DN_TRY(hipMemcpyAsync(h->blk, blk.data(), sizeof(dn::InflateBlock) * (size_t) n_blocks, hipMemcpyHostToDevice, st));
+        DN_TRY(hipEventRecord(h->ev0, st));
+        DN_TRY(dn::inflate_launch(st, h->comp, comp_cap, h->blk, n_blocks, h->win, h->blk_status));
+        DN_TRY(hipEventRecord(h->ev1, st));
+        if (total > 0) DN_TRY(hipMemcpyAsync(h->host_win, h->win, (size_t) total, hipMemcpyDeviceToHost, st));
+        if (n_blocks > 0) DN_TRY(hipMemcpyAsync(status, h->blk_status, sizeof(int32_t) * (size_t) n_blocks, hipMemcpyDeviceToHost, st));
+        DN_TRY(hipStreamSynchronize(st));
+        if (device_ms) {
+            float ms = 0.f;
+            DN_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+            *device_ms = ms;
+        }
+        *host_window = h->host_win;
+        *n_bytes = total;
+        h->resident = total;
+        for (int64_t b = 0; b < n_blocks; b++)
+            if (status[b] != 0) { h->resident = -1; break; }     // a block that failed left its bytes unspecified
+        return DN_OK;
+    });
 }
 
 extern "C" int dn_bam_rows_append_resident(dn_bam_rows h, const int64_t *rec_off, int64_t n_rec)
 {
-    g_reads_err.clear();
-    if (!h || n_rec < 0 || (n_rec > 0 && !rec_off)) { g_reads_err = "dn_bam_rows_append_resident: bad argument"; return DN_E_INVALID; }
-    if (h->resident < 0) { g_reads_err = "dn_bam_rows_append_resident: no resident window (dn_bam_rows_inflate first)"; return DN_E_STATE; }
+    dn::clear_error();
+    if (!h || n_rec < 0 || (n_rec > 0 && !rec_off)) return dn::fail(DN_E_INVALID, "dn_bam_rows_append_resident: bad argument");
+    if (h->resident < 0) return dn::fail(DN_E_STATE, "dn_bam_rows_append_resident: no resident window (dn_bam_rows_inflate first)");
     if (n_rec == 0) return DN_OK;
     const int rc = check_offsets("dn_bam_rows_append_resident", h->resident, rec_off, n_rec);
     if (rc != DN_OK) return rc;
-    BAM_TRY(hipSetDevice(h->device));
-    return append_window(h, h->host_win, h->resident, rec_off, n_rec);
+    DN_TRY(hipSetDevice(h->device));
+    return dn::synced(h->st, [&]() -> int { return append_window(h, h->host_win, h->resident, rec_off, n_rec); });
 }
 
 extern "C" int dn_bam_rows_info(dn_bam_rows h, int64_t *n_rows, int64_t *n_ops, int64_t *n_name_bytes, int32_t *max_key_len)
 {
-    g_reads_err.clear();
-    if (!h) { g_reads_err = "dn_bam_rows_info: bad argument"; return DN_E_INVALID; }
+    dn::clear_error();
+    if (!h) return dn::fail(DN_E_INVALID, "dn_bam_rows_info: bad argument");
     if (n_rows) *n_rows = h->n_rows;
     if (n_ops) *n_ops = h->n_ops;
     if (n_name_bytes) *n_name_bytes = h->n_names;
-    if (max_key_len) {
-        BAM_TRY(hipSetDevice(h->device));
-        BAM_TRY(hipMemcpyAsync(max_key_len, h->max_key, sizeof(int32_t), hipMemcpyDeviceToHost, h->st));
-        BAM_TRY(hipStreamSynchronize(h->st));
-    }
-    return DN_OK;
+    if (!max_key_len) return DN_OK;
+    DN_TRY(hipSetDevice(h->device));
+    return dn::synced(h->st, [&]() -> int {
+        DN_TRY(hipMemcpyAsync(max_key_len, h->max_key, sizeof(int32_t), hipMemcpyDeviceToHost, h->st));
+        DN_TRY(hipStreamSynchronize(h->st));
+        return DN_OK;
+    });
 }
 
 extern "C" int dn_bam_rows_keys(dn_bam_rows h, int32_t width, uint8_t *keys)
 {
-    g_reads_err.clear();
-    if (!h || width < 1 || (h->n_rows > 0 && !keys)) { g_reads_err = "dn_bam_rows_keys: bad argument"; return DN_E_INVALID; }
+    dn::clear_error();
+    if (!h || width < 1 || (h->n_rows > 0 && !keys)) return dn::fail(DN_E_INVALID, "dn_bam_rows_keys: bad argument");
     if (h->n_rows == 0) return DN_OK;
     int32_t mk = 0;
-    BAM_TRY(hipSetDevice(h->device));
-    BAM_TRY(hipMemcpyAsync(&mk, h->max_key, sizeof(int32_t), hipMemcpyDeviceToHost, h->st));
-    BAM_TRY(hipStreamSynchronize(h->st));
-    if (width < mk) { g_reads_err = "dn_bam_rows_keys: width below the longest key (" + std::to_string(mk) + ")"; return DN_E_INVALID; }
     dn::DeviceBuffer<uint8_t> d_keys;
-    BAM_TRY(alloc_padded(d_keys, (size_t) (h->n_rows * width)));
-    hipLaunchKernelGGL(k_bam_keys, dim3(grid_for(h->n_rows)), dim3(kNT), 0, h->st, h->n_rows, h->name_beg.get(), h->key_len.get(),
-                       h->names.get(), width, d_keys.get());
-    BAM_TRY(hipGetLastError());
-    BAM_TRY(hipMemcpyAsync(keys, d_keys, (size_t) (h->n_rows * width), hipMemcpyDeviceToHost, h->st));
-    BAM_TRY(hipStreamSynchronize(h->st));
-    return DN_OK;
+    DN_TRY(hipSetDevice(h->device));
+    return dn::synced(h->st, [&]() -> int {
+        DN_TRY(hipMemcpyAsync(&mk, h->max_key, sizeof(int32_t), hipMemcpyDeviceToHost, h->st));
+        DN_TRY(hipStreamSynchronize(h->st));
+        if (width < mk) return dn::fail(DN_E_INVALID, "dn_bam_rows_keys: width below the longest key (" + std::to_string(mk) + ")");
+        DN_TRY(alloc_padded(d_keys, (size_t) (h->n_rows * width)));
+        hipLaunchKernelGGL(k_bam_keys, dim3(grid_for(h->n_rows)), dim3(kNT), 0, h->st, h->n_rows, h->name_beg.get(), h->key_len.get(),
+                           h->names.get(), width, d_keys.get());
+        DN_TRY(hipGetLastError());
+        DN_TRY(hipMemcpyAsync(keys, d_keys, (size_t) (h->n_rows * width), hipMemcpyDeviceToHost, h->st));
+        DN_TRY(hipStreamSynchronize(h->st));
+        return DN_OK;
+    });
 }
 
 extern "C" int dn_bam_rows_fetch(dn_bam_rows h, int64_t *pos, int64_t *op_beg, int32_t *n_op, uint32_t *ops, int64_t *name_beg,
                                  int32_t *name_len, uint8_t *names)
 {
-    g_reads_err.clear();
-    if (!h) { g_reads_err = "dn_bam_rows_fetch: bad argument"; return DN_E_INVALID; }
+    dn::clear_error();
+    if (!h) return dn::fail(DN_E_INVALID, "dn_bam_rows_fetch: bad argument");
     hipStream_t st = h->st;
     const size_t n = (size_t) h->n_rows;
-    BAM_TRY(hipSetDevice(h->device));
-    if (n > 0) {
-        if (pos) BAM_TRY(hipMemcpyAsync(pos, h->pos, sizeof(int64_t) * n, hipMemcpyDeviceToHost, st));
-        if (op_beg) BAM_TRY(hipMemcpyAsync(op_beg, h->op_beg, sizeof(int64_t) * n, hipMemcpyDeviceToHost, st));
-        if (n_op) BAM_TRY(hipMemcpyAsync(n_op, h->n_op, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
-        if (name_beg) BAM_TRY(hipMemcpyAsync(name_beg, h->name_beg, sizeof(int64_t) * n, hipMemcpyDeviceToHost, st));
-        if (name_len) BAM_TRY(hipMemcpyAsync(name_len, h->name_len, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
-    }
-    if (ops && h->n_ops > 0) BAM_TRY(hipMemcpyAsync(ops, h->ops, sizeof(uint32_t) * (size_t) h->n_ops, hipMemcpyDeviceToHost, st));
-    if (names && h->n_names > 0) BAM_TRY(hipMemcpyAsync(names, h->names, (size_t) h->n_names, hipMemcpyDeviceToHost, st));
-    BAM_TRY(hipStreamSynchronize(st));
-    return DN_OK;
+    DN_TRY(hipSetDevice(h->device));
+    return dn::synced(st, [&]() -> int {
+        if (n > 0) {
+            if (pos) DN_TRY(hipMemcpyAsync(pos, h->pos, sizeof(int64_t) * n, hipMemcpyDeviceToHost, st));
+            if (op_beg) DN_TRY(hipMemcpyAsync(op_beg, h->op_beg, sizeof(int64_t) * n, hipMemcpyDeviceToHost, st));
+            if (n_op) DN_TRY(hipMemcpyAsync(n_op, h->n_op, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+            if (name_beg) DN_TRY(hipMemcpyAsync(name_beg, h->name_beg, sizeof(int64_t) * n, hipMemcpyDeviceToHost, st));
+            if (name_len) DN_TRY(hipMemcpyAsync(name_len, h->name_len, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+        }
+        if (ops && h->n_ops > 0) DN_TRY(hipMemcpyAsync(ops, h->ops, sizeof(uint32_t) * (size_t) h->n_ops, hipMemcpyDeviceToHost, st));
+        if (names && h->n_names > 0) DN_TRY(hipMemcpyAsync(names, h->names, (size_t) h->n_names, hipMemcpyDeviceToHost, st));
+        DN_TRY(hipStreamSynchronize(st));
+        return DN_OK;
+    });
 }
 
 extern "C" int dn_bam_rows_coverage(dn_bam_rows h, const int32_t *order, const int32_t *pair_id, int64_t n_pair_ids,
@@ -1242,13 +1117,9 @@ extern "C" int dn_bam_rows_coverage(dn_bam_rows h, const int32_t *order, const i
                                     int64_t csr_cap, int64_t *nnz, int32_t *csr_idx, int64_t *csr_val,
                                     int64_t *n_isolated_reads, double *device_ms)
 {
-    int rc = DN_OK;
-    g_reads_err.clear();
-    if (!h || (h->F.paired && h->n_rows > 0 && !order)) { g_reads_err = "dn_bam_rows_coverage: bad argument"; return DN_E_INVALID; }
-    if (h->has_no_cigar) {                                  // the reference's CIGAR regex on cigarstring None
-        g_reads_err = "read " + h->no_cigar + " has no CIGAR string";
-        return DN_E_INVALID;
-    }
+    dn::clear_error();
+    if (!h || (h->F.paired && h->n_rows > 0 && !order)) return dn::fail(DN_E_INVALID, "dn_bam_rows_coverage: bad argument");
+    if (h->has_no_cigar) return dn::fail(DN_E_INVALID, "read " + h->no_cigar + " has no CIGAR string");     // the reference's CIGAR regex on cigarstring None
     COVERAGE_IO;
     const int64_t n = h->n_rows;
     hipStream_t st = h->st;
@@ -1257,75 +1128,68 @@ extern "C" int dn_bam_rows_coverage(dn_bam_rows h, const int32_t *order, const i
     dn::DeviceBuffer<int32_t> g_cnt, d_order;
     const int64_t *p_pos = h->pos, *p_beg = h->op_beg;
     const int32_t *p_cnt = h->n_op;
-    RD_TRY(hipSetDevice(h->device));
-    if (order && n > 0) {                                   // rows in the caller's order (paired: the sort by qname_unpaired)
-        h_order.assign(order, order + n);
-        for (int64_t r = 0; r < n; r++)
-            if (order[r] < 0 || order[r] >= n) { g_reads_err = "dn_bam_rows_coverage: order out of range"; return DN_E_INVALID; }
-        RD_TRY(alloc_padded(d_order, n)); RD_TRY(alloc_padded(g_pos, n)); RD_TRY(alloc_padded(g_beg, n)); RD_TRY(alloc_padded(g_cnt, n));
-        RD_TRY(hipMemcpyAsync(d_order, order, sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_bam_gather, dim3(grid_for(n)), dim3(kNT), 0, st, n, d_order.get(), h->pos.get(), h->op_beg.get(),
-                           h->n_op.get(), g_pos.get(), g_beg.get(), g_cnt.get());
-        RD_TRY(hipGetLastError());
-        p_pos = g_pos; p_beg = g_beg; p_cnt = g_cnt;
-    }
-    rc = coverage_stages(st, h->F.paired, n, p_pos, BamCigars{p_beg, p_cnt, h->ops}, pair_id, n_pair_ids, io, [&](int64_t r) {
-        const int64_t s = h_order.empty() ? r : h_order[r];
-        int64_t beg = 0;
-        int32_t cnt = 0;
-        std::vector<uint32_t> ops;
-        std::string name;
-        if (hipMemcpy(&beg, h->op_beg + s, sizeof(beg), hipMemcpyDeviceToHost) == hipSuccess &&
-            hipMemcpy(&cnt, h->n_op + s, sizeof(cnt), hipMemcpyDeviceToHost) == hipSuccess && cnt >= 0) {
-            ops.resize((size_t) cnt);
-            if (cnt > 0 && hipMemcpy(ops.data(), h->ops + beg, sizeof(uint32_t) * (size_t) cnt, hipMemcpyDeviceToHost) != hipSuccess) ops.clear();
+    DN_TRY(hipSetDevice(h->device));
+    return dn::synced(st, [&]() -> int {
+        if (order && n > 0) {                                   // rows in the caller's order (paired: the sort by qname_unpaired)
+            h_order.assign(order, order + n);
+            for (int64_t r = 0; r < n; r++)
+                if (order[r] < 0 || order[r] >= n) return dn::fail(DN_E_INVALID, "dn_bam_rows_coverage: order out of range");
+            DN_TRY(alloc_padded(d_order, n)); DN_TRY(alloc_padded(g_pos, n)); DN_TRY(alloc_padded(g_beg, n)); DN_TRY(alloc_padded(g_cnt, n));
+            DN_TRY(hipMemcpyAsync(d_order, order, sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(k_bam_gather, dim3(grid_for(n)), dim3(kNT), 0, st, n, d_order.get(), h->pos.get(), h->op_beg.get(),
+                               h->n_op.get(), g_pos.get(), g_beg.get(), g_cnt.get());
+            DN_TRY(hipGetLastError());
+            p_pos = g_pos; p_beg = g_beg; p_cnt = g_cnt;
         }
-        int64_t nb = 0;
-        int32_t nl = 0;
-        if (hipMemcpy(&nb, h->name_beg + s, sizeof(nb), hipMemcpyDeviceToHost) == hipSuccess &&
-            hipMemcpy(&nl, h->name_len + s, sizeof(nl), hipMemcpyDeviceToHost) == hipSuccess && nl > 0) {
-            name.resize((size_t) nl);
-            if (hipMemcpy(&name[0], h->names + nb, (size_t) nl, hipMemcpyDeviceToHost) != hipSuccess) name = "?";
-        }
-        return cigar_string(ops.data(), (int64_t) ops.size()) + " (read " + name + ")";
+        return coverage_stages(st, h->F.paired, n, p_pos, BamCigars{p_beg, p_cnt, h->ops}, pair_id, n_pair_ids, io, [&](int64_t r) {
+            const int64_t s = h_order.empty() ? r : h_order[r];
+            int64_t beg = 0;
+            int32_t cnt = 0;
+            std::vector<uint32_t> ops;
+            std::string name;
+            if (hipMemcpy(&beg, h->op_beg + s, sizeof(beg), hipMemcpyDeviceToHost) == hipSuccess &&
+                hipMemcpy(&cnt, h->n_op + s, sizeof(cnt), hipMemcpyDeviceToHost) == hipSuccess && cnt >= 0) {
+                ops.resize((size_t) cnt);
+                if (cnt > 0 && hipMemcpy(ops.data(), h->ops + beg, sizeof(uint32_t) * (size_t) cnt, hipMemcpyDeviceToHost) != hipSuccess) ops.clear();
+            }
+            int64_t nb = 0;
+            int32_t nl = 0;
+            if (hipMemcpy(&nb, h->name_beg + s, sizeof(nb), hipMemcpyDeviceToHost) == hipSuccess &&
+                hipMemcpy(&nl, h->name_len + s, sizeof(nl), hipMemcpyDeviceToHost) == hipSuccess && nl > 0) {
+                name.resize((size_t) nl);
+                if (hipMemcpy(&name[0], h->names + nb, (size_t) nl, hipMemcpyDeviceToHost) != hipSuccess) name = "?";
+            }
+            return cigar_string(ops.data(), (int64_t) ops.size()) + " (read " + name + ")";
+        });
     });
-done:
-    (void) hipStreamSynchronize(st);
-    return rc;
 }
 
 extern "C" int dn_bam_cigar_bounds(int device, int64_t n, const int64_t *pos, const int64_t *op_off, const uint32_t *ops,
                                    int32_t max_seg, int32_t *nseg, int64_t *bounds, int64_t *end_pos)
 {
-    int rc = DN_OK;
-    g_reads_err.clear();
-    if (n < 0 || max_seg < 1 || max_seg > kMaxSeg || (n > 0 && (!pos || !op_off || !nseg || !bounds || !end_pos))) {
-        g_reads_err = "dn_bam_cigar_bounds: bad argument";
-        return DN_E_INVALID;
-    }
+    dn::clear_error();
+    if (n < 0 || max_seg < 1 || max_seg > kMaxSeg || (n > 0 && (!pos || !op_off || !nseg || !bounds || !end_pos)))
+        return dn::fail(DN_E_INVALID, "dn_bam_cigar_bounds: bad argument");
     if (n == 0) return DN_OK;
     const int64_t n_ops = op_off[n];
     std::vector<int32_t> cnt((size_t) n);
     for (int64_t r = 0; r < n; r++) {
-        if (op_off[r + 1] < op_off[r] || op_off[r] < 0 || op_off[r + 1] - op_off[r] > INT32_MAX) {
-            g_reads_err = "dn_bam_cigar_bounds: bad op_off";
-            return DN_E_INVALID;
-        }
+        if (op_off[r + 1] < op_off[r] || op_off[r] < 0 || op_off[r + 1] - op_off[r] > INT32_MAX)
+            return dn::fail(DN_E_INVALID, "dn_bam_cigar_bounds: bad op_off");
         cnt[(size_t) r] = (int32_t) (op_off[r + 1] - op_off[r]);
     }
-    if (n_ops > 0 && !ops) { g_reads_err = "dn_bam_cigar_bounds: bad argument"; return DN_E_INVALID; }
+    if (n_ops > 0 && !ops) return dn::fail(DN_E_INVALID, "dn_bam_cigar_bounds: bad argument");
     dn::DeviceBuffer<int64_t> d_beg;
     dn::DeviceBuffer<int32_t> d_cnt;
     dn::DeviceBuffer<uint32_t> d_ops;
     dn::Stream st;
-    RD_TRY(hipSetDevice(device));
-    RD_TRY(st.create(hipStreamCreate));
-    RD_TRY(alloc_padded(d_beg, n)); RD_TRY(alloc_padded(d_cnt, n)); RD_TRY(alloc_padded(d_ops, n_ops));
-    RD_TRY(hipMemcpyAsync(d_beg, op_off, sizeof(int64_t) * (size_t) n, hipMemcpyHostToDevice, st));
-    RD_TRY(hipMemcpyAsync(d_cnt, cnt.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, st));
-    if (n_ops > 0) RD_TRY(hipMemcpyAsync(d_ops, ops, sizeof(uint32_t) * (size_t) n_ops, hipMemcpyHostToDevice, st));
-    rc = cigar_debug(st, n, pos, BamCigars{d_beg, d_cnt, d_ops}, max_seg, nseg, bounds, end_pos);
-done:
-    if (st) (void) hipStreamSynchronize(st);
-    return rc;
+    DN_TRY(hipSetDevice(device));
+    DN_TRY(st.create(hipStreamCreate));
+    return dn::synced(st, [&]() -> int {
+        DN_TRY(alloc_padded(d_beg, n)); DN_TRY(alloc_padded(d_cnt, n)); DN_TRY(alloc_padded(d_ops, n_ops));
+        DN_TRY(hipMemcpyAsync(d_beg, op_off, sizeof(int64_t) * (size_t) n, hipMemcpyHostToDevice, st));
+        DN_TRY(hipMemcpyAsync(d_cnt, cnt.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, st));
+        if (n_ops > 0) DN_TRY(hipMemcpyAsync(d_ops, ops, sizeof(uint32_t) * (size_t) n_ops, hipMemcpyHostToDevice, st));
+        return cigar_debug(st, n, pos, BamCigars{d_beg, d_cnt, d_ops}, max_seg, nseg, bounds, end_pos);
+    });
 }

@@ -73,11 +73,7 @@ def scan_window(buf, device=None):
                          _lib._p(cols['chr_hash'], u64), _lib._p(cols['start'], i64), _lib._p(cols['end'], i64),
                          _lib._p(cols['gene_beg'], i64), _lib._p(cols['gene_len'], i32), _lib._p(cols['gene_hash'], u64),
                          ctypes.byref(err_line), ctypes.byref(err_kind), ctypes.byref(copy_ms), ctypes.byref(dev_ms))
-    if rc != _lib.DN_OK:
-        msg = lib.dn_gtf_last_error().decode('utf-8', 'replace')
-        if rc == _lib.DN_E_INVALID:
-            raise ValueError(msg)
-        raise _lib.DegnormAmdError('dn_gtf_scan failed ({0}): {1}'.format(rc, msg))
+    _lib._check(rc, 'dn_gtf_scan')
     n = int(n_rows.value)
     err = (int(err_line.value), int(err_kind.value)) if err_kind.value else None
     return int(n_lines.value), {k: v[:n] for k, v in cols.items()}, err, float(copy_ms.value), float(dev_ms.value)

@@ -23,6 +23,7 @@ import re
 import numpy as np
 
 from . import _lib
+from ._lib import _p as _ptr
 
 _TOKEN = re.compile(r'(\d+)([A-Z]?)')
 
@@ -175,10 +176,6 @@ class Annotation(object):
         self.n_isolated, self.n_overlap = len(iso), len(ol_gene)
 
 
-def _ptr(a, t):
-    return a.ctypes.data_as(ctypes.POINTER(t)) if a is not None else None
-
-
 def device_read_coverage(pos, off, cig, pair_id, n_ids, ann, paired, device=None):
     """
     One dn_read_coverage call on packed reads and an Annotation: (counts int64[n_genes], overlap span vectors int64 with
@@ -205,11 +202,7 @@ def device_read_coverage(pos, off, cig, pair_id, n_ids, ann, paired, device=None
                               len(ann.iso_union), _ptr(ann.iso_union, i64),
                               n_genes, _ptr(counts, i64), _ptr(ol_cov, i64), cap, ctypes.byref(nnz),
                               _ptr(csr_idx, i32), _ptr(csr_val, i64), ctypes.byref(n_iso_reads), ctypes.byref(ms))
-    if rc != _lib.DN_OK:
-        msg = lib.dn_reads_last_error().decode('utf-8', 'replace')
-        if rc == _lib.DN_E_INVALID:
-            raise ValueError(msg)
-        raise _lib.DegnormAmdError('dn_read_coverage failed ({0}): {1}'.format(rc, msg))
+    _lib._check(rc, 'dn_read_coverage')
     k = int(nnz.value)
     return counts[:n_genes], ol_cov, csr_idx[:k].copy(), csr_val[:k].copy(), int(n_iso_reads.value), float(ms.value)
 
@@ -226,9 +219,7 @@ def device_cigar_bounds(cigars, starts, max_seg=16, device=None):
     rc = lib.dn_reads_cigar_bounds(int(os.environ.get('LOCAL_RANK', 0)) if device is None else int(device), n,
                                    _ptr(pos, ctypes.c_int64), _ptr(off, ctypes.c_int64), _ptr(cig, ctypes.c_uint8), int(max_seg),
                                    _ptr(nseg, ctypes.c_int32), _ptr(bounds, ctypes.c_int64), _ptr(end_pos, ctypes.c_int64))
-    if rc != _lib.DN_OK:
-        raise _lib.DegnormAmdError('dn_reads_cigar_bounds failed ({0}): {1}'.format(
-            rc, lib.dn_reads_last_error().decode('utf-8', 'replace')))
+    _lib._check(rc, 'dn_reads_cigar_bounds', invalid_is_value_error=False)
     b = bounds.reshape(max(n, 1), 2 * max_seg)
     out = [b[r, :2 * nseg[r]].tolist() if nseg[r] > 0 else None for r in range(n)]
     if (nseg[:n] < 0).any():

@@ -9,7 +9,10 @@
  *
  * Conventions
  *   - plain C types only; the caller allocates every host output; nothing throws across the boundary.
- *   - every function returns DN_OK (0) or a negative DN_E_* code; dn_last_error() gives the text.
+ *   - every function returns DN_OK (0) or a negative DN_E_* code; dn_last_error() gives the text.  The library keeps ONE
+ *     text per thread: dn_assemble_last_error(), dn_reads_last_error() and dn_gtf_last_error() return the same string and
+ *     stay for the callers that name their family.  A call's text is valid until the thread's next call that fails or
+ *     (the reads, BAM and inflate entry points) clears it on entry.
  *   - per-gene problems the reference would raise on (ArpackError, empty np.min, svds ValueError:
  *     SURVEY H8) are reported in the per-gene trace status instead of aborting the batch.
  *   - a handle owns one HIP device, one stream, the resident coverage and all scratch; it is not
@@ -218,7 +221,7 @@ int  dn_assemble_coverage(int device, int64_t chrom_len, int32_t p, const int64_
                           int64_t n_chunks, const int32_t *chunk_gene, const int64_t *chunk_src,
                           const int64_t *chunk_dst_in_gene, const int32_t *chunk_len,
                           float *out_packed, double *device_ms);
-const char *dn_assemble_last_error(void);
+const char *dn_assemble_last_error(void);          /* = dn_last_error() */
 
 /* Reads -> coverage and read counts (one sample, one chromosome) -------------------------------------
  * Replaces: the per-read loop of BamReadsProcessor.chromosome_coverage_read_counts (reads.py:397-774): CIGAR parsing
@@ -261,7 +264,7 @@ int  dn_read_coverage(int device, int32_t paired, int64_t n_rows, const int64_t 
  * than max_seg) as bounds[r * 2 * max_seg ..] (start, end inclusive), and end_pos[r] = pos + sum of all op lengths (:404). */
 int  dn_reads_cigar_bounds(int device, int64_t n, const int64_t *pos, const int64_t *cigar_off, const uint8_t *cigar,
                            int32_t max_seg, int32_t *nseg, int64_t *bounds, int64_t *end_pos);
-const char *dn_reads_last_error(void);
+const char *dn_reads_last_error(void);             /* = dn_last_error() */
 
 /* BAM records -> coverage and read counts (NativeBamReadsProcessor, degnorm_amd/bam.py) ------------------------------
  * The host inflates a chromosome's BGZF blocks window by window; the device decodes the records and keeps the rows the
@@ -371,7 +374,7 @@ int  dn_gtf_scan(int device, const uint8_t *buf, int64_t n_bytes, int64_t row_ca
                  int64_t *line, int64_t *chr_beg, int32_t *chr_len, uint64_t *chr_hash, int64_t *start, int64_t *end,
                  int64_t *gene_beg, int32_t *gene_len, uint64_t *gene_hash, int64_t *err_line, int32_t *err_kind,
                  double *copy_ms, double *device_ms);
-const char *dn_gtf_last_error(void);
+const char *dn_gtf_last_error(void);               /* = dn_last_error() */
 
 /* Measurement hooks (bench.py) -------------------------------------------------------------------- */
 /* Device time in ms of the most recent dn_baseline_iteration's main kernel, measured with HIP events
