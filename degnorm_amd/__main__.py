@@ -51,6 +51,8 @@ def argparser():
                     help='host threads for reading .bam files and packing genes (default 1)')
     ap.add_argument('--device-inflate', action='store_true',
                     help='inflate the BGZF blocks of the .bam files on the GPU instead of with zlib on the host')
+    ap.add_argument('--device-frame', action='store_true',
+                    help='find the record starts of the inflated .bam bytes on the GPU instead of with a serial walk on the host')
     return ap
 
 
@@ -168,7 +170,8 @@ def main(argv=None):
         run_pipeline(args.bam_files, args.bai_files, args.genome_annotation, output_dir, degnorm_iter=args.iter,
                      nmf_iter=args.nmf_iter, downsample_rate=args.downsample_rate, minimax_coverage=args.minimax_coverage,
                      skip_baseline_selection=args.skip_baseline_selection, unique_alignment=not args.non_unique_alignments,
-                     n_jobs=args.proc_per_node, inflate='device' if args.device_inflate else 'host')
+                     n_jobs=args.proc_per_node, inflate='device' if args.device_inflate else 'host',
+                     frame='device' if args.device_frame else 'host')
     logging.info('DegNorm pipeline complete! Exiting...')
     return 0
 

@@ -112,6 +112,14 @@ def load(build_if_missing=False):
     lib.dn_reads_last_error.restype = c.c_char_p
     u32 = c.c_uint32
     lib.dn_bam_frame.argtypes = [P(u8), i64, i32, P(i32), P(i64), i64, P(i64), P(i64)]
+    lib.dn_bam_frame_segments_host.argtypes = [P(u8), i64, i32, P(i32), i64, P(i64), i64, P(i64), P(i64), P(i64)]
+    lib.dn_bam_frame_device.argtypes = [c.c_int, P(u8), i64, i32, P(i32), i64, P(i64), i64, P(i64), P(i64), P(i64), P(dbl)]
+    lib.dn_bam_frame_segment_default.argtypes = []
+    lib.dn_bam_frame_segment_default.restype = i64
+    lib.dn_bam_rows_append_framed.argtypes = [vp, P(u8), i64, P(i64)]
+    lib.dn_bam_rows_inflate_framed.argtypes = [vp, P(u8), i64, i64, P(i64), P(i32), P(i32), i32, i32, P(i32), P(i64), P(i64), P(dbl), P(dbl)]
+    lib.dn_bam_rows_frame_segment.argtypes = [vp, i64]
+    lib.dn_bam_rows_frame_info.argtypes = [vp, P(i64), P(i64), P(dbl), P(dbl)]
     lib.dn_bam_rows_create.argtypes = [c.c_int, i32, i32, i32, P(vp)]
     lib.dn_bam_rows_destroy.argtypes = [vp]
     lib.dn_bam_rows_destroy.restype = None

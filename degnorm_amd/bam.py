@@ -8,6 +8,11 @@ Native BAM input for the reads stage: NativeBamReadsProcessor opens sorted, inde
               With inflate='device' the blocks of a window go to the device as they are in the file and the library's own
               DEFLATE decoder (csrc/dn_inflate.hip, one block per wavefront) builds the window where the decode kernels
               read it; the host frames a copy of it and uploads only the record offsets
+              With frame='device' the window is framed where it lies (csrc/dn_frame.hip: every segment of the window guesses
+              a record start and walks the block_size chain from it, the host stitches the per-segment table -- no window
+              byte -- and has wrong guesses walked again, so the result is the serial walk's for every input).  Together
+              with inflate='device' the inflated bytes never visit the host; the record cut by a window end waits on the
+              device for the next window
     device    (csrc/dn_reads.hip) the records of each window are decoded, filtered by the reference's rules (reads.py
               load_chromosome_reads) and appended to a device-resident row store; the coverage stages read their binary
               CIGARs in place
@@ -241,18 +246,43 @@ def reference_range(ref):
 
 # --- framing and the device row store ------------------------------------------------------------------------------------
 
-def frame_records(buf, tid=-1, last_pos=_INT32_MIN):
+def frame_records(buf, tid=-1, last_pos=_INT32_MIN, device=None, segment_bytes=None, stats=None):
     """
     Start offsets (int64) of the complete records of inflated BAM bytes, the bytes they span (the rest is a record cut by
     the end of buf) and the last record's pos.  With tid >= 0 every record must belong to tid and be sorted (ValueError).
     Runs in the library's host code: no device needed.
+
+    With `device` or `segment_bytes` the segmented algorithm of csrc/dn_frame.hip runs instead of the serial walk, with the
+    same results and errors: on GPU `device`, or (device=None) its host build, which needs no GPU.  segment_bytes: at least
+    64; None is the library's default.  stats, a dict, receives `segments`, `fixups` (segments whose guessed entry was not
+    the true one and that were walked again) and `device_ms`.
     """
     a = np.frombuffer(buf, dtype=np.uint8) if len(buf) else np.zeros(1, np.uint8)
     cap = len(buf) // 36 + 1
     off = np.empty(cap, dtype=np.int64)
     n, used, lp = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int32(last_pos)
-    _check(_lib.load().dn_bam_frame(_ptr(a, ctypes.c_uint8), len(buf), int(tid), ctypes.byref(lp), _ptr(off, ctypes.c_int64),
-                                    cap, ctypes.byref(n), ctypes.byref(used)), 'dn_bam_frame')
+    lib = _lib.load()
+    if device is None and segment_bytes is None:
+        _check(lib.dn_bam_frame(_ptr(a, ctypes.c_uint8), len(buf), int(tid), ctypes.byref(lp), _ptr(off, ctypes.c_int64),
+                                cap, ctypes.byref(n), ctypes.byref(used)), 'dn_bam_frame')
+        if stats is not None:
+            stats.update(segments=0, fixups=0, device_ms=0.0)
+        return off[:n.value], int(used.value), int(lp.value)
+    seg = 0 if segment_bytes is None else int(segment_bytes)
+    if seg != 0 and seg < 64:
+        raise ValueError('segment_bytes must be at least 64, not {0}'.format(segment_bytes))
+    fix, ms = ctypes.c_int64(0), ctypes.c_double(0.0)
+    args = (_ptr(a, ctypes.c_uint8), len(buf), int(tid), ctypes.byref(lp), seg, _ptr(off, ctypes.c_int64), cap, ctypes.byref(n),
+            ctypes.byref(used), ctypes.byref(fix))
+    try:
+        if device is None:
+            _check(lib.dn_bam_frame_segments_host(*args), 'dn_bam_frame_segments_host')
+        else:
+            _check(lib.dn_bam_frame_device(int(device), *(args + (ctypes.byref(ms),))), 'dn_bam_frame_device')
+    finally:
+        if stats is not None:
+            size = seg or int(lib.dn_bam_frame_segment_default())
+            stats.update(segments=(len(buf) + size - 1) // size, fixups=int(fix.value), device_ms=float(ms.value))
     return off[:n.value], int(used.value), int(lp.value)
 
 
@@ -299,6 +329,40 @@ class DeviceRows(object):
                'dn_bam_rows_inflate')
         data = np.ctypeslib.as_array(view, shape=(n_bytes.value,)) if n_bytes.value else np.zeros(0, np.uint8)
         return data, status[:len(blocks)], float(ms.value)
+
+    def frame_segment(self, segment_bytes):
+        """The segment size of this store's device framing (None or 0: the library's default)."""
+        _check(self.lib.dn_bam_rows_frame_segment(self.h, int(segment_bytes or 0)), 'dn_bam_rows_frame_segment')
+
+    def append_framed(self, buf):
+        """dn_bam_rows_append_framed: upload buf, frame it on the device, decode and append.  Returns the bytes consumed."""
+        a = np.frombuffer(buf, dtype=np.uint8) if len(buf) else np.zeros(1, np.uint8)
+        used = ctypes.c_int64(0)
+        _check(self.lib.dn_bam_rows_append_framed(self.h, _ptr(a, ctypes.c_uint8), len(buf), ctypes.byref(used)), 'dn_bam_rows_append_framed')
+        return int(used.value)
+
+    def inflate_framed(self, blocks, head_skip, tail_keep):
+        """
+        dn_bam_rows_inflate_framed: the next window inflated, framed, decoded and appended on the device; the record its end
+        cuts stays there.  Returns the status of every block, the bytes carried over, and the ms of inflate and framing.
+        """
+        comp, n_comp, pay_off, pay_len, isize = _block_layout(blocks)
+        isize32 = np.where(isize > 2 ** 31 - 1, -1, isize).astype(np.int32)      # the library refuses a negative size
+        status = np.zeros(max(len(blocks), 1), np.int32)
+        n_bytes, n_carry, ms, fms = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_double(0.0), ctypes.c_double(0.0)
+        i64, i32, u8 = ctypes.c_int64, ctypes.c_int32, ctypes.c_uint8
+        rc = self.lib.dn_bam_rows_inflate_framed(self.h, _ptr(comp, u8), n_comp, len(blocks), _ptr(pay_off, i64), _ptr(pay_len, i32),
+                                                 _ptr(isize32, i32), int(head_skip), int(tail_keep), _ptr(status, i32),
+                                                 ctypes.byref(n_bytes), ctypes.byref(n_carry), ctypes.byref(ms), ctypes.byref(fms))
+        _check(rc, 'dn_bam_rows_inflate_framed')
+        return status[:len(blocks)], int(n_carry.value), float(ms.value), float(fms.value)
+
+    def frame_info(self):
+        """(segments, fix-ups, framing's device ms, decode's host ms) summed over the windows this store framed on the device."""
+        n_seg, n_fix, ms, dms = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_double(0.0), ctypes.c_double(0.0)
+        _check(self.lib.dn_bam_rows_frame_info(self.h, ctypes.byref(n_seg), ctypes.byref(n_fix), ctypes.byref(ms), ctypes.byref(dms)),
+               'dn_bam_rows_frame_info')
+        return int(n_seg.value), int(n_fix.value), float(ms.value), float(dms.value)
 
     def append_resident(self, rec_off):
         if len(rec_off) == 0:
@@ -384,16 +448,23 @@ def cigar_strings(op_beg, n_op, ops):
 class NativeBamReadsProcessor(BamReadsProcessor):
 
     def __init__(self, bam_file, index_file, chroms=None, n_jobs=1, output_dir=None, unique_alignment=True, verbose=True,
-                 window_bytes=256 << 20, inflate='host'):
+                 window_bytes=256 << 20, inflate='host', frame='host', frame_segment_bytes=None):
         """
         BamReadsProcessor on the library's own BAM reader: no pysam.  n_jobs sizes the thread pool that inflates BGZF
         blocks; window_bytes bounds the inflated bytes held (on the host and on the device) besides the chromosome's rows.
         inflate='host' inflates with zlib in that pool; inflate='device' hands the compressed blocks to the library's DEFLATE
         kernel (device_rows, and with it coverage and load_chromosome_reads; the header and the strand check stay on zlib).
+        frame='host' finds the record starts of a window with the library's serial host walk; frame='device' finds them on
+        the GPU (with either inflate; the strand check stays on the host walk), in segments of frame_segment_bytes (None:
+        the library's default).  timing then has frame_device_ms and frame_fixups instead of frame_s.
         """
         if inflate not in ('host', 'device'):
             raise ValueError("inflate must be 'host' or 'device', not {0!r}".format(inflate))
+        if frame not in ('host', 'device'):
+            raise ValueError("frame must be 'host' or 'device', not {0!r}".format(frame))
         self.inflate = inflate
+        self.frame = frame
+        self.frame_segment_bytes = frame_segment_bytes
         self.window_bytes = max(int(window_bytes), 1)
         self.timing = {}
         super(NativeBamReadsProcessor, self).__init__(bam_file, index_file, chroms=chroms, n_jobs=n_jobs, output_dir=output_dir,
@@ -486,6 +557,8 @@ class NativeBamReadsProcessor(BamReadsProcessor):
         carry, last = b'', _INT32_MIN
         t = self.timing
         try:
+            if self.frame == 'device':
+                return self._device_framed(chrom, rows)
             if self.inflate == 'device':
                 return self._device_windows(chrom, rows)
             for win in self.windows(chrom):
@@ -526,6 +599,46 @@ class NativeBamReadsProcessor(BamReadsProcessor):
             carry = data[used:].tobytes()
         if carry:
             raise ValueError('{0}: a record of {1} is cut short at the end of its index range'.format(self.filename, chrom))
+        return rows
+
+    def _device_framed(self, chrom, rows):
+        """device_rows with frame='device': every window is framed on the device, wherever it was inflated."""
+        t = self.timing
+        cut = '{0}: a record of {1} is cut short at the end of its index range'.format(self.filename, chrom)
+        rows.frame_segment(self.frame_segment_bytes)
+        calls = 0.0                         # seconds in the library's one call per window: it splits them (frame_info)
+        try:
+            if self.inflate == 'device':
+                n_carry = 0
+                for batch, cbeg, ubeg, cend, uend in self._batches(chrom):
+                    t0 = time.perf_counter()
+                    status, n_carry, ms, fms = rows.inflate_framed([b for _, b in batch], ubeg if batch[0][0] == cbeg else 0,
+                                                                   uend if batch[-1][0] == cend else -1)
+                    t1 = time.perf_counter()
+                    _raise_status(status, lambda k: '{0}: the BGZF block at byte {1}'.format(self.filename, batch[k][0]))
+                    t['inflate_device_ms'] = t.get('inflate_device_ms', 0.0) + ms
+                    calls += t1 - t0
+                if n_carry:
+                    raise ValueError(cut)
+            else:
+                carry = b''
+                for win in self.windows(chrom):
+                    data = carry + win if carry else win
+                    t0 = time.perf_counter()
+                    used = rows.append_framed(data)
+                    calls += time.perf_counter() - t0
+                    carry = data[used:]
+                if carry:
+                    raise ValueError(cut)
+        finally:
+            _, fixups, ms, decode_ms = rows.frame_info()
+            t['frame_device_ms'] = t.get('frame_device_ms', 0.0) + ms
+            t['frame_fixups'] = t.get('frame_fixups', 0) + fixups
+            t['decode_s'] = t.get('decode_s', 0.0) + 1e-3 * decode_ms
+            # what is left of the calls: the copy of the window (inflate='host') or of its blocks and their inflate ('device')
+            rest = max(calls - 1e-3 * (ms + decode_ms), 0.0)
+            key = 'inflate_s' if self.inflate == 'device' else 'upload_s'
+            t[key] = t.get(key, 0.0) + rest
         return rows
 
     def load_chromosome_reads(self, chrom):

@@ -20,6 +20,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <chrono>
 #include <functional>
 #include <memory>
 #include <string>
@@ -27,6 +28,7 @@
 #include "../../include/degnorm_amd.h"
 #include "dn_host.hpp"
 #include "dn_inflate.hpp"
+#include "dn_frame.hpp"
 
 namespace {
 
@@ -585,8 +587,9 @@ extern "C" int dn_reads_cigar_bounds(int device, int64_t n, const int64_t *pos, 
 // BAM records -> device-resident rows (NativeBamReadsProcessor, degnorm_amd/bam.py).
 //
 // The host inflates one window of a chromosome's BGZF blocks and frames it (dn_bam_frame: the start of every complete
-// record); k_bam_scan decodes every record of the window and applies the reference's read filters (reads.py
-// load_chromosome_reads), three scans give each kept row its place, and k_bam_write appends the kept rows, in file order,
+// record), or the window is framed where it lies on the device (dn_frame.hip; dn_bam_rows_append_framed, and
+// dn_bam_rows_inflate_framed, after which a window's inflated bytes never visit the host); k_bam_scan decodes every
+// record of the window and applies the reference's read filters (reads.py load_chromosome_reads), three scans give each kept row its place, and k_bam_write appends the kept rows, in file order,
 // to the row store: position, binary CIGAR ops, read name and the length of its qname_unpaired prefix.  The coverage
 // stages then read the binary CIGARs in place (BamCigars).  Record fields sit at arbitrary byte offsets: every load below
 // is a byte load.
@@ -817,6 +820,15 @@ struct dn_bam_rows_s {
     dn::PinnedBuffer<uint8_t> host_win;
     dn::Event ev0, ev1;
     int64_t cap_host = 0, resident = -1;
+    // device framing (dn_bam_rows_append_framed, dn_bam_rows_inflate_framed): its work buffers, the record cut by the end of
+    // the window before (dn_bam_rows_inflate_framed keeps it on the device), the segment size asked for (0: the default), the
+    // sums dn_bam_rows_frame_info reports and the pos of the last record framed
+    dn::FrameWork frame;
+    dn::GrowBuffer<uint8_t> carry;
+    int64_t n_carry = 0, frame_segment = 0, frame_segments = 0, frame_fixups = 0;
+    double frame_ms = 0.0, framed_decode_ms = 0.0;
+    int32_t last_pos = INT32_MIN;
+    dn::Event ev2, ev3;
     std::string no_cigar;                  // the name of the first kept row without CIGAR ops ("" while there is none)
     bool has_no_cigar = false;
 };
@@ -884,19 +896,40 @@ extern "C" void dn_bam_rows_destroy(dn_bam_rows h)
 
 namespace {
 
-// Decode, filter and compact the n_rec records of the window in h->win (n_bytes of it; `window` is a host copy of the same
-// bytes, read only to name a read in an error text) and append the kept rows.
-int append_window(dn_bam_rows h, const uint8_t *window, int64_t n_bytes, const int64_t *rec_off, int64_t n_rec)
+// the record offsets of a window framed on the host, to where append_window reads them
+int upload_offsets(dn_bam_rows h, const int64_t *rec_off, int64_t n_rec)
+{
+    DN_TRY(h->rec_off.reserve(n_rec + 1, 0, h->st));
+    DN_TRY(hipMemcpyAsync(h->rec_off, rec_off, sizeof(int64_t) * (size_t) n_rec, hipMemcpyHostToDevice, h->st));
+    return DN_OK;
+}
+
+// Decode, filter and compact the n_rec records of the window in h->win (n_bytes of it), whose offsets are in h->rec_off, and
+// append the kept rows.  `window` is a host copy of the same bytes, read only to name a read in an error text; without one
+// (NULL) the at most 36 + 255 bytes of that record come from the device.
+int append_window(dn_bam_rows h, const uint8_t *window, int64_t n_bytes, int64_t n_rec)
 {
     hipStream_t st = h->st;
     int32_t tot[3];                                  // what the stream copies to the host
     unsigned long long herr[kBamNErr];
+    int64_t name_off = 0;
+    uint8_t name_rec[36 + 255];
+    const auto name_of = [&](unsigned long long i) -> std::string {
+        if (hipMemcpyAsync(&name_off, h->rec_off + i, sizeof(name_off), hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess || name_off < 0 || name_off > n_bytes)
+            return "?";
+        if (window) return bam_name(window, n_bytes, name_off);
+        const int64_t len = n_bytes - name_off < (int64_t) sizeof(name_rec) ? n_bytes - name_off : (int64_t) sizeof(name_rec);
+        if (len <= 0 || hipMemcpyAsync(name_rec, h->win + name_off, (size_t) len, hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess)
+            return "?";
+        return bam_name(name_rec, len, 0);
+    };
     return dn::synced(st, [&]() -> int {
         // per record, and one more for the totals of the scans
-        DN_TRY(h->rec_off.reserve(n_rec + 1, 0, st)); DN_TRY(h->keep.reserve(n_rec + 1, 0, st)); DN_TRY(h->w_ops.reserve(n_rec + 1, 0, st));
+        DN_TRY(h->keep.reserve(n_rec + 1, 0, st)); DN_TRY(h->w_ops.reserve(n_rec + 1, 0, st));
         DN_TRY(h->w_name.reserve(n_rec + 1, 0, st)); DN_TRY(h->rank.reserve(n_rec + 1, 0, st)); DN_TRY(h->op_rank.reserve(n_rec + 1, 0, st));
         DN_TRY(h->name_rank.reserve(n_rec + 1, 0, st));
-        DN_TRY(hipMemcpyAsync(h->rec_off, rec_off, sizeof(int64_t) * (size_t) n_rec, hipMemcpyHostToDevice, st));
         DN_TRY(hipMemsetAsync(h->err, 0xff, sizeof(unsigned long long) * kBamNErr, st));
         DN_TRY(hipMemsetAsync(h->keep + n_rec, 0, sizeof(int32_t), st));
         DN_TRY(hipMemsetAsync(h->w_ops + n_rec, 0, sizeof(int32_t), st));
@@ -914,15 +947,15 @@ int append_window(dn_bam_rows h, const uint8_t *window, int64_t n_bytes, const i
         DN_TRY(hipMemcpyAsync(herr, h->err, sizeof(herr), hipMemcpyDeviceToHost, st));
         DN_TRY(hipStreamSynchronize(st));
         if (herr[kBamErrMalformed] != ~0ull)
-            return dn::fail(DN_E_INVALID, "malformed BAM record (read " + bam_name(window, n_bytes, rec_off[herr[kBamErrMalformed]]) + ")");
+            return dn::fail(DN_E_INVALID, "malformed BAM record (read " + name_of(herr[kBamErrMalformed]) + ")");
         if (herr[kBamErrNh] != ~0ull)
-            return dn::fail(DN_E_INVALID, "read " + bam_name(window, n_bytes, rec_off[herr[kBamErrNh]]) + " has an NH tag of a non-integer type");
+            return dn::fail(DN_E_INVALID, "read " + name_of(herr[kBamErrNh]) + " has an NH tag of a non-integer type");
         if (herr[kBamErrUnsupported] != ~0ull)
-            return dn::fail(DN_E_UNSUPPORTED, "read " + bam_name(window, n_bytes, rec_off[herr[kBamErrUnsupported]]) +
+            return dn::fail(DN_E_UNSUPPORTED, "read " + name_of(herr[kBamErrUnsupported]) +
                                               " has a CIGAR op code above 8 or a CIGAR moved to the CG tag (not supported)");
         if (herr[kBamErrNoCigar] != ~0ull && !h->has_no_cigar) {
             h->has_no_cigar = true;
-            h->no_cigar = bam_name(window, n_bytes, rec_off[herr[kBamErrNoCigar]]);
+            h->no_cigar = name_of(herr[kBamErrNoCigar]);
         }
         if (h->n_rows + tot[0] > INT32_MAX - 1) return dn::fail(DN_E_UNSUPPORTED, "dn_bam_rows_append: more than 2^31 - 2 rows");
         if (tot[0] > 0) {
@@ -966,9 +999,35 @@ extern "C" int dn_bam_rows_append(dn_bam_rows h, const uint8_t *window, int64_t 
     return dn::synced(h->st, [&]() -> int {
         DN_TRY(h->win.reserve(n_bytes, 0, h->st));         // window scratch: nothing to keep (the previous append has finished)
         DN_TRY(hipMemcpyAsync(h->win, window, (size_t) n_bytes, hipMemcpyHostToDevice, h->st));
-        return append_window(h, window, n_bytes, rec_off, n_rec);
+        const int urc = upload_offsets(h, rec_off, n_rec);
+        return urc != DN_OK ? urc : append_window(h, window, n_bytes, n_rec);
     });
 }
+
+namespace {
+
+// the InflateBlock of every block of a window that starts with n_carry carried bytes; the window's size in total
+int window_blocks(const char *who, int64_t n_carry, int64_t n_comp, int64_t n_blocks, const int64_t *pay_off, const int32_t *pay_len,
+                  const int32_t *isize, int32_t head_skip, int32_t tail_keep, std::vector<dn::InflateBlock> &blk, int64_t &total)
+{
+    const std::string w(who);
+    blk.resize((size_t) n_blocks);
+    total = n_carry;
+    for (int64_t b = 0; b < n_blocks; b++) {
+        if (pay_off[b] < 0 || pay_len[b] < 0 || pay_off[b] > n_comp || pay_len[b] > n_comp - pay_off[b])
+            return dn::fail(DN_E_INVALID, w + ": payload of block " + std::to_string(b) + " outside comp");
+        if (isize[b] < 0) return dn::fail(DN_E_INVALID, w + ": block " + std::to_string(b) + " has a negative inflated size");
+        int32_t hi = isize[b], lo = 0;                  // the last block is cut first, then the first one, as the host path does
+        if (b == n_blocks - 1 && tail_keep >= 0 && tail_keep < hi) hi = tail_keep;
+        if (b == 0) lo = head_skip < hi ? head_skip : hi;
+        blk[(size_t) b] = dn::InflateBlock{pay_off[b], total, pay_len[b], isize[b], lo, hi - lo};
+        total += hi - lo;
+    }
+    if (total > INT32_MAX) return dn::fail(DN_E_INVALID, w + ": window beyond 2^31 - 1 bytes");
+    return DN_OK;
+}
+
+}  // namespace
 
 extern "C" int dn_bam_rows_inflate(dn_bam_rows h, const uint8_t *carry, int64_t n_carry, const uint8_t *comp, int64_t n_comp,
                                    int64_t n_blocks, const int64_t *pay_off, const int32_t *pay_len, const int32_t *isize,
@@ -979,20 +1038,10 @@ extern "C" int dn_bam_rows_inflate(dn_bam_rows h, const uint8_t *carry, int64_t 
     if (!h || n_carry < 0 || (n_carry > 0 && !carry) || n_comp < 0 || (n_comp > 0 && !comp) || n_blocks < 0 || n_blocks > INT32_MAX ||
         (n_blocks > 0 && (!pay_off || !pay_len || !isize || !status)) || head_skip < 0 || !host_window || !n_bytes)
         return dn::fail(DN_E_INVALID, "dn_bam_rows_inflate: bad argument");
-    std::vector<dn::InflateBlock> blk((size_t) n_blocks);
-    int64_t total = n_carry;
-    for (int64_t b = 0; b < n_blocks; b++) {
-        if (pay_off[b] < 0 || pay_len[b] < 0 || pay_off[b] > n_comp || pay_len[b] > n_comp - pay_off[b])
-            return dn::fail(DN_E_INVALID, "dn_bam_rows_inflate: payload of block " + std::to_string(b) + " outside comp");
-        if (isize[b] < 0)       // no upper bound: the ring decoder does not need one, and the host path reads over-long blocks too
-            return dn::fail(DN_E_INVALID, "dn_bam_rows_inflate: block " + std::to_string(b) + " has a negative inflated size");
-        int32_t hi = isize[b], lo = 0;                  // the last block is cut first, then the first one, as the host path does
-        if (b == n_blocks - 1 && tail_keep >= 0 && tail_keep < hi) hi = tail_keep;
-        if (b == 0) lo = head_skip < hi ? head_skip : hi;
-        blk[(size_t) b] = dn::InflateBlock{pay_off[b], total, pay_len[b], isize[b], lo, hi - lo};
-        total += hi - lo;
-    }
-    if (total > INT32_MAX) return dn::fail(DN_E_INVALID, "dn_bam_rows_inflate: window beyond 2^31 - 1 bytes");
+    std::vector<dn::InflateBlock> blk;
+    int64_t total = 0;
+    const int brc = window_blocks("dn_bam_rows_inflate", n_carry, n_comp, n_blocks, pay_off, pay_len, isize, head_skip, tail_keep, blk, total);
+    if (brc != DN_OK) return brc;
     hipStream_t st = h->st;
     DN_TRY(hipSetDevice(h->device));
     h->resident = -1;
@@ -1041,7 +1090,120 @@ extern "C" int dn_bam_rows_append_resident(dn_bam_rows h, const int64_t *rec_off
     const int rc = check_offsets("dn_bam_rows_append_resident", h->resident, rec_off, n_rec);
     if (rc != DN_OK) return rc;
     DN_TRY(hipSetDevice(h->device));
-    return dn::synced(h->st, [&]() -> int { return append_window(h, h->host_win, h->resident, rec_off, n_rec); });
+    return dn::synced(h->st, [&]() -> int {
+        const int urc = upload_offsets(h, rec_off, n_rec);
+        return urc != DN_OK ? urc : append_window(h, h->host_win, h->resident, n_rec);
+    });
+}
+
+// what every device framing of a store adds to the sums of dn_bam_rows_frame_info
+static void count_framing(dn_bam_rows h, const dn::FrameResult &R)
+{
+    h->frame_segments += R.n_segments;
+    h->frame_fixups += R.n_fixups;
+    h->frame_ms += R.device_ms;
+}
+
+extern "C" int dn_bam_rows_frame_segment(dn_bam_rows h, int64_t segment_bytes)
+{
+    dn::clear_error();
+    if (!h || (segment_bytes != 0 && segment_bytes < dn::kFrameSegmentMin))
+        return dn::fail(DN_E_INVALID, "dn_bam_rows_frame_segment: bad argument (segment_bytes is 0 or at least 64)");
+    h->frame_segment = segment_bytes;
+    return DN_OK;
+}
+
+// append_window on a window framed on the device, its host time added to the store's sum
+static int append_framed_window(dn_bam_rows h, const uint8_t *window, int64_t n_bytes, int64_t n_rec)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = n_rec > 0 ? append_window(h, window, n_bytes, n_rec) : DN_OK;
+    h->framed_decode_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return rc;
+}
+
+extern "C" int dn_bam_rows_frame_info(dn_bam_rows h, int64_t *n_segments, int64_t *n_fixups, double *device_ms, double *decode_ms)
+{
+    dn::clear_error();
+    if (!h) return dn::fail(DN_E_INVALID, "dn_bam_rows_frame_info: bad argument");
+    if (n_segments) *n_segments = h->frame_segments;
+    if (n_fixups) *n_fixups = h->frame_fixups;
+    if (device_ms) *device_ms = h->frame_ms;
+    if (decode_ms) *decode_ms = h->framed_decode_ms;
+    return DN_OK;
+}
+
+extern "C" int dn_bam_rows_append_framed(dn_bam_rows h, const uint8_t *window, int64_t n_bytes, int64_t *consumed)
+{
+    dn::clear_error();
+    if (!h || n_bytes < 0 || n_bytes > INT32_MAX || (n_bytes > 0 && !window) || !consumed)
+        return dn::fail(DN_E_INVALID, "dn_bam_rows_append_framed: bad argument");
+    dn::FrameResult R;
+    DN_TRY(hipSetDevice(h->device));
+    h->resident = -1;
+    return dn::synced(h->st, [&]() -> int {
+        DN_TRY(h->win.reserve(n_bytes, 0, h->st));
+        if (n_bytes > 0) DN_TRY(hipMemcpyAsync(h->win, window, (size_t) n_bytes, hipMemcpyHostToDevice, h->st));
+        const int rc = dn::frame_window(h->st, h->frame, h->win, n_bytes, h->F.tid, &h->last_pos, h->frame_segment, -1, h->rec_off, R);
+        count_framing(h, R);
+        if (rc != DN_OK) return rc;
+        *consumed = R.consumed;
+        return append_framed_window(h, window, n_bytes, R.n_rec);
+    });
+}
+
+extern "C" int dn_bam_rows_inflate_framed(dn_bam_rows h, const uint8_t *comp, int64_t n_comp, int64_t n_blocks, const int64_t *pay_off,
+                                          const int32_t *pay_len, const int32_t *isize, int32_t head_skip, int32_t tail_keep,
+                                          int32_t *status, int64_t *n_bytes, int64_t *n_carry, double *inflate_ms, double *frame_ms)
+{
+    dn::clear_error();
+    if (!h || n_comp < 0 || (n_comp > 0 && !comp) || n_blocks < 0 || n_blocks > INT32_MAX ||
+        (n_blocks > 0 && (!pay_off || !pay_len || !isize || !status)) || head_skip < 0 || !n_bytes || !n_carry)
+        return dn::fail(DN_E_INVALID, "dn_bam_rows_inflate_framed: bad argument");
+    std::vector<dn::InflateBlock> blk;
+    int64_t total = 0;
+    const int brc = window_blocks("dn_bam_rows_inflate_framed", h->n_carry, n_comp, n_blocks, pay_off, pay_len, isize, head_skip, tail_keep, blk, total);
+    if (brc != DN_OK) return brc;
+    hipStream_t st = h->st;
+    dn::FrameResult R;
+    DN_TRY(hipSetDevice(h->device));
+    h->resident = -1;
+    if (frame_ms) *frame_ms = 0.0;
+    return dn::synced(st, [&]() -> int {
+        DN_TRY(h->win.reserve(total, 0, st));
+        const int64_t comp_cap = dn::inflate_comp_cap(n_comp);
+        DN_TRY(h->comp.reserve(comp_cap, 0, st));
+        DN_TRY(h->blk.reserve(n_blocks, 0, st)); DN_TRY(h->blk_status.reserve(n_blocks, 0, st));
+        if (!h->ev2) { DN_TRY(h->ev2.create(hipEventCreate)); DN_TRY(h->ev3.create(hipEventCreate)); }
+        // the record cut by the end of the window before goes first: it waited in h->carry while h->win was reused
+        if (h->n_carry > 0) DN_TRY(hipMemcpyAsync(h->win, h->carry, (size_t) h->n_carry, hipMemcpyDeviceToDevice, st));
+        if (n_comp > 0) DN_TRY(hipMemcpyAsync(h->comp, comp, (size_t) n_comp, hipMemcpyHostToDevice, st));
+        if (n_blocks > 0) DN_TRY(hipMemcpyAsync(h->blk, blk.data(), sizeof(dn::InflateBlock) * (size_t) n_blocks, hipMemcpyHostToDevice, st));
+        DN_TRY(hipEventRecord(h->ev2, st));
+        DN_TRY(dn::inflate_launch(st, h->comp, comp_cap, h->blk, n_blocks, h->win, h->blk_status));
+        DN_TRY(hipEventRecord(h->ev3, st));
+        if (n_blocks > 0) DN_TRY(hipMemcpyAsync(status, h->blk_status, sizeof(int32_t) * (size_t) n_blocks, hipMemcpyDeviceToHost, st));
+        DN_TRY(hipStreamSynchronize(st));
+        if (inflate_ms) {
+            float ms = 0.f;
+            DN_TRY(hipEventElapsedTime(&ms, h->ev2, h->ev3));
+            *inflate_ms = ms;
+        }
+        *n_bytes = total;
+        *n_carry = h->n_carry;
+        for (int64_t b = 0; b < n_blocks; b++)
+            if (status[b] != 0) return DN_OK;               // a block that failed left its bytes unspecified: the caller reports it
+        const int rc = dn::frame_window(st, h->frame, h->win, total, h->F.tid, &h->last_pos, h->frame_segment, -1, h->rec_off, R);
+        count_framing(h, R);
+        if (frame_ms) *frame_ms = R.device_ms;
+        if (rc != DN_OK) return rc;
+        const int64_t left = total - R.consumed;
+        DN_TRY(h->carry.reserve(left, 0, st));
+        if (left > 0) DN_TRY(hipMemcpyAsync(h->carry, h->win + R.consumed, (size_t) left, hipMemcpyDeviceToDevice, st));
+        h->n_carry = left;
+        *n_carry = left;
+        return append_framed_window(h, nullptr, total, R.n_rec);
+    });
 }
 
 extern "C" int dn_bam_rows_info(dn_bam_rows h, int64_t *n_rows, int64_t *n_ops, int64_t *n_name_bytes, int32_t *max_key_len)

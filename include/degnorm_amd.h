@@ -350,6 +350,40 @@ int  dn_bam_rows_inflate(dn_bam_rows h, const uint8_t *carry, int64_t n_carry, c
                          int32_t *status, double *device_ms);
 int  dn_bam_rows_append_resident(dn_bam_rows h, const int64_t *rec_off, int64_t n_rec);
 
+/* Record framing on the device (csrc/dn_frame.hip) ----------------------------------------------------------------------
+ * dn_bam_frame's walk, block_size to block_size, is serial.  Here the window is cut into segments of segment_bytes (at
+ * least 64; 0: the library's default, dn_bam_frame_segment_default()): every segment guesses where a record starts in it
+ * and walks the chain from there, the host stitches the per-segment results from offset 0 and has a segment whose guess
+ * was not the true entry walked again (a fix-up), and a last pass writes the offsets and checks refID and order.  Offsets,
+ * *n_rec, *consumed, *last_pos and every error -- code, text, and which one wins when a window holds several -- equal
+ * dn_bam_frame's for every input, whatever the guesses were; *n_fixups (nullable) counts the segments walked again.
+ *   dn_bam_frame_segments_host  the same source compiled for the host, one segment after the other; no device is touched.
+ *   dn_bam_frame_device   copy buf to `device`, frame it there, copy the offsets back to rec_off (host memory).  device_ms
+ *                         (nullable): first framing kernel to the last, by HIP events.  For tests and tools.
+ *   dn_bam_rows_append_framed   dn_bam_rows_append without offsets: upload the window, frame it on the device, decode it
+ *                         and append its kept rows.  *consumed = the bytes the complete records span; the caller carries
+ *                         the rest to its next window.  The store remembers the last pos between calls.
+ *   dn_bam_rows_inflate_framed  dn_bam_rows_inflate, then framing, decoding and appending on the device: no host copy of
+ *                         the window.  The record cut by the window end stays on the device and starts the next window;
+ *                         *n_carry = its bytes, *n_bytes = the bytes of this window.  When a block failed (status[b] != 0)
+ *                         the call returns DN_OK before framing, as dn_bam_rows_inflate does.  inflate_ms / frame_ms
+ *                         (nullable): the inflate kernel and the framing of this window.
+ *   dn_bam_rows_frame_segment   the segment size of a store's framing from now on (0: the default).
+ *   dn_bam_rows_frame_info      sums over every window a store framed on the device (nullable outputs): segments, fix-ups,
+ *                         the device ms of framing, and the host's ms in decoding and appending those windows.
+ * Errors: dn_reads_last_error(). */
+int64_t dn_bam_frame_segment_default(void);
+int  dn_bam_frame_segments_host(const uint8_t *buf, int64_t n_bytes, int32_t tid, int32_t *last_pos, int64_t segment_bytes,
+                                int64_t *rec_off, int64_t cap, int64_t *n_rec, int64_t *consumed, int64_t *n_fixups);
+int  dn_bam_frame_device(int device, const uint8_t *buf, int64_t n_bytes, int32_t tid, int32_t *last_pos, int64_t segment_bytes,
+                         int64_t *rec_off, int64_t cap, int64_t *n_rec, int64_t *consumed, int64_t *n_fixups, double *device_ms);
+int  dn_bam_rows_append_framed(dn_bam_rows h, const uint8_t *window, int64_t n_bytes, int64_t *consumed);
+int  dn_bam_rows_inflate_framed(dn_bam_rows h, const uint8_t *comp, int64_t n_comp, int64_t n_blocks, const int64_t *pay_off,
+                                const int32_t *pay_len, const int32_t *isize, int32_t head_skip, int32_t tail_keep,
+                                int32_t *status, int64_t *n_bytes, int64_t *n_carry, double *inflate_ms, double *frame_ms);
+int  dn_bam_rows_frame_segment(dn_bam_rows h, int64_t segment_bytes);
+int  dn_bam_rows_frame_info(dn_bam_rows h, int64_t *n_segments, int64_t *n_fixups, double *device_ms, double *decode_ms);
+
 /* GTF annotation scan (GeneAnnotationLoader, degnorm_amd/loaders.py) --------------------------------------------------
  * Replaces the reference's read_csv of the nine columns, its lower-case `apply` on the feature column and its regex
  * `apply` per exon row (loaders.py:128-152, _attribute_to_gene :102-112).  buf holds the n_bytes raw bytes of a GTF file,

@@ -6,14 +6,19 @@ indexed BAM, and on a paired variant (the same reads named <i // 2>.1 / .2, mate
   inflate_ms        BGZF inflate of the chromosome's blocks: zlib on the host in n_jobs threads (--inflate host), or the
                     library's DEFLATE kernel with the copy of the compressed blocks in and of the window back (--inflate device)
   inflate_device_ms the DEFLATE kernel alone, by events (0 with --inflate host); inflate_gbps: inflated bytes over it
-  frame_ms          host record framing (dn_bam_frame)
-  decode_ms         the append calls: window upload, decode / filter kernels, compaction into the row store
+  frame_ms          host record framing (dn_bam_frame; 0 with --frame device)
+  frame_device_ms   record framing on the device (--frame device): first framing kernel to the last of every window, by events,
+                    the host's stitch of the segment table between them included; frame_fixups: segments walked again
+  decode_ms         the append calls: window upload, decode / filter kernels, compaction into the row store (with --frame
+                    device the library's own clock around decode and compaction; the upload of a host-inflated window is
+                    upload_ms then)
   coverage_ms       the coverage call on the stored rows (paired: with the key download and the host sort)
   coverage_device_ms  device time of the coverage stages (events on its stream)
   reads_per_s       end to end: reads / chromosome_coverage_read_counts (files written, index and header already read)
   in_memory_reads_per_s  chromosome_coverage_read_counts_df on the same reads held as a DataFrame
 
     python tools/bam_speed.py [--reads 2000000] [--jobs 4] [--reps 3] [--dir DIR] [--inflate host|device] [--level 1]
+                               [--frame host|device] [--segment-bytes N] [--cases se,pe]
 
 --level is the deflate level of the written files (the fixture writer's level 1 on random sequence bytes is nearly
 literal-only; real files are level 6 and full of matches).  Files found in --dir from an earlier run with the same
@@ -41,11 +46,11 @@ from degnorm_amd import bam                          # noqa: E402
 from degnorm_amd import reads as dr                  # noqa: E402
 
 
-def _best(path, chrom, ov, gene_df, exon_df, out, jobs, reps, inflate):
+def _best(path, chrom, ov, gene_df, exon_df, out, jobs, reps, inflate, frame='host', segment_bytes=None):
     best, rows = None, []
     for k in range(reps + 1):                        # the first run loads the library and warms the device up
         proc = bam.NativeBamReadsProcessor(path, path + '.bai', output_dir=os.path.join(out, str(k)), n_jobs=jobs, verbose=False,
-                                           inflate=inflate)
+                                           inflate=inflate, frame=frame, frame_segment_bytes=segment_bytes)
         os.makedirs(proc.save_dir, exist_ok=True)
         proc.timing = {}
         t0 = time.perf_counter()
@@ -53,14 +58,15 @@ def _best(path, chrom, ov, gene_df, exon_df, out, jobs, reps, inflate):
         e2e = time.perf_counter() - t0
         t = proc.timing
         row = {'inflate_ms': 1e3 * t.get('inflate_s', 0), 'inflate_device_ms': t.get('inflate_device_ms', 0),
-               'frame_ms': 1e3 * t.get('frame_s', 0), 'decode_ms': 1e3 * t.get('decode_s', 0),
+               'frame_ms': 1e3 * t.get('frame_s', 0), 'frame_device_ms': t.get('frame_device_ms', 0),
+               'frame_fixups': t.get('frame_fixups', 0), 'upload_ms': 1e3 * t.get('upload_s', 0), 'decode_ms': 1e3 * t.get('decode_s', 0),
                'coverage_ms': 1e3 * t.get('coverage_s', 0), 'coverage_device_ms': t.get('coverage_device_ms', 0), 'e2e_ms': 1e3 * e2e}
         if k > 0:
             rows.append(row)
             if best is None or row['e2e_ms'] < best['e2e_ms']:
                 best = row
     best = {key: round(v, 3 if key.endswith('device_ms') else 1) for key, v in best.items()}
-    for key in ('inflate_ms', 'e2e_ms'):
+    for key in ('inflate_ms', 'frame_ms', 'frame_device_ms', 'e2e_ms'):
         best[key + '_min'] = round(min(r[key] for r in rows), 1)
         best[key + '_max'] = round(max(r[key] for r in rows), 1)
     return best
@@ -74,6 +80,9 @@ def main():
     ap.add_argument('--dir', default=None)
     ap.add_argument('--inflate', choices=['host', 'device'], default='host')
     ap.add_argument('--level', type=int, default=1)
+    ap.add_argument('--frame', choices=['host', 'device'], default='host')
+    ap.add_argument('--segment-bytes', type=int, default=None, help='segment size of --frame device (default: the library\'s)')
+    ap.add_argument('--cases', default='se,pe', help='se, pe or se,pe')
     a = ap.parse_args()
     reads, chrom_len, ov, gene_df, exon_df = rf.scale_case(n_reads=a.reads)
     work = a.dir or tempfile.mkdtemp(prefix='bam_speed_')
@@ -81,9 +90,10 @@ def main():
         se = pd.DataFrame({'ref': 0, 'pos': reads.pos.values, 'qname': reads.qname.astype(str).values, 'cigar': reads.cigar.values})
         pe = se.assign(qname=['{0}.{1}'.format(i // 2, 1 + i % 2) for i in range(len(se))], next_ref=0)
         t0 = time.perf_counter()
-        files = {name: os.path.join(work, '{0}_{1}_l{2}.bam'.format(name, a.reads, a.level)) for name in ('se', 'pe')}
+        cases = [c for c in ('se', 'pe') if c in a.cases.split(',')]
+        files = {name: os.path.join(work, '{0}_{1}_l{2}.bam'.format(name, a.reads, a.level)) for name in cases}
         for name, df in (('se', se), ('pe', pe)):
-            if not (os.path.isfile(files[name]) and os.path.isfile(files[name] + '.bai')):
+            if name in files and not (os.path.isfile(files[name]) and os.path.isfile(files[name] + '.bai')):
                 bf.write_bam(files[name], [('chrS', chrom_len)], df, level=a.level)
         write_s = time.perf_counter() - t0
         inflated = {name: int(bam.bgzf_blocks(files[name])[2].sum()) for name in files}
@@ -93,12 +103,12 @@ def main():
             dr.chromosome_coverage_read_counts_df(reads, chrom_len, ov, gene_df, exon_df, False)
             dt = time.perf_counter() - t0
             in_mem = dt if in_mem is None else min(in_mem, dt)
-        out = {'tool': 'bam_speed', 'reads': a.reads, 'jobs': a.jobs, 'inflate': a.inflate, 'level': a.level,
-               'bam_mb': round(os.path.getsize(files['se']) / 2 ** 20, 1), 'inflated_mb': round(inflated['se'] / 2 ** 20, 1),
+        out = {'tool': 'bam_speed', 'reads': a.reads, 'jobs': a.jobs, 'inflate': a.inflate, 'frame': a.frame, 'level': a.level,
+               'bam_mb': round(os.path.getsize(files[cases[0]]) / 2 ** 20, 1), 'inflated_mb': round(inflated[cases[0]] / 2 ** 20, 1),
                'write_s': round(write_s, 1)}
-        for name in ('se', 'pe'):
-            row = _best(files[name], 'chrS', ov, gene_df, exon_df, os.path.join(work, 'out_{0}_{1}'.format(name, a.inflate)),
-                        a.jobs, a.reps, a.inflate)
+        for name in cases:
+            row = _best(files[name], 'chrS', ov, gene_df, exon_df, os.path.join(work, 'out_{0}_{1}_{2}'.format(name, a.inflate, a.frame)),
+                        a.jobs, a.reps, a.inflate, a.frame, a.segment_bytes)
             if row['inflate_device_ms'] > 0:
                 row['inflate_gbps'] = round(inflated[name] / (row['inflate_device_ms'] * 1e-3) / 1e9, 2)
             row['reads_per_s'] = round(a.reads / (row['e2e_ms'] * 1e-3))
