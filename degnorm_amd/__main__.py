@@ -5,8 +5,11 @@
     python -m degnorm_amd --bam-dir DIR -g genes.gtf -o out
     python -m degnorm_amd -w PREVIOUS_OUTPUT_DIR -o out
 
-The flags and their validation follow the reference.  Not offered: --plot-genes, the HTML report, creating missing .bai
-files (a missing index is an error here; the reference shells out to samtools) and the MPI command (see
+    python -m degnorm_amd --bam-dir DIR --create-bai -g genes.gtf -o out
+
+The flags and their validation follow the reference.  With --create-bai a .bam file without a .bai file next to it gets
+one before the run (the reference shells out to samtools for this; here degnorm_amd.bam.create_index builds it on the GPU);
+without the flag a missing index is an error.  Not offered: --plot-genes, the HTML report and the MPI command (see
 degnorm_amd.warm_start --mpi for the sharded NMF-OA run).
 """
 import argparse
@@ -21,8 +24,8 @@ def argparser():
     ap = argparse.ArgumentParser(
         prog='python -m degnorm_amd',
         description='DegNorm (RNA-seq degradation normalization) from .bam and .gtf files on an AMD Instinct GPU.',
-        epilog='Not available in this command: --plot-genes, the HTML summary report, creation of missing .bai index files '
-               '(index your .bam files first, e.g. with samtools index) and the MPI command.')
+        epilog='A .bam file needs its .bai index file; --create-bai makes the missing ones.  Not available in this command: '
+               '--plot-genes, the HTML summary report and the MPI command.')
     ap.add_argument('--bam-files', nargs='+', default=None,
                     help='sorted .bam alignment files, one per sample (single-end or paired), at least two')
     ap.add_argument('--bai-files', nargs='+', default=None,
@@ -49,6 +52,9 @@ def argparser():
                     help='keep reads flagged NH > 1 (by default only uniquely aligned reads count)')
     ap.add_argument('-p', '--proc-per-node', type=int, default=1,
                     help='host threads for reading .bam files and packing genes (default 1)')
+    ap.add_argument('--create-bai', action='store_true',
+                    help='create the .bai index file X.bai of every X.bam that has none next to it, on the GPU, before the run '
+                         '(not with --bai-files)')
     ap.add_argument('--device-inflate', action='store_true',
                     help='inflate the BGZF blocks of the .bam files on the GPU instead of with zlib on the host')
     ap.add_argument('--device-frame', action='store_true',
@@ -62,19 +68,26 @@ def bai_from_bam_file(bam_file):
     return bam_file[:-3] + 'bai'
 
 
-def _default_bai_files(bam_files):
-    bai_files = []
+def _default_bai_files(bam_files, create=False):
+    """(X.bai of every X.bam, the .bam files whose X.bai is missing); without `create` a missing one is an error."""
+    bai_files, create_bai_files = [], []
     for bam_file in bam_files:
         bai_file = re.sub('.bam$', '.bai', bam_file)
         if not os.path.isfile(bai_file):
-            raise FileNotFoundError('No .bai index file {0} for {1}: index the .bam file first (e.g. samtools index), or name '
-                                    'the index files with --bai-files.'.format(bai_from_bam_file(bam_file), bam_file))
+            if not create:
+                raise FileNotFoundError('No .bai index file {0} for {1}: pass --create-bai to have it made, index the .bam file '
+                                        'first (e.g. samtools index), or name the index files with --bai-files.'
+                                        .format(bai_from_bam_file(bam_file), bam_file))
+            bai_file = bai_from_bam_file(bam_file)
+            create_bai_files.append(bam_file)
         bai_files.append(bai_file)
-    return bai_files
+    return bai_files, create_bai_files
 
 
 def validate_args(args):
-    """The reference's checks on parsed arguments (utils.py:338-482); fills args.bam_files / args.bai_files."""
+    """The reference's checks on parsed arguments (utils.py:338-482); fills args.bam_files / args.bai_files, and
+    args.create_bai_files with the .bam files whose index is to be made first (empty without args.create_bai)."""
+    create = getattr(args, 'create_bai', False)
     if (not args.bam_files and not args.bam_dir) and (not args.warm_start_dir):
         raise ValueError('Must specify either --bam-files, --bam-dir, or --warm-start-dir as a data input option.')
     n_cpu = os.cpu_count() or 1
@@ -91,12 +104,13 @@ def validate_args(args):
             logging.warning('Using warm-start directory. Supplied .bam files, .bam directory, '
                             'and genome annotation file will be ignored.')
         args.bam_files = args.bai_files = args.bam_dir = args.genome_annotation = None
+        args.create_bai_files = None
         return args
     if not args.genome_annotation:
         raise ValueError('If warm-start directory not specified, gene annotation file must be specified!')
     if not os.path.isfile(args.genome_annotation):
         raise FileNotFoundError('Gene annotation file {0} not found.'.format(args.genome_annotation))
-    bam_files, bai_files = [], []
+    bam_files, bai_files, create_bai_files = [], [], []
     if args.bam_dir:
         if args.bam_files is not None or args.bai_files is not None:
             raise ValueError('Do not specify both a --bam-dir and either --bam-files and/or --bai-files.'
@@ -106,7 +120,7 @@ def validate_args(args):
         bam_files = [os.path.join(args.bam_dir, f) for f in sorted(os.listdir(args.bam_dir)) if f.endswith('.bam')]
         if len(bam_files) < 2:
             raise ValueError('Only found {0} .bam files within directory {1}'.format(len(bam_files), args.bam_dir))
-        bai_files = _default_bai_files(bam_files)
+        bai_files, create_bai_files = _default_bai_files(bam_files, create)
     else:
         for bam_file in args.bam_files:
             if not bam_file.endswith('.bam'):
@@ -124,12 +138,12 @@ def validate_args(args):
                     raise FileNotFoundError('Count not find .bai file {0}'.format(bai_file))
                 bai_files.append(bai_file)
         else:
-            bai_files = _default_bai_files(bam_files)
+            bai_files, create_bai_files = _default_bai_files(bam_files, create)
     if len(bam_files) < 2:
         raise ValueError('Fewer than 2 .bam files were found. Not sufficiently many to run DegNorm.')
     if len(bam_files) != len(set(bam_files)):
         raise ValueError('Supplied .bam files are not uniquely named!')
-    args.bam_files, args.bai_files = bam_files, bai_files
+    args.bam_files, args.bai_files, args.create_bai_files = bam_files, bai_files, create_bai_files
     return args
 
 
@@ -167,6 +181,11 @@ def main(argv=None):
                             minimax_coverage=args.minimax_coverage)
     else:
         from .pipeline import run_pipeline
+        if args.create_bai_files:
+            from .utils import create_index_file
+            for k, bam_file in enumerate(args.create_bai_files):
+                logging.info('creating index file for {0} -- {1} / {2}'.format(bam_file, k + 1, len(args.create_bai_files)))
+                create_index_file(bam_file, device=int(os.environ.get('LOCAL_RANK', 0)))
         run_pipeline(args.bam_files, args.bai_files, args.genome_annotation, output_dir, degnorm_iter=args.iter,
                      nmf_iter=args.nmf_iter, downsample_rate=args.downsample_rate, minimax_coverage=args.minimax_coverage,
                      skip_baseline_selection=args.skip_baseline_selection, unique_alignment=not args.non_unique_alignments,

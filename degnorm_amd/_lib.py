@@ -135,6 +135,13 @@ def load(build_if_missing=False):
     lib.dn_bam_rows_coverage.argtypes = [vp, P(i32), P(i32), i64] + lib.dn_read_coverage.argtypes[8:]
     lib.dn_bam_cigar_bounds.argtypes = [c.c_int, i64, P(i64), P(i64), P(u32), i32, P(i32), P(i64), P(i64)]
     u64 = c.c_uint64
+    lib.dn_bai_create.argtypes = [c.c_int, i32, i64, P(vp)]
+    lib.dn_bai_destroy.argtypes = [vp]
+    lib.dn_bai_destroy.restype = None
+    lib.dn_bai_window.argtypes = [vp, P(u8), i64, i64, P(i64), P(i32), P(i32), P(i64), i32, P(i32), P(i64), P(dbl), P(dbl), P(dbl)]
+    lib.dn_bai_window_host.argtypes = [vp, P(u8), i64, i64, P(i32), P(i64), i32, P(i64)]
+    lib.dn_bai_finish.argtypes = [vp, i64, P(i64)]
+    lib.dn_bai_fetch.argtypes = [vp, P(i32), P(i32), P(u64), P(i32), P(i32), P(u64), P(u64)]
     lib.dn_gtf_scan.argtypes = [c.c_int, P(c.c_uint8), i64, i64, P(i64), P(i64), P(i64), P(i64), P(i32), P(u64), P(i64), P(i64),
                                 P(i64), P(i32), P(u64), P(i64), P(i32), P(dbl), P(dbl)]
     lib.dn_gtf_last_error.restype = c.c_char_p

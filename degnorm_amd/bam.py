@@ -19,6 +19,10 @@ Native BAM input for the reads stage: NativeBamReadsProcessor opens sorted, inde
 
 Single-end reads never come back to the host.  Paired reads bring back only their qname_unpaired keys: the host sorts them
 as pandas' sort_values does (numpy's quicksort on fixed-width bytes) and hands the order and the pair ids back.
+
+A file without an index gets one from build_index / create_index (csrc/dn_bai.hip): one pass over every record of the file,
+inflated, framed and indexed on the device window by window (or, device=None, with zlib and the host build of the same
+source); parse_bai / BamIndex.tobytes / write_bai read and write whole .bai files, index_chunks is the region query.
 """
 import ctypes
 import os
@@ -668,3 +672,250 @@ class NativeBamReadsProcessor(BamReadsProcessor):
             rows.close()
         csr, ol_cov_dict, read_counts = coverage_outputs(ann, counts, ol_cov, idx, val, n_iso_reads)
         return csr, ol_cov_dict, read_counts, n_reads
+
+
+# --- creating an index ---------------------------------------------------------------------------------------------------
+
+class BamIndex(object):
+    """
+    A .bai index.  `refs` holds per reference a dict with `bins`, the list of (bin id, chunks) in the order of the file --
+    chunks a (n, 2) uint64 array of [begin, end) virtual offsets; the pseudo-bin 37450 is one of the entries -- and
+    `ioffset`, the linear index (uint64).  build_index writes the bins in ascending order and the pseudo-bin last;
+    parse_bai keeps whatever order the file has, so tobytes() gives the file back.  n_no_coor: the count of records
+    without a reference, None for a file that ends before it.
+    """
+
+    def __init__(self, refs, n_no_coor=None):
+        self.refs = refs
+        self.n_no_coor = n_no_coor
+
+    def pseudo(self, tid):
+        """(offset of the first record, end of the last, mapped, unmapped) of a reference, or None without a pseudo-bin."""
+        for bin_id, ch in self.refs[tid]['bins']:
+            if bin_id == PSEUDO_BIN:
+                return tuple(int(x) for x in ch.reshape(-1)[:4])
+        return None
+
+    def tobytes(self):
+        out = [b'BAI\x01', struct.pack('<i', len(self.refs))]
+        for ref in self.refs:
+            out.append(struct.pack('<i', len(ref['bins'])))
+            for bin_id, ch in ref['bins']:
+                out.append(struct.pack('<Ii', bin_id, len(ch)))
+                out.append(np.ascontiguousarray(ch, dtype='<u8').tobytes())
+            out.append(struct.pack('<i', len(ref['ioffset'])))
+            out.append(np.ascontiguousarray(ref['ioffset'], dtype='<u8').tobytes())
+        if self.n_no_coor is not None:
+            out.append(struct.pack('<Q', self.n_no_coor))
+        return b''.join(out)
+
+
+def parse_bai(path):
+    """The whole of a .bai index file as a BamIndex."""
+    with open(path, 'rb') as f:
+        b = f.read()
+    if b[:4] != b'BAI\x01':
+        raise ValueError('{0} is not a .bai index'.format(path))
+    try:
+        n_ref = struct.unpack_from('<i', b, 4)[0]
+        p, refs = 8, []
+        for _ in range(n_ref):
+            n_bin = struct.unpack_from('<i', b, p)[0]
+            p += 4
+            bins = []
+            for _ in range(n_bin):
+                bin_id, n_chunk = struct.unpack_from('<Ii', b, p)
+                p += 8
+                bins.append((bin_id, np.frombuffer(b, dtype='<u8', count=2 * n_chunk, offset=p).reshape(n_chunk, 2).astype(np.uint64)))
+                p += 16 * n_chunk
+            n_intv = struct.unpack_from('<i', b, p)[0]
+            p += 4
+            refs.append({'bins': bins, 'ioffset': np.frombuffer(b, dtype='<u8', count=n_intv, offset=p).astype(np.uint64)})
+            p += 8 * n_intv
+    except (struct.error, ValueError) as e:
+        raise ValueError('{0}: truncated .bai index ({1})'.format(path, e))
+    return BamIndex(refs, struct.unpack_from('<Q', b, p)[0] if len(b) >= p + 8 else None)
+
+
+def write_bai(index, path):
+    """Write a BamIndex to `path`: to a temporary file next to it, renamed when complete."""
+    tmp = '{0}.tmp{1}'.format(path, os.getpid())
+    try:
+        with open(tmp, 'wb') as f:
+            f.write(index.tobytes())
+        os.replace(tmp, path)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+    return path
+
+
+def _host_inflate(bam_file, batch, pool):
+    """The data of the blocks of batch by zlib; a block that fails is named with the text of the library's own decoder."""
+    blocks = [b for _, b in batch]
+    try:
+        return list(pool.map(inflate_block, blocks)) if pool is not None else [inflate_block(b) for b in blocks]
+    except (zlib.error, ValueError, struct.error) as e:
+        comp, n_comp, pay_off, pay_len, isize = _block_layout(blocks)
+        n = len(blocks)
+        out_off = np.zeros(n + 1, np.int64)
+        np.cumsum(np.clip(isize[:n], 0, 65536), out=out_off[1:])
+        out, status = np.zeros(int(out_off[-1]) + 1, np.uint8), np.zeros(max(n, 1), np.int32)
+        i64, i32, u8 = ctypes.c_int64, ctypes.c_int32, ctypes.c_uint8
+        if n and int(isize[:n].max()) <= 65536:
+            _check(_lib.load().dn_bgzf_inflate_host(_ptr(comp, u8), n_comp, n, _ptr(pay_off, i64), _ptr(pay_len, i32), _ptr(out_off, i64),
+                                                    _ptr(out, u8), _ptr(status, i32)), 'dn_bgzf_inflate_host')
+            _raise_status(status[:n], lambda k: '{0}: the BGZF block at byte {1}'.format(bam_file, batch[k][0]))
+        raise ValueError('{0}: a BGZF block at or after byte {1} does not inflate: {2}'.format(bam_file, batch[0][0], e))
+
+
+def build_index(bam_file, device=None, n_jobs=1, window_bytes=256 << 20, segment_bytes=None, stats=None):
+    """
+    The .bai index of a coordinate-sorted BAM file as a BamIndex, from one pass over all its records (csrc/dn_bai.hip; the
+    index is defined in include/degnorm_amd.h).  device=k: the blocks of about window_bytes of inflated data go to GPU k as
+    they are in the file and are inflated, framed and indexed there; only the tables of run heads and linear-index claims
+    come back.  device=None: the blocks are inflated with zlib in n_jobs threads and the library's host build of the same
+    source walks them; no GPU is needed.  Both give the same index and the same errors (ValueError naming the file and
+    the record).  segment_bytes: of the framing (None: the library's default).  stats, a dict, receives
+    `inflate_device_ms`, `frame_device_ms`, `index_device_ms`, `frame_fixups`, `records`, `chunks` and `windows`.
+    """
+    if not has_eof_block(bam_file):
+        raise ValueError('{0}: no BGZF end-of-file block; the file is truncated'.format(bam_file))
+    if segment_bytes is not None and int(segment_bytes) < 64:
+        raise ValueError('segment_bytes must be at least 64, not {0}'.format(segment_bytes))
+    window_bytes = max(int(256 << 20 if window_bytes is None else window_bytes), 1)
+    lib = _lib.load()
+    i64, i32, u8, u64 = ctypes.c_int64, ctypes.c_int32, ctypes.c_uint8, ctypes.c_uint64
+    pool = ThreadPoolExecutor(max_workers=int(n_jobs)) if device is None and int(n_jobs) > 1 else None
+    h = ctypes.c_void_p()
+    ms = {'inflate_device_ms': 0.0, 'frame_device_ms': 0.0, 'index_device_ms': 0.0}
+    end = {'coffset': None, 'open': False}          # the block behind the last one that holds a byte
+
+    def blocks():
+        for off, blk in iter_blocks(bam_file):
+            if end['open']:
+                end['coffset'] = off
+            end['open'] = struct.unpack_from('<I', blk, len(blk) - 4)[0] > 0
+            yield off, blk
+
+    def call(rc, what):
+        try:
+            _check(rc, what)
+        except ValueError as e:
+            raise ValueError('{0}: {1}'.format(bam_file, e))
+
+    def window(batch, head_skip):
+        n_rec = i64(0)
+        coffset = np.array([off for off, _ in batch], dtype=np.int64)
+        if device is None:
+            data = _host_inflate(bam_file, batch, pool)
+            isize = np.array([len(d) for d in data], dtype=np.int64)
+            isize32 = np.where(isize > 2 ** 31 - 1, -1, isize).astype(np.int32)
+            joined = np.frombuffer(b''.join(data), dtype=np.uint8) if int(isize.sum()) else np.zeros(1, np.uint8)
+            call(lib.dn_bai_window_host(h, _ptr(joined, u8), int(isize.sum()), len(batch), _ptr(isize32, i32), _ptr(coffset, i64),
+                                        int(head_skip), ctypes.byref(n_rec)), 'dn_bai_window_host')
+            return
+        comp, n_comp, pay_off, pay_len, isize = _block_layout([b for _, b in batch])
+        isize32 = np.where(isize > 2 ** 31 - 1, -1, isize).astype(np.int32)      # the library refuses a negative size
+        status = np.zeros(max(len(batch), 1), np.int32)
+        t = [ctypes.c_double(0.0) for _ in range(3)]
+        call(lib.dn_bai_window(h, _ptr(comp, u8), n_comp, len(batch), _ptr(pay_off, i64), _ptr(pay_len, i32), _ptr(isize32, i32),
+                               _ptr(coffset, i64), int(head_skip), _ptr(status, i32), ctypes.byref(n_rec), ctypes.byref(t[0]),
+                               ctypes.byref(t[1]), ctypes.byref(t[2])), 'dn_bai_window')
+        for key, v in zip(('inflate_device_ms', 'frame_device_ms', 'index_device_ms'), t):
+            ms[key] += float(v.value)
+        _raise_status(status[:len(batch)], lambda k: '{0}: the BGZF block at byte {1}'.format(bam_file, batch[k][0]))
+
+    try:
+        it = blocks()
+        data, got, first = bytearray(), None, None
+        for off, blk in it:                          # the header, on zlib whatever the device: it may span several blocks
+            start = len(data)
+            data += _host_inflate(bam_file, [(off, blk)], None)[0]
+            got = parse_header(data)
+            if got is not None:
+                first = (off, blk)
+                break
+        if got is None:
+            raise ValueError('{0}: BAM header cut short'.format(bam_file))
+        header_end, refs = got
+        call(lib.dn_bai_create(-1 if device is None else int(device), len(refs), int(segment_bytes or 0), ctypes.byref(h)), 'dn_bai_create')
+        # the first window starts inside the block in which the header ends
+        batch, size, head_skip = [first], len(data) - header_end, header_end - start
+        del data
+        for off, blk in it:
+            if size >= window_bytes:
+                window(batch, head_skip)
+                batch, size, head_skip = [], 0, 0
+            batch.append((off, blk))
+            size += struct.unpack_from('<I', blk, len(blk) - 4)[0]
+        if batch:
+            window(batch, head_skip)
+        if end['coffset'] is None or end['open']:
+            raise ValueError('{0}: no BGZF end-of-file block; the file is truncated'.format(bam_file))
+        sizes = np.zeros(8, dtype=np.int64)
+        call(lib.dn_bai_finish(h, int(end['coffset']) << 16, _ptr(sizes, i64)), 'dn_bai_finish')
+        n_bins, n_chunks, n_intv = (int(x) for x in sizes[:3])
+        n_ref = len(refs)
+        ref_n_bin, ref_n_intv = np.zeros(max(n_ref, 1), np.int32), np.zeros(max(n_ref, 1), np.int32)
+        pseudo = np.zeros(max(4 * n_ref, 1), np.uint64)
+        bin_id, bin_n_chunk = np.zeros(max(n_bins, 1), np.int32), np.zeros(max(n_bins, 1), np.int32)
+        chunks, ioffset = np.zeros(max(2 * n_chunks, 1), np.uint64), np.zeros(max(n_intv, 1), np.uint64)
+        call(lib.dn_bai_fetch(h, _ptr(ref_n_bin, i32), _ptr(ref_n_intv, i32), _ptr(pseudo, u64), _ptr(bin_id, i32), _ptr(bin_n_chunk, i32),
+                              _ptr(chunks, u64), _ptr(ioffset, u64)), 'dn_bai_fetch')
+    finally:
+        if h:
+            lib.dn_bai_destroy(h)
+        if pool is not None:
+            pool.shutdown()
+    out, b, c, w = [], 0, 0, 0
+    chunks = chunks[:2 * n_chunks].reshape(n_chunks, 2)
+    for r in range(n_ref):
+        bins = []
+        for k in range(b, b + int(ref_n_bin[r])):
+            bins.append((int(bin_id[k]), chunks[c:c + int(bin_n_chunk[k])].copy()))
+            c += int(bin_n_chunk[k])
+        b += int(ref_n_bin[r])
+        if bins:
+            bins.append((PSEUDO_BIN, pseudo[4 * r:4 * r + 4].reshape(2, 2).copy()))
+        out.append({'bins': bins, 'ioffset': ioffset[w:w + int(ref_n_intv[r])].copy()})
+        w += int(ref_n_intv[r])
+    if stats is not None:
+        stats.update(ms, frame_fixups=int(sizes[6]), records=int(sizes[3]), chunks=n_chunks, windows=int(sizes[5]))
+    return BamIndex(out, int(sizes[4]))
+
+
+def create_index(bam_file, bai_file=None, overwrite=False, **kw):
+    """Build the index of bam_file (build_index's keywords) and write it to bai_file (default bam_file + '.bai'); its path."""
+    bai_file = bam_file + '.bai' if bai_file is None else bai_file
+    if os.path.exists(bai_file) and not overwrite:
+        raise FileExistsError('{0} exists; pass overwrite=True to replace it'.format(bai_file))
+    return write_bai(build_index(bam_file, **kw), bai_file)
+
+
+def reg2bins(beg, end):
+    """The bins that may hold records overlapping [beg, end) (SAM specification 5.3)."""
+    beg, end = max(int(beg), 0), min(int(end), 1 << 29) - 1
+    bins = [0]
+    for shift, first in ((26, 1), (23, 9), (20, 73), (17, 585), (14, 4681)):
+        bins.extend(range(first + (beg >> shift), first + (end >> shift) + 1))
+    return bins
+
+
+def index_chunks(index, tid, beg, end):
+    """
+    The [begin, end) virtual-offset ranges a reader has to scan for the records of reference tid that overlap [beg, end):
+    the chunks of reg2bins(beg, end) that end above the linear index's lower bound for beg, sorted and coalesced.
+    """
+    ref = index.refs[tid]
+    ioffset = ref['ioffset']
+    low = int(ioffset[min(max(int(beg), 0) >> 14, len(ioffset) - 1)]) if len(ioffset) else 0
+    want = set(reg2bins(beg, end))
+    found = sorted((int(b), int(e)) for bin_id, ch in ref['bins'] if bin_id in want for b, e in ch.tolist() if e > low)
+    out = []
+    for b, e in found:
+        if out and b <= out[-1][1]:
+            out[-1] = (out[-1][0], max(out[-1][1], e))
+        else:
+            out.append((b, e))
+    return out

@@ -1,0 +1,683 @@
+// dn_bai.hip -- the .bai index of a coordinate-sorted BAM file, built from a pass over every record on the device.
+//
+// A window (the record cut by the window before + the inflated BGZF blocks of about window_bytes) is inflated
+// (dn::inflate_launch) and framed (dn::frame_window, tid = -1) where it lies; then, one lane per record:
+//
+//   records   k_bai_records reads refID, pos, flag and the CIGAR, computes [beg, end), the bin (reg2bin), the packed
+//             (refID, bin) key and the record's virtual offset -- a binary search of the window's piece table, which says for
+//             every stretch of window bytes which block (file offset) and which byte of it they are; carried bytes keep the
+//             pieces of the blocks they came from -- and checks order against the record before (the window's first record
+//             against the carried state of the last record of the window before).  The first error wins (atomicMin)
+//   max-scan  within a reference records are sorted, so the smallest vbeg over a 16 kb window of the linear index is that
+//             of the first record in file order that overlaps it.  With E(r) the largest (end - 1) >> 14 of the reference's
+//             earlier records, record r claims the windows max(beg >> 14, E(r) + 1) .. (end - 1) >> 14.  refID does not
+//             decrease, so E comes from one plain inclusive max-scan of refID << 32 | ((end - 1) >> 14) + 1: a later
+//             reference outweighs every window of an earlier one.  No atomics and no dense per-reference array
+//   flags     k_bai_flags marks run heads (the key differs from the record before) and claims (the range is not empty)
+//   scatter   after two exclusive sums, k_bai_scatter writes the heads (key, vbeg, ordinal in the window, unmapped records
+//             before it) and the claims (refID, first and last window, vbeg), and the last lane leaves the carried state
+//
+// Only these two small tables return to the host.  There they are stitched (a run that goes on across a window boundary is
+// one run; a run ends where the next begins), and dn_bai_finish sorts the runs by key (stably: file order within a bin),
+// joins chunks that touch in one block, and fills the linear index.
+//
+// The three per-record steps are __host__ __device__ functions; the _host entry points run them in plain loops on bytes the
+// caller inflated, under the same stitch, so the index is testable without a device.
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+#include <stdint.h>
+#include <algorithm>
+#include <numeric>
+#include <string>
+#include <vector>
+#include "../../include/degnorm_amd.h"
+#include "dn_host.hpp"
+#include "dn_inflate.hpp"
+#include "dn_frame.hpp"
+
+#define DN_HD __host__ __device__ __forceinline__
+
+namespace {
+
+constexpr int kNT = 256;
+constexpr int64_t kMaxCoord = (int64_t) 1 << 29;
+constexpr uint32_t kUnplaced = 0xffffffffu;        // the reference part of the key of a record with refID < 0
+
+enum { kBaiOk = 0, kBaiShape = 1, kBaiRef = 2, kBaiRefOrder = 3, kBaiPosOrder = 4, kBaiRange = 5, kBaiOffset = 6 };
+
+// window bytes [win, the next piece's win) are the bytes uoff .. of the BGZF block at file offset coffset
+struct Piece {
+    int64_t win, coffset;
+    int32_t uoff, pad;
+};
+
+// what the next window needs of the last record before it: any = 0 before the first record of the file
+struct Carry {
+    uint64_t key, emax;
+    int32_t ref, pos, any, pad;
+};
+
+struct Head {
+    uint64_t key, vbeg;
+    int32_t idx, unmapped_before;      // the record's ordinal in its window; placed records with flag & 4 before it there
+};
+
+struct Claim {
+    uint64_t vbeg;
+    int32_t ref;
+    uint32_t lohi;                     // first window << 16 | last window
+};
+
+struct Totals {
+    int64_t heads, unmapped, claims;
+};
+
+// per-record arrays of one window
+struct Recs {
+    uint64_t *key, *vbeg, *emax_in, *emax;       // emax: the inclusive max-scan of emax_in
+    uint32_t *win;                               // beg >> 14 << 16 | (end - 1) >> 14
+    uint8_t *fl;                                 // bit 0: placed and flag & 4
+    uint64_t *hs, *hs_sum;                       // head flag | unmapped flag << 32, and its exclusive sum
+    int32_t *cf, *cf_sum;                        // claim flag, and its exclusive sum
+};
+
+DN_HD uint32_t b_u16(const uint8_t *p) { return (uint32_t) p[0] | ((uint32_t) p[1] << 8); }
+DN_HD uint32_t b_u32(const uint8_t *p)
+{
+    return (uint32_t) p[0] | ((uint32_t) p[1] << 8) | ((uint32_t) p[2] << 16) | ((uint32_t) p[3] << 24);
+}
+
+DN_HD uint32_t ref_key(int32_t ref) { return ref < 0 ? kUnplaced : (uint32_t) ref; }
+
+// SAM specification 5.3; 0 <= beg < end <= 2^29
+DN_HD uint32_t reg2bin(int64_t beg, int64_t end)
+{
+    --end;
+    if (beg >> 14 == end >> 14) return (uint32_t) (((1 << 15) - 1) / 7 + (beg >> 14));
+    if (beg >> 17 == end >> 17) return (uint32_t) (((1 << 12) - 1) / 7 + (beg >> 17));
+    if (beg >> 20 == end >> 20) return (uint32_t) (((1 << 9) - 1) / 7 + (beg >> 20));
+    if (beg >> 23 == end >> 23) return (uint32_t) (((1 << 6) - 1) / 7 + (beg >> 23));
+    if (beg >> 26 == end >> 26) return (uint32_t) (((1 << 3) - 1) / 7 + (beg >> 26));
+    return 0;
+}
+
+DN_HD uint64_t piece_voffset(const Piece *pc, int32_t n_pieces, int64_t o)
+{
+    int32_t lo = 0, hi = n_pieces - 1;             // the last piece with win <= o; piece 0 starts at 0
+    while (lo < hi) {
+        const int32_t mid = (lo + hi + 1) >> 1;
+        if (pc[mid].win <= o) lo = mid; else hi = mid - 1;
+    }
+    const int64_t u = pc[lo].uoff + (o - pc[lo].win);
+    return u < 65536 ? (uint64_t) pc[lo].coffset << 16 | (uint64_t) u : ~(uint64_t) 0;     // 16 bits for the place in the block
+}
+
+// Record i of the window: its entries of R, and kBaiOk or what is wrong with it.  frame_window established that the
+// record lies inside the window; the bounds are checked again so that offsets that do not belong to w cannot lead outside.
+DN_HD int bai_record(const uint8_t *w, int64_t n_bytes, const int64_t *rec_off, int64_t i, const Piece *pc, int32_t n_pieces,
+                     int32_t n_ref, const Carry &cin, const Recs &R)
+{
+    const int64_t o = rec_off[i];
+    R.key[i] = (uint64_t) kUnplaced << 32; R.vbeg[i] = 0; R.emax_in[i] = 0; R.win[i] = 0; R.fl[i] = 0;
+    if (o < 0 || o + 36 > n_bytes) return kBaiShape;
+    const int64_t bs = (int32_t) b_u32(w + o), l_name = w[o + 12], n_cig = b_u16(w + o + 16);
+    if (bs < 32 || o + 4 + bs > n_bytes || 32 + l_name + 4 * n_cig > bs) return kBaiShape;
+    const int32_t ref = (int32_t) b_u32(w + o + 4), pos = (int32_t) b_u32(w + o + 8);
+    const uint32_t flag = b_u16(w + o + 18);
+    int64_t rlen = 0;
+    const uint8_t *c = w + o + 36 + l_name;
+    for (int64_t k = 0; k < n_cig; k++) {
+        const uint32_t op = b_u32(c + 4 * k), code = op & 15;
+        if (code == 0 || code == 2 || code == 3 || code == 7 || code == 8) rlen += op >> 4;
+    }
+    if ((flag & 4) || n_cig == 0 || rlen == 0) rlen = 1;
+    int64_t beg = pos, end = beg + rlen;
+    if (ref >= 0) {
+        if (beg < 0) beg = 0;
+        if (end <= 0) end = 1;
+    }
+    const bool in_range = beg <= kMaxCoord && end <= kMaxCoord;
+    const uint32_t rk = ref_key(ref);
+    const uint32_t bin = ref >= 0 && in_range ? reg2bin(beg, end) : 0;
+    const uint32_t bw = ref >= 0 && in_range ? (uint32_t) (beg >> 14) : 0, ew = ref >= 0 && in_range ? (uint32_t) ((end - 1) >> 14) : 0;
+    R.key[i] = (uint64_t) rk << 32 | bin;
+    R.vbeg[i] = piece_voffset(pc, n_pieces, o);
+    R.emax_in[i] = (uint64_t) rk << 32 | (ref >= 0 ? ew + 1 : 0);
+    R.win[i] = bw << 16 | ew;
+    R.fl[i] = ref >= 0 && (flag & 4) ? 1 : 0;
+    bool has_prev = cin.any != 0;
+    int32_t pref = cin.ref, ppos = cin.pos;
+    if (i > 0) {
+        const int64_t po = rec_off[i - 1];
+        has_prev = po >= 0 && po + 12 <= n_bytes;
+        if (has_prev) { pref = (int32_t) b_u32(w + po + 4); ppos = (int32_t) b_u32(w + po + 8); }
+    }
+    if (ref >= n_ref) return kBaiRef;
+    if (has_prev && rk < ref_key(pref)) return kBaiRefOrder;
+    if (has_prev && ref >= 0 && ref == pref && pos < ppos) return kBaiPosOrder;
+    if (!in_range) return kBaiRange;
+    if (R.vbeg[i] == ~(uint64_t) 0) return kBaiOffset;
+    return kBaiOk;
+}
+
+// Is record i the head of a run, and which windows of the linear index does it claim (lo > hi: none)?
+DN_HD void bai_flags(const Recs &R, int64_t i, const Carry &cin, bool &head, uint32_t &lo, uint32_t &hi)
+{
+    const uint64_t key = R.key[i];
+    const uint64_t prev_key = i > 0 ? R.key[i - 1] : cin.any ? cin.key : ~(uint64_t) 0;
+    head = key != prev_key;
+    uint64_t pe = i > 0 ? R.emax[i - 1] : 0;
+    if (cin.any && cin.emax > pe) pe = cin.emax;
+    const uint32_t rk = (uint32_t) (key >> 32), bw = R.win[i] >> 16;
+    const uint32_t past = (uint32_t) (pe >> 32) == rk ? (uint32_t) pe : 0;         // E + 1, or 0 for the reference's first record
+    lo = bw > past ? bw : past;
+    hi = R.win[i] & 0xffff;
+    if (rk == kUnplaced) { lo = 1; hi = 0; }
+}
+
+DN_HD void bai_flag_pass(const Recs &R, int64_t i, const Carry &cin)
+{
+    bool head;
+    uint32_t lo, hi;
+    bai_flags(R, i, cin, head, lo, hi);
+    R.hs[i] = (uint64_t) (head ? 1 : 0) | (uint64_t) (R.fl[i] & 1) << 32;
+    R.cf[i] = lo <= hi ? 1 : 0;
+}
+
+DN_HD void bai_scatter_pass(const uint8_t *w, const int64_t *rec_off, const Recs &R, int64_t i, int64_t n_rec, const Carry &cin,
+                            Head *heads, Claim *claims, Totals *tot, Carry *cout)
+{
+    bool head;
+    uint32_t lo, hi;
+    bai_flags(R, i, cin, head, lo, hi);
+    const uint64_t s = R.hs_sum[i];
+    if (head) heads[(uint32_t) s] = Head{R.key[i], R.vbeg[i], (int32_t) i, (int32_t) (s >> 32)};
+    if (lo <= hi) claims[R.cf_sum[i]] = Claim{R.vbeg[i], (int32_t) (R.key[i] >> 32), lo << 16 | hi};
+    if (i == n_rec - 1) {
+        const uint64_t t = s + R.hs[i];
+        *tot = Totals{(int64_t) (uint32_t) t, (int64_t) (t >> 32), (int64_t) R.cf_sum[i] + R.cf[i]};
+        const int64_t o = rec_off[i];
+        uint64_t e = R.emax[i];
+        if (cin.any && cin.emax > e) e = cin.emax;
+        *cout = Carry{R.key[i], e, (int32_t) b_u32(w + o + 4), (int32_t) b_u32(w + o + 8), 1, 0};
+    }
+}
+
+__global__ __launch_bounds__(kNT) void k_bai_records(const uint8_t *__restrict__ w, int64_t n_bytes, const int64_t *__restrict__ rec_off,
+                                                     int64_t n_rec, const Piece *__restrict__ pc, int32_t n_pieces, int32_t n_ref,
+                                                     const Carry *__restrict__ cin, Recs R, unsigned long long *__restrict__ err)
+{
+    const Carry c = *cin;
+    for (int64_t i = (int64_t) blockIdx.x * kNT + threadIdx.x; i < n_rec; i += (int64_t) gridDim.x * kNT) {
+        const int e = bai_record(w, n_bytes, rec_off, i, pc, n_pieces, n_ref, c, R);
+        if (e != kBaiOk) atomicMin(err, (unsigned long long) i << 3 | (unsigned long long) e);
+    }
+}
+
+__global__ __launch_bounds__(kNT) void k_bai_flags(int64_t n_rec, const Carry *__restrict__ cin, Recs R)
+{
+    const Carry c = *cin;
+    for (int64_t i = (int64_t) blockIdx.x * kNT + threadIdx.x; i < n_rec; i += (int64_t) gridDim.x * kNT) bai_flag_pass(R, i, c);
+}
+
+__global__ __launch_bounds__(kNT) void k_bai_scatter(const uint8_t *__restrict__ w, const int64_t *__restrict__ rec_off, int64_t n_rec,
+                                                     const Carry *__restrict__ cin, Recs R, Head *__restrict__ heads,
+                                                     Claim *__restrict__ claims, Totals *__restrict__ tot, Carry *__restrict__ cout)
+{
+    const Carry c = *cin;
+    for (int64_t i = (int64_t) blockIdx.x * kNT + threadIdx.x; i < n_rec; i += (int64_t) gridDim.x * kNT)
+        bai_scatter_pass(w, rec_off, R, i, n_rec, c, heads, claims, tot, cout);
+}
+
+inline unsigned grid_for(int64_t n)
+{
+    const int64_t g = (n + kNT - 1) / kNT;
+    return (unsigned) (g < 1 ? 1 : g > (1 << 20) ? (1 << 20) : g);
+}
+
+struct Run {
+    uint64_t key, vbeg, vend;
+    int64_t n, n_unmapped;
+};
+
+}  // namespace
+
+struct dn_bai_s {
+    int device = -1;                   // < 0: the host build
+    int32_t n_ref = 0;
+    int64_t segment = 0;
+    int64_t n_records = 0, n_windows = 0, n_fixups = 0;
+    bool failed = false, finished = false;
+    std::vector<Piece> carry_pieces;   // of the record cut by the end of the window before, rebased to offset 0
+    int64_t n_carry = 0;
+    std::vector<Run> runs;             // in file order
+    std::vector<Claim> claims;
+    // the host build: the carried bytes and the carried state
+    std::vector<uint8_t> h_carry;
+    Carry h_state{0, 0, 0, 0, 0, 0};
+    // the device path
+    dn::Stream st;
+    dn::GrowBuffer<uint8_t> win, comp, carry;
+    dn::GrowBuffer<dn::InflateBlock> blk;
+    dn::GrowBuffer<int32_t> blk_status;
+    dn::GrowBuffer<int64_t> rec_off;
+    dn::GrowBuffer<Piece> pieces;
+    dn::GrowBuffer<uint64_t> key, vbeg, emax_in, emax, hs, hs_sum;
+    dn::GrowBuffer<uint32_t> rwin;
+    dn::GrowBuffer<uint8_t> fl;
+    dn::GrowBuffer<int32_t> cf, cf_sum;
+    dn::GrowBuffer<Head> heads;
+    dn::GrowBuffer<Claim> d_claims;
+    dn::DeviceBuffer<Carry> state;     // two entries: read one, write the other
+    dn::DeviceBuffer<Totals> totals;
+    dn::DeviceBuffer<unsigned long long> err;
+    int parity = 0;
+    dn::FrameWork frame;
+    dn::Scratch scratch;
+    dn::Event ev0, ev1, ev2, ev3;
+    // what dn_bai_finish built
+    std::vector<int32_t> ref_n_bin, ref_n_intv, bin_id, bin_n_chunk;
+    std::vector<uint64_t> ref_pseudo, chunks, ioffset;
+    int64_t n_no_coor = 0;
+};
+
+namespace {
+
+int record_error(dn_bai h, int code, int64_t idx, int32_t ref, int32_t pos)
+{
+    const std::string who = "record " + std::to_string(h->n_records + idx) + " (refID " + std::to_string(ref) + ", position " + std::to_string(pos) + ")";
+    h->failed = true;
+    switch (code) {
+    case kBaiShape: return dn::fail(DN_E_INVALID, "malformed BAM " + who + ": its read name and CIGAR do not fit inside the record");
+    case kBaiRef: return dn::fail(DN_E_INVALID, who + " names a reference the header does not have (" + std::to_string(h->n_ref) + " references)");
+    case kBaiRefOrder: return dn::fail(DN_E_INVALID, "BAM file is not sorted by coordinate: " + who + " follows a record of a later reference");
+    case kBaiPosOrder: return dn::fail(DN_E_INVALID, "BAM file is not sorted by coordinate: " + who + " follows a larger position of the same reference");
+    case kBaiRange: return dn::fail(DN_E_INVALID, who + " reaches beyond position 2^29: a .bai index cannot hold it");
+    default: return dn::fail(DN_E_INVALID, who + " starts beyond byte 65535 of its BGZF block: a virtual offset cannot hold it");
+    }
+}
+
+// the pieces of a window: those of the carried bytes, then one per block that keeps a byte; the window's size
+int window_pieces(dn_bai h, const char *who, int64_t n_blocks, const int32_t *isize, const int64_t *coffset, int32_t head_skip,
+                  std::vector<Piece> &pc, std::vector<dn::InflateBlock> *blk, const int64_t *pay_off, const int32_t *pay_len, int64_t n_comp,
+                  int64_t &total)
+{
+    const std::string w(who);
+    pc = h->carry_pieces;
+    total = h->n_carry;
+    if (blk) blk->resize((size_t) n_blocks);
+    for (int64_t b = 0; b < n_blocks; b++) {
+        if (isize[b] < 0) return dn::fail(DN_E_INVALID, w + ": block " + std::to_string(b) + " has a negative inflated size");
+        if (coffset[b] < 0 || coffset[b] >= ((int64_t) 1 << 48)) return dn::fail(DN_E_INVALID, w + ": file offset of block " + std::to_string(b) + " outside 0 .. 2^48");
+        if (blk && (pay_off[b] < 0 || pay_len[b] < 0 || pay_off[b] > n_comp || pay_len[b] > n_comp - pay_off[b]))
+            return dn::fail(DN_E_INVALID, w + ": payload of block " + std::to_string(b) + " outside comp");
+        const int32_t lo = b == 0 ? (head_skip < isize[b] ? head_skip : isize[b]) : 0, keep = isize[b] - lo;
+        if (blk) (*blk)[(size_t) b] = dn::InflateBlock{pay_off[b], total, pay_len[b], isize[b], lo, keep};
+        if (keep > 0) pc.push_back(Piece{total, coffset[b], lo, 0});
+        total += keep;
+    }
+    if (total > INT32_MAX) return dn::fail(DN_E_INVALID, w + ": window beyond 2^31 - 1 bytes");
+    return DN_OK;
+}
+
+// the pieces of the bytes [consumed, total) of the window, rebased: the next window's carry
+void carry_pieces(dn_bai h, const std::vector<Piece> &pc, int64_t consumed, int64_t total)
+{
+    std::vector<Piece> out;
+    for (size_t k = 0; k < pc.size(); k++) {
+        const int64_t end = k + 1 < pc.size() ? pc[k + 1].win : total;
+        if (end <= consumed) continue;
+        const int64_t from = pc[k].win > consumed ? pc[k].win : consumed;
+        out.push_back(Piece{from - consumed, pc[k].coffset, (int32_t) (pc[k].uoff + (from - pc[k].win)), 0});
+    }
+    h->carry_pieces.swap(out);
+    h->n_carry = total - consumed;
+}
+
+// stitch one window's tables onto the runs and claims so far
+void absorb(dn_bai h, int64_t n_rec, const Totals &tot, const Head *heads, const Claim *cl)
+{
+    int64_t at = 0, unm = 0;
+    for (int64_t j = 0; j < tot.heads; j++) {
+        if (!h->runs.empty()) {
+            Run &r = h->runs.back();
+            r.n += heads[j].idx - at;
+            r.n_unmapped += heads[j].unmapped_before - unm;
+            r.vend = heads[j].vbeg;
+        }
+        h->runs.push_back(Run{heads[j].key, heads[j].vbeg, 0, 0, 0});
+        at = heads[j].idx;
+        unm = heads[j].unmapped_before;
+    }
+    if (!h->runs.empty()) {
+        h->runs.back().n += n_rec - at;
+        h->runs.back().n_unmapped += tot.unmapped - unm;
+    }
+    h->claims.insert(h->claims.end(), cl, cl + tot.claims);
+    h->n_records += n_rec;
+}
+
+int check_handle(dn_bai h, const char *who, bool device)
+{
+    if (!h || (h->device >= 0) != device) return dn::fail(DN_E_INVALID, std::string(who) + ": bad argument");
+    if (h->failed || h->finished) return dn::fail(DN_E_STATE, std::string(who) + ": the index is finished or has failed");
+    return DN_OK;
+}
+
+// the index kernels on the n_rec records of the window h->win (n_bytes), whose offsets are in h->rec_off
+int index_window(dn_bai h, int64_t n_bytes, int64_t n_rec, const std::vector<Piece> &pc, std::vector<Head> &heads, std::vector<Claim> &cl,
+                 Totals &tot, unsigned long long &h_err, int64_t &h_off, uint8_t *h_rec)
+{
+    hipStream_t st = h->st;
+    DN_TRY(h->pieces.reserve((int64_t) pc.size(), 0, st));
+    DN_TRY(h->key.reserve(n_rec, 0, st)); DN_TRY(h->vbeg.reserve(n_rec, 0, st)); DN_TRY(h->emax_in.reserve(n_rec, 0, st));
+    DN_TRY(h->emax.reserve(n_rec, 0, st)); DN_TRY(h->hs.reserve(n_rec, 0, st)); DN_TRY(h->hs_sum.reserve(n_rec, 0, st));
+    DN_TRY(h->rwin.reserve(n_rec, 0, st)); DN_TRY(h->fl.reserve(n_rec, 0, st)); DN_TRY(h->cf.reserve(n_rec, 0, st));
+    DN_TRY(h->cf_sum.reserve(n_rec, 0, st)); DN_TRY(h->heads.reserve(n_rec, 0, st)); DN_TRY(h->d_claims.reserve(n_rec, 0, st));
+    const Recs R{h->key.get(), h->vbeg.get(), h->emax_in.get(), h->emax.get(), h->rwin.get(), h->fl.get(), h->hs.get(), h->hs_sum.get(),
+                 h->cf.get(), h->cf_sum.get()};
+    const Carry *cin = h->state.get() + h->parity;
+    Carry *cout = h->state.get() + (h->parity ^ 1);
+    const unsigned grid = grid_for(n_rec);
+    DN_TRY(hipMemcpyAsync(h->pieces, pc.data(), sizeof(Piece) * pc.size(), hipMemcpyHostToDevice, st));
+    DN_TRY(hipMemsetAsync(h->err, 0xff, sizeof(unsigned long long), st));
+    DN_TRY(hipEventRecord(h->ev2, st));
+    hipLaunchKernelGGL(k_bai_records, dim3(grid), dim3(kNT), 0, st, (const uint8_t *) h->win.get(), n_bytes, (const int64_t *) h->rec_off.get(), n_rec,
+                       (const Piece *) h->pieces.get(), (int32_t) pc.size(), h->n_ref, cin, R, h->err.get());
+    DN_TRY(hipGetLastError());
+    DN_TRY(hipMemcpyAsync(&h_err, h->err, sizeof(h_err), hipMemcpyDeviceToHost, st));
+    DN_TRY(hipStreamSynchronize(st));
+    if (h_err != ~0ull) {
+        const int64_t idx = (int64_t) (h_err >> 3);
+        DN_TRY(hipMemcpyAsync(&h_off, h->rec_off + idx, sizeof(h_off), hipMemcpyDeviceToHost, st));
+        DN_TRY(hipStreamSynchronize(st));
+        int32_t ref = -1, pos = -1;
+        if (h_off >= 0 && h_off + 12 <= n_bytes) {
+            DN_TRY(hipMemcpyAsync(h_rec, h->win + h_off, 12, hipMemcpyDeviceToHost, st));
+            DN_TRY(hipStreamSynchronize(st));
+            ref = (int32_t) b_u32(h_rec + 4);
+            pos = (int32_t) b_u32(h_rec + 8);
+        }
+        return record_error(h, (int) (h_err & 7), idx, ref, pos);
+    }
+    DN_TRY(h->scratch.run([&](void *tmp, size_t &bytes) {
+        return hipcub::DeviceScan::InclusiveScan(tmp, bytes, R.emax_in, R.emax, hipcub::Max(), (int) n_rec, st);
+    }));
+    hipLaunchKernelGGL(k_bai_flags, dim3(grid), dim3(kNT), 0, st, n_rec, cin, R);
+    DN_TRY(hipGetLastError());
+    DN_TRY(h->scratch.run([&](void *tmp, size_t &bytes) { return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, R.hs, R.hs_sum, (int) n_rec, st); }));
+    DN_TRY(h->scratch.run([&](void *tmp, size_t &bytes) { return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, R.cf, R.cf_sum, (int) n_rec, st); }));
+    hipLaunchKernelGGL(k_bai_scatter, dim3(grid), dim3(kNT), 0, st, (const uint8_t *) h->win.get(), (const int64_t *) h->rec_off.get(), n_rec, cin, R,
+                       h->heads.get(), h->d_claims.get(), h->totals.get(), cout);
+    DN_TRY(hipGetLastError());
+    DN_TRY(hipEventRecord(h->ev3, st));
+    DN_TRY(hipMemcpyAsync(&tot, h->totals, sizeof(Totals), hipMemcpyDeviceToHost, st));
+    DN_TRY(hipStreamSynchronize(st));
+    if (tot.heads < 0 || tot.heads > n_rec || tot.claims < 0 || tot.claims > n_rec) return dn::fail(DN_E_STATE, "dn_bai_window: table sizes outside the window");
+    heads.resize((size_t) tot.heads);
+    cl.resize((size_t) tot.claims);
+    if (tot.heads > 0) DN_TRY(hipMemcpyAsync(heads.data(), h->heads, sizeof(Head) * heads.size(), hipMemcpyDeviceToHost, st));
+    if (tot.claims > 0) DN_TRY(hipMemcpyAsync(cl.data(), h->d_claims, sizeof(Claim) * cl.size(), hipMemcpyDeviceToHost, st));
+    DN_TRY(hipStreamSynchronize(st));
+    h->parity ^= 1;
+    return DN_OK;
+}
+
+}  // namespace
+
+extern "C" int dn_bai_create(int device, int32_t n_ref, int64_t segment_bytes, dn_bai *out)
+{
+    dn::clear_error();
+    if (!out || n_ref < 0 || (segment_bytes != 0 && segment_bytes < dn::kFrameSegmentMin))
+        return dn::fail(DN_E_INVALID, "dn_bai_create: bad argument (segment_bytes is 0 or at least 64)");
+    dn_bai h = new dn_bai_s();
+    h->device = device < 0 ? -1 : device;
+    h->n_ref = n_ref;
+    h->segment = segment_bytes;
+    const int rc = [&]() -> int {
+        if (device < 0) return DN_OK;
+        DN_TRY(hipSetDevice(device));
+        DN_TRY(h->st.create(hipStreamCreate));
+        DN_TRY(dn::alloc_padded(h->state, 2));
+        DN_TRY(dn::alloc_padded(h->totals, 1));
+        DN_TRY(dn::alloc_padded(h->err, 1));
+        DN_TRY(hipMemsetAsync(h->state, 0, 2 * sizeof(Carry), h->st));
+        DN_TRY(h->ev0.create(hipEventCreate)); DN_TRY(h->ev1.create(hipEventCreate));
+        DN_TRY(h->ev2.create(hipEventCreate)); DN_TRY(h->ev3.create(hipEventCreate));
+        DN_TRY(hipStreamSynchronize(h->st));
+        return DN_OK;
+    }();
+    if (rc != DN_OK) { delete h; return rc; }
+    *out = h;
+    return DN_OK;
+}
+
+extern "C" void dn_bai_destroy(dn_bai h)
+{
+    if (!h) return;
+    if (h->device >= 0) {
+        (void) hipSetDevice(h->device);
+        if (h->st) (void) hipStreamSynchronize(h->st);
+    }
+    delete h;
+}
+
+extern "C" int dn_bai_window(dn_bai h, const uint8_t *comp, int64_t n_comp, int64_t n_blocks, const int64_t *pay_off, const int32_t *pay_len,
+                             const int32_t *isize, const int64_t *coffset, int32_t head_skip, int32_t *status, int64_t *n_rec,
+                             double *inflate_ms, double *frame_ms, double *index_ms)
+{
+    dn::clear_error();
+    int rc = check_handle(h, "dn_bai_window", true);
+    if (rc != DN_OK) return rc;
+    if (n_comp < 0 || (n_comp > 0 && !comp) || n_blocks < 0 || n_blocks > INT32_MAX ||
+        (n_blocks > 0 && (!pay_off || !pay_len || !isize || !coffset || !status)) || head_skip < 0 || !n_rec)
+        return dn::fail(DN_E_INVALID, "dn_bai_window: bad argument");
+    std::vector<Piece> pc;
+    std::vector<dn::InflateBlock> blk;
+    std::vector<Head> heads;
+    std::vector<Claim> cl;
+    Totals tot{0, 0, 0};
+    unsigned long long h_err = ~0ull;
+    int64_t h_off = 0, total = 0;
+    uint8_t h_rec[12] = {0};
+    dn::FrameResult R;
+    rc = window_pieces(h, "dn_bai_window", n_blocks, isize, coffset, head_skip, pc, &blk, pay_off, pay_len, n_comp, total);
+    if (rc != DN_OK) return rc;
+    hipStream_t st = h->st;
+    DN_TRY(hipSetDevice(h->device));
+    *n_rec = 0;
+    if (inflate_ms) *inflate_ms = 0.0;
+    if (frame_ms) *frame_ms = 0.0;
+    if (index_ms) *index_ms = 0.0;
+    return dn::synced(st, [&]() -> int {
+        DN_TRY(h->win.reserve(total, 0, st));
+        const int64_t comp_cap = dn::inflate_comp_cap(n_comp);
+        DN_TRY(h->comp.reserve(comp_cap, 0, st));
+        DN_TRY(h->blk.reserve(n_blocks, 0, st)); DN_TRY(h->blk_status.reserve(n_blocks, 0, st));
+        // the record cut by the end of the window before goes first: it waited in h->carry while h->win was reused
+        if (h->n_carry > 0) DN_TRY(hipMemcpyAsync(h->win, h->carry, (size_t) h->n_carry, hipMemcpyDeviceToDevice, st));
+        if (n_comp > 0) DN_TRY(hipMemcpyAsync(h->comp, comp, (size_t) n_comp, hipMemcpyHostToDevice, st));
+        if (n_blocks > 0) DN_TRY(hipMemcpyAsync(h->blk, blk.data(), sizeof(dn::InflateBlock) * (size_t) n_blocks, hipMemcpyHostToDevice, st));
+        DN_TRY(hipEventRecord(h->ev0, st));
+        DN_TRY(dn::inflate_launch(st, h->comp, comp_cap, h->blk, n_blocks, h->win, h->blk_status));
+        DN_TRY(hipEventRecord(h->ev1, st));
+        if (n_blocks > 0) DN_TRY(hipMemcpyAsync(status, h->blk_status, sizeof(int32_t) * (size_t) n_blocks, hipMemcpyDeviceToHost, st));
+        DN_TRY(hipStreamSynchronize(st));
+        if (inflate_ms) {
+            float ms = 0.f;
+            DN_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+            *inflate_ms = ms;
+        }
+        for (int64_t b = 0; b < n_blocks; b++)
+            if (status[b] != 0) { h->failed = true; return DN_OK; }      // a block that failed left its bytes unspecified: the caller reports it
+        const int frc = dn::frame_window(st, h->frame, h->win, total, -1, nullptr, h->segment, -1, h->rec_off, R);
+        h->n_fixups += R.n_fixups;
+        if (frame_ms) *frame_ms = R.device_ms;
+        if (frc != DN_OK) { h->failed = true; return frc; }
+        if (R.n_rec > 0) {
+            const int irc = index_window(h, total, R.n_rec, pc, heads, cl, tot, h_err, h_off, h_rec);
+            if (irc != DN_OK) { h->failed = true; return irc; }
+            if (index_ms) {
+                float ms = 0.f;
+                DN_TRY(hipEventElapsedTime(&ms, h->ev2, h->ev3));
+                *index_ms = ms;
+            }
+        }
+        const int64_t left = total - R.consumed;
+        DN_TRY(h->carry.reserve(left, 0, st));
+        if (left > 0) DN_TRY(hipMemcpyAsync(h->carry, h->win + R.consumed, (size_t) left, hipMemcpyDeviceToDevice, st));
+        carry_pieces(h, pc, R.consumed, total);
+        absorb(h, R.n_rec, tot, heads.data(), cl.data());
+        h->n_windows++;
+        *n_rec = R.n_rec;
+        return DN_OK;
+    });
+}
+
+extern "C" int dn_bai_window_host(dn_bai h, const uint8_t *data, int64_t n_data, int64_t n_blocks, const int32_t *isize, const int64_t *coffset,
+                                  int32_t head_skip, int64_t *n_rec)
+{
+    dn::clear_error();
+    int rc = check_handle(h, "dn_bai_window_host", false);
+    if (rc != DN_OK) return rc;
+    if (n_data < 0 || (n_data > 0 && !data) || n_blocks < 0 || (n_blocks > 0 && (!isize || !coffset)) || head_skip < 0 || !n_rec)
+        return dn::fail(DN_E_INVALID, "dn_bai_window_host: bad argument");
+    std::vector<Piece> pc;
+    int64_t total = 0, sum = 0;
+    rc = window_pieces(h, "dn_bai_window_host", n_blocks, isize, coffset, head_skip, pc, nullptr, nullptr, nullptr, 0, total);
+    if (rc != DN_OK) return rc;
+    for (int64_t b = 0; b < n_blocks; b++) sum += isize[b];
+    if (sum != n_data) return dn::fail(DN_E_INVALID, "dn_bai_window_host: the blocks' sizes do not add up to n_data");
+    const int64_t skip = n_blocks > 0 ? (head_skip < isize[0] ? head_skip : isize[0]) : 0;
+    std::vector<uint8_t> win(h->h_carry);
+    win.insert(win.end(), data + skip, data + n_data);
+    win.resize(win.size() + 16);                                       // as the device buffers: slack behind the window
+    std::vector<int64_t> off((size_t) (total / 36 + 2));
+    int64_t nr = 0, consumed = 0, fix = 0;
+    rc = dn_bam_frame_segments_host(win.data(), total, -1, nullptr, h->segment, off.data(), (int64_t) off.size(), &nr, &consumed, &fix);
+    h->n_fixups += fix;
+    if (rc != DN_OK) { h->failed = true; return rc; }
+    std::vector<Head> heads;
+    std::vector<Claim> cl;
+    Totals tot{0, 0, 0};
+    if (nr > 0) {
+        const size_t n = (size_t) nr;
+        std::vector<uint64_t> key(n), vbeg(n), emax_in(n), emax(n), hs(n), hs_sum(n);
+        std::vector<uint32_t> rwin(n);
+        std::vector<uint8_t> fl(n);
+        std::vector<int32_t> cf(n), cf_sum(n);
+        const Recs R{key.data(), vbeg.data(), emax_in.data(), emax.data(), rwin.data(), fl.data(), hs.data(), hs_sum.data(), cf.data(), cf_sum.data()};
+        for (int64_t i = 0; i < nr; i++) {
+            const int e = bai_record(win.data(), total, off.data(), i, pc.data(), (int32_t) pc.size(), h->n_ref, h->h_state, R);
+            if (e != kBaiOk) {
+                const int64_t o = off[(size_t) i];
+                const bool in = o >= 0 && o + 12 <= total;
+                return record_error(h, e, i, in ? (int32_t) b_u32(win.data() + o + 4) : -1, in ? (int32_t) b_u32(win.data() + o + 8) : -1);
+            }
+        }
+        for (size_t i = 0; i < n; i++) emax[i] = i > 0 && emax[i - 1] > emax_in[i] ? emax[i - 1] : emax_in[i];
+        for (int64_t i = 0; i < nr; i++) bai_flag_pass(R, i, h->h_state);
+        uint64_t s = 0;
+        int32_t c = 0;
+        for (size_t i = 0; i < n; i++) { hs_sum[i] = s; s += hs[i]; cf_sum[i] = c; c += cf[i]; }
+        heads.resize((size_t) (uint32_t) s);
+        cl.resize((size_t) c);
+        Carry next = h->h_state;
+        for (int64_t i = 0; i < nr; i++) bai_scatter_pass(win.data(), off.data(), R, i, nr, h->h_state, heads.data(), cl.data(), &tot, &next);
+        h->h_state = next;
+    }
+    h->h_carry.assign(win.begin() + consumed, win.begin() + total);
+    carry_pieces(h, pc, consumed, total);
+    absorb(h, nr, tot, heads.data(), cl.data());
+    h->n_windows++;
+    *n_rec = nr;
+    return DN_OK;
+}
+
+extern "C" int dn_bai_finish(dn_bai h, int64_t end_voffset, int64_t *sizes)
+{
+    dn::clear_error();
+    if (!h || !sizes || end_voffset < 0) return dn::fail(DN_E_INVALID, "dn_bai_finish: bad argument");
+    if (h->failed || h->finished) return dn::fail(DN_E_STATE, "dn_bai_finish: the index is finished or has failed");
+    if (h->n_carry > 0) {
+        h->failed = true;
+        return dn::fail(DN_E_INVALID, "record " + std::to_string(h->n_records) + " is cut by the end of the file (" + std::to_string(h->n_carry) +
+                                      " bytes of it are there)");
+    }
+    const size_t n_ref = (size_t) h->n_ref;
+    if (!h->runs.empty()) h->runs.back().vend = (uint64_t) end_voffset;
+    h->ref_n_bin.assign(n_ref, 0);
+    h->ref_n_intv.assign(n_ref, 0);
+    h->ref_pseudo.assign(4 * n_ref, 0);
+    std::vector<uint8_t> seen(n_ref, 0);
+    std::vector<size_t> order;
+    for (size_t k = 0; k < h->runs.size(); k++) {
+        const Run &r = h->runs[k];
+        const uint32_t ref = (uint32_t) (r.key >> 32);
+        if (ref == kUnplaced) { h->n_no_coor += r.n; continue; }
+        uint64_t *p = &h->ref_pseudo[4 * (size_t) ref];
+        if (!seen[ref]) { seen[ref] = 1; p[0] = r.vbeg; }
+        p[1] = r.vend;
+        p[2] += (uint64_t) (r.n - r.n_unmapped);
+        p[3] += (uint64_t) r.n_unmapped;
+        order.push_back(k);
+    }
+    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return h->runs[a].key < h->runs[b].key; });
+    // chunks of a bin in file order; one that begins in the block the one before it ends in is joined to it
+    uint64_t cur = ~(uint64_t) 0;
+    for (size_t k : order) {
+        const Run &r = h->runs[k];
+        if (r.key != cur) {
+            cur = r.key;
+            h->bin_id.push_back((int32_t) (uint32_t) r.key);
+            h->bin_n_chunk.push_back(0);
+            h->ref_n_bin[(size_t) (r.key >> 32)]++;
+        } else if (h->chunks.back() >> 16 >= r.vbeg >> 16) {
+            h->chunks.back() = r.vend;
+            continue;
+        }
+        h->chunks.push_back(r.vbeg);
+        h->chunks.push_back(r.vend);
+        h->bin_n_chunk.back()++;
+    }
+    // the linear index: claims are in file order, so per reference ascending and disjoint; a window nobody claimed takes
+    // the value of the next one that was
+    std::vector<int64_t> ioff_at(n_ref + 1, 0);
+    for (const Claim &c : h->claims) {
+        const int32_t hi = (int32_t) (c.lohi & 0xffff) + 1;
+        if (hi > h->ref_n_intv[(size_t) c.ref]) h->ref_n_intv[(size_t) c.ref] = hi;
+    }
+    for (size_t r = 0; r < n_ref; r++) ioff_at[r + 1] = ioff_at[r] + h->ref_n_intv[r];
+    h->ioffset.assign((size_t) ioff_at[n_ref], ~(uint64_t) 0);
+    for (const Claim &c : h->claims)
+        for (uint32_t wdw = c.lohi >> 16; wdw <= (c.lohi & 0xffff); wdw++) h->ioffset[(size_t) (ioff_at[(size_t) c.ref] + wdw)] = c.vbeg;
+    for (size_t r = 0; r < n_ref; r++)
+        for (int64_t wdw = ioff_at[r + 1] - 2; wdw >= ioff_at[r]; wdw--)
+            if (h->ioffset[(size_t) wdw] == ~(uint64_t) 0) h->ioffset[(size_t) wdw] = h->ioffset[(size_t) wdw + 1];
+    h->finished = true;
+    sizes[0] = (int64_t) h->bin_id.size();
+    sizes[1] = (int64_t) h->chunks.size() / 2;
+    sizes[2] = (int64_t) h->ioffset.size();
+    sizes[3] = h->n_records;
+    sizes[4] = h->n_no_coor;
+    sizes[5] = h->n_windows;
+    sizes[6] = h->n_fixups;
+    return DN_OK;
+}
+
+extern "C" int dn_bai_fetch(dn_bai h, int32_t *ref_n_bin, int32_t *ref_n_intv, uint64_t *ref_pseudo, int32_t *bin_id, int32_t *bin_n_chunk,
+                            uint64_t *chunks, uint64_t *ioffset)
+{
+    dn::clear_error();
+    if (!h || !ref_n_bin || !ref_n_intv || !ref_pseudo || !bin_id || !bin_n_chunk || !chunks || !ioffset)
+        return dn::fail(DN_E_INVALID, "dn_bai_fetch: bad argument");
+    if (!h->finished) return dn::fail(DN_E_STATE, "dn_bai_fetch: dn_bai_finish first");
+    std::copy(h->ref_n_bin.begin(), h->ref_n_bin.end(), ref_n_bin);
+    std::copy(h->ref_n_intv.begin(), h->ref_n_intv.end(), ref_n_intv);
+    std::copy(h->ref_pseudo.begin(), h->ref_pseudo.end(), ref_pseudo);
+    std::copy(h->bin_id.begin(), h->bin_id.end(), bin_id);
+    std::copy(h->bin_n_chunk.begin(), h->bin_n_chunk.end(), bin_n_chunk);
+    std::copy(h->chunks.begin(), h->chunks.end(), chunks);
+    std::copy(h->ioffset.begin(), h->ioffset.end(), ioffset);
+    return DN_OK;
+}

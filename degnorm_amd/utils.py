@@ -194,3 +194,18 @@ def chunk_bounds(length, n):
         return [0]
     size = int(np.ceil(length / n))
     return list(range(0, length, size)) + [length]
+
+
+def bai_from_bam_file(bam_file):
+    if not bam_file.endswith('.bam'):
+        raise ValueError('{0} must have a .bam extension.'.format(bam_file))
+    return bam_file[:-3] + 'bai'
+
+
+def create_index_file(bam_file, **kw):
+    """
+    Create the .bai index of a .bam file next to it, X.bam -> X.bai (the reference's utils.create_index_file, which shells
+    out to samtools; here degnorm_amd.bam.create_index builds it, on the GPU with device=k).  Returns the .bai path.
+    """
+    from .bam import create_index
+    return create_index(bam_file, bai_from_bam_file(bam_file), **kw)

@@ -384,6 +384,48 @@ int  dn_bam_rows_inflate_framed(dn_bam_rows h, const uint8_t *comp, int64_t n_co
 int  dn_bam_rows_frame_segment(dn_bam_rows h, int64_t segment_bytes);
 int  dn_bam_rows_frame_info(dn_bam_rows h, int64_t *n_segments, int64_t *n_fixups, double *device_ms, double *decode_ms);
 
+/* .bai index of a BAM file (csrc/dn_bai.hip; degnorm_amd.bam.build_index) -------------------------------------------------
+ * One pass over every record of a coordinate-sorted file, window by window, all references: per record [beg, end) on its
+ * reference (end - beg from the CIGAR ops M D N = X; 1 when flag & 4, without CIGAR or when that sum is 0; beg below 0
+ * becomes 0 and end below 1 becomes 1 on a reference), bin = reg2bin(beg, end) of the SAM specification 5.3, and the
+ * virtual offset of its first byte.  The index holds, per reference with records, its bins in ascending order -- per bin
+ * the chunks of its maximal runs of consecutive records in file order, two joined when the later begins in the BGZF block
+ * the earlier ends in, nothing else merged and no bin folded into its parent --, the pseudo-bin's four values and the
+ * linear index (per 16 kb window the smallest offset of a record that overlaps it, mapped or not; an empty window takes
+ * the next one's value).  A CIGAR kept in the CG tag (more than 65 535 ops) is read as stored in the record.
+ *   dn_bai_create         a builder for a file of n_ref references on `device`, or (device < 0) the host build, which
+ *                         touches no device.  segment_bytes: of the framing (0: the default).
+ *   dn_bai_window         device builder: the next window.  comp holds n_blocks whole BGZF blocks, described as for
+ *                         dn_bam_rows_inflate_framed, coffset[b] the file offset of block b; head_skip bytes of the first
+ *                         block are left out (the first window starts where the BAM header ends).  The blocks are inflated
+ *                         behind the record the window before cut, which waited on the device; the window is framed and
+ *                         indexed where it lies, and only the tables of run heads and linear-index claims come back.  When
+ *                         a block failed (status[b] != 0) the call returns DN_OK and the builder is spent.  *n_rec: the
+ *                         records of this window; inflate_ms / frame_ms / index_ms (nullable): by HIP events.
+ *   dn_bai_window_host    host builder: the same on the n_data inflated bytes of the n_blocks blocks.
+ *   dn_bai_finish         no more windows; end_voffset is the virtual offset of the end of the stream (the block behind the
+ *                         last one that holds a byte, offset 0).  sizes[0 .. 6] = bins (without pseudo-bins), chunks,
+ *                         linear-index entries, records, records with refID < 0, windows, framing fix-ups.
+ *   dn_bai_fetch          ref_n_bin[n_ref] (without the pseudo-bin), ref_n_intv[n_ref], ref_pseudo[4 n_ref] (offset of the
+ *                         first record, end of the last, mapped, unmapped), then per bin in (reference, bin) order bin_id
+ *                         and bin_n_chunk, the chunks as (begin, end) pairs, and the linear indexes one after the other.
+ * DN_E_INVALID with a text naming the record's ordinal in the file: refID not below n_ref, refID decreasing (a negative
+ * one counts as behind every reference), pos decreasing within a reference, beg or end above 2^29, a record whose name
+ * and CIGAR do not fit in it, a record that starts beyond byte 65535 of its block (no virtual offset can name it), a record
+ * cut by the end of the file, and the errors of the framing.  Host and device builders
+ * give the same texts.  After an error a builder only accepts dn_bai_destroy.  Errors: dn_last_error(). */
+typedef struct dn_bai_s *dn_bai;
+int  dn_bai_create(int device, int32_t n_ref, int64_t segment_bytes, dn_bai *out);
+void dn_bai_destroy(dn_bai h);
+int  dn_bai_window(dn_bai h, const uint8_t *comp, int64_t n_comp, int64_t n_blocks, const int64_t *pay_off, const int32_t *pay_len,
+                   const int32_t *isize, const int64_t *coffset, int32_t head_skip, int32_t *status, int64_t *n_rec,
+                   double *inflate_ms, double *frame_ms, double *index_ms);
+int  dn_bai_window_host(dn_bai h, const uint8_t *data, int64_t n_data, int64_t n_blocks, const int32_t *isize, const int64_t *coffset,
+                        int32_t head_skip, int64_t *n_rec);
+int  dn_bai_finish(dn_bai h, int64_t end_voffset, int64_t *sizes);
+int  dn_bai_fetch(dn_bai h, int32_t *ref_n_bin, int32_t *ref_n_intv, uint64_t *ref_pseudo, int32_t *bin_id, int32_t *bin_n_chunk,
+                  uint64_t *chunks, uint64_t *ioffset);
+
 /* GTF annotation scan (GeneAnnotationLoader, degnorm_amd/loaders.py) --------------------------------------------------
  * Replaces the reference's read_csv of the nine columns, its lower-case `apply` on the feature column and its regex
  * `apply` per exon row (loaders.py:128-152, _attribute_to_gene :102-112).  buf holds the n_bytes raw bytes of a GTF file,
