@@ -59,6 +59,9 @@ def argparser():
                     help='inflate the BGZF blocks of the .bam files on the GPU instead of with zlib on the host')
     ap.add_argument('--device-frame', action='store_true',
                     help='find the record starts of the inflated .bam bytes on the GPU instead of with a serial walk on the host')
+    ap.add_argument('--verify-crc', action='store_true',
+                    help='check every BGZF block read from the .bam files against the CRC32 of its trailer (also while '
+                         '--create-bai indexes them) and stop at the first that differs')
     return ap
 
 
@@ -185,12 +188,12 @@ def main(argv=None):
             from .utils import create_index_file
             for k, bam_file in enumerate(args.create_bai_files):
                 logging.info('creating index file for {0} -- {1} / {2}'.format(bam_file, k + 1, len(args.create_bai_files)))
-                create_index_file(bam_file, device=int(os.environ.get('LOCAL_RANK', 0)))
+                create_index_file(bam_file, device=int(os.environ.get('LOCAL_RANK', 0)), verify=getattr(args, 'verify_crc', False))
         run_pipeline(args.bam_files, args.bai_files, args.genome_annotation, output_dir, degnorm_iter=args.iter,
                      nmf_iter=args.nmf_iter, downsample_rate=args.downsample_rate, minimax_coverage=args.minimax_coverage,
                      skip_baseline_selection=args.skip_baseline_selection, unique_alignment=not args.non_unique_alignments,
                      n_jobs=args.proc_per_node, inflate='device' if args.device_inflate else 'host',
-                     frame='device' if args.device_frame else 'host')
+                     frame='device' if args.device_frame else 'host', verify=getattr(args, 'verify_crc', False))
     logging.info('DegNorm pipeline complete! Exiting...')
     return 0
 

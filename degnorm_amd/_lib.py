@@ -129,6 +129,10 @@ def load(build_if_missing=False):
                                         P(i32), P(dbl)]
     lib.dn_bgzf_inflate_host.argtypes = [P(u8), i64, i64, P(i64), P(i32), P(i64), P(u8), P(i32)]
     lib.dn_bgzf_inflate.argtypes = [c.c_int, P(u8), i64, i64, P(i64), P(i32), P(i64), P(u8), P(i32), P(dbl), P(dbl)]
+    lib.dn_bgzf_inflate_check_host.argtypes = lib.dn_bgzf_inflate_host.argtypes + [P(u32)]
+    lib.dn_bgzf_inflate_check.argtypes = lib.dn_bgzf_inflate.argtypes + [P(u32)]
+    lib.dn_bgzf_crc32_host.argtypes = [P(u8), i64, i32, i32, P(u32)]
+    lib.dn_bam_rows_expect_crc.argtypes = [vp, P(u32), i64]
     lib.dn_bam_rows_info.argtypes = [vp, P(i64), P(i64), P(i64), P(i32)]
     lib.dn_bam_rows_keys.argtypes = [vp, i32, P(u8)]
     lib.dn_bam_rows_fetch.argtypes = [vp, P(i64), P(i64), P(i32), P(u32), P(i64), P(i32), P(u8)]
@@ -140,6 +144,7 @@ def load(build_if_missing=False):
     lib.dn_bai_destroy.restype = None
     lib.dn_bai_window.argtypes = [vp, P(u8), i64, i64, P(i64), P(i32), P(i32), P(i64), i32, P(i32), P(i64), P(dbl), P(dbl), P(dbl)]
     lib.dn_bai_window_host.argtypes = [vp, P(u8), i64, i64, P(i32), P(i64), i32, P(i64)]
+    lib.dn_bai_expect_crc.argtypes = [vp, P(u32), i64]
     lib.dn_bai_finish.argtypes = [vp, i64, P(i64)]
     lib.dn_bai_fetch.argtypes = [vp, P(i32), P(i32), P(u64), P(i32), P(i32), P(u64), P(u64)]
     lib.dn_gtf_scan.argtypes = [c.c_int, P(c.c_uint8), i64, i64, P(i64), P(i64), P(i64), P(i64), P(i32), P(u64), P(i64), P(i64),

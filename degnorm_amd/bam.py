@@ -23,6 +23,10 @@ as pandas' sort_values does (numpy's quicksort on fixed-width bytes) and hands t
 A file without an index gets one from build_index / create_index (csrc/dn_bai.hip): one pass over every record of the file,
 inflated, framed and indexed on the device window by window (or, device=None, with zlib and the host build of the same
 source); parse_bai / BamIndex.tobytes / write_bai read and write whole .bai files, index_chunks is the region query.
+
+Every path that inflates takes verify=True: the inflated bytes of each BGZF block are then compared with the CRC32 of its
+trailer -- zlib.crc32 where zlib inflates, the wavefront that inflates the block where the device does -- and a block that
+differs is a ValueError naming the file and the block's offset.  verify_bgzf checks a whole file that way (bgzip -t).
 """
 import ctypes
 import os
@@ -102,18 +106,47 @@ def has_eof_block(path):
         return f.read() == BGZF_EOF
 
 
-def inflate_block(blk):
-    """The data of one BGZF block (raw deflate between the header and the CRC32 / ISIZE trailer)."""
+INFLATE_E_CRC = 8
+INFLATE_ERRORS = {1: 'bad block type or header', 2: 'bad code lengths', 3: 'invalid code', 4: 'distance too far back',
+                  5: 'input ended early', 6: 'inflated size differs from ISIZE', 7: 'bytes after the final deflate block',
+                  8: 'CRC32 differs from the block trailer'}
+
+
+class BgzfCrcError(ValueError):
+    """A BGZF block that inflates to ISIZE bytes whose CRC32 is not the one in its trailer."""
+
+
+def inflate_block(blk, verify=False):
+    """
+    The data of one BGZF block (raw deflate between the header and the CRC32 / ISIZE trailer).  verify: the data must have
+    the trailer's CRC32 (BgzfCrcError, a ValueError).
+    """
     xlen = struct.unpack_from('<H', blk, 10)[0]
-    isize = struct.unpack_from('<I', blk, len(blk) - 4)[0]
+    crc, isize = struct.unpack_from('<II', blk, len(blk) - 8)
     data = zlib.decompress(blk[12 + xlen:len(blk) - 8], -15)
     if len(data) != isize:
         raise ValueError('BGZF block inflates to {0} bytes, ISIZE says {1}'.format(len(data), isize))
+    if verify and zlib.crc32(data) & 0xffffffff != crc:
+        raise BgzfCrcError('BGZF block does not inflate: ' + INFLATE_ERRORS[INFLATE_E_CRC])
     return data
 
 
-INFLATE_ERRORS = {1: 'bad block type or header', 2: 'bad code lengths', 3: 'invalid code', 4: 'distance too far back',
-                  5: 'input ended early', 6: 'inflated size differs from ISIZE', 7: 'bytes after the final deflate block'}
+def _inflate_verified(blk):
+    return inflate_block(blk, True)
+
+
+def _block_error(path, offset, status):
+    return '{0}: the BGZF block at byte {1} does not inflate: {2}'.format(path, offset, INFLATE_ERRORS.get(int(status), 'error {0}'.format(int(status))))
+
+
+def block_crcs(blocks):
+    """The CRC32 of the trailer of every block of a list of whole BGZF blocks (uint32; one entry for an empty list)."""
+    crc = np.zeros(max(len(blocks), 1), np.uint32)
+    for k, blk in enumerate(blocks):
+        if len(blk) < 20:
+            raise ValueError('BGZF block {0} is cut short ({1} bytes)'.format(k, len(blk)))
+        crc[k] = struct.unpack_from('<I', blk, len(blk) - 8)[0]
+    return crc
 
 
 def _block_layout(blocks):
@@ -133,11 +166,11 @@ def _block_layout(blocks):
     return comp, p, pay_off, pay_len, isize
 
 
-def inflate_blocks(blocks, device=None):
+def inflate_blocks(blocks, device=None, verify=False):
     """
     The data of whole BGZF blocks (as iter_blocks yields them), inflated by the library's own DEFLATE decoder: on the host
     (device=None; no GPU needed) or on GPU `device`, one block per wavefront.  ValueError names the first block that does
-    not decode.
+    not decode or (verify) whose bytes do not have the CRC32 of its trailer.
     """
     blocks = list(blocks)
     n = len(blocks)
@@ -150,10 +183,15 @@ def inflate_blocks(blocks, device=None):
     status = np.zeros(max(n, 1), np.int32)
     i64, i32, u8 = ctypes.c_int64, ctypes.c_int32, ctypes.c_uint8
     args = (_ptr(comp, u8), n_comp, n, _ptr(pay_off, i64), _ptr(pay_len, i32), _ptr(out_off, i64), _ptr(out, u8), _ptr(status, i32))
-    if device is None:
+    crc = _ptr(block_crcs(blocks), ctypes.c_uint32) if verify else None
+    if device is None and not verify:
         _check(_lib.load().dn_bgzf_inflate_host(*args), 'dn_bgzf_inflate_host')
-    else:
+    elif device is None:
+        _check(_lib.load().dn_bgzf_inflate_check_host(*(args + (crc,))), 'dn_bgzf_inflate_check_host')
+    elif not verify:
         _check(_lib.load().dn_bgzf_inflate(int(device), *(args + (None, None))), 'dn_bgzf_inflate')
+    else:
+        _check(_lib.load().dn_bgzf_inflate_check(int(device), *(args + (None, None, crc))), 'dn_bgzf_inflate_check')
     _raise_status(status[:n], lambda k: 'BGZF block {0}'.format(k))
     data = out.tobytes()
     return [data[out_off[k]:out_off[k + 1]] for k in range(n)]
@@ -193,11 +231,14 @@ def parse_header(data):
     return p, refs
 
 
-def read_header(path):
-    """[(SQ name, length)] of a BAM file, in refID order."""
+def read_header(path, verify=False):
+    """[(SQ name, length)] of a BAM file, in refID order.  verify: its blocks must have the CRC32s of their trailers."""
     data = bytearray()
-    for _, blk in iter_blocks(path):
-        data += inflate_block(blk)
+    for off, blk in iter_blocks(path):
+        try:
+            data += inflate_block(blk, verify)
+        except BgzfCrcError:
+            raise ValueError(_block_error(path, off, INFLATE_E_CRC))
         got = parse_header(data)
         if got is not None:
             return got[1]
@@ -316,12 +357,20 @@ class DeviceRows(object):
         _check(self.lib.dn_bam_rows_append(self.h, _ptr(a, ctypes.c_uint8), len(buf), _ptr(rec_off, ctypes.c_int64),
                                            len(rec_off)), 'dn_bam_rows_append')
 
-    def inflate(self, carry, blocks, head_skip, tail_keep):
+    def expect_crc(self, crc):
+        """dn_bam_rows_expect_crc: the next inflate / inflate_framed checks its blocks against these CRC32s (one per block)."""
+        crc = np.ascontiguousarray(crc, dtype=np.uint32)
+        _check(self.lib.dn_bam_rows_expect_crc(self.h, _ptr(crc, ctypes.c_uint32) if len(crc) else None, len(crc)), 'dn_bam_rows_expect_crc')
+
+    def inflate(self, carry, blocks, head_skip, tail_keep, verify=False):
         """
         dn_bam_rows_inflate: the next window (carry + the inflated blocks, trimmed) built on the device.  Returns a view of
         the library's host copy of it (valid until the next call), the status of every block and the kernel's ms.
+        verify: every block, all of it, must have the CRC32 of its trailer (status 8 otherwise).
         """
         comp, n_comp, pay_off, pay_len, isize = _block_layout(blocks)
+        if verify:
+            self.expect_crc(block_crcs(blocks)[:len(blocks)])
         isize32 = np.where(isize > 2 ** 31 - 1, -1, isize).astype(np.int32)      # the library refuses a negative size
         status = np.zeros(max(len(blocks), 1), np.int32)
         c = np.frombuffer(carry, dtype=np.uint8) if len(carry) else np.zeros(1, np.uint8)
@@ -345,12 +394,15 @@ class DeviceRows(object):
         _check(self.lib.dn_bam_rows_append_framed(self.h, _ptr(a, ctypes.c_uint8), len(buf), ctypes.byref(used)), 'dn_bam_rows_append_framed')
         return int(used.value)
 
-    def inflate_framed(self, blocks, head_skip, tail_keep):
+    def inflate_framed(self, blocks, head_skip, tail_keep, verify=False):
         """
         dn_bam_rows_inflate_framed: the next window inflated, framed, decoded and appended on the device; the record its end
         cuts stays there.  Returns the status of every block, the bytes carried over, and the ms of inflate and framing.
+        verify: as for inflate.
         """
         comp, n_comp, pay_off, pay_len, isize = _block_layout(blocks)
+        if verify:
+            self.expect_crc(block_crcs(blocks)[:len(blocks)])
         isize32 = np.where(isize > 2 ** 31 - 1, -1, isize).astype(np.int32)      # the library refuses a negative size
         status = np.zeros(max(len(blocks), 1), np.int32)
         n_bytes, n_carry, ms, fms = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_double(0.0), ctypes.c_double(0.0)
@@ -452,7 +504,7 @@ def cigar_strings(op_beg, n_op, ops):
 class NativeBamReadsProcessor(BamReadsProcessor):
 
     def __init__(self, bam_file, index_file, chroms=None, n_jobs=1, output_dir=None, unique_alignment=True, verbose=True,
-                 window_bytes=256 << 20, inflate='host', frame='host', frame_segment_bytes=None):
+                 window_bytes=256 << 20, inflate='host', frame='host', frame_segment_bytes=None, verify=False):
         """
         BamReadsProcessor on the library's own BAM reader: no pysam.  n_jobs sizes the thread pool that inflates BGZF
         blocks; window_bytes bounds the inflated bytes held (on the host and on the device) besides the chromosome's rows.
@@ -461,6 +513,8 @@ class NativeBamReadsProcessor(BamReadsProcessor):
         frame='host' finds the record starts of a window with the library's serial host walk; frame='device' finds them on
         the GPU (with either inflate; the strand check stays on the host walk), in segments of frame_segment_bytes (None:
         the library's default).  timing then has frame_device_ms and frame_fixups instead of frame_s.
+        verify=True compares every block that is inflated -- by either side, and also for the header and the strand check
+        -- with the CRC32 of its trailer; a block that differs is a ValueError naming the file and the block's offset.
         """
         if inflate not in ('host', 'device'):
             raise ValueError("inflate must be 'host' or 'device', not {0!r}".format(inflate))
@@ -469,6 +523,7 @@ class NativeBamReadsProcessor(BamReadsProcessor):
         self.inflate = inflate
         self.frame = frame
         self.frame_segment_bytes = frame_segment_bytes
+        self.verify = bool(verify)
         self.window_bytes = max(int(window_bytes), 1)
         self.timing = {}
         super(NativeBamReadsProcessor, self).__init__(bam_file, index_file, chroms=chroms, n_jobs=n_jobs, output_dir=output_dir,
@@ -482,7 +537,7 @@ class NativeBamReadsProcessor(BamReadsProcessor):
         if self._refs is None:
             if not has_eof_block(self.filename):
                 raise ValueError('{0}: no BGZF end-of-file block; the file is truncated'.format(self.filename))
-            self._refs = read_header(self.filename)
+            self._refs = read_header(self.filename, self.verify)
             self._index, _ = read_bai(self.index_filename)
             if len(self._index) != len(self._refs):
                 raise ValueError('{0} indexes {1} references, {2} has {3}'.format(
@@ -530,7 +585,13 @@ class NativeBamReadsProcessor(BamReadsProcessor):
     def _inflate(self, batch, pool, cbeg, ubeg, cend, uend):
         t0 = time.perf_counter()
         blocks = [b for _, b in batch]
-        data = list(pool.map(inflate_block, blocks)) if pool is not None else [inflate_block(b) for b in blocks]
+        one = _inflate_verified if self.verify else inflate_block
+        data = []
+        try:
+            for d in (pool.map(one, blocks) if pool is not None else map(one, blocks)):      # in file order: the first bad block raises
+                data.append(d)
+        except BgzfCrcError:
+            raise ValueError(_block_error(self.filename, batch[len(data)][0], INFLATE_E_CRC))
         for k, (off, _) in enumerate(batch):
             if off == cend:
                 data[k] = data[k][:uend]
@@ -589,7 +650,7 @@ class NativeBamReadsProcessor(BamReadsProcessor):
         for batch, cbeg, ubeg, cend, uend in self._batches(chrom):
             t0 = time.perf_counter()
             data, status, ms = rows.inflate(carry, [b for _, b in batch], ubeg if batch[0][0] == cbeg else 0,
-                                            uend if batch[-1][0] == cend else -1)
+                                            uend if batch[-1][0] == cend else -1, self.verify)
             t1 = time.perf_counter()
             _raise_status(status, lambda k: '{0}: the BGZF block at byte {1}'.format(self.filename, batch[k][0]))
             off, used, last = frame_records(data, self._tid[chrom], last)
@@ -617,7 +678,7 @@ class NativeBamReadsProcessor(BamReadsProcessor):
                 for batch, cbeg, ubeg, cend, uend in self._batches(chrom):
                     t0 = time.perf_counter()
                     status, n_carry, ms, fms = rows.inflate_framed([b for _, b in batch], ubeg if batch[0][0] == cbeg else 0,
-                                                                   uend if batch[-1][0] == cend else -1)
+                                                                   uend if batch[-1][0] == cend else -1, self.verify)
                     t1 = time.perf_counter()
                     _raise_status(status, lambda k: '{0}: the BGZF block at byte {1}'.format(self.filename, batch[k][0]))
                     t['inflate_device_ms'] = t.get('inflate_device_ms', 0.0) + ms
@@ -750,11 +811,20 @@ def write_bai(index, path):
     return path
 
 
-def _host_inflate(bam_file, batch, pool):
-    """The data of the blocks of batch by zlib; a block that fails is named with the text of the library's own decoder."""
+def _host_inflate(bam_file, batch, pool, verify=False):
+    """
+    The data of the blocks of batch by zlib (verify: and their CRC32s by zlib.crc32, in the same pool); a block that fails
+    is named with the text of the library's own decoder.
+    """
     blocks = [b for _, b in batch]
+    one = _inflate_verified if verify else inflate_block
+    data = []
     try:
-        return list(pool.map(inflate_block, blocks)) if pool is not None else [inflate_block(b) for b in blocks]
+        for d in (pool.map(one, blocks) if pool is not None else map(one, blocks)):      # in file order: the first bad block raises
+            data.append(d)
+        return data
+    except BgzfCrcError:                                 # the blocks before it were good: this is the one, whatever its ISIZE
+        raise ValueError(_block_error(bam_file, batch[len(data)][0], INFLATE_E_CRC))
     except (zlib.error, ValueError, struct.error) as e:
         comp, n_comp, pay_off, pay_len, isize = _block_layout(blocks)
         n = len(blocks)
@@ -763,20 +833,22 @@ def _host_inflate(bam_file, batch, pool):
         out, status = np.zeros(int(out_off[-1]) + 1, np.uint8), np.zeros(max(n, 1), np.int32)
         i64, i32, u8 = ctypes.c_int64, ctypes.c_int32, ctypes.c_uint8
         if n and int(isize[:n].max()) <= 65536:
-            _check(_lib.load().dn_bgzf_inflate_host(_ptr(comp, u8), n_comp, n, _ptr(pay_off, i64), _ptr(pay_len, i32), _ptr(out_off, i64),
-                                                    _ptr(out, u8), _ptr(status, i32)), 'dn_bgzf_inflate_host')
+            crc = _ptr(block_crcs(blocks), ctypes.c_uint32) if verify else None
+            _check(_lib.load().dn_bgzf_inflate_check_host(_ptr(comp, u8), n_comp, n, _ptr(pay_off, i64), _ptr(pay_len, i32), _ptr(out_off, i64),
+                                                          _ptr(out, u8), _ptr(status, i32), crc), 'dn_bgzf_inflate_check_host')
             _raise_status(status[:n], lambda k: '{0}: the BGZF block at byte {1}'.format(bam_file, batch[k][0]))
         raise ValueError('{0}: a BGZF block at or after byte {1} does not inflate: {2}'.format(bam_file, batch[0][0], e))
 
 
-def build_index(bam_file, device=None, n_jobs=1, window_bytes=256 << 20, segment_bytes=None, stats=None):
+def build_index(bam_file, device=None, n_jobs=1, window_bytes=256 << 20, segment_bytes=None, stats=None, verify=False):
     """
     The .bai index of a coordinate-sorted BAM file as a BamIndex, from one pass over all its records (csrc/dn_bai.hip; the
     index is defined in include/degnorm_amd.h).  device=k: the blocks of about window_bytes of inflated data go to GPU k as
     they are in the file and are inflated, framed and indexed there; only the tables of run heads and linear-index claims
     come back.  device=None: the blocks are inflated with zlib in n_jobs threads and the library's host build of the same
     source walks them; no GPU is needed.  Both give the same index and the same errors (ValueError naming the file and
-    the record).  segment_bytes: of the framing (None: the library's default).  stats, a dict, receives
+    the record).  verify: every block must have the CRC32 of its trailer, checked where the block is inflated (ValueError
+    naming the file and the block's offset).  segment_bytes: of the framing (None: the library's default).  stats, a dict, receives
     `inflate_device_ms`, `frame_device_ms`, `index_device_ms`, `frame_fixups`, `records`, `chunks` and `windows`.
     """
     if not has_eof_block(bam_file):
@@ -808,7 +880,7 @@ def build_index(bam_file, device=None, n_jobs=1, window_bytes=256 << 20, segment
         n_rec = i64(0)
         coffset = np.array([off for off, _ in batch], dtype=np.int64)
         if device is None:
-            data = _host_inflate(bam_file, batch, pool)
+            data = _host_inflate(bam_file, batch, pool, verify)
             isize = np.array([len(d) for d in data], dtype=np.int64)
             isize32 = np.where(isize > 2 ** 31 - 1, -1, isize).astype(np.int32)
             joined = np.frombuffer(b''.join(data), dtype=np.uint8) if int(isize.sum()) else np.zeros(1, np.uint8)
@@ -819,6 +891,8 @@ def build_index(bam_file, device=None, n_jobs=1, window_bytes=256 << 20, segment
         isize32 = np.where(isize > 2 ** 31 - 1, -1, isize).astype(np.int32)      # the library refuses a negative size
         status = np.zeros(max(len(batch), 1), np.int32)
         t = [ctypes.c_double(0.0) for _ in range(3)]
+        if verify:
+            call(lib.dn_bai_expect_crc(h, _ptr(block_crcs([b for _, b in batch]), ctypes.c_uint32), len(batch)), 'dn_bai_expect_crc')
         call(lib.dn_bai_window(h, _ptr(comp, u8), n_comp, len(batch), _ptr(pay_off, i64), _ptr(pay_len, i32), _ptr(isize32, i32),
                                _ptr(coffset, i64), int(head_skip), _ptr(status, i32), ctypes.byref(n_rec), ctypes.byref(t[0]),
                                ctypes.byref(t[1]), ctypes.byref(t[2])), 'dn_bai_window')
@@ -831,7 +905,7 @@ def build_index(bam_file, device=None, n_jobs=1, window_bytes=256 << 20, segment
         data, got, first = bytearray(), None, None
         for off, blk in it:                          # the header, on zlib whatever the device: it may span several blocks
             start = len(data)
-            data += _host_inflate(bam_file, [(off, blk)], None)[0]
+            data += _host_inflate(bam_file, [(off, blk)], None, verify)[0]
             got = parse_header(data)
             if got is not None:
                 first = (off, blk)
@@ -891,6 +965,60 @@ def create_index(bam_file, bai_file=None, overwrite=False, **kw):
     if os.path.exists(bai_file) and not overwrite:
         raise FileExistsError('{0} exists; pass overwrite=True to replace it'.format(bai_file))
     return write_bai(build_index(bam_file, **kw), bai_file)
+
+
+def verify_bgzf(path, device=None, n_jobs=1, window_bytes=256 << 20):
+    """
+    Check a whole BGZF file as `bgzip -t` does: it ends with the end-of-file block, and every block inflates to its ISIZE
+    bytes, which have the CRC32 of its trailer.  device=k: the blocks of about window_bytes of inflated data go to GPU k as
+    they are in the file, every wavefront inflates and checks one, and only the statuses come back -- no inflated byte is
+    written or copied.  device=None: zlib and zlib.crc32 in n_jobs threads.  ValueError names the file and the first bad
+    block.  Returns {'blocks', 'compressed_bytes', 'inflated_bytes', 'device_ms'}.
+    """
+    if not has_eof_block(path):
+        raise ValueError('{0}: no BGZF end-of-file block; the file is truncated'.format(path))
+    window_bytes = max(int(256 << 20 if window_bytes is None else window_bytes), 1)
+    out = {'blocks': 0, 'compressed_bytes': 0, 'inflated_bytes': 0, 'device_ms': 0.0}
+    pool = ThreadPoolExecutor(max_workers=int(n_jobs)) if device is None and int(n_jobs) > 1 else None
+    i64, i32, u8 = ctypes.c_int64, ctypes.c_int32, ctypes.c_uint8
+
+    def window(batch):
+        blocks = [b for _, b in batch]
+        if device is None:
+            _host_inflate(path, batch, pool, True)
+            return
+        comp, n_comp, pay_off, pay_len, isize = _block_layout(blocks)
+        n = len(blocks)
+        if int(isize[:n].max()) > 65536:
+            k = int(isize[:n].argmax())
+            raise ValueError('{0}: the BGZF block at byte {1} claims an inflated size of {2} bytes'.format(path, batch[k][0], int(isize[k])))
+        out_off = np.zeros(n + 1, np.int64)
+        np.cumsum(isize[:n], out=out_off[1:])
+        status, ms = np.zeros(n, np.int32), ctypes.c_double(0.0)
+        _check(_lib.load().dn_bgzf_inflate_check(int(device), _ptr(comp, u8), n_comp, n, _ptr(pay_off, i64), _ptr(pay_len, i32),
+                                                 _ptr(out_off, i64), None, _ptr(status, i32), None, ctypes.byref(ms),
+                                                 _ptr(block_crcs(blocks), ctypes.c_uint32)), 'dn_bgzf_inflate_check')
+        out['device_ms'] += float(ms.value)
+        _raise_status(status, lambda k: '{0}: the BGZF block at byte {1}'.format(path, batch[k][0]))
+
+    try:
+        batch, size = [], 0
+        for off, blk in iter_blocks(path):
+            isize = struct.unpack_from('<I', blk, len(blk) - 4)[0]
+            batch.append((off, blk))
+            size += isize
+            out['blocks'] += 1
+            out['compressed_bytes'] += len(blk)
+            out['inflated_bytes'] += isize
+            if size >= window_bytes:
+                window(batch)
+                batch, size = [], 0
+        if batch:
+            window(batch)
+    finally:
+        if pool is not None:
+            pool.shutdown()
+    return out
 
 
 def reg2bins(beg, end):

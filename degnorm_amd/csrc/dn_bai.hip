@@ -260,6 +260,8 @@ struct dn_bai_s {
     dn::GrowBuffer<uint8_t> win, comp, carry;
     dn::GrowBuffer<dn::InflateBlock> blk;
     dn::GrowBuffer<int32_t> blk_status;
+    std::vector<uint32_t> expect_crc;  // dn_bai_expect_crc: the CRC32 of every block of the next dn_bai_window
+    bool crc_armed = false;
     dn::GrowBuffer<int64_t> rec_off;
     dn::GrowBuffer<Piece> pieces;
     dn::GrowBuffer<uint64_t> key, vbeg, emax_in, emax, hs, hs_sum;
@@ -462,16 +464,36 @@ extern "C" void dn_bai_destroy(dn_bai h)
     delete h;
 }
 
+extern "C" int dn_bai_expect_crc(dn_bai h, const uint32_t *crc32, int64_t n_blocks)
+{
+    dn::clear_error();
+    if (!h || n_blocks < 0 || n_blocks > INT32_MAX || (n_blocks > 0 && !crc32)) return dn::fail(DN_E_INVALID, "dn_bai_expect_crc: bad argument");
+    if (h->device < 0) return dn::fail(DN_E_STATE, "dn_bai_expect_crc: a host builder is handed inflated bytes; its caller checks them");
+    h->expect_crc.assign(crc32, crc32 + n_blocks);
+    h->crc_armed = true;
+    return DN_OK;
+}
+
 extern "C" int dn_bai_window(dn_bai h, const uint8_t *comp, int64_t n_comp, int64_t n_blocks, const int64_t *pay_off, const int32_t *pay_len,
                              const int32_t *isize, const int64_t *coffset, int32_t head_skip, int32_t *status, int64_t *n_rec,
                              double *inflate_ms, double *frame_ms, double *index_ms)
 {
     dn::clear_error();
+    std::vector<uint32_t> crc;         // the armed CRC32s are this call's, whatever it returns: taken before any check
+    const bool armed = h && h->crc_armed;
+    if (h) {
+        crc.swap(h->expect_crc);
+        h->expect_crc.clear();
+        h->crc_armed = false;
+    }
     int rc = check_handle(h, "dn_bai_window", true);
     if (rc != DN_OK) return rc;
     if (n_comp < 0 || (n_comp > 0 && !comp) || n_blocks < 0 || n_blocks > INT32_MAX ||
         (n_blocks > 0 && (!pay_off || !pay_len || !isize || !coffset || !status)) || head_skip < 0 || !n_rec)
         return dn::fail(DN_E_INVALID, "dn_bai_window: bad argument");
+    if (armed && (int64_t) crc.size() != n_blocks)
+        return dn::fail(DN_E_INVALID, "dn_bai_window: " + std::to_string(crc.size()) + " CRC32s were announced (dn_bai_expect_crc) for " +
+                                      std::to_string(n_blocks) + " blocks");
     std::vector<Piece> pc;
     std::vector<dn::InflateBlock> blk;
     std::vector<Head> heads;
@@ -483,6 +505,8 @@ extern "C" int dn_bai_window(dn_bai h, const uint8_t *comp, int64_t n_comp, int6
     dn::FrameResult R;
     rc = window_pieces(h, "dn_bai_window", n_blocks, isize, coffset, head_skip, pc, &blk, pay_off, pay_len, n_comp, total);
     if (rc != DN_OK) return rc;
+    if (armed)
+        for (size_t b = 0; b < blk.size(); b++) { blk[b].crc = crc[b]; blk[b].check = 1; }
     hipStream_t st = h->st;
     DN_TRY(hipSetDevice(h->device));
     *n_rec = 0;

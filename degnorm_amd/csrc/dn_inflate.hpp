@@ -6,10 +6,13 @@
 namespace dn {
 
 // One BGZF block of a launch.  Its raw-deflate payload is comp[pay_off .. pay_off + pay_len) and must inflate to exactly
-// isize bytes; of those, bytes [skip, skip + keep) are written to out[dst_off ..).
+// isize bytes; of those, bytes [skip, skip + keep) are written to out[dst_off ..).  With check != 0 the CRC32 of all isize
+// bytes must be crc (the block's trailer), else the block's status is DN_INFLATE_E_CRC.
 struct InflateBlock {
     int64_t pay_off, dst_off;
     int32_t pay_len, isize, skip, keep;
+    uint32_t crc;
+    int32_t check;
 };
 
 // bytes a device copy of n_comp compressed bytes must be allocated with (the kernel reads it in whole 16-byte pieces)

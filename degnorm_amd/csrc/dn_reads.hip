@@ -820,6 +820,9 @@ struct dn_bam_rows_s {
     dn::PinnedBuffer<uint8_t> host_win;
     dn::Event ev0, ev1;
     int64_t cap_host = 0, resident = -1;
+    // dn_bam_rows_expect_crc: the CRC32 of every block of the next dn_bam_rows_inflate / dn_bam_rows_inflate_framed
+    std::vector<uint32_t> expect_crc;
+    bool crc_armed = false;
     // device framing (dn_bam_rows_append_framed, dn_bam_rows_inflate_framed): its work buffers, the record cut by the end of
     // the window before (dn_bam_rows_inflate_framed keeps it on the device), the segment size asked for (0: the default), the
     // sums dn_bam_rows_frame_info reports and the pos of the last record framed
@@ -1027,7 +1030,39 @@ int window_blocks(const char *who, int64_t n_carry, int64_t n_comp, int64_t n_bl
     return DN_OK;
 }
 
+// hand the armed CRC32s (dn_bam_rows_expect_crc) to an inflate call and disarm the store: the first thing such a call does,
+// so that the arming is spent whatever the call then returns.  h may be null (the call refuses it next).
+bool take_expected_crc(dn_bam_rows h, std::vector<uint32_t> &crc)
+{
+    if (!h) return false;
+    const bool armed = h->crc_armed;
+    crc.swap(h->expect_crc);
+    h->expect_crc.clear();
+    h->crc_armed = false;
+    return armed;
+}
+
+int crc_count_error(const char *who, const char *armed_by, size_t n_crc, int64_t n_blocks)
+{
+    return dn::fail(DN_E_INVALID, std::string(who) + ": " + std::to_string(n_crc) + " CRC32s were announced (" + armed_by + ") for " +
+                                  std::to_string(n_blocks) + " blocks");
+}
+
+void check_blocks(std::vector<dn::InflateBlock> &blk, const std::vector<uint32_t> &crc)
+{
+    for (size_t b = 0; b < blk.size(); b++) { blk[b].crc = crc[b]; blk[b].check = 1; }
+}
+
 }  // namespace
+
+extern "C" int dn_bam_rows_expect_crc(dn_bam_rows h, const uint32_t *crc32, int64_t n_blocks)
+{
+    dn::clear_error();
+    if (!h || n_blocks < 0 || n_blocks > INT32_MAX || (n_blocks > 0 && !crc32)) return dn::fail(DN_E_INVALID, "dn_bam_rows_expect_crc: bad argument");
+    h->expect_crc.assign(crc32, crc32 + n_blocks);
+    h->crc_armed = true;
+    return DN_OK;
+}
 
 extern "C" int dn_bam_rows_inflate(dn_bam_rows h, const uint8_t *carry, int64_t n_carry, const uint8_t *comp, int64_t n_comp,
                                    int64_t n_blocks, const int64_t *pay_off, const int32_t *pay_len, const int32_t *isize,
@@ -1035,13 +1070,17 @@ extern "C" int dn_bam_rows_inflate(dn_bam_rows h, const uint8_t *carry, int64_t 
                                    int32_t *status, double *device_ms)
 {
     dn::clear_error();
+    std::vector<uint32_t> crc;
+    const bool armed = take_expected_crc(h, crc);
     if (!h || n_carry < 0 || (n_carry > 0 && !carry) || n_comp < 0 || (n_comp > 0 && !comp) || n_blocks < 0 || n_blocks > INT32_MAX ||
         (n_blocks > 0 && (!pay_off || !pay_len || !isize || !status)) || head_skip < 0 || !host_window || !n_bytes)
         return dn::fail(DN_E_INVALID, "dn_bam_rows_inflate: bad argument");
+    if (armed && (int64_t) crc.size() != n_blocks) return crc_count_error("dn_bam_rows_inflate", "dn_bam_rows_expect_crc", crc.size(), n_blocks);
     std::vector<dn::InflateBlock> blk;
     int64_t total = 0;
     const int brc = window_blocks("dn_bam_rows_inflate", n_carry, n_comp, n_blocks, pay_off, pay_len, isize, head_skip, tail_keep, blk, total);
     if (brc != DN_OK) return brc;
+    if (armed) check_blocks(blk, crc);
     hipStream_t st = h->st;
     DN_TRY(hipSetDevice(h->device));
     h->resident = -1;
@@ -1157,13 +1196,17 @@ extern "C" int dn_bam_rows_inflate_framed(dn_bam_rows h, const uint8_t *comp, in
                                           int32_t *status, int64_t *n_bytes, int64_t *n_carry, double *inflate_ms, double *frame_ms)
 {
     dn::clear_error();
+    std::vector<uint32_t> crc;
+    const bool armed = take_expected_crc(h, crc);
     if (!h || n_comp < 0 || (n_comp > 0 && !comp) || n_blocks < 0 || n_blocks > INT32_MAX ||
         (n_blocks > 0 && (!pay_off || !pay_len || !isize || !status)) || head_skip < 0 || !n_bytes || !n_carry)
         return dn::fail(DN_E_INVALID, "dn_bam_rows_inflate_framed: bad argument");
+    if (armed && (int64_t) crc.size() != n_blocks) return crc_count_error("dn_bam_rows_inflate_framed", "dn_bam_rows_expect_crc", crc.size(), n_blocks);
     std::vector<dn::InflateBlock> blk;
     int64_t total = 0;
     const int brc = window_blocks("dn_bam_rows_inflate_framed", h->n_carry, n_comp, n_blocks, pay_off, pay_len, isize, head_skip, tail_keep, blk, total);
     if (brc != DN_OK) return brc;
+    if (armed) check_blocks(blk, crc);
     hipStream_t st = h->st;
     dn::FrameResult R;
     DN_TRY(hipSetDevice(h->device));

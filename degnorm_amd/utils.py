@@ -205,7 +205,8 @@ def bai_from_bam_file(bam_file):
 def create_index_file(bam_file, **kw):
     """
     Create the .bai index of a .bam file next to it, X.bam -> X.bai (the reference's utils.create_index_file, which shells
-    out to samtools; here degnorm_amd.bam.create_index builds it, on the GPU with device=k).  Returns the .bai path.
+    out to samtools; here degnorm_amd.bam.create_index builds it, on the GPU with device=k; verify=True has every BGZF block
+    checked against the CRC32 of its trailer on the way).  Returns the .bai path.
     """
     from .bam import create_index
     return create_index(bam_file, bai_from_bam_file(bam_file), **kw)

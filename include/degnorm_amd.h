@@ -331,6 +331,22 @@ int  dn_bam_cigar_bounds(int device, int64_t n, const int64_t *pos, const int64_
  *                         block, and zlib-based readers accept such files).  device_ms (nullable): the inflate kernel.
  *   dn_bam_rows_append_resident   dn_bam_rows_append on the resident window, without uploading it again; DN_E_STATE when
  *                         there is none.
+ * The CRC32 of a block's trailer (RFC 1952: reflected polynomial 0xEDB88320, register 0xFFFFFFFF at the start, inverted at
+ * the end) is compared with the inflated bytes only where the caller asks for it; a block that decodes and differs gets
+ * status[b] = DN_INFLATE_E_CRC, and a block that does not decode keeps its decode error.  The CRC covers the whole block,
+ * also the bytes a head_skip or tail_keep leaves out of the window.  On the device every lane of the block's wavefront takes
+ * one slice of the bytes the LDS ring is about to flush and the wave combines the slices ("BGZF inflate").
+ *   dn_bgzf_inflate_check_host / dn_bgzf_inflate_check   dn_bgzf_inflate_host / dn_bgzf_inflate with crc32[b], the CRC32 of
+ *                         block b's trailer; crc32 == NULL: no check.  out == NULL: the blocks are decoded and checked and
+ *                         their bytes dropped (on the device nothing is written or copied back but the statuses).
+ *   dn_bgzf_crc32_host    *crc = the CRC32 of data[0 .. n) by the routines the kernel uses: the data cut into spans of
+ *                         flush_bytes (at least 1) as the ring's flushes cut a block, every span into `lanes` slices
+ *                         (1 .. 64; else DN_E_INVALID).  No device is touched.
+ *   dn_bam_rows_expect_crc   arm the store's next dn_bam_rows_inflate or dn_bam_rows_inflate_framed with the trailer CRC32 of
+ *                         each of its n_blocks blocks.  That call consumes the arming whatever it returns; when its block
+ *                         count is another, it returns DN_E_INVALID before it touches the store.
+ *   dn_bai_expect_crc     the same for a device builder's next dn_bai_window; DN_E_STATE on a host builder, whose caller
+ *                         holds the inflated bytes and checks them itself.
  * Errors: dn_reads_last_error(). */
 #define DN_INFLATE_E_HEADER    1   /* block type 3, a stored block whose LEN / NLEN disagree, too many code lengths         */
 #define DN_INFLATE_E_LENGTHS   2   /* over-subscribed or incomplete code lengths, a bad repeat, no end-of-block code        */
@@ -339,6 +355,7 @@ int  dn_bam_cigar_bounds(int device, int64_t n, const int64_t *pos, const int64_
 #define DN_INFLATE_E_INPUT     5   /* the payload ends before the final block does                                          */
 #define DN_INFLATE_E_SIZE      6   /* the output is not ISIZE bytes long                                                    */
 #define DN_INFLATE_E_TRAILING  7   /* bytes left in the payload after the final block                                       */
+#define DN_INFLATE_E_CRC       8   /* decoded, but the CRC32 of the bytes is not the trailer's (only where it is checked)   */
 int  dn_bgzf_inflate_host(const uint8_t *comp, int64_t n_comp, int64_t n_blocks, const int64_t *pay_off, const int32_t *pay_len,
                           const int64_t *out_off, uint8_t *out, int32_t *status);
 int  dn_bgzf_inflate(int device, const uint8_t *comp, int64_t n_comp, int64_t n_blocks, const int64_t *pay_off,
@@ -349,6 +366,13 @@ int  dn_bam_rows_inflate(dn_bam_rows h, const uint8_t *carry, int64_t n_carry, c
                          int32_t head_skip, int32_t tail_keep, const uint8_t **host_window, int64_t *n_bytes,
                          int32_t *status, double *device_ms);
 int  dn_bam_rows_append_resident(dn_bam_rows h, const int64_t *rec_off, int64_t n_rec);
+int  dn_bgzf_inflate_check_host(const uint8_t *comp, int64_t n_comp, int64_t n_blocks, const int64_t *pay_off, const int32_t *pay_len,
+                                const int64_t *out_off, uint8_t *out, int32_t *status, const uint32_t *crc32);
+int  dn_bgzf_inflate_check(int device, const uint8_t *comp, int64_t n_comp, int64_t n_blocks, const int64_t *pay_off,
+                           const int32_t *pay_len, const int64_t *out_off, uint8_t *out, int32_t *status, double *copy_ms,
+                           double *device_ms, const uint32_t *crc32);
+int  dn_bgzf_crc32_host(const uint8_t *data, int64_t n, int32_t lanes, int32_t flush_bytes, uint32_t *crc);
+int  dn_bam_rows_expect_crc(dn_bam_rows h, const uint32_t *crc32, int64_t n_blocks);
 
 /* Record framing on the device (csrc/dn_frame.hip) ----------------------------------------------------------------------
  * dn_bam_frame's walk, block_size to block_size, is serial.  Here the window is cut into segments of segment_bytes (at
@@ -402,6 +426,7 @@ int  dn_bam_rows_frame_info(dn_bam_rows h, int64_t *n_segments, int64_t *n_fixup
  *                         indexed where it lies, and only the tables of run heads and linear-index claims come back.  When
  *                         a block failed (status[b] != 0) the call returns DN_OK and the builder is spent.  *n_rec: the
  *                         records of this window; inflate_ms / frame_ms / index_ms (nullable): by HIP events.
+ *                         dn_bai_expect_crc (BGZF inflate, above) has the next window's blocks checked against their CRC32s.
  *   dn_bai_window_host    host builder: the same on the n_data inflated bytes of the n_blocks blocks.
  *   dn_bai_finish         no more windows; end_voffset is the virtual offset of the end of the stream (the block behind the
  *                         last one that holds a byte, offset 0).  sizes[0 .. 6] = bins (without pseudo-bins), chunks,
@@ -422,6 +447,7 @@ int  dn_bai_window(dn_bai h, const uint8_t *comp, int64_t n_comp, int64_t n_bloc
                    double *inflate_ms, double *frame_ms, double *index_ms);
 int  dn_bai_window_host(dn_bai h, const uint8_t *data, int64_t n_data, int64_t n_blocks, const int32_t *isize, const int64_t *coffset,
                         int32_t head_skip, int64_t *n_rec);
+int  dn_bai_expect_crc(dn_bai h, const uint32_t *crc32, int64_t n_blocks);
 int  dn_bai_finish(dn_bai h, int64_t end_voffset, int64_t *sizes);
 int  dn_bai_fetch(dn_bai h, int32_t *ref_n_bin, int32_t *ref_n_intv, uint64_t *ref_pseudo, int32_t *bin_id, int32_t *bin_n_chunk,
                   uint64_t *chunks, uint64_t *ioffset);

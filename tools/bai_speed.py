@@ -42,14 +42,14 @@ def _span(values, digits=1):
     return [round(min(values), digits), round(max(values), digits)]
 
 
-def _level(path, modes, jobs, reps):
+def _level(path, modes, jobs, reps, verify=False):
     rows = {m: [] for m in modes}
     out = {}
     for k in range(reps + 1):                        # the first round loads the library and warms the device up
         for m in modes:
             stats = {}
             t0 = time.perf_counter()
-            bam.create_index(path, path + '.' + m, overwrite=True, device=0 if m == 'device' else None, n_jobs=jobs, stats=stats)
+            bam.create_index(path, path + '.' + m, overwrite=True, device=0 if m == 'device' else None, n_jobs=jobs, stats=stats, verify=verify)
             stats['e2e_ms'] = 1e3 * (time.perf_counter() - t0)
             if k > 0:
                 rows[m].append(stats)
@@ -86,6 +86,7 @@ def main():
     ap.add_argument('--levels', default='1,6')
     ap.add_argument('--modes', default='device,host')
     ap.add_argument('--dir', default=None)
+    ap.add_argument('--verify', action='store_true', help='check every BGZF block against the CRC32 of its trailer')
     a = ap.parse_args()
     modes = [m for m in ('device', 'host') if m in a.modes.split(',')]
     reads, chrom_len, _, _, _ = rf.scale_case(n_reads=a.reads)
@@ -94,11 +95,13 @@ def main():
     try:
         os.makedirs(work, exist_ok=True)
         out = {'tool': 'bai_speed', 'reads': a.reads, 'jobs': a.jobs, 'reps': a.reps, 'modes': modes}
+        if a.verify:
+            out['verify'] = True
         for level in (int(x) for x in a.levels.split(',')):
             path = os.path.join(work, 'se_{0}_l{1}.bam'.format(a.reads, level))
             if not os.path.isfile(path):
                 bf.write_bam(path, [('chrS', chrom_len)], se, level=level, index=False)
-            row = _level(path, modes, a.jobs, a.reps)
+            row = _level(path, modes, a.jobs, a.reps, a.verify)
             row['bam_mb'] = round(os.path.getsize(path) / 2 ** 20, 1)
             row['inflated_mb'] = round(int(bam.bgzf_blocks(path)[2].sum()) / 2 ** 20, 1)
             out['level{0}'.format(level)] = row

@@ -46,11 +46,11 @@ from degnorm_amd import bam                          # noqa: E402
 from degnorm_amd import reads as dr                  # noqa: E402
 
 
-def _best(path, chrom, ov, gene_df, exon_df, out, jobs, reps, inflate, frame='host', segment_bytes=None):
+def _best(path, chrom, ov, gene_df, exon_df, out, jobs, reps, inflate, frame='host', segment_bytes=None, verify=False):
     best, rows = None, []
     for k in range(reps + 1):                        # the first run loads the library and warms the device up
         proc = bam.NativeBamReadsProcessor(path, path + '.bai', output_dir=os.path.join(out, str(k)), n_jobs=jobs, verbose=False,
-                                           inflate=inflate, frame=frame, frame_segment_bytes=segment_bytes)
+                                           inflate=inflate, frame=frame, frame_segment_bytes=segment_bytes, verify=verify)
         os.makedirs(proc.save_dir, exist_ok=True)
         proc.timing = {}
         t0 = time.perf_counter()
@@ -69,6 +69,9 @@ def _best(path, chrom, ov, gene_df, exon_df, out, jobs, reps, inflate, frame='ho
     for key in ('inflate_ms', 'frame_ms', 'frame_device_ms', 'e2e_ms'):
         best[key + '_min'] = round(min(r[key] for r in rows), 1)
         best[key + '_max'] = round(max(r[key] for r in rows), 1)
+    if inflate == 'device':                          # the kernel's own spread: what --verify is held against
+        best['inflate_device_ms_min'] = round(min(r['inflate_device_ms'] for r in rows), 3)
+        best['inflate_device_ms_max'] = round(max(r['inflate_device_ms'] for r in rows), 3)
     return best
 
 
@@ -83,6 +86,7 @@ def main():
     ap.add_argument('--frame', choices=['host', 'device'], default='host')
     ap.add_argument('--segment-bytes', type=int, default=None, help='segment size of --frame device (default: the library\'s)')
     ap.add_argument('--cases', default='se,pe', help='se, pe or se,pe')
+    ap.add_argument('--verify', action='store_true', help='check every BGZF block against the CRC32 of its trailer')
     a = ap.parse_args()
     reads, chrom_len, ov, gene_df, exon_df = rf.scale_case(n_reads=a.reads)
     work = a.dir or tempfile.mkdtemp(prefix='bam_speed_')
@@ -106,9 +110,11 @@ def main():
         out = {'tool': 'bam_speed', 'reads': a.reads, 'jobs': a.jobs, 'inflate': a.inflate, 'frame': a.frame, 'level': a.level,
                'bam_mb': round(os.path.getsize(files[cases[0]]) / 2 ** 20, 1), 'inflated_mb': round(inflated[cases[0]] / 2 ** 20, 1),
                'write_s': round(write_s, 1)}
+        if a.verify:
+            out['verify'] = True
         for name in cases:
             row = _best(files[name], 'chrS', ov, gene_df, exon_df, os.path.join(work, 'out_{0}_{1}_{2}'.format(name, a.inflate, a.frame)),
-                        a.jobs, a.reps, a.inflate, a.frame, a.segment_bytes)
+                        a.jobs, a.reps, a.inflate, a.frame, a.segment_bytes, a.verify)
             if row['inflate_device_ms'] > 0:
                 row['inflate_gbps'] = round(inflated[name] / (row['inflate_device_ms'] * 1e-3) / 1e9, 2)
             row['reads_per_s'] = round(a.reads / (row['e2e_ms'] * 1e-3))
