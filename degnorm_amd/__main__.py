@@ -6,10 +6,15 @@
     python -m degnorm_amd -w PREVIOUS_OUTPUT_DIR -o out
 
     python -m degnorm_amd --bam-dir DIR --create-bai -g genes.gtf -o out
+    python -m degnorm_amd --bam-dir DIR --sort-bam -g genes.gtf -o out
 
 The flags and their validation follow the reference.  With --create-bai a .bam file without a .bai file next to it gets
 one before the run (the reference shells out to samtools for this; here degnorm_amd.bam.create_index builds it on the GPU);
-without the flag a missing index is an error.  Not offered: --plot-genes, the HTML report and the MPI command (see
+without the flag a missing index is an error.  With --sort-bam every .bam file whose header does not say SO:coordinate --
+an aligner's unsorted or name-collated output -- is first sorted by coordinate on the GPU (degnorm_amd.bam.sort_bam; the
+reference's documentation runs samtools sort for this) to <output directory>/sorted_bam/<the same file name>, indexed
+there, and read in place of the input; the sorted copies are kept, and files that say SO:coordinate are used as they are.
+Not offered: --plot-genes, the HTML report and the MPI command (see
 degnorm_amd.warm_start --mpi for the sharded NMF-OA run).
 """
 import argparse
@@ -24,8 +29,9 @@ def argparser():
     ap = argparse.ArgumentParser(
         prog='python -m degnorm_amd',
         description='DegNorm (RNA-seq degradation normalization) from .bam and .gtf files on an AMD Instinct GPU.',
-        epilog='A .bam file needs its .bai index file; --create-bai makes the missing ones.  Not available in this command: '
-               '--plot-genes, the HTML summary report and the MPI command.')
+        epilog='Not available in this command: --plot-genes, the HTML summary report and the MPI command.  A .bam file must be '
+               'sorted by coordinate and needs its .bai index file: --sort-bam sorts (and indexes) the files that are not sorted, '
+               '--create-bai makes the missing index files of sorted ones.')
     ap.add_argument('--bam-files', nargs='+', default=None,
                     help='sorted .bam alignment files, one per sample (single-end or paired), at least two')
     ap.add_argument('--bai-files', nargs='+', default=None,
@@ -55,13 +61,17 @@ def argparser():
     ap.add_argument('--create-bai', action='store_true',
                     help='create the .bai index file X.bai of every X.bam that has none next to it, on the GPU, before the run '
                          '(not with --bai-files)')
+    ap.add_argument('--sort-bam', action='store_true',
+                    help='sort every .bam file whose header does not say SO:coordinate by coordinate, on the GPU, to '
+                         '<output directory>/sorted_bam/<same name>, index the sorted copy there and use it in place of the '
+                         'input; the copies are kept (not with --bai-files)')
     ap.add_argument('--device-inflate', action='store_true',
                     help='inflate the BGZF blocks of the .bam files on the GPU instead of with zlib on the host')
     ap.add_argument('--device-frame', action='store_true',
                     help='find the record starts of the inflated .bam bytes on the GPU instead of with a serial walk on the host')
     ap.add_argument('--verify-crc', action='store_true',
                     help='check every BGZF block read from the .bam files against the CRC32 of its trailer (also while '
-                         '--create-bai indexes them) and stop at the first that differs')
+                         '--create-bai indexes and --sort-bam sorts them) and stop at the first that differs')
     return ap
 
 
@@ -71,10 +81,14 @@ def bai_from_bam_file(bam_file):
     return bam_file[:-3] + 'bai'
 
 
-def _default_bai_files(bam_files, create=False):
-    """(X.bai of every X.bam, the .bam files whose X.bai is missing); without `create` a missing one is an error."""
+def _default_bai_files(bam_files, create=False, sort=()):
+    """(X.bai of every X.bam, the .bam files whose X.bai is missing); without `create` a missing one is an error.  The
+    files of `sort` are sorted and indexed later: their entry is None."""
     bai_files, create_bai_files = [], []
     for bam_file in bam_files:
+        if bam_file in sort:
+            bai_files.append(None)
+            continue
         bai_file = re.sub('.bam$', '.bai', bam_file)
         if not os.path.isfile(bai_file):
             if not create:
@@ -87,10 +101,21 @@ def _default_bai_files(bam_files, create=False):
     return bai_files, create_bai_files
 
 
+def _unsorted(bam_files):
+    """The .bam files whose header does not say SO:coordinate."""
+    from .bam import sort_order
+    return [b for b in bam_files if sort_order(b) != 'coordinate']
+
+
 def validate_args(args):
     """The reference's checks on parsed arguments (utils.py:338-482); fills args.bam_files / args.bai_files, and
-    args.create_bai_files with the .bam files whose index is to be made first (empty without args.create_bai)."""
+    args.create_bai_files with the .bam files whose index is to be made first (empty without args.create_bai) and
+    args.sort_bam_files with those that are to be sorted first (empty without args.sort_bam; their index file is None)."""
     create = getattr(args, 'create_bai', False)
+    sort = getattr(args, 'sort_bam', False)
+    args.sort_bam_files = []
+    if sort and args.bai_files is not None:
+        raise ValueError('Do not specify both --sort-bam and --bai-files: a sorted copy gets an index file of its own.')
     if (not args.bam_files and not args.bam_dir) and (not args.warm_start_dir):
         raise ValueError('Must specify either --bam-files, --bam-dir, or --warm-start-dir as a data input option.')
     n_cpu = os.cpu_count() or 1
@@ -123,7 +148,7 @@ def validate_args(args):
         bam_files = [os.path.join(args.bam_dir, f) for f in sorted(os.listdir(args.bam_dir)) if f.endswith('.bam')]
         if len(bam_files) < 2:
             raise ValueError('Only found {0} .bam files within directory {1}'.format(len(bam_files), args.bam_dir))
-        bai_files, create_bai_files = _default_bai_files(bam_files, create)
+        bai_files, create_bai_files = _default_bai_files(bam_files, create, _unsorted(bam_files) if sort else ())
     else:
         for bam_file in args.bam_files:
             if not bam_file.endswith('.bam'):
@@ -141,12 +166,15 @@ def validate_args(args):
                     raise FileNotFoundError('Count not find .bai file {0}'.format(bai_file))
                 bai_files.append(bai_file)
         else:
-            bai_files, create_bai_files = _default_bai_files(bam_files, create)
+            bai_files, create_bai_files = _default_bai_files(bam_files, create, _unsorted(bam_files) if sort else ())
     if len(bam_files) < 2:
         raise ValueError('Fewer than 2 .bam files were found. Not sufficiently many to run DegNorm.')
     if len(bam_files) != len(set(bam_files)):
         raise ValueError('Supplied .bam files are not uniquely named!')
     args.bam_files, args.bai_files, args.create_bai_files = bam_files, bai_files, create_bai_files
+    args.sort_bam_files = [b for b, i in zip(bam_files, bai_files) if i is None]
+    if len(set(os.path.basename(b) for b in args.sort_bam_files)) != len(args.sort_bam_files):
+        raise ValueError('The .bam files to be sorted are not uniquely named: their sorted copies share one directory.')
     return args
 
 
@@ -170,11 +198,7 @@ def create_output_dir(user_input=None):
     return output_dir
 
 
-def main(argv=None):
-    args = validate_args(argparser().parse_args(argv))
-    output_dir = create_output_dir(args.output_dir)
-    logging.basicConfig(level=logging.INFO, format='DegNorm (%(asctime)s) ---- %(message)s', datefmt='%m/%d/%Y %I:%M:%S',
-                        handlers=[logging.StreamHandler(), logging.FileHandler(os.path.join(output_dir, 'degnorm.log'))])
+def _run(args, output_dir, device, verify):
     logging.info('DegNorm output directory -- {0}'.format(output_dir))
     if args.warm_start_dir:
         from .warm_start import run_from_warm_start
@@ -184,17 +208,42 @@ def main(argv=None):
                             minimax_coverage=args.minimax_coverage)
     else:
         from .pipeline import run_pipeline
-        if args.create_bai_files:
-            from .utils import create_index_file
-            for k, bam_file in enumerate(args.create_bai_files):
-                logging.info('creating index file for {0} -- {1} / {2}'.format(bam_file, k + 1, len(args.create_bai_files)))
-                create_index_file(bam_file, device=int(os.environ.get('LOCAL_RANK', 0)), verify=getattr(args, 'verify_crc', False))
+        for k, bam_file in enumerate(args.sort_bam_files):
+            from .bam import create_index, sort_bam
+            sorted_dir = os.path.join(output_dir, 'sorted_bam')
+            os.makedirs(sorted_dir, exist_ok=True)
+            logging.info('sorting {0} by coordinate -- {1} / {2}'.format(bam_file, k + 1, len(args.sort_bam_files)))
+            at = args.bam_files.index(bam_file)
+            args.bam_files[at] = sort_bam(bam_file, os.path.join(sorted_dir, os.path.basename(bam_file)), device=device,
+                                          n_jobs=args.proc_per_node, verify=verify)
+            args.bai_files[at] = create_index(args.bam_files[at], bai_from_bam_file(args.bam_files[at]), device=device, verify=verify)
         run_pipeline(args.bam_files, args.bai_files, args.genome_annotation, output_dir, degnorm_iter=args.iter,
                      nmf_iter=args.nmf_iter, downsample_rate=args.downsample_rate, minimax_coverage=args.minimax_coverage,
                      skip_baseline_selection=args.skip_baseline_selection, unique_alignment=not args.non_unique_alignments,
                      n_jobs=args.proc_per_node, inflate='device' if args.device_inflate else 'host',
-                     frame='device' if args.device_frame else 'host', verify=getattr(args, 'verify_crc', False))
+                     frame='device' if args.device_frame else 'host', verify=verify)
     logging.info('DegNorm pipeline complete! Exiting...')
+
+
+def main(argv=None):
+    args = validate_args(argparser().parse_args(argv))
+    fmt = {'format': 'DegNorm (%(asctime)s) ---- %(message)s', 'datefmt': '%m/%d/%Y %I:%M:%S'}
+    logging.basicConfig(level=logging.INFO, handlers=[logging.StreamHandler()], **fmt)
+    device, verify = int(os.environ.get('LOCAL_RANK', 0)), getattr(args, 'verify_crc', False)
+    # the missing index files first: a file that cannot be indexed stops the run before an output directory exists
+    for k, bam_file in enumerate(args.create_bai_files or []):
+        from .utils import create_index_file
+        logging.info('creating index file for {0} -- {1} / {2}'.format(bam_file, k + 1, len(args.create_bai_files)))
+        create_index_file(bam_file, device=device, verify=verify)
+    output_dir = create_output_dir(args.output_dir)
+    log_file = logging.FileHandler(os.path.join(output_dir, 'degnorm.log'))
+    log_file.setFormatter(logging.Formatter(fmt['format'], fmt['datefmt']))
+    logging.getLogger().addHandler(log_file)
+    try:
+        _run(args, output_dir, device, verify)
+    finally:                                             # a later call in this process logs to its own file only
+        logging.getLogger().removeHandler(log_file)
+        log_file.close()
     return 0
 
 

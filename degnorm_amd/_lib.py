@@ -147,6 +147,16 @@ def load(build_if_missing=False):
     lib.dn_bai_expect_crc.argtypes = [vp, P(u32), i64]
     lib.dn_bai_finish.argtypes = [vp, i64, P(i64)]
     lib.dn_bai_fetch.argtypes = [vp, P(i32), P(i32), P(u64), P(i32), P(i32), P(u64), P(u64)]
+    lib.dn_bam_sort_device_memory.argtypes = [c.c_int, P(i64), P(i64)]
+    lib.dn_bam_sort_create.argtypes = [c.c_int, i32, i64, i64, i64, P(vp)]
+    lib.dn_bam_sort_destroy.argtypes = [vp]
+    lib.dn_bam_sort_destroy.restype = None
+    lib.dn_bam_sort_window.argtypes = [vp, P(u8), i64, i64, P(i64), P(i32), P(i32), i32, P(i32), P(dbl)]
+    lib.dn_bam_sort_window_host.argtypes = [vp, P(u8), i64, i32]
+    lib.dn_bam_sort_expect_crc.argtypes = [vp, P(u32), i64]
+    lib.dn_bam_sort_finish.argtypes = [vp, P(i64), P(i64), P(i64), P(dbl), P(dbl), P(dbl)]
+    lib.dn_bam_sort_ends.argtypes = [vp, i64, i64, P(i64)]
+    lib.dn_bam_sort_read.argtypes = [vp, i64, i64, P(u8)]
     lib.dn_gtf_scan.argtypes = [c.c_int, P(c.c_uint8), i64, i64, P(i64), P(i64), P(i64), P(i64), P(i32), P(u64), P(i64), P(i64),
                                 P(i64), P(i32), P(u64), P(i64), P(i32), P(dbl), P(dbl)]
     lib.dn_gtf_last_error.restype = c.c_char_p

@@ -24,6 +24,11 @@ A file without an index gets one from build_index / create_index (csrc/dn_bai.hi
 inflated, framed and indexed on the device window by window (or, device=None, with zlib and the host build of the same
 source); parse_bai / BamIndex.tobytes / write_bai read and write whole .bai files, index_chunks is the region query.
 
+A file that is not sorted by coordinate -- an aligner's default output -- is sorted by sort_bam (csrc/dn_sort.hip): the whole
+inflated record stream is inflated into one device buffer, framed, keyed, radix-sorted (stably: ties keep file order) and
+copied record by record into a second buffer; the host cuts, deflates (zlib) and writes the blocks of the sorted file under a
+header that says SO:coordinate.  device=None does the same with zlib and the host build of the same source.
+
 Every path that inflates takes verify=True: the inflated bytes of each BGZF block are then compared with the CRC32 of its
 trailer -- zlib.crc32 where zlib inflates, the wavefront that inflates the block where the device does -- and a block that
 differs is a ValueError naming the file and the block's offset.  verify_bgzf checks a whole file that way (bgzip -t).
@@ -1047,3 +1052,266 @@ def index_chunks(index, tid, beg, end):
         else:
             out.append((b, e))
     return out
+
+
+# --- sorting by coordinate -------------------------------------------------------------------------------------------------
+
+BGZF_BLOCK_DATA = 0xff00         # inflated bytes a written block holds at most (htslib's BGZF_BLOCK_SIZE)
+DEVICE_MEMORY_SHARE = 0.8        # of the device's free memory a sort may plan with
+_SORT_TABLE_BYTES = 56           # per record: offset, two (key, ordinal) pairs, length and destination
+_ENDS_CHUNK = 1 << 20            # record ends fetched at a time
+
+
+def _header_data(path, verify=False):
+    """(inflated bytes of the blocks the BAM header lies in, their number, header end, [(SQ name, length)])."""
+    data = bytearray()
+    for k, (off, blk) in enumerate(iter_blocks(path)):
+        data += _host_inflate(path, [(off, blk)], None, verify)[0]
+        got = parse_header(data)
+        if got is not None:
+            return bytes(data), k + 1, got[0], got[1]
+    raise ValueError('{0}: BAM header cut short'.format(path))
+
+
+def _header_lines(text):
+    return text.rstrip(b'\x00').decode('latin-1').split('\n')
+
+
+def sort_order(path):
+    """The SO: value of the @HD line of a BAM file's header ('coordinate', 'queryname', 'unsorted', ...), or None without one."""
+    data = _header_data(path)[0]
+    l_text = struct.unpack_from('<i', data, 4)[0]
+    first = _header_lines(data[8:8 + l_text])[0]
+    if first.startswith('@HD'):
+        for field in first.split('\t')[1:]:
+            if field.startswith('SO:'):
+                return field[3:]
+    return None
+
+
+def coordinate_header(header):
+    """
+    The bytes of a BAM header (magic to the end of the reference list) with the sort order of its text set to coordinate:
+    the SO: field of the @HD line is replaced (appended when the line has none), a text without @HD line gets
+    '@HD\\tVN:1.6\\tSO:coordinate' as its first line; other fields and lines, and the reference list, stay as they are.
+    """
+    l_text = struct.unpack_from('<i', header, 4)[0]
+    lines = _header_lines(header[8:8 + l_text])
+    if lines[0].startswith('@HD'):
+        fields = lines[0].split('\t')
+        if any(f.startswith('SO:') for f in fields[1:]):
+            fields = [fields[0]] + ['SO:coordinate' if f.startswith('SO:') else f for f in fields[1:]]
+        else:
+            fields.append('SO:coordinate')
+        lines[0] = '\t'.join(fields)
+    else:
+        lines.insert(0, '@HD\tVN:1.6\tSO:coordinate')
+        if lines[-1] != '':                           # an empty text, or one that does not end its last line
+            lines.append('')
+    text = '\n'.join(lines).encode('latin-1')
+    return header[:4] + struct.pack('<i', len(text)) + text + header[8 + l_text:]
+
+
+def bgzf_compress(data, level=1):
+    """One BGZF block holding `data` (at most 0xff00 bytes), deflated by zlib at `level`."""
+    c = zlib.compressobj(int(level), zlib.DEFLATED, -15)
+    raw = c.compress(data) + c.flush()
+    total = 18 + len(raw) + 8
+    if len(data) > BGZF_BLOCK_DATA or total > 65536:
+        raise ValueError('a BGZF block cannot hold {0} bytes'.format(len(data)))
+    return (b'\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff\x06\x00BC\x02\x00' + struct.pack('<H', total - 1) + raw +
+            struct.pack('<II', zlib.crc32(data) & 0xffffffff, len(data)))
+
+
+def _block_cuts(end_chunks):
+    """
+    [begin, end) of the blocks of a record stream whose records end at the offsets `end_chunks` yields (ascending int64
+    arrays): a block takes whole records while they fit in BGZF_BLOCK_DATA bytes; a record longer than that is cut into
+    blocks of its own.
+    """
+    cur, cand = 0, None
+    for ends in end_chunks:
+        i, n = 0, len(ends)
+        while i < n:
+            k = int(np.searchsorted(ends, cur + BGZF_BLOCK_DATA, side='right'))
+            if k > i:
+                cand, i = int(ends[k - 1]), k
+                if k == n:
+                    break                             # the next chunk's first records may still fit
+            elif cand is None:
+                end = int(ends[i])
+                while cur < end:
+                    nxt = min(cur + BGZF_BLOCK_DATA, end)
+                    yield cur, nxt
+                    cur = nxt
+                i += 1
+                continue
+            yield cur, cand
+            cur, cand = cand, None
+    if cand is not None:
+        yield cur, cand
+
+
+def device_memory(device):
+    """(free, total) bytes of GPU `device`."""
+    free, total = ctypes.c_int64(0), ctypes.c_int64(0)
+    _check(_lib.load().dn_bam_sort_device_memory(int(device), ctypes.byref(free), ctypes.byref(total)), 'dn_bam_sort_device_memory')
+    return int(free.value), int(total.value)
+
+
+def sort_bam(src, dst, device=None, n_jobs=1, level=1, window_bytes=256 << 20, segment_bytes=None, verify=False, overwrite=False,
+             max_device_bytes=None, stats=None):
+    """
+    Write the BAM file `src` sorted by coordinate to `dst` (what `samtools sort` is run for before an index can be made);
+    returns dst.  The order is defined in include/degnorm_amd.h: ascending (refID, pos), records without a reference last,
+    and records of equal (refID, pos) in the order of src -- which is not samtools' tie rule, so the two programs' outputs
+    may differ in the order of such records.
+
+    device=k: the BGZF blocks go to GPU k about window_bytes of inflated data at a time and are inflated there into one
+    buffer that holds the whole record stream, which is framed, keyed, sorted (radix sort of key and ordinal), and copied
+    record by record into a second buffer of the same size (csrc/dn_sort.hip); the sorted stream comes back window_bytes at
+    a time.  The device must hold the stream twice: the need -- twice the inflated size, the largest window's compressed
+    blocks and 56 bytes for each record, estimated at one per 128 bytes -- is checked before anything is uploaded against
+    max_device_bytes, by default 0.8 of the memory hipMemGetInfo reports free, and a ValueError gives both figures.
+    device=None: zlib inflates in n_jobs threads and the host build of the same source sorts (std::stable_sort); no GPU is
+    needed.  Both write the same file.
+
+    The header is copied with its @HD line's SO: set to coordinate (coordinate_header).  The output's blocks hold at most
+    0xff00 inflated bytes and end where a record ends (a longer record gets blocks of its own), are deflated by zlib at
+    `level` in n_jobs threads, and are written to dst + '.tmp', which becomes dst when complete.  verify: every block of src
+    must have the CRC32 of its trailer.  Errors are ValueErrors that name src and the block's offset or the record's
+    ordinal, the same from both paths, and leave neither dst nor dst + '.tmp' behind; FileExistsError when dst exists and
+    overwrite is off.  stats, a dict, receives `inflate_device_ms`, `frame_device_ms`, `frame_fixups`, `sort_device_ms` (key
+    pass, sort and scan), `gather_device_ms`, `records`, `bytes`, `windows` and `deflate_s`.
+    """
+    if os.path.exists(dst) and not overwrite:
+        raise FileExistsError('{0} exists; pass overwrite=True to replace it'.format(dst))
+    if not has_eof_block(src):
+        raise ValueError('{0}: no BGZF end-of-file block; the file is truncated'.format(src))
+    if segment_bytes is not None and int(segment_bytes) < 64:
+        raise ValueError('segment_bytes must be at least 64, not {0}'.format(segment_bytes))
+    window_bytes = max(int(256 << 20 if window_bytes is None else window_bytes), 1)
+    lib = _lib.load()
+    i64, i32, u8 = ctypes.c_int64, ctypes.c_int32, ctypes.c_uint8
+    n_jobs = max(int(n_jobs), 1)
+    pool = ThreadPoolExecutor(max_workers=n_jobs) if n_jobs > 1 else None
+    h = ctypes.c_void_p()
+    tmp = dst + '.tmp'
+    t = {'inflate_device_ms': 0.0, 'deflate_s': 0.0, 'windows': 0}
+
+    def call(rc, what):
+        try:
+            _check(rc, what)
+        except ValueError as e:
+            raise ValueError('{0}: {1}'.format(src, e))
+
+    def window(batch, head_skip):
+        t['windows'] += 1
+        if device is None:
+            data = b''.join(_host_inflate(src, batch, pool, verify))
+            joined = np.frombuffer(data, dtype=np.uint8) if data else np.zeros(1, np.uint8)
+            call(lib.dn_bam_sort_window_host(h, _ptr(joined, u8), len(data), int(head_skip)), 'dn_bam_sort_window_host')
+            return
+        blocks = [b for _, b in batch]
+        comp, n_comp, pay_off, pay_len, isize = _block_layout(blocks)
+        isize32 = np.where(isize > 2 ** 31 - 1, -1, isize).astype(np.int32)      # the library refuses a negative size
+        status, ms = np.zeros(max(len(batch), 1), np.int32), ctypes.c_double(0.0)
+        if verify:
+            call(lib.dn_bam_sort_expect_crc(h, _ptr(block_crcs(blocks), ctypes.c_uint32), len(batch)), 'dn_bam_sort_expect_crc')
+        call(lib.dn_bam_sort_window(h, _ptr(comp, u8), n_comp, len(batch), _ptr(pay_off, i64), _ptr(pay_len, i32), _ptr(isize32, i32),
+                                    int(head_skip), _ptr(status, i32), ctypes.byref(ms)), 'dn_bam_sort_window')
+        t['inflate_device_ms'] += float(ms.value)
+        _raise_status(status[:len(batch)], lambda k: '{0}: the BGZF block at byte {1}'.format(src, batch[k][0]))
+
+    def batches(skip_blocks):
+        """Lists of (offset, block) of about window_bytes of inflated data, from block number skip_blocks on."""
+        batch, size = [], 0
+        for k, (off, blk) in enumerate(iter_blocks(src)):
+            if k < skip_blocks:
+                continue
+            batch.append((off, blk))
+            size += struct.unpack_from('<I', blk, len(blk) - 4)[0]
+            if size >= window_bytes:
+                yield batch
+                batch, size = [], 0
+        if batch:
+            yield batch
+
+    def ends_chunks(n_records):
+        for first in range(0, n_records, _ENDS_CHUNK):
+            n = min(_ENDS_CHUNK, n_records - first)
+            ends = np.zeros(n, np.int64)
+            call(lib.dn_bam_sort_ends(h, first, n, _ptr(ends, i64)), 'dn_bam_sort_ends')
+            yield ends
+
+    def deflated(parts):
+        t0 = time.perf_counter()
+        one = lambda d: bgzf_compress(d, level)                                  # noqa: E731
+        out = list(pool.map(one, parts) if pool is not None else map(one, parts))
+        t['deflate_s'] += time.perf_counter() - t0
+        return out
+
+    try:
+        # the header, on zlib whatever the device: it may span several blocks; and the size of the whole stream
+        data, head_blocks, header_end, refs = _header_data(src, verify)
+        _, _, isizes = bgzf_blocks(src)
+        n_stream = int(isizes.sum()) - header_end
+        n_comp_max, size, comp = 0, 0, 0
+        for k in range(head_blocks - 1, len(isizes)):                            # the compressed bytes of the largest window
+            size, comp = size + int(isizes[k]), comp + 65536
+            if size >= window_bytes or k == len(isizes) - 1:
+                n_comp_max, size, comp = max(n_comp_max, comp), 0, 0
+        if device is not None:
+            need = 2 * n_stream + n_comp_max + _SORT_TABLE_BYTES * (n_stream // 128 + 1)
+            have = int(DEVICE_MEMORY_SHARE * device_memory(device)[0]) if max_device_bytes is None else int(max_device_bytes)
+            if need > have:
+                raise ValueError('{0}: sorting needs about {1} bytes of device memory ({2} bytes of records), {3} are allowed; '
+                                 'a file that does not fit the device cannot be sorted here'.format(src, need, n_stream, have))
+        call(lib.dn_bam_sort_create(-1 if device is None else int(device), len(refs), n_stream, int(segment_bytes or 0), window_bytes,
+                                    ctypes.byref(h)), 'dn_bam_sort_create')
+        # the first window starts inside the block in which the header ends
+        head_skip = header_end - (len(data) - int(isizes[head_blocks - 1]))
+        for batch in batches(head_blocks - 1):
+            window(batch, head_skip)
+            head_skip = 0
+        n_rec, n_bytes, fix = i64(0), i64(0), i64(0)
+        ms = [ctypes.c_double(0.0) for _ in range(3)]
+        call(lib.dn_bam_sort_finish(h, ctypes.byref(n_rec), ctypes.byref(n_bytes), ctypes.byref(fix), ctypes.byref(ms[0]), ctypes.byref(ms[1]),
+                                    ctypes.byref(ms[2])), 'dn_bam_sort_finish')
+        header = coordinate_header(data[:header_end])
+        buf = {'lo': 0, 'data': b''}
+
+        def stream(a, b):
+            """Bytes [a, b) of the sorted stream; fetched window_bytes at a time, in ascending order."""
+            if b > buf['lo'] + len(buf['data']):
+                n = min(max(window_bytes, b - a), n_bytes.value - a)
+                arr = np.zeros(max(n, 1), np.uint8)
+                call(lib.dn_bam_sort_read(h, a, n, _ptr(arr, u8)), 'dn_bam_sort_read')
+                buf['lo'], buf['data'] = a, arr[:n].tobytes()
+            return buf['data'][a - buf['lo']:b - buf['lo']]
+
+        with open(tmp, 'wb') as f:
+            for blk in deflated([header[a:a + BGZF_BLOCK_DATA] for a in range(0, len(header), BGZF_BLOCK_DATA)]):
+                f.write(blk)
+            parts = []
+            for a, b in _block_cuts(ends_chunks(int(n_rec.value))):
+                parts.append(stream(a, b))
+                if len(parts) >= 64 * n_jobs:
+                    for blk in deflated(parts):
+                        f.write(blk)
+                    parts = []
+            for blk in deflated(parts):
+                f.write(blk)
+            f.write(BGZF_EOF)
+        os.replace(tmp, dst)
+    finally:
+        if h:
+            lib.dn_bam_sort_destroy(h)
+        if pool is not None:
+            pool.shutdown()
+        if os.path.exists(tmp):
+            os.remove(tmp)
+    if stats is not None:
+        stats.update(t, frame_device_ms=float(ms[0].value), sort_device_ms=float(ms[1].value), gather_device_ms=float(ms[2].value),
+                     frame_fixups=int(fix.value), records=int(n_rec.value), bytes=int(n_bytes.value))
+    return dst

@@ -5,7 +5,7 @@ In-tree build of libdegnorm_amd.so (HIP kernels + C ABI) for gfx950 with hipcc.
 
 One translation unit per sample count p (dn_inst.hip -DDN_P=p), the run-time-p family (dn_generic.hip, compiled three
 times: 256- and 64-thread builds on float32 counts, a 256-thread build on float64 input), the coverage-assembly,
-reads-processing, BGZF-inflate, record-framing, BAM-index and GTF-scan units plus the C-ABI unit; objects are compiled
+reads-processing, BGZF-inflate, record-framing, BAM-index, BAM-sort and GTF-scan units plus the C-ABI unit; objects are compiled
 in parallel and linked into degnorm_amd/libdegnorm_amd.so.  hipcc cross-compiles without a GPU.
 """
 import os
@@ -139,6 +139,11 @@ def build_library(force=False, verbose=False):
     objs.append(o_bai)
     if force or _newer(o_bai, [bai] + host_hdr):
         jobs.append([hipcc] + FLAGS + ['-c', bai, '-o', o_bai])
+    srt = os.path.join(CSRC, 'dn_sort.hip')             # BAM records -> the coordinate-sorted record stream (bam.sort_bam)
+    o_srt = os.path.join(OBJ, 'dn_sort.o')
+    objs.append(o_srt)
+    if force or _newer(o_srt, [srt] + host_hdr):
+        jobs.append([hipcc] + FLAGS + ['-c', srt, '-o', o_srt])
     gtf = os.path.join(CSRC, 'dn_gtf.hip')              # GTF bytes -> exon table (GeneAnnotationLoader, loaders.py)
     o_gtf = os.path.join(OBJ, 'dn_gtf.o')
     objs.append(o_gtf)

@@ -337,8 +337,13 @@ template <class B> int frame_run(B &be, int32_t *last_pos, int64_t cap, dn::Fram
                                       " inside the index range of refID " + std::to_string(be.tid));
     }
     if (cap >= 0 && n_rec > cap) return dn::fail(DN_E_INVALID, "dn_bam_frame: more records than cap");
-    if (state == dn::kFrameBad)
+    if (state == dn::kFrameBad) {
+        R.n_rec = n_rec;
+        R.consumed = cur;
+        R.bad = true;
+        R.bad_bs = bad_bs;
         return dn::fail(DN_E_INVALID, "malformed BAM record at byte " + std::to_string(cur) + " of the window (block_size " + std::to_string(bad_bs) + ")");
+    }
     if (be.tid >= 0 && n_rec > 0) *last_pos = prev;
     R.n_rec = n_rec;
     R.consumed = cur;

@@ -40,6 +40,10 @@ struct FrameWork {
 struct FrameResult {
     int64_t n_rec = 0, consumed = 0, n_segments = 0, n_fixups = 0;
     float device_ms = 0.f;              // first framing kernel to the last, the host's stitch between them included
+    // when the walk stopped at a record whose block_size is below 32 (the call then fails): n_rec records lie before it, it
+    // starts at `consumed`, and bad_bs is its block_size
+    bool bad = false;
+    int32_t bad_bs = 0;
 };
 
 // Frame the n_bytes of the device window d_win on stream st: what dn_bam_frame does on the host, with the same results and

@@ -210,3 +210,17 @@ def create_index_file(bam_file, **kw):
     """
     from .bam import create_index
     return create_index(bam_file, bai_from_bam_file(bam_file), **kw)
+
+
+def sort_bam_file(bam_file, out_dir=None, **kw):
+    """
+    Sort a .bam file by coordinate, X.bam -> X_sorted.bam (the `samtools sort S1.bam -o S1_sorted.bam` of the reference's
+    documentation; here degnorm_amd.bam.sort_bam does it, on the GPU with device=k), next to the input or in out_dir.
+    Keywords are sort_bam's.  Returns the path of the sorted file.
+    """
+    import os
+    from .bam import sort_bam
+    if not bam_file.endswith('.bam'):
+        raise ValueError('{0} must have a .bam extension.'.format(bam_file))
+    name = os.path.basename(bam_file)[:-4] + '_sorted.bam'
+    return sort_bam(bam_file, os.path.join(os.path.dirname(bam_file) if out_dir is None else out_dir, name), **kw)

@@ -452,6 +452,45 @@ int  dn_bai_finish(dn_bai h, int64_t end_voffset, int64_t *sizes);
 int  dn_bai_fetch(dn_bai h, int32_t *ref_n_bin, int32_t *ref_n_intv, uint64_t *ref_pseudo, int32_t *bin_id, int32_t *bin_n_chunk,
                   uint64_t *chunks, uint64_t *ioffset);
 
+/* Coordinate sort of a BAM file (csrc/dn_sort.hip; degnorm_amd.bam.sort_bam) ----------------------------------------------
+ * The order: records ascend by key = ref_key << 32 | (uint32) (pos + 1), where ref_key is refID, or the largest 32-bit
+ * value for refID -1 -- unplaced records go last, and pos -1 sorts first within its reference -- and records of equal key
+ * keep the order they have in the input (a stable sort; flag, strand and read name play no part).  The whole inflated
+ * record stream of the file (what follows the BAM header; n_inflated bytes) is held twice: as read and sorted.
+ *   dn_bam_sort_device_memory   free and total bytes of `device` (hipMemGetInfo), for the caller's check before a sort.
+ *   dn_bam_sort_create    a sort of a file of n_ref references and n_inflated bytes of records on `device`, or (device < 0)
+ *                         the host build, which touches no device.  segment_bytes: of the framing (0: the default);
+ *                         piece_bytes: the stream is framed this many bytes at a time (0: 256 MiB; a piece grows when a
+ *                         record is longer than it).
+ *   dn_bam_sort_window    device sort: the next blocks of the file, described as for dn_bai_window, inflated to their place in
+ *                         the stream; head_skip bytes of the first block are left out (the first window starts where the BAM
+ *                         header ends).  When a block failed (status[b] != 0) the call returns DN_OK and the sort is spent.
+ *                         dn_bam_sort_expect_crc has the next window's blocks checked against the CRC32s of their trailers
+ *                         (DN_E_STATE on a host sort, whose caller holds the inflated bytes and checks them itself).
+ *   dn_bam_sort_window_host   host sort: the next n_data inflated bytes, without their first head_skip.
+ *   dn_bam_sort_finish    no more windows: frame the stream, compute key and length of every record and check it, sort
+ *                         (key, ordinal) stably, sum the lengths in sorted order and copy every record to its place.
+ *                         *n_records and *n_bytes: of the sorted stream; nullable: the framing's fix-ups, and the device ms
+ *                         of framing, of keys + sort + sum, and of the copy (0 on the host).
+ *   dn_bam_sort_ends      ends[k] = the byte of the sorted stream at which record first + k ends, for n records.
+ *   dn_bam_sort_read      n bytes of the sorted stream from byte off on, to dst (host memory).
+ * DN_E_INVALID with a text naming the record's ordinal in the input, the first such record winning: a block_size below 32,
+ * a record whose name and CIGAR do not fit in it, refID outside -1 .. n_ref - 1, pos below -1, a record cut by the end of
+ * the file.  Host and device sorts give the same texts and the same stream.  After an error a sort only accepts
+ * dn_bam_sort_destroy.  Errors: dn_last_error(). */
+typedef struct dn_bam_sort_s *dn_bam_sort;
+int  dn_bam_sort_device_memory(int device, int64_t *free_bytes, int64_t *total_bytes);
+int  dn_bam_sort_create(int device, int32_t n_ref, int64_t n_inflated, int64_t segment_bytes, int64_t piece_bytes, dn_bam_sort *out);
+void dn_bam_sort_destroy(dn_bam_sort h);
+int  dn_bam_sort_window(dn_bam_sort h, const uint8_t *comp, int64_t n_comp, int64_t n_blocks, const int64_t *pay_off, const int32_t *pay_len,
+                        const int32_t *isize, int32_t head_skip, int32_t *status, double *inflate_ms);
+int  dn_bam_sort_window_host(dn_bam_sort h, const uint8_t *data, int64_t n_data, int32_t head_skip);
+int  dn_bam_sort_expect_crc(dn_bam_sort h, const uint32_t *crc32, int64_t n_blocks);
+int  dn_bam_sort_finish(dn_bam_sort h, int64_t *n_records, int64_t *n_bytes, int64_t *n_fixups, double *frame_ms, double *sort_ms,
+                        double *gather_ms);
+int  dn_bam_sort_ends(dn_bam_sort h, int64_t first, int64_t n, int64_t *ends);
+int  dn_bam_sort_read(dn_bam_sort h, int64_t off, int64_t n, uint8_t *dst);
+
 /* GTF annotation scan (GeneAnnotationLoader, degnorm_amd/loaders.py) --------------------------------------------------
  * Replaces the reference's read_csv of the nine columns, its lower-case `apply` on the feature column and its regex
  * `apply` per exon row (loaders.py:128-152, _attribute_to_gene :102-112).  buf holds the n_bytes raw bytes of a GTF file,
