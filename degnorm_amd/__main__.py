@@ -65,6 +65,9 @@ def argparser():
                     help='sort every .bam file whose header does not say SO:coordinate by coordinate, on the GPU, to '
                          '<output directory>/sorted_bam/<same name>, index the sorted copy there and use it in place of the '
                          'input; the copies are kept (not with --bai-files)')
+    ap.add_argument('--native-deflate', action='store_true',
+                    help='with --sort-bam: deflate the blocks of the sorted copies on the GPU with the library\'s own encoder '
+                         'instead of with zlib on the host')
     ap.add_argument('--device-inflate', action='store_true',
                     help='inflate the BGZF blocks of the .bam files on the GPU instead of with zlib on the host')
     ap.add_argument('--device-frame', action='store_true',
@@ -116,6 +119,8 @@ def validate_args(args):
     args.sort_bam_files = []
     if sort and args.bai_files is not None:
         raise ValueError('Do not specify both --sort-bam and --bai-files: a sorted copy gets an index file of its own.')
+    if getattr(args, 'native_deflate', False) and not sort:
+        raise ValueError('Do not specify --native-deflate without --sort-bam: it chooses the encoder of the sorted copies.')
     if (not args.bam_files and not args.bam_dir) and (not args.warm_start_dir):
         raise ValueError('Must specify either --bam-files, --bam-dir, or --warm-start-dir as a data input option.')
     n_cpu = os.cpu_count() or 1
@@ -215,7 +220,8 @@ def _run(args, output_dir, device, verify):
             logging.info('sorting {0} by coordinate -- {1} / {2}'.format(bam_file, k + 1, len(args.sort_bam_files)))
             at = args.bam_files.index(bam_file)
             args.bam_files[at] = sort_bam(bam_file, os.path.join(sorted_dir, os.path.basename(bam_file)), device=device,
-                                          n_jobs=args.proc_per_node, verify=verify)
+                                          n_jobs=args.proc_per_node, verify=verify,
+                                          deflate='native' if getattr(args, 'native_deflate', False) else 'zlib')
             args.bai_files[at] = create_index(args.bam_files[at], bai_from_bam_file(args.bam_files[at]), device=device, verify=verify)
         run_pipeline(args.bam_files, args.bai_files, args.genome_annotation, output_dir, degnorm_iter=args.iter,
                      nmf_iter=args.nmf_iter, downsample_rate=args.downsample_rate, minimax_coverage=args.minimax_coverage,

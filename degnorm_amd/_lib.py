@@ -157,6 +157,12 @@ def load(build_if_missing=False):
     lib.dn_bam_sort_finish.argtypes = [vp, P(i64), P(i64), P(i64), P(dbl), P(dbl), P(dbl)]
     lib.dn_bam_sort_ends.argtypes = [vp, i64, i64, P(i64)]
     lib.dn_bam_sort_read.argtypes = [vp, i64, i64, P(u8)]
+    lib.dn_bam_sort_deflate.argtypes = [vp, i64, P(i64), P(i32), P(u8), i64, P(i64), P(dbl)]
+    lib.dn_bgzf_deflate_bound.argtypes = [i64, P(i32)]
+    lib.dn_bgzf_deflate_bound.restype = i64
+    lib.dn_bgzf_deflate_host.argtypes = [P(u8), i64, i64, P(i64), P(i32), P(u8), i64, P(i64)]
+    lib.dn_bgzf_deflate.argtypes = [c.c_int, P(u8), i64, i64, P(i64), P(i32), P(u8), i64, P(i64), P(dbl)]
+    lib.dn_deflate_code_lengths_host.argtypes = [P(u32), i32, i32, P(u8)]
     lib.dn_gtf_scan.argtypes = [c.c_int, P(c.c_uint8), i64, i64, P(i64), P(i64), P(i64), P(i64), P(i32), P(u64), P(i64), P(i64),
                                 P(i64), P(i32), P(u64), P(i64), P(i32), P(dbl), P(dbl)]
     lib.dn_gtf_last_error.restype = c.c_char_p

@@ -27,7 +27,9 @@ source); parse_bai / BamIndex.tobytes / write_bai read and write whole .bai file
 A file that is not sorted by coordinate -- an aligner's default output -- is sorted by sort_bam (csrc/dn_sort.hip): the whole
 inflated record stream is inflated into one device buffer, framed, keyed, radix-sorted (stably: ties keep file order) and
 copied record by record into a second buffer; the host cuts, deflates (zlib) and writes the blocks of the sorted file under a
-header that says SO:coordinate.  device=None does the same with zlib and the host build of the same source.
+header that says SO:coordinate.  device=None does the same with zlib and the host build of the same source.  With
+deflate='native' the blocks are written by the library's own DEFLATE encoder instead (csrc/dn_deflate.hip, bgzf_deflate): on the
+device the sorted stream is deflated where it lies, one block per wavefront, and only the blocks come back.
 
 Every path that inflates takes verify=True: the inflated bytes of each BGZF block are then compared with the CRC32 of its
 trailer -- zlib.crc32 where zlib inflates, the wavefront that inflates the block where the device does -- and a block that
@@ -1060,6 +1062,7 @@ BGZF_BLOCK_DATA = 0xff00         # inflated bytes a written block holds at most 
 DEVICE_MEMORY_SHARE = 0.8        # of the device's free memory a sort may plan with
 _SORT_TABLE_BYTES = 56           # per record: offset, two (key, ordinal) pairs, length and destination
 _ENDS_CHUNK = 1 << 20            # record ends fetched at a time
+_DEFLATE_REGION = 2 * 65536      # device bytes the encoder needs for one block (slot and compacted copy)
 
 
 def _header_data(path, verify=False):
@@ -1123,6 +1126,35 @@ def bgzf_compress(data, level=1):
             struct.pack('<II', zlib.crc32(data) & 0xffffffff, len(data)))
 
 
+def bgzf_deflate(parts, device=None):
+    """
+    One whole BGZF block per `bytes` of `parts` (each at most 0xff00 bytes, else ValueError), deflated by the library's own
+    DEFLATE encoder (csrc/dn_deflate.hip): on the host (device=None; no GPU needed) or on GPU `device`, one block per
+    wavefront.  Both write the same bytes.  The counterpart of inflate_blocks.
+    """
+    parts = [bytes(p) for p in parts]
+    n = len(parts)
+    for k, part in enumerate(parts):
+        if len(part) > BGZF_BLOCK_DATA:
+            raise ValueError('part {0} holds {1} bytes; a BGZF block holds at most {2}'.format(k, len(part), BGZF_BLOCK_DATA))
+    lens = np.array([len(part) for part in parts] + [0], np.int32)
+    beg = np.zeros(n + 1, np.int64)
+    np.cumsum(lens[:n], out=beg[1:])
+    joined = b''.join(parts)
+    data = np.frombuffer(joined, dtype=np.uint8) if joined else np.zeros(1, np.uint8)
+    lib = _lib.load()
+    i64, i32, u8 = ctypes.c_int64, ctypes.c_int32, ctypes.c_uint8
+    cap = int(lib.dn_bgzf_deflate_bound(n, _ptr(lens, i32)))
+    out, out_off = np.zeros(max(cap, 1), np.uint8), np.zeros(n + 1, np.int64)
+    args = (_ptr(data, u8), len(joined), n, _ptr(beg, i64), _ptr(lens, i32), _ptr(out, u8), cap, _ptr(out_off, i64))
+    if device is None:
+        _check(lib.dn_bgzf_deflate_host(*args), 'dn_bgzf_deflate_host')
+    else:
+        _check(lib.dn_bgzf_deflate(int(device), *(args + (None,))), 'dn_bgzf_deflate')
+    raw = out[:int(out_off[n])].tobytes()
+    return [raw[out_off[k]:out_off[k + 1]] for k in range(n)]
+
+
 def _block_cuts(end_chunks):
     """
     [begin, end) of the blocks of a record stream whose records end at the offsets `end_chunks` yields (ascending int64
@@ -1160,7 +1192,7 @@ def device_memory(device):
 
 
 def sort_bam(src, dst, device=None, n_jobs=1, level=1, window_bytes=256 << 20, segment_bytes=None, verify=False, overwrite=False,
-             max_device_bytes=None, stats=None):
+             max_device_bytes=None, stats=None, deflate='zlib'):
     """
     Write the BAM file `src` sorted by coordinate to `dst` (what `samtools sort` is run for before an index can be made);
     returns dst.  The order is defined in include/degnorm_amd.h: ascending (refID, pos), records without a reference last,
@@ -1182,8 +1214,18 @@ def sort_bam(src, dst, device=None, n_jobs=1, level=1, window_bytes=256 << 20, s
     must have the CRC32 of its trailer.  Errors are ValueErrors that name src and the block's offset or the record's
     ordinal, the same from both paths, and leave neither dst nor dst + '.tmp' behind; FileExistsError when dst exists and
     overwrite is off.  stats, a dict, receives `inflate_device_ms`, `frame_device_ms`, `frame_fixups`, `sort_device_ms` (key
-    pass, sort and scan), `gather_device_ms`, `records`, `bytes`, `windows` and `deflate_s`.
+    pass, sort and scan), `gather_device_ms`, `records`, `bytes`, `windows`, `deflate_s`, `deflate_device_ms` (the encoder's
+    kernels; 0 with zlib and on the host) and `out_bytes` (the bytes of the blocks that hold records: the file without its
+    header blocks and its end-of-file block).
+
+    deflate='native': the blocks are written by the library's own encoder (csrc/dn_deflate.hip, bgzf_deflate) in place of
+    zlib; `level` applies to 'zlib' only.  On a device the sorted stream is deflated where it lies, about window_bytes of
+    it at a time, and only the blocks come back; device=None runs the host build of the same source, and the header blocks
+    go through it in both cases, so device=k and device=None write the same file.  The file differs from the 'zlib' one
+    in its compressed bytes only: the blocks are cut at the same records.
     """
+    if deflate not in ('zlib', 'native'):
+        raise ValueError("deflate must be 'zlib' or 'native', not {0!r}".format(deflate))
     if os.path.exists(dst) and not overwrite:
         raise FileExistsError('{0} exists; pass overwrite=True to replace it'.format(dst))
     if not has_eof_block(src):
@@ -1197,7 +1239,7 @@ def sort_bam(src, dst, device=None, n_jobs=1, level=1, window_bytes=256 << 20, s
     pool = ThreadPoolExecutor(max_workers=n_jobs) if n_jobs > 1 else None
     h = ctypes.c_void_p()
     tmp = dst + '.tmp'
-    t = {'inflate_device_ms': 0.0, 'deflate_s': 0.0, 'windows': 0}
+    t = {'inflate_device_ms': 0.0, 'deflate_s': 0.0, 'windows': 0, 'deflate_device_ms': 0.0, 'out_bytes': 0}
 
     def call(rc, what):
         try:
@@ -1263,6 +1305,8 @@ def sort_bam(src, dst, device=None, n_jobs=1, level=1, window_bytes=256 << 20, s
                 n_comp_max, size, comp = max(n_comp_max, comp), 0, 0
         if device is not None:
             need = 2 * n_stream + n_comp_max + _SORT_TABLE_BYTES * (n_stream // 128 + 1)
+            if deflate == 'native' and n_stream + 64 < _DEFLATE_REGION:      # too small to lend the encoder its slots
+                need += _DEFLATE_REGION
             have = int(DEVICE_MEMORY_SHARE * device_memory(device)[0]) if max_device_bytes is None else int(max_device_bytes)
             if need > have:
                 raise ValueError('{0}: sorting needs about {1} bytes of device memory ({2} bytes of records), {3} are allowed; '
@@ -1290,18 +1334,48 @@ def sort_bam(src, dst, device=None, n_jobs=1, level=1, window_bytes=256 << 20, s
                 buf['lo'], buf['data'] = a, arr[:n].tobytes()
             return buf['data'][a - buf['lo']:b - buf['lo']]
 
+        def native(f, cuts):
+            """The blocks of the ranges `cuts` of the sorted stream, deflated where the stream lies, to f."""
+            t0 = time.perf_counter()
+            beg = np.array([a for a, _ in cuts] + [0], np.int64)
+            lens = np.array([b - a for a, b in cuts] + [0], np.int32)
+            cap = int(lib.dn_bgzf_deflate_bound(len(cuts), _ptr(lens, i32)))
+            out, out_off, dms = np.zeros(max(cap, 1), np.uint8), np.zeros(len(cuts) + 1, np.int64), ctypes.c_double(0.0)
+            call(lib.dn_bam_sort_deflate(h, len(cuts), _ptr(beg, i64), _ptr(lens, i32), _ptr(out, u8), cap, _ptr(out_off, i64),
+                                         ctypes.byref(dms)), 'dn_bam_sort_deflate')
+            t['deflate_device_ms'] += float(dms.value)
+            t['deflate_s'] += time.perf_counter() - t0
+            t['out_bytes'] += int(out_off[len(cuts)])
+            f.write(memoryview(out)[:int(out_off[len(cuts)])])
+
+        head_parts = [header[a:a + BGZF_BLOCK_DATA] for a in range(0, len(header), BGZF_BLOCK_DATA)]
         with open(tmp, 'wb') as f:
-            for blk in deflated([header[a:a + BGZF_BLOCK_DATA] for a in range(0, len(header), BGZF_BLOCK_DATA)]):
-                f.write(blk)
-            parts = []
-            for a, b in _block_cuts(ends_chunks(int(n_rec.value))):
-                parts.append(stream(a, b))
-                if len(parts) >= 64 * n_jobs:
-                    for blk in deflated(parts):
-                        f.write(blk)
-                    parts = []
-            for blk in deflated(parts):
-                f.write(blk)
+            if deflate == 'native':
+                for blk in bgzf_deflate(head_parts):
+                    f.write(blk)
+                cuts, size = [], 0
+                for a, b in _block_cuts(ends_chunks(int(n_rec.value))):
+                    cuts.append((a, b))
+                    size += b - a
+                    if size >= window_bytes:
+                        native(f, cuts)
+                        cuts, size = [], 0
+                if cuts:
+                    native(f, cuts)
+            else:
+                for blk in deflated(head_parts):
+                    f.write(blk)
+                parts = []
+                for a, b in _block_cuts(ends_chunks(int(n_rec.value))):
+                    parts.append(stream(a, b))
+                    if len(parts) >= 64 * n_jobs:
+                        for blk in deflated(parts):
+                            t['out_bytes'] += len(blk)
+                            f.write(blk)
+                        parts = []
+                for blk in deflated(parts):
+                    t['out_bytes'] += len(blk)
+                    f.write(blk)
             f.write(BGZF_EOF)
         os.replace(tmp, dst)
     finally:

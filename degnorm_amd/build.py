@@ -5,7 +5,7 @@ In-tree build of libdegnorm_amd.so (HIP kernels + C ABI) for gfx950 with hipcc.
 
 One translation unit per sample count p (dn_inst.hip -DDN_P=p), the run-time-p family (dn_generic.hip, compiled three
 times: 256- and 64-thread builds on float32 counts, a 256-thread build on float64 input), the coverage-assembly,
-reads-processing, BGZF-inflate, record-framing, BAM-index, BAM-sort and GTF-scan units plus the C-ABI unit; objects are compiled
+reads-processing, BGZF-inflate, BGZF-deflate, record-framing, BAM-index, BAM-sort and GTF-scan units plus the C-ABI unit; objects are compiled
 in parallel and linked into degnorm_amd/libdegnorm_amd.so.  hipcc cross-compiles without a GPU.
 """
 import os
@@ -89,7 +89,8 @@ def build_library(force=False, verbose=False):
     hipcc = _hipcc()
     hdr = [os.path.join(CSRC, 'dn_kernels.hpp'), os.path.join(CSRC, 'dn_reduce.hpp'), os.path.join(HERE, '..', 'include', 'degnorm_amd.h'),
            os.path.abspath(__file__)]
-    host_hdr = hdr + [os.path.join(CSRC, 'dn_host.hpp'), os.path.join(CSRC, 'dn_inflate.hpp'), os.path.join(CSRC, 'dn_frame.hpp')]     # the host-side units: api, reads, assemble
+    host_hdr = hdr + [os.path.join(CSRC, 'dn_host.hpp'), os.path.join(CSRC, 'dn_inflate.hpp'), os.path.join(CSRC, 'dn_frame.hpp'), os.path.join(CSRC, 'dn_crc.hpp'),
+                      os.path.join(CSRC, 'dn_deflate.hpp')]     # the host-side units: api, reads, assemble
     jobs = []
     objs = []
     inst = os.path.join(CSRC, 'dn_inst.hip')
@@ -129,6 +130,11 @@ def build_library(force=False, verbose=False):
     objs.append(o_inf)
     if force or _newer(o_inf, [inf] + host_hdr):
         jobs.append([hipcc] + FLAGS + ['-c', inf, '-o', o_inf])
+    dfl = os.path.join(CSRC, 'dn_deflate.hip')          # byte ranges -> BGZF blocks (bam.bgzf_deflate, bam.sort_bam deflate='native')
+    o_dfl = os.path.join(OBJ, 'dn_deflate.o')
+    objs.append(o_dfl)
+    if force or _newer(o_dfl, [dfl] + host_hdr):
+        jobs.append([hipcc] + FLAGS + ['-c', dfl, '-o', o_dfl])
     frm = os.path.join(CSRC, 'dn_frame.hip')            # inflated BAM bytes -> record offsets (NativeBamReadsProcessor frame='device', bam.py)
     o_frm = os.path.join(OBJ, 'dn_frame.o')
     objs.append(o_frm)

@@ -12,6 +12,8 @@
 //             written in 16-byte pieces aligned to the destination; the 16 source bytes of a piece come from two aligned
 //             16-byte loads and a funnel shift by the record's source misalignment.  The at most 15 bytes before the first
 //             and behind the last aligned piece share their 16 bytes with the neighbouring records and are copied byte by byte
+//   deflate   (dn_bam_sort_deflate, for a caller that writes the file with the library's encoder) ranges of the sorted stream
+//             become BGZF blocks where the stream lies (dn::deflate_device); the unsorted copy, dead by then, lends the slots
 //
 // The order: ascending key = ref_key << 32 | (uint32) (pos + 1), ref_key = refID, or the largest value for refID -1, so
 // unplaced records go last and pos -1 sorts first within a reference; records of equal key keep their order in the input.
@@ -33,6 +35,7 @@
 #include "dn_host.hpp"
 #include "dn_inflate.hpp"
 #include "dn_frame.hpp"
+#include "dn_deflate.hpp"
 
 #define DN_HD __host__ __device__ __forceinline__
 
@@ -224,6 +227,10 @@ struct dn_bam_sort_s {
     dn::FrameWork frame;
     dn::Scratch scratch;
     dn::Event ev0, ev1, ev2, ev3;
+    // dn_bam_sort_deflate on the device: its tables, and its own region where the dead input copy is too small for one block
+    dn::DeflateTables deflate;
+    dn::DeviceBuffer<uint8_t> deflate_region;
+    bool deflating = false;
 };
 
 namespace {
@@ -691,4 +698,39 @@ extern "C" int dn_bam_sort_read(dn_bam_sort h, int64_t off, int64_t n, uint8_t *
         DN_TRY(hipStreamSynchronize(h->st));
         return DN_OK;
     });
+}
+
+extern "C" int dn_bam_sort_deflate(dn_bam_sort h, int64_t n_blocks, const int64_t *beg, const int32_t *len, uint8_t *out, int64_t out_cap,
+                                   int64_t *out_off, double *deflate_ms)
+{
+    dn::clear_error();
+    if (!h) return dn::fail(DN_E_INVALID, "dn_bam_sort_deflate: bad argument");
+    if (!h->finished || h->failed) return dn::fail(DN_E_STATE, "dn_bam_sort_deflate: the sort is not finished or has failed");
+    const int rc = dn::deflate_validate("dn_bam_sort_deflate", h->n_bytes, n_blocks, beg, len, out, out_cap, out_off);
+    if (rc != DN_OK) return rc;
+    if (deflate_ms) *deflate_ms = 0.0;
+    if (h->device < 0) return dn::deflate_host(h->h_out.data(), h->n_bytes, n_blocks, beg, len, out, out_off);
+    DN_TRY(hipSetDevice(h->device));
+    const int rc2 = dn::synced(h->st, [&]() -> int {
+        if (!h->deflating) {
+            // what only the sort needed goes: the deflate tables are smaller, so the device need stays below the sort's
+            DN_TRY(hipStreamSynchronize(h->st));
+            h->comp = dn::GrowBuffer<uint8_t>(); h->blk = dn::GrowBuffer<dn::InflateBlock>(); h->blk_status = dn::GrowBuffer<int32_t>();
+            h->piece_off = dn::GrowBuffer<int64_t>(); h->off = dn::GrowBuffer<int64_t>();
+            h->key = dn::GrowBuffer<uint64_t>(); h->key2 = dn::GrowBuffer<uint64_t>();
+            h->ord = dn::GrowBuffer<uint32_t>(); h->ord2 = dn::GrowBuffer<uint32_t>(); h->len = dn::GrowBuffer<uint32_t>();
+            h->deflating = true;
+        }
+        // the unsorted copy of the stream is dead since the gather: it holds the slots and the compacted blocks
+        uint8_t *region = h->in.get();
+        int64_t region_bytes = (h->n_bytes + kSlack) & ~(int64_t) 15;
+        if (region_bytes < dn::kDeflateRegionPerBlock) {
+            region_bytes = dn::kDeflateRegionPerBlock;
+            if (!h->deflate_region) DN_TRY(h->deflate_region.alloc((size_t) region_bytes));
+            region = h->deflate_region.get();
+        }
+        return dn::deflate_device(h->st, h->out.get(), n_blocks, beg, len, region, region_bytes, h->deflate, out, out_off, deflate_ms);
+    });
+    if (rc2 != DN_OK) h->failed = true;
+    return rc2;
 }

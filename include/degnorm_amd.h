@@ -491,6 +491,41 @@ int  dn_bam_sort_finish(dn_bam_sort h, int64_t *n_records, int64_t *n_bytes, int
 int  dn_bam_sort_ends(dn_bam_sort h, int64_t first, int64_t n, int64_t *ends);
 int  dn_bam_sort_read(dn_bam_sort h, int64_t off, int64_t n, uint8_t *dst);
 
+/* BGZF deflate (csrc/dn_deflate.hip; degnorm_amd.bam.bgzf_deflate, sort_bam(deflate='native')) -----------------------------
+ * The library's own DEFLATE encoder, the counterpart of dn_bgzf_inflate: byte ranges of at most 0xff00 bytes become whole
+ * BGZF blocks -- the 18-byte header with BSIZE, a raw-DEFLATE payload (RFC 1951), CRC32 and ISIZE.  One source, written
+ * against a memory policy: the host build runs lane after lane, the device build one 64-lane workgroup per block, and both
+ * write the same bytes for every input ("BGZF deflate", defines the parse).  Every byte string is a valid input,
+ * so there is no per-block status.  Block b holds data[beg[b] .. beg[b] + len[b]); the blocks are written back to back into
+ * out, block b at out_off[b], and out_off[n_blocks] is their size.  No DEFLATE block is larger than its stored form, so a
+ * block of len bytes is at most len + 26 + 6 * max(1, ceil(len / 8192)) bytes, below 65536:
+ *   dn_bgzf_deflate_bound       the sum of that bound over len[0 .. n_blocks): the out_cap that always suffices; -1 when a
+ *                         length is outside 0 .. 0xff00.
+ *   dn_bgzf_deflate_host  the host build; no device is touched.
+ *   dn_bgzf_deflate       copy data to `device`, deflate there (one wave per block into a 64 KiB slot of its own, at most
+ *                         1024 blocks in flight; the slots are compacted on the device) and copy only the blocks back.
+ *                         device_ms (nullable): the kernels, by HIP events.
+ *   dn_deflate_code_lengths_host   the code-length builder the encoder uses, for tests: lens[0 .. n) of a prefix code for
+ *                         the symbols with freq != 0, no length above `limit` (n is 1 .. 288, limit 1 .. 15, 2^limit at
+ *                         least n).  Huffman's lengths where they fit the limit; always a complete code (Kraft sum 1) when
+ *                         two or more symbols are used; one used symbol gets length 1; unused symbols get 0.
+ *   dn_bam_sort_deflate   ranges of the sorted stream of a finished sort (dn_bam_sort_finish returned DN_OK; DN_E_STATE
+ *                         otherwise, and for a sort that has failed) as BGZF blocks.  A device sort deflates the stream
+ *                         where it lies; the unsorted copy, dead since the sort finished, lends the slots and the room for
+ *                         the compacted blocks (a stream too small for one slot gets 128 KiB of its own), and the sort's
+ *                         key and offset tables are released at the first call, so the device need stays below the
+ *                         sort's.  A host sort (device < 0) runs the host build.  deflate_ms (nullable): the kernels.
+ * DN_E_INVALID before any launch: a length outside 0 .. 0xff00, a range outside data (or the stream), an out_cap below
+ * dn_bgzf_deflate_bound.  Errors: dn_last_error(). */
+int64_t dn_bgzf_deflate_bound(int64_t n_blocks, const int32_t *len);
+int  dn_bgzf_deflate_host(const uint8_t *data, int64_t n_data, int64_t n_blocks, const int64_t *beg, const int32_t *len, uint8_t *out,
+                          int64_t out_cap, int64_t *out_off);
+int  dn_bgzf_deflate(int device, const uint8_t *data, int64_t n_data, int64_t n_blocks, const int64_t *beg, const int32_t *len,
+                     uint8_t *out, int64_t out_cap, int64_t *out_off, double *device_ms);
+int  dn_deflate_code_lengths_host(const uint32_t *freq, int32_t n, int32_t limit, uint8_t *lens);
+int  dn_bam_sort_deflate(dn_bam_sort h, int64_t n_blocks, const int64_t *beg, const int32_t *len, uint8_t *out, int64_t out_cap,
+                         int64_t *out_off, double *deflate_ms);
+
 /* GTF annotation scan (GeneAnnotationLoader, degnorm_amd/loaders.py) --------------------------------------------------
  * Replaces the reference's read_csv of the nine columns, its lower-case `apply` on the feature column and its regex
  * `apply` per exon row (loaders.py:128-152, _attribute_to_gene :102-112).  buf holds the n_bytes raw bytes of a GTF file,

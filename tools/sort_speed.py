@@ -7,12 +7,19 @@ with its records permuted by a seed and its header saying SO:unsorted:
              reports: inflate_device_ms, frame_device_ms, sort_device_ms, gather_device_ms (by events), deflate_s
   host       sort_bam(device=None, n_jobs=--jobs): zlib inflate in the same pool and the host build of the same source
 
+--deflate native has the blocks written by the library's own encoder (csrc/dn_deflate.hip) in place of zlib: on the device the
+sorted stream is deflated where it lies and only the blocks are fetched.  Every line then also holds deflate_device_ms (the
+encoder's kernels, by events), out_bytes (the blocks that hold records), out_file_bytes (the size of the written file) and,
+for the device, fetched_bytes: what came back from the device after the sort -- the record ends and the sorted stream ('zlib')
+or the blocks ('native').
+
 The two modes run alternated in one process, --reps times each after one warm-up each; every figure is reported as [minimum,
 maximum] over the repetitions.  `same` says whether the two wrote the same bytes.  The device line also holds the yardstick
 of the gather kernel: a device-to-device hipMemcpyAsync of the same byte count, timed by events in this
 process, both as bytes read + bytes written per second.
 
-    python tools/sort_speed.py [--reads 2000000] [--jobs 16] [--reps 5] [--level 1] [--seed 0] [--modes device,host] [--dir DIR]
+    python tools/sort_speed.py [--reads 2000000] [--jobs 16] [--reps 5] [--level 1] [--seed 0] [--modes device,host] [--deflate zlib]
+                                [--dir DIR]
 
 Prints one JSON line per mode.  Needs a GPU unless --modes host.
 """
@@ -114,6 +121,7 @@ def main():
     ap.add_argument('--level', type=int, default=1)
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--modes', default='device,host')
+    ap.add_argument('--deflate', choices=('zlib', 'native'), default='zlib')
     ap.add_argument('--dir', default=None)
     a = ap.parse_args()
     modes = [m for m in ('device', 'host') if m in a.modes.split(',')]
@@ -131,7 +139,8 @@ def main():
             for m in modes:
                 stats = {}
                 t0 = time.perf_counter()
-                bam.sort_bam(path, path + '.' + m, overwrite=True, device=0 if m == 'device' else None, n_jobs=a.jobs, level=a.level, stats=stats)
+                bam.sort_bam(path, path + '.' + m, overwrite=True, device=0 if m == 'device' else None, n_jobs=a.jobs, level=a.level, stats=stats,
+                             deflate=a.deflate)
                 stats['e2e_ms'] = 1e3 * (time.perf_counter() - t0)
                 if k > 0:
                     rows[m].append(stats)
@@ -143,11 +152,14 @@ def main():
             out = {'tool': 'sort_speed', 'mode': m, 'reads': a.reads, 'jobs': a.jobs, 'reps': a.reps, 'level': a.level, 'seed': a.seed,
                    'bam_mb': round(os.path.getsize(path) / 2 ** 20, 1), 'inflated_mb': round(n_stream / 2 ** 20, 1),
                    'sorted_order': bam.sort_order(path + '.' + m), 'e2e_ms': _span([r['e2e_ms'] for r in rows[m]]),
-                   'deflate_s': _span([r['deflate_s'] for r in rows[m]], 3)}
+                   'deflate_s': _span([r['deflate_s'] for r in rows[m]], 3), 'deflate': a.deflate,
+                   'deflate_device_ms': _span([r['deflate_device_ms'] for r in rows[m]], 3), 'out_bytes': rows[m][-1]['out_bytes'],
+                   'out_file_bytes': os.path.getsize(path + '.' + m)}
             out.update({key: rows[m][-1][key] for key in ('records', 'bytes', 'windows', 'frame_fixups')})
             if same is not None:
                 out['same'] = same
             if m == 'device':
+                out['fetched_bytes'] = 8 * rows[m][-1]['records'] + rows[m][-1]['bytes' if a.deflate == 'zlib' else 'out_bytes']
                 out.update({key: _span([r[key] for r in rows[m]], 3) for key in SPLIT})
                 n = rows[m][-1]['bytes']
                 copy = d2d_copy_ms(n, a.reps)
