@@ -36,6 +36,7 @@ trailer -- zlib.crc32 where zlib inflates, the wavefront that inflates the block
 differs is a ValueError naming the file and the block's offset.  verify_bgzf checks a whole file that way (bgzip -t).
 """
 import ctypes
+import itertools
 import os
 import struct
 import time
@@ -211,6 +212,67 @@ def _raise_status(status, where):
         raise ValueError('{0} does not inflate: {1}'.format(where(k), INFLATE_ERRORS.get(int(status[k]), 'error {0}'.format(int(status[k])))))
 
 
+def _raise_block_status(path, batch, status):
+    """ValueError naming the file and the offset of the first of the (offset, block) pairs of batch whose status is not 0."""
+    _raise_status(status[:len(batch)], lambda k: '{0}: the BGZF block at byte {1}'.format(path, batch[k][0]))
+
+
+def _batched(blocks, window_bytes, size=0):
+    """
+    Lists of the (file offset, block) pairs that `blocks` yields: a list ends with the block that brings its inflated data to
+    window_bytes.  size: what the first list counts before its first block (negative: bytes of that block that are not its).
+    A loop over whole files drops its list (`del batch`) when it is done with it: otherwise the blocks of one window stay
+    allocated while the next window's are read, which costs more than the marshalling of a window does.
+    """
+    batch = []
+    for off, blk in blocks:
+        batch.append((off, blk))
+        size += struct.unpack_from('<I', blk, len(blk) - 4)[0]
+        if size >= window_bytes:
+            yield batch
+            batch, size = [], 0
+    if batch:
+        yield batch
+
+
+def _block_args(blocks):
+    """
+    What every inflate entry point of the library takes for whole BGZF blocks: the ctypes arguments (comp, n_comp, n_blocks,
+    pay_off, pay_len), the blocks' ISIZEs as they are in the file (int64) and the status array the call fills.
+    """
+    comp, n_comp, pay_off, pay_len, isize = _block_layout(blocks)
+    args = (_ptr(comp, ctypes.c_uint8), n_comp, len(blocks), _ptr(pay_off, ctypes.c_int64), _ptr(pay_len, ctypes.c_int32))
+    return args, isize, np.zeros(max(len(blocks), 1), np.int32)
+
+
+def _window_args(blocks, verify=False, expect_crc=None):
+    """
+    What the window entry points take: _block_args' arguments with the ISIZEs as their sixth, and the status array.  verify:
+    the CRC32s of the blocks' trailers are announced first, through expect_crc (which takes the uint32 array).
+    """
+    args, isize, status = _block_args(blocks)
+    if verify:
+        expect_crc(block_crcs(blocks)[:len(blocks)])
+    isize32 = np.where(isize > 2 ** 31 - 1, -1, isize).astype(np.int32)      # the library refuses a negative size
+    return args + (_ptr(isize32, ctypes.c_int32),), status
+
+
+def _zlib_inflate(path, batch, pool, verify=False):
+    """
+    The data of the blocks of batch, in file order, by zlib (in pool, when there is one).  verify: the first block whose data
+    does not have the CRC32 of its trailer is a BgzfCrcError (a ValueError) naming the file and its offset.
+    """
+    blocks = [b for _, b in batch]
+    one = _inflate_verified if verify else inflate_block
+    data = []
+    try:
+        for d in (pool.map(one, blocks) if pool is not None else map(one, blocks)):      # in file order: the first bad block raises
+            data.append(d)
+    except BgzfCrcError:                                 # the blocks before it were good: this is the one, whatever its ISIZE
+        raise BgzfCrcError(_block_error(path, batch[len(data)][0], INFLATE_E_CRC))
+    return data
+
+
 # --- header and index ----------------------------------------------------------------------------------------------------
 
 def parse_header(data):
@@ -375,18 +437,12 @@ class DeviceRows(object):
         the library's host copy of it (valid until the next call), the status of every block and the kernel's ms.
         verify: every block, all of it, must have the CRC32 of its trailer (status 8 otherwise).
         """
-        comp, n_comp, pay_off, pay_len, isize = _block_layout(blocks)
-        if verify:
-            self.expect_crc(block_crcs(blocks)[:len(blocks)])
-        isize32 = np.where(isize > 2 ** 31 - 1, -1, isize).astype(np.int32)      # the library refuses a negative size
-        status = np.zeros(max(len(blocks), 1), np.int32)
+        args, status = _window_args(blocks, verify, self.expect_crc)
         c = np.frombuffer(carry, dtype=np.uint8) if len(carry) else np.zeros(1, np.uint8)
         view, n_bytes, ms = ctypes.POINTER(ctypes.c_uint8)(), ctypes.c_int64(0), ctypes.c_double(0.0)
-        i64, i32, u8 = ctypes.c_int64, ctypes.c_int32, ctypes.c_uint8
-        _check(self.lib.dn_bam_rows_inflate(self.h, _ptr(c, u8), len(carry), _ptr(comp, u8), n_comp, len(blocks), _ptr(pay_off, i64),
-                                            _ptr(pay_len, i32), _ptr(isize32, i32), int(head_skip), int(tail_keep),
-                                            ctypes.byref(view), ctypes.byref(n_bytes), _ptr(status, i32), ctypes.byref(ms)),
-               'dn_bam_rows_inflate')
+        args = (_ptr(c, ctypes.c_uint8), len(carry)) + args + (int(head_skip), int(tail_keep), ctypes.byref(view), ctypes.byref(n_bytes),
+                                                               _ptr(status, ctypes.c_int32), ctypes.byref(ms))
+        _check(self.lib.dn_bam_rows_inflate(self.h, *args), 'dn_bam_rows_inflate')
         data = np.ctypeslib.as_array(view, shape=(n_bytes.value,)) if n_bytes.value else np.zeros(0, np.uint8)
         return data, status[:len(blocks)], float(ms.value)
 
@@ -407,17 +463,11 @@ class DeviceRows(object):
         cuts stays there.  Returns the status of every block, the bytes carried over, and the ms of inflate and framing.
         verify: as for inflate.
         """
-        comp, n_comp, pay_off, pay_len, isize = _block_layout(blocks)
-        if verify:
-            self.expect_crc(block_crcs(blocks)[:len(blocks)])
-        isize32 = np.where(isize > 2 ** 31 - 1, -1, isize).astype(np.int32)      # the library refuses a negative size
-        status = np.zeros(max(len(blocks), 1), np.int32)
+        args, status = _window_args(blocks, verify, self.expect_crc)
         n_bytes, n_carry, ms, fms = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_double(0.0), ctypes.c_double(0.0)
-        i64, i32, u8 = ctypes.c_int64, ctypes.c_int32, ctypes.c_uint8
-        rc = self.lib.dn_bam_rows_inflate_framed(self.h, _ptr(comp, u8), n_comp, len(blocks), _ptr(pay_off, i64), _ptr(pay_len, i32),
-                                                 _ptr(isize32, i32), int(head_skip), int(tail_keep), _ptr(status, i32),
-                                                 ctypes.byref(n_bytes), ctypes.byref(n_carry), ctypes.byref(ms), ctypes.byref(fms))
-        _check(rc, 'dn_bam_rows_inflate_framed')
+        args += (int(head_skip), int(tail_keep), _ptr(status, ctypes.c_int32), ctypes.byref(n_bytes), ctypes.byref(n_carry), ctypes.byref(ms),
+                 ctypes.byref(fms))
+        _check(self.lib.dn_bam_rows_inflate_framed(self.h, *args), 'dn_bam_rows_inflate_framed')
         return status[:len(blocks)], int(n_carry.value), float(ms.value), float(fms.value)
 
     def frame_info(self):
@@ -564,16 +614,8 @@ class NativeBamReadsProcessor(BamReadsProcessor):
         window_bytes = window_bytes or self.window_bytes
         vbeg, vend = rng
         cbeg, ubeg, cend, uend = vbeg >> 16, vbeg & 0xffff, vend >> 16, vend & 0xffff
-        batch, size = [], 0
-        for off, blk in iter_blocks(self.filename, cbeg):
-            if off > cend or (off == cend and uend == 0):
-                break
-            batch.append((off, blk))
-            size += struct.unpack_from('<I', blk, len(blk) - 4)[0]
-            if size >= window_bytes:
-                yield batch, cbeg, ubeg, cend, uend
-                batch, size = [], 0
-        if batch:
+        in_range = itertools.takewhile(lambda ob: ob[0] < cend or (ob[0] == cend and uend > 0), iter_blocks(self.filename, cbeg))
+        for batch in _batched(in_range, window_bytes):
             yield batch, cbeg, ubeg, cend, uend
 
     def windows(self, chrom, window_bytes=None):
@@ -591,14 +633,7 @@ class NativeBamReadsProcessor(BamReadsProcessor):
 
     def _inflate(self, batch, pool, cbeg, ubeg, cend, uend):
         t0 = time.perf_counter()
-        blocks = [b for _, b in batch]
-        one = _inflate_verified if self.verify else inflate_block
-        data = []
-        try:
-            for d in (pool.map(one, blocks) if pool is not None else map(one, blocks)):      # in file order: the first bad block raises
-                data.append(d)
-        except BgzfCrcError:
-            raise ValueError(_block_error(self.filename, batch[len(data)][0], INFLATE_E_CRC))
+        data = _zlib_inflate(self.filename, batch, pool, self.verify)
         for k, (off, _) in enumerate(batch):
             if off == cend:
                 data[k] = data[k][:uend]
@@ -659,7 +694,7 @@ class NativeBamReadsProcessor(BamReadsProcessor):
             data, status, ms = rows.inflate(carry, [b for _, b in batch], ubeg if batch[0][0] == cbeg else 0,
                                             uend if batch[-1][0] == cend else -1, self.verify)
             t1 = time.perf_counter()
-            _raise_status(status, lambda k: '{0}: the BGZF block at byte {1}'.format(self.filename, batch[k][0]))
+            _raise_block_status(self.filename, batch, status)
             off, used, last = frame_records(data, self._tid[chrom], last)
             t2 = time.perf_counter()
             rows.append_resident(off)
@@ -687,7 +722,7 @@ class NativeBamReadsProcessor(BamReadsProcessor):
                     status, n_carry, ms, fms = rows.inflate_framed([b for _, b in batch], ubeg if batch[0][0] == cbeg else 0,
                                                                    uend if batch[-1][0] == cend else -1, self.verify)
                     t1 = time.perf_counter()
-                    _raise_status(status, lambda k: '{0}: the BGZF block at byte {1}'.format(self.filename, batch[k][0]))
+                    _raise_block_status(self.filename, batch, status)
                     t['inflate_device_ms'] = t.get('inflate_device_ms', 0.0) + ms
                     calls += t1 - t0
                 if n_carry:
@@ -823,27 +858,22 @@ def _host_inflate(bam_file, batch, pool, verify=False):
     The data of the blocks of batch by zlib (verify: and their CRC32s by zlib.crc32, in the same pool); a block that fails
     is named with the text of the library's own decoder.
     """
-    blocks = [b for _, b in batch]
-    one = _inflate_verified if verify else inflate_block
-    data = []
     try:
-        for d in (pool.map(one, blocks) if pool is not None else map(one, blocks)):      # in file order: the first bad block raises
-            data.append(d)
-        return data
-    except BgzfCrcError:                                 # the blocks before it were good: this is the one, whatever its ISIZE
-        raise ValueError(_block_error(bam_file, batch[len(data)][0], INFLATE_E_CRC))
+        return _zlib_inflate(bam_file, batch, pool, verify)
+    except BgzfCrcError:                                 # a wrong CRC32: _zlib_inflate has named the block
+        raise
     except (zlib.error, ValueError, struct.error) as e:
-        comp, n_comp, pay_off, pay_len, isize = _block_layout(blocks)
+        blocks = [b for _, b in batch]
+        args, isize, status = _block_args(blocks)
         n = len(blocks)
         out_off = np.zeros(n + 1, np.int64)
         np.cumsum(np.clip(isize[:n], 0, 65536), out=out_off[1:])
-        out, status = np.zeros(int(out_off[-1]) + 1, np.uint8), np.zeros(max(n, 1), np.int32)
-        i64, i32, u8 = ctypes.c_int64, ctypes.c_int32, ctypes.c_uint8
+        out = np.zeros(int(out_off[-1]) + 1, np.uint8)
         if n and int(isize[:n].max()) <= 65536:
             crc = _ptr(block_crcs(blocks), ctypes.c_uint32) if verify else None
-            _check(_lib.load().dn_bgzf_inflate_check_host(_ptr(comp, u8), n_comp, n, _ptr(pay_off, i64), _ptr(pay_len, i32), _ptr(out_off, i64),
-                                                          _ptr(out, u8), _ptr(status, i32), crc), 'dn_bgzf_inflate_check_host')
-            _raise_status(status[:n], lambda k: '{0}: the BGZF block at byte {1}'.format(bam_file, batch[k][0]))
+            args += (_ptr(out_off, ctypes.c_int64), _ptr(out, ctypes.c_uint8), _ptr(status, ctypes.c_int32), crc)
+            _check(_lib.load().dn_bgzf_inflate_check_host(*args), 'dn_bgzf_inflate_check_host')
+            _raise_block_status(bam_file, batch, status)
         raise ValueError('{0}: a BGZF block at or after byte {1} does not inflate: {2}'.format(bam_file, batch[0][0], e))
 
 
@@ -894,44 +924,25 @@ def build_index(bam_file, device=None, n_jobs=1, window_bytes=256 << 20, segment
             call(lib.dn_bai_window_host(h, _ptr(joined, u8), int(isize.sum()), len(batch), _ptr(isize32, i32), _ptr(coffset, i64),
                                         int(head_skip), ctypes.byref(n_rec)), 'dn_bai_window_host')
             return
-        comp, n_comp, pay_off, pay_len, isize = _block_layout([b for _, b in batch])
-        isize32 = np.where(isize > 2 ** 31 - 1, -1, isize).astype(np.int32)      # the library refuses a negative size
-        status = np.zeros(max(len(batch), 1), np.int32)
+        args, status = _window_args([b for _, b in batch], verify, lambda crc: call(
+            lib.dn_bai_expect_crc(h, _ptr(crc, ctypes.c_uint32), len(crc)), 'dn_bai_expect_crc'))
         t = [ctypes.c_double(0.0) for _ in range(3)]
-        if verify:
-            call(lib.dn_bai_expect_crc(h, _ptr(block_crcs([b for _, b in batch]), ctypes.c_uint32), len(batch)), 'dn_bai_expect_crc')
-        call(lib.dn_bai_window(h, _ptr(comp, u8), n_comp, len(batch), _ptr(pay_off, i64), _ptr(pay_len, i32), _ptr(isize32, i32),
-                               _ptr(coffset, i64), int(head_skip), _ptr(status, i32), ctypes.byref(n_rec), ctypes.byref(t[0]),
-                               ctypes.byref(t[1]), ctypes.byref(t[2])), 'dn_bai_window')
+        args += (_ptr(coffset, i64), int(head_skip), _ptr(status, i32), ctypes.byref(n_rec), ctypes.byref(t[0]), ctypes.byref(t[1]),
+                 ctypes.byref(t[2]))
+        call(lib.dn_bai_window(h, *args), 'dn_bai_window')
         for key, v in zip(('inflate_device_ms', 'frame_device_ms', 'index_device_ms'), t):
             ms[key] += float(v.value)
-        _raise_status(status[:len(batch)], lambda k: '{0}: the BGZF block at byte {1}'.format(bam_file, batch[k][0]))
+        _raise_block_status(bam_file, batch, status)
 
     try:
-        it = blocks()
-        data, got, first = bytearray(), None, None
-        for off, blk in it:                          # the header, on zlib whatever the device: it may span several blocks
-            start = len(data)
-            data += _host_inflate(bam_file, [(off, blk)], None, verify)[0]
-            got = parse_header(data)
-            if got is not None:
-                first = (off, blk)
-                break
-        if got is None:
-            raise ValueError('{0}: BAM header cut short'.format(bam_file))
-        header_end, refs = got
+        # the header, on zlib whatever the device: it may span several blocks
+        _, head_blocks, _, head_skip, refs = _header_data(bam_file, verify)
         call(lib.dn_bai_create(-1 if device is None else int(device), len(refs), int(segment_bytes or 0), ctypes.byref(h)), 'dn_bai_create')
-        # the first window starts inside the block in which the header ends
-        batch, size, head_skip = [first], len(data) - header_end, header_end - start
-        del data
-        for off, blk in it:
-            if size >= window_bytes:
-                window(batch, head_skip)
-                batch, size, head_skip = [], 0, 0
-            batch.append((off, blk))
-            size += struct.unpack_from('<I', blk, len(blk) - 4)[0]
-        if batch:
+        # the first window starts inside the block in which the header ends, and holds the bytes behind the header
+        for batch in _batched(itertools.islice(blocks(), head_blocks - 1, None), window_bytes, -head_skip):
             window(batch, head_skip)
+            head_skip = 0
+            del batch
         if end['coffset'] is None or end['open']:
             raise ValueError('{0}: no BGZF end-of-file block; the file is truncated'.format(bam_file))
         sizes = np.zeros(8, dtype=np.int64)
@@ -987,41 +998,33 @@ def verify_bgzf(path, device=None, n_jobs=1, window_bytes=256 << 20):
     window_bytes = max(int(256 << 20 if window_bytes is None else window_bytes), 1)
     out = {'blocks': 0, 'compressed_bytes': 0, 'inflated_bytes': 0, 'device_ms': 0.0}
     pool = ThreadPoolExecutor(max_workers=int(n_jobs)) if device is None and int(n_jobs) > 1 else None
-    i64, i32, u8 = ctypes.c_int64, ctypes.c_int32, ctypes.c_uint8
+    i64, i32 = ctypes.c_int64, ctypes.c_int32
 
     def window(batch):
         blocks = [b for _, b in batch]
         if device is None:
             _host_inflate(path, batch, pool, True)
             return
-        comp, n_comp, pay_off, pay_len, isize = _block_layout(blocks)
+        args, isize, status = _block_args(blocks)
         n = len(blocks)
         if int(isize[:n].max()) > 65536:
             k = int(isize[:n].argmax())
             raise ValueError('{0}: the BGZF block at byte {1} claims an inflated size of {2} bytes'.format(path, batch[k][0], int(isize[k])))
         out_off = np.zeros(n + 1, np.int64)
         np.cumsum(isize[:n], out=out_off[1:])
-        status, ms = np.zeros(n, np.int32), ctypes.c_double(0.0)
-        _check(_lib.load().dn_bgzf_inflate_check(int(device), _ptr(comp, u8), n_comp, n, _ptr(pay_off, i64), _ptr(pay_len, i32),
-                                                 _ptr(out_off, i64), None, _ptr(status, i32), None, ctypes.byref(ms),
-                                                 _ptr(block_crcs(blocks), ctypes.c_uint32)), 'dn_bgzf_inflate_check')
+        ms = ctypes.c_double(0.0)
+        args += (_ptr(out_off, i64), None, _ptr(status, i32), None, ctypes.byref(ms), _ptr(block_crcs(blocks), ctypes.c_uint32))
+        _check(_lib.load().dn_bgzf_inflate_check(int(device), *args), 'dn_bgzf_inflate_check')
         out['device_ms'] += float(ms.value)
-        _raise_status(status, lambda k: '{0}: the BGZF block at byte {1}'.format(path, batch[k][0]))
+        _raise_block_status(path, batch, status)
 
     try:
-        batch, size = [], 0
-        for off, blk in iter_blocks(path):
-            isize = struct.unpack_from('<I', blk, len(blk) - 4)[0]
-            batch.append((off, blk))
-            size += isize
-            out['blocks'] += 1
-            out['compressed_bytes'] += len(blk)
-            out['inflated_bytes'] += isize
-            if size >= window_bytes:
-                window(batch)
-                batch, size = [], 0
-        if batch:
+        for batch in _batched(iter_blocks(path), window_bytes):
+            out['blocks'] += len(batch)
+            out['compressed_bytes'] += sum(len(blk) for _, blk in batch)
+            out['inflated_bytes'] += sum(struct.unpack_from('<I', blk, len(blk) - 4)[0] for _, blk in batch)
             window(batch)
+            del batch
     finally:
         if pool is not None:
             pool.shutdown()
@@ -1066,13 +1069,17 @@ _DEFLATE_REGION = 2 * 65536      # device bytes the encoder needs for one block 
 
 
 def _header_data(path, verify=False):
-    """(inflated bytes of the blocks the BAM header lies in, their number, header end, [(SQ name, length)])."""
+    """
+    (inflated bytes of the blocks the BAM header lies in, their number, header end, the bytes of the last of these blocks that
+    belong to the header, [(SQ name, length)]).
+    """
     data = bytearray()
     for k, (off, blk) in enumerate(iter_blocks(path)):
+        start = len(data)
         data += _host_inflate(path, [(off, blk)], None, verify)[0]
         got = parse_header(data)
         if got is not None:
-            return bytes(data), k + 1, got[0], got[1]
+            return bytes(data), k + 1, got[0], got[0] - start, got[1]
     raise ValueError('{0}: BAM header cut short'.format(path))
 
 
@@ -1254,30 +1261,12 @@ def sort_bam(src, dst, device=None, n_jobs=1, level=1, window_bytes=256 << 20, s
             joined = np.frombuffer(data, dtype=np.uint8) if data else np.zeros(1, np.uint8)
             call(lib.dn_bam_sort_window_host(h, _ptr(joined, u8), len(data), int(head_skip)), 'dn_bam_sort_window_host')
             return
-        blocks = [b for _, b in batch]
-        comp, n_comp, pay_off, pay_len, isize = _block_layout(blocks)
-        isize32 = np.where(isize > 2 ** 31 - 1, -1, isize).astype(np.int32)      # the library refuses a negative size
-        status, ms = np.zeros(max(len(batch), 1), np.int32), ctypes.c_double(0.0)
-        if verify:
-            call(lib.dn_bam_sort_expect_crc(h, _ptr(block_crcs(blocks), ctypes.c_uint32), len(batch)), 'dn_bam_sort_expect_crc')
-        call(lib.dn_bam_sort_window(h, _ptr(comp, u8), n_comp, len(batch), _ptr(pay_off, i64), _ptr(pay_len, i32), _ptr(isize32, i32),
-                                    int(head_skip), _ptr(status, i32), ctypes.byref(ms)), 'dn_bam_sort_window')
+        args, status = _window_args([b for _, b in batch], verify, lambda crc: call(
+            lib.dn_bam_sort_expect_crc(h, _ptr(crc, ctypes.c_uint32), len(crc)), 'dn_bam_sort_expect_crc'))
+        ms = ctypes.c_double(0.0)
+        call(lib.dn_bam_sort_window(h, *(args + (int(head_skip), _ptr(status, i32), ctypes.byref(ms)))), 'dn_bam_sort_window')
         t['inflate_device_ms'] += float(ms.value)
-        _raise_status(status[:len(batch)], lambda k: '{0}: the BGZF block at byte {1}'.format(src, batch[k][0]))
-
-    def batches(skip_blocks):
-        """Lists of (offset, block) of about window_bytes of inflated data, from block number skip_blocks on."""
-        batch, size = [], 0
-        for k, (off, blk) in enumerate(iter_blocks(src)):
-            if k < skip_blocks:
-                continue
-            batch.append((off, blk))
-            size += struct.unpack_from('<I', blk, len(blk) - 4)[0]
-            if size >= window_bytes:
-                yield batch
-                batch, size = [], 0
-        if batch:
-            yield batch
+        _raise_block_status(src, batch, status)
 
     def ends_chunks(n_records):
         for first in range(0, n_records, _ENDS_CHUNK):
@@ -1295,7 +1284,7 @@ def sort_bam(src, dst, device=None, n_jobs=1, level=1, window_bytes=256 << 20, s
 
     try:
         # the header, on zlib whatever the device: it may span several blocks; and the size of the whole stream
-        data, head_blocks, header_end, refs = _header_data(src, verify)
+        data, head_blocks, header_end, head_skip, refs = _header_data(src, verify)
         _, _, isizes = bgzf_blocks(src)
         n_stream = int(isizes.sum()) - header_end
         n_comp_max, size, comp = 0, 0, 0
@@ -1313,11 +1302,11 @@ def sort_bam(src, dst, device=None, n_jobs=1, level=1, window_bytes=256 << 20, s
                                  'a file that does not fit the device cannot be sorted here'.format(src, need, n_stream, have))
         call(lib.dn_bam_sort_create(-1 if device is None else int(device), len(refs), n_stream, int(segment_bytes or 0), window_bytes,
                                     ctypes.byref(h)), 'dn_bam_sort_create')
-        # the first window starts inside the block in which the header ends
-        head_skip = header_end - (len(data) - int(isizes[head_blocks - 1]))
-        for batch in batches(head_blocks - 1):
+        # the first window starts inside the block in which the header ends, and counts that block whole
+        for batch in _batched(itertools.islice(iter_blocks(src), head_blocks - 1, None), window_bytes):
             window(batch, head_skip)
             head_skip = 0
+            del batch
         n_rec, n_bytes, fix = i64(0), i64(0), i64(0)
         ms = [ctypes.c_double(0.0) for _ in range(3)]
         call(lib.dn_bam_sort_finish(h, ctypes.byref(n_rec), ctypes.byref(n_bytes), ctypes.byref(fix), ctypes.byref(ms[0]), ctypes.byref(ms[1]),

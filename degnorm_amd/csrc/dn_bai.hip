@@ -1,7 +1,7 @@
 // dn_bai.hip -- the .bai index of a coordinate-sorted BAM file, built from a pass over every record on the device.
 //
 // A window (the record cut by the window before + the inflated BGZF blocks of about window_bytes) is inflated
-// (dn::inflate_launch) and framed (dn::frame_window, tid = -1) where it lies; then, one lane per record:
+// (dn::InflateWindow) and framed (dn::frame_window, tid = -1) where it lies; then, one lane per record:
 //
 //   records   k_bai_records reads refID, pos, flag and the CIGAR, computes [beg, end), the bin (reg2bin), the packed
 //             (refID, bin) key and the record's virtual offset -- a binary search of the window's piece table, which says for
@@ -249,7 +249,6 @@ struct dn_bai_s {
     int64_t n_records = 0, n_windows = 0, n_fixups = 0;
     bool failed = false, finished = false;
     std::vector<Piece> carry_pieces;   // of the record cut by the end of the window before, rebased to offset 0
-    int64_t n_carry = 0;
     std::vector<Run> runs;             // in file order
     std::vector<Claim> claims;
     // the host build: the carried bytes and the carried state
@@ -257,11 +256,9 @@ struct dn_bai_s {
     Carry h_state{0, 0, 0, 0, 0, 0};
     // the device path
     dn::Stream st;
-    dn::GrowBuffer<uint8_t> win, comp, carry;
-    dn::GrowBuffer<dn::InflateBlock> blk;
-    dn::GrowBuffer<int32_t> blk_status;
-    std::vector<uint32_t> expect_crc;  // dn_bai_expect_crc: the CRC32 of every block of the next dn_bai_window
-    bool crc_armed = false;
+    dn::GrowBuffer<uint8_t> win;
+    dn::InflateWindow ingest;          // of dn_bai_window; armed by dn_bai_expect_crc
+    dn::DeviceCarry carry;             // carry.n is the carried length in both builds; the host build's bytes are h_carry
     dn::GrowBuffer<int64_t> rec_off;
     dn::GrowBuffer<Piece> pieces;
     dn::GrowBuffer<uint64_t> key, vbeg, emax_in, emax, hs, hs_sum;
@@ -276,7 +273,7 @@ struct dn_bai_s {
     int parity = 0;
     dn::FrameWork frame;
     dn::Scratch scratch;
-    dn::Event ev0, ev1, ev2, ev3;
+    dn::Event ev2, ev3;                // around the index kernels
     // what dn_bai_finish built
     std::vector<int32_t> ref_n_bin, ref_n_intv, bin_id, bin_n_chunk;
     std::vector<uint64_t> ref_pseudo, chunks, ioffset;
@@ -299,26 +296,13 @@ int record_error(dn_bai h, int code, int64_t idx, int32_t ref, int32_t pos)
     }
 }
 
-// the pieces of a window: those of the carried bytes, then one per block that keeps a byte; the window's size
-int window_pieces(dn_bai h, const char *who, int64_t n_blocks, const int32_t *isize, const int64_t *coffset, int32_t head_skip,
-                  std::vector<Piece> &pc, std::vector<dn::InflateBlock> *blk, const int64_t *pay_off, const int32_t *pay_len, int64_t n_comp,
-                  int64_t &total)
+// A window's pieces are those of the carried bytes, then one per block that keeps a byte.  This checks block b's file offset
+// and adds its piece: `keep` bytes from byte `skip` of the block, at window offset `at`.
+int add_piece(const char *who, std::vector<Piece> &pc, int64_t b, int64_t coffset, int64_t at, int32_t skip, int32_t keep)
 {
-    const std::string w(who);
-    pc = h->carry_pieces;
-    total = h->n_carry;
-    if (blk) blk->resize((size_t) n_blocks);
-    for (int64_t b = 0; b < n_blocks; b++) {
-        if (isize[b] < 0) return dn::fail(DN_E_INVALID, w + ": block " + std::to_string(b) + " has a negative inflated size");
-        if (coffset[b] < 0 || coffset[b] >= ((int64_t) 1 << 48)) return dn::fail(DN_E_INVALID, w + ": file offset of block " + std::to_string(b) + " outside 0 .. 2^48");
-        if (blk && (pay_off[b] < 0 || pay_len[b] < 0 || pay_off[b] > n_comp || pay_len[b] > n_comp - pay_off[b]))
-            return dn::fail(DN_E_INVALID, w + ": payload of block " + std::to_string(b) + " outside comp");
-        const int32_t lo = b == 0 ? (head_skip < isize[b] ? head_skip : isize[b]) : 0, keep = isize[b] - lo;
-        if (blk) (*blk)[(size_t) b] = dn::InflateBlock{pay_off[b], total, pay_len[b], isize[b], lo, keep};
-        if (keep > 0) pc.push_back(Piece{total, coffset[b], lo, 0});
-        total += keep;
-    }
-    if (total > INT32_MAX) return dn::fail(DN_E_INVALID, w + ": window beyond 2^31 - 1 bytes");
+    if (coffset < 0 || coffset >= ((int64_t) 1 << 48))
+        return dn::fail(DN_E_INVALID, std::string(who) + ": file offset of block " + std::to_string(b) + " outside 0 .. 2^48");
+    if (keep > 0) pc.push_back(Piece{at, coffset, skip, 0});
     return DN_OK;
 }
 
@@ -333,7 +317,6 @@ void carry_pieces(dn_bai h, const std::vector<Piece> &pc, int64_t consumed, int6
         out.push_back(Piece{from - consumed, pc[k].coffset, (int32_t) (pc[k].uoff + (from - pc[k].win)), 0});
     }
     h->carry_pieces.swap(out);
-    h->n_carry = total - consumed;
 }
 
 // stitch one window's tables onto the runs and claims so far
@@ -444,7 +427,6 @@ extern "C" int dn_bai_create(int device, int32_t n_ref, int64_t segment_bytes, d
         DN_TRY(dn::alloc_padded(h->totals, 1));
         DN_TRY(dn::alloc_padded(h->err, 1));
         DN_TRY(hipMemsetAsync(h->state, 0, 2 * sizeof(Carry), h->st));
-        DN_TRY(h->ev0.create(hipEventCreate)); DN_TRY(h->ev1.create(hipEventCreate));
         DN_TRY(h->ev2.create(hipEventCreate)); DN_TRY(h->ev3.create(hipEventCreate));
         DN_TRY(hipStreamSynchronize(h->st));
         return DN_OK;
@@ -467,11 +449,9 @@ extern "C" void dn_bai_destroy(dn_bai h)
 extern "C" int dn_bai_expect_crc(dn_bai h, const uint32_t *crc32, int64_t n_blocks)
 {
     dn::clear_error();
-    if (!h || n_blocks < 0 || n_blocks > INT32_MAX || (n_blocks > 0 && !crc32)) return dn::fail(DN_E_INVALID, "dn_bai_expect_crc: bad argument");
+    if (!h) return dn::fail(DN_E_INVALID, "dn_bai_expect_crc: bad argument");
     if (h->device < 0) return dn::fail(DN_E_STATE, "dn_bai_expect_crc: a host builder is handed inflated bytes; its caller checks them");
-    h->expect_crc.assign(crc32, crc32 + n_blocks);
-    h->crc_armed = true;
-    return DN_OK;
+    return h->ingest.arm("dn_bai_expect_crc", crc32, n_blocks);
 }
 
 extern "C" int dn_bai_window(dn_bai h, const uint8_t *comp, int64_t n_comp, int64_t n_blocks, const int64_t *pay_off, const int32_t *pay_len,
@@ -479,23 +459,13 @@ extern "C" int dn_bai_window(dn_bai h, const uint8_t *comp, int64_t n_comp, int6
                              double *inflate_ms, double *frame_ms, double *index_ms)
 {
     dn::clear_error();
-    std::vector<uint32_t> crc;         // the armed CRC32s are this call's, whatever it returns: taken before any check
-    const bool armed = h && h->crc_armed;
-    if (h) {
-        crc.swap(h->expect_crc);
-        h->expect_crc.clear();
-        h->crc_armed = false;
-    }
+    if (h) h->ingest.take();
     int rc = check_handle(h, "dn_bai_window", true);
     if (rc != DN_OK) return rc;
     if (n_comp < 0 || (n_comp > 0 && !comp) || n_blocks < 0 || n_blocks > INT32_MAX ||
         (n_blocks > 0 && (!pay_off || !pay_len || !isize || !coffset || !status)) || head_skip < 0 || !n_rec)
         return dn::fail(DN_E_INVALID, "dn_bai_window: bad argument");
-    if (armed && (int64_t) crc.size() != n_blocks)
-        return dn::fail(DN_E_INVALID, "dn_bai_window: " + std::to_string(crc.size()) + " CRC32s were announced (dn_bai_expect_crc) for " +
-                                      std::to_string(n_blocks) + " blocks");
-    std::vector<Piece> pc;
-    std::vector<dn::InflateBlock> blk;
+    std::vector<Piece> pc(h->carry_pieces);
     std::vector<Head> heads;
     std::vector<Claim> cl;
     Totals tot{0, 0, 0};
@@ -503,10 +473,13 @@ extern "C" int dn_bai_window(dn_bai h, const uint8_t *comp, int64_t n_comp, int6
     int64_t h_off = 0, total = 0;
     uint8_t h_rec[12] = {0};
     dn::FrameResult R;
-    rc = window_pieces(h, "dn_bai_window", n_blocks, isize, coffset, head_skip, pc, &blk, pay_off, pay_len, n_comp, total);
+    rc = h->ingest.plan("dn_bai_window", "dn_bai_expect_crc", n_comp, n_blocks, pay_off, pay_len, isize, head_skip, -1, h->carry.n, total);
+    for (int64_t b = 0; b < n_blocks && rc == DN_OK; b++) {
+        const dn::InflateBlock &B = h->ingest.blk[(size_t) b];
+        rc = add_piece("dn_bai_window", pc, b, coffset[b], B.dst_off, B.skip, B.keep);
+    }
     if (rc != DN_OK) return rc;
-    if (armed)
-        for (size_t b = 0; b < blk.size(); b++) { blk[b].crc = crc[b]; blk[b].check = 1; }
+    if (total > INT32_MAX) return dn::window_size_error("dn_bai_window");
     hipStream_t st = h->st;
     DN_TRY(hipSetDevice(h->device));
     *n_rec = 0;
@@ -515,25 +488,11 @@ extern "C" int dn_bai_window(dn_bai h, const uint8_t *comp, int64_t n_comp, int6
     if (index_ms) *index_ms = 0.0;
     return dn::synced(st, [&]() -> int {
         DN_TRY(h->win.reserve(total, 0, st));
-        const int64_t comp_cap = dn::inflate_comp_cap(n_comp);
-        DN_TRY(h->comp.reserve(comp_cap, 0, st));
-        DN_TRY(h->blk.reserve(n_blocks, 0, st)); DN_TRY(h->blk_status.reserve(n_blocks, 0, st));
-        // the record cut by the end of the window before goes first: it waited in h->carry while h->win was reused
-        if (h->n_carry > 0) DN_TRY(hipMemcpyAsync(h->win, h->carry, (size_t) h->n_carry, hipMemcpyDeviceToDevice, st));
-        if (n_comp > 0) DN_TRY(hipMemcpyAsync(h->comp, comp, (size_t) n_comp, hipMemcpyHostToDevice, st));
-        if (n_blocks > 0) DN_TRY(hipMemcpyAsync(h->blk, blk.data(), sizeof(dn::InflateBlock) * (size_t) n_blocks, hipMemcpyHostToDevice, st));
-        DN_TRY(hipEventRecord(h->ev0, st));
-        DN_TRY(dn::inflate_launch(st, h->comp, comp_cap, h->blk, n_blocks, h->win, h->blk_status));
-        DN_TRY(hipEventRecord(h->ev1, st));
-        if (n_blocks > 0) DN_TRY(hipMemcpyAsync(status, h->blk_status, sizeof(int32_t) * (size_t) n_blocks, hipMemcpyDeviceToHost, st));
-        DN_TRY(hipStreamSynchronize(st));
-        if (inflate_ms) {
-            float ms = 0.f;
-            DN_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-            *inflate_ms = ms;
-        }
-        for (int64_t b = 0; b < n_blocks; b++)
-            if (status[b] != 0) { h->failed = true; return DN_OK; }      // a block that failed left its bytes unspecified: the caller reports it
+        DN_TRY(h->carry.put(st, h->win));                   // the record cut by the end of the window before goes first
+        bool ok = true;
+        const int wrc = h->ingest.run(st, comp, n_comp, h->win, status, inflate_ms, ok);
+        if (wrc != DN_OK) return wrc;
+        if (!ok) { h->failed = true; return DN_OK; }
         const int frc = dn::frame_window(st, h->frame, h->win, total, -1, nullptr, h->segment, -1, h->rec_off, R);
         h->n_fixups += R.n_fixups;
         if (frame_ms) *frame_ms = R.device_ms;
@@ -547,9 +506,7 @@ extern "C" int dn_bai_window(dn_bai h, const uint8_t *comp, int64_t n_comp, int6
                 *index_ms = ms;
             }
         }
-        const int64_t left = total - R.consumed;
-        DN_TRY(h->carry.reserve(left, 0, st));
-        if (left > 0) DN_TRY(hipMemcpyAsync(h->carry, h->win + R.consumed, (size_t) left, hipMemcpyDeviceToDevice, st));
+        DN_TRY(h->carry.keep(st, h->win, R.consumed, total));
         carry_pieces(h, pc, R.consumed, total);
         absorb(h, R.n_rec, tot, heads.data(), cl.data());
         h->n_windows++;
@@ -566,13 +523,19 @@ extern "C" int dn_bai_window_host(dn_bai h, const uint8_t *data, int64_t n_data,
     if (rc != DN_OK) return rc;
     if (n_data < 0 || (n_data > 0 && !data) || n_blocks < 0 || (n_blocks > 0 && (!isize || !coffset)) || head_skip < 0 || !n_rec)
         return dn::fail(DN_E_INVALID, "dn_bai_window_host: bad argument");
-    std::vector<Piece> pc;
-    int64_t total = 0, sum = 0;
-    rc = window_pieces(h, "dn_bai_window_host", n_blocks, isize, coffset, head_skip, pc, nullptr, nullptr, nullptr, 0, total);
-    if (rc != DN_OK) return rc;
-    for (int64_t b = 0; b < n_blocks; b++) sum += isize[b];
+    std::vector<Piece> pc(h->carry_pieces);
+    int64_t total = h->carry.n, sum = 0, skip = 0;
+    for (int64_t b = 0; b < n_blocks; b++) {
+        if (isize[b] < 0) return dn::fail(DN_E_INVALID, "dn_bai_window_host: block " + std::to_string(b) + " has a negative inflated size");
+        int32_t lo, keep;
+        dn::window_trim(b, n_blocks, isize[b], head_skip, -1, lo, keep);
+        if ((rc = add_piece("dn_bai_window_host", pc, b, coffset[b], total, lo, keep)) != DN_OK) return rc;
+        if (b == 0) skip = lo;
+        total += keep;
+        sum += isize[b];
+    }
+    if (total > INT32_MAX) return dn::window_size_error("dn_bai_window_host");
     if (sum != n_data) return dn::fail(DN_E_INVALID, "dn_bai_window_host: the blocks' sizes do not add up to n_data");
-    const int64_t skip = n_blocks > 0 ? (head_skip < isize[0] ? head_skip : isize[0]) : 0;
     std::vector<uint8_t> win(h->h_carry);
     win.insert(win.end(), data + skip, data + n_data);
     win.resize(win.size() + 16);                                       // as the device buffers: slack behind the window
@@ -611,6 +574,7 @@ extern "C" int dn_bai_window_host(dn_bai h, const uint8_t *data, int64_t n_data,
         h->h_state = next;
     }
     h->h_carry.assign(win.begin() + consumed, win.begin() + total);
+    h->carry.n = total - consumed;
     carry_pieces(h, pc, consumed, total);
     absorb(h, nr, tot, heads.data(), cl.data());
     h->n_windows++;
@@ -623,9 +587,9 @@ extern "C" int dn_bai_finish(dn_bai h, int64_t end_voffset, int64_t *sizes)
     dn::clear_error();
     if (!h || !sizes || end_voffset < 0) return dn::fail(DN_E_INVALID, "dn_bai_finish: bad argument");
     if (h->failed || h->finished) return dn::fail(DN_E_STATE, "dn_bai_finish: the index is finished or has failed");
-    if (h->n_carry > 0) {
+    if (h->carry.n > 0) {
         h->failed = true;
-        return dn::fail(DN_E_INVALID, "record " + std::to_string(h->n_records) + " is cut by the end of the file (" + std::to_string(h->n_carry) +
+        return dn::fail(DN_E_INVALID, "record " + std::to_string(h->n_records) + " is cut by the end of the file (" + std::to_string(h->carry.n) +
                                       " bytes of it are there)");
     }
     const size_t n_ref = (size_t) h->n_ref;

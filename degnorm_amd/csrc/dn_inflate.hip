@@ -459,8 +459,7 @@ int validate(const char *who, const uint8_t *comp, int64_t n_comp, int64_t n_blo
     blk.resize((size_t) n_blocks);
     for (int64_t b = 0; b < n_blocks; b++) {
         const int64_t isize = out_off[b + 1] - out_off[b];
-        if (pay_off[b] < 0 || pay_len[b] < 0 || pay_off[b] > n_comp || pay_len[b] > n_comp - pay_off[b])
-            return bad(w + ": payload of block " + std::to_string(b) + " outside comp");
+        if (!dn::payload_inside(pay_off[b], pay_len[b], n_comp)) return bad(w + ": payload of block " + std::to_string(b) + " outside comp");
         if (isize < 0 || isize > 65536) return bad(w + ": block " + std::to_string(b) + " has an inflated size outside 0 .. 65536");
         blk[(size_t) b] = dn::InflateBlock{pay_off[b], out ? out_off[b] : 0, pay_len[b], (int32_t) isize, 0, out ? (int32_t) isize : 0,
                                            crc32 ? crc32[b] : 0u, crc32 ? 1 : 0};
@@ -537,6 +536,61 @@ hipError_t dn::inflate_launch(hipStream_t st, const uint8_t *d_comp, int64_t com
     if (n_blocks <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_bgzf_inflate, dim3((unsigned) n_blocks), dim3(64), 0, st, d_comp, comp_cap, d_blk, n_blocks, d_out, d_status);
     return hipGetLastError();
+}
+
+int dn::InflateWindow::arm(const char *who, const uint32_t *crc32, int64_t n_blocks)
+{
+    if (n_blocks < 0 || n_blocks > INT32_MAX || (n_blocks > 0 && !crc32)) return bad(std::string(who) + ": bad argument");
+    announced.assign(crc32, crc32 + n_blocks);
+    armed = true;
+    return DN_OK;
+}
+
+int dn::InflateWindow::plan(const char *who, const char *armed_by, int64_t n_comp, int64_t n_blocks, const int64_t *pay_off,
+                            const int32_t *pay_len, const int32_t *isize, int32_t head_skip, int32_t tail_keep, int64_t base, int64_t &total)
+{
+    const std::string w(who);
+    if (checking && (int64_t) crc.size() != n_blocks)
+        return bad(w + ": " + std::to_string(crc.size()) + " CRC32s were announced (" + armed_by + ") for " + std::to_string(n_blocks) + " blocks");
+    blk.resize((size_t) n_blocks);
+    total = base;
+    for (int64_t b = 0; b < n_blocks; b++) {
+        if (isize[b] < 0) return bad(w + ": block " + std::to_string(b) + " has a negative inflated size");
+        if (!payload_inside(pay_off[b], pay_len[b], n_comp)) return bad(w + ": payload of block " + std::to_string(b) + " outside comp");
+        int32_t skip, keep;
+        window_trim(b, n_blocks, isize[b], head_skip, tail_keep, skip, keep);
+        blk[(size_t) b] = InflateBlock{pay_off[b], total, pay_len[b], isize[b], skip, keep, checking ? crc[(size_t) b] : 0u, checking ? 1 : 0};
+        total += keep;
+    }
+    return DN_OK;
+}
+
+int dn::InflateWindow::queue(hipStream_t st, const uint8_t *comp_bytes, int64_t n_comp, uint8_t *d_out, int32_t *status)
+{
+    const int64_t n_blocks = (int64_t) blk.size(), comp_cap = inflate_comp_cap(n_comp);
+    DN_TRY(comp.reserve(comp_cap, 0, st));
+    DN_TRY(d_blk.reserve(n_blocks, 0, st)); DN_TRY(d_status.reserve(n_blocks, 0, st));
+    if (!ev0) { DN_TRY(ev0.create(hipEventCreate)); DN_TRY(ev1.create(hipEventCreate)); }
+    if (n_comp > 0) DN_TRY(hipMemcpyAsync(comp, comp_bytes, (size_t) n_comp, hipMemcpyHostToDevice, st));
+    if (n_blocks > 0) DN_TRY(hipMemcpyAsync(d_blk, blk.data(), sizeof(InflateBlock) * (size_t) n_blocks, hipMemcpyHostToDevice, st));
+    DN_TRY(hipEventRecord(ev0, st));
+    DN_TRY(inflate_launch(st, comp, comp_cap, d_blk, n_blocks, d_out, d_status));
+    DN_TRY(hipEventRecord(ev1, st));
+    if (n_blocks > 0) DN_TRY(hipMemcpyAsync(status, d_status, sizeof(int32_t) * (size_t) n_blocks, hipMemcpyDeviceToHost, st));
+    return DN_OK;
+}
+
+int dn::InflateWindow::wait(hipStream_t st, const int32_t *status, double *ms, bool &ok)
+{
+    DN_TRY(hipStreamSynchronize(st));
+    if (ms) {
+        float t = 0.f;
+        DN_TRY(hipEventElapsedTime(&t, ev0, ev1));
+        *ms = t;
+    }
+    ok = true;
+    for (size_t b = 0; b < blk.size(); b++) ok = ok && status[b] == 0;
+    return DN_OK;
 }
 
 extern "C" int dn_bgzf_inflate_host(const uint8_t *comp, int64_t n_comp, int64_t n_blocks, const int64_t *pay_off, const int32_t *pay_len,

@@ -812,26 +812,19 @@ struct dn_bam_rows_s {
     dn::GrowBuffer<uint8_t> names, win;
     dn::DeviceBuffer<unsigned long long> err;
     dn::Scratch scratch;                   // of the three scans of a window
-    // device inflate (dn_bam_rows_inflate): the compressed blocks, their descriptors and states, the pinned host copy of the
-    // window, and the bytes of h->win that hold the resident window (-1: none)
-    dn::GrowBuffer<uint8_t> comp;
-    dn::GrowBuffer<dn::InflateBlock> blk;
-    dn::GrowBuffer<int32_t> blk_status;
+    // device inflate (dn_bam_rows_inflate, dn_bam_rows_inflate_framed; armed by dn_bam_rows_expect_crc): the window ingest, the
+    // pinned host copy of the window, and the bytes of h->win that hold the resident window (-1: none)
+    dn::InflateWindow ingest;
     dn::PinnedBuffer<uint8_t> host_win;
-    dn::Event ev0, ev1;
     int64_t cap_host = 0, resident = -1;
-    // dn_bam_rows_expect_crc: the CRC32 of every block of the next dn_bam_rows_inflate / dn_bam_rows_inflate_framed
-    std::vector<uint32_t> expect_crc;
-    bool crc_armed = false;
     // device framing (dn_bam_rows_append_framed, dn_bam_rows_inflate_framed): its work buffers, the record cut by the end of
     // the window before (dn_bam_rows_inflate_framed keeps it on the device), the segment size asked for (0: the default), the
     // sums dn_bam_rows_frame_info reports and the pos of the last record framed
     dn::FrameWork frame;
-    dn::GrowBuffer<uint8_t> carry;
-    int64_t n_carry = 0, frame_segment = 0, frame_segments = 0, frame_fixups = 0;
+    dn::DeviceCarry carry;
+    int64_t frame_segment = 0, frame_segments = 0, frame_fixups = 0;
     double frame_ms = 0.0, framed_decode_ms = 0.0;
     int32_t last_pos = INT32_MIN;
-    dn::Event ev2, ev3;
     std::string no_cigar;                  // the name of the first kept row without CIGAR ops ("" while there is none)
     bool has_no_cigar = false;
 };
@@ -1007,61 +1000,20 @@ extern "C" int dn_bam_rows_append(dn_bam_rows h, const uint8_t *window, int64_t 
     });
 }
 
-namespace {
-
-// the InflateBlock of every block of a window that starts with n_carry carried bytes; the window's size in total
-int window_blocks(const char *who, int64_t n_carry, int64_t n_comp, int64_t n_blocks, const int64_t *pay_off, const int32_t *pay_len,
-                  const int32_t *isize, int32_t head_skip, int32_t tail_keep, std::vector<dn::InflateBlock> &blk, int64_t &total)
+// plan the window of an inflate call of the store behind `base` carried bytes
+static int plan_window(dn_bam_rows h, const char *who, int64_t base, int64_t n_comp, int64_t n_blocks, const int64_t *pay_off,
+                       const int32_t *pay_len, const int32_t *isize, int32_t head_skip, int32_t tail_keep, int64_t &total)
 {
-    const std::string w(who);
-    blk.resize((size_t) n_blocks);
-    total = n_carry;
-    for (int64_t b = 0; b < n_blocks; b++) {
-        if (pay_off[b] < 0 || pay_len[b] < 0 || pay_off[b] > n_comp || pay_len[b] > n_comp - pay_off[b])
-            return dn::fail(DN_E_INVALID, w + ": payload of block " + std::to_string(b) + " outside comp");
-        if (isize[b] < 0) return dn::fail(DN_E_INVALID, w + ": block " + std::to_string(b) + " has a negative inflated size");
-        int32_t hi = isize[b], lo = 0;                  // the last block is cut first, then the first one, as the host path does
-        if (b == n_blocks - 1 && tail_keep >= 0 && tail_keep < hi) hi = tail_keep;
-        if (b == 0) lo = head_skip < hi ? head_skip : hi;
-        blk[(size_t) b] = dn::InflateBlock{pay_off[b], total, pay_len[b], isize[b], lo, hi - lo};
-        total += hi - lo;
-    }
-    if (total > INT32_MAX) return dn::fail(DN_E_INVALID, w + ": window beyond 2^31 - 1 bytes");
-    return DN_OK;
+    const int rc = h->ingest.plan(who, "dn_bam_rows_expect_crc", n_comp, n_blocks, pay_off, pay_len, isize, head_skip, tail_keep, base, total);
+    if (rc != DN_OK) return rc;
+    return total > INT32_MAX ? dn::window_size_error(who) : DN_OK;
 }
-
-// hand the armed CRC32s (dn_bam_rows_expect_crc) to an inflate call and disarm the store: the first thing such a call does,
-// so that the arming is spent whatever the call then returns.  h may be null (the call refuses it next).
-bool take_expected_crc(dn_bam_rows h, std::vector<uint32_t> &crc)
-{
-    if (!h) return false;
-    const bool armed = h->crc_armed;
-    crc.swap(h->expect_crc);
-    h->expect_crc.clear();
-    h->crc_armed = false;
-    return armed;
-}
-
-int crc_count_error(const char *who, const char *armed_by, size_t n_crc, int64_t n_blocks)
-{
-    return dn::fail(DN_E_INVALID, std::string(who) + ": " + std::to_string(n_crc) + " CRC32s were announced (" + armed_by + ") for " +
-                                  std::to_string(n_blocks) + " blocks");
-}
-
-void check_blocks(std::vector<dn::InflateBlock> &blk, const std::vector<uint32_t> &crc)
-{
-    for (size_t b = 0; b < blk.size(); b++) { blk[b].crc = crc[b]; blk[b].check = 1; }
-}
-
-}  // namespace
 
 extern "C" int dn_bam_rows_expect_crc(dn_bam_rows h, const uint32_t *crc32, int64_t n_blocks)
 {
     dn::clear_error();
-    if (!h || n_blocks < 0 || n_blocks > INT32_MAX || (n_blocks > 0 && !crc32)) return dn::fail(DN_E_INVALID, "dn_bam_rows_expect_crc: bad argument");
-    h->expect_crc.assign(crc32, crc32 + n_blocks);
-    h->crc_armed = true;
-    return DN_OK;
+    if (!h) return dn::fail(DN_E_INVALID, "dn_bam_rows_expect_crc: bad argument");
+    return h->ingest.arm("dn_bam_rows_expect_crc", crc32, n_blocks);
 }
 
 extern "C" int dn_bam_rows_inflate(dn_bam_rows h, const uint8_t *carry, int64_t n_carry, const uint8_t *comp, int64_t n_comp,
@@ -1070,25 +1022,18 @@ extern "C" int dn_bam_rows_inflate(dn_bam_rows h, const uint8_t *carry, int64_t 
                                    int32_t *status, double *device_ms)
 {
     dn::clear_error();
-    std::vector<uint32_t> crc;
-    const bool armed = take_expected_crc(h, crc);
+    if (h) h->ingest.take();
     if (!h || n_carry < 0 || (n_carry > 0 && !carry) || n_comp < 0 || (n_comp > 0 && !comp) || n_blocks < 0 || n_blocks > INT32_MAX ||
         (n_blocks > 0 && (!pay_off || !pay_len || !isize || !status)) || head_skip < 0 || !host_window || !n_bytes)
         return dn::fail(DN_E_INVALID, "dn_bam_rows_inflate: bad argument");
-    if (armed && (int64_t) crc.size() != n_blocks) return crc_count_error("dn_bam_rows_inflate", "dn_bam_rows_expect_crc", crc.size(), n_blocks);
-    std::vector<dn::InflateBlock> blk;
     int64_t total = 0;
-    const int brc = window_blocks("dn_bam_rows_inflate", n_carry, n_comp, n_blocks, pay_off, pay_len, isize, head_skip, tail_keep, blk, total);
+    const int brc = plan_window(h, "dn_bam_rows_inflate", n_carry, n_comp, n_blocks, pay_off, pay_len, isize, head_skip, tail_keep, total);
     if (brc != DN_OK) return brc;
-    if (armed) check_blocks(blk, crc);
     hipStream_t st = h->st;
     DN_TRY(hipSetDevice(h->device));
     h->resident = -1;
     return dn::synced(st, [&]() -> int {
         DN_TRY(h->win.reserve(total, 0, st));
-        const int64_t comp_cap = dn::inflate_comp_cap(n_comp);
-        DN_TRY(h->comp.reserve(comp_cap, 0, st));
-        DN_TRY(h->blk.reserve(n_blocks, 0, st)); DN_TRY(h->blk_status.reserve(n_blocks, 0, st));
         if (total + 16 > h->cap_host) {
             const int64_t c = dn::grown_capacity(h->cap_host, total + 16);
             dn::PinnedBuffer<uint8_t> nb;                   // the old copy stays until the new one exists, as in GrowBuffer
@@ -1096,26 +1041,15 @@ extern "C" int dn_bam_rows_inflate(dn_bam_rows h, const uint8_t *carry, int64_t 
             h->host_win = std::move(nb);
             h->cap_host = c;
         }
-        if (!h->ev0) { DN_TRY(h->ev0.create(hipEventCreate)); DN_TRY(h->ev1.create(hipEventCreate)); }
         if (n_carry > 0) DN_TRY(hipMemcpyAsync(h->win, carry, (size_t) n_carry, hipMemcpyHostToDevice, st));
-        if (n_comp > 0) DN_TRY(hipMemcpyAsync(h->comp, comp, (size_t) n_comp, hipMemcpyHostToDevice, st));
-        if (n_blocks > 0) DN_TRY(hipMemcpyAsync(h->blk, blk.data(), sizeof(dn::InflateBlock) * (size_t) n_blocks, hipMemcpyHostToDevice, st));
-        DN_TRY(hipEventRecord(h->ev0, st));
-        DN_TRY(dn::inflate_launch(st, h->comp, comp_cap, h->blk, n_blocks, h->win, h->blk_status));
-        DN_TRY(hipEventRecord(h->ev1, st));
+        bool ok = true;
+        int rc = h->ingest.queue(st, comp, n_comp, h->win, status);
+        if (rc != DN_OK) return rc;
         if (total > 0) DN_TRY(hipMemcpyAsync(h->host_win, h->win, (size_t) total, hipMemcpyDeviceToHost, st));
-        if (n_blocks > 0) DN_TRY(hipMemcpyAsync(status, h->blk_status, sizeof(int32_t) * (size_t) n_blocks, hipMemcpyDeviceToHost, st));
-        DN_TRY(hipStreamSynchronize(st));
-        if (device_ms) {
-            float ms = 0.f;
-            DN_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-            *device_ms = ms;
-        }
+        if ((rc = h->ingest.wait(st, status, device_ms, ok)) != DN_OK) return rc;
         *host_window = h->host_win;
         *n_bytes = total;
-        h->resident = total;
-        for (int64_t b = 0; b < n_blocks; b++)
-            if (status[b] != 0) { h->resident = -1; break; }     // a block that failed left its bytes unspecified
+        h->resident = ok ? total : -1;
         return DN_OK;
     });
 }
@@ -1196,17 +1130,13 @@ extern "C" int dn_bam_rows_inflate_framed(dn_bam_rows h, const uint8_t *comp, in
                                           int32_t *status, int64_t *n_bytes, int64_t *n_carry, double *inflate_ms, double *frame_ms)
 {
     dn::clear_error();
-    std::vector<uint32_t> crc;
-    const bool armed = take_expected_crc(h, crc);
+    if (h) h->ingest.take();
     if (!h || n_comp < 0 || (n_comp > 0 && !comp) || n_blocks < 0 || n_blocks > INT32_MAX ||
         (n_blocks > 0 && (!pay_off || !pay_len || !isize || !status)) || head_skip < 0 || !n_bytes || !n_carry)
         return dn::fail(DN_E_INVALID, "dn_bam_rows_inflate_framed: bad argument");
-    if (armed && (int64_t) crc.size() != n_blocks) return crc_count_error("dn_bam_rows_inflate_framed", "dn_bam_rows_expect_crc", crc.size(), n_blocks);
-    std::vector<dn::InflateBlock> blk;
     int64_t total = 0;
-    const int brc = window_blocks("dn_bam_rows_inflate_framed", h->n_carry, n_comp, n_blocks, pay_off, pay_len, isize, head_skip, tail_keep, blk, total);
+    const int brc = plan_window(h, "dn_bam_rows_inflate_framed", h->carry.n, n_comp, n_blocks, pay_off, pay_len, isize, head_skip, tail_keep, total);
     if (brc != DN_OK) return brc;
-    if (armed) check_blocks(blk, crc);
     hipStream_t st = h->st;
     dn::FrameResult R;
     DN_TRY(hipSetDevice(h->device));
@@ -1214,37 +1144,19 @@ extern "C" int dn_bam_rows_inflate_framed(dn_bam_rows h, const uint8_t *comp, in
     if (frame_ms) *frame_ms = 0.0;
     return dn::synced(st, [&]() -> int {
         DN_TRY(h->win.reserve(total, 0, st));
-        const int64_t comp_cap = dn::inflate_comp_cap(n_comp);
-        DN_TRY(h->comp.reserve(comp_cap, 0, st));
-        DN_TRY(h->blk.reserve(n_blocks, 0, st)); DN_TRY(h->blk_status.reserve(n_blocks, 0, st));
-        if (!h->ev2) { DN_TRY(h->ev2.create(hipEventCreate)); DN_TRY(h->ev3.create(hipEventCreate)); }
-        // the record cut by the end of the window before goes first: it waited in h->carry while h->win was reused
-        if (h->n_carry > 0) DN_TRY(hipMemcpyAsync(h->win, h->carry, (size_t) h->n_carry, hipMemcpyDeviceToDevice, st));
-        if (n_comp > 0) DN_TRY(hipMemcpyAsync(h->comp, comp, (size_t) n_comp, hipMemcpyHostToDevice, st));
-        if (n_blocks > 0) DN_TRY(hipMemcpyAsync(h->blk, blk.data(), sizeof(dn::InflateBlock) * (size_t) n_blocks, hipMemcpyHostToDevice, st));
-        DN_TRY(hipEventRecord(h->ev2, st));
-        DN_TRY(dn::inflate_launch(st, h->comp, comp_cap, h->blk, n_blocks, h->win, h->blk_status));
-        DN_TRY(hipEventRecord(h->ev3, st));
-        if (n_blocks > 0) DN_TRY(hipMemcpyAsync(status, h->blk_status, sizeof(int32_t) * (size_t) n_blocks, hipMemcpyDeviceToHost, st));
-        DN_TRY(hipStreamSynchronize(st));
-        if (inflate_ms) {
-            float ms = 0.f;
-            DN_TRY(hipEventElapsedTime(&ms, h->ev2, h->ev3));
-            *inflate_ms = ms;
-        }
+        DN_TRY(h->carry.put(st, h->win));                   // the record cut by the end of the window before goes first
+        bool ok = true;
+        int rc = h->ingest.run(st, comp, n_comp, h->win, status, inflate_ms, ok);
+        if (rc != DN_OK) return rc;
         *n_bytes = total;
-        *n_carry = h->n_carry;
-        for (int64_t b = 0; b < n_blocks; b++)
-            if (status[b] != 0) return DN_OK;               // a block that failed left its bytes unspecified: the caller reports it
-        const int rc = dn::frame_window(st, h->frame, h->win, total, h->F.tid, &h->last_pos, h->frame_segment, -1, h->rec_off, R);
+        *n_carry = h->carry.n;
+        if (!ok) return DN_OK;
+        rc = dn::frame_window(st, h->frame, h->win, total, h->F.tid, &h->last_pos, h->frame_segment, -1, h->rec_off, R);
         count_framing(h, R);
         if (frame_ms) *frame_ms = R.device_ms;
         if (rc != DN_OK) return rc;
-        const int64_t left = total - R.consumed;
-        DN_TRY(h->carry.reserve(left, 0, st));
-        if (left > 0) DN_TRY(hipMemcpyAsync(h->carry, h->win + R.consumed, (size_t) left, hipMemcpyDeviceToDevice, st));
-        h->n_carry = left;
-        *n_carry = left;
+        DN_TRY(h->carry.keep(st, h->win, R.consumed, total));
+        *n_carry = h->carry.n;
         return append_framed_window(h, nullptr, total, R.n_rec);
     });
 }

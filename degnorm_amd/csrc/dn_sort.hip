@@ -215,11 +215,7 @@ struct dn_bam_sort_s {
     // the device path
     dn::Stream st;
     dn::DeviceBuffer<uint8_t> in, out;
-    dn::GrowBuffer<uint8_t> comp;
-    dn::GrowBuffer<dn::InflateBlock> blk;
-    dn::GrowBuffer<int32_t> blk_status;
-    std::vector<uint32_t> expect_crc;  // dn_bam_sort_expect_crc: the CRC32 of every block of the next dn_bam_sort_window
-    bool crc_armed = false;
+    dn::InflateWindow ingest;          // of dn_bam_sort_window; armed by dn_bam_sort_expect_crc
     dn::GrowBuffer<int64_t> piece_off, off, dst;
     dn::GrowBuffer<uint64_t> key, key2;
     dn::GrowBuffer<uint32_t> ord, ord2, len;
@@ -537,64 +533,33 @@ extern "C" void dn_bam_sort_destroy(dn_bam_sort h)
 extern "C" int dn_bam_sort_expect_crc(dn_bam_sort h, const uint32_t *crc32, int64_t n_blocks)
 {
     dn::clear_error();
-    if (!h || n_blocks < 0 || n_blocks > INT32_MAX || (n_blocks > 0 && !crc32)) return dn::fail(DN_E_INVALID, "dn_bam_sort_expect_crc: bad argument");
+    if (!h) return dn::fail(DN_E_INVALID, "dn_bam_sort_expect_crc: bad argument");
     if (h->device < 0) return dn::fail(DN_E_STATE, "dn_bam_sort_expect_crc: a host sort is handed inflated bytes; its caller checks them");
-    h->expect_crc.assign(crc32, crc32 + n_blocks);
-    h->crc_armed = true;
-    return DN_OK;
+    return h->ingest.arm("dn_bam_sort_expect_crc", crc32, n_blocks);
 }
 
 extern "C" int dn_bam_sort_window(dn_bam_sort h, const uint8_t *comp, int64_t n_comp, int64_t n_blocks, const int64_t *pay_off, const int32_t *pay_len,
                                   const int32_t *isize, int32_t head_skip, int32_t *status, double *inflate_ms)
 {
     dn::clear_error();
-    std::vector<uint32_t> crc;         // the armed CRC32s are this call's, whatever it returns: taken before any check
-    const bool armed = h && h->crc_armed;
-    if (h) {
-        crc.swap(h->expect_crc);
-        h->expect_crc.clear();
-        h->crc_armed = false;
-    }
+    if (h) h->ingest.take();
     int rc = check_handle(h, "dn_bam_sort_window", true);
     if (rc != DN_OK) return rc;
     if (n_comp < 0 || (n_comp > 0 && !comp) || n_blocks < 0 || n_blocks > INT32_MAX || (n_blocks > 0 && (!pay_off || !pay_len || !isize || !status)) ||
         head_skip < 0)
         return dn::fail(DN_E_INVALID, "dn_bam_sort_window: bad argument");
-    if (armed && (int64_t) crc.size() != n_blocks)
-        return dn::fail(DN_E_INVALID, "dn_bam_sort_window: " + std::to_string(crc.size()) + " CRC32s were announced (dn_bam_sort_expect_crc) for " +
-                                      std::to_string(n_blocks) + " blocks");
-    std::vector<dn::InflateBlock> blk((size_t) n_blocks);
-    int64_t at = h->filled;
-    for (int64_t b = 0; b < n_blocks; b++) {
-        if (isize[b] < 0) return dn::fail(DN_E_INVALID, "dn_bam_sort_window: block " + std::to_string(b) + " has a negative inflated size");
-        if (pay_off[b] < 0 || pay_len[b] < 0 || pay_off[b] > n_comp || pay_len[b] > n_comp - pay_off[b])
-            return dn::fail(DN_E_INVALID, "dn_bam_sort_window: payload of block " + std::to_string(b) + " outside comp");
-        const int32_t lo = b == 0 ? (head_skip < isize[b] ? head_skip : isize[b]) : 0, keep = isize[b] - lo;
-        blk[(size_t) b] = dn::InflateBlock{pay_off[b], at, pay_len[b], isize[b], lo, keep, armed ? crc[(size_t) b] : 0u, armed ? 1 : 0};
-        at += keep;
-    }
+    int64_t at = 0;
+    rc = h->ingest.plan("dn_bam_sort_window", "dn_bam_sort_expect_crc", n_comp, n_blocks, pay_off, pay_len, isize, head_skip, -1, h->filled, at);
+    if (rc != DN_OK) return rc;
     if (at > h->n_bytes) return dn::fail(DN_E_INVALID, "dn_bam_sort_window: the blocks hold more bytes than dn_bam_sort_create was told");
     hipStream_t st = h->st;
     DN_TRY(hipSetDevice(h->device));
     if (inflate_ms) *inflate_ms = 0.0;
     return dn::synced(st, [&]() -> int {
-        const int64_t comp_cap = dn::inflate_comp_cap(n_comp);
-        DN_TRY(h->comp.reserve(comp_cap, 0, st));
-        DN_TRY(h->blk.reserve(n_blocks, 0, st)); DN_TRY(h->blk_status.reserve(n_blocks, 0, st));
-        if (n_comp > 0) DN_TRY(hipMemcpyAsync(h->comp, comp, (size_t) n_comp, hipMemcpyHostToDevice, st));
-        if (n_blocks > 0) DN_TRY(hipMemcpyAsync(h->blk, blk.data(), sizeof(dn::InflateBlock) * (size_t) n_blocks, hipMemcpyHostToDevice, st));
-        DN_TRY(hipEventRecord(h->ev0, st));
-        DN_TRY(dn::inflate_launch(st, h->comp, comp_cap, h->blk, n_blocks, h->in, h->blk_status));
-        DN_TRY(hipEventRecord(h->ev1, st));
-        if (n_blocks > 0) DN_TRY(hipMemcpyAsync(status, h->blk_status, sizeof(int32_t) * (size_t) n_blocks, hipMemcpyDeviceToHost, st));
-        DN_TRY(hipStreamSynchronize(st));
-        if (inflate_ms) {
-            float ms = 0.f;
-            DN_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-            *inflate_ms = ms;
-        }
-        for (int64_t b = 0; b < n_blocks; b++)
-            if (status[b] != 0) { h->failed = true; return DN_OK; }      // a block that failed left its bytes unspecified: the caller reports it
+        bool ok = true;
+        const int wrc = h->ingest.run(st, comp, n_comp, h->in, status, inflate_ms, ok);
+        if (wrc != DN_OK) return wrc;
+        if (!ok) { h->failed = true; return DN_OK; }
         h->filled = at;
         h->n_windows++;
         return DN_OK;
@@ -715,7 +680,7 @@ extern "C" int dn_bam_sort_deflate(dn_bam_sort h, int64_t n_blocks, const int64_
         if (!h->deflating) {
             // what only the sort needed goes: the deflate tables are smaller, so the device need stays below the sort's
             DN_TRY(hipStreamSynchronize(h->st));
-            h->comp = dn::GrowBuffer<uint8_t>(); h->blk = dn::GrowBuffer<dn::InflateBlock>(); h->blk_status = dn::GrowBuffer<int32_t>();
+            h->ingest = dn::InflateWindow();
             h->piece_off = dn::GrowBuffer<int64_t>(); h->off = dn::GrowBuffer<int64_t>();
             h->key = dn::GrowBuffer<uint64_t>(); h->key2 = dn::GrowBuffer<uint64_t>();
             h->ord = dn::GrowBuffer<uint32_t>(); h->ord2 = dn::GrowBuffer<uint32_t>(); h->len = dn::GrowBuffer<uint32_t>();

@@ -1,8 +1,9 @@
 """
 GPU tests of the BGZF CRC32 check (csrc/dn_inflate.hip, WaveMem::flush): every valid case verified in one launch, the sizes at
 which slicing and flushing change, blocks with wrong bytes (each first judged by the host build of the same source) among
-valid ones, the row store's armed windows, the reader on every inflate x frame combination, the index builder, verify_bgzf
-and the pipeline.  As in test_gpu_inflate.py, corrupt blocks go to the device only after the valid batch has passed.
+valid ones, the armed windows of the row store, the index builder and the sort handle, the reader on every inflate x frame
+combination, build_index, verify_bgzf, sort_bam and the pipeline.  As in test_gpu_inflate.py, corrupt blocks go to the device only
+after the valid batch has passed.
 """
 import ctypes
 import os
@@ -183,6 +184,176 @@ def test_row_store_windows_armed():
         finally:
             rows.close()
     assert got[True] == got[False] and got[True][1][0] > 500 and got[True][0] > 0
+
+
+class _Windows(object):
+    """dn_bai_* or dn_bam_sort_* through ctypes: one handle that takes windows of whole BGZF blocks, on GPU 0 or (host) the host build."""
+
+    def __init__(self, kind, n_bytes, host=False):
+        self.lib, self.kind, self.host, self.h = _lib.load(), kind, host, ctypes.c_void_p()
+        if kind == 'bai':
+            rc = self.lib.dn_bai_create(-1 if host else 0, 3, 0, ctypes.byref(self.h))
+        else:
+            rc = self.lib.dn_bam_sort_create(-1 if host else 0, 3, n_bytes, 0, 0, ctypes.byref(self.h))
+        assert rc == 0
+
+    def close(self):
+        (self.lib.dn_bai_destroy if self.kind == 'bai' else self.lib.dn_bam_sort_destroy)(self.h)
+
+    def expect_crc(self, crc):
+        fn = self.lib.dn_bai_expect_crc if self.kind == 'bai' else self.lib.dn_bam_sort_expect_crc
+        return fn(self.h, crc.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), len(crc))
+
+    def window(self, blocks, head_skip):
+        """(return code, the library's error text, status of every block)."""
+        P, c = ctypes.POINTER, ctypes
+        comp, n_comp, pay_off, pay_len, isize = bam._block_layout(blocks)
+        n, isize32, status = len(blocks), isize.astype(np.int32), np.full(len(blocks), -9, np.int32)
+        coffset = np.concatenate([[0], np.cumsum([len(b) for b in blocks])[:-1]]).astype(np.int64)
+        if self.host:
+            data = np.frombuffer(b''.join(bam.inflate_block(b) for b in blocks), dtype=np.uint8)
+            if self.kind == 'bai':
+                rc = self.lib.dn_bai_window_host(self.h, data.ctypes.data_as(P(c.c_uint8)), len(data), n, isize32.ctypes.data_as(P(c.c_int32)),
+                                                 coffset.ctypes.data_as(P(c.c_int64)), head_skip, ctypes.byref(c.c_int64()))
+            else:
+                rc = self.lib.dn_bam_sort_window_host(self.h, data.ctypes.data_as(P(c.c_uint8)), len(data), head_skip)
+        else:
+            args = (self.h, comp.ctypes.data_as(P(c.c_uint8)), n_comp, n, pay_off.ctypes.data_as(P(c.c_int64)),
+                    pay_len.ctypes.data_as(P(c.c_int32)), isize32.ctypes.data_as(P(c.c_int32)))
+            st = status.ctypes.data_as(P(c.c_int32))
+            if self.kind == 'bai':
+                rc = self.lib.dn_bai_window(*(args + (coffset.ctypes.data_as(P(c.c_int64)), head_skip, st, ctypes.byref(c.c_int64()), None, None, None)))
+            else:
+                rc = self.lib.dn_bam_sort_window(*(args + (head_skip, st, None)))
+        return rc, self.lib.dn_last_error().decode(), status.tolist()
+
+    def result(self, end_voffset):
+        """(return code of the finish call, the index tables or the sorted stream as bytes)."""
+        P, c = ctypes.POINTER, ctypes
+        if self.kind == 'sort':
+            n_rec, n_bytes = c.c_int64(0), c.c_int64(0)
+            rc = self.lib.dn_bam_sort_finish(self.h, ctypes.byref(n_rec), ctypes.byref(n_bytes), None, None, None, None)
+            if rc != 0:
+                return rc, None
+            out = np.zeros(n_bytes.value, np.uint8)
+            assert self.lib.dn_bam_sort_read(self.h, 0, n_bytes.value, out.ctypes.data_as(P(c.c_uint8))) == 0
+            return rc, (n_rec.value, out.tobytes())
+        sizes = np.zeros(8, np.int64)
+        rc = self.lib.dn_bai_finish(self.h, end_voffset, sizes.ctypes.data_as(P(c.c_int64)))
+        if rc != 0:
+            return rc, None
+        n_bins, n_chunks, n_intv = (int(x) for x in sizes[:3])
+        i32 = [np.zeros(max(k, 1), np.int32) for k in (3, 3, n_bins, n_bins)]
+        u64 = [np.zeros(max(k, 1), np.uint64) for k in (12, 2 * n_chunks, n_intv)]
+        p32, p64 = (lambda a: a.ctypes.data_as(P(c.c_int32))), (lambda a: a.ctypes.data_as(P(c.c_uint64)))
+        assert self.lib.dn_bai_fetch(self.h, p32(i32[0]), p32(i32[1]), p64(u64[0]), p32(i32[2]), p32(i32[3]), p64(u64[1]), p64(u64[2])) == 0
+        return rc, (sizes[:5].tolist(),) + tuple(a.tobytes() for a in i32 + u64)
+
+
+@pytest.mark.parametrize('kind', ['bai', 'sort'])
+def test_index_and_sort_windows_armed(kind):
+    """
+    test_row_store_windows_armed's second fixture (_records() cut at 65 280 and 65 280 + 70 000: three blocks, the middle one
+    beyond 64 KiB) through the armed windows of the index builder and of the sort handle.  A .bai cannot address a record
+    that starts beyond byte 65 535 of its block, so the builder (device and host alike) refuses these blocks' records: for
+    'bai' they go through an armed window once, up to that refusal, and the other steps run on the same records cut at
+    65 280 and 65 280 + 65 536 and ended at the last record inside the next 65 536 bytes -- three blocks, the middle one of
+    the largest size a block can have, 64 KiB.
+    """
+    assert _VALID_PASSED
+    rec, offs = _records()
+    head_skip = int(offs[3])
+    cuts = [0, 65280, 65280 + 70000, len(rec)]
+    if kind == 'bai':
+        blocks = [_blk(rec[x:y], 1) for x, y in zip(cuts[:-1], cuts[1:])]
+        res = []
+        for host in (True, False):
+            w = _Windows(kind, 0, host)
+            try:
+                if not host:
+                    assert w.expect_crc(bam.block_crcs(blocks)) == 0
+                res.append(w.window(blocks, head_skip))
+            finally:
+                w.close()
+        assert res[1][:2] == res[0][:2] and res[1][0] == _lib.DN_E_INVALID and res[1][2] == [0, 0, 0]
+        assert 'starts beyond byte 65535 of its BGZF block' in res[1][1]
+        cuts = [0, 65280, 65280 + 65536, int(offs[offs <= 65280 + 2 * 65536][-1])]
+    blocks = [_blk(rec[x:y], 1) for x, y in zip(cuts[:-1], cuts[1:])]
+    wrong = [blk[:-8] + bytes([blk[-8] ^ 1]) + blk[-7:] for blk in (blocks[0], blocks[2])]
+    flipped = [wrong[0], blocks[1], wrong[1]]
+    for blk in wrong:                                                             # judged on the host first, as every bad block: by zlib,
+        with pytest.raises(bam.BgzfCrcError):                                     # the host build of the decoder stops at 64 KiB
+            bam.inflate_block(blk, True)
+    n_bytes, end = cuts[-1] - head_skip, sum(len(b) for b in blocks) << 16
+    who = 'dn_bai' if kind == 'bai' else 'dn_bam_sort'
+
+    def run(host, steps):
+        w = _Windows(kind, n_bytes, host)
+        try:
+            return steps(w)
+        finally:
+            w.close()
+
+    want = run(True, lambda w: (w.window(blocks, head_skip)[0], w.result(end)))
+    assert want[0] == 0 and want[1][0] == 0 and want[1][1] is not None
+
+    def unarmed(w):
+        # a count that differs from the call's: an error with the exact text, the arming is spent, the handle goes on
+        assert w.expect_crc(np.zeros(2, np.uint32)) == 0
+        rc, text, _ = w.window(blocks, head_skip)
+        assert rc == _lib.DN_E_INVALID and text == '{0}_window: 2 CRC32s were announced ({0}_expect_crc) for 3 blocks'.format(who)
+        # a call refused for its arguments spends the arming too: the window after it is not checked against these zeros
+        assert w.expect_crc(np.zeros(3, np.uint32)) == 0
+        rc, text, _ = w.window(blocks, -1)
+        assert rc == _lib.DN_E_INVALID and text == who + '_window: bad argument'
+        rc, _, status = w.window(blocks, head_skip)
+        assert rc == 0 and status == [0, 0, 0]
+        return w.result(end)
+
+    def armed(w):
+        assert w.expect_crc(bam.block_crcs(blocks)) == 0
+        rc, _, status = w.window(blocks, head_skip)
+        assert rc == 0 and status == [0, 0, 0]
+        return w.result(end)
+
+    def flipped_unarmed(w):                                                       # nobody looks at the trailers
+        rc, _, status = w.window(flipped, head_skip)
+        assert rc == 0 and status == [0, 0, 0]
+        return w.result(end)
+
+    def flipped_armed(w):
+        assert w.expect_crc(bam.block_crcs(flipped)) == 0
+        rc, _, status = w.window(flipped, head_skip)
+        assert rc == 0 and status == [cc.E_CRC, 0, cc.E_CRC]
+        rc, text, _ = w.window(blocks, head_skip)                                 # the handle has failed
+        assert rc == _lib.DN_E_STATE and text.startswith(who + '_window: ')
+        return w.result(end)
+
+    assert run(False, unarmed) == want[1]
+    assert run(False, armed) == want[1]
+    assert run(False, flipped_unarmed) == want[1]
+    assert run(False, flipped_armed) == (_lib.DN_E_STATE, None)
+
+
+def test_device_sort_verified(damaged, tmp_path):
+    """sort_bam(device=0, verify=True): the damaged block is named as the host sort names it; a good file is written as without the check."""
+    assert _VALID_PASSED
+    path, good_path, chrom, offset = damaged
+    dst = str(tmp_path / 'sorted.bam')
+    with pytest.raises(ValueError) as host:
+        bam.sort_bam(path, dst, device=None, verify=True)
+    assert str(host.value) == cc.crc_message(path, offset)
+    with pytest.raises(ValueError) as dev:
+        bam.sort_bam(path, dst, device=0, verify=True, window_bytes=70000)
+    assert str(dev.value) == str(host.value)
+    assert not os.path.exists(dst) and not os.path.exists(dst + '.tmp')
+    got = {}
+    for verify in (False, True):
+        stats = {}
+        with open(bam.sort_bam(good_path, dst, device=0, verify=verify, window_bytes=70000, overwrite=True, stats=stats), 'rb') as f:
+            got[verify] = f.read()
+        assert stats['windows'] > 1 and stats['records'] > 2000
+    assert got[True] == got[False] and len(got[True]) > 10000
 
 
 @pytest.fixture(scope='module')
