@@ -6,8 +6,11 @@ In-tree build of libdegnorm_amd.so (HIP kernels + C ABI) for gfx950 with hipcc.
 One translation unit per sample count p (dn_inst.hip -DDN_P=p), the run-time-p family (dn_generic.hip, compiled three
 times: 256- and 64-thread builds on float32 counts, a 256-thread build on float64 input), the coverage-assembly,
 reads-processing, BGZF-inflate, BGZF-deflate, record-framing, BAM-index, BAM-sort and GTF-scan units plus the C-ABI unit; objects are compiled
-in parallel and linked into degnorm_amd/libdegnorm_amd.so.  hipcc cross-compiles without a GPU.
+in parallel and linked into degnorm_amd/libdegnorm_amd.so.  hipcc cross-compiles without a GPU.  The host-side units (HOST_UNITS
+and the C-ABI unit) are rebuilt when include/degnorm_amd.h or any header under csrc/ changes (dn_host.hpp, dn_bam_record.hpp --
+what a BAM record is -- and the units' own headers).
 """
+import glob
 import os
 import subprocess
 import sys
@@ -46,6 +49,15 @@ def sched_flags(p):
     if 'DN_HIPCC_FLAGS' in os.environ:
         return SCHED
     return [] if 3 <= p <= 12 else MAX_ILP
+# the host-side units besides the C-ABI unit, one object each: source csrc/<name>.hip, object <name>.o
+HOST_UNITS = ('dn_assemble',    # per-gene coverage assembly
+              'dn_reads',       # reads -> coverage / read counts (BamReadsProcessor, reads.py)
+              'dn_inflate',     # BGZF blocks -> inflated bytes (NativeBamReadsProcessor inflate='device', bam.py)
+              'dn_deflate',     # byte ranges -> BGZF blocks (bam.bgzf_deflate, bam.sort_bam deflate='native')
+              'dn_frame',       # inflated BAM bytes -> record offsets (NativeBamReadsProcessor frame='device', bam.py)
+              'dn_bai',         # BAM records -> .bai index (bam.build_index)
+              'dn_sort',        # BAM records -> the coordinate-sorted record stream (bam.sort_bam)
+              'dn_gtf')         # GTF bytes -> exon table (GeneAnnotationLoader, loaders.py)
 FLAGS = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC', '-fno-fast-math', '-ffp-contract=on',
          '-Wall', '-Wno-unused-function']
 
@@ -89,8 +101,7 @@ def build_library(force=False, verbose=False):
     hipcc = _hipcc()
     hdr = [os.path.join(CSRC, 'dn_kernels.hpp'), os.path.join(CSRC, 'dn_reduce.hpp'), os.path.join(HERE, '..', 'include', 'degnorm_amd.h'),
            os.path.abspath(__file__)]
-    host_hdr = hdr + [os.path.join(CSRC, 'dn_host.hpp'), os.path.join(CSRC, 'dn_inflate.hpp'), os.path.join(CSRC, 'dn_frame.hpp'), os.path.join(CSRC, 'dn_crc.hpp'),
-                      os.path.join(CSRC, 'dn_deflate.hpp')]     # the host-side units: api, reads, assemble
+    host_hdr = hdr + glob.glob(os.path.join(CSRC, '*.hpp'))     # of the host-side units (HOST_UNITS and dn_api): no list to keep
     jobs = []
     objs = []
     inst = os.path.join(CSRC, 'dn_inst.hip')
@@ -115,46 +126,11 @@ def build_library(force=False, verbose=False):
     objs.append(o_f64)
     if force or _newer(o_f64, [gen] + hdr):
         jobs.append([hipcc] + FLAGS + EXTRA + ['-DDN_GEN_NT=256', '-DDN_GEN_F64=1', '-c', gen, '-o', o_f64])
-    asm = os.path.join(CSRC, 'dn_assemble.hip')
-    o_asm = os.path.join(OBJ, 'dn_assemble.o')
-    objs.append(o_asm)
-    if force or _newer(o_asm, [asm] + host_hdr):
-        jobs.append([hipcc] + FLAGS + ['-c', asm, '-o', o_asm])
-    rd = os.path.join(CSRC, 'dn_reads.hip')             # reads -> coverage / read counts (BamReadsProcessor, reads.py)
-    o_rd = os.path.join(OBJ, 'dn_reads.o')
-    objs.append(o_rd)
-    if force or _newer(o_rd, [rd] + host_hdr):
-        jobs.append([hipcc] + FLAGS + ['-c', rd, '-o', o_rd])
-    inf = os.path.join(CSRC, 'dn_inflate.hip')          # BGZF blocks -> inflated bytes (NativeBamReadsProcessor inflate='device', bam.py)
-    o_inf = os.path.join(OBJ, 'dn_inflate.o')
-    objs.append(o_inf)
-    if force or _newer(o_inf, [inf] + host_hdr):
-        jobs.append([hipcc] + FLAGS + ['-c', inf, '-o', o_inf])
-    dfl = os.path.join(CSRC, 'dn_deflate.hip')          # byte ranges -> BGZF blocks (bam.bgzf_deflate, bam.sort_bam deflate='native')
-    o_dfl = os.path.join(OBJ, 'dn_deflate.o')
-    objs.append(o_dfl)
-    if force or _newer(o_dfl, [dfl] + host_hdr):
-        jobs.append([hipcc] + FLAGS + ['-c', dfl, '-o', o_dfl])
-    frm = os.path.join(CSRC, 'dn_frame.hip')            # inflated BAM bytes -> record offsets (NativeBamReadsProcessor frame='device', bam.py)
-    o_frm = os.path.join(OBJ, 'dn_frame.o')
-    objs.append(o_frm)
-    if force or _newer(o_frm, [frm] + host_hdr):
-        jobs.append([hipcc] + FLAGS + ['-c', frm, '-o', o_frm])
-    bai = os.path.join(CSRC, 'dn_bai.hip')              # BAM records -> .bai index (bam.build_index)
-    o_bai = os.path.join(OBJ, 'dn_bai.o')
-    objs.append(o_bai)
-    if force or _newer(o_bai, [bai] + host_hdr):
-        jobs.append([hipcc] + FLAGS + ['-c', bai, '-o', o_bai])
-    srt = os.path.join(CSRC, 'dn_sort.hip')             # BAM records -> the coordinate-sorted record stream (bam.sort_bam)
-    o_srt = os.path.join(OBJ, 'dn_sort.o')
-    objs.append(o_srt)
-    if force or _newer(o_srt, [srt] + host_hdr):
-        jobs.append([hipcc] + FLAGS + ['-c', srt, '-o', o_srt])
-    gtf = os.path.join(CSRC, 'dn_gtf.hip')              # GTF bytes -> exon table (GeneAnnotationLoader, loaders.py)
-    o_gtf = os.path.join(OBJ, 'dn_gtf.o')
-    objs.append(o_gtf)
-    if force or _newer(o_gtf, [gtf] + host_hdr):
-        jobs.append([hipcc] + FLAGS + ['-c', gtf, '-o', o_gtf])
+    for unit in HOST_UNITS:
+        src, o = os.path.join(CSRC, unit + '.hip'), os.path.join(OBJ, unit + '.o')
+        objs.append(o)
+        if force or _newer(o, [src] + host_hdr):
+            jobs.append([hipcc] + FLAGS + ['-c', src, '-o', o])
     api = os.path.join(CSRC, 'dn_api.hip')
     o_api =os.path.join(OBJ, 'dn_api.o')
     objs.append(o_api)

@@ -7,7 +7,7 @@
 //             (refID, bin) key and the record's virtual offset -- a binary search of the window's piece table, which says for
 //             every stretch of window bytes which block (file offset) and which byte of it they are; carried bytes keep the
 //             pieces of the blocks they came from -- and checks order against the record before (the window's first record
-//             against the carried state of the last record of the window before).  The first error wins (atomicMin)
+//             against the carried state of the last record of the window before).  The first error wins (dn::note_error)
 //   max-scan  within a reference records are sorted, so the smallest vbeg over a 16 kb window of the linear index is that
 //             of the first record in file order that overlaps it.  With E(r) the largest (end - 1) >> 14 of the reference's
 //             earlier records, record r claims the windows max(beg >> 14, E(r) + 1) .. (end - 1) >> 14.  refID does not
@@ -21,8 +21,9 @@
 // one run; a run ends where the next begins), and dn_bai_finish sorts the runs by key (stably: file order within a bin),
 // joins chunks that touch in one block, and fills the linear index.
 //
-// The three per-record steps are __host__ __device__ functions; the _host entry points run them in plain loops on bytes the
-// caller inflated, under the same stitch, so the index is testable without a device.
+// The three per-record steps are __host__ __device__ functions on the record view of dn_bam_record.hpp.  The steps of a
+// window are written once (run_window) over two backends: DeviceIndex queues kernels and hipcub scans on the window where it
+// was inflated, HostIndex runs plain loops on bytes the caller inflated, so the index is testable without a device.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <stdint.h>
@@ -34,14 +35,17 @@
 #include "dn_host.hpp"
 #include "dn_inflate.hpp"
 #include "dn_frame.hpp"
-
-#define DN_HD __host__ __device__ __forceinline__
+#include "dn_bam_record.hpp"
 
 namespace {
 
+using dn::kUnplaced;
+using dn::le32;
+using dn::ref_key;
+
 constexpr int kNT = 256;
 constexpr int64_t kMaxCoord = (int64_t) 1 << 29;
-constexpr uint32_t kUnplaced = 0xffffffffu;        // the reference part of the key of a record with refID < 0
+constexpr int64_t kGridCap = 1 << 20;
 
 enum { kBaiOk = 0, kBaiShape = 1, kBaiRef = 2, kBaiRefOrder = 3, kBaiPosOrder = 4, kBaiRange = 5, kBaiOffset = 6 };
 
@@ -81,14 +85,6 @@ struct Recs {
     int32_t *cf, *cf_sum;                        // claim flag, and its exclusive sum
 };
 
-DN_HD uint32_t b_u16(const uint8_t *p) { return (uint32_t) p[0] | ((uint32_t) p[1] << 8); }
-DN_HD uint32_t b_u32(const uint8_t *p)
-{
-    return (uint32_t) p[0] | ((uint32_t) p[1] << 8) | ((uint32_t) p[2] << 16) | ((uint32_t) p[3] << 24);
-}
-
-DN_HD uint32_t ref_key(int32_t ref) { return ref < 0 ? kUnplaced : (uint32_t) ref; }
-
 // SAM specification 5.3; 0 <= beg < end <= 2^29
 DN_HD uint32_t reg2bin(int64_t beg, int64_t end)
 {
@@ -119,15 +115,15 @@ DN_HD int bai_record(const uint8_t *w, int64_t n_bytes, const int64_t *rec_off, 
 {
     const int64_t o = rec_off[i];
     R.key[i] = (uint64_t) kUnplaced << 32; R.vbeg[i] = 0; R.emax_in[i] = 0; R.win[i] = 0; R.fl[i] = 0;
-    if (o < 0 || o + 36 > n_bytes) return kBaiShape;
-    const int64_t bs = (int32_t) b_u32(w + o), l_name = w[o + 12], n_cig = b_u16(w + o + 16);
-    if (bs < 32 || o + 4 + bs > n_bytes || 32 + l_name + 4 * n_cig > bs) return kBaiShape;
-    const int32_t ref = (int32_t) b_u32(w + o + 4), pos = (int32_t) b_u32(w + o + 8);
-    const uint32_t flag = b_u16(w + o + 18);
+    dn::BamHead H;
+    if (!dn::bam_head(w, n_bytes, o, H) || !H.names_fit()) return kBaiShape;
+    const int32_t ref = H.ref, pos = H.pos;
+    const uint32_t flag = H.flag;
+    const int64_t n_cig = H.n_cig;
     int64_t rlen = 0;
-    const uint8_t *c = w + o + 36 + l_name;
+    const uint8_t *c = w + H.cigar();
     for (int64_t k = 0; k < n_cig; k++) {
-        const uint32_t op = b_u32(c + 4 * k), code = op & 15;
+        const uint32_t op = le32(c + 4 * k), code = op & 15;
         if (code == 0 || code == 2 || code == 3 || code == 7 || code == 8) rlen += op >> 4;
     }
     if ((flag & 4) || n_cig == 0 || rlen == 0) rlen = 1;
@@ -149,8 +145,8 @@ DN_HD int bai_record(const uint8_t *w, int64_t n_bytes, const int64_t *rec_off, 
     int32_t pref = cin.ref, ppos = cin.pos;
     if (i > 0) {
         const int64_t po = rec_off[i - 1];
-        has_prev = po >= 0 && po + 12 <= n_bytes;
-        if (has_prev) { pref = (int32_t) b_u32(w + po + 4); ppos = (int32_t) b_u32(w + po + 8); }
+        has_prev = po >= 0 && po + dn::kBamPosEnd <= n_bytes;
+        if (has_prev) { pref = (int32_t) le32(w + po + dn::kBamRef); ppos = (int32_t) le32(w + po + dn::kBamPos); }
     }
     if (ref >= n_ref) return kBaiRef;
     if (has_prev && rk < ref_key(pref)) return kBaiRefOrder;
@@ -199,7 +195,7 @@ DN_HD void bai_scatter_pass(const uint8_t *w, const int64_t *rec_off, const Recs
         const int64_t o = rec_off[i];
         uint64_t e = R.emax[i];
         if (cin.any && cin.emax > e) e = cin.emax;
-        *cout = Carry{R.key[i], e, (int32_t) b_u32(w + o + 4), (int32_t) b_u32(w + o + 8), 1, 0};
+        *cout = Carry{R.key[i], e, (int32_t) le32(w + o + dn::kBamRef), (int32_t) le32(w + o + dn::kBamPos), 1, 0};
     }
 }
 
@@ -210,7 +206,7 @@ __global__ __launch_bounds__(kNT) void k_bai_records(const uint8_t *__restrict__
     const Carry c = *cin;
     for (int64_t i = (int64_t) blockIdx.x * kNT + threadIdx.x; i < n_rec; i += (int64_t) gridDim.x * kNT) {
         const int e = bai_record(w, n_bytes, rec_off, i, pc, n_pieces, n_ref, c, R);
-        if (e != kBaiOk) atomicMin(err, (unsigned long long) i << 3 | (unsigned long long) e);
+        if (e != kBaiOk) dn::note_error(err, i, e);
     }
 }
 
@@ -229,12 +225,6 @@ __global__ __launch_bounds__(kNT) void k_bai_scatter(const uint8_t *__restrict__
         bai_scatter_pass(w, rec_off, R, i, n_rec, c, heads, claims, tot, cout);
 }
 
-inline unsigned grid_for(int64_t n)
-{
-    const int64_t g = (n + kNT - 1) / kNT;
-    return (unsigned) (g < 1 ? 1 : g > (1 << 20) ? (1 << 20) : g);
-}
-
 struct Run {
     uint64_t key, vbeg, vend;
     int64_t n, n_unmapped;
@@ -251,14 +241,14 @@ struct dn_bai_s {
     std::vector<Piece> carry_pieces;   // of the record cut by the end of the window before, rebased to offset 0
     std::vector<Run> runs;             // in file order
     std::vector<Claim> claims;
-    // the host build: the carried bytes and the carried state
+    // HostIndex: the bytes of the record cut by the end of the window before, and the carried state
     std::vector<uint8_t> h_carry;
     Carry h_state{0, 0, 0, 0, 0, 0};
-    // the device path
+    // DeviceIndex
     dn::Stream st;
     dn::GrowBuffer<uint8_t> win;
     dn::InflateWindow ingest;          // of dn_bai_window; armed by dn_bai_expect_crc
-    dn::DeviceCarry carry;             // carry.n is the carried length in both builds; the host build's bytes are h_carry
+    dn::DeviceCarry carry;             // the bytes of the record cut by the end of the window before
     dn::GrowBuffer<int64_t> rec_off;
     dn::GrowBuffer<Piece> pieces;
     dn::GrowBuffer<uint64_t> key, vbeg, emax_in, emax, hs, hs_sum;
@@ -278,17 +268,18 @@ struct dn_bai_s {
     std::vector<int32_t> ref_n_bin, ref_n_intv, bin_id, bin_n_chunk;
     std::vector<uint64_t> ref_pseudo, chunks, ioffset;
     int64_t n_no_coor = 0;
+
+    int64_t carried() const { return device < 0 ? (int64_t) h_carry.size() : carry.n; }
 };
 
 namespace {
 
 int record_error(dn_bai h, int code, int64_t idx, int32_t ref, int32_t pos)
 {
-    const std::string who = "record " + std::to_string(h->n_records + idx) + " (refID " + std::to_string(ref) + ", position " + std::to_string(pos) + ")";
-    h->failed = true;
+    const std::string who = dn::record_name(h->n_records + idx, ref, pos);
     switch (code) {
-    case kBaiShape: return dn::fail(DN_E_INVALID, "malformed BAM " + who + ": its read name and CIGAR do not fit inside the record");
-    case kBaiRef: return dn::fail(DN_E_INVALID, who + " names a reference the header does not have (" + std::to_string(h->n_ref) + " references)");
+    case kBaiShape: return dn::record_shape_error(who);
+    case kBaiRef: return dn::record_reference_error(who, h->n_ref);
     case kBaiRefOrder: return dn::fail(DN_E_INVALID, "BAM file is not sorted by coordinate: " + who + " follows a record of a later reference");
     case kBaiPosOrder: return dn::fail(DN_E_INVALID, "BAM file is not sorted by coordinate: " + who + " follows a larger position of the same reference");
     case kBaiRange: return dn::fail(DN_E_INVALID, who + " reaches beyond position 2^29: a .bai index cannot hold it");
@@ -342,70 +333,209 @@ void absorb(dn_bai h, int64_t n_rec, const Totals &tot, const Head *heads, const
     h->n_records += n_rec;
 }
 
-int check_handle(dn_bai h, const char *who, bool device)
-{
-    if (!h || (h->device >= 0) != device) return dn::fail(DN_E_INVALID, std::string(who) + ": bad argument");
-    if (h->failed || h->finished) return dn::fail(DN_E_STATE, std::string(who) + ": the index is finished or has failed");
-    return DN_OK;
-}
+// One window on the host: plain loops over the bytes the caller inflated, behind those carried from the window before
+struct HostIndex {
+    dn_bai h;
+    std::vector<uint8_t> win;
+    std::vector<int64_t> off;
+    std::vector<uint64_t> key, vbeg, emax_in, emax, hs, hs_sum;
+    std::vector<uint32_t> rwin;
+    std::vector<uint8_t> fl;
+    std::vector<int32_t> cf, cf_sum;
+    Recs R{};
+    Carry next{0, 0, 0, 0, 0, 0};
+    std::vector<Head> heads;
+    std::vector<Claim> cl;
+    Totals tot{0, 0, 0};
 
-// the index kernels on the n_rec records of the window h->win (n_bytes), whose offsets are in h->rec_off
-int index_window(dn_bai h, int64_t n_bytes, int64_t n_rec, const std::vector<Piece> &pc, std::vector<Head> &heads, std::vector<Claim> &cl,
-                 Totals &tot, unsigned long long &h_err, int64_t &h_off, uint8_t *h_rec)
-{
-    hipStream_t st = h->st;
-    DN_TRY(h->pieces.reserve((int64_t) pc.size(), 0, st));
-    DN_TRY(h->key.reserve(n_rec, 0, st)); DN_TRY(h->vbeg.reserve(n_rec, 0, st)); DN_TRY(h->emax_in.reserve(n_rec, 0, st));
-    DN_TRY(h->emax.reserve(n_rec, 0, st)); DN_TRY(h->hs.reserve(n_rec, 0, st)); DN_TRY(h->hs_sum.reserve(n_rec, 0, st));
-    DN_TRY(h->rwin.reserve(n_rec, 0, st)); DN_TRY(h->fl.reserve(n_rec, 0, st)); DN_TRY(h->cf.reserve(n_rec, 0, st));
-    DN_TRY(h->cf_sum.reserve(n_rec, 0, st)); DN_TRY(h->heads.reserve(n_rec, 0, st)); DN_TRY(h->d_claims.reserve(n_rec, 0, st));
-    const Recs R{h->key.get(), h->vbeg.get(), h->emax_in.get(), h->emax.get(), h->rwin.get(), h->fl.get(), h->hs.get(), h->hs_sum.get(),
-                 h->cf.get(), h->cf_sum.get()};
-    const Carry *cin = h->state.get() + h->parity;
-    Carry *cout = h->state.get() + (h->parity ^ 1);
-    const unsigned grid = grid_for(n_rec);
-    DN_TRY(hipMemcpyAsync(h->pieces, pc.data(), sizeof(Piece) * pc.size(), hipMemcpyHostToDevice, st));
-    DN_TRY(hipMemsetAsync(h->err, 0xff, sizeof(unsigned long long), st));
-    DN_TRY(hipEventRecord(h->ev2, st));
-    hipLaunchKernelGGL(k_bai_records, dim3(grid), dim3(kNT), 0, st, (const uint8_t *) h->win.get(), n_bytes, (const int64_t *) h->rec_off.get(), n_rec,
-                       (const Piece *) h->pieces.get(), (int32_t) pc.size(), h->n_ref, cin, R, h->err.get());
-    DN_TRY(hipGetLastError());
-    DN_TRY(hipMemcpyAsync(&h_err, h->err, sizeof(h_err), hipMemcpyDeviceToHost, st));
-    DN_TRY(hipStreamSynchronize(st));
-    if (h_err != ~0ull) {
-        const int64_t idx = (int64_t) (h_err >> 3);
-        DN_TRY(hipMemcpyAsync(&h_off, h->rec_off + idx, sizeof(h_off), hipMemcpyDeviceToHost, st));
-        DN_TRY(hipStreamSynchronize(st));
-        int32_t ref = -1, pos = -1;
-        if (h_off >= 0 && h_off + 12 <= n_bytes) {
-            DN_TRY(hipMemcpyAsync(h_rec, h->win + h_off, 12, hipMemcpyDeviceToHost, st));
-            DN_TRY(hipStreamSynchronize(st));
-            ref = (int32_t) b_u32(h_rec + 4);
-            pos = (int32_t) b_u32(h_rec + 8);
-        }
-        return record_error(h, (int) (h_err & 7), idx, ref, pos);
+    HostIndex(dn_bai h_, const uint8_t *data, int64_t n_data) : h(h_), win(h_->h_carry)
+    {
+        win.insert(win.end(), data, data + n_data);
+        win.resize(win.size() + 16);                                    // as the device buffers: slack behind the window
     }
-    DN_TRY(h->scratch.run([&](void *tmp, size_t &bytes) {
-        return hipcub::DeviceScan::InclusiveScan(tmp, bytes, R.emax_in, R.emax, hipcub::Max(), (int) n_rec, st);
-    }));
-    hipLaunchKernelGGL(k_bai_flags, dim3(grid), dim3(kNT), 0, st, n_rec, cin, R);
-    DN_TRY(hipGetLastError());
-    DN_TRY(h->scratch.run([&](void *tmp, size_t &bytes) { return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, R.hs, R.hs_sum, (int) n_rec, st); }));
-    DN_TRY(h->scratch.run([&](void *tmp, size_t &bytes) { return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, R.cf, R.cf_sum, (int) n_rec, st); }));
-    hipLaunchKernelGGL(k_bai_scatter, dim3(grid), dim3(kNT), 0, st, (const uint8_t *) h->win.get(), (const int64_t *) h->rec_off.get(), n_rec, cin, R,
-                       h->heads.get(), h->d_claims.get(), h->totals.get(), cout);
-    DN_TRY(hipGetLastError());
-    DN_TRY(hipEventRecord(h->ev3, st));
-    DN_TRY(hipMemcpyAsync(&tot, h->totals, sizeof(Totals), hipMemcpyDeviceToHost, st));
-    DN_TRY(hipStreamSynchronize(st));
-    if (tot.heads < 0 || tot.heads > n_rec || tot.claims < 0 || tot.claims > n_rec) return dn::fail(DN_E_STATE, "dn_bai_window: table sizes outside the window");
-    heads.resize((size_t) tot.heads);
-    cl.resize((size_t) tot.claims);
-    if (tot.heads > 0) DN_TRY(hipMemcpyAsync(heads.data(), h->heads, sizeof(Head) * heads.size(), hipMemcpyDeviceToHost, st));
-    if (tot.claims > 0) DN_TRY(hipMemcpyAsync(cl.data(), h->d_claims, sizeof(Claim) * cl.size(), hipMemcpyDeviceToHost, st));
-    DN_TRY(hipStreamSynchronize(st));
-    h->parity ^= 1;
-    return DN_OK;
+    int frame(int64_t total, int64_t &nr, int64_t &consumed, int64_t &fixups)
+    {
+        off.resize((size_t) (total / dn::kBamName + 2));
+        return dn_bam_frame_segments_host(win.data(), total, -1, nullptr, h->segment, off.data(), (int64_t) off.size(), &nr, &consumed, &fixups);
+    }
+    // stops at the first faulty record
+    int records(int64_t total, int64_t nr, const std::vector<Piece> &pc, unsigned long long &e, int32_t &ref, int32_t &pos)
+    {
+        const size_t n = (size_t) nr;
+        key.resize(n); vbeg.resize(n); emax_in.resize(n); emax.resize(n); hs.resize(n); hs_sum.resize(n);
+        rwin.resize(n); fl.resize(n); cf.resize(n); cf_sum.resize(n);
+        R = Recs{key.data(), vbeg.data(), emax_in.data(), emax.data(), rwin.data(), fl.data(), hs.data(), hs_sum.data(), cf.data(), cf_sum.data()};
+        for (int64_t i = 0; i < nr && e == dn::kNoError; i++) {
+            const int code = bai_record(win.data(), total, off.data(), i, pc.data(), (int32_t) pc.size(), h->n_ref, h->h_state, R);
+            if (code != kBaiOk) dn::note_error(&e, i, code);
+        }
+        if (e != dn::kNoError) dn::error_record_host(off.data(), dn::error_ordinal(e), win.data(), total, ref, pos);
+        return DN_OK;
+    }
+    int max_scan(int64_t nr)
+    {
+        for (size_t i = 0; i < (size_t) nr; i++) emax[i] = i > 0 && emax[i - 1] > emax_in[i] ? emax[i - 1] : emax_in[i];
+        return DN_OK;
+    }
+    int flags(int64_t nr)
+    {
+        for (int64_t i = 0; i < nr; i++) bai_flag_pass(R, i, h->h_state);
+        return DN_OK;
+    }
+    int sums(int64_t nr)
+    {
+        uint64_t s = 0;
+        int32_t c = 0;
+        for (size_t i = 0; i < (size_t) nr; i++) { hs_sum[i] = s; s += hs[i]; cf_sum[i] = c; c += cf[i]; }
+        heads.resize((size_t) (uint32_t) s);
+        cl.resize((size_t) c);
+        return DN_OK;
+    }
+    int scatter(int64_t nr)
+    {
+        for (int64_t i = 0; i < nr; i++) bai_scatter_pass(win.data(), off.data(), R, i, nr, h->h_state, heads.data(), cl.data(), &tot, &next);
+        return DN_OK;
+    }
+    int fetch(int64_t)
+    {
+        h->h_state = next;
+        return DN_OK;
+    }
+    int keep(int64_t consumed, int64_t total)
+    {
+        h->h_carry.assign(win.begin() + consumed, win.begin() + total);
+        return DN_OK;
+    }
+};
+
+// The same on the device, on the window h->win and the offsets h->rec_off.  What queued copies write lives in this object,
+// which dn_bai_window declares outside the body it hands to dn::synced.
+struct DeviceIndex {
+    dn_bai h;
+    unsigned long long h_err = dn::kNoError;
+    dn::ErrorProbe probe;
+    Recs R{};
+    const Carry *cin = nullptr;
+    Carry *cout = nullptr;
+    unsigned grid = 1;
+    std::vector<Head> heads;
+    std::vector<Claim> cl;
+    Totals tot{0, 0, 0};
+    double frame_ms = 0.0, index_ms = 0.0;
+
+    int frame(int64_t total, int64_t &nr, int64_t &consumed, int64_t &fixups)
+    {
+        dn::FrameResult F;
+        const int rc = dn::frame_window(h->st, h->frame, h->win, total, -1, nullptr, h->segment, -1, h->rec_off, F);
+        nr = F.n_rec; consumed = F.consumed; fixups = F.n_fixups;
+        frame_ms = F.device_ms;
+        return rc;
+    }
+    // reports an error after the pass over the whole window
+    int records(int64_t total, int64_t nr, const std::vector<Piece> &pc, unsigned long long &e, int32_t &ref, int32_t &pos)
+    {
+        hipStream_t st = h->st;
+        DN_TRY(h->pieces.reserve((int64_t) pc.size(), 0, st));
+        DN_TRY(h->key.reserve(nr, 0, st)); DN_TRY(h->vbeg.reserve(nr, 0, st)); DN_TRY(h->emax_in.reserve(nr, 0, st));
+        DN_TRY(h->emax.reserve(nr, 0, st)); DN_TRY(h->hs.reserve(nr, 0, st)); DN_TRY(h->hs_sum.reserve(nr, 0, st));
+        DN_TRY(h->rwin.reserve(nr, 0, st)); DN_TRY(h->fl.reserve(nr, 0, st)); DN_TRY(h->cf.reserve(nr, 0, st));
+        DN_TRY(h->cf_sum.reserve(nr, 0, st)); DN_TRY(h->heads.reserve(nr, 0, st)); DN_TRY(h->d_claims.reserve(nr, 0, st));
+        R = Recs{h->key.get(), h->vbeg.get(), h->emax_in.get(), h->emax.get(), h->rwin.get(), h->fl.get(), h->hs.get(), h->hs_sum.get(),
+                 h->cf.get(), h->cf_sum.get()};
+        cin = h->state.get() + h->parity;
+        cout = h->state.get() + (h->parity ^ 1);
+        grid = dn::grid_for(nr, kNT, kGridCap);
+        DN_TRY(hipMemcpyAsync(h->pieces, pc.data(), sizeof(Piece) * pc.size(), hipMemcpyHostToDevice, st));
+        DN_TRY(hipMemsetAsync(h->err, 0xff, sizeof(unsigned long long), st));
+        DN_TRY(hipEventRecord(h->ev2, st));
+        hipLaunchKernelGGL(k_bai_records, dim3(grid), dim3(kNT), 0, st, (const uint8_t *) h->win.get(), total, (const int64_t *) h->rec_off.get(), nr,
+                           (const Piece *) h->pieces.get(), (int32_t) pc.size(), h->n_ref, cin, R, h->err.get());
+        DN_TRY(hipGetLastError());
+        DN_TRY(hipMemcpyAsync(&h_err, h->err, sizeof(h_err), hipMemcpyDeviceToHost, st));
+        DN_TRY(hipStreamSynchronize(st));
+        e = h_err;
+        return e == dn::kNoError ? DN_OK : dn::error_record_device(st, h->rec_off, dn::error_ordinal(e), h->win, total, probe, ref, pos);
+    }
+    int max_scan(int64_t nr)
+    {
+        DN_TRY(h->scratch.run([&](void *tmp, size_t &bytes) {
+            return hipcub::DeviceScan::InclusiveScan(tmp, bytes, R.emax_in, R.emax, hipcub::Max(), (int) nr, h->st);
+        }));
+        return DN_OK;
+    }
+    int flags(int64_t nr)
+    {
+        hipLaunchKernelGGL(k_bai_flags, dim3(grid), dim3(kNT), 0, h->st, nr, cin, R);
+        DN_TRY(hipGetLastError());
+        return DN_OK;
+    }
+    int sums(int64_t nr)
+    {
+        DN_TRY(h->scratch.run([&](void *tmp, size_t &bytes) { return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, R.hs, R.hs_sum, (int) nr, h->st); }));
+        DN_TRY(h->scratch.run([&](void *tmp, size_t &bytes) { return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, R.cf, R.cf_sum, (int) nr, h->st); }));
+        return DN_OK;
+    }
+    int scatter(int64_t nr)
+    {
+        hipLaunchKernelGGL(k_bai_scatter, dim3(grid), dim3(kNT), 0, h->st, (const uint8_t *) h->win.get(), (const int64_t *) h->rec_off.get(), nr, cin, R,
+                           h->heads.get(), h->d_claims.get(), h->totals.get(), cout);
+        DN_TRY(hipGetLastError());
+        DN_TRY(hipEventRecord(h->ev3, h->st));
+        return DN_OK;
+    }
+    // the two tables and their sizes come to the host; index_ms: around the index kernels
+    int fetch(int64_t nr)
+    {
+        hipStream_t st = h->st;
+        DN_TRY(hipMemcpyAsync(&tot, h->totals, sizeof(Totals), hipMemcpyDeviceToHost, st));
+        DN_TRY(hipStreamSynchronize(st));
+        if (tot.heads < 0 || tot.heads > nr || tot.claims < 0 || tot.claims > nr) return dn::fail(DN_E_STATE, "dn_bai_window: table sizes outside the window");
+        heads.resize((size_t) tot.heads);
+        cl.resize((size_t) tot.claims);
+        if (tot.heads > 0) DN_TRY(hipMemcpyAsync(heads.data(), h->heads, sizeof(Head) * heads.size(), hipMemcpyDeviceToHost, st));
+        if (tot.claims > 0) DN_TRY(hipMemcpyAsync(cl.data(), h->d_claims, sizeof(Claim) * cl.size(), hipMemcpyDeviceToHost, st));
+        DN_TRY(hipStreamSynchronize(st));
+        h->parity ^= 1;
+        float ms = 0.f;
+        DN_TRY(hipEventElapsedTime(&ms, h->ev2, h->ev3));
+        index_ms = ms;
+        return DN_OK;
+    }
+    int keep(int64_t consumed, int64_t total)
+    {
+        DN_TRY(h->carry.keep(h->st, h->win, consumed, total));
+        return DN_OK;
+    }
+};
+
+// One window of `total` bytes whose pieces are pc, on either backend: frame it, run the three per-record passes with the
+// scan and the two sums between them, carry the record the window end cuts, and stitch the window's tables onto the
+// handle's.  Whatever fails spends the builder.
+template <class B> int run_window(dn_bai h, B &be, const std::vector<Piece> &pc, int64_t total, int64_t *n_rec)
+{
+    const int rc = [&]() -> int {
+        int64_t nr = 0, consumed = 0, fixups = 0;
+        int rc = be.frame(total, nr, consumed, fixups);
+        h->n_fixups += fixups;
+        if (rc != DN_OK) return rc;
+        if (nr > 0) {
+            unsigned long long e = dn::kNoError;
+            int32_t ref = -1, pos = -1;
+            if ((rc = be.records(total, nr, pc, e, ref, pos)) != DN_OK) return rc;
+            if (e != dn::kNoError) return record_error(h, dn::error_code(e), dn::error_ordinal(e), ref, pos);
+            if ((rc = be.max_scan(nr)) != DN_OK || (rc = be.flags(nr)) != DN_OK || (rc = be.sums(nr)) != DN_OK ||
+                (rc = be.scatter(nr)) != DN_OK || (rc = be.fetch(nr)) != DN_OK)
+                return rc;
+        }
+        if ((rc = be.keep(consumed, total)) != DN_OK) return rc;
+        carry_pieces(h, pc, consumed, total);
+        absorb(h, nr, be.tot, be.heads.data(), be.cl.data());
+        h->n_windows++;
+        *n_rec = nr;
+        return DN_OK;
+    }();
+    if (rc != DN_OK) h->failed = true;
+    return rc;
 }
 
 }  // namespace
@@ -460,19 +590,13 @@ extern "C" int dn_bai_window(dn_bai h, const uint8_t *comp, int64_t n_comp, int6
 {
     dn::clear_error();
     if (h) h->ingest.take();
-    int rc = check_handle(h, "dn_bai_window", true);
+    int rc = dn::check_handle(h, "dn_bai_window", "index", true);
     if (rc != DN_OK) return rc;
     if (n_comp < 0 || (n_comp > 0 && !comp) || n_blocks < 0 || n_blocks > INT32_MAX ||
         (n_blocks > 0 && (!pay_off || !pay_len || !isize || !coffset || !status)) || head_skip < 0 || !n_rec)
         return dn::fail(DN_E_INVALID, "dn_bai_window: bad argument");
     std::vector<Piece> pc(h->carry_pieces);
-    std::vector<Head> heads;
-    std::vector<Claim> cl;
-    Totals tot{0, 0, 0};
-    unsigned long long h_err = ~0ull;
-    int64_t h_off = 0, total = 0;
-    uint8_t h_rec[12] = {0};
-    dn::FrameResult R;
+    int64_t total = 0;
     rc = h->ingest.plan("dn_bai_window", "dn_bai_expect_crc", n_comp, n_blocks, pay_off, pay_len, isize, head_skip, -1, h->carry.n, total);
     for (int64_t b = 0; b < n_blocks && rc == DN_OK; b++) {
         const dn::InflateBlock &B = h->ingest.blk[(size_t) b];
@@ -484,47 +608,31 @@ extern "C" int dn_bai_window(dn_bai h, const uint8_t *comp, int64_t n_comp, int6
     DN_TRY(hipSetDevice(h->device));
     *n_rec = 0;
     if (inflate_ms) *inflate_ms = 0.0;
-    if (frame_ms) *frame_ms = 0.0;
-    if (index_ms) *index_ms = 0.0;
-    return dn::synced(st, [&]() -> int {
+    DeviceIndex be{h};
+    rc = dn::synced(st, [&]() -> int {
         DN_TRY(h->win.reserve(total, 0, st));
         DN_TRY(h->carry.put(st, h->win));                   // the record cut by the end of the window before goes first
         bool ok = true;
         const int wrc = h->ingest.run(st, comp, n_comp, h->win, status, inflate_ms, ok);
         if (wrc != DN_OK) return wrc;
-        if (!ok) { h->failed = true; return DN_OK; }
-        const int frc = dn::frame_window(st, h->frame, h->win, total, -1, nullptr, h->segment, -1, h->rec_off, R);
-        h->n_fixups += R.n_fixups;
-        if (frame_ms) *frame_ms = R.device_ms;
-        if (frc != DN_OK) { h->failed = true; return frc; }
-        if (R.n_rec > 0) {
-            const int irc = index_window(h, total, R.n_rec, pc, heads, cl, tot, h_err, h_off, h_rec);
-            if (irc != DN_OK) { h->failed = true; return irc; }
-            if (index_ms) {
-                float ms = 0.f;
-                DN_TRY(hipEventElapsedTime(&ms, h->ev2, h->ev3));
-                *index_ms = ms;
-            }
-        }
-        DN_TRY(h->carry.keep(st, h->win, R.consumed, total));
-        carry_pieces(h, pc, R.consumed, total);
-        absorb(h, R.n_rec, tot, heads.data(), cl.data());
-        h->n_windows++;
-        *n_rec = R.n_rec;
-        return DN_OK;
+        if (!ok) { h->failed = true; return DN_OK; }        // the caller reads the statuses
+        return run_window(h, be, pc, total, n_rec);
     });
+    if (frame_ms) *frame_ms = be.frame_ms;
+    if (index_ms) *index_ms = be.index_ms;
+    return rc;
 }
 
 extern "C" int dn_bai_window_host(dn_bai h, const uint8_t *data, int64_t n_data, int64_t n_blocks, const int32_t *isize, const int64_t *coffset,
                                   int32_t head_skip, int64_t *n_rec)
 {
     dn::clear_error();
-    int rc = check_handle(h, "dn_bai_window_host", false);
+    int rc = dn::check_handle(h, "dn_bai_window_host", "index", false);
     if (rc != DN_OK) return rc;
     if (n_data < 0 || (n_data > 0 && !data) || n_blocks < 0 || (n_blocks > 0 && (!isize || !coffset)) || head_skip < 0 || !n_rec)
         return dn::fail(DN_E_INVALID, "dn_bai_window_host: bad argument");
     std::vector<Piece> pc(h->carry_pieces);
-    int64_t total = h->carry.n, sum = 0, skip = 0;
+    int64_t total = h->carried(), sum = 0, skip = 0;
     for (int64_t b = 0; b < n_blocks; b++) {
         if (isize[b] < 0) return dn::fail(DN_E_INVALID, "dn_bai_window_host: block " + std::to_string(b) + " has a negative inflated size");
         int32_t lo, keep;
@@ -536,50 +644,8 @@ extern "C" int dn_bai_window_host(dn_bai h, const uint8_t *data, int64_t n_data,
     }
     if (total > INT32_MAX) return dn::window_size_error("dn_bai_window_host");
     if (sum != n_data) return dn::fail(DN_E_INVALID, "dn_bai_window_host: the blocks' sizes do not add up to n_data");
-    std::vector<uint8_t> win(h->h_carry);
-    win.insert(win.end(), data + skip, data + n_data);
-    win.resize(win.size() + 16);                                       // as the device buffers: slack behind the window
-    std::vector<int64_t> off((size_t) (total / 36 + 2));
-    int64_t nr = 0, consumed = 0, fix = 0;
-    rc = dn_bam_frame_segments_host(win.data(), total, -1, nullptr, h->segment, off.data(), (int64_t) off.size(), &nr, &consumed, &fix);
-    h->n_fixups += fix;
-    if (rc != DN_OK) { h->failed = true; return rc; }
-    std::vector<Head> heads;
-    std::vector<Claim> cl;
-    Totals tot{0, 0, 0};
-    if (nr > 0) {
-        const size_t n = (size_t) nr;
-        std::vector<uint64_t> key(n), vbeg(n), emax_in(n), emax(n), hs(n), hs_sum(n);
-        std::vector<uint32_t> rwin(n);
-        std::vector<uint8_t> fl(n);
-        std::vector<int32_t> cf(n), cf_sum(n);
-        const Recs R{key.data(), vbeg.data(), emax_in.data(), emax.data(), rwin.data(), fl.data(), hs.data(), hs_sum.data(), cf.data(), cf_sum.data()};
-        for (int64_t i = 0; i < nr; i++) {
-            const int e = bai_record(win.data(), total, off.data(), i, pc.data(), (int32_t) pc.size(), h->n_ref, h->h_state, R);
-            if (e != kBaiOk) {
-                const int64_t o = off[(size_t) i];
-                const bool in = o >= 0 && o + 12 <= total;
-                return record_error(h, e, i, in ? (int32_t) b_u32(win.data() + o + 4) : -1, in ? (int32_t) b_u32(win.data() + o + 8) : -1);
-            }
-        }
-        for (size_t i = 0; i < n; i++) emax[i] = i > 0 && emax[i - 1] > emax_in[i] ? emax[i - 1] : emax_in[i];
-        for (int64_t i = 0; i < nr; i++) bai_flag_pass(R, i, h->h_state);
-        uint64_t s = 0;
-        int32_t c = 0;
-        for (size_t i = 0; i < n; i++) { hs_sum[i] = s; s += hs[i]; cf_sum[i] = c; c += cf[i]; }
-        heads.resize((size_t) (uint32_t) s);
-        cl.resize((size_t) c);
-        Carry next = h->h_state;
-        for (int64_t i = 0; i < nr; i++) bai_scatter_pass(win.data(), off.data(), R, i, nr, h->h_state, heads.data(), cl.data(), &tot, &next);
-        h->h_state = next;
-    }
-    h->h_carry.assign(win.begin() + consumed, win.begin() + total);
-    h->carry.n = total - consumed;
-    carry_pieces(h, pc, consumed, total);
-    absorb(h, nr, tot, heads.data(), cl.data());
-    h->n_windows++;
-    *n_rec = nr;
-    return DN_OK;
+    HostIndex be(h, data + skip, n_data - skip);
+    return run_window(h, be, pc, total, n_rec);
 }
 
 extern "C" int dn_bai_finish(dn_bai h, int64_t end_voffset, int64_t *sizes)
@@ -587,10 +653,9 @@ extern "C" int dn_bai_finish(dn_bai h, int64_t end_voffset, int64_t *sizes)
     dn::clear_error();
     if (!h || !sizes || end_voffset < 0) return dn::fail(DN_E_INVALID, "dn_bai_finish: bad argument");
     if (h->failed || h->finished) return dn::fail(DN_E_STATE, "dn_bai_finish: the index is finished or has failed");
-    if (h->carry.n > 0) {
+    if (h->carried() > 0) {
         h->failed = true;
-        return dn::fail(DN_E_INVALID, "record " + std::to_string(h->n_records) + " is cut by the end of the file (" + std::to_string(h->carry.n) +
-                                      " bytes of it are there)");
+        return dn::record_cut_error(h->n_records, h->carried());
     }
     const size_t n_ref = (size_t) h->n_ref;
     if (!h->runs.empty()) h->runs.back().vend = (uint64_t) end_voffset;

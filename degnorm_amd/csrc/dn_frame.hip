@@ -21,8 +21,8 @@
 //
 // Guess, walk and emit of one segment are __host__ __device__ functions; dn_bam_frame_segments_host runs them in plain
 // loops under the same stitch, so the whole algorithm, fix-ups included, is testable without a device.  Every read is
-// checked against n_bytes first: garbage yields a state, never an access outside the window.  Loads are byte loads, as in
-// dn_reads.hip, because record fields sit at arbitrary offsets.
+// checked against n_bytes first: garbage yields a state, never an access outside the window.  The readers and the offsets
+// of the fixed fields are those of dn_bam_record.hpp; the rules below are this unit's own.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <stdint.h>
@@ -31,19 +31,16 @@
 #include "../../include/degnorm_amd.h"
 #include "dn_host.hpp"
 #include "dn_frame.hpp"
-
-#define DN_HD __host__ __device__ __forceinline__
+#include "dn_bam_record.hpp"
 
 namespace {
 
+using dn::le16;
+using dn::le32;
+
 constexpr int kNT = 256;
 constexpr int kWave = 64;
-
-DN_HD uint32_t f_u16(const uint8_t *p) { return (uint32_t) p[0] | ((uint32_t) p[1] << 8); }
-DN_HD uint32_t f_u32(const uint8_t *p)
-{
-    return (uint32_t) p[0] | ((uint32_t) p[1] << 8) | ((uint32_t) p[2] << 16) | ((uint32_t) p[3] << 24);
-}
+constexpr int64_t kGridCap = 1 << 20;
 
 // The fixed fields of the record at o (o + 36 <= n_bytes is the caller's): of tid, and sized within block_size bs.  Beyond
 // what a record must satisfy, the guess also wants what records of real files satisfy -- a read name of at least one
@@ -52,13 +49,13 @@ DN_HD uint32_t f_u32(const uint8_t *p)
 // that fails them costs a fix-up, never a wrong result.
 DN_HD bool frame_fields_ok(const uint8_t *w, int64_t o, int32_t bs, int32_t tid)
 {
-    const uint8_t *p = w + o + 4;
-    if (tid >= 0 && (int32_t) f_u32(p) != tid) return false;
-    const int64_t l_name = p[8], n_cig = f_u16(p + 12);
-    const int32_t l_seq = (int32_t) f_u32(p + 16);
+    const uint8_t *p = w + o;
+    if (tid >= 0 && (int32_t) le32(p + dn::kBamRef) != tid) return false;
+    const int64_t l_name = p[dn::kBamLName], n_cig = le16(p + dn::kBamNCigar);
+    const int32_t l_seq = (int32_t) le32(p + dn::kBamLSeq);
     if (l_name < 2 || l_seq < 0) return false;
-    if ((int32_t) f_u32(p + 4) < -1 || (int32_t) f_u32(p + 20) < -1 || (int32_t) f_u32(p + 24) < -1) return false;
-    return 32 + l_name + 4 * n_cig + ((int64_t) l_seq + 1) / 2 + l_seq <= bs;
+    if ((int32_t) le32(p + dn::kBamPos) < -1 || (int32_t) le32(p + dn::kBamNextRef) < -1 || (int32_t) le32(p + dn::kBamNextPos) < -1) return false;
+    return dn::kBamMinSize + l_name + 4 * n_cig + ((int64_t) l_seq + 1) / 2 + l_seq <= bs;
 }
 
 constexpr int kFrameLookAhead = 2;      // records behind a candidate whose fixed fields must look right too
@@ -67,17 +64,17 @@ constexpr int kFrameLookAhead = 2;      // records behind a candidate whose fixe
 // whatever of the fixed parts of the kFrameLookAhead records behind it is inside the window passes frame_fields_ok too.
 DN_HD bool frame_plausible(const uint8_t *w, int64_t n_bytes, int64_t p, int32_t tid)
 {
-    if (p < 0 || p + 36 > n_bytes) return false;
-    int32_t bs = (int32_t) f_u32(w + p);
-    if (bs < 32 || p + 4 + (int64_t) bs > n_bytes) return false;
+    if (p < 0 || p + dn::kBamName > n_bytes) return false;
+    int32_t bs = (int32_t) le32(w + p);
+    if (bs < dn::kBamMinSize || p + 4 + (int64_t) bs > n_bytes) return false;
     if (!frame_fields_ok(w, p, bs, tid)) return false;
-    if (w[p + 35 + w[p + 12]] != 0) return false;          // inside the record: 32 + l_read_name <= bs
+    if (w[p + dn::kBamName + w[p + dn::kBamLName] - 1] != 0) return false;    // inside the record: 32 + l_read_name <= bs
     int64_t q = p;
     for (int k = 0; k < kFrameLookAhead; k++) {
         q += 4 + (int64_t) bs;
-        if (q + 36 > n_bytes) return true;
-        bs = (int32_t) f_u32(w + q);
-        if (bs < 32 || !frame_fields_ok(w, q, bs, tid)) return false;
+        if (q + dn::kBamName > n_bytes) return true;
+        bs = (int32_t) le32(w + q);
+        if (bs < dn::kBamMinSize || !frame_fields_ok(w, q, bs, tid)) return false;
     }
     return true;
 }
@@ -90,10 +87,10 @@ DN_HD dn::FrameSeg frame_walk(const uint8_t *w, int64_t n_bytes, int64_t entry, 
     int64_t o = entry;
     while (o < limit) {
         if (o + 4 > n_bytes) { G.state = dn::kFrameTail; break; }
-        const int32_t bs = (int32_t) f_u32(w + o);
-        if (bs < 32) { G.state = dn::kFrameBad; G.bad_bs = bs; break; }
+        const int32_t bs = (int32_t) le32(w + o);
+        if (bs < dn::kBamMinSize) { G.state = dn::kFrameBad; G.bad_bs = bs; break; }
         if (o + 4 + (int64_t) bs > n_bytes) { G.state = dn::kFrameTail; break; }
-        G.last_pos = (int32_t) f_u32(w + o + 8);
+        G.last_pos = (int32_t) le32(w + o + dn::kBamPos);
         G.count++;
         o += 4 + (int64_t) bs;
     }
@@ -109,12 +106,12 @@ DN_HD int64_t frame_emit(const uint8_t *w, int64_t n_bytes, const dn::FrameSeg &
 {
     int64_t o = G.entry, bad = -1;
     for (int32_t i = 0; i < G.count; i++) {
-        if (o < 0 || o + 12 > n_bytes) break;
-        const int32_t bs = (int32_t) f_u32(w + o);
-        if (bs < 32) break;
+        if (o < 0 || o + dn::kBamPosEnd > n_bytes) break;
+        const int32_t bs = (int32_t) le32(w + o);
+        if (bs < dn::kBamMinSize) break;
         rec_off[base + i] = o;
         if (tid >= 0) {
-            const int32_t ref = (int32_t) f_u32(w + o + 4), pos = (int32_t) f_u32(w + o + 8);
+            const int32_t ref = (int32_t) le32(w + o + dn::kBamRef), pos = (int32_t) le32(w + o + dn::kBamPos);
             if ((ref != tid || pos < prev) && bad < 0) bad = base + i;
             prev = pos;
         }
@@ -179,12 +176,6 @@ __global__ __launch_bounds__(kNT) void k_frame_emit(const uint8_t *__restrict__ 
     }
 }
 
-inline unsigned grid_for(int64_t n, int per_block)
-{
-    const int64_t g = (n + per_block - 1) / per_block;
-    return (unsigned) (g < 1 ? 1 : g > (1 << 20) ? (1 << 20) : g);
-}
-
 // the segments walked in a plain loop on the host
 struct HostFrame {
     const uint8_t *w;
@@ -221,8 +212,8 @@ struct HostFrame {
     }
     int record(int64_t i, int32_t &ref, int32_t &pos)
     {
-        ref = (int32_t) f_u32(w + off[(size_t) i] + 4);
-        pos = (int32_t) f_u32(w + off[(size_t) i] + 8);
+        ref = (int32_t) le32(w + off[(size_t) i] + dn::kBamRef);
+        pos = (int32_t) le32(w + off[(size_t) i] + dn::kBamPos);
         return DN_OK;
     }
 };
@@ -240,14 +231,14 @@ struct DeviceFrame {
     std::vector<dn::FramePlan> plan;
     unsigned long long h_err = ~0ull;
     int64_t h_off = 0;
-    uint8_t h_rec[12] = {0};
+    uint8_t h_rec[dn::kBamPosEnd] = {0};
 
     int table()
     {
         DN_TRY(W.seg.reserve(n_seg, 0, st));
-        hipLaunchKernelGGL(k_frame_guess, dim3(grid_for(n_seg, kNT / kWave)), dim3(kNT), 0, st, w, n_bytes, tid, S, n_seg, W.seg.get());
+        hipLaunchKernelGGL(k_frame_guess, dim3(dn::grid_for(n_seg, kNT / kWave, kGridCap)), dim3(kNT), 0, st, w, n_bytes, tid, S, n_seg, W.seg.get());
         DN_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_frame_walk, dim3(grid_for(n_seg, kNT)), dim3(kNT), 0, st, w, n_bytes, S, (int64_t) 0, n_seg, (int64_t) -1, W.seg.get());
+        hipLaunchKernelGGL(k_frame_walk, dim3(dn::grid_for(n_seg, kNT, kGridCap)), dim3(kNT), 0, st, w, n_bytes, S, (int64_t) 0, n_seg, (int64_t) -1, W.seg.get());
         DN_TRY(hipGetLastError());
         DN_TRY(hipMemcpyAsync(T.data(), W.seg, sizeof(dn::FrameSeg) * (size_t) n_seg, hipMemcpyDeviceToHost, st));
         DN_TRY(hipStreamSynchronize(st));
@@ -268,12 +259,12 @@ struct DeviceFrame {
         if (!W.err) DN_TRY(dn::alloc_padded(W.err, 1));
         DN_TRY(hipMemcpyAsync(W.plan, plan.data(), sizeof(dn::FramePlan) * (size_t) n_seg, hipMemcpyHostToDevice, st));
         DN_TRY(hipMemsetAsync(W.err, 0xff, sizeof(unsigned long long), st));
-        hipLaunchKernelGGL(k_frame_counts, dim3(grid_for(n_seg, kNT)), dim3(kNT), 0, st, n_seg, W.seg.get(), W.plan.get(), W.cnt.get());
+        hipLaunchKernelGGL(k_frame_counts, dim3(dn::grid_for(n_seg, kNT, kGridCap)), dim3(kNT), 0, st, n_seg, W.seg.get(), W.plan.get(), W.cnt.get());
         DN_TRY(hipGetLastError());
         DN_TRY(W.scratch.run([&](void *tmp, size_t &bytes) {
             return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, W.cnt.get(), W.base.get(), (int) n_seg, st);
         }));
-        hipLaunchKernelGGL(k_frame_emit, dim3(grid_for(n_seg, kNT)), dim3(kNT), 0, st, w, n_bytes, tid, n_seg, W.seg.get(), W.plan.get(),
+        hipLaunchKernelGGL(k_frame_emit, dim3(dn::grid_for(n_seg, kNT, kGridCap)), dim3(kNT), 0, st, w, n_bytes, tid, n_seg, W.seg.get(), W.plan.get(),
                            W.base.get(), rec_off.get(), W.err.get());
         DN_TRY(hipGetLastError());
         DN_TRY(hipMemcpyAsync(&h_err, W.err, sizeof(h_err), hipMemcpyDeviceToHost, st));
@@ -285,11 +276,11 @@ struct DeviceFrame {
     {
         DN_TRY(hipMemcpyAsync(&h_off, rec_off + i, sizeof(h_off), hipMemcpyDeviceToHost, st));
         DN_TRY(hipStreamSynchronize(st));
-        if (h_off < 0 || h_off + 12 > n_bytes) return dn::fail(DN_E_STATE, "frame_window: record offset outside the window");
+        if (h_off < 0 || h_off + dn::kBamPosEnd > n_bytes) return dn::fail(DN_E_STATE, "frame_window: record offset outside the window");
         DN_TRY(hipMemcpyAsync(h_rec, w + h_off, sizeof(h_rec), hipMemcpyDeviceToHost, st));
         DN_TRY(hipStreamSynchronize(st));
-        ref = (int32_t) f_u32(h_rec + 4);
-        pos = (int32_t) f_u32(h_rec + 8);
+        ref = (int32_t) le32(h_rec + dn::kBamRef);
+        pos = (int32_t) le32(h_rec + dn::kBamPos);
         return DN_OK;
     }
 };

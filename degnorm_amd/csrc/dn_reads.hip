@@ -29,10 +29,12 @@
 #include "dn_host.hpp"
 #include "dn_inflate.hpp"
 #include "dn_frame.hpp"
+#include "dn_bam_record.hpp"
 
 namespace {
 
 constexpr int kNT = 256;
+constexpr int64_t kGridCap = 65536;
 constexpr int kMaxSeg = DN_READS_MAX_SEG;           // match segments per row (per mate)
 constexpr int kMaxPiece = 2 * kMaxSeg + 1;          // a pair's segments plus the wrap piece of the overlap-gene index
 
@@ -330,8 +332,6 @@ struct NonZero {
     __host__ __device__ bool operator()(const int32_t &i) const { return cov[i] != 0; }
 };
 
-inline unsigned grid_for(int64_t n) { const int64_t g = (n + kNT - 1) / kNT; return (unsigned) (g < 1 ? 1 : g > 65536 ? 65536 : g); }
-
 // k_cigar_debug on n rows whose CIGARs are already on the device (`cig`); pos and the outputs are host arrays.
 template <class C>
 int cigar_debug(hipStream_t st, int64_t n, const int64_t *pos, C cig, int32_t max_seg, int32_t *nseg, int64_t *bounds, int64_t *end_pos)
@@ -342,7 +342,7 @@ int cigar_debug(hipStream_t st, int64_t n, const int64_t *pos, C cig, int32_t ma
         DN_TRY(alloc_padded(d_pos, n)); DN_TRY(alloc_padded(d_n, n)); DN_TRY(alloc_padded(d_b, n * 2 * max_seg)); DN_TRY(alloc_padded(d_end, n));
         DN_TRY(hipMemcpyAsync(d_pos, pos, sizeof(int64_t) * (size_t) n, hipMemcpyHostToDevice, st));
         DN_TRY(hipMemsetAsync(d_b, 0, sizeof(int64_t) * (size_t) (n * 2 * max_seg), st));
-        hipLaunchKernelGGL(k_cigar_debug<C>, dim3(grid_for(n)), dim3(kNT), 0, st, n, d_pos, cig, max_seg, d_n, d_b, d_end);
+        hipLaunchKernelGGL(k_cigar_debug<C>, dim3(dn::grid_for(n, kNT, kGridCap)), dim3(kNT), 0, st, n, d_pos, cig, max_seg, d_n, d_b, d_end);
         DN_TRY(hipGetLastError());
         DN_TRY(hipMemcpyAsync(nseg, d_n, sizeof(int32_t) * (size_t) n, hipMemcpyDeviceToHost, st));
         DN_TRY(hipMemcpyAsync(bounds, d_b, sizeof(int64_t) * (size_t) (n * 2 * max_seg), hipMemcpyDeviceToHost, st));
@@ -440,19 +440,19 @@ int coverage_stages(hipStream_t st, int32_t paired, int64_t n_rows, const int64_
         DN_TRY(hipMemsetAsync(d_err, 0xff, 3 * sizeof(unsigned long long), st));
         if (paired) DN_TRY(hipMemsetAsync(d_pcnt, 0, sizeof(int32_t) * (size_t) n_pair_ids, st));
         if (n_rows > 0) {
-            hipLaunchKernelGGL(k_prefilter<C>, dim3(grid_for(n_rows)), dim3(kNT), 0, st, n_rows, d_pos, cig, io.keep_lo, io.keep_hi,
+            hipLaunchKernelGGL(k_prefilter<C>, dim3(dn::grid_for(n_rows, kNT, kGridCap)), dim3(kNT), 0, st, n_rows, d_pos, cig, io.keep_lo, io.keep_hi,
                                paired ? d_pid.get() : (const int32_t *) nullptr, d_pcnt, d_end, d_keep);
             DN_TRY(hipGetLastError());
             int64_t n_units = n_rows;
             if (paired) {
-                hipLaunchKernelGGL(k_pair_flag, dim3(grid_for(n_rows)), dim3(kNT), 0, st, n_rows, d_pid, d_pcnt, d_keep);
+                hipLaunchKernelGGL(k_pair_flag, dim3(dn::grid_for(n_rows, kNT, kGridCap)), dim3(kNT), 0, st, n_rows, d_pid, d_pcnt, d_keep);
                 DN_TRY(hipGetLastError());
                 // exclusive rank of every surviving row; rank[n_rows] is the number of survivors
                 DN_TRY(hipMemsetAsync(d_keep + n_rows, 0, sizeof(int32_t), st));       // keep[n_rows] = 0: rank[n_rows] = #survivors
                 DN_TRY(scratch.run([&](void *tmp, size_t &bytes) {
                     return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, d_keep.get(), d_rank.get(), (int) n_rows + 1, st);
                 }));
-                hipLaunchKernelGGL(k_pair_compact, dim3(grid_for(n_rows)), dim3(kNT), 0, st, n_rows, d_keep, d_rank, d_rows);
+                hipLaunchKernelGGL(k_pair_compact, dim3(dn::grid_for(n_rows, kNT, kGridCap)), dim3(kNT), 0, st, n_rows, d_keep, d_rank, d_rows);
                 DN_TRY(hipGetLastError());
                 DN_TRY(hipMemcpyAsync(&survivors, d_rank + n_rows, sizeof(int32_t), hipMemcpyDeviceToHost, st));
                 DN_TRY(hipStreamSynchronize(st));
@@ -466,7 +466,7 @@ int coverage_stages(hipStream_t st, int32_t paired, int64_t n_rows, const int64_
                 A.ol_gene = d_olg; A.ol_gstart0 = d_gs0; A.ol_cov_off = d_coff; A.ol_exon_off = d_oxo; A.ol_exon = d_oex;
                 A.n_iso = n_iso; A.iso_iv = d_iiv; A.iso_gene = d_ig; A.n_iso_union = n_iso_union; A.iso_union = d_iu;
                 A.counts = d_counts; A.ol_diff = d_oldiff; A.chrom_diff = d_cdiff; A.n_iso_reads = d_niso; A.err = d_err;
-                hipLaunchKernelGGL(k_reads<C>, dim3(grid_for(n_units)), dim3(kNT), 0, st, A);
+                hipLaunchKernelGGL(k_reads<C>, dim3(dn::grid_for(n_units, kNT, kGridCap)), dim3(kNT), 0, st, A);
                 DN_TRY(hipGetLastError());
             }
         }
@@ -478,7 +478,7 @@ int coverage_stages(hipStream_t st, int32_t paired, int64_t n_rows, const int64_
             DN_TRY(scratch.run([&](void *tmp, size_t &bytes) {
                 return hipcub::DeviceScan::InclusiveSum(tmp, bytes, d_oldiff.get(), d_olcov.get(), (int) ol_total, st);
             }));
-            hipLaunchKernelGGL(k_widen, dim3(grid_for(ol_total)), dim3(kNT), 0, st, ol_total, d_olcov, d_val64);
+            hipLaunchKernelGGL(k_widen, dim3(dn::grid_for(ol_total, kNT, kGridCap)), dim3(kNT), 0, st, ol_total, d_olcov, d_val64);
             DN_TRY(hipGetLastError());
         }
         // chromosome vector -> CSR (positions ascending)
@@ -491,7 +491,7 @@ int coverage_stages(hipStream_t st, int32_t paired, int64_t n_rows, const int64_
         DN_TRY(hipMemcpyAsync(&h_niso, d_niso, sizeof(h_niso), hipMemcpyDeviceToHost, st));
         DN_TRY(hipStreamSynchronize(st));
         if (h_nsel > 0) {
-            hipLaunchKernelGGL(k_gather_csr, dim3(grid_for(h_nsel)), dim3(kNT), 0, st, (int64_t) h_nsel, d_csr_idx, d_ccov, d_csr_val);
+            hipLaunchKernelGGL(k_gather_csr, dim3(dn::grid_for(h_nsel, kNT, kGridCap)), dim3(kNT), 0, st, (int64_t) h_nsel, d_csr_idx, d_ccov, d_csr_val);
             DN_TRY(hipGetLastError());
         }
         DN_TRY(hipEventRecord(e1, st));
@@ -591,44 +591,25 @@ extern "C" int dn_reads_cigar_bounds(int device, int64_t n, const int64_t *pos, 
 // dn_bam_rows_inflate_framed, after which a window's inflated bytes never visit the host); k_bam_scan decodes every
 // record of the window and applies the reference's read filters (reads.py load_chromosome_reads), three scans give each kept row its place, and k_bam_write appends the kept rows, in file order,
 // to the row store: position, binary CIGAR ops, read name and the length of its qname_unpaired prefix.  The coverage
-// stages then read the binary CIGARs in place (BamCigars).  Record fields sit at arbitrary byte offsets: every load below
-// is a byte load.
+// stages then read the binary CIGARs in place (BamCigars).  The fixed part of a record is read through dn_bam_record.hpp.
 
 namespace {
 
 enum { kBamErrMalformed, kBamErrUnsupported, kBamErrNh, kBamErrNoCigar, kBamNErr };
 
-__device__ __forceinline__ uint32_t ld_u16(const uint8_t *p) { return (uint32_t) p[0] | ((uint32_t) p[1] << 8); }
-__device__ __forceinline__ uint32_t ld_u32(const uint8_t *p)
-{
-    return (uint32_t) p[0] | ((uint32_t) p[1] << 8) | ((uint32_t) p[2] << 16) | ((uint32_t) p[3] << 24);
-}
+using dn::le16;
+using dn::le32;
 
-struct BamRec {
-    int32_t ref, pos, next_ref, l_seq;
-    uint32_t l_name, n_cig;
-    int64_t name, cig, aux, end;        // byte offsets into the window
+struct BamRec : dn::BamHead {
+    int64_t aux;                        // where the aux fields begin: a byte offset into the window, as name(), cigar(), end()
 };
 
 // the fixed part of the record at window offset o; false when the record does not fit its block_size / the window
 __device__ bool bam_parse(const uint8_t *w, int64_t n_bytes, int64_t o, BamRec &R)
 {
-    if (o < 0 || o + 36 > n_bytes) return false;
-    const int32_t bs = (int32_t) ld_u32(w + o);
-    if (bs < 32 || o + 4 + (int64_t) bs > n_bytes) return false;
-    const uint8_t *p = w + o + 4;
-    R.ref = (int32_t) ld_u32(p);
-    R.pos = (int32_t) ld_u32(p + 4);
-    R.l_name = p[8];
-    R.n_cig = ld_u16(p + 12);
-    R.l_seq = (int32_t) ld_u32(p + 16);
-    R.next_ref = (int32_t) ld_u32(p + 20);
-    R.name = o + 36;
-    R.cig = R.name + R.l_name;
-    R.end = o + 4 + bs;
-    if (R.l_name < 1 || R.l_seq < 0) return false;
-    R.aux = R.cig + 4 * (int64_t) R.n_cig + ((int64_t) R.l_seq + 1) / 2 + R.l_seq;
-    return R.aux <= R.end;
+    if (!dn::bam_head(w, n_bytes, o, R) || R.l_name < 1 || R.l_seq < 0) return false;
+    R.aux = R.cigar() + 4 * (int64_t) R.n_cig + ((int64_t) R.l_seq + 1) / 2 + R.l_seq;
+    return R.aux <= R.end();
 }
 
 __device__ __forceinline__ int aux_size(uint8_t t)
@@ -662,10 +643,10 @@ __device__ bool bam_aux(const uint8_t *w, int64_t q, int64_t end, int &nh_state,
                 switch (ty) {
                 case 'c': nh = (int8_t) w[q]; break;
                 case 'C': nh = w[q]; break;
-                case 's': nh = (int16_t) ld_u16(w + q); break;
-                case 'S': nh = ld_u16(w + q); break;
-                case 'i': nh = (int32_t) ld_u32(w + q); break;
-                case 'I': nh = ld_u32(w + q); break;
+                case 's': nh = (int16_t) le16(w + q); break;
+                case 'S': nh = le16(w + q); break;
+                case 'i': nh = (int32_t) le32(w + q); break;
+                case 'I': nh = le32(w + q); break;
                 default: nh_state = 2;                      // A, f
                 }
             }
@@ -678,7 +659,7 @@ __device__ bool bam_aux(const uint8_t *w, int64_t q, int64_t end, int &nh_state,
         } else if (ty == 'B') {
             if (q + 5 > end) return false;
             const int esz = aux_size(w[q]);
-            const int64_t cnt = ld_u32(w + q + 1);
+            const int64_t cnt = le32(w + q + 1);
             if (esz == 0 || w[q] == 'A') return false;
             q += 5;
             if (cnt * esz > end - q) return false;
@@ -710,16 +691,16 @@ __global__ __launch_bounds__(kNT) void k_bam_scan(const uint8_t *__restrict__ w,
             int64_t nh;
             bool cg;
             k = 1;
-            if (!bam_aux(w, R.aux, R.end, nh_state, nh, cg)) { atomicMin(err + kBamErrMalformed, (unsigned long long) i); k = 0; }
+            if (!bam_aux(w, R.aux, R.end(), nh_state, nh, cg)) { atomicMin(err + kBamErrMalformed, (unsigned long long) i); k = 0; }
             else if (F.unique && nh_state == 2) { atomicMin(err + kBamErrNh, (unsigned long long) i); k = 0; }
             else if (F.unique && nh_state == 1 && nh > 1) k = 0;
             else if (F.paired && R.next_ref == -1) k = 0;
             if (k) {
                 if (R.n_cig == 0) atomicMin(err + kBamErrNoCigar, (unsigned long long) i);
                 bool bad = false;
-                for (uint32_t c = 0; c < R.n_cig; c++) bad |= (ld_u32(w + R.cig + 4 * (int64_t) c) & 15u) > 8u;
+                for (uint32_t c = 0; c < R.n_cig; c++) bad |= (le32(w + R.cigar() + 4 * (int64_t) c) & 15u) > 8u;
                 // a CIGAR moved to the CG tag leaves <l_seq>S<ref_len>N in the record
-                if (cg && R.n_cig == 2 && ld_u32(w + R.cig) == (((uint32_t) R.l_seq << 4) | 4u) && (ld_u32(w + R.cig + 4) & 15u) == 3u)
+                if (cg && R.n_cig == 2 && le32(w + R.cigar()) == (((uint32_t) R.l_seq << 4) | 4u) && (le32(w + R.cigar() + 4) & 15u) == 3u)
                     bad = true;
                 if (bad) atomicMin(err + kBamErrUnsupported, (unsigned long long) i);
             }
@@ -751,10 +732,10 @@ __global__ __launch_bounds__(kNT) void k_bam_write(const uint8_t *__restrict__ w
         O.pos[r] = R.pos;
         O.op_beg[r] = ob;
         O.n_op[r] = (int32_t) R.n_cig;
-        for (uint32_t c = 0; c < R.n_cig; c++) O.ops[ob + c] = ld_u32(w + R.cig + 4 * (int64_t) c);
+        for (uint32_t c = 0; c < R.n_cig; c++) O.ops[ob + c] = le32(w + R.cigar() + 4 * (int64_t) c);
         int32_t key = 0;                        // qname_unpaired = the name up to its last '.', '' without one
         for (int32_t c = 0; c < nl; c++) {
-            const uint8_t ch = w[R.name + c];
+            const uint8_t ch = w[R.name() + c];
             O.names[nb + c] = ch;
             if (ch == '.') key = c;
         }
@@ -784,10 +765,10 @@ __global__ __launch_bounds__(kNT) void k_bam_gather(int64_t n, const int32_t *__
 
 std::string bam_name(const uint8_t *w, int64_t n_bytes, int64_t o)
 {
-    if (o + 36 > n_bytes) return "?";
-    const int64_t l = w[o + 12];
-    if (l < 1 || o + 36 + l > n_bytes) return "?";
-    return std::string((const char *) w + o + 36, (size_t) (l - 1));
+    if (o + dn::kBamName > n_bytes) return "?";
+    const int64_t l = w[o + dn::kBamLName];
+    if (l < 1 || o + dn::kBamName + l > n_bytes) return "?";
+    return std::string((const char *) w + o + dn::kBamName, (size_t) (l - 1));
 }
 
 std::string cigar_string(const uint32_t *ops, int64_t n)
@@ -837,15 +818,13 @@ extern "C" int dn_bam_frame(const uint8_t *buf, int64_t n_bytes, int32_t tid, in
         return dn::fail(DN_E_INVALID, "dn_bam_frame: bad argument");
     int64_t o = 0, n = 0;
     while (o + 4 <= n_bytes) {
-        int32_t bs, ref, pos;
-        memcpy(&bs, buf + o, 4);
-        if (bs < 32)
+        const int32_t bs = (int32_t) dn::le32(buf + o);
+        if (bs < dn::kBamMinSize)
             return dn::fail(DN_E_INVALID, "malformed BAM record at byte " + std::to_string(o) + " of the window (block_size " + std::to_string(bs) + ")");
         if (o + 4 + (int64_t) bs > n_bytes) break;          // the tail: carried over to the next window
         if (n >= cap) return dn::fail(DN_E_INVALID, "dn_bam_frame: more records than cap");
         if (tid >= 0) {
-            memcpy(&ref, buf + o + 4, 4);
-            memcpy(&pos, buf + o + 8, 4);
+            const int32_t ref = (int32_t) dn::le32(buf + o + dn::kBamRef), pos = (int32_t) dn::le32(buf + o + dn::kBamPos);
             if (ref != tid || pos < *last_pos)
                 return dn::fail(DN_E_INVALID, "BAM file is not sorted by coordinate, or its index is stale: a record of refID " + std::to_string(ref) +
                                               " at position " + std::to_string(pos) + " follows position " + std::to_string(*last_pos) +
@@ -930,7 +909,7 @@ int append_window(dn_bam_rows h, const uint8_t *window, int64_t n_bytes, int64_t
         DN_TRY(hipMemsetAsync(h->keep + n_rec, 0, sizeof(int32_t), st));
         DN_TRY(hipMemsetAsync(h->w_ops + n_rec, 0, sizeof(int32_t), st));
         DN_TRY(hipMemsetAsync(h->w_name + n_rec, 0, sizeof(int32_t), st));
-        hipLaunchKernelGGL(k_bam_scan, dim3(grid_for(n_rec)), dim3(kNT), 0, st, h->win.get(), n_bytes, h->rec_off.get(), n_rec, h->F,
+        hipLaunchKernelGGL(k_bam_scan, dim3(dn::grid_for(n_rec, kNT, kGridCap)), dim3(kNT), 0, st, h->win.get(), n_bytes, h->rec_off.get(), n_rec, h->F,
                            h->keep.get(), h->w_ops.get(), h->w_name.get(), h->err.get());
         DN_TRY(hipGetLastError());
         const auto rank_of = [&](int32_t *flag, int32_t *rank) {      // exclusive; rank[n_rec] is the total
@@ -961,7 +940,7 @@ int append_window(dn_bam_rows h, const uint8_t *window, int64_t n_bytes, int64_t
             DN_TRY(h->ops.reserve(h->n_ops + tot[1], h->n_ops, st));
             DN_TRY(h->names.reserve(h->n_names + tot[2], h->n_names, st));
             BamRowsOut O{h->pos, h->op_beg, h->name_beg, h->n_op, h->name_len, h->key_len, h->ops, h->names, h->max_key};
-            hipLaunchKernelGGL(k_bam_write, dim3(grid_for(n_rec)), dim3(kNT), 0, st, h->win.get(), n_bytes, h->rec_off.get(), n_rec,
+            hipLaunchKernelGGL(k_bam_write, dim3(dn::grid_for(n_rec, kNT, kGridCap)), dim3(kNT), 0, st, h->win.get(), n_bytes, h->rec_off.get(), n_rec,
                                h->keep.get(), h->rank.get(), h->op_rank.get(), h->name_rank.get(), h->n_rows, h->n_ops, h->n_names, O);
             DN_TRY(hipGetLastError());
             DN_TRY(hipStreamSynchronize(st));
@@ -1190,7 +1169,7 @@ extern "C" int dn_bam_rows_keys(dn_bam_rows h, int32_t width, uint8_t *keys)
         DN_TRY(hipStreamSynchronize(h->st));
         if (width < mk) return dn::fail(DN_E_INVALID, "dn_bam_rows_keys: width below the longest key (" + std::to_string(mk) + ")");
         DN_TRY(alloc_padded(d_keys, (size_t) (h->n_rows * width)));
-        hipLaunchKernelGGL(k_bam_keys, dim3(grid_for(h->n_rows)), dim3(kNT), 0, h->st, h->n_rows, h->name_beg.get(), h->key_len.get(),
+        hipLaunchKernelGGL(k_bam_keys, dim3(dn::grid_for(h->n_rows, kNT, kGridCap)), dim3(kNT), 0, h->st, h->n_rows, h->name_beg.get(), h->key_len.get(),
                            h->names.get(), width, d_keys.get());
         DN_TRY(hipGetLastError());
         DN_TRY(hipMemcpyAsync(keys, d_keys, (size_t) (h->n_rows * width), hipMemcpyDeviceToHost, h->st));
@@ -1253,7 +1232,7 @@ extern "C" int dn_bam_rows_coverage(dn_bam_rows h, const int32_t *order, const i
                 if (order[r] < 0 || order[r] >= n) return dn::fail(DN_E_INVALID, "dn_bam_rows_coverage: order out of range");
             DN_TRY(alloc_padded(d_order, n)); DN_TRY(alloc_padded(g_pos, n)); DN_TRY(alloc_padded(g_beg, n)); DN_TRY(alloc_padded(g_cnt, n));
             DN_TRY(hipMemcpyAsync(d_order, order, sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(k_bam_gather, dim3(grid_for(n)), dim3(kNT), 0, st, n, d_order.get(), h->pos.get(), h->op_beg.get(),
+            hipLaunchKernelGGL(k_bam_gather, dim3(dn::grid_for(n, kNT, kGridCap)), dim3(kNT), 0, st, n, d_order.get(), h->pos.get(), h->op_beg.get(),
                                h->n_op.get(), g_pos.get(), g_beg.get(), g_cnt.get());
             DN_TRY(hipGetLastError());
             p_pos = g_pos; p_beg = g_beg; p_cnt = g_cnt;

@@ -4,7 +4,8 @@
 //             the stream (dn::inflate_launch, InflateBlock::dst_off), so the buffer is the file's record stream, contiguous
 //   frame     dn::frame_window (tid = -1) over the buffer in pieces; a record that a piece cuts starts the next piece
 //   keys      k_sort_keys, one lane per record: block_size, refID and pos give the key and the record's length, and the
-//             record is checked (sort_record).  The first error in input order wins (atomicMin on the ordinal)
+//             record is checked (sort_record, on the record view of dn_bam_record.hpp).  The first error in input order
+//             wins (dn::note_error)
 //   sort      hipcub::DeviceRadixSort::SortPairs of (key, ordinal), which is stable, over the bits that can differ: those of
 //             the largest pos + 1 met, then those of n_ref -- two LSD passes over one ping-pong pair of arrays
 //   scan      the lengths in sorted order, exclusive sum: where each record goes
@@ -15,8 +16,8 @@
 //   deflate   (dn_bam_sort_deflate, for a caller that writes the file with the library's encoder) ranges of the sorted stream
 //             become BGZF blocks where the stream lies (dn::deflate_device); the unsorted copy, dead by then, lends the slots
 //
-// The order: ascending key = ref_key << 32 | (uint32) (pos + 1), ref_key = refID, or the largest value for refID -1, so
-// unplaced records go last and pos -1 sorts first within a reference; records of equal key keep their order in the input.
+// The order: ascending key = dn::ref_key(refID) << 32 | (uint32) (pos + 1): refID -1 has the largest ref_key, so unplaced
+// records go last, and pos -1 sorts first within a reference; records of equal key keep their order in the input.
 // (The arrays hold n_ref in place of that largest value: the same order in fewer bits.)
 //
 // The per-record steps (sort_record, copy_plan, load16_at) are __host__ __device__ functions; the host build runs them in
@@ -36,8 +37,7 @@
 #include "dn_inflate.hpp"
 #include "dn_frame.hpp"
 #include "dn_deflate.hpp"
-
-#define DN_HD __host__ __device__ __forceinline__
+#include "dn_bam_record.hpp"
 
 namespace {
 
@@ -46,14 +46,9 @@ constexpr int kWave = 64;
 constexpr int kGroup = 16;                         // lanes that copy one record
 constexpr int64_t kSlack = 64;                     // bytes behind the stream: load16_at reads whole aligned 16-byte pieces
 constexpr int64_t kPieceDefault = (int64_t) 256 << 20;
+constexpr int64_t kGridCap = 1 << 20;
 
 enum { kSortOk = 0, kSortShape = 1, kSortRef = 2, kSortPos = 3 };
-
-DN_HD uint32_t s_u16(const uint8_t *p) { return (uint32_t) p[0] | ((uint32_t) p[1] << 8); }
-DN_HD uint32_t s_u32(const uint8_t *p)
-{
-    return (uint32_t) p[0] | ((uint32_t) p[1] << 8) | ((uint32_t) p[2] << 16) | ((uint32_t) p[3] << 24);
-}
 
 // The record at byte o of the stream s: its key, its length with the block_size field and pos + 1; kSortOk or what is wrong
 // with it.  The framing established that the record lies inside the stream; the bounds are checked again so that offsets
@@ -61,15 +56,14 @@ DN_HD uint32_t s_u32(const uint8_t *p)
 DN_HD int sort_record(const uint8_t *s, int64_t n_bytes, int64_t o, int32_t n_ref, uint64_t &key, uint32_t &len, uint32_t &pos1)
 {
     key = 0; len = 0; pos1 = 0;
-    if (o < 0 || o + 36 > n_bytes) return kSortShape;
-    const int64_t bs = (int32_t) s_u32(s + o), l_name = s[o + 12], n_cig = s_u16(s + o + 16);
-    if (bs < 32 || o + 4 + bs > n_bytes || 32 + l_name + 4 * n_cig > bs) return kSortShape;
-    len = (uint32_t) (4 + bs);
-    const int32_t ref = (int32_t) s_u32(s + o + 4), pos = (int32_t) s_u32(s + o + 8);
-    if (ref < -1 || ref >= n_ref) return kSortRef;
-    if (pos < -1) return kSortPos;
-    pos1 = (uint32_t) (pos + 1);
-    key = (uint64_t) (uint32_t) (ref < 0 ? n_ref : ref) << 32 | pos1;
+    dn::BamHead H;
+    if (!dn::bam_head(s, n_bytes, o, H) || !H.names_fit()) return kSortShape;
+    len = (uint32_t) (4 + H.bs);
+    if (H.ref < -1 || H.ref >= n_ref) return kSortRef;
+    if (H.pos < -1) return kSortPos;
+    pos1 = (uint32_t) (H.pos + 1);
+    const uint32_t rk = dn::ref_key(H.ref);                 // the arrays hold n_ref in place of kUnplaced
+    key = (uint64_t) (rk == dn::kUnplaced ? (uint32_t) n_ref : rk) << 32 | pos1;
     return kSortOk;
 }
 
@@ -157,7 +151,7 @@ __global__ __launch_bounds__(kNT) void k_sort_keys(const uint8_t *__restrict__ s
         uint32_t l, p1;
         const int e = sort_record(s, n_bytes, o, n_ref, k, l, p1);
         off[first + i] = o; key[first + i] = k; ord[first + i] = (uint32_t) (first + i); len[first + i] = l;
-        if (e != kSortOk) atomicMin(err, (unsigned long long) (first + i) << 3 | (unsigned long long) e);
+        if (e != kSortOk) dn::note_error(err, first + i, e);
         top = p1 > top ? p1 : top;
     }
     for (int m = kWave / 2; m > 0; m >>= 1) {
@@ -185,12 +179,6 @@ __global__ __launch_bounds__(kNT) void k_sort_gather(const uint8_t *__restrict__
         for (int k = lane; k < 32; k += kGroup) copy_piece(in, out, src, d, len, P, -1 - k);
         for (int64_t c = lane; c < P.n_body; c += kGroup) copy_piece(in, out, src, d, len, P, c);
     }
-}
-
-inline unsigned grid_for(int64_t n, int per_block)
-{
-    const int64_t g = (n + per_block - 1) / per_block;
-    return (unsigned) (g < 1 ? 1 : g > (1 << 20) ? (1 << 20) : g);
 }
 
 inline int bits_of(uint64_t v)
@@ -231,18 +219,14 @@ struct dn_bam_sort_s {
 
 namespace {
 
-std::string who_is(int64_t idx, int32_t ref, int32_t pos)
-{
-    return "record " + std::to_string(idx) + " (refID " + std::to_string(ref) + ", position " + std::to_string(pos) + ")";
-}
-
 int record_error(dn_bam_sort h, int code, int64_t idx, int32_t ref, int32_t pos)
 {
+    const std::string who = dn::record_name(idx, ref, pos);
     h->failed = true;
     switch (code) {
-    case kSortShape: return dn::fail(DN_E_INVALID, "malformed BAM " + who_is(idx, ref, pos) + ": its read name and CIGAR do not fit inside the record");
-    case kSortRef: return dn::fail(DN_E_INVALID, who_is(idx, ref, pos) + " names a reference the header does not have (" + std::to_string(h->n_ref) + " references)");
-    default: return dn::fail(DN_E_INVALID, who_is(idx, ref, pos) + " has a position below -1");
+    case kSortShape: return dn::record_shape_error(who);
+    case kSortRef: return dn::record_reference_error(who, h->n_ref);
+    default: return dn::fail(DN_E_INVALID, who + " has a position below -1");
     }
 }
 
@@ -256,14 +240,7 @@ int bad_size_error(dn_bam_sort h, int64_t idx, int64_t at, int32_t bs)
 int cut_error(dn_bam_sort h, int64_t left)
 {
     h->failed = true;
-    return dn::fail(DN_E_INVALID, "record " + std::to_string(h->n_records) + " is cut by the end of the file (" + std::to_string(left) + " bytes of it are there)");
-}
-
-int check_handle(dn_bam_sort h, const char *who, bool device)
-{
-    if (!h || (h->device >= 0) != device) return dn::fail(DN_E_INVALID, std::string(who) + ": bad argument");
-    if (h->failed || h->finished) return dn::fail(DN_E_STATE, std::string(who) + ": the sort is finished or has failed");
-    return DN_OK;
+    return dn::record_cut_error(h->n_records, left);
 }
 
 // the steps of dn_bam_sort_finish on the host's copy of the stream
@@ -272,7 +249,7 @@ struct HostSort {
     std::vector<int64_t> piece_off, off;
     std::vector<uint64_t> key;
     std::vector<uint32_t> ord, len;
-    unsigned long long err = ~0ull;
+    unsigned long long err = dn::kNoError;
 
     // frame the piece [base, base + n): nr records, `used` bytes; bad: the record behind them has the block_size bad_bs
     int frame(int64_t base, int64_t n, int64_t &nr, int64_t &used, bool &bad, int32_t &bad_bs)
@@ -287,8 +264,8 @@ struct HostSort {
         // the only record the framing of a mixed stream refuses is one with a block_size below 32: the serial walk finds it
         nr = used = 0;
         while (used + 4 <= n) {
-            const int32_t bs = (int32_t) s_u32(w + used);
-            if (bs < 32) { bad = true; bad_bs = bs; dn::clear_error(); return DN_OK; }
+            const int32_t bs = (int32_t) dn::le32(w + used);
+            if (bs < dn::kBamMinSize) { bad = true; bad_bs = bs; dn::clear_error(); return DN_OK; }
             if (used + 4 + (int64_t) bs > n) break;
             piece_off[(size_t) nr++] = used;
             used += 4 + (int64_t) bs;
@@ -305,7 +282,7 @@ struct HostSort {
             off[g] = piece_off[(size_t) i] + base;
             const int e = sort_record(h->h_in.data(), h->n_bytes, off[g], h->n_ref, key[g], len[g], p1);
             ord[g] = (uint32_t) g;
-            if (e != kSortOk && err == ~0ull) err = (unsigned long long) g << 3 | (unsigned long long) e;
+            if (e != kSortOk) dn::note_error(&err, (int64_t) g, e);
             top = p1 > top ? p1 : top;
         }
         return DN_OK;
@@ -313,11 +290,7 @@ struct HostSort {
     int first_error(unsigned long long &e, int32_t &ref, int32_t &pos)
     {
         e = err;
-        if (e == ~0ull) return DN_OK;
-        const int64_t o = off[(size_t) (e >> 3)];
-        const bool inside = o >= 0 && o + 12 <= h->n_bytes;
-        ref = inside ? (int32_t) s_u32(h->h_in.data() + o + 4) : -1;
-        pos = inside ? (int32_t) s_u32(h->h_in.data() + o + 8) : -1;
+        if (e != dn::kNoError) dn::error_record_host(off.data(), dn::error_ordinal(e), h->h_in.data(), h->n_bytes, ref, pos);
         return DN_OK;
     }
     int sort_and_gather(int /*pos_bits*/, int /*ref_bits*/, int64_t &total)
@@ -342,9 +315,9 @@ struct HostSort {
 // body it hands to dn::synced
 struct DeviceSort {
     dn_bam_sort h;
-    unsigned long long h_err[2] = {~0ull, 0};
-    int64_t h_off = 0, h_total = 0;
-    uint8_t h_rec[12] = {0};
+    unsigned long long h_err[2] = {dn::kNoError, 0};
+    int64_t h_total = 0;
+    dn::ErrorProbe probe;
     float sort_ms = 0.f, gather_ms = 0.f;
 
     int frame(int64_t base, int64_t n, int64_t &nr, int64_t &used, bool &bad, int32_t &bad_bs)
@@ -365,7 +338,7 @@ struct DeviceSort {
         DN_TRY(h->off.reserve(first + nr, first, st)); DN_TRY(h->key.reserve(first + nr, first, st));
         DN_TRY(h->ord.reserve(first + nr, first, st)); DN_TRY(h->len.reserve(first + nr, first, st));
         DN_TRY(hipEventRecord(h->ev0, st));
-        hipLaunchKernelGGL(k_sort_keys, dim3(grid_for(nr, kNT)), dim3(kNT), 0, st, (const uint8_t *) h->in.get(), h->n_bytes,
+        hipLaunchKernelGGL(k_sort_keys, dim3(dn::grid_for(nr, kNT, kGridCap)), dim3(kNT), 0, st, (const uint8_t *) h->in.get(), h->n_bytes,
                            (const int64_t *) h->piece_off.get(), base, nr, first, h->n_ref, h->off.get(), h->key.get(), h->ord.get(), h->len.get(),
                            h->err.get());
         DN_TRY(hipGetLastError());
@@ -382,17 +355,7 @@ struct DeviceSort {
         DN_TRY(hipMemcpyAsync(h_err, h->err, sizeof(h_err), hipMemcpyDeviceToHost, st));
         DN_TRY(hipStreamSynchronize(st));
         e = h_err[0];
-        if (e == ~0ull) return DN_OK;
-        DN_TRY(hipMemcpyAsync(&h_off, h->off + (int64_t) (e >> 3), sizeof(h_off), hipMemcpyDeviceToHost, st));
-        DN_TRY(hipStreamSynchronize(st));
-        ref = pos = -1;
-        if (h_off >= 0 && h_off + 12 <= h->n_bytes) {
-            DN_TRY(hipMemcpyAsync(h_rec, h->in + h_off, 12, hipMemcpyDeviceToHost, st));
-            DN_TRY(hipStreamSynchronize(st));
-            ref = (int32_t) s_u32(h_rec + 4);
-            pos = (int32_t) s_u32(h_rec + 8);
-        }
-        return DN_OK;
+        return e == dn::kNoError ? DN_OK : dn::error_record_device(st, h->off, dn::error_ordinal(e), h->in, h->n_bytes, probe, ref, pos);
     }
     uint32_t top() const { return (uint32_t) h_err[1]; }
     int sort_and_gather(int pos_bits, int ref_bits, int64_t &total)
@@ -412,7 +375,7 @@ struct DeviceSort {
             std::swap(ka, kb);
             std::swap(oa, ob);
         }
-        hipLaunchKernelGGL(k_sort_lengths, dim3(grid_for(n + 1, kNT)), dim3(kNT), 0, st, (const uint32_t *) oa, (const uint32_t *) h->len.get(), n,
+        hipLaunchKernelGGL(k_sort_lengths, dim3(dn::grid_for(n + 1, kNT, kGridCap)), dim3(kNT), 0, st, (const uint32_t *) oa, (const uint32_t *) h->len.get(), n,
                            h->dst.get());
         DN_TRY(hipGetLastError());
         DN_TRY(h->scratch.run([&](void *tmp, size_t &bytes) {
@@ -427,7 +390,7 @@ struct DeviceSort {
         total = h_total;
         if (total != h->n_bytes) return DN_OK;                         // the records do not tile the stream: nothing is copied
         DN_TRY(hipEventRecord(h->ev2, st));
-        hipLaunchKernelGGL(k_sort_gather, dim3(grid_for(n, kNT / kGroup)), dim3(kNT), 0, st, (const uint8_t *) h->in.get(), (const int64_t *) h->off.get(),
+        hipLaunchKernelGGL(k_sort_gather, dim3(dn::grid_for(n, kNT / kGroup, kGridCap)), dim3(kNT), 0, st, (const uint8_t *) h->in.get(), (const int64_t *) h->off.get(),
                            (const uint32_t *) oa, (const int64_t *) h->dst.get(), n, h->out.get());
         DN_TRY(hipGetLastError());
         DN_TRY(hipEventRecord(h->ev3, st));
@@ -450,10 +413,10 @@ template <class B> int run_sort(dn_bam_sort h, B &be, uint32_t &top)
         if (rc != DN_OK) { h->failed = true; return rc; }
         if (nr > 0) {
             if ((rc = be.keys(base, nr, top)) != DN_OK) { h->failed = true; return rc; }
-            unsigned long long e = ~0ull;
+            unsigned long long e = dn::kNoError;
             int32_t ref = -1, pos = -1;
             if ((rc = be.first_error(e, ref, pos)) != DN_OK) { h->failed = true; return rc; }
-            if (e != ~0ull) return record_error(h, (int) (e & 7), (int64_t) (e >> 3), ref, pos);
+            if (e != dn::kNoError) return record_error(h, dn::error_code(e), dn::error_ordinal(e), ref, pos);
         }
         if (bad) return bad_size_error(h, h->n_records + nr, base + used, bad_bs);
         h->n_records += nr;
@@ -543,7 +506,7 @@ extern "C" int dn_bam_sort_window(dn_bam_sort h, const uint8_t *comp, int64_t n_
 {
     dn::clear_error();
     if (h) h->ingest.take();
-    int rc = check_handle(h, "dn_bam_sort_window", true);
+    int rc = dn::check_handle(h, "dn_bam_sort_window", "sort", true);
     if (rc != DN_OK) return rc;
     if (n_comp < 0 || (n_comp > 0 && !comp) || n_blocks < 0 || n_blocks > INT32_MAX || (n_blocks > 0 && (!pay_off || !pay_len || !isize || !status)) ||
         head_skip < 0)
@@ -569,7 +532,7 @@ extern "C" int dn_bam_sort_window(dn_bam_sort h, const uint8_t *comp, int64_t n_
 extern "C" int dn_bam_sort_window_host(dn_bam_sort h, const uint8_t *data, int64_t n_data, int32_t head_skip)
 {
     dn::clear_error();
-    const int rc = check_handle(h, "dn_bam_sort_window_host", false);
+    const int rc = dn::check_handle(h, "dn_bam_sort_window_host", "sort", false);
     if (rc != DN_OK) return rc;
     if (n_data < 0 || (n_data > 0 && !data) || head_skip < 0) return dn::fail(DN_E_INVALID, "dn_bam_sort_window_host: bad argument");
     const int64_t skip = head_skip < n_data ? head_skip : n_data;

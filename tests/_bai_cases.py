@@ -21,6 +21,9 @@ REF_OPS = set('MDN=X')
 WINDOWS = (1, 70000, None)
 SEGMENTS = (256, None)
 LAYOUTS = ('aligned', 'straddle', 'midheader', 'empty')
+# the sizes every error file is built with: one window; a window per block; windows of four blocks, so that a fault at record
+# 900 of an error file lies in a later window and its text must still count the records of the windows before
+ERROR_SIZES = ({}, {'window_bytes': 1, 'segment_bytes': 256}, {'window_bytes': 70000})
 BLOCK = 20000
 
 
@@ -275,8 +278,10 @@ def error_files(tmp):
     good['qname'] = ['q{0}'.format(k) for k in range(n)]
     out = {}
 
-    def write(name, frame, text, hdr=hdr, cut=0, eof=True, corrupt=False):
+    def write(name, frame, text, hdr=hdr, cut=0, eof=True, corrupt=False, patch=None):
         data, offs = bf.encode_records(frame.reset_index(drop=True))
+        if patch:
+            data = bytes(patch(bytearray(data), offs))
         if cut:
             data = data[:-cut]
         p = str(tmp / (name + '.bam'))
@@ -294,6 +299,7 @@ def error_files(tmp):
     bad = good.copy()
     bad.loc[900, 'pos'] = 5
     write('pos_order', bad, 'not sorted by coordinate: record 900 (refID 0, position 5)')
+    assert len(hdr) + bf.encode_records(good)[1][900] > 4 * BLOCK       # behind the first window of ERROR_SIZES[2]: four blocks
     bad = good.copy()
     bad.loc[n - 1, 'ref'] = 2
     write('ref_range', bad, 'record {0} (refID 2'.format(n - 1))
@@ -302,4 +308,15 @@ def error_files(tmp):
     write('cut', good, 'record {0} is cut by the end of the file'.format(n - 1), cut=10)
     write('no_eof', good, 'no BGZF end-of-file block', eof=False)
     write('inflate', good, 'the BGZF block at byte {0} does not inflate: bad block type or header', corrupt=True)
+
+    def many_cigar_ops(data, offs):                          # n_cigar_op; block_size stays, so the chain of records is intact
+        data[offs[700] + 16:offs[700] + 18] = struct.pack('<H', 0xffff)
+        return data
+
+    # the three texts below are what the library gave before the index and the sort shared their error path
+    write('shape', good, 'malformed BAM record 700 (refID 0, position 54355): its read name and CIGAR do not fit inside the record', patch=many_cigar_ops)
+    bad = good.copy()                                        # the earlier fault has the larger code: the ordinal decides
+    bad.loc[300, 'pos'] = 5
+    bad.loc[900, 'ref'] = 2
+    write('two_faults', bad, 'BAM file is not sorted by coordinate: record 300 (refID 0, position 5) follows a larger position of the same reference')
     return out

@@ -236,4 +236,15 @@ def error_files(tmp):
     bad = good.copy()
     bad.loc[300, 'pos'] = -7
     write('pos_range', bad, 'record 300 (refID {0}, position -7) has a position below -1'.format(int(bad.ref[300])))
+
+    def many_cigar_ops(data, offs):                         # n_cigar_op; block_size stays, so the chain of records is intact
+        data[offs[700] + 16:offs[700] + 18] = struct.pack('<H', 0xffff)
+        return data
+
+    # the two texts below are what the library gave before the index and the sort shared their error path
+    write('shape', good, 'malformed BAM record 700 (refID 1, position 35368): its read name and CIGAR do not fit inside the record', patch=many_cigar_ops)
+    bad = good.copy()                                       # the earlier fault has the larger code: the ordinal decides
+    bad.loc[300, 'pos'] = -7
+    bad.loc[900, 'ref'] = 2
+    write('two_faults', bad, 'record 300 (refID 1, position -7) has a position below -1')
     return out

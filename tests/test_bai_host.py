@@ -124,7 +124,7 @@ def test_parse_bai_round_trips_a_fixture_index(tmp_path):
 
 def test_errors(tmp_path):
     for name, (path, text) in bc.error_files(tmp_path).items():
-        for kw in ({}, {'window_bytes': 1, 'segment_bytes': 256}):
+        for kw in bc.ERROR_SIZES:
             with pytest.raises(ValueError) as e:
                 bam.build_index(path, **kw)
             assert text in str(e.value) and str(e.value).startswith(path + ': '), (name, str(e.value))

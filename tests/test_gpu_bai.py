@@ -51,7 +51,7 @@ def test_device_build_equals_host_build(name, layout, tmp_path):
 def test_errors_equal_the_host_texts(tmp_path):
     assert len(_VALID_PASSED) == len(bc.CASES) * len(bc.LAYOUTS), 'no error input goes to the device before the valid cases have passed in this run'
     for name, (path, text) in bc.error_files(tmp_path).items():
-        for kw in ({}, {'window_bytes': 1, 'segment_bytes': 256}):
+        for kw in bc.ERROR_SIZES:
             with pytest.raises(ValueError) as host:
                 bam.build_index(path, **kw)
             assert text in str(host.value), name                   # the host build first
