@@ -72,6 +72,9 @@ def argparser():
                     help='inflate the BGZF blocks of the .bam files on the GPU instead of with zlib on the host')
     ap.add_argument('--device-frame', action='store_true',
                     help='find the record starts of the inflated .bam bytes on the GPU instead of with a serial walk on the host')
+    ap.add_argument('--device-pair', action='store_true',
+                    help='pair the mates of paired-end .bam files on the GPU instead of with a sort of their names on the host; '
+                         'reads of equal name keep their order in the file')
     ap.add_argument('--verify-crc', action='store_true',
                     help='check every BGZF block read from the .bam files against the CRC32 of its trailer (also while '
                          '--create-bai indexes and --sort-bam sorts them) and stop at the first that differs')
@@ -227,7 +230,8 @@ def _run(args, output_dir, device, verify):
                      nmf_iter=args.nmf_iter, downsample_rate=args.downsample_rate, minimax_coverage=args.minimax_coverage,
                      skip_baseline_selection=args.skip_baseline_selection, unique_alignment=not args.non_unique_alignments,
                      n_jobs=args.proc_per_node, inflate='device' if args.device_inflate else 'host',
-                     frame='device' if args.device_frame else 'host', verify=verify)
+                     frame='device' if args.device_frame else 'host', verify=verify,
+                     pair='device' if getattr(args, 'device_pair', False) else 'host')
     logging.info('DegNorm pipeline complete! Exiting...')
 
 

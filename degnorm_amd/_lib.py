@@ -137,6 +137,8 @@ def load(build_if_missing=False):
     lib.dn_bam_rows_keys.argtypes = [vp, i32, P(u8)]
     lib.dn_bam_rows_fetch.argtypes = [vp, P(i64), P(i64), P(i32), P(u32), P(i64), P(i32), P(u8)]
     lib.dn_bam_rows_coverage.argtypes = [vp, P(i32), P(i32), i64] + lib.dn_read_coverage.argtypes[8:]
+    lib.dn_bam_rows_pair.argtypes = [vp, P(i32), P(i32), P(i64), P(c.c_double)]
+    lib.dn_bam_pair_host.argtypes = [i64, P(i64), P(i32), P(u8), P(i32), P(i32), P(i64)]
     lib.dn_bam_cigar_bounds.argtypes = [c.c_int, i64, P(i64), P(i64), P(u32), i32, P(i32), P(i64), P(i64)]
     u64 = c.c_uint64
     lib.dn_bai_create.argtypes = [c.c_int, i32, i64, P(vp)]

@@ -507,10 +507,35 @@ class DeviceRows(object):
                                           _ptr(name_beg, i64), _ptr(name_len, i32), _ptr(names, ctypes.c_uint8)), 'dn_bam_rows_fetch')
         return pos[:n], op_beg[:n], n_op[:n], ops[:n_ops], name_beg[:n], name_len[:n], names[:n_names]
 
-    def coverage(self, ann):
-        """dn_bam_rows_coverage: the outputs of reads.device_read_coverage for the stored rows."""
+    def pair(self, fetch=False):
+        """
+        dn_bam_rows_pair: pair the mates on the device and keep the result there.  Rows go in ascending qname_unpaired order,
+        equal keys in file order: np.argsort(self.keys(), kind='stable').  Returns (order int32, pair_id int32, number of ids,
+        device ms) with fetch=True, (None, None, number of ids, device ms) otherwise.
+        """
+        n = self.info()[0] if fetch else 0
+        order = np.zeros(max(n, 1), np.int32) if fetch else None
+        pair_id = np.zeros(max(n, 1), np.int32) if fetch else None
+        n_ids, ms = ctypes.c_int64(0), ctypes.c_double(0.0)
+        _check(self.lib.dn_bam_rows_pair(self.h, _ptr(order, ctypes.c_int32), _ptr(pair_id, ctypes.c_int32), ctypes.byref(n_ids),
+                                         ctypes.byref(ms)), 'dn_bam_rows_pair')
+        if fetch:
+            return order[:n], pair_id[:n], int(n_ids.value), float(ms.value)
+        return None, None, int(n_ids.value), float(ms.value)
+
+    def coverage(self, ann, pair='host'):
+        """
+        dn_bam_rows_coverage: the outputs of reads.device_read_coverage for the stored rows.  A paired store's mates are
+        paired on the host in the reference's order (pair_order; pair='host') or on the device with equal keys in file order
+        (self.pair(); pair='device'), which moves no keys to the host; self.pair_ms is then the pairing's device ms.
+        """
+        if pair not in ('host', 'device'):
+            raise ValueError("pair must be 'host' or 'device', not {0!r}".format(pair))
         order, pair_id, n_ids = None, None, 0
-        if self.paired:
+        self.pair_ms = 0.0
+        if self.paired and pair == 'device':
+            self.pair_ms = self.pair()[3]
+        elif self.paired:
             order, pair_id, n_ids = pair_order(self.keys())
         i32, i64, dbl = ctypes.c_int32, ctypes.c_int64, ctypes.c_double
         n_genes = len(ann.genes)
@@ -549,6 +574,28 @@ def pair_order(keys):
     return order, pair_id, int(pair_id[-1]) + 1 if len(sk) else 0
 
 
+def pair_rows(keys):
+    """
+    The order and pair ids of DeviceRows.pair() for these keys (an S-dtype array, or a list of bytes), computed by the
+    library's host build of the same passes (dn_bam_pair_host; no device needed): (order int32, pair_id int32, number of
+    ids) with order == np.argsort(keys, kind='stable').
+    """
+    keys = [bytes(k) for k in (keys.tolist() if isinstance(keys, np.ndarray) else keys)]
+    n = len(keys)
+    key_len = np.array([len(k) for k in keys], dtype=np.int32).reshape(n)
+    name_beg = np.zeros(max(n, 1), dtype=np.int64)
+    if n > 1:
+        np.cumsum(key_len[:-1], out=name_beg[1:n])
+    blob = b''.join(keys)
+    names = np.frombuffer(blob, dtype=np.uint8) if blob else np.zeros(1, np.uint8)
+    order, pair_id = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+    n_ids = ctypes.c_int64(0)
+    key_len = key_len if n else np.zeros(1, np.int32)
+    _check(_lib.load().dn_bam_pair_host(n, _ptr(name_beg, ctypes.c_int64), _ptr(key_len, ctypes.c_int32), _ptr(names, ctypes.c_uint8),
+                                        _ptr(order, ctypes.c_int32), _ptr(pair_id, ctypes.c_int32), ctypes.byref(n_ids)), 'dn_bam_pair_host')
+    return order[:n], pair_id[:n], int(n_ids.value)
+
+
 def cigar_strings(op_beg, n_op, ops):
     """pysam's cigarstring of every row (None for a row without ops)."""
     lens, codes = (ops >> 4).tolist(), (ops & 15).tolist()
@@ -561,7 +608,7 @@ def cigar_strings(op_beg, n_op, ops):
 class NativeBamReadsProcessor(BamReadsProcessor):
 
     def __init__(self, bam_file, index_file, chroms=None, n_jobs=1, output_dir=None, unique_alignment=True, verbose=True,
-                 window_bytes=256 << 20, inflate='host', frame='host', frame_segment_bytes=None, verify=False):
+                 window_bytes=256 << 20, inflate='host', frame='host', frame_segment_bytes=None, verify=False, pair='host'):
         """
         BamReadsProcessor on the library's own BAM reader: no pysam.  n_jobs sizes the thread pool that inflates BGZF
         blocks; window_bytes bounds the inflated bytes held (on the host and on the device) besides the chromosome's rows.
@@ -572,13 +619,20 @@ class NativeBamReadsProcessor(BamReadsProcessor):
         the library's default).  timing then has frame_device_ms and frame_fixups instead of frame_s.
         verify=True compares every block that is inflated -- by either side, and also for the header and the strand check
         -- with the CRC32 of its trailer; a block that differs is a ValueError naming the file and the block's offset.
+        pair='host' pairs the mates of a paired-end file on the host, in the reference's order (pair_order); pair='device'
+        pairs them on the GPU, equal keys in file order (DeviceRows.pair), with either inflate and frame; timing then has
+        pair_device_ms.  Coverage can differ between the two only where a pair's mates overlap on the reference.  No effect on
+        a single-end file, nor on load_chromosome_reads.
         """
         if inflate not in ('host', 'device'):
             raise ValueError("inflate must be 'host' or 'device', not {0!r}".format(inflate))
         if frame not in ('host', 'device'):
             raise ValueError("frame must be 'host' or 'device', not {0!r}".format(frame))
+        if pair not in ('host', 'device'):
+            raise ValueError("pair must be 'host' or 'device', not {0!r}".format(pair))
         self.inflate = inflate
         self.frame = frame
+        self.pair = pair
         self.frame_segment_bytes = frame_segment_bytes
         self.verify = bool(verify)
         self.window_bytes = max(int(window_bytes), 1)
@@ -768,9 +822,11 @@ class NativeBamReadsProcessor(BamReadsProcessor):
         try:
             n_reads = rows.info()[0]
             t0 = time.perf_counter()
-            counts, ol_cov, idx, val, n_iso_reads, ms = rows.coverage(ann)
+            counts, ol_cov, idx, val, n_iso_reads, ms = rows.coverage(ann, self.pair)
             self.timing['coverage_s'] = self.timing.get('coverage_s', 0.0) + time.perf_counter() - t0
             self.timing['coverage_device_ms'] = self.timing.get('coverage_device_ms', 0.0) + ms
+            if self.pair == 'device':
+                self.timing['pair_device_ms'] = self.timing.get('pair_device_ms', 0.0) + rows.pair_ms
         finally:
             rows.close()
         csr, ol_cov_dict, read_counts = coverage_outputs(ann, counts, ol_cov, idx, val, n_iso_reads)

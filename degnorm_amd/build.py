@@ -5,7 +5,7 @@ In-tree build of libdegnorm_amd.so (HIP kernels + C ABI) for gfx950 with hipcc.
 
 One translation unit per sample count p (dn_inst.hip -DDN_P=p), the run-time-p family (dn_generic.hip, compiled three
 times: 256- and 64-thread builds on float32 counts, a 256-thread build on float64 input), the coverage-assembly,
-reads-processing, BGZF-inflate, BGZF-deflate, record-framing, BAM-index, BAM-sort and GTF-scan units plus the C-ABI unit; objects are compiled
+reads-processing, mate-pairing, BGZF-inflate, BGZF-deflate, record-framing, BAM-index, BAM-sort and GTF-scan units plus the C-ABI unit; objects are compiled
 in parallel and linked into degnorm_amd/libdegnorm_amd.so.  hipcc cross-compiles without a GPU.  The host-side units (HOST_UNITS
 and the C-ABI unit) are rebuilt when include/degnorm_amd.h or any header under csrc/ changes (dn_host.hpp, dn_bam_record.hpp --
 what a BAM record is -- and the units' own headers).
@@ -52,6 +52,7 @@ def sched_flags(p):
 # the host-side units besides the C-ABI unit, one object each: source csrc/<name>.hip, object <name>.o
 HOST_UNITS = ('dn_assemble',    # per-gene coverage assembly
               'dn_reads',       # reads -> coverage / read counts (BamReadsProcessor, reads.py)
+              'dn_pair',        # qname_unpaired keys -> mate order and pair ids (DeviceRows.pair, bam.pair_rows)
               'dn_inflate',     # BGZF blocks -> inflated bytes (NativeBamReadsProcessor inflate='device', bam.py)
               'dn_deflate',     # byte ranges -> BGZF blocks (bam.bgzf_deflate, bam.sort_bam deflate='native')
               'dn_frame',       # inflated BAM bytes -> record offsets (NativeBamReadsProcessor frame='device', bam.py)

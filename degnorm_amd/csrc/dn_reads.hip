@@ -30,6 +30,7 @@
 #include "dn_inflate.hpp"
 #include "dn_frame.hpp"
 #include "dn_bam_record.hpp"
+#include "dn_pair.hpp"
 
 namespace {
 
@@ -366,20 +367,21 @@ struct CoverageIO {
 };
 
 // The coverage stages on n_rows device-resident rows (positions d_pos, CIGARs `cig`), queued on `st` after whatever the
-// caller queued there (its uploads).  pair_id (host, paired only) is uploaded here.  cigar_text(r) gives row r's CIGAR
-// as text for the error messages.
+// caller queued there (its uploads).  pair_id (host, paired only) is checked and uploaded here; d_pair_id, when not NULL,
+// is the same array already on the device and the library's own (dn_bam_rows_pair): pair_id is then not read.
+// cigar_text(r) gives row r's CIGAR as text for the error messages.
 template <class C>
 int coverage_stages(hipStream_t st, int32_t paired, int64_t n_rows, const int64_t *d_pos, C cig, const int32_t *pair_id,
-                    int64_t n_pair_ids, const CoverageIO &io, const std::function<std::string(int64_t)> &cigar_text)
+                    const int32_t *d_pair_id, int64_t n_pair_ids, const CoverageIO &io, const std::function<std::string(int64_t)> &cigar_text)
 {
     const int64_t chrom_len = io.chrom_len, n_exon = io.n_exon, n_groups = io.n_groups, n_iso = io.n_iso, n_iso_union = io.n_iso_union,
                   n_genes = io.n_genes, csr_cap = io.csr_cap;
     if (n_rows < 0 || n_rows > INT32_MAX - 1 || chrom_len <= 0 || chrom_len > INT32_MAX - 4 || n_exon < 0 || n_groups < 0 || n_iso < 0 || n_iso_union < 0 ||
-        n_genes < 0 || !io.counts || !io.nnz || !io.n_isolated_reads || (paired && n_rows > 0 && (!pair_id || n_pair_ids < 1)) ||
+        n_genes < 0 || !io.counts || !io.nnz || !io.n_isolated_reads || (paired && n_rows > 0 && ((!pair_id && !d_pair_id) || n_pair_ids < 1)) ||
         (n_groups > 0 && (!io.group_iv || !io.group_gene_off || !io.ol_cov || !io.ol_cov_off)) ||
         (n_iso > 0 && (!io.iso_iv || !io.iso_gene || !io.iso_union)) || csr_cap < 0 || (csr_cap > 0 && (!io.csr_idx || !io.csr_val)))
         return dn::fail(DN_E_INVALID, "dn_read_coverage: bad argument");
-    if (paired)
+    if (paired && !d_pair_id)
         for (int64_t r = 0; r < n_rows; r++)
             if (pair_id[r] < 0 || pair_id[r] >= n_pair_ids) return dn::fail(DN_E_INVALID, "dn_read_coverage: pair id out of range");
     const int32_t *group_gene_off = io.group_gene_off, *ol_gene = io.ol_gene, *ol_exon_off = io.ol_exon_off, *iso_gene = io.iso_gene;
@@ -407,6 +409,7 @@ int coverage_stages(hipStream_t st, int32_t paired, int64_t n_rows, const int64_
     unsigned long long h_err[3], h_niso = 0;         // what the stream copies to the host
     int h_nsel = 0;
     int32_t survivors = 0;
+    const int32_t *p_pid = d_pair_id;                // the pair ids the kernels read: the caller's, or the upload in d_pid
     std::vector<int> h_counts(n_genes > 0 ? n_genes : 1);
     return dn::synced(st, [&]() -> int {
         DN_TRY(e0.create(hipEventCreate));
@@ -422,7 +425,8 @@ int coverage_stages(hipStream_t st, int32_t paired, int64_t n_rows, const int64_
         DN_TRY(alloc_padded(d_csr_idx, chrom_len)); DN_TRY(alloc_padded(d_csr_val, chrom_len)); DN_TRY(alloc_padded(d_nsel, 1));
         DN_TRY(alloc_padded(d_niso, 1)); DN_TRY(alloc_padded(d_err, 3));
         if (paired) {
-            DN_TRY(alloc_padded(d_pid, n_rows)); DN_TRY(alloc_padded(d_pcnt, n_pair_ids)); DN_TRY(alloc_padded(d_rank, n_rows + 1));
+            if (!d_pair_id) { DN_TRY(alloc_padded(d_pid, n_rows)); p_pid = d_pid; }
+            DN_TRY(alloc_padded(d_pcnt, n_pair_ids)); DN_TRY(alloc_padded(d_rank, n_rows + 1));
             DN_TRY(alloc_padded(d_rows, n_rows));
         }
 #define H2D(d, h, n) do { if ((n) > 0) DN_TRY(hipMemcpyAsync(d, h, sizeof(*(d)) * (size_t) (n), hipMemcpyHostToDevice, st)); } while (0)
@@ -430,7 +434,7 @@ int coverage_stages(hipStream_t st, int32_t paired, int64_t n_rows, const int64_
         H2D(d_olg, ol_gene, n_ol); H2D(d_gs0, io.ol_gene_start0, n_ol); H2D(d_coff, ol_cov_off, n_ol > 0 ? n_ol + 1 : 0);
         H2D(d_oxo, ol_exon_off, n_ol > 0 ? n_ol + 1 : 0); H2D(d_oex, io.ol_exon_bounds, 2 * n_ol_exon);
         H2D(d_iiv, io.iso_iv, 2 * n_iso); H2D(d_ig, iso_gene, n_iso); H2D(d_iu, io.iso_union, 2 * n_iso_union);
-        if (paired) H2D(d_pid, pair_id, n_rows);
+        if (paired && !d_pair_id) H2D(d_pid, pair_id, n_rows);
 #undef H2D
         DN_TRY(hipEventRecord(e0, st));
         DN_TRY(hipMemsetAsync(d_counts, 0, sizeof(int) * (size_t) (n_genes > 0 ? n_genes : 1), st));
@@ -441,11 +445,11 @@ int coverage_stages(hipStream_t st, int32_t paired, int64_t n_rows, const int64_
         if (paired) DN_TRY(hipMemsetAsync(d_pcnt, 0, sizeof(int32_t) * (size_t) n_pair_ids, st));
         if (n_rows > 0) {
             hipLaunchKernelGGL(k_prefilter<C>, dim3(dn::grid_for(n_rows, kNT, kGridCap)), dim3(kNT), 0, st, n_rows, d_pos, cig, io.keep_lo, io.keep_hi,
-                               paired ? d_pid.get() : (const int32_t *) nullptr, d_pcnt, d_end, d_keep);
+                               paired ? p_pid : (const int32_t *) nullptr, d_pcnt, d_end, d_keep);
             DN_TRY(hipGetLastError());
             int64_t n_units = n_rows;
             if (paired) {
-                hipLaunchKernelGGL(k_pair_flag, dim3(dn::grid_for(n_rows, kNT, kGridCap)), dim3(kNT), 0, st, n_rows, d_pid, d_pcnt, d_keep);
+                hipLaunchKernelGGL(k_pair_flag, dim3(dn::grid_for(n_rows, kNT, kGridCap)), dim3(kNT), 0, st, n_rows, p_pid, d_pcnt.get(), d_keep.get());
                 DN_TRY(hipGetLastError());
                 // exclusive rank of every surviving row; rank[n_rows] is the number of survivors
                 DN_TRY(hipMemsetAsync(d_keep + n_rows, 0, sizeof(int32_t), st));       // keep[n_rows] = 0: rank[n_rows] = #survivors
@@ -556,7 +560,7 @@ extern "C" int dn_read_coverage(int device, int32_t paired, int64_t n_rows, cons
             DN_TRY(hipMemcpyAsync(d_off, cigar_off, sizeof(int64_t) * (size_t) (n_rows + 1), hipMemcpyHostToDevice, st));
         }
         if (n_bytes > 0) DN_TRY(hipMemcpyAsync(d_cig, cigar, (size_t) n_bytes, hipMemcpyHostToDevice, st));
-        return coverage_stages(st, paired, n_rows, d_pos, StrCigars{d_off, d_cig}, pair_id, n_pair_ids, io, [&](int64_t r) {
+        return coverage_stages(st, paired, n_rows, d_pos, StrCigars{d_off, d_cig}, pair_id, nullptr, n_pair_ids, io, [&](int64_t r) {
             return std::string((const char *) cigar + cigar_off[r], (size_t) (cigar_off[r + 1] - cigar_off[r]));
         });
     });
@@ -806,6 +810,11 @@ struct dn_bam_rows_s {
     int64_t frame_segment = 0, frame_segments = 0, frame_fixups = 0;
     double frame_ms = 0.0, framed_decode_ms = 0.0;
     int32_t last_pos = INT32_MIN;
+    // dn_bam_rows_pair: the rows in qname_unpaired order and the pair id of each row of that order, for the n_rows there
+    // were then (has_pairing; an append of rows ends it), and the number of ids
+    dn::DeviceBuffer<int32_t> pair_order, pair_id;
+    int64_t n_pair_ids = 0;
+    bool has_pairing = false;
     std::string no_cigar;                  // the name of the first kept row without CIGAR ops ("" while there is none)
     bool has_no_cigar = false;
 };
@@ -945,6 +954,7 @@ int append_window(dn_bam_rows h, const uint8_t *window, int64_t n_bytes, int64_t
             DN_TRY(hipGetLastError());
             DN_TRY(hipStreamSynchronize(st));
             h->n_rows += tot[0];
+            h->has_pairing = false;
             h->n_ops += tot[1];
             h->n_names += tot[2];
         }
@@ -1201,6 +1211,44 @@ extern "C" int dn_bam_rows_fetch(dn_bam_rows h, int64_t *pos, int64_t *op_beg, i
     });
 }
 
+extern "C" int dn_bam_rows_pair(dn_bam_rows h, int32_t *order_out, int32_t *pair_id_out, int64_t *n_pair_ids, double *device_ms)
+{
+    dn::clear_error();
+    if (!h || !h->F.paired || h->n_rows > INT32_MAX) return dn::fail(DN_E_INVALID, "dn_bam_rows_pair: bad argument (a paired store of fewer than 2^31 rows)");
+    const int64_t n = h->n_rows;
+    hipStream_t st = h->st;
+    int32_t mk = 0, last_id = -1;                    // what the stream copies to the host
+    dn::PairWork work;
+    dn::Event e0, e1;
+    h->has_pairing = false;
+    h->n_pair_ids = 0;
+    if (n_pair_ids) *n_pair_ids = 0;
+    if (device_ms) *device_ms = 0.0;
+    DN_TRY(hipSetDevice(h->device));
+    return dn::synced(st, [&]() -> int {
+        if (n > 0) {
+            DN_TRY(e0.create(hipEventCreate));
+            DN_TRY(e1.create(hipEventCreate));
+            DN_TRY(hipMemcpyAsync(&mk, h->max_key, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            DN_TRY(hipStreamSynchronize(st));
+            DN_TRY(alloc_padded(h->pair_order, (size_t) n)); DN_TRY(alloc_padded(h->pair_id, (size_t) n));
+            DN_TRY(hipEventRecord(e0, st));
+            const int rc = dn::pair_device(st, n, mk, h->name_beg, h->key_len, h->names, work, h->pair_order, h->pair_id);
+            if (rc != DN_OK) return rc;
+            DN_TRY(hipEventRecord(e1, st));
+            DN_TRY(hipMemcpyAsync(&last_id, h->pair_id + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            if (order_out) DN_TRY(hipMemcpyAsync(order_out, h->pair_order, sizeof(int32_t) * (size_t) n, hipMemcpyDeviceToHost, st));
+            if (pair_id_out) DN_TRY(hipMemcpyAsync(pair_id_out, h->pair_id, sizeof(int32_t) * (size_t) n, hipMemcpyDeviceToHost, st));
+            DN_TRY(hipStreamSynchronize(st));
+            if (device_ms) { float ms = 0.f; DN_TRY(hipEventElapsedTime(&ms, e0, e1)); *device_ms = ms; }
+            h->n_pair_ids = (int64_t) last_id + 1;
+        }
+        h->has_pairing = true;
+        if (n_pair_ids) *n_pair_ids = h->n_pair_ids;
+        return DN_OK;
+    });
+}
+
 extern "C" int dn_bam_rows_coverage(dn_bam_rows h, const int32_t *order, const int32_t *pair_id, int64_t n_pair_ids,
                                     int64_t chrom_len, int64_t keep_lo, int64_t keep_hi,
                                     int64_t n_exon, const int64_t *exon_iv,
@@ -1214,7 +1262,9 @@ extern "C" int dn_bam_rows_coverage(dn_bam_rows h, const int32_t *order, const i
                                     int64_t *n_isolated_reads, double *device_ms)
 {
     dn::clear_error();
-    if (!h || (h->F.paired && h->n_rows > 0 && !order)) return dn::fail(DN_E_INVALID, "dn_bam_rows_coverage: bad argument");
+    if (!h) return dn::fail(DN_E_INVALID, "dn_bam_rows_coverage: bad argument");
+    const bool resident = h->F.paired && h->n_rows > 0 && !order && !pair_id && h->has_pairing;     // the pairing of dn_bam_rows_pair
+    if (h->F.paired && h->n_rows > 0 && !order && !resident) return dn::fail(DN_E_INVALID, "dn_bam_rows_coverage: bad argument");
     if (h->has_no_cigar) return dn::fail(DN_E_INVALID, "read " + h->no_cigar + " has no CIGAR string");     // the reference's CIGAR regex on cigarstring None
     COVERAGE_IO;
     const int64_t n = h->n_rows;
@@ -1236,9 +1286,21 @@ extern "C" int dn_bam_rows_coverage(dn_bam_rows h, const int32_t *order, const i
                                h->n_op.get(), g_pos.get(), g_beg.get(), g_cnt.get());
             DN_TRY(hipGetLastError());
             p_pos = g_pos; p_beg = g_beg; p_cnt = g_cnt;
+        } else if (resident) {                                  // the same rows in the store's own order: nothing to check or upload
+            DN_TRY(alloc_padded(g_pos, n)); DN_TRY(alloc_padded(g_beg, n)); DN_TRY(alloc_padded(g_cnt, n));
+            hipLaunchKernelGGL(k_bam_gather, dim3(dn::grid_for(n, kNT, kGridCap)), dim3(kNT), 0, st, n, (const int32_t *) h->pair_order.get(), h->pos.get(),
+                               h->op_beg.get(), h->n_op.get(), g_pos.get(), g_beg.get(), g_cnt.get());
+            DN_TRY(hipGetLastError());
+            p_pos = g_pos; p_beg = g_beg; p_cnt = g_cnt;
         }
-        return coverage_stages(st, h->F.paired, n, p_pos, BamCigars{p_beg, p_cnt, h->ops}, pair_id, n_pair_ids, io, [&](int64_t r) {
-            const int64_t s = h_order.empty() ? r : h_order[r];
+        return coverage_stages(st, h->F.paired, n, p_pos, BamCigars{p_beg, p_cnt, h->ops}, pair_id, resident ? h->pair_id.get() : nullptr,
+                               resident ? h->n_pair_ids : n_pair_ids, io, [&](int64_t r) {
+            int64_t s = h_order.empty() ? r : h_order[r];
+            if (resident) {
+                int32_t o = -1;
+                if (hipMemcpy(&o, h->pair_order + r, sizeof(o), hipMemcpyDeviceToHost) != hipSuccess || o < 0 || o >= n) return std::string("?");
+                s = o;
+            }
             int64_t beg = 0;
             int32_t cnt = 0;
             std::vector<uint32_t> ops;

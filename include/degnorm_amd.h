@@ -286,6 +286,21 @@ const char *dn_reads_last_error(void);             /* = dn_last_error() */
  *   dn_bam_rows_coverage  dn_read_coverage on the stored rows, taken in `order` (row indices; required when paired, NULL for
  *                         file order) with pair_id[k] the pair id of the k-th row taken.  A kept row without CIGAR ops gives
  *                         DN_E_INVALID naming the read (the reference's regex fails on cigarstring None).
+ *                         A paired store that dn_bam_rows_pair has paired also takes order == NULL and pair_id == NULL: the
+ *                         call then reads the store's own two arrays where they lie, and n_pair_ids is ignored.
+ *   dn_bam_rows_pair      pair the mates of a paired store on its device (csrc/dn_pair.hip) and keep the result there:
+ *                         `order`, the rows in ascending qname_unpaired order, and `pair_id`, for every position of that
+ *                         order the number of distinct keys before it; *n_pair_ids = the last id + 1 (0 for no rows).
+ *                         Keys compare as unsigned bytes, zero-padded to the longest key (a key that is a prefix of
+ *                         another comes first), and rows of equal key stay in ascending row order, which is file order:
+ *                         order is np.argsort(keys, kind='stable') on the keys of dn_bam_rows_keys.  This is not the
+ *                         reference's order for equal keys -- there pandas' quicksort leaves the two mates of a pair in
+ *                         an order of its own making -- and the clipping of a pair's second mate against its first is
+ *                         not symmetric; the results can differ only for pairs whose mates overlap on the reference.
+ *                         order_out / pair_id_out (n_rows each, nullable) receive copies, for tests.  An unpaired store
+ *                         is DN_E_INVALID.  Rows appended later end the pairing.
+ *   dn_bam_pair_host      host only: the same order and ids for n keys names[name_beg[r] .. name_beg[r] + key_len[r]),
+ *                         by the same passes with std::stable_sort; n below 2^31.
  *   dn_bam_cigar_bounds   dn_reads_cigar_bounds on binary CIGARs: row r's ops are ops[op_off[r] .. op_off[r+1]).
  * Errors: dn_reads_last_error(). */
 typedef struct dn_bam_rows_s *dn_bam_rows;
@@ -309,6 +324,9 @@ int  dn_bam_rows_coverage(dn_bam_rows h, const int32_t *order, const int32_t *pa
                           int64_t n_genes, int64_t *counts, int64_t *ol_cov,
                           int64_t csr_cap, int64_t *nnz, int32_t *csr_idx, int64_t *csr_val,
                           int64_t *n_isolated_reads, double *device_ms);
+int  dn_bam_rows_pair(dn_bam_rows h, int32_t *order_out, int32_t *pair_id_out, int64_t *n_pair_ids, double *device_ms);
+int  dn_bam_pair_host(int64_t n, const int64_t *name_beg, const int32_t *key_len, const uint8_t *names, int32_t *order,
+                      int32_t *pair_id, int64_t *n_pair_ids);
 int  dn_bam_cigar_bounds(int device, int64_t n, const int64_t *pos, const int64_t *op_off, const uint32_t *ops,
                          int32_t max_seg, int32_t *nseg, int64_t *bounds, int64_t *end_pos);
 

@@ -12,18 +12,20 @@ indexed BAM, and on a paired variant (the same reads named <i // 2>.1 / .2, mate
   decode_ms         the append calls: window upload, decode / filter kernels, compaction into the row store (with --frame
                     device the library's own clock around decode and compaction; the upload of a host-inflated window is
                     upload_ms then)
-  coverage_ms       the coverage call on the stored rows (paired: with the key download and the host sort)
+  coverage_ms       the coverage call on the stored rows (paired: with the key download and the host sort, or with
+                    --pair device the pairing on the device)
+  pair_device_ms    the pairing on the device alone, by events (0 with --pair host and for single-end)
   coverage_device_ms  device time of the coverage stages (events on its stream)
   reads_per_s       end to end: reads / chromosome_coverage_read_counts (files written, index and header already read)
   in_memory_reads_per_s  chromosome_coverage_read_counts_df on the same reads held as a DataFrame
 
     python tools/bam_speed.py [--reads 2000000] [--jobs 4] [--reps 3] [--dir DIR] [--inflate host|device] [--level 1]
-                               [--frame host|device] [--segment-bytes N] [--cases se,pe]
+                               [--frame host|device] [--segment-bytes N] [--cases se,pe] [--pair host|device]
 
 --level is the deflate level of the written files (the fixture writer's level 1 on random sequence bytes is nearly
 literal-only; real files are level 6 and full of matches).  Files found in --dir from an earlier run with the same
 --reads and --level are used again.  Every case reports its best repetition (by e2e_ms) and, as *_min / *_max, the
-spread of inflate_ms and e2e_ms over the repetitions.  Prints one JSON line.  Needs a GPU.
+spread of inflate_ms, coverage_ms, pair_device_ms and e2e_ms over the repetitions.  Prints one JSON line.  Needs a GPU.
 """
 import argparse
 import json
@@ -46,11 +48,12 @@ from degnorm_amd import bam                          # noqa: E402
 from degnorm_amd import reads as dr                  # noqa: E402
 
 
-def _best(path, chrom, ov, gene_df, exon_df, out, jobs, reps, inflate, frame='host', segment_bytes=None, verify=False):
+def _best(path, chrom, ov, gene_df, exon_df, out, jobs, reps, inflate, frame='host', segment_bytes=None, verify=False, pair='host'):
     best, rows = None, []
+    shutil.rmtree(out, ignore_errors=True)            # of an earlier run in the same --dir: files that exist are not written again
     for k in range(reps + 1):                        # the first run loads the library and warms the device up
         proc = bam.NativeBamReadsProcessor(path, path + '.bai', output_dir=os.path.join(out, str(k)), n_jobs=jobs, verbose=False,
-                                           inflate=inflate, frame=frame, frame_segment_bytes=segment_bytes, verify=verify)
+                                           inflate=inflate, frame=frame, frame_segment_bytes=segment_bytes, verify=verify, pair=pair)
         os.makedirs(proc.save_dir, exist_ok=True)
         proc.timing = {}
         t0 = time.perf_counter()
@@ -60,15 +63,16 @@ def _best(path, chrom, ov, gene_df, exon_df, out, jobs, reps, inflate, frame='ho
         row = {'inflate_ms': 1e3 * t.get('inflate_s', 0), 'inflate_device_ms': t.get('inflate_device_ms', 0),
                'frame_ms': 1e3 * t.get('frame_s', 0), 'frame_device_ms': t.get('frame_device_ms', 0),
                'frame_fixups': t.get('frame_fixups', 0), 'upload_ms': 1e3 * t.get('upload_s', 0), 'decode_ms': 1e3 * t.get('decode_s', 0),
-               'coverage_ms': 1e3 * t.get('coverage_s', 0), 'coverage_device_ms': t.get('coverage_device_ms', 0), 'e2e_ms': 1e3 * e2e}
+               'coverage_ms': 1e3 * t.get('coverage_s', 0), 'coverage_device_ms': t.get('coverage_device_ms', 0), 'pair_device_ms': t.get('pair_device_ms', 0),
+               'e2e_ms': 1e3 * e2e}
         if k > 0:
             rows.append(row)
             if best is None or row['e2e_ms'] < best['e2e_ms']:
                 best = row
     best = {key: round(v, 3 if key.endswith('device_ms') else 1) for key, v in best.items()}
-    for key in ('inflate_ms', 'frame_ms', 'frame_device_ms', 'e2e_ms'):
-        best[key + '_min'] = round(min(r[key] for r in rows), 1)
-        best[key + '_max'] = round(max(r[key] for r in rows), 1)
+    for key in ('inflate_ms', 'frame_ms', 'frame_device_ms', 'coverage_ms', 'pair_device_ms', 'e2e_ms'):
+        best[key + '_min'] = round(min(r[key] for r in rows), 3 if key.endswith('device_ms') else 1)
+        best[key + '_max'] = round(max(r[key] for r in rows), 3 if key.endswith('device_ms') else 1)
     if inflate == 'device':                          # the kernel's own spread: what --verify is held against
         best['inflate_device_ms_min'] = round(min(r['inflate_device_ms'] for r in rows), 3)
         best['inflate_device_ms_max'] = round(max(r['inflate_device_ms'] for r in rows), 3)
@@ -85,6 +89,7 @@ def main():
     ap.add_argument('--level', type=int, default=1)
     ap.add_argument('--frame', choices=['host', 'device'], default='host')
     ap.add_argument('--segment-bytes', type=int, default=None, help='segment size of --frame device (default: the library\'s)')
+    ap.add_argument('--pair', choices=['host', 'device'], default='host', help='where the mates of the paired case are paired')
     ap.add_argument('--cases', default='se,pe', help='se, pe or se,pe')
     ap.add_argument('--verify', action='store_true', help='check every BGZF block against the CRC32 of its trailer')
     a = ap.parse_args()
@@ -107,14 +112,14 @@ def main():
             dr.chromosome_coverage_read_counts_df(reads, chrom_len, ov, gene_df, exon_df, False)
             dt = time.perf_counter() - t0
             in_mem = dt if in_mem is None else min(in_mem, dt)
-        out = {'tool': 'bam_speed', 'reads': a.reads, 'jobs': a.jobs, 'inflate': a.inflate, 'frame': a.frame, 'level': a.level,
+        out = {'tool': 'bam_speed', 'reads': a.reads, 'jobs': a.jobs, 'inflate': a.inflate, 'frame': a.frame, 'pair': a.pair, 'level': a.level,
                'bam_mb': round(os.path.getsize(files[cases[0]]) / 2 ** 20, 1), 'inflated_mb': round(inflated[cases[0]] / 2 ** 20, 1),
                'write_s': round(write_s, 1)}
         if a.verify:
             out['verify'] = True
         for name in cases:
-            row = _best(files[name], 'chrS', ov, gene_df, exon_df, os.path.join(work, 'out_{0}_{1}_{2}'.format(name, a.inflate, a.frame)),
-                        a.jobs, a.reps, a.inflate, a.frame, a.segment_bytes, a.verify)
+            row = _best(files[name], 'chrS', ov, gene_df, exon_df, os.path.join(work, 'out_{0}_{1}_{2}_{3}'.format(name, a.inflate, a.frame, a.pair)),
+                        a.jobs, a.reps, a.inflate, a.frame, a.segment_bytes, a.verify, a.pair)
             if row['inflate_device_ms'] > 0:
                 row['inflate_gbps'] = round(inflated[name] / (row['inflate_device_ms'] * 1e-3) / 1e9, 2)
             row['reads_per_s'] = round(a.reads / (row['e2e_ms'] * 1e-3))
