@@ -34,6 +34,11 @@ device the sorted stream is deflated where it lies, one block per wavefront, and
 Every path that inflates takes verify=True: the inflated bytes of each BGZF block are then compared with the CRC32 of its
 trailer -- zlib.crc32 where zlib inflates, the wavefront that inflates the block where the device does -- and a block that
 differs is a ValueError naming the file and the block's offset.  verify_bgzf checks a whole file that way (bgzip -t).
+
+The four drivers -- the reader's device_rows, build_index, sort_bam and verify_bgzf -- take their blocks from one window feed
+(_WindowFeed): it cuts the file, or one reference's index range, into windows by one rule (_window_cuts) and yields _Window
+items that inflate themselves on the host (_host_inflate, one error text for every driver) or go to a handle as they are.
+The handles that take windows have one shape (_WindowHandle): DeviceRows, _IndexBuilder (dn_bai_*) and _Sorter (dn_bam_sort_*).
 """
 import ctypes
 import itertools
@@ -139,10 +144,6 @@ def inflate_block(blk, verify=False):
     return data
 
 
-def _inflate_verified(blk):
-    return inflate_block(blk, True)
-
-
 def _block_error(path, offset, status):
     return '{0}: the BGZF block at byte {1} does not inflate: {2}'.format(path, offset, INFLATE_ERRORS.get(int(status), 'error {0}'.format(int(status))))
 
@@ -174,6 +175,19 @@ def _block_layout(blocks):
     return comp, p, pay_off, pay_len, isize
 
 
+def _out_offsets(isize, n):
+    """
+    Where the data of n blocks with these ISIZEs begins and ends when it is written back to back (n + 1 int64 offsets), or
+    (None, k) when block k, the largest, claims more than the 65536 bytes the library's decoder takes: the caller names it.
+    """
+    k = int(isize[:n].argmax()) if n else 0
+    if n and int(isize[k]) > 65536:
+        return None, k
+    out_off = np.zeros(n + 1, np.int64)
+    np.cumsum(isize[:n], out=out_off[1:])
+    return out_off, None
+
+
 def inflate_blocks(blocks, device=None, verify=False):
     """
     The data of whole BGZF blocks (as iter_blocks yields them), inflated by the library's own DEFLATE decoder: on the host
@@ -183,10 +197,9 @@ def inflate_blocks(blocks, device=None, verify=False):
     blocks = list(blocks)
     n = len(blocks)
     comp, n_comp, pay_off, pay_len, isize = _block_layout(blocks)
-    if n and int(isize[:n].max()) > 65536:
-        raise ValueError('BGZF block {0} claims an inflated size of {1} bytes'.format(int(isize[:n].argmax()), int(isize[:n].max())))
-    out_off = np.zeros(n + 1, np.int64)
-    np.cumsum(isize[:n], out=out_off[1:])
+    out_off, big = _out_offsets(isize, n)
+    if big is not None:
+        raise ValueError('BGZF block {0} claims an inflated size of {1} bytes'.format(big, int(isize[big])))
     out = np.zeros(int(out_off[-1]) + 1, np.uint8)
     status = np.zeros(max(n, 1), np.int32)
     i64, i32, u8 = ctypes.c_int64, ctypes.c_int32, ctypes.c_uint8
@@ -217,22 +230,37 @@ def _raise_block_status(path, batch, status):
     _raise_status(status[:len(batch)], lambda k: '{0}: the BGZF block at byte {1}'.format(path, batch[k][0]))
 
 
-def _batched(blocks, window_bytes, size=0):
+def _isize(blk):
+    """The ISIZE of a whole BGZF block: the inflated size its trailer claims."""
+    return struct.unpack_from('<I', blk, len(blk) - 4)[0]
+
+
+def _window_cuts(sizes, window_bytes, size0=0):
     """
-    Lists of the (file offset, block) pairs that `blocks` yields: a list ends with the block that brings its inflated data to
-    window_bytes.  size: what the first list counts before its first block (negative: bytes of that block that are not its).
-    A loop over whole files drops its list (`del batch`) when it is done with it: otherwise the blocks of one window stay
-    allocated while the next window's are read, which costs more than the marshalling of a window does.
+    The cut rule of every window loop: the number of items of each window over items of these sizes, in order.  A window ends
+    with the item that brings its size to window_bytes; the first window starts counting at size0 (negative: bytes of its first
+    item that are not its), every later one at 0, and the last takes what is left.
     """
-    batch = []
-    for off, blk in blocks:
-        batch.append((off, blk))
-        size += struct.unpack_from('<I', blk, len(blk) - 4)[0]
+    n, size = 0, size0
+    for s in sizes:
+        n, size = n + 1, size + s
         if size >= window_bytes:
-            yield batch
-            batch, size = [], 0
-    if batch:
-        yield batch
+            yield n
+            n, size = 0, 0
+    if n:
+        yield n
+
+
+def _batched(blocks, window_bytes, size=0, weigh=lambda ob: _isize(ob[1])):
+    """
+    Lists of the (file offset, block) pairs that `blocks` yields, cut by _window_cuts on the blocks' ISIZEs (size: its size0;
+    weigh: the size of an item of another kind).  A loop over whole files drops its list (`del batch`) when it is done with it:
+    otherwise the blocks of one window stay allocated while the next window's are read, which costs more than the marshalling of
+    a window does.  This generator keeps no reference to a list it has yielded.
+    """
+    blocks, weighed = itertools.tee(blocks)
+    for n in _window_cuts(map(weigh, weighed), window_bytes, size):
+        yield list(itertools.islice(blocks, n))
 
 
 def _block_args(blocks):
@@ -257,20 +285,126 @@ def _window_args(blocks, verify=False, expect_crc=None):
     return args + (_ptr(isize32, ctypes.c_int32),), status
 
 
-def _zlib_inflate(path, batch, pool, verify=False):
+def _host_inflate(path, batch, pool, verify=False):
     """
-    The data of the blocks of batch, in file order, by zlib (in pool, when there is one).  verify: the first block whose data
-    does not have the CRC32 of its trailer is a BgzfCrcError (a ValueError) naming the file and its offset.
+    The data of the blocks of batch, in file order, by zlib (in pool, when there is one; verify: and their CRC32s by
+    zlib.crc32, in the same pool).  The first block that fails is a ValueError naming the file and its offset with the text of the
+    library's own decoder; one whose data does not have the CRC32 of its trailer is a BgzfCrcError (a ValueError).
     """
     blocks = [b for _, b in batch]
-    one = _inflate_verified if verify else inflate_block
+    one = (lambda blk: inflate_block(blk, True)) if verify else inflate_block
     data = []
     try:
         for d in (pool.map(one, blocks) if pool is not None else map(one, blocks)):      # in file order: the first bad block raises
             data.append(d)
     except BgzfCrcError:                                 # the blocks before it were good: this is the one, whatever its ISIZE
         raise BgzfCrcError(_block_error(path, batch[len(data)][0], INFLATE_E_CRC))
+    except (zlib.error, ValueError, struct.error) as e:  # the library's host decoder finds the block and the words
+        args, isize, status = _block_args(blocks)
+        out_off, big = _out_offsets(isize, len(blocks))
+        if big is None:
+            out = np.zeros(int(out_off[-1]) + 1, np.uint8)
+            crc = _ptr(block_crcs(blocks), ctypes.c_uint32) if verify else None
+            args += (_ptr(out_off, ctypes.c_int64), _ptr(out, ctypes.c_uint8), _ptr(status, ctypes.c_int32), crc)
+            _check(_lib.load().dn_bgzf_inflate_check_host(*args), 'dn_bgzf_inflate_check_host')
+            _raise_block_status(path, batch, status)
+        raise ValueError('{0}: a BGZF block at or after byte {1} does not inflate: {2}'.format(path, batch[0][0], e))
     return data
+
+
+# --- the window feed -----------------------------------------------------------------------------------------------------
+
+class _Closing(object):
+    """The with statement for an object with close()."""
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class _Window(object):
+    """
+    One window of a _WindowFeed: `batch`, the (file offset, block) pairs of whole BGZF blocks in file order; head_skip, the
+    bytes of the first block's data that are not the window's; tail_keep, the bytes of the last block's data that are (-1: all
+    of them).  verify is the feed's.
+    """
+
+    def __init__(self, feed, batch, head_skip=0, tail_keep=-1):
+        self.feed, self.batch, self.head_skip, self.tail_keep, self.verify = feed, batch, int(head_skip), int(tail_keep), feed.verify
+
+    @property
+    def blocks(self):
+        return [blk for _, blk in self.batch]
+
+    def host_data(self):
+        """The data of every block, whole, by zlib in the feed's pool (_host_inflate: its errors name the file and the block)."""
+        return _host_inflate(self.feed.path, self.batch, self.feed.pool, self.verify)
+
+    def host_bytes(self):
+        """The window's bytes: the blocks' data joined, without what head_skip and tail_keep leave out."""
+        data = self.host_data()
+        if self.tail_keep >= 0:
+            data[-1] = data[-1][:self.tail_keep]
+        if self.head_skip:
+            data[0] = data[0][self.head_skip:]
+        return b''.join(data)
+
+    def check(self, status):
+        """ValueError naming the file and the first block whose status, as a device entry point filled it, is not 0."""
+        _raise_block_status(self.feed.path, self.batch, status)
+
+
+class _WindowFeed(_Closing):
+    """
+    The BGZF windows of one file, for every driver that reads one (the reader, build_index, sort_bam, verify_bgzf): the path,
+    window_bytes (None: 256 MiB), verify, and the zlib thread pool of a caller that inflates on the host (n_jobs > 1; a caller
+    that inflates on the device passes 1), shut down by close() or the with statement.  Refuses a file without BGZF's
+    end-of-file block.  whole() and reference() yield _Window items cut by _window_cuts.
+    """
+
+    def __init__(self, path, window_bytes=None, verify=False, n_jobs=1):
+        if not has_eof_block(path):
+            raise ValueError('{0}: no BGZF end-of-file block; the file is truncated'.format(path))
+        self.path, self.verify = path, bool(verify)
+        self.window_bytes = max(int(256 << 20 if window_bytes is None else window_bytes), 1)
+        self.pool = ThreadPoolExecutor(max_workers=int(n_jobs)) if int(n_jobs) > 1 else None
+
+    def close(self):
+        if self.pool is not None:
+            self.pool.shutdown()
+            self.pool = None
+
+    def header(self):
+        """_header_data of the file: on zlib whatever the device, since the header may span several blocks."""
+        return _header_data(self.path, self.verify)
+
+    def whole(self, first=0, size0=0, head_skip=0):
+        """
+        The windows of the whole file from block `first` on; the first window leaves out head_skip bytes of that block's data and
+        starts counting at size0.
+        """
+        return self._windows(itertools.islice(iter_blocks(self.path), first, None), size0, head_skip)
+
+    def reference(self, rng):
+        """
+        The windows of the blocks that hold the [begin, end) virtual offsets rng (reference_range; None: no window): the first
+        starts at begin's offset into its block, the last ends at end's.
+        """
+        if rng is None:
+            return iter(())
+        cbeg, ubeg, cend, uend = rng[0] >> 16, rng[0] & 0xffff, rng[1] >> 16, rng[1] & 0xffff
+        in_range = itertools.takewhile(lambda ob: ob[0] < cend or (ob[0] == cend and uend > 0), iter_blocks(self.path, cbeg))
+        return self._windows(in_range, 0, ubeg, cend, uend)
+
+    def _windows(self, blocks, size0, head_skip, cend=-1, uend=-1):
+        for batch in _batched(blocks, self.window_bytes, size0):
+            win = _Window(self, batch, head_skip, uend if batch[-1][0] == cend else -1)
+            del batch                                    # the item holds the only reference to its blocks
+            yield win
+            # the caller is done with the window: its blocks go here, before those of the next window are read (_batched)
+            win.batch, head_skip = None, 0
 
 
 # --- header and index ----------------------------------------------------------------------------------------------------
@@ -302,15 +436,21 @@ def parse_header(data):
 
 def read_header(path, verify=False):
     """[(SQ name, length)] of a BAM file, in refID order.  verify: its blocks must have the CRC32s of their trailers."""
+    return _header_data(path, verify)[4]
+
+
+def _header_data(path, verify=False):
+    """
+    (inflated bytes of the blocks the BAM header lies in, their number, header end, the bytes of the last of these blocks that
+    belong to the header, [(SQ name, length)]).
+    """
     data = bytearray()
-    for off, blk in iter_blocks(path):
-        try:
-            data += inflate_block(blk, verify)
-        except BgzfCrcError:
-            raise ValueError(_block_error(path, off, INFLATE_E_CRC))
+    for k, (off, blk) in enumerate(iter_blocks(path)):
+        start = len(data)
+        data += _host_inflate(path, [(off, blk)], None, verify)[0]
         got = parse_header(data)
         if got is not None:
-            return got[1]
+            return bytes(data), k + 1, got[0], got[0] - start, got[1]
     raise ValueError('{0}: BAM header cut short'.format(path))
 
 
@@ -360,6 +500,13 @@ def reference_range(ref):
 
 # --- framing and the device row store ------------------------------------------------------------------------------------
 
+def _segment_arg(segment_bytes):
+    """The segment size of the framing as the library takes it: 0, its default, for None; ValueError below 64."""
+    if segment_bytes is not None and int(segment_bytes) < 64:
+        raise ValueError('segment_bytes must be at least 64, not {0}'.format(segment_bytes))
+    return int(segment_bytes or 0)
+
+
 def frame_records(buf, tid=-1, last_pos=_INT32_MIN, device=None, segment_bytes=None, stats=None):
     """
     Start offsets (int64) of the complete records of inflated BAM bytes, the bytes they span (the rest is a record cut by
@@ -382,9 +529,7 @@ def frame_records(buf, tid=-1, last_pos=_INT32_MIN, device=None, segment_bytes=N
         if stats is not None:
             stats.update(segments=0, fixups=0, device_ms=0.0)
         return off[:n.value], int(used.value), int(lp.value)
-    seg = 0 if segment_bytes is None else int(segment_bytes)
-    if seg != 0 and seg < 64:
-        raise ValueError('segment_bytes must be at least 64, not {0}'.format(segment_bytes))
+    seg = _segment_arg(segment_bytes or None)            # 0 is the library's default here too
     fix, ms = ctypes.c_int64(0), ctypes.c_double(0.0)
     args = (_ptr(a, ctypes.c_uint8), len(buf), int(tid), ctypes.byref(lp), seg, _ptr(off, ctypes.c_int64), cap, ctypes.byref(n),
             ctypes.byref(used), ctypes.byref(fix))
@@ -400,8 +545,39 @@ def frame_records(buf, tid=-1, last_pos=_INT32_MIN, device=None, segment_bytes=N
     return off[:n.value], int(used.value), int(lp.value)
 
 
-class DeviceRows(object):
+class _WindowHandle(_Closing):
+    """
+    What the library handles that take BGZF windows share -- DeviceRows (dn_bam_rows_*) here, _IndexBuilder (dn_bai_*) and _Sorter
+    (dn_bam_sort_*) below.  Each creates its handle `h` and names its `unit`; from here come close() (<unit>_destroy),
+    expect_crc() (<unit>_expect_crc), the arguments of the unit's device entry points, and call(), which names the file of a
+    handle that has a `path` in front of a ValueError.
+    """
+    unit, path = None, None
+
+    def close(self):
+        if self.h:
+            getattr(self.lib, self.unit + '_destroy')(self.h)
+            self.h = ctypes.c_void_p()
+
+    def call(self, rc, what):
+        try:
+            _check(rc, what)
+        except ValueError as e:
+            raise e if self.path is None else ValueError('{0}: {1}'.format(self.path, e))
+
+    def expect_crc(self, crc):
+        """<unit>_expect_crc: the next window inflated on the device checks its blocks against these CRC32s (one per block)."""
+        crc, what = np.ascontiguousarray(crc, dtype=np.uint32), self.unit + '_expect_crc'
+        self.call(getattr(self.lib, what)(self.h, _ptr(crc, ctypes.c_uint32) if len(crc) else None, len(crc)), what)
+
+    def window_args(self, blocks, verify=False):
+        """_window_args of a window's blocks; verify: their CRC32s are announced to this handle first."""
+        return _window_args(blocks, verify, self.expect_crc)
+
+
+class DeviceRows(_WindowHandle):
     """The device-resident rows of one chromosome (dn_bam_rows): kept records in file order."""
+    unit = 'dn_bam_rows'
 
     def __init__(self, tid, unique_alignment, paired, device=None):
         self.lib = _lib.load()
@@ -410,11 +586,6 @@ class DeviceRows(object):
         dev = int(os.environ.get('LOCAL_RANK', 0)) if device is None else int(device)
         _check(self.lib.dn_bam_rows_create(dev, int(tid), 1 if unique_alignment else 0, 1 if paired else 0,
                                            ctypes.byref(self.h)), 'dn_bam_rows_create')
-
-    def close(self):
-        if self.h:
-            self.lib.dn_bam_rows_destroy(self.h)
-            self.h = ctypes.c_void_p()
 
     def __del__(self):
         self.close()
@@ -426,18 +597,13 @@ class DeviceRows(object):
         _check(self.lib.dn_bam_rows_append(self.h, _ptr(a, ctypes.c_uint8), len(buf), _ptr(rec_off, ctypes.c_int64),
                                            len(rec_off)), 'dn_bam_rows_append')
 
-    def expect_crc(self, crc):
-        """dn_bam_rows_expect_crc: the next inflate / inflate_framed checks its blocks against these CRC32s (one per block)."""
-        crc = np.ascontiguousarray(crc, dtype=np.uint32)
-        _check(self.lib.dn_bam_rows_expect_crc(self.h, _ptr(crc, ctypes.c_uint32) if len(crc) else None, len(crc)), 'dn_bam_rows_expect_crc')
-
     def inflate(self, carry, blocks, head_skip, tail_keep, verify=False):
         """
         dn_bam_rows_inflate: the next window (carry + the inflated blocks, trimmed) built on the device.  Returns a view of
         the library's host copy of it (valid until the next call), the status of every block and the kernel's ms.
         verify: every block, all of it, must have the CRC32 of its trailer (status 8 otherwise).
         """
-        args, status = _window_args(blocks, verify, self.expect_crc)
+        args, status = self.window_args(blocks, verify)
         c = np.frombuffer(carry, dtype=np.uint8) if len(carry) else np.zeros(1, np.uint8)
         view, n_bytes, ms = ctypes.POINTER(ctypes.c_uint8)(), ctypes.c_int64(0), ctypes.c_double(0.0)
         args = (_ptr(c, ctypes.c_uint8), len(carry)) + args + (int(head_skip), int(tail_keep), ctypes.byref(view), ctypes.byref(n_bytes),
@@ -463,7 +629,7 @@ class DeviceRows(object):
         cuts stays there.  Returns the status of every block, the bytes carried over, and the ms of inflate and framing.
         verify: as for inflate.
         """
-        args, status = _window_args(blocks, verify, self.expect_crc)
+        args, status = self.window_args(blocks, verify)
         n_bytes, n_carry, ms, fms = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_double(0.0), ctypes.c_double(0.0)
         args += (int(head_skip), int(tail_keep), _ptr(status, ctypes.c_int32), ctypes.byref(n_bytes), ctypes.byref(n_carry), ctypes.byref(ms),
                  ctypes.byref(fms))
@@ -646,9 +812,7 @@ class NativeBamReadsProcessor(BamReadsProcessor):
 
     def _load(self):
         if self._refs is None:
-            if not has_eof_block(self.filename):
-                raise ValueError('{0}: no BGZF end-of-file block; the file is truncated'.format(self.filename))
-            self._refs = read_header(self.filename, self.verify)
+            self._refs = self._feed(False).header()[4]
             self._index, _ = read_bai(self.index_filename)
             if len(self._index) != len(self._refs):
                 raise ValueError('{0} indexes {1} references, {2} has {3}'.format(
@@ -659,41 +823,32 @@ class NativeBamReadsProcessor(BamReadsProcessor):
         self._load()
         return {name: length for name, length in self._refs}
 
-    def _batches(self, chrom, window_bytes=None):
-        """((file offset, block) of about window_bytes of inflated data, cbeg, ubeg, cend, uend) over chrom's index range."""
+    def _feed(self, host, window_bytes=None):
+        """The file's window feed (a context manager); host: with the pool of n_jobs threads that inflates its blocks here."""
+        return _WindowFeed(self.filename, window_bytes or self.window_bytes, self.verify, self.n_jobs if host else 1)
+
+    def _chrom_windows(self, feed, chrom):
+        """The feed's windows over chrom's index range."""
         self._load()
-        rng = reference_range(self._index[self._tid[chrom]])
-        if rng is None:
-            return
-        window_bytes = window_bytes or self.window_bytes
-        vbeg, vend = rng
-        cbeg, ubeg, cend, uend = vbeg >> 16, vbeg & 0xffff, vend >> 16, vend & 0xffff
-        in_range = itertools.takewhile(lambda ob: ob[0] < cend or (ob[0] == cend and uend > 0), iter_blocks(self.filename, cbeg))
-        for batch in _batched(in_range, window_bytes):
-            yield batch, cbeg, ubeg, cend, uend
+        return feed.reference(reference_range(self._index[self._tid[chrom]]))
+
+    def _batches(self, chrom, window_bytes=None):
+        """The windows over chrom's index range, for a caller that only walks them: no pool."""
+        return self._chrom_windows(self._feed(False, window_bytes), chrom)
 
     def windows(self, chrom, window_bytes=None):
         """
         Inflated bytes of the blocks that hold chrom's records, about window_bytes at a time; a record may be cut at the
         end of one window and continue in the next.  Adds host inflate seconds to self.timing['inflate_s'].
         """
-        pool = ThreadPoolExecutor(max_workers=int(self.n_jobs)) if int(self.n_jobs) > 1 else None
-        try:
-            for batch, cbeg, ubeg, cend, uend in self._batches(chrom, window_bytes):
-                yield self._inflate(batch, pool, cbeg, ubeg, cend, uend)
-        finally:
-            if pool is not None:
-                pool.shutdown()
+        self._load()
+        with self._feed(True, window_bytes) as feed:
+            for win in self._chrom_windows(feed, chrom):
+                yield self._inflate(win)
 
-    def _inflate(self, batch, pool, cbeg, ubeg, cend, uend):
+    def _inflate(self, win):
         t0 = time.perf_counter()
-        data = _zlib_inflate(self.filename, batch, pool, self.verify)
-        for k, (off, _) in enumerate(batch):
-            if off == cend:
-                data[k] = data[k][:uend]
-            if off == cbeg:
-                data[k] = data[k][ubeg:]
-        out = b''.join(data)
+        out = win.host_bytes()
         self.timing['inflate_s'] = self.timing.get('inflate_s', 0.0) + time.perf_counter() - t0
         return out
 
@@ -712,94 +867,73 @@ class NativeBamReadsProcessor(BamReadsProcessor):
         return names
 
     def device_rows(self, chrom, device=None):
-        """The chromosome's kept records as a DeviceRows store (file order)."""
+        """
+        The chromosome's kept records as a DeviceRows store (file order): one loop over the windows of its index range, in
+        which inflate and frame choose the store's entry point.  The record a window's end cuts is carried to the next
+        window: its bytes here, or (inflate and frame both 'device') their number, while the bytes wait on the device.
+        """
         self._load()
-        rows = DeviceRows(self._tid[chrom], self.unique_alignment, self.paired, device)
+        tid, t = self._tid[chrom], self.timing
+        host_inflate, host_frame = self.inflate == 'host', self.frame == 'host'
+        rows = DeviceRows(tid, self.unique_alignment, self.paired, device)
         carry, last = b'', _INT32_MIN
-        t = self.timing
+        calls = 0.0                         # frame='device': seconds in the library's one call per window; it splits them (frame_info)
+
+        def add(key, value):
+            t[key] = t.get(key, 0.0) + value
+
         try:
-            if self.frame == 'device':
-                return self._device_framed(chrom, rows)
-            if self.inflate == 'device':
-                return self._device_windows(chrom, rows)
-            for win in self.windows(chrom):
-                data = carry + win if carry else win
-                t0 = time.perf_counter()
-                off, used, last = frame_records(data, self._tid[chrom], last)
-                t1 = time.perf_counter()
-                rows.append(data, off)
-                t2 = time.perf_counter()
-                t['frame_s'] = t.get('frame_s', 0.0) + t1 - t0
-                t['decode_s'] = t.get('decode_s', 0.0) + t2 - t1
-                carry = data[used:]
-            if carry:
-                raise ValueError('{0}: a record of {1} is cut short at the end of its index range'.format(self.filename, chrom))
+            if not host_frame:
+                rows.frame_segment(self.frame_segment_bytes)
+            try:
+                with self._feed(host_inflate) as feed:
+                    for win in self._chrom_windows(feed, chrom):
+                        if host_inflate:
+                            data = self._inflate(win)
+                            data = carry + data if carry else data
+                        t0 = time.perf_counter()
+                        if host_inflate and host_frame:
+                            off, used, last = frame_records(data, tid, last)
+                            t1 = time.perf_counter()
+                            rows.append(data, off)
+                            add('frame_s', t1 - t0)
+                            add('decode_s', time.perf_counter() - t1)
+                            carry = data[used:]
+                        elif host_frame:
+                            data, status, ms = rows.inflate(carry, win.blocks, win.head_skip, win.tail_keep, self.verify)
+                            t1 = time.perf_counter()
+                            win.check(status)
+                            off, used, last = frame_records(data, tid, last)
+                            t2 = time.perf_counter()
+                            rows.append_resident(off)
+                            add('inflate_s', t1 - t0)
+                            add('inflate_device_ms', ms)
+                            add('frame_s', t2 - t1)
+                            add('decode_s', time.perf_counter() - t2)
+                            carry = data[used:].tobytes()
+                        elif host_inflate:
+                            used = rows.append_framed(data)
+                            calls += time.perf_counter() - t0
+                            carry = data[used:]
+                        else:
+                            status, carry, ms, _ = rows.inflate_framed(win.blocks, win.head_skip, win.tail_keep, self.verify)
+                            t1 = time.perf_counter()
+                            win.check(status)
+                            add('inflate_device_ms', ms)
+                            calls += t1 - t0
+                if carry:
+                    raise ValueError('{0}: a record of {1} is cut short at the end of its index range'.format(self.filename, chrom))
+            finally:
+                if not host_frame:
+                    _, fixups, ms, decode_ms = rows.frame_info()
+                    add('frame_device_ms', ms)
+                    t['frame_fixups'] = t.get('frame_fixups', 0) + fixups
+                    add('decode_s', 1e-3 * decode_ms)
+                    # what is left of the calls: the copy of the window (inflate='host') or of its blocks and their inflate ('device')
+                    add('inflate_s' if self.inflate == 'device' else 'upload_s', max(calls - 1e-3 * (ms + decode_ms), 0.0))
         except Exception:
             rows.close()
             raise
-        return rows
-
-    def _device_windows(self, chrom, rows):
-        """device_rows with inflate='device': every window is inflated into the row store and decoded where it lies."""
-        carry, last = b'', _INT32_MIN
-        t = self.timing
-        for batch, cbeg, ubeg, cend, uend in self._batches(chrom):
-            t0 = time.perf_counter()
-            data, status, ms = rows.inflate(carry, [b for _, b in batch], ubeg if batch[0][0] == cbeg else 0,
-                                            uend if batch[-1][0] == cend else -1, self.verify)
-            t1 = time.perf_counter()
-            _raise_block_status(self.filename, batch, status)
-            off, used, last = frame_records(data, self._tid[chrom], last)
-            t2 = time.perf_counter()
-            rows.append_resident(off)
-            t3 = time.perf_counter()
-            t['inflate_s'] = t.get('inflate_s', 0.0) + t1 - t0
-            t['inflate_device_ms'] = t.get('inflate_device_ms', 0.0) + ms
-            t['frame_s'] = t.get('frame_s', 0.0) + t2 - t1
-            t['decode_s'] = t.get('decode_s', 0.0) + t3 - t2
-            carry = data[used:].tobytes()
-        if carry:
-            raise ValueError('{0}: a record of {1} is cut short at the end of its index range'.format(self.filename, chrom))
-        return rows
-
-    def _device_framed(self, chrom, rows):
-        """device_rows with frame='device': every window is framed on the device, wherever it was inflated."""
-        t = self.timing
-        cut = '{0}: a record of {1} is cut short at the end of its index range'.format(self.filename, chrom)
-        rows.frame_segment(self.frame_segment_bytes)
-        calls = 0.0                         # seconds in the library's one call per window: it splits them (frame_info)
-        try:
-            if self.inflate == 'device':
-                n_carry = 0
-                for batch, cbeg, ubeg, cend, uend in self._batches(chrom):
-                    t0 = time.perf_counter()
-                    status, n_carry, ms, fms = rows.inflate_framed([b for _, b in batch], ubeg if batch[0][0] == cbeg else 0,
-                                                                   uend if batch[-1][0] == cend else -1, self.verify)
-                    t1 = time.perf_counter()
-                    _raise_block_status(self.filename, batch, status)
-                    t['inflate_device_ms'] = t.get('inflate_device_ms', 0.0) + ms
-                    calls += t1 - t0
-                if n_carry:
-                    raise ValueError(cut)
-            else:
-                carry = b''
-                for win in self.windows(chrom):
-                    data = carry + win if carry else win
-                    t0 = time.perf_counter()
-                    used = rows.append_framed(data)
-                    calls += time.perf_counter() - t0
-                    carry = data[used:]
-                if carry:
-                    raise ValueError(cut)
-        finally:
-            _, fixups, ms, decode_ms = rows.frame_info()
-            t['frame_device_ms'] = t.get('frame_device_ms', 0.0) + ms
-            t['frame_fixups'] = t.get('frame_fixups', 0) + fixups
-            t['decode_s'] = t.get('decode_s', 0.0) + 1e-3 * decode_ms
-            # what is left of the calls: the copy of the window (inflate='host') or of its blocks and their inflate ('device')
-            rest = max(calls - 1e-3 * (ms + decode_ms), 0.0)
-            key = 'inflate_s' if self.inflate == 'device' else 'upload_s'
-            t[key] = t.get(key, 0.0) + rest
         return rows
 
     def load_chromosome_reads(self, chrom):
@@ -847,6 +981,26 @@ class BamIndex(object):
     def __init__(self, refs, n_no_coor=None):
         self.refs = refs
         self.n_no_coor = n_no_coor
+
+    @classmethod
+    def from_tables(cls, ref_n_bin, ref_n_intv, pseudo, bin_id, bin_n_chunk, chunks, ioffset, n_no_coor):
+        """
+        The index of the flat tables dn_bai_fetch fills: per reference its number of bins and of linear-index entries and its
+        pseudo-bin's four values; per bin, in reference order, its id and its number of chunks; the (n, 2) chunks and the
+        linear-index entries of all of them.  A reference with bins gets its pseudo-bin as the last of them.
+        """
+        refs, b, c, w = [], 0, 0, 0
+        for r in range(len(ref_n_bin)):
+            bins = []
+            for k in range(b, b + int(ref_n_bin[r])):
+                bins.append((int(bin_id[k]), chunks[c:c + int(bin_n_chunk[k])].copy()))
+                c += int(bin_n_chunk[k])
+            b += int(ref_n_bin[r])
+            if bins:
+                bins.append((PSEUDO_BIN, pseudo[4 * r:4 * r + 4].reshape(2, 2).copy()))
+            refs.append({'bins': bins, 'ioffset': ioffset[w:w + int(ref_n_intv[r])].copy()})
+            w += int(ref_n_intv[r])
+        return cls(refs, n_no_coor)
 
     def pseudo(self, tid):
         """(offset of the first record, end of the last, mapped, unmapped) of a reference, or None without a pseudo-bin."""
@@ -909,28 +1063,61 @@ def write_bai(index, path):
     return path
 
 
-def _host_inflate(bam_file, batch, pool, verify=False):
+class _IndexBuilder(_WindowHandle):
     """
-    The data of the blocks of batch by zlib (verify: and their CRC32s by zlib.crc32, in the same pool); a block that fails
-    is named with the text of the library's own decoder.
+    The index builder of one file (dn_bai_*): on GPU `device`, or (None) the library's host build.  window() takes the file's
+    windows in order, finish() closes the pass, fetch() reads the tables out.  ms: the device's milliseconds so far.
     """
-    try:
-        return _zlib_inflate(bam_file, batch, pool, verify)
-    except BgzfCrcError:                                 # a wrong CRC32: _zlib_inflate has named the block
-        raise
-    except (zlib.error, ValueError, struct.error) as e:
-        blocks = [b for _, b in batch]
-        args, isize, status = _block_args(blocks)
-        n = len(blocks)
-        out_off = np.zeros(n + 1, np.int64)
-        np.cumsum(np.clip(isize[:n], 0, 65536), out=out_off[1:])
-        out = np.zeros(int(out_off[-1]) + 1, np.uint8)
-        if n and int(isize[:n].max()) <= 65536:
-            crc = _ptr(block_crcs(blocks), ctypes.c_uint32) if verify else None
-            args += (_ptr(out_off, ctypes.c_int64), _ptr(out, ctypes.c_uint8), _ptr(status, ctypes.c_int32), crc)
-            _check(_lib.load().dn_bgzf_inflate_check_host(*args), 'dn_bgzf_inflate_check_host')
-            _raise_block_status(bam_file, batch, status)
-        raise ValueError('{0}: a BGZF block at or after byte {1} does not inflate: {2}'.format(bam_file, batch[0][0], e))
+    unit = 'dn_bai'
+
+    def __init__(self, path, device, n_ref, segment=0):
+        self.lib, self.path, self.device, self.n_ref, self.h = _lib.load(), path, device, int(n_ref), ctypes.c_void_p()
+        self.ms = {'inflate_device_ms': 0.0, 'frame_device_ms': 0.0, 'index_device_ms': 0.0}
+        self.call(self.lib.dn_bai_create(-1 if device is None else int(device), self.n_ref, segment, ctypes.byref(self.h)), 'dn_bai_create')
+
+    def window(self, win):
+        """dn_bai_window_host on the window's zlib-inflated data (device=None), dn_bai_window on its blocks as they are."""
+        i64, i32 = ctypes.c_int64, ctypes.c_int32
+        n_rec = i64(0)
+        coffset = np.array([off for off, _ in win.batch], dtype=np.int64)
+        if self.device is None:
+            data = win.host_data()
+            isize = np.array([len(d) for d in data], dtype=np.int32)     # of whole blocks: deflate cannot expand one past int32
+            n_data = int(isize.sum(dtype=np.int64))
+            joined = np.frombuffer(b''.join(data), dtype=np.uint8) if n_data else np.zeros(1, np.uint8)
+            self.call(self.lib.dn_bai_window_host(self.h, _ptr(joined, ctypes.c_uint8), n_data, len(data), _ptr(isize, i32), _ptr(coffset, i64),
+                                                  win.head_skip, ctypes.byref(n_rec)), 'dn_bai_window_host')
+            return
+        args, status = self.window_args(win.blocks, win.verify)
+        t = [ctypes.c_double(0.0) for _ in range(3)]
+        args += (_ptr(coffset, i64), win.head_skip, _ptr(status, i32), ctypes.byref(n_rec), ctypes.byref(t[0]), ctypes.byref(t[1]),
+                 ctypes.byref(t[2]))
+        self.call(self.lib.dn_bai_window(self.h, *args), 'dn_bai_window')
+        for key, v in zip(('inflate_device_ms', 'frame_device_ms', 'index_device_ms'), t):
+            self.ms[key] += float(v.value)
+        win.check(status)
+
+    def finish(self, end_voffset):
+        """
+        dn_bai_finish: end_voffset is the virtual offset of the end of the stream.  Returns its sizes: bins (without pseudo-bins),
+        chunks, linear-index entries, records, records without a reference, windows, framing fix-ups.
+        """
+        sizes = np.zeros(8, dtype=np.int64)
+        self.call(self.lib.dn_bai_finish(self.h, int(end_voffset), _ptr(sizes, ctypes.c_int64)), 'dn_bai_finish')
+        return sizes
+
+    def fetch(self, sizes):
+        """dn_bai_fetch: the finished index (sizes: what finish returned) as a BamIndex."""
+        i32, u64 = ctypes.c_int32, ctypes.c_uint64
+        n_bins, n_chunks, n_intv = (int(x) for x in sizes[:3])
+        ref_n_bin, ref_n_intv = np.zeros(max(self.n_ref, 1), np.int32), np.zeros(max(self.n_ref, 1), np.int32)
+        pseudo = np.zeros(max(4 * self.n_ref, 1), np.uint64)
+        bin_id, bin_n_chunk = np.zeros(max(n_bins, 1), np.int32), np.zeros(max(n_bins, 1), np.int32)
+        chunks, ioffset = np.zeros(max(2 * n_chunks, 1), np.uint64), np.zeros(max(n_intv, 1), np.uint64)
+        self.call(self.lib.dn_bai_fetch(self.h, _ptr(ref_n_bin, i32), _ptr(ref_n_intv, i32), _ptr(pseudo, u64), _ptr(bin_id, i32),
+                                        _ptr(bin_n_chunk, i32), _ptr(chunks, u64), _ptr(ioffset, u64)), 'dn_bai_fetch')
+        return BamIndex.from_tables(ref_n_bin[:self.n_ref], ref_n_intv, pseudo, bin_id, bin_n_chunk,
+                                    chunks[:2 * n_chunks].reshape(n_chunks, 2), ioffset, int(sizes[4]))
 
 
 def build_index(bam_file, device=None, n_jobs=1, window_bytes=256 << 20, segment_bytes=None, stats=None, verify=False):
@@ -944,93 +1131,25 @@ def build_index(bam_file, device=None, n_jobs=1, window_bytes=256 << 20, segment
     naming the file and the block's offset).  segment_bytes: of the framing (None: the library's default).  stats, a dict, receives
     `inflate_device_ms`, `frame_device_ms`, `index_device_ms`, `frame_fixups`, `records`, `chunks` and `windows`.
     """
-    if not has_eof_block(bam_file):
-        raise ValueError('{0}: no BGZF end-of-file block; the file is truncated'.format(bam_file))
-    if segment_bytes is not None and int(segment_bytes) < 64:
-        raise ValueError('segment_bytes must be at least 64, not {0}'.format(segment_bytes))
-    window_bytes = max(int(256 << 20 if window_bytes is None else window_bytes), 1)
-    lib = _lib.load()
-    i64, i32, u8, u64 = ctypes.c_int64, ctypes.c_int32, ctypes.c_uint8, ctypes.c_uint64
-    pool = ThreadPoolExecutor(max_workers=int(n_jobs)) if device is None and int(n_jobs) > 1 else None
-    h = ctypes.c_void_p()
-    ms = {'inflate_device_ms': 0.0, 'frame_device_ms': 0.0, 'index_device_ms': 0.0}
-    end = {'coffset': None, 'open': False}          # the block behind the last one that holds a byte
-
-    def blocks():
-        for off, blk in iter_blocks(bam_file):
-            if end['open']:
-                end['coffset'] = off
-            end['open'] = struct.unpack_from('<I', blk, len(blk) - 4)[0] > 0
-            yield off, blk
-
-    def call(rc, what):
-        try:
-            _check(rc, what)
-        except ValueError as e:
-            raise ValueError('{0}: {1}'.format(bam_file, e))
-
-    def window(batch, head_skip):
-        n_rec = i64(0)
-        coffset = np.array([off for off, _ in batch], dtype=np.int64)
-        if device is None:
-            data = _host_inflate(bam_file, batch, pool, verify)
-            isize = np.array([len(d) for d in data], dtype=np.int64)
-            isize32 = np.where(isize > 2 ** 31 - 1, -1, isize).astype(np.int32)
-            joined = np.frombuffer(b''.join(data), dtype=np.uint8) if int(isize.sum()) else np.zeros(1, np.uint8)
-            call(lib.dn_bai_window_host(h, _ptr(joined, u8), int(isize.sum()), len(batch), _ptr(isize32, i32), _ptr(coffset, i64),
-                                        int(head_skip), ctypes.byref(n_rec)), 'dn_bai_window_host')
-            return
-        args, status = _window_args([b for _, b in batch], verify, lambda crc: call(
-            lib.dn_bai_expect_crc(h, _ptr(crc, ctypes.c_uint32), len(crc)), 'dn_bai_expect_crc'))
-        t = [ctypes.c_double(0.0) for _ in range(3)]
-        args += (_ptr(coffset, i64), int(head_skip), _ptr(status, i32), ctypes.byref(n_rec), ctypes.byref(t[0]), ctypes.byref(t[1]),
-                 ctypes.byref(t[2]))
-        call(lib.dn_bai_window(h, *args), 'dn_bai_window')
-        for key, v in zip(('inflate_device_ms', 'frame_device_ms', 'index_device_ms'), t):
-            ms[key] += float(v.value)
-        _raise_block_status(bam_file, batch, status)
-
-    try:
-        # the header, on zlib whatever the device: it may span several blocks
-        _, head_blocks, _, head_skip, refs = _header_data(bam_file, verify)
-        call(lib.dn_bai_create(-1 if device is None else int(device), len(refs), int(segment_bytes or 0), ctypes.byref(h)), 'dn_bai_create')
-        # the first window starts inside the block in which the header ends, and holds the bytes behind the header
-        for batch in _batched(itertools.islice(blocks(), head_blocks - 1, None), window_bytes, -head_skip):
-            window(batch, head_skip)
-            head_skip = 0
-            del batch
-        if end['coffset'] is None or end['open']:
-            raise ValueError('{0}: no BGZF end-of-file block; the file is truncated'.format(bam_file))
-        sizes = np.zeros(8, dtype=np.int64)
-        call(lib.dn_bai_finish(h, int(end['coffset']) << 16, _ptr(sizes, i64)), 'dn_bai_finish')
-        n_bins, n_chunks, n_intv = (int(x) for x in sizes[:3])
-        n_ref = len(refs)
-        ref_n_bin, ref_n_intv = np.zeros(max(n_ref, 1), np.int32), np.zeros(max(n_ref, 1), np.int32)
-        pseudo = np.zeros(max(4 * n_ref, 1), np.uint64)
-        bin_id, bin_n_chunk = np.zeros(max(n_bins, 1), np.int32), np.zeros(max(n_bins, 1), np.int32)
-        chunks, ioffset = np.zeros(max(2 * n_chunks, 1), np.uint64), np.zeros(max(n_intv, 1), np.uint64)
-        call(lib.dn_bai_fetch(h, _ptr(ref_n_bin, i32), _ptr(ref_n_intv, i32), _ptr(pseudo, u64), _ptr(bin_id, i32), _ptr(bin_n_chunk, i32),
-                              _ptr(chunks, u64), _ptr(ioffset, u64)), 'dn_bai_fetch')
-    finally:
-        if h:
-            lib.dn_bai_destroy(h)
-        if pool is not None:
-            pool.shutdown()
-    out, b, c, w = [], 0, 0, 0
-    chunks = chunks[:2 * n_chunks].reshape(n_chunks, 2)
-    for r in range(n_ref):
-        bins = []
-        for k in range(b, b + int(ref_n_bin[r])):
-            bins.append((int(bin_id[k]), chunks[c:c + int(bin_n_chunk[k])].copy()))
-            c += int(bin_n_chunk[k])
-        b += int(ref_n_bin[r])
-        if bins:
-            bins.append((PSEUDO_BIN, pseudo[4 * r:4 * r + 4].reshape(2, 2).copy()))
-        out.append({'bins': bins, 'ioffset': ioffset[w:w + int(ref_n_intv[r])].copy()})
-        w += int(ref_n_intv[r])
+    with _WindowFeed(bam_file, window_bytes, verify, n_jobs if device is None else 1) as feed:
+        segment = _segment_arg(segment_bytes)
+        _, head_blocks, _, head_skip, refs = feed.header()
+        with _IndexBuilder(bam_file, device, len(refs), segment) as bai:
+            end, is_open = None, False                   # the block behind the last one that holds a byte
+            # the first window starts inside the block in which the header ends, and holds the bytes behind the header
+            for win in feed.whole(head_blocks - 1, -head_skip, head_skip):
+                for off, blk in win.batch:
+                    if is_open:
+                        end = off
+                    is_open = _isize(blk) > 0
+                bai.window(win)
+            if end is None or is_open:
+                raise ValueError('{0}: no BGZF end-of-file block; the file is truncated'.format(bam_file))
+            sizes = bai.finish(end << 16)
+            index = bai.fetch(sizes)
     if stats is not None:
-        stats.update(ms, frame_fixups=int(sizes[6]), records=int(sizes[3]), chunks=n_chunks, windows=int(sizes[5]))
-    return BamIndex(out, int(sizes[4]))
+        stats.update(bai.ms, frame_fixups=int(sizes[6]), records=int(sizes[3]), chunks=int(sizes[1]), windows=int(sizes[5]))
+    return index
 
 
 def create_index(bam_file, bai_file=None, overwrite=False, **kw):
@@ -1049,41 +1168,27 @@ def verify_bgzf(path, device=None, n_jobs=1, window_bytes=256 << 20):
     written or copied.  device=None: zlib and zlib.crc32 in n_jobs threads.  ValueError names the file and the first bad
     block.  Returns {'blocks', 'compressed_bytes', 'inflated_bytes', 'device_ms'}.
     """
-    if not has_eof_block(path):
-        raise ValueError('{0}: no BGZF end-of-file block; the file is truncated'.format(path))
-    window_bytes = max(int(256 << 20 if window_bytes is None else window_bytes), 1)
     out = {'blocks': 0, 'compressed_bytes': 0, 'inflated_bytes': 0, 'device_ms': 0.0}
-    pool = ThreadPoolExecutor(max_workers=int(n_jobs)) if device is None and int(n_jobs) > 1 else None
-    i64, i32 = ctypes.c_int64, ctypes.c_int32
-
-    def window(batch):
-        blocks = [b for _, b in batch]
-        if device is None:
-            _host_inflate(path, batch, pool, True)
-            return
-        args, isize, status = _block_args(blocks)
-        n = len(blocks)
-        if int(isize[:n].max()) > 65536:
-            k = int(isize[:n].argmax())
-            raise ValueError('{0}: the BGZF block at byte {1} claims an inflated size of {2} bytes'.format(path, batch[k][0], int(isize[k])))
-        out_off = np.zeros(n + 1, np.int64)
-        np.cumsum(isize[:n], out=out_off[1:])
-        ms = ctypes.c_double(0.0)
-        args += (_ptr(out_off, i64), None, _ptr(status, i32), None, ctypes.byref(ms), _ptr(block_crcs(blocks), ctypes.c_uint32))
-        _check(_lib.load().dn_bgzf_inflate_check(int(device), *args), 'dn_bgzf_inflate_check')
-        out['device_ms'] += float(ms.value)
-        _raise_block_status(path, batch, status)
-
-    try:
-        for batch in _batched(iter_blocks(path), window_bytes):
-            out['blocks'] += len(batch)
-            out['compressed_bytes'] += sum(len(blk) for _, blk in batch)
-            out['inflated_bytes'] += sum(struct.unpack_from('<I', blk, len(blk) - 4)[0] for _, blk in batch)
-            window(batch)
-            del batch
-    finally:
-        if pool is not None:
-            pool.shutdown()
+    with _WindowFeed(path, window_bytes, True, n_jobs if device is None else 1) as feed:
+        for win in feed.whole():
+            blocks = win.blocks
+            out['blocks'] += len(blocks)
+            out['compressed_bytes'] += sum(len(blk) for blk in blocks)
+            out['inflated_bytes'] += sum(_isize(blk) for blk in blocks)
+            if device is None:
+                win.host_data()
+                continue
+            args, isize, status = _block_args(blocks)
+            out_off, big = _out_offsets(isize, len(blocks))
+            if big is not None:
+                raise ValueError('{0}: the BGZF block at byte {1} claims an inflated size of {2} bytes'.format(path, win.batch[big][0],
+                                                                                                             int(isize[big])))
+            ms = ctypes.c_double(0.0)
+            args += (_ptr(out_off, ctypes.c_int64), None, _ptr(status, ctypes.c_int32), None, ctypes.byref(ms),
+                     _ptr(block_crcs(blocks), ctypes.c_uint32))
+            _check(_lib.load().dn_bgzf_inflate_check(int(device), *args), 'dn_bgzf_inflate_check')
+            out['device_ms'] += float(ms.value)
+            win.check(status)
     return out
 
 
@@ -1122,21 +1227,6 @@ DEVICE_MEMORY_SHARE = 0.8        # of the device's free memory a sort may plan w
 _SORT_TABLE_BYTES = 56           # per record: offset, two (key, ordinal) pairs, length and destination
 _ENDS_CHUNK = 1 << 20            # record ends fetched at a time
 _DEFLATE_REGION = 2 * 65536      # device bytes the encoder needs for one block (slot and compacted copy)
-
-
-def _header_data(path, verify=False):
-    """
-    (inflated bytes of the blocks the BAM header lies in, their number, header end, the bytes of the last of these blocks that
-    belong to the header, [(SQ name, length)]).
-    """
-    data = bytearray()
-    for k, (off, blk) in enumerate(iter_blocks(path)):
-        start = len(data)
-        data += _host_inflate(path, [(off, blk)], None, verify)[0]
-        got = parse_header(data)
-        if got is not None:
-            return bytes(data), k + 1, got[0], got[0] - start, got[1]
-    raise ValueError('{0}: BAM header cut short'.format(path))
 
 
 def _header_lines(text):
@@ -1254,6 +1344,73 @@ def device_memory(device):
     return int(free.value), int(total.value)
 
 
+class _Sorter(_WindowHandle):
+    """
+    The coordinate sort of one file (dn_bam_sort_*): on GPU `device`, or (None) the library's host build.  window() takes the
+    file's windows in order and finish() sorts; ends(), read() and deflate() then read the sorted stream out.
+    windows and inflate_device_ms: the windows taken and the device's milliseconds of inflate so far.
+    """
+    unit = 'dn_bam_sort'
+
+    def __init__(self, path, device, n_ref, n_stream, segment, window_bytes):
+        self.lib, self.path, self.device, self.window_bytes, self.h = _lib.load(), path, device, window_bytes, ctypes.c_void_p()
+        self.windows, self.inflate_device_ms, self.n_bytes, self._lo, self._data = 0, 0.0, 0, 0, b''
+        self.call(self.lib.dn_bam_sort_create(-1 if device is None else int(device), int(n_ref), int(n_stream), segment, window_bytes,
+                                              ctypes.byref(self.h)), 'dn_bam_sort_create')
+
+    def window(self, win):
+        """dn_bam_sort_window_host on the window's zlib-inflated data (device=None), dn_bam_sort_window on its blocks as they are."""
+        self.windows += 1
+        if self.device is None:
+            data = b''.join(win.host_data())
+            joined = np.frombuffer(data, dtype=np.uint8) if data else np.zeros(1, np.uint8)
+            self.call(self.lib.dn_bam_sort_window_host(self.h, _ptr(joined, ctypes.c_uint8), len(data), win.head_skip), 'dn_bam_sort_window_host')
+            return
+        args, status = self.window_args(win.blocks, win.verify)
+        ms = ctypes.c_double(0.0)
+        self.call(self.lib.dn_bam_sort_window(self.h, *(args + (win.head_skip, _ptr(status, ctypes.c_int32), ctypes.byref(ms)))),
+                  'dn_bam_sort_window')
+        self.inflate_device_ms += float(ms.value)
+        win.check(status)
+
+    def finish(self):
+        """dn_bam_sort_finish: (records, bytes of the sorted stream, framing fix-ups, device ms of framing, of the sort, of the gather)."""
+        n_rec, n_bytes, fix = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        ms = [ctypes.c_double(0.0) for _ in range(3)]
+        self.call(self.lib.dn_bam_sort_finish(self.h, ctypes.byref(n_rec), ctypes.byref(n_bytes), ctypes.byref(fix), ctypes.byref(ms[0]),
+                                              ctypes.byref(ms[1]), ctypes.byref(ms[2])), 'dn_bam_sort_finish')
+        self.n_bytes = int(n_bytes.value)
+        return (int(n_rec.value), self.n_bytes, int(fix.value)) + tuple(float(v.value) for v in ms)
+
+    def ends(self, n_records):
+        """dn_bam_sort_ends: where the records of the sorted stream end (ascending int64 arrays of at most _ENDS_CHUNK)."""
+        for first in range(0, n_records, _ENDS_CHUNK):
+            n = min(_ENDS_CHUNK, n_records - first)
+            ends = np.zeros(n, np.int64)
+            self.call(self.lib.dn_bam_sort_ends(self.h, first, n, _ptr(ends, ctypes.c_int64)), 'dn_bam_sort_ends')
+            yield ends
+
+    def read(self, a, b):
+        """Bytes [a, b) of the sorted stream; fetched (dn_bam_sort_read) window_bytes at a time, for ranges in ascending order."""
+        if b > self._lo + len(self._data):
+            n = min(max(self.window_bytes, b - a), self.n_bytes - a)
+            arr = np.zeros(max(n, 1), np.uint8)
+            self.call(self.lib.dn_bam_sort_read(self.h, a, n, _ptr(arr, ctypes.c_uint8)), 'dn_bam_sort_read')
+            self._lo, self._data = a, arr[:n].tobytes()
+        return self._data[a - self._lo:b - self._lo]
+
+    def deflate(self, cuts):
+        """dn_bam_sort_deflate: the BGZF blocks of the ranges `cuts` of the sorted stream, deflated where the stream lies, and the device ms."""
+        i64, i32 = ctypes.c_int64, ctypes.c_int32
+        beg = np.array([a for a, _ in cuts] + [0], np.int64)
+        lens = np.array([b - a for a, b in cuts] + [0], np.int32)
+        cap = int(self.lib.dn_bgzf_deflate_bound(len(cuts), _ptr(lens, i32)))
+        out, out_off, ms = np.zeros(max(cap, 1), np.uint8), np.zeros(len(cuts) + 1, np.int64), ctypes.c_double(0.0)
+        self.call(self.lib.dn_bam_sort_deflate(self.h, len(cuts), _ptr(beg, i64), _ptr(lens, i32), _ptr(out, ctypes.c_uint8), cap, _ptr(out_off, i64),
+                                               ctypes.byref(ms)), 'dn_bam_sort_deflate')
+        return memoryview(out)[:int(out_off[len(cuts)])], float(ms.value)
+
+
 def sort_bam(src, dst, device=None, n_jobs=1, level=1, window_bytes=256 << 20, segment_bytes=None, verify=False, overwrite=False,
              max_device_bytes=None, stats=None, deflate='zlib'):
     """
@@ -1291,146 +1448,67 @@ def sort_bam(src, dst, device=None, n_jobs=1, level=1, window_bytes=256 << 20, s
         raise ValueError("deflate must be 'zlib' or 'native', not {0!r}".format(deflate))
     if os.path.exists(dst) and not overwrite:
         raise FileExistsError('{0} exists; pass overwrite=True to replace it'.format(dst))
-    if not has_eof_block(src):
-        raise ValueError('{0}: no BGZF end-of-file block; the file is truncated'.format(src))
-    if segment_bytes is not None and int(segment_bytes) < 64:
-        raise ValueError('segment_bytes must be at least 64, not {0}'.format(segment_bytes))
-    window_bytes = max(int(256 << 20 if window_bytes is None else window_bytes), 1)
-    lib = _lib.load()
-    i64, i32, u8 = ctypes.c_int64, ctypes.c_int32, ctypes.c_uint8
     n_jobs = max(int(n_jobs), 1)
-    pool = ThreadPoolExecutor(max_workers=n_jobs) if n_jobs > 1 else None
-    h = ctypes.c_void_p()
     tmp = dst + '.tmp'
     t = {'inflate_device_ms': 0.0, 'deflate_s': 0.0, 'windows': 0, 'deflate_device_ms': 0.0, 'out_bytes': 0}
-
-    def call(rc, what):
-        try:
-            _check(rc, what)
-        except ValueError as e:
-            raise ValueError('{0}: {1}'.format(src, e))
-
-    def window(batch, head_skip):
-        t['windows'] += 1
-        if device is None:
-            data = b''.join(_host_inflate(src, batch, pool, verify))
-            joined = np.frombuffer(data, dtype=np.uint8) if data else np.zeros(1, np.uint8)
-            call(lib.dn_bam_sort_window_host(h, _ptr(joined, u8), len(data), int(head_skip)), 'dn_bam_sort_window_host')
-            return
-        args, status = _window_args([b for _, b in batch], verify, lambda crc: call(
-            lib.dn_bam_sort_expect_crc(h, _ptr(crc, ctypes.c_uint32), len(crc)), 'dn_bam_sort_expect_crc'))
-        ms = ctypes.c_double(0.0)
-        call(lib.dn_bam_sort_window(h, *(args + (int(head_skip), _ptr(status, i32), ctypes.byref(ms)))), 'dn_bam_sort_window')
-        t['inflate_device_ms'] += float(ms.value)
-        _raise_block_status(src, batch, status)
-
-    def ends_chunks(n_records):
-        for first in range(0, n_records, _ENDS_CHUNK):
-            n = min(_ENDS_CHUNK, n_records - first)
-            ends = np.zeros(n, np.int64)
-            call(lib.dn_bam_sort_ends(h, first, n, _ptr(ends, i64)), 'dn_bam_sort_ends')
-            yield ends
-
-    def deflated(parts):
-        t0 = time.perf_counter()
-        one = lambda d: bgzf_compress(d, level)                                  # noqa: E731
-        out = list(pool.map(one, parts) if pool is not None else map(one, parts))
-        t['deflate_s'] += time.perf_counter() - t0
-        return out
-
     try:
-        # the header, on zlib whatever the device: it may span several blocks; and the size of the whole stream
-        data, head_blocks, header_end, head_skip, refs = _header_data(src, verify)
-        _, _, isizes = bgzf_blocks(src)
-        n_stream = int(isizes.sum()) - header_end
-        n_comp_max, size, comp = 0, 0, 0
-        for k in range(head_blocks - 1, len(isizes)):                            # the compressed bytes of the largest window
-            size, comp = size + int(isizes[k]), comp + 65536
-            if size >= window_bytes or k == len(isizes) - 1:
-                n_comp_max, size, comp = max(n_comp_max, comp), 0, 0
-        if device is not None:
-            need = 2 * n_stream + n_comp_max + _SORT_TABLE_BYTES * (n_stream // 128 + 1)
-            if deflate == 'native' and n_stream + 64 < _DEFLATE_REGION:      # too small to lend the encoder its slots
-                need += _DEFLATE_REGION
-            have = int(DEVICE_MEMORY_SHARE * device_memory(device)[0]) if max_device_bytes is None else int(max_device_bytes)
-            if need > have:
-                raise ValueError('{0}: sorting needs about {1} bytes of device memory ({2} bytes of records), {3} are allowed; '
-                                 'a file that does not fit the device cannot be sorted here'.format(src, need, n_stream, have))
-        call(lib.dn_bam_sort_create(-1 if device is None else int(device), len(refs), n_stream, int(segment_bytes or 0), window_bytes,
-                                    ctypes.byref(h)), 'dn_bam_sort_create')
-        # the first window starts inside the block in which the header ends, and counts that block whole
-        for batch in _batched(itertools.islice(iter_blocks(src), head_blocks - 1, None), window_bytes):
-            window(batch, head_skip)
-            head_skip = 0
-            del batch
-        n_rec, n_bytes, fix = i64(0), i64(0), i64(0)
-        ms = [ctypes.c_double(0.0) for _ in range(3)]
-        call(lib.dn_bam_sort_finish(h, ctypes.byref(n_rec), ctypes.byref(n_bytes), ctypes.byref(fix), ctypes.byref(ms[0]), ctypes.byref(ms[1]),
-                                    ctypes.byref(ms[2])), 'dn_bam_sort_finish')
-        header = coordinate_header(data[:header_end])
-        buf = {'lo': 0, 'data': b''}
+        # the pool inflates (device=None) and deflates (deflate='zlib')
+        with _WindowFeed(src, window_bytes, verify, n_jobs if device is None or deflate == 'zlib' else 1) as feed:
+            segment, window_bytes = _segment_arg(segment_bytes), feed.window_bytes
 
-        def stream(a, b):
-            """Bytes [a, b) of the sorted stream; fetched window_bytes at a time, in ascending order."""
-            if b > buf['lo'] + len(buf['data']):
-                n = min(max(window_bytes, b - a), n_bytes.value - a)
-                arr = np.zeros(max(n, 1), np.uint8)
-                call(lib.dn_bam_sort_read(h, a, n, _ptr(arr, u8)), 'dn_bam_sort_read')
-                buf['lo'], buf['data'] = a, arr[:n].tobytes()
-            return buf['data'][a - buf['lo']:b - buf['lo']]
+            def deflated(parts):
+                t0 = time.perf_counter()
+                one = lambda d: bgzf_compress(d, level)                              # noqa: E731
+                out = list(feed.pool.map(one, parts) if feed.pool is not None else map(one, parts))
+                t['deflate_s'] += time.perf_counter() - t0
+                return out
 
-        def native(f, cuts):
-            """The blocks of the ranges `cuts` of the sorted stream, deflated where the stream lies, to f."""
-            t0 = time.perf_counter()
-            beg = np.array([a for a, _ in cuts] + [0], np.int64)
-            lens = np.array([b - a for a, b in cuts] + [0], np.int32)
-            cap = int(lib.dn_bgzf_deflate_bound(len(cuts), _ptr(lens, i32)))
-            out, out_off, dms = np.zeros(max(cap, 1), np.uint8), np.zeros(len(cuts) + 1, np.int64), ctypes.c_double(0.0)
-            call(lib.dn_bam_sort_deflate(h, len(cuts), _ptr(beg, i64), _ptr(lens, i32), _ptr(out, u8), cap, _ptr(out_off, i64),
-                                         ctypes.byref(dms)), 'dn_bam_sort_deflate')
-            t['deflate_device_ms'] += float(dms.value)
-            t['deflate_s'] += time.perf_counter() - t0
-            t['out_bytes'] += int(out_off[len(cuts)])
-            f.write(memoryview(out)[:int(out_off[len(cuts)])])
-
-        head_parts = [header[a:a + BGZF_BLOCK_DATA] for a in range(0, len(header), BGZF_BLOCK_DATA)]
-        with open(tmp, 'wb') as f:
-            if deflate == 'native':
-                for blk in bgzf_deflate(head_parts):
-                    f.write(blk)
-                cuts, size = [], 0
-                for a, b in _block_cuts(ends_chunks(int(n_rec.value))):
-                    cuts.append((a, b))
-                    size += b - a
-                    if size >= window_bytes:
-                        native(f, cuts)
-                        cuts, size = [], 0
-                if cuts:
-                    native(f, cuts)
-            else:
-                for blk in deflated(head_parts):
-                    f.write(blk)
-                parts = []
-                for a, b in _block_cuts(ends_chunks(int(n_rec.value))):
-                    parts.append(stream(a, b))
-                    if len(parts) >= 64 * n_jobs:
-                        for blk in deflated(parts):
-                            t['out_bytes'] += len(blk)
-                            f.write(blk)
-                        parts = []
-                for blk in deflated(parts):
-                    t['out_bytes'] += len(blk)
-                    f.write(blk)
-            f.write(BGZF_EOF)
-        os.replace(tmp, dst)
+            # plan memory: the size of the whole stream, and the compressed bytes of the largest window
+            data, head_blocks, header_end, head_skip, refs = feed.header()
+            _, _, isizes = bgzf_blocks(src)
+            n_stream = int(isizes.sum()) - header_end
+            if device is not None:
+                n_comp_max = 65536 * max(_window_cuts(isizes[head_blocks - 1:].tolist(), window_bytes))
+                need = 2 * n_stream + n_comp_max + _SORT_TABLE_BYTES * (n_stream // 128 + 1)
+                if deflate == 'native' and n_stream + 64 < _DEFLATE_REGION:      # too small to lend the encoder its slots
+                    need += _DEFLATE_REGION
+                have = int(DEVICE_MEMORY_SHARE * device_memory(device)[0]) if max_device_bytes is None else int(max_device_bytes)
+                if need > have:
+                    raise ValueError('{0}: sorting needs about {1} bytes of device memory ({2} bytes of records), {3} are allowed; '
+                                     'a file that does not fit the device cannot be sorted here'.format(src, need, n_stream, have))
+            with _Sorter(src, device, len(refs), n_stream, segment, window_bytes) as sorter:
+                # feed windows: the first starts inside the block in which the header ends, and counts that block whole
+                for win in feed.whole(head_blocks - 1, 0, head_skip):
+                    sorter.window(win)
+                n_rec, n_bytes, fix, frame_ms, sort_ms, gather_ms = sorter.finish()
+                t.update(windows=sorter.windows, inflate_device_ms=sorter.inflate_device_ms)
+                # write blocks: the header's, then those of the sorted stream, cut where records end
+                header = coordinate_header(data[:header_end])
+                head_parts = [header[a:a + BGZF_BLOCK_DATA] for a in range(0, len(header), BGZF_BLOCK_DATA)]
+                cuts = _block_cuts(sorter.ends(n_rec))
+                with open(tmp, 'wb') as f:
+                    if deflate == 'native':
+                        f.writelines(bgzf_deflate(head_parts))
+                        for group in _batched(cuts, window_bytes, weigh=lambda ab: ab[1] - ab[0]):
+                            t0 = time.perf_counter()
+                            out, ms = sorter.deflate(group)
+                            t['deflate_device_ms'] += ms
+                            t['deflate_s'] += time.perf_counter() - t0
+                            t['out_bytes'] += len(out)
+                            f.write(out)
+                    else:
+                        f.writelines(deflated(head_parts))
+                        parts = (sorter.read(a, b) for a, b in cuts)
+                        for group in iter(lambda: list(itertools.islice(parts, 64 * n_jobs)), []):
+                            for blk in deflated(group):
+                                t['out_bytes'] += len(blk)
+                                f.write(blk)
+                    f.write(BGZF_EOF)
+                os.replace(tmp, dst)
     finally:
-        if h:
-            lib.dn_bam_sort_destroy(h)
-        if pool is not None:
-            pool.shutdown()
         if os.path.exists(tmp):
             os.remove(tmp)
     if stats is not None:
-        stats.update(t, frame_device_ms=float(ms[0].value), sort_device_ms=float(ms[1].value), gather_device_ms=float(ms[2].value),
-                     frame_fixups=int(fix.value), records=int(n_rec.value), bytes=int(n_bytes.value))
+        stats.update(t, frame_device_ms=frame_ms, sort_device_ms=sort_ms, gather_device_ms=gather_ms, frame_fixups=fix, records=n_rec,
+                     bytes=n_bytes)
     return dst

@@ -75,6 +75,37 @@ def _all_modes(path, chrom, ov, gene_df, exon_df, out, **kw):
     return res
 
 
+TIMING_KEYS = {('host', 'host'): {'inflate_s', 'frame_s', 'decode_s'},
+               ('device', 'host'): {'inflate_s', 'inflate_device_ms', 'frame_s', 'decode_s'},
+               ('host', 'device'): {'inflate_s', 'upload_s', 'frame_device_ms', 'frame_fixups', 'decode_s'},
+               ('device', 'device'): {'inflate_s', 'inflate_device_ms', 'frame_device_ms', 'frame_fixups', 'decode_s'}}
+
+
+def test_one_ingest_loop_serves_the_four_combinations(tmp_path):
+    """Windows of 64 KiB over a single-end file: every combination carries cut records, gives host / host's outputs and keeps its timing keys."""
+    chrom, chrom_len, gene_df, exon_df, ov, src = _layout_case(21, 4000, False)
+    df = pd.DataFrame({'ref': 0, 'pos': src.pos.values, 'qname': src.qname.values, 'cigar': src.cigar.values})
+    p = str(tmp_path / 'se.bam')
+    bf.write_bam(p, [(chrom, chrom_len)], df, straddle=True)
+    kw = {'window_bytes': 1 << 16}
+    res = {}
+    for inflate in ('host', 'device'):
+        for frame in ('host', 'device'):
+            proc, files = _run(p, chrom, ov, gene_df, exon_df, tmp_path / (inflate + '_' + frame), inflate=inflate, frame=frame, **kw)
+            assert not proc.paired
+            res[inflate, frame] = files
+            _same(res['host', 'host'], files)
+            assert set(proc.timing) == TIMING_KEYS[inflate, frame] | {'coverage_s', 'coverage_device_ms'}, (inflate, frame)
+    assert int(res['host', 'host'][2].iloc[:, 1].sum()) > 1000
+    assert len(list(proc._batches(chrom))) > 3
+    carry, last, cut = b'', -2 ** 31, 0                          # the host walk over the same windows: records are cut by window ends
+    for win in proc.windows(chrom):
+        off, used, last = bam.frame_records(carry + win, 0, last)
+        cut += used < len(carry + win)
+        carry = (carry + win)[used:]
+    assert cut > 0 and not carry
+
+
 @pytest.mark.parametrize('straddle', [False, True])
 @pytest.mark.parametrize('key', ['se', 'pe'])
 def test_reader_equals_host_framing_on_goldens(key, straddle, tmp_path):
