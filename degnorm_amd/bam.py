@@ -52,7 +52,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import _check, _p as _ptr
-from .reads import BamReadsProcessor, Annotation, coverage_outputs, reads_frame
+from .reads import BamReadsProcessor, Annotation, check_coverage_call, coverage_outputs, reads_frame
 
 BGZF_EOF = bytes.fromhex('1f8b08040000000000ff0600424302001b0003000000000000000000')
 PSEUDO_BIN = 37450
@@ -721,7 +721,7 @@ class DeviceRows(_WindowHandle):
                                            len(ann.iso_union), _ptr(ann.iso_union, i64),
                                            n_genes, _ptr(counts, i64), _ptr(ol_cov, i64), cap, ctypes.byref(nnz),
                                            _ptr(csr_idx, i32), _ptr(csr_val, i64), ctypes.byref(n_iso_reads), ctypes.byref(ms))
-        _check(rc, 'dn_bam_rows_coverage')
+        check_coverage_call(rc, 'dn_bam_rows_coverage')
         k = int(nnz.value)
         return counts[:n_genes], ol_cov, csr_idx[:k].copy(), csr_val[:k].copy(), int(n_iso_reads.value), float(ms.value)
 

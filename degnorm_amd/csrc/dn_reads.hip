@@ -247,7 +247,8 @@ template <class C> __global__ __launch_bounds__(kNT) void k_reads(ReadsArgs<C> A
             nseg = n1 + n2;
         }
         // exon-union filter: every non-empty segment inside one merged exon interval; an empty one (end < start)
-        // passes like the reference's empty slice.  A bound below 0 (a clipped mate at position 0) drops the read.
+        // passes like the reference's empty slice.  A bound below 0 (a zero-length M at position 0, or a mate clipped
+        // below a mate at position 0) drops the read or pair.
         bool drop = false;
         for (int k = 0; k < nseg && !drop; k++) {
             if (sa[k] < 0 || sb[k] < 0) drop = true;

@@ -176,6 +176,16 @@ class Annotation(object):
         self.n_isolated, self.n_overlap = len(iso), len(ol_gene)
 
 
+def check_coverage_call(rc, what):
+    """
+    _lib._check for the coverage calls.  A kept row with more than DN_READS_MAX_SEG M ops (DN_E_UNSUPPORTED) is a fault of
+    the caller's data, as a CIGAR without an M op is: ValueError with the library's text, which names the CIGAR.
+    """
+    if rc == _lib.DN_E_UNSUPPORTED:
+        raise ValueError(_lib.load().dn_last_error().decode('utf-8', 'replace'))
+    _lib._check(rc, what)
+
+
 def device_read_coverage(pos, off, cig, pair_id, n_ids, ann, paired, device=None):
     """
     One dn_read_coverage call on packed reads and an Annotation: (counts int64[n_genes], overlap span vectors int64 with
@@ -202,7 +212,7 @@ def device_read_coverage(pos, off, cig, pair_id, n_ids, ann, paired, device=None
                               len(ann.iso_union), _ptr(ann.iso_union, i64),
                               n_genes, _ptr(counts, i64), _ptr(ol_cov, i64), cap, ctypes.byref(nnz),
                               _ptr(csr_idx, i32), _ptr(csr_val, i64), ctypes.byref(n_iso_reads), ctypes.byref(ms))
-    _lib._check(rc, 'dn_read_coverage')
+    check_coverage_call(rc, 'dn_read_coverage')
     k = int(nnz.value)
     return counts[:n_genes], ol_cov, csr_idx[:k].copy(), csr_val[:k].copy(), int(n_iso_reads.value), float(ms.value)
 

@@ -244,9 +244,11 @@ const char *dn_assemble_last_error(void);          /* = dn_last_error() */
  * the chromosome coverage as CSR nonzeros (*nnz positions csr_idx ascending, values csr_val; at most csr_cap: the length
  * of the exon union bounds it), *n_isolated_reads (0: the reference writes no chrom_coverage file, :711) and device_ms
  * (nullable).  A kept row whose CIGAR has no M op returns DN_E_INVALID (the reference's ValueError, :63-64); one with more
- * than DN_READS_MAX_SEG M ops returns DN_E_UNSUPPORTED.  A pair whose clipped mate-2 bounds reach below position 0 is dropped
- * (the reference indexes from the vector's end there).  Results are bit-identical from run to run.  Text of the last error:
- * dn_reads_last_error(). */
+ * than DN_READS_MAX_SEG M ops returns DN_E_UNSUPPORTED (both are ValueError in the Python layer, with the CIGAR in the
+ * text).  A read or pair with a segment bound below position 0 is dropped (the reference indexes from the vector's end
+ * there).  Such a bound arises in two ways: a zero-length M op at position 0 (`0M10M` at 0 has the bounds 0, -1, -1, 8),
+ * single-end or paired, and a mate 2 clipped to the left of a mate 1 that starts at position 0.  Results are bit-identical
+ * from run to run.  Text of the last error: dn_reads_last_error(). */
 #define DN_READS_MAX_SEG      32  /* match segments (M ops) per row                                                   */
 int  dn_read_coverage(int device, int32_t paired, int64_t n_rows, const int64_t *pos, const int64_t *cigar_off,
                       const uint8_t *cigar, const int32_t *pair_id, int64_t n_pair_ids,

@@ -85,7 +85,7 @@ def synth_reads(seed, layout, n, skip=('I',), noise=0.15):
     rows = []
     for i in range(n):
         if rng.random() < noise:
-            rows.append(('q{0}'.format(i), int(rng.integers(0, chrom_len - 400)), random_cigar(rng)))
+            rows.append(('q{0}'.format(i), int(rng.integers(0, max(chrom_len - 400, 1))), random_cigar(rng)))
         else:
             s, c = _exon_read(rng, src)
             rows.append(('q{0}'.format(i), s, c))
@@ -119,6 +119,261 @@ def synth_pairs(seed, layout, n_pairs, skip=('I',)):
         if rng.random() < 0.04:                          # orphan
             mates = mates[:1]
         rows += mates
+    return pd.DataFrame(rows, columns=['qname', 'pos', 'cigar', 'qname_unpaired'])
+
+
+# --- seeded edge cases: random annotations and read mutators (tests/_reads_oracle.py is their oracle) ---------------------
+
+def _random_exons(rng, start):
+    """1-4 exons from `start`: apart, touching (gap 0), overlapping or nested in the one before."""
+    exons = [(start, start + int(rng.integers(30, 140)))]
+    for _ in range(int(rng.integers(0, 4))):
+        a, b = exons[-1]
+        kind = int(rng.integers(0, 6))
+        if kind == 0:                                    # touching
+            s = b + 1
+        elif kind == 1:                                  # nested
+            s = int(rng.integers(a, b + 1))
+            exons.append((s, int(rng.integers(s, b + 1))))
+            continue
+        elif kind == 2:                                  # overlapping, reaching further right
+            s = int(rng.integers(a, b + 1))
+            exons.append((s, b + int(rng.integers(1, 60))))
+            continue
+        else:
+            s = b + 1 + int(rng.integers(1, 50))
+        exons.append((s, s + int(rng.integers(30, 140))))
+    return exons
+
+
+def random_layout(seed, variant=None):
+    """
+    A seeded annotation (chrom, chrom_len, genes): 4-14 genes of 1-4 exons on a chromosome shorter than 10 000 bases.
+    Neighbouring genes overlap, touch or lie apart, so the numbers of overlap groups and of isolated-union intervals differ
+    from seed to seed; on some seeds the first gene starts on base 1, on some the last exon ends on the chromosome's last
+    base.  variant='groups_only': every gene is in an overlap group; variant='isolated_only': none is.
+    """
+    assert variant in (None, 'groups_only', 'isolated_only')
+    rng = np.random.default_rng([seed, {None: 0, 'groups_only': 1, 'isolated_only': 2}[variant]])
+    while True:
+        n = int(rng.integers(4, 15))
+        if variant == 'groups_only':
+            n += n % 2
+        genes, reach = [], 0                             # reach: the last base (1-based) any gene so far covers
+        for g in range(n):
+            how = int(rng.integers(0, 3))                # 0 overlap, 1 touch, 2 apart
+            if variant == 'groups_only':
+                how = 0 if g % 2 == 1 or (g > 0 and rng.random() < 0.3) else 2
+            elif variant == 'isolated_only':
+                how = 1 + int(rng.integers(0, 2))
+            if g == 0:
+                start = 1 if rng.random() < 0.4 else int(rng.integers(2, 90))
+            elif how == 0:
+                prev = genes[-1][1]
+                start = int(rng.integers(max(min(a for a, _ in prev), reach - 120), reach + 1))
+            elif how == 1:
+                start = reach + 1
+            else:
+                start = reach + 1 + int(rng.integers(1, 90))
+            exons = _random_exons(rng, start)
+            genes.append(('g{0:02d}'.format(g), exons))
+            reach = max(reach, max(b for _, b in exons))
+        chrom_len = reach if rng.random() < 0.4 else reach + int(rng.integers(1, 90))
+        if chrom_len < 10000:
+            break
+    ov = get_gene_overlap_structure(tables('chrE', genes)[0])
+    assert variant != 'groups_only' or not ov['isolated_genes']
+    assert variant != 'isolated_only' or not ov['overlap_genes']
+    return 'chrE', chrom_len, genes
+
+
+def _zero_length_cigar(rng, cigar):
+    """
+    One of: 0M in front, 0M behind, an M turned into M0N, an M turned into M0M, an N of 4 or more split around a 0M
+    (nN -> aN0M(n-a)N: an empty segment inside the intron, every later segment where it was).
+    """
+    import re
+    how = int(rng.integers(0, 5))
+    if how == 4:
+        gaps = [m for m in re.finditer(r'(\d+)N', cigar) if int(m.group(1)) >= 4]
+        if gaps:
+            m = gaps[int(rng.integers(0, len(gaps)))]
+            n = int(m.group(1))
+            a = int(rng.integers(2, n - 1))
+            return cigar[:m.start()] + '{0}N0M{1}N'.format(a, n - a) + cigar[m.end():]
+        how = 0
+    if how == 0:
+        return '0M' + cigar
+    if how == 1:
+        return cigar + '0M'
+    at = [i for i, ch in enumerate(cigar) if ch == 'M']
+    if not at:
+        return cigar
+    i = at[int(rng.integers(0, len(at)))] + 1
+    return cigar[:i] + ('0N' if how == 2 else '0M') + cigar[i:]
+
+
+def with_zero_length_ops(df, seed, frac=0.3):
+    """A seeded fraction of the rows gets a zero-length op (see _zero_length_cigar), spliced rows twice as often."""
+    rng = np.random.default_rng(seed)
+    df = df.copy()
+    df['cigar'] = [_zero_length_cigar(rng, c) if rng.random() < (2 * frac if 'N' in c else frac) else c for c in df['cigar']]
+    return df
+
+
+def interleave_pairs(df, seed, frac=0.2):
+    """Rows swapped across pair borders (a1 a2 b1 b2 -> a1 b1 a2 b2): surviving mates are no longer consecutive by id."""
+    rng = np.random.default_rng(seed)
+    order = np.arange(len(df))
+    k = 1
+    while k + 1 < len(df):
+        if rng.random() < frac:
+            order[k], order[k + 1] = order[k + 1], order[k]
+            k += 4
+        else:
+            k += 2
+    return df.iloc[order].reset_index(drop=True)
+
+
+def repeat_pair_ids(df, seed, n=3):
+    """A third row for n pair ids (a copy of one of the id's rows, appended): the reference drops all rows of such an id."""
+    rng = np.random.default_rng(seed)
+    extra = df.iloc[rng.choice(len(df), size=min(n, len(df)), replace=False)]
+    return pd.concat([df, extra], ignore_index=True)
+
+
+def _append(df, rows, paired):
+    """rows: per unit a list of (pos, cigar); a paired unit gets a pair id of its own (p<number>, as synth_pairs' ids)."""
+    out = []
+    for k, unit in enumerate(rows, 100000 + len(df)):
+        for m, (p, c) in enumerate(unit):
+            q = 'p{0}'.format(k)
+            out.append(('{0}.{1}'.format(q, m + 1), p, c, q) if paired else ('q{0}'.format(k), p, c))
+    add = pd.DataFrame(out, columns=list(df.columns))
+    return pd.concat([df, add], ignore_index=True)
+
+
+def _pair_up(rows, mate_1):
+    return [[mate_1(p, c), (p, c)] for p, c in rows]
+
+
+def gap_reads(df, layout, paired):
+    """
+    Reads over the border of two touching isolated genes (A ends where B begins): from A's last bases into B, from A's very
+    last base, and the one-base read on it.  As pairs, mate 1 lies just left of mate 2, in A.  Nothing on a layout without
+    such genes.
+    """
+    chrom, chrom_len, genes = layout
+    gdf, _ = tables(chrom, genes)
+    iso = set(get_gene_overlap_structure(gdf)['isolated_genes'])
+    span = {g: (int(a), int(b)) for g, a, b in zip(gdf.gene, gdf.gene_start, gdf.gene_end)}
+    rows = []
+    for (ga, _), (gb, _) in zip(genes[:-1], genes[1:]):
+        if ga in iso and gb in iso and span[ga][1] + 1 == span[gb][0]:
+            last = span[ga][1] - 1                       # 0-based last base of A
+            rows += [(last - 6, '20M'), (last, '12M'), (last, '1M'), (last - 3, '4M0M6M')]
+    units = _pair_up(rows, lambda p, c: (p - 9, '8M')) if paired else [[r] for r in rows]
+    return _append(df, units, paired)
+
+
+def first_base_reads(df, layout, paired):
+    """
+    Reads on the first base of every gene: a one-base segment there (1M, and 1M5N<k>M into the first exon) and a read whose
+    first segment starts there.  On an overlap gene the one-base segment is counted in the wrapped slot only.  As pairs,
+    mate 2 is the read and mate 1 a few bases to its right, so that no clip changes the segment.
+    """
+    chrom, chrom_len, genes = layout
+    rows = []
+    for _, exons in genes:
+        a, b = min(exons)
+        s = a - 1
+        rows += [(s, '1M'), (s, '9M')]
+        if b - a >= 20:
+            rows += [(s, '1M5N7M'), (s, '1M0M'), (s + 1, '0M6M')]
+    units = _pair_up(rows, lambda p, c: (p + 12, '5M')) if paired else [[r] for r in rows]
+    return _append(df, units, paired)
+
+
+def many_segment_reads(df, layout, paired, most=32):
+    """
+    Reads of many short M ops (2M1N ... and, where the exon is long enough, `most` times 1M1N) inside every gene's first
+    exon.  As pairs both mates are such reads, mate 2 some bases right of mate 1 and interleaved with it.
+    """
+    chrom, chrom_len, genes = layout
+    rows = []
+    for k, (_, exons) in enumerate(genes):
+        a, b = min(exons)
+        n = 4 + k % 5
+        if b - a >= 4 * n + 8:
+            rows.append((a + 2, '2M1N' * (n - 1) + '3M'))
+        if b - a >= 2 * most + 6:
+            rows.append((a - 1, '1M1N' * (most - 1) + '1M'))
+    units = _pair_up(rows, lambda p, c: (p + 1, c)) if paired else [[r] for r in rows]
+    return _append(df, units, paired)
+
+
+def position_zero_reads(df, paired):
+    """
+    Units with a bound below 0: rows at position 0 that begin with a zero-length M (its end is -1) and, as pairs, a mate
+    contained in a mate at position 0 (every bound of it is clipped to -1).  They pass the position pre-filter only on a
+    layout whose first gene starts on base 1.
+    """
+    if paired:
+        units = [[(0, '25M'), (3, '6M')], [(0, '30M'), (0, '10M2N5M')], [(0, '0M12M'), (14, '6M')], [(20, '6M'), (0, '0M9M')]]
+    else:
+        units = [[(0, '0M10M')], [(0, '0M')], [(0, '0M5N8M')]]
+    return _append(df, units, paired)
+
+
+def edge_case(layout_seed, paired, n=240, variant=None):
+    """
+    One seeded case with every mutator applied: (reads_df, layout).  Single-end rows are (qname, pos, cigar); paired rows
+    carry qname_unpaired and names that end in .1 / .2.
+    """
+    layout = random_layout(layout_seed, variant)
+    seed = 1000 + 2 * layout_seed + int(paired)
+    if paired:
+        df = synth_pairs(seed, layout, n // 2, skip=())
+        df = repeat_pair_ids(interleave_pairs(with_zero_length_ops(df, seed + 1), seed + 2), seed + 3)
+    else:
+        df = with_zero_length_ops(synth_reads(seed, layout, n, skip=()), seed + 1)
+    df = many_segment_reads(first_base_reads(gap_reads(df, layout, paired), layout, paired), layout, paired)
+    df = position_zero_reads(df, paired)
+    return df, layout
+
+
+def reads_max_seg():
+    """DN_READS_MAX_SEG of include/degnorm_amd.h: the M ops a row may have."""
+    import os
+    import re
+    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'degnorm_amd.h')) as f:
+        return int(re.search(r'#define\s+DN_READS_MAX_SEG\s+(\d+)', f.read()).group(1))
+
+
+def cap_layout():
+    """An overlap gene K with one long exon (first base 50, 0-based), its partner L, and an isolated gene."""
+    return 'chrK', 1300, [('K', [(51, 600)]), ('L', [(551, 700), (801, 900)]), ('M', [(1001, 1200)])]
+
+
+def cap_cigar(n_m, first=1):
+    """n_m M ops of one base (the first of `first` bases) with 1N between them."""
+    return '{0}M1N'.format(first) + '1M1N' * (n_m - 2) + '1M'
+
+
+def cap_reads(paired, most, start=50):
+    """
+    Rows with `most` M ops per row inside K's exon, from K's first base.  Single-end: the row there and one further in.
+    Paired: mate 1 on K's first base with a first M of two bases (its first segment is the wrapped slot and one more base),
+    mate 2 clear to its right, so the pair has 2 * most segments that all stay pieces, and the wrap piece on top of them;
+    and a second pair of such mates, interleaved with each other, in the other order.
+    """
+    if not paired:
+        rows = [('q0', start, cap_cigar(most, first=2)), ('q1', start + 10, cap_cigar(most)), ('q2', start + 300, '40M')]
+        return pd.DataFrame(rows, columns=['qname', 'pos', 'cigar'])
+    far = start + 2 * most + 40
+    rows = [('p0.1', start, cap_cigar(most, first=2), 'p0'), ('p0.2', far, cap_cigar(most), 'p0'),
+            ('p1.2', far + 1, cap_cigar(most), 'p1'), ('p1.1', far, cap_cigar(most), 'p1'),
+            ('p2.1', start + 300, '40M', 'p2'), ('p2.2', start + 320, '40M', 'p2')]
     return pd.DataFrame(rows, columns=['qname', 'pos', 'cigar', 'qname_unpaired'])
 
 

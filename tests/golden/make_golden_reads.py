@@ -1,5 +1,6 @@
 """
-Goldens of the reads -> coverage / read counts path (tests/golden/reads.npz) from the real reference.
+Goldens of the reads -> coverage / read counts path (tests/golden/reads.npz, tests/golden/reads_edges.npz) from the real
+reference.
 
     python tests/golden/make_golden_reads.py /path/to/DegNorm
 
@@ -10,6 +11,13 @@ overlap structure comes from degnorm_amd.gene_processing (the reference's needs 
   pe   paired reads on the same layout (overlapping / contained / spliced mates, swapped mate order, orphans)
   qi   single-end reads on a chromosome whose isolated stage gets no read (no chrom_coverage file)
   fz   random CIGAR strings and the reference's cigar_segment_bounds output (nseg 0: ValueError)
+
+reads_edges.npz holds the seeded edge cases of _reads_fixtures.edge_case (random annotations, the groups-only and the
+isolated-only variant, every read mutator) and the two segment-cap cases (_reads_fixtures.cap_reads: DN_READS_MAX_SEG M ops
+per row) under the keys e00, e01, ... in the same layout, each with the census of
+tests/_reads_oracle.py (<key>_census, in the order of census_keys).  Units with a bound below 0 -- which the library drops
+and the reference does not -- are taken out of these cases first, found by the restatement; and the restatement has to
+reproduce the reference's outputs here, or the script stops.
 """
 import os
 import pickle
@@ -24,6 +32,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
 import _reads_fixtures as rf                      # noqa: E402
+import _reads_oracle as ro                        # noqa: E402
 from degnorm_amd.gene_processing import get_gene_overlap_structure  # noqa: E402
 
 
@@ -72,10 +81,56 @@ def run_reference(R, reads_df, paired, layout, workdir):
     p.chromosome_coverage_read_counts(ov, gene_df, exon_df, chrom)
     f_csr = os.path.join(workdir, 'chrom_coverage_s1_{0}.npz'.format(chrom))
     csr = sparse.load_npz(f_csr) if os.path.isfile(f_csr) else None
-    with open(os.path.join(workdir, 'overlap_coverage_s1_{0}.pkl'.format(chrom)), 'rb') as f:
-        ol = pickle.load(f)
+    f_ol = os.path.join(workdir, 'overlap_coverage_s1_{0}.pkl'.format(chrom))
+    ol = {}                                       # no overlap group: the reference writes no file
+    if os.path.isfile(f_ol):
+        with open(f_ol, 'rb') as f:
+            ol = pickle.load(f)
     cnt = pd.read_csv(os.path.join(workdir, 'read_counts_s1_{0}.csv'.format(chrom)))
     return csr, ol, dict(zip(cnt.gene, cnt.s1))
+
+
+# (layout seed, paired, variant) of the cases e00, e01, ...; the segment-cap cases follow them
+EDGE_CASES = [(s, p, None) for s in range(5) for p in (False, True)] + \
+             [(5, p, v) for v in ('groups_only', 'isolated_only') for p in (False, True)]
+
+
+def without_negative_units(df, layout, paired):
+    """The case without the units the library drops for a bound below 0, and its census (negative_bound == 0)."""
+    chrom, chrom_len, genes = layout
+    gene_df, exon_df = rf.tables(chrom, genes)
+    ov = get_gene_overlap_structure(gene_df)
+    while True:
+        trace = {}
+        res = ro.restate(df, chrom_len, ov, gene_df, exon_df, paired, trace=trace)
+        if not trace['negative_rows']:
+            assert res[3]['negative_bound'] == 0
+            return df, res
+        df = df.drop(df.index[trace['negative_rows']]).reset_index(drop=True)
+
+
+def edge_cases(R):
+    out, total = {'census_keys': np.array(ro.CENSUS_KEYS, dtype='U32')}, []
+    cases = [rf.edge_case(seed, paired, variant=variant) + (paired, 'seed {0} {1}'.format(seed, variant or '')) for seed, paired, variant in EDGE_CASES]
+    cases += [(rf.cap_reads(paired, rf.reads_max_seg()), rf.cap_layout(), paired, 'segment cap') for paired in (False, True)]
+    for k, (df, layout, paired, what) in enumerate(cases):
+        key = 'e{0:02d}'.format(k)
+        df, restated = without_negative_units(df, layout, paired)
+        with tempfile.TemporaryDirectory() as d:
+            res = run_reference(R, df, paired, layout, d)
+        ro.assert_same((res[0], {g: v.astype(np.int64) for g, v in res[1].items()}, {g: int(v) for g, v in res[2].items()}),
+                       restated, key)
+        pack(out, key, df, paired, layout, res)
+        out[key + '_census'] = np.array([restated[3][c] for c in ro.CENSUS_KEYS], dtype=np.int64)
+        total.append(restated[3])
+        print(key, what, 'paired' if paired else 'single', len(df), 'rows; counted', int(out[key + '_counts'].sum()))
+    total = ro.merge_census(total)
+    print('census of the edge cases:', dict(total))
+    missing = [c for c in ro.CENSUS_KEYS if total[c] == 0 and c not in ('negative_bound', 'iso_gap_drop')]
+    assert not missing and total['nseg_max'] >= 4, missing
+    path = os.path.join(ROOT, 'tests', 'golden', 'reads_edges.npz')
+    np.savez_compressed(path, **out)
+    print(path, os.path.getsize(path), 'bytes')
 
 
 def main(ref_root):
@@ -111,6 +166,7 @@ def main(ref_root):
     path = os.path.join(ROOT, 'tests', 'golden', 'reads.npz')
     np.savez_compressed(path, **out)
     print(path, os.path.getsize(path), 'bytes')
+    edge_cases(R)
 
 
 if __name__ == '__main__':
