@@ -426,6 +426,24 @@ struct dn_handle_s {
     bool have_trace = false;
 };
 
+// The exit rule (dn::synced, dn_host.hpp) of the calls that queue on more than the handle's main stream -- the upload and
+// dn_baseline_iteration: run `body`, then wait for every class stream.  dn_destroy waits the same way before it deletes.
+static void wait_streams(dn_handle h) { for (const dn::Stream &st : h->stream) if (st) (void) hipStreamSynchronize(st); }
+
+template <class F> static int synced_classes(dn_handle h, F body)
+{
+    const int rc = body();
+    wait_streams(h);
+    return rc;
+}
+
+// the other entry points: on the handle's device, `body` under dn::synced on the main stream
+template <class F> static int on_main_stream(dn_handle h, F body)
+{
+    DN_TRY(hipSetDevice(h->device));
+    return dn::synced(h->stream[0], body);
+}
+
 // ---------------------------------------------------------------------------------------------------
 // RCCL, resolved at run time.  The library carries no link-time dependency on librccl: a host process that already
 // has one mapped (PyTorch ships its own copy) must share THAT copy -- two RCCL instances in one process each bring their
@@ -511,6 +529,51 @@ int check_f64_batch(dn_handle h, int64_t n, int32_t p, const double *const *x, c
     }
     return DN_OK;
 }
+
+// Pack a float64 batch as the device takes it: matrix m (p x lengths[m], row-major) goes to off[m] of `packed`, its columns
+// start at col[m] (both n + 1 long, off = p * col), `order` is the work queue, longest first.  Returns the longest length.
+// Queued copies read these vectors: the entry point declares them outside its body.
+int64_t pack_f64(int64_t n, int32_t p, const double *const *x, const int64_t *lengths, std::vector<int64_t> &off, std::vector<int64_t> &col,
+                 std::vector<int32_t> &len, std::vector<int32_t> &order, std::vector<double> &packed)
+{
+    int64_t longest = 0;
+    off.assign(n + 1, 0); col.assign(n + 1, 0); len.resize(n); order.resize(n);
+    for (int64_t m = 0; m < n; m++) {
+        len[m] = (int32_t) lengths[m];
+        col[m + 1] = col[m] + lengths[m];
+        off[m + 1] = (int64_t) p * col[m + 1];
+        longest = std::max<int64_t>(longest, lengths[m]);
+    }
+    packed.resize((size_t) off[n]);
+    for (int64_t m = 0; m < n; m++) std::memcpy(packed.data() + off[m], x[m], sizeof(double) * (size_t) p * (size_t) lengths[m]);
+    std::iota(order.begin(), order.end(), 0);
+    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return len[a] > len[b]; });
+    return longest;
+}
+
+// estimate tiles of gene g: (gene, first column) per 256 columns
+void add_tiles(std::vector<int32_t> &tg, std::vector<int32_t> &tc, int64_t g, int32_t len)
+{
+    for (int32_t c = 0; c < len; c += 256) { tg.push_back((int32_t) g); tc.push_back(c); }
+}
+
+// the dn_params of a baseline iteration and the take-every offsets of its n genes; length(g) is the length of gene g
+template <class L> int check_params(const dn_params *prm, const int64_t *ds_start, int64_t n, L length)
+{
+    if (prm->nmf_iter < 1) return fail(DN_E_INVALID, "nmf_iter must be >= 1");
+    if (prm->bins < 1 || prm->bins > dn::MAX_BINS) return fail(DN_E_INVALID, "bins must be in [1, 64]");
+    if (prm->min_high_coverage < 2) return fail(DN_E_INVALID, "min_high_coverage must be >= 2 (nmf.py:34)");
+    if (prm->downsample_rate < 1) return fail(DN_E_INVALID, "downsample_rate must be >= 1");
+    if (prm->downsample_rate > 1) {
+        if (!ds_start) return fail(DN_E_INVALID, "downsample_rate > 1 needs per-gene start offsets");
+        for (int64_t g = 0; g < n; g++) {
+            // nmf.py:443-444 / :479-481: cannot downsample at a rate >= gene length
+            if (length(g) <= prm->downsample_rate) return fail(DN_E_INVALID, "downsample_rate is too large; take-every size > at least one gene.");
+            if (ds_start[g] < 0 || ds_start[g] >= prm->downsample_rate) return fail(DN_E_INVALID, "ds_start out of [0, rate)");
+        }
+    }
+    return DN_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -582,10 +645,21 @@ int dn_destroy(dn_handle h)
 {
     if (!h) return DN_OK;
     (void) hipSetDevice(h->device);
-    if (h->stream[0]) (void) hipStreamSynchronize(h->stream[0]);
+    wait_streams(h);
     (void) dn_comm_destroy(h);
     delete h;                                // the owners release the buffers, then the events and streams
     return DN_OK;
+}
+
+// Lambda LDS tier of kernel set `ks` at `per_cu` resident workgroups, in columns per gene: whatever of the CU's 160 KiB is
+// left per workgroup after the static part, shared by the genes the workgroup carries; a column is p doubles, rounded up to
+// an even number (16-byte aligned).  Only the pair build carries more than one gene (units = 2); the wide and narrow sets
+// have units = 1, and the narrow boundary of class_lengths, which never divided by units, relies on that.
+static int64_t lds_tier_cols(const dn::KernelSet *ks, int per_cu, int32_t p)
+{
+    const int64_t lds_per_block = (160 * 1024) / per_cu - (int64_t) ks->static_lds_bytes - 256;
+    const int64_t ps = p + (p & 1);
+    return lds_per_block > 0 ? lds_per_block / std::max(1, ks->units) / (8 * ps) : 0;
 }
 
 // Scratch slots and LDS tier of one gene class for genes of up to `cols` active columns.  The new scratch is allocated
@@ -615,13 +689,9 @@ static int size_class(dn_handle h, dn_handle_s::GeneClass &C, int32_t cols)
     DN_TRY(ws.alloc((size_t) slot_bytes * (size_t) std::max(slots, 1)));
     C.d_ws = std::move(ws);                                // releases the old scratch
     C.slots = slots; C.S = S; C.slot_bytes = slot_bytes;
-    // lambda LDS tier: whatever of the CU's 160 KiB is left per resident workgroup after the static part
-    const int64_t lds_per_block = (160 * 1024) / per_cu - (int64_t) C.ks->static_lds_bytes - 256;
-    const int64_t ps = p + (p & 1);                        // LDS column stride in doubles (16-B aligned)
-    int64_t lcols = lds_per_block > 0 ? lds_per_block / units / (8 * ps) : 0;
-    lcols = std::min<int64_t>(lcols, C.S) & ~(int64_t) 1;
+    const int64_t lcols = std::min<int64_t>(lds_tier_cols(C.ks, per_cu, p), C.S) & ~(int64_t) 1;
     C.lds_cols = (int32_t) lcols;                          // per unit
-    C.dyn_lds = (size_t) units * (size_t) lcols * 8 * (size_t) ps;
+    C.dyn_lds = (size_t) units * (size_t) lcols * 8 * (size_t) (p + (p & 1));
     return DN_OK;
 }
 
@@ -667,34 +737,31 @@ static void pack_genes(dn_handle h, const CoverageSource &src, int64_t g0, int64
 
 // Chunked, double-buffered upload of a ragged data set: two pinned staging buffers of ~128 MB; the host threads pack chunk
 // k + 1 while chunk k travels (a single 2 GB pinned buffer cost more to allocate than the whole copy takes).
-static int upload_ragged_chunks(dn_handle h, const CoverageSource &src)
+// The staging pair and the events that tell when each is free again belong to the caller: they outlive its wait for the stream.
+static int upload_ragged_chunks(dn_handle h, const CoverageSource &src, dn::PinnedBuffer<float> (&stage)[2], dn::Event (&done)[2])
 {
     const int64_t n = h->n;
     int64_t chunk = (int64_t) 32 << 20;                                     // floats per staging buffer
     if (const char *env = getenv("DN_UPLOAD_CHUNK_FLOATS")) chunk = std::max<int64_t>(1, atoll(env));    // tests: many small chunks
     for (int64_t g = 0; g < n; g++) chunk = std::max(chunk, (int64_t) h->p * h->glen[g]);
     chunk = std::min(chunk, std::max<int64_t>(h->total, 1));
-    dn::PinnedBuffer<float> stage[2];
-    dn::Event done[2];
-    int rc = DN_OK;
-    for (int b = 0; b < 2 && rc == DN_OK; b++) {
+    for (int b = 0; b < 2; b++) {
         if (stage[b].alloc(sizeof(float) * (size_t) chunk) != hipSuccess ||
-            done[b].create(hipEventCreateWithFlags, hipEventDisableTiming) != hipSuccess) rc = fail(DN_E_HIP, "upload: pinned staging buffer");
+            done[b].create(hipEventCreateWithFlags, hipEventDisableTiming) != hipSuccess) return fail(DN_E_HIP, "upload: pinned staging buffer");
     }
     int64_t g0 = 0;
-    for (int k = 0; rc == DN_OK && g0 < n; k++) {
+    for (int k = 0; g0 < n; k++) {
         int64_t g1 = g0, fl = 0;
         while (g1 < n && fl + (int64_t) h->p * h->glen[g1] <= chunk) { fl += (int64_t) h->p * h->glen[g1]; g1++; }
         const int b = k & 1;
-        if (k >= 2 && hipEventSynchronize(done[b]) != hipSuccess) { rc = fail(DN_E_HIP, "upload: event"); break; }
+        if (k >= 2 && hipEventSynchronize(done[b]) != hipSuccess) return fail(DN_E_HIP, "upload: event");
         pack_genes(h, src, g0, g1, stage[b]);
         if (hipMemcpyAsync(h->data.d_cov + h->goff[g0], stage[b], sizeof(float) * (size_t) fl, hipMemcpyHostToDevice, h->stream[0]) != hipSuccess ||
-            hipEventRecord(done[b], h->stream[0]) != hipSuccess) { rc = fail(DN_E_HIP, "upload: copy"); break; }
+            hipEventRecord(done[b], h->stream[0]) != hipSuccess) return fail(DN_E_HIP, "upload: copy");
         g0 = g1;
     }
-    if (rc == DN_OK && hipStreamSynchronize(h->stream[0]) != hipSuccess) rc = fail(DN_E_HIP, "upload: synchronize");
-    if (rc != DN_OK) (void) hipStreamSynchronize(h->stream[0]);                // nothing may still read the staging buffers
-    return rc;
+    if (hipStreamSynchronize(h->stream[0]) != hipSuccess) return fail(DN_E_HIP, "upload: synchronize");
+    return DN_OK;
 }
 
 // Class boundaries of a cohort of p samples served by kernel set `ks` (see dn_handle_s::GeneClass): genes longer than
@@ -714,9 +781,7 @@ static void class_lengths(const dn::KernelSet *ks, int32_t p, int32_t &split_len
             // measured optimum of the boundary on config 2: 3 600-4 000 bases, i.e. ~1.7 x that capacity (split 2 600 /
             // 3 000 / 3 400 / 3 800 / 4 200 -> 11 510 / 11 740 / 11 920 / 11 950 / 11 890 genes/s).  Without a register
             // tier: ~2.1 x the LDS columns (round 1: 2 000-2 200 at 975 columns).
-            const int per_cu_n = std::max(1, narrow->blocks_per_cu(0));
-            const int64_t lds_n = (160 * 1024) / per_cu_n - (int64_t) narrow->static_lds_bytes - 256;
-            const int64_t lds_cols_n = std::max<int64_t>(0, lds_n / (8 * (int64_t) (p + (p & 1))));
+            const int64_t lds_cols_n = lds_tier_cols(narrow, std::max(1, narrow->blocks_per_cu(0)), p);
             const int64_t reg_cols_n = narrow->reg_tier_cols;
             // round 3: 1.775 x capacity (4 000 bases at p = 10) instead of 1.7 x (3 831): the same on the full configuration (-0.2 %), but
             // +2.4 % at the shard sizes of 2 and 8 GPUs (10 000 / 2 500 genes: 727 vs 745 ms, 191 vs 196 ms per run) -- with few genes
@@ -736,78 +801,76 @@ static void class_lengths(const dn::KernelSet *ks, int32_t p, int32_t &split_len
         if (pair) {
             const char *tenv = getenv("DN_TINY_LEN");
             if (tenv) tiny_len = atoi(tenv);
-            else {
-                const int per_cu_t = std::max(1, pair->blocks_per_cu(0));
-                const int64_t lds_t = ((160 * 1024) / per_cu_t - (int64_t) pair->static_lds_bytes - 256) / std::max(1, pair->units);
-                const int64_t lds_cols_t = std::max<int64_t>(0, lds_t / (8 * (int64_t) (p + (p & 1))));
-                tiny_len = (int32_t) (1.7 * (double) (pair->reg_tier_cols + lds_cols_t));
-            }
+            else tiny_len = (int32_t) (1.7 * (double) (pair->reg_tier_cols + lds_tier_cols(pair, std::max(1, pair->blocks_per_cu(0)), p)));
             tiny_len = std::min(tiny_len, split_len);
             if (tiny_len <= 0) { pair = nullptr; tiny_len = 0; }
         }
     }
 }
 
-static int finish_upload_impl(dn_handle h, const CoverageSource &src)
+// Queue the upload and wait for it.  What the queued copies read -- the work queue, the estimate tiles, the staging pair of a
+// ragged upload -- is declared here, outside the body.  A failed upload leaves the handle EMPTY (no resident coverage, later
+// calls return DN_E_STATE), never half-sized.
+static int finish_upload(dn_handle h, const CoverageSource &src)
 {
-    const int64_t n = h->n;
-    const int32_t p = h->p;
-    free_device(h);
-    DN_TRY(hipSetDevice(h->device));
+    std::vector<int32_t> order, tg, tc;
+    dn::PinnedBuffer<float> stage[2];
+    dn::Event done[2];
+    const int rc = synced_classes(h, [&]() -> int {
+        const int64_t n = h->n;
+        const int32_t p = h->p;
+        free_device(h);
+        DN_TRY(hipSetDevice(h->device));
 
-    // work queue: longest gene first (a 17-call gene costs ~17x a 1-call gene)
-    h->have_trace = false;
-    std::vector<int32_t> order(n);
-    std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return h->glen[a] > h->glen[b]; });
+        // work queue: longest gene first (a 17-call gene costs ~17x a 1-call gene)
+        h->have_trace = false;
+        order.resize(n);
+        std::iota(order.begin(), order.end(), 0);
+        std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return h->glen[a] > h->glen[b]; });
 
-    h->svoff.assign(n + 1, 0);
-    for (int64_t g = 0; g < n; g++) h->svoff[g + 1] = h->svoff[g] + h->glen[g];
+        h->svoff.assign(n + 1, 0);
+        for (int64_t g = 0; g < n; g++) h->svoff[g + 1] = h->svoff[g] + h->glen[g];
 
-    // estimate tiles: (gene, first column) per 256 columns
-    std::vector<int32_t> tg, tc;
-    for (int64_t g = 0; g < n; g++)
-        for (int32_t c = 0; c < h->glen[g]; c += 256) { tg.push_back((int32_t) g); tc.push_back(c); }
-    h->n_tiles = (int64_t) tg.size();
+        for (int64_t g = 0; g < n; g++) add_tiles(tg, tc, g, h->glen[g]);
+        h->n_tiles = (int64_t) tg.size();
 
-    DN_TRY(h->data.d_cov.alloc(sizeof(float) * (size_t) std::max<int64_t>(h->total, 1)));
-    DN_TRY(h->data.d_goff.alloc(sizeof(int64_t) * (size_t) (n + 1)));
-    DN_TRY(h->data.d_glen.alloc(sizeof(int32_t) * (size_t) n));
-    DN_TRY(h->data.d_order.alloc(sizeof(int32_t) * (size_t) n));
-    DN_TRY(h->data.d_counter.alloc(sizeof(int32_t) * 4));
-    DN_TRY(h->data.d_ds.alloc(sizeof(int64_t) * (size_t) n));
-    DN_TRY(h->data.d_rho.alloc(sizeof(double) * (size_t) n * p));
-    DN_TRY(h->data.d_flags.alloc(sizeof(int32_t) * (size_t) n));
-    DN_TRY(h->data.d_trace.alloc(sizeof(int32_t) * (size_t) n * dn::TRACE_LEN));
-    DN_TRY(h->data.d_kfin.alloc(sizeof(double) * (size_t) n * p));
-    DN_TRY(h->data.d_emode.alloc(sizeof(int32_t) * (size_t) n));
-    DN_TRY(h->data.d_svoff.alloc(sizeof(int64_t) * (size_t) (n + 1)));
-    DN_TRY(h->data.d_est_sums.alloc(sizeof(double) * (size_t) n * p));
-    DN_TRY(h->data.d_cov_sums.alloc(sizeof(double) * (size_t) n * p));
-    DN_TRY(h->data.d_status.alloc(sizeof(int32_t) * (size_t) n));
-    DN_TRY(h->data.d_rowmax.alloc(sizeof(float) * (size_t) n * p));
-    DN_TRY(h->data.d_x16.alloc(sizeof(int32_t) * (size_t) n));
-    DN_TRY(h->data.d_tile_gene.alloc(sizeof(int32_t) * (size_t) std::max<int64_t>(h->n_tiles, 1)));
-    DN_TRY(h->data.d_tile_col.alloc(sizeof(int32_t) * (size_t) std::max<int64_t>(h->n_tiles, 1)));
+        DN_TRY(h->data.d_cov.alloc(sizeof(float) * (size_t) std::max<int64_t>(h->total, 1)));
+        DN_TRY(h->data.d_goff.alloc(sizeof(int64_t) * (size_t) (n + 1)));
+        DN_TRY(h->data.d_glen.alloc(sizeof(int32_t) * (size_t) n));
+        DN_TRY(h->data.d_order.alloc(sizeof(int32_t) * (size_t) n));
+        DN_TRY(h->data.d_counter.alloc(sizeof(int32_t) * 4));
+        DN_TRY(h->data.d_ds.alloc(sizeof(int64_t) * (size_t) n));
+        DN_TRY(h->data.d_rho.alloc(sizeof(double) * (size_t) n * p));
+        DN_TRY(h->data.d_flags.alloc(sizeof(int32_t) * (size_t) n));
+        DN_TRY(h->data.d_trace.alloc(sizeof(int32_t) * (size_t) n * dn::TRACE_LEN));
+        DN_TRY(h->data.d_kfin.alloc(sizeof(double) * (size_t) n * p));
+        DN_TRY(h->data.d_emode.alloc(sizeof(int32_t) * (size_t) n));
+        DN_TRY(h->data.d_svoff.alloc(sizeof(int64_t) * (size_t) (n + 1)));
+        DN_TRY(h->data.d_est_sums.alloc(sizeof(double) * (size_t) n * p));
+        DN_TRY(h->data.d_cov_sums.alloc(sizeof(double) * (size_t) n * p));
+        DN_TRY(h->data.d_status.alloc(sizeof(int32_t) * (size_t) n));
+        DN_TRY(h->data.d_rowmax.alloc(sizeof(float) * (size_t) n * p));
+        DN_TRY(h->data.d_x16.alloc(sizeof(int32_t) * (size_t) n));
+        DN_TRY(h->data.d_tile_gene.alloc(sizeof(int32_t) * (size_t) std::max<int64_t>(h->n_tiles, 1)));
+        DN_TRY(h->data.d_tile_col.alloc(sizeof(int32_t) * (size_t) std::max<int64_t>(h->n_tiles, 1)));
 
-    if (src.packed) DN_TRY(hipMemcpyAsync(h->data.d_cov, src.packed, sizeof(float) * (size_t) h->total, hipMemcpyHostToDevice, h->stream[0]));
-    else { const int rcu = upload_ragged_chunks(h, src); if (rcu != DN_OK) return rcu; }
-    DN_TRY(hipMemcpyAsync(h->data.d_goff, h->goff.data(), sizeof(int64_t) * (size_t) (n + 1), hipMemcpyHostToDevice, h->stream[0]));
-    DN_TRY(hipMemcpyAsync(h->data.d_glen, h->glen.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
-    DN_TRY(hipMemcpyAsync(h->data.d_order, order.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
-    DN_TRY(hipMemcpyAsync(h->data.d_svoff, h->svoff.data(), sizeof(int64_t) * (size_t) (n + 1), hipMemcpyHostToDevice, h->stream[0]));
-    DN_TRY(hipMemcpyAsync(h->data.d_tile_gene, tg.data(), sizeof(int32_t) * tg.size(), hipMemcpyHostToDevice, h->stream[0]));
-    DN_TRY(hipMemcpyAsync(h->data.d_tile_col, tc.data(), sizeof(int32_t) * tc.size(), hipMemcpyHostToDevice, h->stream[0]));
-    DN_TRY(hipEventRecord(h->ev_i0, h->stream[0]));
-    hipLaunchKernelGGL(k_row_max, dim3((unsigned) std::min<int64_t>(n, (int64_t) h->n_cus * 8)), dim3(256), 0, h->stream[0],
-                       h->data.d_cov, h->data.d_goff, h->data.d_glen, h->data.d_rowmax, h->data.d_x16, (int) n, (int) p);
-    DN_TRY(hipGetLastError());
-    DN_TRY(hipEventRecord(h->ev_i1, h->stream[0]));
-    DN_TRY(hipStreamSynchronize(h->stream[0]));
-    (void) hipEventElapsedTime(&h->last_rowmax_ms, h->ev_i0, h->ev_i1);
+        if (src.packed) DN_TRY(hipMemcpyAsync(h->data.d_cov, src.packed, sizeof(float) * (size_t) h->total, hipMemcpyHostToDevice, h->stream[0]));
+        else { const int rcu = upload_ragged_chunks(h, src, stage, done); if (rcu != DN_OK) return rcu; }
+        DN_TRY(hipMemcpyAsync(h->data.d_goff, h->goff.data(), sizeof(int64_t) * (size_t) (n + 1), hipMemcpyHostToDevice, h->stream[0]));
+        DN_TRY(hipMemcpyAsync(h->data.d_glen, h->glen.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
+        DN_TRY(hipMemcpyAsync(h->data.d_order, order.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
+        DN_TRY(hipMemcpyAsync(h->data.d_svoff, h->svoff.data(), sizeof(int64_t) * (size_t) (n + 1), hipMemcpyHostToDevice, h->stream[0]));
+        DN_TRY(hipMemcpyAsync(h->data.d_tile_gene, tg.data(), sizeof(int32_t) * tg.size(), hipMemcpyHostToDevice, h->stream[0]));
+        DN_TRY(hipMemcpyAsync(h->data.d_tile_col, tc.data(), sizeof(int32_t) * tc.size(), hipMemcpyHostToDevice, h->stream[0]));
+        DN_TRY(hipEventRecord(h->ev_i0, h->stream[0]));
+        hipLaunchKernelGGL(k_row_max, dim3((unsigned) std::min<int64_t>(n, (int64_t) h->n_cus * 8)), dim3(256), 0, h->stream[0],
+                           h->data.d_cov, h->data.d_goff, h->data.d_glen, h->data.d_rowmax, h->data.d_x16, (int) n, (int) p);
+        DN_TRY(hipGetLastError());
+        DN_TRY(hipEventRecord(h->ev_i1, h->stream[0]));
+        DN_TRY(hipStreamSynchronize(h->stream[0]));
+        (void) hipEventElapsedTime(&h->last_rowmax_ms, h->ev_i0, h->ev_i1);
 
-    // gene classes
-    {
+        // gene classes
         const dn::KernelSet *pair = nullptr;
         class_lengths(h->ks, p, h->split_len, h->tiny_len, pair);
         std::vector<int32_t> ord[dn_handle_s::NCLS];
@@ -848,14 +911,8 @@ static int finish_upload_impl(dn_handle h, const CoverageSource &src)
             if (rc != DN_OK) return rc;
         }
         if (h->data.cls[0].n == 0 && (h->data.cls[1].n > 0 || h->data.cls[2].n > 0) && h->ks->p == 0) return fail(DN_E_STATE, "internal: empty wide class for the generic kernels");
-    }
-    return DN_OK;
-}
-
-// A failed upload leaves the handle EMPTY (no resident coverage, later calls return DN_E_STATE), never half-sized.
-static int finish_upload(dn_handle h, const CoverageSource &src)
-{
-    const int rc = finish_upload_impl(h, src);
+        return DN_OK;
+    });
     if (rc != DN_OK) {
         const std::string msg = g_err;
         free_device(h);
@@ -955,35 +1012,36 @@ int dn_ratio_svd_sums(dn_handle h, double *est_sums, double *cov_sums, int32_t *
 {
     if (!h || !h->data.d_cov) return fail(DN_E_STATE, "dn_ratio_svd_sums: nothing uploaded");
     if ((est_sums == nullptr) != (cov_sums == nullptr)) return fail(DN_E_INVALID, "dn_ratio_svd_sums: the two sums are fetched together or not at all");
-    DN_TRY(hipSetDevice(h->device));
     dn::InitArgs a;
     a.cov = h->data.d_cov; a.goff = h->data.d_goff; a.glen = h->data.d_glen; a.order = h->data.d_order; a.counter = h->data.d_counter;
     a.est_sums = h->data.d_est_sums; a.cov_sums = h->data.d_cov_sums; a.status = h->data.d_status; a.n_genes = (int32_t) h->n;
     a.p = h->p; a.ws = h->data.cls[0].d_ws; a.slot_bytes = h->data.cls[0].slot_bytes; a.S = h->data.cls[0].S; a.max_steps = h->max_steps;
     a.x16 = h->data.d_x16;
     { const char *f64 = getenv("DN_INIT_FP64"); a.force_fp64 = (f64 && f64[0] == '1') ? 1 : 0; }
-    DN_TRY(hipMemsetAsync(h->data.d_counter, 0, sizeof(int32_t) * 4, h->stream[0]));
-    // occupancy of the kernel that ks->init() will start: from 17 samples on it is the matrix-core variant (round 2 asked for
-    // the power-iteration kernel's figure here and ran k_ratio_svd_mg at ONE workgroup per CU instead of two)
-    const int which_init = h->p >= 17 ? 2 : 1;
-    int per_cu = std::max(1, h->ks->blocks_per_cu(which_init));
-    int grid = (int) std::min<int64_t>(h->n, (int64_t) per_cu * h->n_cus);
-    if (h->ks->p == 0) grid = std::min(grid, h->data.cls[0].slots);          // generic kernels work in the scratch slots
-    DN_TRY(hipEventRecord(h->ev_i0, h->stream[0]));
-    h->ks->init(a, grid, h->stream[0]);
-    DN_TRY(hipGetLastError());
-    DN_TRY(hipEventRecord(h->ev_i1, h->stream[0]));
-    const size_t np = (size_t) h->n * h->p;
-    if (est_sums) {                     // null: the sums stay on the device (dn_init_partials reduces them there)
-        DN_TRY(hipMemcpyAsync(est_sums, h->data.d_est_sums, sizeof(double) * np, hipMemcpyDeviceToHost, h->stream[0]));
-        DN_TRY(hipMemcpyAsync(cov_sums, h->data.d_cov_sums, sizeof(double) * np, hipMemcpyDeviceToHost, h->stream[0]));
-    }
-    if (status) DN_TRY(hipMemcpyAsync(status, h->data.d_status, sizeof(int32_t) * (size_t) h->n, hipMemcpyDeviceToHost, h->stream[0]));
-    DN_TRY(hipStreamSynchronize(h->stream[0]));
-    DN_TRY(hipEventElapsedTime(&h->last_init_ms, h->ev_i0, h->ev_i1));
-    if (h->ks->p >= 2 && h->ks->p <= 16) snprintf(h->init_name, sizeof(h->init_name), "k_ratio_svd<%d,%d>", h->ks->p, h->ks->nt);
-    else snprintf(h->init_name, sizeof(h->init_name), h->p >= 17 ? "gen::k_ratio_svd_mg" : "gen::k_ratio_svd_gen");
-    return DN_OK;
+    return on_main_stream(h, [&]() -> int {
+        DN_TRY(hipMemsetAsync(h->data.d_counter, 0, sizeof(int32_t) * 4, h->stream[0]));
+        // occupancy of the kernel that ks->init() will start: from 17 samples on it is the matrix-core variant (round 2 asked for
+        // the power-iteration kernel's figure here and ran k_ratio_svd_mg at ONE workgroup per CU instead of two)
+        const int which_init = h->p >= 17 ? 2 : 1;
+        int per_cu = std::max(1, h->ks->blocks_per_cu(which_init));
+        int grid = (int) std::min<int64_t>(h->n, (int64_t) per_cu * h->n_cus);
+        if (h->ks->p == 0) grid = std::min(grid, h->data.cls[0].slots);          // generic kernels work in the scratch slots
+        DN_TRY(hipEventRecord(h->ev_i0, h->stream[0]));
+        h->ks->init(a, grid, h->stream[0]);
+        DN_TRY(hipGetLastError());
+        DN_TRY(hipEventRecord(h->ev_i1, h->stream[0]));
+        const size_t np = (size_t) h->n * h->p;
+        if (est_sums) {                     // null: the sums stay on the device (dn_init_partials reduces them there)
+            DN_TRY(hipMemcpyAsync(est_sums, h->data.d_est_sums, sizeof(double) * np, hipMemcpyDeviceToHost, h->stream[0]));
+            DN_TRY(hipMemcpyAsync(cov_sums, h->data.d_cov_sums, sizeof(double) * np, hipMemcpyDeviceToHost, h->stream[0]));
+        }
+        if (status) DN_TRY(hipMemcpyAsync(status, h->data.d_status, sizeof(int32_t) * (size_t) h->n, hipMemcpyDeviceToHost, h->stream[0]));
+        DN_TRY(hipStreamSynchronize(h->stream[0]));
+        DN_TRY(hipEventElapsedTime(&h->last_init_ms, h->ev_i0, h->ev_i1));
+        if (h->ks->p >= 2 && h->ks->p <= 16) snprintf(h->init_name, sizeof(h->init_name), "k_ratio_svd<%d,%d>", h->ks->p, h->ks->nt);
+        else snprintf(h->init_name, sizeof(h->init_name), h->p >= 17 ? "gen::k_ratio_svd_mg" : "gen::k_ratio_svd_gen");
+        return DN_OK;
+    });
 }
 
 int dn_baseline_iteration(dn_handle h, const double *scale, const dn_params *prm, const int64_t *ds_start,
@@ -992,22 +1050,10 @@ int dn_baseline_iteration(dn_handle h, const double *scale, const dn_params *prm
     if (!h || !h->data.d_cov) return fail(DN_E_STATE, "dn_baseline_iteration: nothing uploaded");
     if (!scale || !prm) return fail(DN_E_INVALID, "dn_baseline_iteration: null argument");
     if ((rho == nullptr) != (flags == nullptr)) return fail(DN_E_INVALID, "dn_baseline_iteration: rho and flags are fetched together or not at all");
-    if (prm->nmf_iter < 1) return fail(DN_E_INVALID, "nmf_iter must be >= 1");
-    if (prm->bins < 1 || prm->bins > dn::MAX_BINS) return fail(DN_E_INVALID, "bins must be in [1, 64]");
-    if (prm->min_high_coverage < 2) return fail(DN_E_INVALID, "min_high_coverage must be >= 2 (nmf.py:34)");
-    if (prm->downsample_rate < 1) return fail(DN_E_INVALID, "downsample_rate must be >= 1");
-    if (prm->downsample_rate > 1) {
-        if (!ds_start) return fail(DN_E_INVALID, "downsample_rate > 1 needs per-gene start offsets");
-        for (int64_t g = 0; g < h->n; g++) {
-            // nmf.py:443-444 / :479-481: cannot downsample at a rate >= gene length
-            if (h->glen[g] <= prm->downsample_rate) return fail(DN_E_INVALID, "downsample_rate is too large; take-every size > at least one gene.");
-            if (ds_start[g] < 0 || ds_start[g] >= prm->downsample_rate) return fail(DN_E_INVALID, "ds_start out of [0, rate)");
-        }
-    }
+    { const int rc = check_params(prm, ds_start, h->n, [&](int64_t g) { return h->glen[g]; }); if (rc != DN_OK) return rc; }
     for (int i = 0; i < h->p; i++) if (!(scale[i] > 0.0) || !std::isfinite(scale[i])) return fail(DN_E_INVALID, "scale factors must be positive and finite");
     DN_TRY(hipSetDevice(h->device));
-
-    {
+    return synced_classes(h, [&]() -> int {
         // the scratch slots were sized at upload (for the announced take-every rate in the one-wave-per-gene family):
         // grow them if this iteration's rate leaves more active columns than they hold
         const int32_t rate = prm->downsample_rate;
@@ -1021,97 +1067,97 @@ int dn_baseline_iteration(dn_handle h, const double *scale, const dn_params *prm
                 if (rc != DN_OK) return rc;
             }
         }
-    }
-    if (prm->want_estimates && !h->data.d_svec)
-        DN_TRY(h->data.d_svec.alloc(sizeof(double) * (size_t) std::max<int64_t>(h->svoff[h->n], 1)));
+        if (prm->want_estimates && !h->data.d_svec)
+            DN_TRY(h->data.d_svec.alloc(sizeof(double) * (size_t) std::max<int64_t>(h->svoff[h->n], 1)));
 
-    dn::IterArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.cov = h->data.d_cov; a.goff = h->data.d_goff; a.glen = h->data.d_glen; a.order = h->data.d_order; a.counter = h->data.d_counter;
-    a.ds_start = nullptr;
-    a.ws = h->data.cls[0].d_ws; a.rho = h->data.d_rho; a.flags = h->data.d_flags; a.trace = h->data.d_trace; a.kfin = h->data.d_kfin; a.emode = h->data.d_emode;
-    a.svec = h->data.d_svec; a.svoff = h->data.d_svoff; a.slot_bytes = h->data.cls[0].slot_bytes; a.n_genes = (int32_t) h->n; a.S = h->data.cls[0].S;
-    a.p = h->p; a.rowmax = h->data.d_rowmax; a.x16 = h->data.d_x16; a.max_steps = h->max_steps;
-    a.T = prm->nmf_iter; a.bins = prm->bins; a.min_hc = prm->min_high_coverage; a.rate = prm->downsample_rate;
-    a.skip = prm->skip_baseline_selection ? 1 : 0; a.want_est = prm->want_estimates ? 1 : 0;
-    for (int i = 0; i < h->p; i++) { a.scale[i] = scale[i]; a.inv_scale[i] = 1.0 / scale[i]; h->last_scale[i] = scale[i]; }
-    for (int i = h->p; i < dn::P_MAX; i++) { a.scale[i] = 1.0; a.inv_scale[i] = 1.0; }
-    if (prm->downsample_rate > 1) {
-        DN_TRY(hipMemcpyAsync(h->data.d_ds, ds_start, sizeof(int64_t) * (size_t) h->n, hipMemcpyHostToDevice, h->stream[0]));
-        a.ds_start = h->data.d_ds;
-    }
-    // The narrow class (state in LDS, little fabric traffic) orders its queue most expensive first from the second
-    // iteration on, the cost of a gene predicted from the previous iteration's counters (sum of active columns over its
-    // nmf() calls plus a fixed part per call worth ~4 columns per lane): its genes are what fills the end of a launch.
-    // The wide class keeps the zigzag (it is bound by the fabric, see upload).
-    for (int wc = 1; wc < dn_handle_s::NCLS; wc++) {
-        auto &C = h->data.cls[wc];
-        if (!h->have_trace || C.n == 0 || !C.ks) continue;
-        const double per_call = 4.0 * (double) (C.ks->nt > 0 ? C.ks->nt : 128);
-        std::vector<std::pair<double, int32_t>> key((size_t) C.n);
-        for (int32_t k = 0; k < C.n; k++) {
-            const int32_t g = C.order[k];
-            const int32_t *tr = &h->data.host_trace[(size_t) g * h->trace_cols];
-            key[k] = {(double) tr[2] + per_call * (double) tr[1] + 1e-3 * (double) h->glen[g], g};
+        dn::IterArgs a;
+        std::memset(&a, 0, sizeof(a));
+        a.cov = h->data.d_cov; a.goff = h->data.d_goff; a.glen = h->data.d_glen; a.order = h->data.d_order; a.counter = h->data.d_counter;
+        a.ds_start = nullptr;
+        a.ws = h->data.cls[0].d_ws; a.rho = h->data.d_rho; a.flags = h->data.d_flags; a.trace = h->data.d_trace; a.kfin = h->data.d_kfin; a.emode = h->data.d_emode;
+        a.svec = h->data.d_svec; a.svoff = h->data.d_svoff; a.slot_bytes = h->data.cls[0].slot_bytes; a.n_genes = (int32_t) h->n; a.S = h->data.cls[0].S;
+        a.p = h->p; a.rowmax = h->data.d_rowmax; a.x16 = h->data.d_x16; a.max_steps = h->max_steps;
+        a.T = prm->nmf_iter; a.bins = prm->bins; a.min_hc = prm->min_high_coverage; a.rate = prm->downsample_rate;
+        a.skip = prm->skip_baseline_selection ? 1 : 0; a.want_est = prm->want_estimates ? 1 : 0;
+        for (int i = 0; i < h->p; i++) { a.scale[i] = scale[i]; a.inv_scale[i] = 1.0 / scale[i]; h->last_scale[i] = scale[i]; }
+        for (int i = h->p; i < dn::P_MAX; i++) { a.scale[i] = 1.0; a.inv_scale[i] = 1.0; }
+        if (prm->downsample_rate > 1) {
+            DN_TRY(hipMemcpyAsync(h->data.d_ds, ds_start, sizeof(int64_t) * (size_t) h->n, hipMemcpyHostToDevice, h->stream[0]));
+            a.ds_start = h->data.d_ds;
         }
-        std::stable_sort(key.begin(), key.end(), [](const std::pair<double, int32_t> &a, const std::pair<double, int32_t> &b) { return a.first > b.first; });
-        for (int32_t k = 0; k < C.n; k++) C.order[k] = key[k].second;
-        DN_TRY(hipMemcpyAsync(C.d_order, C.order.data(), sizeof(int32_t) * (size_t) C.n, hipMemcpyHostToDevice, h->stream[0]));
-    }
-    DN_TRY(hipMemsetAsync(h->data.d_trace, 0, sizeof(int32_t) * (size_t) h->n * dn::TRACE_LEN, h->stream[0]));
-    for (auto &C : h->data.cls) if (C.n > 0) DN_TRY(hipMemsetAsync(C.d_counter, 0, sizeof(int32_t) * 4, h->stream[0]));
-    DN_TRY(hipEventRecord(h->ev_ready, h->stream[0]));
-    int first_cls = -1;
-    for (int c = 0; c < dn_handle_s::NCLS; c++) {
-        auto &C = h->data.cls[c];
-        C.last_ms = 0.f;
-        if (C.n == 0) continue;
-        if (first_cls < 0) first_cls = c;
-        hipStream_t st = h->stream[c];
-        if (c > 0) DN_TRY(hipStreamWaitEvent(st, h->ev_ready, 0));
-        a.order = C.d_order; a.counter = C.d_counter; a.ws = C.d_ws; a.slot_bytes = C.slot_bytes; a.S = C.S;
-        a.lds_cols = C.lds_cols; a.n_genes = C.n;
-        DN_TRY(hipEventRecord(h->ev_start[c], st));
-        const int lrc = C.ks->baseline(a, C.slots, C.dyn_lds, st);
-        if (lrc != 0) return fail(DN_E_HIP, std::string("k_baseline launch: ") + hipGetErrorString((hipError_t) lrc));
-        DN_TRY(hipEventRecord(h->ev_end[c], st));
-    }
-    for (int c = 1; c < dn_handle_s::NCLS; c++)                                   // results are copied on the main stream
-        if (h->data.cls[c].n > 0) DN_TRY(hipStreamWaitEvent(h->stream[0], h->ev_end[c], 0));
-    if (rho) {                          // null: the DI rows stay on the device (dn_outer_partials / dn_outer_apply / dn_fetch_outer)
-        DN_TRY(hipMemcpyAsync(rho, h->data.d_rho, sizeof(double) * (size_t) h->n * h->p, hipMemcpyDeviceToHost, h->stream[0]));
-        DN_TRY(hipMemcpyAsync(flags, h->data.d_flags, sizeof(int32_t) * (size_t) h->n, hipMemcpyDeviceToHost, h->stream[0]));
-    }
-    const int32_t tcols = h->trace_cols;
-    const size_t trace_ints = (size_t) h->n * (size_t) tcols;
-    if (h->data.host_trace_len < trace_ints) {
-        h->data.host_trace_len = 0;
-        DN_TRY(h->data.host_trace.alloc(sizeof(int32_t) * trace_ints));
-        h->data.host_trace_len = trace_ints;
-    }
-    if (tcols == dn::TRACE_LEN)
-        DN_TRY(hipMemcpyAsync(h->data.host_trace, h->data.d_trace, sizeof(int32_t) * trace_ints, hipMemcpyDeviceToHost, h->stream[0]));
-    else {
-        if (!h->data.d_trace_head) DN_TRY(h->data.d_trace_head.alloc(sizeof(int32_t) * (size_t) h->n * dn::TRACE_LEN));
-        hipLaunchKernelGGL(k_trace_head, dim3((unsigned) std::min<size_t>(1024, (trace_ints + 255) / 256)), dim3(256), 0, h->stream[0],
-                           h->data.d_trace, h->data.d_trace_head, (long long) trace_ints, (int) tcols);
-        DN_TRY(hipGetLastError());
-        DN_TRY(hipMemcpyAsync(h->data.host_trace, h->data.d_trace_head, sizeof(int32_t) * trace_ints, hipMemcpyDeviceToHost, h->stream[0]));
-    }
-    DN_TRY(hipStreamSynchronize(h->stream[0]));
-    h->have_trace = (prm->downsample_rate <= 1);          // with down-sampling the active columns are redrawn every iteration
-    if (trace) std::memcpy(trace, h->data.host_trace, sizeof(int32_t) * trace_ints);
-    h->last_span_ms = 0.f;
-    for (int c = 0; c < dn_handle_s::NCLS; c++) {
-        if (h->data.cls[c].n == 0) continue;
-        DN_TRY(hipEventElapsedTime(&h->data.cls[c].last_ms, h->ev_start[c], h->ev_end[c]));
-        float span = 0.f;                                                // the classes are launched in order: the first start opens the span
-        DN_TRY(hipEventElapsedTime(&span, h->ev_start[first_cls], h->ev_end[c]));
-        h->last_span_ms = std::max(h->last_span_ms, span);
-    }
-    h->last_ms = first_cls >= 0 ? h->data.cls[first_cls].last_ms : 0.f;
-    h->data.have_estimate_state = prm->want_estimates != 0;
-    return DN_OK;
+        // The narrow class (state in LDS, little fabric traffic) orders its queue most expensive first from the second
+        // iteration on, the cost of a gene predicted from the previous iteration's counters (sum of active columns over its
+        // nmf() calls plus a fixed part per call worth ~4 columns per lane): its genes are what fills the end of a launch.
+        // The wide class keeps the zigzag (it is bound by the fabric, see upload).
+        for (int wc = 1; wc < dn_handle_s::NCLS; wc++) {
+            auto &C = h->data.cls[wc];
+            if (!h->have_trace || C.n == 0 || !C.ks) continue;
+            const double per_call = 4.0 * (double) (C.ks->nt > 0 ? C.ks->nt : 128);
+            std::vector<std::pair<double, int32_t>> key((size_t) C.n);
+            for (int32_t k = 0; k < C.n; k++) {
+                const int32_t g = C.order[k];
+                const int32_t *tr = &h->data.host_trace[(size_t) g * h->trace_cols];
+                key[k] = {(double) tr[2] + per_call * (double) tr[1] + 1e-3 * (double) h->glen[g], g};
+            }
+            std::stable_sort(key.begin(), key.end(), [](const std::pair<double, int32_t> &a, const std::pair<double, int32_t> &b) { return a.first > b.first; });
+            for (int32_t k = 0; k < C.n; k++) C.order[k] = key[k].second;
+            DN_TRY(hipMemcpyAsync(C.d_order, C.order.data(), sizeof(int32_t) * (size_t) C.n, hipMemcpyHostToDevice, h->stream[0]));
+        }
+        DN_TRY(hipMemsetAsync(h->data.d_trace, 0, sizeof(int32_t) * (size_t) h->n * dn::TRACE_LEN, h->stream[0]));
+        for (auto &C : h->data.cls) if (C.n > 0) DN_TRY(hipMemsetAsync(C.d_counter, 0, sizeof(int32_t) * 4, h->stream[0]));
+        DN_TRY(hipEventRecord(h->ev_ready, h->stream[0]));
+        int first_cls = -1;
+        for (int c = 0; c < dn_handle_s::NCLS; c++) {
+            auto &C = h->data.cls[c];
+            C.last_ms = 0.f;
+            if (C.n == 0) continue;
+            if (first_cls < 0) first_cls = c;
+            hipStream_t st = h->stream[c];
+            if (c > 0) DN_TRY(hipStreamWaitEvent(st, h->ev_ready, 0));
+            a.order = C.d_order; a.counter = C.d_counter; a.ws = C.d_ws; a.slot_bytes = C.slot_bytes; a.S = C.S;
+            a.lds_cols = C.lds_cols; a.n_genes = C.n;
+            DN_TRY(hipEventRecord(h->ev_start[c], st));
+            const int lrc = C.ks->baseline(a, C.slots, C.dyn_lds, st);
+            if (lrc != 0) return fail(DN_E_HIP, std::string("k_baseline launch: ") + hipGetErrorString((hipError_t) lrc));
+            DN_TRY(hipEventRecord(h->ev_end[c], st));
+        }
+        for (int c = 1; c < dn_handle_s::NCLS; c++)                                   // results are copied on the main stream
+            if (h->data.cls[c].n > 0) DN_TRY(hipStreamWaitEvent(h->stream[0], h->ev_end[c], 0));
+        if (rho) {                          // null: the DI rows stay on the device (dn_outer_partials / dn_outer_apply / dn_fetch_outer)
+            DN_TRY(hipMemcpyAsync(rho, h->data.d_rho, sizeof(double) * (size_t) h->n * h->p, hipMemcpyDeviceToHost, h->stream[0]));
+            DN_TRY(hipMemcpyAsync(flags, h->data.d_flags, sizeof(int32_t) * (size_t) h->n, hipMemcpyDeviceToHost, h->stream[0]));
+        }
+        const int32_t tcols = h->trace_cols;
+        const size_t trace_ints = (size_t) h->n * (size_t) tcols;
+        if (h->data.host_trace_len < trace_ints) {
+            h->data.host_trace_len = 0;
+            DN_TRY(h->data.host_trace.alloc(sizeof(int32_t) * trace_ints));
+            h->data.host_trace_len = trace_ints;
+        }
+        if (tcols == dn::TRACE_LEN)
+            DN_TRY(hipMemcpyAsync(h->data.host_trace, h->data.d_trace, sizeof(int32_t) * trace_ints, hipMemcpyDeviceToHost, h->stream[0]));
+        else {
+            if (!h->data.d_trace_head) DN_TRY(h->data.d_trace_head.alloc(sizeof(int32_t) * (size_t) h->n * dn::TRACE_LEN));
+            hipLaunchKernelGGL(k_trace_head, dim3((unsigned) std::min<size_t>(1024, (trace_ints + 255) / 256)), dim3(256), 0, h->stream[0],
+                               h->data.d_trace, h->data.d_trace_head, (long long) trace_ints, (int) tcols);
+            DN_TRY(hipGetLastError());
+            DN_TRY(hipMemcpyAsync(h->data.host_trace, h->data.d_trace_head, sizeof(int32_t) * trace_ints, hipMemcpyDeviceToHost, h->stream[0]));
+        }
+        DN_TRY(hipStreamSynchronize(h->stream[0]));
+        h->have_trace = (prm->downsample_rate <= 1);          // with down-sampling the active columns are redrawn every iteration
+        if (trace) std::memcpy(trace, h->data.host_trace, sizeof(int32_t) * trace_ints);
+        h->last_span_ms = 0.f;
+        for (int c = 0; c < dn_handle_s::NCLS; c++) {
+            if (h->data.cls[c].n == 0) continue;
+            DN_TRY(hipEventElapsedTime(&h->data.cls[c].last_ms, h->ev_start[c], h->ev_end[c]));
+            float span = 0.f;                                                // the classes are launched in order: the first start opens the span
+            DN_TRY(hipEventElapsedTime(&span, h->ev_start[first_cls], h->ev_end[c]));
+            h->last_span_ms = std::max(h->last_span_ms, span);
+        }
+        h->last_ms = first_cls >= 0 ? h->data.cls[first_cls].last_ms : 0.f;
+        h->data.have_estimate_state = prm->want_estimates != 0;
+        return DN_OK;
+    });
 }
 
 static int outer_alloc(dn_handle h, int32_t degnorm_iter)
@@ -1133,108 +1179,119 @@ static int outer_alloc(dn_handle h, int32_t degnorm_iter)
     return DN_OK;
 }
 
+// Queue "block partials + reduce" on the handle's stream: the sums of the initial normalisation (k_init_partials) or of an
+// outer update (k_outer_partials) over the handle's genes, block by block, then added in block order into d_pvec[0 .. 3p + 4)
+static int queue_partials(dn_handle h, bool initial)
+{
+    const int blocks = (int) std::min<int64_t>(OUT_BLOCKS, (h->n + 3) / 4);
+    if (initial)
+        hipLaunchKernelGGL(k_init_partials, dim3(blocks), dim3(256), 0, h->stream[0], h->data.d_est_sums, h->data.d_cov_sums, h->data.d_status, h->data.d_x, h->data.d_part,
+                           (int) h->n, (int) h->p);
+    else
+        hipLaunchKernelGGL(k_outer_partials, dim3(blocks), dim3(256), 0, h->stream[0], h->data.d_rho, h->data.d_rhoc, h->data.d_xw, h->data.d_trace, h->data.d_flags, h->data.d_part,
+                           (int) h->n, (int) h->p);
+    hipLaunchKernelGGL(k_outer_reduce, dim3(1), dim3(256), 0, h->stream[0], h->data.d_part, h->data.d_pvec, blocks, (int) h->p);
+    DN_TRY(hipGetLastError());
+    return DN_OK;
+}
+
 int dn_init_begin(dn_handle h, const double *reads)
 {
     if (!h || !h->data.d_cov) return fail(DN_E_STATE, "dn_init_begin: nothing uploaded");
     if (!reads) return fail(DN_E_INVALID, "dn_init_begin: null argument");
-    DN_TRY(hipSetDevice(h->device));
-    const size_t np = (size_t) h->n * h->p;
-    if (!h->data.d_x) DN_TRY(h->data.d_x.alloc(sizeof(double) * np));
-    DN_TRY(hipMemcpyAsync(h->data.d_x, reads, sizeof(double) * np, hipMemcpyHostToDevice, h->stream[0]));
-    DN_TRY(hipStreamSynchronize(h->stream[0]));
-    return DN_OK;
+    return on_main_stream(h, [&]() -> int {
+        const size_t np = (size_t) h->n * h->p;
+        if (!h->data.d_x) DN_TRY(h->data.d_x.alloc(sizeof(double) * np));
+        DN_TRY(hipMemcpyAsync(h->data.d_x, reads, sizeof(double) * np, hipMemcpyHostToDevice, h->stream[0]));
+        DN_TRY(hipStreamSynchronize(h->stream[0]));
+        return DN_OK;
+    });
 }
 
 int dn_init_partials(dn_handle h, double *partials)
 {
     if (!h || !h->data.d_x) return fail(DN_E_STATE, "dn_init_partials: dn_init_begin has not been called");
     if (!partials) return fail(DN_E_INVALID, "dn_init_partials: null output");
-    DN_TRY(hipSetDevice(h->device));
-    { const int rc = outer_alloc(h, 0); if (rc != DN_OK) return rc; }
-    const int blocks = (int) std::min<int64_t>(OUT_BLOCKS, (h->n + 3) / 4);
-    hipLaunchKernelGGL(k_init_partials, dim3(blocks), dim3(256), 0, h->stream[0], h->data.d_est_sums, h->data.d_cov_sums, h->data.d_status, h->data.d_x, h->data.d_part,
-                       (int) h->n, (int) h->p);
-    hipLaunchKernelGGL(k_outer_reduce, dim3(1), dim3(256), 0, h->stream[0], h->data.d_part, h->data.d_pvec, blocks, (int) h->p);
-    DN_TRY(hipGetLastError());
-    DN_TRY(hipMemcpyAsync(partials, h->data.d_pvec, sizeof(double) * (size_t) (3 * h->p + 4), hipMemcpyDeviceToHost, h->stream[0]));
-    DN_TRY(hipStreamSynchronize(h->stream[0]));
-    return DN_OK;
+    return on_main_stream(h, [&]() -> int {
+        { const int rc = outer_alloc(h, 0); if (rc != DN_OK) return rc; }
+        { const int rc = queue_partials(h, true); if (rc != DN_OK) return rc; }
+        DN_TRY(hipMemcpyAsync(partials, h->data.d_pvec, sizeof(double) * (size_t) (3 * h->p + 4), hipMemcpyDeviceToHost, h->stream[0]));
+        DN_TRY(hipStreamSynchronize(h->stream[0]));
+        return DN_OK;
+    });
 }
 
 int dn_outer_begin_scaled(dn_handle h, const double *norm, int32_t degnorm_iter)
 {
     if (!h || !h->data.d_x) return fail(DN_E_STATE, "dn_outer_begin_scaled: dn_init_begin has not been called");
     if (!norm || degnorm_iter < 1) return fail(DN_E_INVALID, "dn_outer_begin_scaled: bad argument");
-    DN_TRY(hipSetDevice(h->device));
-    { const int rc = outer_alloc(h, degnorm_iter); if (rc != DN_OK) return rc; }
-    const size_t np = (size_t) h->n * h->p;
-    double *d_norm = h->data.d_pvec + (3 * dn::P_MAX + 4) + dn::P_MAX;
-    DN_TRY(hipMemsetAsync(h->data.d_ran, 0, (size_t) h->n * degnorm_iter, h->stream[0]));
-    DN_TRY(hipMemcpyAsync(d_norm, norm, sizeof(double) * (size_t) h->p, hipMemcpyHostToDevice, h->stream[0]));
-    const int blocks = (int) std::min<size_t>(2048, (np + 255) / 256);
-    hipLaunchKernelGGL(k_scale_reads, dim3(blocks), dim3(256), 0, h->stream[0], h->data.d_x, d_norm, h->data.d_xw, (long long) np, (int) h->p);
-    DN_TRY(hipGetLastError());
-    DN_TRY(hipStreamSynchronize(h->stream[0]));
-    return DN_OK;
+    return on_main_stream(h, [&]() -> int {
+        { const int rc = outer_alloc(h, degnorm_iter); if (rc != DN_OK) return rc; }
+        const size_t np = (size_t) h->n * h->p;
+        double *d_norm = h->data.d_pvec + (3 * dn::P_MAX + 4) + dn::P_MAX;
+        DN_TRY(hipMemsetAsync(h->data.d_ran, 0, (size_t) h->n * degnorm_iter, h->stream[0]));
+        DN_TRY(hipMemcpyAsync(d_norm, norm, sizeof(double) * (size_t) h->p, hipMemcpyHostToDevice, h->stream[0]));
+        const int blocks = (int) std::min<size_t>(2048, (np + 255) / 256);
+        hipLaunchKernelGGL(k_scale_reads, dim3(blocks), dim3(256), 0, h->stream[0], h->data.d_x, d_norm, h->data.d_xw, (long long) np, (int) h->p);
+        DN_TRY(hipGetLastError());
+        DN_TRY(hipStreamSynchronize(h->stream[0]));
+        return DN_OK;
+    });
 }
 
 int dn_outer_begin(dn_handle h, const double *x_weighted, int32_t degnorm_iter)
 {
     if (!h || !h->data.d_cov) return fail(DN_E_STATE, "dn_outer_begin: nothing uploaded");
     if (!x_weighted || degnorm_iter < 1) return fail(DN_E_INVALID, "dn_outer_begin: bad argument");
-    DN_TRY(hipSetDevice(h->device));
-    const size_t np = (size_t) h->n * h->p;
-    { const int rc = outer_alloc(h, degnorm_iter); if (rc != DN_OK) return rc; }
-    DN_TRY(hipMemsetAsync(h->data.d_ran, 0, (size_t) h->n * degnorm_iter, h->stream[0]));
-    DN_TRY(hipMemcpyAsync(h->data.d_xw, x_weighted, sizeof(double) * np, hipMemcpyHostToDevice, h->stream[0]));
-    DN_TRY(hipStreamSynchronize(h->stream[0]));
-    return DN_OK;
+    return on_main_stream(h, [&]() -> int {
+        const size_t np = (size_t) h->n * h->p;
+        { const int rc = outer_alloc(h, degnorm_iter); if (rc != DN_OK) return rc; }
+        DN_TRY(hipMemsetAsync(h->data.d_ran, 0, (size_t) h->n * degnorm_iter, h->stream[0]));
+        DN_TRY(hipMemcpyAsync(h->data.d_xw, x_weighted, sizeof(double) * np, hipMemcpyHostToDevice, h->stream[0]));
+        DN_TRY(hipStreamSynchronize(h->stream[0]));
+        return DN_OK;
+    });
 }
 
 int dn_outer_partials(dn_handle h, double *partials)
 {
     if (!h || !h->data.d_xw) return fail(DN_E_STATE, "dn_outer_partials: dn_outer_begin has not been called");
     if (!partials) return fail(DN_E_INVALID, "dn_outer_partials: null output");
-    DN_TRY(hipSetDevice(h->device));
-    const int blocks = (int) std::min<int64_t>(OUT_BLOCKS, (h->n + 3) / 4);
-    hipLaunchKernelGGL(k_outer_partials, dim3(blocks), dim3(256), 0, h->stream[0], h->data.d_rho, h->data.d_rhoc, h->data.d_xw, h->data.d_trace, h->data.d_flags, h->data.d_part,
-                       (int) h->n, (int) h->p);
-    hipLaunchKernelGGL(k_outer_reduce, dim3(1), dim3(256), 0, h->stream[0], h->data.d_part, h->data.d_pvec, blocks, (int) h->p);
-    DN_TRY(hipGetLastError());
-    DN_TRY(hipMemcpyAsync(partials, h->data.d_pvec, sizeof(double) * (size_t) (3 * h->p + 4), hipMemcpyDeviceToHost, h->stream[0]));
-    DN_TRY(hipStreamSynchronize(h->stream[0]));
-    return DN_OK;
+    return on_main_stream(h, [&]() -> int {
+        { const int rc = queue_partials(h, false); if (rc != DN_OK) return rc; }
+        DN_TRY(hipMemcpyAsync(partials, h->data.d_pvec, sizeof(double) * (size_t) (3 * h->p + 4), hipMemcpyDeviceToHost, h->stream[0]));
+        DN_TRY(hipStreamSynchronize(h->stream[0]));
+        return DN_OK;
+    });
 }
 
 int dn_outer_partials_device(dn_handle h, double **d_partials)
 {
     if (!h || !h->data.d_xw) return fail(DN_E_STATE, "dn_outer_partials_device: dn_outer_begin has not been called");
     if (!d_partials) return fail(DN_E_INVALID, "dn_outer_partials_device: null output");
-    DN_TRY(hipSetDevice(h->device));
-    const int blocks = (int) std::min<int64_t>(OUT_BLOCKS, (h->n + 3) / 4);
-    hipLaunchKernelGGL(k_outer_partials, dim3(blocks), dim3(256), 0, h->stream[0], h->data.d_rho, h->data.d_rhoc, h->data.d_xw, h->data.d_trace, h->data.d_flags, h->data.d_part,
-                       (int) h->n, (int) h->p);
-    hipLaunchKernelGGL(k_outer_reduce, dim3(1), dim3(256), 0, h->stream[0], h->data.d_part, h->data.d_pvec, blocks, (int) h->p);
-    DN_TRY(hipGetLastError());
-    DN_TRY(hipStreamSynchronize(h->stream[0]));           // the collective runs on the caller's stream: the sums must be there
-    *d_partials = h->data.d_pvec;
-    return DN_OK;
+    return on_main_stream(h, [&]() -> int {
+        { const int rc = queue_partials(h, false); if (rc != DN_OK) return rc; }
+        DN_TRY(hipStreamSynchronize(h->stream[0]));           // the collective runs on the caller's stream: the sums must be there
+        *d_partials = h->data.d_pvec;
+        return DN_OK;
+    });
 }
 
 int dn_outer_apply(dn_handle h, const double *avg_di, const double *norm, int32_t iter)
 {
     if (!h || !h->data.d_xw) return fail(DN_E_STATE, "dn_outer_apply: dn_outer_begin has not been called");
     if (!norm || iter < 0) return fail(DN_E_INVALID, "dn_outer_apply: bad argument");
-    DN_TRY(hipSetDevice(h->device));
-    double *d_avg = h->data.d_pvec + (3 * dn::P_MAX + 4), *d_norm = d_avg + dn::P_MAX;
-    if (avg_di) DN_TRY(hipMemcpyAsync(d_avg, avg_di, sizeof(double) * (size_t) h->p, hipMemcpyHostToDevice, h->stream[0]));
-    DN_TRY(hipMemcpyAsync(d_norm, norm, sizeof(double) * (size_t) h->p, hipMemcpyHostToDevice, h->stream[0]));
-    const int blocks = (int) std::min<int64_t>(OUT_BLOCKS, (h->n + 3) / 4);
-    hipLaunchKernelGGL(k_outer_apply, dim3(blocks), dim3(256), 0, h->stream[0], h->data.d_rhoc, h->data.d_xw, h->data.d_xadj, h->data.d_flags, h->data.d_ran, d_avg, d_norm,
-                       avg_di ? 1 : 0, (int) h->n, (int) h->p, (int) iter, (int) h->data.n_iter);
-    DN_TRY(hipGetLastError());
-    DN_TRY(hipStreamSynchronize(h->stream[0]));           // the host buffers behind avg_di / norm may go away
-    return DN_OK;
+    return on_main_stream(h, [&]() -> int {
+        double *d_avg = h->data.d_pvec + (3 * dn::P_MAX + 4), *d_norm = d_avg + dn::P_MAX;
+        if (avg_di) DN_TRY(hipMemcpyAsync(d_avg, avg_di, sizeof(double) * (size_t) h->p, hipMemcpyHostToDevice, h->stream[0]));
+        DN_TRY(hipMemcpyAsync(d_norm, norm, sizeof(double) * (size_t) h->p, hipMemcpyHostToDevice, h->stream[0]));
+        const int blocks = (int) std::min<int64_t>(OUT_BLOCKS, (h->n + 3) / 4);
+        hipLaunchKernelGGL(k_outer_apply, dim3(blocks), dim3(256), 0, h->stream[0], h->data.d_rhoc, h->data.d_xw, h->data.d_xadj, h->data.d_flags, h->data.d_ran, d_avg, d_norm,
+                           avg_di ? 1 : 0, (int) h->n, (int) h->p, (int) iter, (int) h->data.n_iter);
+        DN_TRY(hipGetLastError());
+        DN_TRY(hipStreamSynchronize(h->stream[0]));           // the host buffers behind avg_di / norm may go away
+        return DN_OK;
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1322,9 +1379,10 @@ int dn_comm_allreduce(dn_handle h, double *buf, int32_t count)
 {
     if (!h || !h->comm) return fail(DN_E_STATE, "dn_comm_allreduce: dn_comm_create has not been called");
     if (!buf || count < 1 || count > 256) return fail(DN_E_INVALID, "dn_comm_allreduce: 1 .. 256 doubles");
-    DN_TRY(hipSetDevice(h->device));
-    DN_TRY(hipMemcpyAsync(h->d_comm, buf, sizeof(double) * (size_t) count, hipMemcpyHostToDevice, h->stream[0]));
-    return allreduce_to_host(h, h->d_comm, count, buf);
+    return on_main_stream(h, [&]() -> int {
+        DN_TRY(hipMemcpyAsync(h->d_comm, buf, sizeof(double) * (size_t) count, hipMemcpyHostToDevice, h->stream[0]));
+        return allreduce_to_host(h, h->d_comm, count, buf);
+    });
 }
 
 int dn_init_allreduce(dn_handle h, double *totals)
@@ -1332,14 +1390,11 @@ int dn_init_allreduce(dn_handle h, double *totals)
     if (!h || !h->comm) return fail(DN_E_STATE, "dn_init_allreduce: dn_comm_create has not been called");
     if (!h->data.d_x) return fail(DN_E_STATE, "dn_init_allreduce: dn_init_begin has not been called");
     if (!totals) return fail(DN_E_INVALID, "dn_init_allreduce: null output");
-    DN_TRY(hipSetDevice(h->device));
-    { const int rc = outer_alloc(h, 0); if (rc != DN_OK) return rc; }
-    const int blocks = (int) std::min<int64_t>(OUT_BLOCKS, (h->n + 3) / 4);
-    hipLaunchKernelGGL(k_init_partials, dim3(blocks), dim3(256), 0, h->stream[0], h->data.d_est_sums, h->data.d_cov_sums, h->data.d_status, h->data.d_x, h->data.d_part,
-                       (int) h->n, (int) h->p);
-    hipLaunchKernelGGL(k_outer_reduce, dim3(1), dim3(256), 0, h->stream[0], h->data.d_part, h->data.d_pvec, blocks, (int) h->p);
-    DN_TRY(hipGetLastError());
-    return allreduce_to_host(h, h->data.d_pvec, 3 * h->p + 4, totals);
+    return on_main_stream(h, [&]() -> int {
+        { const int rc = outer_alloc(h, 0); if (rc != DN_OK) return rc; }
+        { const int rc = queue_partials(h, true); if (rc != DN_OK) return rc; }
+        return allreduce_to_host(h, h->data.d_pvec, 3 * h->p + 4, totals);
+    });
 }
 
 int dn_outer_allreduce(dn_handle h, double *totals)
@@ -1347,26 +1402,24 @@ int dn_outer_allreduce(dn_handle h, double *totals)
     if (!h || !h->comm) return fail(DN_E_STATE, "dn_outer_allreduce: dn_comm_create has not been called");
     if (!h->data.d_xw) return fail(DN_E_STATE, "dn_outer_allreduce: dn_outer_begin has not been called");
     if (!totals) return fail(DN_E_INVALID, "dn_outer_allreduce: null output");
-    DN_TRY(hipSetDevice(h->device));
-    const int blocks = (int) std::min<int64_t>(OUT_BLOCKS, (h->n + 3) / 4);
-    hipLaunchKernelGGL(k_outer_partials, dim3(blocks), dim3(256), 0, h->stream[0], h->data.d_rho, h->data.d_rhoc, h->data.d_xw, h->data.d_trace, h->data.d_flags, h->data.d_part,
-                       (int) h->n, (int) h->p);
-    hipLaunchKernelGGL(k_outer_reduce, dim3(1), dim3(256), 0, h->stream[0], h->data.d_part, h->data.d_pvec, blocks, (int) h->p);
-    DN_TRY(hipGetLastError());
-    return allreduce_to_host(h, h->data.d_pvec, 3 * h->p + 4, totals);
+    return on_main_stream(h, [&]() -> int {
+        { const int rc = queue_partials(h, false); if (rc != DN_OK) return rc; }
+        return allreduce_to_host(h, h->data.d_pvec, 3 * h->p + 4, totals);
+    });
 }
 
 int dn_fetch_outer(dn_handle h, double *rho, double *x_adj, double *x_weighted, uint8_t *ran)
 {
     if (!h || !h->data.d_xw) return fail(DN_E_STATE, "dn_fetch_outer: dn_outer_begin has not been called");
-    DN_TRY(hipSetDevice(h->device));
-    const size_t np = (size_t) h->n * h->p;
-    if (rho) DN_TRY(hipMemcpyAsync(rho, h->data.d_rhoc, sizeof(double) * np, hipMemcpyDeviceToHost, h->stream[0]));
-    if (x_adj) DN_TRY(hipMemcpyAsync(x_adj, h->data.d_xadj, sizeof(double) * np, hipMemcpyDeviceToHost, h->stream[0]));
-    if (x_weighted) DN_TRY(hipMemcpyAsync(x_weighted, h->data.d_xw, sizeof(double) * np, hipMemcpyDeviceToHost, h->stream[0]));
-    if (ran) DN_TRY(hipMemcpyAsync(ran, h->data.d_ran, (size_t) h->n * h->data.n_iter, hipMemcpyDeviceToHost, h->stream[0]));
-    DN_TRY(hipStreamSynchronize(h->stream[0]));
-    return DN_OK;
+    return on_main_stream(h, [&]() -> int {
+        const size_t np = (size_t) h->n * h->p;
+        if (rho) DN_TRY(hipMemcpyAsync(rho, h->data.d_rhoc, sizeof(double) * np, hipMemcpyDeviceToHost, h->stream[0]));
+        if (x_adj) DN_TRY(hipMemcpyAsync(x_adj, h->data.d_xadj, sizeof(double) * np, hipMemcpyDeviceToHost, h->stream[0]));
+        if (x_weighted) DN_TRY(hipMemcpyAsync(x_weighted, h->data.d_xw, sizeof(double) * np, hipMemcpyDeviceToHost, h->stream[0]));
+        if (ran) DN_TRY(hipMemcpyAsync(ran, h->data.d_ran, (size_t) h->n * h->data.n_iter, hipMemcpyDeviceToHost, h->stream[0]));
+        DN_TRY(hipStreamSynchronize(h->stream[0]));
+        return DN_OK;
+    });
 }
 
 int dn_fetch_rows(dn_handle h, int64_t n_rows, const int64_t *rows, double *rho_raw, int32_t *flags)
@@ -1374,22 +1427,23 @@ int dn_fetch_rows(dn_handle h, int64_t n_rows, const int64_t *rows, double *rho_
     if (!h || !h->data.d_cov) return fail(DN_E_STATE, "dn_fetch_rows: nothing uploaded");
     if (n_rows <= 0 || !rows || !rho_raw || !flags) return fail(DN_E_INVALID, "dn_fetch_rows: bad argument");
     for (int64_t k = 0; k < n_rows; k++) if (rows[k] < 0 || rows[k] >= h->n) return fail(DN_E_INVALID, "dn_fetch_rows: row out of range");
-    DN_TRY(hipSetDevice(h->device));
     const char *what = "dn_fetch_rows";
     dn::DeviceBuffer<int64_t> d_rows;
     dn::DeviceBuffer<double> d_out;
     dn::DeviceBuffer<int32_t> d_fl;
-    DN_TRY(d_rows.alloc(sizeof(int64_t) * (size_t) n_rows));
-    DN_TRY_AS(what, d_out.alloc(sizeof(double) * (size_t) n_rows * h->p));
-    DN_TRY_AS(what, d_fl.alloc(sizeof(int32_t) * (size_t) n_rows));
-    DN_TRY_AS(what, hipMemcpyAsync(d_rows, rows, sizeof(int64_t) * (size_t) n_rows, hipMemcpyHostToDevice, h->stream[0]));
-    const int tot = (int) (n_rows * h->p);
-    hipLaunchKernelGGL(k_gather_rows, dim3((tot + 255) / 256), dim3(256), 0, h->stream[0], h->data.d_rho, h->data.d_flags, d_rows, d_out, d_fl, (int) n_rows, (int) h->p);
-    DN_TRY_AS(what, hipGetLastError());
-    DN_TRY_AS(what, hipMemcpyAsync(rho_raw, d_out, sizeof(double) * (size_t) n_rows * h->p, hipMemcpyDeviceToHost, h->stream[0]));
-    DN_TRY_AS(what, hipMemcpyAsync(flags, d_fl, sizeof(int32_t) * (size_t) n_rows, hipMemcpyDeviceToHost, h->stream[0]));
-    DN_TRY_AS(what, hipStreamSynchronize(h->stream[0]));
-    return DN_OK;
+    return on_main_stream(h, [&]() -> int {
+        DN_TRY(d_rows.alloc(sizeof(int64_t) * (size_t) n_rows));
+        DN_TRY_AS(what, d_out.alloc(sizeof(double) * (size_t) n_rows * h->p));
+        DN_TRY_AS(what, d_fl.alloc(sizeof(int32_t) * (size_t) n_rows));
+        DN_TRY_AS(what, hipMemcpyAsync(d_rows, rows, sizeof(int64_t) * (size_t) n_rows, hipMemcpyHostToDevice, h->stream[0]));
+        const int tot = (int) (n_rows * h->p);
+        hipLaunchKernelGGL(k_gather_rows, dim3((tot + 255) / 256), dim3(256), 0, h->stream[0], h->data.d_rho, h->data.d_flags, d_rows, d_out, d_fl, (int) n_rows, (int) h->p);
+        DN_TRY_AS(what, hipGetLastError());
+        DN_TRY_AS(what, hipMemcpyAsync(rho_raw, d_out, sizeof(double) * (size_t) n_rows * h->p, hipMemcpyDeviceToHost, h->stream[0]));
+        DN_TRY_AS(what, hipMemcpyAsync(flags, d_fl, sizeof(int32_t) * (size_t) n_rows, hipMemcpyDeviceToHost, h->stream[0]));
+        DN_TRY_AS(what, hipStreamSynchronize(h->stream[0]));
+        return DN_OK;
+    });
 }
 
 // First touch of a large, freshly allocated host buffer from several threads at once (one write per 4 KiB page; the caller
@@ -1410,24 +1464,32 @@ static void prefault_pages(void *ptr, size_t bytes, int n_threads)
     for (auto &t : th) t.join();
 }
 
+// the arguments of the estimates kernel after an iteration with want_estimates: gene g goes to out + ooff[g], or, ooff
+// null, to where its coverage lies in the packed layout
+static dn::EstArgs est_args(dn_handle h, double *out, const int64_t *ooff)
+{
+    dn::EstArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.cov = h->data.d_cov; a.goff = h->data.d_goff; a.glen = h->data.d_glen; a.kfin = h->data.d_kfin; a.emode = h->data.d_emode;
+    a.svec = h->data.d_svec; a.svoff = h->data.d_svoff; a.out = out; a.ooff = ooff; a.n_genes = (int32_t) h->n; a.p = h->p;
+    for (int i = 0; i < dn::P_MAX; i++) a.scale[i] = i < h->p ? h->last_scale[i] : 1.0;
+    return a;
+}
+
 int dn_fetch_estimates(dn_handle h, double *out)
 {
     if (!h || !h->data.d_cov) return fail(DN_E_STATE, "dn_fetch_estimates: nothing uploaded");
     if (!h->data.have_estimate_state) return fail(DN_E_STATE, "dn_fetch_estimates: last iteration did not run with want_estimates = 1");
     if (!out) return fail(DN_E_INVALID, "dn_fetch_estimates: null output");
-    DN_TRY(hipSetDevice(h->device));
-    if (!h->data.d_est) DN_TRY(h->data.d_est.alloc(sizeof(double) * (size_t) h->total));
-    dn::EstArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.cov = h->data.d_cov; a.goff = h->data.d_goff; a.glen = h->data.d_glen; a.kfin = h->data.d_kfin; a.emode = h->data.d_emode;
-    a.svec = h->data.d_svec; a.svoff = h->data.d_svoff; a.out = h->data.d_est; a.n_genes = (int32_t) h->n; a.p = h->p;
-    for (int i = 0; i < dn::P_MAX; i++) a.scale[i] = i < h->p ? h->last_scale[i] : 1.0;
-    h->ks->est(a, h->data.d_tile_gene, h->data.d_tile_col, (int) h->n_tiles, h->stream[0]);
-    DN_TRY(hipGetLastError());
-    prefault_pages(out, sizeof(double) * (size_t) h->total, (int) std::thread::hardware_concurrency());     // while the kernel runs
-    DN_TRY(hipMemcpyAsync(out, h->data.d_est, sizeof(double) * (size_t) h->total, hipMemcpyDeviceToHost, h->stream[0]));
-    DN_TRY(hipStreamSynchronize(h->stream[0]));
-    return DN_OK;
+    return on_main_stream(h, [&]() -> int {
+        if (!h->data.d_est) DN_TRY(h->data.d_est.alloc(sizeof(double) * (size_t) h->total));
+        h->ks->est(est_args(h, h->data.d_est, nullptr), h->data.d_tile_gene, h->data.d_tile_col, (int) h->n_tiles, h->stream[0]);
+        DN_TRY(hipGetLastError());
+        prefault_pages(out, sizeof(double) * (size_t) h->total, (int) std::thread::hardware_concurrency());     // while the kernel runs
+        DN_TRY(hipMemcpyAsync(out, h->data.d_est, sizeof(double) * (size_t) h->total, hipMemcpyDeviceToHost, h->stream[0]));
+        DN_TRY(hipStreamSynchronize(h->stream[0]));
+        return DN_OK;
+    });
 }
 
 int dn_fetch_estimates_subset(dn_handle h, int64_t n_sel, const int64_t *gene_ids, double *out)
@@ -1435,230 +1497,187 @@ int dn_fetch_estimates_subset(dn_handle h, int64_t n_sel, const int64_t *gene_id
     if (!h || !h->data.d_cov) return fail(DN_E_STATE, "dn_fetch_estimates_subset: nothing uploaded");
     if (!h->data.have_estimate_state) return fail(DN_E_STATE, "dn_fetch_estimates_subset: last iteration did not run with want_estimates = 1");
     if (n_sel <= 0 || !gene_ids || !out) return fail(DN_E_INVALID, "dn_fetch_estimates_subset: bad argument");
-    DN_TRY(hipSetDevice(h->device));
     std::vector<int64_t> ooff(h->n, -1);
     std::vector<int32_t> tg, tc;
-    int64_t total = 0;
-    for (int64_t k = 0; k < n_sel; k++) {
-        const int64_t g = gene_ids[k];
-        if (g < 0 || g >= h->n) return fail(DN_E_INVALID, "dn_fetch_estimates_subset: gene id out of range");
-        if (ooff[g] >= 0) return fail(DN_E_INVALID, "dn_fetch_estimates_subset: duplicate gene id");
-        ooff[g] = total;
-        total += (int64_t) h->p * h->glen[g];
-        for (int32_t c = 0; c < h->glen[g]; c += 256) { tg.push_back((int32_t) g); tc.push_back(c); }
-    }
     const char *what = "dn_fetch_estimates_subset";
     dn::DeviceBuffer<double> d_out;
     dn::DeviceBuffer<int64_t> d_ooff;
     dn::DeviceBuffer<int32_t> d_tg, d_tc;
-    DN_TRY_AS(what, d_out.alloc(sizeof(double) * (size_t) total));
-    DN_TRY_AS(what, d_ooff.alloc(sizeof(int64_t) * (size_t) h->n));
-    DN_TRY_AS(what, d_tg.alloc(sizeof(int32_t) * tg.size()));
-    DN_TRY_AS(what, d_tc.alloc(sizeof(int32_t) * tc.size()));
-    DN_TRY_AS(what, hipMemcpyAsync(d_ooff, ooff.data(), sizeof(int64_t) * (size_t) h->n, hipMemcpyHostToDevice, h->stream[0]));
-    DN_TRY_AS(what, hipMemcpyAsync(d_tg, tg.data(), sizeof(int32_t) * tg.size(), hipMemcpyHostToDevice, h->stream[0]));
-    DN_TRY_AS(what, hipMemcpyAsync(d_tc, tc.data(), sizeof(int32_t) * tc.size(), hipMemcpyHostToDevice, h->stream[0]));
-    dn::EstArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.cov = h->data.d_cov; a.goff = h->data.d_goff; a.glen = h->data.d_glen; a.kfin = h->data.d_kfin; a.emode = h->data.d_emode;
-    a.svec = h->data.d_svec; a.svoff = h->data.d_svoff; a.out = d_out; a.ooff = d_ooff; a.n_genes = (int32_t) h->n; a.p = h->p;
-    for (int i = 0; i < dn::P_MAX; i++) a.scale[i] = i < h->p ? h->last_scale[i] : 1.0;
-    h->ks->est(a, d_tg, d_tc, (int) tg.size(), h->stream[0]);
-    DN_TRY_AS(what, hipGetLastError());
-    DN_TRY_AS(what, hipMemcpyAsync(out, d_out, sizeof(double) * (size_t) total, hipMemcpyDeviceToHost, h->stream[0]));
-    DN_TRY_AS(what, hipStreamSynchronize(h->stream[0]));
-    return DN_OK;
+    return on_main_stream(h, [&]() -> int {
+        int64_t total = 0;
+        for (int64_t k = 0; k < n_sel; k++) {
+            const int64_t g = gene_ids[k];
+            if (g < 0 || g >= h->n) return fail(DN_E_INVALID, "dn_fetch_estimates_subset: gene id out of range");
+            if (ooff[g] >= 0) return fail(DN_E_INVALID, "dn_fetch_estimates_subset: duplicate gene id");
+            ooff[g] = total;
+            total += (int64_t) h->p * h->glen[g];
+            add_tiles(tg, tc, g, h->glen[g]);
+        }
+        DN_TRY_AS(what, d_out.alloc(sizeof(double) * (size_t) total));
+        DN_TRY_AS(what, d_ooff.alloc(sizeof(int64_t) * (size_t) h->n));
+        DN_TRY_AS(what, d_tg.alloc(sizeof(int32_t) * tg.size()));
+        DN_TRY_AS(what, d_tc.alloc(sizeof(int32_t) * tc.size()));
+        DN_TRY_AS(what, hipMemcpyAsync(d_ooff, ooff.data(), sizeof(int64_t) * (size_t) h->n, hipMemcpyHostToDevice, h->stream[0]));
+        DN_TRY_AS(what, hipMemcpyAsync(d_tg, tg.data(), sizeof(int32_t) * tg.size(), hipMemcpyHostToDevice, h->stream[0]));
+        DN_TRY_AS(what, hipMemcpyAsync(d_tc, tc.data(), sizeof(int32_t) * tc.size(), hipMemcpyHostToDevice, h->stream[0]));
+        h->ks->est(est_args(h, d_out, d_ooff), d_tg, d_tc, (int) tg.size(), h->stream[0]);
+        DN_TRY_AS(what, hipGetLastError());
+        DN_TRY_AS(what, hipMemcpyAsync(out, d_out, sizeof(double) * (size_t) total, hipMemcpyDeviceToHost, h->stream[0]));
+        DN_TRY_AS(what, hipStreamSynchronize(h->stream[0]));
+        return DN_OK;
+    });
 }
-
 
 int dn_nmf_f64(dn_handle h, int64_t n, int32_t p, const double *const *x, const int64_t *lengths, int32_t mode,
                int32_t nmf_iter, double *K, double *E, double *est, int32_t *status)
 {
-    const int rc = check_f64_batch(h, n, p, x, lengths, "dn_nmf_f64");
-    if (rc != DN_OK) return rc;
+    { const int rc = check_f64_batch(h, n, p, x, lengths, "dn_nmf_f64"); if (rc != DN_OK) return rc; }
     if (!K || !E || !status) return fail(DN_E_INVALID, "dn_nmf_f64: null output");
     if (mode != DN_NMF_RANK_ONE && mode != DN_NMF && mode != DN_NMF_RATIO) return fail(DN_E_INVALID, "dn_nmf_f64: unknown mode");
     if (mode == DN_NMF && nmf_iter < 0) return fail(DN_E_INVALID, "dn_nmf_f64: nmf_iter must be >= 0");
-    DN_TRY(hipSetDevice(h->device));
-    std::vector<int64_t> xoff(n), eoff(n + 1, 0);
-    std::vector<int32_t> ncol(n);
-    int64_t maxn = 0;
-    for (int64_t m = 0; m < n; m++) {
-        ncol[m] = (int32_t) lengths[m];
-        eoff[m + 1] = eoff[m] + lengths[m];
-        xoff[m] = (int64_t) p * eoff[m];
-        maxn = std::max<int64_t>(maxn, lengths[m]);
-    }
-    const int64_t total = (int64_t) p * eoff[n];
-    std::vector<double> packed((size_t) total);
-    for (int64_t m = 0; m < n; m++) std::memcpy(packed.data() + xoff[m], x[m], sizeof(double) * (size_t) p * (size_t) lengths[m]);
-    std::vector<int32_t> order(n);                                    // widest first
-    std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return ncol[a] > ncol[b]; });
-    // slot: x + lambda [p][n], residual profile, s_start, A^T u [n] -- fp64, 256-byte aligned
-    const int64_t slot_bytes = ((int64_t) sizeof(double) * (p + 3) * maxn + 255) & ~(int64_t) 255;
-    const int grid = f64_grid(h, 1, n, slot_bytes);
-    if (grid < 1) return fail(DN_E_INVALID, "dn_nmf_f64: " + g_err);
-
-    dn::NmfArgsF64 a;
-    std::memset(&a, 0, sizeof(a));
+    std::vector<int64_t> xoff, eoff;
+    std::vector<int32_t> ncol, order;                                 // widest first
+    std::vector<double> packed;
     dn::DeviceBuffer<double> d_x, d_K, d_E, d_est;
     dn::DeviceBuffer<int64_t> d_xoff, d_eoff;
     dn::DeviceBuffer<int32_t> d_ncol, d_order, d_counter, d_status;
     dn::DeviceBuffer<char> d_ws;
     dn::Event e0, e1;
-    DN_TRY(alloc_f64(d_x, (size_t) total));
-    DN_TRY(alloc_f64(d_xoff, (size_t) n));
-    DN_TRY(alloc_f64(d_eoff, (size_t) n));
-    DN_TRY(alloc_f64(d_ncol, (size_t) n));
-    DN_TRY(alloc_f64(d_order, (size_t) n));
-    DN_TRY(alloc_f64(d_counter, 4));
-    DN_TRY(alloc_f64(d_status, (size_t) n));
-    DN_TRY(alloc_f64(d_K, (size_t) n * p));
-    DN_TRY(alloc_f64(d_E, (size_t) eoff[n]));
-    if (est) DN_TRY(alloc_f64(d_est, (size_t) total));
-    DN_TRY(alloc_f64(d_ws, (size_t) slot_bytes * (size_t) grid));
-    DN_TRY(e0.create(hipEventCreate));
-    DN_TRY(e1.create(hipEventCreate));
-    DN_TRY(hipMemcpyAsync(d_x, packed.data(), sizeof(double) * (size_t) total, hipMemcpyHostToDevice, h->stream[0]));
-    DN_TRY(hipMemcpyAsync(d_xoff, xoff.data(), sizeof(int64_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
-    DN_TRY(hipMemcpyAsync(d_eoff, eoff.data(), sizeof(int64_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
-    DN_TRY(hipMemcpyAsync(d_ncol, ncol.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
-    DN_TRY(hipMemcpyAsync(d_order, order.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
-    DN_TRY(hipMemsetAsync(d_counter, 0, sizeof(int32_t) * 4, h->stream[0]));
-    a.x = d_x; a.xoff = d_xoff; a.ncol = d_ncol; a.eoff = d_eoff; a.order = d_order; a.counter = d_counter;
-    a.K = d_K; a.E = d_E; a.est = d_est; a.status = d_status; a.ws = d_ws; a.slot_bytes = slot_bytes;
-    a.n = (int32_t) n; a.p = p; a.T = mode == DN_NMF ? nmf_iter : 0; a.ratio = mode == DN_NMF_RATIO ? 1 : 0;
-    a.max_steps = h->max_steps;
-    DN_TRY(hipEventRecord(e0, h->stream[0]));
-    const int lrc = dn::launch_nmf_f64(a, grid, h->stream[0]);
-    if (lrc != 0) return fail(DN_E_HIP, std::string("k_nmf_f64 launch: ") + hipGetErrorString((hipError_t) lrc));
-    DN_TRY(hipEventRecord(e1, h->stream[0]));
-    DN_TRY(hipMemcpyAsync(K, d_K, sizeof(double) * (size_t) n * p, hipMemcpyDeviceToHost, h->stream[0]));
-    DN_TRY(hipMemcpyAsync(E, d_E, sizeof(double) * (size_t) eoff[n], hipMemcpyDeviceToHost, h->stream[0]));
-    DN_TRY(hipMemcpyAsync(status, d_status, sizeof(int32_t) * (size_t) n, hipMemcpyDeviceToHost, h->stream[0]));
-    if (est) DN_TRY(hipMemcpyAsync(est, d_est, sizeof(double) * (size_t) total, hipMemcpyDeviceToHost, h->stream[0]));
-    DN_TRY(hipStreamSynchronize(h->stream[0]));
-    DN_TRY(hipEventElapsedTime(&h->last_f64_ms, e0, e1));
-    return DN_OK;
+    return on_main_stream(h, [&]() -> int {
+        const int64_t maxn = pack_f64(n, p, x, lengths, xoff, eoff, ncol, order, packed), total = xoff[n];
+        // slot: x + lambda [p][n], residual profile, s_start, A^T u [n] -- fp64, 256-byte aligned
+        const int64_t slot_bytes = ((int64_t) sizeof(double) * (p + 3) * maxn + 255) & ~(int64_t) 255;
+        const int grid = f64_grid(h, 1, n, slot_bytes);
+        if (grid < 1) return fail(DN_E_INVALID, "dn_nmf_f64: " + g_err);
+        DN_TRY(alloc_f64(d_x, (size_t) total));
+        DN_TRY(alloc_f64(d_xoff, (size_t) n));
+        DN_TRY(alloc_f64(d_eoff, (size_t) n));
+        DN_TRY(alloc_f64(d_ncol, (size_t) n));
+        DN_TRY(alloc_f64(d_order, (size_t) n));
+        DN_TRY(alloc_f64(d_counter, 4));
+        DN_TRY(alloc_f64(d_status, (size_t) n));
+        DN_TRY(alloc_f64(d_K, (size_t) n * p));
+        DN_TRY(alloc_f64(d_E, (size_t) eoff[n]));
+        if (est) DN_TRY(alloc_f64(d_est, (size_t) total));
+        DN_TRY(alloc_f64(d_ws, (size_t) slot_bytes * (size_t) grid));
+        DN_TRY(e0.create(hipEventCreate));
+        DN_TRY(e1.create(hipEventCreate));
+        DN_TRY(hipMemcpyAsync(d_x, packed.data(), sizeof(double) * (size_t) total, hipMemcpyHostToDevice, h->stream[0]));
+        DN_TRY(hipMemcpyAsync(d_xoff, xoff.data(), sizeof(int64_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
+        DN_TRY(hipMemcpyAsync(d_eoff, eoff.data(), sizeof(int64_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
+        DN_TRY(hipMemcpyAsync(d_ncol, ncol.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
+        DN_TRY(hipMemcpyAsync(d_order, order.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
+        DN_TRY(hipMemsetAsync(d_counter, 0, sizeof(int32_t) * 4, h->stream[0]));
+        dn::NmfArgsF64 a;
+        std::memset(&a, 0, sizeof(a));
+        a.x = d_x; a.xoff = d_xoff; a.ncol = d_ncol; a.eoff = d_eoff; a.order = d_order; a.counter = d_counter;
+        a.K = d_K; a.E = d_E; a.est = d_est; a.status = d_status; a.ws = d_ws; a.slot_bytes = slot_bytes;
+        a.n = (int32_t) n; a.p = p; a.T = mode == DN_NMF ? nmf_iter : 0; a.ratio = mode == DN_NMF_RATIO ? 1 : 0;
+        a.max_steps = h->max_steps;
+        DN_TRY(hipEventRecord(e0, h->stream[0]));
+        const int lrc = dn::launch_nmf_f64(a, grid, h->stream[0]);
+        if (lrc != 0) return fail(DN_E_HIP, std::string("k_nmf_f64 launch: ") + hipGetErrorString((hipError_t) lrc));
+        DN_TRY(hipEventRecord(e1, h->stream[0]));
+        DN_TRY(hipMemcpyAsync(K, d_K, sizeof(double) * (size_t) n * p, hipMemcpyDeviceToHost, h->stream[0]));
+        DN_TRY(hipMemcpyAsync(E, d_E, sizeof(double) * (size_t) eoff[n], hipMemcpyDeviceToHost, h->stream[0]));
+        DN_TRY(hipMemcpyAsync(status, d_status, sizeof(int32_t) * (size_t) n, hipMemcpyDeviceToHost, h->stream[0]));
+        if (est) DN_TRY(hipMemcpyAsync(est, d_est, sizeof(double) * (size_t) total, hipMemcpyDeviceToHost, h->stream[0]));
+        DN_TRY(hipStreamSynchronize(h->stream[0]));
+        DN_TRY(hipEventElapsedTime(&h->last_f64_ms, e0, e1));
+        return DN_OK;
+    });
 }
 
 int dn_baseline_selection_f64(dn_handle h, int64_t n, int32_t p, const double *const *F, const int64_t *lengths,
                               const dn_params *prm, const int64_t *ds_start, double *rho, int32_t *flags,
                               int32_t *trace, double *est)
 {
-    const int rc = check_f64_batch(h, n, p, F, lengths, "dn_baseline_selection_f64");
-    if (rc != DN_OK) return rc;
+    { const int rc = check_f64_batch(h, n, p, F, lengths, "dn_baseline_selection_f64"); if (rc != DN_OK) return rc; }
     if (!prm || !rho || !flags) return fail(DN_E_INVALID, "dn_baseline_selection_f64: null argument");
-    if (prm->nmf_iter < 1) return fail(DN_E_INVALID, "nmf_iter must be >= 1");
-    if (prm->bins < 1 || prm->bins > dn::MAX_BINS) return fail(DN_E_INVALID, "bins must be in [1, 64]");
-    if (prm->min_high_coverage < 2) return fail(DN_E_INVALID, "min_high_coverage must be >= 2 (nmf.py:34)");
-    if (prm->downsample_rate < 1) return fail(DN_E_INVALID, "downsample_rate must be >= 1");
-    if (prm->downsample_rate > 1) {
-        if (!ds_start) return fail(DN_E_INVALID, "downsample_rate > 1 needs per-gene start offsets");
-        for (int64_t g = 0; g < n; g++) {
-            if (lengths[g] <= prm->downsample_rate) return fail(DN_E_INVALID, "downsample_rate is too large; take-every size > at least one gene.");
-            if (ds_start[g] < 0 || ds_start[g] >= prm->downsample_rate) return fail(DN_E_INVALID, "ds_start out of [0, rate)");
-        }
-    }
-    DN_TRY(hipSetDevice(h->device));
-    std::vector<int64_t> goff(n + 1, 0), svoff(n + 1, 0);
-    std::vector<int32_t> glen(n);
-    int64_t maxl = 0;
-    for (int64_t g = 0; g < n; g++) {
-        glen[g] = (int32_t) lengths[g];
-        goff[g + 1] = goff[g] + (int64_t) p * lengths[g];
-        svoff[g + 1] = svoff[g] + lengths[g];
-        maxl = std::max<int64_t>(maxl, lengths[g]);
-    }
-    const int64_t total = goff[n];
-    std::vector<double> packed((size_t) total);
-    for (int64_t g = 0; g < n; g++) std::memcpy(packed.data() + goff[g], F[g], sizeof(double) * (size_t) p * (size_t) lengths[g]);
-    std::vector<int32_t> order(n);                                    // longest first
-    std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return glen[a] > glen[b]; });
-    std::vector<int32_t> tg, tc;                                      // estimate tiles: (gene, first column) per 256 columns
-    if (est)
-        for (int64_t g = 0; g < n; g++)
-            for (int32_t c = 0; c < glen[g]; c += 256) { tg.push_back((int32_t) g); tc.push_back(c); }
-    // slot: Fs, Fb (fp64, p x S) + x + lambda (fp64 [p][S]) + s_start, residual profile, A^T u (fp64 [S])
-    const int32_t S = (int32_t) ((maxl + 63) & ~(int64_t) 63);
-    const int64_t slot_bytes = (int64_t) S * ((int64_t) p * 3 * sizeof(double) + 3 * sizeof(double));
-    const int grid = f64_grid(h, 0, n, slot_bytes);
-    if (grid < 1) return fail(DN_E_INVALID, "dn_baseline_selection_f64: " + g_err);
-
+    { const int rc = check_params(prm, ds_start, n, [&](int64_t g) { return lengths[g]; }); if (rc != DN_OK) return rc; }
+    std::vector<int64_t> goff, svoff;
+    std::vector<int32_t> glen, order, tg, tc;                         // order: longest first
+    std::vector<double> packed;
     dn::DeviceBuffer<double> d_cov, d_rowmax, d_rho, d_kfin, d_svec, d_est;
     dn::DeviceBuffer<int64_t> d_goff, d_ds, d_svoff;
-    dn::DeviceBuffer<int32_t> d_glen, d_order, d_counter, d_flags, d_trace, d_emode;
-    dn::DeviceBuffer<int32_t> d_tg, d_tc;
+    dn::DeviceBuffer<int32_t> d_glen, d_order, d_counter, d_flags, d_trace, d_emode, d_tg, d_tc;
     dn::DeviceBuffer<char> d_ws;
     dn::Event e0, e1;
-    DN_TRY(alloc_f64(d_cov, (size_t) total));
-    DN_TRY(alloc_f64(d_goff, (size_t) n + 1));
-    DN_TRY(alloc_f64(d_glen, (size_t) n));
-    DN_TRY(alloc_f64(d_order, (size_t) n));
-    DN_TRY(alloc_f64(d_counter, 4));
-    DN_TRY(alloc_f64(d_rowmax, (size_t) n * p));
-    DN_TRY(alloc_f64(d_rho, (size_t) n * p));
-    DN_TRY(alloc_f64(d_flags, (size_t) n));
-    DN_TRY(alloc_f64(d_trace, (size_t) n * dn::TRACE_LEN));
-    DN_TRY(alloc_f64(d_kfin, (size_t) n * p));
-    DN_TRY(alloc_f64(d_emode, (size_t) n));
-    DN_TRY(alloc_f64(d_ws, (size_t) slot_bytes * (size_t) grid));
-    if (prm->downsample_rate > 1) DN_TRY(alloc_f64(d_ds, (size_t) n));
-    if (est) {
-        DN_TRY(alloc_f64(d_svoff, (size_t) n + 1));
-        DN_TRY(alloc_f64(d_svec, (size_t) svoff[n]));
-        DN_TRY(alloc_f64(d_est, (size_t) total));
-        DN_TRY(alloc_f64(d_tg, tg.size()));
-        DN_TRY(alloc_f64(d_tc, tc.size()));
-    }
-    DN_TRY(e0.create(hipEventCreate));
-    DN_TRY(e1.create(hipEventCreate));
-    DN_TRY(hipMemcpyAsync(d_cov, packed.data(), sizeof(double) * (size_t) total, hipMemcpyHostToDevice, h->stream[0]));
-    DN_TRY(hipMemcpyAsync(d_goff, goff.data(), sizeof(int64_t) * (size_t) (n + 1), hipMemcpyHostToDevice, h->stream[0]));
-    DN_TRY(hipMemcpyAsync(d_glen, glen.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
-    DN_TRY(hipMemcpyAsync(d_order, order.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
-    DN_TRY(hipMemsetAsync(d_counter, 0, sizeof(int32_t) * 4, h->stream[0]));
-    DN_TRY(hipMemsetAsync(d_trace, 0, sizeof(int32_t) * (size_t) n * dn::TRACE_LEN, h->stream[0]));
-    if (d_ds) DN_TRY(hipMemcpyAsync(d_ds, ds_start, sizeof(int64_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
-    if (est) {
-        DN_TRY(hipMemcpyAsync(d_svoff, svoff.data(), sizeof(int64_t) * (size_t) (n + 1), hipMemcpyHostToDevice, h->stream[0]));
-        DN_TRY(hipMemcpyAsync(d_tg, tg.data(), sizeof(int32_t) * tg.size(), hipMemcpyHostToDevice, h->stream[0]));
-        DN_TRY(hipMemcpyAsync(d_tc, tc.data(), sizeof(int32_t) * tc.size(), hipMemcpyHostToDevice, h->stream[0]));
-    }
-    DN_TRY(hipEventRecord(e0, h->stream[0]));
-    int lrc = dn::launch_row_max_f64(d_cov, d_goff, d_glen, d_rowmax, (int) n, p,
-                                     (int) std::min<int64_t>(n, (int64_t) h->n_cus * 8), h->stream[0]);
-    if (lrc != 0) return fail(DN_E_HIP, std::string("k_row_max_f64 launch: ") + hipGetErrorString((hipError_t) lrc));
-
-    dn::IterArgsF64 a;
-    std::memset(&a, 0, sizeof(a));
-    a.cov = d_cov; a.goff = d_goff; a.glen = d_glen; a.order = d_order; a.counter = d_counter; a.ds_start = d_ds;
-    a.rowmax = d_rowmax; a.x16 = nullptr; a.ws = d_ws; a.rho = d_rho; a.flags = d_flags; a.trace = d_trace; a.kfin = d_kfin;
-    a.emode = d_emode; a.svec = d_svec; a.svoff = d_svoff; a.slot_bytes = slot_bytes; a.n_genes = (int32_t) n; a.S = S;
-    a.lds_cols = 0; a.T = prm->nmf_iter; a.bins = prm->bins; a.min_hc = prm->min_high_coverage; a.rate = prm->downsample_rate;
-    a.skip = prm->skip_baseline_selection ? 1 : 0; a.want_est = est ? 1 : 0; a.p = p; a.max_steps = h->max_steps;
-    for (int i = 0; i < dn::P_MAX; i++) { a.scale[i] = 1.0; a.inv_scale[i] = 1.0; }      // F as given
-    lrc = dn::launch_baseline_f64(a, grid, h->stream[0]);
-    if (lrc != 0) return fail(DN_E_HIP, std::string("k_baseline_gen (float64) launch: ") + hipGetErrorString((hipError_t) lrc));
-    if (est) {
-        dn::EstArgsF64 e;
-        std::memset(&e, 0, sizeof(e));
-        e.cov = d_cov; e.goff = d_goff; e.glen = d_glen; e.kfin = d_kfin; e.emode = d_emode; e.svec = d_svec; e.svoff = d_svoff;
-        e.out = d_est; e.ooff = nullptr; e.n_genes = (int32_t) n; e.p = p;
-        for (int i = 0; i < dn::P_MAX; i++) e.scale[i] = 1.0;
-        lrc = dn::launch_est_f64(e, d_tg, d_tc, (int) tg.size(), h->stream[0]);
-        if (lrc != 0) return fail(DN_E_HIP, std::string("k_estimates_gen (float64) launch: ") + hipGetErrorString((hipError_t) lrc));
-    }
-    DN_TRY(hipEventRecord(e1, h->stream[0]));
-    DN_TRY(hipMemcpyAsync(rho, d_rho, sizeof(double) * (size_t) n * p, hipMemcpyDeviceToHost, h->stream[0]));
-    DN_TRY(hipMemcpyAsync(flags, d_flags, sizeof(int32_t) * (size_t) n, hipMemcpyDeviceToHost, h->stream[0]));
-    if (trace) DN_TRY(hipMemcpyAsync(trace, d_trace, sizeof(int32_t) * (size_t) n * dn::TRACE_LEN, hipMemcpyDeviceToHost, h->stream[0]));
-    if (est) DN_TRY(hipMemcpyAsync(est, d_est, sizeof(double) * (size_t) total, hipMemcpyDeviceToHost, h->stream[0]));
-    DN_TRY(hipStreamSynchronize(h->stream[0]));
-    DN_TRY(hipEventElapsedTime(&h->last_f64_ms, e0, e1));
-    return DN_OK;
+    return on_main_stream(h, [&]() -> int {
+        const int64_t maxl = pack_f64(n, p, F, lengths, goff, svoff, glen, order, packed), total = goff[n];
+        if (est)
+            for (int64_t g = 0; g < n; g++) add_tiles(tg, tc, g, glen[g]);
+        // slot: Fs, Fb (fp64, p x S) + x + lambda (fp64 [p][S]) + s_start, residual profile, A^T u (fp64 [S])
+        const int32_t S = (int32_t) ((maxl + 63) & ~(int64_t) 63);
+        const int64_t slot_bytes = (int64_t) S * ((int64_t) p * 3 * sizeof(double) + 3 * sizeof(double));
+        const int grid = f64_grid(h, 0, n, slot_bytes);
+        if (grid < 1) return fail(DN_E_INVALID, "dn_baseline_selection_f64: " + g_err);
+        DN_TRY(alloc_f64(d_cov, (size_t) total));
+        DN_TRY(alloc_f64(d_goff, (size_t) n + 1));
+        DN_TRY(alloc_f64(d_glen, (size_t) n));
+        DN_TRY(alloc_f64(d_order, (size_t) n));
+        DN_TRY(alloc_f64(d_counter, 4));
+        DN_TRY(alloc_f64(d_rowmax, (size_t) n * p));
+        DN_TRY(alloc_f64(d_rho, (size_t) n * p));
+        DN_TRY(alloc_f64(d_flags, (size_t) n));
+        DN_TRY(alloc_f64(d_trace, (size_t) n * dn::TRACE_LEN));
+        DN_TRY(alloc_f64(d_kfin, (size_t) n * p));
+        DN_TRY(alloc_f64(d_emode, (size_t) n));
+        DN_TRY(alloc_f64(d_ws, (size_t) slot_bytes * (size_t) grid));
+        if (prm->downsample_rate > 1) DN_TRY(alloc_f64(d_ds, (size_t) n));
+        if (est) {
+            DN_TRY(alloc_f64(d_svoff, (size_t) n + 1));
+            DN_TRY(alloc_f64(d_svec, (size_t) svoff[n]));
+            DN_TRY(alloc_f64(d_est, (size_t) total));
+            DN_TRY(alloc_f64(d_tg, tg.size()));
+            DN_TRY(alloc_f64(d_tc, tc.size()));
+        }
+        DN_TRY(e0.create(hipEventCreate));
+        DN_TRY(e1.create(hipEventCreate));
+        DN_TRY(hipMemcpyAsync(d_cov, packed.data(), sizeof(double) * (size_t) total, hipMemcpyHostToDevice, h->stream[0]));
+        DN_TRY(hipMemcpyAsync(d_goff, goff.data(), sizeof(int64_t) * (size_t) (n + 1), hipMemcpyHostToDevice, h->stream[0]));
+        DN_TRY(hipMemcpyAsync(d_glen, glen.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
+        DN_TRY(hipMemcpyAsync(d_order, order.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
+        DN_TRY(hipMemsetAsync(d_counter, 0, sizeof(int32_t) * 4, h->stream[0]));
+        DN_TRY(hipMemsetAsync(d_trace, 0, sizeof(int32_t) * (size_t) n * dn::TRACE_LEN, h->stream[0]));
+        if (d_ds) DN_TRY(hipMemcpyAsync(d_ds, ds_start, sizeof(int64_t) * (size_t) n, hipMemcpyHostToDevice, h->stream[0]));
+        if (est) {
+            DN_TRY(hipMemcpyAsync(d_svoff, svoff.data(), sizeof(int64_t) * (size_t) (n + 1), hipMemcpyHostToDevice, h->stream[0]));
+            DN_TRY(hipMemcpyAsync(d_tg, tg.data(), sizeof(int32_t) * tg.size(), hipMemcpyHostToDevice, h->stream[0]));
+            DN_TRY(hipMemcpyAsync(d_tc, tc.data(), sizeof(int32_t) * tc.size(), hipMemcpyHostToDevice, h->stream[0]));
+        }
+        DN_TRY(hipEventRecord(e0, h->stream[0]));
+        int lrc = dn::launch_row_max_f64(d_cov, d_goff, d_glen, d_rowmax, (int) n, p,
+                                         (int) std::min<int64_t>(n, (int64_t) h->n_cus * 8), h->stream[0]);
+        if (lrc != 0) return fail(DN_E_HIP, std::string("k_row_max_f64 launch: ") + hipGetErrorString((hipError_t) lrc));
+        dn::IterArgsF64 a;
+        std::memset(&a, 0, sizeof(a));
+        a.cov = d_cov; a.goff = d_goff; a.glen = d_glen; a.order = d_order; a.counter = d_counter; a.ds_start = d_ds;
+        a.rowmax = d_rowmax; a.x16 = nullptr; a.ws = d_ws; a.rho = d_rho; a.flags = d_flags; a.trace = d_trace; a.kfin = d_kfin;
+        a.emode = d_emode; a.svec = d_svec; a.svoff = d_svoff; a.slot_bytes = slot_bytes; a.n_genes = (int32_t) n; a.S = S;
+        a.lds_cols = 0; a.T = prm->nmf_iter; a.bins = prm->bins; a.min_hc = prm->min_high_coverage; a.rate = prm->downsample_rate;
+        a.skip = prm->skip_baseline_selection ? 1 : 0; a.want_est = est ? 1 : 0; a.p = p; a.max_steps = h->max_steps;
+        for (int i = 0; i < dn::P_MAX; i++) { a.scale[i] = 1.0; a.inv_scale[i] = 1.0; }      // F as given
+        lrc = dn::launch_baseline_f64(a, grid, h->stream[0]);
+        if (lrc != 0) return fail(DN_E_HIP, std::string("k_baseline_gen (float64) launch: ") + hipGetErrorString((hipError_t) lrc));
+        if (est) {
+            dn::EstArgsF64 e;
+            std::memset(&e, 0, sizeof(e));
+            e.cov = d_cov; e.goff = d_goff; e.glen = d_glen; e.kfin = d_kfin; e.emode = d_emode; e.svec = d_svec; e.svoff = d_svoff;
+            e.out = d_est; e.ooff = nullptr; e.n_genes = (int32_t) n; e.p = p;
+            for (int i = 0; i < dn::P_MAX; i++) e.scale[i] = 1.0;
+            lrc = dn::launch_est_f64(e, d_tg, d_tc, (int) tg.size(), h->stream[0]);
+            if (lrc != 0) return fail(DN_E_HIP, std::string("k_estimates_gen (float64) launch: ") + hipGetErrorString((hipError_t) lrc));
+        }
+        DN_TRY(hipEventRecord(e1, h->stream[0]));
+        DN_TRY(hipMemcpyAsync(rho, d_rho, sizeof(double) * (size_t) n * p, hipMemcpyDeviceToHost, h->stream[0]));
+        DN_TRY(hipMemcpyAsync(flags, d_flags, sizeof(int32_t) * (size_t) n, hipMemcpyDeviceToHost, h->stream[0]));
+        if (trace) DN_TRY(hipMemcpyAsync(trace, d_trace, sizeof(int32_t) * (size_t) n * dn::TRACE_LEN, hipMemcpyDeviceToHost, h->stream[0]));
+        if (est) DN_TRY(hipMemcpyAsync(est, d_est, sizeof(double) * (size_t) total, hipMemcpyDeviceToHost, h->stream[0]));
+        DN_TRY(hipStreamSynchronize(h->stream[0]));
+        DN_TRY(hipEventElapsedTime(&h->last_f64_ms, e0, e1));
+        return DN_OK;
+    });
 }
 
 double dn_last_f64_ms(dn_handle h) { return h ? (double) h->last_f64_ms : 0.0; }
@@ -1743,6 +1762,23 @@ __global__ __launch_bounds__(256) void k_read8nt(const float4 *__restrict__ src,
     if (acc == 12345.678f) sink[0] = acc;
 }
 
+// Best GB/s over `reps` timed launches (one more, the first, is not counted) of a kernel that moves `bytes` per launch; the
+// launches run on the handle's stream between its class-0 events, one at a time
+template <class Launch> static double best_gbps(dn_handle h, int reps, double bytes, Launch launch)
+{
+    double best = 0.0;
+    for (int r = 0; r < reps + 1; r++) {
+        (void) hipEventRecord(h->ev_start[0], h->stream[0]);
+        launch();
+        (void) hipEventRecord(h->ev_end[0], h->stream[0]);
+        (void) hipStreamSynchronize(h->stream[0]);
+        float ms = 0.f;
+        (void) hipEventElapsedTime(&ms, h->ev_start[0], h->ev_end[0]);
+        if (r > 0 && ms > 0.f) best = std::max(best, bytes / (ms * 1e-3) / 1e9);
+    }
+    return best;
+}
+
 extern "C" double dn_measure_read_gbps(dn_handle h, int64_t bytes, int reps)
 {
     if (!h || bytes < (1 << 20)) return 0.0;
@@ -1751,28 +1787,16 @@ extern "C" double dn_measure_read_gbps(dn_handle h, int64_t bytes, int reps)
     dn::DeviceBuffer<float> sink;
     const size_t n4 = (size_t) bytes / sizeof(float4);
     if (a.alloc(n4 * sizeof(float4)) != hipSuccess || sink.alloc(256) != hipSuccess) return 0.0;
-    (void) hipMemsetAsync(a, 1, n4 * sizeof(float4), h->stream[0]);
     double best = 0.0;
-    for (int mult : {4, 8, 16, 32}) {                      // workgroups per CU: the best grid is the ceiling
-        for (int r = 0; r < reps + 1; r++) {
-            (void) hipEventRecord(h->ev_start[0], h->stream[0]);
-            hipLaunchKernelGGL(k_read4, dim3(h->n_cus * mult), dim3(256), 0, h->stream[0], a, sink, n4);
-            (void) hipEventRecord(h->ev_end[0], h->stream[0]);
-            (void) hipStreamSynchronize(h->stream[0]);
-            float ms = 0.f;
-            (void) hipEventElapsedTime(&ms, h->ev_start[0], h->ev_end[0]);
-            if (r > 0 && ms > 0.f) best = std::max(best, (double) n4 * sizeof(float4) / (ms * 1e-3) / 1e9);
+    (void) dn::synced(h->stream[0], [&]() -> int {
+        (void) hipMemsetAsync(a, 1, n4 * sizeof(float4), h->stream[0]);
+        for (int mult : {4, 8, 16, 32}) {                      // workgroups per CU: the best grid is the ceiling
+            const double b4 = best_gbps(h, reps, (double) n4 * sizeof(float4), [&]() { hipLaunchKernelGGL(k_read4, dim3(h->n_cus * mult), dim3(256), 0, h->stream[0], a, sink, n4); });
+            const double b8 = best_gbps(h, reps, (double) n4 * sizeof(float4), [&]() { hipLaunchKernelGGL(k_read8nt, dim3(h->n_cus * mult), dim3(256), 0, h->stream[0], a, sink, n4); });
+            best = std::max(best, std::max(b4, b8));
         }
-        for (int r = 0; r < reps + 1; r++) {
-            (void) hipEventRecord(h->ev_start[0], h->stream[0]);
-            hipLaunchKernelGGL(k_read8nt, dim3(h->n_cus * mult), dim3(256), 0, h->stream[0], a, sink, n4);
-            (void) hipEventRecord(h->ev_end[0], h->stream[0]);
-            (void) hipStreamSynchronize(h->stream[0]);
-            float ms = 0.f;
-            (void) hipEventElapsedTime(&ms, h->ev_start[0], h->ev_end[0]);
-            if (r > 0 && ms > 0.f) best = std::max(best, (double) n4 * sizeof(float4) / (ms * 1e-3) / 1e9);
-        }
-    }
+        return DN_OK;
+    });
     return best;
 }
 
@@ -1783,16 +1807,11 @@ extern "C" double dn_measure_copy_gbps(dn_handle h, int64_t bytes, int reps)
     dn::DeviceBuffer<float4> a, b;
     const size_t n4 = (size_t) bytes / sizeof(float4);
     if (a.alloc(n4 * sizeof(float4)) != hipSuccess || b.alloc(n4 * sizeof(float4)) != hipSuccess) return 0.0;
-    (void) hipMemsetAsync(a, 1, n4 * sizeof(float4), h->stream[0]);
     double best = 0.0;
-    for (int r = 0; r < reps + 1; r++) {
-        (void) hipEventRecord(h->ev_start[0], h->stream[0]);
-        hipLaunchKernelGGL(k_copy4, dim3(h->n_cus * 8), dim3(256), 0, h->stream[0], a, b, n4);
-        (void) hipEventRecord(h->ev_end[0], h->stream[0]);
-        (void) hipStreamSynchronize(h->stream[0]);
-        float ms = 0.f;
-        (void) hipEventElapsedTime(&ms, h->ev_start[0], h->ev_end[0]);
-        if (r > 0 && ms > 0.f) best = std::max(best, 2.0 * (double) n4 * sizeof(float4) / (ms * 1e-3) / 1e9);
-    }
+    (void) dn::synced(h->stream[0], [&]() -> int {
+        (void) hipMemsetAsync(a, 1, n4 * sizeof(float4), h->stream[0]);
+        best = best_gbps(h, reps, 2.0 * (double) n4 * sizeof(float4), [&]() { hipLaunchKernelGGL(k_copy4, dim3(h->n_cus * 8), dim3(256), 0, h->stream[0], a, b, n4); });
+        return DN_OK;
+    });
     return best;
 }
