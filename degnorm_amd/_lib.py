@@ -55,6 +55,8 @@ def load(build_if_missing=False):
     lib.dn_last_error.restype = c.c_char_p
     lib.dn_device_count.restype = c.c_int
     lib.dn_p_supported.argtypes = [c.c_int]
+    lib.dn_p_max.argtypes = []
+    lib.dn_p_max.restype = c.c_int
     lib.dn_create.argtypes = [c.c_int, P(vp)]
     lib.dn_destroy.argtypes = [vp]
     lib.dn_upload_ragged.argtypes = [vp, i64, i32, P(vp), P(i64), i32, i32, P(i64)]
@@ -205,6 +207,11 @@ def _p(arr, ctype):
 
 def device_count():
     return int(load().dn_device_count())
+
+
+def p_max():
+    """The widest cohort an upload takes (dn_p_max: 256 samples; 65 and more run on the wide-cohort kernel family)."""
+    return int(load().dn_p_max())
 
 
 class Device:

@@ -3,8 +3,9 @@ In-tree build of libdegnorm_amd.so (HIP kernels + C ABI) for gfx950 with hipcc.
 
     python -m degnorm_amd.build [--force]
 
-One translation unit per sample count p (dn_inst.hip -DDN_P=p), the run-time-p family (dn_generic.hip, compiled three
-times: 256- and 64-thread builds on float32 counts, a 256-thread build on float64 input), the coverage-assembly,
+One translation unit per sample count p (dn_inst.hip -DDN_P=p), the run-time-p family (dn_generic.hip, compiled four
+times: 256- and 64-thread builds on float32 counts, a 256-thread build on float64 input, the wide-cohort build for 65 to 256
+samples), the coverage-assembly,
 reads-processing, mate-pairing, BGZF-inflate, BGZF-deflate, record-framing, BAM-index, BAM-sort and GTF-scan units plus the C-ABI unit; objects are compiled
 in parallel and linked into degnorm_amd/libdegnorm_amd.so.  hipcc cross-compiles without a GPU.  The host-side units (HOST_UNITS
 and the C-ABI unit) are rebuilt when include/degnorm_amd.h or any header under csrc/ changes (dn_host.hpp, dn_bam_record.hpp --
@@ -127,6 +128,10 @@ def build_library(force=False, verbose=False):
     objs.append(o_f64)
     if force or _newer(o_f64, [gen] + hdr):
         jobs.append([hipcc] + FLAGS + EXTRA + ['-DDN_GEN_NT=256', '-DDN_GEN_F64=1', '-c', gen, '-o', o_f64])
+    o_wide = os.path.join(OBJ, 'dn_generic_wide.o')      # the same source for wide cohorts, 65 .. 256 samples (namespace gen_wide)
+    objs.append(o_wide)
+    if force or _newer(o_wide, [gen] + hdr):
+        jobs.append([hipcc] + FLAGS + EXTRA + ['-DDN_GEN_NT=256', '-DDN_GEN_WIDE=1', '-c', gen, '-o', o_wide])
     for unit in HOST_UNITS:
         src, o = os.path.join(CSRC, unit + '.hip'), os.path.join(OBJ, unit + '.o')
         objs.append(o)

@@ -94,7 +94,9 @@ const KernelSet *kernel_set_for(int p)
 #define DN_CASE(P) case P: return DN_WIDE_SET(P)();
         DN_FOR_EACH_P(DN_CASE)
 #undef DN_CASE
-        default: return (p > DN_P_MAX_TEMPLATED && p <= P_MAX) ? kernel_set_generic() : nullptr;
+        default: return (p > DN_P_MAX_TEMPLATED && p <= P_MAX) ? kernel_set_generic()
+                      : (p > P_MAX && p <= P_WIDE_MAX)           ? kernel_set_wide()       // wide cohorts: 65 .. 256 samples
+                                                                 : nullptr;
     }
 }
 }  // namespace dn
@@ -304,6 +306,159 @@ __global__ __launch_bounds__(256) void k_outer_apply(double *__restrict__ rho_c,
     }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// The outer update for wide cohorts (65 <= p <= 256): the same kernels with up to four samples per lane -- one wave per gene,
+// sample 64 r + lane in slot r of the lane -- and block partials of stride 3 * 256 + 4.  The waves of a block, the blocks and the
+// eight running sums of the reduction are combined in the same fixed orders as above: nothing depends on timing.  Cohorts of at
+// most 64 samples keep the kernels above (their summation order is part of their results).
+// ---------------------------------------------------------------------------------------------------
+constexpr int OUT_WP = dn::P_WIDE_MAX;             // 256
+constexpr int OUT_WR = OUT_WP / 64;                // samples per lane
+constexpr int OUT_STRIDE_W = 3 * OUT_WP + 4;
+
+__device__ __forceinline__ void outer_store_partials_w(double (&sm)[4][3][OUT_WP], double (&cnt)[4][4], double *__restrict__ part)
+{
+    for (int t = threadIdx.x; t < 3 * OUT_WP; t += 256) {
+        const int k = t / OUT_WP, i = t - k * OUT_WP;
+        part[(size_t) blockIdx.x * OUT_STRIDE_W + t] = ((sm[0][k][i] + sm[1][k][i]) + sm[2][k][i]) + sm[3][k][i];
+    }
+    if (threadIdx.x < 4) {
+        const int k = threadIdx.x;
+        part[(size_t) blockIdx.x * OUT_STRIDE_W + 3 * OUT_WP + k] = ((cnt[0][k] + cnt[1][k]) + cnt[2][k]) + cnt[3][k];
+    }
+}
+
+__global__ __launch_bounds__(256) void k_outer_partials_w(const double *__restrict__ rho_raw, double *__restrict__ rho_c,
+                                                          const double *__restrict__ xw, const int32_t *__restrict__ trace,
+                                                          const int32_t *__restrict__ flags, double *__restrict__ part, int n, int p)
+{
+    __shared__ double sm[4][3][OUT_WP];
+    __shared__ double cnt[4][4];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int nw = gridDim.x * 4;
+    double a[OUT_WR], b[OUT_WR], ws[OUT_WR], nu = 0.0, nf = 0.0, nc = 0.0, nr = 0.0;
+#pragma unroll
+    for (int q = 0; q < OUT_WR; q++) { a[q] = 0.0; b[q] = 0.0; ws[q] = 0.0; }
+    for (int g = blockIdx.x * 4 + w; g < n; g += nw) {
+        double r[OUT_WR], x[OUT_WR], rmax = 0.0;
+#pragma unroll
+        for (int q = 0; q < OUT_WR; q++) {
+            const int i = 64 * q + lane;
+            r[q] = 0.0; x[q] = 0.0;
+            if (i < p) {
+                double v = rho_raw[(size_t) g * p + i];
+                v = v > 0.9 ? 0.9 : v;                                    // nmf.py:398
+                v = v < 0.0 ? 0.0 : v;                                    // nmf.py:399
+                rho_c[(size_t) g * p + i] = v;
+                r[q] = v;
+                x[q] = xw[(size_t) g * p + i];
+            }
+            rmax = r[q] > rmax ? r[q] : rmax;
+        }
+        const bool untouched = wave_max_d(rmax) == 0.0;                   // nmf.py:155
+#pragma unroll
+        for (int q = 0; q < OUT_WR; q++) {
+            a[q] += untouched ? 0.0 : x[q] / (1.0 - r[q]);                // nmf.py:575
+            b[q] += untouched ? x[q] : 0.0;
+            ws[q] += x[q];
+        }
+        if (lane == 0) {
+            const int st = trace[(size_t) g * dn::TRACE_LEN + 6];
+            nu += untouched ? 1.0 : 0.0; nf += st != 0 ? 1.0 : 0.0; nc += st == dn::ST_NO_CONVERGENCE ? 1.0 : 0.0;
+            nr += flags[g] != 0 ? 1.0 : 0.0;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < OUT_WR; q++) { sm[w][0][64 * q + lane] = a[q]; sm[w][1][64 * q + lane] = b[q]; sm[w][2][64 * q + lane] = ws[q]; }
+    if (lane == 0) { cnt[w][0] = nu; cnt[w][1] = nf; cnt[w][2] = nc; cnt[w][3] = nr; }
+    __syncthreads();
+    outer_store_partials_w(sm, cnt, part);
+}
+
+__global__ __launch_bounds__(256) void k_init_partials_w(const double *__restrict__ est, const double *__restrict__ cov,
+                                                         const int32_t *__restrict__ status, const double *__restrict__ x,
+                                                         double *__restrict__ part, int n, int p)
+{
+    __shared__ double sm[4][3][OUT_WP];
+    __shared__ double cnt[4][4];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int nw = gridDim.x * 4;
+    double a[OUT_WR], b[OUT_WR], nl = 0.0, nb = 0.0;
+#pragma unroll
+    for (int q = 0; q < OUT_WR; q++) { a[q] = 0.0; b[q] = 0.0; }
+    for (int g = blockIdx.x * 4 + w; g < n; g += nw) {
+        double xv[OUT_WR], rmax = -INFINITY;
+#pragma unroll
+        for (int q = 0; q < OUT_WR; q++) {
+            const int i = 64 * q + lane;
+            xv[q] = 0.0;
+            if (i < p) {
+                const double r = 1.0 - cov[(size_t) g * p + i] / (est[(size_t) g * p + i] + 1.0);       // nmf.py:526
+                rmax = r > rmax ? r : rmax;
+                xv[q] = x[(size_t) g * p + i];
+            }
+        }
+        const bool low = wave_max_d(rmax) < 0.1;                          // nmf.py:529
+#pragma unroll
+        for (int q = 0; q < OUT_WR; q++) { a[q] += low ? xv[q] : 0.0; b[q] += xv[q]; }
+        if (lane == 0) { nl += low ? 1.0 : 0.0; nb += status[g] != 0 ? 1.0 : 0.0; }
+    }
+#pragma unroll
+    for (int q = 0; q < OUT_WR; q++) { sm[w][0][64 * q + lane] = a[q]; sm[w][1][64 * q + lane] = b[q]; sm[w][2][64 * q + lane] = 0.0; }
+    if (lane == 0) { cnt[w][0] = nl; cnt[w][1] = nb; cnt[w][2] = 0.0; cnt[w][3] = 0.0; }
+    __syncthreads();
+    outer_store_partials_w(sm, cnt, part);
+}
+
+// one thread per entry of the block partials (grid of ceil(OUT_STRIDE_W / 256) blocks): the reduction of k_outer_reduce
+__global__ __launch_bounds__(256) void k_outer_reduce_w(const double *__restrict__ part, double *__restrict__ out, int nblocks, int p)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= OUT_STRIDE_W) return;
+    double a[8] = {0., 0., 0., 0., 0., 0., 0., 0.};
+    int b = 0;
+    for (; b + 8 <= nblocks; b += 8) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) a[k] += part[(size_t) (b + k) * OUT_STRIDE_W + t];
+    }
+    for (int k = 0; b < nblocks; b++, k++) a[k] += part[(size_t) b * OUT_STRIDE_W + t];
+    const double s = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
+    if (t < 3 * OUT_WP) { const int k = t / OUT_WP, i = t - k * OUT_WP; if (i < p) out[k * p + i] = s; }
+    else out[3 * p + (t - 3 * OUT_WP)] = s;
+}
+
+__global__ __launch_bounds__(256) void k_outer_apply_w(double *__restrict__ rho_c, double *__restrict__ xw, double *__restrict__ xadj,
+                                                       const int32_t *__restrict__ flags, uint8_t *__restrict__ ran,
+                                                       const double *__restrict__ avg_di, const double *__restrict__ norm,
+                                                       int have_avg, int n, int p, int iter, int n_iter)
+{
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int nw = gridDim.x * 4;
+    for (int g = blockIdx.x * 4 + w; g < n; g += nw) {
+        double r[OUT_WR], rmax = 0.0;
+#pragma unroll
+        for (int q = 0; q < OUT_WR; q++) {
+            const int i = 64 * q + lane;
+            r[q] = i < p ? rho_c[(size_t) g * p + i] : 0.0;
+            rmax = r[q] > rmax ? r[q] : rmax;
+        }
+        const bool untouched = wave_max_d(rmax) == 0.0;
+#pragma unroll
+        for (int q = 0; q < OUT_WR; q++) {
+            const int i = 64 * q + lane;
+            if (i < p) {
+                double rv = r[q];
+                if (untouched && have_avg) rv = avg_di[i];                // correct_di_scores, nmf.py:157
+                const double x = xw[(size_t) g * p + i];
+                rho_c[(size_t) g * p + i] = rv;
+                xadj[(size_t) g * p + i] = x / (1.0 - rv);                // nmf.py:581
+                xw[(size_t) g * p + i] = x / norm[i];                     // nmf.py:587
+            }
+        }
+        if (lane == 0 && iter < n_iter) ran[(size_t) g * n_iter + iter] = flags[g] != 0;      // nmf.py:403
+    }
+}
+
 __global__ __launch_bounds__(256) void k_gather_rows(const double *__restrict__ rho_raw, const int32_t *__restrict__ flags,
                                                      const int64_t *__restrict__ rows, double *__restrict__ out_rho,
                                                      int32_t *__restrict__ out_flags, int n_rows, int p)
@@ -393,6 +548,7 @@ struct dn_handle_s {
         dn::DeviceBuffer<int32_t> d_x16;      // n: 1 when every count of the gene is a whole number <= 65535 (packable into 16 bits)
         // outer-update state (dn_outer_begin): clipped / corrected DI, x_weighted, x_adj, ran_baseline_selection, partial sums
         dn::DeviceBuffer<double> d_rhoc, d_xw, d_xadj, d_part, d_pvec;
+        dn::DeviceBuffer<double> d_scales;    // wide cohorts: the scale factors and, at P_WIDE_MAX, their reciprocals (the kernels read them through a pointer)
         dn::DeviceBuffer<double> d_x;         // the read counts (n x p), resident for the device-side initial normalisation (dn_init_begin)
         dn::DeviceBuffer<uint8_t> d_ran;
         int32_t n_iter = 0;
@@ -409,7 +565,8 @@ struct dn_handle_s {
     } data;
     int64_t n_tiles = 0;
     int32_t split_len = 0, tiny_len = 0;
-    double last_scale[dn::P_MAX] = {0};
+    double last_scale[dn::P_WIDE_MAX] = {0};     // of the last iteration: est_args reads it for the sets of p <= 64 (the wide set reads d_scales)
+    double scales_host[2 * dn::P_WIDE_MAX] = {0};   // what d_scales is filled from: outlives the queued copy
     float last_ms = 0.f;
     float last_span_ms = 0.f;     // first launch to last end of the class kernels of the most recent dn_baseline_iteration
     float last_init_ms = 0.f;     // device time of the most recent dn_ratio_svd_sums kernel
@@ -419,7 +576,7 @@ struct dn_handle_s {
     // the collective inside the library (dn_comm_*): one RCCL communicator per handle, all-reduces on the handle's stream
     void *comm = nullptr;         // ncclComm_t
     int32_t comm_rank = 0, comm_size = 0;
-    dn::DeviceBuffer<double> d_comm;     // 256 doubles of scratch (ranks without genes, small host vectors)
+    dn::DeviceBuffer<double> d_comm;     // DN_COMM_MAX_DOUBLES of scratch (ranks without genes, small host vectors)
     int32_t ds_hint = 1;          // take-every rate the caller intends to use (dn_set_downsample_hint); 1 = none
     int32_t max_steps = dn::EIG_MAX_STEPS_DEFAULT;   // step cap of one eigen-solve (dn_set_solver_step_cap)
     int32_t trace_cols = dn::TRACE_LEN;   // leading trace columns copied back per iteration (dn_set_trace_columns)
@@ -596,7 +753,8 @@ int dn_device_count(void)
     return n;
 }
 
-int dn_p_supported(int p) { return dn::kernel_set_for(p) != nullptr; }
+int dn_p_supported(int p) { return p <= dn::P_MAX && dn::kernel_set_for(p) != nullptr; }
+int dn_p_max(void) { return dn::P_WIDE_MAX; }
 
 static int create_streams(dn_handle h)
 {
@@ -851,6 +1009,7 @@ static int finish_upload(dn_handle h, const CoverageSource &src)
         DN_TRY(h->data.d_status.alloc(sizeof(int32_t) * (size_t) n));
         DN_TRY(h->data.d_rowmax.alloc(sizeof(float) * (size_t) n * p));
         DN_TRY(h->data.d_x16.alloc(sizeof(int32_t) * (size_t) n));
+        if (h->ks->baseline_ptr) DN_TRY(h->data.d_scales.alloc(sizeof(double) * 2 * dn::P_WIDE_MAX));
         DN_TRY(h->data.d_tile_gene.alloc(sizeof(int32_t) * (size_t) std::max<int64_t>(h->n_tiles, 1)));
         DN_TRY(h->data.d_tile_col.alloc(sizeof(int32_t) * (size_t) std::max<int64_t>(h->n_tiles, 1)));
 
@@ -928,7 +1087,8 @@ static int check_shape(dn_handle h, int64_t n_genes, int32_t p, const int64_t *l
     if (n_genes <= 0 || n_genes > INT32_MAX) return fail(DN_E_INVALID, "n_genes must be in [1, 2^31)");
     if (p < 2) return fail(DN_E_INVALID, "need at least 2 samples (svds(k=1) requires 1 < min(shape), nmf.py:63)");
     const dn::KernelSet *ks = dn::kernel_set_for(p);
-    if (!ks) return fail(DN_E_UNSUPPORTED, "no kernels compiled for p = " + std::to_string(p));
+    if (!ks) return fail(DN_E_UNSUPPORTED, "no kernels compiled for p = " + std::to_string(p) +
+                                           (p > dn::P_WIDE_MAX ? " (the widest cohort is " + std::to_string(dn::P_WIDE_MAX) + " samples, dn_p_max())" : std::string()));
     // validate into locals; the handle is only touched once everything checks out
     std::vector<int64_t> goff((size_t) n_genes + 1, 0);
     std::vector<int32_t> glen((size_t) n_genes, 0);
@@ -942,7 +1102,7 @@ static int check_shape(dn_handle h, int64_t n_genes, int32_t p, const int64_t *l
     // Down-sampled regime announced by the caller: when no gene can keep more than 12 active columns the run-time-p
     // kernels serve it row-wise, one wavefront per gene (dn_generic.hip, nmf_rows) -- faster than the column-parallel
     // templated kernels from p ~ 8 on (p = 16: 76 000 vs 41 000 genes/s per run, p = 32: 5x).
-    const bool rows_regime = h->ds_hint > 1 && p >= 8 && (lmax + h->ds_hint - 1) / h->ds_hint <= 12;
+    const bool rows_regime = h->ds_hint > 1 && p >= 8 && p <= dn::P_MAX && (lmax + h->ds_hint - 1) / h->ds_hint <= 12;
     const char *force = getenv("DN_FORCE_GENERIC");
     if (rows_regime && !(force && force[0] == '2')) ks = dn::kernel_set_rows();      // DN_FORCE_GENERIC=2: keep the 256-thread family
     else if (rows_regime) ks = dn::kernel_set_generic();
@@ -1022,7 +1182,7 @@ int dn_ratio_svd_sums(dn_handle h, double *est_sums, double *cov_sums, int32_t *
         DN_TRY(hipMemsetAsync(h->data.d_counter, 0, sizeof(int32_t) * 4, h->stream[0]));
         // occupancy of the kernel that ks->init() will start: from 17 samples on it is the matrix-core variant (round 2 asked for
         // the power-iteration kernel's figure here and ran k_ratio_svd_mg at ONE workgroup per CU instead of two)
-        const int which_init = h->p >= 17 ? 2 : 1;
+        const int which_init = h->p >= 17 ? 2 : 1;        // (the wide-cohort set has one initial pass and answers for it either way)
         int per_cu = std::max(1, h->ks->blocks_per_cu(which_init));
         int grid = (int) std::min<int64_t>(h->n, (int64_t) per_cu * h->n_cus);
         if (h->ks->p == 0) grid = std::min(grid, h->data.cls[0].slots);          // generic kernels work in the scratch slots
@@ -1038,7 +1198,8 @@ int dn_ratio_svd_sums(dn_handle h, double *est_sums, double *cov_sums, int32_t *
         if (status) DN_TRY(hipMemcpyAsync(status, h->data.d_status, sizeof(int32_t) * (size_t) h->n, hipMemcpyDeviceToHost, h->stream[0]));
         DN_TRY(hipStreamSynchronize(h->stream[0]));
         DN_TRY(hipEventElapsedTime(&h->last_init_ms, h->ev_i0, h->ev_i1));
-        if (h->ks->p >= 2 && h->ks->p <= 16) snprintf(h->init_name, sizeof(h->init_name), "k_ratio_svd<%d,%d>", h->ks->p, h->ks->nt);
+        if (h->ks->init_name) snprintf(h->init_name, sizeof(h->init_name), "%s", h->ks->init_name);
+        else if (h->ks->p >= 2 && h->ks->p <= 16) snprintf(h->init_name, sizeof(h->init_name), "k_ratio_svd<%d,%d>", h->ks->p, h->ks->nt);
         else snprintf(h->init_name, sizeof(h->init_name), h->p >= 17 ? "gen::k_ratio_svd_mg" : "gen::k_ratio_svd_gen");
         return DN_OK;
     });
@@ -1079,8 +1240,14 @@ int dn_baseline_iteration(dn_handle h, const double *scale, const dn_params *prm
         a.p = h->p; a.rowmax = h->data.d_rowmax; a.x16 = h->data.d_x16; a.max_steps = h->max_steps;
         a.T = prm->nmf_iter; a.bins = prm->bins; a.min_hc = prm->min_high_coverage; a.rate = prm->downsample_rate;
         a.skip = prm->skip_baseline_selection ? 1 : 0; a.want_est = prm->want_estimates ? 1 : 0;
-        for (int i = 0; i < h->p; i++) { a.scale[i] = scale[i]; a.inv_scale[i] = 1.0 / scale[i]; h->last_scale[i] = scale[i]; }
-        for (int i = h->p; i < dn::P_MAX; i++) { a.scale[i] = 1.0; a.inv_scale[i] = 1.0; }
+        for (int i = 0; i < h->p; i++) h->last_scale[i] = scale[i];
+        if (h->ks->baseline_ptr) {          // wide cohorts: the factors travel through d_scales, the struct's arrays stay zero
+            for (int i = 0; i < h->p; i++) { h->scales_host[i] = scale[i]; h->scales_host[dn::P_WIDE_MAX + i] = 1.0 / scale[i]; }
+            DN_TRY(hipMemcpyAsync(h->data.d_scales, h->scales_host, sizeof(double) * 2 * dn::P_WIDE_MAX, hipMemcpyHostToDevice, h->stream[0]));
+        } else {
+            for (int i = 0; i < h->p; i++) { a.scale[i] = scale[i]; a.inv_scale[i] = 1.0 / scale[i]; }
+            for (int i = h->p; i < dn::P_MAX; i++) { a.scale[i] = 1.0; a.inv_scale[i] = 1.0; }
+        }
         if (prm->downsample_rate > 1) {
             DN_TRY(hipMemcpyAsync(h->data.d_ds, ds_start, sizeof(int64_t) * (size_t) h->n, hipMemcpyHostToDevice, h->stream[0]));
             a.ds_start = h->data.d_ds;
@@ -1117,7 +1284,7 @@ int dn_baseline_iteration(dn_handle h, const double *scale, const dn_params *prm
             a.order = C.d_order; a.counter = C.d_counter; a.ws = C.d_ws; a.slot_bytes = C.slot_bytes; a.S = C.S;
             a.lds_cols = C.lds_cols; a.n_genes = C.n;
             DN_TRY(hipEventRecord(h->ev_start[c], st));
-            const int lrc = C.ks->baseline(a, C.slots, C.dyn_lds, st);
+            const int lrc = C.ks->baseline_ptr ? C.ks->baseline_ptr(a, h->data.d_scales, C.slots, st) : C.ks->baseline(a, C.slots, C.dyn_lds, st);
             if (lrc != 0) return fail(DN_E_HIP, std::string("k_baseline launch: ") + hipGetErrorString((hipError_t) lrc));
             DN_TRY(hipEventRecord(h->ev_end[c], st));
         }
@@ -1160,6 +1327,9 @@ int dn_baseline_iteration(dn_handle h, const double *scale, const dn_params *prm
     });
 }
 
+// d_pvec: the 3p + 4 sums, then (at PVEC_SUMS) avg_di and norm, P_WIDE_MAX doubles each
+constexpr int PVEC_SUMS = 3 * dn::P_WIDE_MAX + 4;
+
 static int outer_alloc(dn_handle h, int32_t degnorm_iter)
 {
     const size_t np = (size_t) h->n * h->p;
@@ -1169,8 +1339,8 @@ static int outer_alloc(dn_handle h, int32_t degnorm_iter)
         DN_TRY(h->data.d_xadj.alloc(sizeof(double) * np));
     }
     if (!h->data.d_part) {
-        DN_TRY(h->data.d_part.alloc(sizeof(double) * (size_t) OUT_BLOCKS * OUT_STRIDE));
-        DN_TRY(h->data.d_pvec.alloc(sizeof(double) * (3 * dn::P_MAX + 4 + 2 * dn::P_MAX)));
+        DN_TRY(h->data.d_part.alloc(sizeof(double) * (size_t) OUT_BLOCKS * OUT_STRIDE_W));     // sized for the widest cohort
+        DN_TRY(h->data.d_pvec.alloc(sizeof(double) * (PVEC_SUMS + 2 * dn::P_WIDE_MAX)));
     }
     if (degnorm_iter > 0 && h->data.n_iter != degnorm_iter) {
         DN_TRY(h->data.d_ran.alloc((size_t) h->n * degnorm_iter));
@@ -1184,6 +1354,17 @@ static int outer_alloc(dn_handle h, int32_t degnorm_iter)
 static int queue_partials(dn_handle h, bool initial)
 {
     const int blocks = (int) std::min<int64_t>(OUT_BLOCKS, (h->n + 3) / 4);
+    if (h->p > dn::P_MAX) {                 // wide cohorts: up to four samples per lane
+        if (initial)
+            hipLaunchKernelGGL(k_init_partials_w, dim3(blocks), dim3(256), 0, h->stream[0], h->data.d_est_sums, h->data.d_cov_sums, h->data.d_status, h->data.d_x,
+                               h->data.d_part, (int) h->n, (int) h->p);
+        else
+            hipLaunchKernelGGL(k_outer_partials_w, dim3(blocks), dim3(256), 0, h->stream[0], h->data.d_rho, h->data.d_rhoc, h->data.d_xw, h->data.d_trace, h->data.d_flags,
+                               h->data.d_part, (int) h->n, (int) h->p);
+        hipLaunchKernelGGL(k_outer_reduce_w, dim3((OUT_STRIDE_W + 255) / 256), dim3(256), 0, h->stream[0], h->data.d_part, h->data.d_pvec, blocks, (int) h->p);
+        DN_TRY(hipGetLastError());
+        return DN_OK;
+    }
     if (initial)
         hipLaunchKernelGGL(k_init_partials, dim3(blocks), dim3(256), 0, h->stream[0], h->data.d_est_sums, h->data.d_cov_sums, h->data.d_status, h->data.d_x, h->data.d_part,
                            (int) h->n, (int) h->p);
@@ -1228,7 +1409,7 @@ int dn_outer_begin_scaled(dn_handle h, const double *norm, int32_t degnorm_iter)
     return on_main_stream(h, [&]() -> int {
         { const int rc = outer_alloc(h, degnorm_iter); if (rc != DN_OK) return rc; }
         const size_t np = (size_t) h->n * h->p;
-        double *d_norm = h->data.d_pvec + (3 * dn::P_MAX + 4) + dn::P_MAX;
+        double *d_norm = h->data.d_pvec + PVEC_SUMS + dn::P_WIDE_MAX;
         DN_TRY(hipMemsetAsync(h->data.d_ran, 0, (size_t) h->n * degnorm_iter, h->stream[0]));
         DN_TRY(hipMemcpyAsync(d_norm, norm, sizeof(double) * (size_t) h->p, hipMemcpyHostToDevice, h->stream[0]));
         const int blocks = (int) std::min<size_t>(2048, (np + 255) / 256);
@@ -1282,12 +1463,16 @@ int dn_outer_apply(dn_handle h, const double *avg_di, const double *norm, int32_
     if (!h || !h->data.d_xw) return fail(DN_E_STATE, "dn_outer_apply: dn_outer_begin has not been called");
     if (!norm || iter < 0) return fail(DN_E_INVALID, "dn_outer_apply: bad argument");
     return on_main_stream(h, [&]() -> int {
-        double *d_avg = h->data.d_pvec + (3 * dn::P_MAX + 4), *d_norm = d_avg + dn::P_MAX;
+        double *d_avg = h->data.d_pvec + PVEC_SUMS, *d_norm = d_avg + dn::P_WIDE_MAX;
         if (avg_di) DN_TRY(hipMemcpyAsync(d_avg, avg_di, sizeof(double) * (size_t) h->p, hipMemcpyHostToDevice, h->stream[0]));
         DN_TRY(hipMemcpyAsync(d_norm, norm, sizeof(double) * (size_t) h->p, hipMemcpyHostToDevice, h->stream[0]));
         const int blocks = (int) std::min<int64_t>(OUT_BLOCKS, (h->n + 3) / 4);
-        hipLaunchKernelGGL(k_outer_apply, dim3(blocks), dim3(256), 0, h->stream[0], h->data.d_rhoc, h->data.d_xw, h->data.d_xadj, h->data.d_flags, h->data.d_ran, d_avg, d_norm,
-                           avg_di ? 1 : 0, (int) h->n, (int) h->p, (int) iter, (int) h->data.n_iter);
+        if (h->p > dn::P_MAX)
+            hipLaunchKernelGGL(k_outer_apply_w, dim3(blocks), dim3(256), 0, h->stream[0], h->data.d_rhoc, h->data.d_xw, h->data.d_xadj, h->data.d_flags, h->data.d_ran, d_avg, d_norm,
+                               avg_di ? 1 : 0, (int) h->n, (int) h->p, (int) iter, (int) h->data.n_iter);
+        else
+            hipLaunchKernelGGL(k_outer_apply, dim3(blocks), dim3(256), 0, h->stream[0], h->data.d_rhoc, h->data.d_xw, h->data.d_xadj, h->data.d_flags, h->data.d_ran, d_avg, d_norm,
+                               avg_di ? 1 : 0, (int) h->n, (int) h->p, (int) iter, (int) h->data.n_iter);
         DN_TRY(hipGetLastError());
         DN_TRY(hipStreamSynchronize(h->stream[0]));           // the host buffers behind avg_di / norm may go away
         return DN_OK;
@@ -1332,7 +1517,7 @@ int dn_comm_create(dn_handle h, const uint8_t *id, int32_t rank, int32_t size)
     ncclComm_t c = nullptr;
     RCCL_TRY(api, api->CommInitRank(&c, size, u, rank));
     h->comm = c; h->comm_rank = rank; h->comm_size = size;
-    if (!h->d_comm) DN_TRY(h->d_comm.alloc(sizeof(double) * 256));
+    if (!h->d_comm) DN_TRY(h->d_comm.alloc(sizeof(double) * DN_COMM_MAX_DOUBLES));
     return DN_OK;
 }
 
@@ -1378,7 +1563,7 @@ static int allreduce_to_host(dn_handle h, double *d_buf, int32_t count, double *
 int dn_comm_allreduce(dn_handle h, double *buf, int32_t count)
 {
     if (!h || !h->comm) return fail(DN_E_STATE, "dn_comm_allreduce: dn_comm_create has not been called");
-    if (!buf || count < 1 || count > 256) return fail(DN_E_INVALID, "dn_comm_allreduce: 1 .. 256 doubles");
+    if (!buf || count < 1 || count > DN_COMM_MAX_DOUBLES) return fail(DN_E_INVALID, "dn_comm_allreduce: 1 .. " + std::to_string(DN_COMM_MAX_DOUBLES) + " doubles");
     return on_main_stream(h, [&]() -> int {
         DN_TRY(hipMemcpyAsync(h->d_comm, buf, sizeof(double) * (size_t) count, hipMemcpyHostToDevice, h->stream[0]));
         return allreduce_to_host(h, h->d_comm, count, buf);
@@ -1472,8 +1657,15 @@ static dn::EstArgs est_args(dn_handle h, double *out, const int64_t *ooff)
     std::memset(&a, 0, sizeof(a));
     a.cov = h->data.d_cov; a.goff = h->data.d_goff; a.glen = h->data.d_glen; a.kfin = h->data.d_kfin; a.emode = h->data.d_emode;
     a.svec = h->data.d_svec; a.svoff = h->data.d_svoff; a.out = out; a.ooff = ooff; a.n_genes = (int32_t) h->n; a.p = h->p;
-    for (int i = 0; i < dn::P_MAX; i++) a.scale[i] = i < h->p ? h->last_scale[i] : 1.0;
+    if (!h->ks->est_ptr) for (int i = 0; i < dn::P_MAX; i++) a.scale[i] = i < h->p ? h->last_scale[i] : 1.0;
     return a;
+}
+
+// the estimates kernel of the handle's kernel set; the wide-cohort set reads the scale factors of the last iteration from d_scales
+static void launch_estimates(dn_handle h, const dn::EstArgs &a, const int32_t *tg, const int32_t *tc, int n_tiles)
+{
+    if (h->ks->est_ptr) h->ks->est_ptr(a, h->data.d_scales, tg, tc, n_tiles, h->stream[0]);
+    else h->ks->est(a, tg, tc, n_tiles, h->stream[0]);
 }
 
 int dn_fetch_estimates(dn_handle h, double *out)
@@ -1483,7 +1675,7 @@ int dn_fetch_estimates(dn_handle h, double *out)
     if (!out) return fail(DN_E_INVALID, "dn_fetch_estimates: null output");
     return on_main_stream(h, [&]() -> int {
         if (!h->data.d_est) DN_TRY(h->data.d_est.alloc(sizeof(double) * (size_t) h->total));
-        h->ks->est(est_args(h, h->data.d_est, nullptr), h->data.d_tile_gene, h->data.d_tile_col, (int) h->n_tiles, h->stream[0]);
+        launch_estimates(h, est_args(h, h->data.d_est, nullptr), h->data.d_tile_gene, h->data.d_tile_col, (int) h->n_tiles);
         DN_TRY(hipGetLastError());
         prefault_pages(out, sizeof(double) * (size_t) h->total, (int) std::thread::hardware_concurrency());     // while the kernel runs
         DN_TRY(hipMemcpyAsync(out, h->data.d_est, sizeof(double) * (size_t) h->total, hipMemcpyDeviceToHost, h->stream[0]));
@@ -1520,7 +1712,7 @@ int dn_fetch_estimates_subset(dn_handle h, int64_t n_sel, const int64_t *gene_id
         DN_TRY_AS(what, hipMemcpyAsync(d_ooff, ooff.data(), sizeof(int64_t) * (size_t) h->n, hipMemcpyHostToDevice, h->stream[0]));
         DN_TRY_AS(what, hipMemcpyAsync(d_tg, tg.data(), sizeof(int32_t) * tg.size(), hipMemcpyHostToDevice, h->stream[0]));
         DN_TRY_AS(what, hipMemcpyAsync(d_tc, tc.data(), sizeof(int32_t) * tc.size(), hipMemcpyHostToDevice, h->stream[0]));
-        h->ks->est(est_args(h, d_out, d_ooff), d_tg, d_tc, (int) tg.size(), h->stream[0]);
+        launch_estimates(h, est_args(h, d_out, d_ooff), d_tg, d_tc, (int) tg.size());
         DN_TRY_AS(what, hipGetLastError());
         DN_TRY_AS(what, hipMemcpyAsync(out, d_out, sizeof(double) * (size_t) total, hipMemcpyDeviceToHost, h->stream[0]));
         DN_TRY_AS(what, hipStreamSynchronize(h->stream[0]));

@@ -20,12 +20,21 @@
 // dn_baseline_selection_f64.  The coverage element type cov_t becomes double (float in the two builds above), the row maxima
 // come from k_row_max_f64 in float64, and the batched bare-factorisation kernel k_nmf_f64 exists only here.  The initial
 // ratio-SVD pass (InitArgs, raw counts) is not part of it.
+//
+// -DDN_GEN_WIDE=1 (with DN_GEN_NT=256) is a fourth compilation, namespace gen_wide: cohorts of 65 to 256 samples (P_WIDE_MAX, the
+// widest p for which `tid < p` holds at 256 threads).  The per-sample state in LDS is sized for 256, the scale factors arrive through
+// a pointer (WideIterArgs / WideEstArgs), nmf_rows runs with R = ceil(p / 64) samples per lane (wave 0 of the 256-thread workgroup)
+// for the column counts whose instantiation needs no scratch in its body (rows_fit), nmf_gen does the rest, and the initial pass is
+// k_ratio_svd_wide at the end of this file.
 #include <cstdio>
 #ifndef DN_GEN_NT
 #define DN_GEN_NT 256
 #endif
 #ifndef DN_GEN_F64
 #define DN_GEN_F64 0
+#endif
+#ifndef DN_GEN_WIDE
+#define DN_GEN_WIDE 0
 #endif
 #define DN_P 8          // sizes the shared reduction scratch only (Smem<8, NT>)
 #define DN_NT DN_GEN_NT
@@ -36,6 +45,13 @@
 #error "the float64-input build (DN_GEN_F64) is a 256-thread build"
 #endif
 #define DN_GEN_NS gen_f64
+#undef DN_GEN_MINW
+#define DN_GEN_MINW 2
+#elif DN_GEN_WIDE
+#if DN_GEN_NT != 256
+#error "the wide-cohort build (DN_GEN_WIDE) is a 256-thread build"
+#endif
+#define DN_GEN_NS gen_wide
 #undef DN_GEN_MINW
 #define DN_GEN_MINW 2
 #elif DN_GEN_NT == 256
@@ -59,13 +75,21 @@ namespace DN_GEN_NS {
 using cov_t = double;           // coverage as given (float64), the row maxima in float64
 using GenIterArgs = IterArgsF64;
 using GenEstArgs = EstArgsF64;
+#elif DN_GEN_WIDE
+using cov_t = float;
+using GenIterArgs = WideIterArgs;   // scale factors by pointer
+using GenEstArgs = WideEstArgs;
 #else
 using cov_t = float;            // float32 storage of integer counts (dn_upload_ragged)
 using GenIterArgs = IterArgs;
 using GenEstArgs = EstArgs;
 #endif
 
+#if DN_GEN_WIDE
+constexpr int GP = P_WIDE_MAX;  // 256
+#else
 constexpr int GP = P_MAX;       // 64
+#endif
 constexpr int NT = DN_GEN_NT;
 constexpr int TI = 8;           // rows per reduction tile
 
@@ -231,6 +255,7 @@ constexpr int ROWS_ZSLOT = 255;               // last double of g_rows_tot, kept
 // NSM: compiled column count (2 .. 12: the Gram matrix and the solver's work shrink with it)
 // SAFE: the repeat of a call whose result shows samples decoupled from the top block (dn_kernels.hpp, warm_start_unsafe): every solve
 // block by block.  A separate instantiation -- inside the hot one the rare path cost 32 % (17.6 against 13.3 ms per launch on config 4)
+#if !DN_GEN_WIDE
 template <int NSM, bool SAFE = false>
 __device__ __attribute__((noinline)) void nmf_rows(const cov_t *Fb, double *rs, double *sv, double *sj,
                                                    int n, int S, int T, int first_i, int p)
@@ -347,6 +372,176 @@ __device__ __attribute__((noinline)) void nmf_rows(const cov_t *Fb, double *rs, 
     }
     __syncthreads();
 }
+#else
+// The same routine for wide cohorts, a text of its own so that the builds for p <= 64 keep their code instruction for instruction.
+// R: samples per lane (wide cohorts, R = ceil(p / 64) = 2, 3, 4: sample 64 r + lane in slot r).  The lane's Gram products are summed
+// over its R rows before the reduce-scatter; the solver works on the n x n matrix and does not see R.
+template <int NSM, bool SAFE = false, int R = 1>
+__device__ __attribute__((noinline)) void nmf_rows(const cov_t *Fb, double *rs, double *sv, double *sj,
+                                                   int n, int S, int T, int first_i, int p)
+{
+    constexpr int NGS = NSM * (NSM + 1) / 2;  // packed Gram entries: 10, 36, 78
+    const bool first = first_i != 0;
+    // arguments of a non-inlined function arrive in vector registers: as scalars the loop's tests (last iteration, cold solve, step
+    // cap) are scalar branches, not exec masks with a branch around either side
+    T = __builtin_amdgcn_readfirstlane(T);
+    n = __builtin_amdgcn_readfirstlane(n);
+    p = __builtin_amdgcn_readfirstlane(p);
+    if (wave_id() == 0) {
+        const int lane = lane_id();
+        bool live[R];
+        double *tot = g_rows_tot;
+        double f[R][NSM], a[R][NSM], v[NSM];
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            live[r] = 64 * r + lane < p;
+            const double inv_s = live[r] ? g_st.inv[64 * r + lane] : 0.0;
+#pragma unroll
+            for (int j = 0; j < NSM; j++) {
+                const cov_t xv = (live[r] && j < n) ? Fb[(size_t) (64 * r + lane) * S + j] : (cov_t) 0;
+                f[r][j] = (double) xv * inv_s;
+                a[r][j] = f[r][j];                                      // lmbda = 0 (nmf.py:90)
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < NSM; j++) v[j] = 0.0;
+        if (lane == 0) tot[ROWS_ZSLOT] = 0.0;
+        for (int e = lane; e < NGS; e += 64) {
+            bool diag = false;
+#pragma unroll
+            for (int i = 0; i < NSM; i++) diag = diag || (e == i * (i + 1) / 2 + i);
+            g_rows_dsel[e] = diag ? 1.0 : 0.0;
+        }
+        wave_fence();
+        const double c = 1.0 / sqrt((double) T);                        // nmf.py:91
+        Solver<NSM> sol;                                                // carried solver state (iterate, scale, shift)
+        double theta = 0.0;
+        int steps = 0, st = ST_OK;
+        bool noconv = false;
+        const int maxs = __builtin_amdgcn_readfirstlane(g_st.max_steps);
+#pragma clang loop unroll(disable)
+        for (int t = -1; t < T; t++) {                                  // t = -1: SVD of x itself (nmf.py:88)
+            if (__builtin_expect(t >= 0, 1)) {
+#pragma unroll
+                for (int r = 0; r < R; r++) {
+                    double ts = 0.0;
+#pragma unroll
+                    for (int j = 0; j < NSM; j++) ts = fma(a[r][j], v[j], ts);  // u_s sigma
+#pragma unroll
+                    for (int j = 0; j < NSM; j++) {
+                        const double res = fma(ts, v[j], -f[r][j]);     // K E - x                       nmf.py:94
+                        a[r][j] = fmax(fma(-c, res, a[r][j]), f[r][j]); // x + max(lambda - c res, 0)    nmf.py:95-97
+                    }
+                }
+            }
+            double C[NGS];
+#pragma unroll
+            for (int i = 0; i < NSM; i++)
+#pragma unroll
+                for (int j = 0; j <= i; j++) {
+                    double cij = a[0][i] * a[0][j];
+#pragma unroll
+                    for (int r = 1; r < R; r++) cij = fma(a[r][i], a[r][j], cij);     // the lane's R rows
+                    C[i * (i + 1) / 2 + j] = cij;
+                }
+            // ceil(NGS / 64) reduce-scatter rounds; the lane that ends up with a diagonal entry subtracts the call's shift as it stores
+            // it (round 4: the shift is fixed after the cold solve -- the trace, its test and the read-modify-write of the diagonal
+            // with its two fences are the cold solve's alone; x + lambda >= x entry by entry, so a matrix that was not zero stays so)
+            wave_fence();
+            wave_round_store<NGS, 0, double>(C, tot, lane, t < 0 ? 0.0 : sol.shift(), g_rows_dsel, true);
+            wave_fence();
+            if (__builtin_expect(t < 0, 0)) {
+                double tr = 0.0;
+#pragma unroll
+                for (int i = 0; i < NSM; i++) tr += tot[i * (i + 1) / 2 + i];
+                if (!(tr > 0.0)) { st = ST_ARPACK; break; }
+                sol.cold(tr, v);
+            }
+            int r;
+            if constexpr (SAFE) {                                       // the safe repeat (k_baseline_gen decides): block by block, unshifted
+                r = solve_by_blocks<NSM>(sol, tot, ROWS_ZSLOT, v, theta, maxs, n);
+            } else r = sol.run(tot, ROWS_ZSLOT, v, theta, t == T - 1, maxs, t < 0);
+            steps += r;
+            noconv = noconv || r > maxs;
+            wave_fence();
+        }
+        if (st == ST_OK) {
+            const double sig = sqrt(theta);
+            double ts[R], cs[R], fs[R], ssum = 0.0;
+            double r2[NSM];
+#pragma unroll
+            for (int r = 0; r < R; r++) {
+                ts[r] = 0.0;
+#pragma unroll
+                for (int j = 0; j < NSM; j++) ts[r] = fma(a[r][j], v[j], ts[r]);      // u_s sigma for the final state
+                cs[r] = 0.0; fs[r] = 0.0;
+#pragma unroll
+                for (int j = 0; j < NSM; j++) {
+                    const double ke = ts[r] * v[j];                     // (K E)_sj
+                    cs[r] += ke < f[r][j] ? f[r][j] : ke;               // nmf.py:318
+                    fs[r] += f[r][j];
+                    if (r == 0) ssum += v[j];
+                    double d = ke - f[r][j];
+                    if (!first) d = d < 0.0 ? 0.0 : d;
+                    const double q = d / (f[r][j] + 1.0);               // nmf.py:282
+                    r2[j] = r == 0 ? q * q : fmax(r2[j], q * q);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < NSM; j++) {
+#pragma unroll
+                for (int o = 32; o >= 1; o >>= 1) r2[j] = fmax(r2[j], __shfl_xor(r2[j], o));
+            }
+#pragma unroll
+            for (int j = 0; j < NSM; j++) {
+                if (lane == j && j < n) {
+                    const double sk = sig * v[j];                       // s_k = (A^T u)_k
+                    sj[j] = sk;
+                    rs[j] = r2[j];
+                    if (first) sv[j] = sk;
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < R; r++)
+                if (live[r]) { g_st.u[64 * r + lane] = ts[r] / sig; g_st.csum[64 * r + lane] = cs[r]; g_st.rsum[64 * r + lane] = fs[r]; }
+            if (lane == 0) { g_st.theta = theta; g_st.S = sig * ssum; }
+        }
+        if (st == ST_OK && noconv) st = ST_NO_CONVERGENCE;
+        if (lane == 0) { g_st.status = st; g_st.steps += steps; }
+    }
+    __syncthreads();
+}
+#endif
+
+#if DN_GEN_WIDE
+// Which instantiations of the widened nmf_rows exist: those whose body the compiler keeps in the 256 registers of a wave (two
+// workgroups per CU) with no scratch access between the entry's saves of callee-saved registers and their restores -- read from
+// the disassembly of a build with all of them (README, "Wide cohorts", has the table).  The others stay on nmf_gen.
+// tools/rows_fit_scan.py compiles all of them (-DDN_ROWS_FIT_ALL=1) and prints the table: run it after a compiler update.
+template <int R, int NSM, bool SAFE> constexpr bool rows_fit()
+{
+#ifdef DN_ROWS_FIT_ALL
+    return true;
+#endif
+    return R == 2 ? (SAFE ? NSM <= 10 : NSM != 9)
+         : R == 3 ? (SAFE ? NSM <= 7 : NSM <= 6)
+                  : NSM <= 5;
+}
+
+// nmf_rows<n, SAFE, R> for the run-time column count n <= NSM_MAX; false when that instantiation does not exist (nothing was done)
+template <int R, bool SAFE>
+__device__ __forceinline__ bool rows_call(const cov_t *Fb, double *rs, double *sv, double *sj, int n, int S, int T, int first_i, int p)
+{
+    bool done = false;
+    static_for<2, NSM_MAX + 1>([&](auto N) {
+        constexpr int NS = decltype(N)::value;
+        if constexpr (rows_fit<R, NS, SAFE>()) {
+            if ((n < 2 ? 2 : n) == NS) { nmf_rows<NS, SAFE, R>(Fb, rs, sv, sj, n, S, T, first_i, p); done = true; }
+        }
+    });
+    return done;
+}
+#endif
 
 __device__ __forceinline__ double st_max(const double *v, int p) { double m = v[0]; for (int i = 1; i < p; i++) m = v[i] > m ? v[i] : m; return m; }
 __device__ __forceinline__ double st_min(const double *v, int p) { double m = v[0]; for (int i = 1; i < p; i++) m = v[i] < m ? v[i] : m; return m; }
@@ -464,6 +659,28 @@ __global__ __launch_bounds__(NT, DN_GEN_MINW) void k_baseline_gen(GenIterArgs A)
                     // one instantiation per column count: the n x n Gram matrix has NSM (NSM + 1) / 2 entries to multiply
                     // and reduce-scatter over the lanes every inner iteration (the bulk of the loop's ~1 000 instructions; at
                     // most 64 entries go in ONE round) -- config 4's first calls have 9-10 columns
+#if DN_GEN_WIDE
+                    // at most 12 active columns: the one-wave routine with R = ceil(p / 64) samples per lane where that instantiation
+                    // keeps its state in registers (rows_fit), else -- and for wider matrices -- the block-wide nmf_gen
+                    const int Rw = (p + 63) >> 6;
+                    bool by_rows = false;
+                    if (n <= NSM_MAX) by_rows = Rw == 2 ? rows_call<2, false>(Fb, rs, sv, sj, n, S, A.T, first ? 1 : 0, p)
+                                              : Rw == 3 ? rows_call<3, false>(Fb, rs, sv, sj, n, S, A.T, first ? 1 : 0, p)
+                                                        : rows_call<4, false>(Fb, rs, sv, sj, n, S, A.T, first ? 1 : 0, p);
+                    if (!by_rows) nmf_gen(Fb, Ast, rs, sv, sj, n, S, A.T, first ? 1 : 0, p);
+                    else {
+                        // the safe repeat (dn_kernels.hpp, warm_start_unsafe), the test reduced over all p samples: thread i = sample i
+                        const bool mine = g_st.status == ST_OK && tid < p && g_st.rsum[tid] > 0.0 && g_st.u[tid] < WARM_START_MIN_COMPONENT;
+                        const bool unsafe = __syncthreads_or(mine ? 1 : 0) != 0 || g_st.status == ST_NO_CONVERGENCE;
+                        if (unsafe) {
+                            __syncthreads();
+                            const bool again = Rw == 2 ? rows_call<2, true>(Fb, rs, sv, sj, n, S, A.T, first ? 1 : 0, p)
+                                             : Rw == 3 ? rows_call<3, true>(Fb, rs, sv, sj, n, S, A.T, first ? 1 : 0, p)
+                                                       : rows_call<4, true>(Fb, rs, sv, sj, n, S, A.T, first ? 1 : 0, p);
+                            if (!again) nmf_gen(Fb, Ast, rs, sv, sj, n, S, A.T, first ? 1 : 0, p);      // no safe instantiation: every solve cold
+                        }
+                    }
+#else
 #define DN_ROWS_CASE(N) case N: nmf_rows<N>(Fb, rs, sv, sj, n, S, A.T, first ? 1 : 0, p); break;
                     if (n <= NSM_MAX) {
                         switch (n) {
@@ -494,6 +711,7 @@ __global__ __launch_bounds__(NT, DN_GEN_MINW) void k_baseline_gen(GenIterArgs A)
 #undef DN_ROWS_CASE
                         }
                     }
+#endif
                     if (g_st.status != ST_OK) { status = g_st.status; break; }
                     n_calls++; sum_cols += n;
                     if (first) {
@@ -637,7 +855,7 @@ __global__ __launch_bounds__(NT, DN_GEN_MINW) void k_baseline_gen(GenIterArgs A)
     }
 }
 
-#if DN_GEN_NT == 256 && !DN_GEN_F64
+#if DN_GEN_NT == 256 && !DN_GEN_F64 && !DN_GEN_WIDE
 // ratio_svd + row sums (nmf.py:109-121, :524-525) for run-time p; uses the same scratch slots.
 // y = A (A^T u) on the RAW fp32 coverage (row stride L) in ONE pass: every thread forms s = u . a_j for its columns and
 // adds s a_j to per-thread partials of all p rows (registers), which are then block-reduced in tiles of 8.  The
@@ -1371,7 +1589,204 @@ __global__ __launch_bounds__(NT) void k_ratio_svd_gen(InitArgs A)
     }
 }
 
-#endif  // DN_GEN_NT == 256 && !DN_GEN_F64
+#endif  // DN_GEN_NT == 256 && !DN_GEN_F64 && !DN_GEN_WIDE
+
+#if DN_GEN_WIDE
+// ---------------------------------------------------------------------------------------------------
+// k_ratio_svd_wide: the initial DI pass (nmf.py:109-121, :522-525) for 65 <= p <= 256 in two streaming passes over the raw fp32
+// coverage, whatever the solver's step count.
+//   pass 1  G = X X^T (p x p, fp64) on the matrix cores.  The 16 x 16 tiles on and below the diagonal (136 at p = 256, 8 VGPRs each)
+//           do not fit one wave's registers, so tile e belongs to wave e % 4 (at most 34 accumulators per wave, fixed for the whole
+//           gene: no cross-wave sum, deterministic), and the coverage is staged once per 32-column chunk in LDS as fp32, column-major
+//           and zero-padded to whole row tiles, from where every wave reads the operands of its tiles.  v_mfma_f64_16x16x4_f64
+//           contracts over 4 columns: lane (i = l & 15, k = l >> 4) supplies row 16 t + i of column 4 kk + k for both operands.
+//   G       goes to the tail of the workgroup's scratch slot (p^2 doubles: 512 KiB at p = 256 -- L2-resident), both triangles.
+//   solve   block-wide power iteration on G (thread i = row i, reading column i: coalesced), the stopping rule and the step cap of
+//           top_singular.
+//   pass 2  the same staging; thread i = sample i adds max(u_i s_j, x_ij) and x_ij over the chunk's columns, s_j = u . x_j from eight
+//           partial dot products per column combined in a fixed order.  No reduction: a row's sums live in one thread.
+// ---------------------------------------------------------------------------------------------------
+constexpr int WG_CC = 32;                     // columns per staged chunk
+constexpr int WG_LD = 258;                    // floats per staged column (256 rows + 2: the staging writes of a wave spread over the banks)
+constexpr int WG_SLOTS = 34;                  // ceil(136 / 4) tiles per wave
+constexpr size_t WIDE_G_BYTES = (size_t) GP * GP * sizeof(double);
+__shared__ float g_wstage[WG_CC * WG_LD];
+__shared__ double g_wpart[8][WG_CC];
+
+// columns c0 .. c0 + 31 of the gene into g_wstage[column][row]; rows p .. rp - 1 and columns >= L are zeros
+__device__ __forceinline__ void wide_stage(const float *x, int L, int p, int rp, int c0)
+{
+    const int c4 = threadIdx.x & 7, rr = threadIdx.x >> 3;      // 8 lanes x 4 floats = the 32 columns of one row, 32 rows per trip
+    const int c = c0 + 4 * c4;
+    for (int r0 = 0; r0 < rp; r0 += 32) {
+        const int row = r0 + rr;
+        dn_f4 v = dn_f4{0.0f, 0.0f, 0.0f, 0.0f};
+        if (row < p && c < L) {
+            const float *src = x + (size_t) row * L + c;
+            if (c + 3 < L) v = *(const dn_f4u *) src;
+            else {
+#pragma unroll
+                for (int m = 0; m < 4; m++) if (c + m < L) v[m] = src[m];
+            }
+        }
+#pragma unroll
+        for (int m = 0; m < 4; m++) g_wstage[(4 * c4 + m) * WG_LD + row] = v[m];
+    }
+}
+
+__device__ __forceinline__ void wide_gram_pass(const float *x, double *G, int L, int p)
+{
+    const int lane = lane_id(), w = __builtin_amdgcn_readfirstlane(wave_id());
+    const int li = lane & 15, lk = lane >> 4;
+    const int TR = (p + 15) >> 4, ntiles = TR * (TR + 1) / 2;
+    const int rp = (16 * TR + 31) & ~31;                        // <= 256
+    dn_double4 acc[WG_SLOTS];
+    int off[WG_SLOTS];                                          // 16 t1 | 16 t2 << 16 of the slot's tile (t2 <= t1)
+#pragma unroll
+    for (int k = 0; k < WG_SLOTS; k++) {
+        acc[k] = dn_double4{0.0, 0.0, 0.0, 0.0};
+        const int e = 4 * k + w;
+        int t1 = 0;
+        while ((t1 + 1) * (t1 + 2) / 2 <= e) t1++;
+        const int t2 = e - t1 * (t1 + 1) / 2;
+        off[k] = (16 * t1) | ((16 * t2) << 16);
+    }
+    for (int c0 = 0; c0 < L; c0 += WG_CC) {
+        __syncthreads();                                        // the previous chunk has been consumed
+        wide_stage(x, L, p, rp, c0);
+        __syncthreads();
+#pragma clang loop unroll(disable)
+        for (int kk = 0; kk < WG_CC / 4; kk++) {
+            const float *col = g_wstage + (4 * kk + lk) * WG_LD + li;
+#pragma unroll
+            for (int k = 0; k < WG_SLOTS; k++) {
+                if (4 * k + w < ntiles) {                       // wave-uniform
+                    const double a = (double) col[off[k] & 0xffff], b = (double) col[off[k] >> 16];
+                    acc[k] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[k], 0, 0, 0);
+                }
+            }
+        }
+    }
+    // tile (t1, t2): register r of lane (c = l & 15, q = l >> 4) holds D[16 t1 + q + 4 r][16 t2 + c]
+#pragma unroll
+    for (int k = 0; k < WG_SLOTS; k++) {
+        if (4 * k + w < ntiles) {
+            const int r0 = off[k] & 0xffff, q0 = off[k] >> 16;
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int row = r0 + lk + 4 * r, cl = q0 + li;
+                if (row < p && cl < p) {
+                    G[(size_t) row * p + cl] = acc[k][r];
+                    if (r0 != q0) G[(size_t) cl * p + row] = acc[k][r];
+                }
+            }
+        }
+    }
+    __syncthreads();
+}
+
+// top eigenvector of G (p x p, symmetric, in the scratch slot) into g_st.u: top_singular's iteration with y = G u
+__device__ __forceinline__ int wide_solve(const double *G, int p)
+{
+    const int tid = threadIdx.x;
+    const int cap = 5 * g_st.max_steps;
+    for (int it = 0; ; it++) {
+        if (it >= cap) return ST_NO_CONVERGENCE;
+        if (tid < p) {
+            double s0 = 0.0, s1 = 0.0;
+            int j = 0;
+            for (; j + 1 < p; j += 2) {
+                s0 = fma(G[(size_t) j * p + tid], g_st.u[j], s0);
+                s1 = fma(G[(size_t) (j + 1) * p + tid], g_st.u[j + 1], s1);
+            }
+            if (j < p) s0 = fma(G[(size_t) j * p + tid], g_st.u[j], s0);
+            g_st.y[tid] = s0 + s1;
+        }
+        __syncthreads();
+        if (tid == 0) g_st.steps++;
+        double n2 = 0.0;
+        for (int i = 0; i < p; i++) n2 = fma(g_st.y[i], g_st.y[i], n2);
+        if (!(n2 > 0.0)) return ST_ARPACK;
+        const double inv = 1.0 / sqrt(n2);
+        double d2 = 0.0;
+        for (int i = 0; i < p; i++) { const double d = g_st.y[i] * inv - g_st.u[i]; d2 = fma(d, d, d2); }
+        __syncthreads();
+        if (tid < p) g_st.u[tid] = g_st.y[tid] * inv;
+        __syncthreads();
+        if (d2 <= 1e-27) break;
+    }
+    return ST_OK;
+}
+
+// pass 2: est_sums[i] = sum_j max(u_i s_j, x_ij), cov_sums[i] = sum_j x_ij, thread i = sample i
+__device__ __forceinline__ void wide_pass2(const float *x, int L, int p, double &pe, double &pc)
+{
+    const int tid = threadIdx.x;
+    const int TR = (p + 15) >> 4;
+    const int rp = (16 * TR + 31) & ~31;
+    const int c = tid & (WG_CC - 1), part = tid >> 5;           // s_j: column c, rows 32 part .. 32 part + 31
+    const double ui = tid < p ? g_st.u[tid] : 0.0;
+    pe = 0.0; pc = 0.0;
+    for (int c0 = 0; c0 < L; c0 += WG_CC) {
+        __syncthreads();
+        wide_stage(x, L, p, rp, c0);
+        __syncthreads();
+        {
+            double s = 0.0;
+            const int i1 = 32 * part + 32 < p ? 32 * part + 32 : p;
+            for (int i = 32 * part; i < i1; i++) s = fma(g_st.u[i], (double) g_wstage[c * WG_LD + i], s);
+            g_wpart[part][c] = s;
+        }
+        __syncthreads();
+        if (tid < p) {
+#pragma unroll 4
+            for (int j = 0; j < WG_CC; j++) {
+                const double sj = ((g_wpart[0][j] + g_wpart[1][j]) + (g_wpart[2][j] + g_wpart[3][j])) +
+                                  ((g_wpart[4][j] + g_wpart[5][j]) + (g_wpart[6][j] + g_wpart[7][j]));
+                const double v = (double) g_wstage[j * WG_LD + tid];
+                const double ke = ui * sj;
+                pe += ke < v ? v : ke;                                      // nmf.py:119
+                pc += v;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(NT) void k_ratio_svd_wide(InitArgs A)
+{
+    const int tid = threadIdx.x;
+    const int p = A.p;
+    double *G = reinterpret_cast<double *>(A.ws + (size_t) blockIdx.x * A.slot_bytes + (A.slot_bytes - (int64_t) WIDE_G_BYTES));
+    if (tid == 0) g_st.max_steps = A.max_steps > 0 ? A.max_steps : EIG_MAX_STEPS_DEFAULT;
+    __syncthreads();
+    for (;;) {
+        if (tid == 0) g_sm.gene = atomicAdd(A.counter, 1);
+        __syncthreads();
+        const int q = g_sm.gene;
+        __syncthreads();
+        if (q >= A.n_genes) break;
+        const int g = A.order[q];
+        const int L = A.glen[g];
+        const float *x = A.cov + A.goff[g];
+        int status = ST_OK;
+        double pe = 0.0, pc = 0.0;
+        if (L < 2) status = ST_VALUE_ERROR;
+        else {
+            if (tid < p) g_st.u[tid] = 1.0 / sqrt((double) p);
+            if (tid == 0) g_st.steps = 0;
+            wide_gram_pass(x, G, L, p);
+            status = wide_solve(G, p);
+            if (status == ST_OK) wide_pass2(x, L, p, pe, pc);
+        }
+        if (tid < p) {
+            A.est_sums[(size_t) g * p + tid] = status == ST_OK ? pe : 0.0;
+            A.cov_sums[(size_t) g * p + tid] = status == ST_OK ? pc : 0.0;
+        }
+        if (tid == 0) A.status[g] = status;
+        __syncthreads();
+    }
+}
+#endif  // DN_GEN_WIDE
 
 __global__ __launch_bounds__(256) void k_estimates_gen(GenEstArgs A, const int32_t *__restrict__ tile_gene,
                                                        const int32_t *__restrict__ tile_col0)
@@ -1528,6 +1943,53 @@ int blocks_per_cu_f64(int which)
     return e == hipSuccess ? nb : 0;
 }
 
+#elif DN_GEN_WIDE   // the wide-cohort build: its kernel set
+
+static int launch_baseline_ptr(const IterArgs &a, const double *d_scales, int grid, hipStream_t s)
+{
+    WideIterArgs w;
+    w.cov = a.cov; w.goff = a.goff; w.glen = a.glen; w.order = a.order; w.counter = a.counter; w.ds_start = a.ds_start; w.rowmax = a.rowmax;
+    w.ws = a.ws; w.rho = a.rho; w.flags = a.flags; w.trace = a.trace; w.kfin = a.kfin; w.emode = a.emode; w.svec = a.svec; w.svoff = a.svoff;
+    w.slot_bytes = a.slot_bytes; w.n_genes = a.n_genes; w.S = a.S; w.T = a.T; w.bins = a.bins; w.min_hc = a.min_hc; w.rate = a.rate;
+    w.skip = a.skip; w.want_est = a.want_est; w.p = a.p; w.max_steps = a.max_steps;
+    w.scale = d_scales; w.inv_scale = d_scales + P_WIDE_MAX;
+    hipLaunchKernelGGL(k_baseline_gen, dim3(grid), dim3(NT), 0, s, w);
+    return (int) hipGetLastError();
+}
+static void launch_est_ptr(const EstArgs &a, const double *d_scales, const int32_t *tg, const int32_t *tc, int n_tiles, hipStream_t s)
+{
+    WideEstArgs w;
+    w.cov = a.cov; w.goff = a.goff; w.glen = a.glen; w.kfin = a.kfin; w.emode = a.emode; w.svec = a.svec; w.svoff = a.svoff;
+    w.out = a.out; w.ooff = a.ooff; w.n_genes = a.n_genes; w.p = a.p; w.scale = d_scales;
+    hipLaunchKernelGGL(k_estimates_gen, dim3(n_tiles), dim3(256), 0, s, w, tg, tc);
+}
+static void launch_init(const InitArgs &a, int grid, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_ratio_svd_wide, dim3(grid), dim3(NT), 0, s, a);
+}
+static int blocks_per_cu(int which)
+{
+    int nb = 0;
+    const hipError_t e = which == 0 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_baseline_gen, NT, 0)
+                                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_ratio_svd_wide, NT, 0);
+    return e == hipSuccess ? nb : 0;
+}
+
+}  // namespace gen_wide
+
+const KernelSet *kernel_set_wide()
+{
+    static const KernelSet ks = {
+        0, gen_wide::NT, nullptr, gen_wide::launch_init, nullptr, gen_wide::blocks_per_cu,
+        (size_t) 160 * 1024,               // no LDS tier
+        "gen_wide::k_baseline_gen",        // as rocprofv3 prints it (dn::gen_wide::k_baseline_gen)
+        gen_wide::WIDE_G_BYTES,            // the Gram matrix of the initial pass, at the tail of the slot
+        0, 1,
+        gen_wide::launch_baseline_ptr, gen_wide::launch_est_ptr, "gen_wide::k_ratio_svd_wide",
+    };
+    return &ks;
+}
+
 #else   // the float32 count builds: kernel sets
 
 static int launch_baseline(const IterArgs &a, int grid, size_t, hipStream_t s)
@@ -1593,6 +2055,6 @@ const KernelSet *kernel_set_rows()
     return &ks;
 }
 #endif
-#endif  // DN_GEN_F64
+#endif  // DN_GEN_F64, DN_GEN_WIDE
 
 }  // namespace dn

@@ -43,7 +43,8 @@ namespace dn {
 
 constexpr int TRACE_LEN = 48;
 constexpr int MAX_BINS = 64;
-constexpr int P_MAX = 64;      // largest sample count any kernel accepts (templated and run-time-p kernels alike)
+constexpr int P_MAX = 64;      // largest sample count of the templated kernels and of the families gen, gen_rows and gen_f64
+constexpr int P_WIDE_MAX = 256; // largest sample count of the wide-cohort family (gen_wide): its `tid < p` idiom at 256 threads
 
 enum { EXIT_LOW_COV = 0, EXIT_ZERO_SAMPLE = 1, EXIT_MEDIAN = 2, EXIT_NO_LOOP = 3,
        EXIT_REFINED = 4, EXIT_REFINE_FALLBACK = 5, EXIT_NOT_FOUND_FALLBACK = 6 };
@@ -119,6 +120,49 @@ struct EstArgs {
     int32_t        n_genes;
     int32_t        p;
     double         scale[P_MAX];
+};
+
+// The wide-cohort family (dn_generic.hip compiled with DN_GEN_WIDE=1, namespace gen_wide; 65 <= p <= P_WIDE_MAX): the fields of
+// IterArgs / EstArgs with the scale factors read through a pointer -- 2 x 256 doubles by value would be 4 KiB of kernel arguments.
+struct WideIterArgs {
+    const float   *cov;
+    const int64_t *goff;
+    const int32_t *glen;
+    const int32_t *order;
+    int32_t       *counter;
+    const int64_t *ds_start;
+    const float   *rowmax;
+    char          *ws;
+    double        *rho;
+    int32_t       *flags;
+    int32_t       *trace;
+    double        *kfin;
+    int32_t       *emode;
+    double        *svec;
+    const int64_t *svoff;
+    int64_t        slot_bytes;
+    int32_t        n_genes;
+    int32_t        S;
+    int32_t        T, bins, min_hc, rate, skip, want_est;
+    int32_t        p;
+    int32_t        max_steps;
+    const double  *scale;      // p scale factors (device)
+    const double  *inv_scale;  // p reciprocals (device)
+};
+
+struct WideEstArgs {
+    const float   *cov;
+    const int64_t *goff;
+    const int32_t *glen;
+    const double  *kfin;
+    const int32_t *emode;
+    const double  *svec;
+    const int64_t *svoff;
+    double        *out;
+    const int64_t *ooff;
+    int32_t        n_genes;
+    int32_t        p;
+    const double  *scale;      // p scale factors (device)
 };
 
 // The float64-input path (dn_generic.hip compiled with DN_GEN_F64=1, namespace gen_f64; dn_nmf_f64 / dn_baseline_selection_f64):
@@ -2581,6 +2625,10 @@ typedef int (*baseline_launch_fn)(const IterArgs &, int grid, size_t dyn_lds_byt
 typedef void (*init_launch_fn)(const InitArgs &, int grid, hipStream_t);
 typedef void (*est_launch_fn)(const EstArgs &, const int32_t *, const int32_t *, int n_tiles, hipStream_t);
 typedef int (*occupancy_fn)(int which);
+// the wide-cohort family: the scale arrays of the argument struct are ignored, d_scales holds p scale factors followed, at
+// P_WIDE_MAX, by their reciprocals (device memory, written on the launch's stream)
+typedef int (*baseline_ptr_launch_fn)(const IterArgs &, const double *d_scales, int grid, hipStream_t);
+typedef void (*est_ptr_launch_fn)(const EstArgs &, const double *d_scales, const int32_t *, const int32_t *, int n_tiles, hipStream_t);
 
 struct KernelSet {
     int p;
@@ -2596,10 +2644,14 @@ struct KernelSet {
     int units;                        // genes a workgroup carries at once (2: the pair build, one gene per wavefront; else 1).
                                       // `nt` threads, the LDS tile and a scratch slot belong to ONE unit; `static_lds_bytes`,
                                       // blocks_per_cu() and the dynamic LDS of a launch to the workgroup
+    baseline_ptr_launch_fn baseline_ptr;   // non-null: the set reads its scale factors through a pointer (`baseline` and `est` are null)
+    est_ptr_launch_fn est_ptr;
+    const char *init_name;            // the set's own initial pass as rocprofv3 prints it, or null
 };
 
 const KernelSet *kernel_set_for(int p);   // dn_api.hip
 const KernelSet *kernel_set_generic();    // dn_generic.hip (run-time p, any p <= P_MAX)
+const KernelSet *kernel_set_wide();       // dn_generic.hip compiled with DN_GEN_WIDE=1 (run-time p, P_MAX < p <= P_WIDE_MAX)
 
 // dn_generic.hip compiled with DN_GEN_F64=1 (namespace gen_f64): the float64-input path.  Launchers return hipGetLastError().
 int launch_row_max_f64(const double *cov, const int64_t *goff, const int32_t *glen, double *rowmax, int n, int p, int grid, hipStream_t s);

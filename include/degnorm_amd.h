@@ -61,7 +61,10 @@ typedef struct {
 const char *dn_version(void);
 const char *dn_last_error(void);
 int  dn_device_count(void);
-int  dn_p_supported(int p);                         /* 1 if kernels for p samples are compiled in          */
+int  dn_p_supported(int p);                         /* 1 if kernels for p samples are compiled in: the count-path
+                                                       families of 2 .. 64 samples (0 from 65 on, see dn_p_max) */
+int  dn_p_max(void);                                /* 256: the widest cohort dn_upload_* takes.  65 .. dn_p_max()
+                                                       samples run on the wide-cohort kernel family             */
 
 int  dn_create(int device, dn_handle *out);
 int  dn_destroy(dn_handle h);
@@ -75,7 +78,9 @@ int  dn_destroy(dn_handle h);
  * dn_upload_ragged: genes[g] points at a C-contiguous p x lengths[g] matrix of float64 (is_f32 = 0)
  * or float32 (is_f32 = 1).  *inexact (nullable) receives the number of values that are not exactly
  * representable in float32 (DegNorm coverage is integer counts, reads.py:714,773, so normally 0).
- * dn_upload_packed: the same data already packed (offsets in elements, offsets[n] = total).          */
+ * dn_upload_packed: the same data already packed (offsets in elements, offsets[n] = total).
+ * Both accept 2 <= p <= dn_p_max(); beyond that DN_E_UNSUPPORTED.  The float64 per-gene path (dn_nmf_f64,
+ * dn_baseline_selection_f64) stays at 2 <= p <= 64.                                                   */
 /* Optional, before an upload: the take-every rate the following dn_baseline_iteration calls will use (GeneNMFOA's
  * downsample_rate, nmf.py:36).  Only steers which kernel family serves the data (results do not depend on it): when no
  * gene can keep more than 12 active columns, the row-wise one-wave-per-gene kernels are chosen from p = 8 on.          */
@@ -156,11 +161,13 @@ int  dn_fetch_outer(dn_handle h, double *rho, double *x_adj, double *x_weighted,
  *   dn_comm_create      every rank, collectively: joins the communicator with the handle's GPU (ncclCommInitRank)
  *   dn_init_allreduce   dn_init_partials summed over the ranks: totals[3p + 4], same layout
  *   dn_outer_allreduce  dn_outer_partials summed over the ranks: totals[3p + 4], same layout; dn_outer_apply follows
- *   dn_comm_allreduce   sums a small host vector (<= 256 doubles) over the ranks in place: a rank WITHOUT genes joins the
+ *   dn_comm_allreduce   sums a small host vector (<= DN_COMM_MAX_DOUBLES: the 3p + 4 sums of the widest cohort) over the
+ *                       ranks in place: a rank WITHOUT genes joins the
  *                       two collectives above with zeros through this call (same count 3p + 4), error counts, ...
  *   dn_comm_library     which librccl was bound ("" if none could be loaded).  RCCL is resolved at run time (a copy the
  *                       process already holds, e.g. PyTorch's, else DN_RCCL_PATH, else the system's): no link-time dependency. */
 #define DN_COMM_ID_BYTES 128
+#define DN_COMM_MAX_DOUBLES (3 * 256 + 4)
 int  dn_comm_unique_id(uint8_t *id);
 int  dn_comm_create(dn_handle h, const uint8_t *id, int32_t rank, int32_t size);
 int  dn_comm_destroy(dn_handle h);
