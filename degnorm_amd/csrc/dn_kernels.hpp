@@ -1114,7 +1114,12 @@ struct GeneState {
     int32_t steps;       //   power-iteration steps spent (accumulated over the gene's calls)
     int32_t status;
     int32_t max_steps;   // step cap of one eigen-solve (IterArgs::max_steps)
-    long long stamp[6];  // diagnostic builds (DN_STAMP): cycles in pass / reduction / eigen-solver / whole nmf() calls / final pass / cold start
+#ifdef DN_STAMP
+    long long stamp[8];  // diagnostic builds (DN_STAMP): cycles in pass / reduction / eigen-solver / whole nmf() calls / final pass / cold start /
+                         // pass of the partial register-tier body, and that body's column passes per lane (rounds x T)
+#else
+    long long stamp[6];
+#endif
 };
 
 // The workgroup's LDS objects live at namespace scope so that the out-of-line nmf_call() addresses them with
@@ -1653,6 +1658,18 @@ template <int N, int NT> __device__ __forceinline__ void rt_restore(const int *s
         }
     });
 }
+// column(0), column(1), ... while R < nr (nr wave-uniform, >= 1): the walk of a register tier padded to whole rounds
+template <int R, int RT, typename F>
+__device__ __forceinline__ void partial_rounds(int nr, F &&column)
+{
+    if constexpr (R < RT) {
+        if (R == 0 || R < nr) {                             // a call has at least one column
+            column(std::integral_constant<int, R>{});
+            __builtin_amdgcn_sched_barrier(0);
+            partial_rounds<R + 1, RT>(nr, column);
+        }
+    }
+}
 template <int P, int NT> constexpr size_t rt_save_bytes() { return (size_t) rt_regs_used<P>() * 4 * NT; }
 
 // FULL: the gene fills the register tier (n >= RT * NT): every lane owns all RT columns and the tier is walked as straight-line code
@@ -1781,10 +1798,28 @@ __device__ __forceinline__ void nmf_body(const float *Fb_, double *Lg_, double *
     };
     pass_u();
 
+    // PART: the partial register-tier body (n < NR).  Its tier is padded to whole rounds: in the gene's last round, nr - 1, the lanes
+    // beyond the gene hold state 0 and counts 0, so that the T loop walks rounds 0 .. nr - 1 with no test per lane.  A padded column
+    // stays at zero (col_update: s = u . 0, a = max(0 - c 0, 0)) and its products fma(0, 0, G) return G bit for bit: every lane adds
+    // its own columns in the order it always did.  The padding is written on every call: the drop loop's narrower call finds the
+    // wider one's data in those registers (rt_save's `need` covers round nr - 1).
+    constexpr bool PART = RT > 0 && X16 && !FULL;
+    const int nr = (n + NT - 1) / NT;                            // rounds of the tier this gene reaches (uniform)
     static_for<0, RT>([&](auto rc) {                             // lmbda = zeros (nmf.py:90): state a = x
         constexpr int R = decltype(rc)::value;
         const int k = tid + R * NT;
-        if (k < n) {
+        if constexpr (PART) {
+            if (R < nr) {
+                float xf[P];
+                double f[P];
+#pragma unroll
+                for (int i = 0; i < P; i++) xf[i] = 0.0f;
+                if (k < n) load_x<P>(Fb, k, xf);
+                pass_counts<P, RAW>(xf, inv, f);
+                rt_write<P, CS * R>(f);
+                rt_write_counts<P, CS * R + 2 * P>(xf);
+            }
+        } else if (k < n) {
             float xf[P];
             double f[P];
             load_x<P>(Fb, k, xf);
@@ -1817,10 +1852,11 @@ __device__ __forceinline__ void nmf_body(const float *Fb_, double *Lg_, double *
 #pragma clang loop unroll(disable)
     for (int t = 0; t < T; t++) {
         DN_MARK("iter_begin");
-        if constexpr (!G0) {
+        auto gram_zero = [&]() {
 #pragma unroll
             for (int i = 0; i < CH; i++) G[i] = 0.0;
-        }
+        };
+        if constexpr (!G0 && !PART) gram_zero();
         DN_MARK("zeroed");
         { DN_T0();
         // The columns are walked forwards on even passes and backwards on odd ones (spill tier first, then the LDS tier):
@@ -1838,7 +1874,8 @@ __device__ __forceinline__ void nmf_body(const float *Fb_, double *Lg_, double *
         // as well measured 1.7x SLOWER per column -- the extra live registers end up in AGPRs and every use pays a copy
         // -- and so did a register-resident tier in front of it (tools/trace_stats.py, profiles/round1).
         // register tier: unrolled over the lane's RT columns, the next column's counts requested before this one's arithmetic
-        auto reg_tier = [&]() {
+        // (start: the tier's first column starts the Gram accumulators instead of adding to them)
+        auto reg_tier = [&](auto start) {
             if constexpr (RT > 0 && X16) {
                 // counts AND state in registers: a column of this tier touches no memory in a pass
                 auto column = [&](auto rc) {
@@ -1851,7 +1888,7 @@ __device__ __forceinline__ void nmf_body(const float *Fb_, double *Lg_, double *
                     }
                     rt_read<P, CS * R>(a);
                     col_update<P>(f, a, ud, ur, c);
-                    if constexpr (G0 && R == 0) gram_set_range<P, 0, CH>(G, a); else gram_add_range<P, 0, CH>(G, a);
+                    if constexpr (decltype(start)::value && R == 0) gram_set_range<P, 0, CH>(G, a); else gram_add_range<P, 0, CH>(G, a);
                     rt_write<P, CS * R>(a);
                 };
                 if constexpr (FULL) {
@@ -1860,10 +1897,9 @@ __device__ __forceinline__ void nmf_body(const float *Fb_, double *Lg_, double *
                     // scheduling barrier keeps the columns apart so that the register pressure stays that of one column
                     static_for<0, RT>([&](auto rc) { column(rc); __builtin_amdgcn_sched_barrier(0); });
                 } else {
-                    static_for<0, RT>([&](auto rc) {
-                        constexpr int R = decltype(rc)::value;
-                        if (tid + R * NT < n) column(rc);
-                    });
+                    // the padded rounds 0 .. nr - 1, unmasked like the full tier: one uniform branch per round leaves the chain, and
+                    // rounds >= nr are never visited (a masked copy of a column next to the unmasked one sent the allocator to scratch)
+                    partial_rounds<0, RT>(nr, column);
                 }
             } else if constexpr (RT > 0) {
                 // the next column's counts are requested before this column's arithmetic starts (two columns ahead with two
@@ -1954,9 +1990,16 @@ __device__ __forceinline__ void nmf_body(const float *Fb_, double *Lg_, double *
 #else
 #define DN_TIER(id, call) call
 #endif
-        if constexpr (G0) { DN_MARK("reg_tier"); DN_TIER(1, reg_tier()); DN_MARK("lds_tier"); DN_TIER(2, lds_tier()); }       // the register tier touches no memory: its place is free
-        else if (dir > 0) { DN_MARK("reg_tier"); DN_TIER(1, reg_tier()); DN_MARK("lds_tier"); DN_TIER(2, lds_tier()); DN_MARK("spill_tier"); DN_TIER(3, spill_tier()); }
-        else { DN_MARK("spill_tier_b"); DN_TIER(3, spill_tier()); DN_MARK("lds_tier_b"); DN_TIER(2, lds_tier()); DN_MARK("reg_tier_b"); DN_TIER(1, reg_tier()); }
+        if constexpr (PART) {
+            // n < NR: the LDS and spill tiers are empty.  One scalar test skips their set-up; the loops stay behind it.  Forwards the tier
+            // comes first and its column 0, unmasked in every lane, starts the accumulators (a padded lane with 0 * 0)
+            const bool mem = n > NR;
+            if (dir > 0) { DN_MARK("reg_tier"); DN_TIER(1, reg_tier(std::true_type{})); if (mem) { DN_MARK("lds_tier"); DN_TIER(2, lds_tier()); DN_MARK("spill_tier"); DN_TIER(3, spill_tier()); } }
+            else { gram_zero(); if (mem) { DN_MARK("spill_tier_b"); DN_TIER(3, spill_tier()); DN_MARK("lds_tier_b"); DN_TIER(2, lds_tier()); } DN_MARK("reg_tier_b"); DN_TIER(1, reg_tier(std::false_type{})); }
+        }
+        else if constexpr (G0) { DN_MARK("reg_tier"); DN_TIER(1, reg_tier(std::true_type{})); DN_MARK("lds_tier"); DN_TIER(2, lds_tier()); }       // the register tier touches no memory: its place is free
+        else if (dir > 0) { DN_MARK("reg_tier"); DN_TIER(1, reg_tier(std::false_type{})); DN_MARK("lds_tier"); DN_TIER(2, lds_tier()); DN_MARK("spill_tier"); DN_TIER(3, spill_tier()); }
+        else { DN_MARK("spill_tier_b"); DN_TIER(3, spill_tier()); DN_MARK("lds_tier_b"); DN_TIER(2, lds_tier()); DN_MARK("reg_tier_b"); DN_TIER(1, reg_tier(std::false_type{})); }
         DN_MARK("pass_end");
 #if !(defined(DN_STAMP) && defined(DN_EXP_TIER))
         DN_T1(0);
@@ -2069,6 +2112,7 @@ __device__ __forceinline__ void nmf_body(const float *Fb_, double *Lg_, double *
 #ifdef DN_STAMP
         g_gs.stamp[0] += stamp[0]; g_gs.stamp[1] += stamp[1]; g_gs.stamp[2] += stamp[2];
         g_gs.stamp[4] += __builtin_amdgcn_s_memtime() - t_fin0; g_gs.stamp[5] += stamp[3];
+        if constexpr (RT > 0 && X16 && !FULL) { g_gs.stamp[6] += stamp[0]; g_gs.stamp[7] += (long long) T * ((n + NT - 1) / NT); }
 #endif
     }
     dn_sync();
@@ -2182,6 +2226,9 @@ __global__ __launch_bounds__(NT * DN_UNITS, DN_KERNEL_WAVES) void k_baseline(Ite
         int32_t *tr = A.trace + (size_t) g * TRACE_LEN;
         if (tid < P) { gs.rho[tid] = 0.0; gs.K[tid] = 0.0; gs.us[tid] = 0.0; }
         if (tid == 0) { gs.steps = 0; gs.stamp[0] = gs.stamp[1] = gs.stamp[2] = gs.stamp[3] = gs.stamp[4] = gs.stamp[5] = 0; }
+#ifdef DN_STAMP
+        if (tid == 0) gs.stamp[6] = gs.stamp[7] = 0;
+#endif
 
         // ---- get_high_coverage_idx (nmf.py:66-76) on F = x / s (nmf.py:146) -------------------------
         // max_j fl(x_ij / s_i) = fl((max_j x_ij) / s_i): division by a positive scalar is monotone, so the global maximum
@@ -2495,6 +2542,7 @@ __global__ __launch_bounds__(NT * DN_UNITS, DN_KERNEL_WAVES) void k_baseline(Ite
             tr[47] = (int32_t) ((t_scan1 - t_gene0) >> 10);
             tr[39] = (int32_t) (t_book >> 10);
             tr[38] = (int32_t) ((t_ret != 0 ? __builtin_amdgcn_s_memtime() - t_ret : 0) >> 10);
+            tr[36] = (int32_t) (gs.stamp[6] >> 10); tr[37] = (int32_t) gs.stamp[7];      // the partial register-tier body: pass kilo-cycles, column passes per lane
 #endif
         }
         if (A.want_est && (emode == EM_CLAMPED || emode == EM_RAW)) {

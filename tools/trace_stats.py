@@ -47,6 +47,12 @@ if tr[:, 40:44].any():
         m = ok & (n0 >= a) & (n0 < b)
         if m.any():
             print('  [%4d,%4d): %5d  %7.0f  %7.0f   %.3f' % (a, b, m.sum(), np.median(per_col[m]), np.median(per_it[m]), tr[m, 43].sum() / tot))
+if tr[:, 36:38].any():
+    # the partial register-tier body (calls with fewer columns than the tier holds): its share of all pass cycles, and its pass cycles per
+    # column pass of a lane (the fixed part of a pass included)
+    part, rounds = tr[:, 36].astype(float).sum() * 1024, tr[:, 37].astype(float).sum()
+    print('partial register-tier body: %.3f of pass cycles, %.3f of gene time; %.0f pass cycles per column pass per lane (%.3e column passes per lane)'
+          % (part / (tr[:, 40].astype(float).sum() * 1024), part / (tr[:, 43].astype(float).sum() * 1024), part / max(rounds, 1), rounds))
 if tr[:, 44:47].any():
     ext = tr[:, 44:47].astype(float).sum(axis=0) * 1024
     tot = tr[:, 43].astype(float).sum() * 1024
