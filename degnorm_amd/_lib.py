@@ -76,6 +76,8 @@ def load(build_if_missing=False):
     lib.dn_fetch_outer.argtypes = [vp, P(dbl), P(dbl), P(dbl), P(c.c_uint8)]
     lib.dn_fetch_rows.argtypes = [vp, i64, P(i64), P(dbl), P(i32)]
     lib.dn_fetch_estimates_subset.argtypes = [vp, i64, P(i64), P(dbl)]
+    lib.dn_debug_plant.argtypes = [vp, i32, vp]
+    lib.dn_debug_peek.argtypes = [vp, i32, vp]
     lib.dn_last_kernel_ms.argtypes = [vp]
     lib.dn_last_kernel_ms.restype = dbl
     lib.dn_main_kernel_name.argtypes = [vp]
@@ -443,6 +445,26 @@ class Device:
         flags = np.zeros(rows.size, dtype=np.int32)
         _check(self.lib.dn_fetch_rows(self.h, rows.size, _p(rows, ctypes.c_int64), _p(rho, ctypes.c_double), _p(flags, ctypes.c_int32)))
         return rho, flags.astype(bool)
+
+    # -- the test seam (dn_debug_plant / dn_debug_peek): for the suite, not for the product ------------------------------
+    PLANT = {'rho_raw': (0, np.float64, True), 'flags': (1, np.int32, False), 'iter_status': (2, np.int32, False),
+             'est_sums': (3, np.float64, True), 'cov_sums': (4, np.float64, True), 'init_status': (5, np.int32, False)}
+    PEEK = {'rowmax': (0, np.float32, True), 'x16': (1, np.int32, False)}
+
+    def debug_plant(self, which, values):
+        """Overwrite one device array that only a kernel writes: `which` is a key of PLANT, values its whole content."""
+        code, dt, per_sample = self.PLANT[which]
+        a = np.ascontiguousarray(values, dtype=dt)
+        if a.shape != ((self.n, self.p) if per_sample else (self.n,)):
+            raise ValueError('{0} takes an array of {1}'.format(which, 'n x p' if per_sample else 'n'))
+        _check(self.lib.dn_debug_plant(self.h, code, a.ctypes.data))
+
+    def debug_peek(self, which):
+        """The row maxima ('rowmax', n x p float32) or the 16-bit flags ('x16', n int32) the last upload computed."""
+        code, dt, per_sample = self.PEEK[which]
+        out = np.empty((self.n, self.p) if per_sample else (self.n,), dtype=dt)
+        _check(self.lib.dn_debug_peek(self.h, code, out.ctypes.data))
+        return out
 
     def fetch_estimates_subset(self, gene_ids):
         """Estimates of the chosen genes only (indices in upload order): list of (p x L_g) float64 arrays."""

@@ -1631,6 +1631,47 @@ int dn_fetch_rows(dn_handle h, int64_t n_rows, const int64_t *rows, double *rho_
     });
 }
 
+// The test seam (TEST-ONLY, see the header): state that only a kernel writes, overwritten from host memory, and the two upload
+// outputs that nothing else returns, copied out.  Copies on the main stream, no kernel.
+int dn_debug_plant(dn_handle h, int32_t which, const void *src)
+{
+    if (!h) return fail(DN_E_INVALID, "dn_debug_plant: null handle");
+    if (!src) return fail(DN_E_INVALID, "dn_debug_plant: null source");
+    if (which < DN_PLANT_RHO_RAW || which > DN_PLANT_INIT_STATUS) return fail(DN_E_INVALID, "dn_debug_plant: unknown array");
+    if (!h->data.d_cov) return fail(DN_E_STATE, "dn_debug_plant: nothing uploaded");
+    return on_main_stream(h, [&]() -> int {
+        const size_t n = (size_t) h->n, np = n * (size_t) h->p;
+        switch (which) {
+            case DN_PLANT_RHO_RAW: DN_TRY(hipMemcpyAsync(h->data.d_rho, src, sizeof(double) * np, hipMemcpyHostToDevice, h->stream[0])); break;
+            case DN_PLANT_FLAGS: DN_TRY(hipMemcpyAsync(h->data.d_flags, src, sizeof(int32_t) * n, hipMemcpyHostToDevice, h->stream[0])); break;
+            case DN_PLANT_ITER_STATUS:                         // column 6 of the n x TRACE_LEN counters: a strided copy
+                DN_TRY(hipMemcpy2DAsync(h->data.d_trace + 6, sizeof(int32_t) * dn::TRACE_LEN, src, sizeof(int32_t), sizeof(int32_t), n,
+                                        hipMemcpyHostToDevice, h->stream[0]));
+                break;
+            case DN_PLANT_EST_SUMS: DN_TRY(hipMemcpyAsync(h->data.d_est_sums, src, sizeof(double) * np, hipMemcpyHostToDevice, h->stream[0])); break;
+            case DN_PLANT_COV_SUMS: DN_TRY(hipMemcpyAsync(h->data.d_cov_sums, src, sizeof(double) * np, hipMemcpyHostToDevice, h->stream[0])); break;
+            default: DN_TRY(hipMemcpyAsync(h->data.d_status, src, sizeof(int32_t) * n, hipMemcpyHostToDevice, h->stream[0])); break;
+        }
+        DN_TRY(hipStreamSynchronize(h->stream[0]));           // the host buffer behind src may go away
+        return DN_OK;
+    });
+}
+
+int dn_debug_peek(dn_handle h, int32_t which, void *dst)
+{
+    if (!h) return fail(DN_E_INVALID, "dn_debug_peek: null handle");
+    if (!dst) return fail(DN_E_INVALID, "dn_debug_peek: null destination");
+    if (which != DN_PEEK_ROWMAX && which != DN_PEEK_X16) return fail(DN_E_INVALID, "dn_debug_peek: unknown array");
+    if (!h->data.d_rowmax || !h->data.d_x16) return fail(DN_E_STATE, "dn_debug_peek: nothing uploaded");
+    return on_main_stream(h, [&]() -> int {
+        const size_t n = (size_t) h->n;
+        if (which == DN_PEEK_ROWMAX) DN_TRY(hipMemcpyAsync(dst, h->data.d_rowmax, sizeof(float) * n * (size_t) h->p, hipMemcpyDeviceToHost, h->stream[0]));
+        else DN_TRY(hipMemcpyAsync(dst, h->data.d_x16, sizeof(int32_t) * n, hipMemcpyDeviceToHost, h->stream[0]));
+        DN_TRY(hipStreamSynchronize(h->stream[0]));
+        return DN_OK;
+    });
+}
+
 // First touch of a large, freshly allocated host buffer from several threads at once (one write per 4 KiB page; the caller
 // overwrites every byte afterwards): a single thread faults ~4 GB of new pages in 0.15-0.2 s on the GPU box, which is more
 // than the copy that fills them takes.

@@ -45,6 +45,24 @@ extern "C" int dn_assemble_coverage(int device, int64_t chrom_len, int32_t p, co
                                     float *out_packed, double *device_ms)
 {
     if (chrom_len <= 0 || p < 1 || n_genes < 1 || !lengths || !out_packed || n_chunks < 0) return dn::fail(DN_E_INVALID, "dn_assemble_coverage: bad argument");
+    // The tables are checked before anything reaches the device: a chunk that leaves its gene would be a write outside d_out.
+    // (chunk_src needs no check: k_gather_intervals reads zeros outside the chromosome.)
+    if (!nnz || !indices || !values) return dn::fail(DN_E_INVALID, "dn_assemble_coverage: null sample table");
+    if (n_chunks > 0 && (!chunk_gene || !chunk_src || !chunk_dst_in_gene || !chunk_len)) return dn::fail(DN_E_INVALID, "dn_assemble_coverage: null chunk table");
+    for (int i = 0; i < p; i++) {
+        if (nnz[i] < 0) return dn::fail(DN_E_INVALID, "dn_assemble_coverage: nnz of sample " + std::to_string(i) + " is negative");
+        if (nnz[i] > 0 && (!indices[i] || !values[i])) return dn::fail(DN_E_INVALID, "dn_assemble_coverage: sample " + std::to_string(i) + " has nnz > 0 and a null index or value array");
+    }
+    for (int64_t g = 0; g < n_genes; g++)
+        if (lengths[g] < 0) return dn::fail(DN_E_INVALID, "dn_assemble_coverage: length of gene " + std::to_string(g) + " is negative");
+    for (int64_t c = 0; c < n_chunks; c++) {
+        const char *bad = (chunk_gene[c] < 0 || chunk_gene[c] >= n_genes)               ? " names a gene outside [0, n_genes)"
+                          : chunk_len[c] < 0                                             ? " has a negative length"
+                          : chunk_dst_in_gene[c] < 0                                     ? " has a negative destination"
+                          : chunk_dst_in_gene[c] > lengths[chunk_gene[c]] - chunk_len[c] ? " ends beyond its gene"
+                                                                                         : nullptr;
+        if (bad) return dn::fail(DN_E_INVALID, "dn_assemble_coverage: chunk " + std::to_string(c) + bad);
+    }
     // absolute destination of every chunk for sample 0; sample i adds i * L_gene
     std::vector<int64_t> goff((size_t) n_genes + 1, 0);
     for (int64_t g = 0; g < n_genes; g++) goff[g + 1] = goff[g] + (int64_t) p * lengths[g];

@@ -178,6 +178,33 @@ int  dn_init_allreduce(dn_handle h, double *totals);
 int  dn_outer_allreduce(dn_handle h, double *totals);
 int  dn_fetch_rows(dn_handle h, int64_t n_rows, const int64_t *rows, double *rho_raw, int32_t *flags);
 
+/* TEST-ONLY seam -- not part of the product's path, no caller under degnorm_amd/ besides the ctypes binding ---------------
+ * The O(n p) kernels around the NMF pass read state that only kernels write (the raw DI rows, the flags and the per-gene
+ * status of dn_baseline_iteration; the two sums and the status of dn_ratio_svd_sums) and write two arrays that no entry point
+ * returns (the row maxima and the 16-bit flag of an upload).  The suite plants the former and reads the latter to compare
+ * each of those kernels with a restatement of its own operation on inputs that no data set produces.
+ *   dn_debug_plant   overwrites one device array of an uploaded handle from host memory (copies on the handle's stream,
+ *                    no kernel); src holds the WHOLE array:
+ *                      DN_PLANT_RHO_RAW      n x p doubles   the unclipped DI rows
+ *                      DN_PLANT_FLAGS        n int32         ran_baseline_selection of the last iteration
+ *                      DN_PLANT_ITER_STATUS  n int32         column 6 of the per-gene counters (status of the last iteration)
+ *                      DN_PLANT_EST_SUMS     n x p doubles   est_sums of the initial pass
+ *                      DN_PLANT_COV_SUMS     n x p doubles   cov_sums of the initial pass
+ *                      DN_PLANT_INIT_STATUS  n int32         status of the initial pass
+ *   dn_debug_peek    copies out DN_PEEK_ROWMAX (n x p floats, max_j x_ij of the uploaded coverage) or DN_PEEK_X16 (n int32:
+ *                    1 when every count of the gene is a whole number in [0, 65535])
+ * DN_E_INVALID for a null handle, a null pointer or an unknown array, DN_E_STATE when nothing is uploaded.                    */
+#define DN_PLANT_RHO_RAW 0
+#define DN_PLANT_FLAGS 1
+#define DN_PLANT_ITER_STATUS 2
+#define DN_PLANT_EST_SUMS 3
+#define DN_PLANT_COV_SUMS 4
+#define DN_PLANT_INIT_STATUS 5
+#define DN_PEEK_ROWMAX 0
+#define DN_PEEK_X16 1
+int  dn_debug_plant(dn_handle h, int32_t which, const void *src);
+int  dn_debug_peek(dn_handle h, int32_t which, void *dst);
+
 /* Estimated coverage matrices of the last dn_baseline_iteration run with want_estimates = 1 ----------
  * Replaces: the `estimate` output of baseline_selection (nmf.py:355-369), returned by run() (nmf.py:601).
  * out: float64, gene g at element offset p * sum(lengths[:g]), p x L_g row-major.                     */

@@ -1,7 +1,8 @@
 """
 The refusals of the NMF C ABI (csrc/dn_api.hip) that need no failing HIP call: return code and exact dn_last_error() text, as
 the library gave them before its entry points were put under the exit rule of dn_host.hpp.  test_api_errors_host.py makes
-the calls that are refused before the device is touched, test_gpu_api_exit_rule.py those that need an uploaded handle.
+the calls that are refused before the device is touched, test_gpu_api_exit_rule.py those that need an uploaded handle or an
+empty one.  The test seam (dn_debug_plant, dn_debug_peek) has its rows in all three tables.
 """
 import ctypes
 
@@ -37,6 +38,8 @@ EARLY = {
     'baseline_selection_f64.null_handle': (STATE, b'dn_baseline_selection_f64: null handle'),
     'class_tier_cols.bad': (INVALID, b'dn_class_tier_cols: bad argument'),
     'class_lengths.null': (INVALID, b'dn_class_lengths: null argument'),
+    'debug_plant.null_handle': (INVALID, b'dn_debug_plant: null handle'),
+    'debug_peek.null_handle': (INVALID, b'dn_debug_peek: null handle'),
 }
 # arguments and state of an uploaded handle; its state refusals repeat texts of EARLY
 UPLOADED = {
@@ -53,8 +56,18 @@ UPLOADED = {
     'fetch_estimates_subset.duplicate': (INVALID, b'dn_fetch_estimates_subset: duplicate gene id'),
     'fetch_estimates_subset.range': (INVALID, b'dn_fetch_estimates_subset: gene id out of range'),
     'nmf_f64.mode': (INVALID, b'dn_nmf_f64: unknown mode'),
+    'debug_plant.null': (INVALID, b'dn_debug_plant: null source'),
+    'debug_plant.which': (INVALID, b'dn_debug_plant: unknown array'),
+    'debug_peek.null': (INVALID, b'dn_debug_peek: null destination'),
+    'debug_peek.which': (INVALID, b'dn_debug_peek: unknown array'),
+}
+# state of a handle that exists but holds no data set (a fresh one, or one whose upload was refused)
+EMPTY = {
+    'debug_plant.state': (STATE, b'dn_debug_plant: nothing uploaded'),
+    'debug_peek.state': (STATE, b'dn_debug_peek: nothing uploaded'),
 }
 TABLE = dict(EARLY, **UPLOADED)
+TABLE.update(EMPTY)
 
 
 def refused(lib, rc, key, live=None):

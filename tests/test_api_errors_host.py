@@ -60,6 +60,10 @@ CASES = [
     ('dn_class_tier_cols', {}, 'class_tier_cols.bad'),
     ('dn_class_lengths', {'i1': 10, 'i2': 1}, 'class_lengths.null'),
     ('dn_synchronize', {}, 'null_handle'),
+    ('dn_debug_plant', {}, 'debug_plant.null_handle'),
+    ('dn_debug_plant', {'i1': 9, 'i2': _F32.ctypes.data}, 'debug_plant.null_handle'),       # the handle is looked at first
+    ('dn_debug_peek', {}, 'debug_peek.null_handle'),
+    ('dn_debug_peek', {'i1': 9, 'i2': _F32.ctypes.data}, 'debug_peek.null_handle'),
 ]
 
 

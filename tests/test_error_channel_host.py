@@ -76,6 +76,52 @@ def test_assemble_coverage_bad_argument():
     assert lib.dn_assemble_last_error() == b'dn_assemble_coverage: bad argument'
 
 
+def _assemble(**change):
+    """dn_assemble_coverage on a sound two-sample, two-gene, three-chunk layout with the named arguments replaced; every call of
+    the tests below is refused before the device is touched (the output stays as it was)."""
+    lib = _lib.load()
+    idx, val = np.array([3, 1], np.int32), np.array([5., 7.], np.float32)
+    a = dict(nnz=np.array([2, 0], np.int64), indices=(ctypes.c_void_p * 2)(idx.ctypes.data, None),
+             values=(ctypes.c_void_p * 2)(val.ctypes.data, None), lengths=np.array([6, 4], np.int64),
+             chunk_gene=np.array([0, 0, 1], np.int32), chunk_src=np.array([0, 10, 2], np.int64),
+             chunk_dst=np.array([0, 3, 0], np.int64), chunk_len=np.array([3, 3, 4], np.int32))
+    a.update(change)
+    out = np.full(20, -1.0, np.float32)
+    raw = lambda v: v if v is None or not isinstance(v, np.ndarray) else _ptr(v)
+    rc = lib.dn_assemble_coverage(0, 100, 2, raw(a['nnz']), a['indices'], a['values'], 2, raw(a['lengths']), 3, raw(a['chunk_gene']),
+                                  raw(a['chunk_src']), raw(a['chunk_dst']), raw(a['chunk_len']), _ptr(out), None)
+    assert np.all(out == -1.0)
+    return rc, lib.dn_assemble_last_error()
+
+
+ASSEMBLE_REFUSALS = [
+    (dict(nnz=None), b'dn_assemble_coverage: null sample table'),
+    (dict(indices=None), b'dn_assemble_coverage: null sample table'),
+    (dict(values=None), b'dn_assemble_coverage: null sample table'),
+    (dict(chunk_gene=None), b'dn_assemble_coverage: null chunk table'),
+    (dict(chunk_len=None), b'dn_assemble_coverage: null chunk table'),
+    (dict(nnz=np.array([2, -1], np.int64)), b'dn_assemble_coverage: nnz of sample 1 is negative'),
+    (dict(nnz=np.array([2, 1], np.int64)), b'dn_assemble_coverage: sample 1 has nnz > 0 and a null index or value array'),
+    (dict(indices=(ctypes.c_void_p * 2)(None, None)), b'dn_assemble_coverage: sample 0 has nnz > 0 and a null index or value array'),
+    (dict(values=(ctypes.c_void_p * 2)(None, None)), b'dn_assemble_coverage: sample 0 has nnz > 0 and a null index or value array'),
+    (dict(lengths=np.array([6, -4], np.int64)), b'dn_assemble_coverage: length of gene 1 is negative'),
+    (dict(chunk_gene=np.array([0, 2, 1], np.int32)), b'dn_assemble_coverage: chunk 1 names a gene outside [0, n_genes)'),
+    (dict(chunk_gene=np.array([-1, 0, 1], np.int32)), b'dn_assemble_coverage: chunk 0 names a gene outside [0, n_genes)'),
+    (dict(chunk_len=np.array([3, 3, -1], np.int32)), b'dn_assemble_coverage: chunk 2 has a negative length'),
+    (dict(chunk_dst=np.array([0, -3, 0], np.int64)), b'dn_assemble_coverage: chunk 1 has a negative destination'),
+    (dict(chunk_dst=np.array([0, 4, 0], np.int64)), b'dn_assemble_coverage: chunk 1 ends beyond its gene'),
+    (dict(chunk_len=np.array([3, 3, 5], np.int32)), b'dn_assemble_coverage: chunk 2 ends beyond its gene'),
+    (dict(chunk_dst=np.array([0, 3, 2 ** 62], np.int64), chunk_len=np.array([3, 3, 2 ** 31 - 1], np.int32)),
+     b'dn_assemble_coverage: chunk 2 ends beyond its gene'),
+    (dict(lengths=np.array([5, 4], np.int64)), b'dn_assemble_coverage: chunk 1 ends beyond its gene'),
+]
+
+
+def test_assemble_coverage_refuses_a_bad_table_before_the_device():
+    for change, text in ASSEMBLE_REFUSALS:
+        assert _assemble(**change) == (_lib.DN_E_INVALID, text), sorted(change)
+
+
 def test_inflate_host_payload_outside_comp():
     lib = _lib.load()
     comp, out, status = np.zeros(8, np.uint8), np.zeros(16, np.uint8), np.zeros(1, np.int32)

@@ -113,8 +113,27 @@ def test_refusals_leave_the_handle_as_it_was(three_classes):
     rc = lib.dn_baseline_selection_f64(h, 2, p, ptrs, _ip(lengths), ctypes.byref(prm), None, _dp(rho), _ip(flags, ctypes.c_int32), None, None)
     _api_errors.refused(lib, rc, 'params.nmf_iter', live=(h, p))
 
+    # the test seam: refused for its arguments on this handle, for its state on one that holds no data set
+    _api_errors.refused(lib, lib.dn_debug_plant(h, 0, None), 'debug_plant.null', live=(h, p))
+    for which in (-1, 6):
+        _api_errors.refused(lib, lib.dn_debug_plant(h, which, rho.ctypes.data), 'debug_plant.which', live=(h, p))
+    _api_errors.refused(lib, lib.dn_debug_peek(h, 0, None), 'debug_peek.null', live=(h, p))
+    for which in (-1, 2):
+        _api_errors.refused(lib, lib.dn_debug_peek(h, which, rho.ctypes.data), 'debug_peek.which', live=(h, p))
+    empty = _lib.Device(0)
+    _api_errors.refused(lib, lib.dn_debug_plant(empty.h, 0, rho.ctypes.data), 'debug_plant.state', live=(h, p))
+    _api_errors.refused(lib, lib.dn_debug_peek(empty.h, 0, rho.ctypes.data), 'debug_peek.state', live=(h, p))
+    empty.close()
+
     _same(_run(dev), first)
     dev.close()
+
+
+def test_every_refusal_of_an_uploaded_or_empty_handle_is_made():
+    """The keys of the two tables that need a device all appear in this file (the host file holds the early ones)."""
+    text = open(__file__).read()
+    for key in list(_api_errors.UPLOADED) + list(_api_errors.EMPTY):
+        assert repr(key) in text, key
 
 
 def test_reuse_and_teardown_with_three_live_classes(three_classes):
