@@ -7,6 +7,8 @@
 
     python -m degnorm_amd --bam-dir DIR --create-bai -g genes.gtf -o out
     python -m degnorm_amd --bam-dir DIR --sort-bam -g genes.gtf -o out
+    python -m degnorm_amd --sam-files s1.sam s2.sam -g genes.gtf -o out
+    python -m degnorm_amd --sam-dir DIR -g genes.gtf -o out
 
 The flags and their validation follow the reference.  With --create-bai a .bam file without a .bai file next to it gets
 one before the run (the reference shells out to samtools for this; here degnorm_amd.bam.create_index builds it on the GPU);
@@ -14,7 +16,11 @@ without the flag a missing index is an error.  With --sort-bam every .bam file w
 an aligner's unsorted or name-collated output -- is first sorted by coordinate on the GPU (degnorm_amd.bam.sort_bam; the
 reference's documentation runs samtools sort for this) to <output directory>/sorted_bam/<the same file name>, indexed
 there, and read in place of the input; the sorted copies are kept, and files that say SO:coordinate are used as they are.
-Not offered: --plot-genes, the HTML report and the MPI command (see
+With --sam-files / --sam-dir the inputs are SAM text, what HISAT2, Bowtie2, BWA and (by default) STAR write: every X.sam is
+first converted on the GPU (degnorm_amd.bam.sam_to_bam; the reference's documentation runs samtools view -b for this) to
+<output directory>/converted_bam/X.bam and from there treated as a --sort-bam input: sorted to sorted_bam/ and indexed there
+when its header does not say SO:coordinate, indexed where it lies when it does.  No samtools step is left.
+Not offered: SAM output, gzip-compressed SAM, --plot-genes, the HTML report and the MPI command (see
 degnorm_amd.warm_start --mpi for the sharded NMF-OA run).
 """
 import argparse
@@ -31,7 +37,8 @@ def argparser():
         description='DegNorm (RNA-seq degradation normalization) from .bam and .gtf files on an AMD Instinct GPU.',
         epilog='Not available in this command: --plot-genes, the HTML summary report and the MPI command.  A .bam file must be '
                'sorted by coordinate and needs its .bai index file: --sort-bam sorts (and indexes) the files that are not sorted, '
-               '--create-bai makes the missing index files of sorted ones.')
+               '--create-bai makes the missing index files of sorted ones.  Alignments in SAM text need none of this: '
+               '--sam-files / --sam-dir convert, sort and index them.')
     ap.add_argument('--bam-files', nargs='+', default=None,
                     help='sorted .bam alignment files, one per sample (single-end or paired), at least two')
     ap.add_argument('--bai-files', nargs='+', default=None,
@@ -39,6 +46,12 @@ def argparser():
     ap.add_argument('--bam-dir', default=None,
                     help='directory whose .bam files (with .bai files of the same base name) are the input; '
                          'not together with --bam-files / --bai-files')
+    ap.add_argument('--sam-files', nargs='+', default=None,
+                    help='.sam alignment files (an aligner\'s text output), one per sample, at least two: each is converted on the '
+                         'GPU to <output directory>/converted_bam/<name>.bam, sorted to sorted_bam/ unless its header says '
+                         'SO:coordinate, and indexed; not together with --bam-files, --bam-dir, --bai-files or -w')
+    ap.add_argument('--sam-dir', default=None,
+                    help='directory whose .sam files are the input, as with --sam-files; not together with --sam-files')
     ap.add_argument('-w', '--warm-start-dir', default=None,
                     help='output directory of an earlier run: reuse its coverage matrices, read counts and gene table and '
                          'skip the alignment and annotation stages (.bam / .gtf arguments are then ignored)')
@@ -66,8 +79,8 @@ def argparser():
                          '<output directory>/sorted_bam/<same name>, index the sorted copy there and use it in place of the '
                          'input; the copies are kept (not with --bai-files)')
     ap.add_argument('--native-deflate', action='store_true',
-                    help='with --sort-bam: deflate the blocks of the sorted copies on the GPU with the library\'s own encoder '
-                         'instead of with zlib on the host')
+                    help='with --sort-bam, --sam-files or --sam-dir: deflate the blocks of the converted and sorted copies on the '
+                         'GPU with the library\'s own encoder instead of with zlib on the host')
     ap.add_argument('--device-inflate', action='store_true',
                     help='inflate the BGZF blocks of the .bam files on the GPU instead of with zlib on the host')
     ap.add_argument('--device-frame', action='store_true',
@@ -113,18 +126,50 @@ def _unsorted(bam_files):
     return [b for b in bam_files if sort_order(b) != 'coordinate']
 
 
+def _sam_inputs(args):
+    """The .sam files of --sam-files / --sam-dir, checked: a list of at least two existing files with unique base names."""
+    if args.bam_files or args.bam_dir or args.bai_files is not None or args.warm_start_dir:
+        raise ValueError('Do not specify --sam-files or --sam-dir together with --bam-files, --bam-dir, --bai-files or --warm-start-dir.')
+    if args.sam_files and args.sam_dir:
+        raise ValueError('Do not specify both --sam-files and --sam-dir. Use one input selection method or the other.')
+    if args.sam_dir:
+        if not os.path.isdir(args.sam_dir):
+            raise NotADirectoryError('Cannot find --sam-dir {0}'.format(args.sam_dir))
+        sam_files = [os.path.join(args.sam_dir, f) for f in sorted(os.listdir(args.sam_dir)) if f.endswith('.sam')]
+        if len(sam_files) < 2:
+            raise ValueError('Only found {0} .sam files within directory {1}'.format(len(sam_files), args.sam_dir))
+    else:
+        sam_files = list(args.sam_files)
+        for sam_file in sam_files:
+            if not sam_file.endswith('.sam'):
+                raise ValueError('{0} is not a .sam file.'.format(sam_file))
+            if not os.path.isfile(sam_file):
+                raise FileNotFoundError('Could not find .sam file {0}'.format(sam_file))
+    if len(sam_files) < 2:
+        raise ValueError('Fewer than 2 .sam files were found. Not sufficiently many to run DegNorm.')
+    if len(set(os.path.basename(f) for f in sam_files)) != len(sam_files):
+        raise ValueError('The .sam files are not uniquely named: their converted copies share one directory.')
+    return sam_files
+
+
 def validate_args(args):
     """The reference's checks on parsed arguments (utils.py:338-482); fills args.bam_files / args.bai_files, and
     args.create_bai_files with the .bam files whose index is to be made first (empty without args.create_bai) and
-    args.sort_bam_files with those that are to be sorted first (empty without args.sort_bam; their index file is None)."""
+    args.sort_bam_files with those that are to be sorted first (empty without args.sort_bam; their index file is None).
+    With --sam-files / --sam-dir args.sam_files is the checked list of .sam files and the .bam lists are empty: _run fills them
+    as it converts."""
     create = getattr(args, 'create_bai', False)
     sort = getattr(args, 'sort_bam', False)
     args.sort_bam_files = []
+    args.sam_files, args.sam_dir = getattr(args, 'sam_files', None), getattr(args, 'sam_dir', None)
+    sam = bool(args.sam_files or args.sam_dir)
     if sort and args.bai_files is not None:
         raise ValueError('Do not specify both --sort-bam and --bai-files: a sorted copy gets an index file of its own.')
-    if getattr(args, 'native_deflate', False) and not sort:
+    if getattr(args, 'native_deflate', False) and not sort and not sam:
         raise ValueError('Do not specify --native-deflate without --sort-bam: it chooses the encoder of the sorted copies.')
-    if (not args.bam_files and not args.bam_dir) and (not args.warm_start_dir):
+    if sam:
+        args.sam_files = _sam_inputs(args)
+    if (not args.bam_files and not args.bam_dir) and (not args.warm_start_dir) and not sam:
         raise ValueError('Must specify either --bam-files, --bam-dir, or --warm-start-dir as a data input option.')
     n_cpu = os.cpu_count() or 1
     if args.proc_per_node > n_cpu:
@@ -147,6 +192,9 @@ def validate_args(args):
     if not os.path.isfile(args.genome_annotation):
         raise FileNotFoundError('Gene annotation file {0} not found.'.format(args.genome_annotation))
     bam_files, bai_files, create_bai_files = [], [], []
+    if sam:
+        args.bam_files, args.bai_files, args.create_bai_files = [], [], []
+        return args
     if args.bam_dir:
         if args.bam_files is not None or args.bai_files is not None:
             raise ValueError('Do not specify both a --bam-dir and either --bam-files and/or --bai-files.'
@@ -216,6 +264,20 @@ def _run(args, output_dir, device, verify):
                             minimax_coverage=args.minimax_coverage)
     else:
         from .pipeline import run_pipeline
+        deflate = 'native' if getattr(args, 'native_deflate', False) else 'zlib'
+        for k, sam_file in enumerate(getattr(args, 'sam_files', None) or []):
+            from .bam import create_index, sam_to_bam, sort_order
+            converted_dir = os.path.join(output_dir, 'converted_bam')
+            os.makedirs(converted_dir, exist_ok=True)
+            logging.info('converting {0} to BAM -- {1} / {2}'.format(sam_file, k + 1, len(args.sam_files)))
+            bam_file = sam_to_bam(sam_file, os.path.join(converted_dir, os.path.basename(sam_file)[:-4] + '.bam'), device=device,
+                                  n_jobs=args.proc_per_node, deflate=deflate)
+            args.bam_files.append(bam_file)
+            if sort_order(bam_file) != 'coordinate':
+                args.bai_files.append(None)
+                args.sort_bam_files.append(bam_file)
+            else:
+                args.bai_files.append(create_index(bam_file, bai_from_bam_file(bam_file), device=device, verify=verify))
         for k, bam_file in enumerate(args.sort_bam_files):
             from .bam import create_index, sort_bam
             sorted_dir = os.path.join(output_dir, 'sorted_bam')
@@ -223,8 +285,7 @@ def _run(args, output_dir, device, verify):
             logging.info('sorting {0} by coordinate -- {1} / {2}'.format(bam_file, k + 1, len(args.sort_bam_files)))
             at = args.bam_files.index(bam_file)
             args.bam_files[at] = sort_bam(bam_file, os.path.join(sorted_dir, os.path.basename(bam_file)), device=device,
-                                          n_jobs=args.proc_per_node, verify=verify,
-                                          deflate='native' if getattr(args, 'native_deflate', False) else 'zlib')
+                                          n_jobs=args.proc_per_node, verify=verify, deflate=deflate)
             args.bai_files[at] = create_index(args.bam_files[at], bai_from_bam_file(args.bam_files[at]), device=device, verify=verify)
         run_pipeline(args.bam_files, args.bai_files, args.genome_annotation, output_dir, degnorm_iter=args.iter,
                      nmf_iter=args.nmf_iter, downsample_rate=args.downsample_rate, minimax_coverage=args.minimax_coverage,

@@ -172,6 +172,10 @@ def load(build_if_missing=False):
     lib.dn_gtf_scan.argtypes = [c.c_int, P(c.c_uint8), i64, i64, P(i64), P(i64), P(i64), P(i64), P(i32), P(u64), P(i64), P(i64),
                                 P(i64), P(i32), P(u64), P(i64), P(i32), P(dbl), P(dbl)]
     lib.dn_gtf_last_error.restype = c.c_char_p
+    sam_args = [P(u8), i64, i32, P(u64), P(i32), P(i64), P(i32), P(u8), i64, P(u8), i64, P(i64), i64, P(i64), i64, P(i64), P(i64), P(i64),
+                P(i64), P(i64), P(i32)]
+    lib.dn_sam_encode_host.argtypes = sam_args
+    lib.dn_sam_encode.argtypes = [c.c_int] + sam_args + [P(dbl), P(dbl)]
     lib.dn_outer_partials_device.argtypes = [vp, P(vp)]
     lib.dn_comm_unique_id.argtypes = [P(c.c_uint8)]
     lib.dn_comm_create.argtypes = [vp, P(c.c_uint8), i32, i32]

@@ -31,6 +31,11 @@ header that says SO:coordinate.  device=None does the same with zlib and the hos
 deflate='native' the blocks are written by the library's own DEFLATE encoder instead (csrc/dn_deflate.hip, bgzf_deflate): on the
 device the sorted stream is deflated where it lies, one block per wavefront, and only the blocks come back.
 
+An aligner's text output -- a .sam file -- becomes a BAM file by sam_to_bam (csrc/dn_sam.hip): the host copies the '@' header
+lines into the BAM header and hands the alignment lines over in windows cut at line ends; on the device one lane per line
+measures its record, a scan places it and one lane per line writes it; the host cuts, deflates and writes the blocks, records
+in input order.  device=None runs the host build of the same source; sam_records is the buffer-level call.
+
 Every path that inflates takes verify=True: the inflated bytes of each BGZF block are then compared with the CRC32 of its
 trailer -- zlib.crc32 where zlib inflates, the wavefront that inflates the block where the device does -- and a block that
 differs is a ValueError naming the file and the block's offset.  verify_bgzf checks a whole file that way (bgzip -t).
@@ -1511,4 +1516,270 @@ def sort_bam(src, dst, device=None, n_jobs=1, level=1, window_bytes=256 << 20, s
     if stats is not None:
         stats.update(t, frame_device_ms=frame_ms, sort_device_ms=sort_ms, gather_device_ms=gather_ms, frame_fixups=fix, records=n_rec,
                      bytes=n_bytes)
+    return dst
+
+
+# --- SAM text -----------------------------------------------------------------------------------------------------------------
+
+SAM_ERRORS = {1: 'empty line', 2: 'fewer than 11 tab-separated fields', 3: 'the read name is empty or longer than 254 bytes',
+              4: 'FLAG, POS, MAPQ, PNEXT or TLEN is not a decimal integer in its range',
+              5: 'RNAME or RNEXT names a reference the header has no @SQ line for', 6: 'malformed CIGAR',
+              7: 'more than 65535 CIGAR operations are not supported', 8: 'empty SEQ field',
+              9: "the CIGAR's query length differs from the length of SEQ", 10: 'QUAL is neither * nor as long as SEQ',
+              11: "QUAL byte outside '!' .. '~'", 12: 'malformed optional field', 13: 'optional integer out of range',
+              14: 'B array value outside the range of its type', 15: 'H field with an odd number of bytes',
+              16: 'optional float is not a decimal number'}
+SAM_WINDOW_MAX = 1 << 30         # text bytes dn_sam_encode takes at a time
+
+
+class SamLineError(ValueError):
+    """A malformed SAM alignment line: `line` (1-based, within the text that was encoded) and `what`."""
+
+    def __init__(self, line, what):
+        ValueError.__init__(self, 'line {0}: {1}'.format(line, what))
+        self.line, self.what = line, what
+
+
+def _fnv1a(name):
+    h = 0xcbf29ce484222325
+    for c in name:
+        h = ((h ^ c) * 0x100000001b3) & 0xffffffffffffffff
+    return h
+
+
+class _SamRefs(object):
+    """The reference table dn_sam_encode takes: the names of `refs` ([(name, length)] or names) sorted by their FNV-1a hash."""
+
+    def __init__(self, refs):
+        names = [(r if isinstance(r, (str, bytes)) else r[0]) for r in refs]
+        names = [n.encode('latin-1') if isinstance(n, str) else bytes(n) for n in names]
+        order = sorted(range(len(names)), key=lambda k: (_fnv1a(names[k]), k))
+        self.n = len(names)
+        self.hash = np.array([_fnv1a(names[k]) for k in order] + [0], np.uint64)
+        self.id = np.array(order + [0], np.int32)
+        self.len = np.array([len(names[k]) for k in order] + [0], np.int32)
+        self.beg = np.zeros(self.n + 1, np.int64)
+        np.cumsum(self.len[:self.n], out=self.beg[1:])
+        joined = b''.join(names[k] for k in order)
+        self.n_names = len(joined)
+        self.names = np.frombuffer(joined, dtype=np.uint8) if joined else np.zeros(1, np.uint8)
+
+    def args(self):
+        c = ctypes
+        return (self.n, _ptr(self.hash, c.c_uint64), _ptr(self.id, c.c_int32), _ptr(self.beg, c.c_int64), _ptr(self.len, c.c_int32),
+                _ptr(self.names, c.c_uint8), self.n_names)
+
+
+def _sam_encode(text, table, device, t):
+    """dn_sam_encode / dn_sam_encode_host on one window of alignment lines: (record stream as a uint8 array, int64 record offsets).
+    t, a dict, gains `lines`, `records`, `float_patches`, `copy_ms` and `encode_device_ms`.  SamLineError for a malformed line."""
+    n = len(text)
+    if n == 0:
+        return np.zeros(0, np.uint8), np.zeros(1, np.int64)
+    if n > SAM_WINDOW_MAX:
+        raise ValueError('a window of {0} bytes of SAM text is beyond {1}'.format(n, SAM_WINDOW_MAX))
+    a = np.frombuffer(text, dtype=np.uint8)
+    lines = text.count(b'\n') + 1
+    floats = text.count(b':f:') + (text.count(b',') if b':B:f' in text else 0)
+    c, i64 = ctypes, ctypes.c_int64
+    out, off, patch = np.zeros(2 * n + 36 * lines, np.uint8), np.zeros(lines + 1, np.int64), np.zeros(2 * floats + 2, np.int64)
+    n_lines, n_rec, n_out, n_patch, err_line, err_kind = i64(0), i64(0), i64(0), i64(0), i64(0), c.c_int32(0)
+    copy_ms, ms = c.c_double(0.0), c.c_double(0.0)
+    args = (_ptr(a, c.c_uint8), n) + table.args() + (_ptr(out, c.c_uint8), out.size, _ptr(off, i64), off.size, _ptr(patch, i64), floats,
+                                                     c.byref(n_lines), c.byref(n_rec), c.byref(n_out), c.byref(n_patch), c.byref(err_line),
+                                                     c.byref(err_kind))
+    lib = _lib.load()
+    if device is None:
+        _check(lib.dn_sam_encode_host(*args), 'dn_sam_encode_host')
+    else:
+        _check(lib.dn_sam_encode(int(device), *(args + (c.byref(copy_ms), c.byref(ms)))), 'dn_sam_encode')
+    t['lines'] = t.get('lines', 0) + int(n_lines.value)
+    t['copy_ms'] = t.get('copy_ms', 0.0) + float(copy_ms.value)
+    t['encode_device_ms'] = t.get('encode_device_ms', 0.0) + float(ms.value)
+    if err_kind.value:
+        raise SamLineError(int(err_line.value), SAM_ERRORS.get(int(err_kind.value), 'error {0}'.format(err_kind.value)))
+    t['records'] = t.get('records', 0) + int(n_rec.value)
+    t['float_patches'] = t.get('float_patches', 0) + int(n_patch.value)
+    return out[:int(n_out.value)], off[:int(n_rec.value) + 1]
+
+
+def sam_records(text, refs, device=None, stats=None):
+    """
+    The BAM records of SAM alignment lines: (record stream bytes, int64 offsets at which the records start, one more than
+    records: the last is the stream's size).  `text`: bytes of alignment lines, no '@' header lines, the last line with or
+    without its '\\n'; `refs`: the @SQ names in header order ([(name, length)] as read_header gives them, or names).  The
+    encoding is defined in include/degnorm_amd.h ("SAM text to BAM records"); csrc/dn_sam.hip encodes on GPU `device`, one lane
+    per line, or (device=None) its host build does, which needs no GPU; both give the same bytes.  The counterpart of
+    frame_records and inflate_blocks.  ValueError 'line <n>: <what>' names the first malformed line (1-based).  stats, a dict,
+    receives `lines`, `records`, `float_patches` (float payloads the host filled in with strtod), `copy_ms` and
+    `encode_device_ms` (0 on the host).
+    """
+    t = {}
+    try:
+        out, off = _sam_encode(bytes(text), _SamRefs(refs), device, t)
+    finally:
+        if stats is not None:
+            stats.update({'lines': 0, 'records': 0, 'float_patches': 0, 'copy_ms': 0.0, 'encode_device_ms': 0.0}, **t)
+    return out.tobytes(), off.copy()
+
+
+def sam_header(f, path):
+    """
+    Read the '@' header lines off the start of the open SAM file f: (header text as in the file, [(SN, LN)] of its @SQ lines
+    in order, number of header lines, the bytes read beyond the header).  ValueError for an @SQ line without SN or LN.
+    """
+    buf, pos, n_lines, refs, eof = b'', 0, 0, [], False
+    while True:
+        # the line at pos is whole, or the file at its end, before it is looked at
+        while not eof and (pos >= len(buf) or (buf[pos:pos + 1] == b'@' and buf.find(b'\n', pos) < 0)):
+            more = f.read(_CHUNK)
+            eof = not more
+            buf += more
+        if buf[pos:pos + 1] != b'@':
+            break
+        end = buf.find(b'\n', pos)
+        end = len(buf) if end < 0 else end + 1
+        n_lines += 1
+        fields = buf[pos:end].rstrip(b'\r\n').split(b'\t')
+        if fields[0] == b'@SQ':
+            tags = dict((x[:2], x[3:]) for x in fields[1:] if x[2:3] == b':')
+            for tag in (b'SN', b'LN'):
+                if tag not in tags:
+                    raise ValueError('{0}: line {1}: @SQ line without {2}'.format(path, n_lines, tag.decode()))
+            if not tags[b'LN'].isdigit() or int(tags[b'LN']) >= 2 ** 31:
+                raise ValueError('{0}: line {1}: @SQ line whose LN is not an integer below 2^31'.format(path, n_lines))
+            refs.append((tags[b'SN'].decode('latin-1'), int(tags[b'LN'])))
+        pos = end
+    return buf[:pos], refs, n_lines, buf[pos:]
+
+
+def _sam_windows(f, rest, window_bytes):
+    """Windows of about window_bytes of the open file f (after `rest`, bytes already read), each cut behind its last '\\n';
+    a window without one grows until it has one or the file ends."""
+    buf, eof = rest, False
+    while True:
+        while not eof and (len(buf) < window_bytes or buf.find(b'\n') < 0):
+            more = f.read(max(window_bytes - len(buf), 1 << 16))
+            eof = not more
+            buf += more
+        if not buf:
+            return
+        if eof and len(buf) <= window_bytes:
+            cut = len(buf)                            # the end of the file: the last line may lack its '\n'
+        else:
+            cut = buf.rfind(b'\n', 0, window_bytes) + 1
+            if cut == 0:                              # the first line is longer than a window: the window is that line
+                cut = buf.find(b'\n') + 1 or len(buf)
+        yield buf[:cut]
+        buf = buf[cut:]
+
+
+class _RecordStore(object):
+    """The record stream between the encoder and the block writer: windows are appended, ranges read in ascending order."""
+
+    def __init__(self):
+        self.lo, self.data = 0, bytearray()
+
+    def append(self, part):
+        self.data += part
+
+    def read(self, a, b):
+        if a > self.lo:
+            del self.data[:a - self.lo]
+            self.lo = a
+        return bytes(self.data[a - self.lo:b - self.lo])
+
+
+def sam_to_bam(src, dst, device=None, n_jobs=1, level=1, window_bytes=256 << 20, deflate='zlib', overwrite=False, stats=None):
+    """
+    Write the SAM file `src` as the BAM file `dst` (what `samtools view -b` is run for on an aligner's output); returns dst.
+    Records keep the order of the lines: nothing is sorted (sort_bam does that).
+
+    The '@' header lines are copied as they are into the BAM header, whose reference list is that of the @SQ lines in order
+    (an @SQ line without SN or LN, and a header without @SQ line, are ValueErrors).  The alignment lines go through the
+    encoder in windows of about window_bytes (at most 2^30), each cut behind its last line end: on GPU `device`
+    (csrc/dn_sam.hip: one lane per line measures its record, a scan places it, one lane per line writes it), or with
+    device=None by the host build of the same source, which needs no GPU.  The encoding is defined in
+    include/degnorm_amd.h.  Blocks hold at most 0xff00 bytes and end where a record ends (_block_cuts, as in sort_bam); they
+    are deflated by zlib at `level` in n_jobs threads, or with deflate='native' by the library's own encoder (bgzf_deflate)
+    on the same device (the host build with device=None).  An end-of-file block follows, and dst + '.tmp' becomes dst.
+    device=k and device=None write the same file.
+
+    A malformed line is ValueError('<src>: line <n>: <what>') with the 1-based line of the file, the first such line
+    winning and the text the same from both builds; neither dst nor dst + '.tmp' is left behind.  FileExistsError when dst
+    exists and overwrite is off.  stats, a dict, receives `windows`, `lines` (alignment lines), `records`, `bytes_in` (of
+    src), `record_bytes` (the record stream), `bytes_out` (of dst), `float_patches`, `copy_ms`, `encode_device_ms`, `read_s`,
+    `encode_s` and `deflate_s`.
+    """
+    if deflate not in ('zlib', 'native'):
+        raise ValueError("deflate must be 'zlib' or 'native', not {0!r}".format(deflate))
+    if os.path.exists(dst) and not overwrite:
+        raise FileExistsError('{0} exists; pass overwrite=True to replace it'.format(dst))
+    n_jobs, window_bytes = max(int(n_jobs), 1), min(max(int(window_bytes), 1), SAM_WINDOW_MAX)
+    tmp = dst + '.tmp'
+    t = {'windows': 0, 'lines': 0, 'records': 0, 'float_patches': 0, 'copy_ms': 0.0, 'encode_device_ms': 0.0, 'read_s': 0.0,
+         'encode_s': 0.0, 'deflate_s': 0.0, 'record_bytes': 0}
+    pool = ThreadPoolExecutor(n_jobs) if n_jobs > 1 and deflate == 'zlib' else None
+
+    def deflated(parts, dev):
+        t0 = time.perf_counter()
+        if deflate == 'native':
+            out = bgzf_deflate(parts, dev)
+        else:
+            one = lambda d: bgzf_compress(d, level)                              # noqa: E731
+            out = list(pool.map(one, parts) if pool is not None else map(one, parts))
+        t['deflate_s'] += time.perf_counter() - t0
+        return out
+
+    try:
+        with open(src, 'rb') as f:
+            t0 = time.perf_counter()
+            text, refs, n_head, rest = sam_header(f, src)
+            t['read_s'] += time.perf_counter() - t0
+            if not refs:
+                raise ValueError('{0}: no @SQ line in the header'.format(src))
+            table, store = _SamRefs(refs), _RecordStore()
+            header = b'BAM\x01' + struct.pack('<i', len(text)) + text + struct.pack('<i', len(refs))
+            for name, length in refs:
+                nm = name.encode('latin-1') + b'\x00'
+                header += struct.pack('<i', len(nm)) + nm + struct.pack('<i', length)
+
+            def end_chunks():
+                """The record ends of every window, as offsets into the whole stream; the window's records go to the store first."""
+                windows = _sam_windows(f, rest, window_bytes)
+                while True:
+                    t0 = time.perf_counter()
+                    win = next(windows, None)
+                    t['read_s'] += time.perf_counter() - t0
+                    if win is None:
+                        return
+                    before, t0 = n_head + t['lines'], time.perf_counter()
+                    try:
+                        rec, off = _sam_encode(win, table, device, t)
+                    except SamLineError as e:
+                        raise ValueError('{0}: line {1}: {2}'.format(src, before + e.line, e.what))
+                    t['encode_s'] += time.perf_counter() - t0
+                    t['windows'] += 1
+                    store.append(rec.tobytes())
+                    base, t['record_bytes'] = t['record_bytes'], t['record_bytes'] + len(rec)
+                    yield off[1:] + base
+
+            with open(tmp, 'wb') as out:
+                head_parts = [header[a:a + BGZF_BLOCK_DATA] for a in range(0, len(header), BGZF_BLOCK_DATA)]
+                out.writelines(deflated(head_parts, None))                   # by the host build, as in sort_bam: one file for every device
+                parts = (store.read(a, b) for a, b in _block_cuts(end_chunks()))
+                size = 64 * n_jobs if deflate == 'zlib' else 1024
+                for group in iter(lambda: list(itertools.islice(parts, size)), []):
+                    out.writelines(deflated(group, device))
+                out.write(BGZF_EOF)
+            t['bytes_in'] = f.seek(0, 2)
+        os.replace(tmp, dst)
+    finally:
+        if pool is not None:
+            pool.shutdown()
+        if os.path.exists(tmp):
+            os.remove(tmp)
+    t['bytes_out'] = os.path.getsize(dst)
+    if stats is not None:
+        stats.update(t)
     return dst

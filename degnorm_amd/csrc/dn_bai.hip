@@ -42,6 +42,7 @@ namespace {
 using dn::kUnplaced;
 using dn::le32;
 using dn::ref_key;
+using dn::reg2bin;
 
 constexpr int kNT = 256;
 constexpr int64_t kMaxCoord = (int64_t) 1 << 29;
@@ -84,18 +85,6 @@ struct Recs {
     uint64_t *hs, *hs_sum;                       // head flag | unmapped flag << 32, and its exclusive sum
     int32_t *cf, *cf_sum;                        // claim flag, and its exclusive sum
 };
-
-// SAM specification 5.3; 0 <= beg < end <= 2^29
-DN_HD uint32_t reg2bin(int64_t beg, int64_t end)
-{
-    --end;
-    if (beg >> 14 == end >> 14) return (uint32_t) (((1 << 15) - 1) / 7 + (beg >> 14));
-    if (beg >> 17 == end >> 17) return (uint32_t) (((1 << 12) - 1) / 7 + (beg >> 17));
-    if (beg >> 20 == end >> 20) return (uint32_t) (((1 << 9) - 1) / 7 + (beg >> 20));
-    if (beg >> 23 == end >> 23) return (uint32_t) (((1 << 6) - 1) / 7 + (beg >> 23));
-    if (beg >> 26 == end >> 26) return (uint32_t) (((1 << 3) - 1) / 7 + (beg >> 26));
-    return 0;
-}
 
 DN_HD uint64_t piece_voffset(const Piece *pc, int32_t n_pieces, int64_t o)
 {

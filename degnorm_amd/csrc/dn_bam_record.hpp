@@ -1,7 +1,8 @@
 // dn_bam_record.hpp -- what a BAM record is, for the units that read inflated records (dn_frame.hip, dn_reads.hip,
-// dn_bai.hip, dn_sort.hip): little-endian readers, the fixed part of a record as a view with its shape checks, the key
-// that sorts a refID, the launch grid of a per-record kernel -- and, for the index and the sort, the rule "the first
-// faulty record in file order wins" with the texts that name a record.
+// dn_bai.hip, dn_sort.hip) and the one that writes them (dn_sam.hip): little-endian readers, the fixed part of a record
+// as a view with its shape checks, the key that sorts a refID, the bin of a range, the launch grid of a per-record kernel
+// -- and, for the index and the sort, the rule "the first faulty record in file order wins" with the texts that name a
+// record.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -65,6 +66,19 @@ DN_HD bool bam_head(const uint8_t *w, int64_t n_bytes, int64_t o, BamHead &H)
 // The 32-bit value that orders references: refID -1 maps to the largest, so unplaced records sort last.
 constexpr uint32_t kUnplaced = 0xffffffffu;
 DN_HD uint32_t ref_key(int32_t ref) { return ref < 0 ? kUnplaced : (uint32_t) ref; }
+
+// The bin of [beg, end) on a reference (SAM specification 5.3).  The index (dn_bai.hip) calls it with 0 <= beg < end <= 2^29;
+// the SAM encoder (dn_sam.hip) with any beg >= -1: the shifts are arithmetic, so beg = -1, end = 0 gives 4680.
+DN_HD uint32_t reg2bin(int64_t beg, int64_t end)
+{
+    --end;
+    if (beg >> 14 == end >> 14) return (uint32_t) (((1 << 15) - 1) / 7 + (beg >> 14));
+    if (beg >> 17 == end >> 17) return (uint32_t) (((1 << 12) - 1) / 7 + (beg >> 17));
+    if (beg >> 20 == end >> 20) return (uint32_t) (((1 << 9) - 1) / 7 + (beg >> 20));
+    if (beg >> 23 == end >> 23) return (uint32_t) (((1 << 6) - 1) / 7 + (beg >> 23));
+    if (beg >> 26 == end >> 26) return (uint32_t) (((1 << 3) - 1) / 7 + (beg >> 26));
+    return 0;
+}
 
 // blocks of a grid-stride kernel that gives each block per_block of the n items, at most cap
 inline unsigned grid_for(int64_t n, int per_block, int64_t cap)

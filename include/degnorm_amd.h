@@ -606,6 +606,85 @@ int  dn_gtf_scan(int device, const uint8_t *buf, int64_t n_bytes, int64_t row_ca
                  double *copy_ms, double *device_ms);
 const char *dn_gtf_last_error(void);               /* = dn_last_error() */
 
+/* SAM text to BAM records (csrc/dn_sam.hip; degnorm_amd.bam.sam_records, sam_to_bam) -----------------------------------------
+ * What `samtools view -b` is run for: the alignment lines of a SAM file become BAM records, in input order.  text holds the
+ * n_bytes (1 .. 2^30) of a window of alignment lines -- no '@' header lines -- that ends at a line end.  A line ends at
+ * '\n' (a '\r' before it belongs to the line end) or at the end of the bytes; every line is one record, and an empty line
+ * is an error.  The references are the @SQ names of the header, handed over sorted by the 64-bit FNV-1a hash of the name:
+ * entry k has hash ref_hash[k] (ascending), refID ref_id[k] and the name names[ref_name_beg[k] .. + ref_name_len[k]).  The
+ * encoder hashes RNAME / RNEXT, searches the table and compares the bytes of every entry of that hash.
+ *
+ * The encoding.  A line is 11 mandatory fields and any number of optional ones, separated by single tabs:
+ *   QNAME   1 .. 254 bytes -> read_name with its NUL, l_read_name = length + 1.
+ *   FLAG    0 .. 65535.     MAPQ  0 .. 255.
+ *   RNAME   refID = the @SQ ordinal of the name; `*` is -1; a name the table does not have is an error.
+ *   POS     0 .. 2^31 - 1; pos = POS - 1, so POS 0 gives -1.        PNEXT  the same -> next_pos.
+ *   CIGAR   `*` is 0 ops; else <length><op> groups, op in MIDNSHP=X (codes 0 .. 8), length 0 .. 2^28 - 1, each stored as
+ *           length << 4 | code.  More than 65 535 ops is an error (not supported: no CG tag is written).
+ *   RNEXT   `=` is refID, `*` is -1, else as RNAME.                  TLEN   -2^31 .. 2^31 - 1.
+ *   SEQ     `*` gives l_seq 0; else one base a byte, code = index in `=ACMGRSVTWYHKDBN` in either letter case, any other
+ *           byte 15 (N); two codes a byte, the first in the high nibble, the spare low nibble of an odd length 0.  When
+ *           the CIGAR has ops and SEQ is not `*`, the lengths of its M I S = X ops must add up to l_seq.
+ *   QUAL    `*` gives l_seq bytes 0xFF; else l_seq bytes in '!' .. '~', each stored minus 33.
+ *   bin     the low 16 bits of reg2bin(pos, pos + max(1, sum of the lengths of the M D N = X ops)) of the SAM specification
+ *           5.3, with arithmetic shifts on signed values: pos = -1 without CIGAR gives 4680.
+ *   Integers are decimal digits, at most 18 of them, with a leading '-' where the range has negative values (and a
+ *   leading '+' in optional fields).  The fixed part is block_size, refID, pos, l_read_name, mapq, bin, n_cigar_op, flag,
+ *   l_seq, next_refID, next_pos, tlen; then read_name, the ops, the packed bases, the qualities and the optional fields.
+ *   Optional fields TAG:TYPE:VALUE -> the two tag bytes, a type byte and the value:
+ *     A   one byte.
+ *     i   the smallest type that holds the value, unsigned preferred: C up to 255, S up to 65 535, I up to 4 294 967 295;
+ *         c down to -128, s down to -32 768, i down to -2 147 483 648; a value outside is an error.
+ *     Z   the bytes (none is valid) and a NUL.          H   the same; an odd number of bytes is an error.
+ *     B   VALUE is a subtype t of cCsSiIf and then `,value` any number of times -> B, t, the count as int32, the values in
+ *         t's width; no value is valid; an integer outside t's range is an error.
+ *     f   and the values of B:f: (float) strtod(text) of text that is [+-] followed by inf, infinity, nan in any letter
+ *         case or by digits with at most one '.' and an optional exponent; other text is an error.
+ *   The size of a float payload does not depend on its value, so the device does not read decimals: the record stream
+ *   comes back with those four bytes zero and a patch table of (offset in the stream, offset in text) per payload, and the
+ *   host code fills them with strtod before the call returns -- dn_sam_encode_host does the same -- so both builds write
+ *   the same bytes.  patch[2 k], patch[2 k + 1] is entry k, in stream order, for callers who want to see it.
+ *
+ * Passes (device): line starts as in the GTF scan (newlines per 16 KiB tile, scan, scatter); measure, one lane per line
+ * (every check above, the record's size and float payloads; the first faulty line in file order wins, by atomicMin);
+ * exclusive sums of sizes and payload counts; emit, one lane per line, every record to its offset.  Device memory: the
+ * window padded to 16 KiB, the record stream (at most 2 n_bytes + 36 n_lines), 40 bytes a line and 16 a float payload.
+ * Outputs: out[0 .. *n_out) the record stream, rec_off[0 .. *n_rec] where every record starts (the last entry = *n_out),
+ * *n_lines = *n_rec on success.  out_cap = 2 n_bytes + 36 lines always suffices, rec_cap = lines + 1, patch_cap = entries
+ * the patch table can hold; a capacity that is too small is DN_E_INVALID, found after the measure pass and before anything
+ * is written.  On a malformed line the call still returns DN_OK: *err_kind is the DN_SAM_E_* of the first faulty line,
+ * *err_line its number within text (1-based), and no record comes back.  Within a line the fields are checked in their
+ * order, each one whole before the next is looked for, so a line that ends early is DN_SAM_E_FIELDS only when the fields it
+ * has are well-formed (a line without any tab is DN_SAM_E_FIELDS whatever it holds).  copy_ms / device_ms (nullable): the copy of text to the device, and the first kernel to the last,
+ * by HIP events.
+ *   dn_sam_encode_host    the host build of the same source, line after line; no device is touched.
+ * Errors: dn_last_error(). */
+#define DN_SAM_E_EMPTY      1   /* an empty line                                                                          */
+#define DN_SAM_E_FIELDS     2   /* fewer than 11 tab-separated fields                                                     */
+#define DN_SAM_E_NAME       3   /* a read name that is empty or longer than 254 bytes                                     */
+#define DN_SAM_E_INTEGER    4   /* FLAG, POS, MAPQ, PNEXT or TLEN is not a decimal integer in its range                   */
+#define DN_SAM_E_RNAME      5   /* RNAME or RNEXT names a reference the header does not have                              */
+#define DN_SAM_E_CIGAR      6   /* a CIGAR that is not <length><op> groups over MIDNSHP=X, or a length above 2^28 - 1     */
+#define DN_SAM_E_CIGAR_OPS  7   /* more than 65 535 CIGAR operations: not supported                                       */
+#define DN_SAM_E_SEQ        8   /* an empty SEQ field                                                                     */
+#define DN_SAM_E_SEQ_CIGAR  9   /* the CIGAR's query length is not the length of SEQ                                      */
+#define DN_SAM_E_QUAL_LEN  10   /* QUAL is neither `*` nor as long as SEQ                                                 */
+#define DN_SAM_E_QUAL      11   /* a QUAL byte outside '!' .. '~'                                                         */
+#define DN_SAM_E_TAG       12   /* an optional field that is not TAG:TYPE:VALUE with a known type and a well-formed value */
+#define DN_SAM_E_TAG_RANGE 13   /* an `i` value outside -2 147 483 648 .. 4 294 967 295                                   */
+#define DN_SAM_E_TAG_ARRAY 14   /* a B value outside the range of its subtype                                             */
+#define DN_SAM_E_TAG_HEX   15   /* an H value with an odd number of bytes                                                 */
+#define DN_SAM_E_TAG_FLOAT 16   /* an `f` or B:f value that is not a decimal number                                       */
+int  dn_sam_encode(int device, const uint8_t *text, int64_t n_bytes, int32_t n_ref, const uint64_t *ref_hash, const int32_t *ref_id,
+                   const int64_t *ref_name_beg, const int32_t *ref_name_len, const uint8_t *names, int64_t n_names, uint8_t *out,
+                   int64_t out_cap, int64_t *rec_off, int64_t rec_cap, int64_t *patch, int64_t patch_cap, int64_t *n_lines,
+                   int64_t *n_rec, int64_t *n_out, int64_t *n_patch, int64_t *err_line, int32_t *err_kind, double *copy_ms,
+                   double *device_ms);
+int  dn_sam_encode_host(const uint8_t *text, int64_t n_bytes, int32_t n_ref, const uint64_t *ref_hash, const int32_t *ref_id,
+                        const int64_t *ref_name_beg, const int32_t *ref_name_len, const uint8_t *names, int64_t n_names, uint8_t *out,
+                        int64_t out_cap, int64_t *rec_off, int64_t rec_cap, int64_t *patch, int64_t patch_cap, int64_t *n_lines,
+                        int64_t *n_rec, int64_t *n_out, int64_t *n_patch, int64_t *err_line, int32_t *err_kind);
+
 /* Measurement hooks (bench.py) -------------------------------------------------------------------- */
 /* Device time in ms of the most recent dn_baseline_iteration's main kernel, measured with HIP events
  * on the library's own stream; kernel name via dn_main_kernel_name().                               */
