@@ -26,6 +26,9 @@
 // a pointer (WideIterArgs / WideEstArgs), nmf_rows runs with R = ceil(p / 64) samples per lane (wave 0 of the 256-thread workgroup)
 // for the column counts whose instantiation needs no scratch in its body (rows_fit), nmf_gen does the rest, and the initial pass is
 // k_ratio_svd_wide at the end of this file.
+//
+// All four builds share one text of nmf_rows (R = 1 where p <= 64), one column dispatch (rows_call / nmf_by_rows) and one
+// k_baseline_gen; what differs per build sits behind cov_t, GenIterArgs / GenEstArgs, GP and two `if constexpr (DN_GEN_WIDE)`.
 #include <cstdio>
 #ifndef DN_GEN_NT
 #define DN_GEN_NT 256
@@ -255,127 +258,9 @@ constexpr int ROWS_ZSLOT = 255;               // last double of g_rows_tot, kept
 // NSM: compiled column count (2 .. 12: the Gram matrix and the solver's work shrink with it)
 // SAFE: the repeat of a call whose result shows samples decoupled from the top block (dn_kernels.hpp, warm_start_unsafe): every solve
 // block by block.  A separate instantiation -- inside the hot one the rare path cost 32 % (17.6 against 13.3 ms per launch on config 4)
-#if !DN_GEN_WIDE
-template <int NSM, bool SAFE = false>
-__device__ __attribute__((noinline)) void nmf_rows(const cov_t *Fb, double *rs, double *sv, double *sj,
-                                                   int n, int S, int T, int first_i, int p)
-{
-    constexpr int NGS = NSM * (NSM + 1) / 2;  // packed Gram entries: 10, 36, 78
-    const bool first = first_i != 0;
-    // arguments of a non-inlined function arrive in vector registers: as scalars the loop's tests (last iteration, cold solve, step
-    // cap) are scalar branches, not exec masks with a branch around either side
-    T = __builtin_amdgcn_readfirstlane(T);
-    n = __builtin_amdgcn_readfirstlane(n);
-    p = __builtin_amdgcn_readfirstlane(p);
-    if (wave_id() == 0) {
-        const int lane = lane_id();
-        const bool live = lane < p;
-        double *tot = g_rows_tot;
-        const double inv_s = live ? g_st.inv[lane] : 0.0;
-        double f[NSM], a[NSM], v[NSM];
-#pragma unroll
-        for (int j = 0; j < NSM; j++) {
-            const cov_t xv = (live && j < n) ? Fb[(size_t) lane * S + j] : (cov_t) 0;
-            f[j] = (double) xv * inv_s;
-            a[j] = f[j];                                                // lmbda = 0 (nmf.py:90)
-            v[j] = 0.0;
-        }
-        if (lane == 0) tot[ROWS_ZSLOT] = 0.0;
-        for (int e = lane; e < NGS; e += 64) {
-            bool diag = false;
-#pragma unroll
-            for (int i = 0; i < NSM; i++) diag = diag || (e == i * (i + 1) / 2 + i);
-            g_rows_dsel[e] = diag ? 1.0 : 0.0;
-        }
-        wave_fence();
-        const double c = 1.0 / sqrt((double) T);                        // nmf.py:91
-        Solver<NSM> sol;                                                // carried solver state (iterate, scale, shift)
-        double theta = 0.0;
-        int steps = 0, st = ST_OK;
-        bool noconv = false;
-        const int maxs = __builtin_amdgcn_readfirstlane(g_st.max_steps);
-#pragma clang loop unroll(disable)
-        for (int t = -1; t < T; t++) {                                  // t = -1: SVD of x itself (nmf.py:88)
-            if (__builtin_expect(t >= 0, 1)) {
-                double ts = 0.0;
-#pragma unroll
-                for (int j = 0; j < NSM; j++) ts = fma(a[j], v[j], ts);  // u_s sigma
-#pragma unroll
-                for (int j = 0; j < NSM; j++) {
-                    const double res = fma(ts, v[j], -f[j]);            // K E - x                       nmf.py:94
-                    a[j] = fmax(fma(-c, res, a[j]), f[j]);              // x + max(lambda - c res, 0)    nmf.py:95-97
-                }
-            }
-            double C[NGS];
-#pragma unroll
-            for (int i = 0; i < NSM; i++)
-#pragma unroll
-                for (int j = 0; j <= i; j++) C[i * (i + 1) / 2 + j] = a[i] * a[j];
-            // ceil(NGS / 64) reduce-scatter rounds; the lane that ends up with a diagonal entry subtracts the call's shift as it stores
-            // it (round 4: the shift is fixed after the cold solve -- the trace, its test and the read-modify-write of the diagonal
-            // with its two fences are the cold solve's alone; x + lambda >= x entry by entry, so a matrix that was not zero stays so)
-            wave_fence();
-            wave_round_store<NGS, 0, double>(C, tot, lane, t < 0 ? 0.0 : sol.shift(), g_rows_dsel, true);
-            wave_fence();
-            if (__builtin_expect(t < 0, 0)) {
-                double tr = 0.0;
-#pragma unroll
-                for (int i = 0; i < NSM; i++) tr += tot[i * (i + 1) / 2 + i];
-                if (!(tr > 0.0)) { st = ST_ARPACK; break; }
-                sol.cold(tr, v);
-            }
-            int r;
-            if constexpr (SAFE) {                                       // the safe repeat (k_baseline_gen decides): block by block, unshifted
-                r = solve_by_blocks<NSM>(sol, tot, ROWS_ZSLOT, v, theta, maxs, n);
-            } else r = sol.run(tot, ROWS_ZSLOT, v, theta, t == T - 1, maxs, t < 0);
-            steps += r;
-            noconv = noconv || r > maxs;
-            wave_fence();
-        }
-        if (st == ST_OK) {
-            const double sig = sqrt(theta);
-            double ts = 0.0;
-#pragma unroll
-            for (int j = 0; j < NSM; j++) ts = fma(a[j], v[j], ts);      // u_s sigma for the final state
-            double cs = 0.0, fs = 0.0, ssum = 0.0;
-            double r2[NSM];
-#pragma unroll
-            for (int j = 0; j < NSM; j++) {
-                const double ke = ts * v[j];                            // (K E)_sj
-                cs += ke < f[j] ? f[j] : ke;                            // nmf.py:318
-                fs += f[j];
-                ssum += v[j];
-                double d = ke - f[j];
-                if (!first) d = d < 0.0 ? 0.0 : d;
-                const double r = d / (f[j] + 1.0);                      // nmf.py:282
-                r2[j] = r * r;
-            }
-#pragma unroll
-            for (int j = 0; j < NSM; j++) {
-#pragma unroll
-                for (int o = 32; o >= 1; o >>= 1) r2[j] = fmax(r2[j], __shfl_xor(r2[j], o));
-            }
-#pragma unroll
-            for (int j = 0; j < NSM; j++) {
-                if (lane == j && j < n) {
-                    const double sk = sig * v[j];                       // s_k = (A^T u)_k
-                    sj[j] = sk;
-                    rs[j] = r2[j];
-                    if (first) sv[j] = sk;
-                }
-            }
-            if (live) { g_st.u[lane] = ts / sig; g_st.csum[lane] = cs; g_st.rsum[lane] = fs; }
-            if (lane == 0) { g_st.theta = theta; g_st.S = sig * ssum; }
-        }
-        if (st == ST_OK && noconv) st = ST_NO_CONVERGENCE;
-        if (lane == 0) { g_st.status = st; g_st.steps += steps; }
-    }
-    __syncthreads();
-}
-#else
-// The same routine for wide cohorts, a text of its own so that the builds for p <= 64 keep their code instruction for instruction.
-// R: samples per lane (wide cohorts, R = ceil(p / 64) = 2, 3, 4: sample 64 r + lane in slot r).  The lane's Gram products are summed
-// over its R rows before the reduce-scatter; the solver works on the n x n matrix and does not see R.
+// R: samples per lane, sample 64 r + lane in slot r: 1 in the builds for p <= 64, ceil(p / 64) = 2, 3, 4 for wide cohorts.  One text
+// for every build; at R = 1 the loops over r are single trips and the T loop compiles to what a text without R gives.  The lane's
+// Gram products are summed over its R rows before the reduce-scatter; the solver works on the n x n matrix and does not see R.
 template <int NSM, bool SAFE = false, int R = 1>
 __device__ __attribute__((noinline)) void nmf_rows(const cov_t *Fb, double *rs, double *sv, double *sj,
                                                    int n, int S, int T, int first_i, int p)
@@ -511,24 +396,26 @@ __device__ __attribute__((noinline)) void nmf_rows(const cov_t *Fb, double *rs, 
     }
     __syncthreads();
 }
-#endif
 
-#if DN_GEN_WIDE
-// Which instantiations of the widened nmf_rows exist: those whose body the compiler keeps in the 256 registers of a wave (two
-// workgroups per CU) with no scratch access between the entry's saves of callee-saved registers and their restores -- read from
-// the disassembly of a build with all of them (README, "Wide cohorts", has the table).  The others stay on nmf_gen.
-// tools/rows_fit_scan.py compiles all of them (-DDN_ROWS_FIT_ALL=1) and prints the table: run it after a compiler update.
+// Which instantiations of nmf_rows exist: every column count at R = 1; of the widened ones those whose body the compiler keeps in
+// the 256 registers of a wave (two workgroups per CU) with no scratch access between the entry's saves of callee-saved registers and
+// their restores -- read from the disassembly of a build with all of them (README, "Wide cohorts", has the table).  The others stay
+// on nmf_gen.  tools/rows_fit_scan.py compiles all of them (-DDN_ROWS_FIT_ALL=1) and prints the table: run it after a compiler update.
 template <int R, int NSM, bool SAFE> constexpr bool rows_fit()
 {
 #ifdef DN_ROWS_FIT_ALL
     return true;
 #endif
-    return R == 2 ? (SAFE ? NSM <= 10 : NSM != 9)
+    return R == 1 ? true
+         : R == 2 ? (SAFE ? NSM <= 10 : NSM != 9)
          : R == 3 ? (SAFE ? NSM <= 7 : NSM <= 6)
                   : NSM <= 5;
 }
 
-// nmf_rows<n, SAFE, R> for the run-time column count n <= NSM_MAX; false when that instantiation does not exist (nothing was done)
+// nmf_rows<n, SAFE, R> for the run-time column count n <= NSM_MAX (n < 2: the 2-column one); false when that instantiation does not
+// exist (nothing was done).  One instantiation per column count: the n x n Gram matrix has NSM (NSM + 1) / 2 entries to multiply and
+// reduce-scatter over the lanes every inner iteration (the bulk of the loop's ~1 000 instructions; at most 64 entries go in ONE
+// round) -- config 4's first calls have 9-10 columns.
 template <int R, bool SAFE>
 __device__ __forceinline__ bool rows_call(const cov_t *Fb, double *rs, double *sv, double *sj, int n, int S, int T, int first_i, int p)
 {
@@ -541,7 +428,44 @@ __device__ __forceinline__ bool rows_call(const cov_t *Fb, double *rs, double *s
     });
     return done;
 }
-#endif
+
+// One nmf() call by rows on an active matrix of at most NSM_MAX columns, if the instantiation for this cohort exists (R = 1 in the
+// builds for p <= 64: always; wide cohorts: R = ceil(p / 64), rows_fit); false when nothing was done and nmf_gen has to serve.
+template <bool SAFE>
+__device__ __forceinline__ bool nmf_by_rows(const cov_t *Fb, double *rs, double *sv, double *sj, int n, int S, int T, int first_i, int p)
+{
+    if constexpr (!DN_GEN_WIDE) {
+        rows_call<1, SAFE>(Fb, rs, sv, sj, n, S, T, first_i, p);
+        return true;                            // said outright: the compiler then drops the callers' way to nmf_gen for n <= NSM_MAX
+    } else {
+        const int Rw = (p + 63) >> 6;
+        return Rw == 2 ? rows_call<2, SAFE>(Fb, rs, sv, sj, n, S, T, first_i, p)
+             : Rw == 3 ? rows_call<3, SAFE>(Fb, rs, sv, sj, n, S, T, first_i, p)
+                       : rows_call<4, SAFE>(Fb, rs, sv, sj, n, S, T, first_i, p);
+    }
+}
+
+// After a call by rows: does its result ask for the safe repeat (dn_kernels.hpp, warm_start_unsafe)?  A covered sample whose component
+// of u is (nearly) zero is decoupled from the block the call ended on, a solve in its step cap is most likely two blocks racing.  The
+// same answer in every thread.  The two forms are not interchangeable: the ballot has one sample per lane and relies on every wave
+// seeing all p <= 64 samples; wide cohorts have one sample per thread of the workgroup and reduce through the barrier.
+__device__ __forceinline__ bool rows_unsafe(int p)
+{
+    if constexpr (DN_GEN_WIDE) {
+        const int tid = threadIdx.x;
+        const bool mine = g_st.status == ST_OK && tid < p && g_st.rsum[tid] > 0.0 && g_st.u[tid] < WARM_START_MIN_COMPONENT;
+        return __syncthreads_or(mine ? 1 : 0) != 0 || g_st.status == ST_NO_CONVERGENCE;
+    } else {
+        static_assert(DN_GEN_WIDE || GP <= 64, "the ballot sees one sample per lane");
+        bool unsafe = g_st.status == ST_NO_CONVERGENCE;
+        if (g_st.status == ST_OK) {
+            const int l = threadIdx.x & 63;
+            const bool mine = l < p && g_st.rsum[l] > 0.0 && g_st.u[l] < WARM_START_MIN_COMPONENT;
+            unsafe = __ballot(mine) != 0ull;
+        }
+        return unsafe;
+    }
+}
 
 __device__ __forceinline__ double st_max(const double *v, int p) { double m = v[0]; for (int i = 1; i < p; i++) m = v[i] > m ? v[i] : m; return m; }
 __device__ __forceinline__ double st_min(const double *v, int p) { double m = v[0]; for (int i = 1; i < p; i++) m = v[i] < m ? v[i] : m; return m; }
@@ -656,62 +580,14 @@ __global__ __launch_bounds__(NT, DN_GEN_MINW) void k_baseline_gen(GenIterArgs A)
                 int csize = 1, n_bins = 0;
                 bool first = true, in_loop = false;
                 for (;;) {
-                    // one instantiation per column count: the n x n Gram matrix has NSM (NSM + 1) / 2 entries to multiply
-                    // and reduce-scatter over the lanes every inner iteration (the bulk of the loop's ~1 000 instructions; at
-                    // most 64 entries go in ONE round) -- config 4's first calls have 9-10 columns
-#if DN_GEN_WIDE
-                    // at most 12 active columns: the one-wave routine with R = ceil(p / 64) samples per lane where that instantiation
-                    // keeps its state in registers (rows_fit), else -- and for wider matrices -- the block-wide nmf_gen
-                    const int Rw = (p + 63) >> 6;
-                    bool by_rows = false;
-                    if (n <= NSM_MAX) by_rows = Rw == 2 ? rows_call<2, false>(Fb, rs, sv, sj, n, S, A.T, first ? 1 : 0, p)
-                                              : Rw == 3 ? rows_call<3, false>(Fb, rs, sv, sj, n, S, A.T, first ? 1 : 0, p)
-                                                        : rows_call<4, false>(Fb, rs, sv, sj, n, S, A.T, first ? 1 : 0, p);
-                    if (!by_rows) nmf_gen(Fb, Ast, rs, sv, sj, n, S, A.T, first ? 1 : 0, p);
-                    else {
-                        // the safe repeat (dn_kernels.hpp, warm_start_unsafe), the test reduced over all p samples: thread i = sample i
-                        const bool mine = g_st.status == ST_OK && tid < p && g_st.rsum[tid] > 0.0 && g_st.u[tid] < WARM_START_MIN_COMPONENT;
-                        const bool unsafe = __syncthreads_or(mine ? 1 : 0) != 0 || g_st.status == ST_NO_CONVERGENCE;
-                        if (unsafe) {
-                            __syncthreads();
-                            const bool again = Rw == 2 ? rows_call<2, true>(Fb, rs, sv, sj, n, S, A.T, first ? 1 : 0, p)
-                                             : Rw == 3 ? rows_call<3, true>(Fb, rs, sv, sj, n, S, A.T, first ? 1 : 0, p)
-                                                       : rows_call<4, true>(Fb, rs, sv, sj, n, S, A.T, first ? 1 : 0, p);
-                            if (!again) nmf_gen(Fb, Ast, rs, sv, sj, n, S, A.T, first ? 1 : 0, p);      // no safe instantiation: every solve cold
-                        }
+                    // by rows where an instantiation exists, else -- and for wider matrices -- the block-wide nmf_gen
+                    if (n > NSM_MAX || !nmf_by_rows<false>(Fb, rs, sv, sj, n, S, A.T, first ? 1 : 0, p))
+                        nmf_gen(Fb, Ast, rs, sv, sj, n, S, A.T, first ? 1 : 0, p);
+                    else if (rows_unsafe(p)) {                          // the safe repeat
+                        __syncthreads();
+                        if (!nmf_by_rows<true>(Fb, rs, sv, sj, n, S, A.T, first ? 1 : 0, p))
+                            nmf_gen(Fb, Ast, rs, sv, sj, n, S, A.T, first ? 1 : 0, p);   // no safe instantiation (wide cohorts): every solve cold
                     }
-#else
-#define DN_ROWS_CASE(N) case N: nmf_rows<N>(Fb, rs, sv, sj, n, S, A.T, first ? 1 : 0, p); break;
-                    if (n <= NSM_MAX) {
-                        switch (n) {
-                            DN_ROWS_CASE(3) DN_ROWS_CASE(4) DN_ROWS_CASE(5) DN_ROWS_CASE(6) DN_ROWS_CASE(7) DN_ROWS_CASE(8)
-                            DN_ROWS_CASE(9) DN_ROWS_CASE(10) DN_ROWS_CASE(11) DN_ROWS_CASE(12)
-                            default: nmf_rows<2>(Fb, rs, sv, sj, n, S, A.T, first ? 1 : 0, p); break;
-                        }
-                    }
-#undef DN_ROWS_CASE
-                    else nmf_gen(Fb, Ast, rs, sv, sj, n, S, A.T, first ? 1 : 0, p);
-                    if (n <= NSM_MAX) {
-                        // the safe repeat (dn_kernels.hpp, warm_start_unsafe): a covered sample whose component of u is (nearly) zero is
-                        // decoupled from the block the call ended on, a solve in its step cap is most likely two blocks racing
-                        bool unsafe = g_st.status == ST_NO_CONVERGENCE;
-                        if (g_st.status == ST_OK) {                     // one sample per lane, one ballot (every wave sees all p <= 64 samples)
-                            const int l = threadIdx.x & 63;
-                            const bool mine = l < p && g_st.rsum[l] > 0.0 && g_st.u[l] < WARM_START_MIN_COMPONENT;
-                            unsafe = __ballot(mine) != 0ull;
-                        }
-                        if (unsafe) {
-                            __syncthreads();
-#define DN_ROWS_CASE(N) case N: nmf_rows<N, true>(Fb, rs, sv, sj, n, S, A.T, first ? 1 : 0, p); break;
-                            switch (n) {
-                                DN_ROWS_CASE(3) DN_ROWS_CASE(4) DN_ROWS_CASE(5) DN_ROWS_CASE(6) DN_ROWS_CASE(7) DN_ROWS_CASE(8)
-                                DN_ROWS_CASE(9) DN_ROWS_CASE(10) DN_ROWS_CASE(11) DN_ROWS_CASE(12)
-                                default: nmf_rows<2, true>(Fb, rs, sv, sj, n, S, A.T, first ? 1 : 0, p); break;
-                            }
-#undef DN_ROWS_CASE
-                        }
-                    }
-#endif
                     if (g_st.status != ST_OK) { status = g_st.status; break; }
                     n_calls++; sum_cols += n;
                     if (first) {
@@ -1948,10 +1824,7 @@ int blocks_per_cu_f64(int which)
 static int launch_baseline_ptr(const IterArgs &a, const double *d_scales, int grid, hipStream_t s)
 {
     WideIterArgs w;
-    w.cov = a.cov; w.goff = a.goff; w.glen = a.glen; w.order = a.order; w.counter = a.counter; w.ds_start = a.ds_start; w.rowmax = a.rowmax;
-    w.ws = a.ws; w.rho = a.rho; w.flags = a.flags; w.trace = a.trace; w.kfin = a.kfin; w.emode = a.emode; w.svec = a.svec; w.svoff = a.svoff;
-    w.slot_bytes = a.slot_bytes; w.n_genes = a.n_genes; w.S = a.S; w.T = a.T; w.bins = a.bins; w.min_hc = a.min_hc; w.rate = a.rate;
-    w.skip = a.skip; w.want_est = a.want_est; w.p = a.p; w.max_steps = a.max_steps;
+    static_cast<IterFields<float> &>(w) = a;       // every shared field
     w.scale = d_scales; w.inv_scale = d_scales + P_WIDE_MAX;
     hipLaunchKernelGGL(k_baseline_gen, dim3(grid), dim3(NT), 0, s, w);
     return (int) hipGetLastError();
@@ -1959,8 +1832,8 @@ static int launch_baseline_ptr(const IterArgs &a, const double *d_scales, int gr
 static void launch_est_ptr(const EstArgs &a, const double *d_scales, const int32_t *tg, const int32_t *tc, int n_tiles, hipStream_t s)
 {
     WideEstArgs w;
-    w.cov = a.cov; w.goff = a.goff; w.glen = a.glen; w.kfin = a.kfin; w.emode = a.emode; w.svec = a.svec; w.svoff = a.svoff;
-    w.out = a.out; w.ooff = a.ooff; w.n_genes = a.n_genes; w.p = a.p; w.scale = d_scales;
+    static_cast<EstFields<float> &>(w) = a;
+    w.scale = d_scales;
     hipLaunchKernelGGL(k_estimates_gen, dim3(n_tiles), dim3(256), 0, s, w, tg, tc);
 }
 static void launch_init(const InitArgs &a, int grid, hipStream_t s)
@@ -1979,14 +1852,17 @@ static int blocks_per_cu(int which)
 
 const KernelSet *kernel_set_wide()
 {
-    static const KernelSet ks = {
-        0, gen_wide::NT, nullptr, gen_wide::launch_init, nullptr, gen_wide::blocks_per_cu,
-        (size_t) 160 * 1024,               // no LDS tier
-        "gen_wide::k_baseline_gen",        // as rocprofv3 prints it (dn::gen_wide::k_baseline_gen)
-        gen_wide::WIDE_G_BYTES,            // the Gram matrix of the initial pass, at the tail of the slot
-        0, 1,
-        gen_wide::launch_baseline_ptr, gen_wide::launch_est_ptr, "gen_wide::k_ratio_svd_wide",
-    };
+    static const KernelSet ks = [] {
+        KernelSet k = {};                  // p = 0: run-time p; no register tier; no `baseline` / `est`: the scale factors travel by pointer
+        k.nt = gen_wide::NT; k.units = 1;
+        k.init = gen_wide::launch_init; k.blocks_per_cu = gen_wide::blocks_per_cu;
+        k.baseline_ptr = gen_wide::launch_baseline_ptr; k.est_ptr = gen_wide::launch_est_ptr;
+        k.static_lds_bytes = (size_t) 160 * 1024;          // no LDS tier
+        k.slot_extra_bytes = gen_wide::WIDE_G_BYTES;       // the Gram matrix of the initial pass, at the tail of the slot
+        k.baseline_name = "gen_wide::k_baseline_gen";      // as rocprofv3 prints them (dn::gen_wide::k_baseline_gen)
+        k.init_name = "gen_wide::k_ratio_svd_wide";
+        return k;
+    }();
     return &ks;
 }
 
@@ -2030,28 +1906,29 @@ static int blocks_per_cu(int which)
 }
 #endif
 
+// p = 0: run-time p; no register tier, scale factors by value
+static KernelSet float32_kernel_set(const char *baseline_name)
+{
+    KernelSet k = {};
+    k.nt = NT; k.units = 1;
+    k.baseline = launch_baseline; k.init = launch_init; k.est = launch_est; k.blocks_per_cu = blocks_per_cu;
+    k.static_lds_bytes = (size_t) 160 * 1024;              // no LDS tier: "static" covers the CU so that lds_cols comes out 0
+    k.baseline_name = baseline_name;                       // as rocprofv3 prints it, without the dn::
+    return k;
+}
+
 }  // namespace gen / gen_rows
 
 #if DN_GEN_NT == 256
 const KernelSet *kernel_set_generic()
 {
-    static const KernelSet ks = {
-        0, gen::NT, gen::launch_baseline, gen::launch_init, gen::launch_est, gen::blocks_per_cu,
-        (size_t) 160 * 1024,               // no LDS tier: "static" covers the CU so that lds_cols comes out 0
-        "gen::k_baseline_gen",          // as rocprofv3 prints it (dn::gen::k_baseline_gen)
-        0, 0, 1,
-    };
+    static const KernelSet ks = gen::float32_kernel_set("gen::k_baseline_gen");
     return &ks;
 }
 #else
 const KernelSet *kernel_set_rows()
 {
-    static const KernelSet ks = {
-        0, gen_rows::NT, gen_rows::launch_baseline, gen_rows::launch_init, gen_rows::launch_est, gen_rows::blocks_per_cu,
-        (size_t) 160 * 1024,
-        "gen_rows::k_baseline_gen",     // dn::gen_rows::k_baseline_gen
-        0, 0, 1,
-    };
+    static const KernelSet ks = gen_rows::float32_kernel_set("gen_rows::k_baseline_gen");
     return &ks;
 }
 #endif

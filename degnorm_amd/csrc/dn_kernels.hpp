@@ -23,6 +23,7 @@
 // (raw_units).  For p >= DN_MG_MIN_P the Gram matrix itself is accumulated on the matrix cores (mg_core).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <type_traits>
 #include "dn_reduce.hpp"
@@ -60,15 +61,19 @@ enum { EM_INPUT = 0,        // defaults: estimate = F                           
        EM_CLAMPED = 3,      // n0 == L, fallback: est = max(K_start E_start, F)          nmf.py:343-345, :350-352
        EM_RAW = 4 };        // n0 == L, no loop: est = K_start E_start                   nmf.py:251
 
-struct IterArgs {
-    const float   *cov;        // packed coverage, gene g at goff[g], p rows of glen[g]
+// Arguments of a baseline-selection iteration, the part every kernel family shares.  CovT is the coverage element type: float
+// (integer counts as uploaded) or double (the float64-input path).  The concrete types below add how the scale factors travel.
+template <typename CovT>
+struct IterFields {
+    const CovT    *cov;        // packed coverage, gene g at goff[g], p rows of glen[g]
     const int64_t *goff;
     const int32_t *glen;
     const int32_t *order;      // work queue: gene ids, longest first
     int32_t       *counter;    // queue head
     const int64_t *ds_start;   // per gene, or nullptr
-    const float   *rowmax;     // n x p: max_j x[i][j] of the raw coverage (k_row_max, once per upload)
-    const int32_t *x16;        // n: every count of the gene is a whole number <= 65535 (the register tier may pack them)
+    const CovT    *rowmax;     // n x p: max_j x[i][j] of the raw coverage (k_row_max / k_row_max_f64, once per upload)
+    const int32_t *x16;        // n: every count of the gene is a whole number <= 65535 (the register tier may pack them); read by
+                               // the templated kernels only (float64 input: nullptr)
     char          *ws;         // scratch: slots x slot_bytes
     double        *rho;        // n x p
     int32_t       *flags;      // n
@@ -80,13 +85,21 @@ struct IterArgs {
     int64_t        slot_bytes;
     int32_t        n_genes;
     int32_t        S;          // column stride of the scratch arrays (>= longest gene, multiple of 64)
-    int32_t        lds_cols;   // lambda columns held in LDS (dynamic shared memory = 8 * p * lds_cols bytes)
+    int32_t        lds_cols;   // lambda columns held in LDS (dynamic shared memory = 8 * p * lds_cols bytes; templated kernels only)
     int32_t        T, bins, min_hc, rate, skip, want_est;
     int32_t        p;          // samples (run-time copy; the templated kernels take it from the template)
     int32_t        max_steps;  // step cap of one eigen-solve (power-step equivalents); beyond it the gene gets ST_NO_CONVERGENCE
-    double         scale[P_MAX];
-    double         inv_scale[P_MAX];
 };
+
+struct IterArgs : IterFields<float> { double scale[P_MAX], inv_scale[P_MAX]; };       // p <= P_MAX: the scale factors by value
+
+// The float64-input path (dn_generic.hip compiled with DN_GEN_F64=1, namespace gen_f64; dn_nmf_f64 / dn_baseline_selection_f64):
+// float64 coverage and float64 row maxima.  Its own buffers, scale 1.
+struct IterArgsF64 : IterFields<double> { double scale[P_MAX], inv_scale[P_MAX]; };
+
+// The wide-cohort family (dn_generic.hip compiled with DN_GEN_WIDE=1, namespace gen_wide; 65 <= p <= P_WIDE_MAX): the scale factors
+// are read through a pointer -- 2 x 256 doubles by value would be 4 KiB of kernel arguments.
+struct WideIterArgs : IterFields<float> { const double *scale, *inv_scale; };      // p scale factors, p reciprocals (device)
 
 struct InitArgs {
     const float   *cov;
@@ -107,8 +120,10 @@ struct InitArgs {
     int32_t        force_fp64; // diagnostics (DN_INIT_FP64=1): keep the fp64 Gram pass also where the integer-exact one applies
 };
 
-struct EstArgs {
-    const float   *cov;
+// Arguments of the estimate kernels, shared part and concrete types as above.
+template <typename CovT>
+struct EstFields {
+    const CovT    *cov;
     const int64_t *goff;
     const int32_t *glen;
     const double  *kfin;
@@ -119,96 +134,23 @@ struct EstArgs {
     const int64_t *ooff;
     int32_t        n_genes;
     int32_t        p;
-    double         scale[P_MAX];
 };
+struct EstArgs : EstFields<float> { double scale[P_MAX]; };
+struct EstArgsF64 : EstFields<double> { double scale[P_MAX]; };
+struct WideEstArgs : EstFields<float> { const double *scale; };     // p scale factors (device)
 
-// The wide-cohort family (dn_generic.hip compiled with DN_GEN_WIDE=1, namespace gen_wide; 65 <= p <= P_WIDE_MAX): the fields of
-// IterArgs / EstArgs with the scale factors read through a pointer -- 2 x 256 doubles by value would be 4 KiB of kernel arguments.
-struct WideIterArgs {
-    const float   *cov;
-    const int64_t *goff;
-    const int32_t *glen;
-    const int32_t *order;
-    int32_t       *counter;
-    const int64_t *ds_start;
-    const float   *rowmax;
-    char          *ws;
-    double        *rho;
-    int32_t       *flags;
-    int32_t       *trace;
-    double        *kfin;
-    int32_t       *emode;
-    double        *svec;
-    const int64_t *svoff;
-    int64_t        slot_bytes;
-    int32_t        n_genes;
-    int32_t        S;
-    int32_t        T, bins, min_hc, rate, skip, want_est;
-    int32_t        p;
-    int32_t        max_steps;
-    const double  *scale;      // p scale factors (device)
-    const double  *inv_scale;  // p reciprocals (device)
-};
-
-struct WideEstArgs {
-    const float   *cov;
-    const int64_t *goff;
-    const int32_t *glen;
-    const double  *kfin;
-    const int32_t *emode;
-    const double  *svec;
-    const int64_t *svoff;
-    double        *out;
-    const int64_t *ooff;
-    int32_t        n_genes;
-    int32_t        p;
-    const double  *scale;      // p scale factors (device)
-};
-
-// The float64-input path (dn_generic.hip compiled with DN_GEN_F64=1, namespace gen_f64; dn_nmf_f64 / dn_baseline_selection_f64):
-// the same fields as IterArgs / EstArgs with float64 coverage and float64 row maxima (k_row_max_f64).  Its own buffers, scale 1.
-struct IterArgsF64 {
-    const double  *cov;
-    const int64_t *goff;
-    const int32_t *glen;
-    const int32_t *order;
-    int32_t       *counter;
-    const int64_t *ds_start;
-    const double  *rowmax;     // n x p: max_j F[i][j]
-    const int32_t *x16;        // unused (nullptr): no 16-bit packing of float64 input
-    char          *ws;
-    double        *rho;
-    int32_t       *flags;
-    int32_t       *trace;
-    double        *kfin;
-    int32_t       *emode;
-    double        *svec;
-    const int64_t *svoff;
-    int64_t        slot_bytes;
-    int32_t        n_genes;
-    int32_t        S;
-    int32_t        lds_cols;
-    int32_t        T, bins, min_hc, rate, skip, want_est;
-    int32_t        p;
-    int32_t        max_steps;
-    double         scale[P_MAX];
-    double         inv_scale[P_MAX];
-};
-
-struct EstArgsF64 {
-    const double  *cov;
-    const int64_t *goff;
-    const int32_t *glen;
-    const double  *kfin;
-    const int32_t *emode;
-    const double  *svec;
-    const int64_t *svoff;
-    double        *out;
-    const int64_t *ooff;
-    int32_t        n_genes;
-    int32_t        p;
-    double         scale[P_MAX];
-};
+// The templated kernels of dn_inst.hip and the launchers read these blocks as bytes: the layout is part of the contract.
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winvalid-offsetof"
+template <typename A> constexpr bool iter_layout_kept()
+{
+    return sizeof(A) == 1208 && offsetof(A, slot_bytes) == 128 && offsetof(A, p) == 172 && offsetof(A, scale) == 184 &&
+           offsetof(A, inv_scale) == 696;
+}
+template <typename A> constexpr bool est_layout_kept() { return sizeof(A) == 592 && offsetof(A, p) == 76 && offsetof(A, scale) == 80; }
+static_assert(iter_layout_kept<IterArgs>() && iter_layout_kept<IterArgsF64>(), "IterArgs / IterArgsF64: layout moved");
+static_assert(est_layout_kept<EstArgs>() && est_layout_kept<EstArgsF64>(), "EstArgs / EstArgsF64: layout moved");
+#pragma clang diagnostic pop
 
 // Bare factorisations of a batch of independent float64 matrices (k_nmf_f64): rank_one_approx (nmf.py:55-64, T = 0),
 // nmf() (:78-107, T iterations), ratio_svd (:109-121, T = 0, ratio = 1).
