@@ -34,7 +34,7 @@ from datetime import datetime
 def argparser():
     ap = argparse.ArgumentParser(
         prog='python -m degnorm_amd',
-        description='DegNorm (RNA-seq degradation normalization) from .bam and .gtf files on an AMD Instinct GPU.',
+        description='DegNorm (RNA-seq degradation normalization) from .bam and .gtf / .gff3 files on an AMD Instinct GPU.',
         epilog='Not available in this command: --plot-genes, the HTML summary report and the MPI command.  A .bam file must be '
                'sorted by coordinate and needs its .bai index file: --sort-bam sorts (and indexes) the files that are not sorted, '
                '--create-bai makes the missing index files of sorted ones.  Alignments in SAM text need none of this: '
@@ -54,9 +54,9 @@ def argparser():
                     help='directory whose .sam files are the input, as with --sam-files; not together with --sam-files')
     ap.add_argument('-w', '--warm-start-dir', default=None,
                     help='output directory of an earlier run: reuse its coverage matrices, read counts and gene table and '
-                         'skip the alignment and annotation stages (.bam / .gtf arguments are then ignored)')
+                         'skip the alignment and annotation stages (.bam / annotation arguments are then ignored)')
     ap.add_argument('-g', '--genome-annotation', type=str, default=None,
-                    help='.gtf annotation file; required unless -w is given')
+                    help='.gtf, .gff3 or .gff (read as GFF3) annotation file; required unless -w is given')
     ap.add_argument('-o', '--output-dir', type=str, default=None,
                     help='output directory: created when it does not exist; inside an existing directory, or without this '
                          'flag in the working directory, a degnorm_<mmddYYYY>_<HHMMSS> directory is created')

@@ -176,6 +176,12 @@ def load(build_if_missing=False):
                 P(i64), P(i64), P(i32)]
     lib.dn_sam_encode_host.argtypes = sam_args
     lib.dn_sam_encode.argtypes = [c.c_int] + sam_args + [P(dbl), P(dbl)]
+    gff3_cols = [P(i64), P(i64), P(i32), P(u64), P(i64), P(i64), P(i64), P(i32), P(u64)]
+    lib.dn_gff3_open.argtypes = [c.c_int, i64, i32, P(vp)]
+    lib.dn_gff3_window.argtypes = [vp, P(u8), i64, i64, P(i64), P(i64)] + gff3_cols + [P(u8), P(i64), P(i64), P(i32), P(dbl), P(dbl)]
+    lib.dn_gff3_resolve.argtypes = [vp, i64, P(i64), P(i64), P(i32), P(u64), P(i64), P(i32), P(u64), P(i64), P(i64), P(i32), P(dbl)]
+    lib.dn_gff3_close.argtypes = [vp]
+    lib.dn_gff3_scan_host.argtypes = [P(u8), i64, i32, i64, P(i64), P(i64)] + gff3_cols + [P(i64), P(i64), P(i64), P(i32)]
     lib.dn_outer_partials_device.argtypes = [vp, P(vp)]
     lib.dn_comm_unique_id.argtypes = [P(c.c_uint8)]
     lib.dn_comm_create.argtypes = [vp, P(c.c_uint8), i32, i32]

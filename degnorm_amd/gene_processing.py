@@ -1,5 +1,5 @@
 """
-Annotation processing (reference: `degnorm/gene_processing.py`): GeneAnnotationProcessor (:8-123) turns a .gtf file into
+Annotation processing (reference: `degnorm/gene_processing.py`): GeneAnnotationProcessor (:8-123) turns a .gtf or .gff3 file into
 the exon table the reads stage, the coverage merge and the result writer take, and get_gene_overlap_structure (:126-231)
 splits one chromosome's genes into overlap groups and isolated genes.
 
@@ -17,7 +17,7 @@ import logging
 
 import numpy as np
 
-from .loaders import GeneAnnotationLoader
+from .loaders import annotation_loader
 from .utils import subset_to_chrom
 
 
@@ -25,7 +25,7 @@ class GeneAnnotationProcessor(object):
 
     def __init__(self, annotation_file, chroms=None, verbose=True):
         """
-        :param annotation_file: str .gtf file
+        :param annotation_file: str .gtf, .gff3 or .gff file
         :param chroms: str or list of str chromosome names: subset the annotation to them
         :param verbose: bool write progress to the logger?
         """
@@ -38,8 +38,8 @@ class GeneAnnotationProcessor(object):
                 self.chroms = [self.chroms]
 
     def load(self):
-        """The exon rows of the file (GeneAnnotationLoader.get_data), subset to self.chroms when given."""
-        self.loader = GeneAnnotationLoader(self.filename)
+        """The exon rows of the file (the get_data of the loader its extension picks), subset to self.chroms when given."""
+        self.loader = annotation_loader(self.filename)
         return self._subset(self.loader.get_data())
 
     def _subset(self, exon_df):

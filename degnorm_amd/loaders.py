@@ -1,4 +1,7 @@
 """
+Annotation loaders on the device: GTF (GeneAnnotationLoader) and GFF3 (Gff3AnnotationLoader); `annotation_loader` picks one
+by the file's extension.
+
 GTF annotation loader on the device (reference: `degnorm/loaders.py:73-168`, GeneAnnotationLoader).
 
 The reference reads the nine columns with pandas, lower-cases the feature column and runs a regex per exon row.  Here the
@@ -16,6 +19,14 @@ removes every occurrence of the tag's text from the piece); start and end are 1 
 Two deliberate differences from the reference: lines that start with `#` and empty lines are skipped (the reference
 raises on them, so it refuses every Ensembl or GENCODE download), and `chr` is always the file's text (pandas' type
 inference turns a column of `01` into 1).  There is no CPU fallback: without a device `get_data` raises DegnormAmdError.
+
+GFF3 (`dn_gff3_*`, csrc/dn_gff3.hip; include/degnorm_amd.h, "GFF3 annotation scan", defines the rule): an exon line may name
+only its Parent, so the gene of an exon is a join over the whole file.  The file's text stays on the device for one load;
+every window gives its exon rows -- with the gene's name, or with the Parent still to resolve -- and leaves its node rows
+(the lines with an ID) on the device; `dn_gff3_resolve` then walks every pending exon up to its gene.  Spans are offsets in
+the file, so names are interned over a memory map of it.  Values are the file's bytes: no percent-decoding.  The same table
+comes out as for the GTF twin of the annotation, and like GTF the file loader has no CPU fallback (`gff3_scan` on a buffer has
+a host build, which the tests hold to a plain restatement of the rule).
 """
 import ctypes
 import os
@@ -30,6 +41,13 @@ _COMPARE_BYTES = 32 << 20           # bytes held at a time when the names of a h
 _KINDS = {1: 'must have the 9 mandatory .gtf columns.\nRead more at https://useast.ensembl.org/info/website/upload/gff.html',
           2: 'is an exon record without a usable gene_name or gene_id identifier tag.',
           3: 'is an exon record whose start or end is not an integer.'}
+_GFF3_KINDS = {1: 'must have the 9 mandatory .gff3 columns.\nRead more at https://github.com/The-Sequence-Ontology/Specifications/blob/master/gff3.md',
+               2: 'is an exon record without a usable gene_name, gene, Parent or gene_id attribute.',
+               3: 'is an exon record whose start or end is not an integer.',
+               4: 'is an exon record whose chain of Parent attributes names an ID that no record has.',
+               5: 'is an exon record whose chain of Parent attributes does not reach a gene within 8 records.'}
+_GFF3_COLS = (('line', np.int64), ('chr_beg', np.int64), ('chr_len', np.int32), ('chr_hash', np.uint64), ('start', np.int64),
+              ('end', np.int64), ('gene_beg', np.int64), ('gene_len', np.int32), ('gene_hash', np.uint64))
 
 
 class Loader(object):
@@ -195,3 +213,196 @@ class GeneAnnotationLoader(Loader):
         return DataFrame({'chr': np.array(chr_names, dtype=object)[chr_code[keep]] if chr_names else np.zeros(0, dtype=object),
                           'start': start[keep].astype(np.int64), 'end': end[keep].astype(np.int64),
                           'gene': np.array(gene_names, dtype=object)[gene_code[keep]] if gene_names else np.zeros(0, dtype=object)})
+
+
+def _gff3_col_args(cols):
+    return [_lib._p(cols[k], {np.int64: ctypes.c_int64, np.int32: ctypes.c_int32, np.uint64: ctypes.c_uint64}[t]) for k, t in _GFF3_COLS]
+
+
+class Gff3Scan(object):
+    """
+    One load of a GFF3 text of total_bytes on the device (dn_gff3_open ... dn_gff3_close): `window(buf)` for every piece of the
+    text in order, each ending at a line end, then `resolve()`; use as a context manager.  `pending` collects the exon rows that
+    named a Parent: (row index among all rows so far, line, parent span and hash).
+    """
+
+    def __init__(self, total_bytes, device=None, hash_bits=64):
+        self.lib = _lib.load()
+        self.h = ctypes.c_void_p(None)
+        dev = int(os.environ.get('LOCAL_RANK', 0)) if device is None else int(device)
+        _lib._check(self.lib.dn_gff3_open(dev, int(total_bytes), int(hash_bits), ctypes.byref(self.h)), 'dn_gff3_open')
+        self.lines, self.fasta_line, self.nodes = 0, 0, 0
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self):
+        if self.h:
+            self.lib.dn_gff3_close(self.h)
+            self.h = ctypes.c_void_p(None)
+
+    def window(self, buf):
+        """
+        dn_gff3_window on the next piece of the text: (dict of the exon rows' columns -- `line` 1-based in the file, spans as
+        offsets in the file, `pending` 1 where gene_* is a Parent still to resolve --, (error line, error kind) or None,
+        copy-in ms, device ms).  self.fasta_line becomes the line of `##FASTA` once a window held it: feed no more then.
+        """
+        a = np.frombuffer(buf, dtype=np.uint8)
+        cap = a.size // 20 + 1
+        cols = {k: np.empty(cap, dtype=t) for k, t in _GFF3_COLS}
+        pending = np.empty(cap, dtype=np.uint8)
+        i64 = ctypes.c_int64
+        n_lines, n_rows, fasta, err_line, err_kind = i64(0), i64(0), i64(0), i64(0), ctypes.c_int32(0)
+        copy_ms, dev_ms = ctypes.c_double(0.0), ctypes.c_double(0.0)
+        rc = self.lib.dn_gff3_window(self.h, _lib._p(a, ctypes.c_uint8), a.size, cap, ctypes.byref(n_lines), ctypes.byref(n_rows),
+                                     *(_gff3_col_args(cols) + [_lib._p(pending, ctypes.c_uint8), ctypes.byref(fasta), ctypes.byref(err_line),
+                                                               ctypes.byref(err_kind), ctypes.byref(copy_ms), ctypes.byref(dev_ms)]))
+        _lib._check(rc, 'dn_gff3_window')
+        n = int(n_rows.value)
+        self.lines += int(n_lines.value)
+        self.fasta_line = int(fasta.value)
+        cols = {k: v[:n] for k, v in cols.items()}
+        cols['pending'] = pending[:n]
+        err = (int(err_line.value), int(err_kind.value)) if err_kind.value else None
+        return cols, err, float(copy_ms.value), float(dev_ms.value)
+
+    def resolve(self, line, par_beg, par_len, par_hash):
+        """dn_gff3_resolve: (name_beg, name_len, name_hash of every pending row, (error line, kind) or None, ms)."""
+        n = int(line.size)
+        line, par_beg = np.ascontiguousarray(line, dtype=np.int64), np.ascontiguousarray(par_beg, dtype=np.int64)
+        par_len, par_hash = np.ascontiguousarray(par_len, dtype=np.int32), np.ascontiguousarray(par_hash, dtype=np.uint64)
+        out = np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int32), np.empty(n, dtype=np.uint64)
+        i64, i32, u64 = ctypes.c_int64, ctypes.c_int32, ctypes.c_uint64
+        n_nodes, err_line, err_kind, ms = i64(0), i64(0), i32(0), ctypes.c_double(0.0)
+        rc = self.lib.dn_gff3_resolve(self.h, n, _lib._p(line, i64), _lib._p(par_beg, i64), _lib._p(par_len, i32), _lib._p(par_hash, u64),
+                                      _lib._p(out[0], i64), _lib._p(out[1], i32), _lib._p(out[2], u64), ctypes.byref(n_nodes),
+                                      ctypes.byref(err_line), ctypes.byref(err_kind), ctypes.byref(ms))
+        _lib._check(rc, 'dn_gff3_resolve')
+        self.nodes = int(n_nodes.value)
+        err = (int(err_line.value), int(err_kind.value)) if err_kind.value else None
+        return out[0], out[1], out[2], err, float(ms.value)
+
+
+def _resolve_pending(scan, cols):
+    """The rows `cols` (all windows, concatenated) with the names of the pending ones filled in by scan.resolve: (error or
+    None, resolve ms, number of pending rows)."""
+    idx = np.flatnonzero(cols['pending'])
+    nb, nl, nh, err, ms = scan.resolve(cols['line'][idx], cols['gene_beg'][idx], cols['gene_len'][idx], cols['gene_hash'][idx])
+    if err is None:
+        cols['gene_beg'][idx], cols['gene_len'][idx], cols['gene_hash'][idx] = nb, nl, nh
+    return err, ms, int(idx.size)
+
+
+def gff3_scan(data, device=None, hash_bits=64, stats=None):
+    """
+    The GFF3 rule on the bytes of a whole annotation: (number of lines, dict of the exon rows' columns in file order -- `line`
+    1-based, `chr_beg`, `chr_len`, `chr_hash`, `start`, `end`, and `gene_beg`, `gene_len`, `gene_hash` of the resolved gene
+    name --, (error line, error kind) or None; with an error there are no rows).  device=None runs the host build
+    (dn_gff3_scan_host), a device index the device build as one window.  hash_bits masks the hashes of IDs and Parents in
+    both builds: with few bits many IDs share a hash, and the result must not change.  stats (dict): `nodes`, `walked_exons`.
+    """
+    a = np.frombuffer(data, dtype=np.uint8)
+    stats = {} if stats is None else stats
+    if a.size == 0:
+        stats.update(nodes=0, walked_exons=0)
+        return 0, {k: np.zeros(0, dtype=t) for k, t in _GFF3_COLS}, None
+    if device is None:
+        lib = _lib.load()
+        cap = a.size // 20 + 1
+        cols = {k: np.empty(cap, dtype=t) for k, t in _GFF3_COLS}
+        i64 = ctypes.c_int64
+        n_lines, n_rows, n_nodes, n_walked, err_line, err_kind = i64(0), i64(0), i64(0), i64(0), i64(0), ctypes.c_int32(0)
+        rc = lib.dn_gff3_scan_host(_lib._p(a, ctypes.c_uint8), a.size, int(hash_bits), cap, ctypes.byref(n_lines), ctypes.byref(n_rows),
+                                   *(_gff3_col_args(cols) + [ctypes.byref(n_nodes), ctypes.byref(n_walked), ctypes.byref(err_line),
+                                                             ctypes.byref(err_kind)]))
+        _lib._check(rc, 'dn_gff3_scan_host')
+        stats.update(nodes=int(n_nodes.value), walked_exons=int(n_walked.value))
+        err = (int(err_line.value), int(err_kind.value)) if err_kind.value else None
+        return int(n_lines.value), {k: v[:int(n_rows.value)] for k, v in cols.items()}, err
+    with Gff3Scan(a.size, device, hash_bits) as scan:
+        cols, err, _, _ = scan.window(a)
+        walked = 0
+        if err is None:
+            err, _, walked = _resolve_pending(scan, cols)
+        stats.update(nodes=scan.nodes, walked_exons=walked)
+        if err is not None:
+            cols = {k: v[:0] for k, v in cols.items()}
+        cols.pop('pending')
+        return scan.lines, cols, err
+
+
+class Gff3AnnotationLoader(GeneAnnotationLoader):
+
+    def __init__(self, to_load, window_bytes=None, device=None):
+        """
+        .gff3 / .gff file loader on the device (a .gff file is read as GFF3); the table of GeneAnnotationLoader.
+
+        :param to_load: str the realpath to a .gff3 file.
+        :param window_bytes: the file is uploaded and scanned in windows of about this many bytes, cut at line ends (default
+        WINDOW_BYTES); the table and the errors do not depend on it.
+        :param device: HIP device index (default: LOCAL_RANK or 0).
+        """
+        Loader.__init__(self, ['.gff3', '.gff'])
+        self.get_file(to_load)
+        self.window_bytes = max(int(WINDOW_BYTES if window_bytes is None else window_bytes), 1)
+        self.device = device
+        self.timing = {}
+
+    def _raise(self, err):
+        raise ValueError('File {0}, line {1} {2}'.format(self.filename, err[0], _GFF3_KINDS[err[1]]))
+
+    def exon_codes(self):
+        """As GeneAnnotationLoader.exon_codes.  The text stays on the device until every exon has its gene."""
+        t = self.timing = {'read_s': 0.0, 'copy_ms': 0.0, 'device_ms': 0.0, 'resolve_ms': 0.0, 'bytes': 0, 'lines': 0, 'nodes': 0,
+                           'walked_exons': 0}
+        size = os.path.getsize(self.filename)
+        empty = np.zeros(0, dtype=np.int64)
+        if size == 0:
+            return empty, empty, empty, empty, [], []
+        parts = []
+        with Gff3Scan(size, self.device) as scan:
+            t0 = time.perf_counter()
+            for win in iter_windows(self.filename, self.window_bytes):
+                t['read_s'] += time.perf_counter() - t0
+                cols, err, copy_ms, dev_ms = scan.window(win)
+                t['copy_ms'] += copy_ms
+                t['device_ms'] += dev_ms
+                t['bytes'] += len(win)
+                if err is not None:
+                    self._raise(err)
+                parts.append(cols)
+                t0 = time.perf_counter()
+                if scan.fasta_line:
+                    break
+            t['read_s'] += time.perf_counter() - t0
+            t['lines'] = scan.lines
+            cols = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]} if parts else None
+            if cols is None or cols['line'].size == 0:
+                return empty, empty, empty, empty, [], []
+            err, t['resolve_ms'], t['walked_exons'] = _resolve_pending(scan, cols)
+            t['nodes'] = scan.nodes
+            if err is not None:
+                self._raise(err)
+        a = np.memmap(self.filename, dtype=np.uint8, mode='r')
+        chr_table, gene_table = {}, {}
+        chr_code = intern_spans(a, cols['chr_beg'], cols['chr_len'].astype(np.int64), cols['chr_hash'], chr_table)
+        gene_code = intern_spans(a, cols['gene_beg'], cols['gene_len'].astype(np.int64), cols['gene_hash'], gene_table)
+        names = [[b.decode('utf-8', 'replace') for b in tab] for tab in (chr_table, gene_table)]
+        return chr_code, cols['start'], cols['end'], gene_code, names[0], names[1]
+
+
+ANNOTATION_LOADERS = (('.gtf', GeneAnnotationLoader), ('.gff3', Gff3AnnotationLoader), ('.gff', Gff3AnnotationLoader))
+
+
+def annotation_loader(path, **kw):
+    """The loader of an annotation file by its extension: .gtf -> GeneAnnotationLoader, .gff3 / .gff -> Gff3AnnotationLoader."""
+    if isinstance(path, str):
+        for ext, cls in ANNOTATION_LOADERS:
+            if path.endswith(ext):
+                return cls(path, **kw)
+    loader = Loader([ext for ext, _ in ANNOTATION_LOADERS])
+    loader.get_file(path)                            # raises: data type, file not found, or "does not end with"
+    raise ValueError('file {0} does not end with {1}'.format(path, ', '.join(loader.filetypes)))

@@ -1,11 +1,11 @@
 """
-DegNorm end to end from .bam and .gtf files (reference: `degnorm/__main__.py:56-286`).
+DegNorm end to end from .bam and .gtf or .gff3 files (reference: `degnorm/__main__.py:56-286`).
 
     prepare_inputs(bam_files, bai_files, genome_annotation, output_dir, ...)   everything up to the NMF-OA input
     run_pipeline(bam_files, bai_files, genome_annotation, output_dir, ...)     prepare_inputs, GeneNMFOA.run, save_results
 
 Every stage is the library's own: NativeBamReadsProcessor reads the alignments (no pysam), GeneAnnotationProcessor the
-annotation (device GTF scan), merge_coverage assembles the gene matrices on the device.  The output directory ends up as
+annotation (device GTF or GFF3 scan), merge_coverage assembles the gene matrices on the device.  The output directory ends up as
 the reference leaves it -- gene_exon_metadata.csv, read_counts.csv, <chr>/coverage_matrices_<chr>.pkl and the result
 files -- so warm_start.load_from_previous and `python -m degnorm_amd -w` accept it.
 """
@@ -91,7 +91,7 @@ def run_pipeline(bam_files, bai_files, genome_annotation, output_dir, degnorm_it
                  minimax_coverage=0, skip_baseline_selection=False, unique_alignment=True, n_jobs=1, verbose=True, device=None,
                  inflate='host', frame='host', verify=False, pair='host'):
     """
-    DegNorm on .bam files and a .gtf annotation, results written to output_dir (an existing directory).  verify: check every
+    DegNorm on .bam files and a .gtf or .gff3 annotation, results written to output_dir (an existing directory).  verify: check every
     BGZF block read against the CRC32 of its trailer (ValueError naming the file and the block).
 
     :return: (fitted GeneNMFOA, estimates, gene_cov_dict, read_count_df, genes_df, exon_df, sample_ids)

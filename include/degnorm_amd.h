@@ -685,6 +685,73 @@ int  dn_sam_encode_host(const uint8_t *text, int64_t n_bytes, int32_t n_ref, con
                         int64_t out_cap, int64_t *rec_off, int64_t rec_cap, int64_t *patch, int64_t patch_cap, int64_t *n_lines,
                         int64_t *n_rec, int64_t *n_out, int64_t *n_patch, int64_t *err_line, int32_t *err_kind);
 
+/* GFF3 annotation scan (csrc/dn_gff3.hip, csrc/dn_gff3.hpp; Gff3AnnotationLoader and gff3_scan, degnorm_amd/loaders.py) ---------
+ * The exon table of a GFF3 file: the GTF scan's output for the other annotation format.  In GFF3 an exon line may carry only
+ * `Parent=transcript:...`, the transcript line `Parent=gene:...`, and only the gene line the name: the gene of an exon is the
+ * result of a join over the whole file, with parents and children any distance apart and in either order.
+ *
+ * Lines, as in the GTF scan.  A line ends at '\n' or at the end of the bytes; a trailing '\r' is dropped.  Empty lines and
+ * lines whose first byte is '#' are skipped (`##gff-version 3`, `###`).  A line that is exactly `##FASTA` ends the annotation:
+ * that line and every line after it are ignored, with any error they would raise.  Every other line must hold at least eight
+ * tabs (DN_GFF3_E_FIELDS).
+ * Attributes: field nine, up to a further tab or the line's end.  It is split at ';', ASCII spaces are stripped from each
+ * piece, each piece is split at its first '=' into tag and value (a piece without '=' is a tag with an empty value), and
+ * spaces are stripped from both.  Tags compare exactly and case-sensitively (`gene` is not `gene_id`); the first piece with a
+ * tag wins, whether its value is empty or not.  Values are the file's bytes: there is NO percent-decoding (`%3B` stays `%3B`).
+ * `Parent` may be a comma-separated list: its first element, spaces stripped, is used, and an empty one counts as no Parent.
+ * Kinds of line.  An exon line has `exon` as its third field in any letter case; its fourth and fifth fields must be 1 .. 18
+ * decimal digits (DN_GFF3_E_INTEGER).  A node is any other line with a non-empty `ID`; it records its ID, its first parent or
+ * none, gname = the first non-empty of `gene_name` and `gene`, and rname = the first non-empty of `Name`, `gene_id` and the
+ * ID.  When several lines share an ID (legal for discontinuous features), the first in file order is the node.
+ * The gene of an exon line:
+ *   1  its own first non-empty of `gene_name` and `gene` (GENCODE and RefSeq files end here);
+ *   2  otherwise, with a Parent, the node of that ID is looked up, and at each node: gname if it has one; otherwise rname
+ *      if the node has no parent; otherwise on to the node's parent.  An ID no node has is DN_GFF3_E_PARENT; more than 8
+ *      lookups are DN_GFF3_E_DEPTH (which also ends cycles); both are reported at the exon's line;
+ *   3  otherwise, without a Parent, its own non-empty `gene_id`; failing that DN_GFF3_E_GENE.
+ * Errors.  Errors of a line itself (FIELDS, INTEGER, GENE) win over link errors (PARENT, DEPTH); within each class the
+ * smallest line number wins.  Neither the rows nor the error depend on how the file is cut into windows.
+ *
+ * One load.  dn_gff3_open checks the need (about 1.5 times the file and 64 MiB) against the free device memory before
+ * anything is uploaded -- a file that does not fit is DN_E_INVALID with a message -- and allocates one zeroed buffer of
+ * total_bytes padded to whole 16 KiB tiles, where the text stays until dn_gff3_close.  hash_bits (1 .. 64, normally 64) masks
+ * the hashes of IDs and Parents to that many bits, in both builds: a way for tests to fill the runs of equal hashes.
+ * dn_gff3_window takes the next n_bytes (1 .. 2^30) of the file, which end at a line end (only the last window may end without
+ * one): upload to their place, line starts (the GTF scan's three passes over the tiles the window touches), one lane per
+ * line (classify, parse, 64-bit FNV-1a hashes; first error and first `##FASTA` line by atomicMin), and two compactions in file
+ * order.  The exon rows come back as in dn_gtf_scan, with `line` 1-based in the file and spans as offsets in the file:
+ * pending[r] = 0, gene_* is the gene's name; pending[r] = 1, gene_* is the Parent to resolve and gene_hash its masked hash.
+ * Node rows stay on the device.  *fasta_line: the line of `##FASTA` when the window held it (0: not), after which no further
+ * window is taken.  On a malformed line the call returns DN_OK with *err_kind / *err_line (in the file) and no rows.
+ * dn_gff3_resolve takes the pending rows of all windows (line, Parent span and hash as dn_gff3_window gave them; spans outside
+ * the bytes uploaded are DN_E_INVALID): the node rows are sorted as (ID hash, ordinal) by a stable radix sort, and one lane
+ * per row walks: per lookup a lower-bound search on the hash, then a scan of that hash's run for the first node whose ID has
+ * the wanted length and bytes -- two IDs that share a hash stay apart, nothing is decided by a hash alone.  It returns the
+ * span and the full hash of every row's gene name, *n_nodes, or the first link error.  Every byte read lies below its
+ * line's end, the walk stops after 8 lookups and the run scan at the run's end: malformed input gives a status, nothing else.
+ *   dn_gff3_scan_host    the host build of the same source on a whole buffer, line after line, names resolved (row_cap:
+ *                        n_bytes / 20 + 1 suffices); *n_walked = the rows that named a Parent.  No device is touched.
+ * copy_ms / device_ms / resolve_ms (nullable): by HIP events.  Results are bit-identical from run to run.  Errors: dn_last_error(). */
+#define DN_GFF3_E_FIELDS   1   /* fewer than nine tab-separated fields                                                   */
+#define DN_GFF3_E_GENE     2   /* an exon line without gene_name, gene, Parent or gene_id                                */
+#define DN_GFF3_E_INTEGER  3   /* an exon line whose start or end is not a decimal integer                               */
+#define DN_GFF3_E_PARENT   4   /* an exon line whose chain of parents names an ID that no line has                       */
+#define DN_GFF3_E_DEPTH    5   /* an exon line whose chain of parents takes more than 8 lookups                          */
+typedef struct dn_gff3_ *dn_gff3;
+int  dn_gff3_open(int device, int64_t total_bytes, int32_t hash_bits, dn_gff3 *out);
+int  dn_gff3_window(dn_gff3 h, const uint8_t *bytes, int64_t n_bytes, int64_t row_cap, int64_t *n_lines, int64_t *n_rows,
+                    int64_t *line, int64_t *chr_beg, int32_t *chr_len, uint64_t *chr_hash, int64_t *start, int64_t *end,
+                    int64_t *gene_beg, int32_t *gene_len, uint64_t *gene_hash, uint8_t *pending, int64_t *fasta_line,
+                    int64_t *err_line, int32_t *err_kind, double *copy_ms, double *device_ms);
+int  dn_gff3_resolve(dn_gff3 h, int64_t n, const int64_t *line, const int64_t *par_beg, const int32_t *par_len, const uint64_t *par_hash,
+                     int64_t *name_beg, int32_t *name_len, uint64_t *name_hash, int64_t *n_nodes, int64_t *err_line, int32_t *err_kind,
+                     double *resolve_ms);
+int  dn_gff3_close(dn_gff3 h);
+int  dn_gff3_scan_host(const uint8_t *data, int64_t n_bytes, int32_t hash_bits, int64_t row_cap, int64_t *n_lines, int64_t *n_rows,
+                       int64_t *line, int64_t *chr_beg, int32_t *chr_len, uint64_t *chr_hash, int64_t *start, int64_t *end,
+                       int64_t *gene_beg, int32_t *gene_len, uint64_t *gene_hash, int64_t *n_nodes, int64_t *n_walked, int64_t *err_line,
+                       int32_t *err_kind);
+
 /* Measurement hooks (bench.py) -------------------------------------------------------------------- */
 /* Device time in ms of the most recent dn_baseline_iteration's main kernel, measured with HIP events
  * on the library's own stream; kernel name via dn_main_kernel_name().                               */
