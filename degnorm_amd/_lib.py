@@ -92,6 +92,9 @@ def load(build_if_missing=False):
     lib.dn_split_length.restype = i32
     lib.dn_class_lengths.argtypes = [vp, i32, i32, P(i32), P(i32)]
     lib.dn_class_tier_cols.argtypes = [vp, c.c_int, P(i32), P(i32)]
+    if hasattr(lib, 'dn_handdown'):        # absent from builds before hand-down (A/B runs load them through DN_LIB_PATH)
+        lib.dn_handdown.argtypes = [vp, c.c_int, P(i32), P(i32)]
+        lib.dn_handdown.restype = c.c_int
     lib.dn_tiny_length.argtypes = [vp]
     lib.dn_tiny_length.restype = i32
     lib.dn_class_kernel_ms.argtypes = [vp, c.c_int]
@@ -612,6 +615,12 @@ class Device:
 
     def tiny_length(self):
         return int(self.lib.dn_tiny_length(self.h))
+
+    def handdown(self, cls):
+        """(width at which class `cls` parks a gene for the next narrower class, genes it parked in the last baseline_iteration)."""
+        a, b = ctypes.c_int32(0), ctypes.c_int32(0)
+        _check(self.lib.dn_handdown(self.h, int(cls), ctypes.byref(a), ctypes.byref(b)))
+        return int(a.value), int(b.value)
 
     def class_kernel_ms(self, cls):
         return float(self.lib.dn_class_kernel_ms(self.h, int(cls)))

@@ -497,6 +497,7 @@ struct dn_handle_s {
     // (declared before `data`, so that the buffers are released first)
     dn::Stream stream[NCLS];
     dn::Event ev_start[NCLS], ev_end[NCLS];
+    dn::Event ev_mid[NCLS];          // end of a class's first launch (hand-down: the next class's second launch waits for it)
     dn::Event ev_ready, ev_i0, ev_i1;
     const dn::KernelSet *ks = nullptr;
 
@@ -518,6 +519,13 @@ struct dn_handle_s {
         const dn::KernelSet *ks = nullptr;
         int32_t n = 0;
         int32_t longest = 0;              // longest gene of the class
+        // Hand-down (see dn_baseline_iteration): genes of the next wider class, parked between two nmf() calls of their drop loop once
+        // they have shrunk to hand_cols columns, are finished by a second launch of this class
+        int32_t recv_longest = 0;         // longest gene this class may receive (0: it receives none); its slots hold that too
+        int32_t hand_cols = 0;            // THIS class parks a gene at that width: what the next class holds in registers + LDS (0: never)
+        dn::DeviceBuffer<int32_t> d_inq;  // continuation queue: gene ids of the donor class, in order of arrival; its length is d_counter[2],
+                                          // the head of the second launch d_counter[1]
+        int32_t parked = 0;               // genes this class parked in the most recent iteration
         dn::DeviceBuffer<int32_t> d_order;
         std::vector<int32_t> order;       // host copy of the work queue (gene ids)
         dn::DeviceBuffer<int32_t> d_counter;
@@ -545,6 +553,9 @@ struct dn_handle_s {
         dn::DeviceBuffer<double> d_svec;
         dn::DeviceBuffer<int64_t> d_svoff;
         dn::DeviceBuffer<float> d_rowmax;     // n x p row maxima of the raw coverage (k_row_max at upload)
+        dn::PinnedBuffer<int32_t> host_parked;   // per donor class: genes parked in the last iteration
+        dn::DeviceBuffer<int32_t> d_hand_int; // hand-down: the continuation records, n x HAND_INTS integers and
+        dn::DeviceBuffer<double> d_hand_dbl;  //   n x (5 p + 1) doubles (IterFields)
         dn::DeviceBuffer<int32_t> d_x16;      // n: 1 when every count of the gene is a whole number <= 65535 (packable into 16 bits)
         // outer-update state (dn_outer_begin): clipped / corrected DI, x_weighted, x_adj, ran_baseline_selection, partial sums
         dn::DeviceBuffer<double> d_rhoc, d_xw, d_xadj, d_part, d_pvec;
@@ -769,6 +780,7 @@ static int create_streams(dn_handle h)
         DN_TRY(h->stream[c].create(hipStreamCreateWithPriority, hipStreamNonBlocking, prio[c]));
         DN_TRY(h->ev_start[c].create(hipEventCreate));
         DN_TRY(h->ev_end[c].create(hipEventCreate));
+        DN_TRY(h->ev_mid[c].create(hipEventCreateWithFlags, hipEventDisableTiming));
     }
     DN_TRY(h->ev_ready.create(hipEventCreateWithFlags, hipEventDisableTiming));
     DN_TRY(h->ev_i0.create(hipEventCreate));
@@ -1054,6 +1066,9 @@ static int finish_upload(dn_handle h, const CoverageSource &src)
             if (n0 & 1) mixed.push_back(ord[0][n0 / 2]);
             ord[0] = mixed;
         }
+        // Hand-down between the classes of the templated kernels (DN_HANDDOWN=0: off)
+        const char *henv = getenv("DN_HANDDOWN");
+        const bool handdown = h->ks->p != 0 && !h->ks->baseline_ptr && !(henv && henv[0] == '0');
         for (int c = 0; c < dn_handle_s::NCLS; c++) {
             auto &C = h->data.cls[c];
             C.n = (int32_t) ord[c].size();
@@ -1065,9 +1080,33 @@ static int finish_upload(dn_handle h, const CoverageSource &src)
             // columns a scratch slot must hold: the longest gene of the class, or -- for the one-wave-per-gene family,
             // chosen because the announced take-every rate leaves every gene at most 12 active columns -- that bound
             int32_t cols = C.longest = h->glen[ord[c][0]];
+            C.recv_longest = 0; C.hand_cols = 0; C.parked = 0;
+            if (handdown && c > 0 && h->data.cls[c - 1].n > 0) {        // a class that receives holds the donor's longest gene too
+                C.recv_longest = h->data.cls[c - 1].longest;
+                DN_TRY(C.d_inq.alloc(sizeof(int32_t) * (size_t) h->data.cls[c - 1].n));
+                cols = std::max(cols, C.recv_longest);
+            }
             if (C.ks == dn::kernel_set_rows()) cols = (cols + h->ds_hint - 1) / h->ds_hint;
             const int rc = size_class(h, C, cols);
             if (rc != DN_OK) return rc;
+        }
+        {
+            // a class parks a gene once the next class would hold it on chip: that class's register tier + its LDS tier
+            // (DN_HANDDOWN_COLS=a,b overrides the wide and the narrow class's width)
+            int32_t over[2] = {-1, -1};
+            if (const char *cenv = getenv("DN_HANDDOWN_COLS")) (void) sscanf(cenv, "%d,%d", &over[0], &over[1]);
+            bool any = false;
+            for (int c = 0; c + 1 < dn_handle_s::NCLS; c++) {
+                const auto &R = h->data.cls[c + 1];
+                if (h->data.cls[c].n == 0 || R.n == 0 || h->ks->p == 0 || h->ks->baseline_ptr) continue;
+                h->data.cls[c].hand_cols = over[c] >= 0 ? over[c] : R.ks->reg_tier_cols + R.lds_cols;     // known also with hand-down off (diagnostic builds)
+                any = any || (R.recv_longest > 0 && h->data.cls[c].hand_cols > 0);
+            }
+            if (any) {
+                DN_TRY(h->data.host_parked.alloc(sizeof(int32_t) * dn_handle_s::NCLS));
+                DN_TRY(h->data.d_hand_int.alloc(sizeof(int32_t) * (size_t) n * dn::HAND_INTS));
+                DN_TRY(h->data.d_hand_dbl.alloc(sizeof(double) * (size_t) n * (size_t) (5 * p + 1)));
+            }
         }
         if (h->data.cls[0].n == 0 && (h->data.cls[1].n > 0 || h->data.cls[2].n > 0) && h->ks->p == 0) return fail(DN_E_STATE, "internal: empty wide class for the generic kernels");
         return DN_OK;
@@ -1220,7 +1259,7 @@ int dn_baseline_iteration(dn_handle h, const double *scale, const dn_params *prm
         const int32_t rate = prm->downsample_rate;
         for (auto &C : h->data.cls) {
             if (C.n == 0 || !C.ks) continue;
-            const int32_t longest = C.longest;
+            const int32_t longest = std::max(C.longest, C.recv_longest);
             const int32_t need = rate > 1 ? (longest + rate - 1) / rate : longest;
             if (need > C.S) {
                 DN_TRY(hipStreamSynchronize(h->stream[0]));
@@ -1274,6 +1313,10 @@ int dn_baseline_iteration(dn_handle h, const double *scale, const dn_params *prm
         for (auto &C : h->data.cls) if (C.n > 0) DN_TRY(hipMemsetAsync(C.d_counter, 0, sizeof(int32_t) * 4, h->stream[0]));
         DN_TRY(hipEventRecord(h->ev_ready, h->stream[0]));
         int first_cls = -1;
+        // hand-down needs the whole gene in the drop loop's own columns and no estimate state: off with want_estimates (the s_start
+        // vector stays in the donor's slot), with down-sampling, and when the record cannot hold the bin list
+        const bool hand_ok = h->data.d_hand_int && !prm->want_estimates && prm->downsample_rate <= 1 && prm->bins <= dn::HAND_MAX_BINS;
+        bool donor_parks = false, parked_from[dn_handle_s::NCLS] = {false, false, false};
         for (int c = 0; c < dn_handle_s::NCLS; c++) {
             auto &C = h->data.cls[c];
             C.last_ms = 0.f;
@@ -1283,13 +1326,36 @@ int dn_baseline_iteration(dn_handle h, const double *scale, const dn_params *prm
             if (c > 0) DN_TRY(hipStreamWaitEvent(st, h->ev_ready, 0));
             a.order = C.d_order; a.counter = C.d_counter; a.ws = C.d_ws; a.slot_bytes = C.slot_bytes; a.S = C.S;
             a.lds_cols = C.lds_cols; a.n_genes = C.n;
+            // Hand-down.  The first launch of a class parks the genes that its drop loop has shrunk to hand_cols columns into the next
+            // class's continuation queue; that class's SECOND launch, queued on its own stream behind its first and behind the end of
+            // this one (ev_mid), finishes them.  Every dependency sits at a kernel boundary: no workgroup waits for another kernel,
+            // and a second launch whose queue is empty ends at once.  One level per gene: a second launch parks nothing, so a wide
+            // gene never reaches the pair class.
+            C.parked = 0;
+            a.handdown_cols = C.hand_cols;
+            a.hand_int = h->data.d_hand_int; a.hand_dbl = h->data.d_hand_dbl;
+            a.park_queue = nullptr; a.park_count = nullptr; a.resume_queue = nullptr; a.resume_count = nullptr;
+            const bool parks = hand_ok && c + 1 < dn_handle_s::NCLS && C.hand_cols > 0 && h->data.cls[c + 1].recv_longest > 0 && h->data.cls[c + 1].n > 0;
+            if (parks) { a.park_queue = h->data.cls[c + 1].d_inq; a.park_count = h->data.cls[c + 1].d_counter + 2; }
             DN_TRY(hipEventRecord(h->ev_start[c], st));
             const int lrc = C.ks->baseline_ptr ? C.ks->baseline_ptr(a, h->data.d_scales, C.slots, st) : C.ks->baseline(a, C.slots, C.dyn_lds, st);
             if (lrc != 0) return fail(DN_E_HIP, std::string("k_baseline launch: ") + hipGetErrorString((hipError_t) lrc));
+            if (parks) DN_TRY(hipEventRecord(h->ev_mid[c], st));
+            if (c > 0 && donor_parks) {
+                DN_TRY(hipStreamWaitEvent(st, h->ev_mid[c - 1], 0));
+                a.park_queue = nullptr; a.park_count = nullptr;
+                a.counter = C.d_counter + 1; a.resume_queue = C.d_inq; a.resume_count = C.d_counter + 2;
+                const int lrc2 = C.ks->baseline(a, C.slots, C.dyn_lds, st);
+                if (lrc2 != 0) return fail(DN_E_HIP, std::string("k_baseline launch (continuations): ") + hipGetErrorString((hipError_t) lrc2));
+            }
             DN_TRY(hipEventRecord(h->ev_end[c], st));
+            parked_from[c] = c > 0 && donor_parks;
+            donor_parks = parks;
         }
         for (int c = 1; c < dn_handle_s::NCLS; c++)                                   // results are copied on the main stream
             if (h->data.cls[c].n > 0) DN_TRY(hipStreamWaitEvent(h->stream[0], h->ev_end[c], 0));
+        for (int c = 1; c < dn_handle_s::NCLS; c++)                                   // how many genes each donor parked (dn_handdown)
+            if (parked_from[c]) DN_TRY(hipMemcpyAsync(h->data.host_parked + (c - 1), h->data.cls[c].d_counter + 2, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream[0]));
         if (rho) {                          // null: the DI rows stay on the device (dn_outer_partials / dn_outer_apply / dn_fetch_outer)
             DN_TRY(hipMemcpyAsync(rho, h->data.d_rho, sizeof(double) * (size_t) h->n * h->p, hipMemcpyDeviceToHost, h->stream[0]));
             DN_TRY(hipMemcpyAsync(flags, h->data.d_flags, sizeof(int32_t) * (size_t) h->n, hipMemcpyDeviceToHost, h->stream[0]));
@@ -1311,6 +1377,7 @@ int dn_baseline_iteration(dn_handle h, const double *scale, const dn_params *prm
             DN_TRY(hipMemcpyAsync(h->data.host_trace, h->data.d_trace_head, sizeof(int32_t) * trace_ints, hipMemcpyDeviceToHost, h->stream[0]));
         }
         DN_TRY(hipStreamSynchronize(h->stream[0]));
+        for (int c = 1; c < dn_handle_s::NCLS; c++) if (parked_from[c]) h->data.cls[c - 1].parked = h->data.host_parked[c - 1];
         h->have_trace = (prm->downsample_rate <= 1);          // with down-sampling the active columns are redrawn every iteration
         if (trace) std::memcpy(trace, h->data.host_trace, sizeof(int32_t) * trace_ints);
         h->last_span_ms = 0.f;
@@ -1924,6 +1991,15 @@ const char *dn_main_kernel_name(dn_handle h) { return (h && h->ks) ? h->ks->base
 double dn_class_kernel_ms(dn_handle h, int cls) { return (h && cls >= 0 && cls < dn_handle_s::NCLS) ? (double) h->data.cls[cls].last_ms : 0.0; }
 const char *dn_class_kernel_name(dn_handle h, int cls) { return (h && cls >= 0 && cls < dn_handle_s::NCLS && h->data.cls[cls].ks && h->data.cls[cls].n > 0) ? h->data.cls[cls].ks->baseline_name : ""; }
 int32_t dn_tiny_length(dn_handle h) { return h ? h->tiny_len : 0; }
+
+int dn_handdown(dn_handle h, int cls, int32_t *cols, int32_t *parked)
+{
+    if (!h || !cols || !parked) return fail(DN_E_INVALID, "dn_handdown: null argument");
+    if (cls < 0 || cls >= dn_handle_s::NCLS) return fail(DN_E_INVALID, "dn_handdown: no such class");
+    *cols = h->data.cls[cls].hand_cols;
+    *parked = h->data.cls[cls].parked;
+    return DN_OK;
+}
 int dn_class_tier_cols(dn_handle h, int cls, int32_t *reg_cols, int32_t *lds_cols)
 {
     if (!h || cls < 0 || cls >= dn_handle_s::NCLS || !reg_cols || !lds_cols) return fail(DN_E_INVALID, "dn_class_tier_cols: bad argument");

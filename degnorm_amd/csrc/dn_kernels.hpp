@@ -89,7 +89,18 @@ struct IterFields {
     int32_t        T, bins, min_hc, rate, skip, want_est;
     int32_t        p;          // samples (run-time copy; the templated kernels take it from the template)
     int32_t        max_steps;  // step cap of one eigen-solve (power-step equivalents); beyond it the gene gets ST_NO_CONVERGENCE
+    // Hand-down (templated kernels; see k_baseline): a gene whose drop loop has shrunk it to at most handdown_cols columns is parked
+    // between two nmf() calls and finished by a later launch of the next narrower class.
+    int32_t        handdown_cols;   // register + LDS tier columns of the next narrower class (0: there is none)
+    int32_t       *hand_int;        // continuation records, one per gene: HAND_INTS integers and
+    double        *hand_dbl;        //   5 p + 1 doubles (rho, K, us, rho_fb, sumF, sig0)
+    int32_t       *park_queue;      // this launch parks genes: their ids, appended in order of arrival (nullptr: it parks nothing)
+    int32_t       *park_count;      //   and how many
+    const int32_t *resume_queue;    // this launch finishes parked genes: the queue it takes them from (nullptr: it walks `order`)
+    const int32_t *resume_count;    //   and its length, final before the launch starts
 };
+constexpr int HAND_MAX_BINS = 32;                 // bins of the drop loop a continuation record holds (alive[])
+constexpr int HAND_INTS = 16 + HAND_MAX_BINS;     // n0, n, csize, n_bins, n_calls, n_drops, sum_cols (2), flag, exit_code, loop_reason, emode, steps
 
 struct IterArgs : IterFields<float> { double scale[P_MAX], inv_scale[P_MAX]; };       // p <= P_MAX: the scale factors by value
 
@@ -144,8 +155,8 @@ struct WideEstArgs : EstFields<float> { const double *scale; };     // p scale f
 #pragma clang diagnostic ignored "-Winvalid-offsetof"
 template <typename A> constexpr bool iter_layout_kept()
 {
-    return sizeof(A) == 1208 && offsetof(A, slot_bytes) == 128 && offsetof(A, p) == 172 && offsetof(A, scale) == 184 &&
-           offsetof(A, inv_scale) == 696;
+    return sizeof(A) == 1256 && offsetof(A, slot_bytes) == 128 && offsetof(A, p) == 172 && offsetof(A, hand_int) == 184 &&
+           offsetof(A, scale) == 232 && offsetof(A, inv_scale) == 744;
 }
 template <typename A> constexpr bool est_layout_kept() { return sizeof(A) == 592 && offsetof(A, p) == 76 && offsetof(A, scale) == 80; }
 static_assert(iter_layout_kept<IterArgs>() && iter_layout_kept<IterArgsF64>(), "IterArgs / IterArgsF64: layout moved");
@@ -2113,6 +2124,31 @@ template <int P> __device__ __forceinline__ double lds_min(const double *v)
 #pragma unroll
   for (int i = 1; i < P; i++) { const double t = v[i]; m = t < m ? t : m; } return m; }
 
+// Columns kb .. n - 1 of the working copy Fb from the pristine Fs through the surviving bins (alive[], bins of csize columns),
+// four columns per thread in flight.  The caller orders it against the writers of alive[] and the readers of Fb.
+template <int P, int NT>
+__device__ __forceinline__ void rebuild_fb(const float *Fs, float *Fb, const int32_t *alive, int S, int csize, int n, int kb, int tid)
+{
+    for (int k0 = kb + tid; k0 < n; k0 += 4 * NT) {
+        float v[4][P];
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            const int k = (k0 + c * NT < n) ? k0 + c * NT : k0;
+            const int a = k / csize;
+            const int ko = alive[a] * csize + (k - a * csize);
+#pragma unroll
+            for (int i = 0; i < P; i++) v[c][i] = Fs[(size_t) i * S + ko];
+        }
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            if (k0 + c * NT < n) {
+#pragma unroll
+                for (int i = 0; i < P; i++) Fb[(size_t) (k0 + c * NT) * P + i] = v[c][i];
+            }
+        }
+    }
+}
+
 template <int P, int NT>
 __global__ __launch_bounds__(NT * DN_UNITS, DN_KERNEL_WAVES) void k_baseline(IterArgs A)
 {
@@ -2153,17 +2189,23 @@ __global__ __launch_bounds__(NT * DN_UNITS, DN_KERNEL_WAVES) void k_baseline(Ite
         dn_sync();
         const int q = sm.gene;
         dn_sync();
-        if (q >= A.n_genes) break;
-        const int g = A.order[q];
+        // Hand-down.  A launch with a resume queue finishes genes that the next wider class parked (below, at the top of the call loop):
+        // the queue was filled by a kernel that ended before this one started, so its length is final and a workgroup that finds it
+        // empty leaves at once.  Nothing here ever waits for another kernel.
+        const bool resume = A.resume_queue != nullptr;
+        if (q >= (resume ? *A.resume_count : A.n_genes)) break;
+        const int g = resume ? A.resume_queue[q] : A.order[q];
         const int L = A.glen[g];
         const float *x = A.cov + A.goff[g];
+        bool parked = false;
 
         int n0 = 0, n_calls = 0, n_drops = 0, exit_code = EXIT_LOW_COV, loop_reason = LOOP_NOT_ENTERED;
         int status = ST_OK, flag = 0, emode = EM_INPUT;
         long long sum_cols = 0;
 #ifdef DN_STAMP
         const long long t_gene0 = __builtin_amdgcn_s_memtime();
-        long long t_ret = 0, t_book = 0;
+        long long t_ret = 0, t_book = 0, t_hand = 0;
+        int n_hand = 0;
 #endif
         int32_t *tr = A.trace + (size_t) g * TRACE_LEN;
         if (tid < P) { gs.rho[tid] = 0.0; gs.K[tid] = 0.0; gs.us[tid] = 0.0; }
@@ -2252,17 +2294,62 @@ __global__ __launch_bounds__(NT * DN_UNITS, DN_KERNEL_WAVES) void k_baseline(Ite
 #endif
         int n = n0;                   // current width of Fb
         if (n0 >= A.min_hc) {
-            if (!(lds_min<P>(gs.sumF) > 0.0)) exit_code = EXIT_ZERO_SAMPLE;            // nmf.py:241
+            if (!resume && !(lds_min<P>(gs.sumF) > 0.0)) exit_code = EXIT_ZERO_SAMPLE;            // nmf.py:241 (a parked gene has passed it)
             else {
                 const double min_gene_len = fmax(2.0, ceil(200.0 * (1.0 / (double) rate)));   // nmf.py:261
                 const double min_bins = ceil((double) A.bins * 0.2);                         // nmf.py:35
                 int csize = 1, n_bins = 0;
                 bool first = true, in_loop = false;
+                if (resume) {
+                    // a parked gene: the scan above has refilled this slot's Fs (same row maxima, same scale factors, so the same columns);
+                    // the record puts the state machine back where the donor left it, between two calls of the drop loop.  sumF is carried,
+                    // not the scan's: this class adds it in another order, and rho_fb and the refinement must see the donor's bits
+                    const int32_t *ri = A.hand_int + (size_t) g * HAND_INTS;
+                    const double *rd = A.hand_dbl + (size_t) g * (5 * P + 1);
+                    n = ri[1]; csize = ri[2]; n_bins = ri[3]; n_calls = ri[4]; n_drops = ri[5];
+                    sum_cols = (long long) (((unsigned long long) (uint32_t) ri[7] << 32) | (unsigned long long) (uint32_t) ri[6]);
+                    flag = ri[8]; exit_code = ri[9]; loop_reason = ri[10]; emode = ri[11];
+                    if (tid < n_bins) sm.alive[tid] = ri[16 + tid];
+                    if (tid == 0) {
+                        gs.steps = ri[12];
+#pragma unroll
+                        for (int i = 0; i < P; i++) {
+                            gs.rho[i] = rd[i]; gs.K[i] = rd[P + i]; gs.us[i] = rd[2 * P + i]; gs.rho_fb[i] = rd[3 * P + i]; gs.sumF[i] = rd[4 * P + i];
+                        }
+                        gs.sig0 = rd[5 * P];
+                    }
+                    first = false; in_loop = true;
+                    dn_sync();
+                    rebuild_fb<P, NT>(Fs, Fb, sm.alive, S, csize, n, 0, tid);
+                    dn_sync();
+                }
                 // One nmf() call per trip: the first on F_start (nmf.py:245), the others inside the
                 // `while max(rho) > 0.1` loop of nmf.py:273-324 after a bin has been dropped.
                 for (;;) {
+                    if (A.park_queue != nullptr && !first && in_loop && n <= A.handdown_cols) {
+                        // the drop loop has shrunk the gene to what the next narrower class holds in registers and LDS: park it.  Every call
+                        // is a cold start from Fb, so no tier state travels -- only the state machine's variables and GeneState
+                        int32_t *ri = A.hand_int + (size_t) g * HAND_INTS;
+                        double *rd = A.hand_dbl + (size_t) g * (5 * P + 1);
+                        if (tid < n_bins) ri[16 + tid] = sm.alive[tid];
+                        if (tid == 0) {
+                            ri[0] = n0; ri[1] = n; ri[2] = csize; ri[3] = n_bins; ri[4] = n_calls; ri[5] = n_drops;
+                            ri[6] = (int32_t) (uint32_t) (unsigned long long) sum_cols; ri[7] = (int32_t) (uint32_t) ((unsigned long long) sum_cols >> 32);
+                            ri[8] = flag; ri[9] = exit_code; ri[10] = loop_reason; ri[11] = emode; ri[12] = gs.steps;
+#pragma unroll
+                            for (int i = 0; i < P; i++) {
+                                rd[i] = gs.rho[i]; rd[P + i] = gs.K[i]; rd[2 * P + i] = gs.us[i]; rd[3 * P + i] = gs.rho_fb[i]; rd[4 * P + i] = gs.sumF[i];
+                            }
+                            rd[5 * P] = gs.sig0;
+                            A.park_queue[atomicAdd(A.park_count, 1)] = g;
+                        }
+                        parked = true;
+                        break;
+                    }
 #ifdef DN_STAMP
                     if (t_ret != 0) t_book += __builtin_amdgcn_s_memtime() - t_ret;      // between two nmf() calls
+                    const long long t_call = __builtin_amdgcn_s_memtime();
+                    const bool hand = !first && in_loop && n <= A.handdown_cols;           // a drop-loop call the next narrower class holds on chip
 #endif
                     nmf_call<P, NT>(Fb, Lg, rs, sv, rtsave, n, S, nL, A.T, first ? 1 : 0, x16);       // results in gs (LDS)
                     if constexpr (P < DN_MG_MIN_P) {
@@ -2285,6 +2372,7 @@ __global__ __launch_bounds__(NT * DN_UNITS, DN_KERNEL_WAVES) void k_baseline(Ite
                     }
 #ifdef DN_STAMP
                     t_ret = __builtin_amdgcn_s_memtime();
+                    if (hand) { t_hand += t_ret - t_call; n_hand++; }
 #endif
                     if (gs.status != ST_OK) { status = gs.status; break; }
                     const double *u = gs.u, *sums = gs.sums;
@@ -2379,29 +2467,12 @@ __global__ __launch_bounds__(NT * DN_UNITS, DN_KERNEL_WAVES) void k_baseline(Ite
                     dn_sync();
                     // columns in front of the dropped bin keep their place; the others are fetched again from the pristine
                     // copy, four columns per thread in flight
-                    for (int k0 = kb + tid; k0 < n; k0 += 4 * NT) {
-                        float v[4][P];
-#pragma unroll
-                        for (int c = 0; c < 4; c++) {
-                            const int k = (k0 + c * NT < n) ? k0 + c * NT : k0;
-                            const int a = k / csize;
-                            const int ko = sm.alive[a] * csize + (k - a * csize);
-#pragma unroll
-                            for (int i = 0; i < P; i++) v[c][i] = Fs[(size_t) i * S + ko];
-                        }
-#pragma unroll
-                        for (int c = 0; c < 4; c++) {
-                            if (k0 + c * NT < n) {
-#pragma unroll
-                                for (int i = 0; i < P; i++) Fb[(size_t) (k0 + c * NT) * P + i] = v[c][i];
-                            }
-                        }
-                    }
+                    rebuild_fb<P, NT>(Fs, Fb, sm.alive, S, csize, n, kb, tid);
                     dn_sync();
                     if (n < 2) { loop_reason = LOOP_VALUE_ERROR; break; }                        // svds ValueError, nmf.py:306-310
                 }
 
-                if (in_loop && status == ST_OK) {
+                if (in_loop && status == ST_OK && !parked) {
                     bool fallback = false;
                     if (lds_max<P>(gs.rho) < 0.2) {                                              // nmf.py:327
                         double K[P];
@@ -2447,7 +2518,7 @@ __global__ __launch_bounds__(NT * DN_UNITS, DN_KERNEL_WAVES) void k_baseline(Ite
                     dn_sync();
                 }
                 // the re-expansion fix-up runs (and may raise) whenever the estimate is narrower than F  nmf.py:358-362
-                if (status == ST_OK && exit_code >= EXIT_NO_LOOP && n0 < L) {
+                if (status == ST_OK && exit_code >= EXIT_NO_LOOP && n0 < L && !parked) {
                     double K[P];
 #pragma unroll
                     for (int i = 0; i < P; i++) K[i] = gs.K[i];
@@ -2465,7 +2536,7 @@ __global__ __launch_bounds__(NT * DN_UNITS, DN_KERNEL_WAVES) void k_baseline(Ite
         const bool zero_out = (status != ST_OK) || exit_code <= EXIT_MEDIAN;
         if (zero_out) { emode = EM_INPUT; if (status != ST_OK) flag = 0; }
 
-        if (tid == 0) {
+        if (tid == 0 && !parked) {             // a parked gene's results are written by the class that finishes it
 #pragma unroll
             for (int i = 0; i < P; i++) {
                 A.rho[(size_t) g * P + i] = zero_out ? 0.0 : gs.rho[i];
@@ -2484,10 +2555,11 @@ __global__ __launch_bounds__(NT * DN_UNITS, DN_KERNEL_WAVES) void k_baseline(Ite
             tr[47] = (int32_t) ((t_scan1 - t_gene0) >> 10);
             tr[39] = (int32_t) (t_book >> 10);
             tr[38] = (int32_t) ((t_ret != 0 ? __builtin_amdgcn_s_memtime() - t_ret : 0) >> 10);
+            tr[35] = (int32_t) (t_hand >> 10); tr[34] = n_hand;     // drop-loop calls of at most A.handdown_cols columns: kilo-cycles, calls
             tr[36] = (int32_t) (gs.stamp[6] >> 10); tr[37] = (int32_t) gs.stamp[7];      // the partial register-tier body: pass kilo-cycles, column passes per lane
 #endif
         }
-        if (A.want_est && (emode == EM_CLAMPED || emode == EM_RAW)) {
+        if (A.want_est && !parked && (emode == EM_CLAMPED || emode == EM_RAW)) {
             double *dst = A.svec + A.svoff[g];
             for (int k = tid; k < n0; k += NT) dst[k] = sv[k];
         }

@@ -765,7 +765,7 @@ const char *dn_init_kernel_name(dn_handle h);
 /* Genes are run in up to three classes: class 0 = genes longer than dn_split_length() (256-thread workgroups, one per CU),
  * class 1 = the others (128-thread workgroups, two per CU), class 2 = genes of at most dn_tiny_length() bases (one wavefront
  * per gene, two genes per 128-thread workgroup; 0 when the class does not exist for this sample count); one kernel launch
- * per non-empty class and outer iteration. */
+ * per non-empty class and outer iteration, and a second one for a class that receives handed-down genes (dn_handdown). */
 int32_t dn_split_length(dn_handle h);
 /* The same two boundaries for ANY cohort of p samples before anything is uploaded (they depend on p and on the device's
  * register / LDS capacity, not on the data): what a host needs to deal genes to GPUs by predicted cost so that every GPU gets
@@ -780,6 +780,14 @@ const char *dn_class_kernel_name(dn_handle h, int cls);
  * the state; a gene with a count beyond 16 bits keeps more) and those of its LDS tile.  Active columns beyond their sum live in
  * the scratch slot (spill tier).  0 / 0 for an empty class. */
 int  dn_class_tier_cols(dn_handle h, int cls, int32_t *reg_cols, int32_t *lds_cols);
+/* Hand-down: a gene of class 0 or 1 whose drop loop has shrunk it to at most `cols` active columns -- what the next class keeps in
+ * registers and LDS; DN_HANDDOWN_COLS=a,b overrides the two widths -- is parked between two nmf() calls and finished by a second
+ * launch of the next class, queued behind the end of the donor's launch (one level per gene).  Off with DN_HANDDOWN=0 at the
+ * upload, for a launch with want_estimates or down-sampling, beyond 32 bins, and outside the templated kernels (p > 64, the
+ * run-time-p family): *cols is then the width it would use and *parked stays 0.  *parked: genes class `cls` parked in the most
+ * recent dn_baseline_iteration.  A handed-down gene's Gram sums are added in another lane order, so its DI agrees with the run
+ * without hand-down to rounding (1e-5 relative against the oracle), not to the bit; the trace counters are the same. */
+int  dn_handdown(dn_handle h, int cls, int32_t *cols, int32_t *parked);
 int  dn_synchronize(dn_handle h);
 /* Stream-copy ceiling of this device (GB/s, float4 copy of `bytes` bytes, best of `reps`).          */
 double dn_measure_copy_gbps(dn_handle h, int64_t bytes, int reps);

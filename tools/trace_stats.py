@@ -53,8 +53,19 @@ if tr[:, 36:38].any():
     part, rounds = tr[:, 36].astype(float).sum() * 1024, tr[:, 37].astype(float).sum()
     print('partial register-tier body: %.3f of pass cycles, %.3f of gene time; %.0f pass cycles per column pass per lane (%.3e column passes per lane)'
           % (part / (tr[:, 40].astype(float).sum() * 1024), part / (tr[:, 43].astype(float).sum() * 1024), part / max(rounds, 1), rounds))
+if tr[:, 34:36].any():
+    # drop-loop calls narrow enough for the next narrower class's register + LDS tiers (IterFields::handdown_cols): what handing
+    # such a gene down a class between two calls could move, per class as a share of the class's gene time
+    split, tiny = dev.split_length(), dev.tiny_length()
+    for c, m in enumerate((lengths > split, (lengths <= split) & (lengths > tiny), lengths <= tiny)):
+        if not m.any():
+            continue
+        hand, tot_c, tot = tr[m, 35].astype(float).sum(), tr[m, 43].astype(float).sum(), tr[:, 43].astype(float).sum()
+        print('class %d: %5d genes, %.3f of all gene time; drop-loop calls within the next class\'s on-chip capacity: %d calls in %d genes, '
+              '%.3f of the class\'s gene time, %.3f of all gene time' % (c, m.sum(), tot_c / tot, tr[m, 34].sum(), (tr[m, 34] > 0).sum(),
+                                                                       hand / max(tot_c, 1), hand / tot))
 if tr[:, 44:47].any():
-    ext = tr[:, 44:47].astype(float).sum(axis=0) * 1024
+    ext =tr[:, 44:47].astype(float).sum(axis=0) * 1024
     tot = tr[:, 43].astype(float).sum() * 1024
     inner = tr[:, 40:43].astype(float).sum() * 1024
     print('share of gene time: pass+reduce+eigen %.3f | nmf() calls %.3f (cold start %.3f, final pass %.3f, save/restore+rest %.3f) | outside nmf() %.3f'
