@@ -21,7 +21,9 @@ first converted on the GPU (degnorm_amd.bam.sam_to_bam; the reference's document
 <output directory>/converted_bam/X.bam and from there treated as a --sort-bam input: sorted to sorted_bam/ and indexed there
 when its header does not say SO:coordinate, indexed where it lies when it does.  No samtools step is left.
 Not offered: SAM output, gzip-compressed SAM, --plot-genes, the HTML report and the MPI command (see
-degnorm_amd.warm_start --mpi for the sharded NMF-OA run).
+degnorm_amd.warm_start --mpi for the sharded NMF-OA run).  Raw and estimated coverage curves of an output directory as text
+files: `python -m degnorm_amd.data_access -d OUTPUT_DIR -g GENE [GENE ...] | all -o SAVE_DIR` (the reference's
+get_coverage_data; its get_coverage_plots is not offered).
 """
 import argparse
 import logging
@@ -35,7 +37,8 @@ def argparser():
     ap = argparse.ArgumentParser(
         prog='python -m degnorm_amd',
         description='DegNorm (RNA-seq degradation normalization) from .bam and .gtf / .gff3 files on an AMD Instinct GPU.',
-        epilog='Not available in this command: --plot-genes, the HTML summary report and the MPI command.  A .bam file must be '
+        epilog='Not available in this command: --plot-genes, the HTML summary report and the MPI command; coverage curves of an output '
+               'directory are written as text by `python -m degnorm_amd.data_access` (plots are not offered).  A .bam file must be '
                'sorted by coordinate and needs its .bai index file: --sort-bam sorts (and indexes) the files that are not sorted, '
                '--create-bai makes the missing index files of sorted ones.  Alignments in SAM text need none of this: '
                '--sam-files / --sam-dir convert, sort and index them.')

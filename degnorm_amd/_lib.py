@@ -185,6 +185,15 @@ def load(build_if_missing=False):
     lib.dn_gff3_resolve.argtypes = [vp, i64, P(i64), P(i64), P(i32), P(u64), P(i64), P(i32), P(u64), P(i64), P(i64), P(i32), P(dbl)]
     lib.dn_gff3_close.argtypes = [vp]
     lib.dn_gff3_scan_host.argtypes = [P(u8), i64, i32, i64, P(i64), P(i64)] + gff3_cols + [P(i64), P(i64), P(i64), P(i32)]
+    text_args = [P(dbl), i64, i64, i32, P(i64), P(i64), P(i64), P(u8), P(vp)]
+    lib.dn_cov_text_host.argtypes = text_args
+    lib.dn_cov_text.argtypes = [c.c_int] + text_args + [P(dbl)]
+    lib.dn_text_bytes.argtypes = [vp]
+    lib.dn_text_bytes.restype = vp
+    lib.dn_text_size.argtypes = [vp]
+    lib.dn_text_size.restype = i64
+    lib.dn_text_free.argtypes = [vp]
+    lib.dn_text_free.restype = None
     lib.dn_outer_partials_device.argtypes = [vp, P(vp)]
     lib.dn_comm_unique_id.argtypes = [P(c.c_uint8)]
     lib.dn_comm_create.argtypes = [vp, P(c.c_uint8), i32, i32]

@@ -752,6 +752,50 @@ int  dn_gff3_scan_host(const uint8_t *data, int64_t n_bytes, int32_t hash_bits, 
                        int64_t *gene_beg, int32_t *gene_len, uint64_t *gene_hash, int64_t *n_nodes, int64_t *n_walked, int64_t *err_line,
                        int32_t *err_kind);
 
+/* Coverage matrices to text (csrc/dn_text.hip, csrc/dn_text.hpp; degnorm_amd.data_access.get_coverage_data, cov_text) ----------
+ * What `DataFrame(cov.T).to_csv(file, index=None, sep=' ', float_format='%.5f')` writes below its header line, for a batch of
+ * genes.  x holds n_x doubles; gene g is the p x len[g] row-major (sample-major) matrix at x + beg[g], as it lies in the
+ * pickles of an output directory.  Its piece of the text has len[g] lines, line j is x[0][j] x[1][j] ... x[p-1][j] -- so the
+ * call also transposes -- every value as '%.5f', values separated by single spaces, every line ended by '\n'.
+ *
+ * The rule, exact for every finite double with |x| < 2^63:
+ *   1  x is split into sign, 53-bit significand m and exponent e, |x| = m 2^e; a subnormal has e = -1074 and no hidden bit.
+ *   2  |x| 10^5 = (m 3125) 2^(e + 5), and m 3125 < 2^65 fits two 64-bit words.
+ *   3  For e + 5 >= 0 that integer, shifted left, is the result.
+ *   4  Otherwise it is shifted right by -(e + 5) -- the quotient is 0 for shifts of 66 and more -- and the bits shifted out
+ *      are compared with one half: round half to even.
+ *   5  The result q is printed as q / 100000, a point, and q % 100000 on five digits, with '-' in front when the sign bit is
+ *      set: -0.0 and -1e-9 both give -0.00000, as C does.
+ *   6  The code splits off the integer part of |x| first and scales only the fraction, so that everything but the product
+ *      stays in 64 bits (10^5 is even, so the fraction's q decides a tie, and a fraction that rounds up to 100000 carries
+ *      into the integer part).  Decimal digits come from divisions by constants, 32-bit ones below 10^9.
+ * A gene that holds a NaN, an infinity or a value with |x| >= 2^63 is not formatted: flag[g] = 1 and its piece is empty
+ * (pandas prints NaN as an empty field with quoting of its own; get_coverage_data writes such genes through pandas).
+ *
+ * Passes (device): the matrices are uploaded once; measure, one lane per line (the line's width, its gene by a search in
+ * the running sum of the lengths, the gene's flag); an exclusive sum over the n_lines + 1 widths, read as 0 for the lines
+ * of flagged genes; emit, one wavefront per 64 consecutive lines, whose text is one contiguous run: the lanes write their
+ * lines into an 8 KiB LDS chunk that stands for a 16-byte-aligned stretch of the output -- a run longer than that takes
+ * several trips, a value across a chunk's end is formatted on both sides -- and the wavefront copies the chunk out in
+ * 16-byte pieces, with byte stores only at the run's two ends.  Both walks are one routine with and without stores
+ * (dn::text::walk_line), so the second writes what the first measured, and no store leaves the measured size.  The text
+ * comes back into pinned memory of exactly the scanned size, owned by *text.
+ * Outputs: text_off[0 .. n_genes] where every gene's piece starts in the text (the last entry = dn_text_size), flag[0 ..
+ * n_genes), *text.  dn_text_bytes / dn_text_size give the text, dn_text_free releases it (null: nothing happens).
+ * Refused with DN_E_INVALID before any work: a null pointer, p < 2 or p > 4096, n_x < 1, n_genes < 1, a negative length, a
+ * gene that leaves x, two genes that overlap, more than 2^30 lines, and (dn_cov_text) a device index out of range.
+ * ms (nullable, 5 doubles, by HIP events): upload, measure, scan, emit, copy back.
+ *   dn_cov_text_host    the host build of the same source, line after line, into plain memory; no device is touched.
+ * Results are the same bytes from run to run and in both builds.  Errors: dn_last_error(). */
+typedef struct dn_text_ *dn_text;
+int  dn_cov_text(int device, const double *x, int64_t n_x, int64_t n_genes, int32_t p, const int64_t *beg, const int64_t *len,
+                 int64_t *text_off, uint8_t *flag, dn_text *text, double *ms);
+int  dn_cov_text_host(const double *x, int64_t n_x, int64_t n_genes, int32_t p, const int64_t *beg, const int64_t *len,
+                      int64_t *text_off, uint8_t *flag, dn_text *text);
+const uint8_t *dn_text_bytes(dn_text text);
+int64_t dn_text_size(dn_text text);
+void dn_text_free(dn_text text);
+
 /* Measurement hooks (bench.py) -------------------------------------------------------------------- */
 /* Device time in ms of the most recent dn_baseline_iteration's main kernel, measured with HIP events
  * on the library's own stream; kernel name via dn_main_kernel_name().                               */
