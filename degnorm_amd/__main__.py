@@ -12,8 +12,9 @@
 
 The flags and their validation follow the reference.  With --create-bai a .bam file without a .bai file next to it gets
 one before the run (the reference shells out to samtools for this; here degnorm_amd.bam.create_index builds it on the GPU);
-without the flag a missing index is an error.  With --sort-bam every .bam file whose header does not say SO:coordinate --
-an aligner's unsorted or name-collated output -- is first sorted by coordinate on the GPU (degnorm_amd.bam.sort_bam; the
+without the flag a missing index is an error.  A .bai index ends at position 2^29: --index-format csi has every index the
+command creates written as X.csi, and where X.bai is missing an X.csi or X.bam.csi that lies there is read.
+With --sort-bam every .bam file whose header does not say SO:coordinate -- an aligner's unsorted or name-collated output -- is first sorted by coordinate on the GPU (degnorm_amd.bam.sort_bam; the
 reference's documentation runs samtools sort for this) to <output directory>/sorted_bam/<the same file name>, indexed
 there, and read in place of the input; the sorted copies are kept, and files that say SO:coordinate are used as they are.
 With --sam-files / --sam-dir the inputs are SAM text, what HISAT2, Bowtie2, BWA and (by default) STAR write: every X.sam is
@@ -45,7 +46,8 @@ def argparser():
     ap.add_argument('--bam-files', nargs='+', default=None,
                     help='sorted .bam alignment files, one per sample (single-end or paired), at least two')
     ap.add_argument('--bai-files', nargs='+', default=None,
-                    help='.bai index files in the order of --bam-files; without this flag every X.bam needs X.bai next to it')
+                    help='.bai (or .csi) index files in the order of --bam-files; without this flag every X.bam needs X.bai (or, '
+                         'without one, X.csi or X.bam.csi) next to it')
     ap.add_argument('--bam-dir', default=None,
                     help='directory whose .bam files (with .bai files of the same base name) are the input; '
                          'not together with --bam-files / --bai-files')
@@ -77,6 +79,10 @@ def argparser():
     ap.add_argument('--create-bai', action='store_true',
                     help='create the .bai index file X.bai of every X.bam that has none next to it, on the GPU, before the run '
                          '(not with --bai-files)')
+    ap.add_argument('--index-format', choices=('bai', 'csi'), default='bai',
+                    help='the format of every index file this command creates (--create-bai, and the sorted copies of --sort-bam, '
+                         '--sam-files and --sam-dir): bai (the default), or csi, which a reference of more than 2^29 bases needs; '
+                         'X.csi is written in place of X.bai')
     ap.add_argument('--sort-bam', action='store_true',
                     help='sort every .bam file whose header does not say SO:coordinate by coordinate, on the GPU, to '
                          '<output directory>/sorted_bam/<same name>, index the sorted copy there and use it in place of the '
@@ -103,9 +109,10 @@ def bai_from_bam_file(bam_file):
     return bam_file[:-3] + 'bai'
 
 
-def _default_bai_files(bam_files, create=False, sort=()):
-    """(X.bai of every X.bam, the .bam files whose X.bai is missing); without `create` a missing one is an error.  The
-    files of `sort` are sorted and indexed later: their entry is None."""
+def _default_bai_files(bam_files, create=False, sort=(), fmt='bai'):
+    """(X.bai of every X.bam, the .bam files whose X.bai is missing); without `create` a missing one is an error.  Where
+    X.bai is missing, X.csi and then X.bam.csi are taken; an index that is created is X.<fmt>.  The files of `sort` are
+    sorted and indexed later: their entry is None."""
     bai_files, create_bai_files = [], []
     for bam_file in bam_files:
         if bam_file in sort:
@@ -113,11 +120,15 @@ def _default_bai_files(bam_files, create=False, sort=()):
             continue
         bai_file = re.sub('.bam$', '.bai', bam_file)
         if not os.path.isfile(bai_file):
+            csi_files = [f for f in (re.sub('.bam$', '.csi', bam_file), bam_file + '.csi') if os.path.isfile(f)]
+            if csi_files:
+                bai_files.append(csi_files[0])
+                continue
             if not create:
                 raise FileNotFoundError('No .bai index file {0} for {1}: pass --create-bai to have it made, index the .bam file '
                                         'first (e.g. samtools index), or name the index files with --bai-files.'
                                         .format(bai_from_bam_file(bam_file), bam_file))
-            bai_file = bai_from_bam_file(bam_file)
+            bai_file = bai_from_bam_file(bam_file)[:-3] + fmt
             create_bai_files.append(bam_file)
         bai_files.append(bai_file)
     return bai_files, create_bai_files
@@ -163,6 +174,7 @@ def validate_args(args):
     as it converts."""
     create = getattr(args, 'create_bai', False)
     sort = getattr(args, 'sort_bam', False)
+    fmt = args.index_format = getattr(args, 'index_format', 'bai')
     args.sort_bam_files = []
     args.sam_files, args.sam_dir = getattr(args, 'sam_files', None), getattr(args, 'sam_dir', None)
     sam = bool(args.sam_files or args.sam_dir)
@@ -207,7 +219,7 @@ def validate_args(args):
         bam_files = [os.path.join(args.bam_dir, f) for f in sorted(os.listdir(args.bam_dir)) if f.endswith('.bam')]
         if len(bam_files) < 2:
             raise ValueError('Only found {0} .bam files within directory {1}'.format(len(bam_files), args.bam_dir))
-        bai_files, create_bai_files = _default_bai_files(bam_files, create, _unsorted(bam_files) if sort else ())
+        bai_files, create_bai_files = _default_bai_files(bam_files, create, _unsorted(bam_files) if sort else (), fmt)
     else:
         for bam_file in args.bam_files:
             if not bam_file.endswith('.bam'):
@@ -219,13 +231,13 @@ def validate_args(args):
             if len(args.bai_files) != len(bam_files):
                 raise ValueError('Number of supplied .bai files does not match number of supplied .bam files.')
             for bai_file in args.bai_files:
-                if not bai_file.endswith('.bai'):
+                if not bai_file.endswith(('.bai', '.csi')):
                     raise ValueError('{0} is not a .bai file.'.format(bai_file))
                 if not os.path.isfile(bai_file):
                     raise FileNotFoundError('Count not find .bai file {0}'.format(bai_file))
                 bai_files.append(bai_file)
         else:
-            bai_files, create_bai_files = _default_bai_files(bam_files, create, _unsorted(bam_files) if sort else ())
+            bai_files, create_bai_files = _default_bai_files(bam_files, create, _unsorted(bam_files) if sort else (), fmt)
     if len(bam_files) < 2:
         raise ValueError('Fewer than 2 .bam files were found. Not sufficiently many to run DegNorm.')
     if len(bam_files) != len(set(bam_files)):
@@ -268,6 +280,7 @@ def _run(args, output_dir, device, verify):
     else:
         from .pipeline import run_pipeline
         deflate = 'native' if getattr(args, 'native_deflate', False) else 'zlib'
+        fmt = getattr(args, 'index_format', 'bai')
         for k, sam_file in enumerate(getattr(args, 'sam_files', None) or []):
             from .bam import create_index, sam_to_bam, sort_order
             converted_dir = os.path.join(output_dir, 'converted_bam')
@@ -280,7 +293,7 @@ def _run(args, output_dir, device, verify):
                 args.bai_files.append(None)
                 args.sort_bam_files.append(bam_file)
             else:
-                args.bai_files.append(create_index(bam_file, bai_from_bam_file(bam_file), device=device, verify=verify))
+                args.bai_files.append(create_index(bam_file, bai_from_bam_file(bam_file)[:-3] + fmt, device=device, verify=verify, fmt=fmt))
         for k, bam_file in enumerate(args.sort_bam_files):
             from .bam import create_index, sort_bam
             sorted_dir = os.path.join(output_dir, 'sorted_bam')
@@ -289,7 +302,8 @@ def _run(args, output_dir, device, verify):
             at = args.bam_files.index(bam_file)
             args.bam_files[at] = sort_bam(bam_file, os.path.join(sorted_dir, os.path.basename(bam_file)), device=device,
                                           n_jobs=args.proc_per_node, verify=verify, deflate=deflate)
-            args.bai_files[at] = create_index(args.bam_files[at], bai_from_bam_file(args.bam_files[at]), device=device, verify=verify)
+            args.bai_files[at] = create_index(args.bam_files[at], bai_from_bam_file(args.bam_files[at])[:-3] + fmt, device=device,
+                                              verify=verify, fmt=fmt)
         run_pipeline(args.bam_files, args.bai_files, args.genome_annotation, output_dir, degnorm_iter=args.iter,
                      nmf_iter=args.nmf_iter, downsample_rate=args.downsample_rate, minimax_coverage=args.minimax_coverage,
                      skip_baseline_selection=args.skip_baseline_selection, unique_alignment=not args.non_unique_alignments,
@@ -308,7 +322,7 @@ def main(argv=None):
     for k, bam_file in enumerate(args.create_bai_files or []):
         from .utils import create_index_file
         logging.info('creating index file for {0} -- {1} / {2}'.format(bam_file, k + 1, len(args.create_bai_files)))
-        create_index_file(bam_file, device=device, verify=verify)
+        create_index_file(bam_file, device=device, verify=verify, fmt=args.index_format)
     output_dir = create_output_dir(args.output_dir)
     log_file = logging.FileHandler(os.path.join(output_dir, 'degnorm.log'))
     log_file.setFormatter(logging.Formatter(fmt['format'], fmt['datefmt']))

@@ -156,6 +156,8 @@ def load(build_if_missing=False):
     lib.dn_bai_expect_crc.argtypes = [vp, P(u32), i64]
     lib.dn_bai_finish.argtypes = [vp, i64, P(i64)]
     lib.dn_bai_fetch.argtypes = [vp, P(i32), P(i32), P(u64), P(i32), P(i32), P(u64), P(u64)]
+    lib.dn_csi_create.argtypes = [c.c_int, i32, i64, i32, i32, P(vp)]
+    lib.dn_csi_loffset.argtypes = [vp, P(u64)]
     lib.dn_bam_sort_device_memory.argtypes = [c.c_int, P(i64), P(i64)]
     lib.dn_bam_sort_create.argtypes = [c.c_int, i32, i64, i64, i64, P(vp)]
     lib.dn_bam_sort_destroy.argtypes = [vp]

@@ -23,6 +23,8 @@ as pandas' sort_values does (numpy's quicksort on fixed-width bytes) and hands t
 A file without an index gets one from build_index / create_index (csrc/dn_bai.hip): one pass over every record of the file,
 inflated, framed and indexed on the device window by window (or, device=None, with zlib and the host build of the same
 source); parse_bai / BamIndex.tobytes / write_bai read and write whole .bai files, index_chunks is the region query.
+A .bai ends at position 2^29: fmt='csi' builds the .csi index of (min_shift, depth) with the same builder, parse_csi /
+write_index read and write its BGZF-compressed file, and read_index gives the reader what read_bai gives it, from either.
 
 A file that is not sorted by coordinate -- an aligner's default output -- is sorted by sort_bam (csrc/dn_sort.hip): the whole
 inflated record stream is inflated into one device buffer, framed, keyed, radix-sorted (stably: ties keep file order) and
@@ -494,6 +496,78 @@ def read_bai(path):
     return refs, n_no_coor
 
 
+def pseudo_bin(depth):
+    """The id of the pseudo-bin of an index of `depth` levels: 37450 at the .bai's depth 5."""
+    return ((1 << 3 * (int(depth) + 1)) - 1) // 7 + 1
+
+
+def _csi_bytes(path, raw):
+    """The inflated bytes of a .csi file (a BGZF stream; any sequence of gzip members is read), which start with the magic."""
+    out, rest = [], raw
+    try:
+        while rest:
+            d = zlib.decompressobj(31)
+            out.append(d.decompress(rest))
+            if not d.eof:
+                raise ValueError('{0}: truncated .csi index (its last gzip member is cut short)'.format(path))
+            rest = d.unused_data
+    except zlib.error as e:
+        raise ValueError('{0} is not a .csi index ({1})'.format(path, e))
+    data = b''.join(out)
+    if data[:4] != b'CSI\x01':
+        raise ValueError('{0} is not a .csi index'.format(path))
+    return data
+
+
+def _csi_fields(path, b):
+    """(min_shift, depth, aux, [per reference [(bin, loffset, (n, 2) chunks)] in file order], n_no_coor or None)."""
+    try:
+        min_shift, depth, l_aux = struct.unpack_from('<iii', b, 4)
+        if l_aux < 0 or 16 + l_aux + 4 > len(b):
+            raise ValueError('l_aux = {0}'.format(l_aux))
+        aux = bytes(b[16:16 + l_aux])
+        p = 16 + l_aux
+        n_ref = struct.unpack_from('<i', b, p)[0]
+        p += 4
+        refs = []
+        for _ in range(n_ref):
+            n_bin = struct.unpack_from('<i', b, p)[0]
+            p += 4
+            bins = []
+            for _ in range(n_bin):
+                bin_id, loffset, n_chunk = struct.unpack_from('<IQi', b, p)
+                p += 16
+                bins.append((bin_id, loffset, np.frombuffer(b, dtype='<u8', count=2 * n_chunk, offset=p).reshape(n_chunk, 2).astype(np.uint64)))
+                p += 16 * n_chunk
+            refs.append(bins)
+    except (struct.error, ValueError) as e:
+        raise ValueError('{0}: truncated .csi index ({1})'.format(path, e))
+    return min_shift, depth, aux, refs, struct.unpack_from('<Q', b, p)[0] if len(b) >= p + 8 else None
+
+
+def read_index(path):
+    """
+    What the reader needs of an index file, as read_bai gives it.  A file that starts with the gzip magic is a .csi index
+    (a BGZF stream whose inflated bytes start with 'CSI\\1'; ValueError otherwise); any other file goes to read_bai.
+    """
+    with open(path, 'rb') as f:
+        raw = f.read()
+    if raw[:2] != b'\x1f\x8b':
+        return read_bai(path)
+    min_shift, depth, _, bins, n_no_coor = _csi_fields(path, _csi_bytes(path, raw))
+    refs = []
+    for ref_bins in bins:
+        pseudo, lo, hi = None, None, None
+        for bin_id, _, ch in ref_bins:
+            if bin_id == pseudo_bin(depth):
+                pseudo = tuple(int(x) for x in ch.reshape(-1)[:4])
+            elif len(ch):
+                lo = int(ch[:, 0].min()) if lo is None else min(lo, int(ch[:, 0].min()))
+                hi = int(ch[:, 1].max()) if hi is None else max(hi, int(ch[:, 1].max()))
+        refs.append({'n_bin': len(ref_bins), 'pseudo': pseudo, 'chunk_min': lo, 'chunk_max': hi})
+    return refs, n_no_coor
+
+
 def reference_range(ref):
     """[begin, end) virtual offsets of one reference's records from its .bai entry, or None when it has no reads."""
     if ref['pseudo'] is not None:
@@ -777,6 +851,7 @@ def cigar_strings(op_beg, n_op, ops):
 # --- the processor -------------------------------------------------------------------------------------------------------
 
 class NativeBamReadsProcessor(BamReadsProcessor):
+    index_extensions = ('.bai', '.csi')          # read_index tells them apart by their first bytes
 
     def __init__(self, bam_file, index_file, chroms=None, n_jobs=1, output_dir=None, unique_alignment=True, verbose=True,
                  window_bytes=256 << 20, inflate='host', frame='host', frame_segment_bytes=None, verify=False, pair='host'):
@@ -818,7 +893,7 @@ class NativeBamReadsProcessor(BamReadsProcessor):
     def _load(self):
         if self._refs is None:
             self._refs = self._feed(False).header()[4]
-            self._index, _ = read_bai(self.index_filename)
+            self._index, _ = read_index(self.index_filename)
             if len(self._index) != len(self._refs):
                 raise ValueError('{0} indexes {1} references, {2} has {3}'.format(
                     self.index_filename, len(self._index), self.filename, len(self._refs)))
@@ -981,40 +1056,63 @@ class BamIndex(object):
     `ioffset`, the linear index (uint64).  build_index writes the bins in ascending order and the pseudo-bin last;
     parse_bai keeps whatever order the file has, so tobytes() gives the file back.  n_no_coor: the count of records
     without a reference, None for a file that ends before it.
+
+    fmt='csi': a .csi index of (min_shift, depth) (include/degnorm_amd.h).  `ioffset` is empty and every reference has
+    `loffset`, one offset per entry of `bins` (0 for the pseudo-bin, which is pseudo_bin(depth)); aux: the file's auxiliary
+    bytes.  tobytes() gives the inflated bytes of the file, write_index compresses them.
     """
 
-    def __init__(self, refs, n_no_coor=None):
+    def __init__(self, refs, n_no_coor=None, fmt='bai', min_shift=14, depth=5, aux=b''):
         self.refs = refs
         self.n_no_coor = n_no_coor
+        self.fmt, self.min_shift, self.depth, self.aux = fmt, int(min_shift), int(depth), aux
 
     @classmethod
-    def from_tables(cls, ref_n_bin, ref_n_intv, pseudo, bin_id, bin_n_chunk, chunks, ioffset, n_no_coor):
+    def from_tables(cls, ref_n_bin, ref_n_intv, pseudo, bin_id, bin_n_chunk, chunks, ioffset, n_no_coor, loffset=None, **kw):
         """
         The index of the flat tables dn_bai_fetch fills: per reference its number of bins and of linear-index entries and its
         pseudo-bin's four values; per bin, in reference order, its id and its number of chunks; the (n, 2) chunks and the
-        linear-index entries of all of them.  A reference with bins gets its pseudo-bin as the last of them.
+        linear-index entries of all of them.  A reference with bins gets its pseudo-bin as the last of them.  loffset: the
+        column of dn_csi_loffset, for a .csi index (kw: fmt, min_shift, depth).
         """
-        refs, b, c, w = [], 0, 0, 0
+        index = cls([], n_no_coor, **kw)
+        refs, b, c, w = index.refs, 0, 0, 0
         for r in range(len(ref_n_bin)):
             bins = []
             for k in range(b, b + int(ref_n_bin[r])):
                 bins.append((int(bin_id[k]), chunks[c:c + int(bin_n_chunk[k])].copy()))
                 c += int(bin_n_chunk[k])
-            b += int(ref_n_bin[r])
             if bins:
-                bins.append((PSEUDO_BIN, pseudo[4 * r:4 * r + 4].reshape(2, 2).copy()))
+                bins.append((index.pseudo_bin, pseudo[4 * r:4 * r + 4].reshape(2, 2).copy()))
             refs.append({'bins': bins, 'ioffset': ioffset[w:w + int(ref_n_intv[r])].copy()})
+            if loffset is not None:
+                refs[-1]['loffset'] = [int(x) for x in loffset[b:b + int(ref_n_bin[r])]] + ([0] if bins else [])
+            b += int(ref_n_bin[r])
             w += int(ref_n_intv[r])
-        return cls(refs, n_no_coor)
+        return index
+
+    @property
+    def pseudo_bin(self):
+        return pseudo_bin(self.depth)
 
     def pseudo(self, tid):
         """(offset of the first record, end of the last, mapped, unmapped) of a reference, or None without a pseudo-bin."""
         for bin_id, ch in self.refs[tid]['bins']:
-            if bin_id == PSEUDO_BIN:
+            if bin_id == self.pseudo_bin:
                 return tuple(int(x) for x in ch.reshape(-1)[:4])
         return None
 
     def tobytes(self):
+        if self.fmt == 'csi':
+            out = [b'CSI\x01', struct.pack('<iii', self.min_shift, self.depth, len(self.aux)), self.aux, struct.pack('<i', len(self.refs))]
+            for ref in self.refs:
+                out.append(struct.pack('<i', len(ref['bins'])))
+                for (bin_id, ch), loffset in zip(ref['bins'], ref['loffset']):
+                    out.append(struct.pack('<IQi', bin_id, loffset, len(ch)))
+                    out.append(np.ascontiguousarray(ch, dtype='<u8').tobytes())
+            if self.n_no_coor is not None:
+                out.append(struct.pack('<Q', self.n_no_coor))
+            return b''.join(out)
         out = [b'BAI\x01', struct.pack('<i', len(self.refs))]
         for ref in self.refs:
             out.append(struct.pack('<i', len(ref['bins'])))
@@ -1055,17 +1153,68 @@ def parse_bai(path):
     return BamIndex(refs, struct.unpack_from('<Q', b, p)[0] if len(b) >= p + 8 else None)
 
 
-def write_bai(index, path):
-    """Write a BamIndex to `path`: to a temporary file next to it, renamed when complete."""
+def parse_csi(path):
+    """The whole of a .csi index file as a BamIndex: its aux bytes and the order of its bins kept."""
+    with open(path, 'rb') as f:
+        raw = f.read()
+    if raw[:2] != b'\x1f\x8b':
+        raise ValueError('{0} is not a .csi index'.format(path))
+    min_shift, depth, aux, bins, n_no_coor = _csi_fields(path, _csi_bytes(path, raw))
+    refs = [{'bins': [(b, ch) for b, _, ch in ref], 'loffset': [lo for _, lo, _ in ref], 'ioffset': np.zeros(0, np.uint64)} for ref in bins]
+    return BamIndex(refs, n_no_coor, fmt='csi', min_shift=min_shift, depth=depth, aux=aux)
+
+
+def _write_replacing(data, path):
     tmp = '{0}.tmp{1}'.format(path, os.getpid())
     try:
         with open(tmp, 'wb') as f:
-            f.write(index.tobytes())
+            f.write(data)
         os.replace(tmp, path)
     finally:
         if os.path.exists(tmp):
             os.remove(tmp)
     return path
+
+
+def write_bai(index, path):
+    """Write a BamIndex to `path`: to a temporary file next to it, renamed when complete."""
+    return _write_replacing(index.tobytes(), path)
+
+
+def write_index(index, path):
+    """
+    Write a BamIndex to `path` as its format asks: a .bai as write_bai does, a .csi as BGZF blocks of its bytes (zlib, level
+    6) and the end-of-file block; to a temporary file next to it, renamed when complete.
+    """
+    if index.fmt != 'csi':
+        return write_bai(index, path)
+    data = index.tobytes()
+    blocks = [bgzf_compress(data[k:k + BGZF_BLOCK_DATA], 6) for k in range(0, len(data), BGZF_BLOCK_DATA)]
+    return _write_replacing(b''.join(blocks) + BGZF_EOF, path)
+
+
+def csi_depth(min_shift, longest):
+    """The smallest depth with 2^(min_shift + 3 depth) >= longest + 256: this library's rule where the caller names none."""
+    depth = 0
+    while (1 << (int(min_shift) + 3 * depth)) < int(longest) + 256:
+        depth += 1
+    return depth
+
+
+def _index_format(fmt, min_shift, depth):
+    """The checked (fmt, min_shift, depth) of build_index's keywords; depth stays None where it is left open."""
+    if fmt not in ('bai', 'csi'):
+        raise ValueError("fmt must be 'bai' or 'csi', not {0!r}".format(fmt))
+    if fmt == 'bai':
+        if int(min_shift) != 14 or depth not in (None, 5):
+            raise ValueError('a .bai index has min_shift 14 and depth 5; pass fmt=\'csi\' for other values')
+        return fmt, 14, 5
+    min_shift = int(min_shift)
+    if not 1 <= min_shift <= 30:
+        raise ValueError('min_shift must be 1 .. 30, not {0}'.format(min_shift))
+    if depth is not None and (not 0 <= int(depth) <= 8 or min_shift + 3 * int(depth) > 54):
+        raise ValueError('depth must be 0 .. 8 with min_shift + 3 depth at most 54, not {0} (min_shift {1})'.format(depth, min_shift))
+    return fmt, min_shift, None if depth is None else int(depth)
 
 
 class _IndexBuilder(_WindowHandle):
@@ -1075,10 +1224,15 @@ class _IndexBuilder(_WindowHandle):
     """
     unit = 'dn_bai'
 
-    def __init__(self, path, device, n_ref, segment=0):
+    def __init__(self, path, device, n_ref, segment=0, fmt='bai', min_shift=14, depth=5):
         self.lib, self.path, self.device, self.n_ref, self.h = _lib.load(), path, device, int(n_ref), ctypes.c_void_p()
+        self.fmt, self.min_shift, self.depth = fmt, min_shift, depth
         self.ms = {'inflate_device_ms': 0.0, 'frame_device_ms': 0.0, 'index_device_ms': 0.0}
-        self.call(self.lib.dn_bai_create(-1 if device is None else int(device), self.n_ref, segment, ctypes.byref(self.h)), 'dn_bai_create')
+        dev = -1 if device is None else int(device)
+        if fmt == 'csi':
+            self.call(self.lib.dn_csi_create(dev, self.n_ref, segment, min_shift, depth, ctypes.byref(self.h)), 'dn_csi_create')
+        else:
+            self.call(self.lib.dn_bai_create(dev, self.n_ref, segment, ctypes.byref(self.h)), 'dn_bai_create')
 
     def window(self, win):
         """dn_bai_window_host on the window's zlib-inflated data (device=None), dn_bai_window on its blocks as they are."""
@@ -1121,11 +1275,17 @@ class _IndexBuilder(_WindowHandle):
         chunks, ioffset = np.zeros(max(2 * n_chunks, 1), np.uint64), np.zeros(max(n_intv, 1), np.uint64)
         self.call(self.lib.dn_bai_fetch(self.h, _ptr(ref_n_bin, i32), _ptr(ref_n_intv, i32), _ptr(pseudo, u64), _ptr(bin_id, i32),
                                         _ptr(bin_n_chunk, i32), _ptr(chunks, u64), _ptr(ioffset, u64)), 'dn_bai_fetch')
+        loffset = None
+        if self.fmt == 'csi':
+            loffset = np.zeros(max(n_bins, 1), np.uint64)
+            self.call(self.lib.dn_csi_loffset(self.h, _ptr(loffset, u64)), 'dn_csi_loffset')
         return BamIndex.from_tables(ref_n_bin[:self.n_ref], ref_n_intv, pseudo, bin_id, bin_n_chunk,
-                                    chunks[:2 * n_chunks].reshape(n_chunks, 2), ioffset, int(sizes[4]))
+                                    chunks[:2 * n_chunks].reshape(n_chunks, 2), ioffset, int(sizes[4]), loffset=loffset,
+                                    fmt=self.fmt, min_shift=self.min_shift, depth=self.depth)
 
 
-def build_index(bam_file, device=None, n_jobs=1, window_bytes=256 << 20, segment_bytes=None, stats=None, verify=False):
+def build_index(bam_file, device=None, n_jobs=1, window_bytes=256 << 20, segment_bytes=None, stats=None, verify=False, fmt='bai',
+                min_shift=14, depth=None):
     """
     The .bai index of a coordinate-sorted BAM file as a BamIndex, from one pass over all its records (csrc/dn_bai.hip; the
     index is defined in include/degnorm_amd.h).  device=k: the blocks of about window_bytes of inflated data go to GPU k as
@@ -1135,11 +1295,19 @@ def build_index(bam_file, device=None, n_jobs=1, window_bytes=256 << 20, segment
     the record).  verify: every block must have the CRC32 of its trailer, checked where the block is inflated (ValueError
     naming the file and the block's offset).  segment_bytes: of the framing (None: the library's default).  stats, a dict, receives
     `inflate_device_ms`, `frame_device_ms`, `index_device_ms`, `frame_fixups`, `records`, `chunks` and `windows`.
+    fmt='csi': the .csi index of (min_shift, depth) instead, which holds positions up to 2^(min_shift + 3 depth) where a
+    .bai ends at 2^29; depth=None takes csi_depth of the header's longest reference.  Values out of range are a ValueError
+    before the file is opened.
     """
+    fmt, min_shift, depth = _index_format(fmt, min_shift, depth)
     with _WindowFeed(bam_file, window_bytes, verify, n_jobs if device is None else 1) as feed:
         segment = _segment_arg(segment_bytes)
         _, head_blocks, _, head_skip, refs = feed.header()
-        with _IndexBuilder(bam_file, device, len(refs), segment) as bai:
+        if depth is None:
+            depth = csi_depth(min_shift, max([length for _, length in refs] + [0]))
+            if depth > 8 or min_shift + 3 * depth > 54:
+                raise ValueError('{0}: no .csi index of min_shift {1} holds its longest reference'.format(bam_file, min_shift))
+        with _IndexBuilder(bam_file, device, len(refs), segment, fmt, min_shift, depth) as bai:
             end, is_open = None, False                   # the block behind the last one that holds a byte
             # the first window starts inside the block in which the header ends, and holds the bytes behind the header
             for win in feed.whole(head_blocks - 1, -head_skip, head_skip):
@@ -1157,12 +1325,16 @@ def build_index(bam_file, device=None, n_jobs=1, window_bytes=256 << 20, segment
     return index
 
 
-def create_index(bam_file, bai_file=None, overwrite=False, **kw):
-    """Build the index of bam_file (build_index's keywords) and write it to bai_file (default bam_file + '.bai'); its path."""
-    bai_file = bam_file + '.bai' if bai_file is None else bai_file
+def create_index(bam_file, bai_file=None, overwrite=False, fmt='bai', **kw):
+    """
+    Build the index of bam_file (build_index's keywords) and write it to bai_file (default bam_file + '.bai', or + '.csi'
+    for fmt='csi'); its path.
+    """
+    _index_format(fmt, kw.get('min_shift', 14), kw.get('depth'))
+    bai_file = bam_file + '.' + fmt if bai_file is None else bai_file
     if os.path.exists(bai_file) and not overwrite:
         raise FileExistsError('{0} exists; pass overwrite=True to replace it'.format(bai_file))
-    return write_bai(build_index(bam_file, **kw), bai_file)
+    return write_index(build_index(bam_file, fmt=fmt, **kw), bai_file)
 
 
 def verify_bgzf(path, device=None, n_jobs=1, window_bytes=256 << 20):
@@ -1197,24 +1369,48 @@ def verify_bgzf(path, device=None, n_jobs=1, window_bytes=256 << 20):
     return out
 
 
-def reg2bins(beg, end):
-    """The bins that may hold records overlapping [beg, end) (SAM specification 5.3)."""
-    beg, end = max(int(beg), 0), min(int(end), 1 << 29) - 1
+def _bin_levels(min_shift, depth):
+    """(level, first bin, shift of the bins' span) of the levels below the root."""
+    return [(l, ((1 << 3 * l) - 1) // 7, min_shift + 3 * (depth - l)) for l in range(1, depth + 1)]
+
+
+def reg2bins(beg, end, min_shift=14, depth=5):
+    """The bins that may hold records overlapping [beg, end) (SAM specification 5.3; of a .csi index of (min_shift, depth))."""
+    beg, end = max(int(beg), 0), min(int(end), 1 << (min_shift + 3 * depth)) - 1
     bins = [0]
-    for shift, first in ((26, 1), (23, 9), (20, 73), (17, 585), (14, 4681)):
+    for _, first, shift in _bin_levels(min_shift, depth):
         bins.extend(range(first + (beg >> shift), first + (end >> shift) + 1))
     return bins
+
+
+def _csi_low(index, ref, beg):
+    """The largest loffset over the stored bins whose interval begins at or before beg: every one bounds the region's records."""
+    levels = [(0, 0, index.min_shift + 3 * index.depth)] + _bin_levels(index.min_shift, index.depth)
+    low = 0
+    for (bin_id, _), loffset in zip(ref['bins'], ref['loffset']):
+        if bin_id == index.pseudo_bin:
+            continue
+        _, first, shift = [lv for lv in levels if lv[1] <= bin_id][-1]
+        if (bin_id - first) << shift <= beg:
+            low = max(low, int(loffset))
+    return low
 
 
 def index_chunks(index, tid, beg, end):
     """
     The [begin, end) virtual-offset ranges a reader has to scan for the records of reference tid that overlap [beg, end):
-    the chunks of reg2bins(beg, end) that end above the linear index's lower bound for beg, sorted and coalesced.
+    the chunks of reg2bins(beg, end) that end above the linear index's lower bound for beg, sorted and coalesced.  On a .csi
+    index the bound is the largest loffset of a stored bin that begins at or before beg.
     """
     ref = index.refs[tid]
     ioffset = ref['ioffset']
-    low = int(ioffset[min(max(int(beg), 0) >> 14, len(ioffset) - 1)]) if len(ioffset) else 0
-    want = set(reg2bins(beg, end))
+    if index.fmt == 'csi':
+        low = _csi_low(index, ref, max(int(beg), 0))
+        want = set(reg2bins(beg, end, index.min_shift, index.depth))
+        want.discard(index.pseudo_bin)
+    else:
+        low = int(ioffset[min(max(int(beg), 0) >> 14, len(ioffset) - 1)]) if len(ioffset) else 0
+        want = set(reg2bins(beg, end))
     found = sorted((int(b), int(e)) for bin_id, ch in ref['bins'] if bin_id in want for b, e in ch.tolist() if e > low)
     out = []
     for b, e in found:

@@ -1,4 +1,8 @@
-// dn_bai.hip -- the .bai index of a coordinate-sorted BAM file, built from a pass over every record on the device.
+// dn_bai.hip -- the .bai or .csi index of a coordinate-sorted BAM file, built from a pass over every record on the device.
+//
+// Both are one binning index (include/degnorm_amd.h): bins of 2^min_shift bases ("granules"; a .bai's 16 kb windows) in
+// `depth` levels below the root.  A .bai is (14, 5) with a linear index, a .csi any (min_shift, depth) with one offset per
+// bin; the builder carries the pair (Binning) and the kernels take it by value.  Below, 14 stands for min_shift.
 //
 // A window (the record cut by the window before + the inflated BGZF blocks of about window_bytes) is inflated
 // (dn::InflateWindow) and framed (dn::frame_window, tid = -1) where it lies; then, one lane per record:
@@ -19,7 +23,8 @@
 //
 // Only these two small tables return to the host.  There they are stitched (a run that goes on across a window boundary is
 // one run; a run ends where the next begins), and dn_bai_finish sorts the runs by key (stably: file order within a bin),
-// joins chunks that touch in one block, and fills the linear index.
+// joins chunks that touch in one block, and fills the linear index -- or, for a .csi, finds every bin's offset by a search
+// of the claims, which are what the linear index would be filled from.
 //
 // The three per-record steps are __host__ __device__ functions on the record view of dn_bam_record.hpp.  The steps of a
 // window are written once (run_window) over two backends: DeviceIndex queues kernels and hipcub scans on the window where it
@@ -45,7 +50,6 @@ using dn::ref_key;
 using dn::reg2bin;
 
 constexpr int kNT = 256;
-constexpr int64_t kMaxCoord = (int64_t) 1 << 29;
 constexpr int64_t kGridCap = 1 << 20;
 
 enum { kBaiOk = 0, kBaiShape = 1, kBaiRef = 2, kBaiRefOrder = 3, kBaiPosOrder = 4, kBaiRange = 5, kBaiOffset = 6 };
@@ -67,11 +71,25 @@ struct Head {
     int32_t idx, unmapped_before;      // the record's ordinal in its window; placed records with flag & 4 before it there
 };
 
+// the first and the last granule (of 2^min_shift bases; a .bai's 16 kb windows) of a record or of a claim
+struct Span {
+    uint32_t lo, hi;
+};
+
 struct Claim {
     uint64_t vbeg;
     int32_t ref;
-    uint32_t lohi;                     // first window << 16 | last window
+    Span g;
+    int32_t pad;
 };
+
+// The binning scheme of the builder, handed to the kernels by value: a .bai is (14, 5).  cap = 2^(min_shift + 3 depth) is the
+// largest end the index can hold, so a granule index stays below 2^(3 depth) <= 2^24.
+struct Binning {
+    int32_t min_shift, depth;
+    int64_t cap;
+};
+constexpr Binning kBaiBinning{14, 5, (int64_t) 1 << 29};
 
 struct Totals {
     int64_t heads, unmapped, claims;
@@ -80,7 +98,7 @@ struct Totals {
 // per-record arrays of one window
 struct Recs {
     uint64_t *key, *vbeg, *emax_in, *emax;       // emax: the inclusive max-scan of emax_in
-    uint32_t *win;                               // beg >> 14 << 16 | (end - 1) >> 14
+    Span *win;                                   // beg >> min_shift and (end - 1) >> min_shift
     uint8_t *fl;                                 // bit 0: placed and flag & 4
     uint64_t *hs, *hs_sum;                       // head flag | unmapped flag << 32, and its exclusive sum
     int32_t *cf, *cf_sum;                        // claim flag, and its exclusive sum
@@ -100,10 +118,10 @@ DN_HD uint64_t piece_voffset(const Piece *pc, int32_t n_pieces, int64_t o)
 // Record i of the window: its entries of R, and kBaiOk or what is wrong with it.  frame_window established that the
 // record lies inside the window; the bounds are checked again so that offsets that do not belong to w cannot lead outside.
 DN_HD int bai_record(const uint8_t *w, int64_t n_bytes, const int64_t *rec_off, int64_t i, const Piece *pc, int32_t n_pieces,
-                     int32_t n_ref, const Carry &cin, const Recs &R)
+                     int32_t n_ref, const Binning &B, const Carry &cin, const Recs &R)
 {
     const int64_t o = rec_off[i];
-    R.key[i] = (uint64_t) kUnplaced << 32; R.vbeg[i] = 0; R.emax_in[i] = 0; R.win[i] = 0; R.fl[i] = 0;
+    R.key[i] = (uint64_t) kUnplaced << 32; R.vbeg[i] = 0; R.emax_in[i] = 0; R.win[i] = Span{0, 0}; R.fl[i] = 0;
     dn::BamHead H;
     if (!dn::bam_head(w, n_bytes, o, H) || !H.names_fit()) return kBaiShape;
     const int32_t ref = H.ref, pos = H.pos;
@@ -121,14 +139,17 @@ DN_HD int bai_record(const uint8_t *w, int64_t n_bytes, const int64_t *rec_off, 
         if (beg < 0) beg = 0;
         if (end <= 0) end = 1;
     }
-    const bool in_range = beg <= kMaxCoord && end <= kMaxCoord;
+    const bool in_range = beg <= B.cap && end <= B.cap;
     const uint32_t rk = ref_key(ref);
-    const uint32_t bin = ref >= 0 && in_range ? reg2bin(beg, end) : 0;
-    const uint32_t bw = ref >= 0 && in_range ? (uint32_t) (beg >> 14) : 0, ew = ref >= 0 && in_range ? (uint32_t) ((end - 1) >> 14) : 0;
+    const uint32_t bin = ref >= 0 && in_range ? reg2bin(beg, end, B.min_shift, B.depth) : 0;
+    const uint32_t bw = ref >= 0 && in_range ? (uint32_t) (beg >> B.min_shift) : 0;
+    const uint32_t ew = ref >= 0 && in_range ? (uint32_t) ((end - 1) >> B.min_shift) : 0;
     R.key[i] = (uint64_t) rk << 32 | bin;
     R.vbeg[i] = piece_voffset(pc, n_pieces, o);
+    // one word still holds reference and granule: pos is an int32, so even at min_shift 1 the last granule + 1 is at most
+    // 2^30 (and, as end <= cap, below 2^24 + 1 in an index that accepts the record)
     R.emax_in[i] = (uint64_t) rk << 32 | (ref >= 0 ? ew + 1 : 0);
-    R.win[i] = bw << 16 | ew;
+    R.win[i] = Span{bw, ew};
     R.fl[i] = ref >= 0 && (flag & 4) ? 1 : 0;
     bool has_prev = cin.any != 0;
     int32_t pref = cin.ref, ppos = cin.pos;
@@ -153,10 +174,10 @@ DN_HD void bai_flags(const Recs &R, int64_t i, const Carry &cin, bool &head, uin
     head = key != prev_key;
     uint64_t pe = i > 0 ? R.emax[i - 1] : 0;
     if (cin.any && cin.emax > pe) pe = cin.emax;
-    const uint32_t rk = (uint32_t) (key >> 32), bw = R.win[i] >> 16;
+    const uint32_t rk = (uint32_t) (key >> 32), bw = R.win[i].lo;
     const uint32_t past = (uint32_t) (pe >> 32) == rk ? (uint32_t) pe : 0;         // E + 1, or 0 for the reference's first record
     lo = bw > past ? bw : past;
-    hi = R.win[i] & 0xffff;
+    hi = R.win[i].hi;
     if (rk == kUnplaced) { lo = 1; hi = 0; }
 }
 
@@ -177,7 +198,7 @@ DN_HD void bai_scatter_pass(const uint8_t *w, const int64_t *rec_off, const Recs
     bai_flags(R, i, cin, head, lo, hi);
     const uint64_t s = R.hs_sum[i];
     if (head) heads[(uint32_t) s] = Head{R.key[i], R.vbeg[i], (int32_t) i, (int32_t) (s >> 32)};
-    if (lo <= hi) claims[R.cf_sum[i]] = Claim{R.vbeg[i], (int32_t) (R.key[i] >> 32), lo << 16 | hi};
+    if (lo <= hi) claims[R.cf_sum[i]] = Claim{R.vbeg[i], (int32_t) (R.key[i] >> 32), Span{lo, hi}, 0};
     if (i == n_rec - 1) {
         const uint64_t t = s + R.hs[i];
         *tot = Totals{(int64_t) (uint32_t) t, (int64_t) (t >> 32), (int64_t) R.cf_sum[i] + R.cf[i]};
@@ -190,11 +211,11 @@ DN_HD void bai_scatter_pass(const uint8_t *w, const int64_t *rec_off, const Recs
 
 __global__ __launch_bounds__(kNT) void k_bai_records(const uint8_t *__restrict__ w, int64_t n_bytes, const int64_t *__restrict__ rec_off,
                                                      int64_t n_rec, const Piece *__restrict__ pc, int32_t n_pieces, int32_t n_ref,
-                                                     const Carry *__restrict__ cin, Recs R, unsigned long long *__restrict__ err)
+                                                     Binning B, const Carry *__restrict__ cin, Recs R, unsigned long long *__restrict__ err)
 {
     const Carry c = *cin;
     for (int64_t i = (int64_t) blockIdx.x * kNT + threadIdx.x; i < n_rec; i += (int64_t) gridDim.x * kNT) {
-        const int e = bai_record(w, n_bytes, rec_off, i, pc, n_pieces, n_ref, c, R);
+        const int e = bai_record(w, n_bytes, rec_off, i, pc, n_pieces, n_ref, B, c, R);
         if (e != kBaiOk) dn::note_error(err, i, e);
     }
 }
@@ -224,6 +245,8 @@ struct Run {
 struct dn_bai_s {
     int device = -1;                   // < 0: the host build
     int32_t n_ref = 0;
+    bool csi = false;                  // a .csi builder: per-bin loffset in place of the linear index
+    Binning binning = kBaiBinning;
     int64_t segment = 0;
     int64_t n_records = 0, n_windows = 0, n_fixups = 0;
     bool failed = false, finished = false;
@@ -241,7 +264,7 @@ struct dn_bai_s {
     dn::GrowBuffer<int64_t> rec_off;
     dn::GrowBuffer<Piece> pieces;
     dn::GrowBuffer<uint64_t> key, vbeg, emax_in, emax, hs, hs_sum;
-    dn::GrowBuffer<uint32_t> rwin;
+    dn::GrowBuffer<Span> rwin;
     dn::GrowBuffer<uint8_t> fl;
     dn::GrowBuffer<int32_t> cf, cf_sum;
     dn::GrowBuffer<Head> heads;
@@ -255,7 +278,7 @@ struct dn_bai_s {
     dn::Event ev2, ev3;                // around the index kernels
     // what dn_bai_finish built
     std::vector<int32_t> ref_n_bin, ref_n_intv, bin_id, bin_n_chunk;
-    std::vector<uint64_t> ref_pseudo, chunks, ioffset;
+    std::vector<uint64_t> ref_pseudo, chunks, ioffset, loffset;
     int64_t n_no_coor = 0;
 
     int64_t carried() const { return device < 0 ? (int64_t) h_carry.size() : carry.n; }
@@ -271,7 +294,11 @@ int record_error(dn_bai h, int code, int64_t idx, int32_t ref, int32_t pos)
     case kBaiRef: return dn::record_reference_error(who, h->n_ref);
     case kBaiRefOrder: return dn::fail(DN_E_INVALID, "BAM file is not sorted by coordinate: " + who + " follows a record of a later reference");
     case kBaiPosOrder: return dn::fail(DN_E_INVALID, "BAM file is not sorted by coordinate: " + who + " follows a larger position of the same reference");
-    case kBaiRange: return dn::fail(DN_E_INVALID, who + " reaches beyond position 2^29: a .bai index cannot hold it");
+    case kBaiRange:
+        if (!h->csi) return dn::fail(DN_E_INVALID, who + " reaches beyond position 2^29: a .bai index cannot hold it");
+        return dn::fail(DN_E_INVALID, who + " reaches beyond position 2^" + std::to_string(h->binning.min_shift + 3 * h->binning.depth) +
+                                          ": a .csi index of min_shift " + std::to_string(h->binning.min_shift) + " and depth " +
+                                          std::to_string(h->binning.depth) + " cannot hold it");
     default: return dn::fail(DN_E_INVALID, who + " starts beyond byte 65535 of its BGZF block: a virtual offset cannot hold it");
     }
 }
@@ -328,7 +355,7 @@ struct HostIndex {
     std::vector<uint8_t> win;
     std::vector<int64_t> off;
     std::vector<uint64_t> key, vbeg, emax_in, emax, hs, hs_sum;
-    std::vector<uint32_t> rwin;
+    std::vector<Span> rwin;
     std::vector<uint8_t> fl;
     std::vector<int32_t> cf, cf_sum;
     Recs R{};
@@ -355,7 +382,7 @@ struct HostIndex {
         rwin.resize(n); fl.resize(n); cf.resize(n); cf_sum.resize(n);
         R = Recs{key.data(), vbeg.data(), emax_in.data(), emax.data(), rwin.data(), fl.data(), hs.data(), hs_sum.data(), cf.data(), cf_sum.data()};
         for (int64_t i = 0; i < nr && e == dn::kNoError; i++) {
-            const int code = bai_record(win.data(), total, off.data(), i, pc.data(), (int32_t) pc.size(), h->n_ref, h->h_state, R);
+            const int code = bai_record(win.data(), total, off.data(), i, pc.data(), (int32_t) pc.size(), h->n_ref, h->binning, h->h_state, R);
             if (code != kBaiOk) dn::note_error(&e, i, code);
         }
         if (e != dn::kNoError) dn::error_record_host(off.data(), dn::error_ordinal(e), win.data(), total, ref, pos);
@@ -438,7 +465,7 @@ struct DeviceIndex {
         DN_TRY(hipMemsetAsync(h->err, 0xff, sizeof(unsigned long long), st));
         DN_TRY(hipEventRecord(h->ev2, st));
         hipLaunchKernelGGL(k_bai_records, dim3(grid), dim3(kNT), 0, st, (const uint8_t *) h->win.get(), total, (const int64_t *) h->rec_off.get(), nr,
-                           (const Piece *) h->pieces.get(), (int32_t) pc.size(), h->n_ref, cin, R, h->err.get());
+                           (const Piece *) h->pieces.get(), (int32_t) pc.size(), h->n_ref, h->binning, cin, R, h->err.get());
         DN_TRY(hipGetLastError());
         DN_TRY(hipMemcpyAsync(&h_err, h->err, sizeof(h_err), hipMemcpyDeviceToHost, st));
         DN_TRY(hipStreamSynchronize(st));
@@ -527,16 +554,15 @@ template <class B> int run_window(dn_bai h, B &be, const std::vector<Piece> &pc,
     return rc;
 }
 
-}  // namespace
-
-extern "C" int dn_bai_create(int device, int32_t n_ref, int64_t segment_bytes, dn_bai *out)
+int create_builder(const char *who, int device, int32_t n_ref, int64_t segment_bytes, bool csi, Binning binning, dn_bai *out)
 {
-    dn::clear_error();
     if (!out || n_ref < 0 || (segment_bytes != 0 && segment_bytes < dn::kFrameSegmentMin))
-        return dn::fail(DN_E_INVALID, "dn_bai_create: bad argument (segment_bytes is 0 or at least 64)");
+        return dn::fail(DN_E_INVALID, std::string(who) + ": bad argument (segment_bytes is 0 or at least 64)");
     dn_bai h = new dn_bai_s();
     h->device = device < 0 ? -1 : device;
     h->n_ref = n_ref;
+    h->csi = csi;
+    h->binning = binning;
     h->segment = segment_bytes;
     const int rc = [&]() -> int {
         if (device < 0) return DN_OK;
@@ -553,6 +579,23 @@ extern "C" int dn_bai_create(int device, int32_t n_ref, int64_t segment_bytes, d
     if (rc != DN_OK) { delete h; return rc; }
     *out = h;
     return DN_OK;
+}
+
+}  // namespace
+
+extern "C" int dn_bai_create(int device, int32_t n_ref, int64_t segment_bytes, dn_bai *out)
+{
+    dn::clear_error();
+    return create_builder("dn_bai_create", device, n_ref, segment_bytes, false, kBaiBinning, out);
+}
+
+extern "C" int dn_csi_create(int device, int32_t n_ref, int64_t segment_bytes, int32_t min_shift, int32_t depth, dn_bai *out)
+{
+    dn::clear_error();
+    if (min_shift < 1 || min_shift > 30 || depth < 0 || depth > 8 || min_shift + 3 * depth > 54)
+        return dn::fail(DN_E_INVALID, "dn_csi_create: min_shift is 1 .. 30, depth 0 .. 8 and min_shift + 3 depth at most 54");
+    return create_builder("dn_csi_create", device, n_ref, segment_bytes, true,
+                          Binning{min_shift, depth, (int64_t) 1 << (min_shift + 3 * depth)}, out);
 }
 
 extern "C" void dn_bai_destroy(dn_bai h)
@@ -685,17 +728,38 @@ extern "C" int dn_bai_finish(dn_bai h, int64_t end_voffset, int64_t *sizes)
     // the linear index: claims are in file order, so per reference ascending and disjoint; a window nobody claimed takes
     // the value of the next one that was
     std::vector<int64_t> ioff_at(n_ref + 1, 0);
-    for (const Claim &c : h->claims) {
-        const int32_t hi = (int32_t) (c.lohi & 0xffff) + 1;
-        if (hi > h->ref_n_intv[(size_t) c.ref]) h->ref_n_intv[(size_t) c.ref] = hi;
+    if (h->csi) {
+        // no dense table: the back-filled linear index at a bin's first granule is the vbeg of the reference's first claim whose
+        // last granule is at or beyond it -- one exists, since a record of the bin ends beyond the bin's start
+        std::vector<size_t> claim_at(n_ref + 1, 0);
+        for (const Claim &c : h->claims) claim_at[(size_t) c.ref + 1]++;
+        for (size_t r = 0; r < n_ref; r++) claim_at[r + 1] += claim_at[r];
+        const int depth = h->binning.depth;
+        size_t b = 0;
+        for (size_t r = 0; r < n_ref; r++)
+            for (int32_t k = 0; k < h->ref_n_bin[r]; k++, b++) {
+                const uint32_t bin = (uint32_t) h->bin_id[b];
+                int level = 0;
+                uint32_t first = 0;                                     // the first bin of the level
+                while (level < depth && bin >= first + ((uint32_t) 1 << 3 * level)) { first += (uint32_t) 1 << 3 * level; level++; }
+                const uint32_t g0 = (bin - first) << 3 * (depth - level);
+                const Claim *lo = h->claims.data() + claim_at[r], *hi = h->claims.data() + claim_at[r + 1];
+                const Claim *at = std::partition_point(lo, hi, [&](const Claim &c) { return c.g.hi < g0; });
+                h->loffset.push_back(at != hi ? at->vbeg : 0);
+            }
+    } else {
+        for (const Claim &c : h->claims) {
+            const int32_t hi = (int32_t) c.g.hi + 1;
+            if (hi > h->ref_n_intv[(size_t) c.ref]) h->ref_n_intv[(size_t) c.ref] = hi;
+        }
+        for (size_t r = 0; r < n_ref; r++) ioff_at[r + 1] = ioff_at[r] + h->ref_n_intv[r];
+        h->ioffset.assign((size_t) ioff_at[n_ref], ~(uint64_t) 0);
+        for (const Claim &c : h->claims)
+            for (uint32_t wdw = c.g.lo; wdw <= c.g.hi; wdw++) h->ioffset[(size_t) (ioff_at[(size_t) c.ref] + wdw)] = c.vbeg;
+        for (size_t r = 0; r < n_ref; r++)
+            for (int64_t wdw = ioff_at[r + 1] - 2; wdw >= ioff_at[r]; wdw--)
+                if (h->ioffset[(size_t) wdw] == ~(uint64_t) 0) h->ioffset[(size_t) wdw] = h->ioffset[(size_t) wdw + 1];
     }
-    for (size_t r = 0; r < n_ref; r++) ioff_at[r + 1] = ioff_at[r] + h->ref_n_intv[r];
-    h->ioffset.assign((size_t) ioff_at[n_ref], ~(uint64_t) 0);
-    for (const Claim &c : h->claims)
-        for (uint32_t wdw = c.lohi >> 16; wdw <= (c.lohi & 0xffff); wdw++) h->ioffset[(size_t) (ioff_at[(size_t) c.ref] + wdw)] = c.vbeg;
-    for (size_t r = 0; r < n_ref; r++)
-        for (int64_t wdw = ioff_at[r + 1] - 2; wdw >= ioff_at[r]; wdw--)
-            if (h->ioffset[(size_t) wdw] == ~(uint64_t) 0) h->ioffset[(size_t) wdw] = h->ioffset[(size_t) wdw + 1];
     h->finished = true;
     sizes[0] = (int64_t) h->bin_id.size();
     sizes[1] = (int64_t) h->chunks.size() / 2;
@@ -711,7 +775,7 @@ extern "C" int dn_bai_fetch(dn_bai h, int32_t *ref_n_bin, int32_t *ref_n_intv, u
                             uint64_t *chunks, uint64_t *ioffset)
 {
     dn::clear_error();
-    if (!h || !ref_n_bin || !ref_n_intv || !ref_pseudo || !bin_id || !bin_n_chunk || !chunks || !ioffset)
+    if (!h || !ref_n_bin || !ref_n_intv || !ref_pseudo || !bin_id || !bin_n_chunk || !chunks || (!ioffset && !h->csi))
         return dn::fail(DN_E_INVALID, "dn_bai_fetch: bad argument");
     if (!h->finished) return dn::fail(DN_E_STATE, "dn_bai_fetch: dn_bai_finish first");
     std::copy(h->ref_n_bin.begin(), h->ref_n_bin.end(), ref_n_bin);
@@ -721,5 +785,15 @@ extern "C" int dn_bai_fetch(dn_bai h, int32_t *ref_n_bin, int32_t *ref_n_intv, u
     std::copy(h->bin_n_chunk.begin(), h->bin_n_chunk.end(), bin_n_chunk);
     std::copy(h->chunks.begin(), h->chunks.end(), chunks);
     std::copy(h->ioffset.begin(), h->ioffset.end(), ioffset);
+    return DN_OK;
+}
+
+extern "C" int dn_csi_loffset(dn_bai h, uint64_t *loffset)
+{
+    dn::clear_error();
+    if (!h || !loffset) return dn::fail(DN_E_INVALID, "dn_csi_loffset: bad argument");
+    if (!h->csi) return dn::fail(DN_E_STATE, "dn_csi_loffset: a .bai builder has a linear index, no per-bin offsets");
+    if (!h->finished) return dn::fail(DN_E_STATE, "dn_csi_loffset: dn_bai_finish first");
+    std::copy(h->loffset.begin(), h->loffset.end(), loffset);
     return DN_OK;
 }

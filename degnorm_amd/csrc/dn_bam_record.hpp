@@ -67,8 +67,8 @@ DN_HD bool bam_head(const uint8_t *w, int64_t n_bytes, int64_t o, BamHead &H)
 constexpr uint32_t kUnplaced = 0xffffffffu;
 DN_HD uint32_t ref_key(int32_t ref) { return ref < 0 ? kUnplaced : (uint32_t) ref; }
 
-// The bin of [beg, end) on a reference (SAM specification 5.3).  The index (dn_bai.hip) calls it with 0 <= beg < end <= 2^29;
-// the SAM encoder (dn_sam.hip) with any beg >= -1: the shifts are arithmetic, so beg = -1, end = 0 gives 4680.
+// The bin of [beg, end) on a reference (SAM specification 5.3), which holds for 0 <= beg < end <= 2^29.  The SAM encoder
+// (dn_sam.hip) calls it with any beg >= -1: the shifts are arithmetic, so beg = -1, end = 0 gives 4680.
 DN_HD uint32_t reg2bin(int64_t beg, int64_t end)
 {
     --end;
@@ -77,6 +77,20 @@ DN_HD uint32_t reg2bin(int64_t beg, int64_t end)
     if (beg >> 20 == end >> 20) return (uint32_t) (((1 << 9) - 1) / 7 + (beg >> 20));
     if (beg >> 23 == end >> 23) return (uint32_t) (((1 << 6) - 1) / 7 + (beg >> 23));
     if (beg >> 26 == end >> 26) return (uint32_t) (((1 << 3) - 1) / 7 + (beg >> 26));
+    return 0;
+}
+
+// The same for a binning scheme of `depth` levels below the root whose smallest bins span 2^min_shift bases (the .csi
+// index; (14, 5) is the function above), with 0 <= beg < end <= 2^(min_shift + 3 depth), min_shift + 3 depth <= 54, depth <= 8.
+DN_HD uint32_t reg2bin(int64_t beg, int64_t end, int min_shift, int depth)
+{
+    int l = depth, s = min_shift;
+    uint32_t t = (((uint32_t) 1 << 3 * depth) - 1) / 7;
+    --end;
+    while (l > 0) {
+        if (beg >> s == end >> s) return t + (uint32_t) (beg >> s);
+        --l; s += 3; t -= (uint32_t) 1 << 3 * l;
+    }
     return 0;
 }
 

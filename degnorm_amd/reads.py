@@ -291,6 +291,7 @@ def reads_frame(rows, paired):
 
 
 class BamReadsProcessor(object):
+    index_extensions = ('.bai',)                 # what the backend that opens the file can read
 
     def __init__(self, bam_file, index_file, chroms=None, n_jobs=1, output_dir=None, unique_alignment=True, verbose=True):
         """
@@ -315,7 +316,7 @@ class BamReadsProcessor(object):
             raise ValueError('{0} is not a .bam file'.format(bam_file))
         if not os.path.isfile(index_file):
             raise FileNotFoundError('{0} .bam index file not found'.format(index_file))
-        if not index_file.endswith('.bai'):
+        if not index_file.endswith(self.index_extensions):
             raise ValueError('.bam index file does not have correct .bai file extension.')
         self.get_header()
         self.determine_if_paired()

@@ -202,14 +202,20 @@ def bai_from_bam_file(bam_file):
     return bam_file[:-3] + 'bai'
 
 
-def create_index_file(bam_file, **kw):
+def index_from_bam_file(bam_file, fmt='bai'):
+    """X.bai of X.bam, or X.csi for fmt='csi'."""
+    return bai_from_bam_file(bam_file)[:-3] + fmt
+
+
+def create_index_file(bam_file, fmt='bai', **kw):
     """
     Create the .bai index of a .bam file next to it, X.bam -> X.bai (the reference's utils.create_index_file, which shells
     out to samtools; here degnorm_amd.bam.create_index builds it, on the GPU with device=k; verify=True has every BGZF block
-    checked against the CRC32 of its trailer on the way).  Returns the .bai path.
+    checked against the CRC32 of its trailer on the way).  fmt='csi': the .csi index X.csi, for references beyond 2^29 bases
+    (min_shift and depth as bam.build_index takes them).  Returns the index file's path.
     """
     from .bam import create_index
-    return create_index(bam_file, bai_from_bam_file(bam_file), **kw)
+    return create_index(bam_file, index_from_bam_file(bam_file, fmt), fmt=fmt, **kw)
 
 
 def sort_bam_file(bam_file, out_dir=None, **kw):

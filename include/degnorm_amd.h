@@ -506,6 +506,52 @@ int  dn_bai_finish(dn_bai h, int64_t end_voffset, int64_t *sizes);
 int  dn_bai_fetch(dn_bai h, int32_t *ref_n_bin, int32_t *ref_n_intv, uint64_t *ref_pseudo, int32_t *bin_id, int32_t *bin_n_chunk,
                   uint64_t *chunks, uint64_t *ioffset);
 
+/* .csi index of a BAM file (the same builder, csrc/dn_bai.hip; degnorm_amd.bam.build_index(fmt='csi')) ---------------------
+ * The binning index of the .bai with two parameters: min_shift, the bits of the smallest bins' span (a "granule" of
+ * 2^min_shift bases), and depth, the number of levels below the root bin 0.  It holds one offset per bin in place of the
+ * linear index, reaches positions up to 2^(min_shift + 3 depth), and its file is BGZF-compressed.  (14, 5) is the
+ * binning of the .bai, whose cap of 2^29 bases is why this index exists.
+ *   File.   A BGZF stream that ends with the end-of-file block.  Its inflated bytes, little-endian:
+ *             magic "CSI\1", int32 min_shift, int32 depth, int32 l_aux, uint8 aux[l_aux], int32 n_ref;
+ *             per reference  int32 n_bin;
+ *             per bin        uint32 bin, uint64 loffset, int32 n_chunk, then n_chunk pairs uint64 beg, end;
+ *             optionally     uint64 n_no_coor.
+ *   Bins.   reg2bin(beg, end):
+ *               l = depth; s = min_shift; t = ((1 << 3*depth) - 1) / 7; --end
+ *               while l > 0:
+ *                   if beg >> s == end >> s: return t + (beg >> s)
+ *                   --l; s += 3; t -= 1 << 3*l
+ *               return 0
+ *           Level l (0 is the root) has 8^l bins from t_l = (8^l - 1) / 7 on, each of 2^s_l bases, s_l = min_shift + 3 (depth - l);
+ *           a bin of level l starts at (bin - t_l) << s_l.  The bins that may hold records overlapping [beg, end) are
+ *           t_l + (beg >> s_l) .. t_l + ((end - 1) >> s_l) at every level l.  The pseudo-bin is ((1 << 3 (depth + 1)) - 1) / 7 + 1
+ *           (37450 at depth 5) with two "chunks", (offset of the first record, end of the last) and (mapped, unmapped);
+ *           its loffset is 0.  The largest end an index can hold is 2^(min_shift + 3 depth).
+ *   What the builder writes.  Per record [beg, end), the chunks of a bin and the rule that joins them, bins in ascending
+ *           order, the pseudo-bin last and n_no_coor always: all as the .bai section above defines them.  l_aux = 0.
+ *           loffset(bin) is the virtual offset of the first record of the reference, in file order, whose end lies beyond
+ *           the start of the bin's interval: the back-filled linear index of granule 2^min_shift at the bin's first granule.
+ *           The builder keeps no such table.  Record r claims the granules max(beg >> min_shift, E(r) + 1) .. (end - 1) >>
+ *           min_shift (E(r): the largest last granule of the reference's earlier records), as for the .bai; the claims of a
+ *           reference are disjoint and ascending, and loffset(bin) is the offset of the first whose last granule is at or
+ *           beyond the bin's first -- a binary search, whatever min_shift is.
+ *   Parameters.  min_shift 1 .. 30, depth 0 .. 8, min_shift + 3 depth <= 54.  Where the caller leaves depth open
+ *           (bam.build_index(depth=None)) this library takes the smallest depth with 2^(min_shift + 3 depth) >= the longest
+ *           reference of the header + 256; this is the library's own rule.  Byte equality with the .csi files of other
+ *           programs is not claimed, as it is not for the .bai.
+ *   Query (bam.index_chunks).  The chunks of the bins above, without those that end at or below `low`, sorted and coalesced.
+ *           low is the largest loffset over the stored bins of the reference whose interval begins at or before beg (0
+ *           without one): a record that overlaps the region ends beyond beg, hence beyond such a bin's start.
+ *   dn_csi_create         dn_bai_create for a .csi index of (min_shift, depth).  The handle is a dn_bai: dn_bai_window,
+ *                         dn_bai_window_host, dn_bai_expect_crc, dn_bai_finish and dn_bai_destroy take it.  dn_bai_finish gives
+ *                         sizes[2] = 0 and dn_bai_fetch ref_n_intv = 0 and no ioffset entry (ioffset may be null).
+ *   dn_csi_loffset        after dn_bai_finish: loffset[sizes[0]], one per bin in the order of dn_bai_fetch's bin_id.
+ *                         DN_E_STATE on a dn_bai_create builder.
+ * Errors as for the .bai, but for the range: "<record> reaches beyond position 2^<min_shift + 3 depth>: a .csi index of
+ * min_shift <m> and depth <d> cannot hold it". */
+int  dn_csi_create(int device, int32_t n_ref, int64_t segment_bytes, int32_t min_shift, int32_t depth, dn_bai *out);
+int  dn_csi_loffset(dn_bai h, uint64_t *loffset);
+
 /* Coordinate sort of a BAM file (csrc/dn_sort.hip; degnorm_amd.bam.sort_bam) ----------------------------------------------
  * The order: records ascend by key = ref_key << 32 | (uint32) (pos + 1), where ref_key is refID, or the largest 32-bit
  * value for refID -1 -- unplaced records go last, and pos -1 sorts first within its reference -- and records of equal key

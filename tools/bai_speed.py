@@ -10,9 +10,11 @@ an index at deflate levels 1 and 6:
 The two modes run alternated, --reps times each after one warm-up each; every figure is reported as [minimum, maximum] over
 the repetitions.  `same` says whether the two wrote the same bytes.  When a samtools is on PATH, `samtools index -@ 16` is
 timed on the same file and its output compared with ours (`samtools_same`); otherwise samtools is "not compared with
-samtools".  Nothing is fetched.
+samtools".  Nothing is fetched.  --format csi times the .csi index instead (min_shift 14, the depth left to the library;
+its file is BGZF-compressed on the host, which e2e_ms includes); samtools is then not run.
 
     python tools/bai_speed.py [--reads 2000000] [--jobs 16] [--reps 3] [--levels 1,6] [--modes device,host] [--dir DIR]
+                              [--format bai|csi]
 
 Prints one JSON line.  Needs a GPU unless --modes host.
 """
@@ -42,14 +44,15 @@ def _span(values, digits=1):
     return [round(min(values), digits), round(max(values), digits)]
 
 
-def _level(path, modes, jobs, reps, verify=False):
+def _level(path, modes, jobs, reps, verify=False, fmt='bai'):
     rows = {m: [] for m in modes}
     out = {}
     for k in range(reps + 1):                        # the first round loads the library and warms the device up
         for m in modes:
             stats = {}
             t0 = time.perf_counter()
-            bam.create_index(path, path + '.' + m, overwrite=True, device=0 if m == 'device' else None, n_jobs=jobs, stats=stats, verify=verify)
+            bam.create_index(path, path + '.' + m, overwrite=True, device=0 if m == 'device' else None, n_jobs=jobs, stats=stats, verify=verify,
+                             fmt=fmt)
             stats['e2e_ms'] = 1e3 * (time.perf_counter() - t0)
             if k > 0:
                 rows[m].append(stats)
@@ -62,7 +65,7 @@ def _level(path, modes, jobs, reps, verify=False):
         with open(path + '.' + modes[0], 'rb') as fa, open(path + '.' + modes[1], 'rb') as fb:
             out['same'] = fa.read() == fb.read()
     out['bai_bytes'] = os.path.getsize(path + '.' + modes[0])
-    samtools = shutil.which('samtools')
+    samtools = shutil.which('samtools') if fmt == 'bai' else None
     if samtools is None:
         out['samtools'] = 'not compared with samtools'
     else:
@@ -86,6 +89,7 @@ def main():
     ap.add_argument('--levels', default='1,6')
     ap.add_argument('--modes', default='device,host')
     ap.add_argument('--dir', default=None)
+    ap.add_argument('--format', choices=('bai', 'csi'), default='bai', help='the index format to time')
     ap.add_argument('--verify', action='store_true', help='check every BGZF block against the CRC32 of its trailer')
     a = ap.parse_args()
     modes = [m for m in ('device', 'host') if m in a.modes.split(',')]
@@ -97,11 +101,13 @@ def main():
         out = {'tool': 'bai_speed', 'reads': a.reads, 'jobs': a.jobs, 'reps': a.reps, 'modes': modes}
         if a.verify:
             out['verify'] = True
+        if a.format != 'bai':
+            out['format'] = a.format
         for level in (int(x) for x in a.levels.split(',')):
             path = os.path.join(work, 'se_{0}_l{1}.bam'.format(a.reads, level))
             if not os.path.isfile(path):
                 bf.write_bam(path, [('chrS', chrom_len)], se, level=level, index=False)
-            row = _level(path, modes, a.jobs, a.reps, a.verify)
+            row = _level(path, modes, a.jobs, a.reps, a.verify, a.format)
             row['bam_mb'] = round(os.path.getsize(path) / 2 ** 20, 1)
             row['inflated_mb'] = round(int(bam.bgzf_blocks(path)[2].sum()) / 2 ** 20, 1)
             out['level{0}'.format(level)] = row
