@@ -5,14 +5,15 @@
 // the gene of an exon comes out of a join over the whole file.  So the file's text stays on the device for one load (a
 // handle owns one buffer of the file's size, padded to whole tiles and zeroed), and windows that end at line ends are
 // uploaded to their place in it.  Per window:
-//   1  k_count_newlines, k_scan, k_line_starts   where every line starts (dn_lines.hpp, shared with dn_gtf.hip and
+//   1  k_count_newlines, k_scan, k_line_starts   where every line starts (LineTable, dn_lines.hpp, shared with dn_gtf.hip and
 //                      dn_sam.hip), over the tiles the window touches; the lines of the first tile that belong to the
 //                      window before are not looked at again
 //   2  k_gff3_parse    one lane per line: exon row, node row, ##FASTA or nothing (gff3::parse_line), FNV-1a hashes of the
 //                      spans; the first faulty line and the first ##FASTA line by atomicMin
 //   3  k_gff3_mark     exon lines and node lines above the ##FASTA line, counted per 256-line block
-//   4  k_scan twice, k_gff3_compact twice: exon rows to a table that goes to the host, node rows to the end of the handle's
-//                      node store; both in file order, all offsets global to the file
+//   4  k_scan twice, k_compact twice (dn_annot.hpp, the exon table shared with dn_gtf.hip): exon rows to a table that goes
+//                      to the host, node rows to the end of the handle's node store, which has no line, start and end
+//                      columns; both in file order, all offsets global to the file
 // dn_gff3_resolve then sorts the node rows as (ID hash, ordinal) with hipcub::DeviceRadixSort::SortPairs -- a stable sort, so
 // nodes of one hash stay in file order -- and runs one lane per exon that named a Parent (k_gff3_walk, gff3::walk): a
 // lower-bound search on the hash, a scan of the run of that hash for the first node whose ID has the wanted bytes, at most
@@ -31,7 +32,7 @@
 #include <vector>
 #include "../../include/degnorm_amd.h"
 #include "dn_host.hpp"
-#include "dn_lines.hpp"
+#include "dn_annot.hpp"
 #include "dn_gff3.hpp"
 
 namespace {
@@ -39,37 +40,28 @@ namespace {
 namespace g3 = dn::gff3;
 
 constexpr int64_t kMaxWindow = (int64_t) 1 << 30;
-constexpr unsigned long long kNone = ~0ull;
-
-// the columns of the lines of a window (one entry per line), of the exon rows and of the node store
-struct Cols {
-    int64_t *line, *c_beg, *start, *end, *a_beg;
-    int32_t *c_len, *a_len;
-    uint64_t *c_hash, *a_hash;
-    uint8_t *open;
-};
 
 // Lane j takes line n_head + j of the tile range: the lines before belong to the window before.  Positions are relative to
 // the first tile, which starts at byte `base` of the file; line numbers count from line_base.
 __global__ __launch_bounds__(kNT) void k_gff3_parse(const uint8_t *__restrict__ buf, int64_t base, int64_t rel_end,
                                                      const int64_t *__restrict__ line_start, int64_t n_starts, int64_t n_head, int64_t line_base,
-                                                     uint64_t mask, Cols rec, uint8_t *__restrict__ kind,
+                                                     uint64_t mask, ExonCols rec, uint8_t *__restrict__ kind,
                                                      unsigned long long *__restrict__ first_error, unsigned long long *__restrict__ first_fasta)
 {
     const int64_t j = (int64_t) blockIdx.x * kNT + threadIdx.x, i = n_head + j;
     if (i >= n_starts) return;
-    const int64_t beg = line_start[i];
-    const int64_t end = i + 1 < n_starts ? line_start[i + 1] - 1 : rel_end;
-    const unsigned long long line = (unsigned long long) (line_base + j + 1);
+    int64_t beg, end;
+    line_span(line_start, n_starts, rel_end, i, &beg, &end);
+    const int64_t line = line_base + j + 1;
     Bytes b(buf);
     g3::Line L{0, 0, 0, 0, 0, 0, 0};
-    const int r = beg >= 0 && beg <= end && end <= rel_end ? g3::parse_line(b, beg, end, L) : g3::kSkip;
-    if (r < 0) atomicMin(first_error, (line << 8) | (unsigned long long) (-r));
-    if (r == g3::kFasta) atomicMin(first_fasta, line);
-    const bool row = r == g3::kExon || r == g3::kNode;
+    const int r = beg >= 0 && beg <= end && end <= rel_end ? g3::parse_line(b, beg, end, L) : dn::kSkip;
+    if (r < 0) report_error(first_error, line, -r);
+    if (r == g3::kFasta) atomicMin(first_fasta, (unsigned long long) line);
+    const bool row = r == dn::kExon || r == g3::kNode;
     if (row) {
-        const uint64_t c_hash = g3::fnv1a(b, L.c_lo, L.c_hi), a_hash = g3::fnv1a(b, L.a_lo, L.a_hi);
-        rec.line[j] = (int64_t) line;
+        const uint64_t c_hash = dn::fnv1a(b, L.c_lo, L.c_hi), a_hash = dn::fnv1a(b, L.a_lo, L.a_hi);
+        rec.line[j] = line;
         rec.c_beg[j] = base + L.c_lo;
         rec.c_len[j] = (int32_t) (L.c_hi - L.c_lo);
         rec.c_hash[j] = r == g3::kNode ? c_hash & mask : c_hash;
@@ -83,11 +75,6 @@ __global__ __launch_bounds__(kNT) void k_gff3_parse(const uint8_t *__restrict__ 
     kind[j] = (uint8_t) (row ? r : 0);
 }
 
-__device__ inline bool kept_as(int which, const uint8_t *__restrict__ kind, int64_t j, int64_t n_lanes, int64_t line_base, unsigned long long fasta)
-{
-    return j < n_lanes && kind[j] == (uint8_t) which && (unsigned long long) (line_base + j + 1) < fasta;
-}
-
 __global__ __launch_bounds__(kNT) void k_gff3_mark(const uint8_t *__restrict__ kind, int64_t n_lanes, int64_t line_base,
                                                     const unsigned long long *__restrict__ first_fasta, int32_t *__restrict__ block_exons,
                                                     int32_t *__restrict__ block_nodes)
@@ -95,34 +82,10 @@ __global__ __launch_bounds__(kNT) void k_gff3_mark(const uint8_t *__restrict__ k
     const int64_t j = (int64_t) blockIdx.x * kNT + threadIdx.x;
     const unsigned long long fasta = *first_fasta;
     int total;
-    (void) block_exclusive(kept_as(g3::kExon, kind, j, n_lanes, line_base, fasta) ? 1 : 0, &total);
+    (void) block_exclusive(kept_as(dn::kExon, kind, j, n_lanes, line_base, fasta) ? 1 : 0, &total);
     if (threadIdx.x == 0) block_exons[blockIdx.x] = total;
     (void) block_exclusive(kept_as(g3::kNode, kind, j, n_lanes, line_base, fasta) ? 1 : 0, &total);
     if (threadIdx.x == 0) block_nodes[blockIdx.x] = total;
-}
-
-// the lines of kind `which` to rows [0, n_rows) of `row`, in file order; a node row has no line, start and end
-__global__ __launch_bounds__(kNT) void k_gff3_compact(int which, const uint8_t *__restrict__ kind, int64_t n_lanes, int64_t line_base,
-                                                       const unsigned long long *__restrict__ first_fasta, const int64_t *__restrict__ block_off,
-                                                       Cols rec, Cols row, int64_t n_rows)
-{
-    const int64_t j = (int64_t) blockIdx.x * kNT + threadIdx.x;
-    const int kept = kept_as(which, kind, j, n_lanes, line_base, *first_fasta) ? 1 : 0;
-    int total;
-    const int64_t r = block_off[blockIdx.x] + block_exclusive(kept, &total);
-    if (!kept || r < 0 || r >= n_rows) return;
-    if (which == g3::kExon) {
-        row.line[r] = rec.line[j];
-        row.start[r] = rec.start[j];
-        row.end[r] = rec.end[j];
-    }
-    row.c_beg[r] = rec.c_beg[j];
-    row.c_len[r] = rec.c_len[j];
-    row.c_hash[r] = rec.c_hash[j];
-    row.a_beg[r] = rec.a_beg[j];
-    row.a_len[r] = rec.a_len[j];
-    row.a_hash[r] = rec.a_hash[j];
-    row.open[r] = rec.open[j];
 }
 
 __global__ __launch_bounds__(kNT) void k_gff3_iota(uint32_t *__restrict__ out, int64_t n)
@@ -146,34 +109,13 @@ __global__ __launch_bounds__(kNT) void k_gff3_walk(const uint8_t *__restrict__ b
     uint64_t hash = par_hash[i];
     const int e = g3::walk(want, have, N, &beg, &len, &hash);
     if (e) {
-        atomicMin(first_error, ((unsigned long long) line[i] << 8) | (unsigned long long) e);
+        report_error(first_error, line[i], e);
         beg = 0; len = 0; hash = 0;
     }
     name_beg[i] = beg;
     name_len[i] = len;
     name_hash[i] = hash;
 }
-
-struct ColBuffers {
-    dn::DeviceBuffer<int64_t> line, c_beg, start, end, a_beg;
-    dn::DeviceBuffer<int32_t> c_len, a_len;
-    dn::DeviceBuffer<uint64_t> c_hash, a_hash;
-    dn::DeviceBuffer<uint8_t> open;
-    hipError_t alloc(int64_t n)
-    {
-        const size_t m = (size_t) (n > 0 ? n : 1);
-        hipError_t e = hipSuccess;
-        for (dn::DeviceBuffer<int64_t> *b : {&line, &c_beg, &start, &end, &a_beg})
-            if (e == hipSuccess) e = b->alloc(m * sizeof(int64_t));
-        for (dn::DeviceBuffer<int32_t> *b : {&c_len, &a_len})
-            if (e == hipSuccess) e = b->alloc(m * sizeof(int32_t));
-        for (dn::DeviceBuffer<uint64_t> *b : {&c_hash, &a_hash})
-            if (e == hipSuccess) e = b->alloc(m * sizeof(uint64_t));
-        if (e == hipSuccess) e = open.alloc(m);
-        return e;
-    }
-    Cols view() const { return Cols{line, c_beg, start, end, a_beg, c_len, a_len, c_hash, a_hash, open}; }
-};
 
 // the node rows of the file so far, in file order: c = the ID (hash masked), a = the name or the Parent
 struct NodeStore {
@@ -192,19 +134,12 @@ struct NodeStore {
         if (e == hipSuccess) e = open.reserve(need, used, st);
         return e;
     }
-    Cols at(int64_t k) const
+    ExonCols at(int64_t k) const
     {
-        return Cols{nullptr, id_beg.get() + k, nullptr, nullptr, a_beg.get() + k, id_len.get() + k, a_len.get() + k, id_hash.get() + k,
+        return ExonCols{nullptr, id_beg.get() + k, nullptr, nullptr, a_beg.get() + k, id_len.get() + k, a_len.get() + k, id_hash.get() + k,
                     a_hash.get() + k, open.get() + k};
     }
 };
-
-int64_t count_newlines(const uint8_t *p, int64_t n)
-{
-    int64_t k = 0;
-    for (const uint8_t *e = p + n; (p = (const uint8_t *) memchr(p, '\n', (size_t) (e - p))) != nullptr; p++) k++;
-    return k;
-}
 
 }  // namespace
 
@@ -279,22 +214,21 @@ extern "C" int dn_gff3_window(dn_gff3 h, const uint8_t *bytes, int64_t n_bytes, 
     // what the stream reads or writes: owned here, so that it outlives the wait of dn::synced
     dn::Event e0, e1, e2;
     dn::DeviceBuffer<uint8_t> d_kind;
-    dn::DeviceBuffer<int32_t> d_tile_count, d_block_exons, d_block_nodes;
-    dn::DeviceBuffer<int64_t> d_tile_off, d_exon_off, d_node_off, d_line_start, d_total;
+    dn::DeviceBuffer<int32_t> d_block_exons, d_block_nodes;
+    dn::DeviceBuffer<int64_t> d_exon_off, d_node_off;
     dn::DeviceBuffer<unsigned long long> d_marks;                   // first error, first ##FASTA line
-    ColBuffers rec, row;
-    const unsigned long long none[2] = {kNone, kNone};
-    unsigned long long marks[2] = {kNone, kNone};
-    int64_t n_newlines = 0, n_exons = 0, n_new_nodes = 0;
+    LineTable lines;
+    ExonBuffers rec, row;
+    const unsigned long long none[2] = {kNoError, kNoFasta};
+    unsigned long long marks[2] = {kNoError, kNoFasta};
+    int64_t n_exons = 0, n_new_nodes = 0;
     DN_TRY(hipSetDevice(h->device));
     hipStream_t st = h->st;
     return dn::synced(st, [&]() -> int {
         DN_TRY(e0.create(hipEventCreate));
         DN_TRY(e1.create(hipEventCreate));
         DN_TRY(e2.create(hipEventCreate));
-        DN_TRY(d_tile_count.alloc(sizeof(int32_t) * (size_t) n_tiles));
-        DN_TRY(d_tile_off.alloc(sizeof(int64_t) * (size_t) n_tiles));
-        DN_TRY(d_total.alloc(sizeof(int64_t)));
+        DN_TRY(lines.alloc(n_tiles));
         DN_TRY(d_marks.alloc(sizeof(none)));
         DN_TRY(hipEventRecord(e0, st));
         DN_TRY(hipMemcpyAsync(h->buf.get() + h->pos, bytes, (size_t) n_bytes, hipMemcpyHostToDevice, st));
@@ -302,70 +236,58 @@ extern "C" int dn_gff3_window(dn_gff3 h, const uint8_t *bytes, int64_t n_bytes, 
         DN_TRY(hipEventRecord(e1, st));
 
         const uint8_t *tiles = h->buf.get() + base;                 // the tiles the window touches; behind rel_end they hold zeros
-        hipLaunchKernelGGL(k_count_newlines, dim3(grid_capped(n_tiles)), dim3(kNT), 0, st, (const uint4 *) tiles, n_tiles, d_tile_count.get());
-        hipLaunchKernelGGL(k_scan, dim3(1), dim3(kScanNT), 0, st, d_tile_count.get(), n_tiles, d_tile_off.get(), d_total.get());
-        DN_TRY(hipGetLastError());
-        DN_TRY(hipMemcpyAsync(&n_newlines, d_total, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        DN_TRY(hipStreamSynchronize(st));
-        if (n_newlines < n_head || n_newlines > rel_end) return dn::fail(DN_E_STATE, "dn_gff3_window: newline count out of range");
-
-        const int64_t n_starts = n_newlines + 1;                    // the last one starts an empty line when the bytes end in '\n'
+        const int rc = lines.find(st, tiles, n_tiles, n_head, rel_end, "dn_gff3_window");
+        if (rc != DN_OK) return rc;
+        const int64_t n_newlines = lines.n_newlines, n_starts = lines.n_starts;
         const int64_t n_lanes = n_starts - n_head;
         const int64_t n_blocks = (n_lanes + kNT - 1) / kNT;
-        DN_TRY(d_line_start.alloc(sizeof(int64_t) * (size_t) n_starts));
         DN_TRY(d_kind.alloc((size_t) n_lanes));
         DN_TRY(d_block_exons.alloc(sizeof(int32_t) * (size_t) n_blocks));
         DN_TRY(d_block_nodes.alloc(sizeof(int32_t) * (size_t) n_blocks));
         DN_TRY(d_exon_off.alloc(sizeof(int64_t) * (size_t) n_blocks));
         DN_TRY(d_node_off.alloc(sizeof(int64_t) * (size_t) n_blocks));
-        DN_TRY(rec.alloc(n_lanes));
-        DN_TRY(hipMemsetAsync(d_line_start, 0, sizeof(int64_t), st));
-        hipLaunchKernelGGL(k_line_starts, dim3(grid_capped(n_tiles)), dim3(kNT), 0, st, tiles, n_tiles, (const int64_t *) d_tile_off.get(),
-                           d_line_start.get(), n_starts);
-        hipLaunchKernelGGL(k_gff3_parse, dim3((unsigned) n_blocks), dim3(kNT), 0, st, tiles, base, rel_end, (const int64_t *) d_line_start.get(), n_starts,
-                           n_head, line_base, h->mask, rec.view(), d_kind.get(), d_marks.get(), d_marks.get() + 1);
+        DN_TRY(rec.alloc(n_lanes, true));
+        hipLaunchKernelGGL(k_gff3_parse, dim3((unsigned) n_blocks), dim3(kNT), 0, st, tiles, base, rel_end, (const int64_t *) lines.line_start.get(),
+                           n_starts, n_head, line_base, h->mask, rec.view(), d_kind.get(), d_marks.get(), d_marks.get() + 1);
         hipLaunchKernelGGL(k_gff3_mark, dim3((unsigned) n_blocks), dim3(kNT), 0, st, (const uint8_t *) d_kind.get(), n_lanes, line_base,
                            (const unsigned long long *) d_marks.get() + 1, d_block_exons.get(), d_block_nodes.get());
-        hipLaunchKernelGGL(k_scan, dim3(1), dim3(kScanNT), 0, st, d_block_exons.get(), n_blocks, d_exon_off.get(), d_total.get());
+        hipLaunchKernelGGL(k_scan, dim3(1), dim3(kScanNT), 0, st, d_block_exons.get(), n_blocks, d_exon_off.get(), lines.total.get());
         DN_TRY(hipGetLastError());
-        DN_TRY(hipMemcpyAsync(&n_exons, d_total, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        hipLaunchKernelGGL(k_scan, dim3(1), dim3(kScanNT), 0, st, d_block_nodes.get(), n_blocks, d_node_off.get(), d_total.get());
+        DN_TRY(hipMemcpyAsync(&n_exons, lines.total, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        hipLaunchKernelGGL(k_scan, dim3(1), dim3(kScanNT), 0, st, d_block_nodes.get(), n_blocks, d_node_off.get(), lines.total.get());
         DN_TRY(hipGetLastError());
-        DN_TRY(hipMemcpyAsync(&n_new_nodes, d_total, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        DN_TRY(hipMemcpyAsync(&n_new_nodes, lines.total, sizeof(int64_t), hipMemcpyDeviceToHost, st));
         DN_TRY(hipMemcpyAsync(marks, d_marks, sizeof(marks), hipMemcpyDeviceToHost, st));
         DN_TRY(hipStreamSynchronize(st));
 
         const int64_t win_lines = n_newlines - n_head + (bytes[n_bytes - 1] != '\n' ? 1 : 0);
-        const bool fasta = marks[1] != kNone;
-        const bool error = marks[0] != kNone && (!fasta || (marks[0] >> 8) < marks[1]);
+        const bool fasta = marks[1] != kNoFasta;
+        int64_t e_line = 0;
+        int32_t e_kind = 0;
+        const bool error = unpack_error(marks[0], &e_line, &e_kind) && (!fasta || (unsigned long long) e_line < marks[1]);
         *n_lines = win_lines;
         if (fasta) *fasta_line = (int64_t) marks[1];
         if (error) {
-            *err_line = (int64_t) (marks[0] >> 8);
-            *err_kind = (int32_t) (marks[0] & 0xffu);
+            *err_line = e_line;
+            *err_kind = e_kind;
             DN_TRY(hipEventRecord(e2, st));
         } else {
             if (n_exons < 0 || n_exons > n_lanes || n_new_nodes < 0 || n_new_nodes > n_lanes) return dn::fail(DN_E_STATE, "dn_gff3_window: row counts out of range");
             if (n_exons > row_cap) return dn::fail(DN_E_INVALID, "dn_gff3_window: more exon lines than the caller's tables hold");
             if (h->n_nodes + n_new_nodes > 0x7fffffffll) return dn::fail(DN_E_INVALID, "dn_gff3_window: more than 2^31 - 1 lines with an ID");
-            DN_TRY(row.alloc(n_exons));
+            DN_TRY(row.alloc(n_exons, true));
             DN_TRY(h->nodes.reserve(h->n_nodes + n_new_nodes, h->n_nodes, st));
             if (n_exons > 0)
-                hipLaunchKernelGGL(k_gff3_compact, dim3((unsigned) n_blocks), dim3(kNT), 0, st, (int) g3::kExon, (const uint8_t *) d_kind.get(), n_lanes,
+                hipLaunchKernelGGL(k_compact, dim3((unsigned) n_blocks), dim3(kNT), 0, st, (int) dn::kExon, (const uint8_t *) d_kind.get(), n_lanes,
                                    line_base, (const unsigned long long *) d_marks.get() + 1, (const int64_t *) d_exon_off.get(), rec.view(), row.view(),
                                    n_exons);
             if (n_new_nodes > 0)
-                hipLaunchKernelGGL(k_gff3_compact, dim3((unsigned) n_blocks), dim3(kNT), 0, st, (int) g3::kNode, (const uint8_t *) d_kind.get(), n_lanes,
+                hipLaunchKernelGGL(k_compact, dim3((unsigned) n_blocks), dim3(kNT), 0, st, (int) g3::kNode, (const uint8_t *) d_kind.get(), n_lanes,
                                    line_base, (const unsigned long long *) d_marks.get() + 1, (const int64_t *) d_node_off.get(), rec.view(),
                                    h->nodes.at(h->n_nodes), n_new_nodes);
             DN_TRY(hipGetLastError());
             DN_TRY(hipEventRecord(e2, st));
-#define GFF3_OUT(dst, src, T) do { if (n_exons > 0) DN_TRY(hipMemcpyAsync(dst, src, sizeof(T) * (size_t) n_exons, hipMemcpyDeviceToHost, st)); } while (0)
-            GFF3_OUT(line, row.line, int64_t); GFF3_OUT(chr_beg, row.c_beg, int64_t); GFF3_OUT(chr_len, row.c_len, int32_t);
-            GFF3_OUT(chr_hash, row.c_hash, uint64_t); GFF3_OUT(start, row.start, int64_t); GFF3_OUT(end, row.end, int64_t);
-            GFF3_OUT(gene_beg, row.a_beg, int64_t); GFF3_OUT(gene_len, row.a_len, int32_t); GFF3_OUT(gene_hash, row.a_hash, uint64_t);
-            GFF3_OUT(pending, row.open, uint8_t);
-#undef GFF3_OUT
+            DN_TRY(copy_rows(st, ExonCols{line, chr_beg, start, end, gene_beg, chr_len, gene_len, chr_hash, gene_hash, pending}, row.view(), n_exons));
         }
         DN_TRY(hipStreamSynchronize(st));
         if (copy_ms) { float ms = 0.f; DN_TRY(hipEventElapsedTime(&ms, e0, e1)); *copy_ms = ms; }
@@ -407,8 +329,7 @@ extern "C" int dn_gff3_resolve(dn_gff3 h, int64_t n, const int64_t *line, const 
     dn::DeviceBuffer<int32_t> d_par_len, d_name_len;
     dn::DeviceBuffer<unsigned long long> d_err;
     dn::Scratch scratch;
-    unsigned long long first_error = kNone;
-    const unsigned long long none = kNone;
+    unsigned long long first_error = kNoError;
     DN_TRY(hipSetDevice(h->device));
     hipStream_t st = h->st;
     return dn::synced(st, [&]() -> int {
@@ -429,7 +350,7 @@ extern "C" int dn_gff3_resolve(dn_gff3 h, int64_t n, const int64_t *line, const 
         DN_TRY(hipMemcpyAsync(d_par_beg, par_beg, sizeof(int64_t) * (size_t) n, hipMemcpyHostToDevice, st));
         DN_TRY(hipMemcpyAsync(d_par_len, par_len, sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, st));
         DN_TRY(hipMemcpyAsync(d_par_hash, par_hash, sizeof(uint64_t) * (size_t) n, hipMemcpyHostToDevice, st));
-        DN_TRY(hipMemcpyAsync(d_err, &none, sizeof(none), hipMemcpyHostToDevice, st));
+        DN_TRY(hipMemcpyAsync(d_err, &kNoError, sizeof(kNoError), hipMemcpyHostToDevice, st));
         DN_TRY(hipEventRecord(e1, st));
         if (m > 0) {
             hipLaunchKernelGGL(k_gff3_iota, dim3((unsigned) ((m + kNT - 1) / kNT)), dim3(kNT), 0, st, d_iota.get(), m);
@@ -451,10 +372,7 @@ extern "C" int dn_gff3_resolve(dn_gff3 h, int64_t n, const int64_t *line, const 
         DN_TRY(hipMemcpyAsync(name_len, d_name_len, sizeof(int32_t) * (size_t) n, hipMemcpyDeviceToHost, st));
         DN_TRY(hipMemcpyAsync(name_hash, d_name_hash, sizeof(uint64_t) * (size_t) n, hipMemcpyDeviceToHost, st));
         DN_TRY(hipStreamSynchronize(st));
-        if (first_error != kNone) {
-            *err_line = (int64_t) (first_error >> 8);
-            *err_kind = (int32_t) (first_error & 0xffu);
-        }
+        (void) unpack_error(first_error, err_line, err_kind);
         if (resolve_ms) { float ms = 0.f; DN_TRY(hipEventElapsedTime(&ms, e1, e2)); *resolve_ms = ms; }
         return DN_OK;
     });
@@ -471,7 +389,7 @@ extern "C" int dn_gff3_scan_host(const uint8_t *data, int64_t n_bytes, int32_t h
         return dn::fail(DN_E_INVALID, "dn_gff3_scan_host: bad argument");
     *n_lines = 0; *n_rows = 0; *n_nodes = 0; *n_walked = 0; *err_line = 0; *err_kind = 0;
     const uint64_t mask = g3::hash_mask(hash_bits);
-    g3::HostText in{data}, other{data};
+    dn::HostText in{data}, other{data};
     struct Exon { int64_t line, c_beg, start, end, a_beg; int32_t c_len, a_len; int open; };
     std::vector<Exon> exons;
     std::vector<int64_t> id_beg, a_beg;
@@ -493,11 +411,11 @@ extern "C" int dn_gff3_scan_host(const uint8_t *data, int64_t n_bytes, int32_t h
                 return DN_OK;
             }
             if (r == g3::kFasta) ended = true;
-            if (r == g3::kExon)
+            if (r == dn::kExon)
                 exons.push_back(Exon{lines + 1, L.c_lo, L.start, L.end, L.a_lo, (int32_t) (L.c_hi - L.c_lo), (int32_t) (L.a_hi - L.a_lo), L.open});
             if (r == g3::kNode) {
-                id_beg.push_back(L.c_lo); id_len.push_back((int32_t) (L.c_hi - L.c_lo)); id_hash.push_back(g3::fnv1a(in, L.c_lo, L.c_hi) & mask);
-                const uint64_t hh = g3::fnv1a(in, L.a_lo, L.a_hi);
+                id_beg.push_back(L.c_lo); id_len.push_back((int32_t) (L.c_hi - L.c_lo)); id_hash.push_back(dn::fnv1a(in, L.c_lo, L.c_hi) & mask);
+                const uint64_t hh = dn::fnv1a(in, L.a_lo, L.a_hi);
                 a_beg.push_back(L.a_lo); a_len.push_back((int32_t) (L.a_hi - L.a_lo)); a_hash.push_back(L.open ? hh & mask : hh);
                 open.push_back((uint8_t) L.open);
             }
@@ -519,7 +437,7 @@ extern "C" int dn_gff3_scan_host(const uint8_t *data, int64_t n_bytes, int32_t h
         const Exon &x = exons[k];
         int64_t g_beg = x.a_beg;
         int32_t g_len = x.a_len;
-        uint64_t g_hash = g3::fnv1a(in, x.a_beg, x.a_beg + x.a_len);
+        uint64_t g_hash = dn::fnv1a(in, x.a_beg, x.a_beg + x.a_len);
         if (x.open) {
             g_hash &= mask;
             walked++;
@@ -531,7 +449,7 @@ extern "C" int dn_gff3_scan_host(const uint8_t *data, int64_t n_bytes, int32_t h
                 return DN_OK;
             }
         }
-        line[k] = x.line; chr_beg[k] = x.c_beg; chr_len[k] = x.c_len; chr_hash[k] = g3::fnv1a(in, x.c_beg, x.c_beg + x.c_len);
+        line[k] = x.line; chr_beg[k] = x.c_beg; chr_len[k] = x.c_len; chr_hash[k] = dn::fnv1a(in, x.c_beg, x.c_beg + x.c_len);
         start[k] = x.start; end[k] = x.end; gene_beg[k] = g_beg; gene_len[k] = g_len; gene_hash[k] = g_hash;
     }
     *n_rows = (int64_t) exons.size();

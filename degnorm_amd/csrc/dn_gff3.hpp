@@ -1,8 +1,7 @@
 // dn_gff3.hpp -- one GFF3 line -> an exon row or a node row, and the walk from an exon's Parent to its gene
 // (include/degnorm_amd.h, "GFF3 annotation scan", defines both).  One source for both builds: parse_line and walk are
-// __host__ __device__ templates over a byte reader M, where at(pos) gives the byte at pos.  The device build reads aligned
-// 8-byte words of a buffer padded to whole tiles (Bytes, dn_lines.hpp); the host build reads the caller's bytes as they are
-// (HostText), so a read past a line's end is a read past the buffer for the last line and a sanitizer sees it.
+// __host__ __device__ templates over a byte reader M (dn_fields.hpp, which also has the field walk and the hash they share
+// with the GTF rule): Bytes on the device, HostText on the host.
 // Every read of parse_line lies in [beg, end) of its line; every read of walk lies inside a span that parse_line cut out of
 // a line.  walk makes at most kMaxLookups lookups, and the scan of a run of equal hashes ends at the run's end.
 #pragma once
@@ -10,22 +9,14 @@
 #include <stdint.h>
 
 #include "../../include/degnorm_amd.h"
-
-#ifndef DN_HD
-#define DN_HD __host__ __device__ inline
-#endif
+#include "dn_fields.hpp"
 
 namespace dn {
 namespace gff3 {
 
 constexpr int kMaxLookups = 8;
 
-struct HostText {
-    const uint8_t *p;
-    DN_HD uint32_t at(int64_t pos) const { return p[pos]; }
-};
-
-enum { kSkip = 0, kExon = 1, kNode = 2, kFasta = 3 };
+enum { kNode = 2, kFasta = 3 };         // besides kSkip and kExon (dn_fields.hpp)
 
 // What a line becomes.  An exon row: c = the chromosome name, start, end, a = its gene name (open 0) or the first element of
 // its Parent (open 1).  A node row: c = its ID, a = the name an exon that reaches it gets (open 0: gname, or rname when the
@@ -35,28 +26,7 @@ struct Line {
     int open;
 };
 
-template <class M> DN_HD uint64_t fnv1a(M &in, int64_t lo, int64_t hi)
-{
-    uint64_t h = 0xcbf29ce484222325ull;
-    for (int64_t p = lo; p < hi; p++) h = (h ^ in.at(p)) * 0x100000001b3ull;
-    return h;
-}
-
 DN_HD uint64_t hash_mask(int32_t hash_bits) { return hash_bits >= 64 ? ~0ull : hash_bits <= 0 ? 0ull : (1ull << hash_bits) - 1ull; }
-
-// [lo, hi) as a decimal integer of 1 .. 18 digits and nothing else
-template <class M> DN_HD bool parse_int(M &in, int64_t lo, int64_t hi, int64_t *out)
-{
-    if (hi <= lo || hi - lo > 18) return false;
-    int64_t v = 0;
-    for (int64_t p = lo; p < hi; p++) {
-        const uint32_t c = in.at(p);
-        if (c < '0' || c > '9') return false;
-        v = v * 10 + (int64_t) (c - '0');
-    }
-    *out = v;
-    return true;
-}
 
 // is [lo, hi) exactly `word` (n bytes)?
 template <class M> DN_HD bool is_word(M &in, int64_t lo, int64_t hi, const char *word, int n)
@@ -124,29 +94,15 @@ template <class M> DN_HD int parse_line(M &in, int64_t beg, int64_t end, Line &L
     if (end > beg && in.at(end - 1) == '\r') end--;
     if (end <= beg) return kSkip;
     if (in.at(beg) == '#') return is_word(in, beg, end, "##FASTA", 7) ? kFasta : kSkip;
-    int64_t t1 = 0, t2 = 0, t3 = 0, t4 = 0, t5 = 0, t8 = 0;
-    int nt = 0;
-    for (int64_t p = beg; p < end; p++) {
-        if (in.at(p) != '\t') continue;
-        nt++;
-        if (nt == 1) t1 = p;
-        else if (nt == 2) t2 = p;
-        else if (nt == 3) t3 = p;
-        else if (nt == 4) t4 = p;
-        else if (nt == 5) t5 = p;
-        else if (nt == 8) { t8 = p; break; }
-    }
-    if (nt < 8) return -DN_GFF3_E_FIELDS;
-    int64_t fe = t8 + 1;                                 // field nine ends at a further tab or at the line's end
+    NineFields F;
+    if (!nine_fields(in, beg, end, F)) return -DN_GFF3_E_FIELDS;
+    int64_t fe = F.t8 + 1;                               // field nine ends at a further tab or at the line's end
     while (fe < end && in.at(fe) != '\t') fe++;
-    bool exon = t3 - t2 - 1 == 4;
-    const char word[4] = {'e', 'x', 'o', 'n'};
-    for (int k = 0; k < 4 && exon; k++) exon = (in.at(t2 + 1 + k) | 0x20u) == (uint32_t) word[k];
     Tags T;
-    if (exon) {
-        if (!parse_int(in, t3 + 1, t4, &L.start) || !parse_int(in, t4 + 1, t5, &L.end)) return -DN_GFF3_E_INTEGER;
-        read_tags(in, t8 + 1, fe, T);
-        L.c_lo = beg; L.c_hi = t1;
+    if (is_exon(in, F)) {
+        if (!parse_uint(in, F.t3 + 1, F.t4, &L.start) || !parse_uint(in, F.t4 + 1, F.t5, &L.end)) return -DN_GFF3_E_INTEGER;
+        read_tags(in, F.t8 + 1, fe, T);
+        L.c_lo = beg; L.c_hi = F.t1;
         L.open = 0;
         if (T.gname_hi > T.gname_lo) { L.a_lo = T.gname_lo; L.a_hi = T.gname_hi; }
         else if (T.gene_hi > T.gene_lo) { L.a_lo = T.gene_lo; L.a_hi = T.gene_hi; }
@@ -155,7 +111,7 @@ template <class M> DN_HD int parse_line(M &in, int64_t beg, int64_t end, Line &L
         else return -DN_GFF3_E_GENE;
         return kExon;
     }
-    read_tags(in, t8 + 1, fe, T);
+    read_tags(in, F.t8 + 1, fe, T);
     if (T.id_hi <= T.id_lo) return kSkip;
     L.c_lo = T.id_lo; L.c_hi = T.id_hi;
     L.start = 0; L.end = 0;

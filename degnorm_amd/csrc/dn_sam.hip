@@ -2,9 +2,10 @@
 // "SAM text to BAM records", defines the encoding and dn_sam.hpp holds it, one source for both builds).
 //
 // A window of alignment lines that ends at a line end goes to the GPU and comes back as the record stream, in input order:
-//   1  k_count_newlines, k_scan, k_line_starts   where every line starts (dn_lines.hpp, shared with dn_gtf.hip)
+//   1  k_count_newlines, k_scan, k_line_starts   where every line starts (LineTable, dn_lines.hpp, shared with dn_gtf.hip and
+//                      dn_gff3.hip)
 //   2  k_sam_measure   one lane per line: every field checked, the record's size and its number of float payloads; the
-//                      first faulty line in file order by atomicMin on (line << 8 | kind), as in k_parse_lines
+//                      first faulty line in file order by atomicMin (report_error, dn_lines.hpp)
 //   3  hipcub::DeviceScan::ExclusiveSum of the sizes -> the record offsets, and of the payload counts -> the first patch
 //                      entry of every line; both over n_lines + 1 entries, so the last one is the total
 //   4  k_sam_emit      one lane per line: the record to its offset, byte by byte with ordinary vector stores, and the
@@ -33,13 +34,6 @@ using dn::sam::Refs;
 
 constexpr int64_t kMaxWindow = (int64_t) 1 << 30;
 
-// the line i of n_lines: [beg, end) without its '\n'; n_starts = the number of '\n' + 1 entries of line_start
-__device__ inline void line_span(const int64_t *__restrict__ line_start, int64_t n_starts, int64_t n_bytes, int64_t i, int64_t *beg, int64_t *end)
-{
-    *beg = line_start[i];
-    *end = i + 1 < n_starts ? line_start[i + 1] - 1 : n_bytes;
-}
-
 // size[i], n_float[i] for i < n_lines, and 0 in entry n_lines, which makes the exclusive sums end with the totals
 __global__ __launch_bounds__(kNT) void k_sam_measure(const uint8_t *__restrict__ buf, int64_t n_bytes, const int64_t *__restrict__ line_start,
                                                       int64_t n_starts, int64_t n_lines, Refs R, int64_t *__restrict__ size,
@@ -54,7 +48,7 @@ __global__ __launch_bounds__(kNT) void k_sam_measure(const uint8_t *__restrict__
         Bytes b(buf);
         const int e = beg <= end && end <= n_bytes ? dn::sam::encode_line<Bytes, false>(b, beg, end, R, nullptr, 0, 0, nullptr, 0, L) : DN_SAM_E_EMPTY;
         if (e) {
-            atomicMin(first_error, ((unsigned long long) (i + 1) << 8) | (unsigned long long) e);
+            report_error(first_error, i + 1, e);
             L.size = 0; L.n_float = 0;
         }
     }
@@ -90,13 +84,6 @@ int check_refs(const char *who, int32_t n_ref, const uint64_t *hash, const int32
         if (k > 0 && hash[k] < hash[k - 1]) return dn::fail(DN_E_INVALID, std::string(who) + ": the reference table is not sorted by hash");
     }
     return DN_OK;
-}
-
-int64_t count_lines(const uint8_t *text, int64_t n_bytes)
-{
-    int64_t n = 0;
-    for (const uint8_t *p = text, *e = text + n_bytes; (p = (const uint8_t *) memchr(p, '\n', (size_t) (e - p))) != nullptr; p++) n++;
-    return n + (text[n_bytes - 1] != '\n' ? 1 : 0);
 }
 
 // the float payloads: the text of entry k -- up to ',', a tab, the line end or the end of the bytes -- through strtod
@@ -145,7 +132,7 @@ extern "C" int dn_sam_encode_host(const uint8_t *text, int64_t n_bytes, int32_t 
     if (rc == DN_OK) rc = check_refs("dn_sam_encode_host", n_ref, ref_hash, ref_id, ref_name_beg, ref_name_len, names, n_names);
     if (rc != DN_OK) return rc;
     const Refs R{n_ref, ref_hash, ref_id, ref_name_beg, ref_name_len, names};
-    const int64_t lines = count_lines(text, n_bytes);
+    const int64_t lines = count_newlines(text, n_bytes) + (text[n_bytes - 1] != '\n' ? 1 : 0);
     *n_lines = lines;
     // where the lines start, then the measure pass
     std::vector<int64_t> start((size_t) lines + 1), off((size_t) lines + 1), foff((size_t) lines + 1);
@@ -156,11 +143,11 @@ extern "C" int dn_sam_encode_host(const uint8_t *text, int64_t n_bytes, int32_t 
         pos = nl ? (int64_t) (nl - text) + 1 : n_bytes + 1;
     }
     start[(size_t) lines] = pos;                                // one behind the '\n' of the last line, or n_bytes + 1 without one
-    dn::sam::HostText in{text};
+    dn::HostText in{text};
     int64_t total = 0, n_float = 0;
     for (int64_t i = 0; i < lines; i++) {
         LineSize L;
-        const int e = dn::sam::encode_line<dn::sam::HostText, false>(in, start[(size_t) i], start[(size_t) i + 1] - 1, R, nullptr, 0, 0, nullptr, 0, L);
+        const int e = dn::sam::encode_line<dn::HostText, false>(in, start[(size_t) i], start[(size_t) i + 1] - 1, R, nullptr, 0, 0, nullptr, 0, L);
         if (e) {
             *err_line = i + 1;
             *err_kind = e;
@@ -178,7 +165,7 @@ extern "C" int dn_sam_encode_host(const uint8_t *text, int64_t n_bytes, int32_t 
     for (int64_t i = 0; i < lines; i++) {
         LineSize L;
         const int64_t o = off[(size_t) i], f = foff[(size_t) i];
-        (void) dn::sam::encode_line<dn::sam::HostText, true>(in, start[(size_t) i], start[(size_t) i + 1] - 1, R, out + o, off[(size_t) i + 1] - o, o,
+        (void) dn::sam::encode_line<dn::HostText, true>(in, start[(size_t) i], start[(size_t) i + 1] - 1, R, out + o, off[(size_t) i + 1] - o, o,
                                                              patch ? patch + 2 * f : nullptr, foff[(size_t) i + 1] - f, L);
     }
     memcpy(rec_off, off.data(), sizeof(int64_t) * (size_t) (lines + 1));
@@ -204,14 +191,14 @@ extern "C" int dn_sam_encode(int device, const uint8_t *text, int64_t n_bytes, i
     dn::Stream st;
     dn::Event e0, e1, e2;
     dn::DeviceBuffer<uint8_t> d_buf, d_names, d_out;
-    dn::DeviceBuffer<int32_t> d_tile_count, d_ref_id, d_ref_len;
+    dn::DeviceBuffer<int32_t> d_ref_id, d_ref_len;
     dn::DeviceBuffer<uint64_t> d_ref_hash;
-    dn::DeviceBuffer<int64_t> d_tile_off, d_line_start, d_total, d_ref_beg, d_size, d_float, d_rec_off, d_patch_off, d_patch;
+    dn::DeviceBuffer<int64_t> d_ref_beg, d_size, d_float, d_rec_off, d_patch_off, d_patch;
     dn::DeviceBuffer<unsigned long long> d_err;
+    LineTable table;
     dn::Scratch scratch;
-    const unsigned long long no_error = ~0ull;
-    unsigned long long first_error = no_error;
-    int64_t n_newlines = 0, total = 0, floats = 0;
+    unsigned long long first_error = kNoError;
+    int64_t total = 0, floats = 0;
     DN_TRY(hipSetDevice(device));
     DN_TRY(st.create(hipStreamCreate));
     return dn::synced(st, [&]() -> int {
@@ -219,9 +206,7 @@ extern "C" int dn_sam_encode(int device, const uint8_t *text, int64_t n_bytes, i
         DN_TRY(e1.create(hipEventCreate));
         DN_TRY(e2.create(hipEventCreate));
         DN_TRY(d_buf.alloc((size_t) padded));
-        DN_TRY(d_tile_count.alloc(sizeof(int32_t) * (size_t) n_tiles));
-        DN_TRY(d_tile_off.alloc(sizeof(int64_t) * (size_t) n_tiles));
-        DN_TRY(d_total.alloc(sizeof(int64_t)));
+        DN_TRY(table.alloc(n_tiles));
         DN_TRY(d_err.alloc(sizeof(unsigned long long)));
         DN_TRY(d_ref_hash.alloc(sizeof(uint64_t) * n_tab));
         DN_TRY(d_ref_id.alloc(sizeof(int32_t) * n_tab));
@@ -229,9 +214,8 @@ extern "C" int dn_sam_encode(int device, const uint8_t *text, int64_t n_bytes, i
         DN_TRY(d_ref_len.alloc(sizeof(int32_t) * n_tab));
         DN_TRY(d_names.alloc((size_t) (n_names > 0 ? n_names : 1)));
         DN_TRY(hipEventRecord(e0, st));
-        DN_TRY(hipMemcpyAsync(d_buf, text, (size_t) n_bytes, hipMemcpyHostToDevice, st));
-        if (padded > n_bytes) DN_TRY(hipMemsetAsync(d_buf.get() + n_bytes, 0, (size_t) (padded - n_bytes), st));
-        DN_TRY(hipMemcpyAsync(d_err, &no_error, sizeof(no_error), hipMemcpyHostToDevice, st));
+        DN_TRY(upload_padded(st, d_buf, text, n_bytes, padded));
+        DN_TRY(hipMemcpyAsync(d_err, &kNoError, sizeof(kNoError), hipMemcpyHostToDevice, st));
         if (n_ref > 0) {
             DN_TRY(hipMemcpyAsync(d_ref_hash, ref_hash, sizeof(uint64_t) * (size_t) n_ref, hipMemcpyHostToDevice, st));
             DN_TRY(hipMemcpyAsync(d_ref_id, ref_id, sizeof(int32_t) * (size_t) n_ref, hipMemcpyHostToDevice, st));
@@ -241,29 +225,20 @@ extern "C" int dn_sam_encode(int device, const uint8_t *text, int64_t n_bytes, i
         if (n_names > 0) DN_TRY(hipMemcpyAsync(d_names, names, (size_t) n_names, hipMemcpyHostToDevice, st));
         DN_TRY(hipEventRecord(e1, st));
 
-        hipLaunchKernelGGL(k_count_newlines, dim3(grid_capped(n_tiles)), dim3(kNT), 0, st, (const uint4 *) d_buf.get(), n_tiles, d_tile_count.get());
-        hipLaunchKernelGGL(k_scan, dim3(1), dim3(kScanNT), 0, st, d_tile_count.get(), n_tiles, d_tile_off.get(), d_total.get());
-        DN_TRY(hipGetLastError());
-        DN_TRY(hipMemcpyAsync(&n_newlines, d_total, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        DN_TRY(hipStreamSynchronize(st));
-        if (n_newlines < 0 || n_newlines > n_bytes) return dn::fail(DN_E_STATE, "dn_sam_encode: newline count out of range");
-
-        const int64_t n_starts = n_newlines + 1;                       // the last one starts an empty line when the bytes end in '\n'
-        const int64_t lines = n_newlines + (text[n_bytes - 1] != '\n' ? 1 : 0);
+        const int find_rc = table.find(st, d_buf, n_tiles, 0, n_bytes, "dn_sam_encode");
+        if (find_rc != DN_OK) return find_rc;
+        const int64_t n_starts = table.n_starts;
+        const int64_t lines = table.n_newlines + (text[n_bytes - 1] != '\n' ? 1 : 0);
         const size_t n_per_line = sizeof(int64_t) * (size_t) (lines + 1);
         const unsigned n_blocks = (unsigned) ((lines + 1 + kNT - 1) / kNT);
         const Refs R{n_ref, d_ref_hash.get(), d_ref_id.get(), d_ref_beg.get(), d_ref_len.get(), d_names.get()};
         *n_lines = lines;
-        DN_TRY(d_line_start.alloc(sizeof(int64_t) * (size_t) n_starts));
         DN_TRY(d_size.alloc(n_per_line));
         DN_TRY(d_float.alloc(n_per_line));
         DN_TRY(d_rec_off.alloc(n_per_line));
         DN_TRY(d_patch_off.alloc(n_per_line));
-        DN_TRY(hipMemsetAsync(d_line_start, 0, sizeof(int64_t), st));
-        hipLaunchKernelGGL(k_line_starts, dim3(grid_capped(n_tiles)), dim3(kNT), 0, st, (const uint8_t *) d_buf.get(), n_tiles,
-                           (const int64_t *) d_tile_off.get(), d_line_start.get(), n_starts);
         hipLaunchKernelGGL(k_sam_measure, dim3(n_blocks), dim3(kNT), 0, st, (const uint8_t *) d_buf.get(), n_bytes,
-                           (const int64_t *) d_line_start.get(), n_starts, lines, R, d_size.get(), d_float.get(), d_err.get());
+                           (const int64_t *) table.line_start.get(), n_starts, lines, R, d_size.get(), d_float.get(), d_err.get());
         DN_TRY(hipGetLastError());
         DN_TRY(scratch.run([&](void *tmp, size_t &bytes) {
             return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, (const int64_t *) d_size.get(), d_rec_off.get(), (int) (lines + 1), st);
@@ -276,9 +251,7 @@ extern "C" int dn_sam_encode(int device, const uint8_t *text, int64_t n_bytes, i
         DN_TRY(hipMemcpyAsync(&floats, d_patch_off.get() + lines, sizeof(int64_t), hipMemcpyDeviceToHost, st));
         DN_TRY(hipStreamSynchronize(st));
 
-        if (first_error != no_error) {
-            *err_line = (int64_t) (first_error >> 8);
-            *err_kind = (int32_t) (first_error & 0xffu);
+        if (unpack_error(first_error, err_line, err_kind)) {
             DN_TRY(hipEventRecord(e2, st));
         } else {
             if (total < 0 || floats < 0) return dn::fail(DN_E_STATE, "dn_sam_encode: sizes out of range");
@@ -288,7 +261,7 @@ extern "C" int dn_sam_encode(int device, const uint8_t *text, int64_t n_bytes, i
             DN_TRY(d_patch.alloc(sizeof(int64_t) * 2 * (size_t) (floats > 0 ? floats : 1)));
             if (lines > 0) {
                 hipLaunchKernelGGL(k_sam_emit, dim3((unsigned) ((lines + kNT - 1) / kNT)), dim3(kNT), 0, st, (const uint8_t *) d_buf.get(), n_bytes,
-                                   (const int64_t *) d_line_start.get(), n_starts, lines, R, (const int64_t *) d_rec_off.get(),
+                                   (const int64_t *) table.line_start.get(), n_starts, lines, R, (const int64_t *) d_rec_off.get(),
                                    (const int64_t *) d_patch_off.get(), d_out.get(), total, d_patch.get(), floats);
                 DN_TRY(hipGetLastError());
             }
@@ -298,7 +271,7 @@ extern "C" int dn_sam_encode(int device, const uint8_t *text, int64_t n_bytes, i
             if (floats > 0) DN_TRY(hipMemcpyAsync(patch, d_patch, sizeof(int64_t) * 2 * (size_t) floats, hipMemcpyDeviceToHost, st));
         }
         DN_TRY(hipStreamSynchronize(st));
-        if (first_error == no_error) {
+        if (first_error == kNoError) {
             for (int64_t k = 0; k < floats; k++)           // the device wrote these: hold them to the arrays before they are used
                 if (patch[2 * k] < 0 || patch[2 * k] + 4 > total || patch[2 * k + 1] < 0 || patch[2 * k + 1] >= n_bytes)
                     return dn::fail(DN_E_STATE, "dn_sam_encode: patch entry out of range");

@@ -1,8 +1,7 @@
 // dn_sam.hpp -- one SAM alignment line -> one BAM record (include/degnorm_amd.h, "SAM text to BAM records", defines the
 // encoding).  One source for both builds: encode_line is __host__ __device__ code against two policies,
-//   M   where the text is read: at(pos) gives the byte at pos.  The device build reads aligned 8-byte words of a buffer
-//       padded to whole tiles (Bytes, dn_lines.hpp); the host build reads the caller's bytes as they are (HostText), so a
-//       read past a line's end is a read past the buffer for the last line and a sanitizer sees it.
+//   M   where the text is read (dn_fields.hpp, which also has the hash, the digits and the word test used here): Bytes on
+//       the device, HostText on the host.
 //   E   whether the record is written.  encode_line<M, false> walks the line, checks every field and returns
 //       the record's size and its number of float payloads; encode_line<M, true> walks it again and writes every byte of
 //       the record except the float payloads, for which it notes (place in the record stream, place in the text).
@@ -14,6 +13,7 @@
 
 #include "../../include/degnorm_amd.h"
 #include "dn_bam_record.hpp"
+#include "dn_fields.hpp"
 
 namespace dn {
 namespace sam {
@@ -27,11 +27,6 @@ struct Refs {
     const int64_t *name_beg;
     const int32_t *name_len;
     const uint8_t *names;
-};
-
-struct HostText {
-    const uint8_t *p;
-    DN_HD uint32_t at(int64_t pos) const { return p[pos]; }
 };
 
 // what a line becomes: the bytes of its record, block_size word included, and its float payloads
@@ -55,13 +50,6 @@ constexpr int64_t kMaxCigarLen = (1 << 28) - 1;         // an op is len << 4 | c
 constexpr int kMaxCigarOps = 65535;
 constexpr int kMaxName = 254;
 
-template <class M> DN_HD uint64_t fnv1a(M &in, int64_t lo, int64_t hi)
-{
-    uint64_t h = 0xcbf29ce484222325ull;
-    for (int64_t p = lo; p < hi; p++) h = (h ^ in.at(p)) * 0x100000001b3ull;
-    return h;
-}
-
 // the end of the field that starts at a: the next tab, or end
 template <class M> DN_HD int64_t field_end(M &in, int64_t a, int64_t end)
 {
@@ -77,13 +65,8 @@ template <class M> DN_HD bool parse_int(M &in, int64_t lo, int64_t hi, bool sign
         const uint32_t c = in.at(lo);
         if ((c == '-' && sign) || (c == '+' && plus)) { neg = c == '-'; lo++; }
     }
-    if (hi <= lo || hi - lo > 18) return false;
     int64_t v = 0;
-    for (int64_t p = lo; p < hi; p++) {
-        const uint32_t c = in.at(p);
-        if (c < '0' || c > '9') return false;
-        v = v * 10 + (int64_t) (c - '0');
-    }
+    if (!parse_uint(in, lo, hi, &v)) return false;
     *out = neg ? -v : v;
     return true;
 }
@@ -91,15 +74,6 @@ template <class M> DN_HD bool parse_int(M &in, int64_t lo, int64_t hi, bool sign
 template <class M> DN_HD bool parse_range(M &in, int64_t lo, int64_t hi, bool sign, int64_t vmin, int64_t vmax, int64_t *out)
 {
     return parse_int(in, lo, hi, sign, false, out) && *out >= vmin && *out <= vmax;
-}
-
-// does [lo, hi) spell `word` (n lower-case letters) in any letter case?
-template <class M> DN_HD bool spells(M &in, int64_t lo, int64_t hi, const char *word, int n)
-{
-    if (hi - lo != n) return false;
-    for (int k = 0; k < n; k++)
-        if ((in.at(lo + k) | 0x20u) != (uint32_t) word[k]) return false;
-    return true;
 }
 
 // [lo, hi) is text strtod reads whole as a decimal number: [+-] then inf, infinity, nan, or digits with at most one '.'

@@ -46,8 +46,25 @@ _GFF3_KINDS = {1: 'must have the 9 mandatory .gff3 columns.\nRead more at https:
                3: 'is an exon record whose start or end is not an integer.',
                4: 'is an exon record whose chain of Parent attributes names an ID that no record has.',
                5: 'is an exon record whose chain of Parent attributes does not reach a gene within 8 records.'}
-_GFF3_COLS = (('line', np.int64), ('chr_beg', np.int64), ('chr_len', np.int32), ('chr_hash', np.uint64), ('start', np.int64),
+# the columns of an exon row, in the order the C entries of both scanners take them
+_EXON_COLS = (('line', np.int64), ('chr_beg', np.int64), ('chr_len', np.int32), ('chr_hash', np.uint64), ('start', np.int64),
               ('end', np.int64), ('gene_beg', np.int64), ('gene_len', np.int32), ('gene_hash', np.uint64))
+_C_TYPES = {np.int64: ctypes.c_int64, np.int32: ctypes.c_int32, np.uint64: ctypes.c_uint64}
+
+
+def _exon_cols(cap):
+    """Exon columns of `cap` rows for a C entry to fill: (dict of arrays, their pointers as arguments)."""
+    cols = {k: np.empty(cap, dtype=t) for k, t in _EXON_COLS}
+    return cols, [_lib._p(cols[k], _C_TYPES[t]) for k, t in _EXON_COLS]
+
+
+def _error(err_line, err_kind):
+    """(error line, error kind) of a C entry's two outputs, or None."""
+    return (int(err_line.value), int(err_kind.value)) if err_kind.value else None
+
+
+def _device(device):
+    return int(os.environ.get('LOCAL_RANK', 0)) if device is None else int(device)
 
 
 class Loader(object):
@@ -79,22 +96,15 @@ def scan_window(buf, device=None):
     lib = _lib.load()
     a = np.frombuffer(buf, dtype=np.uint8)
     cap = a.size // 20 + 1
-    i64, i32, u64 = ctypes.c_int64, ctypes.c_int32, ctypes.c_uint64
-    cols = {k: np.empty(cap, dtype=t) for k, t in (('line', np.int64), ('chr_beg', np.int64), ('chr_len', np.int32),
-                                                  ('chr_hash', np.uint64), ('start', np.int64), ('end', np.int64),
-                                                  ('gene_beg', np.int64), ('gene_len', np.int32), ('gene_hash', np.uint64))}
-    n_lines, n_rows, err_line, err_kind = i64(0), i64(0), i64(0), i32(0)
+    cols, col_args = _exon_cols(cap)
+    i64 = ctypes.c_int64
+    n_lines, n_rows, err_line, err_kind = i64(0), i64(0), i64(0), ctypes.c_int32(0)
     copy_ms, dev_ms = ctypes.c_double(0.0), ctypes.c_double(0.0)
-    dev = int(os.environ.get('LOCAL_RANK', 0)) if device is None else int(device)
-    rc = lib.dn_gtf_scan(dev, _lib._p(a, ctypes.c_uint8), a.size, cap, ctypes.byref(n_lines), ctypes.byref(n_rows),
-                         _lib._p(cols['line'], i64), _lib._p(cols['chr_beg'], i64), _lib._p(cols['chr_len'], i32),
-                         _lib._p(cols['chr_hash'], u64), _lib._p(cols['start'], i64), _lib._p(cols['end'], i64),
-                         _lib._p(cols['gene_beg'], i64), _lib._p(cols['gene_len'], i32), _lib._p(cols['gene_hash'], u64),
-                         ctypes.byref(err_line), ctypes.byref(err_kind), ctypes.byref(copy_ms), ctypes.byref(dev_ms))
+    rc = lib.dn_gtf_scan(_device(device), _lib._p(a, ctypes.c_uint8), a.size, cap, ctypes.byref(n_lines), ctypes.byref(n_rows),
+                         *(col_args + [ctypes.byref(err_line), ctypes.byref(err_kind), ctypes.byref(copy_ms), ctypes.byref(dev_ms)]))
     _lib._check(rc, 'dn_gtf_scan')
     n = int(n_rows.value)
-    err = (int(err_line.value), int(err_kind.value)) if err_kind.value else None
-    return int(n_lines.value), {k: v[:n] for k, v in cols.items()}, err, float(copy_ms.value), float(dev_ms.value)
+    return int(n_lines.value), {k: v[:n] for k, v in cols.items()}, _error(err_line, err_kind), float(copy_ms.value), float(dev_ms.value)
 
 
 def _same_bytes(a, beg, other, length):
@@ -155,16 +165,18 @@ def iter_windows(filename, window_bytes):
 
 
 class GeneAnnotationLoader(Loader):
+    FILETYPES = '.gtf'
 
     def __init__(self, to_load, window_bytes=None, device=None):
         """
         .gtf file loader on the device.
 
-        :param to_load: str the realpath to a .gtf file.
-        :param window_bytes: the file is scanned in windows of about this many bytes, cut at line ends (default WINDOW_BYTES).
+        :param to_load: str the realpath to a file that ends with FILETYPES.
+        :param window_bytes: the file is uploaded and scanned in windows of about this many bytes, cut at line ends (default
+        WINDOW_BYTES); the table and the errors do not depend on it.
         :param device: HIP device index (default: LOCAL_RANK or 0).
         """
-        Loader.__init__(self, '.gtf')
+        Loader.__init__(self, self.FILETYPES)
         self.get_file(to_load)
         self.window_bytes = max(int(WINDOW_BYTES if window_bytes is None else window_bytes), 1)
         self.device = device
@@ -215,10 +227,6 @@ class GeneAnnotationLoader(Loader):
                           'gene': np.array(gene_names, dtype=object)[gene_code[keep]] if gene_names else np.zeros(0, dtype=object)})
 
 
-def _gff3_col_args(cols):
-    return [_lib._p(cols[k], {np.int64: ctypes.c_int64, np.int32: ctypes.c_int32, np.uint64: ctypes.c_uint64}[t]) for k, t in _GFF3_COLS]
-
-
 class Gff3Scan(object):
     """
     One load of a GFF3 text of total_bytes on the device (dn_gff3_open ... dn_gff3_close): `window(buf)` for every piece of the
@@ -229,8 +237,7 @@ class Gff3Scan(object):
     def __init__(self, total_bytes, device=None, hash_bits=64):
         self.lib = _lib.load()
         self.h = ctypes.c_void_p(None)
-        dev = int(os.environ.get('LOCAL_RANK', 0)) if device is None else int(device)
-        _lib._check(self.lib.dn_gff3_open(dev, int(total_bytes), int(hash_bits), ctypes.byref(self.h)), 'dn_gff3_open')
+        _lib._check(self.lib.dn_gff3_open(_device(device), int(total_bytes), int(hash_bits), ctypes.byref(self.h)), 'dn_gff3_open')
         self.lines, self.fasta_line, self.nodes = 0, 0, 0
 
     def __enter__(self):
@@ -252,22 +259,21 @@ class Gff3Scan(object):
         """
         a = np.frombuffer(buf, dtype=np.uint8)
         cap = a.size // 20 + 1
-        cols = {k: np.empty(cap, dtype=t) for k, t in _GFF3_COLS}
+        cols, col_args = _exon_cols(cap)
         pending = np.empty(cap, dtype=np.uint8)
         i64 = ctypes.c_int64
         n_lines, n_rows, fasta, err_line, err_kind = i64(0), i64(0), i64(0), i64(0), ctypes.c_int32(0)
         copy_ms, dev_ms = ctypes.c_double(0.0), ctypes.c_double(0.0)
         rc = self.lib.dn_gff3_window(self.h, _lib._p(a, ctypes.c_uint8), a.size, cap, ctypes.byref(n_lines), ctypes.byref(n_rows),
-                                     *(_gff3_col_args(cols) + [_lib._p(pending, ctypes.c_uint8), ctypes.byref(fasta), ctypes.byref(err_line),
-                                                               ctypes.byref(err_kind), ctypes.byref(copy_ms), ctypes.byref(dev_ms)]))
+                                     *(col_args + [_lib._p(pending, ctypes.c_uint8), ctypes.byref(fasta), ctypes.byref(err_line),
+                                                   ctypes.byref(err_kind), ctypes.byref(copy_ms), ctypes.byref(dev_ms)]))
         _lib._check(rc, 'dn_gff3_window')
         n = int(n_rows.value)
         self.lines += int(n_lines.value)
         self.fasta_line = int(fasta.value)
         cols = {k: v[:n] for k, v in cols.items()}
         cols['pending'] = pending[:n]
-        err = (int(err_line.value), int(err_kind.value)) if err_kind.value else None
-        return cols, err, float(copy_ms.value), float(dev_ms.value)
+        return cols, _error(err_line, err_kind), float(copy_ms.value), float(dev_ms.value)
 
     def resolve(self, line, par_beg, par_len, par_hash):
         """dn_gff3_resolve: (name_beg, name_len, name_hash of every pending row, (error line, kind) or None, ms)."""
@@ -282,8 +288,7 @@ class Gff3Scan(object):
                                       ctypes.byref(err_line), ctypes.byref(err_kind), ctypes.byref(ms))
         _lib._check(rc, 'dn_gff3_resolve')
         self.nodes = int(n_nodes.value)
-        err = (int(err_line.value), int(err_kind.value)) if err_kind.value else None
-        return out[0], out[1], out[2], err, float(ms.value)
+        return out[0], out[1], out[2], _error(err_line, err_kind), float(ms.value)
 
 
 def _resolve_pending(scan, cols):
@@ -308,20 +313,18 @@ def gff3_scan(data, device=None, hash_bits=64, stats=None):
     stats = {} if stats is None else stats
     if a.size == 0:
         stats.update(nodes=0, walked_exons=0)
-        return 0, {k: np.zeros(0, dtype=t) for k, t in _GFF3_COLS}, None
+        return 0, _exon_cols(0)[0], None
     if device is None:
         lib = _lib.load()
         cap = a.size // 20 + 1
-        cols = {k: np.empty(cap, dtype=t) for k, t in _GFF3_COLS}
+        cols, col_args = _exon_cols(cap)
         i64 = ctypes.c_int64
         n_lines, n_rows, n_nodes, n_walked, err_line, err_kind = i64(0), i64(0), i64(0), i64(0), i64(0), ctypes.c_int32(0)
         rc = lib.dn_gff3_scan_host(_lib._p(a, ctypes.c_uint8), a.size, int(hash_bits), cap, ctypes.byref(n_lines), ctypes.byref(n_rows),
-                                   *(_gff3_col_args(cols) + [ctypes.byref(n_nodes), ctypes.byref(n_walked), ctypes.byref(err_line),
-                                                             ctypes.byref(err_kind)]))
+                                   *(col_args + [ctypes.byref(n_nodes), ctypes.byref(n_walked), ctypes.byref(err_line), ctypes.byref(err_kind)]))
         _lib._check(rc, 'dn_gff3_scan_host')
         stats.update(nodes=int(n_nodes.value), walked_exons=int(n_walked.value))
-        err = (int(err_line.value), int(err_kind.value)) if err_kind.value else None
-        return int(n_lines.value), {k: v[:int(n_rows.value)] for k, v in cols.items()}, err
+        return int(n_lines.value), {k: v[:int(n_rows.value)] for k, v in cols.items()}, _error(err_line, err_kind)
     with Gff3Scan(a.size, device, hash_bits) as scan:
         cols, err, _, _ = scan.window(a)
         walked = 0
@@ -335,21 +338,8 @@ def gff3_scan(data, device=None, hash_bits=64, stats=None):
 
 
 class Gff3AnnotationLoader(GeneAnnotationLoader):
-
-    def __init__(self, to_load, window_bytes=None, device=None):
-        """
-        .gff3 / .gff file loader on the device (a .gff file is read as GFF3); the table of GeneAnnotationLoader.
-
-        :param to_load: str the realpath to a .gff3 file.
-        :param window_bytes: the file is uploaded and scanned in windows of about this many bytes, cut at line ends (default
-        WINDOW_BYTES); the table and the errors do not depend on it.
-        :param device: HIP device index (default: LOCAL_RANK or 0).
-        """
-        Loader.__init__(self, ['.gff3', '.gff'])
-        self.get_file(to_load)
-        self.window_bytes = max(int(WINDOW_BYTES if window_bytes is None else window_bytes), 1)
-        self.device = device
-        self.timing = {}
+    """.gff3 / .gff file loader on the device (a .gff file is read as GFF3): the constructor and the table of GeneAnnotationLoader."""
+    FILETYPES = ['.gff3', '.gff']
 
     def _raise(self, err):
         raise ValueError('File {0}, line {1} {2}'.format(self.filename, err[0], _GFF3_KINDS[err[1]]))
