@@ -21,7 +21,8 @@ With --sam-files / --sam-dir the inputs are SAM text, what HISAT2, Bowtie2, BWA 
 first converted on the GPU (degnorm_amd.bam.sam_to_bam; the reference's documentation runs samtools view -b for this) to
 <output directory>/converted_bam/X.bam and from there treated as a --sort-bam input: sorted to sorted_bam/ and indexed there
 when its header does not say SO:coordinate, indexed where it lies when it does.  No samtools step is left.
-Not offered: SAM output, gzip-compressed SAM, --plot-genes, the HTML report and the MPI command (see
+Annotations and SAM text may be gzip-compressed (genes.gtf.gz, genes.gff3.gz, X.sam.gz): degnorm_amd.gz inflates them on the GPU.
+Not offered: SAM output, gzip output, zstd, bzip2 and .Z input, --plot-genes, the HTML report and the MPI command (see
 degnorm_amd.warm_start --mpi for the sharded NMF-OA run).  Raw and estimated coverage curves of an output directory as text
 files: `python -m degnorm_amd.data_access -d OUTPUT_DIR -g GENE [GENE ...] | all -o SAVE_DIR` (the reference's
 get_coverage_data; its get_coverage_plots is not offered).
@@ -61,7 +62,7 @@ def argparser():
                     help='output directory of an earlier run: reuse its coverage matrices, read counts and gene table and '
                          'skip the alignment and annotation stages (.bam / annotation arguments are then ignored)')
     ap.add_argument('-g', '--genome-annotation', type=str, default=None,
-                    help='.gtf, .gff3 or .gff (read as GFF3) annotation file; required unless -w is given')
+                    help='.gtf, .gff3 or .gff (read as GFF3) annotation file, optionally gzip-compressed (.gtf.gz ...); required unless -w is given')
     ap.add_argument('-o', '--output-dir', type=str, default=None,
                     help='output directory: created when it does not exist; inside an existing directory, or without this '
                          'flag in the working directory, a degnorm_<mmddYYYY>_<HHMMSS> directory is created')
@@ -141,7 +142,8 @@ def _unsorted(bam_files):
 
 
 def _sam_inputs(args):
-    """The .sam files of --sam-files / --sam-dir, checked: a list of at least two existing files with unique base names."""
+    """The .sam and .sam.gz files of --sam-files / --sam-dir, checked: a list of at least two existing files with unique base names."""
+    from .gz import is_gz, strip_gz
     if args.bam_files or args.bam_dir or args.bai_files is not None or args.warm_start_dir:
         raise ValueError('Do not specify --sam-files or --sam-dir together with --bam-files, --bam-dir, --bai-files or --warm-start-dir.')
     if args.sam_files and args.sam_dir:
@@ -149,19 +151,22 @@ def _sam_inputs(args):
     if args.sam_dir:
         if not os.path.isdir(args.sam_dir):
             raise NotADirectoryError('Cannot find --sam-dir {0}'.format(args.sam_dir))
-        sam_files = [os.path.join(args.sam_dir, f) for f in sorted(os.listdir(args.sam_dir)) if f.endswith('.sam')]
+        sam_files = [os.path.join(args.sam_dir, f) for f in sorted(os.listdir(args.sam_dir)) if strip_gz(f).endswith('.sam')]
+        for f in sam_files:
+            if is_gz(f) and strip_gz(f) in sam_files:
+                raise ValueError('{0} and {1} would both become {2}.bam: keep one of them.'.format(strip_gz(f), f, os.path.basename(f)[:-7]))
         if len(sam_files) < 2:
             raise ValueError('Only found {0} .sam files within directory {1}'.format(len(sam_files), args.sam_dir))
     else:
         sam_files = list(args.sam_files)
         for sam_file in sam_files:
-            if not sam_file.endswith('.sam'):
-                raise ValueError('{0} is not a .sam file.'.format(sam_file))
+            if not strip_gz(sam_file).endswith('.sam'):
+                raise ValueError('{0} is not a .sam file. (X.sam or X.sam.gz is expected.)'.format(sam_file))
             if not os.path.isfile(sam_file):
                 raise FileNotFoundError('Could not find .sam file {0}'.format(sam_file))
     if len(sam_files) < 2:
         raise ValueError('Fewer than 2 .sam files were found. Not sufficiently many to run DegNorm.')
-    if len(set(os.path.basename(f) for f in sam_files)) != len(sam_files):
+    if len(set(os.path.basename(strip_gz(f)) for f in sam_files)) != len(sam_files):
         raise ValueError('The .sam files are not uniquely named: their converted copies share one directory.')
     return sam_files
 
@@ -283,10 +288,11 @@ def _run(args, output_dir, device, verify):
         fmt = getattr(args, 'index_format', 'bai')
         for k, sam_file in enumerate(getattr(args, 'sam_files', None) or []):
             from .bam import create_index, sam_to_bam, sort_order
+            from .gz import strip_gz
             converted_dir = os.path.join(output_dir, 'converted_bam')
             os.makedirs(converted_dir, exist_ok=True)
             logging.info('converting {0} to BAM -- {1} / {2}'.format(sam_file, k + 1, len(args.sam_files)))
-            bam_file = sam_to_bam(sam_file, os.path.join(converted_dir, os.path.basename(sam_file)[:-4] + '.bam'), device=device,
+            bam_file = sam_to_bam(sam_file, os.path.join(converted_dir, os.path.basename(strip_gz(sam_file))[:-4] + '.bam'), device=device,
                                   n_jobs=args.proc_per_node, deflate=deflate)
             args.bam_files.append(bam_file)
             if sort_order(bam_file) != 'coordinate':

@@ -196,6 +196,12 @@ def load(build_if_missing=False):
     lib.dn_text_size.restype = i64
     lib.dn_text_free.argtypes = [vp]
     lib.dn_text_free.restype = None
+    lib.dn_gz_open.argtypes = [vp, i64, i32, i64, i64, i32, i32, P(vp)]
+    lib.dn_gz_next.argtypes = [vp, P(vp), P(i64), P(i32)]
+    lib.dn_gz_counters.argtypes = [vp, P(i64), P(dbl)]
+    lib.dn_gz_tables.argtypes = [vp, P(i64), P(vp), P(i64), P(vp)]
+    lib.dn_gz_close.argtypes = [vp]
+    lib.dn_gz_close.restype = None
     lib.dn_outer_partials_device.argtypes = [vp, P(vp)]
     lib.dn_comm_unique_id.argtypes = [P(c.c_uint8)]
     lib.dn_comm_create.argtypes = [vp, P(c.c_uint8), i32, i32]

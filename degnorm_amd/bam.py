@@ -57,7 +57,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from . import _lib
+from . import _lib, gz
 from ._lib import _check, _p as _ptr
 from .reads import BamReadsProcessor, Annotation, check_coverage_call, coverage_outputs, reads_frame
 
@@ -1888,7 +1888,7 @@ class _RecordStore(object):
 
 def sam_to_bam(src, dst, device=None, n_jobs=1, level=1, window_bytes=256 << 20, deflate='zlib', overwrite=False, stats=None):
     """
-    Write the SAM file `src` as the BAM file `dst` (what `samtools view -b` is run for on an aligner's output); returns dst.
+    Write the SAM file `src` (X.sam, or gzip-compressed X.sam.gz) as the BAM file `dst` (what `samtools view -b` is run for on an aligner's output); returns dst.
     Records keep the order of the lines: nothing is sorted (sort_bam does that).
 
     The '@' header lines are copied as they are into the BAM header, whose reference list is that of the @SQ lines in order
@@ -1928,7 +1928,7 @@ def sam_to_bam(src, dst, device=None, n_jobs=1, level=1, window_bytes=256 << 20,
         return out
 
     try:
-        with open(src, 'rb') as f:
+        with gz.open_text(src, device=device) as f:            # X.sam.gz: the inflated text, by the same device or the host build
             t0 = time.perf_counter()
             text, refs, n_head, rest = sam_header(f, src)
             t['read_s'] += time.perf_counter() - t0
@@ -1968,7 +1968,7 @@ def sam_to_bam(src, dst, device=None, n_jobs=1, level=1, window_bytes=256 << 20,
                 for group in iter(lambda: list(itertools.islice(parts, size)), []):
                     out.writelines(deflated(group, device))
                 out.write(BGZF_EOF)
-            t['bytes_in'] = f.seek(0, 2)
+            t['bytes_in'] = os.path.getsize(src)
         os.replace(tmp, dst)
     finally:
         if pool is not None:

@@ -1,10 +1,12 @@
 // dn_inflate.hip -- raw DEFLATE (RFC 1951) decoder for BGZF blocks, one block per wavefront.
 //
 // A BGZF block is an independent raw-deflate stream of at most 64 KiB that names its own inflated size (ISIZE), so the
-// blocks of a window inflate side by side.  The decoder below (inflate_block) is written once, as __host__ __device__ code
-// against a memory policy M that says how input words, output bytes and the window of history are reached:
+// blocks of a window inflate side by side.  The decoder (dn_inflate_core.hpp, shared with the gzip unit dn_gz.hip; a block is
+// the span from bit 0 with no history: inflate_block below) is written once, as __host__ __device__ code against a memory
+// policy M that says how input words, output bytes and the window of history are reached:
 //
-//   HostMem   plain arrays: the payload is read with bounds-checked loads, the output is written in place.  This is what
+//   HostMem   plain arrays: the payload is read with bounds-checked loads, the output is written in place (and into a ring
+//             of history, which a gzip segment preloads).  This is what
 //             dn_bgzf_inflate_host runs, block after block, without a device: the build that is debugged and fuzzed.
 //   WaveMem   one 64-lane workgroup (one wave) per block.  All 64 lanes run the bit reader and the symbol loop on the same
 //             state (SIMT executes them at the price of one), so every branch is wave-uniform and nothing has to be
@@ -36,383 +38,28 @@
 #include "dn_inflate.hpp"
 
 #define DN_HD __host__ __device__ __forceinline__
-#include "dn_crc.hpp"
+#include "dn_inflate_core.hpp"
 
 namespace {
 
-constexpr int kLitBits = 10, kDistBits = 9, kClBits = 7;
-constexpr int kRing = 32768;                 // bytes of history in LDS (device)
-constexpr int kWin = 2048;                   // bytes of payload in LDS (device)
-constexpr int kHeaderBytes = 640;            // a dynamic block header is at most 3 + 14 + 57 + 316 * 14 bits = 563 bytes
-constexpr int kSymbolBytes = 16;             // a length/distance pair is at most 48 bits; two refills of 4 bytes
-
-struct Tables {
-    uint16_t *lit, *dist;                    // first-level tables, 1 << kLitBits and 1 << kDistBits entries
-    uint16_t *sym_l, *sym_d;                 // symbols sorted by code length, then by value (288 and 32)
-    uint16_t *cnt_l, *cnt_d;                 // number of codes of each length (16 each)
-    uint16_t *offs;                          // scratch of build_table (16)
-    uint8_t *lens;                           // code lengths being read (320)
-};
-
-struct BitReader {
-    uint64_t bb = 0;                         // bits not yet consumed, the next one lowest
-    int32_t bc = 0;                          // how many of them
-    int32_t next = 0;                        // payload offset of the next word to load
-    int32_t n_in = 0;                        // payload bytes
-};
-
-template <class M> DN_HD void seek(BitReader &r, M &m, int32_t p)      // continue at payload byte p
-{
-    m.ensure_in(p, kHeaderBytes, r.n_in);
-    const int32_t a = m.misalign(p);
-    const uint32_t w = m.word(p - a, r.n_in);
-    r.bb = (uint64_t) (w >> (8 * a));
-    r.bc = 32 - 8 * a;
-    r.next = p - a + 4;
-}
-template <class M> DN_HD void refill(BitReader &r, M &m)               // at least 33 bits afterwards
-{
-    if (r.bc <= 32) {
-        r.bb |= (uint64_t) m.word(r.next, r.n_in) << r.bc;
-        r.bc += 32;
-        r.next += 4;
-    }
-}
-DN_HD uint32_t peek(const BitReader &r, int n) { return (uint32_t) r.bb & ((1u << n) - 1u); }
-DN_HD void drop(BitReader &r, int n) { r.bb >>= n; r.bc -= n; }
-DN_HD uint32_t take(BitReader &r, int n) { const uint32_t v = peek(r, n); drop(r, n); return v; }
-DN_HD int64_t bits_used(const BitReader &r) { return (int64_t) r.next * 8 - r.bc; }
-DN_HD bool overrun(const BitReader &r) { return bits_used(r) > (int64_t) r.n_in * 8; }
-
-DN_HD uint32_t reverse_bits(uint32_t v, int n)
-{
-    uint32_t r = 0;
-    for (int i = 0; i < n; i++) { r = (r << 1) | (v & 1u); v >>= 1; }
-    return r;
-}
-
-// Canonical Huffman code of lens[0 .. n): cnt, sym and the first-level table of `bits` bits.  0, or DN_INFLATE_E_LENGTHS for
-// an over-subscribed set or an incomplete one (zlib's rule: a lone code of one bit may stay incomplete when `lone_ok`).
-template <class M>
-DN_HD int build_table(M &m, const uint8_t *lens, int n, uint16_t *cnt, uint16_t *sym, uint16_t *offs, uint16_t *tab, int bits, bool lone_ok)
-{
-    for (int l = 0; l < 16; l++) m.set(cnt + l, 0);
-    for (int i = 0; i < n; i++) { const int l = lens[i] & 15; m.set(cnt + l, (uint16_t) (cnt[l] + 1)); }
-    for (int k = 0; k < (1 << bits); k += M::kLanes) m.set_lane(tab + k, 0);
-    if (cnt[0] == n) return 0;                                  // no codes: every lookup fails
-    int left = 1, max = 0;
-    for (int l = 1; l < 16; l++) {
-        left = (left << 1) - (int) cnt[l];
-        if (left < 0) return DN_INFLATE_E_LENGTHS;
-        if (cnt[l]) max = l;
-    }
-    if (left > 0 && !(lone_ok && max == 1)) return DN_INFLATE_E_LENGTHS;
-    m.set(offs + 1, 0);
-    for (int l = 1; l < 15; l++) m.set(offs + l + 1, (uint16_t) (offs[l] + cnt[l]));
-    for (int i = 0; i < n; i++) {
-        const int l = lens[i] & 15;
-        if (l) { const int o = offs[l]; m.set(sym + o, (uint16_t) i); m.set(offs + l, (uint16_t) (o + 1)); }
-    }
-    uint32_t code = 0;
-    int index = 0;
-    for (int l = 1; l <= bits && l <= max; l++) {
-        const int c = cnt[l];
-        for (int j = 0; j < c; j++) {
-            const uint16_t e = (uint16_t) ((sym[index + j] << 4) | l);
-            for (uint32_t k = reverse_bits(code + j, l); k < (1u << bits); k += 1u << l) m.set(tab + k, e);
-        }
-        index += c;
-        code = (code + c) << 1;
-    }
-    return 0;
-}
-
-// the symbol of the next code: first-level table, else the canonical walk; -1 when no code matches.  Needs 15 bits.
-DN_HD int decode_symbol(BitReader &r, const uint16_t *tab, int bits, const uint16_t *cnt, const uint16_t *sym)
-{
-    const uint32_t e = tab[peek(r, bits)];
-    if (e) { drop(r, e & 15); return (int) (e >> 4); }
-    int code = 0, first = 0, index = 0;
-    uint32_t b = (uint32_t) r.bb;
-    for (int l = 1; l < 16; l++) {
-        code |= (int) (b & 1u);
-        b >>= 1;
-        const int c = cnt[l];
-        if (code - c < first) { drop(r, l); return sym[index + (code - first)]; }
-        index += c;
-        first = (first + c) << 1;
-        code <<= 1;
-    }
-    return -1;
-}
-
-template <class M> DN_HD int read_dynamic(BitReader &r, M &m, const Tables &t, int &n_lit, int &n_dist)
-{
-    const uint8_t order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
-    refill(r, m);
-    n_lit = (int) take(r, 5) + 257;
-    n_dist = (int) take(r, 5) + 1;
-    const int n_cl = (int) take(r, 4) + 4;
-    if (n_lit > 286 || n_dist > 30) return DN_INFLATE_E_HEADER;
-    for (int i = 0; i < 19; i++) m.set8(t.lens + i, 0);
-    for (int i = 0; i < n_cl; i++) { refill(r, m); m.set8(t.lens + order[i], (uint8_t) take(r, 3)); }
-    int rc = build_table(m, t.lens, 19, t.cnt_l, t.sym_l, t.offs, t.lit, kClBits, false);
-    if (rc) return rc;
-    int i = 0, prev = 0;
-    while (i < n_lit + n_dist) {
-        refill(r, m);
-        const uint32_t e = t.lit[peek(r, kClBits)];
-        if (!e) return DN_INFLATE_E_LENGTHS;
-        drop(r, e & 15);
-        const int s = (int) (e >> 4);
-        if (s < 16) { m.set8(t.lens + i++, (uint8_t) s); prev = s; continue; }
-        int rep, v = 0;
-        if (s == 16) { if (i == 0) return DN_INFLATE_E_LENGTHS; v = prev; rep = 3 + (int) take(r, 2); }
-        else if (s == 17) rep = 3 + (int) take(r, 3);
-        else rep = 11 + (int) take(r, 7);
-        if (i + rep > n_lit + n_dist) return DN_INFLATE_E_LENGTHS;
-        for (int k = 0; k < rep; k++) m.set8(t.lens + i++, (uint8_t) v);
-        prev = v;
-    }
-    if (overrun(r)) return DN_INFLATE_E_INPUT;
-    if (t.lens[256] == 0) return DN_INFLATE_E_LENGTHS;          // no end-of-block code
-    return 0;
-}
-
-// Inflate one payload of n_in bytes into exactly isize bytes.  0 or DN_INFLATE_E_*.  Every trip of the block loop and of the
-// symbol loop consumes at least one bit and ends on the first bit beyond the payload, so both are bounded by 8 * n_in.
-// With m.check the block must also have the CRC32 `crc`; a decode error wins over DN_INFLATE_E_CRC.
+// Inflate one payload of n_in bytes into exactly isize bytes: the span from bit 0 with no history that stops at its final
+// block (dn_inflate_core.hpp).  0 or DN_INFLATE_E_*.  With m.check the block must also have the CRC32 `crc` (m.crc starts at
+// 0xffffffff); a decode error wins over DN_INFLATE_E_CRC.
 template <class M> DN_HD int inflate_block(M &m, const Tables &t, int32_t n_in, int32_t isize, uint32_t crc)
 {
-    BitReader r;
-    r.n_in = n_in;
-    int32_t out_pos = 0;
-    seek(r, m, 0);
-    for (bool last = false; !last;) {
-        m.ensure_in(r.next, kHeaderBytes, n_in);
-        refill(r, m);
-        last = take(r, 1) != 0;
-        const uint32_t type = take(r, 2);
-        if (overrun(r)) return DN_INFLATE_E_INPUT;
-        if (type == 3) return DN_INFLATE_E_HEADER;
-        if (type == 0) {
-            const int64_t p = (bits_used(r) + 7) >> 3;          // LEN and NLEN start at the next byte boundary
-            if (p + 4 > n_in) return DN_INFLATE_E_INPUT;
-            seek(r, m, (int32_t) p);
-            refill(r, m);
-            const uint32_t len = take(r, 16), nlen = take(r, 16);
-            if ((len ^ nlen) != 0xffffu) return DN_INFLATE_E_HEADER;
-            if (p + 4 + len > n_in) return DN_INFLATE_E_INPUT;
-            if ((int64_t) out_pos + len > isize) return DN_INFLATE_E_SIZE;
-            m.stored((int32_t) p + 4, (int32_t) len, out_pos);
-            out_pos += (int32_t) len;
-            seek(r, m, (int32_t) p + 4 + (int32_t) len);
-            continue;
-        }
-        int n_lit = 288, n_dist = 32;
-        if (type == 1) {
-            for (int i = 0; i < 288; i++) m.set8(t.lens + i, (uint8_t) (i < 144 ? 8 : i < 256 ? 9 : i < 280 ? 7 : 8));
-            for (int i = 288; i < 320; i++) m.set8(t.lens + i, 5);
-        } else {
-            const int rc = read_dynamic(r, m, t, n_lit, n_dist);
-            if (rc) return rc;
-        }
-        int rc = build_table(m, t.lens, n_lit, t.cnt_l, t.sym_l, t.offs, t.lit, kLitBits, true);
-        if (rc == 0) rc = build_table(m, t.lens + n_lit, n_dist, t.cnt_d, t.sym_d, t.offs, t.dist, kDistBits, true);
-        if (rc) return rc;
-        for (;;) {
-            m.ensure_in(r.next, kSymbolBytes, n_in);
-            m.ensure_out(out_pos, 258);
-            refill(r, m);
-            int s = decode_symbol(r, t.lit, kLitBits, t.cnt_l, t.sym_l);
-            if (s < 0) return overrun(r) ? DN_INFLATE_E_INPUT : DN_INFLATE_E_CODE;
-            if (s < 256) {
-                if (overrun(r)) return DN_INFLATE_E_INPUT;
-                if (out_pos >= isize) return DN_INFLATE_E_SIZE;
-                m.put(out_pos++, (uint8_t) s);
-                continue;
-            }
-            if (s == 256) {
-                if (overrun(r)) return DN_INFLATE_E_INPUT;
-                break;
-            }
-            s -= 257;
-            if (s >= 29) return DN_INFLATE_E_CODE;
-            int len;
-            if (s < 8) len = 3 + s;
-            else if (s == 28) len = 258;
-            else { const int e = (s - 4) >> 2; len = 3 + ((4 + (s & 3)) << e) + (int) take(r, e); }
-            refill(r, m);
-            int d = decode_symbol(r, t.dist, kDistBits, t.cnt_d, t.sym_d);
-            if (d < 0) return overrun(r) ? DN_INFLATE_E_INPUT : DN_INFLATE_E_CODE;
-            if (d >= 30) return DN_INFLATE_E_CODE;
-            int dist;
-            if (d < 4) dist = 1 + d;
-            else { const int e = (d - 2) >> 1; dist = 1 + ((2 + (d & 1)) << e) + (int) take(r, e); }
-            if (overrun(r)) return DN_INFLATE_E_INPUT;
-            if (dist > out_pos) return DN_INFLATE_E_DISTANCE;
-            if (out_pos + len > isize) return DN_INFLATE_E_SIZE;
-            m.copy(out_pos, dist, len);
-            out_pos += len;
-        }
-    }
-    if (out_pos != isize) return DN_INFLATE_E_SIZE;
-    if (((bits_used(r) + 7) >> 3) != n_in) return DN_INFLATE_E_TRAILING;
-    m.finish(out_pos);
+    Stop stop{Stop::kFinal, 0, 0, nullptr, 0};
+    stop.whole = true;
+    Segment o;
+    inflate_span(m, t, n_in, 0, stop, 0, isize, o);
+    if (o.status) return o.status;
+    if (o.out_len != isize) return DN_INFLATE_E_SIZE;
+    if (((o.exit + 7) >> 3) != n_in) return DN_INFLATE_E_TRAILING;
     if (m.check && (m.crc ^ 0xffffffffu) != crc) return DN_INFLATE_E_CRC;
     return 0;
 }
 
-// --- host: plain arrays ---------------------------------------------------------------------------------------------------
-
-struct HostMem {
-    static constexpr int kLanes = 1;
-    const uint8_t *in;              // the payload
-    uint8_t *out;                   // isize bytes
-    bool check;                     // keep the CRC register
-    uint32_t crc = 0xffffffffu;
-
-    void ensure_in(int32_t, int32_t, int32_t) {}
-    void ensure_out(int32_t, int32_t) {}
-    int32_t misalign(int32_t) const { return 0; }
-    uint32_t word(int32_t p, int32_t n_in) const
-    {
-        uint32_t w = 0;
-        for (int k = 0; k < 4; k++)
-            if (p + k >= 0 && p + k < n_in) w |= (uint32_t) in[p + k] << (8 * k);
-        return w;
-    }
-    void set(uint16_t *p, uint16_t v) { *p = v; }
-    void set_lane(uint16_t *p, uint16_t v) { *p = v; }
-    void set8(uint8_t *p, uint8_t v) { *p = v; }
-    void put(int32_t pos, uint8_t v) { out[pos] = v; }
-    void copy(int32_t pos, int32_t dist, int32_t len)
-    {
-        for (int32_t i = 0; i < len; i++) out[pos + i] = out[pos + i - dist];
-    }
-    void stored(int32_t src, int32_t len, int32_t pos) { memcpy(out + pos, in + src, (size_t) len); }
-    void finish(int32_t pos) { if (check) crc = crc_host(crc, out, pos, 64, kRing); }      // sliced and cut as the device does
-};
-
-// --- device: one wave, history and payload window in LDS -----------------------------------------------------------------
-
-struct RingReader {
-    const uint32_t *ring32;
-    __device__ __forceinline__ uint32_t dword(int32_t p) const { return ring32[(uint32_t) (p >> 2) & (kRing / 4 - 1)]; }
-};
-
-// the CRC register reg after the ring's bytes [a, b) too.  A call, not inline: flush() is inlined into the symbol loop, and
-// the loop of a launch that checks nothing should stay the code it was.
-__device__ __noinline__ uint32_t wave_crc(const uint8_t *ring, uint32_t reg, int32_t a, int32_t b, int32_t lane)
-{
-    uint32_t x = crc_slice(RingReader{reinterpret_cast<const uint32_t *>(ring)}, a, b, lane, 64);
-    for (int o = 32; o > 0; o >>= 1) x ^= (uint32_t) __shfl_xor((int) x, o, 64);
-    return crc_join(reg, x, a, b);
-}
-
-struct WaveMem {
-    static constexpr int kLanes = 64;
-    uint8_t *ring;                  // LDS, kRing bytes
-    uint32_t *win;                  // LDS, kWin bytes: comp[wbase .. wbase + kWin)
-    const uint8_t *comp;
-    int64_t comp_cap, abs0, wbase;  // abs0: the payload's offset in comp; wbase: a multiple of 16
-    uint8_t *dst;                   // where byte `skip` of the output goes
-    int32_t skip, keep, flushed, lane;
-    bool check;                     // keep the CRC register
-    uint32_t crc;
-
-    __device__ __forceinline__ void fence() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); }
-
-    __device__ __forceinline__ void ensure_in(int32_t p, int32_t k, int32_t n_in)
-    {
-        const int64_t a = abs0 + p;
-        int64_t need = a + k;
-        if (need > abs0 + n_in) need = abs0 + n_in;
-        if (a >= wbase && need <= wbase + kWin) return;
-        wbase = a & ~(int64_t) 15;
-        fence();
-        for (int j = lane; j < kWin / 16; j += 64) {
-            const int64_t o = wbase + 16 * (int64_t) j;
-            uint4 v = make_uint4(0, 0, 0, 0);
-            if (o >= 0 && o + 16 <= comp_cap) v = *reinterpret_cast<const uint4 *>(comp + o);
-            reinterpret_cast<uint4 *>(win)[j] = v;
-        }
-        fence();
-    }
-    __device__ __forceinline__ int32_t misalign(int32_t p) const { return (int32_t) ((abs0 + p) & 3); }
-    __device__ __forceinline__ uint32_t word(int32_t p, int32_t n_in) const      // bytes beyond the payload read as 0, as on the host
-    {
-        const uint32_t w = win[(uint32_t) ((abs0 + p - wbase) >> 2) & (kWin / 4 - 1)];
-        if (p + 4 <= n_in) return w;
-        return p >= n_in ? 0u : w & (0xffffffffu >> (8 * (p + 4 - n_in)));
-    }
-    __device__ __forceinline__ void set(uint16_t *p, uint16_t v) { if (lane == 0) *p = v; fence(); }
-    __device__ __forceinline__ void set_lane(uint16_t *p, uint16_t v) { p[lane] = v; fence(); }
-    __device__ __forceinline__ void set8(uint8_t *p, uint8_t v) { if (lane == 0) *p = v; fence(); }
-    __device__ __forceinline__ void put(int32_t pos, uint8_t v) { if (lane == 0) ring[pos & (kRing - 1)] = v; fence(); }
-
-    // out[pos .. pos + len) = out[pos - dist ..): every lane a byte; a period shorter than the wave doubles each step
-    __device__ __forceinline__ void copy(int32_t pos, int32_t dist, int32_t len)
-    {
-        int32_t done = 0, d = dist;
-        while (done < len) {
-            int32_t step = d < 64 ? d : 64;
-            if (step > len - done) step = len - done;
-            uint8_t v = 0;
-            if (lane < step) v = ring[(pos + done + lane - d) & (kRing - 1)];
-            fence();
-            if (lane < step) ring[(pos + done + lane) & (kRing - 1)] = v;
-            fence();
-            done += step;
-            if (d < 64) d += d;
-        }
-    }
-
-    // ring bytes [flushed, to) -> global memory, the part inside [skip, skip + keep); all of them into the CRC register
-    __device__ __forceinline__ void flush(int32_t to)
-    {
-        fence();
-        if (check && to > flushed) crc = wave_crc(ring, crc, flushed, to, lane);
-        int32_t lo = flushed > skip ? flushed : skip, hi = to < skip + keep ? to : skip + keep;
-        flushed = to;
-        if (lo >= hi) return;
-        int32_t head = (int32_t) ((0 - (reinterpret_cast<uintptr_t>(dst) + (uintptr_t) (lo - skip))) & 15u);
-        if (head > hi - lo) head = hi - lo;
-        if (lane < head) dst[lo - skip + lane] = ring[(lo + lane) & (kRing - 1)];
-        const int32_t body = lo + head, n_vec = (hi - body) >> 4;
-        const uint32_t *ring32 = reinterpret_cast<const uint32_t *>(ring);
-        for (int32_t v = lane; v < n_vec; v += 64) {
-            const int32_t s = body + 16 * v;
-            const uint32_t sh = 8u * (uint32_t) (s & 3);
-            uint32_t w[5];
-            for (int k = 0; k < 5; k++) w[k] = ring32[(uint32_t) ((s >> 2) + k) & (kRing / 4 - 1)];
-            uint4 q;
-            q.x = (uint32_t) ((((uint64_t) w[1] << 32) | w[0]) >> sh);
-            q.y = (uint32_t) ((((uint64_t) w[2] << 32) | w[1]) >> sh);
-            q.z = (uint32_t) ((((uint64_t) w[3] << 32) | w[2]) >> sh);
-            q.w = (uint32_t) ((((uint64_t) w[4] << 32) | w[3]) >> sh);
-            *reinterpret_cast<uint4 *>(dst + (s - skip)) = q;
-        }
-        const int32_t tail = body + 16 * n_vec;
-        if (tail + lane < hi) dst[tail - skip + lane] = ring[(tail + lane) & (kRing - 1)];
-    }
-    __device__ __forceinline__ void ensure_out(int32_t pos, int32_t k)
-    {
-        if (pos + k - flushed > kRing) flush(pos);
-    }
-    __device__ __forceinline__ void stored(int32_t src, int32_t len, int32_t pos)
-    {
-        while (len > 0) {
-            if (pos - flushed >= kRing) flush(pos);
-            int32_t chunk = kRing - (pos - flushed);
-            if (chunk > len) chunk = len;
-            for (int32_t i = lane; i < chunk; i += 64) ring[(pos + i) & (kRing - 1)] = comp[abs0 + src + i];
-            fence();
-            src += chunk; pos += chunk; len -= chunk;
-        }
-    }
-    __device__ __forceinline__ void finish(int32_t pos) { flush(pos); }
-};
+using BlockHost = HostMem<kBytes, int32_t>;      // a BGZF block is counted in 32 bits
+using BlockWave = WaveMem<kBytes, int32_t>;
 
 __global__ __launch_bounds__(64) void k_bgzf_inflate(const uint8_t *__restrict__ comp, int64_t comp_cap,
                                                      const dn::InflateBlock *__restrict__ blk, int64_t n_blocks,
@@ -426,7 +73,8 @@ __global__ __launch_bounds__(64) void k_bgzf_inflate(const uint8_t *__restrict__
     if (b >= n_blocks) return;
     const dn::InflateBlock B = blk[b];
     Tables t{s_lit, s_dist, s_sym_l, s_sym_d, s_cnt_l, s_cnt_d, s_offs, s_lens};
-    WaveMem m;
+    BlockWave m;
+    m.tail = nullptr;
     m.ring = s_ring;
     m.win = s_win;
     m.comp = comp;
@@ -478,9 +126,10 @@ int inflate_host(const char *who, const uint8_t *comp, int64_t n_comp, int64_t n
     uint16_t lit[1 << kLitBits], dist[1 << kDistBits], sym_l[288], sym_d[32], cnt_l[16], cnt_d[16], offs[16];
     uint8_t lens[320];
     const Tables t{lit, dist, sym_l, sym_d, cnt_l, cnt_d, offs, lens};
-    std::vector<uint8_t> dropped(out ? 0 : 65536);
+    std::vector<uint8_t> dropped(out ? 0 : 65536), ring(kRing);
     for (const dn::InflateBlock &B : blk) {
-        HostMem m{comp + B.pay_off, out ? out + B.dst_off : dropped.data(), B.check != 0};
+        BlockHost m{comp + B.pay_off, ring.data(), out ? out + B.dst_off : dropped.data(), nullptr, B.check != 0};
+        m.crc = 0xffffffffu;
         status[&B - blk.data()] = inflate_block(m, t, B.pay_len, B.isize, B.crc);
     }
     return DN_OK;

@@ -34,7 +34,7 @@ import time
 
 import numpy as np
 
-from . import _lib
+from . import _lib, gz
 
 WINDOW_BYTES = 256 << 20            # as NativeBamReadsProcessor (bam.py)
 _COMPARE_BYTES = 32 << 20           # bytes held at a time when the names of a hash group are compared
@@ -145,10 +145,11 @@ def intern_spans(a, beg, length, hashes, table):
                     dtype=np.int64)
 
 
-def iter_windows(filename, window_bytes):
-    """The file's bytes in pieces of about window_bytes that end at a line end (the last one at the end of the file)."""
+def iter_windows(filename, window_bytes, device=None):
+    """The file's bytes in pieces of about window_bytes that end at a line end (the last one at the end of the file).  The
+    bytes of a .gz file are its inflated ones (gz.open_text: on GPU `device`, or with device=None by the host build)."""
     carry = b''
-    with open(filename, 'rb') as f:
+    with gz.open_text(filename, device=device) as f:
         while True:
             more = f.read(window_bytes)
             if not more:
@@ -165,7 +166,7 @@ def iter_windows(filename, window_bytes):
 
 
 class GeneAnnotationLoader(Loader):
-    FILETYPES = '.gtf'
+    FILETYPES = ['.gtf', '.gtf.gz']
 
     def __init__(self, to_load, window_bytes=None, device=None):
         """
@@ -192,7 +193,7 @@ class GeneAnnotationLoader(Loader):
         line_base = 0
         t = self.timing = {'read_s': 0.0, 'copy_ms': 0.0, 'device_ms': 0.0, 'bytes': 0}
         t0 = time.perf_counter()
-        for win in iter_windows(self.filename, self.window_bytes):
+        for win in iter_windows(self.filename, self.window_bytes, _device(self.device)):
             t['read_s'] += time.perf_counter() - t0
             n_lines, cols, err, copy_ms, dev_ms = scan_window(win, self.device)
             t['copy_ms'] += copy_ms
@@ -339,7 +340,7 @@ def gff3_scan(data, device=None, hash_bits=64, stats=None):
 
 class Gff3AnnotationLoader(GeneAnnotationLoader):
     """.gff3 / .gff file loader on the device (a .gff file is read as GFF3): the constructor and the table of GeneAnnotationLoader."""
-    FILETYPES = ['.gff3', '.gff']
+    FILETYPES = ['.gff3', '.gff', '.gff3.gz', '.gff.gz']
 
     def _raise(self, err):
         raise ValueError('File {0}, line {1} {2}'.format(self.filename, err[0], _GFF3_KINDS[err[1]]))
@@ -348,15 +349,18 @@ class Gff3AnnotationLoader(GeneAnnotationLoader):
         """As GeneAnnotationLoader.exon_codes.  The text stays on the device until every exon has its gene."""
         t = self.timing = {'read_s': 0.0, 'copy_ms': 0.0, 'device_ms': 0.0, 'resolve_ms': 0.0, 'bytes': 0, 'lines': 0, 'nodes': 0,
                            'walked_exons': 0}
-        size = os.path.getsize(self.filename)
+        zipped = gz.is_gz(self.filename)             # the text's size: from a first scan of the .gz file, not from its ISIZE
+        size = gz.inflated_size(self.filename, _device(self.device)) if zipped else os.path.getsize(self.filename)
         empty = np.zeros(0, dtype=np.int64)
         if size == 0:
             return empty, empty, empty, empty, [], []
-        parts = []
+        parts, text = [], []
         with Gff3Scan(size, self.device) as scan:
             t0 = time.perf_counter()
-            for win in iter_windows(self.filename, self.window_bytes):
+            for win in iter_windows(self.filename, self.window_bytes, _device(self.device)):
                 t['read_s'] += time.perf_counter() - t0
+                if zipped:
+                    text.append(win)
                 cols, err, copy_ms, dev_ms = scan.window(win)
                 t['copy_ms'] += copy_ms
                 t['device_ms'] += dev_ms
@@ -376,7 +380,7 @@ class Gff3AnnotationLoader(GeneAnnotationLoader):
             t['nodes'] = scan.nodes
             if err is not None:
                 self._raise(err)
-        a = np.memmap(self.filename, dtype=np.uint8, mode='r')
+        a = np.frombuffer(b''.join(text), dtype=np.uint8) if zipped else np.memmap(self.filename, dtype=np.uint8, mode='r')
         chr_table, gene_table = {}, {}
         chr_code = intern_spans(a, cols['chr_beg'], cols['chr_len'].astype(np.int64), cols['chr_hash'], chr_table)
         gene_code = intern_spans(a, cols['gene_beg'], cols['gene_len'].astype(np.int64), cols['gene_hash'], gene_table)
@@ -384,11 +388,13 @@ class Gff3AnnotationLoader(GeneAnnotationLoader):
         return chr_code, cols['start'], cols['end'], gene_code, names[0], names[1]
 
 
-ANNOTATION_LOADERS = (('.gtf', GeneAnnotationLoader), ('.gff3', Gff3AnnotationLoader), ('.gff', Gff3AnnotationLoader))
+ANNOTATION_LOADERS = (('.gtf', GeneAnnotationLoader), ('.gff3', Gff3AnnotationLoader), ('.gff', Gff3AnnotationLoader),
+                      ('.gtf.gz', GeneAnnotationLoader), ('.gff3.gz', Gff3AnnotationLoader), ('.gff.gz', Gff3AnnotationLoader))
 
 
 def annotation_loader(path, **kw):
-    """The loader of an annotation file by its extension: .gtf -> GeneAnnotationLoader, .gff3 / .gff -> Gff3AnnotationLoader."""
+    """The loader of an annotation file by its extension: .gtf -> GeneAnnotationLoader, .gff3 / .gff -> Gff3AnnotationLoader;
+    the same with a further .gz (gz.open_text inflates it)."""
     if isinstance(path, str):
         for ext, cls in ANNOTATION_LOADERS:
             if path.endswith(ext):

@@ -234,13 +234,14 @@ def sort_bam_file(bam_file, out_dir=None, **kw):
 
 def sam_to_bam_file(sam_file, out_dir=None, **kw):
     """
-    Convert a .sam file to BAM, X.sam -> X.bam (the `samtools view -b` an aligner's text output needs before anything else
+    Convert a .sam or .sam.gz file to BAM, X.sam / X.sam.gz -> X.bam (the `samtools view -b` an aligner's text output needs before anything else
     can read it; here degnorm_amd.bam.sam_to_bam does it, on the GPU with device=k), next to the input or in out_dir.
     Keywords are sam_to_bam's.  Returns the path of the .bam file.
     """
     import os
     from .bam import sam_to_bam
-    if not sam_file.endswith('.sam'):
-        raise ValueError('{0} must have a .sam extension.'.format(sam_file))
-    name = os.path.basename(sam_file)[:-4] + '.bam'
+    from .gz import strip_gz
+    if not strip_gz(sam_file).endswith('.sam'):
+        raise ValueError('{0} must have a .sam extension (or .sam.gz).'.format(sam_file))
+    name = os.path.basename(strip_gz(sam_file))[:-4] + '.bam'
     return sam_to_bam(sam_file, os.path.join(os.path.dirname(sam_file) if out_dir is None else out_dir, name), **kw)

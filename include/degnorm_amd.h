@@ -842,6 +842,94 @@ const uint8_t *dn_text_bytes(dn_text text);
 int64_t dn_text_size(dn_text text);
 void dn_text_free(dn_text text);
 
+/* gzip streams (csrc/dn_gz.hip, csrc/dn_gz.hpp; degnorm_amd/gz.py) ---------------------------------------------------------------
+ * The inflated bytes of a .gz file (RFC 1952 around RFC 1951), chunk-parallel: what `*.gtf.gz`, `*.gff3.gz` and `*.sam.gz` need
+ * before the scans can read them.  A gzip member is one DEFLATE stream whose 32 KiB history runs through the whole member, so it
+ * does not inflate block by block as BGZF does.  It is inflated chunk by chunk, by guess, walk, stitch and fix-up (the scheme
+ * of dn_frame.hip): an entry is guessed per chunk, every chunk is decoded from its guess without its history, the unknown
+ * bytes tracked as 16-bit markers; the host stitches the chain from the true start and walks again only where a guess was
+ * wrong; the windows are propagated in chain order; every segment is decoded for real with its window preloaded.
+ *
+ * Bits.  Byte p of the file holds bits 8 p .. 8 p + 7, least significant first, as RFC 1951 packs them.
+ * Container.  A member starts with the magic 1f 8b, CM = 8 and a FLG byte whose bits 5 .. 7 are zero; MTIME, XFL and OS are
+ * ignored.  FEXTRA, FNAME, FCOMMENT and FHCRC are skipped; the FHCRC value (the low 16 bits of the CRC32 of the header bytes
+ * before it) is compared when `verify` is on.  The DEFLATE stream follows the header; the trailer (CRC32, ISIZE, little endian)
+ * starts at the first byte boundary at or behind the final block's end.  ISIZE is always compared with the member's length mod
+ * 2^32, the CRC32 when `verify` is on, the CRC32 first.  Any number of members follow each other, an empty one is legal, and
+ * no bytes at all are no members.  Behind a member zero bytes are skipped; what follows them is the next member when it starts
+ * with the magic and `trailing garbage` otherwise.  (A BGZF file -- the first member carries the BC extra subfield -- is a gzip
+ * file too and inflates here, but degnorm_amd.gz sends it down the BGZF path, block by block.)
+ * Chunks.  The compressed bytes are cut on an absolute grid of chunk_bytes = C (a power of two, 4 KiB .. 16 MiB; degnorm_amd.gz takes 16 KiB):
+ * chunk c is bytes [c C, (c + 1) C), the last one ends with the file.  The guess of chunk c is the smallest bit offset b of
+ * the chunk's bits [8 c C, min(8 (c + 1) C, 8 n)) that passes the guess rule, or none (-1).
+ * The guess rule at bit b, all of:
+ *   1  BFINAL = 0 and BTYPE = 2 (the three bits at b are 0, 0, 1), HLIT <= 29, HDIST <= 29;
+ *   2  the HCLEN + 4 code-length code lengths are complete: the sum of 2^-len over the non-zero ones is exactly 1;
+ *   3  the HLIT + 257 + HDIST + 1 code lengths decode: every code exists, a repeat of the previous length (16) is not the
+ *      first symbol, no repeat leaves the count, nothing reads beyond the file; symbol 256 has a code.  (A 16 behind a run
+ *      of zeros written by 17 or 18 repeats zero.)
+ *   4  the literal/length code is complete (sum exactly 1); the distance code is complete, or has no code at all, or has one
+ *      code of one bit;
+ *   5  the block's symbols decode to the end-of-block symbol: every code exists, no length symbol 286 or 287, no distance
+ *      symbol 30 or 31, nothing reads beyond the file.  Distances are not compared with anything: the history is unknown;
+ *   6  the three bits behind the end-of-block code lie inside the file and are not BTYPE = 3.
+ * Stored and fixed blocks are never guessed (the chain reaches them), and a guess may be wrong: a rule, not the truth.
+ * Segments.  A true entry is the first bit of a block on the chain that starts at the first block of a member.  The stitch
+ * is at a true entry e in chunk c = e / 8 C, at first that of the first member's first block:
+ *   - if e is the guess of c, the chunk is confirmed: its segment runs along the block chain to the first block end at or
+ *     beyond the chunk's end 8 (c + 1) C, or to the end of a final block if that comes first;
+ *   - otherwise the segment is a fix-up: it is walked from e and ends at the first block end y that is the guess of the
+ *     chunk y lies in (whichever chunk that is, c included), or at the end of a final block if that comes first.  A run of
+ *     wrong or missing guesses is one walk.
+ * The segment's exit is the next entry; behind a final block (exit kind DN_GZ_EXIT_MEMBER, else DN_GZ_EXIT_BLOCK) the trailer
+ * is read, then padding and the next header, and the next entry is the first bit behind that header.  The chunks strictly
+ * between an entry's chunk and its exit's chunk are jumped over: their guesses and walks contribute nothing.  The output is
+ * the serial decoder's for every input, whatever the guesses were; guesses only decide the cost.
+ * Markers.  A walk keeps the last 32 768 output symbols as uint16: a literal is 0 .. 255, 0x8000 | j is "byte j of the 32 768
+ * that precede the entry" (j = 32 767 is the byte just before it).  The ring starts as the identity, ring[j] = 0x8000 | j, so a
+ * back-reference is one read of the ring, and a segment shorter than 32 KiB passes the older window through.  A walk leaves
+ * its exit bit, its output length (int64), its exit kind, its number of blocks and the ring in order (tail, 32 768 symbols).
+ * Windows, in chain order: win[s + 1][j] = tail[s][j] < 256 ? tail[s][j] : win[s][tail[s][j] & 0x7fff]; at a member's first
+ * segment the window is all zero.  have[s] = min(32 768, the member's output before s).
+ * Emit.  Every segment is decoded again by the byte decoder with win[s] preloaded, from its entry to its exit, to its place
+ * (the exclusive sum of the output lengths).  A distance beyond out_pos + have[s] is DN_INFLATE_E_DISTANCE; a length other
+ * than the walk's is DN_INFLATE_E_SIZE; the other statuses are those of the BGZF decoder.  The segment's CRC register starts
+ * from zero; the host joins the registers in order (reg = reg x^(8 len) + seg, dn_crc.hpp) and compares at the trailer.
+ * Spans.  The file is taken in spans of about window_bytes compressed bytes (default 64 MiB, at least one chunk), each starting
+ * at the chunk of the next entry.  A walk that the span's end cuts is dropped and its entry starts the next span; when no
+ * segment of a span ends inside it the span is doubled (up to 1 GiB).  A guess whose trial decode the span's end cuts is none
+ * in that span, so the counters and tables are those of the definition above when the file is one span.  Device memory per
+ * span: the compressed bytes, 64 KiB + 32 KiB per chunk and fix-up, and the inflated bytes; the need is compared with the free
+ * memory before the upload, and a span that does not fit is DN_E_INVALID with the sizes in the message.
+ * Errors: DN_E_INVALID, dn_last_error() = `gzip member at byte <offset of the member's magic>: <what>`, where <what> is one
+ * of: truncated header | bad magic | compression method <CM> | reserved flag bits set | header CRC mismatch |
+ * invalid block header | invalid code lengths | invalid code | distance beyond the start of the member | truncated deflate
+ * stream | inflated length disagrees with the walk | truncated trailer | CRC32 mismatch | ISIZE mismatch | trailing garbage
+ * (there <offset> is that of the first such byte).  The first error in stream order wins; the text is the same from both
+ * builds; neither the bytes nor the errors depend on chunk_bytes or window_bytes.
+ *
+ * dn_gz_open takes the whole compressed file (comp stays the caller's and must outlive the handle); device >= 0 is the device
+ * build, device = -1 the host build of the same source, which touches no device.  emit = 0 decodes nothing for real: the tables
+ * only.  dn_gz_next inflates the next span: *out / *n_out are its bytes (owned by the handle, valid until the next call; pinned
+ * host memory in the device build), *done = 1 with *n_out = 0 behind the last one.  After an error the handle only closes.
+ * Kernels (one wave per chunk or segment, 64 threads): k_gz_guess tests 64 bit offsets a step, one per lane (rules 1 and 2 in
+ * registers), and sends the survivors in ascending order through rules 3 .. 6; k_gz_walk is the marker decoder with a 64 KiB
+ * uint16 ring in LDS (about 70 KiB a workgroup, two per CU); k_gz_windows is one workgroup that walks the chain; k_gz_emit is
+ * the byte decoder with the ring preloaded, CRC and 16-byte stores in its flush.
+ * dn_gz_counters: DN_GZ_N_COUNTERS int64 (order below) and 6 doubles, ms by HIP events (0 in the host build): copy, guess,
+ * walk (fix-ups included), windows, emit, copy back.  dn_gz_tables: after the last span, the guess of every chunk (absolute
+ * bit or -1) and four int64 per segment: entry bit, exit bit, output length, exit kind.  The pointers are the handle's. */
+#define DN_GZ_EXIT_BLOCK   0
+#define DN_GZ_EXIT_MEMBER  1
+#define DN_GZ_N_COUNTERS   10  /* members, chunks, guessed, confirmed, jumped, fixups, segments, blocks, bytes_in, bytes_out */
+typedef struct dn_gz_ *dn_gz;
+int  dn_gz_open(const uint8_t *comp, int64_t n_comp, int32_t device, int64_t chunk_bytes, int64_t window_bytes, int32_t verify,
+                int32_t emit, dn_gz *out);
+int  dn_gz_next(dn_gz h, const uint8_t **out, int64_t *n_out, int32_t *done);
+int  dn_gz_counters(dn_gz h, int64_t *counters, double *ms);
+int  dn_gz_tables(dn_gz h, int64_t *n_chunks, const int64_t **guess, int64_t *n_segments, const int64_t **segments);
+void dn_gz_close(dn_gz h);
+
 /* Measurement hooks (bench.py) -------------------------------------------------------------------- */
 /* Device time in ms of the most recent dn_baseline_iteration's main kernel, measured with HIP events
  * on the library's own stream; kernel name via dn_main_kernel_name().                               */
