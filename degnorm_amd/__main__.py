@@ -21,6 +21,11 @@ With --sam-files / --sam-dir the inputs are SAM text, what HISAT2, Bowtie2, BWA 
 first converted on the GPU (degnorm_amd.bam.sam_to_bam; the reference's documentation runs samtools view -b for this) to
 <output directory>/converted_bam/X.bam and from there treated as a --sort-bam input: sorted to sorted_bam/ and indexed there
 when its header does not say SO:coordinate, indexed where it lies when it does.  No samtools step is left.
+--pair-by flag pairs mates by FLAG (0x1, 0x40, 0x80) and mate position, what those aligners write: both mates of a template
+carry one name there, and the default --pair-by name (the reference's .1 / .2 suffixes) takes such a file for single-end.
+--pair-by auto tries the names first.  --exclude-flags, --require-flags (decimal or 0x...) and --min-mapq drop records as
+samtools view -F / -f / -q does; they work on --bam-* inputs and on --sam-* / --sort-bam ones, whose converted and sorted
+copies keep FLAG, MAPQ and PNEXT.
 Annotations and SAM text may be gzip-compressed (genes.gtf.gz, genes.gff3.gz, X.sam.gz): degnorm_amd.gz inflates them on the GPU.
 Not offered: SAM output, gzip output, zstd, bzip2 and .Z input, --plot-genes, the HTML report and the MPI command (see
 degnorm_amd.warm_start --mpi for the sharded NMF-OA run).  Raw and estimated coverage curves of an output directory as text
@@ -33,6 +38,14 @@ import os
 import re
 import sys
 from datetime import datetime
+
+
+def _flag_mask(text):
+    """A FLAG mask of the command line: decimal, or hexadecimal with 0x in front."""
+    try:
+        return int(text, 16 if text.lower().startswith('0x') else 10)
+    except ValueError:
+        raise argparse.ArgumentTypeError('{0!r} is not a decimal or 0x... number'.format(text))
 
 
 def argparser():
@@ -98,6 +111,17 @@ def argparser():
     ap.add_argument('--device-pair', action='store_true',
                     help='pair the mates of paired-end .bam files on the GPU instead of with a sort of their names on the host; '
                          'reads of equal name keep their order in the file')
+    ap.add_argument('--pair-by', choices=('name', 'flag', 'auto'), default='name',
+                    help='how paired-end files are recognised and their mates told: name (the default) -- read names that end in '
+                         '.1 / .2, mates share the name before that suffix; flag -- FLAG 0x1 / 0x40 / 0x80 and the mate position, '
+                         'what HISAT2, STAR, BWA and Bowtie2 write (always paired on the GPU); auto -- name if the names say '
+                         'paired, otherwise flag')
+    ap.add_argument('--exclude-flags', type=_flag_mask, default=0, metavar='MASK',
+                    help='drop every record that has one of these FLAG bits set, as samtools view -F (decimal or 0x...; e.g. 0x904 '
+                         'for unmapped, secondary and supplementary records; default 0)')
+    ap.add_argument('--require-flags', type=_flag_mask, default=0, metavar='MASK',
+                    help='drop every record that lacks one of these FLAG bits, as samtools view -f (decimal or 0x...; default 0)')
+    ap.add_argument('--min-mapq', type=int, default=0, help='drop every record whose MAPQ is below this, as samtools view -q (0 .. 255; default 0)')
     ap.add_argument('--verify-crc', action='store_true',
                     help='check every BGZF block read from the .bam files against the CRC32 of its trailer (also while '
                          '--create-bai indexes and --sort-bam sorts them) and stop at the first that differs')
@@ -196,6 +220,10 @@ def validate_args(args):
         logging.warning('{0} is greater than the number of available cores ({1}). Reducing to {2}.'
                         .format(args.proc_per_node, n_cpu, max(n_cpu - 1, 1)))
         args.proc_per_node = max(n_cpu - 1, 1)
+    if not args.warm_start_dir:
+        from .bam import check_read_options
+        check_read_options(getattr(args, 'pair_by', 'name'), getattr(args, 'exclude_flags', 0), getattr(args, 'require_flags', 0),
+                           getattr(args, 'min_mapq', 0))
     if (args.nmf_iter < 1) or (args.iter < 1) or (args.downsample_rate < 1):
         raise ValueError('--nmf-iter, --iter, and --downsample-rate must all be >= 1.')
     if args.warm_start_dir:
@@ -315,7 +343,9 @@ def _run(args, output_dir, device, verify):
                      skip_baseline_selection=args.skip_baseline_selection, unique_alignment=not args.non_unique_alignments,
                      n_jobs=args.proc_per_node, inflate='device' if args.device_inflate else 'host',
                      frame='device' if args.device_frame else 'host', verify=verify,
-                     pair='device' if getattr(args, 'device_pair', False) else 'host')
+                     pair='device' if getattr(args, 'device_pair', False) else 'host', pairing=getattr(args, 'pair_by', 'name'),
+                     exclude_flags=getattr(args, 'exclude_flags', 0), require_flags=getattr(args, 'require_flags', 0),
+                     min_mapq=getattr(args, 'min_mapq', 0))
     logging.info('DegNorm pipeline complete! Exiting...')
 
 

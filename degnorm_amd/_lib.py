@@ -35,6 +35,12 @@ class Params(ctypes.Structure):
                 ('want_estimates', ctypes.c_int32), ('reserved', ctypes.c_int32 * 2)]
 
 
+class BamRowsOptions(ctypes.Structure):
+    """dn_bam_rows_options: pairing (0 by name, 1 by FLAG), the two flag masks and the lowest MAPQ kept."""
+    _fields_ = [('pairing', ctypes.c_int32), ('exclude_flags', ctypes.c_uint32), ('require_flags', ctypes.c_uint32),
+                ('min_mapq', ctypes.c_int32)]
+
+
 def load(build_if_missing=False):
     """Load the shared library (optionally building it first).  Raises if it cannot be loaded."""
     global _lib
@@ -146,6 +152,10 @@ def load(build_if_missing=False):
     lib.dn_bam_rows_coverage.argtypes = [vp, P(i32), P(i32), i64] + lib.dn_read_coverage.argtypes[8:]
     lib.dn_bam_rows_pair.argtypes = [vp, P(i32), P(i32), P(i64), P(c.c_double)]
     lib.dn_bam_pair_host.argtypes = [i64, P(i64), P(i32), P(u8), P(i32), P(i32), P(i64)]
+    lib.dn_bam_rows_create_with.argtypes = [c.c_int, i32, i32, i32, P(BamRowsOptions), P(vp)]
+    lib.dn_bam_rows_dropped.argtypes = [vp, P(i64), P(i64), P(i64)]
+    lib.dn_bam_rows_fetch_mates.argtypes = [vp, P(c.c_uint16), P(u8), P(i32)]
+    lib.dn_bam_mate_host.argtypes = [i64, P(i64), P(i32), P(u8), P(i64), P(i32), P(c.c_uint16), P(i32), P(i32), P(i64)]
     lib.dn_bam_cigar_bounds.argtypes = [c.c_int, i64, P(i64), P(i64), P(u32), i32, P(i32), P(i64), P(i64)]
     u64 = c.c_uint64
     lib.dn_bai_create.argtypes = [c.c_int, i32, i64, P(vp)]

@@ -624,6 +624,18 @@ def frame_records(buf, tid=-1, last_pos=_INT32_MIN, device=None, segment_bytes=N
     return off[:n.value], int(used.value), int(lp.value)
 
 
+PAIRINGS = ('name', 'flag', 'auto')
+
+
+def check_read_options(pairing, exclude_flags, require_flags, min_mapq, modes=PAIRINGS):
+    """ValueError unless pairing is one of `modes`, the two masks are ints in 0 .. 0xffff and min_mapq is an int in 0 .. 255."""
+    if pairing not in modes:
+        raise ValueError('pairing must be {0}, not {1!r}'.format(' or '.join(repr(m) for m in modes), pairing))
+    for name, v, top in (('exclude_flags', exclude_flags, 0xffff), ('require_flags', require_flags, 0xffff), ('min_mapq', min_mapq, 255)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= top:
+            raise ValueError('{0} must be an integer in 0 .. {1}, not {2!r}'.format(name, top, v))
+
+
 class _WindowHandle(_Closing):
     """
     What the library handles that take BGZF windows share -- DeviceRows (dn_bam_rows_*) here, _IndexBuilder (dn_bai_*) and _Sorter
@@ -658,13 +670,26 @@ class DeviceRows(_WindowHandle):
     """The device-resident rows of one chromosome (dn_bam_rows): kept records in file order."""
     unit = 'dn_bam_rows'
 
-    def __init__(self, tid, unique_alignment, paired, device=None):
+    def __init__(self, tid, unique_alignment, paired, device=None, pairing='name', exclude_flags=0, require_flags=0, min_mapq=0):
+        """
+        pairing: how a paired store tells mates -- 'name' (qname_unpaired) or 'flag' (FLAG bits and mate positions; the
+        rule is in include/degnorm_amd.h).  exclude_flags, require_flags, min_mapq: the read filters, 0 for none.  With
+        the defaults this is the store of dn_bam_rows_create.
+        """
+        self.h = ctypes.c_void_p()
+        check_read_options(pairing, exclude_flags, require_flags, min_mapq, modes=('name', 'flag'))
         self.lib = _lib.load()
         self.paired = bool(paired)
-        self.h = ctypes.c_void_p()
+        self.by_flag = self.paired and pairing == 'flag'
+        self.filtered = bool(exclude_flags or require_flags or min_mapq)
         dev = int(os.environ.get('LOCAL_RANK', 0)) if device is None else int(device)
-        _check(self.lib.dn_bam_rows_create(dev, int(tid), 1 if unique_alignment else 0, 1 if paired else 0,
-                                           ctypes.byref(self.h)), 'dn_bam_rows_create')
+        if self.by_flag or self.filtered:
+            opt = _lib.BamRowsOptions(1 if self.by_flag else 0, int(exclude_flags), int(require_flags), int(min_mapq))
+            _check(self.lib.dn_bam_rows_create_with(dev, int(tid), 1 if unique_alignment else 0, 1 if paired else 0, ctypes.byref(opt),
+                                                    ctypes.byref(self.h)), 'dn_bam_rows_create_with')
+        else:
+            _check(self.lib.dn_bam_rows_create(dev, int(tid), 1 if unique_alignment else 0, 1 if paired else 0,
+                                               ctypes.byref(self.h)), 'dn_bam_rows_create')
 
     def __del__(self):
         self.close()
@@ -752,10 +777,25 @@ class DeviceRows(_WindowHandle):
                                           _ptr(name_beg, i64), _ptr(name_len, i32), _ptr(names, ctypes.c_uint8)), 'dn_bam_rows_fetch')
         return pos[:n], op_beg[:n], n_op[:n], ops[:n_ops], name_beg[:n], name_len[:n], names[:n_names]
 
+    def fetch_mates(self):
+        """(flag uint16, mapq uint8, next_pos int32) of the rows of a store that pairs by FLAG (ValueError for any other)."""
+        n = self.info()[0]
+        flag, mapq, pnext = np.zeros(max(n, 1), np.uint16), np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.int32)
+        _check(self.lib.dn_bam_rows_fetch_mates(self.h, _ptr(flag, ctypes.c_uint16), _ptr(mapq, ctypes.c_uint8), _ptr(pnext, ctypes.c_int32)),
+               'dn_bam_rows_fetch_mates')
+        return flag[:n], mapq[:n], pnext[:n]
+
+    def dropped(self):
+        """Records of the windows so far that (exclude_flags / require_flags, min_mapq, the FLAG rule's candidate test) dropped."""
+        a, b, c = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        _check(self.lib.dn_bam_rows_dropped(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), 'dn_bam_rows_dropped')
+        return int(a.value), int(b.value), int(c.value)
+
     def pair(self, fetch=False):
         """
         dn_bam_rows_pair: pair the mates on the device and keep the result there.  Rows go in ascending qname_unpaired order,
-        equal keys in file order: np.argsort(self.keys(), kind='stable').  Returns (order int32, pair_id int32, number of ids,
+        equal keys in file order: np.argsort(self.keys(), kind='stable').  A store that pairs by FLAG orders them by the whole
+        name, then by the two mate coordinates (mate_rows on the host).  Returns (order int32, pair_id int32, number of ids,
         device ms) with fetch=True, (None, None, number of ids, device ms) otherwise.
         """
         n = self.info()[0] if fetch else 0
@@ -772,13 +812,14 @@ class DeviceRows(_WindowHandle):
         """
         dn_bam_rows_coverage: the outputs of reads.device_read_coverage for the stored rows.  A paired store's mates are
         paired on the host in the reference's order (pair_order; pair='host') or on the device with equal keys in file order
-        (self.pair(); pair='device'), which moves no keys to the host; self.pair_ms is then the pairing's device ms.
+        (self.pair(); pair='device'), which moves no keys to the host; self.pair_ms is then the pairing's device ms.  A store
+        that pairs by FLAG is always paired on the device, whatever `pair` says.
         """
         if pair not in ('host', 'device'):
             raise ValueError("pair must be 'host' or 'device', not {0!r}".format(pair))
         order, pair_id, n_ids = None, None, 0
         self.pair_ms = 0.0
-        if self.paired and pair == 'device':
+        if self.paired and (pair == 'device' or self.by_flag):
             self.pair_ms = self.pair()[3]
         elif self.paired:
             order, pair_id, n_ids = pair_order(self.keys())
@@ -841,6 +882,35 @@ def pair_rows(keys):
     return order[:n], pair_id[:n], int(n_ids.value)
 
 
+def mate_rows(names, pos, next_pos, flag):
+    """
+    The order and pair ids of DeviceRows.pair() for a store that pairs by FLAG, for rows in file order with these names (an
+    S-dtype array or a list of bytes), positions, mate positions and FLAGs, computed by the library's host build of the same
+    passes (dn_bam_mate_host; no device needed): (order int32, pair_id int32, number of ids).  Rows go by name, then by
+    (uint32) (pos_first + 1), then by (uint32) (pos_last + 1), rows of equal key in file order; a row with 0x40 set has
+    pos_first = pos and pos_last = next_pos, any other row the other way round.
+    """
+    names = [bytes(k) for k in (names.tolist() if isinstance(names, np.ndarray) else names)]
+    n = len(names)
+    pos, next_pos, flag = (np.ascontiguousarray(a, dtype=t).reshape(-1) for a, t in ((pos, np.int64), (next_pos, np.int32), (flag, np.uint16)))
+    if not len(pos) == len(next_pos) == len(flag) == n:
+        raise ValueError('mate_rows: names, pos, next_pos and flag must have one entry per row')
+    name_len = np.array([len(k) for k in names] or [0], dtype=np.int32)
+    name_beg = np.zeros(max(n, 1), dtype=np.int64)
+    if n > 1:
+        np.cumsum(name_len[:-1], out=name_beg[1:n])
+    blob = b''.join(names)
+    chars = np.frombuffer(blob, dtype=np.uint8) if blob else np.zeros(1, np.uint8)
+    if n == 0:
+        pos, next_pos, flag = np.zeros(1, np.int64), np.zeros(1, np.int32), np.zeros(1, np.uint16)
+    order, pair_id = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+    n_ids = ctypes.c_int64(0)
+    _check(_lib.load().dn_bam_mate_host(n, _ptr(name_beg, ctypes.c_int64), _ptr(name_len, ctypes.c_int32), _ptr(chars, ctypes.c_uint8),
+                                        _ptr(pos, ctypes.c_int64), _ptr(next_pos, ctypes.c_int32), _ptr(flag, ctypes.c_uint16),
+                                        _ptr(order, ctypes.c_int32), _ptr(pair_id, ctypes.c_int32), ctypes.byref(n_ids)), 'dn_bam_mate_host')
+    return order[:n], pair_id[:n], int(n_ids.value)
+
+
 def cigar_strings(op_beg, n_op, ops):
     """pysam's cigarstring of every row (None for a row without ops)."""
     lens, codes = (ops >> 4).tolist(), (ops & 15).tolist()
@@ -854,7 +924,8 @@ class NativeBamReadsProcessor(BamReadsProcessor):
     index_extensions = ('.bai', '.csi')          # read_index tells them apart by their first bytes
 
     def __init__(self, bam_file, index_file, chroms=None, n_jobs=1, output_dir=None, unique_alignment=True, verbose=True,
-                 window_bytes=256 << 20, inflate='host', frame='host', frame_segment_bytes=None, verify=False, pair='host'):
+                 window_bytes=256 << 20, inflate='host', frame='host', frame_segment_bytes=None, verify=False, pair='host',
+                 pairing='name', exclude_flags=0, require_flags=0, min_mapq=0):
         """
         BamReadsProcessor on the library's own BAM reader: no pysam.  n_jobs sizes the thread pool that inflates BGZF
         blocks; window_bytes bounds the inflated bytes held (on the host and on the device) besides the chromosome's rows.
@@ -869,7 +940,18 @@ class NativeBamReadsProcessor(BamReadsProcessor):
         pairs them on the GPU, equal keys in file order (DeviceRows.pair), with either inflate and frame; timing then has
         pair_device_ms.  Coverage can differ between the two only where a pair's mates overlap on the reference.  No effect on
         a single-end file, nor on load_chromosome_reads.
+        pairing says which records form a fragment.  'name' (the default, the reference's rule): the file is paired when the
+        first 301 names of the first chromosome end in exactly .1 and .2, and mates share the name up to its last '.'.
+        'flag': it is paired when one of those 301 records has FLAG 0x1, and mates are told by FLAG bits and mate positions
+        (include/degnorm_amd.h), always on the device whatever `pair` says -- what HISAT2, STAR, BWA and Bowtie2 write.
+        'auto': the name rule if it says paired, otherwise the FLAG rule, otherwise single-end; self.pairing_rule is then
+        the rule in force.  exclude_flags / require_flags / min_mapq drop records as samtools view -F / -f / -q does, before
+        every other rule; all 0 by default.  self.dropped sums what each rule dropped.
         """
+        check_read_options(pairing, exclude_flags, require_flags, min_mapq)
+        self.pairing, self.pairing_rule = pairing, 'flag' if pairing == 'flag' else 'name'
+        self.exclude_flags, self.require_flags, self.min_mapq = int(exclude_flags), int(require_flags), int(min_mapq)
+        self.dropped = {'flags': 0, 'mapq': 0, 'not_candidate': 0}
         if inflate not in ('host', 'device'):
             raise ValueError("inflate must be 'host' or 'device', not {0!r}".format(inflate))
         if frame not in ('host', 'device'):
@@ -932,19 +1014,40 @@ class NativeBamReadsProcessor(BamReadsProcessor):
         self.timing['inflate_s'] = self.timing.get('inflate_s', 0.0) + time.perf_counter() - t0
         return out
 
-    def _leading_query_names(self, chrom):
+    def _leading_records(self, chrom):
+        """(query names, FLAGs) of the first 301 records of chrom, in file order, unfiltered."""
         self._load()
-        names, carry, last = [], b'', _INT32_MIN
+        names, flags, carry, last = [], [], b'', _INT32_MIN
         for win in self.windows(chrom, window_bytes=1 << 20):
             data = carry + win
             off, used, last = frame_records(data, self._tid[chrom], last)
             for o in off.tolist():
                 l_name = data[o + 12]
                 names.append(data[o + 36:o + 35 + l_name].decode('ascii', 'replace'))
+                flags.append(data[o + 18] | data[o + 19] << 8)
                 if len(names) > 300:
-                    return names
+                    return names, flags
             carry = data[used:]
-        return names
+        return names, flags
+
+    def _leading_query_names(self, chrom):
+        return self._leading_records(chrom)[0]
+
+    def determine_if_paired(self):
+        """
+        self.paired and self.pairing_rule by self.pairing: the reference's rule on the leading names ('name'), any leading
+        record with FLAG 0x1 ('flag'), or the first of the two that says paired ('auto').
+        """
+        if self.pairing == 'name':
+            return super(NativeBamReadsProcessor, self).determine_if_paired()
+        self.paired = False
+        names, flags = self._leading_records(self.chroms[0])
+        by_name = set(x.split('.')[-1] for x in names) == {'1', '2'}
+        by_flag = any(f & 0x1 for f in flags)
+        if self.pairing == 'auto' and by_name:
+            self.pairing_rule, self.paired = 'name', True
+        else:
+            self.pairing_rule, self.paired = 'flag' if by_flag or self.pairing == 'flag' else 'name', by_flag
 
     def device_rows(self, chrom, device=None):
         """
@@ -955,7 +1058,8 @@ class NativeBamReadsProcessor(BamReadsProcessor):
         self._load()
         tid, t = self._tid[chrom], self.timing
         host_inflate, host_frame = self.inflate == 'host', self.frame == 'host'
-        rows = DeviceRows(tid, self.unique_alignment, self.paired, device)
+        rows = DeviceRows(tid, self.unique_alignment, self.paired, device, self.pairing_rule, self.exclude_flags, self.require_flags,
+                          self.min_mapq)
         carry, last = b'', _INT32_MIN
         calls = 0.0                         # frame='device': seconds in the library's one call per window; it splits them (frame_info)
 
@@ -1003,6 +1107,10 @@ class NativeBamReadsProcessor(BamReadsProcessor):
                             calls += t1 - t0
                 if carry:
                     raise ValueError('{0}: a record of {1} is cut short at the end of its index range'.format(self.filename, chrom))
+                if rows.filtered or rows.by_flag:
+                    rows.n_dropped = dict(zip(('flags', 'mapq', 'not_candidate'), rows.dropped()))
+                    for k, v in rows.n_dropped.items():
+                        self.dropped[k] += v
             finally:
                 if not host_frame:
                     _, fixups, ms, decode_ms = rows.frame_info()
@@ -1019,16 +1127,22 @@ class NativeBamReadsProcessor(BamReadsProcessor):
     def load_chromosome_reads(self, chrom):
         """
         The reference's DataFrame of one chromosome's reads (`qname`, `pos`, `cigar`, plus `qname_unpaired` and sorted by
-        it when paired), built from the device-decoded rows.
+        it when paired), built from the device-decoded rows.  A file paired by FLAG gives the candidate rows in file order
+        with `qname`, `pos`, `cigar`, `flag`, `mapq`, `pnext`, and `qname_unpaired` equal to `qname`.
         """
         rows = self.device_rows(chrom)
         try:
             pos, op_beg, n_op, ops, name_beg, name_len, names = rows.fetch()
+            mates = rows.fetch_mates() if rows.by_flag else None
         finally:
             rows.close()
         nb = names.tobytes()
         qname = [nb[b:b + k].decode('ascii', 'replace') for b, k in zip(name_beg.tolist(), name_len.tolist())]
-        return reads_frame(list(zip(qname, pos.tolist(), cigar_strings(op_beg, n_op, ops))), self.paired)
+        df = reads_frame(list(zip(qname, pos.tolist(), cigar_strings(op_beg, n_op, ops))), self.paired and mates is None)
+        if mates is not None:
+            df['flag'], df['mapq'], df['pnext'] = mates[0].astype(np.int64), mates[1].astype(np.int64), mates[2].astype(np.int64)
+            df['qname_unpaired'] = df['qname']
+        return df
 
     def _chromosome_coverage(self, chrom, chrom_len, gene_overlap_dat, chrom_gene_df, chrom_exon_df):
         ann = Annotation(chrom_len, gene_overlap_dat, chrom_gene_df, chrom_exon_df)
@@ -1039,8 +1153,10 @@ class NativeBamReadsProcessor(BamReadsProcessor):
             counts, ol_cov, idx, val, n_iso_reads, ms = rows.coverage(ann, self.pair)
             self.timing['coverage_s'] = self.timing.get('coverage_s', 0.0) + time.perf_counter() - t0
             self.timing['coverage_device_ms'] = self.timing.get('coverage_device_ms', 0.0) + ms
-            if self.pair == 'device':
+            if self.pair == 'device' or rows.by_flag:
                 self.timing['pair_device_ms'] = self.timing.get('pair_device_ms', 0.0) + rows.pair_ms
+            d = getattr(rows, 'n_dropped', None)
+            self._chrom_note = '' if d is None else '; dropped by flags {flags}, by MAPQ {mapq}, not a mate candidate {not_candidate}'.format(**d)
         finally:
             rows.close()
         csr, ol_cov_dict, read_counts = coverage_outputs(ann, counts, ol_cov, idx, val, n_iso_reads)

@@ -42,6 +42,25 @@ __host__ __device__ __forceinline__ bool pair_same_key(const uint8_t *names, int
     return true;
 }
 
+// Pairing by FLAG (the rule: include/degnorm_amd.h).  A row's key is then its whole name and the two mate coordinates,
+// which these arrays give; pos == NULL is the name rule above.  The coordinates are one more chunk below the name's:
+// mate_chunk, sorted before every name chunk, so rows go by name, then (uint32) (pos_first + 1), then
+// (uint32) (pos_last + 1).  A row with 0x40 set is a first mate: pos_first is its pos and pos_last its next_pos; any
+// other row has them the other way round.
+struct MateCoords {
+    const int64_t *pos = nullptr;
+    const int32_t *next_pos = nullptr;
+    const uint16_t *flag = nullptr;
+};
+
+constexpr uint32_t kFlagFirst = 0x40, kFlagLast = 0x80;
+
+__host__ __device__ __forceinline__ uint64_t mate_chunk(int64_t pos, int32_t next_pos, uint32_t flag)
+{
+    const uint32_t p = (uint32_t) pos + 1u, q = (uint32_t) next_pos + 1u;           // -1 (no position) sorts first
+    return (flag & kFlagFirst) ? (uint64_t) p << 32 | q : (uint64_t) q << 32 | p;
+}
+
 // What pair_device needs besides its outputs: two (uint64, int32) arrays of n and the radix sort's workspace.  Declared
 // by the frame that waits for the stream.
 struct PairWork {
@@ -51,8 +70,8 @@ struct PairWork {
 };
 
 // Queue the pairing of n rows (0 < n < 2^31) with keys of at most max_key bytes on st: order[n] and pair_id[n], device
-// arrays.  The number of ids is pair_id[n - 1] + 1.  A DN_* code.
+// arrays.  The number of ids is pair_id[n - 1] + 1.  mates.pos != NULL: the keys end in the rows' mate_chunk.  A DN_* code.
 int pair_device(hipStream_t st, int64_t n, int32_t max_key, const int64_t *name_beg, const int32_t *key_len, const uint8_t *names,
-                PairWork &W, int32_t *order, int32_t *pair_id);
+                const MateCoords &mates, PairWork &W, int32_t *order, int32_t *pair_id);
 
 }  // namespace dn

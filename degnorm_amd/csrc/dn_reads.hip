@@ -6,7 +6,8 @@
 //
 //   k_prefilter      per row: CIGAR length sum -> end_pos (:404), position pre-filter (:412-413), pair occurrence counts
 //   k_pair_flag / scan / k_pair_compact      (paired) rows whose pair id occurs exactly twice, in the given row order
-//                                             (:417-420); consecutive survivors form the pairs (:451)
+//                                             (:417-420); consecutive survivors form the pairs (:451).  Pairing by FLAG: twice,
+//                                             once as a first mate (0x40) and once as a last one (MateBits)
 //   k_reads          per read (or pair): CIGAR parse (:9-66), mate-2 clipping (:459-470), exon-union filter (:474-484,
 //                    :499-507), overlap-group stage (:585-632), isolated-gene stage (:685-774); integer atomics for the
 //                    counts, +1 / -1 events of the read's merged runs into two difference arrays
@@ -24,6 +25,7 @@
 #include <functional>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include "../../include/degnorm_amd.h"
 #include "dn_host.hpp"
@@ -180,9 +182,20 @@ template <class C> struct ReadsArgs {
                                           // overlap-gene index leaves [-1, L) (exons outside the gene span)
 };
 
-template <class C>
+// Pairing by FLAG: the FLAG of the row taken at position r is flag[order[r]].  A pair is then a key with two rows of which
+// one is a first mate (0x40): every row adds 1 to its key's counter and a first mate kMateFirst besides, and the counter
+// of a pair -- and of nothing else, among at most kMateRowsMax rows: the sum is taken modulo 2^32, and rows = 2 (mod 2^30)
+// leaves rows = 2 -- reads kMatePair.  The name rule (flag == NULL) adds 1 per row and a pair reads 2.
+struct MateBits {
+    const uint16_t *flag = nullptr;
+    const int32_t *order = nullptr;
+};
+constexpr int32_t kMateFirst = 1 << 30, kMatePair = 2 | kMateFirst;
+constexpr int64_t kMateRowsMax = (int64_t) 1 << 30;
+
+template <class C, bool MATES>
 __global__ __launch_bounds__(kNT) void k_prefilter(int64_t n, const int64_t *__restrict__ pos, C cig, int64_t keep_lo, int64_t keep_hi,
-                                                   const int32_t *__restrict__ pair_id, int32_t *__restrict__ pair_cnt,
+                                                   const int32_t *__restrict__ pair_id, int32_t *__restrict__ pair_cnt, MateBits mates,
                                                    int64_t *__restrict__ end_pos, int32_t *__restrict__ keep)
 {
     for (int64_t r = (int64_t) blockIdx.x * kNT + threadIdx.x; r < n; r += (int64_t) gridDim.x * kNT) {
@@ -190,15 +203,19 @@ __global__ __launch_bounds__(kNT) void k_prefilter(int64_t n, const int64_t *__r
         end_pos[r] = e;
         const int32_t k = pos[r] >= keep_lo && e <= keep_hi;
         keep[r] = k;
-        if (k && pair_id) atomicAdd(pair_cnt + pair_id[r], 1);
+        if (MATES) {
+            if (k) atomicAdd((unsigned int *) pair_cnt + pair_id[r], (mates.flag[mates.order[r]] & dn::kFlagFirst) ? 1u | (unsigned int) kMateFirst : 1u);
+        } else if (k && pair_id) {
+            atomicAdd(pair_cnt + pair_id[r], 1);
+        }
     }
 }
 
 __global__ __launch_bounds__(kNT) void k_pair_flag(int64_t n, const int32_t *__restrict__ pair_id, const int32_t *__restrict__ pair_cnt,
-                                                   int32_t *__restrict__ keep)
+                                                   int32_t is_pair, int32_t *__restrict__ keep)
 {
     for (int64_t r = (int64_t) blockIdx.x * kNT + threadIdx.x; r < n; r += (int64_t) gridDim.x * kNT)
-        keep[r] = keep[r] && pair_cnt[pair_id[r]] == 2;
+        keep[r] = keep[r] && pair_cnt[pair_id[r]] == is_pair;
 }
 
 __global__ __launch_bounds__(kNT) void k_pair_compact(int64_t n, const int32_t *__restrict__ keep, const int32_t *__restrict__ rank,
@@ -370,11 +387,16 @@ struct CoverageIO {
 // The coverage stages on n_rows device-resident rows (positions d_pos, CIGARs `cig`), queued on `st` after whatever the
 // caller queued there (its uploads).  pair_id (host, paired only) is checked and uploaded here; d_pair_id, when not NULL,
 // is the same array already on the device and the library's own (dn_bam_rows_pair): pair_id is then not read.
+// mates.flag != NULL (BamCigars with d_pair_id only): the pairs are those of the FLAG rule (MateBits).
 // cigar_text(r) gives row r's CIGAR as text for the error messages.
 template <class C>
 int coverage_stages(hipStream_t st, int32_t paired, int64_t n_rows, const int64_t *d_pos, C cig, const int32_t *pair_id,
-                    const int32_t *d_pair_id, int64_t n_pair_ids, const CoverageIO &io, const std::function<std::string(int64_t)> &cigar_text)
+                    const int32_t *d_pair_id, int64_t n_pair_ids, const CoverageIO &io, const std::function<std::string(int64_t)> &cigar_text,
+                    MateBits mates = MateBits{})
 {
+    constexpr bool kCanMate = std::is_same<C, BamCigars>::value;
+    if (mates.flag && (!kCanMate || !paired || !d_pair_id || !mates.order || n_rows > kMateRowsMax))
+        return dn::fail(n_rows > kMateRowsMax ? DN_E_UNSUPPORTED : DN_E_INVALID, "dn_read_coverage: pairing by FLAG takes a paired row store of at most 2^30 rows");
     const int64_t chrom_len = io.chrom_len, n_exon = io.n_exon, n_groups = io.n_groups, n_iso = io.n_iso, n_iso_union = io.n_iso_union,
                   n_genes = io.n_genes, csr_cap = io.csr_cap;
     if (n_rows < 0 || n_rows > INT32_MAX - 1 || chrom_len <= 0 || chrom_len > INT32_MAX - 4 || n_exon < 0 || n_groups < 0 || n_iso < 0 || n_iso_union < 0 ||
@@ -445,12 +467,20 @@ int coverage_stages(hipStream_t st, int32_t paired, int64_t n_rows, const int64_
         DN_TRY(hipMemsetAsync(d_err, 0xff, 3 * sizeof(unsigned long long), st));
         if (paired) DN_TRY(hipMemsetAsync(d_pcnt, 0, sizeof(int32_t) * (size_t) n_pair_ids, st));
         if (n_rows > 0) {
-            hipLaunchKernelGGL(k_prefilter<C>, dim3(dn::grid_for(n_rows, kNT, kGridCap)), dim3(kNT), 0, st, n_rows, d_pos, cig, io.keep_lo, io.keep_hi,
-                               paired ? p_pid : (const int32_t *) nullptr, d_pcnt, d_end, d_keep);
+            const dim3 pre_grid(dn::grid_for(n_rows, kNT, kGridCap));
+            if constexpr (kCanMate) {
+                if (mates.flag)
+                    hipLaunchKernelGGL((k_prefilter<C, true>), pre_grid, dim3(kNT), 0, st, n_rows, d_pos, cig, io.keep_lo, io.keep_hi, p_pid, d_pcnt.get(),
+                                       mates, d_end.get(), d_keep.get());
+            }
+            if (!mates.flag)
+                hipLaunchKernelGGL((k_prefilter<C, false>), pre_grid, dim3(kNT), 0, st, n_rows, d_pos, cig, io.keep_lo, io.keep_hi,
+                                   paired ? p_pid : (const int32_t *) nullptr, d_pcnt.get(), mates, d_end.get(), d_keep.get());
             DN_TRY(hipGetLastError());
             int64_t n_units = n_rows;
             if (paired) {
-                hipLaunchKernelGGL(k_pair_flag, dim3(dn::grid_for(n_rows, kNT, kGridCap)), dim3(kNT), 0, st, n_rows, p_pid, d_pcnt.get(), d_keep.get());
+                hipLaunchKernelGGL(k_pair_flag, dim3(dn::grid_for(n_rows, kNT, kGridCap)), dim3(kNT), 0, st, n_rows, p_pid, d_pcnt.get(),
+                                   mates.flag ? kMatePair : 2, d_keep.get());
                 DN_TRY(hipGetLastError());
                 // exclusive rank of every surviving row; rank[n_rows] is the number of survivors
                 DN_TRY(hipMemsetAsync(d_keep + n_rows, 0, sizeof(int32_t), st));       // keep[n_rows] = 0: rank[n_rows] = #survivors
@@ -597,6 +627,10 @@ extern "C" int dn_reads_cigar_bounds(int device, int64_t n, const int64_t *pos, 
 // record of the window and applies the reference's read filters (reads.py load_chromosome_reads), three scans give each kept row its place, and k_bam_write appends the kept rows, in file order,
 // to the row store: position, binary CIGAR ops, read name and the length of its qname_unpaired prefix.  The coverage
 // stages then read the binary CIGARs in place (BamCigars).  The fixed part of a record is read through dn_bam_record.hpp.
+// A store made by dn_bam_rows_create_with runs the scan with the read filters (FLAG masks, MAPQ) in front of the other rules
+// and, when it pairs by FLAG, keeps the candidate rows of that rule with their FLAG, MAPQ and PNEXT (the rule:
+// include/degnorm_amd.h); the store of dn_bam_rows_create runs the kernels without any of it (k_bam_scan<false>,
+// k_bam_write<false>).
 
 namespace {
 
@@ -679,12 +713,31 @@ __device__ bool bam_aux(const uint8_t *w, int64_t q, int64_t end, int &nh_state,
 
 struct BamFilter {
     int32_t tid, unique, paired;
+    // the options of dn_bam_rows_create_with (all 0: the store of dn_bam_rows_create)
+    int32_t by_flag;                    // a paired store whose rows are the candidates of the FLAG rule
+    uint32_t exclude, require;
+    int32_t min_mapq;
+    bool options() const { return by_flag || exclude || require || min_mapq; }
 };
 
-// per record: kept (refID == tid, NH rule, mate rule), its op count and name length when kept; errors (first record index)
+enum { kDropFlags, kDropMapq, kDropCandidate, kNDrop };
+constexpr int kBamMapq = 13;            // the MAPQ byte of a record
+
+// a record that passed the read filters and the NH rule is a row of a FLAG-rule store
+__device__ __forceinline__ bool mate_candidate(const BamRec &R, int32_t tid)
+{
+    const uint32_t f = R.flag;
+    return (f & 0x1u) && !(f & 0xCu) && R.next_ref == tid && ((f & dn::kFlagFirst) != 0) != ((f & dn::kFlagLast) != 0);
+}
+
+// per record: kept (refID == tid, NH rule, mate rule), its op count and name length when kept; errors (first record index).
+// OPTIONS (F.options()): the read filters come first among the rules that drop a well-formed record, the FLAG rule's
+// candidate test stands in for the mate rule, and dropped[] counts what each took.
+template <bool OPTIONS>
 __global__ __launch_bounds__(kNT) void k_bam_scan(const uint8_t *__restrict__ w, int64_t n_bytes, const int64_t *__restrict__ rec_off,
                                                   int64_t n_rec, BamFilter F, int32_t *__restrict__ keep, int32_t *__restrict__ n_ops,
-                                                  int32_t *__restrict__ n_name, unsigned long long *__restrict__ err)
+                                                  int32_t *__restrict__ n_name, unsigned long long *__restrict__ err,
+                                                  unsigned long long *__restrict__ dropped)
 {
     for (int64_t i = (int64_t) blockIdx.x * kNT + threadIdx.x; i < n_rec; i += (int64_t) gridDim.x * kNT) {
         BamRec R;
@@ -697,8 +750,11 @@ __global__ __launch_bounds__(kNT) void k_bam_scan(const uint8_t *__restrict__ w,
             bool cg;
             k = 1;
             if (!bam_aux(w, R.aux, R.end(), nh_state, nh, cg)) { atomicMin(err + kBamErrMalformed, (unsigned long long) i); k = 0; }
+            else if (OPTIONS && ((R.flag & F.exclude) != 0 || (R.flag & F.require) != F.require)) { atomicAdd(dropped + kDropFlags, 1ull); k = 0; }
+            else if (OPTIONS && (int32_t) w[R.o + kBamMapq] < F.min_mapq) { atomicAdd(dropped + kDropMapq, 1ull); k = 0; }
             else if (F.unique && nh_state == 2) { atomicMin(err + kBamErrNh, (unsigned long long) i); k = 0; }
             else if (F.unique && nh_state == 1 && nh > 1) k = 0;
+            else if (OPTIONS && F.by_flag) { if (!mate_candidate(R, F.tid)) { atomicAdd(dropped + kDropCandidate, 1ull); k = 0; } }
             else if (F.paired && R.next_ref == -1) k = 0;
             if (k) {
                 if (R.n_cig == 0) atomicMin(err + kBamErrNoCigar, (unsigned long long) i);
@@ -722,8 +778,14 @@ struct BamRowsOut {
     uint32_t *ops;
     uint8_t *names;
     int32_t *max_key;
+    // a FLAG-rule store only
+    uint16_t *flag;
+    uint8_t *mapq;
+    int32_t *next_pos;
 };
 
+// MATES: the rows of a FLAG-rule store, which keep FLAG, MAPQ and PNEXT and whose key is the whole name
+template <bool MATES>
 __global__ __launch_bounds__(kNT) void k_bam_write(const uint8_t *__restrict__ w, int64_t n_bytes, const int64_t *__restrict__ rec_off,
                                                    int64_t n_rec, const int32_t *__restrict__ keep, const int32_t *__restrict__ rank,
                                                    const int32_t *__restrict__ op_rank, const int32_t *__restrict__ name_rank,
@@ -743,6 +805,12 @@ __global__ __launch_bounds__(kNT) void k_bam_write(const uint8_t *__restrict__ w
             const uint8_t ch = w[R.name() + c];
             O.names[nb + c] = ch;
             if (ch == '.') key = c;
+        }
+        if (MATES) {
+            key = nl;
+            O.flag[r] = (uint16_t) R.flag;
+            O.mapq[r] = w[R.o + kBamMapq];
+            O.next_pos[r] = R.next_pos;
         }
         O.name_beg[r] = nb;
         O.name_len[r] = nl;
@@ -793,6 +861,11 @@ struct dn_bam_rows_s {
     dn::GrowBuffer<int64_t> pos, op_beg, name_beg, rec_off;
     dn::GrowBuffer<int32_t> n_op, name_len, key_len;
     dn::DeviceBuffer<int32_t> max_key;
+    // a FLAG-rule store's FLAG, MAPQ and PNEXT per row, and for every store with options what each rule dropped so far
+    dn::GrowBuffer<uint16_t> flag;
+    dn::GrowBuffer<uint8_t> mapq;
+    dn::GrowBuffer<int32_t> next_pos;
+    dn::DeviceBuffer<unsigned long long> dropped;
     dn::GrowBuffer<int32_t> keep, w_ops, w_name, rank, op_rank, name_rank;
     dn::GrowBuffer<uint32_t> ops;
     dn::GrowBuffer<uint8_t> names, win;
@@ -849,26 +922,79 @@ extern "C" int dn_bam_frame(const uint8_t *buf, int64_t n_bytes, int32_t tid, in
     return DN_OK;
 }
 
-extern "C" int dn_bam_rows_create(int device, int32_t tid, int32_t unique_alignment, int32_t paired, dn_bam_rows *out)
+static int rows_create(const char *who, int device, const BamFilter &F, dn_bam_rows *out)
 {
-    dn::clear_error();
-    if (!out) return dn::fail(DN_E_INVALID, "dn_bam_rows_create: bad argument");
     *out = nullptr;
-    const char *who = "dn_bam_rows_create";
     auto h = std::make_unique<dn_bam_rows_s>();
     h->device = device;
-    h->F = BamFilter{tid, unique_alignment ? 1 : 0, paired ? 1 : 0};
+    h->F = F;
     DN_TRY_AS(who, hipSetDevice(device));
     DN_TRY_AS(who, h->st.create(hipStreamCreate));
     const int rc = dn::synced(h->st, [&]() -> int {
         DN_TRY_AS(who, alloc_padded(h->max_key, 1));
         DN_TRY_AS(who, alloc_padded(h->err, kBamNErr));
+        DN_TRY_AS(who, alloc_padded(h->dropped, kNDrop));
         DN_TRY_AS(who, hipMemsetAsync(h->max_key, 0, sizeof(int32_t), h->st));
+        DN_TRY_AS(who, hipMemsetAsync(h->dropped, 0, sizeof(unsigned long long) * kNDrop, h->st));
         DN_TRY_AS(who, hipStreamSynchronize(h->st));
         return DN_OK;
     });
     if (rc == DN_OK) *out = h.release();
     return rc;
+}
+
+extern "C" int dn_bam_rows_create(int device, int32_t tid, int32_t unique_alignment, int32_t paired, dn_bam_rows *out)
+{
+    dn::clear_error();
+    if (!out) return dn::fail(DN_E_INVALID, "dn_bam_rows_create: bad argument");
+    return rows_create("dn_bam_rows_create", device, BamFilter{tid, unique_alignment ? 1 : 0, paired ? 1 : 0, 0, 0u, 0u, 0}, out);
+}
+
+extern "C" int dn_bam_rows_create_with(int device, int32_t tid, int32_t unique_alignment, int32_t paired, const dn_bam_rows_options *opt,
+                                       dn_bam_rows *out)
+{
+    dn::clear_error();
+    if (!out || !opt || (opt->pairing != DN_PAIR_BY_NAME && opt->pairing != DN_PAIR_BY_FLAG) || opt->exclude_flags > 0xffffu ||
+        opt->require_flags > 0xffffu || opt->min_mapq < 0 || opt->min_mapq > 255)
+        return dn::fail(DN_E_INVALID, "dn_bam_rows_create_with: bad argument (pairing 0 or 1, flag masks up to 0xffff, min_mapq 0 .. 255)");
+    const int32_t by_flag = paired && opt->pairing == DN_PAIR_BY_FLAG;
+    return rows_create("dn_bam_rows_create_with", device,
+                       BamFilter{tid, unique_alignment ? 1 : 0, paired ? 1 : 0, by_flag, opt->exclude_flags, opt->require_flags, opt->min_mapq}, out);
+}
+
+extern "C" int dn_bam_rows_dropped(dn_bam_rows h, int64_t *by_flags, int64_t *by_mapq, int64_t *not_candidate)
+{
+    dn::clear_error();
+    if (!h) return dn::fail(DN_E_INVALID, "dn_bam_rows_dropped: bad argument");
+    unsigned long long d[kNDrop] = {0, 0, 0};
+    DN_TRY(hipSetDevice(h->device));
+    const int rc = dn::synced(h->st, [&]() -> int {
+        DN_TRY(hipMemcpyAsync(d, h->dropped, sizeof(d), hipMemcpyDeviceToHost, h->st));
+        DN_TRY(hipStreamSynchronize(h->st));
+        return DN_OK;
+    });
+    if (rc != DN_OK) return rc;
+    if (by_flags) *by_flags = (int64_t) d[kDropFlags];
+    if (by_mapq) *by_mapq = (int64_t) d[kDropMapq];
+    if (not_candidate) *not_candidate = (int64_t) d[kDropCandidate];
+    return DN_OK;
+}
+
+extern "C" int dn_bam_rows_fetch_mates(dn_bam_rows h, uint16_t *flag, uint8_t *mapq, int32_t *next_pos)
+{
+    dn::clear_error();
+    if (!h || !h->F.by_flag) return dn::fail(DN_E_INVALID, "dn_bam_rows_fetch_mates: bad argument (a store that pairs by FLAG)");
+    hipStream_t st = h->st;
+    const size_t n = (size_t) h->n_rows;
+    if (n == 0) return DN_OK;
+    DN_TRY(hipSetDevice(h->device));
+    return dn::synced(st, [&]() -> int {
+        if (flag) DN_TRY(hipMemcpyAsync(flag, h->flag, sizeof(uint16_t) * n, hipMemcpyDeviceToHost, st));
+        if (mapq) DN_TRY(hipMemcpyAsync(mapq, h->mapq, n, hipMemcpyDeviceToHost, st));
+        if (next_pos) DN_TRY(hipMemcpyAsync(next_pos, h->next_pos, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+        DN_TRY(hipStreamSynchronize(st));
+        return DN_OK;
+    });
 }
 
 extern "C" void dn_bam_rows_destroy(dn_bam_rows h)
@@ -919,8 +1045,9 @@ int append_window(dn_bam_rows h, const uint8_t *window, int64_t n_bytes, int64_t
         DN_TRY(hipMemsetAsync(h->keep + n_rec, 0, sizeof(int32_t), st));
         DN_TRY(hipMemsetAsync(h->w_ops + n_rec, 0, sizeof(int32_t), st));
         DN_TRY(hipMemsetAsync(h->w_name + n_rec, 0, sizeof(int32_t), st));
-        hipLaunchKernelGGL(k_bam_scan, dim3(dn::grid_for(n_rec, kNT, kGridCap)), dim3(kNT), 0, st, h->win.get(), n_bytes, h->rec_off.get(), n_rec, h->F,
-                           h->keep.get(), h->w_ops.get(), h->w_name.get(), h->err.get());
+        hipLaunchKernelGGL(h->F.options() ? k_bam_scan<true> : k_bam_scan<false>, dim3(dn::grid_for(n_rec, kNT, kGridCap)), dim3(kNT), 0, st,
+                           (const uint8_t *) h->win.get(), n_bytes, (const int64_t *) h->rec_off.get(), n_rec, h->F, h->keep.get(), h->w_ops.get(),
+                           h->w_name.get(), h->err.get(), h->dropped.get());
         DN_TRY(hipGetLastError());
         const auto rank_of = [&](int32_t *flag, int32_t *rank) {      // exclusive; rank[n_rec] is the total
             return h->scratch.run([&](void *tmp, size_t &bytes) { return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, flag, rank, (int) n_rec + 1, st); });
@@ -949,9 +1076,14 @@ int append_window(dn_bam_rows h, const uint8_t *window, int64_t n_bytes, int64_t
             DN_TRY(h->n_op.reserve(rows, n, st)); DN_TRY(h->name_len.reserve(rows, n, st)); DN_TRY(h->key_len.reserve(rows, n, st));
             DN_TRY(h->ops.reserve(h->n_ops + tot[1], h->n_ops, st));
             DN_TRY(h->names.reserve(h->n_names + tot[2], h->n_names, st));
-            BamRowsOut O{h->pos, h->op_beg, h->name_beg, h->n_op, h->name_len, h->key_len, h->ops, h->names, h->max_key};
-            hipLaunchKernelGGL(k_bam_write, dim3(dn::grid_for(n_rec, kNT, kGridCap)), dim3(kNT), 0, st, h->win.get(), n_bytes, h->rec_off.get(), n_rec,
-                               h->keep.get(), h->rank.get(), h->op_rank.get(), h->name_rank.get(), h->n_rows, h->n_ops, h->n_names, O);
+            if (h->F.by_flag) {
+                DN_TRY(h->flag.reserve(rows, n, st)); DN_TRY(h->mapq.reserve(rows, n, st)); DN_TRY(h->next_pos.reserve(rows, n, st));
+            }
+            BamRowsOut O{h->pos, h->op_beg, h->name_beg, h->n_op, h->name_len, h->key_len, h->ops, h->names, h->max_key, h->flag, h->mapq, h->next_pos};
+            hipLaunchKernelGGL(h->F.by_flag ? k_bam_write<true> : k_bam_write<false>, dim3(dn::grid_for(n_rec, kNT, kGridCap)), dim3(kNT), 0, st,
+                               (const uint8_t *) h->win.get(), n_bytes, (const int64_t *) h->rec_off.get(), n_rec, (const int32_t *) h->keep.get(),
+                               (const int32_t *) h->rank.get(), (const int32_t *) h->op_rank.get(), (const int32_t *) h->name_rank.get(), h->n_rows,
+                               h->n_ops, h->n_names, O);
             DN_TRY(hipGetLastError());
             DN_TRY(hipStreamSynchronize(st));
             h->n_rows += tot[0];
@@ -1234,7 +1366,9 @@ extern "C" int dn_bam_rows_pair(dn_bam_rows h, int32_t *order_out, int32_t *pair
             DN_TRY(hipStreamSynchronize(st));
             DN_TRY(alloc_padded(h->pair_order, (size_t) n)); DN_TRY(alloc_padded(h->pair_id, (size_t) n));
             DN_TRY(hipEventRecord(e0, st));
-            const int rc = dn::pair_device(st, n, mk, h->name_beg, h->key_len, h->names, work, h->pair_order, h->pair_id);
+            dn::MateCoords mates;
+            if (h->F.by_flag) { mates.pos = h->pos; mates.next_pos = h->next_pos; mates.flag = h->flag; }
+            const int rc = dn::pair_device(st, n, mk, h->name_beg, h->key_len, h->names, mates, work, h->pair_order, h->pair_id);
             if (rc != DN_OK) return rc;
             DN_TRY(hipEventRecord(e1, st));
             DN_TRY(hipMemcpyAsync(&last_id, h->pair_id + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -1266,6 +1400,10 @@ extern "C" int dn_bam_rows_coverage(dn_bam_rows h, const int32_t *order, const i
     if (!h) return dn::fail(DN_E_INVALID, "dn_bam_rows_coverage: bad argument");
     const bool resident = h->F.paired && h->n_rows > 0 && !order && !pair_id && h->has_pairing;     // the pairing of dn_bam_rows_pair
     if (h->F.paired && h->n_rows > 0 && !order && !resident) return dn::fail(DN_E_INVALID, "dn_bam_rows_coverage: bad argument");
+    if (h->F.by_flag && h->n_rows > 0 && !resident)
+        return dn::fail(DN_E_INVALID, "dn_bam_rows_coverage: a store that pairs by FLAG takes the pairing of dn_bam_rows_pair (order and pair_id NULL)");
+    MateBits mate_bits;
+    if (h->F.by_flag && resident) { mate_bits.flag = h->flag; mate_bits.order = h->pair_order; }
     if (h->has_no_cigar) return dn::fail(DN_E_INVALID, "read " + h->no_cigar + " has no CIGAR string");     // the reference's CIGAR regex on cigarstring None
     COVERAGE_IO;
     const int64_t n = h->n_rows;
@@ -1319,7 +1457,7 @@ extern "C" int dn_bam_rows_coverage(dn_bam_rows h, const int32_t *order, const i
                 if (hipMemcpy(&name[0], h->names + nb, (size_t) nl, hipMemcpyDeviceToHost) != hipSuccess) name = "?";
             }
             return cigar_string(ops.data(), (int64_t) ops.size()) + " (read " + name + ")";
-        });
+        }, mate_bits);
     });
 }
 

@@ -15,7 +15,7 @@ import shutil
 
 import numpy as np
 
-from .bam import NativeBamReadsProcessor
+from .bam import NativeBamReadsProcessor, check_read_options
 from .coverage_merge import merge_coverage, merge_read_counts
 from .gene_processing import GeneAnnotationProcessor, get_gene_overlap_structure
 from .utils import subset_to_chrom
@@ -24,17 +24,20 @@ from .warm_start import select_genes
 
 def prepare_inputs(bam_files, bai_files, genome_annotation, output_dir, downsample_rate=1, minimax_coverage=0,
                    unique_alignment=True, n_jobs=1, verbose=True, device=None, inflate='host', frame='host', verify=False,
-                   pair='host'):
+                   pair='host', pairing='name', exclude_flags=0, require_flags=0, min_mapq=0):
     """
     The reference's .bam preprocessing path and gene filter (__main__.py:56-247): chromosomes common to every .bam header and
     the annotation, per-sample coverage and read counts, their merge (coverage matrices pickled per chromosome into
     output_dir, per-sample directories removed), the gene tables re-ordered to the coverage dict, gene_exon_metadata.csv and
     read_counts.csv, then the filter on maximum coverage and length.  inflate, frame: NativeBamReadsProcessor's
     (each 'host' or 'device'); verify: check every BGZF block read against the CRC32 of its trailer; pair: where the mates of
-    paired-end files are paired ('host': the reference's order; 'device': on the GPU, equal names in file order).
+    paired-end files are paired ('host': the reference's order; 'device': on the GPU, equal names in file order).  pairing
+    ('name', 'flag' or 'auto'), exclude_flags, require_flags, min_mapq: which records form a fragment and which are dropped
+    first (NativeBamReadsProcessor); a bad value is a ValueError before any file is opened.
 
     :return: (gene_cov_dict, read_count_df, genes_df, exon_df, sample_ids)
     """
+    check_read_options(pairing, exclude_flags, require_flags, min_mapq)
     chroms = list()
     for bam_file, bai_file in zip(bam_files, bai_files):
         header = NativeBamReadsProcessor(bam_file, index_file=bai_file, verbose=False, verify=verify).header
@@ -59,7 +62,8 @@ def prepare_inputs(bam_files, bai_files, genome_annotation, output_dir, downsamp
         logging.info('Loading RNA-seq data file {0} / {1}'.format(idx + 1, len(bam_files)))
         reader = NativeBamReadsProcessor(bam_file, index_file=bai_file, chroms=chroms, n_jobs=n_jobs, output_dir=output_dir,
                                          unique_alignment=unique_alignment, verbose=verbose, inflate=inflate, frame=frame,
-                                         verify=verify, pair=pair)
+                                         verify=verify, pair=pair, pairing=pairing, exclude_flags=exclude_flags,
+                                         require_flags=require_flags, min_mapq=min_mapq)
         sample_ids.append(reader.sample_id)
         reader.coverage_read_counts(gene_overlap_dict, gene_df=genes_df, exon_df=exon_df)
 
@@ -89,10 +93,11 @@ def prepare_inputs(bam_files, bai_files, genome_annotation, output_dir, downsamp
 
 def run_pipeline(bam_files, bai_files, genome_annotation, output_dir, degnorm_iter=5, nmf_iter=100, downsample_rate=1,
                  minimax_coverage=0, skip_baseline_selection=False, unique_alignment=True, n_jobs=1, verbose=True, device=None,
-                 inflate='host', frame='host', verify=False, pair='host'):
+                 inflate='host', frame='host', verify=False, pair='host', pairing='name', exclude_flags=0, require_flags=0, min_mapq=0):
     """
     DegNorm on .bam files and a .gtf or .gff3 annotation, results written to output_dir (an existing directory).  verify: check every
-    BGZF block read against the CRC32 of its trailer (ValueError naming the file and the block).
+    BGZF block read against the CRC32 of its trailer (ValueError naming the file and the block).  pairing, exclude_flags,
+    require_flags, min_mapq: as for prepare_inputs.
 
     :return: (fitted GeneNMFOA, estimates, gene_cov_dict, read_count_df, genes_df, exon_df, sample_ids)
     """
@@ -100,7 +105,7 @@ def run_pipeline(bam_files, bai_files, genome_annotation, output_dir, degnorm_it
     gene_cov_dict, read_count_df, genes_df, exon_df, sample_ids = prepare_inputs(
         bam_files, bai_files, genome_annotation, output_dir, downsample_rate=downsample_rate, minimax_coverage=minimax_coverage,
         unique_alignment=unique_alignment, n_jobs=n_jobs, verbose=verbose, device=device, inflate=inflate, frame=frame,
-        verify=verify, pair=pair)
+        verify=verify, pair=pair, pairing=pairing, exclude_flags=exclude_flags, require_flags=require_flags, min_mapq=min_mapq)
     logging.info('RNA-seq sample identifiers: \n\t' + ', '.join(sample_ids))
     logging.info('DegNorm will run on {0} genes, downsampling rate = 1 / {1}, {2} baseline selection.'
                  .format(len(gene_cov_dict), downsample_rate, 'without' if skip_baseline_selection else 'with'))

@@ -432,8 +432,8 @@ class BamReadsProcessor(object):
             sparse.save_npz(chrom_cov_file, matrix=csr)
         DataFrame({'gene': list(read_counts.keys()), self.sample_id: list(read_counts.values())}).to_csv(count_file, index=False)
         if verbose:
-            logging.info('SAMPLE {0}, CHR {1} -- {2} reads, {3} counted'.format(
-                self.sample_id, chrom, n_reads, sum(read_counts.values())))
+            logging.info('SAMPLE {0}, CHR {1} -- {2} reads, {3} counted{4}'.format(
+                self.sample_id, chrom, n_reads, sum(read_counts.values()), getattr(self, '_chrom_note', '')))
         return None
 
     def _chromosome_coverage(self, chrom, chrom_len, gene_overlap_dat, chrom_gene_df, chrom_exon_df):

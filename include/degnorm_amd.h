@@ -338,8 +338,50 @@ const char *dn_reads_last_error(void);             /* = dn_last_error() */
  *   dn_bam_pair_host      host only: the same order and ids for n keys names[name_beg[r] .. name_beg[r] + key_len[r]),
  *                         by the same passes with std::stable_sort; n below 2^31.
  *   dn_bam_cigar_bounds   dn_reads_cigar_bounds on binary CIGARs: row r's ops are ops[op_off[r] .. op_off[r+1]).
+ *
+ * Read filters and pairing by FLAG (dn_bam_rows_create_with; with every option 0 it is dn_bam_rows_create).
+ * Read filters, of a single-end and a paired store alike.  A well-formed record of refID tid is dropped
+ *   - when flag & exclude_flags != 0, or flag & require_flags != require_flags (counted as dropped by flags), else
+ *   - when its MAPQ byte, 0 .. 255 taken as that number, is below min_mapq (counted as dropped by MAPQ).
+ * The filters come before the NH rule, the mate rule and the CIGAR checks: a record they drop raises none of the errors of
+ * a kept row (NH of a non-integer type, no CIGAR, an unsupported op, a CIGAR in CG); a malformed record is an error
+ * whatever the filters say.
+ * Pairing by FLAG (pairing = DN_PAIR_BY_FLAG on a paired store; aligners that give both mates of a template one QNAME).
+ *   - Candidate rows are the records that pass the read filters and the NH rule and have 0x1 set, 0x4 and 0x8 clear,
+ *     next_refID == tid and exactly one of 0x40 and 0x80 set.  No other record is stored (counted as not a candidate);
+ *     this stands in for the rule next_refID != -1.
+ *   - The mate key of a row is (QNAME bytes, pos_first, pos_last): a 0x40 row has pos_first = pos and pos_last = next_pos,
+ *     a 0x80 row pos_first = next_pos and pos_last = pos.  Two alignments of one multi-mapping template at different loci
+ *     have different keys.
+ *   - dn_bam_rows_pair orders the rows by name -- unsigned bytes, zero-padded, as above, the whole name being the key --
+ *     then by (uint32) (pos_first + 1), then by (uint32) (pos_last + 1); rows of equal key stay in file order, and pair_id
+ *     is the number of distinct keys before a position.
+ *   - A pair is a key whose rows, among those that pass the position pre-filter of the coverage stages (keep_lo, keep_hi),
+ *     are exactly two, one with 0x40 and one with 0x80.  Any other composition contributes nothing.  Mate 1 of the
+ *     asymmetric clipping is the row that comes first in the file.
+ *   dn_bam_rows_coverage of such a store takes the pairing of dn_bam_rows_pair only (order == NULL, pair_id == NULL), and
+ *   at most 2^30 rows.
+ *   dn_bam_rows_dropped      what each rule dropped in the windows appended so far (nullable outputs).
+ *   dn_bam_rows_fetch_mates  FLAG, MAPQ and next_pos of the rows of a store that pairs by FLAG (nullable outputs; any other
+ *                            store is DN_E_INVALID: it does not keep them).
+ *   dn_bam_mate_host         host only: order and ids of the FLAG rule for n rows with names names[name_beg[r] .. name_beg[r] +
+ *                            name_len[r]), by the passes of dn_bam_rows_pair with std::stable_sort.  A row with 0x40 set counts
+ *                            as a first mate, any other as a last one.
  * Errors: dn_reads_last_error(). */
 typedef struct dn_bam_rows_s *dn_bam_rows;
+enum { DN_PAIR_BY_NAME = 0, DN_PAIR_BY_FLAG = 1 };
+typedef struct {
+    int32_t  pairing;                   /* DN_PAIR_BY_NAME or DN_PAIR_BY_FLAG (which matters to a paired store only) */
+    uint32_t exclude_flags;             /* up to 0xffff */
+    uint32_t require_flags;             /* up to 0xffff */
+    int32_t  min_mapq;                  /* 0 .. 255 */
+} dn_bam_rows_options;
+int  dn_bam_rows_create_with(int device, int32_t tid, int32_t unique_alignment, int32_t paired, const dn_bam_rows_options *opt,
+                             dn_bam_rows *out);
+int  dn_bam_rows_dropped(dn_bam_rows h, int64_t *by_flags, int64_t *by_mapq, int64_t *not_candidate);
+int  dn_bam_rows_fetch_mates(dn_bam_rows h, uint16_t *flag, uint8_t *mapq, int32_t *next_pos);
+int  dn_bam_mate_host(int64_t n, const int64_t *name_beg, const int32_t *name_len, const uint8_t *names, const int64_t *pos,
+                      const int32_t *next_pos, const uint16_t *flag, int32_t *order, int32_t *pair_id, int64_t *n_pair_ids);
 int  dn_bam_frame(const uint8_t *buf, int64_t n_bytes, int32_t tid, int32_t *last_pos, int64_t *rec_off, int64_t cap,
                   int64_t *n_rec, int64_t *consumed);
 int  dn_bam_rows_create(int device, int32_t tid, int32_t unique_alignment, int32_t paired, dn_bam_rows *out);

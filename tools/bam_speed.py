@@ -1,7 +1,9 @@
 """
 Speed of the native BAM path (degnorm_amd.bam.NativeBamReadsProcessor) on the synthetic scale chromosome of the GPU tests
 (tests/_reads_fixtures.scale_case: 20 Mb, 2 000 genes, 2 M single-end reads of the forms aM / aMnNbM), written as a sorted,
-indexed BAM, and on a paired variant (the same reads named <i // 2>.1 / .2, mates next to each other):
+indexed BAM, and on a paired variant (the same reads named <i // 2>.1 / .2, mates next to each other; with --pairing flag
+both mates are named <i // 2> and carry FLAG 0x41 / 0x81 plus strand bits and the mate's position as PNEXT, as an aligner
+writes them, and the reader pairs them by FLAG):
 
   inflate_ms        BGZF inflate of the chromosome's blocks: zlib on the host in n_jobs threads (--inflate host), or the
                     library's DEFLATE kernel with the copy of the compressed blocks in and of the window back (--inflate device)
@@ -21,6 +23,7 @@ indexed BAM, and on a paired variant (the same reads named <i // 2>.1 / .2, mate
 
     python tools/bam_speed.py [--reads 2000000] [--jobs 4] [--reps 3] [--dir DIR] [--inflate host|device] [--level 1]
                                [--frame host|device] [--segment-bytes N] [--cases se,pe] [--pair host|device]
+                               [--pairing name|flag]
 
 --level is the deflate level of the written files (the fixture writer's level 1 on random sequence bytes is nearly
 literal-only; real files are level 6 and full of matches).  Files found in --dir from an earlier run with the same
@@ -43,17 +46,22 @@ import numpy as np                                   # noqa: E402
 import pandas as pd                                  # noqa: E402
 
 import _bam_fixtures as bf                           # noqa: E402
+import _flag_cases as fc                             # noqa: E402
 import _reads_fixtures as rf                         # noqa: E402
 from degnorm_amd import bam                          # noqa: E402
 from degnorm_amd import reads as dr                  # noqa: E402
 
 
-def _best(path, chrom, ov, gene_df, exon_df, out, jobs, reps, inflate, frame='host', segment_bytes=None, verify=False, pair='host'):
+def _best(path, chrom, ov, gene_df, exon_df, out, jobs, reps, inflate, frame='host', segment_bytes=None, verify=False, pair='host',
+          pairing='name'):
     best, rows = None, []
     shutil.rmtree(out, ignore_errors=True)            # of an earlier run in the same --dir: files that exist are not written again
     for k in range(reps + 1):                        # the first run loads the library and warms the device up
         proc = bam.NativeBamReadsProcessor(path, path + '.bai', output_dir=os.path.join(out, str(k)), n_jobs=jobs, verbose=False,
-                                           inflate=inflate, frame=frame, frame_segment_bytes=segment_bytes, verify=verify, pair=pair)
+                                           inflate=inflate, frame=frame, frame_segment_bytes=segment_bytes, verify=verify, pair=pair,
+                                           pairing=pairing)
+        if k == 0 and path.rsplit(os.sep, 1)[-1].startswith('pe'):
+            assert proc.paired, 'the paired file was taken for single-end'
         os.makedirs(proc.save_dir, exist_ok=True)
         proc.timing = {}
         t0 = time.perf_counter()
@@ -90,6 +98,8 @@ def main():
     ap.add_argument('--frame', choices=['host', 'device'], default='host')
     ap.add_argument('--segment-bytes', type=int, default=None, help='segment size of --frame device (default: the library\'s)')
     ap.add_argument('--pair', choices=['host', 'device'], default='host', help='where the mates of the paired case are paired')
+    ap.add_argument('--pairing', choices=['name', 'flag'], default='name',
+                    help='flag: the paired case is written with equal names, FLAG bits and PNEXT, and paired by FLAG (on the device)')
     ap.add_argument('--cases', default='se,pe', help='se, pe or se,pe')
     ap.add_argument('--verify', action='store_true', help='check every BGZF block against the CRC32 of its trailer')
     a = ap.parse_args()
@@ -98,12 +108,19 @@ def main():
     try:
         se = pd.DataFrame({'ref': 0, 'pos': reads.pos.values, 'qname': reads.qname.astype(str).values, 'cigar': reads.cigar.values})
         pe = se.assign(qname=['{0}.{1}'.format(i // 2, 1 + i % 2) for i in range(len(se))], next_ref=0)
+        if a.pairing == 'flag':
+            n, strand = len(se), np.random.default_rng(1).choice([0x0, 0x10, 0x20], len(se))
+            mate = np.arange(n) ^ 1
+            mate[mate >= n] = n - 1                  # an odd count: the last read names itself, and is its key's only row
+            pe = se.assign(qname=[str(i // 2) for i in range(n)], next_ref=0, flag=0x1 | np.where(np.arange(n) % 2 == 0, 0x40, 0x80) | strand,
+                           next_pos=se.pos.values[mate], mapq=60)
         t0 = time.perf_counter()
         cases = [c for c in ('se', 'pe') if c in a.cases.split(',')]
-        files = {name: os.path.join(work, '{0}_{1}_l{2}.bam'.format(name, a.reads, a.level)) for name in cases}
+        files = {name: os.path.join(work, '{0}_{1}_l{2}.bam'.format(name + ('_flag' if name == 'pe' and a.pairing == 'flag' else ''), a.reads, a.level))
+                 for name in cases}
         for name, df in (('se', se), ('pe', pe)):
             if name in files and not (os.path.isfile(files[name]) and os.path.isfile(files[name] + '.bai')):
-                bf.write_bam(files[name], [('chrS', chrom_len)], df, level=a.level)
+                (fc.write_bam if 'next_pos' in df else bf.write_bam)(files[name], [('chrS', chrom_len)], df, level=a.level)
         write_s = time.perf_counter() - t0
         inflated = {name: int(bam.bgzf_blocks(files[name])[2].sum()) for name in files}
         in_mem = None
@@ -112,14 +129,21 @@ def main():
             dr.chromosome_coverage_read_counts_df(reads, chrom_len, ov, gene_df, exon_df, False)
             dt = time.perf_counter() - t0
             in_mem = dt if in_mem is None else min(in_mem, dt)
-        out = {'tool': 'bam_speed', 'reads': a.reads, 'jobs': a.jobs, 'inflate': a.inflate, 'frame': a.frame, 'pair': a.pair, 'level': a.level,
+        out = {'tool': 'bam_speed', 'reads': a.reads, 'jobs': a.jobs, 'inflate': a.inflate, 'frame': a.frame, 'pair': a.pair, 'pairing': a.pairing, 'level': a.level,
                'bam_mb': round(os.path.getsize(files[cases[0]]) / 2 ** 20, 1), 'inflated_mb': round(inflated[cases[0]] / 2 ** 20, 1),
                'write_s': round(write_s, 1)}
         if a.verify:
             out['verify'] = True
+        if a.pairing == 'flag' and 'pe' in files:
+            # what the default (pairing by name) makes of this file: it takes it for single-end, so every pair whose two mates
+            # it counts is counted as two reads.  On the host: the in-memory path on the same rows, single-end against paired.
+            both = pe.assign(qname_unpaired=pe.qname)
+            as_reads = dr.chromosome_coverage_read_counts_df(both, chrom_len, ov, gene_df, exon_df, False)[2]
+            as_pairs = dr.chromosome_coverage_read_counts_df(both.sort_values('qname_unpaired', kind='stable'), chrom_len, ov, gene_df, exon_df, True)[2]
+            out['default_counts_as_reads'], out['pairs_counted'] = int(sum(as_reads.values())), int(sum(as_pairs.values()))
         for name in cases:
             row = _best(files[name], 'chrS', ov, gene_df, exon_df, os.path.join(work, 'out_{0}_{1}_{2}_{3}'.format(name, a.inflate, a.frame, a.pair)),
-                        a.jobs, a.reps, a.inflate, a.frame, a.segment_bytes, a.verify, a.pair)
+                        a.jobs, a.reps, a.inflate, a.frame, a.segment_bytes, a.verify, a.pair, a.pairing if name == 'pe' else 'name')
             if row['inflate_device_ms'] > 0:
                 row['inflate_gbps'] = round(inflated[name] / (row['inflate_device_ms'] * 1e-3) / 1e9, 2)
             row['reads_per_s'] = round(a.reads / (row['e2e_ms'] * 1e-3))
