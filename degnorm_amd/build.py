@@ -6,7 +6,8 @@ In-tree build of libdegnorm_amd.so (HIP kernels + C ABI) for gfx950 with hipcc.
 One translation unit per sample count p (dn_inst.hip -DDN_P=p), the run-time-p family (dn_generic.hip, compiled four
 times: 256- and 64-thread builds on float32 counts, a 256-thread build on float64 input, the wide-cohort build for 65 to 256
 samples), the coverage-assembly,
-reads-processing, mate-pairing, BGZF-inflate, BGZF-deflate, record-framing, BAM-index, BAM-sort, GTF-scan, SAM-encode, GFF3-scan, coverage-text and gzip-inflate units plus the C-ABI unit; objects are compiled
+reads-processing, mate-pairing, BGZF-inflate, BGZF-deflate, record-framing, BAM-index, BAM-sort, GTF-scan, SAM-encode, GFF3-scan, coverage-text,
+gzip-inflate and outer-update (dn_outer.hip: the kernels the C-ABI unit launches directly) units plus the C-ABI unit; objects are compiled
 in parallel and linked into degnorm_amd/libdegnorm_amd.so.  hipcc cross-compiles without a GPU.  The host-side units (HOST_UNITS
 and the C-ABI unit) are rebuilt when include/degnorm_amd.h or any header under csrc/ changes (dn_host.hpp, dn_bam_record.hpp --
 what a BAM record is -- and the units' own headers).
@@ -63,7 +64,8 @@ HOST_UNITS = ('dn_assemble',    # per-gene coverage assembly
               'dn_sam',         # SAM alignment lines -> BAM records (bam.sam_records, bam.sam_to_bam)
               'dn_gff3',        # GFF3 bytes -> exon table, exon parents resolved to genes (Gff3AnnotationLoader, loaders.py)
               'dn_text',        # coverage matrices -> the '%.5f' text of their files (get_coverage_data, data_access.py)
-              'dn_gz')          # gzip members -> inflated bytes, chunk-parallel (gz.gunzip, gz.open_text, gz.py)
+              'dn_gz',          # gzip members -> inflated bytes, chunk-parallel (gz.gunzip, gz.open_text, gz.py)
+              'dn_outer')       # the kernels the C-ABI unit launches directly: outer update, row maxima, gathers (dn_outer.hpp)
 FLAGS = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC', '-fno-fast-math', '-ffp-contract=on',
          '-Wall', '-Wno-unused-function']
 

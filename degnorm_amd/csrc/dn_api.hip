@@ -1,7 +1,9 @@
 // dn_api.hip -- C ABI (include/degnorm_amd.h) over the kernels of dn_kernels.hpp: device handle, host packer,
-// resident buffers, launches.  Host side only; the kernels are instantiated per sample count in dn_inst.hip.
+// resident buffers, launches.  Host side only; the kernels are instantiated per sample count in dn_inst.hip, and the ones this
+// unit launches itself (outer update, row maxima, gathers) are in dn_outer.hip behind the launchers of dn_outer.hpp.
 #include "dn_kernels.hpp"
 #include "dn_host.hpp"
+#include "dn_outer.hpp"
 #include "../../include/degnorm_amd.h"
 
 #include <dlfcn.h>
@@ -100,385 +102,6 @@ const KernelSet *kernel_set_for(int p)
     }
 }
 }  // namespace dn
-
-// Row maxima of the raw coverage, once per upload: max_j fl(x_ij / s_i) = fl((max_j x_ij) / s_i) for s_i > 0, so the
-// 0.1 * max(F) threshold of get_high_coverage_idx (nmf.py:66-76) needs these p numbers per gene instead of a scan of
-// the whole scaled matrix in every outer iteration (SURVEY 8(d), config-4 regime note).  One workgroup per gene, one wave per
-// row at a time.  Round 4: a pure max-reduce has to stream -- a wave keeps FOUR 16-byte loads per lane in flight (4 KiB per wave
-// and trip; rows are only 4-byte aligned, so a scalar head brings the wave to a 16-byte boundary first) instead of one dword
-// (round 3: 2.77 TB/s on config 4's 27.5 GB).
-__device__ __forceinline__ void row_max_acc(float v, float &m, bool &ok)
-{
-    m = fmaxf(m, v);
-    ok = ok && (v >= 0.0f) && (v <= 65535.0f) && (v == truncf(v));
-}
-
-__global__ __launch_bounds__(256) void k_row_max(const float *__restrict__ cov, const int64_t *__restrict__ goff,
-                                                 const int32_t *__restrict__ glen, float *__restrict__ rowmax,
-                                                 int32_t *__restrict__ x16, int n, int p)
-{
-    __shared__ int ok_w[4];
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (int g = blockIdx.x; g < n; g += gridDim.x) {
-        const int L = glen[g];
-        bool ok = true;                                    // every value a whole number in [0, 65535]: fits 16 bits exactly
-        for (int i = w; i < p; i += 4) {
-            const float *row = cov + goff[g] + (size_t) i * L;
-            float m = row[0];
-            const int head = (int) (((16u - (unsigned) ((size_t) row & 15u)) & 15u) >> 2);     // floats up to the next 16-byte boundary
-            const int h = head < L ? head : L;
-            if (lane < h) row_max_acc(row[lane], m, ok);
-            const float4 *q = reinterpret_cast<const float4 *>(row + h);
-            const int n4 = (L - h) >> 2;
-            int j = lane;
-            typedef float vf4 __attribute__((ext_vector_type(4)));
-            const vf4 *qv = reinterpret_cast<const vf4 *>(q);
-            for (; j + 448 < n4; j += 512) {               // eight independent 16-byte loads per lane in flight, read once: non-temporal
-                vf4 v[8];
-#pragma unroll
-                for (int k = 0; k < 8; k++) v[k] = __builtin_nontemporal_load(qv + j + 64 * k);
-#pragma unroll
-                for (int k = 0; k < 8; k++) { row_max_acc(v[k].x, m, ok); row_max_acc(v[k].y, m, ok); row_max_acc(v[k].z, m, ok); row_max_acc(v[k].w, m, ok); }
-            }
-            for (; j + 192 < n4; j += 256) {               // four
-                const float4 a = q[j], b = q[j + 64], c = q[j + 128], d = q[j + 192];
-                row_max_acc(a.x, m, ok); row_max_acc(a.y, m, ok); row_max_acc(a.z, m, ok); row_max_acc(a.w, m, ok);
-                row_max_acc(b.x, m, ok); row_max_acc(b.y, m, ok); row_max_acc(b.z, m, ok); row_max_acc(b.w, m, ok);
-                row_max_acc(c.x, m, ok); row_max_acc(c.y, m, ok); row_max_acc(c.z, m, ok); row_max_acc(c.w, m, ok);
-                row_max_acc(d.x, m, ok); row_max_acc(d.y, m, ok); row_max_acc(d.z, m, ok); row_max_acc(d.w, m, ok);
-            }
-            for (; j < n4; j += 64) {
-                const float4 a = q[j];
-                row_max_acc(a.x, m, ok); row_max_acc(a.y, m, ok); row_max_acc(a.z, m, ok); row_max_acc(a.w, m, ok);
-            }
-            const int t0 = h + 4 * n4;                     // scalar tail (< 4 floats)
-            if (t0 + lane < L) row_max_acc(row[t0 + lane], m, ok);
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-            if (lane == 0) rowmax[(size_t) g * p + i] = m;
-        }
-        const int all_ok = __all(ok);
-        if (lane == 0) ok_w[w] = all_ok;
-        __syncthreads();
-        if (threadIdx.x == 0) x16[g] = (ok_w[0] && ok_w[1] && ok_w[2] && ok_w[3]) ? 1 : 0;
-        __syncthreads();
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// The outer DegNorm update on the device (nmf.py:398-399, :148-158, :575-590; nmf_mpi.py:821-838).  Per outer iteration
-// the host needs 3p + 4 numbers, not the n x p DI matrix: one wave per gene, lane i = sample i.
-//   k_outer_partials  clip rho to [0, 0.9]; untouched = (max_i rho == 0); per-sample partial sums
-//                     A = sum_touched x_w / (1 - rho), B = sum_untouched x_w, W = sum x_w; counts of untouched / failed /
-//                     unconverged genes.  Block partials, then k_outer_reduce adds them in block order (deterministic).
-//   k_outer_apply     rho[untouched] = avg_di; x_adj = x_w / (1 - rho); x_w /= norm; ran_baseline_selection[:, iter].
-// ---------------------------------------------------------------------------------------------------
-constexpr int OUT_BLOCKS = 512;
-constexpr int OUT_STRIDE = 3 * 64 + 4;          // per block: A[64] B[64] W[64] n_untouched n_failed n_noconv n_flagged
-
-__device__ __forceinline__ double wave_max_d(double v)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) { const double t = __shfl_xor(v, o); v = t > v ? t : v; }
-    return v;
-}
-
-__global__ __launch_bounds__(256) void k_outer_partials(const double *__restrict__ rho_raw, double *__restrict__ rho_c,
-                                                        const double *__restrict__ xw, const int32_t *__restrict__ trace,
-                                                        const int32_t *__restrict__ flags, double *__restrict__ part, int n, int p)
-{
-    __shared__ double sm[4][3][64];
-    __shared__ double cnt[4][4];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int nw = gridDim.x * 4;
-    double a = 0.0, b = 0.0, ws = 0.0, nu = 0.0, nf = 0.0, nc = 0.0, nr = 0.0;
-    for (int g = blockIdx.x * 4 + w; g < n; g += nw) {
-        double r = 0.0, x = 0.0;
-        if (lane < p) {
-            r = rho_raw[(size_t) g * p + lane];
-            r = r > 0.9 ? 0.9 : r;                                        // nmf.py:398
-            r = r < 0.0 ? 0.0 : r;                                        // nmf.py:399
-            rho_c[(size_t) g * p + lane] = r;
-            x = xw[(size_t) g * p + lane];
-        }
-        const bool untouched = wave_max_d(r) == 0.0;                      // nmf.py:155
-        a += untouched ? 0.0 : x / (1.0 - r);                             // nmf.py:575
-        b += untouched ? x : 0.0;
-        ws += x;
-        if (lane == 0) {
-            const int st = trace[(size_t) g * dn::TRACE_LEN + 6];
-            nu += untouched ? 1.0 : 0.0; nf += st != 0 ? 1.0 : 0.0; nc += st == dn::ST_NO_CONVERGENCE ? 1.0 : 0.0;
-            nr += flags[g] != 0 ? 1.0 : 0.0;                              // ran_baseline_selection[:, i].sum() (nmf.py:571)
-        }
-    }
-    sm[w][0][lane] = a; sm[w][1][lane] = b; sm[w][2][lane] = ws;
-    if (lane == 0) { cnt[w][0] = nu; cnt[w][1] = nf; cnt[w][2] = nc; cnt[w][3] = nr; }
-    __syncthreads();
-    if (threadIdx.x < 192) {
-        const int k = threadIdx.x >> 6, i = threadIdx.x & 63;
-        part[(size_t) blockIdx.x * OUT_STRIDE + 64 * k + i] = ((sm[0][k][i] + sm[1][k][i]) + sm[2][k][i]) + sm[3][k][i];
-    } else if (threadIdx.x < 196) {
-        const int k = threadIdx.x - 192;
-        part[(size_t) blockIdx.x * OUT_STRIDE + 192 + k] = ((cnt[0][k] + cnt[1][k]) + cnt[2][k]) + cnt[3][k];
-    }
-}
-
-// The initial normalisation on the device (nmf.py:524-531): rho0 = 1 - cov_sums / (est_sums + 1) per gene, `low` =
-// (max_i rho0 < 0.1), per-sample sums of the read counts over the low genes and over all genes, the number of low genes and
-// of genes whose initial SVD failed.  Same block-partial layout as k_outer_partials (A = low sums, B = all sums, W unused).
-__global__ __launch_bounds__(256) void k_init_partials(const double *__restrict__ est, const double *__restrict__ cov,
-                                                       const int32_t *__restrict__ status, const double *__restrict__ x,
-                                                       double *__restrict__ part, int n, int p)
-{
-    __shared__ double sm[4][3][64];
-    __shared__ double cnt[4][4];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int nw = gridDim.x * 4;
-    double a = 0.0, b = 0.0, nl = 0.0, nb = 0.0;
-    for (int g = blockIdx.x * 4 + w; g < n; g += nw) {
-        double r = -INFINITY, xv = 0.0;
-        if (lane < p) {
-            r = 1.0 - cov[(size_t) g * p + lane] / (est[(size_t) g * p + lane] + 1.0);       // nmf.py:526
-            xv = x[(size_t) g * p + lane];
-        }
-        const bool low = wave_max_d(r) < 0.1;                             // nmf.py:529
-        a += low ? xv : 0.0;
-        b += xv;
-        if (lane == 0) { nl += low ? 1.0 : 0.0; nb += status[g] != 0 ? 1.0 : 0.0; }
-    }
-    sm[w][0][lane] = a; sm[w][1][lane] = b; sm[w][2][lane] = 0.0;
-    if (lane == 0) { cnt[w][0] = nl; cnt[w][1] = nb; cnt[w][2] = 0.0; cnt[w][3] = 0.0; }
-    __syncthreads();
-    if (threadIdx.x < 192) {
-        const int k = threadIdx.x >> 6, i = threadIdx.x & 63;
-        part[(size_t) blockIdx.x * OUT_STRIDE + 64 * k + i] = ((sm[0][k][i] + sm[1][k][i]) + sm[2][k][i]) + sm[3][k][i];
-    } else if (threadIdx.x < 196) {
-        const int k = threadIdx.x - 192;
-        part[(size_t) blockIdx.x * OUT_STRIDE + 192 + k] = ((cnt[0][k] + cnt[1][k]) + cnt[2][k]) + cnt[3][k];
-    }
-}
-
-// x_weighted = x / norm (nmf.py:533)
-__global__ __launch_bounds__(256) void k_scale_reads(const double *__restrict__ x, const double *__restrict__ norm,
-                                                     double *__restrict__ xw, long long np, int p)
-{
-    for (long long i = (long long) blockIdx.x * 256 + threadIdx.x; i < np; i += (long long) gridDim.x * 256)
-        xw[i] = x[i] / norm[i % p];
-}
-
-__global__ __launch_bounds__(256) void k_outer_reduce(const double *__restrict__ part, double *__restrict__ out, int nblocks, int p)
-{
-    const int t = threadIdx.x;
-    if (t >= 196) return;
-    // eight independent running sums (block b goes to sum b % 8: eight loads in flight instead of a chain of nblocks dependent ones
-    // -- 117 us for 512 blocks in round 3), combined in one fixed order: the result does not depend on timing
-    double a[8] = {0., 0., 0., 0., 0., 0., 0., 0.};
-    int b = 0;
-    for (; b + 8 <= nblocks; b += 8) {
-#pragma unroll
-        for (int k = 0; k < 8; k++) a[k] += part[(size_t) (b + k) * OUT_STRIDE + t];
-    }
-    for (int k = 0; b < nblocks; b++, k++) a[k] += part[(size_t) b * OUT_STRIDE + t];
-    const double s = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
-    const int k = t >> 6, i = t & 63;
-    if (t < 192) { if (i < p) out[k * p + i] = s; }
-    else out[3 * p + (t - 192)] = s;
-}
-
-__global__ __launch_bounds__(256) void k_outer_apply(double *__restrict__ rho_c, double *__restrict__ xw, double *__restrict__ xadj,
-                                                     const int32_t *__restrict__ flags, uint8_t *__restrict__ ran,
-                                                     const double *__restrict__ avg_di, const double *__restrict__ norm,
-                                                     int have_avg, int n, int p, int iter, int n_iter)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int nw = gridDim.x * 4;
-    for (int g = blockIdx.x * 4 + w; g < n; g += nw) {
-        double r = lane < p ? rho_c[(size_t) g * p + lane] : 0.0;
-        const bool untouched = wave_max_d(r) == 0.0;
-        if (lane < p) {
-            if (untouched && have_avg) r = avg_di[lane];                  // correct_di_scores, nmf.py:157
-            const double x = xw[(size_t) g * p + lane];
-            rho_c[(size_t) g * p + lane] = r;
-            xadj[(size_t) g * p + lane] = x / (1.0 - r);                  // nmf.py:581
-            xw[(size_t) g * p + lane] = x / norm[lane];                   // nmf.py:587
-        }
-        if (lane == 0 && iter < n_iter) ran[(size_t) g * n_iter + iter] = flags[g] != 0;      // nmf.py:403
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// The outer update for wide cohorts (65 <= p <= 256): the same kernels with up to four samples per lane -- one wave per gene,
-// sample 64 r + lane in slot r of the lane -- and block partials of stride 3 * 256 + 4.  The waves of a block, the blocks and the
-// eight running sums of the reduction are combined in the same fixed orders as above: nothing depends on timing.  Cohorts of at
-// most 64 samples keep the kernels above (their summation order is part of their results).
-// ---------------------------------------------------------------------------------------------------
-constexpr int OUT_WP = dn::P_WIDE_MAX;             // 256
-constexpr int OUT_WR = OUT_WP / 64;                // samples per lane
-constexpr int OUT_STRIDE_W = 3 * OUT_WP + 4;
-
-__device__ __forceinline__ void outer_store_partials_w(double (&sm)[4][3][OUT_WP], double (&cnt)[4][4], double *__restrict__ part)
-{
-    for (int t = threadIdx.x; t < 3 * OUT_WP; t += 256) {
-        const int k = t / OUT_WP, i = t - k * OUT_WP;
-        part[(size_t) blockIdx.x * OUT_STRIDE_W + t] = ((sm[0][k][i] + sm[1][k][i]) + sm[2][k][i]) + sm[3][k][i];
-    }
-    if (threadIdx.x < 4) {
-        const int k = threadIdx.x;
-        part[(size_t) blockIdx.x * OUT_STRIDE_W + 3 * OUT_WP + k] = ((cnt[0][k] + cnt[1][k]) + cnt[2][k]) + cnt[3][k];
-    }
-}
-
-__global__ __launch_bounds__(256) void k_outer_partials_w(const double *__restrict__ rho_raw, double *__restrict__ rho_c,
-                                                          const double *__restrict__ xw, const int32_t *__restrict__ trace,
-                                                          const int32_t *__restrict__ flags, double *__restrict__ part, int n, int p)
-{
-    __shared__ double sm[4][3][OUT_WP];
-    __shared__ double cnt[4][4];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int nw = gridDim.x * 4;
-    double a[OUT_WR], b[OUT_WR], ws[OUT_WR], nu = 0.0, nf = 0.0, nc = 0.0, nr = 0.0;
-#pragma unroll
-    for (int q = 0; q < OUT_WR; q++) { a[q] = 0.0; b[q] = 0.0; ws[q] = 0.0; }
-    for (int g = blockIdx.x * 4 + w; g < n; g += nw) {
-        double r[OUT_WR], x[OUT_WR], rmax = 0.0;
-#pragma unroll
-        for (int q = 0; q < OUT_WR; q++) {
-            const int i = 64 * q + lane;
-            r[q] = 0.0; x[q] = 0.0;
-            if (i < p) {
-                double v = rho_raw[(size_t) g * p + i];
-                v = v > 0.9 ? 0.9 : v;                                    // nmf.py:398
-                v = v < 0.0 ? 0.0 : v;                                    // nmf.py:399
-                rho_c[(size_t) g * p + i] = v;
-                r[q] = v;
-                x[q] = xw[(size_t) g * p + i];
-            }
-            rmax = r[q] > rmax ? r[q] : rmax;
-        }
-        const bool untouched = wave_max_d(rmax) == 0.0;                   // nmf.py:155
-#pragma unroll
-        for (int q = 0; q < OUT_WR; q++) {
-            a[q] += untouched ? 0.0 : x[q] / (1.0 - r[q]);                // nmf.py:575
-            b[q] += untouched ? x[q] : 0.0;
-            ws[q] += x[q];
-        }
-        if (lane == 0) {
-            const int st = trace[(size_t) g * dn::TRACE_LEN + 6];
-            nu += untouched ? 1.0 : 0.0; nf += st != 0 ? 1.0 : 0.0; nc += st == dn::ST_NO_CONVERGENCE ? 1.0 : 0.0;
-            nr += flags[g] != 0 ? 1.0 : 0.0;
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < OUT_WR; q++) { sm[w][0][64 * q + lane] = a[q]; sm[w][1][64 * q + lane] = b[q]; sm[w][2][64 * q + lane] = ws[q]; }
-    if (lane == 0) { cnt[w][0] = nu; cnt[w][1] = nf; cnt[w][2] = nc; cnt[w][3] = nr; }
-    __syncthreads();
-    outer_store_partials_w(sm, cnt, part);
-}
-
-__global__ __launch_bounds__(256) void k_init_partials_w(const double *__restrict__ est, const double *__restrict__ cov,
-                                                         const int32_t *__restrict__ status, const double *__restrict__ x,
-                                                         double *__restrict__ part, int n, int p)
-{
-    __shared__ double sm[4][3][OUT_WP];
-    __shared__ double cnt[4][4];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int nw = gridDim.x * 4;
-    double a[OUT_WR], b[OUT_WR], nl = 0.0, nb = 0.0;
-#pragma unroll
-    for (int q = 0; q < OUT_WR; q++) { a[q] = 0.0; b[q] = 0.0; }
-    for (int g = blockIdx.x * 4 + w; g < n; g += nw) {
-        double xv[OUT_WR], rmax = -INFINITY;
-#pragma unroll
-        for (int q = 0; q < OUT_WR; q++) {
-            const int i = 64 * q + lane;
-            xv[q] = 0.0;
-            if (i < p) {
-                const double r = 1.0 - cov[(size_t) g * p + i] / (est[(size_t) g * p + i] + 1.0);       // nmf.py:526
-                rmax = r > rmax ? r : rmax;
-                xv[q] = x[(size_t) g * p + i];
-            }
-        }
-        const bool low = wave_max_d(rmax) < 0.1;                          // nmf.py:529
-#pragma unroll
-        for (int q = 0; q < OUT_WR; q++) { a[q] += low ? xv[q] : 0.0; b[q] += xv[q]; }
-        if (lane == 0) { nl += low ? 1.0 : 0.0; nb += status[g] != 0 ? 1.0 : 0.0; }
-    }
-#pragma unroll
-    for (int q = 0; q < OUT_WR; q++) { sm[w][0][64 * q + lane] = a[q]; sm[w][1][64 * q + lane] = b[q]; sm[w][2][64 * q + lane] = 0.0; }
-    if (lane == 0) { cnt[w][0] = nl; cnt[w][1] = nb; cnt[w][2] = 0.0; cnt[w][3] = 0.0; }
-    __syncthreads();
-    outer_store_partials_w(sm, cnt, part);
-}
-
-// one thread per entry of the block partials (grid of ceil(OUT_STRIDE_W / 256) blocks): the reduction of k_outer_reduce
-__global__ __launch_bounds__(256) void k_outer_reduce_w(const double *__restrict__ part, double *__restrict__ out, int nblocks, int p)
-{
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= OUT_STRIDE_W) return;
-    double a[8] = {0., 0., 0., 0., 0., 0., 0., 0.};
-    int b = 0;
-    for (; b + 8 <= nblocks; b += 8) {
-#pragma unroll
-        for (int k = 0; k < 8; k++) a[k] += part[(size_t) (b + k) * OUT_STRIDE_W + t];
-    }
-    for (int k = 0; b < nblocks; b++, k++) a[k] += part[(size_t) b * OUT_STRIDE_W + t];
-    const double s = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
-    if (t < 3 * OUT_WP) { const int k = t / OUT_WP, i = t - k * OUT_WP; if (i < p) out[k * p + i] = s; }
-    else out[3 * p + (t - 3 * OUT_WP)] = s;
-}
-
-__global__ __launch_bounds__(256) void k_outer_apply_w(double *__restrict__ rho_c, double *__restrict__ xw, double *__restrict__ xadj,
-                                                       const int32_t *__restrict__ flags, uint8_t *__restrict__ ran,
-                                                       const double *__restrict__ avg_di, const double *__restrict__ norm,
-                                                       int have_avg, int n, int p, int iter, int n_iter)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int nw = gridDim.x * 4;
-    for (int g = blockIdx.x * 4 + w; g < n; g += nw) {
-        double r[OUT_WR], rmax = 0.0;
-#pragma unroll
-        for (int q = 0; q < OUT_WR; q++) {
-            const int i = 64 * q + lane;
-            r[q] = i < p ? rho_c[(size_t) g * p + i] : 0.0;
-            rmax = r[q] > rmax ? r[q] : rmax;
-        }
-        const bool untouched = wave_max_d(rmax) == 0.0;
-#pragma unroll
-        for (int q = 0; q < OUT_WR; q++) {
-            const int i = 64 * q + lane;
-            if (i < p) {
-                double rv = r[q];
-                if (untouched && have_avg) rv = avg_di[i];                // correct_di_scores, nmf.py:157
-                const double x = xw[(size_t) g * p + i];
-                rho_c[(size_t) g * p + i] = rv;
-                xadj[(size_t) g * p + i] = x / (1.0 - rv);                // nmf.py:581
-                xw[(size_t) g * p + i] = x / norm[i];                     // nmf.py:587
-            }
-        }
-        if (lane == 0 && iter < n_iter) ran[(size_t) g * n_iter + iter] = flags[g] != 0;      // nmf.py:403
-    }
-}
-
-__global__ __launch_bounds__(256) void k_gather_rows(const double *__restrict__ rho_raw, const int32_t *__restrict__ flags,
-                                                     const int64_t *__restrict__ rows, double *__restrict__ out_rho,
-                                                     int32_t *__restrict__ out_flags, int n_rows, int p)
-{
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n_rows * p) return;
-    const int k = t / p, i = t - k * p;
-    out_rho[t] = rho_raw[(size_t) rows[k] * p + i];
-    if (i == 0) out_flags[k] = flags[rows[k]];
-}
-
-// the first `cols` counters of every gene, packed: what comes back to the host per iteration when the caller does not want the
-// whole trace (dn_set_trace_columns)
-__global__ __launch_bounds__(256) void k_trace_head(const int32_t *__restrict__ trace, int32_t *__restrict__ head, long long n_cols_total, int cols)
-{
-    for (long long t = (long long) blockIdx.x * 256 + threadIdx.x; t < n_cols_total; t += (long long) gridDim.x * 256) {
-        const long long g = t / cols;
-        head[t] = trace[g * dn::TRACE_LEN + (t - g * cols)];
-    }
-}
 
 // the library's one error text (dn_host.hpp); every dn_*_last_error returns it
 static thread_local std::string g_err;
@@ -1034,8 +657,7 @@ static int finish_upload(dn_handle h, const CoverageSource &src)
         DN_TRY(hipMemcpyAsync(h->data.d_tile_gene, tg.data(), sizeof(int32_t) * tg.size(), hipMemcpyHostToDevice, h->stream[0]));
         DN_TRY(hipMemcpyAsync(h->data.d_tile_col, tc.data(), sizeof(int32_t) * tc.size(), hipMemcpyHostToDevice, h->stream[0]));
         DN_TRY(hipEventRecord(h->ev_i0, h->stream[0]));
-        hipLaunchKernelGGL(k_row_max, dim3((unsigned) std::min<int64_t>(n, (int64_t) h->n_cus * 8)), dim3(256), 0, h->stream[0],
-                           h->data.d_cov, h->data.d_goff, h->data.d_glen, h->data.d_rowmax, h->data.d_x16, (int) n, (int) p);
+        dn::outer::row_max(h->stream[0], h->data.d_cov, h->data.d_goff, h->data.d_glen, h->data.d_rowmax, h->data.d_x16, n, (int) p, h->n_cus);
         DN_TRY(hipGetLastError());
         DN_TRY(hipEventRecord(h->ev_i1, h->stream[0]));
         DN_TRY(hipStreamSynchronize(h->stream[0]));
@@ -1371,8 +993,7 @@ int dn_baseline_iteration(dn_handle h, const double *scale, const dn_params *prm
             DN_TRY(hipMemcpyAsync(h->data.host_trace, h->data.d_trace, sizeof(int32_t) * trace_ints, hipMemcpyDeviceToHost, h->stream[0]));
         else {
             if (!h->data.d_trace_head) DN_TRY(h->data.d_trace_head.alloc(sizeof(int32_t) * (size_t) h->n * dn::TRACE_LEN));
-            hipLaunchKernelGGL(k_trace_head, dim3((unsigned) std::min<size_t>(1024, (trace_ints + 255) / 256)), dim3(256), 0, h->stream[0],
-                               h->data.d_trace, h->data.d_trace_head, (long long) trace_ints, (int) tcols);
+            dn::outer::trace_head(h->stream[0], h->data.d_trace, h->data.d_trace_head, trace_ints, (int) tcols);
             DN_TRY(hipGetLastError());
             DN_TRY(hipMemcpyAsync(h->data.host_trace, h->data.d_trace_head, sizeof(int32_t) * trace_ints, hipMemcpyDeviceToHost, h->stream[0]));
         }
@@ -1406,7 +1027,7 @@ static int outer_alloc(dn_handle h, int32_t degnorm_iter)
         DN_TRY(h->data.d_xadj.alloc(sizeof(double) * np));
     }
     if (!h->data.d_part) {
-        DN_TRY(h->data.d_part.alloc(sizeof(double) * (size_t) OUT_BLOCKS * OUT_STRIDE_W));     // sized for the widest cohort
+        DN_TRY(h->data.d_part.alloc(sizeof(double) * dn::outer::PART_DOUBLES));     // sized for the widest cohort
         DN_TRY(h->data.d_pvec.alloc(sizeof(double) * (PVEC_SUMS + 2 * dn::P_WIDE_MAX)));
     }
     if (degnorm_iter > 0 && h->data.n_iter != degnorm_iter) {
@@ -1420,25 +1041,9 @@ static int outer_alloc(dn_handle h, int32_t degnorm_iter)
 // outer update (k_outer_partials) over the handle's genes, block by block, then added in block order into d_pvec[0 .. 3p + 4)
 static int queue_partials(dn_handle h, bool initial)
 {
-    const int blocks = (int) std::min<int64_t>(OUT_BLOCKS, (h->n + 3) / 4);
-    if (h->p > dn::P_MAX) {                 // wide cohorts: up to four samples per lane
-        if (initial)
-            hipLaunchKernelGGL(k_init_partials_w, dim3(blocks), dim3(256), 0, h->stream[0], h->data.d_est_sums, h->data.d_cov_sums, h->data.d_status, h->data.d_x,
-                               h->data.d_part, (int) h->n, (int) h->p);
-        else
-            hipLaunchKernelGGL(k_outer_partials_w, dim3(blocks), dim3(256), 0, h->stream[0], h->data.d_rho, h->data.d_rhoc, h->data.d_xw, h->data.d_trace, h->data.d_flags,
-                               h->data.d_part, (int) h->n, (int) h->p);
-        hipLaunchKernelGGL(k_outer_reduce_w, dim3((OUT_STRIDE_W + 255) / 256), dim3(256), 0, h->stream[0], h->data.d_part, h->data.d_pvec, blocks, (int) h->p);
-        DN_TRY(hipGetLastError());
-        return DN_OK;
-    }
-    if (initial)
-        hipLaunchKernelGGL(k_init_partials, dim3(blocks), dim3(256), 0, h->stream[0], h->data.d_est_sums, h->data.d_cov_sums, h->data.d_status, h->data.d_x, h->data.d_part,
-                           (int) h->n, (int) h->p);
-    else
-        hipLaunchKernelGGL(k_outer_partials, dim3(blocks), dim3(256), 0, h->stream[0], h->data.d_rho, h->data.d_rhoc, h->data.d_xw, h->data.d_trace, h->data.d_flags, h->data.d_part,
-                           (int) h->n, (int) h->p);
-    hipLaunchKernelGGL(k_outer_reduce, dim3(1), dim3(256), 0, h->stream[0], h->data.d_part, h->data.d_pvec, blocks, (int) h->p);
+    const dn_handle_s::DataSet &d = h->data;
+    if (initial) dn::outer::init_partials(h->stream[0], d.d_est_sums, d.d_cov_sums, d.d_status, d.d_x, d.d_part, d.d_pvec, h->n, (int) h->p);
+    else dn::outer::partials(h->stream[0], d.d_rho, d.d_rhoc, d.d_xw, d.d_trace, d.d_flags, d.d_part, d.d_pvec, h->n, (int) h->p);
     DN_TRY(hipGetLastError());
     return DN_OK;
 }
@@ -1479,8 +1084,7 @@ int dn_outer_begin_scaled(dn_handle h, const double *norm, int32_t degnorm_iter)
         double *d_norm = h->data.d_pvec + PVEC_SUMS + dn::P_WIDE_MAX;
         DN_TRY(hipMemsetAsync(h->data.d_ran, 0, (size_t) h->n * degnorm_iter, h->stream[0]));
         DN_TRY(hipMemcpyAsync(d_norm, norm, sizeof(double) * (size_t) h->p, hipMemcpyHostToDevice, h->stream[0]));
-        const int blocks = (int) std::min<size_t>(2048, (np + 255) / 256);
-        hipLaunchKernelGGL(k_scale_reads, dim3(blocks), dim3(256), 0, h->stream[0], h->data.d_x, d_norm, h->data.d_xw, (long long) np, (int) h->p);
+        dn::outer::scale_reads(h->stream[0], h->data.d_x, d_norm, h->data.d_xw, np, (int) h->p);
         DN_TRY(hipGetLastError());
         DN_TRY(hipStreamSynchronize(h->stream[0]));
         return DN_OK;
@@ -1533,13 +1137,8 @@ int dn_outer_apply(dn_handle h, const double *avg_di, const double *norm, int32_
         double *d_avg = h->data.d_pvec + PVEC_SUMS, *d_norm = d_avg + dn::P_WIDE_MAX;
         if (avg_di) DN_TRY(hipMemcpyAsync(d_avg, avg_di, sizeof(double) * (size_t) h->p, hipMemcpyHostToDevice, h->stream[0]));
         DN_TRY(hipMemcpyAsync(d_norm, norm, sizeof(double) * (size_t) h->p, hipMemcpyHostToDevice, h->stream[0]));
-        const int blocks = (int) std::min<int64_t>(OUT_BLOCKS, (h->n + 3) / 4);
-        if (h->p > dn::P_MAX)
-            hipLaunchKernelGGL(k_outer_apply_w, dim3(blocks), dim3(256), 0, h->stream[0], h->data.d_rhoc, h->data.d_xw, h->data.d_xadj, h->data.d_flags, h->data.d_ran, d_avg, d_norm,
-                               avg_di ? 1 : 0, (int) h->n, (int) h->p, (int) iter, (int) h->data.n_iter);
-        else
-            hipLaunchKernelGGL(k_outer_apply, dim3(blocks), dim3(256), 0, h->stream[0], h->data.d_rhoc, h->data.d_xw, h->data.d_xadj, h->data.d_flags, h->data.d_ran, d_avg, d_norm,
-                               avg_di ? 1 : 0, (int) h->n, (int) h->p, (int) iter, (int) h->data.n_iter);
+        dn::outer::apply(h->stream[0], h->data.d_rhoc, h->data.d_xw, h->data.d_xadj, h->data.d_flags, h->data.d_ran, d_avg, d_norm, avg_di != nullptr,
+                         h->n, (int) h->p, (int) iter, (int) h->data.n_iter);
         DN_TRY(hipGetLastError());
         DN_TRY(hipStreamSynchronize(h->stream[0]));           // the host buffers behind avg_di / norm may go away
         return DN_OK;
@@ -1688,8 +1287,7 @@ int dn_fetch_rows(dn_handle h, int64_t n_rows, const int64_t *rows, double *rho_
         DN_TRY_AS(what, d_out.alloc(sizeof(double) * (size_t) n_rows * h->p));
         DN_TRY_AS(what, d_fl.alloc(sizeof(int32_t) * (size_t) n_rows));
         DN_TRY_AS(what, hipMemcpyAsync(d_rows, rows, sizeof(int64_t) * (size_t) n_rows, hipMemcpyHostToDevice, h->stream[0]));
-        const int tot = (int) (n_rows * h->p);
-        hipLaunchKernelGGL(k_gather_rows, dim3((tot + 255) / 256), dim3(256), 0, h->stream[0], h->data.d_rho, h->data.d_flags, d_rows, d_out, d_fl, (int) n_rows, (int) h->p);
+        dn::outer::gather_rows(h->stream[0], h->data.d_rho, h->data.d_flags, d_rows, d_out, d_fl, (int) n_rows, (int) h->p);
         DN_TRY_AS(what, hipGetLastError());
         DN_TRY_AS(what, hipMemcpyAsync(rho_raw, d_out, sizeof(double) * (size_t) n_rows * h->p, hipMemcpyDeviceToHost, h->stream[0]));
         DN_TRY_AS(what, hipMemcpyAsync(flags, d_fl, sizeof(int32_t) * (size_t) n_rows, hipMemcpyDeviceToHost, h->stream[0]));

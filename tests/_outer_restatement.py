@@ -1,6 +1,7 @@
 """
 The outer DegNorm update and the initial normalisation restated in numpy float64, as references for the O(n p) kernels of
-csrc/dn_api.hip (k_outer_partials, k_outer_reduce, k_outer_apply, k_init_partials, k_scale_reads and their _w copies).
+csrc/dn_outer.hip (k_scale_reads and the family k_outer_partials, k_outer_reduce, k_outer_apply, k_init_partials <WR>, whose
+two instantiations -- one sample per lane for at most 64 samples, four for 65 to 256 -- share everything below).
 
 Reference lines (degnorm/nmf.py of the reference): the DI clip :398-399, the ran_baseline_selection column :403,
 correct_di_scores :148-158, x_adj :575 and :581, the normalisation :584-587, the initial pass :524-533 -- in the formulation

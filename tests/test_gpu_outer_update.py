@@ -1,7 +1,7 @@
 """
-The O(n p) kernels around the NMF pass (csrc/dn_api.hip: k_outer_partials, k_outer_reduce, k_outer_apply, k_init_partials,
-k_scale_reads and their _w copies for 65 to 256 samples) against tests/_outer_restatement.py, on state planted through the
-test seam (dn_debug_plant): DI rows that no data set produces -- above 0.9, negative, -0.0, a single denormal, a single
+The O(n p) kernels around the NMF pass (csrc/dn_outer.hip: k_scale_reads and k_outer_partials, k_outer_reduce, k_outer_apply,
+k_init_partials <WR>, instantiated with one sample per lane for at most 64 samples and with four for 65 to 256) against
+tests/_outer_restatement.py, on state planted through the test seam (dn_debug_plant): DI rows that no data set produces -- above 0.9, negative, -0.0, a single denormal, a single
 non-zero entry in the last sample or in one per-lane slot --, every status and flag value, gene counts on both sides of
 every block-count edge (a multiple of 4 genes, of 8 blocks, the 512-block cap) and sample counts on both sides of every
 lane-slot edge.  The genes themselves are trivial (one base, constant counts): nothing here runs the NMF pass.

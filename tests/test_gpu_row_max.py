@@ -1,5 +1,5 @@
 """
-k_row_max (csrc/dn_api.hip) against numpy, through the test seam (dn_debug_peek): the kernel runs once per upload, for every
+k_row_max (csrc/dn_outer.hip) against numpy, through the test seam (dn_debug_peek): the kernel runs once per upload, for every
 cohort width (finish_upload launches it whatever p is, wide cohorts included), and writes the row maxima behind the
 0.1 * max(F) threshold and the per-gene flag that lets the NMF pass read the counts as 16-bit integers.  Neither comes back
 through any other entry point.

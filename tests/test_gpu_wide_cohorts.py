@@ -1,8 +1,8 @@
 """
 Wide cohorts on the device: 65 to 256 samples on the kernel family gen_wide (csrc/dn_generic.hip compiled with DN_GEN_WIDE=1:
 gen_wide::k_baseline_gen, gen_wide::k_ratio_svd_wide, the estimates kernel with the scale factors by pointer) and the wide
-outer-update kernels of csrc/dn_api.hip, against the CPU oracle (which has no cap on p).  Tolerances are those of
-tests/test_gpu_parity.py.  The sample counts: 65 is one past a wavefront, 96 a partly filled second one, 128 / 129 the boundary
+instantiation (four samples per lane) of the outer-update kernels of csrc/dn_outer.hip, against the CPU oracle (which has no
+cap on p).  Tolerances are those of tests/test_gpu_parity.py.  The sample counts: 65 is one past a wavefront, 96 a partly filled second one, 128 / 129 the boundary
 between two and three, 200 a ragged fourth, 256 the ceiling where every `tid < p` thread is live.
 """
 from collections import OrderedDict
@@ -164,7 +164,7 @@ def _cohort_200():
 
 def test_outer_update_with_four_samples_per_lane():
     """The wide outer-update kernels with all four per-lane slots live (p = 200: samples 128 .. 199 in slots 2 and 3, the tail of
-    k_outer_reduce_w beyond p): the device's update against the host's on the same sweeps."""
+    k_outer_reduce<4> beyond p): the device's update against the host's on the same sweeps."""
     from degnorm_amd.nmf_mpi import ShardedNMFOA, LocalComm
     p, covs, reads = _cohort_200()
     out = []
