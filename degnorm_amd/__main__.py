@@ -26,6 +26,8 @@ carry one name there, and the default --pair-by name (the reference's .1 / .2 su
 --pair-by auto tries the names first.  --exclude-flags, --require-flags (decimal or 0x...) and --min-mapq drop records as
 samtools view -F / -f / -q does; they work on --bam-* inputs and on --sam-* / --sort-bam ones, whose converted and sorted
 copies keep FLAG, MAPQ and PNEXT.
+--stranded forward | reverse counts reads by strand (stranded libraries; reverse is dUTP / TruSeq Stranded): every gene with
+the reads of its own strand only, opposite-strand genes on the same bases apart; it reaches the same inputs.
 Annotations and SAM text may be gzip-compressed (genes.gtf.gz, genes.gff3.gz, X.sam.gz): degnorm_amd.gz inflates them on the GPU.
 Not offered: SAM output, gzip output, zstd, bzip2 and .Z input, --plot-genes, the HTML report and the MPI command (see
 degnorm_amd.warm_start --mpi for the sharded NMF-OA run).  Raw and estimated coverage curves of an output directory as text
@@ -122,6 +124,11 @@ def argparser():
     ap.add_argument('--require-flags', type=_flag_mask, default=0, metavar='MASK',
                     help='drop every record that lacks one of these FLAG bits, as samtools view -f (decimal or 0x...; default 0)')
     ap.add_argument('--min-mapq', type=int, default=0, help='drop every record whose MAPQ is below this, as samtools view -q (0 .. 255; default 0)')
+    ap.add_argument('--stranded', choices=('no', 'forward', 'reverse'), default='no',
+                    help='count reads by strand, for stranded libraries: forward -- a single read or first mate lies on the strand '
+                         'of its gene (htseq-count -s yes, featureCounts -s 1); reverse -- on the opposite strand, dUTP / TruSeq Stranded '
+                         '(-s reverse, -s 2).  Genes without a single strand in the annotation are left out; no (the default) counts '
+                         'every read as if the library were unstranded')
     ap.add_argument('--verify-crc', action='store_true',
                     help='check every BGZF block read from the .bam files against the CRC32 of its trailer (also while '
                          '--create-bai indexes and --sort-bam sorts them) and stop at the first that differs')
@@ -222,8 +229,10 @@ def validate_args(args):
         args.proc_per_node = max(n_cpu - 1, 1)
     if not args.warm_start_dir:
         from .bam import check_read_options
+        from .reads import check_stranded
         check_read_options(getattr(args, 'pair_by', 'name'), getattr(args, 'exclude_flags', 0), getattr(args, 'require_flags', 0),
                            getattr(args, 'min_mapq', 0))
+        check_stranded(getattr(args, 'stranded', 'no'))
     if (args.nmf_iter < 1) or (args.iter < 1) or (args.downsample_rate < 1):
         raise ValueError('--nmf-iter, --iter, and --downsample-rate must all be >= 1.')
     if args.warm_start_dir:
@@ -345,7 +354,7 @@ def _run(args, output_dir, device, verify):
                      frame='device' if args.device_frame else 'host', verify=verify,
                      pair='device' if getattr(args, 'device_pair', False) else 'host', pairing=getattr(args, 'pair_by', 'name'),
                      exclude_flags=getattr(args, 'exclude_flags', 0), require_flags=getattr(args, 'require_flags', 0),
-                     min_mapq=getattr(args, 'min_mapq', 0))
+                     min_mapq=getattr(args, 'min_mapq', 0), stranded=getattr(args, 'stranded', 'no'))
     logging.info('DegNorm pipeline complete! Exiting...')
 
 

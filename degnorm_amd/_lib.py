@@ -121,6 +121,11 @@ def load(build_if_missing=False):
     lib.dn_read_coverage.argtypes = [c.c_int, i32, i64, P(i64), P(i64), P(u8), P(i32), i64, i64, i64, i64, i64, P(i64),
                                      i64, P(i64), P(i32), P(i32), P(i64), P(i64), P(i32), P(i64), i64, P(i64), P(i32),
                                      i64, P(i64), i64, P(i64), P(i64), i64, P(i64), P(i32), P(i64), P(i64), P(dbl)]
+    # strand-specific counting: the sibling takes (sense, strand) after the reads.  Absent from builds before it (A/B runs
+    # load them through DN_LIB_PATH)
+    if hasattr(lib, 'dn_read_coverage_strand'):
+        lib.dn_read_coverage_strand.argtypes = lib.dn_read_coverage.argtypes[:8] + [P(u8), i32] + lib.dn_read_coverage.argtypes[8:]
+        lib.dn_read_sense_host.argtypes = [i64, P(c.c_uint16), P(u8), i32, i32, P(u8)]
     lib.dn_reads_cigar_bounds.argtypes = [c.c_int, i64, P(i64), P(i64), P(u8), i32, P(i32), P(i64), P(i64)]
     lib.dn_reads_last_error.restype = c.c_char_p
     u32 = c.c_uint32
@@ -150,6 +155,10 @@ def load(build_if_missing=False):
     lib.dn_bam_rows_keys.argtypes = [vp, i32, P(u8)]
     lib.dn_bam_rows_fetch.argtypes = [vp, P(i64), P(i64), P(i32), P(u32), P(i64), P(i32), P(u8)]
     lib.dn_bam_rows_coverage.argtypes = [vp, P(i32), P(i32), i64] + lib.dn_read_coverage.argtypes[8:]
+    if hasattr(lib, 'dn_bam_rows_set_stranded'):
+        lib.dn_bam_rows_set_stranded.argtypes = [vp, i32]
+        lib.dn_bam_rows_fetch_sense.argtypes = [vp, P(u8)]
+        lib.dn_bam_rows_coverage_strand.argtypes = [vp, i32] + lib.dn_bam_rows_coverage.argtypes[1:]
     lib.dn_bam_rows_pair.argtypes = [vp, P(i32), P(i32), P(i64), P(c.c_double)]
     lib.dn_bam_pair_host.argtypes = [i64, P(i64), P(i32), P(u8), P(i32), P(i32), P(i64)]
     lib.dn_bam_rows_create_with.argtypes = [c.c_int, i32, i32, i32, P(BamRowsOptions), P(vp)]
@@ -187,6 +196,9 @@ def load(build_if_missing=False):
     lib.dn_gtf_scan.argtypes = [c.c_int, P(c.c_uint8), i64, i64, P(i64), P(i64), P(i64), P(i64), P(i32), P(u64), P(i64), P(i64),
                                 P(i64), P(i32), P(u64), P(i64), P(i32), P(dbl), P(dbl)]
     lib.dn_gtf_last_error.restype = c.c_char_p
+    if hasattr(lib, 'dn_gtf_scan_strand'):           # the strand column of the annotation scans: absent from builds before it
+        a = lib.dn_gtf_scan.argtypes
+        lib.dn_gtf_scan_strand.argtypes = a[:15] + [P(c.c_uint8)] + a[15:]
     sam_args = [P(u8), i64, i32, P(u64), P(i32), P(i64), P(i32), P(u8), i64, P(u8), i64, P(i64), i64, P(i64), i64, P(i64), P(i64), P(i64),
                 P(i64), P(i64), P(i32)]
     lib.dn_sam_encode_host.argtypes = sam_args
@@ -197,6 +209,11 @@ def load(build_if_missing=False):
     lib.dn_gff3_resolve.argtypes = [vp, i64, P(i64), P(i64), P(i32), P(u64), P(i64), P(i32), P(u64), P(i64), P(i64), P(i32), P(dbl)]
     lib.dn_gff3_close.argtypes = [vp]
     lib.dn_gff3_scan_host.argtypes = [P(u8), i64, i32, i64, P(i64), P(i64)] + gff3_cols + [P(i64), P(i64), P(i64), P(i32)]
+    if hasattr(lib, 'dn_gff3_window_strand'):
+        lib.dn_gff3_window_strand.argtypes = ([vp, P(u8), i64, i64, P(i64), P(i64)] + gff3_cols +
+                                              [P(u8), P(u8), P(i64), P(i64), P(i32), P(dbl), P(dbl)])
+        lib.dn_gff3_scan_host_strand.argtypes = ([P(u8), i64, i32, i64, P(i64), P(i64)] + gff3_cols +
+                                                 [P(u8), P(i64), P(i64), P(i64), P(i32)])
     text_args = [P(dbl), i64, i64, i32, P(i64), P(i64), P(i64), P(u8), P(vp)]
     lib.dn_cov_text_host.argtypes = text_args
     lib.dn_cov_text.argtypes = [c.c_int] + text_args + [P(dbl)]

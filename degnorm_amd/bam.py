@@ -49,7 +49,9 @@ The handles that take windows have one shape (_WindowHandle): DeviceRows, _Index
 """
 import ctypes
 import itertools
+import logging
 import os
+import pickle as pkl
 import struct
 import time
 import zlib
@@ -59,7 +61,8 @@ import numpy as np
 
 from . import _lib, gz
 from ._lib import _check, _p as _ptr
-from .reads import BamReadsProcessor, Annotation, check_coverage_call, coverage_outputs, reads_frame
+from .reads import (BamReadsProcessor, Annotation, STRANDED, STRANDS, check_coverage_call, check_strand, check_stranded,
+                    coverage_outputs, reads_frame)
 
 BGZF_EOF = bytes.fromhex('1f8b08040000000000ff0600424302001b0003000000000000000000')
 PSEUDO_BIN = 37450
@@ -670,14 +673,18 @@ class DeviceRows(_WindowHandle):
     """The device-resident rows of one chromosome (dn_bam_rows): kept records in file order."""
     unit = 'dn_bam_rows'
 
-    def __init__(self, tid, unique_alignment, paired, device=None, pairing='name', exclude_flags=0, require_flags=0, min_mapq=0):
+    def __init__(self, tid, unique_alignment, paired, device=None, pairing='name', exclude_flags=0, require_flags=0, min_mapq=0,
+                 stranded='no'):
         """
         pairing: how a paired store tells mates -- 'name' (qname_unpaired) or 'flag' (FLAG bits and mate positions; the
         rule is in include/degnorm_amd.h).  exclude_flags, require_flags, min_mapq: the read filters, 0 for none.  With
-        the defaults this is the store of dn_bam_rows_create.
+        the defaults this is the store of dn_bam_rows_create.  stranded 'forward' or 'reverse': the store also keeps the
+        sense of every row (dn_bam_rows_set_stranded), for coverage(..., strand=).
         """
         self.h = ctypes.c_void_p()
         check_read_options(pairing, exclude_flags, require_flags, min_mapq, modes=('name', 'flag'))
+        self.stranded = check_stranded(stranded)
+        self._paired_rows = -1                           # the rows there were at the last pair()
         self.lib = _lib.load()
         self.paired = bool(paired)
         self.by_flag = self.paired and pairing == 'flag'
@@ -690,6 +697,8 @@ class DeviceRows(_WindowHandle):
         else:
             _check(self.lib.dn_bam_rows_create(dev, int(tid), 1 if unique_alignment else 0, 1 if paired else 0,
                                                ctypes.byref(self.h)), 'dn_bam_rows_create')
+        if self.stranded != 'no':
+            _check(self.lib.dn_bam_rows_set_stranded(self.h, STRANDED.index(self.stranded)), 'dn_bam_rows_set_stranded')
 
     def __del__(self):
         self.close()
@@ -785,6 +794,13 @@ class DeviceRows(_WindowHandle):
                'dn_bam_rows_fetch_mates')
         return flag[:n], mapq[:n], pnext[:n]
 
+    def fetch_sense(self):
+        """The sense of the rows of a stranded store as bytes '+' / '-' (uint8; ValueError for any other store)."""
+        n = self.info()[0]
+        sense = np.zeros(max(n, 1), np.uint8)
+        _check(self.lib.dn_bam_rows_fetch_sense(self.h, _ptr(sense, ctypes.c_uint8)), 'dn_bam_rows_fetch_sense')
+        return sense[:n]
+
     def dropped(self):
         """Records of the windows so far that (exclude_flags / require_flags, min_mapq, the FLAG rule's candidate test) dropped."""
         a, b, c = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
@@ -804,22 +820,32 @@ class DeviceRows(_WindowHandle):
         n_ids, ms = ctypes.c_int64(0), ctypes.c_double(0.0)
         _check(self.lib.dn_bam_rows_pair(self.h, _ptr(order, ctypes.c_int32), _ptr(pair_id, ctypes.c_int32), ctypes.byref(n_ids),
                                          ctypes.byref(ms)), 'dn_bam_rows_pair')
+        self._paired_rows = self.info()[0]               # rows appended later end the pairing
         if fetch:
             return order[:n], pair_id[:n], int(n_ids.value), float(ms.value)
         return None, None, int(n_ids.value), float(ms.value)
 
-    def coverage(self, ann, pair='host'):
+    def coverage(self, ann, pair='host', strand=None):
         """
         dn_bam_rows_coverage: the outputs of reads.device_read_coverage for the stored rows.  A paired store's mates are
         paired on the host in the reference's order (pair_order; pair='host') or on the device with equal keys in file order
         (self.pair(); pair='device'), which moves no keys to the host; self.pair_ms is then the pairing's device ms.  A store
         that pairs by FLAG is always paired on the device, whatever `pair` says.
+        strand '+' or '-' (a stranded store only): dn_bam_rows_coverage_strand on the rows of that sense, with ann the
+        annotation of that strand.  Such a call always pairs on the device, and the calls of both strands share one pairing
+        (pair_ms is 0.0 for the call that found it there).
         """
         if pair not in ('host', 'device'):
             raise ValueError("pair must be 'host' or 'device', not {0!r}".format(pair))
+        if strand is not None and self.stranded == 'no':
+            raise ValueError("coverage(strand=) takes a store created with stranded='forward' or 'reverse'")
+        sel = () if strand is None else (check_strand(strand),)
         order, pair_id, n_ids = None, None, 0
         self.pair_ms = 0.0
-        if self.paired and (pair == 'device' or self.by_flag):
+        if self.paired and sel:
+            if self.info()[0] != self._paired_rows:
+                self.pair_ms = self.pair()[3]
+        elif self.paired and (pair == 'device' or self.by_flag):
             self.pair_ms = self.pair()[3]
         elif self.paired:
             order, pair_id, n_ids = pair_order(self.keys())
@@ -831,17 +857,18 @@ class DeviceRows(_WindowHandle):
         csr_idx = np.zeros(cap, dtype=np.int32)
         csr_val = np.zeros(cap, dtype=np.int64)
         nnz, n_iso_reads, ms = ctypes.c_int64(0), ctypes.c_int64(0), dbl(0.0)
-        rc = self.lib.dn_bam_rows_coverage(self.h, _ptr(order, i32), _ptr(pair_id, i32), int(n_ids),
-                                           ann.chrom_len, ann.keep_lo, ann.keep_hi,
-                                           len(ann.exon_iv), _ptr(ann.exon_iv, i64),
-                                           len(ann.group_iv), _ptr(ann.group_iv, i64), _ptr(ann.group_gene_off, i32),
-                                           _ptr(ann.ol_gene, i32), _ptr(ann.ol_gs0, i64), _ptr(ann.ol_cov_off, i64),
-                                           _ptr(ann.ol_exon_off, i32), _ptr(ann.ol_exon, i64),
-                                           len(ann.iso_iv), _ptr(ann.iso_iv, i64), _ptr(ann.iso_gene, i32),
-                                           len(ann.iso_union), _ptr(ann.iso_union, i64),
-                                           n_genes, _ptr(counts, i64), _ptr(ol_cov, i64), cap, ctypes.byref(nnz),
-                                           _ptr(csr_idx, i32), _ptr(csr_val, i64), ctypes.byref(n_iso_reads), ctypes.byref(ms))
-        check_coverage_call(rc, 'dn_bam_rows_coverage')
+        call = self.lib.dn_bam_rows_coverage_strand if sel else self.lib.dn_bam_rows_coverage
+        rc = call(*((self.h,) + sel + (_ptr(order, i32), _ptr(pair_id, i32), int(n_ids),
+                                      ann.chrom_len, ann.keep_lo, ann.keep_hi,
+                                      len(ann.exon_iv), _ptr(ann.exon_iv, i64),
+                                      len(ann.group_iv), _ptr(ann.group_iv, i64), _ptr(ann.group_gene_off, i32),
+                                      _ptr(ann.ol_gene, i32), _ptr(ann.ol_gs0, i64), _ptr(ann.ol_cov_off, i64),
+                                      _ptr(ann.ol_exon_off, i32), _ptr(ann.ol_exon, i64),
+                                      len(ann.iso_iv), _ptr(ann.iso_iv, i64), _ptr(ann.iso_gene, i32),
+                                      len(ann.iso_union), _ptr(ann.iso_union, i64),
+                                      n_genes, _ptr(counts, i64), _ptr(ol_cov, i64), cap, ctypes.byref(nnz),
+                                      _ptr(csr_idx, i32), _ptr(csr_val, i64), ctypes.byref(n_iso_reads), ctypes.byref(ms))))
+        check_coverage_call(rc, 'dn_bam_rows_coverage_strand' if sel else 'dn_bam_rows_coverage')
         k = int(nnz.value)
         return counts[:n_genes], ol_cov, csr_idx[:k].copy(), csr_val[:k].copy(), int(n_iso_reads.value), float(ms.value)
 
@@ -925,7 +952,7 @@ class NativeBamReadsProcessor(BamReadsProcessor):
 
     def __init__(self, bam_file, index_file, chroms=None, n_jobs=1, output_dir=None, unique_alignment=True, verbose=True,
                  window_bytes=256 << 20, inflate='host', frame='host', frame_segment_bytes=None, verify=False, pair='host',
-                 pairing='name', exclude_flags=0, require_flags=0, min_mapq=0):
+                 pairing='name', exclude_flags=0, require_flags=0, min_mapq=0, stranded='no'):
         """
         BamReadsProcessor on the library's own BAM reader: no pysam.  n_jobs sizes the thread pool that inflates BGZF
         blocks; window_bytes bounds the inflated bytes held (on the host and on the device) besides the chromosome's rows.
@@ -947,8 +974,14 @@ class NativeBamReadsProcessor(BamReadsProcessor):
         'auto': the name rule if it says paired, otherwise the FLAG rule, otherwise single-end; self.pairing_rule is then
         the rule in force.  exclude_flags / require_flags / min_mapq drop records as samtools view -F / -f / -q does, before
         every other rule; all 0 by default.  self.dropped sums what each rule dropped.
+        stranded 'forward' or 'reverse' counts reads by strand (the rule: include/degnorm_amd.h, "Strand-specific counting"):
+        the gene tables then carry a `strand` column of '+' and '-', every chromosome is two passes over one row store, each
+        strand's genes with their own overlap structure and the rows of that sense, mates are paired on the device whatever
+        `pair` says, and the chromosome's files are read_counts_<s>_<chr>.csv, overlap_coverage_<s>_<chr>.pkl and
+        chrom_coverage_<s>_<chr>_plus.npz / _minus.npz.  'no' (the default) is the processor without the option.
         """
         check_read_options(pairing, exclude_flags, require_flags, min_mapq)
+        self.stranded = check_stranded(stranded)
         self.pairing, self.pairing_rule = pairing, 'flag' if pairing == 'flag' else 'name'
         self.exclude_flags, self.require_flags, self.min_mapq = int(exclude_flags), int(require_flags), int(min_mapq)
         self.dropped = {'flags': 0, 'mapq': 0, 'not_candidate': 0}
@@ -1059,7 +1092,7 @@ class NativeBamReadsProcessor(BamReadsProcessor):
         tid, t = self._tid[chrom], self.timing
         host_inflate, host_frame = self.inflate == 'host', self.frame == 'host'
         rows = DeviceRows(tid, self.unique_alignment, self.paired, device, self.pairing_rule, self.exclude_flags, self.require_flags,
-                          self.min_mapq)
+                          self.min_mapq, self.stranded)
         carry, last = b'', _INT32_MIN
         calls = 0.0                         # frame='device': seconds in the library's one call per window; it splits them (frame_info)
 
@@ -1128,12 +1161,14 @@ class NativeBamReadsProcessor(BamReadsProcessor):
         """
         The reference's DataFrame of one chromosome's reads (`qname`, `pos`, `cigar`, plus `qname_unpaired` and sorted by
         it when paired), built from the device-decoded rows.  A file paired by FLAG gives the candidate rows in file order
-        with `qname`, `pos`, `cigar`, `flag`, `mapq`, `pnext`, and `qname_unpaired` equal to `qname`.
+        with `qname`, `pos`, `cigar`, `flag`, `mapq`, `pnext`, and `qname_unpaired` equal to `qname`.  A stranded processor
+        adds `sense`, '+' or '-', the strand each row's fragment came from.
         """
         rows = self.device_rows(chrom)
         try:
             pos, op_beg, n_op, ops, name_beg, name_len, names = rows.fetch()
             mates = rows.fetch_mates() if rows.by_flag else None
+            sense = rows.fetch_sense() if self.stranded != 'no' else None
         finally:
             rows.close()
         nb = names.tobytes()
@@ -1142,7 +1177,80 @@ class NativeBamReadsProcessor(BamReadsProcessor):
         if mates is not None:
             df['flag'], df['mapq'], df['pnext'] = mates[0].astype(np.int64), mates[1].astype(np.int64), mates[2].astype(np.int64)
             df['qname_unpaired'] = df['qname']
+        if sense is not None:                                       # the frame's index is the row in file order, sorted or not
+            df['sense'] = np.array(['+', '-'], dtype=object)[(sense == ord('-')).astype(np.int64)][df.index.values]
         return df
+
+    def _files(self, chrom):
+        """The files of one chromosome; stranded: (chrom_coverage {strand: file}, overlap_coverage, read_counts)."""
+        cov, ol, counts = super(NativeBamReadsProcessor, self)._files(chrom)
+        if self.stranded == 'no':
+            return cov, ol, counts
+        return {s: cov[:-len('.npz')] + tail + '.npz' for s, tail in zip(STRANDS, ('_plus', '_minus'))}, ol, counts
+
+    def chromosome_coverage_read_counts(self, gene_overlap_dat, chrom_gene_df, chrom_exon_df, chrom):
+        """
+        BamReadsProcessor's, and for a stranded processor the two passes of include/degnorm_amd.h, "Strand-specific counting":
+        chrom_gene_df carries `strand`, '+' or '-' for every gene; each strand's genes get their own overlap structure
+        (gene_overlap_dat, the structure of both strands together, is not read) and the rows of their sense.  Written:
+        read_counts_<s>_<chr>.csv (all genes, chrom_gene_df order), overlap_coverage_<s>_<chr>.pkl (the overlap genes of '+',
+        then of '-') and chrom_coverage_<s>_<chr>_plus.npz / _minus.npz (either is not written when no read reached that
+        strand's isolated stage).  When every file the chromosome needs exists, nothing is computed.
+        """
+        if self.stranded == 'no':
+            return super(NativeBamReadsProcessor, self).chromosome_coverage_read_counts(gene_overlap_dat, chrom_gene_df, chrom_exon_df, chrom)
+        from pandas import DataFrame
+        from scipy import sparse
+        from .gene_processing import get_gene_overlap_structure
+        if 'strand' not in chrom_gene_df.columns or not chrom_gene_df['strand'].isin(STRANDS).all():
+            raise ValueError("a stranded run takes genes with a `strand` column of '+' and '-' "
+                             "(GeneAnnotationProcessor(..., strand=True) leaves the other genes out)")
+        parts = {}
+        for s in STRANDS:
+            genes = chrom_gene_df[chrom_gene_df['strand'] == s]
+            if len(genes):
+                parts[s] = (get_gene_overlap_structure(genes), genes, chrom_exon_df[chrom_exon_df['gene'].isin(genes['gene'])])
+        cov_files, ol_cov_file, count_file = self._files(chrom)
+        n_ol = sum(len(g) for ov, _, _ in parts.values() for g in ov['overlap_genes'])
+        if all(not ov['isolated_genes'] or os.path.isfile(cov_files[s]) for s, (ov, _, _) in parts.items()) \
+                and (n_ol == 0 or os.path.isfile(ol_cov_file)) and os.path.isfile(count_file):
+            if self.verbose:
+                logging.info('SAMPLE {0}, CHR {1} -- all coverage and read count files already present; skipping.'
+                             .format(self.sample_id, chrom))
+            return None
+        chrom_len = int(self.header[self.header.chr == chrom].length.iloc[0])
+        anns = {s: Annotation(chrom_len, ov, genes, exons) for s, (ov, genes, exons) in parts.items()}
+        rows = self.device_rows(chrom)
+        try:
+            n_reads = rows.info()[0]
+            n_minus = int((rows.fetch_sense() == ord('-')).sum())
+            out = {}
+            for s, ann in anns.items():
+                t0 = time.perf_counter()
+                out[s] = rows.coverage(ann, 'device', strand=s)
+                self.timing['coverage_s'] = self.timing.get('coverage_s', 0.0) + time.perf_counter() - t0
+                self.timing['coverage_device_ms'] = self.timing.get('coverage_device_ms', 0.0) + out[s][5]
+                self.timing['pair_device_ms'] = self.timing.get('pair_device_ms', 0.0) + rows.pair_ms
+            d = getattr(rows, 'n_dropped', None)
+        finally:
+            rows.close()
+        ol_cov_dict, counts = {}, {}
+        for s, ann in anns.items():
+            csr, ol, cnt = coverage_outputs(ann, *out[s][:5])
+            ol_cov_dict.update(ol)
+            counts.update(cnt)
+            if csr is not None:
+                sparse.save_npz(cov_files[s], matrix=csr)
+        if n_ol > 0:
+            with open(ol_cov_file, 'wb') as f:
+                pkl.dump(ol_cov_dict, f)
+        genes = chrom_gene_df['gene'].tolist()
+        DataFrame({'gene': genes, self.sample_id: [counts[g] for g in genes]}).to_csv(count_file, index=False)
+        if self.verbose:
+            note = '' if d is None else '; dropped by flags {flags}, by MAPQ {mapq}, not a mate candidate {not_candidate}'.format(**d)
+            logging.info('SAMPLE {0}, CHR {1} -- {2} reads ({3} of sense +, {4} of sense -), {5} counted{6}'.format(
+                self.sample_id, chrom, n_reads, n_reads - n_minus, n_minus, sum(counts.values()), note))
+        return None
 
     def _chromosome_coverage(self, chrom, chrom_len, gene_overlap_dat, chrom_gene_df, chrom_exon_df):
         ann = Annotation(chrom_len, gene_overlap_dat, chrom_gene_df, chrom_exon_df)

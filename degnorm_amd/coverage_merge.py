@@ -53,12 +53,16 @@ def gene_intervals(chrom_exon_df):
     return genes, out
 
 
-def _load_sample_rows(data_dir, sample_ids, chrom):
-    """CSR rows of every sample (None where the file is missing) and the chromosome length."""
+_STRAND_SUFFIX = {None: '', '+': '_plus', '-': '_minus'}
+
+
+def _load_sample_rows(data_dir, sample_ids, chrom, strand=None):
+    """CSR rows of every sample (None where the file is missing) and the chromosome length.  strand '+' / '-': the files of a
+    stranded run, chrom_coverage_<sample>_<chr>_plus.npz / _minus.npz."""
     from scipy import sparse
     rows, n = [], None
     for s in sample_ids:
-        f = os.path.join(data_dir, s, 'chrom_coverage_{0}_{1}.npz'.format(s, chrom))
+        f = os.path.join(data_dir, s, 'chrom_coverage_{0}_{1}{2}.npz'.format(s, chrom, _STRAND_SUFFIX[strand]))
         if os.path.isfile(f):
             m = sparse.load_npz(f).tocsr()
             if m.shape[0] != 1:
@@ -71,7 +75,7 @@ def _load_sample_rows(data_dir, sample_ids, chrom):
     return rows, n
 
 
-def assemble_chrom_packed(data_dir, sample_ids, chrom_exon_df, device=None, verbose=True, chunk=4096):
+def assemble_chrom_packed(data_dir, sample_ids, chrom_exon_df, device=None, verbose=True, chunk=4096, strand=None):
     """
     :return: (genes, packed float32 1-d array, lengths int64, device milliseconds) or (None, None, None, 0.0) when no
              sample has coverage for the chromosome (the reference returns an empty dict there, :247-252).
@@ -80,7 +84,7 @@ def assemble_chrom_packed(data_dir, sample_ids, chrom_exon_df, device=None, verb
     if len(unique_chrom) > 1:
         raise ValueError('chrom_exon_df contains exon data for more than one chromosome!')
     chrom = unique_chrom[0]
-    rows, n = _load_sample_rows(data_dir, sample_ids, chrom)
+    rows, n = _load_sample_rows(data_dir, sample_ids, chrom, strand)
     if n is None:
         if verbose:
             logging.info('CHR {0} -- no chromosome coverage files available.'.format(chrom))
@@ -135,12 +139,16 @@ def assemble_chrom_packed(data_dir, sample_ids, chrom_exon_df, device=None, verb
     return genes, packed, lengths, float(ms.value)
 
 
-def merge_chrom_coverage(data_dir, sample_ids, chrom_exon_df, verbose=True, device=None):
+def merge_chrom_coverage(data_dir, sample_ids, chrom_exon_df, verbose=True, device=None, strand=None):
     """
     Drop-in for the reference's `merge_chrom_coverage` (reads_coverage_merge.py:167-372): {gene: (p x L) float64}
-    with genes in the reference's insertion order; an empty dict when no sample has the chromosome.
+    with genes in the reference's insertion order; an empty dict when no sample has the chromosome.  strand '+' / '-': the
+    genes of chrom_exon_df (those of that strand) from that strand's chromosome vectors, the _plus / _minus files of a
+    stranded run.
     """
-    genes, packed, lengths, _ = assemble_chrom_packed(data_dir, sample_ids, chrom_exon_df, device=device, verbose=verbose)
+    if strand not in _STRAND_SUFFIX:
+        raise ValueError("strand must be None, '+' or '-', not {0!r}".format(strand))
+    genes, packed, lengths, _ = assemble_chrom_packed(data_dir, sample_ids, chrom_exon_df, device=device, verbose=verbose, strand=strand)
     if genes is None:
         return dict()
     p = len(sample_ids)
@@ -202,11 +210,21 @@ def merge_coverage(data_dir, sample_ids, exon_df, n_jobs=1, output_dir=None, ver
     reads_coverage_merge.py:375-457): the genes merge_chrom_coverage slices from the chromosome coverage, then the genes of
     overlap groups, whose matrices from the overlap files replace the sliced ones.  With output_dir each chromosome's dict
     is pickled to `<output_dir>/<chr>/coverage_matrices_<chr>.pkl`.  n_jobs is kept for the signature: the chromosomes go
-    through the device one after another.
+    through the device one after another.  When exon_df has a `strand` column (a stranded run), each chromosome takes its '+'
+    genes and then its '-' genes through the assembly, each strand from its own chromosome vectors; the overlap matrices are
+    laid over them as before, and that is the gene order of the result.
     """
     gene_cov_dict = OrderedDict()
     for chrom in exon_df.chr.unique():
-        chrom_cov_dict = merge_chrom_coverage(data_dir, sample_ids, exon_df[exon_df.chr.isin([chrom])], verbose=verbose, device=device)
+        chrom_exon_df = exon_df[exon_df.chr.isin([chrom])]
+        if 'strand' in exon_df.columns:
+            chrom_cov_dict = {}
+            for s in ('+', '-'):
+                strand_exon_df = chrom_exon_df[chrom_exon_df['strand'] == s]
+                if len(strand_exon_df):
+                    chrom_cov_dict.update(merge_chrom_coverage(data_dir, sample_ids, strand_exon_df, verbose=verbose, device=device, strand=s))
+        else:
+            chrom_cov_dict = merge_chrom_coverage(data_dir, sample_ids, chrom_exon_df, verbose=verbose, device=device)
         chrom_cov_dict = {**chrom_cov_dict, **merge_overlap_gene_coverage(data_dir, sample_ids, chrom)}
         for gene in chrom_cov_dict:
             gene_cov_dict[gene] = chrom_cov_dict[gene]

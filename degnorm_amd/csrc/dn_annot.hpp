@@ -4,6 +4,7 @@
 // the rows to the caller.  c is the chromosome name (a node's ID), a the gene name (or the Parent still to resolve).
 #pragma once
 #include "dn_lines.hpp"
+#include "dn_fields.hpp"
 
 namespace {
 
@@ -48,6 +49,34 @@ __global__ __launch_bounds__(kNT) void k_compact(int which, const uint8_t *__res
     put(row.a_len, r, rec.a_len, j);
     put(row.a_hash, r, rec.a_hash, j);
     put(row.open, r, rec.open, j);
+}
+
+// The optional strand column of both scans (dn::strand_field, dn_fields.hpp), two small kernels that run only when the caller
+// asks for it, while the window's text is resident; the parse kernels and k_compact know nothing of it.
+// k_strand_check: one lane per line, as the parse kernel (lane j takes line n_head + j of the table): an exon line whose field
+// seven is not one of + - . ? is reported as `err_kind` to the word the parse kernel reports to, so the first faulty line wins
+// whatever its fault.
+__global__ __launch_bounds__(kNT) void k_strand_check(const uint8_t *__restrict__ buf, int64_t limit, const int64_t *__restrict__ line_start,
+                                                       int64_t n_starts, int64_t n_head, int64_t line_base, const uint8_t *__restrict__ kind,
+                                                       int err_kind, unsigned long long *__restrict__ first_error)
+{
+    const int64_t j = (int64_t) blockIdx.x * kNT + threadIdx.x, i = n_head + j;
+    if (i >= n_starts || kind[j] != (uint8_t) dn::kExon) return;
+    int64_t beg, end;
+    line_span(line_start, n_starts, limit, i, &beg, &end);
+    Bytes b(buf);
+    if (beg < 0 || end > limit || !dn::strand_field(b, beg, end)) report_error(first_error, line_base + j + 1, err_kind);
+}
+
+// k_row_strand: one lane per exon row, after compaction: from the row's line start (c_beg, an offset into buf) to field seven.
+__global__ __launch_bounds__(kNT) void k_row_strand(const uint8_t *__restrict__ buf, int64_t limit, const int64_t *__restrict__ c_beg,
+                                                     int64_t n_rows, uint8_t *__restrict__ strand)
+{
+    const int64_t r = (int64_t) blockIdx.x * kNT + threadIdx.x;
+    if (r >= n_rows) return;
+    Bytes b(buf);
+    const int64_t beg = c_beg[r];
+    strand[r] = beg >= 0 && beg < limit ? dn::strand_field(b, beg, limit) : 0;
 }
 
 struct ExonBuffers {

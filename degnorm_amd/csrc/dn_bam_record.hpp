@@ -94,6 +94,20 @@ DN_HD uint32_t reg2bin(int64_t beg, int64_t end, int min_shift, int depth)
     return 0;
 }
 
+// Strand-specific counting (include/degnorm_amd.h): the strand the fragment of a row came from, '+' or '-'.  A row is a last
+// mate when FLAG 0x1 and 0x80 are both set, and in a store paired by the name rule (by_name) also when its name ends in '2'
+// (name_last: the last byte of the name, 0 for an empty one).  The sense is the strand the row aligned to (0x10: '-'),
+// flipped for a last mate and flipped once more for the protocol kStrandReverse.
+enum : int { kStrandNo = 0, kStrandForward = 1, kStrandReverse = 2 };
+constexpr uint8_t kSensePlus = '+', kSenseMinus = '-';
+
+DN_HD uint8_t row_sense(uint32_t flag, uint8_t name_last, bool by_name, int protocol)
+{
+    const bool last_mate = (flag & 0x81u) == 0x81u || (by_name && name_last == '2');
+    const bool minus = ((flag & 0x10u) != 0) != last_mate;
+    return (minus != (protocol == kStrandReverse)) ? kSenseMinus : kSensePlus;
+}
+
 // blocks of a grid-stride kernel that gives each block per_block of the n items, at most cap
 inline unsigned grid_for(int64_t n, int per_block, int64_t cap)
 {

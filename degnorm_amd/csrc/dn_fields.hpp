@@ -77,6 +77,23 @@ template <class M> DN_HD bool nine_fields(M &in, int64_t beg, int64_t end, NineF
     return nt == 8;
 }
 
+// Field seven of the annotation line that starts at beg, for the optional strand column of both scans: the byte when the
+// field is exactly one of + - . ? and 0 otherwise.  The walk ends at the sixth tab, at a '\n' or at `limit`, whichever comes
+// first, so it stays inside the line and below limit.
+template <class M> DN_HD uint8_t strand_field(M &in, int64_t beg, int64_t limit)
+{
+    int nt = 0;
+    int64_t p = beg;
+    while (p < limit && nt < 6) {
+        const uint32_t c = in.at(p++);
+        if (c == '\n') return 0;
+        if (c == '\t') nt++;
+    }
+    if (nt < 6 || p + 1 >= limit || in.at(p + 1) != '\t') return 0;
+    const uint32_t c = in.at(p);
+    return c == '+' || c == '-' || c == '.' || c == '?' ? (uint8_t) c : 0;
+}
+
 // is field three `exon` in any letter case?
 template <class M> DN_HD bool is_exon(M &in, const NineFields &F) { return spells(in, F.t2 + 1, F.t3, "exon", 4); }
 

@@ -196,10 +196,11 @@ extern "C" int dn_gff3_close(dn_gff3 h)
     return DN_OK;
 }
 
-extern "C" int dn_gff3_window(dn_gff3 h, const uint8_t *bytes, int64_t n_bytes, int64_t row_cap, int64_t *n_lines, int64_t *n_rows,
-                              int64_t *line, int64_t *chr_beg, int32_t *chr_len, uint64_t *chr_hash, int64_t *start, int64_t *end,
-                              int64_t *gene_beg, int32_t *gene_len, uint64_t *gene_hash, uint8_t *pending, int64_t *fasta_line,
-                              int64_t *err_line, int32_t *err_kind, double *copy_ms, double *device_ms)
+// dn_gff3_window, and with `strand` not null dn_gff3_window_strand: field seven of every exon row of the window
+static int gff3_window(dn_gff3 h, const uint8_t *bytes, int64_t n_bytes, int64_t row_cap, int64_t *n_lines, int64_t *n_rows,
+                       int64_t *line, int64_t *chr_beg, int32_t *chr_len, uint64_t *chr_hash, int64_t *start, int64_t *end,
+                       int64_t *gene_beg, int32_t *gene_len, uint64_t *gene_hash, uint8_t *pending, uint8_t *strand, int64_t *fasta_line,
+                       int64_t *err_line, int32_t *err_kind, double *copy_ms, double *device_ms)
 {
     dn::clear_error();
     if (!h || !bytes || n_bytes < 1 || n_bytes > kMaxWindow || row_cap < 0 || !n_lines || !n_rows || !line || !chr_beg || !chr_len || !chr_hash
@@ -213,7 +214,7 @@ extern "C" int dn_gff3_window(dn_gff3 h, const uint8_t *bytes, int64_t n_bytes, 
     const int64_t head = h->pos - base, rel_end = head + n_bytes, n_head = h->tail_nl, line_base = h->lines;
     // what the stream reads or writes: owned here, so that it outlives the wait of dn::synced
     dn::Event e0, e1, e2;
-    dn::DeviceBuffer<uint8_t> d_kind;
+    dn::DeviceBuffer<uint8_t> d_kind, d_strand;
     dn::DeviceBuffer<int32_t> d_block_exons, d_block_nodes;
     dn::DeviceBuffer<int64_t> d_exon_off, d_node_off;
     dn::DeviceBuffer<unsigned long long> d_marks;                   // first error, first ##FASTA line
@@ -249,6 +250,9 @@ extern "C" int dn_gff3_window(dn_gff3 h, const uint8_t *bytes, int64_t n_bytes, 
         DN_TRY(rec.alloc(n_lanes, true));
         hipLaunchKernelGGL(k_gff3_parse, dim3((unsigned) n_blocks), dim3(kNT), 0, st, tiles, base, rel_end, (const int64_t *) lines.line_start.get(),
                            n_starts, n_head, line_base, h->mask, rec.view(), d_kind.get(), d_marks.get(), d_marks.get() + 1);
+        if (strand)
+            hipLaunchKernelGGL(k_strand_check, dim3((unsigned) n_blocks), dim3(kNT), 0, st, tiles, rel_end, (const int64_t *) lines.line_start.get(),
+                               n_starts, n_head, line_base, (const uint8_t *) d_kind.get(), (int) DN_GFF3_E_STRAND, d_marks.get());
         hipLaunchKernelGGL(k_gff3_mark, dim3((unsigned) n_blocks), dim3(kNT), 0, st, (const uint8_t *) d_kind.get(), n_lanes, line_base,
                            (const unsigned long long *) d_marks.get() + 1, d_block_exons.get(), d_block_nodes.get());
         hipLaunchKernelGGL(k_scan, dim3(1), dim3(kScanNT), 0, st, d_block_exons.get(), n_blocks, d_exon_off.get(), lines.total.get());
@@ -286,7 +290,14 @@ extern "C" int dn_gff3_window(dn_gff3 h, const uint8_t *bytes, int64_t n_bytes, 
                                    line_base, (const unsigned long long *) d_marks.get() + 1, (const int64_t *) d_node_off.get(), rec.view(),
                                    h->nodes.at(h->n_nodes), n_new_nodes);
             DN_TRY(hipGetLastError());
+            if (strand && n_exons > 0) {                            // the text is resident: c_beg is an offset into the file
+                DN_TRY(d_strand.alloc((size_t) n_exons));
+                hipLaunchKernelGGL(k_row_strand, dim3((unsigned) ((n_exons + kNT - 1) / kNT)), dim3(kNT), 0, st, (const uint8_t *) h->buf.get(),
+                                   h->pos + n_bytes, (const int64_t *) row.c_beg.get(), n_exons, d_strand.get());
+                DN_TRY(hipGetLastError());
+            }
             DN_TRY(hipEventRecord(e2, st));
+            if (strand && n_exons > 0) DN_TRY(hipMemcpyAsync(strand, d_strand, (size_t) n_exons, hipMemcpyDeviceToHost, st));
             DN_TRY(copy_rows(st, ExonCols{line, chr_beg, start, end, gene_beg, chr_len, gene_len, chr_hash, gene_hash, pending}, row.view(), n_exons));
         }
         DN_TRY(hipStreamSynchronize(st));
@@ -305,6 +316,24 @@ extern "C" int dn_gff3_window(dn_gff3 h, const uint8_t *bytes, int64_t n_bytes, 
         }
         return DN_OK;
     });
+}
+
+extern "C" int dn_gff3_window(dn_gff3 h, const uint8_t *bytes, int64_t n_bytes, int64_t row_cap, int64_t *n_lines, int64_t *n_rows,
+                              int64_t *line, int64_t *chr_beg, int32_t *chr_len, uint64_t *chr_hash, int64_t *start, int64_t *end,
+                              int64_t *gene_beg, int32_t *gene_len, uint64_t *gene_hash, uint8_t *pending, int64_t *fasta_line,
+                              int64_t *err_line, int32_t *err_kind, double *copy_ms, double *device_ms)
+{
+    return gff3_window(h, bytes, n_bytes, row_cap, n_lines, n_rows, line, chr_beg, chr_len, chr_hash, start, end, gene_beg, gene_len, gene_hash,
+                       pending, nullptr, fasta_line, err_line, err_kind, copy_ms, device_ms);
+}
+
+extern "C" int dn_gff3_window_strand(dn_gff3 h, const uint8_t *bytes, int64_t n_bytes, int64_t row_cap, int64_t *n_lines, int64_t *n_rows,
+                                     int64_t *line, int64_t *chr_beg, int32_t *chr_len, uint64_t *chr_hash, int64_t *start, int64_t *end,
+                                     int64_t *gene_beg, int32_t *gene_len, uint64_t *gene_hash, uint8_t *pending, uint8_t *strand,
+                                     int64_t *fasta_line, int64_t *err_line, int32_t *err_kind, double *copy_ms, double *device_ms)
+{
+    return gff3_window(h, bytes, n_bytes, row_cap, n_lines, n_rows, line, chr_beg, chr_len, chr_hash, start, end, gene_beg, gene_len, gene_hash,
+                       pending, strand, fasta_line, err_line, err_kind, copy_ms, device_ms);
 }
 
 extern "C" int dn_gff3_resolve(dn_gff3 h, int64_t n, const int64_t *line, const int64_t *par_beg, const int32_t *par_len, const uint64_t *par_hash,
@@ -378,10 +407,11 @@ extern "C" int dn_gff3_resolve(dn_gff3 h, int64_t n, const int64_t *line, const 
     });
 }
 
-extern "C" int dn_gff3_scan_host(const uint8_t *data, int64_t n_bytes, int32_t hash_bits, int64_t row_cap, int64_t *n_lines, int64_t *n_rows,
-                                 int64_t *line, int64_t *chr_beg, int32_t *chr_len, uint64_t *chr_hash, int64_t *start, int64_t *end,
-                                 int64_t *gene_beg, int32_t *gene_len, uint64_t *gene_hash, int64_t *n_nodes, int64_t *n_walked, int64_t *err_line,
-                                 int32_t *err_kind)
+// dn_gff3_scan_host, and with `strand` not null dn_gff3_scan_host_strand
+static int gff3_scan_host(const uint8_t *data, int64_t n_bytes, int32_t hash_bits, int64_t row_cap, int64_t *n_lines, int64_t *n_rows,
+                          int64_t *line, int64_t *chr_beg, int32_t *chr_len, uint64_t *chr_hash, int64_t *start, int64_t *end,
+                          int64_t *gene_beg, int32_t *gene_len, uint64_t *gene_hash, uint8_t *strand, int64_t *n_nodes, int64_t *n_walked,
+                          int64_t *err_line, int32_t *err_kind)
 {
     dn::clear_error();
     if (!data || n_bytes < 1 || hash_bits < 1 || hash_bits > 64 || row_cap < 0 || !n_lines || !n_rows || !line || !chr_beg || !chr_len || !chr_hash
@@ -411,6 +441,11 @@ extern "C" int dn_gff3_scan_host(const uint8_t *data, int64_t n_bytes, int32_t h
                 return DN_OK;
             }
             if (r == g3::kFasta) ended = true;
+            if (r == dn::kExon && strand && !dn::strand_field(in, pos, stop)) {
+                *err_line = lines + 1;
+                *err_kind = DN_GFF3_E_STRAND;
+                return DN_OK;
+            }
             if (r == dn::kExon)
                 exons.push_back(Exon{lines + 1, L.c_lo, L.start, L.end, L.a_lo, (int32_t) (L.c_hi - L.c_lo), (int32_t) (L.a_hi - L.a_lo), L.open});
             if (r == g3::kNode) {
@@ -451,8 +486,28 @@ extern "C" int dn_gff3_scan_host(const uint8_t *data, int64_t n_bytes, int32_t h
         }
         line[k] = x.line; chr_beg[k] = x.c_beg; chr_len[k] = x.c_len; chr_hash[k] = dn::fnv1a(in, x.c_beg, x.c_beg + x.c_len);
         start[k] = x.start; end[k] = x.end; gene_beg[k] = g_beg; gene_len[k] = g_len; gene_hash[k] = g_hash;
+        if (strand) strand[k] = dn::strand_field(in, x.c_beg, n_bytes);
     }
     *n_rows = (int64_t) exons.size();
     *n_walked = walked;
     return DN_OK;
+}
+
+extern "C" int dn_gff3_scan_host(const uint8_t *data, int64_t n_bytes, int32_t hash_bits, int64_t row_cap, int64_t *n_lines, int64_t *n_rows,
+                                 int64_t *line, int64_t *chr_beg, int32_t *chr_len, uint64_t *chr_hash, int64_t *start, int64_t *end,
+                                 int64_t *gene_beg, int32_t *gene_len, uint64_t *gene_hash, int64_t *n_nodes, int64_t *n_walked, int64_t *err_line,
+                                 int32_t *err_kind)
+{
+    return gff3_scan_host(data, n_bytes, hash_bits, row_cap, n_lines, n_rows, line, chr_beg, chr_len, chr_hash, start, end, gene_beg, gene_len,
+                          gene_hash, nullptr, n_nodes, n_walked, err_line, err_kind);
+}
+
+extern "C" int dn_gff3_scan_host_strand(const uint8_t *data, int64_t n_bytes, int32_t hash_bits, int64_t row_cap, int64_t *n_lines,
+                                        int64_t *n_rows, int64_t *line, int64_t *chr_beg, int32_t *chr_len, uint64_t *chr_hash, int64_t *start,
+                                        int64_t *end, int64_t *gene_beg, int32_t *gene_len, uint64_t *gene_hash, uint8_t *strand,
+                                        int64_t *n_nodes, int64_t *n_walked, int64_t *err_line, int32_t *err_kind)
+{
+    if (!strand) return dn::fail(DN_E_INVALID, "dn_gff3_scan_host_strand: bad argument");
+    return gff3_scan_host(data, n_bytes, hash_bits, row_cap, n_lines, n_rows, line, chr_beg, chr_len, chr_hash, start, end, gene_beg, gene_len,
+                          gene_hash, strand, n_nodes, n_walked, err_line, err_kind);
 }

@@ -57,10 +57,11 @@ __global__ __launch_bounds__(kNT) void k_parse_lines(const uint8_t *__restrict__
 
 }  // namespace
 
-extern "C" int dn_gtf_scan(int device, const uint8_t *buf, int64_t n_bytes, int64_t row_cap, int64_t *n_lines, int64_t *n_rows,
-                           int64_t *line, int64_t *chr_beg, int32_t *chr_len, uint64_t *chr_hash, int64_t *start, int64_t *end,
-                           int64_t *gene_beg, int32_t *gene_len, uint64_t *gene_hash, int64_t *err_line, int32_t *err_kind,
-                           double *copy_ms, double *device_ms)
+// dn_gtf_scan, and with `strand` not null dn_gtf_scan_strand: field seven of every exon row, checked before the rows are the caller's
+static int gtf_scan(int device, const uint8_t *buf, int64_t n_bytes, int64_t row_cap, int64_t *n_lines, int64_t *n_rows,
+                    int64_t *line, int64_t *chr_beg, int32_t *chr_len, uint64_t *chr_hash, int64_t *start, int64_t *end,
+                    int64_t *gene_beg, int32_t *gene_len, uint64_t *gene_hash, uint8_t *strand, int64_t *err_line, int32_t *err_kind,
+                    double *copy_ms, double *device_ms)
 {
     if (!buf || n_bytes < 1 || row_cap < 0 || !n_lines || !n_rows || !line || !chr_beg || !chr_len || !chr_hash || !start || !end
         || !gene_beg || !gene_len || !gene_hash || !err_line || !err_kind)
@@ -70,7 +71,7 @@ extern "C" int dn_gtf_scan(int device, const uint8_t *buf, int64_t n_bytes, int6
     // what the stream reads or writes: owned here, so that it outlives the wait of dn::synced
     dn::Stream st;
     dn::Event e0, e1, e2;
-    dn::DeviceBuffer<uint8_t> d_buf, d_kind;
+    dn::DeviceBuffer<uint8_t> d_buf, d_kind, d_strand;
     dn::DeviceBuffer<int32_t> d_block_kept;
     dn::DeviceBuffer<int64_t> d_block_off;
     dn::DeviceBuffer<unsigned long long> d_err;
@@ -103,6 +104,10 @@ extern "C" int dn_gtf_scan(int device, const uint8_t *buf, int64_t n_bytes, int6
         hipLaunchKernelGGL(k_parse_lines, dim3((unsigned) n_blocks), dim3(kNT), 0, st, (const uint8_t *) d_buf.get(), n_bytes,
                            (const int64_t *) lines.line_start.get(), n_starts, rec.view(), d_kind.get(), d_block_kept.get(), d_err.get());
         hipLaunchKernelGGL(k_scan, dim3(1), dim3(kScanNT), 0, st, d_block_kept.get(), n_blocks, d_block_off.get(), lines.total.get());
+        if (strand)
+            hipLaunchKernelGGL(k_strand_check, dim3((unsigned) n_blocks), dim3(kNT), 0, st, (const uint8_t *) d_buf.get(), n_bytes,
+                               (const int64_t *) lines.line_start.get(), n_starts, (int64_t) 0, (int64_t) 0, (const uint8_t *) d_kind.get(),
+                               (int) DN_GTF_E_STRAND, d_err.get());
         DN_TRY(hipGetLastError());
         DN_TRY(hipMemcpyAsync(&kept, lines.total, sizeof(int64_t), hipMemcpyDeviceToHost, st));
         DN_TRY(hipMemcpyAsync(&first_error, d_err, sizeof(first_error), hipMemcpyDeviceToHost, st));
@@ -119,7 +124,14 @@ extern "C" int dn_gtf_scan(int device, const uint8_t *buf, int64_t n_bytes, int6
                                    (int64_t) 0, (const unsigned long long *) nullptr, (const int64_t *) d_block_off.get(), rec.view(), row.view(), kept);
                 DN_TRY(hipGetLastError());
             }
+            if (strand && kept > 0) {                               // while the window is resident
+                DN_TRY(d_strand.alloc((size_t) kept));
+                hipLaunchKernelGGL(k_row_strand, dim3((unsigned) ((kept + kNT - 1) / kNT)), dim3(kNT), 0, st, (const uint8_t *) d_buf.get(), n_bytes,
+                                   (const int64_t *) row.c_beg.get(), kept, d_strand.get());
+                DN_TRY(hipGetLastError());
+            }
             DN_TRY(hipEventRecord(e2, st));
+            if (strand && kept > 0) DN_TRY(hipMemcpyAsync(strand, d_strand, (size_t) kept, hipMemcpyDeviceToHost, st));
             DN_TRY(copy_rows(st, ExonCols{line, chr_beg, start, end, gene_beg, chr_len, gene_len, chr_hash, gene_hash, nullptr}, row.view(), kept));
             *n_rows = kept;
         }
@@ -128,4 +140,22 @@ extern "C" int dn_gtf_scan(int device, const uint8_t *buf, int64_t n_bytes, int6
         if (device_ms) { float ms = 0.f; DN_TRY(hipEventElapsedTime(&ms, e1, e2)); *device_ms = ms; }
         return DN_OK;
     });
+}
+
+extern "C" int dn_gtf_scan(int device, const uint8_t *buf, int64_t n_bytes, int64_t row_cap, int64_t *n_lines, int64_t *n_rows,
+                           int64_t *line, int64_t *chr_beg, int32_t *chr_len, uint64_t *chr_hash, int64_t *start, int64_t *end,
+                           int64_t *gene_beg, int32_t *gene_len, uint64_t *gene_hash, int64_t *err_line, int32_t *err_kind,
+                           double *copy_ms, double *device_ms)
+{
+    return gtf_scan(device, buf, n_bytes, row_cap, n_lines, n_rows, line, chr_beg, chr_len, chr_hash, start, end, gene_beg, gene_len, gene_hash,
+                    nullptr, err_line, err_kind, copy_ms, device_ms);
+}
+
+extern "C" int dn_gtf_scan_strand(int device, const uint8_t *buf, int64_t n_bytes, int64_t row_cap, int64_t *n_lines, int64_t *n_rows,
+                                  int64_t *line, int64_t *chr_beg, int32_t *chr_len, uint64_t *chr_hash, int64_t *start, int64_t *end,
+                                  int64_t *gene_beg, int32_t *gene_len, uint64_t *gene_hash, uint8_t *strand, int64_t *err_line,
+                                  int32_t *err_kind, double *copy_ms, double *device_ms)
+{
+    return gtf_scan(device, buf, n_bytes, row_cap, n_lines, n_rows, line, chr_beg, chr_len, chr_hash, start, end, gene_beg, gene_len, gene_hash,
+                    strand, err_line, err_kind, copy_ms, device_ms);
 }

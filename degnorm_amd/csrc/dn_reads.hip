@@ -193,15 +193,31 @@ struct MateBits {
 constexpr int32_t kMateFirst = 1 << 30, kMatePair = 2 | kMateFirst;
 constexpr int64_t kMateRowsMax = (int64_t) 1 << 30;
 
-template <class C, bool MATES>
+// Strand-specific counting: the sense of the row taken at position r is sense[order ? order[r] : r], and the call counts
+// the rows whose sense is `want` (dn::kSensePlus or dn::kSenseMinus).
+struct StrandSel {
+    const uint8_t *sense = nullptr;
+    const int32_t *order = nullptr;
+    uint8_t want = 0;
+};
+
+// STRAND: the position pre-filter also asks for the sense `sel.want`; a row of the other sense is dropped before it is
+// counted for its pair, so a pair whose mates disagree leaves one row here and is no pair.  The instances without it take
+// no selector and are the kernels of the unstranded call.
+template <class C, bool MATES, bool STRAND, class... Sel>
 __global__ __launch_bounds__(kNT) void k_prefilter(int64_t n, const int64_t *__restrict__ pos, C cig, int64_t keep_lo, int64_t keep_hi,
                                                    const int32_t *__restrict__ pair_id, int32_t *__restrict__ pair_cnt, MateBits mates,
-                                                   int64_t *__restrict__ end_pos, int32_t *__restrict__ keep)
+                                                   int64_t *__restrict__ end_pos, int32_t *__restrict__ keep, Sel... sel)
 {
+    static_assert(sizeof...(Sel) == (STRAND ? 1 : 0), "a stranded instance takes one StrandSel, the others none");
     for (int64_t r = (int64_t) blockIdx.x * kNT + threadIdx.x; r < n; r += (int64_t) gridDim.x * kNT) {
         const int64_t e = pos[r] + cigar_length(cig.row(r));
         end_pos[r] = e;
-        const int32_t k = pos[r] >= keep_lo && e <= keep_hi;
+        int32_t k = pos[r] >= keep_lo && e <= keep_hi;
+        if constexpr (STRAND) {
+            const StrandSel s{sel...};
+            k = k && s.sense[s.order ? s.order[r] : r] == s.want;
+        }
         keep[r] = k;
         if (MATES) {
             if (k) atomicAdd((unsigned int *) pair_cnt + pair_id[r], (mates.flag[mates.order[r]] & dn::kFlagFirst) ? 1u | (unsigned int) kMateFirst : 1u);
@@ -392,9 +408,11 @@ struct CoverageIO {
 template <class C>
 int coverage_stages(hipStream_t st, int32_t paired, int64_t n_rows, const int64_t *d_pos, C cig, const int32_t *pair_id,
                     const int32_t *d_pair_id, int64_t n_pair_ids, const CoverageIO &io, const std::function<std::string(int64_t)> &cigar_text,
-                    MateBits mates = MateBits{})
+                    MateBits mates = MateBits{}, StrandSel sel = StrandSel{})
 {
     constexpr bool kCanMate = std::is_same<C, BamCigars>::value;
+    if (sel.want != 0 && ((sel.want != dn::kSensePlus && sel.want != dn::kSenseMinus) || (n_rows > 0 && !sel.sense)))
+        return dn::fail(DN_E_INVALID, "dn_read_coverage: a stranded call takes the sense of every row and the strand '+' or '-'");
     if (mates.flag && (!kCanMate || !paired || !d_pair_id || !mates.order || n_rows > kMateRowsMax))
         return dn::fail(n_rows > kMateRowsMax ? DN_E_UNSUPPORTED : DN_E_INVALID, "dn_read_coverage: pairing by FLAG takes a paired row store of at most 2^30 rows");
     const int64_t chrom_len = io.chrom_len, n_exon = io.n_exon, n_groups = io.n_groups, n_iso = io.n_iso, n_iso_union = io.n_iso_union,
@@ -468,14 +486,21 @@ int coverage_stages(hipStream_t st, int32_t paired, int64_t n_rows, const int64_
         if (paired) DN_TRY(hipMemsetAsync(d_pcnt, 0, sizeof(int32_t) * (size_t) n_pair_ids, st));
         if (n_rows > 0) {
             const dim3 pre_grid(dn::grid_for(n_rows, kNT, kGridCap));
+            const int32_t *pre_pid = mates.flag || paired ? p_pid : nullptr;
             if constexpr (kCanMate) {
-                if (mates.flag)
-                    hipLaunchKernelGGL((k_prefilter<C, true>), pre_grid, dim3(kNT), 0, st, n_rows, d_pos, cig, io.keep_lo, io.keep_hi, p_pid, d_pcnt.get(),
-                                       mates, d_end.get(), d_keep.get());
+                if (mates.flag && sel.want)
+                    hipLaunchKernelGGL((k_prefilter<C, true, true, StrandSel>), pre_grid, dim3(kNT), 0, st, n_rows, d_pos, cig, io.keep_lo, io.keep_hi,
+                                       pre_pid, d_pcnt.get(), mates, d_end.get(), d_keep.get(), sel);
+                else if (mates.flag)
+                    hipLaunchKernelGGL((k_prefilter<C, true, false>), pre_grid, dim3(kNT), 0, st, n_rows, d_pos, cig, io.keep_lo, io.keep_hi, pre_pid,
+                                       d_pcnt.get(), mates, d_end.get(), d_keep.get());
             }
-            if (!mates.flag)
-                hipLaunchKernelGGL((k_prefilter<C, false>), pre_grid, dim3(kNT), 0, st, n_rows, d_pos, cig, io.keep_lo, io.keep_hi,
-                                   paired ? p_pid : (const int32_t *) nullptr, d_pcnt.get(), mates, d_end.get(), d_keep.get());
+            if (!mates.flag && sel.want)
+                hipLaunchKernelGGL((k_prefilter<C, false, true, StrandSel>), pre_grid, dim3(kNT), 0, st, n_rows, d_pos, cig, io.keep_lo, io.keep_hi,
+                                   pre_pid, d_pcnt.get(), mates, d_end.get(), d_keep.get(), sel);
+            else if (!mates.flag)
+                hipLaunchKernelGGL((k_prefilter<C, false, false>), pre_grid, dim3(kNT), 0, st, n_rows, d_pos, cig, io.keep_lo, io.keep_hi, pre_pid,
+                                   d_pcnt.get(), mates, d_end.get(), d_keep.get());
             DN_TRY(hipGetLastError());
             int64_t n_units = n_rows;
             if (paired) {
@@ -561,6 +586,38 @@ int coverage_stages(hipStream_t st, int32_t paired, int64_t n_rows, const int64_
                   ol_cov_off, ol_exon_off, ol_exon_bounds, n_iso, iso_iv, iso_gene, n_iso_union, iso_union, n_genes, counts,  \
                   ol_cov, csr_cap, nnz, csr_idx, csr_val, n_isolated_reads, device_ms}
 
+// dn_read_coverage, and with strand != 0 its stranded sibling: `sense` is then uploaded with the rows
+static int read_coverage(int device, int32_t paired, int64_t n_rows, const int64_t *pos, const int64_t *cigar_off, const uint8_t *cigar,
+                         const int32_t *pair_id, int64_t n_pair_ids, const uint8_t *sense, uint8_t strand, const CoverageIO &io)
+{
+    if (n_rows < 0 || n_rows > INT32_MAX - 1 || (n_rows > 0 && (!pos || !cigar_off || !cigar)))
+        return dn::fail(DN_E_INVALID, "dn_read_coverage: bad argument");
+    const int64_t n_bytes = n_rows > 0 ? cigar_off[n_rows] : 0;
+    dn::DeviceBuffer<int64_t> d_pos, d_off;
+    dn::DeviceBuffer<uint8_t> d_cig, d_sense;
+    dn::Stream st;
+    DN_TRY(hipSetDevice(device));
+    DN_TRY(st.create(hipStreamCreate));
+    return dn::synced(st, [&]() -> int {
+        DN_TRY(alloc_padded(d_pos, n_rows)); DN_TRY(alloc_padded(d_off, n_rows + 1)); DN_TRY(alloc_padded(d_cig, n_bytes));
+        if (n_rows > 0) {
+            DN_TRY(hipMemcpyAsync(d_pos, pos, sizeof(int64_t) * (size_t) n_rows, hipMemcpyHostToDevice, st));
+            DN_TRY(hipMemcpyAsync(d_off, cigar_off, sizeof(int64_t) * (size_t) (n_rows + 1), hipMemcpyHostToDevice, st));
+        }
+        if (n_bytes > 0) DN_TRY(hipMemcpyAsync(d_cig, cigar, (size_t) n_bytes, hipMemcpyHostToDevice, st));
+        StrandSel sel;
+        if (strand) {
+            DN_TRY(alloc_padded(d_sense, n_rows));
+            if (n_rows > 0) DN_TRY(hipMemcpyAsync(d_sense, sense, (size_t) n_rows, hipMemcpyHostToDevice, st));
+            sel.sense = d_sense;
+            sel.want = strand;
+        }
+        return coverage_stages(st, paired, n_rows, d_pos, StrCigars{d_off, d_cig}, pair_id, nullptr, n_pair_ids, io, [&](int64_t r) {
+            return std::string((const char *) cigar + cigar_off[r], (size_t) (cigar_off[r + 1] - cigar_off[r]));
+        }, MateBits{}, sel);
+    });
+}
+
 extern "C" int dn_read_coverage(int device, int32_t paired, int64_t n_rows, const int64_t *pos, const int64_t *cigar_off,
                                 const uint8_t *cigar, const int32_t *pair_id, int64_t n_pair_ids,
                                 int64_t chrom_len, int64_t keep_lo, int64_t keep_hi,
@@ -575,26 +632,43 @@ extern "C" int dn_read_coverage(int device, int32_t paired, int64_t n_rows, cons
                                 int64_t *n_isolated_reads, double *device_ms)
 {
     dn::clear_error();
-    if (n_rows < 0 || n_rows > INT32_MAX - 1 || (n_rows > 0 && (!pos || !cigar_off || !cigar)))
-        return dn::fail(DN_E_INVALID, "dn_read_coverage: bad argument");
     COVERAGE_IO;
-    const int64_t n_bytes = n_rows > 0 ? cigar_off[n_rows] : 0;
-    dn::DeviceBuffer<int64_t> d_pos, d_off;
-    dn::DeviceBuffer<uint8_t> d_cig;
-    dn::Stream st;
-    DN_TRY(hipSetDevice(device));
-    DN_TRY(st.create(hipStreamCreate));
-    return dn::synced(st, [&]() -> int {
-        DN_TRY(alloc_padded(d_pos, n_rows)); DN_TRY(alloc_padded(d_off, n_rows + 1)); DN_TRY(alloc_padded(d_cig, n_bytes));
-        if (n_rows > 0) {
-            DN_TRY(hipMemcpyAsync(d_pos, pos, sizeof(int64_t) * (size_t) n_rows, hipMemcpyHostToDevice, st));
-            DN_TRY(hipMemcpyAsync(d_off, cigar_off, sizeof(int64_t) * (size_t) (n_rows + 1), hipMemcpyHostToDevice, st));
-        }
-        if (n_bytes > 0) DN_TRY(hipMemcpyAsync(d_cig, cigar, (size_t) n_bytes, hipMemcpyHostToDevice, st));
-        return coverage_stages(st, paired, n_rows, d_pos, StrCigars{d_off, d_cig}, pair_id, nullptr, n_pair_ids, io, [&](int64_t r) {
-            return std::string((const char *) cigar + cigar_off[r], (size_t) (cigar_off[r + 1] - cigar_off[r]));
-        });
-    });
+    return read_coverage(device, paired, n_rows, pos, cigar_off, cigar, pair_id, n_pair_ids, nullptr, 0, io);
+}
+
+// '+' or '-' as the selector of a stranded call; 0 for anything else
+static uint8_t strand_selector(int32_t strand) { return strand == dn::kSensePlus || strand == dn::kSenseMinus ? (uint8_t) strand : 0; }
+
+extern "C" int dn_read_coverage_strand(int device, int32_t paired, int64_t n_rows, const int64_t *pos, const int64_t *cigar_off,
+                                       const uint8_t *cigar, const int32_t *pair_id, int64_t n_pair_ids, const uint8_t *sense, int32_t strand,
+                                       int64_t chrom_len, int64_t keep_lo, int64_t keep_hi,
+                                       int64_t n_exon, const int64_t *exon_iv,
+                                       int64_t n_groups, const int64_t *group_iv, const int32_t *group_gene_off,
+                                       const int32_t *ol_gene, const int64_t *ol_gene_start0, const int64_t *ol_cov_off,
+                                       const int32_t *ol_exon_off, const int64_t *ol_exon_bounds,
+                                       int64_t n_iso, const int64_t *iso_iv, const int32_t *iso_gene,
+                                       int64_t n_iso_union, const int64_t *iso_union,
+                                       int64_t n_genes, int64_t *counts, int64_t *ol_cov,
+                                       int64_t csr_cap, int64_t *nnz, int32_t *csr_idx, int64_t *csr_val,
+                                       int64_t *n_isolated_reads, double *device_ms)
+{
+    dn::clear_error();
+    if (!strand_selector(strand) || (n_rows > 0 && !sense))
+        return dn::fail(DN_E_INVALID, "dn_read_coverage_strand: bad argument (the sense of every row, and the strand '+' or '-')");
+    for (int64_t r = 0; r < n_rows; r++)
+        if (sense[r] != dn::kSensePlus && sense[r] != dn::kSenseMinus)
+            return dn::fail(DN_E_INVALID, "dn_read_coverage_strand: the sense of row " + std::to_string(r) + " is neither '+' nor '-'");
+    COVERAGE_IO;
+    return read_coverage(device, paired, n_rows, pos, cigar_off, cigar, pair_id, n_pair_ids, sense, strand_selector(strand), io);
+}
+
+extern "C" int dn_read_sense_host(int64_t n, const uint16_t *flag, const uint8_t *name_last, int32_t by_name, int32_t stranded, uint8_t *sense)
+{
+    dn::clear_error();
+    if (n < 0 || (n > 0 && (!flag || !name_last || !sense)) || (stranded != dn::kStrandForward && stranded != dn::kStrandReverse))
+        return dn::fail(DN_E_INVALID, "dn_read_sense_host: bad argument (stranded 1, forward, or 2, reverse)");
+    for (int64_t r = 0; r < n; r++) sense[r] = dn::row_sense(flag[r], name_last[r], by_name != 0, stranded);
+    return DN_OK;
 }
 
 extern "C" int dn_reads_cigar_bounds(int device, int64_t n, const int64_t *pos, const int64_t *cigar_off, const uint8_t *cigar,
@@ -819,6 +893,20 @@ __global__ __launch_bounds__(kNT) void k_bam_write(const uint8_t *__restrict__ w
     }
 }
 
+// A stranded store (dn_bam_rows_set_stranded): the sense of every kept record of the window (dn::row_sense), written to the
+// row k_bam_write gave it.  One lane per record, while the window is resident; by_name: a paired store of the name rule.
+__global__ __launch_bounds__(kNT) void k_bam_sense(const uint8_t *__restrict__ w, int64_t n_bytes, const int64_t *__restrict__ rec_off,
+                                                   int64_t n_rec, const int32_t *__restrict__ keep, const int32_t *__restrict__ rank,
+                                                   int64_t row0, int32_t by_name, int32_t protocol, uint8_t *__restrict__ sense)
+{
+    for (int64_t i = (int64_t) blockIdx.x * kNT + threadIdx.x; i < n_rec; i += (int64_t) gridDim.x * kNT) {
+        BamRec R;
+        if (!keep[i] || !bam_parse(w, n_bytes, rec_off[i], R)) continue;
+        const uint8_t name_last = R.l_name > 1 ? w[R.name() + R.l_name - 2] : 0;      // l_name counts the NUL
+        sense[row0 + rank[i]] = dn::row_sense(R.flag, name_last, by_name != 0, protocol);
+    }
+}
+
 __global__ __launch_bounds__(kNT) void k_bam_keys(int64_t n, const int64_t *__restrict__ name_beg, const int32_t *__restrict__ key_len,
                                                   const uint8_t *__restrict__ names, int32_t width, uint8_t *__restrict__ out)
 {
@@ -866,6 +954,9 @@ struct dn_bam_rows_s {
     dn::GrowBuffer<uint8_t> mapq;
     dn::GrowBuffer<int32_t> next_pos;
     dn::DeviceBuffer<unsigned long long> dropped;
+    // strand-specific counting (dn_bam_rows_set_stranded): the protocol, dn::kStrandNo for none, and the sense of every row
+    int32_t stranded = dn::kStrandNo;
+    dn::GrowBuffer<uint8_t> sense;
     dn::GrowBuffer<int32_t> keep, w_ops, w_name, rank, op_rank, name_rank;
     dn::GrowBuffer<uint32_t> ops;
     dn::GrowBuffer<uint8_t> names, win;
@@ -1085,6 +1176,13 @@ int append_window(dn_bam_rows h, const uint8_t *window, int64_t n_bytes, int64_t
                                (const int32_t *) h->rank.get(), (const int32_t *) h->op_rank.get(), (const int32_t *) h->name_rank.get(), h->n_rows,
                                h->n_ops, h->n_names, O);
             DN_TRY(hipGetLastError());
+            if (h->stranded != dn::kStrandNo) {
+                DN_TRY(h->sense.reserve(rows, n, st));
+                hipLaunchKernelGGL(k_bam_sense, dim3(dn::grid_for(n_rec, kNT, kGridCap)), dim3(kNT), 0, st, (const uint8_t *) h->win.get(), n_bytes,
+                                   (const int64_t *) h->rec_off.get(), n_rec, (const int32_t *) h->keep.get(), (const int32_t *) h->rank.get(), h->n_rows,
+                                   (int32_t) (h->F.paired && !h->F.by_flag), h->stranded, h->sense.get());
+                DN_TRY(hipGetLastError());
+            }
             DN_TRY(hipStreamSynchronize(st));
             h->n_rows += tot[0];
             h->has_pairing = false;
@@ -1384,20 +1482,34 @@ extern "C" int dn_bam_rows_pair(dn_bam_rows h, int32_t *order_out, int32_t *pair
     });
 }
 
-extern "C" int dn_bam_rows_coverage(dn_bam_rows h, const int32_t *order, const int32_t *pair_id, int64_t n_pair_ids,
-                                    int64_t chrom_len, int64_t keep_lo, int64_t keep_hi,
-                                    int64_t n_exon, const int64_t *exon_iv,
-                                    int64_t n_groups, const int64_t *group_iv, const int32_t *group_gene_off,
-                                    const int32_t *ol_gene, const int64_t *ol_gene_start0, const int64_t *ol_cov_off,
-                                    const int32_t *ol_exon_off, const int64_t *ol_exon_bounds,
-                                    int64_t n_iso, const int64_t *iso_iv, const int32_t *iso_gene,
-                                    int64_t n_iso_union, const int64_t *iso_union,
-                                    int64_t n_genes, int64_t *counts, int64_t *ol_cov,
-                                    int64_t csr_cap, int64_t *nnz, int32_t *csr_idx, int64_t *csr_val,
-                                    int64_t *n_isolated_reads, double *device_ms)
+extern "C" int dn_bam_rows_set_stranded(dn_bam_rows h, int32_t stranded)
 {
     dn::clear_error();
-    if (!h) return dn::fail(DN_E_INVALID, "dn_bam_rows_coverage: bad argument");
+    if (!h || (stranded != dn::kStrandNo && stranded != dn::kStrandForward && stranded != dn::kStrandReverse))
+        return dn::fail(DN_E_INVALID, "dn_bam_rows_set_stranded: bad argument (stranded 0, no, 1, forward, or 2, reverse)");
+    if (h->n_rows > 0 && stranded != h->stranded)
+        return dn::fail(DN_E_STATE, "dn_bam_rows_set_stranded: the store already has rows");
+    h->stranded = stranded;
+    return DN_OK;
+}
+
+extern "C" int dn_bam_rows_fetch_sense(dn_bam_rows h, uint8_t *sense)
+{
+    dn::clear_error();
+    if (!h || h->stranded == dn::kStrandNo || (h->n_rows > 0 && !sense))
+        return dn::fail(DN_E_INVALID, "dn_bam_rows_fetch_sense: bad argument (a stranded store)");
+    if (h->n_rows == 0) return DN_OK;
+    DN_TRY(hipSetDevice(h->device));
+    return dn::synced(h->st, [&]() -> int {
+        DN_TRY(hipMemcpyAsync(sense, h->sense, (size_t) h->n_rows, hipMemcpyDeviceToHost, h->st));
+        DN_TRY(hipStreamSynchronize(h->st));
+        return DN_OK;
+    });
+}
+
+// dn_bam_rows_coverage, and with strand != 0 dn_bam_rows_coverage_strand on the rows of that sense
+static int rows_coverage(dn_bam_rows h, uint8_t strand, const int32_t *order, const int32_t *pair_id, int64_t n_pair_ids, const CoverageIO &io)
+{
     const bool resident = h->F.paired && h->n_rows > 0 && !order && !pair_id && h->has_pairing;     // the pairing of dn_bam_rows_pair
     if (h->F.paired && h->n_rows > 0 && !order && !resident) return dn::fail(DN_E_INVALID, "dn_bam_rows_coverage: bad argument");
     if (h->F.by_flag && h->n_rows > 0 && !resident)
@@ -1405,7 +1517,8 @@ extern "C" int dn_bam_rows_coverage(dn_bam_rows h, const int32_t *order, const i
     MateBits mate_bits;
     if (h->F.by_flag && resident) { mate_bits.flag = h->flag; mate_bits.order = h->pair_order; }
     if (h->has_no_cigar) return dn::fail(DN_E_INVALID, "read " + h->no_cigar + " has no CIGAR string");     // the reference's CIGAR regex on cigarstring None
-    COVERAGE_IO;
+    StrandSel sel;
+    if (strand) { sel.sense = h->sense; sel.want = strand; }
     const int64_t n = h->n_rows;
     hipStream_t st = h->st;
     std::vector<int32_t> h_order;
@@ -1425,12 +1538,14 @@ extern "C" int dn_bam_rows_coverage(dn_bam_rows h, const int32_t *order, const i
                                h->n_op.get(), g_pos.get(), g_beg.get(), g_cnt.get());
             DN_TRY(hipGetLastError());
             p_pos = g_pos; p_beg = g_beg; p_cnt = g_cnt;
-        } else if (resident) {                                  // the same rows in the store's own order: nothing to check or upload
+            sel.order = d_order;
+        } else if (resident) {                                // the same rows in the store's own order: nothing to check or upload
             DN_TRY(alloc_padded(g_pos, n)); DN_TRY(alloc_padded(g_beg, n)); DN_TRY(alloc_padded(g_cnt, n));
             hipLaunchKernelGGL(k_bam_gather, dim3(dn::grid_for(n, kNT, kGridCap)), dim3(kNT), 0, st, n, (const int32_t *) h->pair_order.get(), h->pos.get(),
                                h->op_beg.get(), h->n_op.get(), g_pos.get(), g_beg.get(), g_cnt.get());
             DN_TRY(hipGetLastError());
             p_pos = g_pos; p_beg = g_beg; p_cnt = g_cnt;
+            sel.order = h->pair_order;
         }
         return coverage_stages(st, h->F.paired, n, p_pos, BamCigars{p_beg, p_cnt, h->ops}, pair_id, resident ? h->pair_id.get() : nullptr,
                                resident ? h->n_pair_ids : n_pair_ids, io, [&](int64_t r) {
@@ -1457,8 +1572,45 @@ extern "C" int dn_bam_rows_coverage(dn_bam_rows h, const int32_t *order, const i
                 if (hipMemcpy(&name[0], h->names + nb, (size_t) nl, hipMemcpyDeviceToHost) != hipSuccess) name = "?";
             }
             return cigar_string(ops.data(), (int64_t) ops.size()) + " (read " + name + ")";
-        }, mate_bits);
+        }, mate_bits, sel);
     });
+}
+
+extern "C" int dn_bam_rows_coverage(dn_bam_rows h, const int32_t *order, const int32_t *pair_id, int64_t n_pair_ids,
+                                    int64_t chrom_len, int64_t keep_lo, int64_t keep_hi,
+                                    int64_t n_exon, const int64_t *exon_iv,
+                                    int64_t n_groups, const int64_t *group_iv, const int32_t *group_gene_off,
+                                    const int32_t *ol_gene, const int64_t *ol_gene_start0, const int64_t *ol_cov_off,
+                                    const int32_t *ol_exon_off, const int64_t *ol_exon_bounds,
+                                    int64_t n_iso, const int64_t *iso_iv, const int32_t *iso_gene,
+                                    int64_t n_iso_union, const int64_t *iso_union,
+                                    int64_t n_genes, int64_t *counts, int64_t *ol_cov,
+                                    int64_t csr_cap, int64_t *nnz, int32_t *csr_idx, int64_t *csr_val,
+                                    int64_t *n_isolated_reads, double *device_ms)
+{
+    dn::clear_error();
+    if (!h) return dn::fail(DN_E_INVALID, "dn_bam_rows_coverage: bad argument");
+    COVERAGE_IO;
+    return rows_coverage(h, 0, order, pair_id, n_pair_ids, io);
+}
+
+extern "C" int dn_bam_rows_coverage_strand(dn_bam_rows h, int32_t strand, const int32_t *order, const int32_t *pair_id, int64_t n_pair_ids,
+                                           int64_t chrom_len, int64_t keep_lo, int64_t keep_hi,
+                                           int64_t n_exon, const int64_t *exon_iv,
+                                           int64_t n_groups, const int64_t *group_iv, const int32_t *group_gene_off,
+                                           const int32_t *ol_gene, const int64_t *ol_gene_start0, const int64_t *ol_cov_off,
+                                           const int32_t *ol_exon_off, const int64_t *ol_exon_bounds,
+                                           int64_t n_iso, const int64_t *iso_iv, const int32_t *iso_gene,
+                                           int64_t n_iso_union, const int64_t *iso_union,
+                                           int64_t n_genes, int64_t *counts, int64_t *ol_cov,
+                                           int64_t csr_cap, int64_t *nnz, int32_t *csr_idx, int64_t *csr_val,
+                                           int64_t *n_isolated_reads, double *device_ms)
+{
+    dn::clear_error();
+    if (!h || h->stranded == dn::kStrandNo || !strand_selector(strand))
+        return dn::fail(DN_E_INVALID, "dn_bam_rows_coverage_strand: bad argument (a stranded store, and the strand '+' or '-')");
+    COVERAGE_IO;
+    return rows_coverage(h, strand_selector(strand), order, pair_id, n_pair_ids, io);
 }
 
 extern "C" int dn_bam_cigar_bounds(int device, int64_t n, const int64_t *pos, const int64_t *op_off, const uint32_t *ops,

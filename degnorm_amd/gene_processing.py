@@ -23,12 +23,17 @@ from .utils import subset_to_chrom
 
 class GeneAnnotationProcessor(object):
 
-    def __init__(self, annotation_file, chroms=None, verbose=True):
+    def __init__(self, annotation_file, chroms=None, verbose=True, strand=False):
         """
         :param annotation_file: str .gtf, .gff3 or .gff file
         :param chroms: str or list of str chromosome names: subset the annotation to them
         :param verbose: bool write progress to the logger?
+        :param strand: bool strand-specific counting (include/degnorm_amd.h): keep the `strand` column of the exon lines.  A
+        gene is on '+' or '-' when all its exon rows say so; a gene with '.', '?' or both strands among its rows is unstranded
+        and is left out, with one warning that gives their number and up to ten names; self.unstranded_genes keeps them all.
         """
+        self.strand = bool(strand)
+        self.unstranded_genes = []
         self.filename = annotation_file
         self.verbose = verbose
         self.chroms = chroms
@@ -40,7 +45,7 @@ class GeneAnnotationProcessor(object):
     def load(self):
         """The exon rows of the file (the get_data of the loader its extension picks), subset to self.chroms when given."""
         self.loader = annotation_loader(self.filename)
-        return self._subset(self.loader.get_data())
+        return self._subset(self.loader.get_data(strand=True) if self.strand else self.loader.get_data())
 
     def _subset(self, exon_df):
         if self.chroms:
@@ -72,16 +77,32 @@ class GeneAnnotationProcessor(object):
     def process(self, exon_df):
         """The steps of run() after load(): multi-chromosome genes out, gene outlines joined on, duplicates dropped."""
         exon_df = self.remove_multichrom_genes(exon_df).drop_duplicates()
+        if self.strand:
+            exon_df = self.stranded_genes(exon_df)
         gene_df = self.gene_outline(exon_df)
         exon_df = exon_df.merge(gene_df, on=['chr', 'gene']).drop_duplicates()
         return exon_df
+
+    def stranded_genes(self, exon_df):
+        """The exon rows of the genes whose rows all say '+' or all say '-'; the other genes go to self.unstranded_genes."""
+        per_gene = exon_df.groupby('gene', sort=False)['strand'].agg(['first', 'nunique'])
+        ok = (per_gene['nunique'] == 1) & per_gene['first'].isin(['+', '-'])
+        self.unstranded_genes = per_gene.index[~ok.values].tolist()
+        if self.unstranded_genes:
+            logging.warning('{0} genes without a single strand (., ? or both strands among their exon lines) are left out of the '
+                            'stranded run: {1}{2}'.format(len(self.unstranded_genes), ', '.join(self.unstranded_genes[:10]),
+                                                          ', ...' if len(self.unstranded_genes) > 10 else ''))
+        if exon_df.empty:
+            return exon_df
+        return exon_df[exon_df['gene'].isin(per_gene.index[ok.values])]
 
     def run(self):
         """
         Load the annotation file, remove the genes that occur on several chromosomes, outline every gene and drop
         duplicates (reference gene_processing.py:89-123).
 
-        :return: DataFrame with `chr`, `start`, `end`, `gene`, `gene_start`, `gene_end`: the exons, in file order.
+        :return: DataFrame with `chr`, `start`, `end`, `gene`, `gene_start`, `gene_end`: the exons, in file order; with
+        strand=True also `strand`, '+' or '-', the strand of the row's gene.
         """
         if self.verbose:
             logging.info('Loading genome annotation file {0}...'.format(self.filename))

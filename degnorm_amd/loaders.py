@@ -40,12 +40,14 @@ WINDOW_BYTES = 256 << 20            # as NativeBamReadsProcessor (bam.py)
 _COMPARE_BYTES = 32 << 20           # bytes held at a time when the names of a hash group are compared
 _KINDS = {1: 'must have the 9 mandatory .gtf columns.\nRead more at https://useast.ensembl.org/info/website/upload/gff.html',
           2: 'is an exon record without a usable gene_name or gene_id identifier tag.',
-          3: 'is an exon record whose start or end is not an integer.'}
+          3: 'is an exon record whose start or end is not an integer.',
+          4: 'is an exon record whose strand (column 7) is not one of + - . ?'}
 _GFF3_KINDS = {1: 'must have the 9 mandatory .gff3 columns.\nRead more at https://github.com/The-Sequence-Ontology/Specifications/blob/master/gff3.md',
                2: 'is an exon record without a usable gene_name, gene, Parent or gene_id attribute.',
                3: 'is an exon record whose start or end is not an integer.',
                4: 'is an exon record whose chain of Parent attributes names an ID that no record has.',
-               5: 'is an exon record whose chain of Parent attributes does not reach a gene within 8 records.'}
+               5: 'is an exon record whose chain of Parent attributes does not reach a gene within 8 records.',
+               6: 'is an exon record whose strand (column 7) is not one of + - . ?'}
 # the columns of an exon row, in the order the C entries of both scanners take them
 _EXON_COLS = (('line', np.int64), ('chr_beg', np.int64), ('chr_len', np.int32), ('chr_hash', np.uint64), ('start', np.int64),
               ('end', np.int64), ('gene_beg', np.int64), ('gene_len', np.int32), ('gene_hash', np.uint64))
@@ -87,11 +89,18 @@ class Loader(object):
         raise NotImplementedError('get_data not yet implemented for {0}'.format(self.__class__.__name__))
 
 
-def scan_window(buf, device=None):
+def _strand_col(cap, strand):
+    """The strand column of `cap` rows for a _strand entry to fill, and its argument: ([array], [pointer]), or two empty lists."""
+    col = [np.empty(cap, dtype=np.uint8)] if strand else []
+    return col, [_lib._p(c, ctypes.c_uint8) for c in col]
+
+
+def scan_window(buf, device=None, strand=False):
     """
     dn_gtf_scan on the bytes of one window: (number of lines, dict of the kept lines' columns -- `line` 1-based within the
     window, `chr_beg`, `chr_len`, `chr_hash`, `start`, `end`, `gene_beg`, `gene_len`, `gene_hash` -- (error line, error kind)
-    or None, copy-in ms, device ms).
+    or None, copy-in ms, device ms).  strand=True: dn_gtf_scan_strand, which adds the column `strand` (uint8: field seven of
+    the line, one of + - . ?) and the error kind 4 for a field that is none of them.
     """
     lib = _lib.load()
     a = np.frombuffer(buf, dtype=np.uint8)
@@ -100,10 +109,13 @@ def scan_window(buf, device=None):
     i64 = ctypes.c_int64
     n_lines, n_rows, err_line, err_kind = i64(0), i64(0), i64(0), ctypes.c_int32(0)
     copy_ms, dev_ms = ctypes.c_double(0.0), ctypes.c_double(0.0)
-    rc = lib.dn_gtf_scan(_device(device), _lib._p(a, ctypes.c_uint8), a.size, cap, ctypes.byref(n_lines), ctypes.byref(n_rows),
-                         *(col_args + [ctypes.byref(err_line), ctypes.byref(err_kind), ctypes.byref(copy_ms), ctypes.byref(dev_ms)]))
+    s_col, s_arg = _strand_col(cap, strand)
+    rc = (lib.dn_gtf_scan_strand if strand else lib.dn_gtf_scan)(
+        _device(device), _lib._p(a, ctypes.c_uint8), a.size, cap, ctypes.byref(n_lines), ctypes.byref(n_rows),
+        *(col_args + s_arg + [ctypes.byref(err_line), ctypes.byref(err_kind), ctypes.byref(copy_ms), ctypes.byref(dev_ms)]))
     _lib._check(rc, 'dn_gtf_scan')
     n = int(n_rows.value)
+    cols.update(strand=s_col[0]) if strand else None
     return int(n_lines.value), {k: v[:n] for k, v in cols.items()}, _error(err_line, err_kind), float(copy_ms.value), float(dev_ms.value)
 
 
@@ -183,10 +195,11 @@ class GeneAnnotationLoader(Loader):
         self.device = device
         self.timing = {}
 
-    def exon_codes(self):
+    def exon_codes(self, strand=False):
         """
         The exon lines of the file in file order, names as codes: (chr code, start, end, gene code -- int64 arrays --,
-        chromosome names, gene names: lists of str indexed by code, in order of first appearance).
+        chromosome names, gene names: lists of str indexed by code, in order of first appearance).  strand=True: a seventh
+        entry, the strand byte of every line (uint8: + - . ?).
         """
         chr_table, gene_table = {}, {}
         parts = []
@@ -195,7 +208,7 @@ class GeneAnnotationLoader(Loader):
         t0 = time.perf_counter()
         for win in iter_windows(self.filename, self.window_bytes, _device(self.device)):
             t['read_s'] += time.perf_counter() - t0
-            n_lines, cols, err, copy_ms, dev_ms = scan_window(win, self.device)
+            n_lines, cols, err, copy_ms, dev_ms = scan_window(win, self.device, strand)
             t['copy_ms'] += copy_ms
             t['device_ms'] += dev_ms
             t['bytes'] += len(win)
@@ -204,28 +217,39 @@ class GeneAnnotationLoader(Loader):
             a = np.frombuffer(win, dtype=np.uint8)
             parts.append((intern_spans(a, cols['chr_beg'], cols['chr_len'].astype(np.int64), cols['chr_hash'], chr_table),
                           cols['start'], cols['end'],
-                          intern_spans(a, cols['gene_beg'], cols['gene_len'].astype(np.int64), cols['gene_hash'], gene_table)))
+                          intern_spans(a, cols['gene_beg'], cols['gene_len'].astype(np.int64), cols['gene_hash'], gene_table),
+                          cols['strand'] if strand else None))
             line_base += n_lines
             t0 = time.perf_counter()
         t['read_s'] += time.perf_counter() - t0
         t['lines'] = line_base
         cat = [np.concatenate([p[k] for p in parts]) if parts else np.zeros(0, dtype=np.int64) for k in range(4)]
         names = [[b.decode('utf-8', 'replace') for b in tab] for tab in (chr_table, gene_table)]     # dicts keep insertion order
+        if strand:
+            return cat[0], cat[1], cat[2], cat[3], names[0], names[1], np.concatenate([p[4] for p in parts]) if parts else np.zeros(0, np.uint8)
         return cat[0], cat[1], cat[2], cat[3], names[0], names[1]
 
-    def get_data(self):
+    def get_data(self, strand=False):
         """
         The reference's exon table (loaders.py:114-168): columns `chr` (str), `start` (int64), `end` (int64), `gene` (str),
         one row per exon line of the file, duplicates of the four columns dropped (the first one stays), RangeIndex.
         Malformed input raises ValueError naming the file, the line and what is wrong with it.
+        strand=True (strand-specific counting): a fifth column `strand`, field seven of the exon line itself, '+', '-', '.'
+        or '?'; any other field is then a malformed line.  Duplicates are rows equal in all five columns.
         """
         from pandas import DataFrame
-        chr_code, start, end, gene_code, chr_names, gene_names = self.exon_codes()
-        codes = DataFrame({'chr': chr_code, 'start': start, 'end': end, 'gene': gene_code})
-        keep = ~codes.duplicated().values
-        return DataFrame({'chr': np.array(chr_names, dtype=object)[chr_code[keep]] if chr_names else np.zeros(0, dtype=object),
-                          'start': start[keep].astype(np.int64), 'end': end[keep].astype(np.int64),
-                          'gene': np.array(gene_names, dtype=object)[gene_code[keep]] if gene_names else np.zeros(0, dtype=object)})
+        codes = self.exon_codes(strand)
+        chr_code, start, end, gene_code, chr_names, gene_names = codes[:6]
+        cols = {'chr': chr_code, 'start': start, 'end': end, 'gene': gene_code}
+        if strand:
+            cols['strand'] = codes[6]
+        keep = ~DataFrame(cols).duplicated().values
+        out = {'chr': np.array(chr_names, dtype=object)[chr_code[keep]] if chr_names else np.zeros(0, dtype=object),
+               'start': start[keep].astype(np.int64), 'end': end[keep].astype(np.int64),
+               'gene': np.array(gene_names, dtype=object)[gene_code[keep]] if gene_names else np.zeros(0, dtype=object)}
+        if strand:
+            out['strand'] = np.array([chr(c) for c in range(128)], dtype=object)[codes[6][keep]]
+        return DataFrame(out)
 
 
 class Gff3Scan(object):
@@ -252,11 +276,12 @@ class Gff3Scan(object):
             self.lib.dn_gff3_close(self.h)
             self.h = ctypes.c_void_p(None)
 
-    def window(self, buf):
+    def window(self, buf, strand=False):
         """
         dn_gff3_window on the next piece of the text: (dict of the exon rows' columns -- `line` 1-based in the file, spans as
         offsets in the file, `pending` 1 where gene_* is a Parent still to resolve --, (error line, error kind) or None,
         copy-in ms, device ms).  self.fasta_line becomes the line of `##FASTA` once a window held it: feed no more then.
+        strand=True: dn_gff3_window_strand, which adds the column `strand` (uint8: field seven of the exon line) and error kind 6.
         """
         a = np.frombuffer(buf, dtype=np.uint8)
         cap = a.size // 20 + 1
@@ -265,15 +290,19 @@ class Gff3Scan(object):
         i64 = ctypes.c_int64
         n_lines, n_rows, fasta, err_line, err_kind = i64(0), i64(0), i64(0), i64(0), ctypes.c_int32(0)
         copy_ms, dev_ms = ctypes.c_double(0.0), ctypes.c_double(0.0)
-        rc = self.lib.dn_gff3_window(self.h, _lib._p(a, ctypes.c_uint8), a.size, cap, ctypes.byref(n_lines), ctypes.byref(n_rows),
-                                     *(col_args + [_lib._p(pending, ctypes.c_uint8), ctypes.byref(fasta), ctypes.byref(err_line),
-                                                   ctypes.byref(err_kind), ctypes.byref(copy_ms), ctypes.byref(dev_ms)]))
+        s_col, s_arg = _strand_col(cap, strand)
+        rc = (self.lib.dn_gff3_window_strand if strand else self.lib.dn_gff3_window)(
+            self.h, _lib._p(a, ctypes.c_uint8), a.size, cap, ctypes.byref(n_lines), ctypes.byref(n_rows),
+            *(col_args + [_lib._p(pending, ctypes.c_uint8)] + s_arg + [ctypes.byref(fasta), ctypes.byref(err_line),
+                                                                       ctypes.byref(err_kind), ctypes.byref(copy_ms), ctypes.byref(dev_ms)]))
         _lib._check(rc, 'dn_gff3_window')
         n = int(n_rows.value)
         self.lines += int(n_lines.value)
         self.fasta_line = int(fasta.value)
         cols = {k: v[:n] for k, v in cols.items()}
         cols['pending'] = pending[:n]
+        if strand:
+            cols['strand'] = s_col[0][:n]
         return cols, _error(err_line, err_kind), float(copy_ms.value), float(dev_ms.value)
 
     def resolve(self, line, par_beg, par_len, par_hash):
@@ -302,32 +331,37 @@ def _resolve_pending(scan, cols):
     return err, ms, int(idx.size)
 
 
-def gff3_scan(data, device=None, hash_bits=64, stats=None):
+def gff3_scan(data, device=None, hash_bits=64, stats=None, strand=False):
     """
     The GFF3 rule on the bytes of a whole annotation: (number of lines, dict of the exon rows' columns in file order -- `line`
     1-based, `chr_beg`, `chr_len`, `chr_hash`, `start`, `end`, and `gene_beg`, `gene_len`, `gene_hash` of the resolved gene
     name --, (error line, error kind) or None; with an error there are no rows).  device=None runs the host build
     (dn_gff3_scan_host), a device index the device build as one window.  hash_bits masks the hashes of IDs and Parents in
     both builds: with few bits many IDs share a hash, and the result must not change.  stats (dict): `nodes`, `walked_exons`.
+    strand=True: the _strand entries of both builds, which add the column `strand` (uint8: field seven of the exon line, one of
+    + - . ?) and the error kind 6 for an exon line whose field is none of them.
     """
     a = np.frombuffer(data, dtype=np.uint8)
     stats = {} if stats is None else stats
     if a.size == 0:
         stats.update(nodes=0, walked_exons=0)
-        return 0, _exon_cols(0)[0], None
+        return 0, dict(_exon_cols(0)[0], **({'strand': np.zeros(0, np.uint8)} if strand else {})), None
     if device is None:
         lib = _lib.load()
         cap = a.size // 20 + 1
         cols, col_args = _exon_cols(cap)
         i64 = ctypes.c_int64
         n_lines, n_rows, n_nodes, n_walked, err_line, err_kind = i64(0), i64(0), i64(0), i64(0), i64(0), ctypes.c_int32(0)
-        rc = lib.dn_gff3_scan_host(_lib._p(a, ctypes.c_uint8), a.size, int(hash_bits), cap, ctypes.byref(n_lines), ctypes.byref(n_rows),
-                                   *(col_args + [ctypes.byref(n_nodes), ctypes.byref(n_walked), ctypes.byref(err_line), ctypes.byref(err_kind)]))
+        s_col, s_arg = _strand_col(cap, strand)
+        rc = (lib.dn_gff3_scan_host_strand if strand else lib.dn_gff3_scan_host)(
+            _lib._p(a, ctypes.c_uint8), a.size, int(hash_bits), cap, ctypes.byref(n_lines), ctypes.byref(n_rows),
+            *(col_args + s_arg + [ctypes.byref(n_nodes), ctypes.byref(n_walked), ctypes.byref(err_line), ctypes.byref(err_kind)]))
         _lib._check(rc, 'dn_gff3_scan_host')
+        cols.update(strand=s_col[0]) if strand else None
         stats.update(nodes=int(n_nodes.value), walked_exons=int(n_walked.value))
         return int(n_lines.value), {k: v[:int(n_rows.value)] for k, v in cols.items()}, _error(err_line, err_kind)
     with Gff3Scan(a.size, device, hash_bits) as scan:
-        cols, err, _, _ = scan.window(a)
+        cols, err, _, _ = scan.window(a, strand)
         walked = 0
         if err is None:
             err, _, walked = _resolve_pending(scan, cols)
@@ -345,15 +379,16 @@ class Gff3AnnotationLoader(GeneAnnotationLoader):
     def _raise(self, err):
         raise ValueError('File {0}, line {1} {2}'.format(self.filename, err[0], _GFF3_KINDS[err[1]]))
 
-    def exon_codes(self):
+    def exon_codes(self, strand=False):
         """As GeneAnnotationLoader.exon_codes.  The text stays on the device until every exon has its gene."""
         t = self.timing = {'read_s': 0.0, 'copy_ms': 0.0, 'device_ms': 0.0, 'resolve_ms': 0.0, 'bytes': 0, 'lines': 0, 'nodes': 0,
                            'walked_exons': 0}
         zipped = gz.is_gz(self.filename)             # the text's size: from a first scan of the .gz file, not from its ISIZE
         size = gz.inflated_size(self.filename, _device(self.device)) if zipped else os.path.getsize(self.filename)
         empty = np.zeros(0, dtype=np.int64)
+        none = (empty, empty, empty, empty, [], []) + ((np.zeros(0, np.uint8),) if strand else ())
         if size == 0:
-            return empty, empty, empty, empty, [], []
+            return none
         parts, text = [], []
         with Gff3Scan(size, self.device) as scan:
             t0 = time.perf_counter()
@@ -361,7 +396,7 @@ class Gff3AnnotationLoader(GeneAnnotationLoader):
                 t['read_s'] += time.perf_counter() - t0
                 if zipped:
                     text.append(win)
-                cols, err, copy_ms, dev_ms = scan.window(win)
+                cols, err, copy_ms, dev_ms = scan.window(win, strand)
                 t['copy_ms'] += copy_ms
                 t['device_ms'] += dev_ms
                 t['bytes'] += len(win)
@@ -375,7 +410,7 @@ class Gff3AnnotationLoader(GeneAnnotationLoader):
             t['lines'] = scan.lines
             cols = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]} if parts else None
             if cols is None or cols['line'].size == 0:
-                return empty, empty, empty, empty, [], []
+                return none
             err, t['resolve_ms'], t['walked_exons'] = _resolve_pending(scan, cols)
             t['nodes'] = scan.nodes
             if err is not None:
@@ -385,7 +420,7 @@ class Gff3AnnotationLoader(GeneAnnotationLoader):
         chr_code = intern_spans(a, cols['chr_beg'], cols['chr_len'].astype(np.int64), cols['chr_hash'], chr_table)
         gene_code = intern_spans(a, cols['gene_beg'], cols['gene_len'].astype(np.int64), cols['gene_hash'], gene_table)
         names = [[b.decode('utf-8', 'replace') for b in tab] for tab in (chr_table, gene_table)]
-        return chr_code, cols['start'], cols['end'], gene_code, names[0], names[1]
+        return (chr_code, cols['start'], cols['end'], gene_code, names[0], names[1]) + ((cols['strand'],) if strand else ())
 
 
 ANNOTATION_LOADERS = (('.gtf', GeneAnnotationLoader), ('.gff3', Gff3AnnotationLoader), ('.gff', Gff3AnnotationLoader),

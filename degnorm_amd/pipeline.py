@@ -15,7 +15,7 @@ import shutil
 
 import numpy as np
 
-from .bam import NativeBamReadsProcessor, check_read_options
+from .bam import NativeBamReadsProcessor, check_read_options, check_stranded
 from .coverage_merge import merge_coverage, merge_read_counts
 from .gene_processing import GeneAnnotationProcessor, get_gene_overlap_structure
 from .utils import subset_to_chrom
@@ -24,7 +24,7 @@ from .warm_start import select_genes
 
 def prepare_inputs(bam_files, bai_files, genome_annotation, output_dir, downsample_rate=1, minimax_coverage=0,
                    unique_alignment=True, n_jobs=1, verbose=True, device=None, inflate='host', frame='host', verify=False,
-                   pair='host', pairing='name', exclude_flags=0, require_flags=0, min_mapq=0):
+                   pair='host', pairing='name', exclude_flags=0, require_flags=0, min_mapq=0, stranded='no'):
     """
     The reference's .bam preprocessing path and gene filter (__main__.py:56-247): chromosomes common to every .bam header and
     the annotation, per-sample coverage and read counts, their merge (coverage matrices pickled per chromosome into
@@ -33,11 +33,15 @@ def prepare_inputs(bam_files, bai_files, genome_annotation, output_dir, downsamp
     (each 'host' or 'device'); verify: check every BGZF block read against the CRC32 of its trailer; pair: where the mates of
     paired-end files are paired ('host': the reference's order; 'device': on the GPU, equal names in file order).  pairing
     ('name', 'flag' or 'auto'), exclude_flags, require_flags, min_mapq: which records form a fragment and which are dropped
-    first (NativeBamReadsProcessor); a bad value is a ValueError before any file is opened.
+    first (NativeBamReadsProcessor); a bad value is a ValueError before any file is opened.  stranded ('no', 'forward' or
+    'reverse'; include/degnorm_amd.h, "Strand-specific counting"): count reads by strand -- the annotation keeps its strand
+    column, genes without a single strand are left out, every chromosome is counted per strand, the tables and
+    gene_exon_metadata.csv carry `strand`, and the genes of a chromosome come '+' first, then '-'.
 
     :return: (gene_cov_dict, read_count_df, genes_df, exon_df, sample_ids)
     """
     check_read_options(pairing, exclude_flags, require_flags, min_mapq)
+    by_strand = check_stranded(stranded) != 'no'
     chroms = list()
     for bam_file, bai_file in zip(bam_files, bai_files):
         header = NativeBamReadsProcessor(bam_file, index_file=bai_file, verbose=False, verify=verify).header
@@ -45,16 +49,19 @@ def prepare_inputs(bam_files, bai_files, genome_annotation, output_dir, downsamp
         chroms = new_chroms if not chroms else np.intersect1d(chroms, new_chroms).tolist()
 
     logging.info('Begin genome annotation file processing...')
-    exon_df = GeneAnnotationProcessor(genome_annotation, verbose=verbose, chroms=chroms).run()
+    exon_df = GeneAnnotationProcessor(genome_annotation, verbose=verbose, chroms=chroms, **({'strand': True} if by_strand else {})).run()
     chroms = np.intersect1d(chroms, exon_df.chr.unique()).tolist()
     exon_df = exon_df[exon_df.chr.isin(chroms)]
-    genes_df = exon_df[['chr', 'gene', 'gene_start', 'gene_end']].drop_duplicates().reset_index(drop=True)
+    genes_df = exon_df[['chr', 'gene', 'gene_start', 'gene_end'] + (['strand'] if by_strand else [])].drop_duplicates().reset_index(drop=True)
     logging.info('Found {0} chromosomes in intersection of all experiments and gene annotation data:\n'
                  '\t{1}'.format(len(chroms), ', '.join(chroms)))
 
     gene_overlap_dict = {chrom: get_gene_overlap_structure(subset_to_chrom(genes_df, chrom=chrom)) for chrom in chroms}
-    n_overlap = sum(len(g) for d in gene_overlap_dict.values() for g in d['overlap_genes'])
-    n_isolated = sum(len(d['isolated_genes']) for d in gene_overlap_dict.values())
+    # a stranded run counts each strand's genes with their own structure (the reader builds it again per chromosome): so is the rate
+    counted = [get_gene_overlap_structure(subset_to_chrom(genes_df[genes_df['strand'] == s], chrom=chrom)) for chrom in chroms
+               for s in ('+', '-')] if by_strand else list(gene_overlap_dict.values())
+    n_overlap = sum(len(g) for d in counted for g in d['overlap_genes'])
+    n_isolated = sum(len(d['isolated_genes']) for d in counted)
     logging.info('Rate of gene overlap: {0} / {1}'.format(n_overlap, n_isolated + n_overlap))
 
     sample_ids = list()
@@ -63,7 +70,7 @@ def prepare_inputs(bam_files, bai_files, genome_annotation, output_dir, downsamp
         reader = NativeBamReadsProcessor(bam_file, index_file=bai_file, chroms=chroms, n_jobs=n_jobs, output_dir=output_dir,
                                          unique_alignment=unique_alignment, verbose=verbose, inflate=inflate, frame=frame,
                                          verify=verify, pair=pair, pairing=pairing, exclude_flags=exclude_flags,
-                                         require_flags=require_flags, min_mapq=min_mapq)
+                                         require_flags=require_flags, min_mapq=min_mapq, **({'stranded': stranded} if by_strand else {}))
         sample_ids.append(reader.sample_id)
         reader.coverage_read_counts(gene_overlap_dict, gene_df=genes_df, exon_df=exon_df)
 
@@ -93,11 +100,12 @@ def prepare_inputs(bam_files, bai_files, genome_annotation, output_dir, downsamp
 
 def run_pipeline(bam_files, bai_files, genome_annotation, output_dir, degnorm_iter=5, nmf_iter=100, downsample_rate=1,
                  minimax_coverage=0, skip_baseline_selection=False, unique_alignment=True, n_jobs=1, verbose=True, device=None,
-                 inflate='host', frame='host', verify=False, pair='host', pairing='name', exclude_flags=0, require_flags=0, min_mapq=0):
+                 inflate='host', frame='host', verify=False, pair='host', pairing='name', exclude_flags=0, require_flags=0, min_mapq=0,
+                 stranded='no'):
     """
     DegNorm on .bam files and a .gtf or .gff3 annotation, results written to output_dir (an existing directory).  verify: check every
     BGZF block read against the CRC32 of its trailer (ValueError naming the file and the block).  pairing, exclude_flags,
-    require_flags, min_mapq: as for prepare_inputs.
+    require_flags, min_mapq, stranded: as for prepare_inputs.
 
     :return: (fitted GeneNMFOA, estimates, gene_cov_dict, read_count_df, genes_df, exon_df, sample_ids)
     """
@@ -105,7 +113,8 @@ def run_pipeline(bam_files, bai_files, genome_annotation, output_dir, degnorm_it
     gene_cov_dict, read_count_df, genes_df, exon_df, sample_ids = prepare_inputs(
         bam_files, bai_files, genome_annotation, output_dir, downsample_rate=downsample_rate, minimax_coverage=minimax_coverage,
         unique_alignment=unique_alignment, n_jobs=n_jobs, verbose=verbose, device=device, inflate=inflate, frame=frame,
-        verify=verify, pair=pair, pairing=pairing, exclude_flags=exclude_flags, require_flags=require_flags, min_mapq=min_mapq)
+        verify=verify, pair=pair, pairing=pairing, exclude_flags=exclude_flags, require_flags=require_flags, min_mapq=min_mapq,
+        stranded=stranded)
     logging.info('RNA-seq sample identifiers: \n\t' + ', '.join(sample_ids))
     logging.info('DegNorm will run on {0} genes, downsampling rate = 1 / {1}, {2} baseline selection.'
                  .format(len(gene_cov_dict), downsample_rate, 'without' if skip_baseline_selection else 'with'))

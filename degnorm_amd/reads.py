@@ -186,11 +186,66 @@ def check_coverage_call(rc, what):
     _lib._check(rc, what)
 
 
-def device_read_coverage(pos, off, cig, pair_id, n_ids, ann, paired, device=None):
+STRANDED = ('no', 'forward', 'reverse')
+STRANDS = ('+', '-')
+
+
+def check_stranded(stranded):
+    """ValueError unless stranded is 'no', 'forward' or 'reverse' (the rule: include/degnorm_amd.h, "Strand-specific counting")."""
+    if not isinstance(stranded, str) or stranded not in STRANDED:
+        raise ValueError('stranded must be {0}, not {1!r}'.format(' or '.join(repr(m) for m in STRANDED), stranded))
+    return stranded
+
+
+def check_strand(strand):
+    """ValueError unless strand is '+' or '-'; its byte."""
+    if not isinstance(strand, str) or strand not in STRANDS:
+        raise ValueError("strand must be '+' or '-', not {0!r}".format(strand))
+    return ord(strand)
+
+
+def row_sense(flag, names, by_name, stranded):
+    """
+    The sense ('+' / '-') of rows with these FLAGs and names under protocol `stranded` ('forward' or 'reverse'), by the
+    library's host build of the record rule (dn_read_sense_host; no device needed).  by_name: the rows are those of a store
+    paired by the name rule, where a name ending in '2' also marks a last mate.
+    """
+    if check_stranded(stranded) == 'no':
+        raise ValueError("rows have a sense under 'forward' or 'reverse' only")
+    flag = np.ascontiguousarray(flag, dtype=np.uint16).reshape(-1)
+    n = len(flag)
+    if len(names) != n:
+        raise ValueError('row_sense: one name per FLAG')
+    last = np.array([(x if isinstance(x, bytes) else str(x).encode('ascii', 'replace'))[-1:] or b'\0' for x in names] or [b'\0'],
+                    dtype='S1').view(np.uint8)
+    out = np.zeros(max(n, 1), dtype=np.uint8)
+    f = flag if n else np.zeros(1, np.uint16)
+    _lib._check(_lib.load().dn_read_sense_host(n, _ptr(f, ctypes.c_uint16), _ptr(last, ctypes.c_uint8), 1 if by_name else 0,
+                                               STRANDED.index(stranded), _ptr(out, ctypes.c_uint8)), 'dn_read_sense_host')
+    return [chr(c) for c in out[:n].tolist()]
+
+
+def pack_sense(sense, n_rows):
+    """The per-row sense column ('+' / '-' strings, or their bytes) as the uint8 array dn_read_coverage_strand takes."""
+    a = np.asarray(sense)
+    if a.dtype.kind in 'US' or a.dtype == object:
+        a = np.array([ord(s) if isinstance(s, str) and len(s) == 1 else s[0] if isinstance(s, bytes) and len(s) == 1 else 0
+                      for s in a.tolist()], dtype=np.uint8)
+    a = np.ascontiguousarray(a, dtype=np.uint8).reshape(-1)
+    if len(a) != n_rows or not np.isin(a, (ord('+'), ord('-'))).all():
+        raise ValueError("sense must hold '+' or '-' for every row")
+    return a if n_rows else np.zeros(1, np.uint8)
+
+
+def device_read_coverage(pos, off, cig, pair_id, n_ids, ann, paired, device=None, sense=None, strand=None):
     """
     One dn_read_coverage call on packed reads and an Annotation: (counts int64[n_genes], overlap span vectors int64 with
     their pad slots, CSR indices int32, CSR values int64, number of reads that reached the isolated stage, device ms).
+    With `sense` (uint8 per row) and `strand` ('+' / '-') it is dn_read_coverage_strand: the position pre-filter keeps
+    only the rows of that sense.
     """
+    if (sense is None) != (strand is None):
+        raise ValueError('sense and strand go together')
     lib = _lib.load()
     i32, i64, u8 = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint8
     n_genes = len(ann.genes)
@@ -202,17 +257,22 @@ def device_read_coverage(pos, off, cig, pair_id, n_ids, ann, paired, device=None
     nnz, n_iso_reads, ms = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_double(0.0)
     dev = int(os.environ.get('LOCAL_RANK', 0)) if device is None else int(device)
     n_groups = len(ann.group_iv)
-    rc = lib.dn_read_coverage(dev, 1 if paired else 0, len(pos), _ptr(pos, i64), _ptr(off, i64), _ptr(cig, u8),
-                              _ptr(pair_id, i32), int(n_ids), ann.chrom_len, ann.keep_lo, ann.keep_hi,
-                              len(ann.exon_iv), _ptr(ann.exon_iv, i64),
-                              n_groups, _ptr(ann.group_iv, i64), _ptr(ann.group_gene_off, i32),
-                              _ptr(ann.ol_gene, i32), _ptr(ann.ol_gs0, i64), _ptr(ann.ol_cov_off, i64),
-                              _ptr(ann.ol_exon_off, i32), _ptr(ann.ol_exon, i64),
-                              len(ann.iso_iv), _ptr(ann.iso_iv, i64), _ptr(ann.iso_gene, i32),
-                              len(ann.iso_union), _ptr(ann.iso_union, i64),
-                              n_genes, _ptr(counts, i64), _ptr(ol_cov, i64), cap, ctypes.byref(nnz),
-                              _ptr(csr_idx, i32), _ptr(csr_val, i64), ctypes.byref(n_iso_reads), ctypes.byref(ms))
-    check_coverage_call(rc, 'dn_read_coverage')
+    rows = (dev, 1 if paired else 0, len(pos), _ptr(pos, i64), _ptr(off, i64), _ptr(cig, u8), _ptr(pair_id, i32), int(n_ids))
+    rest = (ann.chrom_len, ann.keep_lo, ann.keep_hi,
+            len(ann.exon_iv), _ptr(ann.exon_iv, i64),
+            n_groups, _ptr(ann.group_iv, i64), _ptr(ann.group_gene_off, i32),
+            _ptr(ann.ol_gene, i32), _ptr(ann.ol_gs0, i64), _ptr(ann.ol_cov_off, i64),
+            _ptr(ann.ol_exon_off, i32), _ptr(ann.ol_exon, i64),
+            len(ann.iso_iv), _ptr(ann.iso_iv, i64), _ptr(ann.iso_gene, i32),
+            len(ann.iso_union), _ptr(ann.iso_union, i64),
+            n_genes, _ptr(counts, i64), _ptr(ol_cov, i64), cap, ctypes.byref(nnz),
+            _ptr(csr_idx, i32), _ptr(csr_val, i64), ctypes.byref(n_iso_reads), ctypes.byref(ms))
+    if strand is None:
+        check_coverage_call(lib.dn_read_coverage(*(rows + rest)), 'dn_read_coverage')
+    else:
+        sense = pack_sense(sense, len(pos))
+        sel = (_ptr(sense, u8), check_strand(strand))
+        check_coverage_call(lib.dn_read_coverage_strand(*(rows + sel + rest)), 'dn_read_coverage_strand')
     k = int(nnz.value)
     return counts[:n_genes], ol_cov, csr_idx[:k].copy(), csr_val[:k].copy(), int(n_iso_reads.value), float(ms.value)
 
@@ -238,20 +298,23 @@ def device_cigar_bounds(cigars, starts, max_seg=16, device=None):
 
 
 def chromosome_coverage_read_counts_df(reads_df, chrom_len, gene_overlap_dat, chrom_gene_df, chrom_exon_df, paired,
-                                       device=None):
+                                       device=None, sense=None, strand=None):
     """
     Coverage and read counts of one sample's reads on one chromosome, on the GPU: the computation of the reference's
     chromosome_coverage_read_counts (reads.py:389-805) without the file I/O.
 
     :param reads_df: the reads in the order they are taken: `pos` (0-based), `cigar`, and `qname_unpaired` when paired
     (pairs are consecutive rows, after the position pre-filter and the rule that a pair id occurs exactly twice).
+    :param sense, strand: strand-specific counting (both or neither): `sense` holds '+' or '-' for every row of reads_df
+    and `strand` is the one counted -- the position pre-filter also drops the rows of the other sense.  The annotation
+    given is that strand's own.
     :return: (scipy.sparse.csr_matrix 1 x chrom_len of int64 -- the isolated genes' chromosome coverage -- or None when no
     read reached the isolated stage; {overlap gene: int64 coverage over its exon positions} in gene_overlap_dat order;
     {gene: read count} in chrom_gene_df order)
     """
     ann = Annotation(chrom_len, gene_overlap_dat, chrom_gene_df, chrom_exon_df)
     pos, off, cig, pair_id, n_ids = pack_reads(reads_df, paired)
-    counts, ol_cov, idx, val, n_iso_reads, _ = device_read_coverage(pos, off, cig, pair_id, n_ids, ann, paired, device)
+    counts, ol_cov, idx, val, n_iso_reads, _ = device_read_coverage(pos, off, cig, pair_id, n_ids, ann, paired, device, sense, strand)
     return coverage_outputs(ann, counts, ol_cov, idx, val, n_iso_reads)
 
 
@@ -293,12 +356,16 @@ def reads_frame(rows, paired):
 class BamReadsProcessor(object):
     index_extensions = ('.bai',)                 # what the backend that opens the file can read
 
-    def __init__(self, bam_file, index_file, chroms=None, n_jobs=1, output_dir=None, unique_alignment=True, verbose=True):
+    def __init__(self, bam_file, index_file, chroms=None, n_jobs=1, output_dir=None, unique_alignment=True, verbose=True,
+                 stranded='no'):
         """
         Coverage and read counts of one alignment file (.bam), as the reference's BamReadsProcessor (reads.py:97-136).
         Needs pysam to open the file (ImportError without it).  n_jobs is kept for the signature: chromosomes run one
-        after another, each as one device call.
+        after another, each as one device call.  This reader does not count by strand: any `stranded` but 'no' is a
+        ValueError (bam.NativeBamReadsProcessor has the option).
         """
+        if check_stranded(stranded) != 'no':
+            raise ValueError('strand-specific counting (stranded={0!r}) needs bam.NativeBamReadsProcessor'.format(stranded))
         self.filename = bam_file
         if not output_dir:
             output_dir = os.path.join(os.path.dirname(self.filename), 'tmp')

@@ -408,6 +408,64 @@ int  dn_bam_pair_host(int64_t n, const int64_t *name_beg, const int32_t *key_len
 int  dn_bam_cigar_bounds(int device, int64_t n, const int64_t *pos, const int64_t *op_off, const uint32_t *ops,
                          int32_t max_seg, int32_t *nseg, int64_t *bounds, int64_t *end_pos);
 
+/* Strand-specific counting -------------------------------------------------------------------------------------------
+ * For stranded libraries (Illumina TruSeq Stranded / dUTP and the like), where a read's orientation tells the strand its
+ * fragment came from.  The reference has no such mode; the rule is this library's, and it is stated so that the unstranded
+ * path above, which is held to the reference, is its oracle.  `stranded` is 'no' (0, the default: everything above, as it
+ * is), 'forward' (1) or 'reverse' (2).
+ * Sense of a row (dn::row_sense, csrc/dn_bam_record.hpp; a function of one record):
+ *   - a row is a last mate when FLAG 0x1 and 0x80 are both set; in a store paired by the name rule also when the last
+ *     byte of its name is '2'.  Every other row counts as a first mate or a single read;
+ *   - sense is '-' when FLAG 0x10 is set, else '+'; it is flipped for a last mate, and once more when stranded is
+ *     'reverse' (dUTP: htseq-count -s reverse, featureCounts -s 2; 'forward' is -s yes / -s 1).
+ * Strand of a gene: '+' or '-' when every exon row of the gene says so in field 7 of the annotation; a gene with '.', '?'
+ * or both strands among its rows is unstranded and is left out of a stranded run.
+ * A stranded chromosome is two chromosomes.  For each strand s, '+' then '-': the genes of strand s and their exons, their
+ * own overlap structure (overlap groups and isolated genes among the genes of that strand only), their own keep_lo,
+ * keep_hi, exon union, groups and isolated spans, and the rows whose sense is s, handed to the coverage stages above
+ * unchanged: the position pre-filter additionally asks for sense == s.  A strand without genes is skipped.
+ * Paired files: a stranded run pairs on the device, equal keys in file order (dn_bam_rows_pair).  The strand test is part
+ * of the position pre-filter and is applied per row, so a pair whose two mates disagree about the fragment's sense leaves
+ * one row on each strand, fails the "exactly two rows" rule in both passes and contributes nothing.
+ * Guarantee: a stranded run over annotation A and file B gives, gene for gene -- read counts, overlap coverage vectors and
+ * chromosome coverage -- what the unstranded code gives on (A+, B+) and on (A-, B-), where As is the exon lines of the
+ * genes on strand s and Bs the records of sense s, in file order.
+ *   dn_read_coverage_strand      dn_read_coverage with sense[r] ('+' or '-') of every row and the strand counted ('+' or '-').
+ *   dn_read_sense_host           host only: dn::row_sense of n rows with these FLAGs and last name bytes (0: empty name);
+ *                                by_name != 0: the rows of a store paired by the name rule; stranded 1 or 2.
+ *   dn_bam_rows_set_stranded     make an empty store keep the sense of its rows under protocol `stranded` (1 or 2; 0 ends
+ *                                it).  A store with rows is DN_E_STATE.  The sense is computed where the window is decoded,
+ *                                which also covers a store paired by the name rule, which does not keep FLAG.
+ *   dn_bam_rows_fetch_sense      the sense of every row of a stranded store (any other store: DN_E_INVALID).
+ *   dn_bam_rows_coverage_strand  dn_bam_rows_coverage on the rows of one sense of a stranded store.  One store, and one
+ *                                dn_bam_rows_pair, serve the calls of both strands. */
+int  dn_read_coverage_strand(int device, int32_t paired, int64_t n_rows, const int64_t *pos, const int64_t *cigar_off,
+                             const uint8_t *cigar, const int32_t *pair_id, int64_t n_pair_ids, const uint8_t *sense, int32_t strand,
+                             int64_t chrom_len, int64_t keep_lo, int64_t keep_hi,
+                             int64_t n_exon, const int64_t *exon_iv,
+                             int64_t n_groups, const int64_t *group_iv, const int32_t *group_gene_off,
+                             const int32_t *ol_gene, const int64_t *ol_gene_start0, const int64_t *ol_cov_off,
+                             const int32_t *ol_exon_off, const int64_t *ol_exon_bounds,
+                             int64_t n_iso, const int64_t *iso_iv, const int32_t *iso_gene,
+                             int64_t n_iso_union, const int64_t *iso_union,
+                             int64_t n_genes, int64_t *counts, int64_t *ol_cov,
+                             int64_t csr_cap, int64_t *nnz, int32_t *csr_idx, int64_t *csr_val,
+                             int64_t *n_isolated_reads, double *device_ms);
+int  dn_read_sense_host(int64_t n, const uint16_t *flag, const uint8_t *name_last, int32_t by_name, int32_t stranded, uint8_t *sense);
+int  dn_bam_rows_set_stranded(dn_bam_rows h, int32_t stranded);
+int  dn_bam_rows_fetch_sense(dn_bam_rows h, uint8_t *sense);
+int  dn_bam_rows_coverage_strand(dn_bam_rows h, int32_t strand, const int32_t *order, const int32_t *pair_id, int64_t n_pair_ids,
+                                 int64_t chrom_len, int64_t keep_lo, int64_t keep_hi,
+                                 int64_t n_exon, const int64_t *exon_iv,
+                                 int64_t n_groups, const int64_t *group_iv, const int32_t *group_gene_off,
+                                 const int32_t *ol_gene, const int64_t *ol_gene_start0, const int64_t *ol_cov_off,
+                                 const int32_t *ol_exon_off, const int64_t *ol_exon_bounds,
+                                 int64_t n_iso, const int64_t *iso_iv, const int32_t *iso_gene,
+                                 int64_t n_iso_union, const int64_t *iso_union,
+                                 int64_t n_genes, int64_t *counts, int64_t *ol_cov,
+                                 int64_t csr_cap, int64_t *nnz, int32_t *csr_idx, int64_t *csr_val,
+                                 int64_t *n_isolated_reads, double *device_ms);
+
 /* BGZF inflate on the device (csrc/dn_inflate.hip) ----------------------------------------------------------------------
  * A raw-DEFLATE (RFC 1951) decoder of the library's own: one BGZF block per wavefront, no zlib.  Block b's payload (the
  * bytes between its gzip header and its CRC32 / ISIZE trailer) is comp[pay_off[b] .. pay_off[b] + pay_len[b]) and must
@@ -688,10 +746,18 @@ int  dn_bam_sort_deflate(dn_bam_sort h, int64_t n_blocks, const int64_t *beg, co
 #define DN_GTF_E_FIELDS   1   /* fewer than nine tab-separated fields                                                   */
 #define DN_GTF_E_GENE     2   /* an exon line without a usable gene_name / gene_id                                      */
 #define DN_GTF_E_INTEGER  3   /* an exon line whose start or end is not a decimal integer                               */
+#define DN_GTF_E_STRAND   4   /* dn_gtf_scan_strand only: an exon line whose seventh field is not one of + - . ?         */
 int  dn_gtf_scan(int device, const uint8_t *buf, int64_t n_bytes, int64_t row_cap, int64_t *n_lines, int64_t *n_rows,
                  int64_t *line, int64_t *chr_beg, int32_t *chr_len, uint64_t *chr_hash, int64_t *start, int64_t *end,
                  int64_t *gene_beg, int32_t *gene_len, uint64_t *gene_hash, int64_t *err_line, int32_t *err_kind,
                  double *copy_ms, double *device_ms);
+/* The same with the strand column (strand-specific counting, above): strand[r] is field seven of the exon line of row r, one
+ * of '+', '-', '.', '?', read from the line itself while the window is resident.  A kept line whose seventh field is anything
+ * else is DN_GTF_E_STRAND, under the same first-error rule.  dn_gtf_scan checks nothing about field seven. */
+int  dn_gtf_scan_strand(int device, const uint8_t *buf, int64_t n_bytes, int64_t row_cap, int64_t *n_lines, int64_t *n_rows,
+                        int64_t *line, int64_t *chr_beg, int32_t *chr_len, uint64_t *chr_hash, int64_t *start, int64_t *end,
+                        int64_t *gene_beg, int32_t *gene_len, uint64_t *gene_hash, uint8_t *strand, int64_t *err_line,
+                        int32_t *err_kind, double *copy_ms, double *device_ms);
 const char *dn_gtf_last_error(void);               /* = dn_last_error() */
 
 /* SAM text to BAM records (csrc/dn_sam.hip; degnorm_amd.bam.sam_records, sam_to_bam) -----------------------------------------
@@ -825,6 +891,7 @@ int  dn_sam_encode_host(const uint8_t *text, int64_t n_bytes, int32_t n_ref, con
 #define DN_GFF3_E_INTEGER  3   /* an exon line whose start or end is not a decimal integer                               */
 #define DN_GFF3_E_PARENT   4   /* an exon line whose chain of parents names an ID that no line has                       */
 #define DN_GFF3_E_DEPTH    5   /* an exon line whose chain of parents takes more than 8 lookups                          */
+#define DN_GFF3_E_STRAND   6   /* the _strand entries only: an exon line whose seventh field is not one of + - . ?       */
 typedef struct dn_gff3_ *dn_gff3;
 int  dn_gff3_open(int device, int64_t total_bytes, int32_t hash_bits, dn_gff3 *out);
 int  dn_gff3_window(dn_gff3 h, const uint8_t *bytes, int64_t n_bytes, int64_t row_cap, int64_t *n_lines, int64_t *n_rows,
@@ -839,6 +906,17 @@ int  dn_gff3_scan_host(const uint8_t *data, int64_t n_bytes, int32_t hash_bits, 
                        int64_t *line, int64_t *chr_beg, int32_t *chr_len, uint64_t *chr_hash, int64_t *start, int64_t *end,
                        int64_t *gene_beg, int32_t *gene_len, uint64_t *gene_hash, int64_t *n_nodes, int64_t *n_walked, int64_t *err_line,
                        int32_t *err_kind);
+/* The same two with the strand column (strand-specific counting, above): strand[r] is field seven of the exon line of row r
+ * -- of the exon line itself, not of its gene's line -- one of '+', '-', '.', '?'.  An exon line above ##FASTA whose seventh
+ * field is anything else is DN_GFF3_E_STRAND, an error of the line itself.  The entries without it check nothing about it. */
+int  dn_gff3_window_strand(dn_gff3 h, const uint8_t *bytes, int64_t n_bytes, int64_t row_cap, int64_t *n_lines, int64_t *n_rows,
+                           int64_t *line, int64_t *chr_beg, int32_t *chr_len, uint64_t *chr_hash, int64_t *start, int64_t *end,
+                           int64_t *gene_beg, int32_t *gene_len, uint64_t *gene_hash, uint8_t *pending, uint8_t *strand,
+                           int64_t *fasta_line, int64_t *err_line, int32_t *err_kind, double *copy_ms, double *device_ms);
+int  dn_gff3_scan_host_strand(const uint8_t *data, int64_t n_bytes, int32_t hash_bits, int64_t row_cap, int64_t *n_lines,
+                              int64_t *n_rows, int64_t *line, int64_t *chr_beg, int32_t *chr_len, uint64_t *chr_hash, int64_t *start,
+                              int64_t *end, int64_t *gene_beg, int32_t *gene_len, uint64_t *gene_hash, uint8_t *strand,
+                              int64_t *n_nodes, int64_t *n_walked, int64_t *err_line, int32_t *err_kind);
 
 /* Coverage matrices to text (csrc/dn_text.hip, csrc/dn_text.hpp; degnorm_amd.data_access.get_coverage_data, cov_text) ----------
  * What `DataFrame(cov.T).to_csv(file, index=None, sep=' ', float_format='%.5f')` writes below its header line, for a batch of

@@ -23,7 +23,7 @@ writes them, and the reader pairs them by FLAG):
 
     python tools/bam_speed.py [--reads 2000000] [--jobs 4] [--reps 3] [--dir DIR] [--inflate host|device] [--level 1]
                                [--frame host|device] [--segment-bytes N] [--cases se,pe] [--pair host|device]
-                               [--pairing name|flag]
+                               [--pairing name|flag] [--stranded no|forward|reverse]
 
 --level is the deflate level of the written files (the fixture writer's level 1 on random sequence bytes is nearly
 literal-only; real files are level 6 and full of matches).  Files found in --dir from an earlier run with the same
@@ -53,13 +53,13 @@ from degnorm_amd import reads as dr                  # noqa: E402
 
 
 def _best(path, chrom, ov, gene_df, exon_df, out, jobs, reps, inflate, frame='host', segment_bytes=None, verify=False, pair='host',
-          pairing='name'):
+          pairing='name', stranded='no'):
     best, rows = None, []
     shutil.rmtree(out, ignore_errors=True)            # of an earlier run in the same --dir: files that exist are not written again
     for k in range(reps + 1):                        # the first run loads the library and warms the device up
         proc = bam.NativeBamReadsProcessor(path, path + '.bai', output_dir=os.path.join(out, str(k)), n_jobs=jobs, verbose=False,
                                            inflate=inflate, frame=frame, frame_segment_bytes=segment_bytes, verify=verify, pair=pair,
-                                           pairing=pairing)
+                                           pairing=pairing, stranded=stranded)
         if k == 0 and path.rsplit(os.sep, 1)[-1].startswith('pe'):
             assert proc.paired, 'the paired file was taken for single-end'
         os.makedirs(proc.save_dir, exist_ok=True)
@@ -101,6 +101,9 @@ def main():
     ap.add_argument('--pairing', choices=['name', 'flag'], default='name',
                     help='flag: the paired case is written with equal names, FLAG bits and PNEXT, and paired by FLAG (on the device)')
     ap.add_argument('--cases', default='se,pe', help='se, pe or se,pe')
+    ap.add_argument('--stranded', choices=['no', 'forward', 'reverse'], default='no',
+                    help='count by strand: the genes alternate strands, the files carry strand bits (mates of a pair agree), and '
+                         'coverage_ms / coverage_device_ms are those of the two per-strand calls')
     ap.add_argument('--verify', action='store_true', help='check every BGZF block against the CRC32 of its trailer')
     a = ap.parse_args()
     reads, chrom_len, ov, gene_df, exon_df = rf.scale_case(n_reads=a.reads)
@@ -114,9 +117,17 @@ def main():
             mate[mate >= n] = n - 1                  # an odd count: the last read names itself, and is its key's only row
             pe = se.assign(qname=[str(i // 2) for i in range(n)], next_ref=0, flag=0x1 | np.where(np.arange(n) % 2 == 0, 0x40, 0x80) | strand,
                            next_pos=se.pos.values[mate], mapq=60)
+        if a.stranded != 'no':
+            # a strand per gene, and strand bits in the files: a random 0x10 per fragment, which the last mate of a pair
+            # carries inverted, so that both mates say one sense
+            gene_df = gene_df.assign(strand=np.where(np.arange(len(gene_df)) % 2 == 0, '+', '-'))
+            rev = np.random.default_rng(2).choice([0x0, 0x10], len(se))
+            se = se.assign(flag=rev)
+            pe = pe.assign(flag=(pe.flag.values & ~0x30 if 'flag' in pe else 0) | (rev[(np.arange(len(se)) // 2) * 2] ^ np.where(np.arange(len(se)) % 2 == 1, 0x10, 0x0)))
         t0 = time.perf_counter()
         cases = [c for c in ('se', 'pe') if c in a.cases.split(',')]
-        files = {name: os.path.join(work, '{0}_{1}_l{2}.bam'.format(name + ('_flag' if name == 'pe' and a.pairing == 'flag' else ''), a.reads, a.level))
+        files = {name: os.path.join(work, '{0}_{1}_l{2}.bam'.format(name + ('_flag' if name == 'pe' and a.pairing == 'flag' else '') +
+                                                                     ('_strand' if a.stranded != 'no' else ''), a.reads, a.level))
                  for name in cases}
         for name, df in (('se', se), ('pe', pe)):
             if name in files and not (os.path.isfile(files[name]) and os.path.isfile(files[name] + '.bai')):
@@ -129,7 +140,7 @@ def main():
             dr.chromosome_coverage_read_counts_df(reads, chrom_len, ov, gene_df, exon_df, False)
             dt = time.perf_counter() - t0
             in_mem = dt if in_mem is None else min(in_mem, dt)
-        out = {'tool': 'bam_speed', 'reads': a.reads, 'jobs': a.jobs, 'inflate': a.inflate, 'frame': a.frame, 'pair': a.pair, 'pairing': a.pairing, 'level': a.level,
+        out = {'tool': 'bam_speed', 'reads': a.reads, 'jobs': a.jobs, 'inflate': a.inflate, 'frame': a.frame, 'pair': a.pair, 'pairing': a.pairing, 'stranded': a.stranded, 'level': a.level,
                'bam_mb': round(os.path.getsize(files[cases[0]]) / 2 ** 20, 1), 'inflated_mb': round(inflated[cases[0]] / 2 ** 20, 1),
                'write_s': round(write_s, 1)}
         if a.verify:
@@ -143,7 +154,7 @@ def main():
             out['default_counts_as_reads'], out['pairs_counted'] = int(sum(as_reads.values())), int(sum(as_pairs.values()))
         for name in cases:
             row = _best(files[name], 'chrS', ov, gene_df, exon_df, os.path.join(work, 'out_{0}_{1}_{2}_{3}'.format(name, a.inflate, a.frame, a.pair)),
-                        a.jobs, a.reps, a.inflate, a.frame, a.segment_bytes, a.verify, a.pair, a.pairing if name == 'pe' else 'name')
+                        a.jobs, a.reps, a.inflate, a.frame, a.segment_bytes, a.verify, a.pair, a.pairing if name == 'pe' else 'name', a.stranded)
             if row['inflate_device_ms'] > 0:
                 row['inflate_gbps'] = round(inflated[name] / (row['inflate_device_ms'] * 1e-3) / 1e9, 2)
             row['reads_per_s'] = round(a.reads / (row['e2e_ms'] * 1e-3))
